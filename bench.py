@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — decode throughput of the MI355X hot path on BASELINE.json's metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Workload (config C4 of BASELINE.json): a batch of 256 independent ~4K-triangle .crt blobs
@@ -18,10 +18,13 @@ block), all threads of all GPUs pulling batches from ONE work queue (an atomic c
 Timing: barrier + device sync, then W warm-up steps flow straight into the K timed steps (the pipeline is NOT drained in
 between); the clock runs from the completion of the last warm-up step to the completion of the K-th timed step, a few more
 steps are queued behind so that every context is still busy when the clock stops, then everything drains, barrier + sync.
-So `--steps 20` measures the same steady state as `--steps 480`.  value = K batches / that time (max over ranks).
-With K < 100 the K-step region is timed R = ~2000/K times back to back (no drain in between) and the MEDIAN region is reported, every
-region's time in `timed_regions`: completions of sixteen batches in flight come in bursts, and one region of 20 steps lands
-anywhere within -15 / +30 % of the long-run rate (tools/pool_probe.py).
+So `--steps 20` measures the same steady state as `--steps 480`.  value = K batches / that time (max over ranks), ms_per_step = that time / K.
+Exactly K steps are timed: completions of sixteen batches in flight come in bursts, and one region of 20 steps lands anywhere within
+-15 / +30 % of the long-run rate (tools/pool_probe.py) - a stable number wants K in the thousands.
+--dump-outputs DIR: after the timed steps, what the last step of the first pool context decoded (the timed path's outputs for the
+256 blobs of GPU 0's batch, concatenated blob after blob) is written to DIR/<name>.npy in float32 - position, normal, uv, color, index
+(per-blob vertex indices) and the per-blob vertex / triangle counts; ~39 MB.  The inputs are seeded: the same arguments give the same
+arrays on any build that decodes correctly.
 `python bench.py --gpus N` without a launcher runs the N GPUs from this one process (one pool, shared queue, N x K steps);
 under torch.distributed.run every rank runs its own one-GPU pool on its shard (seeds 256*rank ..) and RCCL carries only the
 barrier and the max-over-ranks of the time.
@@ -36,9 +39,6 @@ import time
 
 import numpy as np
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "20")   # one HW queue per HIP stream of the pipelined contexts (the ROCm default of 4 makes streams
-                                                   # share queues, and a shared queue serialises its kernels).  Round 4: 20 contexts on 20 queues
-                                                   # (5 x 4; 4 x 5 and 11 x 2 on 22 are the same) are 3 % faster than 16 on 16; 24 is slower again
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
@@ -465,6 +465,24 @@ def encoder_stage(ctx, ca):
     return out
 
 
+def dump_outputs(dirname, ca, pool, blobs, dts):
+    """--dump-outputs: what the timed path left in the first context that decoded item 0 (GPU 0's batch `blobs`) - the outputs of that
+    context's last step - as float32 .npy files, the blobs' arrays concatenated in batch order; `nvert` / `nface` give each blob's rows"""
+    lane = next(l for l in range(pool.lanes) if pool.lane_item(l)[0] == 0)
+    cols = {k: [] for k in dts}
+    nvert, nface = [], []
+    for i, blob in enumerate(blobs):
+        info = ca.probe(blob)
+        nvert.append(info.nvert); nface.append(info.nface)
+        for k, (dt, w) in dts.items():
+            cols[k].append(pool.lane_read(lane, i, k, dt, (info.nface if k == "index" else info.nvert) * w).reshape(-1, w))
+    os.makedirs(dirname, exist_ok=True)
+    for k, parts in cols.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.concatenate(parts).astype(np.float32))
+    np.save(os.path.join(dirname, "nvert.npy"), np.asarray(nvert, dtype=np.float32))
+    np.save(os.path.join(dirname, "nface.npy"), np.asarray(nface, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -477,6 +495,7 @@ def main():
     ap.add_argument("--all-legs", action="store_true", help="N > 1: also run the single-GPU characterisation legs (CPU baseline, Tunstall at roofline scale, single objects, irregular batches) that belong to the N = 1 line")
     ap.add_argument("--no-tunstall-scaled", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the single-object C2 / C3 decodes (tools/prof_run.sh: keeps the rocprofv3 kernel averages about the C4 batch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path decoded in its last step to DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -657,10 +676,10 @@ def main():
     while time.perf_counter() - t_pre < float(os.environ.get("BENCH_PREWARM_SECONDS", "0.3")):
         pool.run(host_items, steps=16 * pool.lanes * nloc, warmup=0, arenas=None)
     barrier()
-    # A K-step region is timed R times back to back (no drain in between) and the MEDIAN region is the one reported: with sixteen batches
-    # in flight completions come in bursts, and a single region of K = 20 steps (1.25 rounds of the contexts) lands anywhere within
-    # -15 / +30 % of the long-run rate (tools/pool_probe.py); every region's time is in `timed_regions`.  K >= 100: five regions (one 480-step region that meets a multi-ms stall reads 25 % low).
-    R = 5 if args.steps >= 100 else max(5, -(-2000 // args.steps) | 1)     # (an odd number of regions, ~2 000 steps in all = 0.18 s: round 3's five regions' median still moved +-8 % run to run, round 4's 25 +-4 % - 11.0 .. 12.1 Gtri/s on five boxes where the 480-step form read 11.9 .. 12.2)
+    # ONE region of exactly K timed steps: --steps is the number of steps timed, and ms_per_step is that region's time / K.  With sixteen
+    # batches in flight completions come in bursts, and a region of K = 20 steps (1.25 rounds of the contexts) lands anywhere within
+    # -15 / +30 % of the long-run rate (tools/pool_probe.py): a stable number wants a long region, i.e. a large K.
+    R = 1
     # (the W warm-up steps the caller asked for, plus eight rounds of the pool's contexts (round 6: two rounds left the first regions at 0.10-0.21 ms on the driver's box): with twenty batches in flight a pipeline that was empty
     # when the run began is not full after five steps, and the first regions would time its filling)
     ramp = 8 * pool.lanes
@@ -708,9 +727,11 @@ def main():
             for k in ("position", "normal", "color", "uv", "index"):
                 d = hashlib.sha256(np.ascontiguousarray(got[k]).tobytes()).hexdigest()
                 assert d == z["%s_sha256_%02d" % (k, i)].tobytes().decode(), ("bit-exact check failed (golden)", i, k)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, ca, pool, items[0], dts)
 
     # beside `value`: the same pipelined steps with the compressed inputs ALREADY RESIDENT in HBM (what rounds 1-3 quoted as `value`): no PCIe
-    # inside the step.  Same R regions of K steps, median reported.
+    # inside the step.  Same region of K steps.
     # (the side legs run 600 steps whatever K is: a 120-step region of sixteen batches in flight lands anywhere within -40 / +5 % of the
     # long-run rate - round 3, profiles/EXPERIMENTS.md - and 600 steps of these take 0.1-0.15 s)
     fh_steps = 600 * nloc
@@ -947,8 +968,7 @@ def main():
             "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
             "timed_regions": {"count": R, "ms_per_step": [round(e / args.steps * 1e3, 4) for e in regions],
                               "mean_ms_per_step": round(elapsed_mean / args.steps * 1e3, 4), "median_over_mean": round(elapsed / elapsed_mean, 4),
-                              "note": "consecutive regions of exactly K steps each, pipeline full throughout; `value` and `ms_per_step` are the median region's; "
-                                      "mean_ms_per_step is all R regions together (a stall anywhere shows there)"},
+                              "note": "one region of exactly K timed steps, pipeline full throughout; `value` and `ms_per_step` are that region's"},
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/i32 integer + f32 normals",
             "data": "synthetic: 256 distinct bumpy-sphere meshes per GPU (seeds 256*g ..), encoded by the repo's byte-identical .crt writer",
             "config": {"workload": "C4: 256 x (2112 verts / 4096 tris), pos14+uv12+normal10(BORDER)+rgba, per GPU; C5 when n_gpus=8",
@@ -956,7 +976,7 @@ def main():
                        "timed_region": "SURVEY 8d primary: K x [H2D of the batch's .crt bytes from ONE pinned host buffer + plan(host walk)+bind+kernels+sync] per GPU, "
                                        "outputs left in HBM; clock from the "
                                        "completion of the last of W warm-up steps to the completion of the K-th timed step, pipeline full at both ends "
-                                       "(barrier + device sync before the warm-up and after the drain); K < 100: ~2000/K such regions back to back, the median one reported (timed_regions); "
+                                       "(barrier + device sync before the warm-up and after the drain); "
                                        "the rate with the compressed inputs already resident in HBM (rounds 1-3's `value`) is `resident_inputs`",
                        "h2d_bytes_per_step": int(stats0.arena_bytes), "pcie_GBps": round(stats0.arena_bytes / (ms_step * 1e-3) / 1e9, 2),
                        "pipeline_depth": depth, "host_threads": nthreads, "host_threads_note": threads_note or None, "launch": mode,

@@ -2,7 +2,6 @@
 import os, sys, time, ctypes as C, collections
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import numpy as np, torch
 import corto_amd as ca
 import bench

@@ -2,7 +2,6 @@
 """Host RSS against steps: the pool with resident inputs, from one pinned buffer, and a bare loop of one batch object decoded again and again on one context.
    python tools/leak_probe.py [steps per slice] [slices]"""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "20")
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import bench
 import corto_amd as ca

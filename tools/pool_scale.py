@@ -2,7 +2,6 @@
 """Is the pipelined step bound by per-step overheads (launches, host) or by GPU work?  Same pool, batches of 64 .. 1024 blobs."""
 import os, sys
 import numpy as np
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import bench
 import corto_amd as ca

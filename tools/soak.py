@@ -2,7 +2,6 @@
 """A long run of the primary region (pinned host -> HBM, 5 x 4 contexts): ms a step per ten-second slice, device memory and host RSS before / after, failed blobs,
 and the outputs of every context's last step against the oracle.   python tools/soak.py [seconds]"""
 import os, sys, time, resource
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "20")
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np, torch
 import bench
