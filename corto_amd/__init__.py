@@ -152,6 +152,9 @@ def lib():
         L.crthip_encode_values.restype = C.c_int64
         L.crthip_encode_values.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.crthip_tunstall_encode_blocks.restype = C.c_int64
+        L.crthip_encode_batch.restype = C.c_int64
+        L.crthip_encode_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.crthip_tunstall_encode_blocks.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.crthip_tunstall_decode_blocks.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.POINTER(KernelTimes)]
@@ -229,11 +232,9 @@ def arena_layout(lens: Sequence[int]):
 DIFF, ESTIMATED, BORDER = 0, 1, 2
 
 
-def encode(mesh, position_bits=14, position_q=0.0, normal_bits=10, normal_prediction=BORDER, color_bits=(6, 7, 6, 5),
-           uv_bits=12, radius_q=1.0, entropy=1, exif=None, with_normal=True, with_color=True, with_uv=True, ctx=None) -> np.ndarray:
-    """.crt blob of a corto_amd.synth.Mesh (byte-identical to upstream crt::Encoder, see csrc/encoder.cpp).  Host only by
-    default; with ctx=Context the value coding and the entropy coder run on the device (crthip_encode_gpu) - same bytes.
-    Same keyword meaning as upstream's CLI: -v position_bits, -n normal_bits, -N prediction, -u uv_bits (src/main.cpp:93-216)."""
+def _mesh_desc(mesh, position_bits=14, position_q=0.0, normal_bits=10, normal_prediction=BORDER, color_bits=(6, 7, 6, 5),
+               uv_bits=12, radius_q=1.0, entropy=1, exif=None, with_normal=True, with_color=True, with_uv=True):
+    """crthip_mesh of a corto_amd.synth.Mesh, and the Python objects it points into (keep them alive while it is used)."""
     m = MeshDesc()
     m.nvert, m.nface = mesh.nvert, mesh.nface
     keep = []
@@ -258,11 +259,23 @@ def encode(mesh, position_bits=14, position_q=0.0, normal_bits=10, normal_predic
         if props:
             cnt = np.array([len(d) for d in props], dtype=np.uint32); keep.append(cnt)
             gflat = b"".join(k.encode() + b"\0" + v.encode() + b"\0" for d in props for k, v in d.items())
-            m.group_nprops = cnt.ctypes.data; m.group_props = gflat
+            m.group_nprops = cnt.ctypes.data; m.group_props = gflat; keep.append(gflat)
     m.entropy = entropy
     if exif:
         flat = b"".join(k.encode() + b"\0" + v.encode() + b"\0" for k, v in exif.items())
-        m.exif = flat; m.nexif = len(exif)
+        m.exif = flat; m.nexif = len(exif); keep.append(flat)
+    keep.append(mesh)
+    return m, keep
+
+
+def encode(mesh, position_bits=14, position_q=0.0, normal_bits=10, normal_prediction=BORDER, color_bits=(6, 7, 6, 5),
+           uv_bits=12, radius_q=1.0, entropy=1, exif=None, with_normal=True, with_color=True, with_uv=True, ctx=None) -> np.ndarray:
+    """.crt blob of a corto_amd.synth.Mesh (byte-identical to upstream crt::Encoder, see csrc/encoder.cpp).  Host only by
+    default; with ctx=Context the value coding and the entropy coder run on the device (crthip_encode_gpu) - same bytes.
+    Same keyword meaning as upstream's CLI: -v position_bits, -n normal_bits, -N prediction, -u uv_bits (src/main.cpp:93-216)."""
+    m, keep = _mesh_desc(mesh, position_bits=position_bits, position_q=position_q, normal_bits=normal_bits, normal_prediction=normal_prediction,
+                         color_bits=color_bits, uv_bits=uv_bits, radius_q=radius_q, entropy=entropy, exif=exif, with_normal=with_normal,
+                         with_color=with_color, with_uv=with_uv)
     cap = 64 * (mesh.nvert + mesh.nface) + 65536            # one pass unless the estimate is too small
     for _ in range(2):
         out = np.zeros(cap + 16, dtype=np.uint8)
@@ -278,6 +291,68 @@ def encode(mesh, position_bits=14, position_q=0.0, normal_bits=10, normal_predic
             return out[off:off + int(n)]
         cap = int(n)
     raise CortoError(-9, "encode: size changed between calls")
+
+
+class EncodeBatchStats(C.Structure):
+    _fields_ = [("wall_ms", C.c_float), ("host_topology_ms", C.c_float), ("host_frame_ms", C.c_float),
+                ("clouds_device_sorted", C.c_uint32), ("clouds_host_sorted", C.c_uint32), ("value_streams", C.c_uint32),
+                ("bytes_to_device", C.c_uint64), ("bytes_from_device", C.c_uint64), ("host_check_ms", C.c_float), ("host_stage_ms", C.c_float),
+                ("sync_wait_ms", C.c_float), ("value_coder_ms", C.c_float), ("upload_ms", C.c_float), ("alloc_ms", C.c_float),
+                ("topology_wait_ms", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def encode_batch(meshes, ctx, kw=None, host_threads=0, raise_on_error=True, with_stats=False):
+    """.crt blobs of a batch of corto_amd.synth.Mesh in one crthip_encode_batch: each byte-identical to encode(mesh, **kw).
+    kw: one dict of encode()'s keywords for all meshes, or one per mesh.  Returns the list of uint8 blobs (empty for a mesh
+    that failed); with raise_on_error=False also the per-mesh status codes; with_stats=True also a dict of the call's
+    statistics and per-kernel times."""
+    meshes = list(meshes)
+    n = len(meshes)
+    if kw is None:
+        kws = [{}] * n
+    elif isinstance(kw, dict):
+        kws = [kw] * n
+    else:
+        kws = list(kw)
+        if len(kws) != n:
+            raise ValueError("encode_batch: %d keyword dicts for %d meshes" % (len(kws), n))
+    descs = (MeshDesc * max(n, 1))()
+    keep = []
+    for i, (mesh, k) in enumerate(zip(meshes, kws)):
+        descs[i], kp = _mesh_desc(mesh, **k)
+        keep.append(kp)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    st = EncodeBatchStats()
+    t = KernelTimes()
+    cap = sum(64 * (m.nvert + m.nface) + 65536 for m in meshes)
+    for _ in range(2):
+        out = np.zeros(cap + 16, dtype=np.uint8)
+        r = lib().crthip_encode_batch(ctx.handle, n, descs, host_threads, _np_ptr(out), cap, _np_ptr(offs), None, None,
+                                      _np_ptr(status), C.byref(st), C.byref(t))
+        if r < 0:
+            _check(int(r))
+        if r <= cap:
+            break
+        cap = int(r)
+    else:
+        raise CortoError(-9, "encode_batch: size changed between calls")
+    status = status[:n]
+    if raise_on_error and (status != 0).any():
+        i = int(np.nonzero(status)[0][0])
+        raise CortoError(int(status[i]), "encode_batch: mesh %d: %s" % (i, lib().crthip_strerror(int(status[i])).decode()))
+    blobs = [out[int(offs[i]):int(offs[i + 1])].copy() for i in range(n)]
+    res = [blobs]
+    if not raise_on_error:
+        res.append(status)
+    if with_stats:
+        d = st.as_dict()
+        d["kernel_times"] = t.as_dict()
+        res.append(d)
+    return res[0] if len(res) == 1 else tuple(res)
 
 
 class Context:

@@ -209,5 +209,43 @@ struct PackJob {
 constexpr uint32_t ENC_PACK_MAX_N = 16;                          // components per element the packing tile is sized for
 constexpr uint32_t ENC_STAGE = 4096, ENC_STAGE_PAD = 576;      // bytes staged in LDS per refill; look-ahead a 64-byte window may need (words <= 255 symbols)
 constexpr uint32_t ENC_HIST_CHUNK = 1u << 18;
+// one piece the value coder copies back compacted (k_enc_gather)
+struct CopyJob { const uint8_t *src; uint8_t *dst; uint64_t bytes, dst_off; };
+
+// ---- crthip_encode_batch (k_encode_batch.hip, encode_batch.cpp) ----
+// estimated normals of one mesh (src/normal_attribute.cpp:113-143): faces in ORIGINAL vertex ids, degenerate ones dropped
+struct EstJob {
+	const uint32_t *faces;         // nface x 3
+	const int32_t *coords;         // quantised positions, nvert x 3
+	int32_t *normals;              // quantised octahedral normals, nvert x 2: the estimate is subtracted in place
+	int32_t *boundary;             // BORDER: nvert XORs of neighbour ids (zeroed), else null
+	uint32_t nface, nvert;
+	uint32_t vbase;                // the mesh's first vertex in the batch's numbering (the corner sort's key)
+	uint32_t fbase;                // its first face in the faces region (the corner sort's payload)
+	uint32_t cbase;                // its first corner in the corner arrays
+	int32_t unit;
+	uint32_t pad[2];
+};
+// residuals of one attribute (GenericAttr::deltaEncode, vertex_attribute.h:130-144; NormalAttr::deltaEncode, normal_attribute.cpp:145-176)
+enum : uint32_t { DENC_I32 = 0, DENC_U8 = 1, DENC_NRM_DIFF = 2, DENC_NRM_EST = 3, DENC_NRM_BORDER = 4 };
+struct DeltaEncJob {
+	const void *values;            // quantised: count_in x N int32, or bytes (colour)
+	const uint32_t *quads;         // (t, a, b, c) per encoded vertex
+	void *out;                     // residuals, count x N (BORDER: the boundary vertices' values, compacted)
+	const int32_t *boundary;       // BORDER
+	uint32_t *out_count;           // BORDER: residuals written
+	uint32_t count, N, kind, parallel;
+};
+// Morton order of one point cloud (src/encoder.cpp:238-262)
+struct ZJob {
+	const int32_t *coords;         // quantised positions, n x 3
+	int32_t *mn;                   // 3: min(0, coordinate), by integer atomics
+	uint64_t *keys; uint32_t *vals;   // n records
+	uint32_t *flag;                // out: adjacent equal keys after the sort
+	uint32_t *quads;               // out: the prediction (t, prev, prev, prev)
+	uint32_t n, pad;
+};
+constexpr uint32_t RS_THREADS = 256, RS_ITEMS = 16, RS_TILE = RS_THREADS*RS_ITEMS;   // radix sort: 8-bit digits, a tile of 4 096 records a workgroup
+constexpr uint32_t DENC_BLOCK = 1024;                                                  // encoded vertices a workgroup of k_enc_delta
 
 } // namespace corto_hip

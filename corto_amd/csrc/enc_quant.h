@@ -1,0 +1,41 @@
+// enc_quant.h — the encoder's per-element quantisation recipes, shared by k_enc_quantize (k_encode.hip) and
+// k_enc_quantize_batch / k_enc_est_normal (k_encode_batch.hip).  Upstream's float operations one by one (no FMA: the library is
+// built with -ffp-contract=off; IEEE divide); (int) is x86's cvttss2si: INT_MIN when out of range.
+#pragma once
+#include "kernels_common.h"
+#include "device_plan.h"
+
+namespace corto_hip {
+
+__device__ __forceinline__ void enc_to_octa(float vx, float vy, float vz, int32_t unit, int32_t o[2]) {   // normal_attribute.h:75-85
+	float s = fabsf(vx) + fabsf(vy); s = s + fabsf(vz);
+	float px = vx/s, py = vy/s;
+	if(vz < 0) {
+		const float qx = 1.0f - fabsf(py), qy = 1.0f - fabsf(px);
+		px = qx; py = qy;
+		if(vx < 0) px = -px;
+		if(vy < 0) py = -py;
+	}
+	o[0] = f2i_x86(px*(float)unit); o[1] = f2i_x86(py*(float)unit);
+}
+
+// element i of job J: GENERIC (int)(x/q) (vertex_attribute.h:97-99); NORMAL toOcta; COLOR byte/qc then (g, b - g, r - g, a)
+// (color_attribute.cpp:30-44, point.h:213)
+__device__ __forceinline__ void enc_quantize_one(const QuantJob &J, uint32_t i) {
+	if(J.kind == 0) {
+		const float x = ((const float *)J.in)[i] - 0.0f;
+		((int32_t *)J.out)[i] = f2i_x86(x/J.q);
+	} else if(J.kind == 1) {
+		const float *v = (const float *)J.in + (size_t)i*3;
+		enc_to_octa(v[0], v[1], v[2], J.unit, (int32_t *)J.out + (size_t)i*2);
+	} else {
+		const uint8_t *c = (const uint8_t *)J.in + (size_t)i*J.N;
+		uint8_t y[4] = {0, 0, 0, 0};
+		for(uint32_t k = 0; k < J.N && k < 4; k++) y[k] = (uint8_t)(c[k]/J.qc[k]);
+		const uint8_t ycc[4] = {y[1], (uint8_t)(y[2] - y[1]), (uint8_t)(y[0] - y[1]), y[3]};
+		uint8_t *o = (uint8_t *)J.out + (size_t)i*J.N;
+		for(uint32_t k = 0; k < J.N && k < 4; k++) o[k] = ycc[k];
+	}
+}
+
+} // namespace corto_hip

@@ -37,7 +37,7 @@ struct Events {
 	hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 	~Events() { for(auto &x : e) if(x) (void)hipEventDestroy(x); }
 };
-struct StageTimes { float hist = 0, parse = 0, pack = 0, tables = 0, trie = 0; bool any_hist = false, any_parse = false, any_pack = false, any_tables = false; uint32_t host_table_streams = 0; };
+using StageTimes = EncStageTimes;
 
 #define ENC_TRY(expr) do { hipError_t e_ = (expr); if(e_ != hipSuccess) return ctx_fail(CRTHIP_E_DEVICE, (std::string(#expr ": ") + hipGetErrorString(e_)).c_str()); } while(0)
 
@@ -206,9 +206,11 @@ int tun_encode_device(hipStream_t st, uint32_t n, const uint8_t *const *d_src, c
 	return CRTHIP_OK;
 }
 
-void report(crthip_kernel_times *times, const StageTimes &tm) {
+} // namespace
+
+void corto_hip::enc_report_times(crthip_kernel_times *times, const EncStageTimes &tm) {
 	if(!times) return;
-	uint32_t k = 0;
+	uint32_t k = times->count;
 	if(tm.any_pack) { times->name[k] = "enc_pack"; times->ms[k] = tm.pack; times->launches[k] = 1; k++; }
 	if(tm.any_hist) { times->name[k] = "enc_hist"; times->ms[k] = tm.hist; times->launches[k] = 1; k++; }
 	if(tm.any_tables) { times->name[k] = "enc_tables"; times->ms[k] = tm.tables; times->launches[k] = 1; k++;
@@ -216,8 +218,6 @@ void report(crthip_kernel_times *times, const StageTimes &tm) {
 	if(tm.any_parse) { times->name[k] = "enc_tun_parse"; times->ms[k] = tm.parse; times->launches[k] = 1; k++; }
 	times->count = k;
 }
-
-} // namespace
 
 extern "C" int64_t crthip_tunstall_encode_blocks(crthip_ctx *ctx, uint32_t n, const uint8_t *const *src, const uint32_t *sizes,
                                                  uint8_t *out, size_t cap, uint64_t *block_offset, crthip_kernel_times *times) {
@@ -241,7 +241,7 @@ extern "C" int64_t crthip_tunstall_encode_blocks(crthip_ctx *ctx, uint32_t n, co
 	std::vector<std::vector<uint8_t>> blocks;
 	StageTimes tm;
 	{ const int e = tun_encode_device(st, n, d_src.data(), sizes, blocks, tm); if(e) return e; }
-	report(times, tm);
+	enc_report_times(times, tm);
 	uint64_t w = 0;
 	for(uint32_t i = 0; i < n; i++) {
 		block_offset[i] = w;
@@ -287,35 +287,17 @@ int corto_hip::quantize_device(crthip_ctx *ctx, const std::vector<QuantRequest> 
 	return CRTHIP_OK;
 }
 
-// bit-width logs + bit packing of n value arrays on the device, then the Tunstall coder over the logs (or raw logs for entropy NONE)
-int corto_hip::encode_value_streams(crthip_ctx *ctx, uint32_t entropy, const std::vector<EncValueStream> &in, std::vector<EncValueResult> &res,
-                                    crthip_kernel_times *times) {
+// bit-width logs + bit packing of n DEVICE-resident value arrays, then the Tunstall coder over the logs (or raw logs for entropy NONE).
+// The caller has set the device and quiesced the context.  Words and raw logs come back compacted, in one copy each.
+int corto_hip::encode_value_streams_device(crthip_ctx *ctx, const std::vector<DevValueStream> &in, std::vector<EncValueResult> &res, EncStageTimes &tm) {
 	const uint32_t n = (uint32_t)in.size();
 	res.assign(n, EncValueResult());
-	if(!ctx) return ctx_fail(CRTHIP_E_ARGUMENT, "encode_value_streams: null context");
-	if(entropy != CRTHIP_ENTROPY_NONE && entropy != CRTHIP_ENTROPY_TUNSTALL) return ctx_fail(CRTHIP_E_ENTROPY, nullptr);
-	if(times) memset(times, 0, sizeof(*times));
-	ENC_TRY(hipSetDevice(ctx_device(ctx)));
-	{ const int e = ctx_quiesce(ctx); if(e) return e; }
 	hipStream_t st = ctx_stream(ctx);
-
-	// device image: values (or symbols) | logs | words | word counts | jobs
-	std::vector<uint64_t> v_off(n), l_off(n), w_off(n);
+	// device image: logs | words | word counts | jobs
+	std::vector<uint64_t> l_off(n), w_off(n);
 	std::vector<uint32_t> nlogs(n);                      // log arrays of stream i (0 for a symbol stream)
-	auto value_bytes = [&](const EncValueStream &s) -> uint64_t {
-		return s.kind == CRTHIP_ENC_SYMBOLS ? s.count : (uint64_t)s.count*s.components*(s.kind == CRTHIP_ENC_VALUES_I8 ? 1 : 4);
-	};
 	uint64_t o = 0;
-	for(uint32_t i = 0; i < n; i++) {
-		const EncValueStream &s = in[i];
-		if(s.count && !s.values) return ctx_fail(CRTHIP_E_ARGUMENT, "encode_value_streams: null values");
-		if(s.kind > CRTHIP_ENC_VALUES_I8) return ctx_fail(CRTHIP_E_ARGUMENT, "encode_value_streams: unknown stream kind");
-		if(s.kind != CRTHIP_ENC_SYMBOLS && (s.components == 0 || s.components > ENC_PACK_MAX_N)) return ctx_fail(CRTHIP_E_LIMIT, "encode_value_streams: components out of range");
-		if((uint64_t)s.count*std::max(1u, s.components) > (1u << 26)) return ctx_fail(CRTHIP_E_LIMIT, "encode_value_streams: array too long");
-		v_off[i] = o; o += (value_bytes(s) + 15) & ~15ull;
-		nlogs[i] = s.kind == CRTHIP_ENC_SYMBOLS ? 0u : s.kind == CRTHIP_ENC_ARRAY ? 1u : s.components;
-	}
-	const uint64_t values_bytes = o;
+	for(uint32_t i = 0; i < n; i++) nlogs[i] = in[i].kind == CRTHIP_ENC_SYMBOLS ? 0u : in[i].kind == CRTHIP_ENC_ARRAY ? 1u : in[i].components;
 	for(uint32_t i = 0; i < n; i++) { l_off[i] = o; o += ((uint64_t)in[i].count*nlogs[i] + 15) & ~15ull; }
 	for(uint32_t i = 0; i < n; i++) { w_off[i] = o; o += nlogs[i] ? ((uint64_t)in[i].count*in[i].components*4 + 8 + 15) & ~15ull : 0; }
 	const uint64_t o_nwords = o; o += ((uint64_t)n*4 + 15) & ~15ull;
@@ -326,63 +308,126 @@ int corto_hip::encode_value_streams(crthip_ctx *ctx, uint32_t entropy, const std
 	for(auto &e : ev.e) ENC_TRY(hipEventCreate(&e));
 	for(uint32_t i = 0; i < n; i++) if(nlogs[i] && in[i].count) { jobs.push_back(PackJob{}); job_stream.push_back(i); }
 	o += (jobs.size()*sizeof(PackJob) + 15) & ~15ull;
+	const uint64_t o_gather = o;                         // copy jobs of the compaction (at most one per stream + one per log array)
+	uint64_t ngather = n;
+	for(uint32_t i = 0; i < n; i++) ngather += nlogs[i] ? nlogs[i] : 1u;
+	o += (ngather*sizeof(CopyJob) + 15) & ~15ull;
 	ENC_TRY(hipMalloc(&dev.p, o + 16));
 	uint8_t *base = dev.u8();
-	{
-		std::vector<uint8_t> h(values_bytes + 16);
-		for(uint32_t i = 0; i < n; i++) if(value_bytes(in[i])) memcpy(h.data() + v_off[i], in[i].values, value_bytes(in[i]));
-		if(values_bytes) ENC_TRY(hipMemcpy(base, h.data(), values_bytes, hipMemcpyHostToDevice));
-	}
 	ENC_TRY(hipMemsetAsync(base + o_nwords, 0, (size_t)(o_jobs - o_nwords), st));
-	StageTimes tm;
 	std::vector<uint32_t> nwords(n, 0);
 	if(!jobs.empty()) {
 		for(size_t j = 0; j < jobs.size(); j++) {
 			const uint32_t i = job_stream[j];
 			PackJob &p = jobs[j];
-			p.values = base + v_off[i]; p.logs = base + l_off[i]; p.words = (uint32_t *)(base + w_off[i]); p.nwords = (uint32_t *)(base + o_nwords) + i;
+			p.values = in[i].values; p.logs = base + l_off[i]; p.words = (uint32_t *)(base + w_off[i]); p.nwords = (uint32_t *)(base + o_nwords) + i;
 			p.count = in[i].count; p.N = in[i].components; p.kind = in[i].kind;
 		}
 		ENC_TRY(hipMemcpyAsync(base + o_jobs, jobs.data(), jobs.size()*sizeof(PackJob), hipMemcpyHostToDevice, st));
+		tm.bytes_to_device += jobs.size()*sizeof(PackJob);
 		ENC_TRY(hipEventRecord(ev.e[4], st));
 		hipLaunchKernelGGL(k_enc_pack, dim3((uint32_t)jobs.size()), dim3(256), 0, st, (const PackJob *)(base + o_jobs), (uint32_t)jobs.size());
 		ENC_TRY(hipEventRecord(ev.e[5], st));
 		ENC_TRY(hipMemcpyAsync(nwords.data(), base + o_nwords, (size_t)n*4, hipMemcpyDeviceToHost, st));
 		ENC_TRY(hipStreamSynchronize(st));
 		ENC_TRY(hipGetLastError());
+		tm.bytes_from_device += (uint64_t)n*4;
 		float ms = 0;
-		if(hipEventElapsedTime(&ms, ev.e[4], ev.e[5]) == hipSuccess) { tm.pack = ms; tm.any_pack = true; }
+		if(hipEventElapsedTime(&ms, ev.e[4], ev.e[5]) == hipSuccess) { tm.pack += ms; tm.any_pack = true; }
 	}
-	// bit words back to the host
+	// what comes back without the entropy coder - the bit words of every stream, the raw logs / symbols of entropy NONE - is
+	// compacted on the device behind the pack and copied back at once
+	std::vector<CopyJob> gather;
+	std::vector<uint64_t> at_words(n, 0);
+	uint64_t back = 0;
 	for(uint32_t i = 0; i < n; i++) {
 		if(!nlogs[i]) continue;
 		if((uint64_t)nwords[i] > (uint64_t)in[i].count*in[i].components + 1) return ctx_fail(CRTHIP_E_DEVICE, "k_enc_pack produced an impossible word count");
 		res[i].words.resize(nwords[i]);
-		if(nwords[i]) ENC_TRY(hipMemcpyAsync(res[i].words.data(), base + w_off[i], (size_t)nwords[i]*4, hipMemcpyDeviceToHost, st));
+		at_words[i] = back;
+		if(nwords[i]) { gather.push_back(CopyJob{base + w_off[i], nullptr, (uint64_t)nwords[i]*4, back}); back += (uint64_t)nwords[i]*4; }
 	}
 	// entropy coder over the log arrays (device resident) and the symbol streams
 	std::vector<const uint8_t *> d_src; std::vector<uint32_t> sizes; std::vector<std::pair<uint32_t, uint32_t>> owner;
+	std::vector<uint64_t> at_raw;
 	for(uint32_t i = 0; i < n; i++) {
-		if(!nlogs[i]) { d_src.push_back(base + v_off[i]); sizes.push_back(in[i].count); owner.push_back({i, 0}); res[i].blocks.resize(1); }
-		else {
-			res[i].blocks.resize(nlogs[i]);
-			for(uint32_t c = 0; c < nlogs[i]; c++) { d_src.push_back(base + l_off[i] + (uint64_t)c*in[i].count); sizes.push_back(in[i].count); owner.push_back({i, c}); }
+		const uint32_t nb = nlogs[i] ? nlogs[i] : 1u;
+		res[i].blocks.resize(nb);
+		for(uint32_t c = 0; c < nb; c++) {
+			const uint8_t *src = nlogs[i] ? base + l_off[i] + (uint64_t)c*in[i].count : (const uint8_t *)in[i].values;
+			const uint32_t size = in[i].count;
+			if(in[i].entropy == CRTHIP_ENTROPY_TUNSTALL) { d_src.push_back(src); sizes.push_back(size); owner.push_back({i, c}); }
+			else {                                                     // OutStream::compress with entropy NONE: i32 size | bytes (cstream.cpp:43-64)
+				std::vector<uint8_t> &b = res[i].blocks[c];
+				b.resize(4 + (size_t)size);
+				memcpy(b.data(), &size, 4);
+				if(size) { gather.push_back(CopyJob{src, nullptr, size, back}); at_raw.push_back(back); back += (size + 15) & ~15ull; }
+				else at_raw.push_back(back);
+			}
 		}
 	}
-	if(entropy == CRTHIP_ENTROPY_TUNSTALL) {
+	if(!gather.empty()) {
+		DevMem dback;
+		ENC_TRY(hipMalloc(&dback.p, back + 16));
+		for(CopyJob &g : gather) g.dst = dback.u8() + g.dst_off;
+		ENC_TRY(hipMemcpyAsync(base + o_gather, gather.data(), gather.size()*sizeof(CopyJob), hipMemcpyHostToDevice, st));
+		hipLaunchKernelGGL(k_enc_gather, dim3((uint32_t)gather.size()), dim3(256), 0, st, (const CopyJob *)(base + o_gather), (uint32_t)gather.size());
+		std::vector<uint8_t> h(back + 16);
+		ENC_TRY(hipMemcpyAsync(h.data(), dback.p, back, hipMemcpyDeviceToHost, st));
+		ENC_TRY(hipStreamSynchronize(st));
+		ENC_TRY(hipGetLastError());
+		tm.bytes_to_device += gather.size()*sizeof(CopyJob); tm.bytes_from_device += back;
+		size_t r = 0;
+		for(uint32_t i = 0; i < n; i++) {
+			if(nlogs[i] && nwords[i]) memcpy(res[i].words.data(), h.data() + at_words[i], (size_t)nwords[i]*4);
+			if(in[i].entropy == CRTHIP_ENTROPY_TUNSTALL) continue;
+			for(std::vector<uint8_t> &b : res[i].blocks) { if(b.size() > 4) memcpy(b.data() + 4, h.data() + at_raw[r], b.size() - 4); r++; }
+		}
+	}
+	if(!d_src.empty()) {
 		std::vector<std::vector<uint8_t>> blocks;
 		{ const int e = tun_encode_device(st, (uint32_t)d_src.size(), d_src.data(), sizes.data(), blocks, tm); if(e) return e; }
-		for(size_t k = 0; k < blocks.size(); k++) res[owner[k].first].blocks[owner[k].second] = std::move(blocks[k]);
-	} else {                                                       // OutStream::compress with entropy NONE: i32 size | bytes (cstream.cpp:43-64)
-		for(size_t k = 0; k < d_src.size(); k++) {
-			std::vector<uint8_t> &b = res[owner[k].first].blocks[owner[k].second];
-			b.resize(4 + (size_t)sizes[k]);
-			memcpy(b.data(), &sizes[k], 4);
-			if(sizes[k]) ENC_TRY(hipMemcpyAsync(b.data() + 4, d_src[k], sizes[k], hipMemcpyDeviceToHost, st));
-		}
+		for(size_t k = 0; k < blocks.size(); k++) { tm.bytes_from_device += blocks[k].size(); res[owner[k].first].blocks[owner[k].second] = std::move(blocks[k]); }
 	}
 	ENC_TRY(hipStreamSynchronize(st));
-	report(times, tm);
+	return CRTHIP_OK;
+}
+
+// the same over HOST arrays, one entropy for all of them (crthip_encode_values, crthip_encode_gpu): the values go up in one copy
+int corto_hip::encode_value_streams(crthip_ctx *ctx, uint32_t entropy, const std::vector<EncValueStream> &in, std::vector<EncValueResult> &res,
+                                    crthip_kernel_times *times) {
+	const uint32_t n = (uint32_t)in.size();
+	res.assign(n, EncValueResult());
+	if(!ctx) return ctx_fail(CRTHIP_E_ARGUMENT, "encode_value_streams: null context");
+	if(entropy != CRTHIP_ENTROPY_NONE && entropy != CRTHIP_ENTROPY_TUNSTALL) return ctx_fail(CRTHIP_E_ENTROPY, nullptr);
+	if(times) memset(times, 0, sizeof(*times));
+	ENC_TRY(hipSetDevice(ctx_device(ctx)));
+	{ const int e = ctx_quiesce(ctx); if(e) return e; }
+	auto value_bytes = [&](const EncValueStream &s) -> uint64_t {
+		return s.kind == CRTHIP_ENC_SYMBOLS ? s.count : (uint64_t)s.count*s.components*(s.kind == CRTHIP_ENC_VALUES_I8 ? 1 : 4);
+	};
+	std::vector<uint64_t> v_off(n);
+	uint64_t o = 0;
+	for(uint32_t i = 0; i < n; i++) {
+		const EncValueStream &s = in[i];
+		if(s.count && !s.values) return ctx_fail(CRTHIP_E_ARGUMENT, "encode_value_streams: null values");
+		if(s.kind > CRTHIP_ENC_VALUES_I8) return ctx_fail(CRTHIP_E_ARGUMENT, "encode_value_streams: unknown stream kind");
+		if(s.kind != CRTHIP_ENC_SYMBOLS && (s.components == 0 || s.components > ENC_PACK_MAX_N)) return ctx_fail(CRTHIP_E_LIMIT, "encode_value_streams: components out of range");
+		if((uint64_t)s.count*std::max(1u, s.components) > (1u << 26)) return ctx_fail(CRTHIP_E_LIMIT, "encode_value_streams: array too long");
+		v_off[i] = o; o += (value_bytes(s) + 15) & ~15ull;
+	}
+	DevMem dev;
+	ENC_TRY(hipMalloc(&dev.p, o + 16));
+	{
+		std::vector<uint8_t> h(o + 16);
+		for(uint32_t i = 0; i < n; i++) if(value_bytes(in[i])) memcpy(h.data() + v_off[i], in[i].values, value_bytes(in[i]));
+		if(o) ENC_TRY(hipMemcpy(dev.p, h.data(), o, hipMemcpyHostToDevice));
+	}
+	std::vector<DevValueStream> d(n);
+	for(uint32_t i = 0; i < n; i++) { d[i].kind = in[i].kind; d[i].count = in[i].count; d[i].components = in[i].components; d[i].entropy = entropy; d[i].values = dev.u8() + v_off[i]; }
+	StageTimes tm;
+	{ const int e = encode_value_streams_device(ctx, d, res, tm); if(e) return e; }
+	enc_report_times(times, tm);
 	return CRTHIP_OK;
 }
 

@@ -54,6 +54,7 @@ constexpr uint32_t DEFER_BITS = 0xFFu;
 struct Sink {
 	std::vector<uint8_t> b;
 	std::vector<Deferred> *defer = nullptr;   // non-null: value / symbol / bit streams are recorded, not written
+	bool shape_only = false;                  // (crthip_encode_batch) ... and only their kind and size: the values live on the device
 	void u8(uint32_t v) { b.push_back((uint8_t)v); }
 	void u16(uint32_t v) { u8(v); u8(v >> 8); }
 	void u32(uint32_t v) { u8(v); u8(v >> 8); u8(v >> 16); u8(v >> 24); }
@@ -205,7 +206,7 @@ struct Tunstall {
 
 // entropy-coded byte array (OutStream::compress / tunstall_compress, cstream.cpp:43-64, 89-109)
 void put_symbols(Sink &s, uint32_t entropy, const uint8_t *data, uint32_t size) {
-	if(s.defer) { Deferred d; d.at = s.b.size(); d.kind = CRTHIP_ENC_SYMBOLS; d.count = size; d.bytes.assign(data, data + size); s.defer->push_back(std::move(d)); return; }
+	if(s.defer) { Deferred d; d.at = s.b.size(); d.kind = CRTHIP_ENC_SYMBOLS; d.count = size; if(!s.shape_only) d.bytes.assign(data, data + size); s.defer->push_back(std::move(d)); return; }
 	if(entropy == CRTHIP_ENTROPY_NONE) { s.u32(size); s.raw(data, size); return; }
 	Tunstall t;
 	t.probabilities(data, (int)size);
@@ -232,8 +233,8 @@ int needed(int a) {                                                             
 template <class T> void put_values(Sink &s, uint32_t entropy, uint32_t size, const T *values, int N) {
 	if(s.defer) {
 		Deferred d; d.at = s.b.size(); d.count = size; d.N = (uint32_t)N;
-		if(sizeof(T) == 1) { d.kind = CRTHIP_ENC_VALUES_I8; d.bytes.assign((const uint8_t *)values, (const uint8_t *)values + (size_t)size*N); }
-		else { d.kind = CRTHIP_ENC_VALUES_I32; d.ints.assign((const int32_t *)values, (const int32_t *)values + (size_t)size*N); }
+		if(sizeof(T) == 1) { d.kind = CRTHIP_ENC_VALUES_I8; if(!s.shape_only) d.bytes.assign((const uint8_t *)values, (const uint8_t *)values + (size_t)size*N); }
+		else { d.kind = CRTHIP_ENC_VALUES_I32; if(!s.shape_only) d.ints.assign((const int32_t *)values, (const int32_t *)values + (size_t)size*N); }
 		s.defer->push_back(std::move(d)); return;
 	}
 	BitWriter bw;
@@ -253,7 +254,7 @@ template <class T> void put_values(Sink &s, uint32_t entropy, uint32_t size, con
 
 // encodeArray (cstream.h:143-164): one log per element
 void put_array(Sink &s, uint32_t entropy, uint32_t size, const int32_t *values, int N) {
-	if(s.defer) { Deferred d; d.at = s.b.size(); d.kind = CRTHIP_ENC_ARRAY; d.count = size; d.N = (uint32_t)N; d.ints.assign(values, values + (size_t)size*N); s.defer->push_back(std::move(d)); return; }
+	if(s.defer) { Deferred d; d.at = s.b.size(); d.kind = CRTHIP_ENC_ARRAY; d.count = size; d.N = (uint32_t)N; if(!s.shape_only) d.ints.assign(values, values + (size_t)size*N); s.defer->push_back(std::move(d)); return; }
 	BitWriter bw;
 	std::vector<uint8_t> logs(size);
 	for(uint32_t i = 0; i < size; i++) {
@@ -565,7 +566,9 @@ struct Encoder {
 		}
 	}
 
-	void encode_mesh() {                                                               // src/encoder.cpp:311-381
+	// The topology pass (src/encoder.cpp:311-376 up to the attributes): degenerate faces dropped per group, the CLERS walk of every
+	// group, split bits, max_front, the prediction quads and current_vertex.  Reads the index alone; nvert stays the input's.
+	void topology() {
 		encoded.assign(nvert, -1);
 		if(group_end.empty()) group_end.push_back(nface);
 		uint32_t start = 0, count = 0;
@@ -583,10 +586,19 @@ struct Encoder {
 		prediction.assign(nvert, Quad{0, 0, 0, 0});
 		start = 0;
 		for(uint32_t g : group_end) { encode_faces((int)start, (int)g); start = g; }
+	}
+
+	void encode_mesh() {                                                               // src/encoder.cpp:311-381
+		topology();
 		for(auto &kv : data) if(kv.second.codec == CRTHIP_CODEC_NORMAL) normal_predelta(kv.second);
 		nvert = current_vertex;
 		prediction.resize(nvert);
 		for(auto &kv : data) delta_encode(kv.second);
+		mesh_body();
+	}
+
+	// everything of a mesh after the header: counts, groups, CLERS, split bits, attributes
+	void mesh_body() {
 		s.u32(nvert); s.u32(nface);
 		groups();
 		s.u32(max_front);
@@ -595,43 +607,69 @@ struct Encoder {
 		for(auto &kv : data) attr_encode(kv.second);
 	}
 
-	struct ZPoint { uint64_t bits; uint32_t pos; bool operator<(const ZPoint &z) const { return bits > z.bits; } };
-
 	void encode_cloud() {                                                              // src/encoder.cpp:238-296
-		const std::vector<int32_t> &coords = data.find("position")->second.values;
-		int32_t mn[3] = {0, 0, 0};
-		for(uint32_t i = 0; i < nvert; i++) for(int k = 0; k < 3; k++) mn[k] = std::min(mn[k], coords[(size_t)i*3 + k]);
-		std::vector<ZPoint> z(nvert);
-		for(uint32_t i = 0; i < nvert; i++) {
-			const uint64_t x = (uint64_t)(int64_t)(coords[(size_t)i*3] - mn[0]), y = (uint64_t)(int64_t)(coords[(size_t)i*3 + 1] - mn[1]), w = (uint64_t)(int64_t)(coords[(size_t)i*3 + 2] - mn[2]);
-			uint64_t bits = 0; const uint64_t l = 1;
-			for(int k = 0; k < 21; k++) bits |= (x & l << k) << (2*k) | (y & l << k) << (2*k + 1) | (w & l << k) << (2*k + 2);   // include/corto/zpoint.h:34-38
-			z[i] = ZPoint{bits, i};
-		}
-		std::sort(z.rbegin(), z.rend());
-		s.u32(nvert); s.u32(0);
-		groups();
+		std::vector<uint32_t> order;
+		corto_hip::morton_order_host(data.find("position")->second.values.data(), nvert, order);
 		prediction.resize(nvert);
-		if(nvert) prediction[0] = Quad{z[0].pos, 0xffffffff, 0xffffffff, 0xffffffff};
-		for(uint32_t i = 1; i < nvert; i++) prediction[i] = Quad{z[i].pos, z[i - 1].pos, z[i - 1].pos, z[i - 1].pos};
+		if(nvert) prediction[0] = Quad{order[0], 0xffffffff, 0xffffffff, 0xffffffff};
+		for(uint32_t i = 1; i < nvert; i++) prediction[i] = Quad{order[i], order[i - 1], order[i - 1], order[i - 1]};
 		for(auto &kv : data) if(kv.second.codec == CRTHIP_CODEC_NORMAL) normal_predelta(kv.second);
 		for(auto &kv : data) delta_encode(kv.second);
+		cloud_body();
+	}
+
+	void cloud_body() {                                                                // (the sort and the residuals write nothing)
+		s.u32(nvert); s.u32(0);
+		groups();
 		for(auto &kv : data) attr_encode(kv.second);
 	}
 };
 
+struct ZPoint { uint64_t bits; uint32_t pos; bool operator<(const ZPoint &z) const { return bits > z.bits; } };
+
 } // namespace
+
+// Arguments are checked before anything is indexed with them (upstream trusts its caller: an index >= nvert writes past its
+// vectors, src/encoder.cpp:341-347).
+int corto_hip::encode_check(const crthip_mesh *m) {
+	if(!m || !m->position) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: no mesh / no positions");
+	if(m->index && m->nface) {
+		if((uint64_t)m->nface*3 > 0xFFFFFFFFull) return corto_hip::ctx_fail(CRTHIP_E_LIMIT, "crthip_encode: too many faces");
+		for(size_t i = 0; i < (size_t)m->nface*3; i++)
+			if(m->index[i] >= m->nvert) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: face index out of range");
+	}
+	if(m->color) {
+		if(m->color_components != 3 && m->color_components != 4) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: color_components must be 3 or 4");
+		for(int k = 0; k < m->color_components; k++)
+			if(m->color_bits[k] < 1 || m->color_bits[k] > 8) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: color_bits must be 1..8");
+	}
+	if(m->normal && (m->normal_bits < 1 || m->normal_bits > 16 || m->normal_prediction < 0 || m->normal_prediction > 2))
+		return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: normal_bits must be 1..16, normal_prediction 0..2");
+	if(m->position_bits > 31) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: position_bits must be < 32");
+	if(m->entropy != CRTHIP_ENTROPY_NONE && m->entropy != CRTHIP_ENTROPY_TUNSTALL) return corto_hip::ctx_fail(CRTHIP_E_ENTROPY, nullptr);
+	if(m->ngroups) {
+		if(!m->group_end || m->ngroups > (1u << 24)) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: groups");
+		uint32_t prev = 0;
+		for(uint32_t g = 0; g < m->ngroups; g++) {
+			// (a point cloud's group table is written as given and never used to index anything, src/encoder.cpp:238-296)
+			if(m->group_end[g] < prev || (m->index && m->nface && m->group_end[g] > m->nface)) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: group ends must be ascending and <= nface");
+			prev = m->group_end[g];
+			if(m->group_nprops && m->group_nprops[g] > 255) return corto_hip::ctx_fail(CRTHIP_E_LIMIT, "crthip_encode: more than 255 properties in a group");
+		}
+	}
+	return CRTHIP_OK;
+}
 
 extern "C" {
 
 
 // Encode a mesh / point cloud into a .crt blob (host only).  Returns the blob size (also when out == NULL or cap is too
 // small: call twice), or <0.  out_nvert/out_nface = counts after unreferenced vertices / degenerate faces are dropped.
-static int64_t encode_impl(const crthip_mesh *m, uint8_t *out, size_t cap, uint32_t *out_nvert, uint32_t *out_nface, crthip_ctx *gpu) {
-	if(!m || !m->position) return CRTHIP_E_ARGUMENT;
-	Encoder E;
-	std::vector<Deferred> deferred;
-	if(gpu) E.s.defer = &deferred;
+// Everything encode_impl knows before the topology pass: exif, groups, the faces, and per attribute its parameters and its
+// quantisation request (in the order the attributes are added; `alloc`: size the value arrays the requests write into).
+// `step`: the position step when the caller has it already (crthip_encode_batch: computed once, before the device quantises).
+struct NamedQuant { std::string name; corto_hip::QuantRequest r; };
+static void setup(const crthip_mesh *m, Encoder &E, std::vector<NamedQuant> &quant, bool alloc, const float *step) {
 	E.nvert = m->nvert; E.nface = m->index ? m->nface : 0; E.entropy = (uint32_t)m->entropy;
 	const char *p = m->exif;
 	for(uint32_t i = 0; i < m->nexif; i++) { std::string k(p); p += k.size() + 1; std::string v(p); p += v.size() + 1; E.exif[k] = v; }
@@ -648,10 +686,14 @@ static int64_t encode_impl(const crthip_mesh *m, uint8_t *out, size_t cap, uint3
 	}
 	if(E.nface) E.faces.assign(m->index, m->index + (size_t)E.nface*3);
 	const uint32_t nv = m->nvert;
-	std::vector<corto_hip::QuantRequest> quant;                     // (device path) the attributes' quantisation, collected and run in one call
+	auto request = [&](const char *name, Attr &a, corto_hip::QuantRequest r, size_t elems, size_t esize) {
+		if(alloc) { if(esize == 1) a.cvalues.resize(elems); else a.values.resize(elems); r.out = esize == 1 ? (void *)a.cvalues.data() : (void *)a.values.data(); }
+		quant.push_back(NamedQuant{name, r});
+	};
 	{	// positions (src/encoder.cpp:49-100, vertex_attribute.h:79-128)
 		float q = m->position_q;
-		if(m->position_bits > 0) {
+		if(step) q = *step;
+		else if(m->position_bits > 0) {
 			float mn[3] = {m->position[0], m->position[1], m->position[2]}, mx[3] = {mn[0], mn[1], mn[2]};
 			for(uint32_t i = 0; i < nv; i++) for(int k = 0; k < 3; k++) { const float v = m->position[(size_t)i*3 + k]; if(v < mn[k]) mn[k] = v; if(v > mx[k]) mx[k] = v; }
 			const float intervals = powf(2.0f, (float)m->position_bits);
@@ -674,42 +716,62 @@ static int64_t encode_impl(const crthip_mesh *m, uint8_t *out, size_t cap, uint3
 		Attr &a = E.data["position"];
 		a.name = "position"; a.N = 3; a.q = q; a.format = CRTHIP_FMT_FLOAT;
 		a.strategy = CRTHIP_CORRELATED | (E.nface > 0 ? CRTHIP_PARALLEL : 0);
-		a.values.resize((size_t)nv*3);
-		if(gpu) { corto_hip::QuantRequest r; r.kind = 0; r.count = nv*3; r.in = m->position; r.out = a.values.data(); r.q = q; quant.push_back(r); }
-		else for(size_t i = 0; i < (size_t)nv*3; i++) a.values[i] = f2i((m->position[i] - 0.0f)/q);
+		corto_hip::QuantRequest r; r.kind = 0; r.count = nv*3; r.in = m->position; r.q = q;
+		request("position", a, r, (size_t)nv*3, 4);
 	}
 	if(m->normal) {
 		Attr &a = E.data["normal"];
 		a.name = "normal"; a.codec = CRTHIP_CODEC_NORMAL; a.N = 3; a.q = powf(2.0f, (float)(m->normal_bits - 1));
 		a.format = CRTHIP_FMT_FLOAT; a.strategy = CRTHIP_CORRELATED; a.prediction = m->normal_prediction;
-		a.values.resize((size_t)nv*2);
-		const int unit = f2i(a.q);
-		if(gpu) { corto_hip::QuantRequest r; r.kind = 1; r.count = nv; r.in = m->normal; r.out = a.values.data(); r.unit = unit; quant.push_back(r); }
-		else for(uint32_t i = 0; i < nv; i++) to_octa(m->normal + (size_t)i*3, unit, &a.values[(size_t)i*2]);
+		corto_hip::QuantRequest r; r.kind = 1; r.count = nv; r.in = m->normal; r.unit = f2i(a.q);
+		request("normal", a, r, (size_t)nv*2, 4);
 	}
 	if(m->color) {
 		Attr &a = E.data["color"];
 		a.name = "color"; a.codec = CRTHIP_CODEC_COLOR; a.N = m->color_components; a.format = CRTHIP_FMT_UINT8; a.strategy = 0; a.q = 0;
 		for(int k = 0; k < 3; k++) a.qc[k] = 1 << (8 - m->color_bits[k]);
 		a.qc[3] = m->color_components == 3 ? 1 : 1 << (8 - m->color_bits[3]);           // addColors3: setQ(r, g, b, 8)
-		a.cvalues.resize((size_t)nv*a.N);
-		if(gpu) { corto_hip::QuantRequest r; r.kind = 2; r.count = nv; r.N = (uint32_t)a.N; r.in = m->color; r.out = a.cvalues.data(); for(int k = 0; k < 4; k++) r.qc[k] = (uint32_t)a.qc[k]; quant.push_back(r); }
-		else for(uint32_t i = 0; i < nv; i++) {                                         // color_attribute.cpp:30-44, point.h:213
-			uint8_t y[4] = {0, 0, 0, 0};
-			for(int k = 0; k < a.N; k++) y[k] = (uint8_t)(m->color[(size_t)i*a.N + k]/a.qc[k]);
-			const uint8_t ycc[4] = {y[1], (uint8_t)(y[2] - y[1]), (uint8_t)(y[0] - y[1]), y[3]};
-			for(int k = 0; k < a.N; k++) a.cvalues[(size_t)i*a.N + k] = ycc[k];
-		}
+		corto_hip::QuantRequest r; r.kind = 2; r.count = nv; r.N = (uint32_t)a.N; r.in = m->color; for(int k = 0; k < 4; k++) r.qc[k] = (uint32_t)a.qc[k];
+		request("color", a, r, (size_t)nv*a.N, 1);
 	}
 	auto generic = [&](const char *name, const float *buf, int N, float q) {
 		Attr &a = E.data[name];
 		a.name = name; a.N = N; a.q = q; a.format = CRTHIP_FMT_FLOAT; a.strategy = 0;
-		a.values.resize((size_t)nv*N);
-		if(gpu) { corto_hip::QuantRequest r; r.kind = 0; r.count = nv*(uint32_t)N; r.in = buf; r.out = a.values.data(); r.q = q; quant.push_back(r); }
-		else for(size_t i = 0; i < (size_t)nv*N; i++) a.values[i] = f2i(buf[i]/q);
+		corto_hip::QuantRequest r; r.kind = 0; r.count = nv*(uint32_t)N; r.in = buf; r.q = q;
+		request(name, a, r, (size_t)nv*N, 4);
 	};
 	if(m->uv) generic("uv", m->uv, 2, m->uv_q);
 	if(m->radius) generic("radius", m->radius, 1, m->radius_q);
+}
+
+// the host's quantisation of one request (what k_enc_quantize does on the device)
+static void quantize_host(const corto_hip::QuantRequest &r) {
+	if(r.kind == 0) {                                                                // vertex_attribute.h:97-99
+		const float *in = (const float *)r.in; int32_t *o = (int32_t *)r.out;
+		for(size_t i = 0; i < r.count; i++) o[i] = f2i((in[i] - 0.0f)/r.q);
+	} else if(r.kind == 1) {
+		for(uint32_t i = 0; i < r.count; i++) to_octa((const float *)r.in + (size_t)i*3, r.unit, (int32_t *)r.out + (size_t)i*2);
+	} else {                                                                         // color_attribute.cpp:30-44, point.h:213
+		const uint8_t *in = (const uint8_t *)r.in; uint8_t *o = (uint8_t *)r.out;
+		const int N = (int)r.N;
+		for(uint32_t i = 0; i < r.count; i++) {
+			uint8_t y[4] = {0, 0, 0, 0};
+			for(int k = 0; k < N; k++) y[k] = (uint8_t)(in[(size_t)i*N + k]/(int)r.qc[k]);
+			const uint8_t ycc[4] = {y[1], (uint8_t)(y[2] - y[1]), (uint8_t)(y[0] - y[1]), y[3]};
+			for(int k = 0; k < N; k++) o[(size_t)i*N + k] = ycc[k];
+		}
+	}
+}
+
+static int64_t encode_impl(const crthip_mesh *m, uint8_t *out, size_t cap, uint32_t *out_nvert, uint32_t *out_nface, crthip_ctx *gpu) {
+	if(!m || !m->position) return CRTHIP_E_ARGUMENT;
+	Encoder E;
+	std::vector<Deferred> deferred;
+	if(gpu) E.s.defer = &deferred;
+	std::vector<NamedQuant> named;
+	setup(m, E, named, true, nullptr);
+	std::vector<corto_hip::QuantRequest> quant;                     // (device path) the attributes' quantisation, collected and run in one call
+	for(const NamedQuant &q : named) { if(gpu) quant.push_back(q.r); else quantize_host(q.r); }
 	if(gpu) { const int qerr = corto_hip::quantize_device(gpu, quant); if(qerr) return qerr; }   // every attribute's quantisation in one device call (k_enc_quantize)
 	E.header();
 	if(E.nface > 0) E.encode_mesh(); else E.encode_cloud();
@@ -746,34 +808,9 @@ static int64_t encode_impl(const crthip_mesh *m, uint8_t *out, size_t cap, uint3
 	return (int64_t)E.s.b.size();
 }
 
-// Arguments are checked before anything is indexed with them (upstream trusts its caller: an index >= nvert writes past its
-// vectors, src/encoder.cpp:341-347), and nothing is thrown across the C boundary.
+// nothing is thrown across the C boundary
 static int64_t encode_checked(const crthip_mesh *m, uint8_t *out, size_t cap, uint32_t *out_nvert, uint32_t *out_nface, crthip_ctx *gpu) {
-	if(!m || !m->position) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: no mesh / no positions");
-	if(m->index && m->nface) {
-		if((uint64_t)m->nface*3 > 0xFFFFFFFFull) return corto_hip::ctx_fail(CRTHIP_E_LIMIT, "crthip_encode: too many faces");
-		for(size_t i = 0; i < (size_t)m->nface*3; i++)
-			if(m->index[i] >= m->nvert) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: face index out of range");
-	}
-	if(m->color) {
-		if(m->color_components != 3 && m->color_components != 4) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: color_components must be 3 or 4");
-		for(int k = 0; k < m->color_components; k++)
-			if(m->color_bits[k] < 1 || m->color_bits[k] > 8) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: color_bits must be 1..8");
-	}
-	if(m->normal && (m->normal_bits < 1 || m->normal_bits > 16 || m->normal_prediction < 0 || m->normal_prediction > 2))
-		return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: normal_bits must be 1..16, normal_prediction 0..2");
-	if(m->position_bits > 31) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: position_bits must be < 32");
-	if(m->entropy != CRTHIP_ENTROPY_NONE && m->entropy != CRTHIP_ENTROPY_TUNSTALL) return corto_hip::ctx_fail(CRTHIP_E_ENTROPY, nullptr);
-	if(m->ngroups) {
-		if(!m->group_end || m->ngroups > (1u << 24)) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: groups");
-		uint32_t prev = 0;
-		for(uint32_t g = 0; g < m->ngroups; g++) {
-			// (a point cloud's group table is written as given and never used to index anything, src/encoder.cpp:238-296)
-			if(m->group_end[g] < prev || (m->index && m->nface && m->group_end[g] > m->nface)) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: group ends must be ascending and <= nface");
-			prev = m->group_end[g];
-			if(m->group_nprops && m->group_nprops[g] > 255) return corto_hip::ctx_fail(CRTHIP_E_LIMIT, "crthip_encode: more than 255 properties in a group");
-		}
-	}
+	{ const int e = corto_hip::encode_check(m); if(e) return e; }
 	try {
 		return encode_impl(m, out, cap, out_nvert, out_nface, gpu);
 	} catch(const std::bad_alloc &) {
@@ -810,4 +847,72 @@ void corto_hip::tun_encoder_tables(const uint32_t counts[256], uint32_t size, Tu
 	for(size_t i = 0; i < t.remap.size() && i < 256; i++) out.remap[i] = t.remap[i];
 	for(size_t i = 0; i < t.lengths.size() && i < 256; i++) out.lengths[i] = (uint16_t)t.lengths[i];
 	out.offsets.assign(t.offsets.begin(), t.offsets.end());
+}
+
+// ---- crthip_encode_batch's host half (encode_batch.cpp runs the rest on the device) ----
+
+void corto_hip::morton_order_host(const int32_t *coords, uint32_t nvert, std::vector<uint32_t> &order) {   // src/encoder.cpp:238-262
+	int32_t mn[3] = {0, 0, 0};
+	for(uint32_t i = 0; i < nvert; i++) for(int k = 0; k < 3; k++) mn[k] = std::min(mn[k], coords[(size_t)i*3 + k]);
+	std::vector<ZPoint> z(nvert);
+	for(uint32_t i = 0; i < nvert; i++) {
+		const uint64_t x = (uint64_t)(int64_t)(coords[(size_t)i*3] - mn[0]), y = (uint64_t)(int64_t)(coords[(size_t)i*3 + 1] - mn[1]), w = (uint64_t)(int64_t)(coords[(size_t)i*3 + 2] - mn[2]);
+		uint64_t bits = 0; const uint64_t l = 1;
+		for(int k = 0; k < 21; k++) bits |= (x & l << k) << (2*k) | (y & l << k) << (2*k + 1) | (w & l << k) << (2*k + 2);   // include/corto/zpoint.h:34-38
+		z[i] = ZPoint{bits, i};
+	}
+	std::sort(z.rbegin(), z.rend());
+	order.resize(nvert);
+	for(uint32_t i = 0; i < nvert; i++) order[i] = z[i].pos;
+}
+
+void corto_hip::batch_setup(const crthip_mesh *m, BatchItem &it) {
+	Encoder E;
+	std::vector<NamedQuant> named;
+	setup(m, E, named, false, nullptr);
+	it.entropy = E.entropy; it.nvert_in = m->nvert; it.nface_in = E.nface;
+	it.attrs.clear();
+	for(auto &kv : E.data) {                                     // the container's order (std::map)
+		const Attr &a = kv.second;
+		BatchAttr b;
+		b.codec = (uint32_t)a.codec; b.N = (uint32_t)a.N; b.prediction = (uint32_t)a.prediction; b.strategy = (uint32_t)a.strategy;
+		for(const NamedQuant &q : named) if(q.name == kv.first) b.quant = q.r;
+		it.attrs.push_back(b);
+	}
+}
+
+void corto_hip::batch_topology(const crthip_mesh *m, BatchItem &it) {
+	Encoder E;
+	std::vector<NamedQuant> named;
+	float step = 0;
+	for(const BatchAttr &b : it.attrs) if(b.codec == CRTHIP_CODEC_GENERIC && b.N == 3 && b.quant.in == m->position) step = b.quant.q;
+	setup(m, E, named, false, &step);
+	std::vector<Deferred> deferred;
+	E.s.defer = &deferred; E.s.shape_only = true;
+	E.header();
+	const bool mesh = E.nface > 0;
+	if(mesh) {
+		E.topology();
+		E.nvert = E.current_vertex;
+		E.prediction.resize(E.nvert);
+		E.mesh_body();
+		it.faces.swap(E.faces);
+		it.quads.resize((size_t)E.nvert*4);
+		if(E.nvert) memcpy(it.quads.data(), E.prediction.data(), (size_t)E.nvert*16);
+		it.clers.swap(E.clers);
+	} else E.cloud_body();
+	it.nvert = E.nvert; it.nface = E.nface;
+	it.frame.swap(E.s.b);
+	it.streams.clear();
+	const size_t first_attr = mesh ? 2 : 0;
+	for(size_t k = 0; k < deferred.size(); k++) {
+		const Deferred &d = deferred[k];
+		BatchStream b;
+		b.at = d.at; b.kind = d.kind; b.count = d.count; b.N = d.N;
+		b.attr = k < first_attr ? (k == 0 ? -1 : -2) : (int32_t)(k - first_attr);
+		if(d.kind == DEFER_BITS) { b.kind = BATCH_BITS; it.split_words = d.words; }
+		else if(b.attr >= 0 && it.attrs[b.attr].codec == CRTHIP_CODEC_NORMAL)         // the residuals' count: every vertex, or (BORDER) the device's
+			b.count = it.attrs[b.attr].prediction == 2 ? 0u : E.nvert;
+		it.streams.push_back(b);
+	}
 }

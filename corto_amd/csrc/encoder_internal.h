@@ -34,6 +34,34 @@ int encode_value_streams(crthip_ctx *ctx, uint32_t entropy, const std::vector<En
 struct QuantRequest { uint32_t kind = 0, count = 0, N = 1; const void *in = nullptr; void *out = nullptr; float q = 0; int32_t unit = 0; uint32_t qc[4] = {1, 1, 1, 1}; };
 int quantize_device(crthip_ctx *ctx, const std::vector<QuantRequest> &reqs);
 
+// the value coders + entropy coder over DEVICE-resident arrays (encode_gpu.cpp); each stream carries its mesh's entropy
+struct DevValueStream { uint32_t kind = 0, count = 0, components = 1, entropy = 0; const void *values = nullptr; };
+struct EncStageTimes { float hist = 0, parse = 0, pack = 0, tables = 0, trie = 0; bool any_hist = false, any_parse = false, any_pack = false, any_tables = false;
+                       uint32_t host_table_streams = 0; uint64_t bytes_to_device = 0, bytes_from_device = 0; };
+int encode_value_streams_device(crthip_ctx *ctx, const std::vector<DevValueStream> &in, std::vector<EncValueResult> &res, EncStageTimes &tm);
+void enc_report_times(crthip_kernel_times *times, const EncStageTimes &tm);   // appends the stages' entries behind times->count
+
+// ---- crthip_encode_batch (encoder.cpp: checks, topology pass and container; encode_batch.cpp: the device half) ----
+int encode_check(const crthip_mesh *m);              // encode_checked's argument checks (sets the last error)
+constexpr uint32_t BATCH_BITS = 0xFFu;                // a stream that is the CLERS split bits, already packed
+struct BatchAttr { uint32_t codec = 0, N = 0, prediction = 0, strategy = 0; QuantRequest quant; };
+struct BatchStream { size_t at = 0; uint32_t kind = 0, count = 0, N = 1; int32_t attr = 0; };   // attr: index in attrs, -1 CLERS symbols, -2 split bits
+struct BatchItem {
+	int32_t status = CRTHIP_OK;
+	uint32_t entropy = 0, nvert_in = 0, nface_in = 0;    // as given (nface_in 0: a point cloud)
+	uint32_t nvert = 0, nface = 0;                        // what the container says (after the topology pass)
+	std::vector<BatchAttr> attrs;                         // the container's order; quant.out unset
+	std::vector<uint32_t> faces;                          // meshes: degenerate faces dropped, original vertex ids
+	std::vector<uint32_t> quads;                          // meshes: the prediction, (t, a, b, c) per encoded vertex
+	std::vector<uint8_t> clers;
+	std::vector<uint32_t> split_words;
+	std::vector<uint8_t> frame;                           // the container without its streams
+	std::vector<BatchStream> streams;                     // where they belong in it, in order (a BORDER normal's count: 0 until the device has it)
+};
+void batch_setup(const crthip_mesh *m, BatchItem &it);           // position step + attribute table (after encode_check)
+void batch_topology(const crthip_mesh *m, BatchItem &it);        // topology pass (meshes) + frame; reads the index alone
+void morton_order_host(const int32_t *coords, uint32_t nvert, std::vector<uint32_t> &order);   // encode_cloud's std::sort of the Morton records
+
 // several blobs with HOST output buffers in one batch (batch.cpp): what crthip_decode_host is one of, and what the crt::Decoder facade's
 // combiner hands over when several threads call decode() at once.  copy_out: copy every output into the caller's buffer before
 // returning; else leave them in the context's pinned landing zone and say where (out_src -> out_dst, out_bytes): valid until the next

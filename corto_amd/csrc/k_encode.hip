@@ -14,6 +14,7 @@
 #include "kernels_common.h"
 #include "kernels.h"
 #include "std_sort_model.h"
+#include "enc_quant.h"
 
 namespace corto_hip {
 
@@ -127,37 +128,11 @@ __global__ __launch_bounds__(256) void k_enc_pack(const PackJob *__restrict__ jo
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Quantisation, elementwise.  The float recipes are upstream's, operation by operation (no FMA: the library is built with
-// -ffp-contract=off; IEEE divide): GENERIC (int)(x/q) (vertex_attribute.h:97-99); NORMAL toOcta (normal_attribute.h:75-85):
-// s = (|x| + |y|) + |z|, p = (x/s, y/s), folded when z < 0, (int)(p*unit); COLOR byte/qc then (g, b - g, r - g, a) (color_attribute.cpp:30-44,
-// point.h:213).  (int) is x86's cvttss2si: INT_MIN when out of range.
+// Quantisation, elementwise (enc_quant.h: upstream's float recipes, shared with k_enc_quantize_batch).
 __global__ __launch_bounds__(256) void k_enc_quantize(QuantJob J) {
 	const uint32_t i = blockIdx.x*256 + threadIdx.x;
 	if(i >= J.count) return;
-	if(J.kind == 0) {
-		const float x = ((const float *)J.in)[i] - 0.0f;
-		((int32_t *)J.out)[i] = f2i_x86(x/J.q);
-	} else if(J.kind == 1) {
-		const float *v = (const float *)J.in + (size_t)i*3;
-		const float vx = v[0], vy = v[1], vz = v[2];
-		float s = fabsf(vx) + fabsf(vy); s = s + fabsf(vz);
-		float px = vx/s, py = vy/s;
-		if(vz < 0) {
-			const float qx = 1.0f - fabsf(py), qy = 1.0f - fabsf(px);
-			px = qx; py = qy;
-			if(vx < 0) px = -px;
-			if(vy < 0) py = -py;
-		}
-		int32_t *o = (int32_t *)J.out + (size_t)i*2;
-		o[0] = f2i_x86(px*(float)J.unit); o[1] = f2i_x86(py*(float)J.unit);
-	} else {
-		const uint8_t *c = (const uint8_t *)J.in + (size_t)i*J.N;
-		uint8_t y[4] = {0, 0, 0, 0};
-		for(uint32_t k = 0; k < J.N && k < 4; k++) y[k] = (uint8_t)(c[k]/J.qc[k]);
-		const uint8_t ycc[4] = {y[1], (uint8_t)(y[2] - y[1]), (uint8_t)(y[0] - y[1]), y[3]};
-		uint8_t *o = (uint8_t *)J.out + (size_t)i*J.N;
-		for(uint32_t k = 0; k < J.N && k < 4; k++) o[k] = ycc[k];
-	}
+	enc_quantize_one(J, i);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -139,5 +139,21 @@ __global__ void k_enc_tables(const uint32_t *counts, const uint32_t *sizes, uint
 __global__ void k_enc_trie(const EncTab *tabs, const uint32_t *ids, EncStream *streams, uint32_t nids, uint32_t trie_cap);
 inline uint32_t enc_parse_lds(uint32_t trie_entries) { return 768 + ENC_STAGE + ENC_STAGE_PAD + 2*((trie_entries + 7) & ~7u); }
 constexpr uint32_t ENC_TRIE_LDS_MAX = 24*1024;         // entries (48 KiB) of trie kept in LDS at most; bigger tries are walked in L2
+__global__ void k_enc_gather(const CopyJob *jobs, uint32_t njobs);
+
+// k_encode_batch.hip (crthip_encode_batch).  block_start[j]: the first workgroup of job j (njobs + 1 entries)
+__global__ void k_enc_quantize_batch(const QuantJob *jobs, const uint32_t *block_start, uint32_t njobs);
+__global__ void k_enc_corners(const EstJob *jobs, const uint32_t *block_start, uint32_t njobs, uint32_t *keys, uint32_t *vals);
+__global__ void k_enc_est_normal(const EstJob *jobs, const uint32_t *block_start, uint32_t njobs, const uint32_t *keys, const uint32_t *vals,
+                                 uint32_t ncorners, const uint32_t *faces);
+__global__ void k_enc_delta(const DeltaEncJob *jobs, const uint32_t *block_start, uint32_t njobs);
+__global__ void k_enc_zmin(ZJob job);
+__global__ void k_enc_zkeys(ZJob job);
+__global__ void k_enc_zflag(ZJob job);
+// LSD radix sort of (u32 or u64 key, u32 value) records by the 8 key bits at `shift`: stable.  hist: 256 x nblocks counts, digit-major
+template <typename K> __global__ void k_enc_rs_hist(const K *keys, uint32_t n, uint32_t shift, uint32_t *hist);
+__global__ void k_enc_rs_scan(uint32_t *hist, uint32_t len);
+template <typename K> __global__ void k_enc_rs_scatter(const K *keys, const uint32_t *vals, K *keys_out, uint32_t *vals_out, uint32_t n, uint32_t shift,
+                                                       const uint32_t *hist);
 
 } // namespace corto_hip

@@ -411,6 +411,38 @@ int64_t crthip_encode_values(crthip_ctx *ctx, uint32_t entropy, uint32_t n, cons
  * container stay on the host): same arguments plus the context, byte-identical output. */
 int64_t crthip_encode_gpu(crthip_ctx *ctx, const crthip_mesh *mesh, uint8_t *out, size_t cap, uint32_t *out_nvert, uint32_t *out_nface);
 
+/* A batch of meshes and point clouds in, one .crt per item out, every blob byte-identical to crthip_encode of that item.
+ * The CLERS topology pass runs on `host_threads` host threads (0: min(16, CPUs of the process's affinity mask)) while the
+ * device quantises; estimated normals, residuals, the point clouds' Morton sort and the value / Tunstall coders run on the
+ * device, all meshes in one set of launches (each point cloud sorted by launches of its own).  Blob i is
+ * out[blob_offset[i] .. blob_offset[i+1]) (n+1 offsets); the call returns the total size, writes only when cap suffices,
+ * and out == NULL sizes only.
+ * Per mesh: crthip_encode's argument checks, a Tunstall stream over 2^23 symbols (CRTHIP_E_LIMIT), or more than 2^26 / 3
+ * vertices (CRTHIP_E_LIMIT: the device value coder's bound on an array; crthip_encode has none) put that CRTHIP_E_* in
+ * status[i] (may be NULL) and give the mesh an empty range; the others are still encoded.  < 0 for the call: null context, no
+ * device, a mesh too big for the device (CRTHIP_E_LIMIT).  No CPU fallback.
+ * Equal Morton keys (duplicate quantised points, coordinates beyond 21 bits): std::sort leaves those in an order no device
+ * sort reproduces, so such a cloud is ordered by the host's std::sort (clouds_host_sorted). */
+typedef struct {
+	float wall_ms;                 /* the whole call */
+	float host_topology_ms;        /* wall time of the host topology passes (they overlap the device work) */
+	float host_frame_ms;           /* headers, groups, CLERS / split splicing, zero padding */
+	uint32_t clouds_device_sorted; /* point clouds whose Morton order came from the device sort */
+	uint32_t clouds_host_sorted;   /* ... from the host std::sort (equal keys) */
+	uint32_t value_streams;        /* streams through the value coder / Tunstall coder in this call */
+	uint64_t bytes_to_device, bytes_from_device;
+	float host_check_ms;           /* argument checks, position steps and attribute tables, before any device work */
+	float host_stage_ms;           /* host copies into the upload buffers (raw attributes, faces, quads, CLERS) */
+	float sync_wait_ms;            /* blocked on the device in the batch's own stages (uploads, sorts, residuals, read-backs) */
+	float value_coder_ms;          /* wall time of the value + Tunstall coders, their copies included */
+	float upload_ms;               /* in the uploads of raw attributes, faces and quads (a copy from pageable memory returns when staged) */
+	float alloc_ms;                /* allocating the device image */
+	float topology_wait_ms;        /* waiting for topology passes that had not finished when the device stages needed them */
+} crthip_encode_batch_stats;
+int64_t crthip_encode_batch(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, uint32_t host_threads,
+                            uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert, uint32_t *out_nface,
+                            int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 // corto_hip — the `corto` command line tool (upstream src/main.cpp:48-388) on this repo's encoder and GPU decoder.
 //
 //   corto_hip [OPTIONS] <FILE.ply>
+//   corto_hip [OPTIONS] <FILE.ply> <FILE.ply> ...    every file to <stem>.crt in one crthip_encode_batch on device 0
 //
 // Same options, same defaults and the same flow as upstream: load the model, encode it to <output>.crt, and - with
 // -P <file.ply> - decode the blob again (here: on the MI355X through the crt::Decoder facade) and save the decoded mesh
@@ -176,9 +177,10 @@ bool save_ply(const std::string &path, const Model &m) {
 
 void usage() {
 	std::cerr <<
-R"use(Usage: corto_hip [OPTIONS] <FILE>
+R"use(Usage: corto_hip [OPTIONS] <FILE> [<FILE> ...]
 
-FILE is the path to a .ply 3D model.
+FILE is the path to a .ply 3D model.  With several files, all are encoded in one batch on the GPU,
+each to <stem>.crt (-o and -P take one file).
   -o <output>: filename of the .crt compressed file.
                if not specified the extension of the input file will be replaced.
   -e <key=value>: add an exif property, or more than one.
@@ -195,24 +197,95 @@ FILE is the path to a .ply 3D model.
 
 bool ends_with(const std::string &s, const std::string &x) { return s.size() >= x.size() && !s.compare(s.size() - x.size(), x.size(), x); }
 
+struct Options {
+	bool pointcloud = false;
+	float vertex_q = 0.0f;
+	int vertex_bits = 0, norm_bits = 10, r_bits = 6, g_bits = 7, b_bits = 6, a_bits = 5, uv_bits = 12;     // src/main.cpp:81-88
+	int prediction = 2;                                                   // BORDER, src/main.cpp:163
+};
+
+// the crthip_mesh upstream's main builds for a loaded model (src/main.cpp:180-222); points into `in`, `group_end` and `ex`
+void describe(Model &in, const Options &o, uint32_t &group_end, const std::string &ex, uint32_t nexif, crthip_mesh &M) {
+	group_end = (uint32_t)(in.index.size()/3);                            // loadPly: one group holding every face (src/meshloader.cpp:121), kept under -p
+	if(o.pointcloud) in.nface = 0;
+	const bool pointcloud = in.nface == 0;
+	memset(&M, 0, sizeof(M));
+	M.nvert = in.nvert; M.nface = in.nface;
+	M.position = in.coords.data();
+	M.index = pointcloud ? nullptr : in.index.data();
+	M.position_bits = o.vertex_bits; M.position_q = o.vertex_q;         // both 0: upstream's heuristic step
+	if(!in.norms.empty() && o.norm_bits > 0) { M.normal = in.norms.data(); M.normal_bits = o.norm_bits; M.normal_prediction = o.prediction; }
+	if(!in.colors.empty() && o.r_bits > 0) {
+		M.color = in.colors.data(); M.color_components = (int32_t)in.ncolor;
+		M.color_bits[0] = o.r_bits; M.color_bits[1] = o.g_bits; M.color_bits[2] = o.b_bits; M.color_bits[3] = o.a_bits;
+	}
+	if(!in.uvs.empty() && o.uv_bits > 0) { M.uv = in.uvs.data(); M.uv_q = (float)pow(2, -o.uv_bits); }
+	if(!in.radiuses.empty()) { M.radius = in.radiuses.data(); M.radius_q = 1.0f; }
+	M.group_end = &group_end; M.ngroups = 1;
+	M.entropy = CRTHIP_ENTROPY_TUNSTALL;
+	M.exif = ex.data(); M.nexif = nexif;
+}
+
+bool write_file(const std::string &path, const uint8_t *p, size_t n) {
+	FILE *file = fopen(path.c_str(), "wb");
+	if(!file) { std::cerr << "Could not open file: " << path << std::endl; return false; }
+	const size_t written = fwrite(p, 1, n, file);
+	fclose(file);
+	if(written != n) { std::cerr << "Failed saving file: " << path << std::endl; return false; }
+	return true;
+}
+
+// several input files: one crthip_encode_batch on device 0, every file to <stem>.crt (the same bytes as one run per file)
+int encode_many(const std::vector<std::string> &inputs, const Options &o, const std::string &ex, uint32_t nexif) {
+	const size_t n = inputs.size();
+	std::vector<Model> models(n);
+	std::vector<uint32_t> group_end(n);
+	std::vector<crthip_mesh> meshes(n);
+	for(size_t i = 0; i < n; i++) {
+		const std::string &input = inputs[i];
+		if(!ends_with(input, ".ply") && !ends_with(input, ".PLY")) { std::cerr << "Failed loading model: " << input << " (only .ply input is supported)" << std::endl; return 1; }
+		std::string err;
+		if(!load_ply(input, models[i], err)) { std::cerr << "Failed loading model: " << input << " (" << err << ")" << std::endl; return 1; }
+	}
+	for(size_t i = 0; i < n; i++) describe(models[i], o, group_end[i], ex, nexif, meshes[i]);
+	crthip_ctx *ctx = nullptr;
+	if(crthip_ctx_create(0, &ctx) != CRTHIP_OK) { std::cerr << "Encoding failed: " << crthip_last_error() << std::endl; return 1; }
+	std::vector<uint64_t> offs(n + 1);
+	std::vector<uint32_t> nvert(n), nface(n);
+	std::vector<int32_t> status(n);
+	int64_t size = crthip_encode_batch(ctx, (uint32_t)n, meshes.data(), 0, nullptr, 0, offs.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
+	std::vector<uint8_t> out(size > 0 ? (size_t)size : 1);
+	if(size >= 0) size = crthip_encode_batch(ctx, (uint32_t)n, meshes.data(), 0, out.data(), out.size(), offs.data(), nvert.data(), nface.data(),
+	                                         status.data(), nullptr, nullptr);
+	if(size < 0) { std::cerr << "Encoding failed: " << crthip_last_error() << std::endl; crthip_ctx_destroy(ctx); return 1; }
+	crthip_ctx_destroy(ctx);
+	int rc = 0;
+	for(size_t i = 0; i < n; i++) {
+		if(status[i] != CRTHIP_OK) { std::cerr << "Encoding failed: " << inputs[i] << ": " << crthip_strerror(status[i]) << std::endl; rc = 1; continue; }
+		const size_t bytes = (size_t)(offs[i + 1] - offs[i]);
+		std::cout << inputs[i] << " Nvert: " << nvert[i] << " Nface: " << nface[i] << " Compressed to: " << bytes << std::endl;
+		const std::string output = inputs[i].substr(0, inputs[i].find_last_of(".")) + ".crt";
+		if(!write_file(output, out.data() + offs[i], bytes)) rc = 1;
+	}
+	return rc;
+}
+
 } // namespace
 
 int main(int argc, char *argv[]) {
 	std::string input, output, plyfile, normal_prediction;
-	bool pointcloud = false;
-	float vertex_q = 0.0f;
-	int vertex_bits = 0, norm_bits = 10, r_bits = 6, g_bits = 7, b_bits = 6, a_bits = 5, uv_bits = 12;     // src/main.cpp:81-88
+	Options o;
 	std::map<std::string, std::string> exif;
 	int c;
 	while((c = getopt(argc, argv, "pAo:v:n:c:u:q:N:e:P:G:")) != -1) {
 		switch(c) {
 		case 'o': output = optarg; break;
-		case 'p': pointcloud = true; break;
-		case 'v': vertex_bits = atoi(optarg); break;
-		case 'n': norm_bits = atoi(optarg); break;
-		case 'c': r_bits = g_bits = a_bits = b_bits = atoi(optarg); break;
-		case 'u': uv_bits = atoi(optarg); break;
-		case 'q': vertex_q = (float)atof(optarg); break;
+		case 'p': o.pointcloud = true; break;
+		case 'v': o.vertex_bits = atoi(optarg); break;
+		case 'n': o.norm_bits = atoi(optarg); break;
+		case 'c': o.r_bits = o.g_bits = o.a_bits = o.b_bits = atoi(optarg); break;
+		case 'u': o.uv_bits = atoi(optarg); break;
+		case 'q': o.vertex_q = (float)atof(optarg); break;
 		case 'N': normal_prediction = optarg; break;
 		case 'P': plyfile = optarg; break;
 		case 'A': std::cerr << "-A (add normals) is not supported" << std::endl; return 1;
@@ -229,43 +302,33 @@ int main(int argc, char *argv[]) {
 		}
 	}
 	if(optind == argc) { std::cerr << "Missing filename" << std::endl; usage(); return 1; }
-	if(optind != argc - 1) { std::cerr << "Too many arguments\n"; usage(); return 1; }
+	auto prediction_ok = [&]() -> bool {
+		if(normal_prediction.empty()) return true;
+		if(normal_prediction == "delta") o.prediction = 0;
+		else if(normal_prediction == "border") o.prediction = 2;
+		else if(normal_prediction == "estimated") o.prediction = 1;
+		else { std::cerr << "Unknown normal prediction: " << normal_prediction << " expecting: delta, border or estimated" << std::endl; return false; }
+		return true;
+	};
+	std::string ex;
+	for(auto &kv : exif) { ex += kv.first; ex.push_back('\0'); ex += kv.second; ex.push_back('\0'); }
+	if(optind != argc - 1) {
+		if(!output.empty() || !plyfile.empty()) { std::cerr << "-o and -P take one input file; with several, each is written to <stem>.crt" << std::endl; usage(); return 1; }
+		if(!prediction_ok()) return 1;
+		return encode_many(std::vector<std::string>(argv + optind, argv + argc), o, ex, (uint32_t)exif.size());
+	}
 	input = argv[optind];
 	if(!ends_with(input, ".ply") && !ends_with(input, ".PLY")) { std::cerr << "Failed loading model: " << input << " (only .ply input is supported)" << std::endl; return 1; }
 
 	Model in;
 	std::string err;
 	if(!load_ply(input, in, err)) { std::cerr << "Failed loading model: " << input << " (" << err << ")" << std::endl; return 1; }
-	const uint32_t group_end = (uint32_t)(in.index.size()/3);            // loadPly: one group holding every face (src/meshloader.cpp:121), kept under -p
-	if(pointcloud) in.nface = 0;
-	pointcloud = in.nface == 0;
-	int prediction = 2;                                                   // BORDER, src/main.cpp:163
-	if(!normal_prediction.empty()) {
-		if(normal_prediction == "delta") prediction = 0;
-		else if(normal_prediction == "border") prediction = 2;
-		else if(normal_prediction == "estimated") prediction = 1;
-		else { std::cerr << "Unknown normal prediction: " << normal_prediction << " expecting: delta, border or estimated" << std::endl; return 1; }
-	}
+	if(!prediction_ok()) return 1;
 
 	// ---- encode (src/main.cpp:180-222) ----
 	crthip_mesh M;
-	memset(&M, 0, sizeof(M));
-	M.nvert = in.nvert; M.nface = in.nface;
-	M.position = in.coords.data();
-	M.index = pointcloud ? nullptr : in.index.data();
-	M.position_bits = vertex_bits; M.position_q = vertex_q;               // both 0: upstream's heuristic step
-	if(!in.norms.empty() && norm_bits > 0) { M.normal = in.norms.data(); M.normal_bits = norm_bits; M.normal_prediction = prediction; }
-	if(!in.colors.empty() && r_bits > 0) {
-		M.color = in.colors.data(); M.color_components = (int32_t)in.ncolor;
-		M.color_bits[0] = r_bits; M.color_bits[1] = g_bits; M.color_bits[2] = b_bits; M.color_bits[3] = a_bits;
-	}
-	if(!in.uvs.empty() && uv_bits > 0) { M.uv = in.uvs.data(); M.uv_q = (float)pow(2, -uv_bits); }
-	if(!in.radiuses.empty()) { M.radius = in.radiuses.data(); M.radius_q = 1.0f; }
-	M.group_end = &group_end; M.ngroups = 1;
-	M.entropy = CRTHIP_ENTROPY_TUNSTALL;
-	std::string ex;
-	for(auto &kv : exif) { ex += kv.first; ex.push_back('\0'); ex += kv.second; ex.push_back('\0'); }
-	M.exif = ex.data(); M.nexif = (uint32_t)exif.size();
+	uint32_t group_end = 0;
+	describe(in, o, group_end, ex, (uint32_t)exif.size(), M);
 	uint32_t nvert = 0, nface = 0;
 	const int64_t size = crthip_encode(&M, nullptr, 0, &nvert, &nface);
 	if(size < 0) { std::cerr << "Encoding failed: " << crthip_last_error() << std::endl; return 1; }
@@ -299,10 +362,5 @@ int main(int argc, char *argv[]) {
 
 	if(output.empty()) output = input.substr(0, input.find_last_of("."));
 	if(!ends_with(output, ".crt")) output += ".crt";
-	FILE *file = fopen(output.c_str(), "wb");
-	if(!file) { std::cerr << "Could not open file: " << output << std::endl; return 1; }
-	const size_t written = fwrite(blob, 1, (size_t)size, file);
-	fclose(file);
-	if(written != (size_t)size) { std::cerr << "Failed saving file: " << output << std::endl; return 1; }
-	return 0;
+	return write_file(output, blob, (size_t)size) ? 0 : 1;
 }

@@ -1,0 +1,73 @@
+"""crthip_encode_batch against the host encoder: one JSON record per workload.
+
+    python tools/encode_batch_rate.py [--out FILE] [--reps 3]
+
+For each workload: the batch call's wall time, its stats and per-kernel times (of the same run), beside crthip_encode on one
+host thread and on 16 (ctypes releases the GIL), crthip_encode_gpu mesh by mesh, and the reference encoder on one core when
+oracle/_ref is present; every leg is the best of --reps runs.  Every batch blob is checked against crthip_encode's bytes."""
+import argparse
+import json
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import corto_amd as ca  # noqa: E402
+from corto_amd import synth  # noqa: E402
+
+
+def workloads():
+    yield "256 x C4 unit", [synth.bumpy_sphere(64, 32, seed=s) for s in range(256)], dict(normal_prediction=ca.BORDER)
+    yield "64 x 16K-triangle", [synth.bumpy_sphere(128, 64, seed=s) for s in range(64)], dict(normal_prediction=ca.BORDER)
+    yield "16 x C2", [synth.bumpy_sphere(512, 250, seed=s) for s in range(16)], dict(normal_prediction=ca.BORDER)
+    yield "C3 cloud", [synth.point_cloud()], dict(normal_prediction=ca.BORDER)
+    yield "4M-point cloud", [synth.point_cloud(2048, 2048, seed=5)], dict(normal_prediction=ca.BORDER)
+
+
+def best(f, reps):
+    """the fastest of `reps` runs, and that run's result (its stats and kernel times belong to the time reported)"""
+    bt, br = None, None
+    for _ in range(reps):
+        t0 = time.perf_counter(); r = f(); t = (time.perf_counter() - t0) * 1e3
+        if bt is None or t < bt:
+            bt, br = t, r
+    return bt, br
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--reps", type=int, default=3)
+    a = ap.parse_args()
+    from oracle import refcodec as rc
+    ctx = ca.Context(0)
+    ctx.set_profiling(True)
+    ca.encode_batch([synth.bumpy_sphere(16, 8)], ctx)                       # warm the context and the kernels
+    recs = []
+    for name, meshes, kw in workloads():
+        ms, (blobs, st) = best(lambda: ca.encode_batch(meshes, ctx, kw=kw, with_stats=True), a.reps)
+        host1, ref = best(lambda: [ca.encode(m, **kw) for m in meshes], a.reps)
+        identical = all(b.tobytes() == r.tobytes() for b, r in zip(blobs, ref))
+        with ThreadPoolExecutor(16) as ex:
+            host16, _ = best(lambda: list(ex.map(lambda m: ca.encode(m, **kw), meshes)), a.reps)
+        gpu1, _ = best(lambda: [ca.encode(m, ctx=ctx, **kw) for m in meshes], a.reps)
+        rec = dict(workload=name, items=len(meshes), triangles=int(sum(m.nface for m in meshes)), vertices=int(sum(m.nvert for m in meshes)),
+                   batch_ms=round(ms, 3), host_1thread_ms=round(host1, 3), host_16threads_ms=round(host16, 3), encode_gpu_per_mesh_ms=round(gpu1, 3),
+                   identical=identical, stats={k: (round(v, 3) if isinstance(v, float) else v) for k, v in st.items() if k != "kernel_times"},
+                   kernel_times={k: dict(ms=round(v["ms"], 4), launches=v["launches"]) for k, v in st["kernel_times"].items()})
+        if rc.available():
+            rec["reference_1core_ms"] = round(best(lambda: [rc.encode(m, **kw) for m in meshes], a.reps)[0], 3)
+        print(json.dumps(rec), flush=True)
+        recs.append(rec)
+    if a.out:
+        with open(a.out, "w") as f:
+            for r in recs:
+                f.write(json.dumps(r) + "\n")
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
