@@ -76,8 +76,8 @@ template <typename T> struct HostArr {  // host image of a device array + where 
 
 struct AttrScratch {
 	// vals: int32 workspace of a generic attribute bound with a stride; facen: the fused normal kernel's face normals when not in LDS
-	uint64_t color = ~0ull, diffs = ~0ull, fired = ~0ull, vals = ~0ull, facen = ~0ull; std::vector<uint64_t> sym;
-	void reset() { color = diffs = fired = vals = facen = ~0ull; sym.clear(); }
+	uint64_t color = ~0ull, diffs = ~0ull, vals = ~0ull, facen = ~0ull; std::vector<uint64_t> sym;
+	void reset() { color = diffs = vals = facen = ~0ull; sym.clear(); }
 };
 struct BlobScratch {
 	uint64_t clers = ~0ull, pred = ~0ull, front_a = ~0ull, front_b = ~0ull, order = ~0ull, delayed = ~0ull, faces = ~0ull;
@@ -238,20 +238,15 @@ static int32_t f2i_x86_host(float x) {
 
 
 
-// launch classes of K-DELTA: 2 - values + prediction graph fit LDS, one wave per attribute (k_delta_lds16, k_delta.hip): as int16 relative
-// to
-// vertex 0, or - `wide`: a context that met values beyond int16 - as int32; else the stretch walk over HBM (k_delta_mesh): 0 = large, 1 =
-// small
-// (meshes beyond LDS, attributes of more than four components)
+// the two launch classes of K-DELTA (k_delta.hip): values + prediction graph fit LDS, one wave per attribute (k_delta_lds16) - as int16 relative to
+// vertex 0, or - `wide`: a context that met values beyond int16 - as int32; else tiles out of an LDS ring (k_delta_tiles: meshes beyond LDS,
+// attributes of more than four components)
 static inline bool delta_hosts_a(const DeltaJob &d) { return !d.is_u8 && d.N == 3; }
 static inline uint64_t delta_lds_need(const DeltaJob &d, bool wide) {          // alone in a workgroup; ~0: not eligible
 	if(d.nvert > DELTA16_NVERT_MAX || d.N < 1 || d.N > 4) return ~0ull;
 	return (uint64_t)delta_vbytes(d.nvert, d.N, d.is_u8 != 0, wide) + delta16_graph_lds(d.nvert, delta_hosts_a(d));
 }
-static inline int delta_class(const DeltaJob &d, bool wide) {
-	if(delta_lds_need(d, wide) <= DELTA16_LDS_MAX) return 2;
-	return d.nvert > DELTA_SMALL_NVERT ? 0 : 1;
-}
+static inline bool delta_in_lds(const DeltaJob &d, bool wide) { return delta_lds_need(d, wide) <= DELTA16_LDS_MAX; }
 static bool normal_fused(uint32_t nvert, uint32_t nface) { return nvert <= 32767 && (uint64_t)3*nface <= 65535 && normal_blob_lds(nvert,
 	nface) <= NORMAL_LDS_MAX; }
 

@@ -104,7 +104,7 @@ constexpr uint32_t UNPACK_WAVE_MAX_LOGS = 16384;   // bit blocks of at most this
 struct DeltaJob {
 	void *values;                  // int32* or uint8*, stride N
 	const uint32_t *pred;
-	uint8_t *fired;                // k_delta_mesh: nvert zeroed flags in HBM (+ the stretch starts behind them); k_delta_tiles: the automaton's progress word (TopoJob.progress) or null
+	uint8_t *progress;             // k_delta_tiles: the automaton's progress word (TopoJob.pad: TOPO_PAD_PROGRESS) or null
 	uint32_t nvert, N;
 	uint8_t parallelogram, is_u8, pad[2];   // pad[1]: k_delta_lds16 keeps 32-bit records in LDS (the whole group says the same); pad[0] (device): `values` holds the raw
 	                               // deltas as int16 (K-BIT's UnpackJob.out_u8 == 2), packed at the front of the buffer the results go to
@@ -113,6 +113,7 @@ struct DeltaJob {
 	                               // 2: colour: YCC -> RGB x qc into `out` (color_attribute.cpp:76-95)
 	float q;
 	uint32_t qc[4];
+	uint32_t first;                // k_delta_tiles: the first component of this job - 0, or a slice of four of an attribute of more (records of N)
 	void *out;                     // colour destination
 	uint32_t out_components, out_stride;
 	int32_t *flags;                // k_delta_lds16: set to 1 when the attribute's values relative to vertex 0 left int16 and were redone in HBM

@@ -753,8 +753,9 @@ __global__ __launch_bounds__(256) void k_delta_lds16(const DeltaJob *__restrict_
 
 
 // ------------------------------------------------------------------------------------------------------------------------------------------------
-// k_delta_tiles (round 6) - meshes too big for the LDS records above (tens of thousands to millions of vertices; rounds 1-5: k_delta_mesh, a walk
-// along the stretches of the prediction graph through L2, three round trips a vertex step: 1.5 of config C2's 4.0 ms).
+// k_delta_tiles (round 6) - every attribute beyond the LDS records above: meshes of tens of thousands to millions of vertices, and attributes of
+// more than four components on any mesh.  (Rounds 1-5 walked the stretches of the prediction graph through L2 instead, three round trips a vertex
+// step: 1.5 of config C2's 4.0 ms.)
 //
 // One workgroup of SIXTEEN waves per (blob, attribute), walking the vertex sequence in TILES of 1 024: thread t has vertex s + t.  What a vertex
 // reads is final data except for the parents inside its own tile, so a tile is the window loop above with a 1 024-wide window that does not slide:
@@ -769,21 +770,26 @@ __global__ __launch_bounds__(256) void k_delta_lds16(const DeltaJob *__restrict_
 //     part of the tile that predicts from the tile's own beginning); the lowest vertex that has not gone always can, so any graph terminates;
 //   * the next tile's triples and raw values are fetched while this one computes; the finished tile goes back to HBM in one coalesced store.
 // Exact as everything else here: sums in 32-bit registers mod 2^32 (bytes: stored mod 256).  A malformed triple (a parent that is not an earlier
-// vertex; vertex 0) leaves the value as it is, as k_delta_mesh does.  vertex_attribute.h:160-176.
+// vertex; vertex 0) leaves the value as it is.  vertex_attribute.h:160-176.
+// An attribute of more than four components is cut into SLICES of up to four (DeltaJob.first), one workgroup each: a component's recurrence reads
+// that component alone, so the slices share nothing but the triples and the progress word.  They store into the same cache lines, different
+// bytes - as neighbouring attributes' buffers always have (the L2 writes back the bytes that were written, not whole lines).
 constexpr uint32_t DT_RING = 4096;
-template <int NC, typename T>
+// STRIDED: a slice, `first` .. `first + NC` of a record of N components; else the whole record (N == NC, the stride a constant)
+template <int NC, typename T, bool STRIDED>
 __device__ __forceinline__ void delta_tiles_body(const DeltaJob &J, CRT_LDS uint32_t *ring, CRT_LDS uint64_t *fm, CRT_LDS uint32_t *gpub, CRT_LDS uint32_t *loc63) {
 	constexpr uint32_t NW = DELTA_THREADS/64;
 	const uint32_t nvert = J.nvert, t = threadIdx.x, lane = lane_id(), w = wave_id();
+	const uint32_t stride = STRIDED ? J.N : (uint32_t)NC;
 	const bool para = J.parallelogram != 0;
 	CRT_GLOBAL const uint32_t *pred = as_global(J.pred);
-	CRT_GLOBAL T *vals = as_global((T *)J.values);
+	CRT_GLOBAL T *vals = as_global((T *)J.values) + (STRIDED ? J.first : 0u);
 	CRT_LDS const uint32_t *fm32 = (CRT_LDS const uint32_t *)fm;
 	const uint64_t lane_le = (2ull << lane) - 1ull;
 	// The automaton may still be running (a lone context decodes the attribute streams beside it and launches this kernel on that second stream):
 	// it publishes how many vertices have their prediction triple - at every slide of its symbol window, 0xFFFFFFFF when it is done - and a tile
 	// waits for the triples it is about to load.  One thread polls; a wait that outlasts any decode (2 s) is given up rather than hung on.
-	CRT_GLOBAL const uint32_t *progress = as_global((const uint32_t *)J.fired);
+	CRT_GLOBAL const uint32_t *progress = as_global((const uint32_t *)J.progress);
 	uint32_t seen = progress ? 0u : 0xFFFFFFFFu;                               // what the word said when it was last looked at (uniform): polled again only when a tile needs more
 	auto wait_for = [&](uint32_t need) {
 		if(seen >= need) return;
@@ -804,16 +810,13 @@ __device__ __forceinline__ void delta_tiles_body(const DeltaJob &J, CRT_LDS uint
 		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 		lds_barrier();                                                         // (the word is read: the next poll may overwrite it)
 	};
-#ifdef DT_DEBUG
-	if(t == 0) printf("tiles job N %u nvert %u progress %p first %u\n", J.N, nvert, (const void *)J.fired, J.fired ? *(const uint32_t *)J.fired : 7u);
-#endif
 	typedef uint32_t u32x3_t __attribute__((ext_vector_type(3)));
 	auto load_pred = [&](uint32_t j) -> u32x3_t { return *(CRT_GLOBAL const u32x3_t *)(pred + (size_t)(j < nvert ? j : nvert - 1u)*3); };
 	wait_for(nvert < DELTA_THREADS ? nvert : DELTA_THREADS);
 	u32x3_t tri = load_pred(t);
 	uint32_t d[NC];
 #pragma unroll
-	for(int q = 0; q < NC; q++) d[q] = t < nvert ? (uint32_t)vals[(size_t)t*NC + q] : 0u;
+	for(int q = 0; q < NC; q++) d[q] = t < nvert ? (uint32_t)vals[(size_t)t*stride + q] : 0u;
 	for(uint32_t s = 0; s < nvert; s += DELTA_THREADS) {
 		const uint32_t i = s + t;
 		const bool in = i < nvert;
@@ -834,9 +837,9 @@ __device__ __forceinline__ void delta_tiles_body(const DeltaJob &J, CRT_LDS uint
 		uint32_t fa[NC], fb[NC], fc[NC];
 #pragma unroll
 		for(int q = 0; q < NC; q++) {
-			fa[q] = a_far ? (uint32_t)__hip_atomic_load(vals + (size_t)a*NC + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-			fb[q] = b_far ? (uint32_t)__hip_atomic_load(vals + (size_t)b*NC + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-			fc[q] = c_far ? (uint32_t)__hip_atomic_load(vals + (size_t)c*NC + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+			fa[q] = a_far ? (uint32_t)__hip_atomic_load(vals + (size_t)a*stride + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+			fb[q] = b_far ? (uint32_t)__hip_atomic_load(vals + (size_t)b*stride + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+			fc[q] = c_far ? (uint32_t)__hip_atomic_load(vals + (size_t)c*stride + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
 		}
 		asm volatile("" ::: "memory");
 		// the next tile's triple and raw values, in flight while this one computes
@@ -845,12 +848,9 @@ __device__ __forceinline__ void delta_tiles_body(const DeltaJob &J, CRT_LDS uint
 			const uint32_t j = i + DELTA_THREADS;
 			tri = load_pred(j);
 #pragma unroll
-			for(int q = 0; q < NC; q++) d[q] = j < nvert ? (uint32_t)vals[(size_t)j*NC + q] : 0u;
+			for(int q = 0; q < NC; q++) d[q] = j < nvert ? (uint32_t)vals[(size_t)j*stride + q] : 0u;
 		}
 		bool fired = !in;
-#ifdef DT_DEBUG
-		uint32_t npass = 0; const uint64_t dt0 = __builtin_amdgcn_s_memtime();
-#endif
 		{ const uint64_t m = __ballot(!in); if(lane == 0) fm[w] = m; }
 		uint32_t fin[NC];
 #pragma unroll
@@ -940,42 +940,42 @@ __device__ __forceinline__ void delta_tiles_body(const DeltaJob &J, CRT_LDS uint
 			}
 			if(lane == 0 && G) fm[w] |= G;
 			lds_barrier();
-#ifdef DT_DEBUG
-			npass++;
-#endif
 		}
-#ifdef DT_DEBUG
-		if(t == 0 && NC == 3 && (s < 4096 || (s & 16383) == 0)) printf("N %u tile %u passes %u clocks %u\n", J.N, s, npass, (uint32_t)(__builtin_amdgcn_s_memtime() - dt0));
-#endif
 		if(in) {
 #pragma unroll
-			for(int q = 0; q < NC; q++) vals[(size_t)i*NC + q] = (T)fin[q];
+			for(int q = 0; q < NC; q++) vals[(size_t)i*stride + q] = (T)fin[q];
 		}
 	}
 }
 
+// nc: the job's components (a slice's: those left, of which it takes four at most)
+template <typename T, bool STRIDED>
+__device__ __forceinline__ void delta_tiles_nc(uint32_t nc, const DeltaJob &J, CRT_LDS uint32_t *ring, CRT_LDS uint64_t *fm, CRT_LDS uint32_t *gpub, CRT_LDS uint32_t *loc63) {
+	switch(nc) {
+	case 1: delta_tiles_body<1, T, STRIDED>(J, ring, fm, gpub, loc63); break;
+	case 2: delta_tiles_body<2, T, STRIDED>(J, ring, fm, gpub, loc63); break;
+	case 3: delta_tiles_body<3, T, STRIDED>(J, ring, fm, gpub, loc63); break;
+	default: delta_tiles_body<4, T, STRIDED>(J, ring, fm, gpub, loc63); break;
+	}
+}
+
+// SLICES: the jobs of attributes of more than four components, a slice each (plan_group.cpp sorts them behind the others): a kernel of its own, so
+// that the whole-attribute kernel keeps its registers (71 VGPRs; with the strided bodies beside them, 78)
+template <bool SLICES>
 __global__ __launch_bounds__(DELTA_THREADS) void k_delta_tiles(const DeltaJob *__restrict__ jobs, uint32_t njobs) {
 	__shared__ uint32_t ring[4*DT_RING];                                       // 64 KB: the last DT_RING vertices' final values, a component an array
 	__shared__ uint64_t fm[DELTA_THREADS/64];                                   // the tile's vertices that have gone
 	__shared__ uint32_t gpub[2*(DELTA_THREADS/64) + 1], loc63[4*DELTA_THREADS/64];  // (gpub[NW]: the progress word as thread 0 last read it; behind it: the waves' open flags)
 	if(blockIdx.x >= njobs) return;
 	const DeltaJob J = jobs[blockIdx.x];
-	if(J.N < 1 || J.N > 4) return;                                              // (more components: k_delta_mesh, launched for those alone)
-	if(J.is_u8) {
-		switch(J.N) {
-		case 1: delta_tiles_body<1, uint8_t>(J, (CRT_LDS uint32_t *)ring, (CRT_LDS uint64_t *)fm, (CRT_LDS uint32_t *)gpub, (CRT_LDS uint32_t *)loc63); break;
-		case 2: delta_tiles_body<2, uint8_t>(J, (CRT_LDS uint32_t *)ring, (CRT_LDS uint64_t *)fm, (CRT_LDS uint32_t *)gpub, (CRT_LDS uint32_t *)loc63); break;
-		case 3: delta_tiles_body<3, uint8_t>(J, (CRT_LDS uint32_t *)ring, (CRT_LDS uint64_t *)fm, (CRT_LDS uint32_t *)gpub, (CRT_LDS uint32_t *)loc63); break;
-		default: delta_tiles_body<4, uint8_t>(J, (CRT_LDS uint32_t *)ring, (CRT_LDS uint64_t *)fm, (CRT_LDS uint32_t *)gpub, (CRT_LDS uint32_t *)loc63); break;
-		}
-	} else {
-		switch(J.N) {
-		case 1: delta_tiles_body<1, uint32_t>(J, (CRT_LDS uint32_t *)ring, (CRT_LDS uint64_t *)fm, (CRT_LDS uint32_t *)gpub, (CRT_LDS uint32_t *)loc63); break;
-		case 2: delta_tiles_body<2, uint32_t>(J, (CRT_LDS uint32_t *)ring, (CRT_LDS uint64_t *)fm, (CRT_LDS uint32_t *)gpub, (CRT_LDS uint32_t *)loc63); break;
-		case 3: delta_tiles_body<3, uint32_t>(J, (CRT_LDS uint32_t *)ring, (CRT_LDS uint64_t *)fm, (CRT_LDS uint32_t *)gpub, (CRT_LDS uint32_t *)loc63); break;
-		default: delta_tiles_body<4, uint32_t>(J, (CRT_LDS uint32_t *)ring, (CRT_LDS uint64_t *)fm, (CRT_LDS uint32_t *)gpub, (CRT_LDS uint32_t *)loc63); break;
-		}
-	}
+	if(J.N < 1 || (!SLICES && J.N > 4)) return;
+	CRT_LDS uint32_t *r = (CRT_LDS uint32_t *)ring, *g = (CRT_LDS uint32_t *)gpub, *l = (CRT_LDS uint32_t *)loc63;
+	CRT_LDS uint64_t *f = (CRT_LDS uint64_t *)fm;
+	if constexpr(SLICES) delta_tiles_nc<uint32_t, true>(J.N - J.first, J, r, f, g, l);   // (colours have at most four components)
+	else if(J.is_u8) delta_tiles_nc<uint8_t, false>(J.N, J, r, f, g, l);
+	else delta_tiles_nc<uint32_t, false>(J.N, J, r, f, g, l);
 }
+template __global__ void k_delta_tiles<false>(const DeltaJob *, uint32_t);
+template __global__ void k_delta_tiles<true>(const DeltaJob *, uint32_t);
 
 } // namespace corto_hip

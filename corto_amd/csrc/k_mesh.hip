@@ -1962,140 +1962,6 @@ __device__ __forceinline__ void topo_lds_kernel(const TopoJob *__restrict__ jobs
 __global__ __launch_bounds__(64) void k_topology_lds(const TopoJob *__restrict__ jobs, const uint32_t *__restrict__ job_ids, uint32_t njobs) { topo_lds_kernel<false>(jobs, job_ids, njobs); }
 __global__ __launch_bounds__(64) void k_topology_lds_big(const TopoJob *__restrict__ jobs, const uint32_t *__restrict__ job_ids, uint32_t njobs) { topo_lds_kernel<true>(jobs, job_ids, njobs); }
 
-// ------------------------------------------------------------------------------------------------
-// K-DELTA (mesh): v[i] += v[a] + v[b] - v[c] (or += v[a]) for i = 1..nvert-1 in index order
-// (vertex_attribute.h:165-176).  a, b, c < i, so the recurrence is a DAG; its depth is only ~3.5*sqrt(n)
-// (158 levels for the 2 112-vertex C4 unit), and it has a shape: in the breadth-first CLERS order nearly
-// every vertex predicts from the vertex made just before it (a = i-1) and two vertices one ring of the front back.
-// So the graph is a set of "stretches" - runs of consecutive vertices, each run a serial chain - skewed against each
-// other by two steps, and the parallelism is ACROSS stretches.  Both kernels below give each lane / thread whole
-// stretches to walk (k_delta_mesh, values in HBM); blobs whose values fit LDS take the window loop of k_delta.hip.
-
-// Attributes too big for LDS (meshes of tens of thousands of vertices, attributes of more than four components): a stretch walk over
-// HBM/L2 by one workgroup.  Thread k walks stretches k, k+T, ... in order and carries the value of the vertex it has just
-// finished in registers (a = i-1 inside a stretch), so the only waiting is for the two parents one ring back - which the
-// neighbouring stretch, two steps ahead, has normally published already.  Flags and values cross waves through L2 with
-// release/acquire at workgroup scope.  One loop, test-and-fire in the same iteration: a lane that spun in an inner wait
-// loop would keep the lanes it is waiting for (same wave) parked at the reconvergence point.
-template <typename T, int NC>
-__device__ void delta_stretch_global(CRT_GLOBAL T *v, CRT_GLOBAL uint8_t *fired, CRT_GLOBAL const uint32_t *starts, uint32_t ns,
-                                     CRT_GLOBAL const uint32_t *pred, uint32_t nvert, uint32_t Nrt, bool para, uint32_t THREADS) {
-	const uint32_t n = NC ? (uint32_t)NC : Nrt;
-	uint32_t k = threadIdx.x;
-	bool active = k < ns;
-	uint32_t i = 0, end = 0;
-	if(active) { i = starts[k]; end = k + 1 < ns ? starts[k + 1] : nvert; }
-	uint32_t a = 0, b = 0, c = 0, na = 0, nb = 0, nc = 0;
-	typedef uint32_t u32x3_t __attribute__((ext_vector_type(3)));
-	auto issue = [&](uint32_t j) -> u32x3_t {                              // the triple of vertex j as one 12-byte load (clamped: unconditional)
-		return *(CRT_GLOBAL const u32x3_t *)(pred + (size_t)(j < nvert ? j : nvert - 1u)*3);
-	};
-	auto take = [&](uint32_t j, u32x3_t t, uint32_t &x, uint32_t &y, uint32_t &z) {
-		asm volatile("" : "+v"(t));
-		x = j < nvert ? t.x : 0u; y = j < nvert ? (para ? t.y : t.x) : 0u; z = j < nvert ? (para ? t.z : t.x) : 0u;
-	};
-	if(active) { const u32x3_t t0 = issue(i), t1 = issue(i + 1); take(i, t0, a, b, c); take(i + 1, t1, na, nb, nc); }   // the next triple is always one vertex ahead of its use
-	T prev[NC ? NC : 1];
-	bool at_start = true, have2 = false;
-	u32x3_t t2 = {0, 0, 0};                                                // ... and the one behind it is in flight while this vertex waits for its parents and fires
-	while(active) {
-		if(!have2) { t2 = issue(i + 2); have2 = true; }
-		const bool inv = !(a < i && b < i && c < i);                        // malformed triple (and vertex 0): the value stays
-		const uint32_t da = inv || !at_start ? 0u : a, db = inv ? 0u : b, dc = inv ? 0u : c;
-		const uint32_t ready = __hip_atomic_load(&fired[da], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) &
-		                       __hip_atomic_load(&fired[db], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) &
-		                       __hip_atomic_load(&fired[dc], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-		if(ready) {
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-			if(NC) {
-				// every value of the step in flight together, then the sums, then the stores (component by component the store of one
-				// fenced in the loads of the next - v may alias itself - and a step was five L2 round trips instead of two)
-				uint32_t g[NC ? NC : 1][4];
-#pragma unroll
-				for(uint32_t q = 0; q < (uint32_t)NC; q++) {
-					g[q][0] = (uint32_t)v[(size_t)i*n + q]; g[q][1] = (uint32_t)v[(size_t)(inv || !at_start ? 0u : a)*n + q];
-					g[q][2] = (uint32_t)v[(size_t)(inv || !para ? 0u : b)*n + q]; g[q][3] = (uint32_t)v[(size_t)(inv || !para ? 0u : c)*n + q];
-				}
-#pragma unroll
-				for(uint32_t q = 0; q < (uint32_t)NC; q++) asm volatile("" : "+v"(g[q][0]), "+v"(g[q][1]), "+v"(g[q][2]), "+v"(g[q][3]));
-#pragma unroll
-				for(uint32_t q = 0; q < (uint32_t)NC; q++) {
-					T x = (T)g[q][0];
-					if(!inv) {
-						const T pa = at_start ? (T)g[q][1] : prev[q];
-						x = (T)(x + pa + (para ? (T)((T)g[q][2] - (T)g[q][3]) : (T)0));
-						v[(size_t)i*n + q] = x;
-					}
-					prev[q] = x;
-				}
-			} else if(!inv) {
-				for(uint32_t q = 0; q < n; q++)
-					v[(size_t)i*n + q] = (T)(v[(size_t)i*n + q] + v[(size_t)a*n + q] + (para ? (T)(v[(size_t)b*n + q] - v[(size_t)c*n + q]) : (T)0));
-			}
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-			__hip_atomic_store(&fired[i], (uint8_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-			i++; at_start = false;
-			a = na; b = nb; c = nc;
-			take(i + 1, t2, na, nb, nc); have2 = false;                        // (issued at the top of this or an earlier pass: back by now)
-			if(i == end) {
-				k += THREADS; active = k < ns;
-				if(active) {
-					i = starts[k]; end = k + 1 < ns ? starts[k + 1] : nvert;
-					const u32x3_t t0 = issue(i), t1 = issue(i + 1);
-					take(i, t0, a, b, c); take(i + 1, t1, na, nb, nc); at_start = true;
-				}
-			}
-		}
-		if(!__any(ready)) __builtin_amdgcn_s_sleep(2);                      // nothing to do in this wave: leave the issue slots to the waves that fire
-	}
-}
-
-__global__ __launch_bounds__(DELTA_THREADS) void k_delta_mesh(const DeltaJob *__restrict__ jobs, uint32_t njobs, uint32_t wide_n_only) {
-	if(blockIdx.x >= njobs) return;
-	const DeltaJob J = jobs[blockIdx.x];
-	if(wide_n_only && J.N <= 4) return;                                      // (k_delta_tiles' job)
-	const uint32_t THREADS = blockDim.x, nvert = J.nvert, t = threadIdx.x, lane = lane_id(), w = wave_id(), nwaves = THREADS >> 6;
-	CRT_GLOBAL const uint32_t *pred = as_global(J.pred);
-	CRT_GLOBAL uint8_t *fired = as_global(J.fired);                       // zero-filled by the host; the stretch starts live behind it
-	CRT_GLOBAL uint32_t *starts = (CRT_GLOBAL uint32_t *)(fired + ((nvert + 15u) & ~15u));
-	__shared__ uint32_t wcount[DELTA_THREADS/64];
-	// stretch starts: vertices that do not predict from the vertex right before them (ordered compaction, THREADS vertices a round)
-	uint32_t ns = 0;
-	for(uint32_t base = 0; base < nvert; base += THREADS) {
-		const uint32_t i = base + t;
-		bool start = false;
-		if(i < nvert) { const uint32_t a = pred[(size_t)i*3]; start = !(a < i && a + 1 == i); }
-		const uint64_t m = __ballot(start);
-		if(lane == 0) wcount[w] = __popcll(m);
-		__syncthreads();
-		uint32_t before = 0, total = 0;
-		for(uint32_t q = 0; q < nwaves; q++) { const uint32_t x = wcount[q]; total += x; if(q < w) before += x; }
-		if(start) starts[ns + before + __popcll(m & ((1ull << lane) - 1ull))] = i;
-		ns += total;
-		__syncthreads();
-	}
-	if(t == 0) __hip_atomic_store(&fired[0], (uint8_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-	__threadfence_block();
-	__syncthreads();
-	const bool para = J.parallelogram != 0;
-	if(J.is_u8) {
-		CRT_GLOBAL uint8_t *v = as_global((uint8_t *)J.values);
-		switch(J.N) {
-		case 3: delta_stretch_global<uint8_t, 3>(v, fired, starts, ns, pred, nvert, J.N, para, THREADS); break;
-		case 4: delta_stretch_global<uint8_t, 4>(v, fired, starts, ns, pred, nvert, J.N, para, THREADS); break;
-		default: delta_stretch_global<uint8_t, 0>(v, fired, starts, ns, pred, nvert, J.N, para, THREADS); break;
-		}
-	} else {
-		CRT_GLOBAL uint32_t *v = as_global((uint32_t *)J.values);
-		switch(J.N) {
-		case 1: delta_stretch_global<uint32_t, 1>(v, fired, starts, ns, pred, nvert, J.N, para, THREADS); break;
-		case 2: delta_stretch_global<uint32_t, 2>(v, fired, starts, ns, pred, nvert, J.N, para, THREADS); break;
-		case 3: delta_stretch_global<uint32_t, 3>(v, fired, starts, ns, pred, nvert, J.N, para, THREADS); break;
-		default: delta_stretch_global<uint32_t, 0>(v, fired, starts, ns, pred, nvert, J.N, para, THREADS); break;
-		}
-	}
-}
-
 } // namespace corto_hip
 
 #ifdef CORTO_TOPO_TIMES

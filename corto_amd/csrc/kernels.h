@@ -84,10 +84,11 @@ inline void topo_lds_geometry(uint32_t nface, uint32_t nclers, uint32_t ring_max
 	symwin = all < TOPO_SYMWIN_MAX ? all : TOPO_SYMWIN_MAX;
 }
 constexpr uint32_t TOPO_LDS_MAX = 156*1024;     // of the CU's 160 KiB
-constexpr uint32_t DELTA_THREADS = 1024, DELTA_SMALL_NVERT = 8192;      // threads of k_delta_mesh's workgroup for one (blob, attribute) too big for LDS; half of them up to DELTA_SMALL_NVERT vertices
-__global__ void k_delta_mesh(const DeltaJob *jobs, uint32_t njobs, uint32_t wide_n_only);       // wide_n_only: the jobs of more than four components alone (the others are k_delta_tiles')
-// k_delta.hip: the same jobs (up to four components) in tiles of DELTA_THREADS vertices out of an LDS ring of recent values (round 6)
-__global__ void k_delta_tiles(const DeltaJob *jobs, uint32_t njobs);
+// k_delta.hip: every K-DELTA job beyond the LDS records below - big meshes, attributes of more than four components - in tiles of DELTA_THREADS
+// vertices out of an LDS ring of recent values, one workgroup a job (round 6).  SLICES: the jobs of attributes of more than four components, a slice
+// of four each
+constexpr uint32_t DELTA_THREADS = 1024;
+template <bool SLICES> __global__ void k_delta_tiles(const DeltaJob *jobs, uint32_t njobs);
 constexpr uint32_t DELTA_GROUP_MAX = 4;
 struct DeltaGroup { uint32_t first, count; };     // DeltaJob entries [first, first + count) of one blob
 // k_delta.hip: one workgroup per blob, one wave per attribute (up to four) + one that builds the prediction graph they share: 16-bit values

@@ -31,11 +31,12 @@ int Planner::carve() {
 	}
 	// zeroed by a memset, present only for big meshes: the counters of the
 	pl.zero_begin = cv.take(0);
-	pl.est_nvert = (uint32_t)est_v; pl.est_nface = (uint32_t)est_f;      // unfused normal pipeline and the fired flags of k_delta_mesh
+	pl.est_nvert = (uint32_t)est_v; pl.est_nface = (uint32_t)est_f;      // unfused normal pipeline
 	if(est_v) {
 		pl.cnt_off = cv.take(est_v*4 + 16); pl.cursor_off = cv.take(est_v*4 + 16); pl.bnd_off = cv.take(est_v*4 + 16);
 	}
-	for(uint32_t i = 0; i < nblobs; i++) {                           // "fired" flags of delta jobs too large for LDS
+	pl.zero_end = cv.take(0);
+	for(uint32_t i = 0; i < nblobs; i++) {                           // k_delta_tiles: one progress word a blob, kept by the automaton
 		const BlobPlan &P = b->blobs[i];
 		const BlobLayout &L = P.L;
 		bs[i].set_attrs(L.attrs.size());
@@ -45,16 +46,9 @@ int Planner::carve() {
 			const AttrHeader &a = L.h.attrs[k];
 			DeltaJob probe{};
 			probe.nvert = L.h.nvert; probe.N = a.codec == CRTHIP_CODEC_NORMAL ? 2u : a.N; probe.is_u8 = a.codec == CRTHIP_CODEC_COLOR;
-			if(delta_class(probe, wide) <= 1) {
-				// k_delta_tiles: one progress word a blob, kept by the automaton; k_delta_mesh (more than four components, or $CORTO_DELTA_WALK): fired
-				// flags (zeroed) + the list of stretch starts behind them
-				bs[i].progress = bs[i].pred - TOPO_PROGRESS_BYTES;           // (zeroed on its own: Planner::upload)
-				if(ctx->dbg.delta_walk || probe.N > 4)
-					bs[i].attr[k].fired = cv.take((((uint64_t)L.h.nvert + 15) & ~15ull) + 4ull*L.h.nvert + 16, 16);
-			}
+			if(!delta_in_lds(probe, wide)) bs[i].progress = bs[i].pred - TOPO_PROGRESS_BYTES;   // (zeroed on its own: Planner::upload)
 		}
 	}
-	pl.zero_end = cv.take(0);
 	// look-back state words of the bit-unpack chunks (k_unpack_extract): one per
 	unpack_state_words = 1;
 	// 1 024 logs of every bound stream, + a spare; uploaded as zeros with the jobs

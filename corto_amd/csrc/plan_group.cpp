@@ -73,14 +73,12 @@ void Planner::group() {
 	place(pl.tun); place(pl.tun_dict); place(pl.tun_chunk_stream); place(pl.tun_group_ids); place(pl.tun_groups); place(pl.fill);
 		place(pl.topo); place(pl.aux_u32); place(pl.topo_lds_ids); place(pl.topo_big_ids); place(pl.topo_glob_ids); place(pl.unpack);
 		place(pl.unpack_chunk_job); place(pl.unpack_wave_ids);
-	// large attributes first: they are launched with four times the threads of the small ones (k_delta_mesh)
-	std::stable_partition(pl.delta.v.begin(), pl.delta.v.end(), [wide_ = wide](const DeltaJob &d) { return delta_class(d, wide_) == 0; });
-	std::stable_partition(pl.delta.v.begin(), pl.delta.v.end(), [wide_ = wide](const DeltaJob &d) { return delta_class(d, wide_) <= 1; });
-	// attributes of one blob that fit LDS together share a workgroup and the prediction graph: consecutive jobs of class 2 with the same
+	// the jobs of k_delta_tiles first - whole attributes, then the slices of those of more than four components (a launch each); then attributes of
+	// one blob that fit LDS together share a workgroup and the prediction graph: consecutive jobs with the same prediction array, up to DELTA_GROUP_MAX
 	{
-		// prediction array, up to DELTA_GROUP_MAX
-		size_t j = 0;
-		while(j < pl.delta.v.size() && delta_class(pl.delta.v[j], wide) < 2) j++;
+		const auto lds_begin = std::stable_partition(pl.delta.v.begin(), pl.delta.v.end(), [wide_ = wide](const DeltaJob &d) { return !delta_in_lds(d, wide_); });
+		std::stable_partition(pl.delta.v.begin(), lds_begin, [](const DeltaJob &d) { return d.N <= 4; });
+		size_t j = (size_t)(lds_begin - pl.delta.v.begin());
 		while(j < pl.delta.v.size()) {
 			const DeltaJob &d0 = pl.delta.v[j];
 			DeltaGroup g{(uint32_t)j, 1};

@@ -181,7 +181,7 @@ int Planner::jobs() {
 				else if(a.codec != CRTHIP_CODEC_COLOR && !bd.stream_values) {
 					DeltaJob probe{};
 					probe.nvert = nvert; probe.N = a.N;
-					hand_i16 = delta_class(probe, wide) >= 2;
+					hand_i16 = delta_in_lds(probe, wide);
 					if(a.strategy & CRTHIP_CORRELATED) hand_i16 = hand_i16 && widths_fit(as.logs[0], 16);
 					else for(uint32_t c = 0; c < a.N && hand_i16; c++) hand_i16 = widths_fit(as.logs[c], 15);
 				}
@@ -227,11 +227,10 @@ int Planner::jobs() {
 					// pad[1]: 32-bit records in LDS (k_delta_lds16)
 					d.parallelogram = para; d.is_u8 = is_u8; d.pad[0] = (uint8_t)((values_real ? 1 : 0) | (hand_i16 ? 2 : 0)); d.pad[1] = wide; d.pad2[0] = ctx->dbg.delta_rounds ?
 						1u : 0u;                                                // (pad[0] bit 0: `values` is a real pointer - host only; bit 1: int16 raw deltas - what the device sees)
-					// (k_delta_mesh's flags, else - k_delta_tiles - the automaton's progress word)
-					d.fired = A.fired != ~0ull ? SP(A.fired) : S.progress != ~0ull ? SP(S.progress) : nullptr;
+					d.progress = S.progress != ~0ull ? SP(S.progress) : nullptr;   // (k_delta_tiles)
 					d.flags = HS(2ull*nblobs + 2ull*i);
 					d.pad2[1] = 2u*nblobs + i;                              // (words from the blob's status to its flags: k_delta_tiles reports a progress word that never came)
-					if(a.codec != CRTHIP_CODEC_NORMAL && delta_class(d, wide) >= 2) {
+					if(a.codec != CRTHIP_CODEC_NORMAL && delta_in_lds(d, wide)) {
 						if(a.codec == CRTHIP_CODEC_COLOR) {
 							d.deq = 2; d.out = bd.buffer; d.out_components = bd.out_components; d.out_stride = bd.stride;
 							for(int c = 0; c < 4; c++) d.qc[c] = as.qc[c];
@@ -239,7 +238,7 @@ int Planner::jobs() {
 						} else if(!bd.stride && bd.format == CRTHIP_FMT_FLOAT && !((int)k == pos_k && pos_ints_needed)) { d.deq = 1; d.q =
 							a.q; dequantised = true; }
 					}
-					pl.delta.v.push_back(d);
+					for(uint32_t f = 0; f < N; f += 4) { d.first = f; pl.delta.v.push_back(d); }   // more than four components: k_delta_tiles jobs of four
 				} else {
 					CloudJob c{};
 					c.values = values; c.nvert = nvert; c.N = N; c.chunk0 = cloud_chunks; c.is_u8 = is_u8; c.pad[0] = values_real;

@@ -32,7 +32,7 @@ int Planner::upload() {
 		u.out_u8 &= 0x7F;
 	}
 	for(auto &d : pl.delta.v) { if(!(d.pad[0] & 1)) d.values = R(d.values); d.pad[0] >>= 1; d.pred = (const uint32_t *)R(d.pred);
-		if(d.fired) d.fired = R(d.fired); d.flags = (int32_t *)R(d.flags); }
+		if(d.progress) d.progress = R(d.progress); d.flags = (int32_t *)R(d.flags); }
 	for(auto &c : pl.cloud.v) { if(!c.pad[0]) c.values = R(c.values); c.pad[0] = 0; }
 	for(auto &n : pl.normal.v) {
 		n.diffs = (int32_t *)R(n.diffs); n.status = (int32_t *)R(n.status);
@@ -113,22 +113,25 @@ int Planner::launch() {
 		LT.begin("unpack_extract", s); hipLaunchKernelGGL(k_unpack_extract, dim3(unpack_chunks), dim3(256), 0, s, D(pl.unpack),
 			D(pl.unpack_chunk_job), unpack_chunks, unpack_partial); LT.end();
 	};
-	// K-DELTA's jobs by class (sorted that way: 0 / 1 = too big for the LDS records, 2 = the groups of k_delta_lds16)
-	uint32_t ncls[3] = {0, 0, 0};
-	for(auto &d : pl.delta.v) ncls[delta_class(d, wide)]++;
+	// K-DELTA's jobs too big for the LDS records (sorted to the front; behind them the groups of k_delta_lds16)
+	uint32_t nbig = 0, nslices = 0;                                              // (the slices: the last nslices of the nbig)
+	for(auto &d : pl.delta.v) if(!delta_in_lds(d, wide)) { nbig++; nslices += d.N > 4 ? 1u : 0u; }
 	bool tiles_launched = false;
 	// the big ones in tiles of 1 024 vertices (k_delta_tiles).  On a lone context this goes to the SECOND stream, behind the attribute streams' bit-unpack
 	// and BESIDE the automaton, whose progress word the tiles wait for: a single big mesh's delta inversion trails its topology instead of following it
 	// (config C2: 1.5 of 4.0 ms).  The automaton is enqueued first on its own stream and waits for nothing of this kernel.
 	// BESIDE the automaton only a handful of workgroups: they hold 66 KB of LDS each while they wait, and a batch of hundreds of big meshes' tiles, resident
 	// first, could keep the automata (up to 156 KB a workgroup) from ever finding a CU - the tiles would wait for a progress word nobody can write.  Up to 48
-	// (sixteen big meshes' three attributes) leave most of the chip free; more run behind the automaton as on a pool context.
+	// (sixteen big meshes' three attributes; a slice of an attribute of more than four components counts as one) leave most of the chip free; more run
+	// behind the automaton as on a pool context.
 	constexpr uint32_t TILES_BESIDE_MAX = 48;
 	auto delta_tiles = [&](hipStream_t s) {
-		const uint32_t nbig = ncls[0] + ncls[1];
-		if(!nbig || ctx->dbg.delta_walk) return;
+		if(!nbig) return;
 		if(s != st && nbig > TILES_BESIDE_MAX) return;
-		LT.begin("delta_tiles", s); hipLaunchKernelGGL(k_delta_tiles, dim3(nbig), dim3(DELTA_THREADS), 0, s, D(pl.delta), nbig); LT.end();
+		LT.begin("delta_tiles", s);
+		if(nbig > nslices) hipLaunchKernelGGL(k_delta_tiles<false>, dim3(nbig - nslices), dim3(DELTA_THREADS), 0, s, D(pl.delta), nbig - nslices);
+		if(nslices) hipLaunchKernelGGL(k_delta_tiles<true>, dim3(nslices), dim3(DELTA_THREADS), 0, s, D(pl.delta) + (nbig - nslices), nslices);
+		LT.end();
 		tiles_launched = true;
 	};
 	auto topology = [&]() -> int {
@@ -162,7 +165,7 @@ int Planner::launch() {
 		if(launch_tun_decode_staged(st, D(pl.tun), D(pl.tun_chunk_stream), tun_chunks, tables, tun_partial, scanned ? 0u : 1u)) return fail(CRTHIP_E_DEVICE);
 		LT.end();
 		if(nfill) { LT.begin("fill"); hipLaunchKernelGGL(k_fill, dim3(nfill), dim3(256), 0, st, D(pl.fill), nfill); LT.end(); }
-		if(!ctx->single_stream && !ctx->dbg.delta_walk && ncls[0] + ncls[1] && ncls[0] + ncls[1] <= TILES_BESIDE_MAX && !pl.topo.v.empty()) {
+		if(!ctx->single_stream && nbig && nbig <= TILES_BESIDE_MAX && !pl.topo.v.empty()) {
 			// a big mesh alone: every stream is decoded; the automaton (one serial chain: 2.2 of C2's 4 ms) goes on on the main stream, the attributes'
 			// bit-unpack and their delta inversion in tiles on the second one, the tiles trailing the automaton's progress word
 			hipStream_t s2 = ctx->stream2;
@@ -197,22 +200,7 @@ int Planner::launch() {
 	}
 	if(!pl.delta.v.empty()) {
 		const uint32_t ngroups = (uint32_t)pl.delta_groups.v.size();
-		// (the timer's names are the kernels that run: `delta_mesh` = the walk over HBM, `delta_lds16` = the LDS form, one workgroup a blob)
-		if(ncls[0] || ncls[1]) {
-			// too big for the LDS records: tiles of 1 024 vertices out of an LDS ring (k_delta_tiles, up to four components); rounds 1-5's stretch walk
-			// over L2 for attributes of more components, and for everything under $CORTO_DELTA_WALK=1
-			const uint32_t nbig = ncls[0] + ncls[1];
-			bool many = false;
-			for(uint32_t k = 0; k < nbig; k++) many = many || pl.delta.v[k].N > 4;
-			if(!ctx->dbg.delta_walk && !tiles_launched) delta_tiles(st);
-			if(ctx->dbg.delta_walk || many) {
-				LT.begin("delta_mesh");
-				const uint32_t only = ctx->dbg.delta_walk ? 0u : 1u;
-				if(ncls[0]) hipLaunchKernelGGL(k_delta_mesh, dim3(ncls[0]), dim3(DELTA_THREADS), 0, st, D(pl.delta), ncls[0], only);
-				if(ncls[1]) hipLaunchKernelGGL(k_delta_mesh, dim3(ncls[1]), dim3(DELTA_THREADS/2), 0, st, D(pl.delta) + ncls[0], ncls[1], only);
-				LT.end();
-			}
-		}
+		if(!tiles_launched) delta_tiles(st);                    // (too big for the LDS records, and not launched beside the automaton above)
 		if(ngroups) { LT.begin("delta_lds16"); hipLaunchKernelGGL(k_delta_lds16, dim3(ngroups), dim3(256), pl.delta16_lds, st, D(pl.delta), D(pl.delta_groups),
 			ngroups); LT.end(); }
 	}

@@ -46,6 +46,11 @@ typedef struct {
 	uint32_t nexif;
 	const uint32_t *group_nprops; // pairs per group, or NULL: Encoder::addGroup(end, props) (include/corto/encoder.h:75)
 	const char *group_props;      // all pairs of all groups, "k\0v\0..."
+	const char *extra_name;       // one more generic FLOAT attribute (Encoder::addAttribute, include/corto/encoder.h:70), or NULL
+	const float *extra;           // nvert*extra_N
+	int32_t extra_N;
+	float extra_q;
+	uint32_t extra_strategy;      // VertexAttribute::Strategy bits: PARALLEL 1, CORRELATED 2
 } ref_mesh_t;
 
 typedef struct {
@@ -106,6 +111,8 @@ int64_t ref_encode(const ref_mesh_t *m, uint8_t *out, int64_t cap, uint32_t *out
 			enc.addUvs(m->uv, m->uv_q);
 		if(m->radius)
 			enc.addAttribute("radius", (const char *)m->radius, VertexAttribute::FLOAT, 1, m->radius_q);
+		if(m->extra_name && m->extra)
+			enc.addAttribute(m->extra_name, (const char *)m->extra, VertexAttribute::FLOAT, m->extra_N, m->extra_q, m->extra_strategy);
 		enc.encode();
 		if(out_nvert) *out_nvert = enc.nvert;
 		if(out_nface) *out_nface = enc.nface;

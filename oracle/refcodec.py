@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "_ref", "libcorto_ref.so")
 
 FLOAT, INT16 = 6, 3          # VertexAttribute::Format (include/corto/vertex_attribute.h:32)
 DIFF, ESTIMATED, BORDER = 0, 1, 2   # NormalAttr::Prediction (include/corto/normal_attribute.h:40-42)
+PARALLEL, CORRELATED = 1, 2         # VertexAttribute::Strategy (include/corto/vertex_attribute.h:33)
 
 
 class _Mesh(C.Structure):
@@ -30,6 +31,7 @@ class _Mesh(C.Structure):
         ("entropy", C.c_int32),
         ("exif", C.c_char_p), ("nexif", C.c_uint32),
         ("group_nprops", C.c_void_p), ("group_props", C.c_char_p),
+        ("extra_name", C.c_char_p), ("extra", C.c_void_p), ("extra_N", C.c_int32), ("extra_q", C.c_float), ("extra_strategy", C.c_uint32),
     ]
 
 
@@ -66,8 +68,9 @@ def _ptr(a):
 
 def encode(mesh, position_bits=14, position_q=0.0, normal_bits=10, normal_prediction=BORDER,
            color_bits=(6, 7, 6, 5), uv_bits=12, radius_q=1.0, entropy=1, exif=None,
-           with_normal=True, with_color=True, with_uv=True) -> np.ndarray:
-    """Reference crt::Encoder -> .crt bytes (uint8 array, 4-byte aligned base)."""
+           with_normal=True, with_color=True, with_uv=True, extra=None) -> np.ndarray:
+    """Reference crt::Encoder -> .crt bytes (uint8 array, 4-byte aligned base).  extra: (name, float32 values (nvert, N), q, strategy) - one more
+    generic attribute, Encoder::addAttribute(name, values, FLOAT, N, q, strategy)."""
     m = _Mesh()
     m.nvert, m.nface = mesh.nvert, mesh.nface
     keep = [mesh.position]
@@ -92,6 +95,11 @@ def encode(mesh, position_bits=14, position_q=0.0, normal_bits=10, normal_predic
             cnt = np.array([len(d) for d in props], dtype=np.uint32); keep.append(cnt)
             gflat = b"".join(k.encode() + b"\0" + v.encode() + b"\0" for d in props for k, v in d.items())
             m.group_nprops = _ptr(cnt); m.group_props = gflat
+    if extra is not None:
+        name, vals, q, strategy = extra
+        vals = np.ascontiguousarray(vals, dtype=np.float32); keep.append(vals)
+        assert vals.shape[0] == mesh.nvert, vals.shape
+        m.extra_name = name.encode(); m.extra = _ptr(vals); m.extra_N = vals.shape[1]; m.extra_q = q; m.extra_strategy = strategy
     m.entropy = entropy
     if exif:
         flat = b"".join(k.encode() + b"\0" + v.encode() + b"\0" for k, v in exif.items())

@@ -123,6 +123,8 @@ def main():
             tunstall_kat()
         if "nonlattice_blobs8" in only:
             nonlattice_blobs()
+        if "generic_wide" in only:
+            generic_wide()
         return
     # mid-size mesh (C1-class, 34 060 verts / 67 600 tris): blob + digests only
     m = synth.bumpy_sphere(260, 130, seed=34)
@@ -149,8 +151,48 @@ def main():
     print("c4_blobs16           %d blobs" % 16)
 
     nonlattice_blobs()
+    generic_wide()
     tunstall_kat()
     delaunay_store()
+
+
+def generic_wide_meshes():
+    """generic attributes of more than four components (Encoder::addAttribute(name, values, FLOAT, N, q, strategy)): (name, mesh, N, strategy, big) -
+    a C4-unit mesh (9 components), two shuffled 45K-vertex meshes (6, first-neighbour; 5, parallelogram) and a point cloud (6)"""
+    return [("small9", synth.bumpy_sphere(64, 32, seed=21), 9, rc.CORRELATED | rc.PARALLEL, False),
+            ("big6", synth.shuffled(synth.bumpy_sphere_flipped(300, 150, seed=22, flip=0.3), seed=23), 6, 0, True),
+            ("big5", synth.shuffled(synth.bumpy_sphere_flipped(300, 150, seed=24, flip=0.3), seed=25), 5, rc.PARALLEL, True),
+            ("cloud6", synth.point_cloud(40, 30, seed=26), 6, rc.CORRELATED, False)]
+
+
+def wide_values(position: np.ndarray, n: int, seed: int) -> np.ndarray:
+    """n smooth float32 components a vertex: sines of random planes through the positions"""
+    rng = np.random.default_rng(seed)
+    d = rng.normal(size=(3, n)); ph = rng.uniform(0, 6.3, n); amp = rng.uniform(0.5, 2.0, n)
+    return (amp * np.sin(position.astype(np.float64) @ d * 3.0 + ph)).astype(np.float32)
+
+
+def generic_wide():
+    """generic_wide.npz: per case the blob, the attribute's float values as the reference decoded them (Decoder::setAttribute(name, buffer, FLOAT)) and the
+    usual arrays - in full for the small ones, SHA-256 digests for the big meshes (which carry no normals, colours or uvs)"""
+    d = {}
+    names = []
+    for k, (name, m, n, strategy, big) in enumerate(generic_wide_meshes()):
+        blob = rc.encode(m, position_bits=10 if big else 14, normal_prediction=rc.BORDER, with_normal=not big, with_color=not big, with_uv=not big,
+                         extra=("wide", wide_values(m.position, n, 40 + k), 1.0 / 64, strategy))
+        ref = rc.decode(blob)
+        ref["wide"] = rc.decode_attr_format(blob, "wide", rc.FLOAT, n)[:ref["nvert"] * n * 4].view(np.float32).reshape(-1, n).copy()
+        d["crt_" + name] = np.asarray(blob).copy()
+        for key, v in ref.items():
+            if isinstance(v, np.ndarray):
+                if big:
+                    d["%s.%s_sha256" % (name, key)] = np.frombuffer(sha(v).encode(), dtype=np.uint8)
+                else:
+                    d["%s.%s" % (name, key)] = v
+        names.append(name)
+        print("generic_wide %-7s crt %7d B  nvert %6d nface %6d  N %d strategy %d" % (name, len(blob), ref["nvert"], ref["nface"], n, strategy))
+    d["names"] = np.frombuffer(",".join(names).encode(), dtype=np.uint8)
+    np.savez_compressed(os.path.join(OUT, "generic_wide.npz"), **d)
 
 
 def delaunay_store():

@@ -1458,7 +1458,7 @@ def test_large_and_small_meshes_in_one_batch(ctx):
 
 def test_wide_context_on_meshes_beyond_the_lds_records(monkeypatch):
     """ADVICE r4: with 32-bit records (a context that met values beyond int16, or $CORTO_DELTA_WIDE=1) K-DELTA keeps meshes of up to 32 767 vertices in LDS;
-    33K-66K vertices (16-bit ids would still do) and positions quantised to 18 bits take the stretch walk over HBM (k_delta_mesh).  A performance trade-off,
+    33K-66K vertices (16-bit ids would still do) and positions quantised to 18 bits take the tiles out of an LDS ring (k_delta_tiles).  A performance trade-off,
     not a correctness one: the same bytes as the oracle on both sides of the limit, narrow and wide, rounds forced or not"""
     from corto_amd import synth
     meshes = [synth.bumpy_sphere(260, 128, seed=41), synth.bumpy_sphere(250, 130, seed=42), synth.delaunay_disc(2310, seed=43, holes=5),
@@ -1479,15 +1479,12 @@ def test_wide_context_on_meshes_beyond_the_lds_records(monkeypatch):
         c.close()
 
 
-@pytest.mark.parametrize("env", [{}, {"CORTO_DELTA_WALK": "1"}])
-def test_big_meshes_through_the_delta_tiles(monkeypatch, env):
-    """Attributes too big for K-DELTA's LDS records go through k_delta_tiles (tiles of 1 024 vertices out of an LDS ring of the last 4 096 values;
-    $CORTO_DELTA_WALK=1: rounds 1-5's stretch walk over L2): a 45K-vertex mesh with SHUFFLED vertex ids (parents anywhere: behind the ring, inside the
+def test_big_meshes_through_the_delta_tiles():
+    """Attributes too big for K-DELTA's LDS records go through k_delta_tiles (tiles of 1 024 vertices out of an LDS ring of the last 4 096 values):
+    a 45K-vertex mesh with SHUFFLED vertex ids (parents anywhere: behind the ring, inside the
     tile, one back - every pass pattern), flipped diagonals, a torus, 18-bit positions, rgb colours, several groups - on a lone context (the tiles run on
     the second stream BESIDE the automaton and wait for its progress word) and on a single-stream one (behind it); plus one of each in ONE batch"""
     from corto_amd import synth
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
     meshes = [synth.shuffled(synth.bumpy_sphere_flipped(300, 150, seed=5, flip=0.3), seed=9),
               synth.bumpy_sphere_flipped(260, 140, seed=6, color_components=3),
               synth.torus(220, 160, seed=7),
@@ -1502,20 +1499,52 @@ def test_big_meshes_through_the_delta_tiles(monkeypatch, env):
             c.set_single_stream(True)
         for i, x in enumerate(blobs):
             b = run_batch(c, [x], color_components=4)
-            assert_same(b.host_outputs(0), refs[i], KEYS, "big mesh %d single=%s env %s" % (i, single, env))
+            assert_same(b.host_outputs(0), refs[i], KEYS, "big mesh %d single=%s" % (i, single))
             b.close()
         b = run_batch(c, blobs, color_components=4)
         for i, r in enumerate(refs):
-            assert_same(b.host_outputs(i), r, KEYS, "big meshes in one batch: %d single=%s env %s" % (i, single, env))
+            assert_same(b.host_outputs(i), r, KEYS, "big meshes in one batch: %d single=%s" % (i, single))
         b.close()
-        if not env:
-            # eighteen big meshes at once: more tile workgroups (54) than may wait BESIDE the automata (48: they hold 66 KB of LDS each and the automata of
-            # big meshes ask for up to 156 KB) - these run behind them, and sixteen (48) beside them
-            for n in (18, 16):
-                b = run_batch(c, [blobs[1], blobs[2]] * (n // 2), color_components=4)
-                for i in range(n):
-                    assert_same(b.host_outputs(i), refs[1 + (i & 1)], KEYS, "%d big meshes in one batch: %d single=%s" % (n, i, single))
-                b.close()
+        # eighteen big meshes at once: more tile workgroups (54) than may wait BESIDE the automata (48: they hold 66 KB of LDS each and the automata of
+        # big meshes ask for up to 156 KB) - these run behind them, and sixteen (48) beside them
+        for n in (18, 16):
+            b = run_batch(c, [blobs[1], blobs[2]] * (n // 2), color_components=4)
+            for i in range(n):
+                assert_same(b.host_outputs(i), refs[1 + (i & 1)], KEYS, "%d big meshes in one batch: %d single=%s" % (n, i, single))
+            b.close()
+        c.close()
+
+
+def test_generic_attributes_of_more_than_four_components():
+    """generic attributes of more than four components (tests/golden/generic_wide.npz, made by the reference): a C4-unit mesh with nine
+    (parallelogram, correlated), two shuffled 45K-vertex meshes with six (first neighbour) and five (parallelogram), a point cloud with six - each
+    blob alone on a lone context (the tiles beside the automaton) and on a single-stream one, then all of them in one batch with a C4 blob"""
+    z = np.load(os.path.join(GOLDEN, "generic_wide.npz"))
+    names = z["names"].tobytes().decode().split(",")
+    blobs = [aligned(z["crt_" + n]) for n in names]
+    c4 = load_golden("c4_unit")
+
+    def check(got, name, tag):
+        for k in KEYS + ("wide",):
+            if "%s.%s" % (name, k) in z.files:
+                assert got[k].tobytes() == z["%s.%s" % (name, k)].tobytes(), (tag, name, k)
+            elif "%s.%s_sha256" % (name, k) in z.files:
+                assert sha(got[k]) == z["%s.%s_sha256" % (name, k)].tobytes().decode(), (tag, name, k)
+            else:
+                assert k not in got, (tag, name, k)
+    for single in (False, True):
+        c = ca.Context(0)
+        if single:
+            c.set_single_stream(True)
+        for n, x in zip(names, blobs):
+            b = run_batch(c, [x])
+            check(b.host_outputs(0), n, "alone single=%s" % single)
+            b.close()
+        b = run_batch(c, blobs + [c4["crt"]])
+        for i, n in enumerate(names):
+            check(b.host_outputs(i), n, "one batch single=%s" % single)
+        assert_same(b.host_outputs(len(names)), c4, KEYS, "C4 blob beside them single=%s" % single)
+        b.close()
         c.close()
 
 
