@@ -29,6 +29,8 @@ struct DebugConfig {
 	                                // width <= 16 bits and the consumer is k_delta_lds16 / k_normal_blob: plan_jobs.cpp)
 	bool unpack_chunked = false;    // $CORTO_UNPACK_CHUNKED=1 (test hook): every bit block through the chunked K-BIT with its look-back - the kernel of big meshes -
 	                                // however small (tests/test_gpu_parity.py runs ragged sizes through both)
+	bool front_off = false;         // $CORTO_FRONT=0 (A/B and test hook): a single-stream context launches the automata and K-BIT as two kernels, one after the
+	                                // other, instead of k_front's one grid (plan_launch.cpp)
 };
 
 inline DebugConfig debug_config_from_env() {
@@ -40,6 +42,7 @@ inline DebugConfig debug_config_from_env() {
 	c.unpack_chunked = on("CORTO_UNPACK_CHUNKED");
 	c.delta_rounds = on("CORTO_DELTA_ROUNDS");
 	c.values_i32 = on("CORTO_VALUES_I32");
+	{ const char *e = getenv("CORTO_FRONT"); c.front_off = e && e[0] == '0'; }
 	return c;
 }
 

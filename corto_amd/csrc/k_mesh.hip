@@ -6,6 +6,7 @@
 // wave per blob; many blobs per launch.
 #include "kernels_common.h"
 #include "kernels.h"
+#include "unpack_wave.h"
 
 namespace corto_hip {
 
@@ -1961,6 +1962,18 @@ __device__ __forceinline__ void topo_lds_kernel(const TopoJob *__restrict__ jobs
 // has the word, so the kernel needs no test); a kernel of its own because the test, or even a TopoJob eight bytes longer, cost the batch's automata 2-3 %.
 __global__ __launch_bounds__(64) void k_topology_lds(const TopoJob *__restrict__ jobs, const uint32_t *__restrict__ job_ids, uint32_t njobs) { topo_lds_kernel<false>(jobs, job_ids, njobs); }
 __global__ __launch_bounds__(64) void k_topology_lds_big(const TopoJob *__restrict__ jobs, const uint32_t *__restrict__ job_ids, uint32_t njobs) { topo_lds_kernel<true>(jobs, job_ids, njobs); }
+
+// K-FRONT (single-stream contexts): a batch's automata and its attributes' bit-unpack in ONE grid.  On a context whose kernels run one after
+// another, k_unpack_wave (32 us a C4 batch) waited for the automaton (160 us) it does not depend on; here its waves fill the chip beside the
+// automata instead.  The automata's workgroups come first, exactly k_topology_lds (the same body, records at LDS address 0), rounded up to
+// whole rounds of the eight XCDs so that the K-BIT workgroups behind them keep their xcd_slot; K-BIT uses no LDS and reads only what the
+// attribute streams' decode, the previous launch, wrote.  No workgroup waits for another.
+__global__ __launch_bounds__(64) void k_front(const TopoJob *__restrict__ jobs, const uint32_t *__restrict__ topo_ids, uint32_t ntopo,
+                                              const UnpackJob *__restrict__ ujobs, const uint32_t *__restrict__ unpack_ids, uint32_t nunpack) {
+	const uint32_t tb = front_topo_blocks(ntopo);
+	if(blockIdx.x < tb) topo_lds_kernel<false>(jobs, topo_ids, ntopo);
+	else unpack_wave_body(ujobs, unpack_ids, nunpack, blockIdx.x - tb);
+}
 
 } // namespace corto_hip
 

@@ -41,6 +41,11 @@ __global__ void k_dequant(const DequantJob *jobs, const uint32_t *block_job, uin
 __global__ void k_topology(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);
 __global__ void k_topology_lds(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);
 __global__ void k_topology_lds_big(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);   // the same automaton keeping a progress word (k_mesh.hip)
+// k_topology_lds and k_unpack_wave in one grid (single-stream contexts): front_topo_blocks(ntopo) automata first, then xcd_grid(nunpack) K-BIT waves
+__host__ __device__ inline uint32_t front_topo_blocks(uint32_t ntopo) { return (ntopo + 7u) & ~7u; }
+__global__ void k_front(const TopoJob *jobs, const uint32_t *topo_ids, uint32_t ntopo, const UnpackJob *ujobs, const uint32_t *unpack_ids, uint32_t nunpack);
+// (K-BIT's waves hold the automata's LDS request too: k_front only while that is small)
+constexpr uint32_t FRONT_LDS_MAX = 32*1024;
 // dynamic LDS bytes k_topology_lds needs for a front of `cap` edges and `nclers` symbols
 constexpr uint32_t TOPO_SPLIT_LDS = 256;          // words of the split / vertex-id bit block staged in LDS
 // LDS of one blob's CLERS automaton (k_mesh.hip): records of the LIVE front only - a ring for the queued edges, a pool for

@@ -195,8 +195,17 @@ int Planner::launch() {
 		HIP_TRY(hipStreamWaitEvent(st, ctx->ev_join, 0));
 	} else {
 		tunstall(st, 0, ntun, 0, tun_chunks, 0, nfill);
-		{ int e_ = topology(); if(e_) return e_; }
-		unpack(st);
+		// one stream: the automata and the attributes' bit-unpack in one grid (k_front) when the batch has nothing else for either -
+		// no big or HBM-front automaton, no chunked K-BIT - and the automata ask for little LDS (K-BIT's waves hold the same request)
+		const uint32_t nuw = (uint32_t)pl.unpack_wave_ids.v.size(), ntl = (uint32_t)pl.topo_lds_ids.v.size();
+		if(ctx->single_stream && !ctx->dbg.front_off && ntl && nuw && pl.topo_big_ids.v.empty() && pl.topo_glob_ids.v.empty() && !unpack_chunks &&
+			pl.topo_lds <= FRONT_LDS_MAX) {
+			LT.begin("front"); hipLaunchKernelGGL(k_front, dim3(front_topo_blocks(ntl) + xcd_grid(nuw)), dim3(64), pl.topo_lds, st, D(pl.topo),
+				D(pl.topo_lds_ids), ntl, D(pl.unpack), D(pl.unpack_wave_ids), nuw); LT.end();
+		} else {
+			{ int e_ = topology(); if(e_) return e_; }
+			unpack(st);
+		}
 	}
 	if(!pl.delta.v.empty()) {
 		const uint32_t ngroups = (uint32_t)pl.delta_groups.v.size();

@@ -91,7 +91,7 @@ extern "C" int crthip_pool_create(uint32_t ndevices, const int *devices, uint32_
 		L.slot = (uint32_t)(i/((size_t)threads_per_device*depth)); L.device = p->devices[L.slot];
 		int err = crthip_ctx_create(L.device, &L.ctx);
 		// two HIP streams per context only while every stream of the GPU gets a hardware queue of its own (corto_hip.h)
-		if(!err && 2*ctx_per_gpu[L.device] > hw_queues) err = crthip_ctx_set_single_stream(L.ctx, 1);
+		if(!err && 2*ctx_per_gpu[L.device] > hw_queues) err = crthip_ctx_set_single_stream(L.ctx, 1);   // (+ the LDS-lean normals: at 4 queues too, 0.114 vs 0.117-0.125 ms/step with the LDS layout, profiles/r07_what_was_measured.txt)
 		if(err) { for(auto &x : p->lanes) destroy_lane(x); delete p; return err; }
 	}
 	for(auto &kv : ctx_per_gpu)
