@@ -200,6 +200,15 @@ int ctx_quiesce(crthip_ctx *ctx) {
 }
 }
 
+int ctx_stream2(crthip_ctx *ctx, hipStream_t *out) {
+	if(!ctx->stream2 && hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking) != hipSuccess) {
+		ctx->stream2 = nullptr; (void)hipGetLastError();
+		return fail(CRTHIP_E_DEVICE, "hipStreamCreateWithFlags (second stream)");
+	}
+	*out = ctx->stream2;
+	return CRTHIP_OK;
+}
+
 extern "C" int crthip_device_count(void) {
 	int n = 0;
 	if(hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -215,8 +224,10 @@ extern "C" int crthip_ctx_create(int device, crthip_ctx **out) {
 	HIP_TRY(hipSetDevice(device));
 	crthip_ctx *c = new crthip_ctx();
 	c->device = device;
+	// stream2 is made by the first launch that forks (ctx_stream2): a stream takes a share of a hardware queue whether it is used or not,
+	// and the runtime gives each new stream the queue with the fewest streams - a pool's single-stream contexts, created one after the
+	// other, then fall on the queues in turn instead of on every other one
 	if(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-	   hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess ||
 	   hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
 	   hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
 	   hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming) != hipSuccess) { delete c; return fail(CRTHIP_E_DEVICE); }
@@ -244,9 +255,9 @@ extern "C" void crthip_ctx_destroy(crthip_ctx *c) {
 	if(c->host_batch) { crthip_batch *hb = c->host_batch; c->host_batch = nullptr; crthip_batch_destroy(hb); }
 	c->scratch.release(); c->staging.release(); c->arena_pin.release(); c->status_host.release(); c->host_out.release();
 		c->host_pin.release();
-	(void)hipStreamSynchronize(c->stream2);
+	if(c->stream2) (void)hipStreamSynchronize(c->stream2);
 	(void)hipEventDestroy(c->ev_fork); (void)hipEventDestroy(c->ev_join); (void)hipEventDestroy(c->ev_done);
-	(void)hipStreamDestroy(c->stream2);
+	if(c->stream2) (void)hipStreamDestroy(c->stream2);
 	(void)hipStreamDestroy(c->stream);
 	delete c;
 }

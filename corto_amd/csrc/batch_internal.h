@@ -139,7 +139,8 @@ struct Plan {
 struct crthip_ctx {
 	int device = 0;
 	hipStream_t stream = nullptr;
-	hipStream_t stream2 = nullptr;  // attribute streams (Tunstall + bit-unpack) run here while the main stream does topology
+	hipStream_t stream2 = nullptr;  // attribute streams (Tunstall + bit-unpack) run here while the main stream does topology; made by
+	                                // the first launch that forks (ctx_stream2), never on a context that stays single-stream
 	hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 	// recorded behind a decode's last kernel: what sync / done wait for, so that work a caller queues on the stream BEHIND a decode
 	hipEvent_t ev_done = nullptr;
@@ -219,6 +220,7 @@ struct crthip_batch {
 };
 
 int harvest(crthip_ctx *ctx);     // wait for the batch in flight on the context, keep its per-blob status, learn from its flags (batch.cpp)
+int ctx_stream2(crthip_ctx *ctx, hipStream_t *out);   // the context's second stream, made on first use (batch.cpp)
 
 // ------------------------------------------------------------------------------------------------
 // planner: everything below turns the walked layouts + bindings into job arrays inside one scratch block

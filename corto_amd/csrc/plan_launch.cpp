@@ -168,7 +168,8 @@ int Planner::launch() {
 		if(!ctx->single_stream && nbig && nbig <= TILES_BESIDE_MAX && !pl.topo.v.empty()) {
 			// a big mesh alone: every stream is decoded; the automaton (one serial chain: 2.2 of C2's 4 ms) goes on on the main stream, the attributes'
 			// bit-unpack and their delta inversion in tiles on the second one, the tiles trailing the automaton's progress word
-			hipStream_t s2 = ctx->stream2;
+			hipStream_t s2;
+			{ int e_ = ctx_stream2(ctx, &s2); if(e_) return e_; }
 			HIP_TRY(hipEventRecord(ctx->ev_fork, st));
 			HIP_TRY(hipStreamWaitEvent(s2, ctx->ev_fork, 0));
 			{ int e_ = topology(); if(e_) return e_; }
@@ -183,7 +184,8 @@ int Planner::launch() {
 	} else if(!pl.topo.v.empty() && (ntun > clers_tun || nfill > clers_fill || unpack_chunks || !pl.unpack_wave_ids.v.empty()) &&
 		!ctx->single_stream) {
 		// fork: attribute streams on stream2, CLERS + topology on the main stream
-		hipStream_t s2 = ctx->stream2;
+		hipStream_t s2;
+		{ int e_ = ctx_stream2(ctx, &s2); if(e_) return e_; }
 		HIP_TRY(hipEventRecord(ctx->ev_fork, st));
 		HIP_TRY(hipStreamWaitEvent(s2, ctx->ev_fork, 0));
 		tunstall(st, 0, clers_tun, 0, clers_chunks, 0, clers_fill);

@@ -90,8 +90,11 @@ extern "C" int crthip_pool_create(uint32_t ndevices, const int *devices, uint32_
 		Lane &L = p->lanes[i];
 		L.slot = (uint32_t)(i/((size_t)threads_per_device*depth)); L.device = p->devices[L.slot];
 		int err = crthip_ctx_create(L.device, &L.ctx);
-		// two HIP streams per context only while every stream of the GPU gets a hardware queue of its own (corto_hip.h)
-		if(!err && 2*ctx_per_gpu[L.device] > hw_queues) err = crthip_ctx_set_single_stream(L.ctx, 1);   // (+ the LDS-lean normals: at 4 queues too, 0.114 vs 0.117-0.125 ms/step with the LDS layout, profiles/r07_what_was_measured.txt)
+		// two HIP streams per context only while every stream of the GPU gets a hardware queue of its own (corto_hip.h).  A single-stream
+		// context never makes its second stream, and the runtime gives each new stream the queue with the fewest streams: lanes made in
+		// [device][thread][depth] order take the queues in turn, so a thread's batches in flight sit on different queues and every queue
+		// carries about as many lanes (profiles/r08_what_was_measured.txt)
+		if(!err && 2*ctx_per_gpu[L.device] > hw_queues) err = crthip_ctx_set_single_stream(L.ctx, 1);   // (+ the LDS-lean normals, profiles/r08_what_was_measured.txt)
 		if(err) { for(auto &x : p->lanes) destroy_lane(x); delete p; return err; }
 	}
 	for(auto &kv : ctx_per_gpu)

@@ -35,4 +35,6 @@ for r in rows:
 for k, v in sorted(acc.items(), key=lambda kv: -sum(kv[1])):
     print("%-28s n=%4d avg %8.1f us max %8.1f" % (k, len(v), sum(v) / len(v), max(v)))
 PY
+# per hardware queue: kernels, busy share, streams; per stream: its queue (the middle half of the run)
+python tools/queue_spread.py $OUT/t
 tail -4 $OUT/log.txt | head -4
