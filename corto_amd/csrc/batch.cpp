@@ -109,16 +109,17 @@ int harvest(crthip_ctx *ctx) {
 	if(ctx->done_covers_seq == ctx->upload_seq) ctx->arena_upload_pending = false;
 	const int32_t *hs = (const int32_t *)ctx->status_host.p;
 	const size_t n = b->blobs.size();
-	for(size_t i = 0; i < n; i++) b->status[i] = b->blobs[i].host_status ? b->blobs[i].host_status : hs[i];
+	const StatusWords W{n};
+	for(size_t i = 0; i < n; i++) b->status[i] = b->blobs[i].host_status ? b->blobs[i].host_status : hs[W.status(i)];
 	b->stats.topology_fallbacks = 0;
-	for(size_t i = 0; i < n; i++) b->stats.topology_fallbacks += (uint64_t)(hs[n + i] & 1);
+	for(size_t i = 0; i < n; i++) b->stats.topology_fallbacks += (uint64_t)(hs[W.topo_flags(i)] & 1);
 	// K-DELTA keeps values in LDS as int16 relative to vertex 0 and redoes an attribute that does not fit in HBM (slow, exact): a context
 	// that meets such blobs (positions quantised beyond 15 bits) plans its next batches with 32-bit values; a long run of batches later it
 	// tries the narrow layout again, with growing patience if that turns out wrong
 	b->stats.delta_redone = 0; b->stats.delta_walked = 0;
-	for(size_t i = 0; i < n; i++) b->stats.delta_walked += (uint32_t)(hs[2*n + 2*i + 1] != 0);
+	for(size_t i = 0; i < n; i++) b->stats.delta_walked += (uint32_t)(hs[W.delta_flags(i) + 1] != 0);
 	if(!b->planned_wide) {
-		for(size_t i = 0; i < n; i++) b->stats.delta_redone += (uint64_t)(hs[2*n + 2*i] != 0);
+		for(size_t i = 0; i < n; i++) b->stats.delta_redone += (uint64_t)(hs[W.delta_flags(i)] != 0);
 		if(b->stats.delta_redone) {
 			ctx->delta_wide = true;
 			// overflowed right after narrowing again (never on a context's first overflow)
@@ -140,17 +141,17 @@ int harvest(crthip_ctx *ctx) {
 		uint32_t ring_m = 1, pool_q8 = 8;
 		const uint32_t cap_before = ctx->topo_pool_cap;
 		uint32_t learnable = 0;
-		for(size_t i = 0; i < n; i++) if(hs[n + i] & 1) {
+		for(size_t i = 0; i < n; i++) if(hs[W.topo_flags(i)] & 1) {
+			const uint32_t tf = (uint32_t)hs[W.topo_flags(i)];
 			// a redo that ended in an error (an untrusted stream runs its pool dry before it fails) teaches nothing, and a front beyond the LDS
 			// form's 4 096 + 4 096 records is on the HBM path by design: neither may scale every OTHER blob's request up
 			if(b->status[i]) continue;
-			if((((uint32_t)hs[n + i] >> 1) & 0x7FFFu) > TOPO_SLOTS_MAX || ((uint32_t)hs[n + i] >> 16) > TOPO_SLOTS_MAX) continue;
+			if(((tf >> 1) & 0x7FFFu) > TOPO_SLOTS_MAX || (tf >> 16) > TOPO_SLOTS_MAX) continue;
 			learnable++;
 			const auto &h = b->blobs[i].L.h;
 			uint32_t ring, pool, symwin;
-			topo_lds_geometry(h.nface, b->blobs[i].L.clers.size, 4096, 1, 8, n >= 32 ? 4u : 8u, topo_boundary_estimate(h.nvert, h.nface),
-				ring, pool, symwin);
-			const uint32_t need_ring = ((uint32_t)hs[n + i] >> 1) & 0x7FFFu, need_pool = (uint32_t)hs[n + i] >> 16;
+			topo_lds_geometry(h.nface, b->blobs[i].L.clers.size, 4096, 1, 8, n >= 32 ? 4u : 8u, ring, pool, symwin);
+			const uint32_t need_ring = (tf >> 1) & 0x7FFFu, need_pool = tf >> 16;
 			uint32_t m = 1;
 			while(ring*m < need_ring && m < 16) m <<= 1;
 			ring_m = std::max(ring_m, m);

@@ -112,7 +112,7 @@ struct Plan {
 	HostArr<DequantJob> dequant; HostArr<uint32_t> dequant_block_job;
 	// scratch regions (offsets)
 	uint64_t zero_begin = 0, zero_end = 0;
-	uint64_t status_off = 0, tables_off = 0, tun_partial_off = 0, unpack_partial_off = 0, cloud_partial_off = 0;
+	uint64_t tables_off = 0, tun_partial_off = 0, unpack_partial_off = 0, cloud_partial_off = 0;
 	uint64_t facen_off = 0, cnt_off = 0, cursor_off = 0, bnd_off = 0, start_off = 0, flag_off = 0, slot_off = 0, adj_off = 0,
 		nscan_partial_off = 0;
 	uint64_t jobs_begin = 0, jobs_bytes = 0;
@@ -121,15 +121,18 @@ struct Plan {
 	bool tun_multi_chunk = false, any_diff_normal = false, any_est_normal = false;
 	uint32_t tun_max_nchunks = 0;
 	uint64_t total = 0;
-	template <typename A> static void clr(A &a) { a.v.clear(); a.dev_off = 0; }
+	// every job array, in the order they are placed in the block (Planner::group) - reset, placed and staged through here
+	template <class F> void each_array(F f) {
+		f(tun); f(tun_dict); f(tun_chunk_stream); f(tun_group_ids); f(tun_groups); f(fill); f(topo); f(aux_u32); f(topo_lds_ids); f(topo_big_ids);
+		f(topo_glob_ids); f(unpack); f(unpack_chunk_job); f(unpack_wave_ids);
+		f(delta); f(delta_groups); f(cloud); f(cloud_chunk_job); f(normal); f(nv_block_job); f(nv_block_first); f(nf_block_job); f(nf_block_first);
+		f(normal_fused_ids); f(dequant); f(dequant_block_job);
+	}
 	void reset() {                                          // keep every vector's capacity
-		clr(tun); clr(tun_dict); clr(tun_chunk_stream); clr(tun_group_ids); clr(tun_groups); clers_groups = 0; clr(fill); clr(topo);
-			clr(aux_u32); clr(topo_lds_ids); clr(topo_big_ids); clr(topo_glob_ids); topo_need.clear();
-		clr(unpack); clr(unpack_chunk_job); clr(unpack_wave_ids); clr(delta); clr(delta_groups); clr(cloud); clr(cloud_chunk_job);
-			clr(normal); clr(nv_block_job); clr(nv_block_first);
-		clr(nf_block_job); clr(nf_block_first); clr(normal_fused_ids); clr(dequant); clr(dequant_block_job);
+		each_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
+		clers_groups = 0; topo_need.clear();
 		topo_lds = topo_big_lds = normal_fused_lds = 0;
-		zero_begin = zero_end = status_off = tables_off = tun_partial_off = unpack_partial_off = cloud_partial_off = 0;
+		zero_begin = zero_end = tables_off = tun_partial_off = unpack_partial_off = cloud_partial_off = 0;
 		facen_off = cnt_off = cursor_off = bnd_off = start_off = flag_off = slot_off = adj_off = nscan_partial_off = 0;
 		jobs_begin = jobs_bytes = 0; est_nvert = est_nface = 0; delta16_lds = 0;
 		tun_multi_chunk = any_diff_normal = any_est_normal = false; total = 0; tun_max_nchunks = 0;
@@ -219,6 +222,16 @@ struct crthip_batch {
 	bool planned_wide = false;          // the decode in flight was planned with K-DELTA's 32-bit layout
 };
 
+// The per-blob status block: four int32 words a blob in the context's pinned host memory (status_host), written by the kernels, zeroed by
+// Planner::upload, read by harvest
+struct StatusWords {
+	size_t n;                                                      // blobs
+	size_t status(size_t i) const { return i; }                    // the blob's CRTHIP_* code (k_topology*, k_normal*, k_delta_tiles)
+	size_t topo_flags(size_t i) const { return n + i; }            // bit 0: the automaton was redone on the HBM front; above it the slots it needed
+	size_t delta_flags(size_t i) const { return 2*n + 2*i; }       // two words: an attribute's values left int16 / an attribute took the walk
+	size_t bytes() const { return n*16; }
+};
+
 int harvest(crthip_ctx *ctx);     // wait for the batch in flight on the context, keep its per-blob status, learn from its flags (batch.cpp)
 int ctx_stream2(crthip_ctx *ctx, hipStream_t *out);   // the context's second stream, made on first use (batch.cpp)
 
@@ -271,10 +284,14 @@ struct Launch {
 };
 
 // The planner of one decode call, stage by stage (round 4: this was one function of 660 lines).  carve() lays the batch's scratch out
-// (pass 1: sizes and offsets only), jobs() writes the job descriptors of every stage with scratch-relative pseudo pointers (pass 2),
-// group() sorts streams by dictionary and attributes into K-DELTA workgroups and places the job arrays, upload() reserves the blocks,
-// rebases the pointers and stages the arrays, launch() enqueues the kernels in the order of crt::Decoder::decodeMesh / decodePointCloud
-// (src/decoder.cpp:133-196), account() fills crthip_batch_stats.
+// (pass 1: sizes and offsets only), jobs() writes the job descriptors of every stage (pass 2), group() sorts streams by dictionary and
+// attributes into K-DELTA workgroups and places the job arrays, upload() reserves the blocks, resolves the pointers and stages the arrays,
+// launch() enqueues the kernels in the order of crt::Decoder::decodeMesh / decodePointCloud (src/decoder.cpp:133-196), account() fills
+// crthip_batch_stats.
+// Planning overlaps the batch in flight, so jobs() runs before the scratch block is reserved: a descriptor's pointer into scratch is
+// SP(offset), the offset with bit 63 set, and upload() passes every pointer field through resolve(), which turns those into base + offset
+// and leaves every other pointer (the arena, the caller's buffers, the pinned status words, null) as it is.  A user-space address on
+// x86-64 never has bit 63 set.  The one exception: TopoJob.group_end holds a byte offset into aux_u32 (placed after jobs()).
 struct Planner {
 	crthip_batch *b; crthip_ctx *ctx; Plan &pl; std::vector<BlobScratch> &bs;
 	// wide: K-DELTA with 32-bit values in LDS (this context met values beyond int16)
@@ -285,14 +302,16 @@ struct Planner {
 	// the CLERS streams come first in every stream / chunk / fill / dictionary array
 	uint32_t clers_tun = 0, clers_chunks = 0, clers_fill = 0, clers_dict = 0;
 	bool share_clers = false, share_attrs = false;
-	int32_t *hs_base = nullptr;                                              // per-blob status words in pinned host memory
+	int32_t *hs_base = nullptr; StatusWords hs;                              // per-blob status words in pinned host memory
 	uint8_t *base = nullptr, *stage = nullptr;                               // the scratch block; the host image of the job arrays
 
 	Planner(crthip_batch *b_) : b(b_), ctx(b_->ctx), pl(b_->ctx->plan), bs(b_->ctx->plan_scratch), nblobs((uint32_t)b_->blobs.size()),
-		wide(b_->ctx->delta_wide), arena(b_->d_arena) {}
-	static uint8_t *SP(uint64_t off) { return (uint8_t *)(uintptr_t)off; }   // scratch-relative pseudo pointer
-	// real pointer (bit 63: R() leaves it alone)
-	int32_t *HS(uint64_t k) const { return (int32_t *)((uintptr_t)(hs_base + k) | (1ull << 63)); }
+		wide(b_->ctx->delta_wide), arena(b_->d_arena), hs{b_->blobs.size()} {}
+	static uint8_t *SP(uint64_t off) { return (uint8_t *)(uintptr_t)(off | (1ull << 63)); }   // a scratch offset in a pointer field
+	template <class T> void resolve(T *&p) const {
+		const uintptr_t v = (uintptr_t)p;
+		if(v >> 63) p = (T *)(base + (v & ~(1ull << 63)));
+	}
 	int carve(); int jobs(); void group(); int upload(); int launch(); void account();
 };
 

@@ -1,6 +1,7 @@
 // device_plan.h — POD descriptors shared by the host planner (batch.cpp) and the HIP kernels.
 // All pointers are DEVICE addresses.  One array of each job type per batch, uploaded in one H2D copy.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <cstdlib>
 
@@ -68,23 +69,23 @@ struct TopoJob {
 	int32_t *flags;                // bit 0: the LDS path ran out of edge slots and the blob was redone on the HBM front
 	uint32_t nclers, split_nwords, ngroups;
 	uint32_t nvert, nface, front_cap, faces_u16;
-	uint32_t pad;
+	uint32_t opts;                 // TOPO_OPT_*
 	// LDS path (k_mesh.hip): ring of queued-edge records (a power of two; 0: not eligible), pool of surviving-edge records,
 	// DELAY stack entries, symbols in the LDS window (a multiple of 8)
 	uint32_t lds_ring, lds_pool, lds_delayed_cap, lds_symwin;
 };
-// TopoJob.pad on the device, bit 1: the automaton keeps a PROGRESS WORD for a consumer that runs BESIDE it (k_delta_tiles on a lone context's second
+// TopoJob.opts, bit 1: the automaton keeps a PROGRESS WORD for a consumer that runs BESIDE it (k_delta_tiles on a lone context's second
 // stream) - the number of vertices whose prediction triple has been written and has arrived (published every 4 096 vertices and at every slide of the
 // symbol window), 0xFFFFFFFF when it is done.  The word sits 16 bytes in front of the triples (zeroed by the host before the launch): no pointer of its
 // own - the automaton's ISA block has no scalar register to spare for one (a TopoJob eight bytes longer cost the C4 batch's automata 3 %).
-constexpr uint32_t TOPO_PAD_PROGRESS = 2u;
+constexpr uint32_t TOPO_OPT_PROGRESS = 2u;
 constexpr uint32_t TOPO_PROGRESS_BYTES = 16u;
 
 // one log stream to turn into values (include/corto/cstream.h:294-360)
 struct UnpackJob {
 	const uint8_t *logs;
 	const uint32_t *words;
-	void *out;                     // int32* or uint8*
+	void *out;                     // int32*, uint8* or int16*: out_kind
 	uint32_t count;                // logs in the stream
 	uint32_t nwords;
 	uint32_t out_limit;            // never write element index >= out_limit (nvert)
@@ -94,8 +95,10 @@ struct UnpackJob {
 	uint16_t stride;               // output elements per vertex
 	uint16_t comp;                 // VALUES: component
 	uint8_t mode;                  // 0 ARRAY, 1 VALUES
-	uint8_t out_u8;                // 1: bytes (colours); 2: int16 (k_unpack_wave only: a stream whose table holds no width above 16 bits, read by k_delta_lds16 / k_normal_blob)
+	uint8_t out_kind;              // UNPACK_OUT_*
 };
+// UNPACK_OUT_I16: k_unpack_wave only - a stream whose table holds no width above 16 bits, read by k_delta_lds16 / k_normal_blob
+enum : uint8_t { UNPACK_OUT_I32 = 0, UNPACK_OUT_U8 = 1, UNPACK_OUT_I16 = 2 };
 
 constexpr uint32_t UNPACK_WAVE_MAX_LOGS = 16384;   // bit blocks of at most this many logs (all streams together): one wave per stream (k_unpack_wave); else chunks of 1 024 with look-back
 
@@ -104,10 +107,11 @@ constexpr uint32_t UNPACK_WAVE_MAX_LOGS = 16384;   // bit blocks of at most this
 struct DeltaJob {
 	void *values;                  // int32* or uint8*, stride N
 	const uint32_t *pred;
-	uint8_t *progress;             // k_delta_tiles: the automaton's progress word (TopoJob.pad: TOPO_PAD_PROGRESS) or null
+	uint8_t *progress;             // k_delta_tiles: the automaton's progress word (TopoJob.opts: TOPO_OPT_PROGRESS) or null
 	uint32_t nvert, N;
-	uint8_t parallelogram, is_u8, pad[2];   // pad[1]: k_delta_lds16 keeps 32-bit records in LDS (the whole group says the same); pad[0] (device): `values` holds the raw
-	                               // deltas as int16 (K-BIT's UnpackJob.out_u8 == 2), packed at the front of the buffer the results go to
+	uint8_t parallelogram, is_u8;
+	uint8_t in_i16;                // `values` holds the raw deltas as int16 (K-BIT's UNPACK_OUT_I16), packed at the front of the buffer the results go to
+	uint8_t wide;                  // k_delta_lds16 keeps 32-bit records in LDS (the whole group says the same)
 	// k_delta_lds16 finishes the attribute on its way out of LDS (no k_dequant launch, no second trip through HBM):
 	uint32_t deq;                  // 0: write the integers back; 1: generic, packed: (float)v*q in place (vertex_attribute.h:190-193);
 	                               // 2: colour: YCC -> RGB x qc into `out` (color_attribute.cpp:76-95)
@@ -117,7 +121,8 @@ struct DeltaJob {
 	void *out;                     // colour destination
 	uint32_t out_components, out_stride;
 	int32_t *flags;                // k_delta_lds16: set to 1 when the attribute's values relative to vertex 0 left int16 and were redone in HBM
-	uint32_t pad2[2];              // pad2[0]: the round loop from vertex 1 (test hook: $CORTO_DELTA_ROUNDS); pad2[1]: words from the blob's status word to `flags` (k_delta_tiles)
+	uint32_t rounds;               // the round loop from vertex 1 (test hook: $CORTO_DELTA_ROUNDS)
+	uint32_t status_back;          // k_delta_tiles: words from the blob's status word forward to `flags`
 };
 
 // point-cloud running sum, one job per (blob, attribute) (vertex_attribute.h:177-181, normal_attribute.cpp:202-207)
@@ -132,7 +137,7 @@ struct NormalJob {
 	int32_t *diffs;                // 2 ints per (corrected) vertex
 	void *out;                     // nvert*3 f32 or i16
 	const int32_t *position;       // delta-decoded integer positions (3 per vertex), ESTIMATED/BORDER only
-	const void *faces;
+	const void *faces;             // ESTIMATED/BORDER only: u32 or, with faces_u16, u16 triples
 	uint32_t nvert, nface, ndiffs;
 	uint32_t vbase, fbase;         // offsets into the batch-wide per-vertex / per-face scratch arrays
 	int32_t unit;                  // (int)q
@@ -143,7 +148,7 @@ struct NormalJob {
 	uint32_t pos_stride;           // bytes from one vertex to the next in pos_out (12 = packed, in place when pos_out == position)
 	void *pos_out;                 // null: leave the positions alone
 	float pos_q;
-	uint32_t diffs_i16;            // k_normal_blob: `diffs` holds int16 pairs (K-BIT's UnpackJob.out_u8 == 2)
+	uint32_t diffs_i16;            // k_normal_blob: `diffs` holds int16 pairs (K-BIT's UNPACK_OUT_I16)
 	float *fn_scratch;             // k_normal_blob without its face normals in LDS: 3 floats per face in HBM scratch (null: recompute them per incident vertex)
 };
 
@@ -161,6 +166,13 @@ struct DequantJob {
 	uint32_t stride;               // bytes from one vertex to the next in `buffer`; 0 = packed
 	uint32_t pad2;
 };
+
+// the layout the kernels read, pinned (TopoJob's size is performance-critical: TOPO_OPT_PROGRESS above)
+static_assert(sizeof(TunStream) == 64 && sizeof(FillJob) == 16 && sizeof(TopoJob) == 136 && sizeof(UnpackJob) == 56 && sizeof(DeltaJob) == 96 &&
+              sizeof(CloudJob) == 24 && sizeof(NormalJob) == 104 && sizeof(DequantJob) == 64, "decode job layout");
+static_assert(offsetof(TopoJob, opts) == 116 && offsetof(UnpackJob, out_kind) == 51 && offsetof(NormalJob, faces_u16) == 58, "decode job layout");
+static_assert(offsetof(DeltaJob, in_i16) == 34 && offsetof(DeltaJob, wide) == 35 && offsetof(DeltaJob, rounds) == 88 &&
+              offsetof(DeltaJob, status_back) == 92, "decode job layout");
 
 // ---- encoder stages (k_encode.hip, encode_gpu.cpp) ----
 // a piece of a source stream for the byte histogram (src/tunstall.cpp:83-115)

@@ -395,7 +395,7 @@ __device__ __forceinline__ uint32_t delta_round_loop(const V &val, CRT_LDS const
 }
 
 // ---- staging: raw int32 deltas in HBM -> int16 records (checked); results back as the int32 / float the caller wants ----
-template <int K, typename S>                                                // S: int32_t, or int16_t when K-BIT wrote halfwords (DeltaJob.pad[0])
+template <int K, typename S>                                                // S: int32_t, or int16_t when K-BIT wrote halfwords (DeltaJob.in_i16)
 __device__ __forceinline__ uint32_t stage_in16(const LdsVal<K> &val, CRT_GLOBAL const S *src, uint32_t nvert, bool ga_here) {
 	constexpr int NC = LdsVal<K>::NC;
 	uint32_t bad = 0;
@@ -574,7 +574,7 @@ __device__ __forceinline__ void stage_out_bytes(const LdsVal<5> &val, const Delt
 template <int K>
 __device__ __forceinline__ uint32_t delta16_in(CRT_LDS uint8_t *rec, const DeltaJob &J, bool ga_here) {
 	LdsVal<K> val{(decltype(LdsVal<K>::p))rec};
-	if(J.pad[0]) return stage_in16<K, int16_t>(val, as_global((const int16_t *)J.values), J.nvert, ga_here);
+	if(J.in_i16) return stage_in16<K, int16_t>(val, as_global((const int16_t *)J.values), J.nvert, ga_here);
 	return stage_in16<K, int32_t>(val, as_global((const int32_t *)J.values), J.nvert, ga_here);
 }
 // returns true if the relative values left int16 (nothing was written back: the caller redoes the attribute in HBM)
@@ -585,11 +585,11 @@ __device__ __forceinline__ bool delta16_run(CRT_LDS uint8_t *rec, const DeltaJob
 	CRT_GLOBAL const int32_t *src = as_global((const int32_t *)J.values);
 	int32_t base[NC];
 #pragma unroll
-	for(int q = 0; q < NC; q++) base[q] = J.pad[0] ? (int32_t)((CRT_GLOBAL const int16_t *)src)[q] : src[q];   // vertex 0 (every lane: one broadcast load each)
+	for(int q = 0; q < NC; q++) base[q] = J.in_i16 ? (int32_t)((CRT_GLOBAL const int16_t *)src)[q] : src[q];   // vertex 0 (every lane: one broadcast load each)
 	const uint32_t nvert = (uint32_t)__builtin_amdgcn_readfirstlane((int)J.nvert);
 	const bool para = __builtin_amdgcn_readfirstlane((int)J.parallelogram) != 0;
 	WindowHand hand{1u, 0ull};
-	if(!J.pad2[0]) bad |= delta_window_run(val, GraphLds{gw, ga}, nvert, para, base, &hand);
+	if(!J.rounds) bad |= delta_window_run(val, GraphLds{gw, ga}, nvert, para, base, &hand);
 	if(hand.s < nvert) {
 		if(lane_id() == 0) as_global(J.flags)[1] = 1;                          // (statistics: this blob's window handed over to the round loop)
 		bad |= para ? delta_round_loop<true>(val, gw, ga, nvert, base, hand) : delta_round_loop<false>(val, gw, ga, nvert, base, hand);
@@ -608,7 +608,7 @@ __device__ __forceinline__ void delta32_run(CRT_LDS uint8_t *rec, const DeltaJob
 	const uint32_t nvert = (uint32_t)__builtin_amdgcn_readfirstlane((int)J.nvert);
 	const bool para = __builtin_amdgcn_readfirstlane((int)J.parallelogram) != 0;
 	WindowHand hand{1u, 0ull};
-	if(!J.pad2[0]) (void)delta_window_run(val, GraphLds{gw, ga}, nvert, para, zero, &hand);
+	if(!J.rounds) (void)delta_window_run(val, GraphLds{gw, ga}, nvert, para, zero, &hand);
 	if(hand.s < nvert) {
 		if(lane_id() == 0) as_global(J.flags)[1] = 1;
 		if(para) (void)delta_round_loop<true>(val, gw, ga, nvert, zero, hand); else (void)delta_round_loop<false>(val, gw, ga, nvert, zero, hand);
@@ -629,7 +629,7 @@ __global__ __launch_bounds__(256) void k_delta_lds16(const DeltaJob *__restrict_
 	extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
 	const uint32_t lane = lane_id(), w = wave_id();
 	const uint32_t nvert = (uint32_t)__builtin_amdgcn_readfirstlane((int)jobs[G.first].nvert);   // (uniform: the window loop's control stays scalar)
-	const bool wide = __builtin_amdgcn_readfirstlane((int)jobs[G.first].pad[1]) != 0;            // 32-bit records (every job of the group says the same)
+	const bool wide = __builtin_amdgcn_readfirstlane((int)jobs[G.first].wide) != 0;            // 32-bit records (every job of the group says the same)
 	CRT_LDS uint8_t *l8 = (CRT_LDS uint8_t *)as_lds(lds);
 	uint32_t off = 0, myoff = 0, ga_addr = 0, ga_shift = 1;
 	bool ga_set = false;
@@ -694,7 +694,7 @@ __global__ __launch_bounds__(256) void k_delta_lds16(const DeltaJob *__restrict_
 		WindowHand hand{1u, 0ull};
 		if(J.parallelogram) {
 			const int32_t zero[4] = {0, 0, 0, 0};
-			if(!J.pad2[0]) (void)delta_window_loop<true>(val, GraphLds{gw, ga}, nvert, zero, &hand);
+			if(!J.rounds) (void)delta_window_loop<true>(val, GraphLds{gw, ga}, nvert, zero, &hand);
 			if(hand.s < nvert) {
 				if(lane == 0) as_global(J.flags)[1] = 1;
 				(void)delta_round_loop<true>(val, gw, ga, nvert, zero, hand);
@@ -702,7 +702,7 @@ __global__ __launch_bounds__(256) void k_delta_lds16(const DeltaJob *__restrict_
 		} else {                                                               // additions only: two packed registers instead of four components
 			const LdsVal<6> val2{(CRT_LDS uint32_t *)rec};
 			const int32_t zero[2] = {0, 0};
-			if(!J.pad2[0]) (void)delta_window_loop<false>(val2, GraphLds{gw, ga}, nvert, zero, &hand);
+			if(!J.rounds) (void)delta_window_loop<false>(val2, GraphLds{gw, ga}, nvert, zero, &hand);
 			if(hand.s < nvert) {                                                   // (the round loop multiplies: four byte components, not two packed registers)
 				if(lane == 0) as_global(J.flags)[1] = 1;
 				const int32_t zero4[4] = {0, 0, 0, 0};
@@ -726,7 +726,7 @@ __global__ __launch_bounds__(256) void k_delta_lds16(const DeltaJob *__restrict_
 		// the relative values left int16: the raw deltas are still in HBM (nothing was written back) - the same loop on them, 32 bits wide,
 		// and a word for the host: its next batches are planned on the wide kernel (batch.cpp: harvest)
 		if(lane == 0) *as_global(J.flags) = 1;
-		if(J.pad[0]) {
+		if(J.in_i16) {
 			// (the raw deltas came as halfwords at the front of the buffer: widened in place from the top down - a chunk's 64 values are read before
 			// they are written, and what a chunk writes lies above everything still unread)
 			CRT_GLOBAL int32_t *v32 = as_global((int32_t *)J.values);
@@ -799,7 +799,7 @@ __device__ __forceinline__ void delta_tiles_body(const DeltaJob &J, CRT_LDS uint
 			while((p = __hip_atomic_load(progress, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT)) < need) {
 				__builtin_amdgcn_s_sleep(32);
 				if(wall_clock64() - t0 > 200000000ull) {                           // (cannot happen: the automaton is enqueued first and waits for nothing of this kernel;
-					as_global(J.flags)[-(int32_t)J.pad2[1]] = -9;                    //  if it ever does, the blob says CRTHIP_E_DEVICE instead of carrying wrong values)
+					as_global(J.flags)[-(int32_t)J.status_back] = -9;                    //  if it ever does, the blob says CRTHIP_E_DEVICE instead of carrying wrong values)
 					p = 0xFFFFFFFFu; break;
 				}
 			}

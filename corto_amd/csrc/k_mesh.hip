@@ -247,7 +247,7 @@ __global__ __launch_bounds__(64) void k_topology(const TopoJob *__restrict__ job
 	const TopoJob J = jobs[job_ids[blockIdx.x]];
 	GlobalFront F{(CRT_GLOBAL u32x4 *)as_global(J.front_a), (CRT_GLOBAL u32x2 *)as_global(J.front_b), as_global(J.order), as_global(J.delayed)};
 	topo_run(J, as_global(J.clers), F);
-	if(J.pad & TOPO_PAD_PROGRESS) __hip_atomic_store((CRT_GLOBAL uint32_t *)((CRT_GLOBAL uint8_t *)as_global(J.pred) - TOPO_PROGRESS_BYTES), 0xFFFFFFFFu, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+	if(J.opts & TOPO_OPT_PROGRESS) __hip_atomic_store((CRT_GLOBAL uint32_t *)((CRT_GLOBAL uint8_t *)as_global(J.pred) - TOPO_PROGRESS_BYTES), 0xFFFFFFFFu, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // LDS path: the front of one blob in LDS, hand-tightened.  A lone wave issues one instruction every ~4 cycles, so this
@@ -1958,7 +1958,7 @@ __device__ __forceinline__ void topo_lds_kernel(const TopoJob *__restrict__ jobs
 }
 
 // Two kernels of the same body.  k_topology_lds: a batch's automata, exactly rounds 1-5's code.  k_topology_lds_big: the launch of the blobs that ask for much
-// more LDS than the rest - big meshes - which ALSO keeps the progress word in front of its triples up to date (device_plan.h: TOPO_PAD_PROGRESS; every mesh
+// more LDS than the rest - big meshes - which ALSO keeps the progress word in front of its triples up to date (device_plan.h: TOPO_OPT_PROGRESS; every mesh
 // has the word, so the kernel needs no test); a kernel of its own because the test, or even a TopoJob eight bytes longer, cost the batch's automata 2-3 %.
 __global__ __launch_bounds__(64) void k_topology_lds(const TopoJob *__restrict__ jobs, const uint32_t *__restrict__ job_ids, uint32_t njobs) { topo_lds_kernel<false>(jobs, job_ids, njobs); }
 __global__ __launch_bounds__(64) void k_topology_lds_big(const TopoJob *__restrict__ jobs, const uint32_t *__restrict__ job_ids, uint32_t njobs) { topo_lds_kernel<true>(jobs, job_ids, njobs); }

@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) void k_unpack_extract(const UnpackJob *__restr
 				if(v < mid) v = -v - mid;
 			}
 			if((uint32_t)k < r && i < J.out_limit) {
-				if(J.out_u8) as_global((uint8_t *)J.out)[(size_t)i*J.stride + J.comp] = (uint8_t)v;
+				if(J.out_kind != UNPACK_OUT_I32) as_global((uint8_t *)J.out)[(size_t)i*J.stride + J.comp] = (uint8_t)v;   // (U8: int16 goes a wave a stream)
 				else as_global((int32_t *)J.out)[(size_t)i*J.stride + J.comp] = v;
 			}
 		}

@@ -2,8 +2,7 @@
 #include "batch_internal.h"
 
 int Planner::carve() {
-	// ---- pass 1: sizes & offsets (device addresses are scratch_base + offset, resolved in pass 2) ----
-	// We first carve all scratch, then reserve the block, then fill job structs with real pointers.
+	// ---- pass 1: sizes & offsets (device addresses are scratch base + offset: jobs() writes them as SP(offset), upload() resolves them) ----
 	// per-blob scratch offsets live in the context and are reset, not reallocated: a decode call used to spend a third of its host
 	// time in malloc/free of these small vectors
 	if(bs.size() < nblobs) bs.resize(nblobs);
@@ -24,7 +23,6 @@ int Planner::carve() {
 	// redone blob does), the host zeroes it before the launch and reads it after the sync - no memset kernel in front of a step
 	// and no copy kernel behind it (each stretched to 50-100 us with eight batches in flight).  Prediction triples are not cleared
 	// either: the automaton writes every vertex it makes and clears the ones it never reached itself (k_mesh.hip).
-	(void)cv.take(256);                                                  // (offset 0 is a null pseudo pointer: the first blob's progress word must not sit there)
 	for(uint32_t i = 0; i < nblobs; i++) {
 		const BlobLayout &L = b->blobs[i].L;
 		if(L.h.nface > 0) bs[i].pred = cv.take((uint64_t)L.h.nvert*12 + TOPO_PROGRESS_BYTES, 16) + TOPO_PROGRESS_BYTES;   // (the automaton's progress word in front: device_plan.h)

@@ -42,14 +42,6 @@ void Planner::group() {
 		if(n.prediction != 0 && !n.fused) for(uint32_t c = 0; c < (n.nface + 255)/256; c++) pl.nf_block_job.v.push_back(j);
 	}
 
-	pl.tun_partial_off = cv.take(((uint64_t)tun_chunks*4 + 4)*8);
-	pl.cloud_partial_off = cv.take(((uint64_t)cloud_chunks + 1)*8);
-
-	// job arrays region
-	pl.jobs_begin = cv.take(0);
-	unpack_state_words = (uint64_t)unpack_chunks + 1;                    // (plan_carve's count was every bound stream's; the bit blocks that go a wave a stream keep no state)
-	pl.unpack_partial_off = cv.take(unpack_state_words*8, 16);           // (first thing in the uploaded block: zeros)
-	auto place = [&](auto &arr) { arr.dev_off = cv.take(arr.v.size()*sizeof(arr.v[0]) + 16, 16); };
 	// the LDS automata go up in ONE launch whose LDS request is the largest of theirs - unless some ask for much more than the others (a
 	// 66K-triangle
 	// mesh among 4K-triangle blobs): those get a launch of their own, so that a big mesh does not cost the small ones their occupancy. 
@@ -65,14 +57,11 @@ void Planner::group() {
 		for(size_t k = 0; k < pl.topo_lds_ids.v.size(); k++) {
 			const uint32_t nd = pl.topo_need[k], id = pl.topo_lds_ids.v[k];
 			// (a blob whose automaton keeps a progress word - an attribute goes through k_delta_tiles - runs in the big launch: k_topology_lds_big is the kernel that does)
-			if(nd <= cut && !(pl.topo.v[id].pad & TOPO_PAD_PROGRESS)) { small_ids.push_back(id); pl.topo_lds = std::max(pl.topo_lds, nd); }
+			if(nd <= cut && !(pl.topo.v[id].opts & TOPO_OPT_PROGRESS)) { small_ids.push_back(id); pl.topo_lds = std::max(pl.topo_lds, nd); }
 			else { pl.topo_big_ids.v.push_back(id); pl.topo_big_lds = std::max(pl.topo_big_lds, nd); }
 		}
 		pl.topo_lds_ids.v.swap(small_ids);
 	}
-	place(pl.tun); place(pl.tun_dict); place(pl.tun_chunk_stream); place(pl.tun_group_ids); place(pl.tun_groups); place(pl.fill);
-		place(pl.topo); place(pl.aux_u32); place(pl.topo_lds_ids); place(pl.topo_big_ids); place(pl.topo_glob_ids); place(pl.unpack);
-		place(pl.unpack_chunk_job); place(pl.unpack_wave_ids);
 	// the jobs of k_delta_tiles first - whole attributes, then the slices of those of more than four components (a launch each); then attributes of
 	// one blob that fit LDS together share a workgroup and the prediction graph: consecutive jobs with the same prediction array, up to DELTA_GROUP_MAX
 	{
@@ -97,11 +86,15 @@ void Planner::group() {
 			j += g.count;
 		}
 	}
-	place(pl.delta); place(pl.delta_groups); place(pl.cloud); place(pl.cloud_chunk_job); place(pl.normal); place(pl.nv_block_job);
-		place(pl.nv_block_first);
-	place(pl.nf_block_job); place(pl.nf_block_first); place(pl.normal_fused_ids); place(pl.dequant); place(pl.dequant_block_job);
+
+	pl.tun_partial_off = cv.take(((uint64_t)tun_chunks*4 + 4)*8);
+	pl.cloud_partial_off = cv.take(((uint64_t)cloud_chunks + 1)*8);
+	// job arrays region
+	pl.jobs_begin = cv.take(0);
+	unpack_state_words = (uint64_t)unpack_chunks + 1;                    // (plan_carve's count was every bound stream's; the bit blocks that go a wave a stream keep no state)
+	pl.unpack_partial_off = cv.take(unpack_state_words*8, 16);           // (first thing in the uploaded block: zeros)
+	pl.each_array([&](auto &arr) { arr.dev_off = cv.take(arr.v.size()*sizeof(arr.v[0]) + 16, 16); });
 	pl.jobs_bytes = cv.take(0) - pl.jobs_begin;
 	pl.total = cv.take(0);
-
 }
 

@@ -1,14 +1,11 @@
-// plan_jobs.cpp — Planner::jobs: pass 2 - the job descriptors of every stage, with scratch-relative pseudo pointers.  See batch_internal.h.
+// plan_jobs.cpp — Planner::jobs: pass 2 - the job descriptors of every stage.  A pointer into scratch is written as SP(offset) and
+// resolved by upload(); every other pointer goes in as the real address (the Planner's comment, batch_internal.h).
 #include "batch_internal.h"
 
 int Planner::jobs() {
-	// ---- pass 2: job structs with offsets stored in pointer fields (rebased after the block is reserved) ----
-	// To keep one pass, pointers are built as (uint8_t*)offset and fixed up by adding the scratch base.
-	// four words a blob: status | automaton flags (bit 0: redone on the HBM front) | K-DELTA: {an attribute's values left int16, an
-	// attribute took the walk}
-	// the block is about to move: the batch in flight writes to it
-	if((size_t)nblobs*16 + 16 > ctx->status_host.cap && harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE);
-	if(ctx->status_host.reserve((size_t)nblobs*16 + 16) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
+	// the status block is about to move: the batch in flight writes to it
+	if(hs.bytes() + 16 > ctx->status_host.cap && harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE);
+	if(ctx->status_host.reserve(hs.bytes() + 16) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
 	hs_base = (int32_t *)ctx->status_host.p;
 
 	// the dictionary (TunTable slot) of a stream: a new one, or the one an earlier stream of this launch group with the same table got
@@ -20,7 +17,7 @@ int Planner::jobs() {
 	uint32_t dict_group0 = 0;
 	auto dict_of = [&](const StreamRef &s, const TunStream &t) -> uint32_t {
 		const uint32_t fresh = (uint32_t)pl.tun_dict.v.size();
-		auto make = [&]() { TunStream d = t; d.table = fresh; d.dict = fresh; d.nchunks = 1; pl.tun_dict.v.push_back(d); return fresh; };
+		auto make = [&]() { TunStream d = t; d.dst = nullptr; d.table = fresh; d.dict = fresh; d.nchunks = 1; pl.tun_dict.v.push_back(d); return fresh; };
 		// (0 / 2: one dictionary per stream, whatever repeats)
 		if(s.nsym > 16 || fresh - dict_group0 >= 4096 || ctx->dbg.tun_share == 0 || ctx->dbg.tun_share == 2) return make();
 		uint64_t h = 0x9E3779B97F4A7C15ull ^ s.nsym;
@@ -41,8 +38,8 @@ int Planner::jobs() {
 		}
 	};
 	auto add_stream = [&](const StreamRef &s, uint64_t sym_off, uint64_t blob_off) -> const uint8_t * {
-		// returns the (pseudo or real) device pointer where the decoded symbols will be; real pointers have bit 63 set
-		if(s.mode == STREAM_RAW) return (const uint8_t *)((uintptr_t)(arena + blob_off + s.payload_off) | (1ull << 63));
+		// where the decoded symbols will be: in the arena, or in scratch
+		if(s.mode == STREAM_RAW) return arena + blob_off + s.payload_off;
 		if(s.mode == STREAM_EMPTY) return SP(0);
 		if(s.mode == STREAM_FILL) { pl.fill.v.push_back(FillJob{SP(sym_off), s.size, s.fill}); return SP(sym_off); }
 		TunStream t{};
@@ -90,26 +87,24 @@ int Planner::jobs() {
 			TopoJob t{};
 			t.clers = clers_ptr;
 			t.split_words = (const uint32_t *)(arena + bo + L.split.words_off);
-			t.group_end = (const uint32_t *)SP(pl.aux_u32.v.size()*4);   // index into aux, rebased later
+			t.group_end = (const uint32_t *)(uintptr_t)(pl.aux_u32.v.size()*4);   // bytes into aux_u32 (resolved by upload)
 			for(uint32_t ge : L.group_end) pl.aux_u32.v.push_back(ge);
 			t.faces = P.index ? P.index : (void *)SP(S.faces);
 			t.pred = (uint32_t *)SP(S.pred);
 			t.front_a = (uint4 *)SP(S.front_a); t.front_b = (uint2 *)SP(S.front_b);
 			t.order = (uint32_t *)SP(S.order); t.delayed = (uint32_t *)SP(S.delayed);
-			t.status = HS(i);
-			t.flags = HS(nblobs + i);
+			t.status = hs_base + hs.status(i);
+			t.flags = hs_base + hs.topo_flags(i);
 			t.nclers = L.clers.size; t.split_nwords = L.split.nwords; t.ngroups = (uint32_t)L.group_end.size();
 			t.nvert = nvert; t.nface = nface; t.front_cap = S.front_cap; t.faces_u16 = P.index ? P.index_u16 : 0;
-			t.pad = P.index ? 1u : 0u;                                   // pad = 1: faces is a real pointer
-			if(S.progress != ~0ull) t.pad |= TOPO_PAD_PROGRESS;
+			t.opts = S.progress != ~0ull ? TOPO_OPT_PROGRESS : 0u;
 			{
 				// every mesh takes the LDS path; a lone big mesh may use most of a CU's LDS, a batch keeps its blobs small
 				uint32_t ring, pool, symwin;
 				uint32_t scale = ctx->topo_scale, pool_q8 = ctx->topo_pool_q8, need;
 				// as much of what the context has learnt as fits a CU
 				for(;;) {
-					topo_lds_geometry(nface, L.clers.size, 4096, scale, pool_q8, nblobs >= 32 ? 4u : 8u, topo_boundary_estimate(nvert,
-						nface), ring, pool, symwin, ctx->topo_pool_cap);
+					topo_lds_geometry(nface, L.clers.size, 4096, scale, pool_q8, nblobs >= 32 ? 4u : 8u, ring, pool, symwin, ctx->topo_pool_cap);
 					// every delayed edge is a pool record: same capacity
 					need = topo_lds_bytes(ring, pool, pool, symwin);
 #ifdef CORTO_TOPO_STAMPS
@@ -156,13 +151,13 @@ int Planner::jobs() {
 			// one wave per stream, no look-back; its bit cursors are 32-bit (k_stream.hip)
 			const bool by_wave = attr_logs <= UNPACK_WAVE_MAX_LOGS && as.bits.nwords < (1u << 26) && !ctx->dbg.unpack_chunked;
 			const uint32_t attr_first = (uint32_t)pl.unpack.v.size();
-			auto push_unpack = [&](const StreamRef &s, const uint8_t *logs, void *out, bool out_real, uint8_t mode, uint16_t fields,
-				uint16_t stride, uint16_t comp, uint8_t u8) {
+			auto push_unpack = [&](const StreamRef &s, const uint8_t *logs, void *out, uint8_t mode, uint16_t fields, uint16_t stride,
+				uint16_t comp, uint8_t out_kind) {
 				if(s.size == 0) return;
 				UnpackJob u{};
 				u.logs = logs; u.words = words; u.out = out; u.count = s.size; u.nwords = as.bits.nwords; u.out_limit = nvert;
 				u.chunk0 = unpack_chunks; u.chain_chunk0 = chain0; u.fields = fields; u.stride = stride; u.comp = comp; u.mode = mode;
-				u.out_u8 = (uint8_t)(u8 | (out_real ? 0x80 : 0));           // bit7: out is a real pointer (cleared at fixup)
+				u.out_kind = out_kind;
 				if(by_wave) { u.chain_chunk0 = attr_first; pl.unpack_wave_ids.v.push_back((uint32_t)pl.unpack.v.size()); }
 				else {
 					const uint32_t nc = (s.size + CHUNK - 1)/CHUNK;
@@ -186,14 +181,14 @@ int Planner::jobs() {
 					else for(uint32_t c = 0; c < a.N && hand_i16; c++) hand_i16 = widths_fit(as.logs[c], 15);
 				}
 			}
-			const uint8_t val_fmt = hand_i16 ? 2 : 0;
+			const uint8_t val_fmt = hand_i16 ? UNPACK_OUT_I16 : UNPACK_OUT_I32;
 			std::vector<const uint8_t *> &logs = ctx->plan_logs;
 			logs.assign(as.logs.size(), nullptr);
 			for(size_t j = 0; j < as.logs.size(); j++) logs[j] = add_stream(as.logs[j], A.sym[j], bo);
 
-			void *values = nullptr; bool values_real = false; uint8_t is_u8 = 0; uint32_t N = a.N; bool para = false; bool do_delta = true;
+			void *values = nullptr; uint8_t is_u8 = 0; uint32_t N = a.N; bool para = false; bool do_delta = true;
 			if(a.codec == CRTHIP_CODEC_NORMAL) {
-				push_unpack(as.logs[0], logs[0], SP(A.diffs), false, 0, 2, 2, 0, val_fmt);
+				push_unpack(as.logs[0], logs[0], SP(A.diffs), 0, 2, 2, 0, val_fmt);
 				// a (malformed) stream with fewer diffs than vertices: upstream's vector is zero-filled behind them
 				// (normal_attribute.cpp:180-184)
 				// (only DIFF reads all nvert entries; the other predictions stop at ndiffs)
@@ -202,7 +197,7 @@ int Planner::jobs() {
 				values = SP(A.diffs); N = 2; para = false;
 				do_delta = as.normal_prediction == 0;                     // DIFF only (normal_attribute.cpp:190-191)
 			} else if(a.codec == CRTHIP_CODEC_COLOR) {
-				for(uint32_t c = 0; c < a.N; c++) push_unpack(as.logs[c], logs[c], SP(A.color), false, 1, 1, (uint16_t)a.N, (uint16_t)c, 1);
+				for(uint32_t c = 0; c < a.N; c++) push_unpack(as.logs[c], logs[c], SP(A.color), 1, 1, (uint16_t)a.N, (uint16_t)c, UNPACK_OUT_U8);
 				values = SP(A.color); is_u8 = 1; para = (a.strategy & CRTHIP_PARALLEL) != 0;
 			} else {
 				// packed output: the caller's buffer is the int32 workspace (like upstream, vertex_attribute.h:190-193); with a stride, or
@@ -210,11 +205,9 @@ int Planner::jobs() {
 				// DOUBLE (eight bytes a value: upstream widens in place, front to back): scratch
 				const bool in_scratch = bd.stride || bd.format == CRTHIP_FMT_DOUBLE;
 				void *work = in_scratch ? (void *)SP(A.vals) : bd.buffer;
-				const bool work_real = !in_scratch;
-				if(a.strategy & CRTHIP_CORRELATED) push_unpack(as.logs[0], logs[0], work, work_real, 0, (uint16_t)a.N, (uint16_t)a.N, 0, val_fmt);
-				else for(uint32_t c = 0; c < a.N; c++) push_unpack(as.logs[c], logs[c], work, work_real, 1, 1, (uint16_t)a.N, (uint16_t)c,
-					val_fmt);
-				values = work; values_real = work_real; para = (a.strategy & CRTHIP_PARALLEL) != 0;
+				if(a.strategy & CRTHIP_CORRELATED) push_unpack(as.logs[0], logs[0], work, 0, (uint16_t)a.N, (uint16_t)a.N, 0, val_fmt);
+				else for(uint32_t c = 0; c < a.N; c++) push_unpack(as.logs[c], logs[c], work, 1, 1, (uint16_t)a.N, (uint16_t)c, val_fmt);
+				values = work; para = (a.strategy & CRTHIP_PARALLEL) != 0;
 				// the device half of a caller-supplied codec object (CRTHIP_BIND_STREAM_VALUES): the stream's int32 values stay as they are -
 				// GenericAttr<int>::decode's result (vertex_attribute.h:151-156); deltaDecode / dequantize are the caller's, on the host
 				if(bd.stream_values) continue;
@@ -224,12 +217,11 @@ int Planner::jobs() {
 				if(mesh) {
 					DeltaJob d{};
 					d.values = values; d.pred = (const uint32_t *)SP(S.pred); d.nvert = nvert; d.N = N;
-					// pad[1]: 32-bit records in LDS (k_delta_lds16)
-					d.parallelogram = para; d.is_u8 = is_u8; d.pad[0] = (uint8_t)((values_real ? 1 : 0) | (hand_i16 ? 2 : 0)); d.pad[1] = wide; d.pad2[0] = ctx->dbg.delta_rounds ?
-						1u : 0u;                                                // (pad[0] bit 0: `values` is a real pointer - host only; bit 1: int16 raw deltas - what the device sees)
+					d.parallelogram = para; d.is_u8 = is_u8; d.in_i16 = hand_i16; d.wide = wide; d.rounds = ctx->dbg.delta_rounds ? 1u : 0u;
 					d.progress = S.progress != ~0ull ? SP(S.progress) : nullptr;   // (k_delta_tiles)
-					d.flags = HS(2ull*nblobs + 2ull*i);
-					d.pad2[1] = 2u*nblobs + i;                              // (words from the blob's status to its flags: k_delta_tiles reports a progress word that never came)
+					d.flags = hs_base + hs.delta_flags(i);
+					// (k_delta_tiles reports a progress word that never came in the blob's status word)
+					d.status_back = (uint32_t)(hs.delta_flags(i) - hs.status(i));
 					if(a.codec != CRTHIP_CODEC_NORMAL && delta_in_lds(d, wide)) {
 						if(a.codec == CRTHIP_CODEC_COLOR) {
 							d.deq = 2; d.out = bd.buffer; d.out_components = bd.out_components; d.out_stride = bd.stride;
@@ -241,7 +233,7 @@ int Planner::jobs() {
 					for(uint32_t f = 0; f < N; f += 4) { d.first = f; pl.delta.v.push_back(d); }   // more than four components: k_delta_tiles jobs of four
 				} else {
 					CloudJob c{};
-					c.values = values; c.nvert = nvert; c.N = N; c.chunk0 = cloud_chunks; c.is_u8 = is_u8; c.pad[0] = values_real;
+					c.values = values; c.nvert = nvert; c.N = N; c.chunk0 = cloud_chunks; c.is_u8 = is_u8;
 					const uint32_t nc = N*((nvert + CHUNK - 1)/CHUNK);
 					for(uint32_t q = 0; q < nc; q++) pl.cloud_chunk_job.v.push_back((uint32_t)pl.cloud.v.size());
 					cloud_chunks += nc;
@@ -256,7 +248,7 @@ int Planner::jobs() {
 					n.out_stride = bd.stride ? bd.stride : (bd.format == CRTHIP_FMT_INT16 ? 6u : 12u);
 					n.ndiffs = std::min(as.logs[0].size, nvert); n.unit = f2i_x86_host(a.q);
 					n.prediction = (uint8_t)pr; n.out_i16 = bd.format == CRTHIP_FMT_INT16;
-					n.status = HS(i);
+					n.status = hs_base + hs.status(i);
 					if(pr != 0) {
 						// (a position under a caller-supplied codec holds stream values, not positions: upstream throws there too, normal_attribute.cpp:210-213)
 						const bool pos_ok = pos_k >= 0 && L.h.attrs[pos_k].codec == CRTHIP_CODEC_GENERIC && L.h.attrs[pos_k].N == 3 &&
@@ -266,8 +258,7 @@ int Planner::jobs() {
 						const bool pos_scratch = P.bind[pos_k].stride != 0 || P.bind[pos_k].format == CRTHIP_FMT_DOUBLE;
 						n.position = pos_scratch ? (const int32_t *)SP(S.attr[pos_k].vals) : (const int32_t *)P.bind[pos_k].buffer;
 						n.faces = P.index ? P.index : (void *)SP(S.faces);
-						// bit7: faces is a real pointer, bit6: position is a scratch offset (both cleared at fixup)
-						n.faces_u16 = (uint8_t)((P.index ? P.index_u16 : 0) | (P.index ? 0x80 : 0) | (pos_scratch ? 0x40 : 0));
+						n.faces_u16 = P.index ? (uint8_t)P.index_u16 : 0;
 						if(normal_fused(nvert, nface)) {
 							n.fused = 1; n.diffs_i16 = hand_i16;
 							n.fn_scratch = A.facen != ~0ull ? (float *)SP(A.facen) : nullptr;

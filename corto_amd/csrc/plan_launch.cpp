@@ -1,5 +1,6 @@
-// plan_launch.cpp — Planner::upload / launch / account: the blocks reserved and the arrays staged, the kernels enqueued in the order of
-// crt::Decoder::decodeMesh / decodePointCloud (src/decoder.cpp:133-196), crthip_batch_stats filled.
+// plan_launch.cpp — Planner::upload / launch / account: the blocks reserved, the descriptors' scratch pointers resolved (SP: batch_internal.h)
+// and the arrays staged, the kernels enqueued in the order of crt::Decoder::decodeMesh / decodePointCloud (src/decoder.cpp:133-196),
+// crthip_batch_stats filled.
 #include "batch_internal.h"
 
 int Planner::upload() {
@@ -9,53 +10,29 @@ int Planner::upload() {
 	if(ctx->scratch.reserve(pl.total + 256) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
 	if(ctx->staging.reserve(pl.jobs_bytes + 256) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
 	base = (uint8_t *)ctx->scratch.p;
-	auto R = [&](const void *pseudo) -> uint8_t * {          // rebase a scratch-relative pseudo pointer
-		uintptr_t v = (uintptr_t)pseudo;
-		if(v >> 63) return (uint8_t *)(v & ~(1ull << 63));     // already real (arena)
-		return base + v;
-	};
-	for(auto &t : pl.tun.v) t.dst = R(t.dst);
-	for(auto &t : pl.tun_dict.v) t.dst = nullptr;
-	for(auto &f : pl.fill.v) f.dst = R(f.dst);
+	// every pointer field of every descriptor (SP offsets become base + offset; TopoJob.group_end: bytes into aux_u32)
+	for(auto &t : pl.tun.v) { resolve(t.src); resolve(t.dst); resolve(t.probs); }
+	for(auto &t : pl.tun_dict.v) { resolve(t.src); resolve(t.dst); resolve(t.probs); }
+	for(auto &f : pl.fill.v) resolve(f.dst);
 	for(auto &t : pl.topo.v) {
-		t.clers = R(t.clers);
 		t.group_end = (const uint32_t *)(base + pl.aux_u32.dev_off + (uintptr_t)t.group_end);
-		if(!(t.pad & 1u)) t.faces = R(t.faces);
-		t.pad &= TOPO_PAD_PROGRESS;
-		t.pred = (uint32_t *)R(t.pred); t.front_a = (uint4 *)R(t.front_a); t.front_b = (uint2 *)R(t.front_b);
-		t.order = (uint32_t *)R(t.order); t.delayed = (uint32_t *)R(t.delayed); t.status = (int32_t *)R(t.status); t.flags =
-			(int32_t *)R(t.flags);
+		resolve(t.clers); resolve(t.split_words); resolve(t.faces); resolve(t.pred); resolve(t.front_a); resolve(t.front_b); resolve(t.order);
+		resolve(t.delayed); resolve(t.status); resolve(t.flags);
 	}
-	for(auto &u : pl.unpack.v) {
-		u.logs = R(u.logs);
-		if(!(u.out_u8 & 0x80)) u.out = R(u.out);
-		u.out_u8 &= 0x7F;
-	}
-	for(auto &d : pl.delta.v) { if(!(d.pad[0] & 1)) d.values = R(d.values); d.pad[0] >>= 1; d.pred = (const uint32_t *)R(d.pred);
-		if(d.progress) d.progress = R(d.progress); d.flags = (int32_t *)R(d.flags); }
-	for(auto &c : pl.cloud.v) { if(!c.pad[0]) c.values = R(c.values); c.pad[0] = 0; }
+	for(auto &u : pl.unpack.v) { resolve(u.logs); resolve(u.words); resolve(u.out); }
+	for(auto &d : pl.delta.v) { resolve(d.values); resolve(d.pred); resolve(d.progress); resolve(d.out); resolve(d.flags); }
+	for(auto &c : pl.cloud.v) resolve(c.values);
 	for(auto &n : pl.normal.v) {
-		n.diffs = (int32_t *)R(n.diffs); n.status = (int32_t *)R(n.status);
-		if(n.prediction != 0 && !(n.faces_u16 & 0x80)) n.faces = R(n.faces);
-		if(n.prediction != 0 && (n.faces_u16 & 0x40)) n.position = (const int32_t *)R(n.position);
-		if(n.fn_scratch) n.fn_scratch = (float *)R(n.fn_scratch);
-		n.faces_u16 &= 0x3F;
+		resolve(n.diffs); resolve(n.out); resolve(n.position); resolve(n.faces); resolve(n.status); resolve(n.pos_out); resolve(n.fn_scratch);
 	}
-	for(auto &q : pl.dequant.v) if(q.is_color || q.stride || q.format == CRTHIP_FMT_DOUBLE) q.src = R(q.src);
+	for(auto &q : pl.dequant.v) { resolve(q.buffer); resolve(q.src); }
 
 	// host image -> device (one copy)
 	stage = (uint8_t *)ctx->staging.p;
 	memset(stage + (pl.unpack_partial_off - pl.jobs_begin), 0, unpack_state_words*8);
 	// (after the harvest above: the previous batch's words have been read)
-	memset(ctx->status_host.p, 0, (size_t)nblobs*16);
-	auto put = [&](auto &arr) { if(!arr.v.empty()) memcpy(stage + (arr.dev_off - pl.jobs_begin), arr.v.data(),
-		arr.v.size()*sizeof(arr.v[0])); };
-	put(pl.tun); put(pl.tun_dict); put(pl.tun_chunk_stream); put(pl.tun_group_ids); put(pl.tun_groups); put(pl.fill); put(pl.topo);
-		put(pl.aux_u32); put(pl.topo_lds_ids); put(pl.topo_big_ids); put(pl.topo_glob_ids); put(pl.unpack); put(pl.unpack_chunk_job);
-		put(pl.unpack_wave_ids);
-	put(pl.delta); put(pl.delta_groups); put(pl.cloud); put(pl.cloud_chunk_job); put(pl.normal); put(pl.nv_block_job);
-		put(pl.nv_block_first);
-	put(pl.nf_block_job); put(pl.nf_block_first); put(pl.normal_fused_ids); put(pl.dequant); put(pl.dequant_block_job);
+	memset(ctx->status_host.p, 0, hs.bytes());
+	pl.each_array([&](auto &arr) { if(!arr.v.empty()) memcpy(stage + (arr.dev_off - pl.jobs_begin), arr.v.data(), arr.v.size()*sizeof(arr.v[0])); });
 
 	return CRTHIP_OK;
 }
@@ -278,7 +255,7 @@ void Planner::account() {
 	b->stats.scratch_bytes = pl.total;
 	b->stats.descriptor_bytes = (uint32_t)pl.jobs_bytes;
 	b->stats.int16_streams = 0;
-	for(const UnpackJob &u : pl.unpack.v) b->stats.int16_streams += u.out_u8 == 2;
+	for(const UnpackJob &u : pl.unpack.v) b->stats.int16_streams += u.out_kind == UNPACK_OUT_I16;
 	b->stats.topology_scale = std::max(ctx->topo_scale, (ctx->topo_pool_q8 + 7)/8); b->stats.delta_wide = wide ? 1u : 0u;
 	uint64_t ob = 0;
 	for(auto &P : b->blobs) {

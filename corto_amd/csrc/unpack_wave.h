@@ -90,7 +90,7 @@ __device__ __forceinline__ void unpack_wave_body(const UnpackJob *__restrict__ j
 	};
 	const bool values = (J.mode & 1u) != 0;
 	const uint32_t stride = J.stride, comp = J.comp, out_limit = J.out_limit;
-	const bool out_u8 = J.out_u8 == 1, out_i16 = J.out_u8 == 2;              // (2: every width of the stream is <= 16 bits - its table says so, plan_jobs.cpp - and K-DELTA / K-NRM read int16)
+	const bool out_u8 = J.out_kind == UNPACK_OUT_U8, out_i16 = J.out_kind == UNPACK_OUT_I16;              // (I16: every width of the stream is <= 16 bits - its table says so, plan_jobs.cpp - and K-DELTA / K-NRM read int16)
 	for(uint32_t base = 0; base < count; base += UW_R*64u) {
 		// this block's widths and bit offsets (a scan per round, the cursor a scalar), then the next block's logs go out before the windows
 		uint32_t d[UW_R], at[UW_R];

@@ -1436,7 +1436,7 @@ def test_topology_lds_slot_overflow_redone_on_hbm_front():
                 exp["index"] = exp["index"].astype(np.uint16)
             assert_same(b.host_outputs(i), exp, KEYS, "blob %d u16=%s" % (i, u16))
         # first pass: the torus (queue of 3 800) and the holey disc (each hole adds boundary the header does not show); the ribbon's 800 boundary
-        # edges are in the header (2V - F, kernels.h: topo_boundary_estimate) and its pool is planned for them from the start (round 5)
+        # edges share the pool's one sink slot (kernels.h: topo_lds_geometry) and fit from the start
         # (later passes: ring and pool each by the factor the redone blobs reported - the torus' queue four-fold, the disc's pool 2-3 x; `topology_scale` is the larger)
         assert b.stats().topology_fallbacks == fallbacks and (b.stats().topology_scale == scale if scale else 2 <= b.stats().topology_scale <= 4), (b.stats().topology_scale, b.stats().topology_fallbacks)
         b.close()
