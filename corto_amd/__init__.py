@@ -77,6 +77,16 @@ class MeshDesc(C.Structure):
     ]
 
 
+class GenericAttrDesc(C.Structure):
+    """crthip_generic_attr: one generic attribute for crthip_encode_attrs (Encoder::addAttribute)."""
+    _fields_ = [("name", C.c_char_p), ("values", C.c_void_p), ("format", C.c_uint32), ("components", C.c_uint32),
+                ("q", C.c_float), ("strategy", C.c_uint32)]
+
+
+class AttrList(C.Structure):
+    _fields_ = [("nattr", C.c_uint32), ("attr", C.c_void_p)]
+
+
 class PoolItem(C.Structure):
     _fields_ = [("nblobs", C.c_uint32), ("blobs", C.c_void_p), ("lens", C.c_void_p), ("device_arena", C.c_void_p)]
 
@@ -149,6 +159,13 @@ def lib():
         L.crthip_encode.argtypes = [C.POINTER(MeshDesc), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.crthip_encode_gpu.restype = C.c_int64
         L.crthip_encode_gpu.argtypes = [C.c_void_p, C.POINTER(MeshDesc), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.crthip_encode_attrs.restype = C.c_int64
+        L.crthip_encode_attrs.argtypes = [C.POINTER(MeshDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.crthip_encode_gpu_attrs.restype = C.c_int64
+        L.crthip_encode_gpu_attrs.argtypes = [C.c_void_p, C.POINTER(MeshDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.crthip_encode_batch_attrs.restype = C.c_int64
+        L.crthip_encode_batch_attrs.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.crthip_encode_values.restype = C.c_int64
         L.crthip_encode_values.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.crthip_tunstall_encode_blocks.restype = C.c_int64
@@ -230,6 +247,36 @@ def arena_layout(lens: Sequence[int]):
 
 
 DIFF, ESTIMATED, BORDER = 0, 1, 2
+PARALLEL, CORRELATED = 1, 2          # VertexAttribute::Strategy bits
+
+# input formats of generic attributes, by numpy dtype (VertexAttribute::Format).  The unsigned ones and dtypes without a format (0xFFFFFFFF)
+# go to C as they are and are refused there with CRTHIP_E_FORMAT, as upstream throws "Unsupported format." for them
+_ATTR_FMT = {np.dtype(np.float32): FMT_FLOAT, np.dtype(np.float64): FMT_DOUBLE, np.dtype(np.int32): FMT_INT32,
+             np.dtype(np.int16): FMT_INT16, np.dtype(np.int8): FMT_INT8, np.dtype(np.uint32): FMT_UINT32,
+             np.dtype(np.uint16): FMT_UINT16, np.dtype(np.uint8): FMT_UINT8}
+
+
+def _attr_list(attributes, nvert):
+    """crthip_attr_list of [(name, array (nvert, N), q, strategy), ...] (None: no list), and the objects it points into."""
+    if attributes is None:
+        return None, []
+    attributes = list(attributes)
+    arr = (GenericAttrDesc * max(len(attributes), 1))()
+    keep = [arr]
+    for k, (name, values, q, strategy) in enumerate(attributes):
+        v = np.ascontiguousarray(values)
+        if v.ndim == 1:
+            v = v.reshape(-1, 1)
+        if v.ndim != 2 or v.shape[0] != nvert:
+            raise ValueError("attribute %r: expected an array of shape (%d, N), got %s" % (name, nvert, v.shape))
+        nm = name.encode() if isinstance(name, str) else bytes(name)
+        keep += [v, nm]
+        d = arr[k]
+        d.name = nm; d.values = v.ctypes.data if v.size else None
+        d.format = _ATTR_FMT.get(v.dtype, 0xFFFFFFFF); d.components = v.shape[1]; d.q = q; d.strategy = strategy
+    lst = AttrList(len(attributes), C.cast(arr, C.c_void_p).value)
+    keep.append(lst)
+    return lst, keep
 
 
 def _mesh_desc(mesh, position_bits=14, position_q=0.0, normal_bits=10, normal_prediction=BORDER, color_bits=(6, 7, 6, 5),
@@ -269,22 +316,29 @@ def _mesh_desc(mesh, position_bits=14, position_q=0.0, normal_bits=10, normal_pr
 
 
 def encode(mesh, position_bits=14, position_q=0.0, normal_bits=10, normal_prediction=BORDER, color_bits=(6, 7, 6, 5),
-           uv_bits=12, radius_q=1.0, entropy=1, exif=None, with_normal=True, with_color=True, with_uv=True, ctx=None) -> np.ndarray:
+           uv_bits=12, radius_q=1.0, entropy=1, exif=None, with_normal=True, with_color=True, with_uv=True, ctx=None,
+           attributes=None) -> np.ndarray:
     """.crt blob of a corto_amd.synth.Mesh (byte-identical to upstream crt::Encoder, see csrc/encoder.cpp).  Host only by
     default; with ctx=Context the value coding and the entropy coder run on the device (crthip_encode_gpu) - same bytes.
-    Same keyword meaning as upstream's CLI: -v position_bits, -n normal_bits, -N prediction, -u uv_bits (src/main.cpp:93-216)."""
+    Same keyword meaning as upstream's CLI: -v position_bits, -n normal_bits, -N prediction, -u uv_bits (src/main.cpp:93-216).
+    attributes: [(name, array (nvert, N), q, strategy), ...] - generic attributes, Encoder::addAttribute(name, array, format, N, q,
+    strategy) with the format taken from the dtype (float32, float64, int32, int16, int8); crthip_encode_attrs / _gpu_attrs."""
     m, keep = _mesh_desc(mesh, position_bits=position_bits, position_q=position_q, normal_bits=normal_bits, normal_prediction=normal_prediction,
                          color_bits=color_bits, uv_bits=uv_bits, radius_q=radius_q, entropy=entropy, exif=exif, with_normal=with_normal,
                          with_color=with_color, with_uv=with_uv)
+    lst, keep_attrs = _attr_list(attributes, mesh.nvert)
+    extra = C.byref(lst) if lst is not None else None
     cap = 64 * (mesh.nvert + mesh.nface) + 65536            # one pass unless the estimate is too small
+    if attributes is not None:
+        cap += sum(8 * np.asarray(a[1]).size for a in attributes)
     for _ in range(2):
         out = np.zeros(cap + 16, dtype=np.uint8)
         off = (-out.ctypes.data) % 16
         dst = out[off:].ctypes.data_as(C.c_void_p)
         if ctx is not None:
-            n = lib().crthip_encode_gpu(ctx.handle, C.byref(m), dst, cap, None, None)
+            n = lib().crthip_encode_gpu_attrs(ctx.handle, C.byref(m), extra, dst, cap, None, None)
         else:
-            n = lib().crthip_encode(C.byref(m), dst, cap, None, None)
+            n = lib().crthip_encode_attrs(C.byref(m), extra, dst, cap, None, None)
         if n < 0:
             _check(int(n))
         if n <= cap:
@@ -306,7 +360,7 @@ class EncodeBatchStats(C.Structure):
 
 def encode_batch(meshes, ctx, kw=None, host_threads=0, raise_on_error=True, with_stats=False):
     """.crt blobs of a batch of corto_amd.synth.Mesh in one crthip_encode_batch: each byte-identical to encode(mesh, **kw).
-    kw: one dict of encode()'s keywords for all meshes, or one per mesh.  Returns the list of uint8 blobs (empty for a mesh
+    kw: one dict of encode()'s keywords for all meshes, or one per mesh (`attributes` included: crthip_encode_batch_attrs).  Returns the list of uint8 blobs (empty for a mesh
     that failed); with raise_on_error=False also the per-mesh status codes; with_stats=True also a dict of the call's
     statistics and per-kernel times."""
     meshes = list(meshes)
@@ -320,19 +374,32 @@ def encode_batch(meshes, ctx, kw=None, host_threads=0, raise_on_error=True, with
         if len(kws) != n:
             raise ValueError("encode_batch: %d keyword dicts for %d meshes" % (len(kws), n))
     descs = (MeshDesc * max(n, 1))()
+    lists = (AttrList * max(n, 1))()
     keep = []
+    with_attrs = False
+    extra_bytes = 0
     for i, (mesh, k) in enumerate(zip(meshes, kws)):
+        k = dict(k)
+        attributes = k.pop("attributes", None)
         descs[i], kp = _mesh_desc(mesh, **k)
         keep.append(kp)
+        if attributes is not None:
+            lst, ka = _attr_list(attributes, mesh.nvert)
+            lists[i] = lst; keep.append(ka); with_attrs = True
+            extra_bytes += sum(8 * np.asarray(a[1]).size for a in attributes)
     offs = np.zeros(n + 1, dtype=np.uint64)
     status = np.zeros(max(n, 1), dtype=np.int32)
     st = EncodeBatchStats()
     t = KernelTimes()
-    cap = sum(64 * (m.nvert + m.nface) + 65536 for m in meshes)
+    cap = sum(64 * (m.nvert + m.nface) + 65536 for m in meshes) + extra_bytes
     for _ in range(2):
         out = np.zeros(cap + 16, dtype=np.uint8)
-        r = lib().crthip_encode_batch(ctx.handle, n, descs, host_threads, _np_ptr(out), cap, _np_ptr(offs), None, None,
-                                      _np_ptr(status), C.byref(st), C.byref(t))
+        if with_attrs:
+            r = lib().crthip_encode_batch_attrs(ctx.handle, n, descs, lists, host_threads, _np_ptr(out), cap, _np_ptr(offs), None, None,
+                                                _np_ptr(status), C.byref(st), C.byref(t))
+        else:
+            r = lib().crthip_encode_batch(ctx.handle, n, descs, host_threads, _np_ptr(out), cap, _np_ptr(offs), None, None,
+                                          _np_ptr(status), C.byref(st), C.byref(t))
         if r < 0:
             _check(int(r))
         if r <= cap:

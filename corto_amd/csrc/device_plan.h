@@ -191,13 +191,17 @@ struct EncStream {
 };
 // one attribute to quantise (k_enc_quantize): include/corto/vertex_attribute.h:79-128, src/normal_attribute.cpp:61-111,
 // src/color_attribute.cpp:23-70
+// kinds: GENERIC from float, int32 / int16 / int8 (QK_INT, element format in `format`) or double input, NORMAL, COLOR
+enum : uint32_t { QK_FLOAT = 0, QK_NORMAL = 1, QK_COLOR = 2, QK_INT = 3, QK_DOUBLE = 4 };
 struct QuantJob {
-	const void *in;                // GENERIC: count floats; NORMAL: count x 3 floats; COLOR: count x N bytes
+	const void *in;                // FLOAT: count floats; INT: count elements of `format`; DOUBLE: count doubles (8-byte aligned);
+	                               // NORMAL: count x 3 floats; COLOR: count x N bytes
 	void *out;                     // GENERIC: count int32; NORMAL: count x 2 int32 (octahedral); COLOR: count x N bytes (YCC)
-	uint32_t count, kind, N;       // kind: 0 GENERIC, 1 NORMAL, 2 COLOR
+	uint32_t count, kind, N;       // kind: QK_*
 	float q;                       // GENERIC: the step
 	int32_t unit;                  // NORMAL: (int)q
 	uint32_t qc[4];                // COLOR: per-channel divisors
+	uint32_t format;               // QK_INT: CRTHIP_FMT_INT32 / INT16 / INT8
 };
 // what k_enc_tables leaves per stream for the Tunstall coder: the block header (probabilities) and the encoder tables
 struct EncTab {

@@ -1,9 +1,11 @@
 // enc_quant.h — the encoder's per-element quantisation recipes, shared by k_enc_quantize (k_encode.hip) and
-// k_enc_quantize_batch / k_enc_est_normal (k_encode_batch.hip).  Upstream's float operations one by one (no FMA: the library is
-// built with -ffp-contract=off; IEEE divide); (int) is x86's cvttss2si: INT_MIN when out of range.
+// k_enc_quantize_batch / k_enc_est_normal (k_encode_batch.hip) - the one recipe table of the device encoders.  Upstream's float
+// operations one by one (no FMA: the library is built with -ffp-contract=off; IEEE divide); (int) is x86's cvttss2si / cvttsd2si:
+// INT_MIN when out of range.
 #pragma once
 #include "kernels_common.h"
 #include "device_plan.h"
+#include "../../include/corto_hip.h"
 
 namespace corto_hip {
 
@@ -19,13 +21,21 @@ __device__ __forceinline__ void enc_to_octa(float vx, float vy, float vz, int32_
 	o[0] = f2i_x86(px*(float)unit); o[1] = f2i_x86(py*(float)unit);
 }
 
-// element i of job J: GENERIC (int)(x/q) (vertex_attribute.h:97-99); NORMAL toOcta; COLOR byte/qc then (g, b - g, r - g, a)
-// (color_attribute.cpp:30-44, point.h:213)
+// element i of job J: GENERIC (int)(x/q) for every input format (vertex_attribute.h:79-104): float and the integers divide in float
+// (an int32 beyond 2^24 rounds to nearest even on its way to float, as cvtsi2ss does), a double divides in double and truncates
+// like cvttsd2si; NORMAL toOcta; COLOR byte/qc then (g, b - g, r - g, a) (color_attribute.cpp:30-44, point.h:213)
 __device__ __forceinline__ void enc_quantize_one(const QuantJob &J, uint32_t i) {
-	if(J.kind == 0) {
+	if(J.kind == QK_FLOAT) {
 		const float x = ((const float *)J.in)[i] - 0.0f;
 		((int32_t *)J.out)[i] = f2i_x86(x/J.q);
-	} else if(J.kind == 1) {
+	} else if(J.kind == QK_INT) {
+		const int32_t v = J.format == CRTHIP_FMT_INT8 ? (int32_t)((const int8_t *)J.in)[i]
+		                : J.format == CRTHIP_FMT_INT16 ? (int32_t)((const int16_t *)J.in)[i] : ((const int32_t *)J.in)[i];
+		((int32_t *)J.out)[i] = f2i_x86((float)v/J.q);
+	} else if(J.kind == QK_DOUBLE) {
+		const double x = ((const double *)J.in)[i];
+		((int32_t *)J.out)[i] = d2i_x86(x/(double)J.q);
+	} else if(J.kind == QK_NORMAL) {
 		const float *v = (const float *)J.in + (size_t)i*3;
 		enc_to_octa(v[0], v[1], v[2], J.unit, (int32_t *)J.out + (size_t)i*2);
 	} else {

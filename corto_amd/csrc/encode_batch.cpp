@@ -67,13 +67,12 @@ template <class F> int32_t item_guard(F f) {
 }
 
 uint64_t al(uint64_t x) { return (x + 255) & ~255ull; }
-uint32_t quant_in_bytes(const QuantRequest &r) { return r.kind == 0 ? r.count*4u : r.kind == 1 ? r.count*12u : r.count*r.N; }
-uint32_t quant_out_bytes(const QuantRequest &r) { return r.kind == 0 ? r.count*4u : r.kind == 1 ? r.count*8u : r.count*r.N; }
 uint32_t rs_blocks(uint32_t n) { return std::max(1u, (n + RS_TILE - 1)/RS_TILE); }
 bool is_mesh(const BatchItem &it) { return it.nface_in > 0; }
 // normals whose residuals are against the estimate (a cloud's estimate is all zeros: its ESTIMATED normals still subtract toOcta of it)
 bool est_of(const BatchItem &it, const BatchAttr &a) { return a.codec == CRTHIP_CODEC_NORMAL && (a.prediction == 1 || (a.prediction == 2 && is_mesh(it))); }
-constexpr uint32_t DIRECT_BYTES = 1u << 20;               // inputs from this size up go to the device straight from the caller's array
+constexpr uint64_t DIRECT_BYTES = 1u << 20;               // inputs from this size up go to the device straight from the caller's array
+                                                          // (any element size and byte count: slots are 256-byte aligned, a copy is bytes)
 
 // where one item lives in the chunk's device image
 struct Slot {
@@ -124,7 +123,7 @@ int radix_sort(hipStream_t st, K *k0, uint32_t *v0, K *k1, uint32_t *v1, uint32_
 }
 
 // the device half of one chunk: items[ids] have been set up; their topology passes run here on the pool, overlapping the device
-int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, std::vector<BatchItem> &items, const std::vector<uint32_t> &ids, uint32_t threads,
+int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_list *extra, std::vector<BatchItem> &items, const std::vector<uint32_t> &ids, uint32_t threads,
               std::vector<std::vector<uint8_t>> &blobs, crthip_encode_batch_stats &S, BatchTimes &bt, EncStageTimes &tm) {
 	hipStream_t st = ctx_stream(ctx);
 	const uint32_t n = (uint32_t)ids.size();
@@ -135,7 +134,7 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, std::vector<BatchItem>
 	const auto t_topo = Clock::now();
 	std::thread pool([&]() {
 		parallel_for(n, threads, [&](uint32_t k) {
-			const int32_t e = item_guard([&] { batch_topology(&meshes[ids[k]], items[ids[k]]); });
+			const int32_t e = item_guard([&] { batch_topology(&meshes[ids[k]], extra ? &extra[ids[k]] : nullptr, items[ids[k]]); });
 			if(e) items[ids[k]].status = e;                      // read by this thread's caller only after the join
 			{ std::lock_guard<std::mutex> g(mu); ready[k] = 1; }
 			cv.notify_all();
@@ -153,13 +152,13 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, std::vector<BatchItem>
 			const BatchItem &it = items[ids[k]];
 			slot[k].in.resize(it.attrs.size()); slot[k].q.resize(it.attrs.size()); slot[k].d.resize(it.attrs.size());
 			for(size_t a = 0; a < it.attrs.size(); a++) {
-				const uint32_t b = quant_in_bytes(it.attrs[a].quant);
+				const uint64_t b = quant_in_bytes(it.attrs[a].quant);
 				if((b >= DIRECT_BYTES) == (big == 1)) { slot[k].in[a] = o; o += al(b); }
 			}
 		}
 	uint64_t staged_total = 0;
 	for(uint32_t k = 0; k < n; k++) for(size_t a = 0; a < items[ids[k]].attrs.size(); a++) {
-		const uint32_t b = quant_in_bytes(items[ids[k]].attrs[a].quant);
+		const uint64_t b = quant_in_bytes(items[ids[k]].attrs[a].quant);
 		if(b < DIRECT_BYTES) staged_total = std::max(staged_total, slot[k].in[a] + b);
 	}
 	const uint64_t o_zero = o;                               // zeroed: BORDER XORs, counts, cloud minima and flags
@@ -224,7 +223,7 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, std::vector<BatchItem>
 		for(uint32_t k = 0; k < n; k++) {
 			const BatchItem &it = items[ids[k]];
 			for(size_t a = 0; a < it.attrs.size(); a++) {
-				const uint32_t b = quant_in_bytes(it.attrs[a].quant);
+				const uint64_t b = quant_in_bytes(it.attrs[a].quant);
 				if(!b) continue;
 				if(b < DIRECT_BYTES) memcpy(stage.data() + slot[k].in[a], it.attrs[a].quant.in, b);
 				else { const auto t0 = Clock::now(); BT_TRY(hipMemcpyAsync(base + slot[k].in[a], it.attrs[a].quant.in, b, hipMemcpyHostToDevice, st)); S.upload_ms += ms_since(t0); }
@@ -249,7 +248,7 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, std::vector<BatchItem>
 				const QuantRequest &r = it.attrs[a].quant;
 				if(!r.count) continue;
 				QuantJob J{};
-				J.in = base + slot[k].in[a]; J.out = base + slot[k].q[a]; J.count = r.count; J.kind = r.kind; J.N = r.N; J.q = r.q; J.unit = r.unit;
+				J.in = base + slot[k].in[a]; J.out = base + slot[k].q[a]; J.count = r.count; J.kind = r.kind; J.N = r.N; J.q = r.q; J.unit = r.unit; J.format = r.format;
 				for(int c = 0; c < 4; c++) J.qc[c] = r.qc[c] ? r.qc[c] : 1u;
 				qj.push_back(J); start.push_back(blocks); blocks += (r.count + 255)/256;
 			}
@@ -277,7 +276,7 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, std::vector<BatchItem>
 		if(it.nvert_in == 0) continue;
 		ZJob Z{};
 		Z.coords = (const int32_t *)(base + slot[k].q[0]);
-		for(size_t a = 0; a < it.attrs.size(); a++) if(it.attrs[a].quant.in == meshes[ids[k]].position) Z.coords = (const int32_t *)(base + slot[k].q[a]);
+		for(size_t a = 0; a < it.attrs.size(); a++) if(it.attrs[a].position) Z.coords = (const int32_t *)(base + slot[k].q[a]);
 		Z.mn = (int32_t *)(base + slot[k].zmn); Z.flag = (uint32_t *)(base + o_zflags) + k; Z.n = it.nvert_in;
 		Z.keys = (uint64_t *)(base + slot[k].zkeys[0]); Z.vals = (uint32_t *)(base + slot[k].zvals[0]);
 		const uint32_t g = (it.nvert_in + 255)/256;
@@ -336,7 +335,7 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, std::vector<BatchItem>
 			const BatchItem &it = items[ids[k]];
 			if(it.status) continue;
 			int pos = 0;
-			for(size_t a = 0; a < it.attrs.size(); a++) if(it.attrs[a].quant.in == meshes[ids[k]].position) pos = (int)a;
+			for(size_t a = 0; a < it.attrs.size(); a++) if(it.attrs[a].position) pos = (int)a;
 			for(size_t a = 0; a < it.attrs.size(); a++) {
 				if(!est_of(it, it.attrs[a])) continue;
 				EstJob J{};
@@ -385,7 +384,7 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, std::vector<BatchItem>
 		if(it.nvert_in == 0 || it.status) continue;
 		if(!zflags[k]) { S.clouds_device_sorted++; continue; }
 		int pos = 0;
-		for(size_t a = 0; a < it.attrs.size(); a++) if(it.attrs[a].quant.in == meshes[ids[k]].position) pos = (int)a;
+		for(size_t a = 0; a < it.attrs.size(); a++) if(it.attrs[a].position) pos = (int)a;
 		std::vector<int32_t> coords((size_t)it.nvert_in*3);
 		BT_TRY(hipMemcpyAsync(coords.data(), base + slot[k].q[pos], coords.size()*4, hipMemcpyDeviceToHost, st));
 		BT_TRY(sync());
@@ -441,13 +440,15 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, std::vector<BatchItem>
 			bt.n_delta++;
 		}
 	}
-	// BORDER counts back
-	std::vector<uint32_t> counts((size_t)n*64, 0);
+	// BORDER counts back (mesh k's attributes from count_at[k] on)
+	std::vector<size_t> count_at(n + 1, 0);
+	for(uint32_t k = 0; k < n; k++) count_at[k + 1] = count_at[k] + items[ids[k]].attrs.size();
+	std::vector<uint32_t> counts(count_at[n] + 1, 0);
 	for(uint32_t k = 0; k < n; k++) {
 		const BatchItem &it = items[ids[k]];
 		if(it.status) continue;
 		for(const BatchAttr &A : it.attrs) if(A.codec == CRTHIP_CODEC_NORMAL && A.prediction == 2 && is_mesh(it)) {
-			BT_TRY(hipMemcpyAsync(&counts[(size_t)k*64], base + slot[k].count, 4*it.attrs.size(), hipMemcpyDeviceToHost, st));
+			BT_TRY(hipMemcpyAsync(&counts[count_at[k]], base + slot[k].count, 4*it.attrs.size(), hipMemcpyDeviceToHost, st));
 			S.bytes_from_device += 4*it.attrs.size();
 		}
 	}
@@ -481,7 +482,7 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, std::vector<BatchItem>
 			if(b.attr == -1) { v.count = (uint32_t)it.clers.size(); v.values = dclers.u8() + clers_at[k]; }
 			else {
 				const BatchAttr &A = it.attrs[b.attr];
-				if(A.codec == CRTHIP_CODEC_NORMAL && A.prediction == 2 && is_mesh(it)) b.count = counts[(size_t)k*64 + b.attr];
+				if(A.codec == CRTHIP_CODEC_NORMAL && A.prediction == 2 && is_mesh(it)) b.count = counts[count_at[k] + b.attr];
 				v.count = b.count;
 				v.values = base + slot[k].d[b.attr];
 			}
@@ -524,7 +525,7 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, std::vector<BatchItem>
 
 } // namespace
 
-static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, uint32_t host_threads,
+static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra, uint32_t host_threads,
                                  uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert, uint32_t *out_nface,
                                  int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times) {
 	const auto t0 = Clock::now();
@@ -545,6 +546,7 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 	for(uint32_t i = 0; i < n; i++) {
 		const crthip_mesh *m = &meshes[i];
 		int e = encode_check(m);
+		if(!e) e = encode_check_attrs(m, extra ? &extra[i] : nullptr, true);
 		if(!e && (uint64_t)m->nvert*3 > (1u << 26)) e = ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: too many vertices for the value coder");
 		if(!e && m->entropy == CRTHIP_ENTROPY_TUNSTALL && m->nvert > (1u << 23))
 			e = ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: a Tunstall stream longer than 2^23 symbols");
@@ -552,7 +554,7 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 		if(!e) ok.push_back(i);
 	}
 	// position steps and attribute tables (the steps' sums are the host's, in its order)
-	parallel_for((uint32_t)ok.size(), threads, [&](uint32_t k) { items[ok[k]].status = item_guard([&] { batch_setup(&meshes[ok[k]], items[ok[k]]); }); });
+	parallel_for((uint32_t)ok.size(), threads, [&](uint32_t k) { items[ok[k]].status = item_guard([&] { batch_setup(&meshes[ok[k]], extra ? &extra[ok[k]] : nullptr, items[ok[k]]); }); });
 	ok.erase(std::remove_if(ok.begin(), ok.end(), [&](uint32_t i) { return items[i].status != CRTHIP_OK; }), ok.end());
 	S.host_check_ms = ms_since(t0);
 
@@ -568,7 +570,7 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 		uint64_t bytes = 0;
 		while(k < ok.size() && (ids.empty() || bytes + item_bytes(items[ok[k]]) <= budget)) { bytes += item_bytes(items[ok[k]]); ids.push_back(ok[k]); k++; }
 		if(bytes > budget) return ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: a mesh too big for the device image");
-		const int e = run_chunk(ctx, meshes, items, ids, threads, blobs, S, bt, tm);
+		const int e = run_chunk(ctx, meshes, extra, items, ids, threads, blobs, S, bt, tm);
 		if(e) return e;
 	}
 
@@ -601,14 +603,20 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 }
 
 // nothing is thrown across the C boundary
-extern "C" int64_t crthip_encode_batch(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, uint32_t host_threads,
-                                       uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert, uint32_t *out_nface,
-                                       int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times) {
+extern "C" int64_t crthip_encode_batch_attrs(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra, uint32_t host_threads,
+                                             uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert, uint32_t *out_nface,
+                                             int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times) {
 	try {
-		return encode_batch_impl(ctx, n, meshes, host_threads, out, cap, blob_offset, out_nvert, out_nface, status, stats, times);
+		return encode_batch_impl(ctx, n, meshes, extra, host_threads, out, cap, blob_offset, out_nvert, out_nface, status, stats, times);
 	} catch(const std::bad_alloc &) {
 		return ctx_fail(CRTHIP_E_NOMEM, nullptr);
 	} catch(...) {
 		return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch: internal error");
 	}
+}
+
+extern "C" int64_t crthip_encode_batch(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, uint32_t host_threads,
+                                       uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert, uint32_t *out_nface,
+                                       int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times) {
+	return crthip_encode_batch_attrs(ctx, n, meshes, nullptr, host_threads, out, cap, blob_offset, out_nvert, out_nface, status, stats, times);
 }

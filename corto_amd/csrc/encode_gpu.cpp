@@ -259,8 +259,8 @@ int corto_hip::quantize_device(crthip_ctx *ctx, const std::vector<QuantRequest> 
 	ENC_TRY(hipSetDevice(ctx_device(ctx)));
 	{ const int e = ctx_quiesce(ctx); if(e) return e; }
 	hipStream_t st = ctx_stream(ctx);
-	auto in_bytes = [](const QuantRequest &r) -> uint64_t { return r.kind == 0 ? (uint64_t)r.count*4 : r.kind == 1 ? (uint64_t)r.count*12 : (uint64_t)r.count*r.N; };
-	auto out_bytes = [](const QuantRequest &r) -> uint64_t { return r.kind == 0 ? (uint64_t)r.count*4 : r.kind == 1 ? (uint64_t)r.count*8 : (uint64_t)r.count*r.N; };
+	auto in_bytes = [](const QuantRequest &r) -> uint64_t { return quant_in_bytes(r); };      // every input 16-byte aligned (doubles: 8)
+	auto out_bytes = [](const QuantRequest &r) -> uint64_t { return quant_out_bytes(r); };
 	std::vector<uint64_t> ioff(reqs.size()), ooff(reqs.size());
 	uint64_t o = 0;
 	for(size_t k = 0; k < reqs.size(); k++) { ioff[k] = o; o += (in_bytes(reqs[k]) + 15) & ~15ull; }
@@ -276,7 +276,7 @@ int corto_hip::quantize_device(crthip_ctx *ctx, const std::vector<QuantRequest> 
 		const QuantRequest &r = reqs[k];
 		if(!r.count) continue;
 		QuantJob J{};
-		J.in = dev.u8() + ioff[k]; J.out = dev.u8() + ooff[k]; J.count = r.count; J.kind = r.kind; J.N = r.N; J.q = r.q; J.unit = r.unit;
+		J.in = dev.u8() + ioff[k]; J.out = dev.u8() + ooff[k]; J.count = r.count; J.kind = r.kind; J.N = r.N; J.q = r.q; J.unit = r.unit; J.format = r.format;
 		for(int c = 0; c < 4; c++) J.qc[c] = r.qc[c] ? r.qc[c] : 1u;
 		hipLaunchKernelGGL(k_enc_quantize, dim3((r.count + 255)/256), dim3(256), 0, st, J);
 	}

@@ -1,8 +1,10 @@
 // encoder.cpp — host-side .crt writer: lets tests and bench.py synthesise inputs on the GPU
 // box without the reference library.  Byte-identical to upstream's crt::Encoder for the attribute set the decoder path
 // covers (positions, normals in all three prediction modes, rgb/rgba colours, uvs, one generic "radius" attribute,
-// groups, exif, entropy NONE/TUNSTALL, meshes and point clouds); tests/test_encoder_cpu.py pins that against the
-// reference-made golden blobs and, where oracle/_ref exists, against the reference on a random corpus.
+// generic attributes of any name, 1..16 components, either strategy bit and FLOAT / DOUBLE / INT32 / INT16 / INT8 input
+// (Encoder::addAttribute, crthip_encode_attrs), groups, exif, entropy NONE/TUNSTALL, meshes and point clouds);
+// tests/test_encoder_cpu.py and tests/test_encode_generic_cpu.py pin that against the reference-made golden blobs and, where
+// oracle/_ref exists, against the reference on a random corpus.
 //
 // What it restates (upstream file:line):
 //   container + stage order   src/encoder.cpp:207-296 (encode, encodePointCloud), :311-381 (encodeMesh)
@@ -29,6 +31,13 @@
 
 #include "../../include/corto_hip.h"
 #include "encoder_internal.h"
+#include "device_plan.h"
+
+using corto_hip::QK_FLOAT;
+using corto_hip::QK_NORMAL;
+using corto_hip::QK_COLOR;
+using corto_hip::QK_INT;
+using corto_hip::QK_DOUBLE;
 
 namespace {
 
@@ -36,6 +45,11 @@ int ilog2u(uint64_t p) { int k = 0; while(p >>= 1) ++k; return k; }             
 
 int32_t f2i(float x) {                                                                 // x86 cvttss2si
 	if(!(x > -2147483904.0f && x < 2147483648.0f)) return INT_MIN;
+	return (int32_t)x;
+}
+
+int32_t d2i(double x) {                                                                // x86 cvttsd2si
+	if(!(x > -2147483649.0 && x < 2147483648.0)) return INT_MIN;
 	return (int32_t)x;
 }
 
@@ -660,6 +674,54 @@ int corto_hip::encode_check(const crthip_mesh *m) {
 	return CRTHIP_OK;
 }
 
+// crthip_encode_attrs's rules for the extra attributes (include/corto_hip.h).  Upstream throws "Unsupported format." for the unsigned
+// formats (vertex_attribute.h:107) and silently drops an attribute whose name is taken (src/encoder.cpp:188); both are refused here.
+int corto_hip::encode_check_attrs(const crthip_mesh *m, const crthip_attr_list *extra, bool device) {
+	if(!extra || extra->nattr == 0) return CRTHIP_OK;
+	if(!extra->attr) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_attrs: null attribute array");
+	std::vector<std::string> taken{"position"};
+	if(m->normal) taken.push_back("normal");
+	if(m->color) taken.push_back("color");
+	if(m->uv) taken.push_back("uv");
+	if(m->radius) taken.push_back("radius");
+	if((uint64_t)taken.size() + extra->nattr > CRTHIP_MAX_ATTRS) return ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_attrs: more than CRTHIP_MAX_ATTRS attributes");
+	for(uint32_t k = 0; k < extra->nattr; k++) {
+		const crthip_generic_attr &g = extra->attr[k];
+		if(!g.name) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_attrs: null name");
+		const size_t len = strnlen(g.name, CRTHIP_NAME_MAX);
+		if(len == 0 || len >= CRTHIP_NAME_MAX) return ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_attrs: a name must have 1..63 bytes");
+		if(g.format != CRTHIP_FMT_FLOAT && g.format != CRTHIP_FMT_DOUBLE && g.format != CRTHIP_FMT_INT32 && g.format != CRTHIP_FMT_INT16 && g.format != CRTHIP_FMT_INT8)
+			return ctx_fail(CRTHIP_E_FORMAT, "Unsupported format.");
+		if(g.components == 0 || g.components > ENC_PACK_MAX_N) return ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_attrs: components must be 1..16");
+		if(!(std::isfinite(g.q) && g.q > 0.0f)) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_attrs: q must be finite and > 0");
+		if(g.strategy & ~(uint32_t)(CRTHIP_PARALLEL | CRTHIP_CORRELATED)) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_attrs: unknown strategy bits");
+		if(!g.values && m->nvert) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_attrs: null values");
+		const std::string name(g.name, len);
+		if(std::find(taken.begin(), taken.end(), name) != taken.end()) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_attrs: attribute name already in use");
+		taken.push_back(name);
+		const uint64_t elems = (uint64_t)m->nvert*g.components;
+		if(elems > 0xFFFFFFFFull) return ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_attrs: nvert*components beyond 2^32");
+		if(device && elems > (1u << 26)) return ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_attrs: nvert*components beyond the device value coder's 2^26");
+	}
+	return CRTHIP_OK;
+}
+
+uint64_t corto_hip::quant_in_bytes(const QuantRequest &r) {
+	const uint64_t n = r.count;
+	switch(r.kind) {
+	case QK_NORMAL: return n*12;
+	case QK_COLOR: return n*r.N;
+	case QK_DOUBLE: return n*8;
+	case QK_INT: return n*(r.format == CRTHIP_FMT_INT8 ? 1 : r.format == CRTHIP_FMT_INT16 ? 2 : 4);
+	default: return n*4;
+	}
+}
+
+uint64_t corto_hip::quant_out_bytes(const QuantRequest &r) {
+	const uint64_t n = r.count;
+	return r.kind == QK_NORMAL ? n*8 : r.kind == QK_COLOR ? n*r.N : n*4;
+}
+
 extern "C" {
 
 
@@ -669,7 +731,8 @@ extern "C" {
 // quantisation request (in the order the attributes are added; `alloc`: size the value arrays the requests write into).
 // `step`: the position step when the caller has it already (crthip_encode_batch: computed once, before the device quantises).
 struct NamedQuant { std::string name; corto_hip::QuantRequest r; };
-static void setup(const crthip_mesh *m, Encoder &E, std::vector<NamedQuant> &quant, bool alloc, const float *step) {
+// `extra`: the caller's generic attributes (Encoder::addAttribute, src/encoder.cpp:187-197), checked by encode_check_attrs.
+static void setup(const crthip_mesh *m, const crthip_attr_list *extra, Encoder &E, std::vector<NamedQuant> &quant, bool alloc, const float *step) {
 	E.nvert = m->nvert; E.nface = m->index ? m->nface : 0; E.entropy = (uint32_t)m->entropy;
 	const char *p = m->exif;
 	for(uint32_t i = 0; i < m->nexif; i++) { std::string k(p); p += k.size() + 1; std::string v(p); p += v.size() + 1; E.exif[k] = v; }
@@ -716,14 +779,14 @@ static void setup(const crthip_mesh *m, Encoder &E, std::vector<NamedQuant> &qua
 		Attr &a = E.data["position"];
 		a.name = "position"; a.N = 3; a.q = q; a.format = CRTHIP_FMT_FLOAT;
 		a.strategy = CRTHIP_CORRELATED | (E.nface > 0 ? CRTHIP_PARALLEL : 0);
-		corto_hip::QuantRequest r; r.kind = 0; r.count = nv*3; r.in = m->position; r.q = q;
+		corto_hip::QuantRequest r; r.kind = QK_FLOAT; r.count = nv*3; r.in = m->position; r.q = q;
 		request("position", a, r, (size_t)nv*3, 4);
 	}
 	if(m->normal) {
 		Attr &a = E.data["normal"];
 		a.name = "normal"; a.codec = CRTHIP_CODEC_NORMAL; a.N = 3; a.q = powf(2.0f, (float)(m->normal_bits - 1));
 		a.format = CRTHIP_FMT_FLOAT; a.strategy = CRTHIP_CORRELATED; a.prediction = m->normal_prediction;
-		corto_hip::QuantRequest r; r.kind = 1; r.count = nv; r.in = m->normal; r.unit = f2i(a.q);
+		corto_hip::QuantRequest r; r.kind = QK_NORMAL; r.count = nv; r.in = m->normal; r.unit = f2i(a.q);
 		request("normal", a, r, (size_t)nv*2, 4);
 	}
 	if(m->color) {
@@ -731,25 +794,41 @@ static void setup(const crthip_mesh *m, Encoder &E, std::vector<NamedQuant> &qua
 		a.name = "color"; a.codec = CRTHIP_CODEC_COLOR; a.N = m->color_components; a.format = CRTHIP_FMT_UINT8; a.strategy = 0; a.q = 0;
 		for(int k = 0; k < 3; k++) a.qc[k] = 1 << (8 - m->color_bits[k]);
 		a.qc[3] = m->color_components == 3 ? 1 : 1 << (8 - m->color_bits[3]);           // addColors3: setQ(r, g, b, 8)
-		corto_hip::QuantRequest r; r.kind = 2; r.count = nv; r.N = (uint32_t)a.N; r.in = m->color; for(int k = 0; k < 4; k++) r.qc[k] = (uint32_t)a.qc[k];
+		corto_hip::QuantRequest r; r.kind = QK_COLOR; r.count = nv; r.N = (uint32_t)a.N; r.in = m->color; for(int k = 0; k < 4; k++) r.qc[k] = (uint32_t)a.qc[k];
 		request("color", a, r, (size_t)nv*a.N, 1);
 	}
-	auto generic = [&](const char *name, const float *buf, int N, float q) {
+	// GenericAttr<int>::quantize (vertex_attribute.h:79-104): the recipe follows the input format, the header keeps it as the format byte
+	auto generic = [&](const char *name, const void *buf, int N, float q, uint32_t format, uint32_t strategy) {
 		Attr &a = E.data[name];
-		a.name = name; a.N = N; a.q = q; a.format = CRTHIP_FMT_FLOAT; a.strategy = 0;
-		corto_hip::QuantRequest r; r.kind = 0; r.count = nv*(uint32_t)N; r.in = buf; r.q = q;
+		a.name = name; a.N = N; a.q = q; a.format = (int)format; a.strategy = (int)strategy;
+		corto_hip::QuantRequest r;
+		r.kind = format == CRTHIP_FMT_FLOAT ? QK_FLOAT : format == CRTHIP_FMT_DOUBLE ? QK_DOUBLE : QK_INT;
+		r.format = format; r.count = nv*(uint32_t)N; r.in = buf; r.q = q;
 		request(name, a, r, (size_t)nv*N, 4);
 	};
-	if(m->uv) generic("uv", m->uv, 2, m->uv_q);
-	if(m->radius) generic("radius", m->radius, 1, m->radius_q);
+	if(m->uv) generic("uv", m->uv, 2, m->uv_q, CRTHIP_FMT_FLOAT, 0);
+	if(m->radius) generic("radius", m->radius, 1, m->radius_q, CRTHIP_FMT_FLOAT, 0);
+	if(extra)
+		for(uint32_t k = 0; k < extra->nattr; k++) {
+			const crthip_generic_attr &g = extra->attr[k];
+			generic(g.name, g.values, (int)g.components, g.q, g.format, g.strategy);
+		}
 }
 
-// the host's quantisation of one request (what k_enc_quantize does on the device)
+// the host's quantisation of one request (what k_enc_quantize does on the device, enc_quant.h)
 static void quantize_host(const corto_hip::QuantRequest &r) {
-	if(r.kind == 0) {                                                                // vertex_attribute.h:97-99
+	if(r.kind == QK_FLOAT) {                                                         // vertex_attribute.h:97-99
 		const float *in = (const float *)r.in; int32_t *o = (int32_t *)r.out;
 		for(size_t i = 0; i < r.count; i++) o[i] = f2i((in[i] - 0.0f)/r.q);
-	} else if(r.kind == 1) {
+	} else if(r.kind == QK_INT) {                                                    // vertex_attribute.h:85-96: int -> float, float division
+		int32_t *o = (int32_t *)r.out;
+		if(r.format == CRTHIP_FMT_INT8) { const int8_t *in = (const int8_t *)r.in; for(size_t i = 0; i < r.count; i++) o[i] = f2i((float)in[i]/r.q); }
+		else if(r.format == CRTHIP_FMT_INT16) { const int16_t *in = (const int16_t *)r.in; for(size_t i = 0; i < r.count; i++) o[i] = f2i((float)in[i]/r.q); }
+		else { const int32_t *in = (const int32_t *)r.in; for(size_t i = 0; i < r.count; i++) o[i] = f2i((float)in[i]/r.q); }
+	} else if(r.kind == QK_DOUBLE) {                                                 // vertex_attribute.h:100-102: double division
+		const double *in = (const double *)r.in; int32_t *o = (int32_t *)r.out;
+		for(size_t i = 0; i < r.count; i++) o[i] = d2i(in[i]/(double)r.q);
+	} else if(r.kind == QK_NORMAL) {
 		for(uint32_t i = 0; i < r.count; i++) to_octa((const float *)r.in + (size_t)i*3, r.unit, (int32_t *)r.out + (size_t)i*2);
 	} else {                                                                         // color_attribute.cpp:30-44, point.h:213
 		const uint8_t *in = (const uint8_t *)r.in; uint8_t *o = (uint8_t *)r.out;
@@ -763,13 +842,14 @@ static void quantize_host(const corto_hip::QuantRequest &r) {
 	}
 }
 
-static int64_t encode_impl(const crthip_mesh *m, uint8_t *out, size_t cap, uint32_t *out_nvert, uint32_t *out_nface, crthip_ctx *gpu) {
+static int64_t encode_impl(const crthip_mesh *m, const crthip_attr_list *extra, uint8_t *out, size_t cap, uint32_t *out_nvert, uint32_t *out_nface,
+                           crthip_ctx *gpu) {
 	if(!m || !m->position) return CRTHIP_E_ARGUMENT;
 	Encoder E;
 	std::vector<Deferred> deferred;
 	if(gpu) E.s.defer = &deferred;
 	std::vector<NamedQuant> named;
-	setup(m, E, named, true, nullptr);
+	setup(m, extra, E, named, true, nullptr);
 	std::vector<corto_hip::QuantRequest> quant;                     // (device path) the attributes' quantisation, collected and run in one call
 	for(const NamedQuant &q : named) { if(gpu) quant.push_back(q.r); else quantize_host(q.r); }
 	if(gpu) { const int qerr = corto_hip::quantize_device(gpu, quant); if(qerr) return qerr; }   // every attribute's quantisation in one device call (k_enc_quantize)
@@ -809,10 +889,12 @@ static int64_t encode_impl(const crthip_mesh *m, uint8_t *out, size_t cap, uint3
 }
 
 // nothing is thrown across the C boundary
-static int64_t encode_checked(const crthip_mesh *m, uint8_t *out, size_t cap, uint32_t *out_nvert, uint32_t *out_nface, crthip_ctx *gpu) {
+static int64_t encode_checked(const crthip_mesh *m, const crthip_attr_list *extra, uint8_t *out, size_t cap, uint32_t *out_nvert, uint32_t *out_nface,
+                              crthip_ctx *gpu) {
 	{ const int e = corto_hip::encode_check(m); if(e) return e; }
+	{ const int e = corto_hip::encode_check_attrs(m, extra, gpu != nullptr); if(e) return e; }
 	try {
-		return encode_impl(m, out, cap, out_nvert, out_nface, gpu);
+		return encode_impl(m, extra, out, cap, out_nvert, out_nface, gpu);
 	} catch(const std::bad_alloc &) {
 		return corto_hip::ctx_fail(CRTHIP_E_NOMEM, nullptr);
 	} catch(...) {
@@ -820,14 +902,23 @@ static int64_t encode_checked(const crthip_mesh *m, uint8_t *out, size_t cap, ui
 	}
 }
 
+int64_t crthip_encode_attrs(const crthip_mesh *m, const crthip_attr_list *extra, uint8_t *out, size_t cap, uint32_t *out_nvert, uint32_t *out_nface) {
+	return encode_checked(m, extra, out, cap, out_nvert, out_nface, nullptr);
+}
+
 int64_t crthip_encode(const crthip_mesh *m, uint8_t *out, size_t cap, uint32_t *out_nvert, uint32_t *out_nface) {
-	return encode_checked(m, out, cap, out_nvert, out_nface, nullptr);
+	return crthip_encode_attrs(m, nullptr, out, cap, out_nvert, out_nface);
 }
 
 // crthip_encode with the value coding (bit widths, bit packing) and the entropy coder on the device (encode_gpu.cpp)
-int64_t crthip_encode_gpu(crthip_ctx *ctx, const crthip_mesh *m, uint8_t *out, size_t cap, uint32_t *out_nvert, uint32_t *out_nface) {
+int64_t crthip_encode_gpu_attrs(crthip_ctx *ctx, const crthip_mesh *m, const crthip_attr_list *extra, uint8_t *out, size_t cap,
+                                uint32_t *out_nvert, uint32_t *out_nface) {
 	if(!ctx) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_gpu: null context (there is no CPU fallback: use crthip_encode for the host encoder)");
-	return encode_checked(m, out, cap, out_nvert, out_nface, ctx);
+	return encode_checked(m, extra, out, cap, out_nvert, out_nface, ctx);
+}
+
+int64_t crthip_encode_gpu(crthip_ctx *ctx, const crthip_mesh *m, uint8_t *out, size_t cap, uint32_t *out_nvert, uint32_t *out_nface) {
+	return crthip_encode_gpu_attrs(ctx, m, nullptr, out, cap, out_nvert, out_nface);
 }
 
 } // extern "C"
@@ -866,27 +957,28 @@ void corto_hip::morton_order_host(const int32_t *coords, uint32_t nvert, std::ve
 	for(uint32_t i = 0; i < nvert; i++) order[i] = z[i].pos;
 }
 
-void corto_hip::batch_setup(const crthip_mesh *m, BatchItem &it) {
+void corto_hip::batch_setup(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it) {
 	Encoder E;
 	std::vector<NamedQuant> named;
-	setup(m, E, named, false, nullptr);
+	setup(m, extra, E, named, false, nullptr);
 	it.entropy = E.entropy; it.nvert_in = m->nvert; it.nface_in = E.nface;
 	it.attrs.clear();
 	for(auto &kv : E.data) {                                     // the container's order (std::map)
 		const Attr &a = kv.second;
 		BatchAttr b;
 		b.codec = (uint32_t)a.codec; b.N = (uint32_t)a.N; b.prediction = (uint32_t)a.prediction; b.strategy = (uint32_t)a.strategy;
+		b.position = kv.first == "position";
 		for(const NamedQuant &q : named) if(q.name == kv.first) b.quant = q.r;
 		it.attrs.push_back(b);
 	}
 }
 
-void corto_hip::batch_topology(const crthip_mesh *m, BatchItem &it) {
+void corto_hip::batch_topology(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it) {
 	Encoder E;
 	std::vector<NamedQuant> named;
 	float step = 0;
-	for(const BatchAttr &b : it.attrs) if(b.codec == CRTHIP_CODEC_GENERIC && b.N == 3 && b.quant.in == m->position) step = b.quant.q;
-	setup(m, E, named, false, &step);
+	for(const BatchAttr &b : it.attrs) if(b.position) step = b.quant.q;
+	setup(m, extra, E, named, false, &step);
 	std::vector<Deferred> deferred;
 	E.s.defer = &deferred; E.s.shape_only = true;
 	E.header();

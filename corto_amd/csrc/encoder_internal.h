@@ -30,8 +30,11 @@ struct EncValueResult {
 int encode_value_streams(crthip_ctx *ctx, uint32_t entropy, const std::vector<EncValueStream> &in, std::vector<EncValueResult> &res,
                          crthip_kernel_times *times);
 
-// quantisation on the device (encode_gpu.cpp: k_enc_quantize): HOST arrays in, HOST arrays out, one upload / download for all of them
-struct QuantRequest { uint32_t kind = 0, count = 0, N = 1; const void *in = nullptr; void *out = nullptr; float q = 0; int32_t unit = 0; uint32_t qc[4] = {1, 1, 1, 1}; };
+// quantisation on the device (encode_gpu.cpp: k_enc_quantize): HOST arrays in, HOST arrays out, one upload / download for all of them.
+// kind: QK_FLOAT, QK_NORMAL, QK_COLOR, QK_INT (format: CRTHIP_FMT_INT32 / INT16 / INT8), QK_DOUBLE - device_plan.h
+struct QuantRequest { uint32_t kind = 0, count = 0, N = 1, format = CRTHIP_FMT_FLOAT; const void *in = nullptr; void *out = nullptr; float q = 0; int32_t unit = 0; uint32_t qc[4] = {1, 1, 1, 1}; };
+uint64_t quant_in_bytes(const QuantRequest &r);      // the raw input's bytes (format-aware)
+uint64_t quant_out_bytes(const QuantRequest &r);     // the quantised values' bytes
 int quantize_device(crthip_ctx *ctx, const std::vector<QuantRequest> &reqs);
 
 // the value coders + entropy coder over DEVICE-resident arrays (encode_gpu.cpp); each stream carries its mesh's entropy
@@ -43,8 +46,10 @@ void enc_report_times(crthip_kernel_times *times, const EncStageTimes &tm);   //
 
 // ---- crthip_encode_batch (encoder.cpp: checks, topology pass and container; encode_batch.cpp: the device half) ----
 int encode_check(const crthip_mesh *m);              // encode_checked's argument checks (sets the last error)
+// the rules of crthip_encode_attrs's extra list (sets the last error); device: also the value coder's bound on nvert*components
+int encode_check_attrs(const crthip_mesh *m, const crthip_attr_list *extra, bool device);
 constexpr uint32_t BATCH_BITS = 0xFFu;                // a stream that is the CLERS split bits, already packed
-struct BatchAttr { uint32_t codec = 0, N = 0, prediction = 0, strategy = 0; QuantRequest quant; };
+struct BatchAttr { uint32_t codec = 0, N = 0, prediction = 0, strategy = 0; bool position = false; QuantRequest quant; };
 struct BatchStream { size_t at = 0; uint32_t kind = 0, count = 0, N = 1; int32_t attr = 0; };   // attr: index in attrs, -1 CLERS symbols, -2 split bits
 struct BatchItem {
 	int32_t status = CRTHIP_OK;
@@ -58,8 +63,9 @@ struct BatchItem {
 	std::vector<uint8_t> frame;                           // the container without its streams
 	std::vector<BatchStream> streams;                     // where they belong in it, in order (a BORDER normal's count: 0 until the device has it)
 };
-void batch_setup(const crthip_mesh *m, BatchItem &it);           // position step + attribute table (after encode_check)
-void batch_topology(const crthip_mesh *m, BatchItem &it);        // topology pass (meshes) + frame; reads the index alone
+// extra: the mesh's generic attributes (or null), checked by encode_check_attrs
+void batch_setup(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it);      // position step + attribute table (after encode_check)
+void batch_topology(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it);   // topology pass (meshes) + frame; reads the index alone
 void morton_order_host(const int32_t *coords, uint32_t nvert, std::vector<uint32_t> &order);   // encode_cloud's std::sort of the Morton records
 
 // several blobs with HOST output buffers in one batch (batch.cpp): what crthip_decode_host is one of, and what the crt::Decoder facade's

@@ -164,6 +164,11 @@ __device__ __forceinline__ int32_t f2i_x86(float x) {
 	if(!(x > -2147483904.0f && x < 2147483648.0f)) return (int32_t)0x80000000;
 	return (int32_t)x;
 }
+// x86 cvttsd2si: truncation; out of (-2^31 - 1, 2^31) or NaN -> INT_MIN (gfx950's v_cvt_i32_f64 saturates and gives 0 for NaN)
+__device__ __forceinline__ int32_t d2i_x86(double x) {
+	if(!(x > -2147483649.0 && x < 2147483648.0)) return (int32_t)0x80000000;
+	return (int32_t)x;
+}
 __device__ __forceinline__ int16_t f2s_x86(float x) { return (int16_t)(uint16_t)(uint32_t)f2i_x86(x); }
 
 } // namespace corto_hip

@@ -37,7 +37,9 @@ extern "C" {
 
 #define CRTHIP_ABI_VERSION 6   /* 2: crthip_attr_binding.stride, crthip_mesh.group_props, crthip_pool_*; 3: crthip_pool_report grew, crthip_pool_warning;
                                   4: integer / DOUBLE output formats of generic attributes, crthip_pool_device_cpus; 5: crthip_pool_set_outputs_to_host;
-                                  6: crthip_pool_set_render_layouts, crthip_kernel_times names are the kernels' (unpack_wave, delta_lds16) */
+                                  6: crthip_pool_set_render_layouts, crthip_kernel_times names are the kernels' (unpack_wave, delta_lds16);
+                                     added within 6: crthip_generic_attr, crthip_attr_list, crthip_encode_attrs, crthip_encode_gpu_attrs,
+                                     crthip_encode_batch_attrs */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -282,7 +284,8 @@ int64_t crthip_pool_lane_read(crthip_pool *pool, uint32_t lane, uint32_t blob, c
 
 /* ---- .crt writer (host only) -------------------------------------------------------------
  * Byte-identical to upstream's crt::Encoder (src/encoder.cpp:207-722) for positions, normals (all three predictions),
- * rgb/rgba colours, uvs, one generic "radius" attribute, groups, exif, entropy NONE/TUNSTALL, meshes and point clouds.
+ * rgb/rgba colours, uvs, one generic "radius" attribute, groups, exif, entropy NONE/TUNSTALL, meshes and point clouds; more generic
+ * attributes through crthip_encode_attrs below.
  * Lets tests and bench.py synthesise inputs without the reference library. */
 typedef struct {
 	uint32_t nvert, nface;
@@ -312,6 +315,38 @@ typedef struct {
 } crthip_mesh;
 /* returns the blob size (also when out == NULL or cap is too small), or <0 */
 int64_t crthip_encode(const crthip_mesh *mesh, uint8_t *out, size_t cap, uint32_t *out_nvert, uint32_t *out_nface);
+
+/* Generic vertex attributes beyond crthip_mesh's fixed slots (additions within ABI 6): upstream's
+ * Encoder::addAttribute(name, buffer, format, components, q, strategy) (include/corto/encoder.h:70, src/encoder.cpp:187-197).
+ * Each one is written as a GENERIC attribute with the caller's N, q, strategy and, as its format byte, the input format.
+ * Quantisation is upstream's `(int)(buffer[i]/q)` as compiled for x86-64 (include/corto/vertex_attribute.h:79-104):
+ *   FLOAT                 (int)(x/q)                   float division, truncation; INT_MIN for NaN / out of range (cvttss2si)
+ *   INT32, INT16, INT8    (int)((float)x/q)            the int -> float conversion rounds to nearest even above 2^24
+ *   DOUBLE                (int)(x/(double)q)           double division, truncation; INT_MIN for NaN / out of range (cvttsd2si)
+ * Checks upstream does not make (it throws "Unsupported format." or silently drops a duplicate name):
+ *   CRTHIP_E_FORMAT    a UINT32 / UINT16 / UINT8 format (or any other value)
+ *   CRTHIP_E_ARGUMENT  a name the mesh already produces (position, and normal / color / uv / radius where the mesh has them) or one
+ *                      repeated in the list; q not finite and > 0; strategy bits other than CRTHIP_PARALLEL | CRTHIP_CORRELATED;
+ *                      values == NULL with nvert > 0
+ *   CRTHIP_E_LIMIT     a name of 0 or >= CRTHIP_NAME_MAX bytes; components 0 or > 16; more than CRTHIP_MAX_ATTRS attributes in all;
+ *                      nvert*components >= 2^32; in the device encoders nvert*components > 2^26 (the value coder's bound)
+ * A residual of exactly INT_MIN in a stream without CORRELATED (NaN / infinite / out-of-range inputs beside zeros) is undefined
+ * upstream (encodeValues writes a 64-bit field, include/corto/cstream.h:128-133): no bytes are promised for it. */
+typedef struct {
+	const char *name;             /* NUL-terminated, 1..63 bytes */
+	const void *values;           /* HOST, nvert*components elements of `format`, packed (vertex-major) */
+	uint32_t format;              /* CRTHIP_FMT_FLOAT, _DOUBLE, _INT32, _INT16 or _INT8 */
+	uint32_t components;          /* 1..16 */
+	float q;                      /* quantisation step */
+	uint32_t strategy;            /* 0, CRTHIP_PARALLEL, CRTHIP_CORRELATED or both */
+} crthip_generic_attr;
+typedef struct {
+	uint32_t nattr;
+	const crthip_generic_attr *attr;
+} crthip_attr_list;
+/* crthip_encode plus the attributes of `extra`: extra == NULL or extra->nattr == 0 is crthip_encode, byte for byte */
+int64_t crthip_encode_attrs(const crthip_mesh *mesh, const crthip_attr_list *extra, uint8_t *out, size_t cap,
+                            uint32_t *out_nvert, uint32_t *out_nface);
 
 /* ---- measurement / test hooks (not needed by integrators) ---- */
 typedef struct {
@@ -412,6 +447,9 @@ int64_t crthip_encode_values(crthip_ctx *ctx, uint32_t entropy, uint32_t n, cons
 /* crthip_encode with the value coding and the entropy coder on the device (the topology pass, quantisation and the
  * container stay on the host): same arguments plus the context, byte-identical output. */
 int64_t crthip_encode_gpu(crthip_ctx *ctx, const crthip_mesh *mesh, uint8_t *out, size_t cap, uint32_t *out_nvert, uint32_t *out_nface);
+/* crthip_encode_gpu with generic attributes (crthip_encode_attrs; ABI 6 addition); the quantisation runs on the device too */
+int64_t crthip_encode_gpu_attrs(crthip_ctx *ctx, const crthip_mesh *mesh, const crthip_attr_list *extra, uint8_t *out, size_t cap,
+                                uint32_t *out_nvert, uint32_t *out_nface);
 
 /* A batch of meshes and point clouds in, one .crt per item out, every blob byte-identical to crthip_encode of that item.
  * The CLERS topology pass runs on `host_threads` host threads (0: min(16, CPUs of the process's affinity mask)) while the
@@ -444,6 +482,12 @@ typedef struct {
 int64_t crthip_encode_batch(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, uint32_t host_threads,
                             uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert, uint32_t *out_nface,
                             int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times);
+/* crthip_encode_batch with generic attributes (ABI 6 addition): extra holds n lists, mesh i gets extra[i] (NULL: none at all);
+ * blob i is byte-identical to crthip_encode_attrs(&meshes[i], &extra[i]).  A mesh whose list breaks a rule of crthip_encode_attrs
+ * gets that code in status[i] and an empty range; the others are still encoded. */
+int64_t crthip_encode_batch_attrs(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra, uint32_t host_threads,
+                                  uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert, uint32_t *out_nface,
+                                  int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times);
 
 #ifdef __cplusplus
 }
