@@ -1,8 +1,17 @@
 #!/usr/bin/env python3
 """bench.py — decode throughput of the MI355X hot path on BASELINE.json's metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does what the headline needs and nothing else: it sets up the pool, warms up, times the K steps, checks what the
+timed path decoded against the CPU oracle, writes --dump-outputs and prints the line (`value`, `ms_per_step`, the timed region's
+windows, host costs, per-GPU rates).  --full runs everything beside it as well: the unpipelined phase (`single_batch`, `kernels`,
+`roofline`), the side legs on the same pool (`resident_inputs`, `scattered_pageable_blobs`, `sustained`, `without_dictionary_sharing`),
+other batches and regions (`irregular_connectivity`, `realistic`, `secondary_region*`, `first_iteration`), ceilings (`pcie`,
+`hbm_ceiling`), one GPU alone beside N (`scaling_report.one_gpu_alone_mtri_per_s`) and the single-GPU characterisations
+(`tunstall_scaled`, `other_configs`, `encoder_stage`, `facade_per_blob`, `cpu_baseline`); --sustain, --no-cpu, --no-tunstall-scaled,
+--no-other-configs and --all-legs shape that run.  Both runs time the same steps the same way.
 
 Workload (config C4 of BASELINE.json): a batch of 256 independent ~4K-triangle .crt blobs
 (2 112 verts / 4 096 tris each; position 14 bit + uv 12 bit + normal 10 bit BORDER + rgba 6/7/6/5)
@@ -11,7 +20,7 @@ A "step" = one pass of the hot path over that batch on SURVEY.md 8d's PRIMARY ti
 (one buffer per batch, arena layout) and the decoded outputs end in device HBM - upload of the 3.7 MB of .crt bytes over PCIe, re-plan
 (crthip_batch_reset: host walk of every blob) + bind + decode (descriptor upload, all kernels) + sync.  (Rounds 1-3 quoted the rate with the
 compressed inputs already resident in HBM as `value`; VERDICT r3 asked for 8d's primary region instead.  The resident-input rate - no
-PCIe inside the step - is measured in the same run and reported beside it as `resident_inputs`, with its own regions and roofline.)
+PCIe inside the step - is measured by --full and reported beside it as `resident_inputs`, with its own regions and roofline.)
 Steps run on the library's decode pool (crthip_pool, csrc/pool.cpp): per GPU --host-threads (default 5) native host threads
 each keep --depth (default 4) batches in flight, every batch on its own context (own HIP streams, scratch and output
 block), all threads of all GPUs pulling batches from ONE work queue (an atomic counter) - no collective anywhere.
@@ -28,7 +37,7 @@ arrays on any build that decodes correctly.
 `python bench.py --gpus N` without a launcher runs the N GPUs from this one process (one pool, shared queue, N x K steps);
 under torch.distributed.run every rank runs its own one-GPU pool on its shard (seeds 256*rank ..) and RCCL carries only the
 barrier and the max-over-ranks of the time.
-`single_batch` reports the unpipelined latency of one step; the per-kernel HIP-event times come from that phase.
+`single_batch` (--full) reports the unpipelined latency of one step; the per-kernel HIP-event times come from that phase.
 One JSON line on stdout (rank 0).
 """
 import argparse
@@ -483,6 +492,26 @@ def dump_outputs(dirname, ca, pool, blobs, dts):
     np.save(os.path.join(dirname, "nface.npy"), np.asarray(nface, dtype=np.float32))
 
 
+def emit(out, n_gpus, dist, full):
+    """rank 0 (`out` is None elsewhere) prints its line after shard.check_bench_line; every rank leaves the process group"""
+    from corto_amd import shard
+    contract_error = None
+    if out is not None:
+        try:
+            shard.check_bench_line(out, n_gpus, full=full)                   # the contract the driver parses (corto_amd/shard.py; tests/test_sharding_cpu.py runs it on an N = 8 line)
+        except ValueError as e:                                               # a violated check must not discard a multi-minute measurement: the line is printed WITH the
+            contract_error = str(e)                                           # violation named in it, and the exit code says so (ADVICE r5)
+            out["contract_error"] = contract_error
+        print(json.dumps(out), flush=True)
+        if contract_error:
+            print("bench.py: " + contract_error, file=sys.stderr, flush=True)
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+    if contract_error:
+        raise SystemExit(3)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -490,11 +519,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=48)
     ap.add_argument("--depth", type=int, default=4, help="batches in flight (contexts) per host thread; 1 = unpipelined")
     ap.add_argument("--host-threads", type=int, default=5, help="native host threads per GPU feeding it (crthip_pool)")
-    ap.add_argument("--sustain", type=float, default=2.0, help="seconds of the `sustained` leg (one long timed region on the same pool); 0 skips it")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--all-legs", action="store_true", help="N > 1: also run the single-GPU characterisation legs (CPU baseline, Tunstall at roofline scale, single objects, irregular batches) that belong to the N = 1 line")
-    ap.add_argument("--no-tunstall-scaled", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the single-object C2 / C3 decodes (tools/prof_run.sh: keeps the rocprofv3 kernel averages about the C4 batch)")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline (see the module docstring); the options below marked --full shape them")
+    ap.add_argument("--sustain", type=float, default=2.0, help="--full: seconds of the `sustained` leg (one long timed region on the same pool); 0 skips it")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--all-legs", action="store_true", help="--full, N > 1: also run the single-GPU characterisation legs (CPU baseline, Tunstall at roofline scale, single objects, irregular batches) that belong to the N = 1 line")
+    ap.add_argument("--no-tunstall-scaled", action="store_true", help="--full: skip the Tunstall leg at roofline scale")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the single-object C2 / C3 decodes (tools/prof_run.sh: keeps the rocprofv3 kernel averages about the C4 batch)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path decoded in its last step to DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
@@ -568,81 +598,86 @@ def main():
         nthreads = min(plan_t)
         print("bench.py: " + threads_note, file=sys.stderr)
     # compressed inputs resident in HBM before the timed region: item j on ITS pool device (j % N: crthip_pool's home-shard-first policy) -
-    # sharding, not replication; a device asked to decode another's item would upload it inside the step
+    # sharding, not replication; a device asked to decode another's item would upload it inside the step.  Only --full reads them (the
+    # unpipelined phase, `resident_inputs`), but a plain run uploads them too, before the pool is made, so that its timed steps start from
+    # the same state: without the upload the region of --steps 20 --warmup 5 came out ~12 % faster (medians of 7 runs on one MI355X; the
+    # extra context and the unpipelined phase of --full moved nothing, and neither did the upload at --steps 4000)
     arenas = [[ca.upload_arena(it, d) if k == j % len(devices) else None for k, d in enumerate(devices)] for j, it in enumerate(items)]
     pool = ca.Pool(devices, threads=nthreads, depth=depth)
-
-    ctx = ca.Context(devices[0])
-    arena = arenas[0][0]
-    b0 = ca.Batch(ctx, blobs, device_arena=arena)
-    b0.allocate_outputs()
-    stats0 = None
-    # one step = plan + bind + decode + sync, through the C ABI only
-    import ctypes as C
-    L = ca.lib()
-    n = len(blobs)
-    ptrs = (C.c_void_p * n)(*[x.ctypes.data for x in blobs])
-    lens = np.array([len(x) for x in blobs], dtype=np.uint32)
-    status = np.zeros(n, dtype=np.int32)
-    handle = [None]
-
-    def launch(from_host=False):
-        buf, binds, index_ptrs, index_fmt = b0._keep
-        dev = None if from_host else C.c_void_p(arena.data_ptr())
-        if handle[0] is None:
-            h = C.c_void_p()
-            ca._check(L.crthip_batch_create(ctx.handle, n, ptrs, lens.ctypes.data_as(C.c_void_p), dev, C.byref(h)))
-            handle[0] = h
-        else:
-            ca._check(L.crthip_batch_reset(handle[0], n, ptrs, lens.ctypes.data_as(C.c_void_p), dev))
-        h = handle[0]
-        ca._check(L.crthip_batch_bind_all(h, binds, index_ptrs, index_fmt.ctypes.data_as(C.c_void_p)))
-        ca._check(L.crthip_batch_decode(h))
-        return h
-
-    def finish(h, st=status):
-        ca._check(L.crthip_batch_sync(h, st.ctypes.data_as(C.c_void_p)))
-        assert (st == 0).all(), st
+    ctx = ca.Context(devices[0]) if args.full else None      # (the unpipelined phase's and the single-GPU legs' context)
 
     def device_sync():
         for d in sorted(set(devices)):
             torch.cuda.synchronize(d)
-        ctx.sync()
+        if ctx is not None:
+            ctx.sync()
 
     def barrier():
         shard.barrier(dist, device_sync)
 
-    # ---- unpipelined phase: latency of one batch, and per-kernel device times (HIP events around every kernel, on the
-    # stream the kernels run on) with nothing else on the GPU - the numbers the rocprofv3 summary in profiles/ agrees with
-    ctx.set_profiling(True)
-    kt_acc = {}
-    solo_steps = max(3, min(10, args.steps))
-    finish(launch())
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(solo_steps):
-        h = launch()
-        finish(h)
-        kt = ca.KernelTimes()
-        L.crthip_batch_kernel_times(h, C.byref(kt))
-        for k, v in kt.as_dict().items():
-            a = kt_acc.setdefault(k, [0.0, 0]); a[0] += v["ms"]; a[1] += v["launches"]
-        st = ca.BatchStats(); L.crthip_batch_get_stats(h, C.byref(st)); stats0 = st
-    solo_ms = (time.perf_counter() - t0) / solo_steps * 1e3
-    ctx.set_profiling(False)
-    # PCIe-inclusive variant of the same unpipelined step: the blobs start in host memory and crthip_batch_create uploads them
-    t0 = time.perf_counter()
-    for _ in range(solo_steps):
-        finish(launch(from_host=True))
-    h2d_ms = (time.perf_counter() - t0) / solo_steps * 1e3
-    # ... and with the decoded outputs copied back to (pinned) host memory as well: what a host-side caller of crt::Decoder pays
-    dbuf = b0._keep[0]
-    hbuf = torch.empty(dbuf.shape, dtype=dbuf.dtype, pin_memory=True)
-    t0 = time.perf_counter()
-    for _ in range(solo_steps):
+    if args.full:
+        arena = arenas[0][0]
+        b0 = ca.Batch(ctx, blobs, device_arena=arena)
+        b0.allocate_outputs()
+        stats0 = None
+        # one step = plan + bind + decode + sync, through the C ABI only
+        import ctypes as C
+        L = ca.lib()
+        n = len(blobs)
+        ptrs = (C.c_void_p * n)(*[x.ctypes.data for x in blobs])
+        lens = np.array([len(x) for x in blobs], dtype=np.uint32)
+        status = np.zeros(n, dtype=np.int32)
+        handle = [None]
+
+        def launch(from_host=False):
+            buf, binds, index_ptrs, index_fmt = b0._keep
+            dev = None if from_host else C.c_void_p(arena.data_ptr())
+            if handle[0] is None:
+                h = C.c_void_p()
+                ca._check(L.crthip_batch_create(ctx.handle, n, ptrs, lens.ctypes.data_as(C.c_void_p), dev, C.byref(h)))
+                handle[0] = h
+            else:
+                ca._check(L.crthip_batch_reset(handle[0], n, ptrs, lens.ctypes.data_as(C.c_void_p), dev))
+            h = handle[0]
+            ca._check(L.crthip_batch_bind_all(h, binds, index_ptrs, index_fmt.ctypes.data_as(C.c_void_p)))
+            ca._check(L.crthip_batch_decode(h))
+            return h
+
+        def finish(h, st=status):
+            ca._check(L.crthip_batch_sync(h, st.ctypes.data_as(C.c_void_p)))
+            assert (st == 0).all(), st
+
+        # ---- unpipelined phase: latency of one batch, and per-kernel device times (HIP events around every kernel, on the
+        # stream the kernels run on) with nothing else on the GPU - the numbers the rocprofv3 summary in profiles/ agrees with
+        ctx.set_profiling(True)
+        kt_acc = {}
+        solo_steps = max(3, min(10, args.steps))
         finish(launch())
-        hbuf.copy_(dbuf, non_blocking=True); torch.cuda.synchronize()
-    d2h_ms = (time.perf_counter() - t0) / solo_steps * 1e3
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(solo_steps):
+            h = launch()
+            finish(h)
+            kt = ca.KernelTimes()
+            L.crthip_batch_kernel_times(h, C.byref(kt))
+            for k, v in kt.as_dict().items():
+                a = kt_acc.setdefault(k, [0.0, 0]); a[0] += v["ms"]; a[1] += v["launches"]
+            st = ca.BatchStats(); L.crthip_batch_get_stats(h, C.byref(st)); stats0 = st
+        solo_ms = (time.perf_counter() - t0) / solo_steps * 1e3
+        ctx.set_profiling(False)
+        # PCIe-inclusive variant of the same unpipelined step: the blobs start in host memory and crthip_batch_create uploads them
+        t0 = time.perf_counter()
+        for _ in range(solo_steps):
+            finish(launch(from_host=True))
+        h2d_ms = (time.perf_counter() - t0) / solo_steps * 1e3
+        # ... and with the decoded outputs copied back to (pinned) host memory as well: what a host-side caller of crt::Decoder pays
+        dbuf = b0._keep[0]
+        hbuf = torch.empty(dbuf.shape, dtype=dbuf.dtype, pin_memory=True)
+        t0 = time.perf_counter()
+        for _ in range(solo_steps):
+            finish(launch())
+            hbuf.copy_(dbuf, non_blocking=True); torch.cuda.synchronize()
+        d2h_ms = (time.perf_counter() - t0) / solo_steps * 1e3
 
     # ---- the timed region (see the module docstring): the pool runs W warm-up steps straight into exactly K timed steps per GPU
     nloc = len(devices)
@@ -700,7 +735,8 @@ def main():
     if rep.poisoned_lanes != pool.lanes:
         raise SystemExit("bench.py: only %d of %d contexts ended on a poisoned output block" % (rep.poisoned_lanes, pool.lanes))
 
-    # untimed bit-exactness check: what EVERY context of EVERY device decoded last, sampled, against the CPU oracle ...
+    # untimed bit-exactness check (a plain run's too: the metric says `bit-exact vs CPU`): what EVERY context of EVERY device decoded last,
+    # sampled, against the CPU oracle ...
     import hashlib
     from oracle import oracle as oc
     dts = {"position": (np.float32, 3), "normal": (np.float32, 3), "color": (np.uint8, 4), "uv": (np.float32, 2), "index": (np.uint32, 3)}
@@ -717,18 +753,77 @@ def main():
             checked += 1
         tail = pool.lane_read(lane, 0, "#tail", np.uint8, 256)       # behind every output array: still the poison
         assert (tail == 0xA5).all(), ("output block was not poisoned before the lane's last step", lane)
-    for i in range(0, NBLOBS, 17):                # ... the unpipelined context's outputs as well ...
-        got, ref = b0.host_outputs(i), oc.decode(blobs[i])
-        for k in ("position", "normal", "color", "uv", "index"):
-            assert got[k].tobytes() == ref[k].tobytes(), ("bit-exact check failed", i, k)
-    if rank == 0:
-        for i in range(16):                       # ... and seeds 0-15 against the digests of the reference decoder's own output
-            got = b0.host_outputs(i)
+    if args.full:
+        for i in range(0, NBLOBS, 17):            # ... the unpipelined context's outputs as well ...
+            got, ref = b0.host_outputs(i), oc.decode(blobs[i])
             for k in ("position", "normal", "color", "uv", "index"):
-                d = hashlib.sha256(np.ascontiguousarray(got[k]).tobytes()).hexdigest()
-                assert d == z["%s_sha256_%02d" % (k, i)].tobytes().decode(), ("bit-exact check failed (golden)", i, k)
+                assert got[k].tobytes() == ref[k].tobytes(), ("bit-exact check failed", i, k)
+        if rank == 0:
+            for i in range(16):                   # ... and seeds 0-15 against the digests of the reference decoder's own output
+                got = b0.host_outputs(i)
+                for k in ("position", "normal", "color", "uv", "index"):
+                    d = hashlib.sha256(np.ascontiguousarray(got[k]).tobytes()).hexdigest()
+                    assert d == z["%s_sha256_%02d" % (k, i)].tobytes().decode(), ("bit-exact check failed (golden)", i, k)
     if rank == 0 and args.dump_outputs:
         dump_outputs(args.dump_outputs, ca, pool, items[0], dts)
+
+    # the headline: the timed region's rates and what the pool reported about it
+    tri_step = float(sum(ca.probe(x).nface for x in items[0]))
+    if world > 1:
+        mine = torch.zeros(world, dtype=torch.float64, device=red_dev); mine[rank] = float(rep.triangles) / max(rep.elapsed_s, 1e-9) / 1e6
+        dist.all_reduce(mine, op=dist.ReduceOp.SUM)
+        per_gpu = [round(float(x), 2) for x in mine.tolist()]
+    else:
+        per_gpu = [round(c * tri_step / max(rep.elapsed_s, 1e-9) / 1e6, 2) for c in list(rep.steps_per_device)[:nloc]]
+    tris_total = shard.sum_over_ranks(float(rep.triangles), dist, red_dev) / R     # (per K-step region)
+    verts_total = shard.sum_over_ranks(float(rep.vertices), dist, red_dev) / R
+    pool_lanes, pool_warning = pool.lanes, pool.warning
+
+    def headline(alone=None):
+        """the line of a plain run; --full adds its legs to it.  `alone`: --full, N > 1: what GPU 0 did alone (Mtri/s)"""
+        ntri, nvert = int(tri_step), int(sum(ca.probe(x).nvert for x in blobs))
+        h2d_bytes = ca.arena_layout([len(x) for x in blobs])[1]
+        ms_step = elapsed / args.steps * 1e3
+        out = {
+            "metric": "Mtriangles/s + Mverts/s decode, 1M-tri batch; bit-exact vs CPU",
+            "value": round(tris_total / elapsed / 1e6, 2), "unit": "Mtri/s",
+            "mverts_per_s": round(verts_total / elapsed / 1e6, 2),
+            "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
+            "timed_regions": {"count": R, "ms_per_step": [round(e / args.steps * 1e3, 4) for e in regions],
+                              "mean_ms_per_step": round(elapsed_mean / args.steps * 1e3, 4), "median_over_mean": round(elapsed / elapsed_mean, 4),
+                              "note": "one region of exactly K timed steps, pipeline full throughout; `value` and `ms_per_step` are that region's"},
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/i32 integer + f32 normals",
+            "data": "synthetic: 256 distinct bumpy-sphere meshes per GPU (seeds 256*g ..), encoded by the repo's byte-identical .crt writer",
+            "config": {"workload": "C4: 256 x (2112 verts / 4096 tris), pos14+uv12+normal10(BORDER)+rgba, per GPU; C5 when n_gpus=8",
+                       "blobs_per_gpu": NBLOBS, "tris_per_gpu": ntri, "verts_per_gpu": nvert,
+                       "timed_region": "SURVEY 8d primary: K x [H2D of the batch's .crt bytes from ONE pinned host buffer + plan(host walk)+bind+kernels+sync] per GPU, "
+                                       "outputs left in HBM; clock from the "
+                                       "completion of the last of W warm-up steps to the completion of the K-th timed step, pipeline full at both ends "
+                                       "(barrier + device sync before the warm-up and after the drain); "
+                                       "the rate with the compressed inputs already resident in HBM (rounds 1-3's `value`) is `resident_inputs` (--full)",
+                       "h2d_bytes_per_step": int(h2d_bytes), "pcie_GBps": round(h2d_bytes / (ms_step * 1e-3) / 1e9, 2),
+                       "pipeline_depth": depth, "host_threads": nthreads, "host_threads_note": threads_note or None, "launch": mode,
+                       "parallelism": "blob-sharded x%d, no collective; %s; %d native host threads x %d batches in flight per GPU" % (
+                           n_gpus, "one process, one work queue over all GPUs" if world == 1 else "one process per GPU, RCCL only for barrier/max", nthreads, depth)},
+            "bit_exact": True, "bit_exact_blobs_checked": checked, "topology_fallbacks": int(rep.topology_fallbacks),
+            "steps_per_device": steps_per_device, "per_gpu_mtri_per_s": per_gpu, "numa_local_input_buffers": numa_local_inputs,
+            "scaling_report": None,
+            "steady_state": window_stats(stamps, pool_lanes),
+            "poisoned_lanes": int(rep.poisoned_lanes), "pool_warning": pool_warning or None,
+            "host_us_per_step_per_thread": round(float(rep.host_us_per_step), 1), "numa_pinned_devices": int(rep.pinned_devices),
+            "host_us": {"per_step_per_thread": round(float(rep.host_us_per_step), 1), "plan_walk_bind": round(float(rep.host_plan_us), 1),
+                        "wait_for_a_context": round(float(rep.host_wait_us), 1), "harvest": round(float(rep.host_finish_us), 1)},
+        }
+        if n_gpus > 1:
+            out["scaling_report"] = shard.scaling_report(out["value"], n_gpus, per_gpu, alone, out["host_us_per_step_per_thread"])
+        if share:
+            out["shared_gpu"] = True
+        return out
+
+    if not args.full:
+        pool.close()
+        emit(headline() if rank == 0 else None, n_gpus, dist, full=False)
+        return
 
     # beside `value`: the same pipelined steps with the compressed inputs ALREADY RESIDENT in HBM (what rounds 1-3 quoted as `value`): no PCIe
     # inside the step.  Same region of K steps.
@@ -794,7 +889,6 @@ def main():
     # synthetic blobs - one generator, 256 seeds, the same connectivity - repeat tables far more than unrelated meshes would.
     # (the main pool is closed first: its sixteen contexts' streams would share the sixteen hardware queues with the side pools' - round 3's
     # first side-leg numbers were taken that way and came out 10-30 % under what the same pool does alone, tools/shape_probe.py)
-    pool_lanes, pool_warning = pool.lanes, pool.warning
     pool.close()
     os.environ["CORTO_TUN_SHARE"] = "2"            # one dictionary per stream whatever repeats (still two kernels: dictionaries, then decodes)
     pool_ns = ca.Pool(devices, threads=nthreads, depth=depth)
@@ -917,19 +1011,10 @@ def main():
         pool_s.close()
     first_iter = first_iteration() if (rank == 0 and not args.no_other_configs) else None
 
-    # SURVEY 8e's scaling report when N > 1: per-GPU rate, what ONE of the GPUs does alone on the same box right now (same pool shape, the
-    # other GPUs idle: every rank but 0 waits at the barrier), efficiency = value / (N x that), and the host-side cost per step
-    scaling_block = None
-    tri_step = float(sum(ca.probe(x).nface for x in items[0]))
-    if world > 1:
-        import torch as _t
-        mine = _t.zeros(world, dtype=_t.float64, device=red_dev); mine[rank] = float(rep.triangles) / max(rep.elapsed_s, 1e-9) / 1e6
-        dist.all_reduce(mine, op=dist.ReduceOp.SUM)
-        per_gpu = [round(float(x), 2) for x in mine.tolist()]
-    else:
-        per_gpu = [round(c * tri_step / max(rep.elapsed_s, 1e-9) / 1e6, 2) for c in list(rep.steps_per_device)[:nloc]]
+    # SURVEY 8e's scaling report when N > 1: beside the per-GPU rates of the headline, what ONE of the GPUs does alone on the same box right now
+    # (same pool shape, the other GPUs idle: every rank but 0 waits at the barrier), efficiency = value / (N x that)
+    alone = None
     if n_gpus > 1:
-        alone = None
         barrier()
         if rank == 0:
             pool_1 = ca.Pool(devices[:1], threads=nthreads, depth=depth)
@@ -939,10 +1024,8 @@ def main():
             alone = rep_1.triangles / rep_1.elapsed_s / 1e6
             pool_1.close()
         barrier()
-        scaling_block = {"per_gpu": per_gpu, "alone": alone}                       # (shard.scaling_report, once `value` is known)
-    tris_total = shard.sum_over_ranks(float(rep.triangles), dist, red_dev) / R     # (per K-step region)
-    verts_total = shard.sum_over_ranks(float(rep.vertices), dist, red_dev) / R
     tris_h = shard.sum_over_ranks(float(rep_h.triangles), dist, red_dev)
+    out = None
     if rank == 0:
         ntri, nvert = int(stats0.total_nface), int(stats0.total_nvert)
         ms_step = elapsed / args.steps * 1e3
@@ -961,31 +1044,8 @@ def main():
         dom_ms = kernels[dom]["ms_per_step"] / max(kernels[dom]["launches_per_step"], 1)
         ach = dom_bytes / (dom_ms * 1e-3) / 1e9
         traffic, traffic_note = pmc_traffic(dom)
-        out = {
-            "metric": "Mtriangles/s + Mverts/s decode, 1M-tri batch; bit-exact vs CPU",
-            "value": round(tris_total / elapsed / 1e6, 2), "unit": "Mtri/s",
-            "mverts_per_s": round(verts_total / elapsed / 1e6, 2),
-            "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
-            "timed_regions": {"count": R, "ms_per_step": [round(e / args.steps * 1e3, 4) for e in regions],
-                              "mean_ms_per_step": round(elapsed_mean / args.steps * 1e3, 4), "median_over_mean": round(elapsed / elapsed_mean, 4),
-                              "note": "one region of exactly K timed steps, pipeline full throughout; `value` and `ms_per_step` are that region's"},
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/i32 integer + f32 normals",
-            "data": "synthetic: 256 distinct bumpy-sphere meshes per GPU (seeds 256*g ..), encoded by the repo's byte-identical .crt writer",
-            "config": {"workload": "C4: 256 x (2112 verts / 4096 tris), pos14+uv12+normal10(BORDER)+rgba, per GPU; C5 when n_gpus=8",
-                       "blobs_per_gpu": NBLOBS, "tris_per_gpu": ntri, "verts_per_gpu": nvert,
-                       "timed_region": "SURVEY 8d primary: K x [H2D of the batch's .crt bytes from ONE pinned host buffer + plan(host walk)+bind+kernels+sync] per GPU, "
-                                       "outputs left in HBM; clock from the "
-                                       "completion of the last of W warm-up steps to the completion of the K-th timed step, pipeline full at both ends "
-                                       "(barrier + device sync before the warm-up and after the drain); "
-                                       "the rate with the compressed inputs already resident in HBM (rounds 1-3's `value`) is `resident_inputs`",
-                       "h2d_bytes_per_step": int(stats0.arena_bytes), "pcie_GBps": round(stats0.arena_bytes / (ms_step * 1e-3) / 1e9, 2),
-                       "pipeline_depth": depth, "host_threads": nthreads, "host_threads_note": threads_note or None, "launch": mode,
-                       "parallelism": "blob-sharded x%d, no collective; %s; %d native host threads x %d batches in flight per GPU" % (
-                           n_gpus, "one process, one work queue over all GPUs" if world == 1 else "one process per GPU, RCCL only for barrier/max", nthreads, depth)},
-            "bit_exact": True, "bit_exact_blobs_checked": checked, "topology_fallbacks": int(rep.topology_fallbacks),
-            "steps_per_device": steps_per_device, "per_gpu_mtri_per_s": per_gpu, "numa_local_input_buffers": numa_local_inputs,
-            "scaling_report": None,
-            "steady_state": window_stats(stamps, pool_lanes),
+        out = headline(alone)
+        out.update({
             "resident_inputs": {"mtri_per_s": round(tris_res / elapsed_res / 1e6, 2), "mverts_per_s": round(tris_res / elapsed_res / 1e6 * nvert / ntri, 2),
                                 "ms_per_step": round(elapsed_res / args.steps * 1e3, 4), "regions_ms_per_step": [round(e / args.steps * 1e3, 4) for e in regions_res],
                                 "whole_path_GBps": round(whole_path_bytes / (elapsed_res / args.steps) / 1e9, 2),
@@ -1010,10 +1070,6 @@ def main():
                               "are a second, smaller copy on the same link (profiles/r06_what_was_measured.txt: sending a third of them moved nothing - a step from the host is the link AND the GPU, both nearly full)"}
                      if pcie_caps else None),
             "sustained": sustained,
-            "poisoned_lanes": int(rep.poisoned_lanes), "pool_warning": pool_warning or None,
-            "host_us_per_step_per_thread": round(float(rep.host_us_per_step), 1), "numa_pinned_devices": int(rep.pinned_devices),
-            "host_us": {"per_step_per_thread": round(float(rep.host_us_per_step), 1), "plan_walk_bind": round(float(rep.host_plan_us), 1),
-                        "wait_for_a_context": round(float(rep.host_wait_us), 1), "harvest": round(float(rep.host_finish_us), 1)},
             "scattered_pageable_blobs": {"mtri_per_s": round(tris_h / elapsed_h / 1e6, 2), "ms_per_step": round(elapsed_h / (fhh_steps / nloc) * 1e3, 4), "steps": fhh_steps // nloc,
                                          **window_stats(stamps_h, pool_lanes), "host_us_per_step_per_thread": round(float(rep_h.host_us_per_step), 1),
                                          "note": "the timed region of `value` with the batch's 256 blobs in 256 separate PAGEABLE host arrays: the worker thread gathers them into "
@@ -1038,13 +1094,9 @@ def main():
                            "GBps": round(whole_path_bytes / (ms_step * 1e-3) / 1e9, 2), "peak": 8000.0, "frac_of_8TBps": round(whole_path_bytes / (ms_step * 1e-3) / 1e9 / 8000.0, 6)},
             "kernels": kernels,
             "hbm_ceiling": hbm_ceiling(torch),
-        }
-        if scaling_block:
-            out["scaling_report"] = shard.scaling_report(out["value"], n_gpus, scaling_block["per_gpu"], scaling_block["alone"], out["host_us_per_step_per_thread"])
+        })
         if n1_only_skipped:
             out["n1_only_legs"] = "skipped (cpu_baseline, tunstall_scaled, other_configs, irregular / realistic: see the N = 1 line; --all-legs runs them)"
-        if share:
-            out["shared_gpu"] = True
         if not args.no_tunstall_scaled:
             out["tunstall_scaled"] = tunstall_scaled(ctx, ca, z)
         if not args.no_other_configs and not args.no_tunstall_scaled:
@@ -1056,20 +1108,7 @@ def main():
             out["vs_cpu_1core"] = round(out["value"] / n_gpus / out["cpu_baseline"]["value"], 2)
             if "facade_per_blob" in out:
                 out["facade_per_blob"]["cpu_reference_us"] = round(4096 / out["cpu_baseline"]["value"], 1)
-        contract_error = None
-        try:
-            shard.check_bench_line(out, n_gpus)                               # the contract the driver parses (corto_amd/shard.py; tests/test_sharding_cpu.py runs it on an N = 8 line)
-        except ValueError as e:                                               # a violated check must not discard a multi-minute measurement: the line is printed WITH the
-            contract_error = str(e)                                           # violation named in it, and the exit code says so
-            out["contract_error"] = contract_error
-        print(json.dumps(out), flush=True)
-        if contract_error:
-            print("bench.py: " + contract_error, file=sys.stderr, flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0 and locals().get("contract_error"):
-        raise SystemExit(3)
+    emit(out, n_gpus, dist, full=True)
 
 
 if __name__ == "__main__":

@@ -99,7 +99,7 @@ def scaling_report(value_mtri: float, n_gpus: int, per_gpu_mtri, one_gpu_alone_m
     rep = {"per_gpu_mtri_per_s": [round(float(x), 2) for x in per_gpu_mtri],
            "one_gpu_alone_mtri_per_s": round(float(one_gpu_alone_mtri), 2) if one_gpu_alone_mtri else None,
            "slowest_over_fastest_gpu": round(min(per_gpu_mtri) / max(per_gpu_mtri), 4) if max(per_gpu_mtri) > 0 else None,
-           "note": "per-GPU rate of the timed steps; one_gpu_alone: GPU 0 with the same pool shape and timed region while the other GPUs idle "
+           "note": "per-GPU rate of the timed steps; one_gpu_alone (bench.py --full): GPU 0 with the same pool shape and timed region while the other GPUs idle "
                    "(measured behind the main run, the main pool closed); efficiency_vs_1gpu = value / (n_gpus x one_gpu_alone)"}
     if one_gpu_alone_mtri:
         rep["efficiency_vs_1gpu"] = round(float(value_mtri) / (n_gpus * float(one_gpu_alone_mtri)), 4)
@@ -112,9 +112,10 @@ BENCH_LINE_KEYS = {"metric": str, "value": (int, float), "unit": str, "n_gpus": 
                    "higher_is_better": bool, "scaling": str, "vs_baseline": (type(None), int, float), "dtype": str, "data": str, "config": dict}
 
 
-def check_bench_line(line: dict, n_gpus: int = None) -> None:
+def check_bench_line(line: dict, n_gpus: int = None, full: bool = True) -> None:
     """the contract every bench.py line keeps (the driver parses it): the named keys with their types, config.workload and no model keys,
-    roofline with achieved / peak / frac consistent, scaling "weak", and at N > 1 a scaling report with one rate per GPU.  Raises ValueError."""
+    roofline with achieved / peak / frac consistent, scaling "weak", and at N > 1 a scaling report with one rate per GPU.  The roofline is
+    measured by `bench.py --full` only: a plain run's line (full=False) may leave it out.  Raises ValueError."""
     for k, t in BENCH_LINE_KEYS.items():
         if k not in line:
             raise ValueError("bench line: key %r missing" % k)
@@ -129,10 +130,11 @@ def check_bench_line(line: dict, n_gpus: int = None) -> None:
     if not (line["value"] > 0 and line["ms_per_step"] > 0):
         raise ValueError("bench line: value / ms_per_step not positive")
     r = line.get("roofline")
-    if not isinstance(r, dict) or r.get("bound") not in ("hbm", "mfma") or r.get("unit") not in ("GB/s", "TFLOP/s"):
-        raise ValueError("bench line: roofline block")
-    if abs(r["achieved"] / r["peak"] - r["frac"]) > 1e-4 or not ("traffic" in r):
-        raise ValueError("bench line: roofline.frac is not achieved / peak")
+    if r is not None or full:
+        if not isinstance(r, dict) or r.get("bound") not in ("hbm", "mfma") or r.get("unit") not in ("GB/s", "TFLOP/s"):
+            raise ValueError("bench line: roofline block")
+        if abs(r["achieved"] / r["peak"] - r["frac"]) > 1e-4 or not ("traffic" in r):
+            raise ValueError("bench line: roofline.frac is not achieved / peak")
     if line["n_gpus"] == 1:
         cb = line.get("cpu_baseline")
         if cb is not None and not (isinstance(cb, dict) and {"value", "unit", "cores", "kind", "sample"} <= set(cb) and cb["kind"] in ("reference", "port")):

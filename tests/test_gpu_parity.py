@@ -1762,6 +1762,30 @@ def test_pool_poisons_outputs_before_the_last_steps(c5_blobs):
     pool.close()
 
 
+@pytest.mark.timeout(300)
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: one JSON line that keeps the contract without a roofline, the timed
+    path's outputs checked against the oracle, --dump-outputs written - and none of the legs that --full runs beside it"""
+    import json
+    import subprocess
+    import sys
+    from corto_amd import shard
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(tmp_path)],
+                         cwd=root, capture_output=True, text=True, timeout=280)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    shard.check_bench_line(j, 1, full=False)
+    assert j["steps"] == 20 and j["warmup"] == 5 and j["bit_exact"] is True and j["bit_exact_blobs_checked"] > 0
+    for k in ("roofline", "kernels", "single_batch", "resident_inputs", "sustained", "secondary_region", "first_iteration", "pcie", "hbm_ceiling",
+              "tunstall_scaled", "other_configs", "cpu_baseline"):
+        assert k not in j, k
+    nvert = np.load(str(tmp_path / "nvert.npy"))
+    assert len(nvert) == 256 and np.load(str(tmp_path / "position.npy")).shape == (int(nvert.sum()), 3)
+
+
 @pytest.mark.timeout(600)
 def test_bench_eight_pool_devices_on_one_gpu():
     """`python bench.py --gpus 8` end to end without eight GPUs ($BENCH_SHARE_GPU=1: eight pool devices on this box's one GPU): the
@@ -1772,7 +1796,7 @@ def test_bench_eight_pool_devices_on_one_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BENCH_SHARE_GPU="1")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--no-cpu", "--no-tunstall-scaled",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--full", "--no-cpu", "--no-tunstall-scaled",
                           "--no-other-configs", "--sustain", "0.3", "--host-threads", "1", "--depth", "2"], env=env, cwd=root, capture_output=True, text=True, timeout=560)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -1800,7 +1824,7 @@ def test_bench_two_ranks_under_torch_distributed_run():
             so.bind(("127.0.0.1", 0)); port = so.getsockname()[1]
         out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
                               os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-                              "--sustain", "0.2", "--host-threads", "2", "--depth", "3"], env=env, cwd=root, capture_output=True, text=True, timeout=280)
+                              "--full", "--sustain", "0.2", "--host-threads", "2", "--depth", "3"], env=env, cwd=root, capture_output=True, text=True, timeout=280)
         if out.returncode == 0:
             break
     assert out.returncode == 0, out.stderr[-3000:]

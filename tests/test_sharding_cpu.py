@@ -122,3 +122,21 @@ def test_bench_line_contract_at_one_and_eight_gpus():
             shard.check_bench_line(bad, 8)
     with pytest.raises(ValueError):
         shard.scaling_report(1.0, 8, [1.0] * 7, 1.0)
+
+
+def test_bench_line_contract_of_a_plain_run():
+    """a plain bench.py run (no --full) measures no roofline: its line passes check_bench_line(full=False) without one, the same line
+    fails the --full contract, and every other check still holds"""
+    import copy
+    for n in (1, 8):
+        plain = _canned_line(n)
+        del plain["roofline"]
+        plain.pop("cpu_baseline", None)
+        shard.check_bench_line(plain, n, full=False)
+        with pytest.raises(ValueError):
+            shard.check_bench_line(plain, n)
+        for breakage in (lambda l: l.update(roofline={"bound": "hbm"}), lambda l: l.update(scaling="strong"), lambda l: l.update(value=0), lambda l: l.pop("ms_per_step")):
+            bad = copy.deepcopy(plain)
+            breakage(bad)
+            with pytest.raises(ValueError):
+                shard.check_bench_line(bad, n, full=False)

@@ -7,8 +7,8 @@ timeout 900 python -m pytest tests -m gpu -q > ${O}_suite.txt 2>&1; echo "suite 
 bash tools/prof_run.sh $TAG > ${O}_prof_run.log 2>&1; tail -22 ${O}_prof_run.log | cut -c1-260
 # the counters of THIS build where bench.py looks for them (roofline.traffic is reported only from a file whose stamp is the running build's)
 cp gpurun_out/prof_$TAG/pmc_per_dispatch.json profiles/${TAG}_pmc_per_dispatch.json
-timeout 600 python bench.py --steps 20 --warmup 5 > ${O}_bench_driver.json 2> ${O}_bench_driver.err; echo "bench (driver form) rc $?"
-timeout 600 python bench.py > ${O}_bench.json 2> ${O}_bench.err; echo "bench (default) rc $?"
+timeout 600 python bench.py --full --steps 20 --warmup 5 > ${O}_bench_driver.json 2> ${O}_bench_driver.err; echo "bench (driver form) rc $?"
+timeout 600 python bench.py --full > ${O}_bench.json 2> ${O}_bench.err; echo "bench (default) rc $?"
 python - <<PY
 import json
 for f in ("${O}_bench_driver.json", "${O}_bench.json"):

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-BENCH="python bench.py --steps 20 --warmup 3 --no-cpu --no-other-configs --sustain 0 --depth 1 --host-threads 1"   # unpipelined: every kernel runs alone, as in bench.py's `kernels` phase
+BENCH="python bench.py --full --steps 20 --warmup 3 --no-cpu --no-other-configs --sustain 0 --depth 1 --host-threads 1"   # unpipelined: every kernel runs alone, as in the `kernels` phase of bench.py --full
 timeout 300 timeout 300 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace -o trace -- $BENCH > $OUT/bench_trace.log 2>&1
 # PMC passes: counters only (no trace domains), one small group per pass
 timeout 300 timeout 300 rocprofv3 --output-format csv --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY -d $OUT/pmc1 -o pmc1 -- $BENCH --no-tunstall-scaled > $OUT/bench_pmc1.log 2>&1

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_write
 mkdir -p $OUT; cd $GRAFT_REPO_ROOT
-B="python bench.py --steps 5 --warmup 1 --no-cpu --no-tunstall-scaled --no-other-configs --depth 1 --host-threads 1"
+B="python bench.py --full --steps 5 --warmup 1 --no-cpu --no-tunstall-scaled --no-other-configs --depth 1 --host-threads 1"
 timeout 300 rocprofv3 --output-format csv --pmc WRITE_SIZE -d $OUT/p -o w -- $B > $OUT/log1.txt 2>&1
 timeout 300 rocprofv3 --output-format csv --pmc FETCH_SIZE -d $OUT/p -o f -- $B > $OUT/log2.txt 2>&1
 python - <<PY
