@@ -188,6 +188,17 @@ def test_bit_unpack_kernel_choice_around_the_threshold(ctx, nu, nv):
     b = run_batch(ctx, [blob], color_components=4)
     assert_same(b.host_outputs(0), r, KEYS, "%dx%d (%d vertices)" % (nu, nv, r["nvert"]))
     b.close()
+    # the kernel each block took: the uv block alone, the position block alone (a profiling context: its launch labels)
+    c = ca.Context(0)
+    c.set_profiling(True)
+    for name, logs in (("uv", 2 * r["nvert"]), ("position", r["nvert"])):
+        b = run_batch(c, [blob], only={name, "index"})
+        assert_same(b.host_outputs(0), r, (name, "index"), "%s alone, %d vertices" % (name, r["nvert"]))
+        ran = set(b.kernel_times())
+        want = "unpack_wave" if logs <= 16384 else "unpack_extract"
+        assert want in ran and ({"unpack_wave", "unpack_extract"} - {want}).isdisjoint(ran), (name, r["nvert"], sorted(ran))
+        b.close()
+    c.close()
 
 
 def test_pool_takes_packed_pinned_items_in_place(c5_blobs):
@@ -1457,9 +1468,11 @@ def test_large_and_small_meshes_in_one_batch(ctx):
 
 
 def test_wide_context_on_meshes_beyond_the_lds_records(monkeypatch):
-    """ADVICE r4: with 32-bit records (a context that met values beyond int16, or $CORTO_DELTA_WIDE=1) K-DELTA keeps meshes of up to 32 767 vertices in LDS;
-    33K-66K vertices (16-bit ids would still do) and positions quantised to 18 bits take the tiles out of an LDS ring (k_delta_tiles).  A performance trade-off,
-    not a correctness one: the same bytes as the oracle on both sides of the limit, narrow and wide, rounds forced or not"""
+    """with 32-bit records (a context that met values beyond int16, or $CORTO_DELTA_WIDE=1) K-DELTA keeps an attribute in LDS while its records and the
+    prediction graph fit DELTA16_LDS_MAX: positions (16-byte records) up to 6 552 vertices, N=1 / 2 / 4 up to 13 104 / 9 360 / 5 956 (int16 records: 10 920
+    for positions); bigger meshes - here 2 112 vertices on one side and 33K-66K on the other, positions quantised to 18 bits among them - take the tiles out of an
+    LDS ring (k_delta_tiles).  A performance trade-off, not a correctness one: the same bytes as the oracle, narrow and wide, rounds forced or not.  The last
+    size inside and the first outside of every record limit, wide and narrow: tests/test_size_classes_gpu.py"""
     from corto_amd import synth
     meshes = [synth.bumpy_sphere(260, 128, seed=41), synth.bumpy_sphere(250, 130, seed=42), synth.delaunay_disc(2310, seed=43, holes=5),
               synth.decimated(synth.icosphere(4, seed=44), keep=0.7, seed=44), synth.bumpy_sphere(64, 32, seed=45)]
