@@ -61,6 +61,12 @@ class BatchStats(C.Structure):
                 ("topology_scale", C.c_uint32), ("tunstall_dictionaries", C.c_uint32), ("delta_redone", C.c_uint32), ("delta_walked", C.c_uint32), ("delta_wide", C.c_uint32), ("descriptor_bytes", C.c_uint32), ("int16_streams", C.c_uint32)]
 
 
+class WalkStats(C.Structure):
+    """crthip_walk_stats: where the last create / reset walked the blobs"""
+    _fields_ = [("device_walked", C.c_uint32), ("host_walked", C.c_uint32), ("bytes_to_host", C.c_uint64), ("walk_kernel_us", C.c_float),
+                ("reserved", C.c_uint32)]
+
+
 class MeshDesc(C.Structure):
     _fields_ = [
         ("nvert", C.c_uint32), ("nface", C.c_uint32),
@@ -143,6 +149,15 @@ def lib():
         L.crthip_ctx_set_single_stream.argtypes = [C.c_void_p, C.c_int]
         L.crthip_ctx_sync.argtypes = [C.c_void_p]
         L.crthip_batch_create.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.crthip_batch_create_resident.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.crthip_batch_reset_resident.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.crthip_batch_exif.restype = C.c_int64
+        L.crthip_batch_exif.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
+        L.crthip_batch_groups.restype = C.c_int64
+        L.crthip_batch_groups.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
+        L.crthip_batch_group_props.restype = C.c_int64
+        L.crthip_batch_group_props.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]
+        L.crthip_batch_walk_stats.argtypes = [C.c_void_p, C.POINTER(WalkStats)]
         L.crthip_batch_destroy.argtypes = [C.c_void_p]
         L.crthip_batch_size.argtypes = [C.c_void_p]
         L.crthip_batch_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BlobInfo)]
@@ -471,9 +486,46 @@ class Batch:
         """crthip_batch_reset: re-plan this object for another list of blobs (bindings and outputs are dropped)."""
         self._plan(blobs, device_arena, create=False)
 
+    @classmethod
+    def resident(cls, ctx: Context, buffer, offsets: Sequence[int], lens: Sequence[int]) -> "Batch":
+        """crthip_batch_create_resident: a batch of blobs that live only in device memory - blob i is the lens[i] bytes at byte
+        offsets[i] of `buffer` (a device tensor; offsets multiples of 16, in any order, any subset).  The walk runs on the device;
+        no host copy of the blobs is needed.  Keep `buffer` unchanged until the batch has been synced."""
+        b = cls.__new__(cls)
+        b.ctx = ctx
+        b.handle = C.c_void_p()
+        b._plan_resident(buffer, offsets, lens, create=True)
+        return b
+
+    def reset_resident(self, buffer, offsets: Sequence[int], lens: Sequence[int]):
+        """crthip_batch_reset_resident: re-plan this object for blobs in device memory (see resident); bindings and outputs are dropped"""
+        self._plan_resident(buffer, offsets, lens, create=False)
+
+    def _plan_resident(self, buffer, offsets, lens, create):
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lens_a = np.ascontiguousarray(lens, dtype=np.uint32)
+        if offs.shape != lens_a.shape or offs.ndim != 1:
+            raise ValueError("resident batch: offsets and lens must be two lists of the same length")
+        n = len(offs)
+        self.blobs = None
+        self._n, self.infos = 0, []                  # (a failed create / reset leaves the object empty-handed)
+        self._ptrs, self._lens, self._offsets = None, lens_a, offs
+        self._arena = buffer
+        base = None
+        if buffer is not None:
+            _torch_ready(buffer.device)              # (what torch queued on the buffer runs on its stream; the walk on the context's own)
+            base = C.c_void_p(buffer.data_ptr())
+        if create:
+            _check(lib().crthip_batch_create_resident(self.ctx.handle, n, base, _np_ptr(offs), _np_ptr(lens_a), C.byref(self.handle)))
+        else:
+            _check(lib().crthip_batch_reset_resident(self.handle, n, base, _np_ptr(offs), _np_ptr(lens_a)))
+        self._n = n
+        self._load_infos(n)
+
     def _plan(self, blobs, device_arena, create):
         self.blobs = list(blobs)
         n = len(self.blobs)
+        self._n = n
         self._ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in self.blobs])
         self._lens = np.array([len(b) for b in self.blobs], dtype=np.uint32)
         self._arena = device_arena
@@ -482,6 +534,9 @@ class Batch:
             _check(lib().crthip_batch_create(self.ctx.handle, n, self._ptrs, _np_ptr(self._lens), arena_ptr, C.byref(self.handle)))
         else:
             _check(lib().crthip_batch_reset(self.handle, n, self._ptrs, _np_ptr(self._lens), arena_ptr))
+        self._load_infos(n)
+
+    def _load_infos(self, n):
         self.infos = []
         for i in range(n):
             info = BlobInfo()
@@ -492,7 +547,43 @@ class Batch:
         self._interleaved = None
 
     def __len__(self):
-        return len(self.blobs)
+        return self._n
+
+    # -- what the walk stored ----------------------------------------------------------------------
+    def exif(self, i: int) -> Dict[str, str]:
+        """crthip_batch_exif: blob i's exif pairs (crthip_probe_exif of a planned batch, host or resident)"""
+        n = lib().crthip_batch_exif(self.handle, i, None, 0)
+        if n < 0:
+            _check(int(n))
+        buf = C.create_string_buffer(int(n) + 1)
+        lib().crthip_batch_exif(self.handle, i, buf, n)
+        parts = buf.raw[:n].split(b"\0")[:-1]
+        return {parts[k].decode(): parts[k + 1].decode() for k in range(0, len(parts), 2)}
+
+    def groups(self, i: int) -> List[int]:
+        """crthip_batch_groups: blob i's group end markers"""
+        n = lib().crthip_batch_groups(self.handle, i, None, 0)
+        if n < 0:
+            _check(int(n))
+        g = np.zeros(max(int(n), 1), dtype=np.uint32)
+        lib().crthip_batch_groups(self.handle, i, _np_ptr(g), int(n))
+        return [int(x) for x in g[:n]]
+
+    def group_props(self, i: int, g: int) -> Dict[str, str]:
+        """crthip_batch_group_props: the properties of group g of blob i"""
+        n = lib().crthip_batch_group_props(self.handle, i, g, None, 0)
+        if n < 0:
+            _check(int(n))
+        buf = C.create_string_buffer(int(n) + 1)
+        lib().crthip_batch_group_props(self.handle, i, g, buf, n)
+        parts = buf.raw[:n].split(b"\0")[:-1]
+        return {parts[k].decode(): parts[k + 1].decode() for k in range(0, len(parts), 2)}
+
+    def walk_stats(self) -> WalkStats:
+        """crthip_batch_walk_stats: blobs walked on the device / on the host, bytes the create copied back, the walk kernel's device time"""
+        s = WalkStats()
+        _check(lib().crthip_batch_walk_stats(self.handle, C.byref(s)))
+        return s
 
     # -- outputs -----------------------------------------------------------------------------------
     def allocate_outputs(self, normal_format=FMT_FLOAT, color_components: Optional[int] = None, index16=False,

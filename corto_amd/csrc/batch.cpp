@@ -5,6 +5,7 @@
 // (src/decoder.cpp:133-196) for a whole batch of blobs at once:
 //   decode-all (Tunstall + bit-unpack) -> topology -> delta-all -> postDelta (normals) -> dequantize-all.
 #include "batch_internal.h"
+#include "crt_walk.h"
 
 // ------------------------------------------------------------------------------------------------
 static thread_local std::string g_error;
@@ -58,14 +59,19 @@ extern "C" int crthip_probe(const uint8_t *blob, size_t len, crthip_blob_info *i
 	return CRTHIP_OK;
 }
 
+// key\0value\0... into out when it fits; the bytes needed
+static int64_t flat_pairs(const std::vector<std::pair<std::string, std::string>> &kvs, char *out, size_t cap) {
+	std::string flat;
+	for(auto &kv : kvs) { flat += kv.first; flat.push_back('\0'); flat += kv.second; flat.push_back('\0'); }
+	if(out && cap >= flat.size()) memcpy(out, flat.data(), flat.size());
+	return (int64_t)flat.size();
+}
+
 extern "C" int64_t crthip_probe_exif(const uint8_t *blob, size_t len, char *out, size_t cap) {
 	BlobHeader h;
 	int err = parse_header(blob, len, h);
 	if(err) return fail(err);
-	std::string flat;
-	for(auto &kv : h.exif) { flat += kv.first; flat.push_back('\0'); flat += kv.second; flat.push_back('\0'); }
-	if(out && cap >= flat.size()) memcpy(out, flat.data(), flat.size());
-	return (int64_t)flat.size();
+	return flat_pairs(h.exif, out, cap);
 }
 
 extern "C" int64_t crthip_probe_groups(const uint8_t *blob, size_t len, uint32_t *group_end, size_t cap) {
@@ -81,10 +87,7 @@ extern "C" int64_t crthip_probe_group_props(const uint8_t *blob, size_t len, uin
 	int err = walk_blob(blob, len, L);
 	if(err) return fail(err);
 	if(g >= L.group_props.size()) return fail(CRTHIP_E_ARGUMENT);
-	std::string flat;
-	for(auto &kv : L.group_props[g]) { flat += kv.first; flat.push_back('\0'); flat += kv.second; flat.push_back('\0'); }
-	if(out && cap >= flat.size()) memcpy(out, flat.data(), flat.size());
-	return (int64_t)flat.size();
+	return flat_pairs(L.group_props[g], out, cap);
 }
 
 extern "C" uint64_t crthip_arena_layout(uint32_t nblobs, const uint32_t *lens, uint64_t *offsets) {
@@ -256,6 +259,9 @@ extern "C" void crthip_ctx_destroy(crthip_ctx *c) {
 	if(c->host_batch) { crthip_batch *hb = c->host_batch; c->host_batch = nullptr; crthip_batch_destroy(hb); }
 	c->scratch.release(); c->staging.release(); c->arena_pin.release(); c->status_host.release(); c->host_out.release();
 		c->host_pin.release();
+	c->walk_dev.release(); c->walk_pin.release();
+	if(c->ev_walk0) (void)hipEventDestroy(c->ev_walk0);
+	if(c->ev_walk1) (void)hipEventDestroy(c->ev_walk1);
 	if(c->stream2) (void)hipStreamSynchronize(c->stream2);
 	(void)hipEventDestroy(c->ev_fork); (void)hipEventDestroy(c->ev_join); (void)hipEventDestroy(c->ev_done);
 	if(c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -301,6 +307,8 @@ static int batch_fill(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs, const u
 	b->ctx = ctx;
 	b->blobs.resize(nblobs);
 	b->stats = crthip_batch_stats{};
+	b->walk = crthip_walk_stats{};
+	b->walk.host_walked = nblobs;
 	b->dirty = true; b->decoded = false;
 	uint64_t off = 0;
 	for(uint32_t i = 0; i < nblobs; i++) {
@@ -383,6 +391,102 @@ extern "C" int crthip_batch_reset(crthip_batch *b, uint32_t nblobs, const uint8_
 	return batch_fill(ctx, b, nblobs, blobs, lens, device_arena);       // on failure the batch is left empty-handed: reset or destroy it
 }
 
+// (re)fill a batch object from blobs that live in device memory: k_walk_blobs walks them on the context's main stream (one wave and one
+// record a blob), the records come back in one copy, and the host turns each into the layout walk_blob would have returned.  A blob whose
+// layout does not fit its record is copied back alone and walked here.  On failure the batch is left empty-handed.
+static int batch_fill_resident(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs, const uint8_t *base, const uint64_t *offsets,
+	const uint32_t *lens) {
+	const double t_create = now_us();
+	b->ctx = ctx;
+	b->blobs.clear(); b->status.clear(); b->d_arena = nullptr; b->arena_bytes = 0;
+	b->stats = crthip_batch_stats{};
+	b->walk = crthip_walk_stats{};
+	b->dirty = true; b->decoded = false;
+	for(uint32_t i = 0; i < nblobs; i++)
+		if(offsets[i] & 15) return fail(CRTHIP_E_ARGUMENT, "resident blob offsets must be multiples of 16 (blob " + std::to_string(i) + ")");
+	const uint32_t cap = WALK_RECORD_BYTES;
+	const size_t jobs_bytes = ((size_t)nblobs*sizeof(WalkJob) + 255) & ~(size_t)255, rec_bytes = (size_t)nblobs*cap;
+	uint8_t *recs = nullptr;
+	if(nblobs) {
+		if(ctx->walk_dev.reserve(jobs_bytes + rec_bytes) != CRTHIP_OK || ctx->walk_pin.reserve(jobs_bytes + rec_bytes) != CRTHIP_OK)
+			return fail(CRTHIP_E_NOMEM);
+		if(!ctx->ev_walk0 && hipEventCreate(&ctx->ev_walk0) != hipSuccess) { ctx->ev_walk0 = nullptr; return fail(CRTHIP_E_DEVICE); }
+		if(!ctx->ev_walk1 && hipEventCreate(&ctx->ev_walk1) != hipSuccess) { ctx->ev_walk1 = nullptr; return fail(CRTHIP_E_DEVICE); }
+		uint8_t *d = (uint8_t *)ctx->walk_dev.p, *h = (uint8_t *)ctx->walk_pin.p;
+		WalkJob *jobs = (WalkJob *)h;
+		for(uint32_t i = 0; i < nblobs; i++) jobs[i] = WalkJob{offsets[i], lens[i], 0};
+		// behind whatever the stream holds (another batch's decode: this waits for it), then one synchronisation
+		hipStream_t st = ctx->stream;
+		bool ok = hipMemcpyAsync(d, h, (size_t)nblobs*sizeof(WalkJob), hipMemcpyHostToDevice, st) == hipSuccess &&
+		          hipEventRecord(ctx->ev_walk0, st) == hipSuccess;
+		if(ok) {
+			hipLaunchKernelGGL(k_walk_blobs, dim3(nblobs), dim3(64), 0, st, base, (const WalkJob *)d, nblobs, d + jobs_bytes, cap);
+			ok = hipGetLastError() == hipSuccess && hipEventRecord(ctx->ev_walk1, st) == hipSuccess &&
+			     hipMemcpyAsync(h + jobs_bytes, d + jobs_bytes, rec_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
+		}
+		const bool synced = hipStreamSynchronize(st) == hipSuccess;
+		if(!ok || !synced) { (void)hipGetLastError(); return fail(CRTHIP_E_DEVICE, "the device walk of resident blobs failed"); }
+		ctx->arena_upload_pending = false; ctx->done_covers_seq = ctx->upload_seq;
+		float ms = 0.f;
+		if(hipEventElapsedTime(&ms, ctx->ev_walk0, ctx->ev_walk1) == hipSuccess) b->walk.walk_kernel_us = ms*1000.f;
+		b->walk.bytes_to_host = rec_bytes;
+		recs = h + jobs_bytes;
+	}
+	b->blobs.resize(nblobs);
+	std::vector<uint32_t> copy;                                    // a fallback blob, 4-byte aligned
+	uint64_t bytes = 0;
+	for(uint32_t i = 0; i < nblobs; i++) {
+		BlobPlan &P = b->blobs[i];
+		reset_layout(P.L);
+		int err = record_to_layout(recs + (size_t)i*cap, cap, P.L);
+		if(err == WALK_FALLBACK) {
+			reset_layout(P.L);
+			copy.resize(((size_t)lens[i] + 3)/4 + 1);
+			if(lens[i] && (hipMemcpyAsync(copy.data(), base + offsets[i], lens[i], hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+			   hipStreamSynchronize(ctx->stream) != hipSuccess)) {
+				(void)hipGetLastError(); b->blobs.clear(); return fail(CRTHIP_E_DEVICE, "copying resident blob " + std::to_string(i) + " back");
+			}
+			b->walk.host_walked++; b->walk.bytes_to_host += lens[i];
+			err = walk_blob((const uint8_t *)copy.data(), lens[i], P.L);
+		} else b->walk.device_walked++;
+		if(err) { b->blobs.clear(); return fail(err, std::string(crthip_strerror(err)) + " (blob " + std::to_string(i) + ")"); }
+		P.arena_off = offsets[i]; P.len = lens[i];
+		P.bind.assign(P.L.h.attrs.size(), Binding{});
+		P.index = nullptr; P.index_u16 = 0; P.host_status = 0;
+		P.dbg_clers = P.dbg_pred = ~0ull; P.dbg_nclers = 0; P.clers_in_arena = false;
+		bytes += ((uint64_t)lens[i] + 15) & ~15ull;
+		b->stats.total_nvert += P.L.h.nvert; b->stats.total_nface += P.L.h.nface;
+		if(P.L.h.nface) { b->stats.clers_symbols += P.L.clers.size; b->stats.split_bytes += (uint64_t)P.L.split.nwords*4; }
+	}
+	b->arena_bytes = bytes;
+	b->stats.arena_bytes = bytes;
+	b->d_arena = base;
+	b->status.assign(nblobs, 0);
+	b->stats.host_create_us = (float)(now_us() - t_create);
+	return CRTHIP_OK;
+}
+
+extern "C" int crthip_batch_create_resident(crthip_ctx *ctx, uint32_t nblobs, const void *device_base, const uint64_t *offsets,
+                                            const uint32_t *lens, crthip_batch **out) {
+	if(!ctx || !out || (nblobs && (!device_base || !offsets || !lens)) || ((uintptr_t)device_base & 15)) return fail(CRTHIP_E_ARGUMENT);
+	HIP_TRY(hipSetDevice(ctx->device));
+	crthip_batch *b = new crthip_batch();
+	const int err = batch_fill_resident(ctx, b, nblobs, (const uint8_t *)device_base, offsets, lens);
+	if(err) { delete b; return err; }
+	*out = b;
+	return CRTHIP_OK;
+}
+
+extern "C" int crthip_batch_reset_resident(crthip_batch *b, uint32_t nblobs, const void *device_base, const uint64_t *offsets,
+                                           const uint32_t *lens) {
+	if(!b || !b->ctx || (nblobs && (!device_base || !offsets || !lens)) || ((uintptr_t)device_base & 15)) return fail(CRTHIP_E_ARGUMENT);
+	crthip_ctx *ctx = b->ctx;
+	HIP_TRY(hipSetDevice(ctx->device));
+	if(ctx->in_flight == b) { if(harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE); }
+	if(ctx->last_decoded == b) ctx->last_decoded = nullptr;
+	return batch_fill_resident(ctx, b, nblobs, (const uint8_t *)device_base, offsets, lens);
+}
+
 extern "C" void crthip_batch_destroy(crthip_batch *b) {
 	if(!b) return;
 	if(b->ctx) {
@@ -400,6 +504,29 @@ extern "C" uint32_t crthip_batch_size(const crthip_batch *b) { return b ? (uint3
 extern "C" int crthip_batch_info(const crthip_batch *b, uint32_t i, crthip_blob_info *info) {
 	if(!b || !info || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT);
 	fill_info(b->blobs[i].L.h, info);
+	return CRTHIP_OK;
+}
+
+extern "C" int64_t crthip_batch_exif(const crthip_batch *b, uint32_t i, char *out, size_t cap) {
+	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT);
+	return flat_pairs(b->blobs[i].L.h.exif, out, cap);
+}
+
+extern "C" int64_t crthip_batch_groups(const crthip_batch *b, uint32_t i, uint32_t *group_end, size_t cap) {
+	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT);
+	const BlobLayout &L = b->blobs[i].L;
+	for(size_t k = 0; k < L.group_end.size() && k < cap; k++) group_end[k] = L.group_end[k];
+	return (int64_t)L.group_end.size();
+}
+
+extern "C" int64_t crthip_batch_group_props(const crthip_batch *b, uint32_t i, uint32_t g, char *out, size_t cap) {
+	if(!b || i >= b->blobs.size() || g >= b->blobs[i].L.group_props.size()) return fail(CRTHIP_E_ARGUMENT);
+	return flat_pairs(b->blobs[i].L.group_props[g], out, cap);
+}
+
+extern "C" int crthip_batch_walk_stats(const crthip_batch *b, crthip_walk_stats *s) {
+	if(!b || !s) return fail(CRTHIP_E_ARGUMENT);
+	*s = b->walk;
 	return CRTHIP_OK;
 }
 

@@ -158,6 +158,10 @@ struct crthip_ctx {
 	PinnedBuf staging;        // host image of the job arrays
 	PinnedBuf arena_pin;      // host image of a batch's blobs on their way to the device (batch_fill: one H2D copy, not waited for)
 	PinnedBuf status_host;
+	// crthip_batch_create_resident: the walk's jobs + records on the device and their pinned host image; its two timing events (made on first use)
+	DeviceBuf walk_dev;
+	PinnedBuf walk_pin;
+	hipEvent_t ev_walk0 = nullptr, ev_walk1 = nullptr;
 	bool profiling = false;
 	KernelTimer timer;
 	crthip_batch *in_flight = nullptr;   // decode enqueued, status not harvested yet
@@ -217,6 +221,7 @@ struct crthip_batch {
 	uint64_t arena_bytes = 0;
 	bool dirty = true;
 	crthip_batch_stats stats{};
+	crthip_walk_stats walk{};
 	std::vector<int32_t> status;
 	bool decoded = false;
 	bool planned_wide = false;          // the decode in flight was planned with K-DELTA's 32-bit layout

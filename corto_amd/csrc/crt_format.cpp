@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "../../include/corto_hip.h"
+#include "crt_walk.h"
 
 namespace corto_hip {
 namespace {
@@ -104,7 +105,71 @@ StreamRef byte_block(Cursor &c, uint32_t entropy, int &err) {
 	return s;
 }
 
+int groups(Cursor &c, BlobLayout &L) {                       // index_attribute.h:89-99
+	uint32_t ngroups = c.u32();
+	if(!c.need((size_t)ngroups * 5)) return CRTHIP_E_TRUNCATED;
+	L.group_end.resize(ngroups);
+	L.group_props.resize(ngroups);
+	for(uint32_t g = 0; g < ngroups && !c.bad; g++) {
+		L.group_end[g] = c.u32();
+		uint32_t np = c.u8();
+		for(uint32_t k = 0; k < np && !c.bad; k++) { std::string key = c.str(), val = c.str(); L.group_props[g].push_back({key, val}); }
+	}
+	return CRTHIP_OK;
+}
+
+// the body items of a walk record (crt_walk.h), bounds-checked: a record that does not hold what its head says is walked on the host
+struct Items {
+	const uint8_t *p; uint32_t len, pos = 0;
+	template <class T> const uint8_t *take(T &v) {
+		if(sizeof(T) > len - pos) return nullptr;
+		const uint8_t *q = p + pos; std::memcpy(&v, q, sizeof(T)); pos += (uint32_t)sizeof(T); return q;
+	}
+	bool stream(StreamRef &s) {
+		WalkStream w;
+		if(!take(w) || w.nprobs > 32 || ((w.nprobs + 3) & ~3u) > len - pos) return false;
+		s.mode = w.mode; s.nsym = w.nsym; s.fill = w.fill; s.max_sym = w.max_sym;
+		s.probs_off = w.probs_off; s.size = w.size; s.csize = w.csize; s.payload_off = w.payload_off;
+		std::memcpy(s.probs16, p + pos, w.nprobs);
+		pos += (w.nprobs + 3) & ~3u;
+		return true;
+	}
+};
+
 } // namespace
+
+int record_to_layout(const uint8_t *rec, uint32_t rec_cap, BlobLayout &L) {
+	WalkHead h;
+	if(rec_cap < sizeof(h)) return WALK_FALLBACK;
+	std::memcpy(&h, rec, sizeof(h));
+	if(h.status) return h.status;
+	if(h.flags & WALK_OVERFLOW) return WALK_FALLBACK;
+	const uint32_t pre = (uint32_t)sizeof(WalkHead);
+	if(h.prefix_len > rec_cap - pre || h.items_off > rec_cap || h.items_len > rec_cap - h.items_off) return WALK_FALLBACK;
+	// header and groups from the blob's own bytes, by the code walk_blob runs on them
+	Cursor c{rec + pre, h.prefix_len};
+	if(header(c, L.h) || groups(c, L) || c.bad || c.pos != h.prefix_len || L.h.attrs.size() != h.nattr) return WALK_FALLBACK;
+	Items it{rec + h.items_off, h.items_len};
+	if(L.h.nface > 0) {
+		L.max_front = h.max_front;
+		if(!it.stream(L.clers)) return WALK_FALLBACK;
+		L.split.words_off = h.split_off; L.split.nwords = h.split_nwords;
+	}
+	L.attrs.resize(L.h.attrs.size());
+	for(size_t i = 0; i < L.h.attrs.size(); i++) {
+		AttrStreams &s = L.attrs[i];
+		WalkAttrItem a;
+		if(!it.take(a)) return WALK_FALLBACK;
+		s.bits.words_off = a.bits_off; s.bits.nwords = a.bits_nwords;
+		s.normal_prediction = a.normal_prediction;
+		for(int k = 0; k < 4; k++) s.qc[k] = a.qc[k];
+		s.logs.resize(a.nlogs);
+		for(uint32_t k = 0; k < a.nlogs; k++) if(!it.stream(s.logs[k])) return WALK_FALLBACK;
+	}
+	if(it.pos != it.len) return WALK_FALLBACK;
+	L.end_offset = h.end_offset;
+	return CRTHIP_OK;
+}
 
 int parse_header(const uint8_t *p, size_t len, BlobHeader &h) {
 	Cursor c{p, len};
@@ -127,15 +192,7 @@ int walk_blob(const uint8_t *p, size_t len, BlobLayout &L) {
 	if(err) return err;
 	const uint32_t entropy = L.h.entropy;
 
-	uint32_t ngroups = c.u32();                              // index_attribute.h:89-99
-	if(!c.need((size_t)ngroups * 5)) return CRTHIP_E_TRUNCATED;
-	L.group_end.resize(ngroups);
-	L.group_props.resize(ngroups);
-	for(uint32_t g = 0; g < ngroups && !c.bad; g++) {
-		L.group_end[g] = c.u32();
-		uint32_t np = c.u8();
-		for(uint32_t k = 0; k < np && !c.bad; k++) { std::string key = c.str(), val = c.str(); L.group_props[g].push_back({key, val}); }
-	}
+	if((err = groups(c, L))) return err;
 	if(L.h.nface > 0) {                                      // index_attribute.h:83-87
 		L.max_front = c.u32();
 		L.clers = byte_block(c, entropy, err);

@@ -74,5 +74,8 @@ struct BlobLayout {
 int parse_header(const uint8_t *p, size_t len, BlobHeader &h);
 int walk_blob(const uint8_t *p, size_t len, BlobLayout &L);      // L must be fresh, or reset_layout()
 void reset_layout(BlobLayout &L);                                 // back to the default state, keeping every vector's capacity
+// a walk record of crt_walk.h (rec_cap bytes) -> the layout walk_blob returns for the same blob: CRTHIP_OK (L filled; L must be fresh, or
+// reset_layout()), the blob's CRTHIP_E_* code, or WALK_FALLBACK: the record does not hold the layout, walk the blob's bytes on the host
+int record_to_layout(const uint8_t *rec, uint32_t rec_cap, BlobLayout &L);
 
 } // namespace corto_hip

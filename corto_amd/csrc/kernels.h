@@ -27,6 +27,10 @@ inline uint32_t xcd_grid(uint32_t n) { return 8u*((n + 7u) >> 3); }
 __global__ void k_fill(const FillJob *jobs, uint32_t njobs);
 __global__ void k_fill_block(uint8_t *dst, uint64_t bytes, uint32_t value);
 
+// k_walk.hip: one wave per blob walks the blob at base + off (16-byte aligned) and writes its crt_walk.h record to records + i*rec_cap
+struct WalkJob { uint64_t off; uint32_t len, pad; };
+__global__ void k_walk_blobs(const uint8_t *base, const WalkJob *jobs, uint32_t nblobs, uint8_t *records, uint32_t rec_cap);
+
 // k_stream.hip
 __global__ void k_scan_u64(uint64_t *a, uint32_t n);
 __global__ void k_u32_chunk_sums(const uint32_t *a, uint32_t n, uint64_t *partial);

@@ -39,7 +39,8 @@ extern "C" {
                                   4: integer / DOUBLE output formats of generic attributes, crthip_pool_device_cpus; 5: crthip_pool_set_outputs_to_host;
                                   6: crthip_pool_set_render_layouts, crthip_kernel_times names are the kernels' (unpack_wave, delta_lds16);
                                      added within 6: crthip_generic_attr, crthip_attr_list, crthip_encode_attrs, crthip_encode_gpu_attrs,
-                                     crthip_encode_batch_attrs */
+                                     crthip_encode_batch_attrs, crthip_batch_create_resident, crthip_batch_reset_resident, crthip_batch_exif,
+                                     crthip_batch_groups, crthip_batch_group_props, crthip_batch_walk_stats */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -167,12 +168,45 @@ int crthip_batch_create(crthip_ctx *ctx, uint32_t nblobs, const uint8_t *const *
 /* Re-plan an existing batch object for a new list of blobs (same meaning as destroy + create, bindings are cleared) reusing
  * its allocations: what a serving loop that decodes batch after batch on one context calls instead of create / destroy. */
 int crthip_batch_reset(crthip_batch *b, uint32_t nblobs, const uint8_t *const *blobs, const uint32_t *lens, const void *device_arena);
+/* Blobs that live ONLY in device memory (a VRAM cache of compressed tiles, bytes read straight into a device tensor, another kernel's
+ * output): blob i is the lens[i] bytes at device_base + offsets[i].  offsets / lens are HOST arrays; the offsets need not follow
+ * crthip_arena_layout, ascend or be contiguous - a batch may pick any subset of a large buffer, a blob more than once.  The walk of
+ * crthip_batch_create runs on the device (one wave per blob, on the context's main stream) and only a fixed record per blob comes back
+ * (crthip_batch_walk_stats); a blob whose layout does not fit its record (kilobytes of exif, hundreds of log streams) is copied back
+ * alone and walked on the host.  The call waits for that walk: one synchronisation of the context's main stream, so a create on a
+ * context whose other batch is still decoding waits behind that decode (the round-robin pattern of INTEGRATION.md §3 finds the
+ * stream idle).
+ * The caller's rules:
+ *   - device_base and every offset are multiples of 16, else CRTHIP_E_ARGUMENT (as is a NULL device_base with nblobs > 0);
+ *   - [offset, offset + lens[i] rounded up to 16) lies inside one allocation (the device reads whole 16-byte words);
+ *   - the caller's writes to the buffer have completed before the call ("Device buffers" above), and the buffer stays unchanged
+ *     until the batch has been synced.
+ * Errors as for crthip_batch_create: the first failing blob's code, "(blob i)" in crthip_last_error().  A failed reset leaves the
+ * object empty-handed.  Afterwards info, bind, decode, sync, stats and crthip_batch_reset work as for a host-created batch, and one
+ * object may switch between host and resident resets. */
+int crthip_batch_create_resident(crthip_ctx *ctx, uint32_t nblobs, const void *device_base, const uint64_t *offsets, const uint32_t *lens,
+                                 crthip_batch **out);
+int crthip_batch_reset_resident(crthip_batch *b, uint32_t nblobs, const void *device_base, const uint64_t *offsets, const uint32_t *lens);
 /* offsets[i] = arena byte offset of blob i under the rule above; returns total arena bytes */
 uint64_t crthip_arena_layout(uint32_t nblobs, const uint32_t *lens, uint64_t *offsets);
 void crthip_batch_destroy(crthip_batch *b);
 
 uint32_t crthip_batch_size(const crthip_batch *b);
 int crthip_batch_info(const crthip_batch *b, uint32_t i, crthip_blob_info *info);
+/* crthip_probe_exif / _groups / _group_props of blob i of a planned batch, from what its walk stored: the same for a batch created
+ * from host or from device memory. */
+int64_t crthip_batch_exif(const crthip_batch *b, uint32_t i, char *out, size_t cap);
+int64_t crthip_batch_groups(const crthip_batch *b, uint32_t i, uint32_t *group_end, size_t cap);
+int64_t crthip_batch_group_props(const crthip_batch *b, uint32_t i, uint32_t g, char *out, size_t cap);
+/* Where the last create / reset walked the blobs. */
+typedef struct {
+	uint32_t device_walked;      /* blobs walked on the device (a resident create) */
+	uint32_t host_walked;        /* blobs walked on the host: every blob of a host create, a resident create's fallbacks */
+	uint64_t bytes_to_host;      /* device-to-host bytes of the create: the walk records and the fallback blobs */
+	float walk_kernel_us;        /* device time of the walk kernel (0 for a host create) */
+	uint32_t reserved;
+} crthip_walk_stats;
+int crthip_batch_walk_stats(const crthip_batch *b, crthip_walk_stats *s);
 
 /* Bind outputs of blob i. attrs has info.nattr entries in info.attr order. index: DEVICE pointer to
  * nface*3 entries of index_format (CRTHIP_FMT_UINT32 or CRTHIP_FMT_UINT16), NULL for point clouds. */
