@@ -180,6 +180,7 @@ int harvest(crthip_ctx *ctx) {
 
 namespace corto_hip {
 int ctx_device(crthip_ctx *ctx) { return ctx->device; }
+int ctx_encode_topology(crthip_ctx *ctx) { return ctx->encode_topology; }
 hipStream_t ctx_stream(crthip_ctx *ctx) { return ctx->stream; }
 // on the context's main stream, ordered before its next decode
 int ctx_fill_async(crthip_ctx *ctx, void *dst, size_t bytes, int value) {
@@ -243,6 +244,7 @@ extern "C" int crthip_ctx_create(int device, crthip_ctx **out) {
 	   hipFuncSetAttribute((const void *)k_topology_lds_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TOPO_LDS_MAX) != hipSuccess ||
 	   hipFuncSetAttribute((const void *)k_delta_lds16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DELTA16_LDS_MAX) != hipSuccess ||
 	   hipFuncSetAttribute((const void *)k_normal_blob, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NORMAL_LDS_MAX) != hipSuccess ||
+	   hipFuncSetAttribute((const void *)k_enc_topo_walk<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ENC_TOPO_LDS_MAX) != hipSuccess ||
 	   hipFuncSetAttribute((const void *)k_enc_tun_parse, hipFuncAttributeMaxDynamicSharedMemorySize,
 	   	(int)enc_parse_lds(ENC_TRIE_LDS_MAX)) != hipSuccess) {
 		crthip_ctx_destroy(c); return fail(CRTHIP_E_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
@@ -278,6 +280,14 @@ extern "C" int crthip_ctx_set_profiling(crthip_ctx *c, int enable) {
 extern "C" int crthip_ctx_set_packed_host_blobs(crthip_ctx *c, int on) {
 	if(!c) return fail(CRTHIP_E_ARGUMENT);
 	c->packed_host = on != 0;
+	return CRTHIP_OK;
+}
+
+extern "C" int crthip_ctx_set_encode_topology(crthip_ctx *c, int where) {
+	if(!c) return fail(CRTHIP_E_ARGUMENT);
+	if(where != CRTHIP_TOPOLOGY_HOST && where != CRTHIP_TOPOLOGY_DEVICE && where != CRTHIP_TOPOLOGY_SPLIT)
+		return fail(CRTHIP_E_ARGUMENT, "crthip_ctx_set_encode_topology: unknown mode");
+	c->encode_topology = where;
 	return CRTHIP_OK;
 }
 

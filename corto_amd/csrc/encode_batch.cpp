@@ -2,7 +2,9 @@
 // to crthip_encode of that item.
 //
 // The serial part - the CLERS topology pass, which reads the index alone - runs on a pool of host threads while the device
-// quantises (encoder.cpp: batch_topology).  Everything per vertex runs on the device and stays resident until the coded streams
+// quantises (encoder.cpp: batch_topology), or, where the context asks for it (crthip_ctx_set_encode_topology), on the device behind the
+// quantiser (k_encode_topo.hip, enc_topology.h): the compacted faces, the quads and the CLERS symbols are then written where the next
+// kernels read them, and one record per mesh comes back for its frame (encoder.cpp: batch_frame).  Everything per vertex runs on the device and stays resident until the coded streams
 // come back (k_encode_batch.hip): quantisation, estimated normals, residuals, the point clouds' Morton sort (one cloud after
 // another: each has its own launches), then the value and
 // Tunstall coders (encode_gpu.cpp: encode_value_streams_device).  The host splices every container from its frame and the coded
@@ -22,6 +24,7 @@
 
 #include "../../include/corto_hip.h"
 #include "device_plan.h"
+#include "enc_topology.h"
 #include "encoder_internal.h"
 #include "kernels.h"
 
@@ -80,6 +83,7 @@ struct Slot {
 	uint64_t faces = 0, quads = 0, boundary = 0, count = 0;
 	uint64_t zkeys[2] = {0, 0}, zvals[2] = {0, 0}, zhist = 0, zmn = 0;
 	uint64_t clers = 0;
+	uint64_t idx = 0, gend_in = 0, gend_out = 0, first = 0, cursor = 0, sides = 0, twin = 0, state = 0, split = 0;   // the device topology pass
 	uint32_t fbase = 0;                   // first face in the faces region (faces units)
 };
 
@@ -91,6 +95,14 @@ uint64_t item_bytes(const BatchItem &it) {
 		b += al((uint64_t)it.nface_in*12) + al((uint64_t)it.nvert_in*16) + al((uint64_t)it.nvert_in*4) + al(it.nface_in*8ull + 64);
 		for(const BatchAttr &a : it.attrs) if(est_of(it, a)) b += 2*(al((uint64_t)it.nface_in*12) + al((uint64_t)it.nface_in*12)) + al(256ull*4*rs_blocks(3*it.nface_in));
 	} else b += 2*al((uint64_t)it.nvert_in*8) + 2*al((uint64_t)it.nvert_in*4) + al((uint64_t)it.nvert_in*16) + al(256ull*4*rs_blocks(it.nvert_in)) + 512;
+	// the device topology pass: raw index and group ends, bucket tables, sides, twins, the walk's global image, split words (private and
+	// packed), record; in every mode but HOST the CLERS symbols have their place in the image
+	if(it.topo_device) {
+		const uint64_t nf = it.nface_in, nv = it.nvert_in;
+		b += al(nf*12) + 2*al(it.topo_groups*4ull) + al((nv + 1)*4) + al(nv*4) + al(nf*3*sizeof(EncTopoSide)) + al(nf*12) + 2*al(enc_topo_split_cap(it.nface_in)*4) + 1024;
+		if(!it.topo_lds) b += al(enc_topo_state_bytes<uint32_t>(it.nface_in, it.nvert_in));
+	}
+	if(it.topo_image) b += al(enc_topo_clers_cap(it.nface_in));
 	return b + 4096;
 }
 
@@ -101,7 +113,13 @@ struct Timer {
 	int end(hipStream_t st) { BT_TRY(hipEventRecord(b, st)); return 0; }
 	float ms() { float m = 0; if(used && hipEventElapsedTime(&m, a, b) != hipSuccess) m = 0; return m; }
 };
-struct BatchTimes { float quant = 0, est = 0, delta = 0, zkeys = 0, zsort = 0; uint32_t n_quant = 0, n_est = 0, n_delta = 0, n_zkeys = 0, n_zsort = 0; };
+struct BatchTimes { float quant = 0, est = 0, delta = 0, zkeys = 0, zsort = 0, topo_c = 0, topo_p = 0, topo_w = 0;
+                    uint32_t n_quant = 0, n_est = 0, n_delta = 0, n_zkeys = 0, n_zsort = 0, n_topo_c = 0, n_topo_p = 0, n_topo_w = 0; };
+struct Event {
+	hipEvent_t e = nullptr;
+	~Event() { if(e) (void)hipEventDestroy(e); }
+	int record(hipStream_t st) { if(!e) BT_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); BT_TRY(hipEventRecord(e, st)); return 0; }
+};
 
 // LSD radix sort of n records in (k0, v0) by key bits [0, bits), ping-ponging through (k1, v1); returns which buffer holds the result
 template <typename K>
@@ -127,18 +145,26 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_list
               std::vector<std::vector<uint8_t>> &blobs, crthip_encode_batch_stats &S, BatchTimes &bt, EncStageTimes &tm) {
 	hipStream_t st = ctx_stream(ctx);
 	const uint32_t n = (uint32_t)ids.size();
+	const int mode = ctx_encode_topology(ctx);
+	// whose topology pass runs where: devk on the device (CRTHIP_TOPOLOGY_DEVICE: every mesh, _SPLIT: those that walk in LDS), hostk
+	// (the other meshes, and every cloud's frame) on the host
+	std::vector<uint32_t> hostk, devk;
+	for(uint32_t k = 0; k < n; k++) (items[ids[k]].topo_device ? devk : hostk).push_back(k);
 	// topology passes (meshes) and frames (everything) on the pool, started first: they need the index alone
 	std::vector<uint8_t> ready(n, 0);
+	for(uint32_t k : devk) ready[k] = 1;
 	std::mutex mu; std::condition_variable cv;
 	double topo_ms = 0;
 	const auto t_topo = Clock::now();
-	std::thread pool([&]() {
-		parallel_for(n, threads, [&](uint32_t k) {
-			const int32_t e = item_guard([&] { batch_topology(&meshes[ids[k]], extra ? &extra[ids[k]] : nullptr, items[ids[k]]); });
-			if(e) items[ids[k]].status = e;                      // read by this thread's caller only after the join
-			{ std::lock_guard<std::mutex> g(mu); ready[k] = 1; }
-			cv.notify_all();
-		});
+	auto host_pass = [&](uint32_t k) {
+		const int32_t e = item_guard([&] { batch_topology(&meshes[ids[k]], extra ? &extra[ids[k]] : nullptr, items[ids[k]]); });
+		if(e) items[ids[k]].status = e;                      // read by this thread's caller only after the join
+		{ std::lock_guard<std::mutex> g(mu); ready[k] = 1; }
+		cv.notify_all();
+	};
+	std::thread pool;
+	if(mode != CRTHIP_TOPOLOGY_DEVICE) pool = std::thread([&]() {      // (device mode starts no thread: the clouds' frames are made inline below)
+		parallel_for((uint32_t)hostk.size(), threads, [&](uint32_t j) { host_pass(hostk[j]); });
 		std::lock_guard<std::mutex> g(mu);
 		topo_ms = ms_since(t_topo);
 	});
@@ -147,20 +173,24 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_list
 	// ---- layout: raw inputs first (one upload), then everything else ----
 	std::vector<Slot> slot(n);
 	uint64_t o = 0;
-	for(int big = 0; big < 2; big++)                          // the small inputs first: they go up staged, in one copy
-		for(uint32_t k = 0; k < n; k++) {
-			const BatchItem &it = items[ids[k]];
-			slot[k].in.resize(it.attrs.size()); slot[k].q.resize(it.attrs.size()); slot[k].d.resize(it.attrs.size());
-			for(size_t a = 0; a < it.attrs.size(); a++) {
-				const uint64_t b = quant_in_bytes(it.attrs[a].quant);
-				if((b >= DIRECT_BYTES) == (big == 1)) { slot[k].in[a] = o; o += al(b); }
-			}
+	struct RawIn { const void *src; uint64_t bytes; uint64_t *off; };
+	std::vector<RawIn> raw;                                  // every raw attribute; for a mesh of the device pass also its index and group ends
+	std::vector<uint32_t> whole(n, 0);                       // the one group of a mesh given without groups
+	for(uint32_t k = 0; k < n; k++) {
+		const BatchItem &it = items[ids[k]];
+		slot[k].in.resize(it.attrs.size()); slot[k].q.resize(it.attrs.size()); slot[k].d.resize(it.attrs.size());
+		for(size_t a = 0; a < it.attrs.size(); a++) raw.push_back(RawIn{it.attrs[a].quant.in, quant_in_bytes(it.attrs[a].quant), &slot[k].in[a]});
+		if(it.topo_device) {
+			const crthip_mesh &m = meshes[ids[k]];
+			whole[k] = it.nface_in;
+			raw.push_back(RawIn{m.index, (uint64_t)it.nface_in*12, &slot[k].idx});
+			raw.push_back(RawIn{m.ngroups ? (const void *)m.group_end : (const void *)&whole[k], (uint64_t)it.topo_groups*4, &slot[k].gend_in});
 		}
-	uint64_t staged_total = 0;
-	for(uint32_t k = 0; k < n; k++) for(size_t a = 0; a < items[ids[k]].attrs.size(); a++) {
-		const uint64_t b = quant_in_bytes(items[ids[k]].attrs[a].quant);
-		if(b < DIRECT_BYTES) staged_total = std::max(staged_total, slot[k].in[a] + b);
 	}
+	for(int big = 0; big < 2; big++)                          // the small inputs first: they go up staged, in one copy
+		for(const RawIn &r : raw) if((r.bytes >= DIRECT_BYTES) == (big == 1)) { *r.off = o; o += al(r.bytes); }
+	uint64_t staged_total = 0;
+	for(const RawIn &r : raw) if(r.bytes < DIRECT_BYTES) staged_total = std::max(staged_total, *r.off + r.bytes);
 	const uint64_t o_zero = o;                               // zeroed: BORDER XORs, counts, cloud minima and flags
 	for(uint32_t k = 0; k < n; k++) {
 		const BatchItem &it = items[ids[k]];
@@ -169,6 +199,14 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_list
 		else { slot[k].zmn = o; o += 256; }
 	}
 	const uint64_t o_zflags = o; o += al((uint64_t)n*4);    // every cloud's equal-key flag, read back in one copy
+	// the device topology pass reports here, read back in one copy: the split words' count, a record per mesh, the new group ends
+	const uint64_t o_back = o;
+	if(!devk.empty()) {
+		o += 256 + al(devk.size()*sizeof(EncTopoRecord));
+		for(uint32_t k : devk) { slot[k].gend_out = o; o += (uint64_t)items[ids[k]].topo_groups*4; }
+		o = al(o);
+	}
+	const uint64_t back_bytes = o - o_back;
 	const uint64_t zero_bytes = o - o_zero;
 	uint32_t faces_total = 0, corners_total = 0;
 	for(uint32_t k = 0; k < n; k++) {
@@ -191,10 +229,26 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_list
 	uint64_t o_ck[2], o_cv[2];
 	for(int b = 0; b < 2; b++) { o_ck[b] = o; o += al((uint64_t)corners_total*4); o_cv[b] = o; o += al((uint64_t)corners_total*4); }
 	const uint64_t o_chist = o; o += al(256ull*4*rs_blocks(corners_total));
+	// the device topology pass's scratch, and (every mode but HOST) each mesh's CLERS symbols where the value coder reads them
+	uint64_t split_cap_total = 0;
+	for(uint32_t k : devk) {
+		const BatchItem &it = items[ids[k]];
+		const uint64_t nf = it.nface_in, nv = it.nvert_in;
+		slot[k].first = o; o += al((nv + 1)*4);
+		slot[k].cursor = o; o += al(nv*4);
+		slot[k].sides = o; o += al(nf*3*sizeof(EncTopoSide));
+		slot[k].twin = o; o += al(nf*12);
+		if(!it.topo_lds) { slot[k].state = o; o += al(enc_topo_state_bytes<uint32_t>(it.nface_in, it.nvert_in)); }
+		slot[k].split = o; o += al(enc_topo_split_cap(it.nface_in)*4);
+		split_cap_total += enc_topo_split_cap(it.nface_in);
+	}
+	const uint64_t o_spack = o; o += al(split_cap_total*4);
+	for(uint32_t k = 0; k < n; k++) if(items[ids[k]].topo_image) { slot[k].clers = o; o += al(enc_topo_clers_cap(items[ids[k]].nface_in)); }
 	const uint64_t o_jobs = o; o += 1u << 16;                // job tables, rewritten stage by stage (stream-ordered)
 	std::vector<uint8_t> jobbuf;
 	uint64_t job_bytes = 0;
 	for(uint32_t k = 0; k < n; k++) job_bytes += items[ids[k]].attrs.size()*(sizeof(QuantJob) + sizeof(DeltaEncJob) + sizeof(EstJob) + 8) + 16;
+	job_bytes += devk.size()*(sizeof(EncTopoJob) + 8);
 	o += al(3*job_bytes);
 	DevMem dev;
 	{ const auto t0 = Clock::now(); BT_TRY(hipMalloc(&dev.p, o + 256)); S.alloc_ms += ms_since(t0); }
@@ -220,15 +274,12 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_list
 	{
 		const auto t_stage = Clock::now();
 		std::vector<uint8_t> stage(staged_total);
-		for(uint32_t k = 0; k < n; k++) {
-			const BatchItem &it = items[ids[k]];
-			for(size_t a = 0; a < it.attrs.size(); a++) {
-				const uint64_t b = quant_in_bytes(it.attrs[a].quant);
-				if(!b) continue;
-				if(b < DIRECT_BYTES) memcpy(stage.data() + slot[k].in[a], it.attrs[a].quant.in, b);
-				else { const auto t0 = Clock::now(); BT_TRY(hipMemcpyAsync(base + slot[k].in[a], it.attrs[a].quant.in, b, hipMemcpyHostToDevice, st)); S.upload_ms += ms_since(t0); }
-				if(b >= DIRECT_BYTES) S.bytes_to_device += b;
-			}
+		for(const RawIn &r : raw) {
+			const uint64_t b = r.bytes;
+			if(!b) continue;
+			if(b < DIRECT_BYTES) memcpy(stage.data() + *r.off, r.src, b);
+			else { const auto t0 = Clock::now(); BT_TRY(hipMemcpyAsync(base + *r.off, r.src, b, hipMemcpyHostToDevice, st)); S.upload_ms += ms_since(t0); }
+			if(b >= DIRECT_BYTES) S.bytes_to_device += b;
 		}
 		S.host_stage_ms += ms_since(t_stage);
 		{ const auto t0 = Clock::now(); if(staged_total) BT_TRY(hipMemcpyAsync(base, stage.data(), staged_total, hipMemcpyHostToDevice, st)); S.upload_ms += ms_since(t0); }
@@ -266,6 +317,52 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_list
 		}
 	}
 
+	// ---- K-ENC-TOPO: the topology pass of the meshes in devk, behind the quantiser; their records start back at once ----
+	Timer ttc, ttp, ttw;
+	Event ev_back;
+	std::vector<uint8_t> back(back_bytes);
+	const auto t_dtopo = Clock::now();
+	if(!devk.empty()) {
+		std::vector<EncTopoJob> tj(devk.size());
+		std::vector<uint32_t> walk_ids;                          // the LDS-resident walks first, then the global ones
+		uint32_t nlds = 0, lds_bytes = 0;
+		for(int pass = 0; pass < 2; pass++) for(uint32_t j = 0; j < devk.size(); j++) if(items[ids[devk[j]]].topo_lds == (pass == 0)) walk_ids.push_back(j);
+		for(uint32_t j = 0; j < devk.size(); j++) {
+			const uint32_t k = devk[j];
+			const BatchItem &it = items[ids[k]];
+			EncTopoJob &J = tj[j];
+			memset(&J, 0, sizeof(J));
+			J.index = (const uint32_t *)(base + slot[k].idx); J.gend_in = (const uint32_t *)(base + slot[k].gend_in);
+			J.faces = (uint32_t *)(base + o_faces) + (size_t)slot[k].fbase*3; J.gend_out = (uint32_t *)(base + slot[k].gend_out);
+			J.first = (uint32_t *)(base + slot[k].first); J.cursor = (uint32_t *)(base + slot[k].cursor);
+			J.sides = (EncTopoSide *)(base + slot[k].sides); J.twin = (uint32_t *)(base + slot[k].twin);
+			J.state = it.topo_lds ? nullptr : base + slot[k].state;
+			J.quads = (uint32_t *)(base + slot[k].quads); J.clers = base + slot[k].clers; J.split = (uint32_t *)(base + slot[k].split);
+			J.split_packed = (uint32_t *)(base + o_spack); J.split_cursor = (uint32_t *)(base + o_back);
+			J.rec = (EncTopoRecord *)(base + o_back + 256) + j;
+			J.nvert = it.nvert_in; J.nface = it.nface_in; J.ngroups = it.topo_groups;
+			if(it.topo_lds) { nlds++; lds_bytes = std::max(lds_bytes, (uint32_t)enc_topo_state_bytes<uint16_t>(it.nface_in, it.nvert_in)); }
+		}
+		const EncTopoJob *dj = (const EncTopoJob *)put_jobs(tj.data(), tj.size()*sizeof(EncTopoJob));
+		const uint32_t *dw = (const uint32_t *)put_jobs(walk_ids.data(), walk_ids.size()*4);
+		if(!jobs_fit) return ctx_fail(CRTHIP_E_DEVICE, "crthip_encode_batch: job tables");
+		const uint32_t nd = (uint32_t)devk.size();
+		if(ttc.begin(st)) return CRTHIP_E_DEVICE;
+		hipLaunchKernelGGL(k_enc_topo_compact, dim3(nd), dim3(ETOPO_THREADS), 0, st, dj, nd);
+		if(ttc.end(st) || ttp.begin(st)) return CRTHIP_E_DEVICE;
+		hipLaunchKernelGGL(k_enc_topo_pair, dim3(nd), dim3(ETOPO_THREADS), 0, st, dj, nd);
+		if(ttp.end(st) || ttw.begin(st)) return CRTHIP_E_DEVICE;
+		if(nlds) hipLaunchKernelGGL(k_enc_topo_walk<true>, dim3(nlds), dim3(ETOPO_THREADS), lds_bytes, st, dj, dw, nlds);
+		if(nd > nlds) hipLaunchKernelGGL(k_enc_topo_walk<false>, dim3(nd - nlds), dim3(ETOPO_THREADS), 0, st, dj, dw + nlds, nd - nlds);
+		if(ttw.end(st)) return CRTHIP_E_DEVICE;
+		BT_TRY(hipGetLastError());
+		bt.n_topo_c++; bt.n_topo_p++; bt.n_topo_w += (nlds ? 1u : 0u) + (nd > nlds ? 1u : 0u);
+		BT_TRY(hipMemcpyAsync(back.data(), base + o_back, back_bytes, hipMemcpyDeviceToHost, st));
+		if(ev_back.record(st)) return CRTHIP_E_DEVICE;
+		S.bytes_from_device += back_bytes;
+		S.topology_device += nd; S.topology_lds += nlds;
+	}
+
 	// ---- point clouds: Morton keys and the radix sort ----
 	std::vector<uint32_t> clouds;
 	for(uint32_t k = 0; k < n; k++) if(!is_mesh(items[ids[k]])) clouds.push_back(k);
@@ -297,13 +394,44 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_list
 		bt.n_zsort += launches + 1;
 	}
 
-	// ---- the topology passes as they finish: each mesh's faces and quads are staged as soon as its pass is done, and go up in
+	// ---- the device pass's records: each mesh's frame from its counts, group ends and split words (those came packed: a second copy)
+	if(mode == CRTHIP_TOPOLOGY_DEVICE) { for(uint32_t k : hostk) host_pass(k); topo_ms = ms_since(t_topo); }   // (the clouds' frames)
+	if(!devk.empty()) {
+		{ const auto t0 = Clock::now(); BT_TRY(hipEventSynchronize(ev_back.e)); S.sync_wait_ms += ms_since(t0); }
+		S.device_topology_ms += (float)ms_since(t_dtopo);
+		uint32_t nwords = 0;
+		memcpy(&nwords, back.data(), 4);
+		std::vector<uint32_t> words(nwords);
+		if(nwords > split_cap_total) return ctx_fail(CRTHIP_E_DEVICE, "crthip_encode_batch: the device topology pass's split words");
+		if(nwords) {
+			BT_TRY(hipMemcpyAsync(words.data(), base + o_spack, (size_t)nwords*4, hipMemcpyDeviceToHost, st));
+			BT_TRY(sync());
+			S.bytes_from_device += (uint64_t)nwords*4;
+		}
+		const auto t0 = Clock::now();
+		for(uint32_t j = 0; j < devk.size(); j++) {
+			const uint32_t k = devk[j];
+			BatchItem &it = items[ids[k]];
+			EncTopoRecord R;
+			memcpy(&R, back.data() + 256 + (size_t)j*sizeof(EncTopoRecord), sizeof(R));
+			if(R.status || R.nvert > it.nvert_in || R.nface > it.nface_in || (uint64_t)R.split_off + R.split_words > nwords || R.nclers > enc_topo_clers_cap(it.nface_in)) {
+				it.status = ctx_fail(CRTHIP_E_DEVICE, "crthip_encode_batch: the device topology pass stopped at a bound");
+				continue;
+			}
+			const int32_t e = item_guard([&] {
+				batch_frame(&meshes[ids[k]], extra ? &extra[ids[k]] : nullptr, it, R, (const uint32_t *)(back.data() + (slot[k].gend_out - o_back)), words.data() + R.split_off);
+			});
+			if(e) it.status = e;
+		}
+		S.host_frame_ms += (float)ms_since(t0);
+	}
+	// ---- the host's topology passes as they finish: each mesh's faces and quads are staged as soon as its pass is done, and go up in
 	// two copies (one copy per mesh measured slower: 24.5 against 20.4 ms for 256 C4 units, tools/encode_batch_rate.py)
 	std::vector<uint8_t> up_quads(mquads_bytes), up_faces((size_t)faces_total*12);
 	for(uint32_t k = 0; k < n; k++) {
 		{ const auto tw = Clock::now(); std::unique_lock<std::mutex> g(mu); cv.wait(g, [&] { return ready[k] != 0; }); S.topology_wait_ms += ms_since(tw); }
 		BatchItem &it = items[ids[k]];
-		if(!is_mesh(it)) continue;
+		if(!is_mesh(it) || it.topo_device) continue;
 		const auto t0 = Clock::now();
 		const size_t fb = std::min(it.faces.size()*4, (size_t)it.nface_in*12), qb = std::min(it.quads.size()*4, (size_t)it.nvert_in*16);
 		if(fb) memcpy(up_faces.data() + (size_t)slot[k].fbase*12, it.faces.data(), fb);
@@ -311,18 +439,30 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_list
 		S.host_stage_ms += ms_since(t0);
 	}
 	{
+		// one copy each per run of neighbouring meshes the host made (all of them, without a device pass)
 		const auto t0 = Clock::now();
-		if(mquads_bytes) BT_TRY(hipMemcpyAsync(base + o_mquads, up_quads.data(), mquads_bytes, hipMemcpyHostToDevice, st));
-		if(faces_total) BT_TRY(hipMemcpyAsync(base + o_faces, up_faces.data(), up_faces.size(), hipMemcpyHostToDevice, st));
+		std::vector<uint32_t> mk;
+		for(uint32_t k = 0; k < n; k++) if(is_mesh(items[ids[k]])) mk.push_back(k);
+		for(size_t a = 0; a < mk.size();) {
+			if(items[ids[mk[a]]].topo_device) { a++; continue; }
+			size_t b = a;
+			while(b + 1 < mk.size() && !items[ids[mk[b + 1]]].topo_device) b++;
+			const BatchItem &last = items[ids[mk[b]]];
+			const uint64_t q0 = slot[mk[a]].quads, q1 = slot[mk[b]].quads + (uint64_t)last.nvert_in*16;
+			const uint64_t f0 = (uint64_t)slot[mk[a]].fbase*12, f1 = ((uint64_t)slot[mk[b]].fbase + last.nface_in)*12;
+			if(q1 > q0) BT_TRY(hipMemcpyAsync(base + q0, up_quads.data() + (q0 - o_mquads), q1 - q0, hipMemcpyHostToDevice, st));
+			if(f1 > f0) BT_TRY(hipMemcpyAsync(base + o_faces + f0, up_faces.data() + f0, f1 - f0, hipMemcpyHostToDevice, st));
+			S.bytes_to_device += (q1 - q0) + (f1 - f0);
+			a = b + 1;
+		}
 		S.upload_ms += ms_since(t0);
 	}
-	S.bytes_to_device += mquads_bytes + up_faces.size();
 	BT_TRY(sync());
-	pool.join();
+	if(pool.joinable()) pool.join();
 	S.host_topology_ms += (float)topo_ms;
 	for(uint32_t k = 0; k < n; k++) {                                     // Tunstall streams over 2^23 symbols: the reference's count*255 overflow
 		BatchItem &it = items[ids[k]];
-		if(it.entropy == CRTHIP_ENTROPY_TUNSTALL && (it.clers.size() > (1u << 23) || it.nvert > (1u << 23)))
+		if(it.entropy == CRTHIP_ENTROPY_TUNSTALL && (it.nclers > (1u << 23) || it.nvert > (1u << 23)))
 			it.status = ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: a Tunstall stream longer than 2^23 symbols");
 	}
 
@@ -343,7 +483,7 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_list
 				J.coords = (const int32_t *)(base + slot[k].q[pos]);
 				J.normals = (int32_t *)(base + slot[k].q[a]);
 				J.boundary = it.attrs[a].prediction == 2 ? (int32_t *)(base + slot[k].boundary) : nullptr;
-				J.nface = (uint32_t)(it.faces.size()/3); J.nvert = it.nvert_in;
+				J.nface = it.nface; J.nvert = it.nvert_in;
 				J.vbase = vbase; J.fbase = slot[k].fbase; J.cbase = cbase; J.unit = it.attrs[a].quant.unit;
 				ej.push_back(J); fstart.push_back(fb); vstart.push_back(vb);
 				fb += (J.nface + 255)/256; vb += (J.nvert + 255)/256;
@@ -454,12 +594,26 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_list
 	}
 	BT_TRY(sync());
 	bt.quant += tq.ms(); bt.est += te.ms(); bt.delta += td.ms();
+	bt.topo_c += ttc.ms(); bt.topo_p += ttp.ms(); bt.topo_w += ttw.ms();
 	for(size_t c = 0; c < clouds.size(); c++) { bt.zkeys += tzk[c].ms(); bt.zsort += tzs[c].ms(); }
 
 	// ---- value + entropy coding: every stream of every mesh in one call; the CLERS symbols go up in one copy ----
 	std::vector<uint64_t> clers_at(n, 0);
 	uint64_t cl = 0;
-	for(uint32_t k = 0; k < n; k++) { clers_at[k] = cl; cl += al(items[ids[k]].clers.size()); }
+	const bool clers_in_image = mode != CRTHIP_TOPOLOGY_HOST;     // the device pass wrote its meshes' symbols there; the host's follow them
+	if(clers_in_image) {
+		const auto t0 = Clock::now();
+		bool any = false;
+		for(uint32_t k = 0; k < n; k++) {
+			const BatchItem &it = items[ids[k]];
+			if(it.topo_device || it.clers.empty() || !it.topo_image) continue;
+			BT_TRY(hipMemcpyAsync(base + slot[k].clers, it.clers.data(), it.clers.size(), hipMemcpyHostToDevice, st));
+			S.bytes_to_device += it.clers.size();
+			any = true;
+		}
+		S.upload_ms += ms_since(t0);
+		if(any) BT_TRY(sync());
+	} else for(uint32_t k = 0; k < n; k++) { clers_at[k] = cl; cl += al(items[ids[k]].clers.size()); }
 	DevMem dclers;
 	if(cl) {
 		const auto t0 = Clock::now();
@@ -479,7 +633,7 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_list
 			if(b.kind == BATCH_BITS) continue;
 			DevValueStream v;
 			v.kind = b.kind; v.entropy = it.entropy; v.components = b.N;
-			if(b.attr == -1) { v.count = (uint32_t)it.clers.size(); v.values = dclers.u8() + clers_at[k]; }
+			if(b.attr == -1) { v.count = it.nclers; v.values = clers_in_image ? base + slot[k].clers : dclers.u8() + clers_at[k]; }
 			else {
 				const BatchAttr &A = it.attrs[b.attr];
 				if(A.codec == CRTHIP_CODEC_NORMAL && A.prediction == 2 && is_mesh(it)) b.count = counts[count_at[k] + b.attr];
@@ -556,6 +710,17 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 	// position steps and attribute tables (the steps' sums are the host's, in its order)
 	parallel_for((uint32_t)ok.size(), threads, [&](uint32_t k) { items[ok[k]].status = item_guard([&] { batch_setup(&meshes[ok[k]], extra ? &extra[ok[k]] : nullptr, items[ok[k]]); }); });
 	ok.erase(std::remove_if(ok.begin(), ok.end(), [&](uint32_t i) { return items[i].status != CRTHIP_OK; }), ok.end());
+	// where each mesh's topology pass runs: from the context's mode and the mesh's sizes alone
+	const int topo_mode = ctx_encode_topology(ctx);
+	if(topo_mode != CRTHIP_TOPOLOGY_HOST)
+		for(uint32_t i : ok) {
+			BatchItem &it = items[i];
+			if(!is_mesh(it)) continue;
+			it.topo_image = true;
+			it.topo_groups = std::max(meshes[i].ngroups, 1u);
+			it.topo_lds = enc_topo_fits_lds(it.nvert_in, it.nface_in);
+			it.topo_device = topo_mode == CRTHIP_TOPOLOGY_DEVICE || it.topo_lds;
+		}
 	S.host_check_ms = ms_since(t0);
 
 	// chunks that fit the device
@@ -592,6 +757,9 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 		uint32_t c = 0;
 		auto add = [&](const char *nm, float ms, uint32_t launches) { if(!launches) return; times->name[c] = nm; times->ms[c] = ms; times->launches[c] = launches; c++; };
 		add("enc_quantize_batch", bt.quant, bt.n_quant);
+		add("enc_topo_compact", bt.topo_c, bt.n_topo_c);
+		add("enc_topo_pair", bt.topo_p, bt.n_topo_p);
+		add("enc_topo_walk", bt.topo_w, bt.n_topo_w);
 		add("enc_est_normal", bt.est, bt.n_est);
 		add("enc_delta", bt.delta, bt.n_delta);
 		add("enc_zkeys", bt.zkeys, bt.n_zkeys);

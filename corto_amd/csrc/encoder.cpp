@@ -32,6 +32,7 @@
 #include "../../include/corto_hip.h"
 #include "encoder_internal.h"
 #include "device_plan.h"
+#include "enc_topology.h"
 
 using corto_hip::QK_FLOAT;
 using corto_hip::QK_NORMAL;
@@ -973,6 +974,23 @@ void corto_hip::batch_setup(const crthip_mesh *m, const crthip_attr_list *extra,
 	}
 }
 
+// the stream table of an item from the slots its body recorded (mesh: CLERS symbols, split bits, then the attributes)
+static void batch_streams(const Encoder &E, const std::vector<Deferred> &deferred, bool mesh, corto_hip::BatchItem &it) {
+	using namespace corto_hip;
+	it.streams.clear();
+	const size_t first_attr = mesh ? 2 : 0;
+	for(size_t k = 0; k < deferred.size(); k++) {
+		const Deferred &d = deferred[k];
+		BatchStream b;
+		b.at = d.at; b.kind = d.kind; b.count = d.count; b.N = d.N;
+		b.attr = k < first_attr ? (k == 0 ? -1 : -2) : (int32_t)(k - first_attr);
+		if(d.kind == DEFER_BITS) { b.kind = BATCH_BITS; it.split_words = d.words; }
+		else if(b.attr >= 0 && it.attrs[b.attr].codec == CRTHIP_CODEC_NORMAL)         // the residuals' count: every vertex, or (BORDER) the device's
+			b.count = it.attrs[b.attr].prediction == 2 ? 0u : E.nvert;
+		it.streams.push_back(b);
+	}
+}
+
 void corto_hip::batch_topology(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it) {
 	Encoder E;
 	std::vector<NamedQuant> named;
@@ -993,18 +1011,47 @@ void corto_hip::batch_topology(const crthip_mesh *m, const crthip_attr_list *ext
 		if(E.nvert) memcpy(it.quads.data(), E.prediction.data(), (size_t)E.nvert*16);
 		it.clers.swap(E.clers);
 	} else E.cloud_body();
-	it.nvert = E.nvert; it.nface = E.nface;
+	it.nvert = E.nvert; it.nface = E.nface; it.nclers = (uint32_t)it.clers.size();
 	it.frame.swap(E.s.b);
-	it.streams.clear();
-	const size_t first_attr = mesh ? 2 : 0;
-	for(size_t k = 0; k < deferred.size(); k++) {
-		const Deferred &d = deferred[k];
-		BatchStream b;
-		b.at = d.at; b.kind = d.kind; b.count = d.count; b.N = d.N;
-		b.attr = k < first_attr ? (k == 0 ? -1 : -2) : (int32_t)(k - first_attr);
-		if(d.kind == DEFER_BITS) { b.kind = BATCH_BITS; it.split_words = d.words; }
-		else if(b.attr >= 0 && it.attrs[b.attr].codec == CRTHIP_CODEC_NORMAL)         // the residuals' count: every vertex, or (BORDER) the device's
-			b.count = it.attrs[b.attr].prediction == 2 ? 0u : E.nvert;
-		it.streams.push_back(b);
-	}
+	batch_streams(E, deferred, mesh, it);
+}
+
+void corto_hip::batch_frame(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it, const EncTopoRecord &rec, const uint32_t *group_end,
+                            const uint32_t *split_words) {
+	Encoder E;
+	std::vector<NamedQuant> named;
+	float step = 0;
+	for(const BatchAttr &b : it.attrs) if(b.position) step = b.quant.q;
+	setup(m, extra, E, named, false, &step);
+	std::vector<Deferred> deferred;
+	E.s.defer = &deferred; E.s.shape_only = true;
+	E.header();
+	const size_t ngroups = std::max<size_t>(E.group_end.size(), 1);
+	E.group_end.assign(group_end, group_end + ngroups);
+	E.nvert = rec.nvert; E.nface = rec.nface; E.max_front = rec.max_front;
+	E.split.words.assign(split_words, split_words + rec.split_words);     // flushed on the device: emit() finds nothing to add
+	// mesh_body with the CLERS symbols' count in place of the symbols
+	E.s.u32(E.nvert); E.s.u32(E.nface);
+	E.groups();
+	E.s.u32(E.max_front);
+	put_symbols(E.s, E.entropy, nullptr, rec.nclers);
+	E.split.emit(E.s);
+	for(auto &kv : E.data) E.attr_encode(kv.second);
+	it.nvert = E.nvert; it.nface = E.nface; it.nclers = rec.nclers;
+	it.frame.swap(E.s.b);
+	batch_streams(E, deferred, true, it);
+}
+
+void corto_hip::topology_host_model(const crthip_mesh *m, TopologyModel &out) {
+	Encoder E;
+	std::vector<NamedQuant> named;
+	float step = 1.0f;
+	setup(m, nullptr, E, named, false, &step);
+	E.topology();
+	out.split_bits = (uint64_t)E.split.words.size()*32 + (uint64_t)(32 - E.split.bits);
+	E.split.flush();
+	out.nvert = E.current_vertex; out.nface = E.nface; out.max_front = E.max_front;
+	out.faces.swap(E.faces); out.group_end.swap(E.group_end); out.clers.swap(E.clers); out.split_words.swap(E.split.words);
+	out.quads.resize((size_t)out.nvert*4);
+	if(out.nvert) memcpy(out.quads.data(), E.prediction.data(), (size_t)out.nvert*16);
 }

@@ -59,6 +59,10 @@ struct BatchItem {
 	std::vector<uint32_t> faces;                          // meshes: degenerate faces dropped, original vertex ids
 	std::vector<uint32_t> quads;                          // meshes: the prediction, (t, a, b, c) per encoded vertex
 	std::vector<uint8_t> clers;
+	uint32_t nclers = 0;                                  // CLERS symbols (clers.size(), or the device pass's count: its symbols stay on the device)
+	bool topo_device = false, topo_lds = false;           // meshes: the topology pass runs on the device / with its walk state in LDS
+	bool topo_image = false;                              // meshes: the CLERS symbols have their place in the chunk's device image (every mode but HOST)
+	uint32_t topo_groups = 1;                             // groups the device pass walks (a mesh given without groups: one)
 	std::vector<uint32_t> split_words;
 	std::vector<uint8_t> frame;                           // the container without its streams
 	std::vector<BatchStream> streams;                     // where they belong in it, in order (a BORDER normal's count: 0 until the device has it)
@@ -66,6 +70,14 @@ struct BatchItem {
 // extra: the mesh's generic attributes (or null), checked by encode_check_attrs
 void batch_setup(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it);      // position step + attribute table (after encode_check)
 void batch_topology(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it);   // topology pass (meshes) + frame; reads the index alone
+// a mesh's frame from what the device topology pass reports (its record, the new group ends, the packed split words): header, counts,
+// groups, max_front and the stream slots, without running the pass
+struct EncTopoRecord;
+void batch_frame(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it, const EncTopoRecord &rec, const uint32_t *group_end,
+                 const uint32_t *split_words);
+// the host encoder's topology pass alone (crthip_encode_topology_model, which = 0); split_bits before the final flush
+struct TopologyModel { std::vector<uint32_t> faces, group_end, quads, split_words; std::vector<uint8_t> clers; uint32_t nvert = 0, nface = 0, max_front = 0; uint64_t split_bits = 0; };
+void topology_host_model(const crthip_mesh *m, TopologyModel &out);
 void morton_order_host(const int32_t *coords, uint32_t nvert, std::vector<uint32_t> &order);   // encode_cloud's std::sort of the Morton records
 
 // several blobs with HOST output buffers in one batch (batch.cpp): what crthip_decode_host is one of, and what the crt::Decoder facade's
@@ -86,6 +98,7 @@ int decode_host_many(crthip_ctx *ctx, uint32_t n, HostDecodeReq *reqs, bool copy
 // context plumbing (batch.cpp)
 int ctx_fail(int code, const char *msg);
 int ctx_device(crthip_ctx *ctx);
+int ctx_encode_topology(crthip_ctx *ctx);   // CRTHIP_TOPOLOGY_* of crthip_ctx_set_encode_topology
 hipStream_t ctx_stream(crthip_ctx *ctx);
 int ctx_quiesce(crthip_ctx *ctx);       // wait for whatever batch is in flight on the context
 int ctx_fill_async(crthip_ctx *ctx, void *dst, size_t bytes, int value);   // k_fill_block on the context's main stream

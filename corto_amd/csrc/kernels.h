@@ -161,4 +161,12 @@ __global__ void k_enc_rs_scan(uint32_t *hist, uint32_t len);
 template <typename K> __global__ void k_enc_rs_scatter(const K *keys, const uint32_t *vals, K *keys_out, uint32_t *vals_out, uint32_t n, uint32_t shift,
                                                        const uint32_t *hist);
 
+// k_encode_topo.hip (crthip_ctx_set_encode_topology): the stages of enc_topology.h, one workgroup of ETOPO_THREADS per mesh.
+// k_enc_topo_walk<true> takes the state image's bytes (enc_topo_state_bytes<uint16_t>) as dynamic LDS, up to ETOPO_LDS_MAX
+struct EncTopoJob;
+constexpr uint32_t ENC_TOPO_LDS_MAX = 156*1024;       // = ETOPO_LDS_MAX (enc_topology.h), of the CU's 160 KiB
+__global__ void k_enc_topo_compact(const EncTopoJob *jobs, uint32_t njobs);
+__global__ void k_enc_topo_pair(const EncTopoJob *jobs, uint32_t njobs);
+template <bool LDS> __global__ void k_enc_topo_walk(const EncTopoJob *jobs, const uint32_t *ids, uint32_t nids);
+
 } // namespace corto_hip

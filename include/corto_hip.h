@@ -487,7 +487,7 @@ int64_t crthip_encode_gpu_attrs(crthip_ctx *ctx, const crthip_mesh *mesh, const 
 
 /* A batch of meshes and point clouds in, one .crt per item out, every blob byte-identical to crthip_encode of that item.
  * The CLERS topology pass runs on `host_threads` host threads (0: min(16, CPUs of the process's affinity mask)) while the
- * device quantises; estimated normals, residuals, the point clouds' Morton sort and the value / Tunstall coders run on the
+ * device quantises (or on the device, where the context says so: crthip_ctx_set_encode_topology below); estimated normals, residuals, the point clouds' Morton sort and the value / Tunstall coders run on the
  * device, all meshes in one set of launches (each point cloud sorted by launches of its own).  Blob i is
  * out[blob_offset[i] .. blob_offset[i+1]) (n+1 offsets); the call returns the total size, writes only when cap suffices,
  * and out == NULL sizes only.
@@ -512,6 +512,9 @@ typedef struct {
 	float upload_ms;               /* in the uploads of raw attributes, faces and quads (a copy from pageable memory returns when staged) */
 	float alloc_ms;                /* allocating the device image */
 	float topology_wait_ms;        /* waiting for topology passes that had not finished when the device stages needed them */
+	uint32_t topology_device;      /* meshes whose topology pass ran on the device in this call (crthip_ctx_set_encode_topology) */
+	uint32_t topology_lds;         /* ... those of them whose walk state was LDS-resident */
+	float device_topology_ms;      /* wall time from the first topology launch to the arrival of the meshes' counts on the host */
 } crthip_encode_batch_stats;
 int64_t crthip_encode_batch(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, uint32_t host_threads,
                             uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert, uint32_t *out_nface,
@@ -522,6 +525,41 @@ int64_t crthip_encode_batch(crthip_ctx *ctx, uint32_t n, const crthip_mesh *mesh
 int64_t crthip_encode_batch_attrs(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra, uint32_t host_threads,
                                   uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert, uint32_t *out_nface,
                                   int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times);
+
+/* Where crthip_encode_batch / crthip_encode_batch_attrs on this context run a mesh's CLERS topology pass (degenerate faces, half-edge
+ * pairing, the walk that writes the CLERS symbols, split bits, vertex numbering and prediction quads).  Same bytes in every mode.
+ *   CRTHIP_TOPOLOGY_HOST    (default) on the host_threads pool, overlapping the device's quantisation
+ *   CRTHIP_TOPOLOGY_DEVICE  every mesh on the device (kernels enc_topo_compact, enc_topo_pair, enc_topo_walk): no host thread is started,
+ *                           host_threads is ignored, the compacted faces, quads and CLERS symbols never leave the device
+ *   CRTHIP_TOPOLOGY_SPLIT   meshes whose walk state fits LDS (crthip_encode_topology_fits_lds) on the device, the others on the pool,
+ *                           at the same time
+ * Any other value: CRTHIP_E_ARGUMENT.  A mesh's connectivity never decides where it runs: non-manifold input is byte-identical too. */
+#define CRTHIP_TOPOLOGY_HOST 0
+#define CRTHIP_TOPOLOGY_DEVICE 1
+#define CRTHIP_TOPOLOGY_SPLIT 2
+int crthip_ctx_set_encode_topology(crthip_ctx *ctx, int where);
+
+/* (test hooks, no device needed)  1 when the device pass keeps this mesh's walk state in LDS, else 0: a function of nvert and nface as
+ * given, the one the batch planner uses. */
+int crthip_encode_topology_fits_lds(const crthip_mesh *m);
+/* The topology pass of one mesh on the host: which = 0 the host encoder's own pass (what crthip_encode runs), which = 1 the source the
+ * device kernels run (csrc/enc_topology.h), compiled for the host, with 16- or 32-bit walk state as the device would pick.  The caller
+ * gives the buffers: faces mesh->nface*3 words, group_end max(mesh->ngroups, 1), quads mesh->nvert*4, clers CRTHIP_TOPOLOGY_CLERS_CAP
+ * bytes, split_words CRTHIP_TOPOLOGY_SPLIT_CAP words (the pass's own bounds); the counts come back in the struct.  CRTHIP_E_ARGUMENT for
+ * another `which`, a point cloud, or a mesh crthip_encode would refuse. */
+#define CRTHIP_TOPOLOGY_CLERS_CAP(nface) (7ull*(nface) + 64)
+#define CRTHIP_TOPOLOGY_SPLIT_CAP(nface) (4ull*(nface) + 4)
+typedef struct {
+	uint32_t *faces;            /* out: compacted faces, nface*3 */
+	uint32_t *group_end;        /* out: ngroups new ends */
+	uint32_t *quads;            /* out: nvert x (t, a, b, c) */
+	uint8_t *clers;             /* out: nclers symbols */
+	uint32_t *split_words;      /* out: nsplit_words words, MSB-first, the last one zero-padded */
+	uint32_t nvert, nface;      /* out: what the container says */
+	uint32_t ngroups, max_front, nclers, split_bits, nsplit_words;
+	uint32_t lds;               /* out: which = 1 walked with the 16-bit (LDS) state */
+} crthip_topology_result;
+int crthip_encode_topology_model(const crthip_mesh *m, int which, crthip_topology_result *r);
 
 #ifdef __cplusplus
 }

@@ -2,6 +2,12 @@
 
     python tools/encode_batch_rate.py [--out FILE] [--reps 3]
 
+    python tools/encode_batch_rate.py --topology [--out FILE] [--reps 3]
+
+--topology: the mesh workloads alone, over where the CLERS topology pass runs (Context.set_encode_topology: host, device, split - host alone
+where the library has no such switch) and host_threads (1, 4, 16); one record per combination with every repetition's time, the best one's
+stats and kernel times, and whether the blobs equal the host mode's.
+
 For each workload: the batch call's wall time, its stats and per-kernel times (of the same run), beside crthip_encode on one
 host thread and on 16 (ctypes releases the GIL), crthip_encode_gpu mesh by mesh, and the reference encoder on one core when
 oracle/_ref is present; every leg is the best of --reps runs.  Every batch blob is checked against crthip_encode's bytes."""
@@ -37,11 +43,52 @@ def best(f, reps):
     return bt, br
 
 
+def topology_axis(reps):
+    modes = ["host"] + (["device", "split"] if hasattr(ca.Context, "set_encode_topology") else [])
+    recs = []
+    for name, meshes, kw in workloads():
+        if meshes[0].nface == 0:
+            continue
+        want = None
+        for mode in modes:
+            ctx = ca.Context(0)
+            ctx.set_profiling(True)
+            if mode != "host":
+                ctx.set_encode_topology(mode)
+            ca.encode_batch(meshes[:2], ctx, kw=kw)                               # warm the context and the kernels
+            for threads in (1, 4, 16):
+                times, bt, br = [], None, None
+                for _ in range(reps):
+                    t0 = time.perf_counter(); r = ca.encode_batch(meshes, ctx, kw=kw, host_threads=threads, with_stats=True); t = (time.perf_counter() - t0) * 1e3
+                    times.append(round(t, 3))
+                    if bt is None or t < bt:
+                        bt, br = t, r
+                blobs, st = br
+                if want is None:
+                    want = [b.tobytes() for b in blobs]
+                rec = dict(workload=name, mode=mode, host_threads=threads, batch_ms=round(bt, 3), reps_ms=times, wall_ms=round(st["wall_ms"], 3),
+                           identical_to_host_mode=[b.tobytes() for b in blobs] == want,
+                           stats={k: (round(v, 3) if isinstance(v, float) else v) for k, v in st.items() if k != "kernel_times"},
+                           kernel_times={k: dict(ms=round(v["ms"], 4), launches=v["launches"]) for k, v in st["kernel_times"].items() if k.startswith("enc_topo")})
+                print(json.dumps(rec), flush=True)
+                recs.append(rec)
+            ctx.close()
+    return recs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--topology", action="store_true", help="the topology mode x host_threads table of the mesh workloads")
     a = ap.parse_args()
+    if a.topology:
+        recs = topology_axis(a.reps)
+        if a.out:
+            with open(a.out, "w") as f:
+                for r in recs:
+                    f.write(json.dumps(r) + "\n")
+        return
     from oracle import refcodec as rc
     ctx = ca.Context(0)
     ctx.set_profiling(True)
