@@ -244,11 +244,7 @@ int ctx_stream2(crthip_ctx *ctx, hipStream_t *out);   // the context's second st
 // ------------------------------------------------------------------------------------------------
 // planner: everything below turns the walked layouts + bindings into job arrays inside one scratch block
 
-struct Carver {                         // bump allocator over the scratch block (offsets only)
-	uint64_t off = 0;
-	uint64_t take(uint64_t bytes, uint64_t align = 256) { off = (off + align - 1) & ~(align - 1); uint64_t r = off; off += bytes;
-		return r; }
-};
+// (Carver, the bump allocator over the scratch block: encoder_internal.h - the batch encoder carves its image with it too)
 
 
 static int32_t f2i_x86_host(float x) {

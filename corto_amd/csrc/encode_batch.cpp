@@ -4,11 +4,16 @@
 // The serial part - the CLERS topology pass, which reads the index alone - runs on a pool of host threads while the device
 // quantises (encoder.cpp: batch_topology), or, where the context asks for it (crthip_ctx_set_encode_topology), on the device behind the
 // quantiser (k_encode_topo.hip, enc_topology.h): the compacted faces, the quads and the CLERS symbols are then written where the next
-// kernels read them, and one record per mesh comes back for its frame (encoder.cpp: batch_frame).  Everything per vertex runs on the device and stays resident until the coded streams
-// come back (k_encode_batch.hip): quantisation, estimated normals, residuals, the point clouds' Morton sort (one cloud after
-// another: each has its own launches), then the value and
-// Tunstall coders (encode_gpu.cpp: encode_value_streams_device).  The host splices every container from its frame and the coded
-// streams.  One device image per chunk of the batch; no allocation per mesh or per stream.
+// kernels read them, and one record per mesh comes back for its frame (encoder.cpp: batch_frame).  Everything per vertex runs on the
+// device and stays resident until the coded streams come back (k_encode_batch.hip): quantisation, estimated normals, residuals, the
+// point clouds' Morton sort (one cloud after another: each has its own launches), then the value and Tunstall coders (encode_gpu.cpp:
+// encode_value_streams_device).  The host splices every container from its frame and the coded streams (encoder_internal.h:
+// splice_container).  One device image per chunk of the batch; no allocation per mesh or per stream.
+//
+// How the file is laid out: ChunkImage / build_image say where everything lives in a chunk's device image (the one place that does: the
+// chunker sizes a chunk by building its image); Chunk is what every stage works on; the stages follow, one function each, in the order
+// encode_chunk calls them.  Each stage's comment names the regions of the image it reads (R) and writes (W) and says whether it returns
+// with the stream synchronised.
 #include <hip/hip_runtime.h>
 #include <sched.h>
 
@@ -17,8 +22,8 @@
 #include <chrono>
 #include <condition_variable>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
-#include <string>
 #include <thread>
 #include <vector>
 
@@ -32,12 +37,8 @@ using namespace corto_hip;
 
 namespace {
 
-#define BT_TRY(expr) do { hipError_t e_ = (expr); if(e_ != hipSuccess) return ctx_fail(CRTHIP_E_DEVICE, (std::string(#expr ": ") + hipGetErrorString(e_)).c_str()); } while(0)
-
 using Clock = std::chrono::steady_clock;
 double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
-
-struct DevMem { void *p = nullptr; ~DevMem() { if(p) (void)hipFree(p); } uint8_t *u8() const { return (uint8_t *)p; } };
 
 uint32_t default_threads() {
 	cpu_set_t set;
@@ -69,57 +70,213 @@ template <class F> int32_t item_guard(F f) {
 	catch(...) { return CRTHIP_E_ARGUMENT; }
 }
 
-uint64_t al(uint64_t x) { return (x + 255) & ~255ull; }
 uint32_t rs_blocks(uint32_t n) { return std::max(1u, (n + RS_TILE - 1)/RS_TILE); }
 bool is_mesh(const BatchItem &it) { return it.nface_in > 0; }
 // normals whose residuals are against the estimate (a cloud's estimate is all zeros: its ESTIMATED normals still subtract toOcta of it)
 bool est_of(const BatchItem &it, const BatchAttr &a) { return a.codec == CRTHIP_CODEC_NORMAL && (a.prediction == 1 || (a.prediction == 2 && is_mesh(it))); }
+bool border_of(const BatchItem &it, const BatchAttr &a) { return a.codec == CRTHIP_CODEC_NORMAL && a.prediction == 2 && is_mesh(it); }   // BORDER normals: the device counts their residuals
 constexpr uint64_t DIRECT_BYTES = 1u << 20;               // inputs from this size up go to the device straight from the caller's array
                                                           // (any element size and byte count: slots are 256-byte aligned, a copy is bytes)
 
-// where one item lives in the chunk's device image
+// ---- the chunk's device image ----
+
+// where one item lives in it
 struct Slot {
 	std::vector<uint64_t> in, q, d;       // per attribute: raw input, quantised values, residuals
-	uint64_t faces = 0, quads = 0, boundary = 0, count = 0;
+	uint64_t quads = 0, boundary = 0, count = 0;
 	uint64_t zkeys[2] = {0, 0}, zvals[2] = {0, 0}, zhist = 0, zmn = 0;
 	uint64_t clers = 0;
 	uint64_t idx = 0, gend_in = 0, gend_out = 0, first = 0, cursor = 0, sides = 0, twin = 0, state = 0, split = 0;   // the device topology pass
 	uint32_t fbase = 0;                   // first face in the faces region (faces units)
 };
+struct RawIn { const void *src; uint64_t bytes, off; };
 
-// the device bytes of one item (for chunking), the same sums the layout below makes
-uint64_t item_bytes(const BatchItem &it) {
-	uint64_t b = 0;
-	for(const BatchAttr &a : it.attrs) b += al(quant_in_bytes(a.quant)) + 2*al(quant_out_bytes(a.quant)) + 256;
-	if(is_mesh(it)) {
-		b += al((uint64_t)it.nface_in*12) + al((uint64_t)it.nvert_in*16) + al((uint64_t)it.nvert_in*4) + al(it.nface_in*8ull + 64);
-		for(const BatchAttr &a : it.attrs) if(est_of(it, a)) b += 2*(al((uint64_t)it.nface_in*12) + al((uint64_t)it.nface_in*12)) + al(256ull*4*rs_blocks(3*it.nface_in));
-	} else b += 2*al((uint64_t)it.nvert_in*8) + 2*al((uint64_t)it.nvert_in*4) + al((uint64_t)it.nvert_in*16) + al(256ull*4*rs_blocks(it.nvert_in)) + 512;
-	// the device topology pass: raw index and group ends, bucket tables, sides, twins, the walk's global image, split words (private and
-	// packed), record; in every mode but HOST the CLERS symbols have their place in the image
-	if(it.topo_device) {
-		const uint64_t nf = it.nface_in, nv = it.nvert_in;
-		b += al(nf*12) + 2*al(it.topo_groups*4ull) + al((nv + 1)*4) + al(nv*4) + al(nf*3*sizeof(EncTopoSide)) + al(nf*12) + 2*al(enc_topo_split_cap(it.nface_in)*4) + 1024;
-		if(!it.topo_lds) b += al(enc_topo_state_bytes<uint32_t>(it.nface_in, it.nvert_in));
+// Every offset of one chunk's image and the totals its copies need.  Items are named by k, their place in ids.
+struct ChunkImage {
+	std::vector<uint32_t> ids;            // the chunk's items (indices of the batch)
+	// whose topology pass runs where: devk on the device (CRTHIP_TOPOLOGY_DEVICE: every mesh, _SPLIT: those that walk in LDS), hostk (the
+	// other meshes, and every cloud's frame) on the host
+	std::vector<uint32_t> devk, hostk, clouds;
+	std::vector<Slot> slot;
+	std::vector<RawIn> raw;               // every raw attribute; for a mesh of the device pass also its index and group ends (given
+	                                      // without groups it is one group, which ends at its face count)
+	uint64_t zero = 0, zflags = 0, back = 0, mquads = 0, faces = 0, ck[2] = {0, 0}, cv[2] = {0, 0}, chist = 0, spack = 0, jobs = 0, total = 0;
+	uint64_t staged_total = 0, zero_bytes = 0, back_bytes = 0, mquads_bytes = 0, split_cap_total = 0;
+	uint32_t faces_total = 0, corners_total = 0;
+	uint64_t rec(size_t j) const { return back + 256 + j*sizeof(EncTopoRecord); }   // the record of mesh devk[j]
+};
+
+// The image of items[ids], without touching the device.  Every region starts on 256 bytes unless it says otherwise.
+ChunkImage build_image(const crthip_mesh *meshes, const std::vector<BatchItem> &items, std::vector<uint32_t> ids) {
+	ChunkImage L;
+	Carver c;
+	auto here = [&] { return c.take(0); };                  // where the next region starts
+	const uint32_t n = (uint32_t)ids.size();
+	L.ids = std::move(ids);
+	L.slot.resize(n);
+	std::vector<uint64_t *> raw_off;                         // raw[i]'s offset in its slot
+	uint64_t job_bytes = 0;
+	for(uint32_t k = 0; k < n; k++) {
+		const BatchItem &it = items[L.ids[k]];
+		Slot &s = L.slot[k];
+		(it.topo_device ? L.devk : L.hostk).push_back(k);
+		if(!is_mesh(it)) L.clouds.push_back(k);
+		s.in.resize(it.attrs.size()); s.q.resize(it.attrs.size()); s.d.resize(it.attrs.size());
+		for(size_t a = 0; a < it.attrs.size(); a++) { L.raw.push_back(RawIn{it.attrs[a].quant.in, quant_in_bytes(it.attrs[a].quant), 0}); raw_off.push_back(&s.in[a]); }
+		if(it.topo_device) {
+			const crthip_mesh &m = meshes[L.ids[k]];
+			L.raw.push_back(RawIn{m.index, (uint64_t)it.nface_in*12, 0}); raw_off.push_back(&s.idx);
+			L.raw.push_back(RawIn{m.ngroups ? (const void *)m.group_end : (const void *)&it.nface_in, (uint64_t)it.topo_groups*4, 0}); raw_off.push_back(&s.gend_in);
+		}
+		job_bytes += it.attrs.size()*(sizeof(QuantJob) + sizeof(DeltaEncJob) + sizeof(EstJob) + 8) + 16 + (it.topo_device ? sizeof(EncTopoJob) + 8 : 0);
 	}
-	if(it.topo_image) b += al(enc_topo_clers_cap(it.nface_in));
-	return b + 4096;
+	// INVARIANT: the raw inputs below DIRECT_BYTES are contiguous at the front of the image - they go up staged, in one copy of
+	// staged_total bytes from offset 0 - and the large ones follow
+	for(int big = 0; big < 2; big++)
+		for(size_t i = 0; i < L.raw.size(); i++) if((L.raw[i].bytes >= DIRECT_BYTES) == (big == 1)) *raw_off[i] = L.raw[i].off = c.take(L.raw[i].bytes);
+	for(const RawIn &r : L.raw) if(r.bytes < DIRECT_BYTES) L.staged_total = std::max(L.staged_total, r.off + r.bytes);
+	// INVARIANT: the zeroed words (BORDER XORs, counts, cloud minima), the clouds' flags and the device topology pass's report are
+	// contiguous - one memset of zero_bytes from `zero` - and the report is one block: it comes back in one copy of back_bytes from `back`
+	L.zero = here();
+	for(uint32_t k = 0; k < n; k++) {
+		const BatchItem &it = items[L.ids[k]];
+		L.slot[k].count = c.take(256);
+		if(is_mesh(it)) { for(const BatchAttr &a : it.attrs) if(border_of(it, a)) L.slot[k].boundary = c.take((uint64_t)it.nvert_in*4); }
+		else L.slot[k].zmn = c.take(256);
+	}
+	L.zflags = c.take((uint64_t)n*4);                        // every cloud's equal-key flag, read back in one copy
+	L.back = here();                                         // the report: the split words' count, a record per mesh (rec()), the new group ends (packed)
+	if(!L.devk.empty()) {
+		c.take(256); c.take(L.devk.size()*sizeof(EncTopoRecord));
+		here();                                              // (the group ends start on 256 and are packed from there)
+		for(uint32_t k : L.devk) L.slot[k].gend_out = c.take((uint64_t)items[L.ids[k]].topo_groups*4, 4);
+	}
+	L.back_bytes = here() - L.back;
+	L.zero_bytes = here() - L.zero;
+	for(uint32_t k = 0; k < n; k++) {
+		const BatchItem &it = items[L.ids[k]];
+		Slot &s = L.slot[k];
+		for(size_t a = 0; a < it.attrs.size(); a++) { s.q[a] = c.take(quant_out_bytes(it.attrs[a].quant)); s.d[a] = c.take(quant_out_bytes(it.attrs[a].quant)); }
+		if(is_mesh(it)) {
+			s.fbase = L.faces_total; L.faces_total += it.nface_in;
+			for(const BatchAttr &a : it.attrs) if(est_of(it, a)) L.corners_total += 3*it.nface_in;
+		} else {
+			for(int b = 0; b < 2; b++) { s.zkeys[b] = c.take((uint64_t)it.nvert_in*8); s.zvals[b] = c.take((uint64_t)it.nvert_in*4); }
+			s.quads = c.take((uint64_t)it.nvert_in*16);
+			s.zhist = c.take(256ull*4*rs_blocks(it.nvert_in));
+		}
+	}
+	// INVARIANT: the meshes' quads lie back to back in item order (16-byte records, no padding between meshes), and so do their faces
+	// (fbase): one upload each per run of neighbouring meshes the host made
+	L.mquads = here();
+	for(uint32_t k = 0; k < n; k++) if(is_mesh(items[L.ids[k]])) L.slot[k].quads = c.take((uint64_t)items[L.ids[k]].nvert_in*16, 16);
+	L.mquads_bytes = c.off - L.mquads;
+	L.faces = c.take((uint64_t)L.faces_total*12);
+	for(int b = 0; b < 2; b++) { L.ck[b] = c.take((uint64_t)L.corners_total*4); L.cv[b] = c.take((uint64_t)L.corners_total*4); }
+	L.chist = c.take(256ull*4*rs_blocks(L.corners_total));
+	// the device topology pass's scratch, and (every mode but HOST) each mesh's CLERS symbols where the value coder reads them
+	for(uint32_t k : L.devk) {
+		const BatchItem &it = items[L.ids[k]];
+		const uint64_t nf = it.nface_in, nv = it.nvert_in;
+		Slot &s = L.slot[k];
+		s.first = c.take((nv + 1)*4);
+		s.cursor = c.take(nv*4);
+		s.sides = c.take(nf*3*sizeof(EncTopoSide));
+		s.twin = c.take(nf*12);
+		if(!it.topo_lds) s.state = c.take(enc_topo_state_bytes<uint32_t>(it.nface_in, it.nvert_in));
+		s.split = c.take(enc_topo_split_cap(it.nface_in)*4);
+		L.split_cap_total += enc_topo_split_cap(it.nface_in);
+	}
+	L.spack = c.take(L.split_cap_total*4);
+	for(uint32_t k = 0; k < n; k++) if(items[L.ids[k]].topo_image) L.slot[k].clers = c.take(enc_topo_clers_cap(items[L.ids[k]].nface_in));
+	L.jobs = c.take(1u << 16);                               // job tables, rewritten stage by stage (stream-ordered): Chunk::put_jobs
+	c.take(3*job_bytes);
+	L.total = here();
+	return L;
 }
 
-struct Timer {
-	hipEvent_t a = nullptr, b = nullptr; bool used = false;
-	~Timer() { if(a) (void)hipEventDestroy(a); if(b) (void)hipEventDestroy(b); }
-	int begin(hipStream_t st) { if(!a) { BT_TRY(hipEventCreate(&a)); BT_TRY(hipEventCreate(&b)); } used = true; BT_TRY(hipEventRecord(a, st)); return 0; }
-	int end(hipStream_t st) { BT_TRY(hipEventRecord(b, st)); return 0; }
-	float ms() { float m = 0; if(used && hipEventElapsedTime(&m, a, b) != hipSuccess) m = 0; return m; }
-};
-struct BatchTimes { float quant = 0, est = 0, delta = 0, zkeys = 0, zsort = 0, topo_c = 0, topo_p = 0, topo_w = 0;
-                    uint32_t n_quant = 0, n_est = 0, n_delta = 0, n_zkeys = 0, n_zsort = 0, n_topo_c = 0, n_topo_p = 0, n_topo_w = 0; };
+// host mode's CLERS symbols go up in an allocation of their own, sized once the passes have made them: item k's at at[k] (one entry
+// per item); returns its bytes
+uint64_t clers_layout(const std::vector<BatchItem> &items, const ChunkImage &img, std::vector<uint64_t> &at) {
+	Carver c;
+	for(size_t k = 0; k < at.size(); k++) at[k] = c.take(items[img.ids[k]].clers.size());
+	return c.take(0);
+}
+
+// ---- what every stage works on ----
+
+// the batch's kernels as crthip_kernel_times names them, in the order they are reported; up to K_STAGES one timer per chunk, then one per cloud
+enum { K_QUANT, K_TOPO_C, K_TOPO_P, K_TOPO_W, K_EST, K_DELTA, K_STAGES, K_ZKEYS = K_STAGES, K_ZSORT, K_COUNT };
+const char *const KERNEL_NAME[K_COUNT] = {"enc_quantize_batch", "enc_topo_compact", "enc_topo_pair", "enc_topo_walk", "enc_est_normal", "enc_delta", "enc_zkeys", "enc_zsort"};
+struct BatchTimes { float ms[K_COUNT] = {}; uint32_t launches[K_COUNT] = {}; };
 struct Event {
 	hipEvent_t e = nullptr;
 	~Event() { if(e) (void)hipEventDestroy(e); }
-	int record(hipStream_t st) { if(!e) BT_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); BT_TRY(hipEventRecord(e, st)); return 0; }
+	int record(hipStream_t st) { if(!e) ENC_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ENC_TRY(hipEventRecord(e, st)); return 0; }
 };
+
+// One chunk in flight.  encode_chunk owns it together with the guards (Joiner, DevMem, Drain); a stage that returns early relies on those
+// and releases nothing itself.  Host buffers that a queued copy reads or writes live here, so they outlive the Drain.
+struct Chunk {
+	crthip_ctx *ctx; hipStream_t st;
+	const crthip_mesh *meshes; const crthip_attr_list *extra;
+	std::vector<BatchItem> &items; const ChunkImage &img;
+	crthip_encode_batch_stats &S; BatchTimes &bt; EncStageTimes &tm;
+	// the host's topology passes: what the pool thread and the stages share (the pool thread's lambdas hold references to this Chunk)
+	std::vector<uint8_t> ready = std::vector<uint8_t>(img.ids.size(), 0);   // per k: its pass (a mesh) or its frame (a cloud) is done; guarded by mu, signalled on cv
+	std::mutex mu; std::condition_variable cv;
+	Clock::time_point t_topo = Clock::now();
+	double topo_ms = 0;                                      // from t_topo until the last pass finished
+	uint8_t *base = nullptr;
+	Carver job_cursor{img.jobs};                             // the job tables' region: [img.jobs, img.total)
+	std::vector<std::vector<uint8_t>> keep;                  // the job tables' host copies live until the chunk has finished
+	bool jobs_fit = true;
+	EventTimer t[K_STAGES];
+	std::vector<EventTimer> tzk, tzs;                             // per cloud
+	Event ev_back;                                           // behind the copy of the device topology pass's report into `back`
+	std::vector<uint8_t> back = std::vector<uint8_t>(img.back_bytes);
+	Clock::time_point t_dtopo;
+
+	uint32_t n() const { return (uint32_t)img.ids.size(); }
+	BatchItem &item(uint32_t k) const { return items[img.ids[k]]; }
+	const crthip_mesh *mesh(uint32_t k) const { return &meshes[img.ids[k]]; }
+	const crthip_attr_list *attrs(uint32_t k) const { return extra ? &extra[img.ids[k]] : nullptr; }
+	template <class T> T *at(uint64_t off) const { return (T *)(base + off); }
+	hipError_t sync() { const auto t0 = Clock::now(); const hipError_t e = hipStreamSynchronize(st); S.sync_wait_ms += ms_since(t0); return e; }
+	uint8_t *put_jobs(const void *p, size_t bytes) {
+		const uint64_t off = job_cursor.take(bytes);
+		if(off + bytes > img.total) { jobs_fit = false; return nullptr; }
+		if(bytes) {
+			keep.emplace_back((const uint8_t *)p, (const uint8_t *)p + bytes);
+			if(hipMemcpyAsync(base + off, keep.back().data(), bytes, hipMemcpyHostToDevice, st) != hipSuccess) jobs_fit = false;
+			S.bytes_to_device += bytes;
+		}
+		return base + off;
+	}
+	// the topology pass (a mesh) or the frame (a cloud) of item k on the host; runs on the pool, or inline (device mode's clouds)
+	void host_pass(uint32_t k) {
+		const int32_t e = item_guard([&] { batch_topology(mesh(k), attrs(k), item(k)); });
+		if(e) item(k).status = e;                                // read by this thread's caller only after the join
+		{ std::lock_guard<std::mutex> g(mu); ready[k] = 1; }
+		cv.notify_all();
+	}
+};
+
+// A stage's job table and its block-start arrays go up behind the previous stage's; `launch(jobs, starts)` then runs between the events
+// of the timers `first` and `last` (K_*; one timer for most stages).  launch returns 0 or the error it has reported.
+template <class J, class L>
+int launch_jobs(Chunk &C, const std::vector<J> &jobs, std::initializer_list<const std::vector<uint32_t> *> starts, int first, int last, L launch) {
+	const J *dj = (const J *)C.put_jobs(jobs.data(), jobs.size()*sizeof(J));
+	const uint32_t *ds[3] = {nullptr, nullptr, nullptr};
+	size_t i = 0;
+	for(const std::vector<uint32_t> *s : starts) ds[i++] = (const uint32_t *)C.put_jobs(s->data(), s->size()*4);
+	if(!C.jobs_fit) return ctx_fail(CRTHIP_E_DEVICE, "crthip_encode_batch: job tables");
+	if(C.t[first].begin(C.st)) return CRTHIP_E_DEVICE;
+	{ const int e = launch(dj, ds); if(e) return e; }
+	if(C.t[last].end(C.st)) return CRTHIP_E_DEVICE;
+	ENC_TRY(hipGetLastError());
+	return 0;
+}
 
 // LSD radix sort of n records in (k0, v0) by key bits [0, bits), ping-ponging through (k1, v1); returns which buffer holds the result
 template <typename K>
@@ -136,399 +293,266 @@ int radix_sort(hipStream_t st, K *k0, uint32_t *v0, K *k1, uint32_t *v1, uint32_
 		where ^= 1;
 		launches += 3;
 	}
-	BT_TRY(hipGetLastError());
+	ENC_TRY(hipGetLastError());
 	return 0;
 }
 
-// the device half of one chunk: items[ids] have been set up; their topology passes run here on the pool, overlapping the device
-int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_list *extra, std::vector<BatchItem> &items, const std::vector<uint32_t> &ids, uint32_t threads,
-              std::vector<std::vector<uint8_t>> &blobs, crthip_encode_batch_stats &S, BatchTimes &bt, EncStageTimes &tm) {
-	hipStream_t st = ctx_stream(ctx);
-	const uint32_t n = (uint32_t)ids.size();
-	const int mode = ctx_encode_topology(ctx);
-	// whose topology pass runs where: devk on the device (CRTHIP_TOPOLOGY_DEVICE: every mesh, _SPLIT: those that walk in LDS), hostk
-	// (the other meshes, and every cloud's frame) on the host
-	std::vector<uint32_t> hostk, devk;
-	for(uint32_t k = 0; k < n; k++) (items[ids[k]].topo_device ? devk : hostk).push_back(k);
-	// topology passes (meshes) and frames (everything) on the pool, started first: they need the index alone
-	std::vector<uint8_t> ready(n, 0);
-	for(uint32_t k : devk) ready[k] = 1;
-	std::mutex mu; std::condition_variable cv;
-	double topo_ms = 0;
-	const auto t_topo = Clock::now();
-	auto host_pass = [&](uint32_t k) {
-		const int32_t e = item_guard([&] { batch_topology(&meshes[ids[k]], extra ? &extra[ids[k]] : nullptr, items[ids[k]]); });
-		if(e) items[ids[k]].status = e;                      // read by this thread's caller only after the join
-		{ std::lock_guard<std::mutex> g(mu); ready[k] = 1; }
-		cv.notify_all();
-	};
-	std::thread pool;
-	if(mode != CRTHIP_TOPOLOGY_DEVICE) pool = std::thread([&]() {      // (device mode starts no thread: the clouds' frames are made inline below)
-		parallel_for((uint32_t)hostk.size(), threads, [&](uint32_t j) { host_pass(hostk[j]); });
-		std::lock_guard<std::mutex> g(mu);
-		topo_ms = ms_since(t_topo);
+// ---- the stages, in the order encode_chunk runs them ----
+
+// Raw inputs up: small ones staged into one copy, large ones straight from the caller; then the zeroed block is cleared.
+// W: every raw input (slot.in, idx, gend_in), [zero, zero + zero_bytes).  Synchronised after the copies (the staging buffer is a local);
+// the memset is left queued.
+int upload_inputs(Chunk &C) {
+	const auto t_stage = Clock::now();
+	std::vector<uint8_t> stage(C.img.staged_total);
+	for(const RawIn &r : C.img.raw) {
+		const uint64_t b = r.bytes;
+		if(!b) continue;
+		if(b < DIRECT_BYTES) memcpy(stage.data() + r.off, r.src, b);
+		else { const auto t0 = Clock::now(); ENC_TRY(hipMemcpyAsync(C.base + r.off, r.src, b, hipMemcpyHostToDevice, C.st)); C.S.upload_ms += ms_since(t0); }
+		if(b >= DIRECT_BYTES) C.S.bytes_to_device += b;
+	}
+	C.S.host_stage_ms += ms_since(t_stage);
+	{ const auto t0 = Clock::now(); if(C.img.staged_total) ENC_TRY(hipMemcpyAsync(C.base, stage.data(), C.img.staged_total, hipMemcpyHostToDevice, C.st)); C.S.upload_ms += ms_since(t0); }
+	C.S.bytes_to_device += C.img.staged_total;
+	ENC_TRY(C.sync());
+	if(C.img.zero_bytes) ENC_TRY(hipMemsetAsync(C.base + C.img.zero, 0, C.img.zero_bytes, C.st));
+	return 0;
+}
+
+// K-ENC-Q: every attribute of every item in one launch.  R: slot.in.  W: slot.q, job tables.  Not synchronised.
+int stage_quantise(Chunk &C) {
+	std::vector<QuantJob> qj; std::vector<uint32_t> start;
+	uint32_t blocks = 0;
+	for(uint32_t k = 0; k < C.n(); k++) {
+		const BatchItem &it = C.item(k);
+		for(size_t a = 0; a < it.attrs.size(); a++) {
+			const QuantRequest &r = it.attrs[a].quant;
+			if(!r.count) continue;
+			qj.push_back(quant_job(r, C.base + C.img.slot[k].in[a], C.base + C.img.slot[k].q[a])); start.push_back(blocks); blocks += (r.count + 255)/256;
+		}
+	}
+	if(qj.empty()) return 0;
+	start.push_back(blocks);
+	const int e = launch_jobs(C, qj, {&start}, K_QUANT, K_QUANT, [&](const QuantJob *dj, const uint32_t *const *ds) {
+		hipLaunchKernelGGL(k_enc_quantize_batch, dim3(blocks), dim3(256), 0, C.st, dj, ds[0], (uint32_t)qj.size());
+		return 0;
 	});
-	struct Joiner { std::thread &t; ~Joiner() { if(t.joinable()) t.join(); } } joiner{pool};
+	if(!e) C.bt.launches[K_QUANT]++;
+	return e;
+}
 
-	// ---- layout: raw inputs first (one upload), then everything else ----
-	std::vector<Slot> slot(n);
-	uint64_t o = 0;
-	struct RawIn { const void *src; uint64_t bytes; uint64_t *off; };
-	std::vector<RawIn> raw;                                  // every raw attribute; for a mesh of the device pass also its index and group ends
-	std::vector<uint32_t> whole(n, 0);                       // the one group of a mesh given without groups
-	for(uint32_t k = 0; k < n; k++) {
-		const BatchItem &it = items[ids[k]];
-		slot[k].in.resize(it.attrs.size()); slot[k].q.resize(it.attrs.size()); slot[k].d.resize(it.attrs.size());
-		for(size_t a = 0; a < it.attrs.size(); a++) raw.push_back(RawIn{it.attrs[a].quant.in, quant_in_bytes(it.attrs[a].quant), &slot[k].in[a]});
-		if(it.topo_device) {
-			const crthip_mesh &m = meshes[ids[k]];
-			whole[k] = it.nface_in;
-			raw.push_back(RawIn{m.index, (uint64_t)it.nface_in*12, &slot[k].idx});
-			raw.push_back(RawIn{m.ngroups ? (const void *)m.group_end : (const void *)&whole[k], (uint64_t)it.topo_groups*4, &slot[k].gend_in});
-		}
+// K-ENC-TOPO: the topology pass of the meshes in devk, behind the quantiser; their report starts back at once.
+// R: slot.idx, gend_in.  W: faces, slot.quads, clers, gend_out, the records and the split cursor (the report), spack, the pass's scratch
+// (first, cursor, sides, twin, state, split), job tables.  Not synchronised: ev_back says when the report is in C.back.
+int stage_topology(Chunk &C) {
+	C.t_dtopo = Clock::now();
+	const uint32_t nd = (uint32_t)C.img.devk.size();
+	if(!nd) return 0;
+	std::vector<EncTopoJob> tj(nd);
+	std::vector<uint32_t> walk_ids;                          // the LDS-resident walks first, then the global ones
+	uint32_t nlds = 0, lds_bytes = 0;
+	for(int pass = 0; pass < 2; pass++) for(uint32_t j = 0; j < nd; j++) if(C.item(C.img.devk[j]).topo_lds == (pass == 0)) walk_ids.push_back(j);
+	for(uint32_t j = 0; j < nd; j++) {
+		const BatchItem &it = C.item(C.img.devk[j]);
+		const Slot &s = C.img.slot[C.img.devk[j]];
+		EncTopoJob &J = tj[j];
+		memset(&J, 0, sizeof(J));
+		J.index = C.at<const uint32_t>(s.idx); J.gend_in = C.at<const uint32_t>(s.gend_in);
+		J.faces = C.at<uint32_t>(C.img.faces) + (size_t)s.fbase*3; J.gend_out = C.at<uint32_t>(s.gend_out);
+		J.first = C.at<uint32_t>(s.first); J.cursor = C.at<uint32_t>(s.cursor);
+		J.sides = C.at<EncTopoSide>(s.sides); J.twin = C.at<uint32_t>(s.twin);
+		J.state = it.topo_lds ? nullptr : C.base + s.state;
+		J.quads = C.at<uint32_t>(s.quads); J.clers = C.base + s.clers; J.split = C.at<uint32_t>(s.split);
+		J.split_packed = C.at<uint32_t>(C.img.spack); J.split_cursor = C.at<uint32_t>(C.img.back);
+		J.rec = C.at<EncTopoRecord>(C.img.rec(j));
+		J.nvert = it.nvert_in; J.nface = it.nface_in; J.ngroups = it.topo_groups;
+		if(it.topo_lds) { nlds++; lds_bytes = std::max(lds_bytes, (uint32_t)enc_topo_state_bytes<uint16_t>(it.nface_in, it.nvert_in)); }
 	}
-	for(int big = 0; big < 2; big++)                          // the small inputs first: they go up staged, in one copy
-		for(const RawIn &r : raw) if((r.bytes >= DIRECT_BYTES) == (big == 1)) { *r.off = o; o += al(r.bytes); }
-	uint64_t staged_total = 0;
-	for(const RawIn &r : raw) if(r.bytes < DIRECT_BYTES) staged_total = std::max(staged_total, *r.off + r.bytes);
-	const uint64_t o_zero = o;                               // zeroed: BORDER XORs, counts, cloud minima and flags
-	for(uint32_t k = 0; k < n; k++) {
-		const BatchItem &it = items[ids[k]];
-		slot[k].count = o; o += 256;
-		if(is_mesh(it)) { for(const BatchAttr &a : it.attrs) if(est_of(it, a) && a.prediction == 2) { slot[k].boundary = o; o += al((uint64_t)it.nvert_in*4); } }
-		else { slot[k].zmn = o; o += 256; }
-	}
-	const uint64_t o_zflags = o; o += al((uint64_t)n*4);    // every cloud's equal-key flag, read back in one copy
-	// the device topology pass reports here, read back in one copy: the split words' count, a record per mesh, the new group ends
-	const uint64_t o_back = o;
-	if(!devk.empty()) {
-		o += 256 + al(devk.size()*sizeof(EncTopoRecord));
-		for(uint32_t k : devk) { slot[k].gend_out = o; o += (uint64_t)items[ids[k]].topo_groups*4; }
-		o = al(o);
-	}
-	const uint64_t back_bytes = o - o_back;
-	const uint64_t zero_bytes = o - o_zero;
-	uint32_t faces_total = 0, corners_total = 0;
-	for(uint32_t k = 0; k < n; k++) {
-		const BatchItem &it = items[ids[k]];
-		for(size_t a = 0; a < it.attrs.size(); a++) { slot[k].q[a] = o; o += al(quant_out_bytes(it.attrs[a].quant)); slot[k].d[a] = o; o += al(quant_out_bytes(it.attrs[a].quant)); }
-		if(is_mesh(it)) {
-			slot[k].fbase = faces_total; faces_total += it.nface_in;
-			for(const BatchAttr &a : it.attrs) if(est_of(it, a)) corners_total += 3*it.nface_in;
-		} else {
-			for(int b = 0; b < 2; b++) { slot[k].zkeys[b] = o; o += al((uint64_t)it.nvert_in*8); slot[k].zvals[b] = o; o += al((uint64_t)it.nvert_in*4); }
-			slot[k].quads = o; o += al((uint64_t)it.nvert_in*16);
-			slot[k].zhist = o; o += al(256ull*4*rs_blocks(it.nvert_in));
-		}
-	}
-	const uint64_t o_mquads = o;                             // the meshes' quads back to back, and their faces: one upload each
-	for(uint32_t k = 0; k < n; k++) if(is_mesh(items[ids[k]])) { slot[k].quads = o; o += (uint64_t)items[ids[k]].nvert_in*16; }
-	const uint64_t mquads_bytes = o - o_mquads;
-	o = al(o);
-	const uint64_t o_faces = o; o += al((uint64_t)faces_total*12);
-	uint64_t o_ck[2], o_cv[2];
-	for(int b = 0; b < 2; b++) { o_ck[b] = o; o += al((uint64_t)corners_total*4); o_cv[b] = o; o += al((uint64_t)corners_total*4); }
-	const uint64_t o_chist = o; o += al(256ull*4*rs_blocks(corners_total));
-	// the device topology pass's scratch, and (every mode but HOST) each mesh's CLERS symbols where the value coder reads them
-	uint64_t split_cap_total = 0;
-	for(uint32_t k : devk) {
-		const BatchItem &it = items[ids[k]];
-		const uint64_t nf = it.nface_in, nv = it.nvert_in;
-		slot[k].first = o; o += al((nv + 1)*4);
-		slot[k].cursor = o; o += al(nv*4);
-		slot[k].sides = o; o += al(nf*3*sizeof(EncTopoSide));
-		slot[k].twin = o; o += al(nf*12);
-		if(!it.topo_lds) { slot[k].state = o; o += al(enc_topo_state_bytes<uint32_t>(it.nface_in, it.nvert_in)); }
-		slot[k].split = o; o += al(enc_topo_split_cap(it.nface_in)*4);
-		split_cap_total += enc_topo_split_cap(it.nface_in);
-	}
-	const uint64_t o_spack = o; o += al(split_cap_total*4);
-	for(uint32_t k = 0; k < n; k++) if(items[ids[k]].topo_image) { slot[k].clers = o; o += al(enc_topo_clers_cap(items[ids[k]].nface_in)); }
-	const uint64_t o_jobs = o; o += 1u << 16;                // job tables, rewritten stage by stage (stream-ordered)
-	std::vector<uint8_t> jobbuf;
-	uint64_t job_bytes = 0;
-	for(uint32_t k = 0; k < n; k++) job_bytes += items[ids[k]].attrs.size()*(sizeof(QuantJob) + sizeof(DeltaEncJob) + sizeof(EstJob) + 8) + 16;
-	job_bytes += devk.size()*(sizeof(EncTopoJob) + 8);
-	o += al(3*job_bytes);
-	DevMem dev;
-	{ const auto t0 = Clock::now(); BT_TRY(hipMalloc(&dev.p, o + 256)); S.alloc_ms += ms_since(t0); }
-	uint8_t *base = dev.u8();
-	struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // every way out waits for the work queued on the image first
-	auto sync = [&]() -> hipError_t { const auto t0 = Clock::now(); const hipError_t e = hipStreamSynchronize(st); S.sync_wait_ms += ms_since(t0); return e; };
-	uint64_t job_cursor = o_jobs;
-	std::vector<std::vector<uint8_t>> keep;                  // the job tables' host copies live until the chunk has finished
-	bool jobs_fit = true;
-	auto put_jobs = [&](const void *p, size_t bytes) -> uint8_t * {
-		uint8_t *d = base + job_cursor;
-		if(job_cursor + bytes > o) { jobs_fit = false; return nullptr; }
-		if(bytes) {
-			keep.emplace_back((const uint8_t *)p, (const uint8_t *)p + bytes);
-			if(hipMemcpyAsync(d, keep.back().data(), bytes, hipMemcpyHostToDevice, st) != hipSuccess) jobs_fit = false;
-			S.bytes_to_device += bytes;
-		}
-		job_cursor += al(bytes);
-		return d;
-	};
+	const int e = launch_jobs(C, tj, {&walk_ids}, K_TOPO_C, K_TOPO_W, [&](const EncTopoJob *dj, const uint32_t *const *ds) {
+		hipLaunchKernelGGL(k_enc_topo_compact, dim3(nd), dim3(ETOPO_THREADS), 0, C.st, dj, nd);
+		if(C.t[K_TOPO_C].end(C.st) || C.t[K_TOPO_P].begin(C.st)) return (int)CRTHIP_E_DEVICE;
+		hipLaunchKernelGGL(k_enc_topo_pair, dim3(nd), dim3(ETOPO_THREADS), 0, C.st, dj, nd);
+		if(C.t[K_TOPO_P].end(C.st) || C.t[K_TOPO_W].begin(C.st)) return (int)CRTHIP_E_DEVICE;
+		if(nlds) hipLaunchKernelGGL(k_enc_topo_walk<true>, dim3(nlds), dim3(ETOPO_THREADS), lds_bytes, C.st, dj, ds[0], nlds);
+		if(nd > nlds) hipLaunchKernelGGL(k_enc_topo_walk<false>, dim3(nd - nlds), dim3(ETOPO_THREADS), 0, C.st, dj, ds[0] + nlds, nd - nlds);
+		return 0;
+	});
+	if(e) return e;
+	C.bt.launches[K_TOPO_C]++; C.bt.launches[K_TOPO_P]++; C.bt.launches[K_TOPO_W] += (nlds ? 1u : 0u) + (nd > nlds ? 1u : 0u);
+	ENC_TRY(hipMemcpyAsync(C.back.data(), C.base + C.img.back, C.img.back_bytes, hipMemcpyDeviceToHost, C.st));
+	if(C.ev_back.record(C.st)) return CRTHIP_E_DEVICE;
+	C.S.bytes_from_device += C.img.back_bytes;
+	C.S.topology_device += nd; C.S.topology_lds += nlds;
+	return 0;
+}
 
-	// ---- raw inputs up: small ones staged into one copy, large ones straight from the caller ----
-	{
-		const auto t_stage = Clock::now();
-		std::vector<uint8_t> stage(staged_total);
-		for(const RawIn &r : raw) {
-			const uint64_t b = r.bytes;
-			if(!b) continue;
-			if(b < DIRECT_BYTES) memcpy(stage.data() + *r.off, r.src, b);
-			else { const auto t0 = Clock::now(); BT_TRY(hipMemcpyAsync(base + *r.off, r.src, b, hipMemcpyHostToDevice, st)); S.upload_ms += ms_since(t0); }
-			if(b >= DIRECT_BYTES) S.bytes_to_device += b;
-		}
-		S.host_stage_ms += ms_since(t_stage);
-		{ const auto t0 = Clock::now(); if(staged_total) BT_TRY(hipMemcpyAsync(base, stage.data(), staged_total, hipMemcpyHostToDevice, st)); S.upload_ms += ms_since(t0); }
-		S.bytes_to_device += staged_total;
-		BT_TRY(sync());
-	}
-	if(zero_bytes) BT_TRY(hipMemsetAsync(base + o_zero, 0, zero_bytes, st));
-
-	// ---- K-ENC-Q ----
-	Timer tq;
-	{
-		std::vector<QuantJob> qj; std::vector<uint32_t> start;
-		uint32_t blocks = 0;
-		for(uint32_t k = 0; k < n; k++) {
-			const BatchItem &it = items[ids[k]];
-			for(size_t a = 0; a < it.attrs.size(); a++) {
-				const QuantRequest &r = it.attrs[a].quant;
-				if(!r.count) continue;
-				QuantJob J{};
-				J.in = base + slot[k].in[a]; J.out = base + slot[k].q[a]; J.count = r.count; J.kind = r.kind; J.N = r.N; J.q = r.q; J.unit = r.unit; J.format = r.format;
-				for(int c = 0; c < 4; c++) J.qc[c] = r.qc[c] ? r.qc[c] : 1u;
-				qj.push_back(J); start.push_back(blocks); blocks += (r.count + 255)/256;
-			}
-		}
-		if(!qj.empty()) {
-			start.push_back(blocks);
-			const QuantJob *dj = (const QuantJob *)put_jobs(qj.data(), qj.size()*sizeof(QuantJob));
-			const uint32_t *ds = (const uint32_t *)put_jobs(start.data(), start.size()*4);
-			if(!jobs_fit) return ctx_fail(CRTHIP_E_DEVICE, "crthip_encode_batch: job tables");
-			if(tq.begin(st)) return CRTHIP_E_DEVICE;
-			hipLaunchKernelGGL(k_enc_quantize_batch, dim3(blocks), dim3(256), 0, st, dj, ds, (uint32_t)qj.size());
-			if(tq.end(st)) return CRTHIP_E_DEVICE;
-			BT_TRY(hipGetLastError());
-			bt.n_quant++;
-		}
-	}
-
-	// ---- K-ENC-TOPO: the topology pass of the meshes in devk, behind the quantiser; their records start back at once ----
-	Timer ttc, ttp, ttw;
-	Event ev_back;
-	std::vector<uint8_t> back(back_bytes);
-	const auto t_dtopo = Clock::now();
-	if(!devk.empty()) {
-		std::vector<EncTopoJob> tj(devk.size());
-		std::vector<uint32_t> walk_ids;                          // the LDS-resident walks first, then the global ones
-		uint32_t nlds = 0, lds_bytes = 0;
-		for(int pass = 0; pass < 2; pass++) for(uint32_t j = 0; j < devk.size(); j++) if(items[ids[devk[j]]].topo_lds == (pass == 0)) walk_ids.push_back(j);
-		for(uint32_t j = 0; j < devk.size(); j++) {
-			const uint32_t k = devk[j];
-			const BatchItem &it = items[ids[k]];
-			EncTopoJob &J = tj[j];
-			memset(&J, 0, sizeof(J));
-			J.index = (const uint32_t *)(base + slot[k].idx); J.gend_in = (const uint32_t *)(base + slot[k].gend_in);
-			J.faces = (uint32_t *)(base + o_faces) + (size_t)slot[k].fbase*3; J.gend_out = (uint32_t *)(base + slot[k].gend_out);
-			J.first = (uint32_t *)(base + slot[k].first); J.cursor = (uint32_t *)(base + slot[k].cursor);
-			J.sides = (EncTopoSide *)(base + slot[k].sides); J.twin = (uint32_t *)(base + slot[k].twin);
-			J.state = it.topo_lds ? nullptr : base + slot[k].state;
-			J.quads = (uint32_t *)(base + slot[k].quads); J.clers = base + slot[k].clers; J.split = (uint32_t *)(base + slot[k].split);
-			J.split_packed = (uint32_t *)(base + o_spack); J.split_cursor = (uint32_t *)(base + o_back);
-			J.rec = (EncTopoRecord *)(base + o_back + 256) + j;
-			J.nvert = it.nvert_in; J.nface = it.nface_in; J.ngroups = it.topo_groups;
-			if(it.topo_lds) { nlds++; lds_bytes = std::max(lds_bytes, (uint32_t)enc_topo_state_bytes<uint16_t>(it.nface_in, it.nvert_in)); }
-		}
-		const EncTopoJob *dj = (const EncTopoJob *)put_jobs(tj.data(), tj.size()*sizeof(EncTopoJob));
-		const uint32_t *dw = (const uint32_t *)put_jobs(walk_ids.data(), walk_ids.size()*4);
-		if(!jobs_fit) return ctx_fail(CRTHIP_E_DEVICE, "crthip_encode_batch: job tables");
-		const uint32_t nd = (uint32_t)devk.size();
-		if(ttc.begin(st)) return CRTHIP_E_DEVICE;
-		hipLaunchKernelGGL(k_enc_topo_compact, dim3(nd), dim3(ETOPO_THREADS), 0, st, dj, nd);
-		if(ttc.end(st) || ttp.begin(st)) return CRTHIP_E_DEVICE;
-		hipLaunchKernelGGL(k_enc_topo_pair, dim3(nd), dim3(ETOPO_THREADS), 0, st, dj, nd);
-		if(ttp.end(st) || ttw.begin(st)) return CRTHIP_E_DEVICE;
-		if(nlds) hipLaunchKernelGGL(k_enc_topo_walk<true>, dim3(nlds), dim3(ETOPO_THREADS), lds_bytes, st, dj, dw, nlds);
-		if(nd > nlds) hipLaunchKernelGGL(k_enc_topo_walk<false>, dim3(nd - nlds), dim3(ETOPO_THREADS), 0, st, dj, dw + nlds, nd - nlds);
-		if(ttw.end(st)) return CRTHIP_E_DEVICE;
-		BT_TRY(hipGetLastError());
-		bt.n_topo_c++; bt.n_topo_p++; bt.n_topo_w += (nlds ? 1u : 0u) + (nd > nlds ? 1u : 0u);
-		BT_TRY(hipMemcpyAsync(back.data(), base + o_back, back_bytes, hipMemcpyDeviceToHost, st));
-		if(ev_back.record(st)) return CRTHIP_E_DEVICE;
-		S.bytes_from_device += back_bytes;
-		S.topology_device += nd; S.topology_lds += nlds;
-	}
-
-	// ---- point clouds: Morton keys and the radix sort ----
-	std::vector<uint32_t> clouds;
-	for(uint32_t k = 0; k < n; k++) if(!is_mesh(items[ids[k]])) clouds.push_back(k);
-	std::vector<Timer> tzk(clouds.size()), tzs(clouds.size());
-	for(size_t c = 0; c < clouds.size(); c++) {
-		const uint32_t k = clouds[c];
-		const BatchItem &it = items[ids[k]];
+// The clouds' Morton keys and radix sort, one cloud after another.  R: slot.q of the position.  W: zmn, zkeys, zvals, zhist, slot.quads
+// (the sorted order as a prediction), the cloud's flag in zflags.  Not synchronised.
+int stage_cloud_sort(Chunk &C) {
+	C.tzk = std::vector<EventTimer>(C.img.clouds.size()); C.tzs = std::vector<EventTimer>(C.img.clouds.size());
+	for(size_t c = 0; c < C.img.clouds.size(); c++) {
+		const uint32_t k = C.img.clouds[c];
+		const BatchItem &it = C.item(k);
+		const Slot &s = C.img.slot[k];
 		if(it.nvert_in == 0) continue;
 		ZJob Z{};
-		Z.coords = (const int32_t *)(base + slot[k].q[0]);
-		for(size_t a = 0; a < it.attrs.size(); a++) if(it.attrs[a].position) Z.coords = (const int32_t *)(base + slot[k].q[a]);
-		Z.mn = (int32_t *)(base + slot[k].zmn); Z.flag = (uint32_t *)(base + o_zflags) + k; Z.n = it.nvert_in;
-		Z.keys = (uint64_t *)(base + slot[k].zkeys[0]); Z.vals = (uint32_t *)(base + slot[k].zvals[0]);
+		Z.coords = C.at<const int32_t>(s.q[it.pos]);
+		Z.mn = C.at<int32_t>(s.zmn); Z.flag = C.at<uint32_t>(C.img.zflags) + k; Z.n = it.nvert_in;
+		Z.keys = C.at<uint64_t>(s.zkeys[0]); Z.vals = C.at<uint32_t>(s.zvals[0]);
 		const uint32_t g = (it.nvert_in + 255)/256;
-		if(tzk[c].begin(st)) return CRTHIP_E_DEVICE;
-		hipLaunchKernelGGL(k_enc_zmin, dim3(g), dim3(256), 0, st, Z);
-		hipLaunchKernelGGL(k_enc_zkeys, dim3(g), dim3(256), 0, st, Z);
-		if(tzk[c].end(st)) return CRTHIP_E_DEVICE;
-		bt.n_zkeys += 2;
+		if(C.tzk[c].begin(C.st)) return CRTHIP_E_DEVICE;
+		hipLaunchKernelGGL(k_enc_zmin, dim3(g), dim3(256), 0, C.st, Z);
+		hipLaunchKernelGGL(k_enc_zkeys, dim3(g), dim3(256), 0, C.st, Z);
+		if(C.tzk[c].end(C.st)) return CRTHIP_E_DEVICE;
+		C.bt.launches[K_ZKEYS] += 2;
 		int where = 0; uint32_t launches = 0;
-		if(tzs[c].begin(st)) return CRTHIP_E_DEVICE;
-		{ const int e = radix_sort(st, Z.keys, Z.vals, (uint64_t *)(base + slot[k].zkeys[1]), (uint32_t *)(base + slot[k].zvals[1]),
-		                           (uint32_t *)(base + slot[k].zhist), it.nvert_in, 64, where, launches); if(e) return e; }
-		Z.keys = (uint64_t *)(base + slot[k].zkeys[where]); Z.vals = (uint32_t *)(base + slot[k].zvals[where]);
-		Z.quads = (uint32_t *)(base + slot[k].quads);
-		hipLaunchKernelGGL(k_enc_zflag, dim3(g), dim3(256), 0, st, Z);
-		if(tzs[c].end(st)) return CRTHIP_E_DEVICE;
-		BT_TRY(hipGetLastError());
-		bt.n_zsort += launches + 1;
+		if(C.tzs[c].begin(C.st)) return CRTHIP_E_DEVICE;
+		{ const int e = radix_sort(C.st, Z.keys, Z.vals, C.at<uint64_t>(s.zkeys[1]), C.at<uint32_t>(s.zvals[1]), C.at<uint32_t>(s.zhist), it.nvert_in, 64, where, launches); if(e) return e; }
+		Z.keys = C.at<uint64_t>(s.zkeys[where]); Z.vals = C.at<uint32_t>(s.zvals[where]);
+		Z.quads = C.at<uint32_t>(s.quads);
+		hipLaunchKernelGGL(k_enc_zflag, dim3(g), dim3(256), 0, C.st, Z);
+		if(C.tzs[c].end(C.st)) return CRTHIP_E_DEVICE;
+		ENC_TRY(hipGetLastError());
+		C.bt.launches[K_ZSORT] += launches + 1;
 	}
+	return 0;
+}
 
-	// ---- the device pass's records: each mesh's frame from its counts, group ends and split words (those came packed: a second copy)
-	if(mode == CRTHIP_TOPOLOGY_DEVICE) { for(uint32_t k : hostk) host_pass(k); topo_ms = ms_since(t_topo); }   // (the clouds' frames)
-	if(!devk.empty()) {
-		{ const auto t0 = Clock::now(); BT_TRY(hipEventSynchronize(ev_back.e)); S.sync_wait_ms += ms_since(t0); }
-		S.device_topology_ms += (float)ms_since(t_dtopo);
-		uint32_t nwords = 0;
-		memcpy(&nwords, back.data(), 4);
-		std::vector<uint32_t> words(nwords);
-		if(nwords > split_cap_total) return ctx_fail(CRTHIP_E_DEVICE, "crthip_encode_batch: the device topology pass's split words");
-		if(nwords) {
-			BT_TRY(hipMemcpyAsync(words.data(), base + o_spack, (size_t)nwords*4, hipMemcpyDeviceToHost, st));
-			BT_TRY(sync());
-			S.bytes_from_device += (uint64_t)nwords*4;
-		}
-		const auto t0 = Clock::now();
-		for(uint32_t j = 0; j < devk.size(); j++) {
-			const uint32_t k = devk[j];
-			BatchItem &it = items[ids[k]];
-			EncTopoRecord R;
-			memcpy(&R, back.data() + 256 + (size_t)j*sizeof(EncTopoRecord), sizeof(R));
-			if(R.status || R.nvert > it.nvert_in || R.nface > it.nface_in || (uint64_t)R.split_off + R.split_words > nwords || R.nclers > enc_topo_clers_cap(it.nface_in)) {
-				it.status = ctx_fail(CRTHIP_E_DEVICE, "crthip_encode_batch: the device topology pass stopped at a bound");
-				continue;
-			}
-			const int32_t e = item_guard([&] {
-				batch_frame(&meshes[ids[k]], extra ? &extra[ids[k]] : nullptr, it, R, (const uint32_t *)(back.data() + (slot[k].gend_out - o_back)), words.data() + R.split_off);
-			});
-			if(e) it.status = e;
-		}
-		S.host_frame_ms += (float)ms_since(t0);
+// The device pass's report: each mesh's frame from its counts, group ends and split words (those came packed: a second copy).
+// R: the report (through C.back), spack.  Waits for ev_back; synchronised only if split words came back.
+int collect_device_passes(Chunk &C) {
+	const ChunkImage &I = C.img;
+	{ const auto t0 = Clock::now(); ENC_TRY(hipEventSynchronize(C.ev_back.e)); C.S.sync_wait_ms += ms_since(t0); }
+	C.S.device_topology_ms += (float)ms_since(C.t_dtopo);
+	uint32_t nwords = 0;
+	memcpy(&nwords, C.back.data(), 4);
+	std::vector<uint32_t> words(nwords);
+	if(nwords > I.split_cap_total) return ctx_fail(CRTHIP_E_DEVICE, "crthip_encode_batch: the device topology pass's split words");
+	if(nwords) {
+		ENC_TRY(hipMemcpyAsync(words.data(), C.base + I.spack, (size_t)nwords*4, hipMemcpyDeviceToHost, C.st));
+		ENC_TRY(C.sync());
+		C.S.bytes_from_device += (uint64_t)nwords*4;
 	}
-	// ---- the host's topology passes as they finish: each mesh's faces and quads are staged as soon as its pass is done, and go up in
-	// two copies (one copy per mesh measured slower: 24.5 against 20.4 ms for 256 C4 units, tools/encode_batch_rate.py)
-	std::vector<uint8_t> up_quads(mquads_bytes), up_faces((size_t)faces_total*12);
-	for(uint32_t k = 0; k < n; k++) {
-		{ const auto tw = Clock::now(); std::unique_lock<std::mutex> g(mu); cv.wait(g, [&] { return ready[k] != 0; }); S.topology_wait_ms += ms_since(tw); }
-		BatchItem &it = items[ids[k]];
+	const auto t0 = Clock::now();
+	for(uint32_t j = 0; j < I.devk.size(); j++) {
+		const uint32_t k = I.devk[j];
+		BatchItem &it = C.item(k);
+		EncTopoRecord R;
+		memcpy(&R, C.back.data() + (I.rec(j) - I.back), sizeof(R));
+		if(R.status || R.nvert > it.nvert_in || R.nface > it.nface_in || (uint64_t)R.split_off + R.split_words > nwords || R.nclers > enc_topo_clers_cap(it.nface_in)) {
+			it.status = ctx_fail(CRTHIP_E_DEVICE, "crthip_encode_batch: the device topology pass stopped at a bound");
+			continue;
+		}
+		const int32_t e = item_guard([&] {
+			batch_frame(C.mesh(k), C.attrs(k), it, R, (const uint32_t *)(C.back.data() + (I.slot[k].gend_out - I.back)), words.data() + R.split_off);
+		});
+		if(e) it.status = e;
+	}
+	C.S.host_frame_ms += (float)ms_since(t0);
+	return 0;
+}
+
+// The topology passes' results.  Device mode's clouds get their frames here, inline; then the device pass's report
+// (collect_device_passes); then the host's passes as they finish: each mesh's faces and quads are staged as soon as its pass is done, and
+// go up in two copies per run of neighbouring meshes the host made (all of them, without a device pass; one copy per mesh measured
+// slower: 24.5 against 20.4 ms for 256 C4 units, tools/encode_batch_rate.py).  W: faces, slot.quads of those meshes.  Synchronised (the
+// staging buffers are locals); every host pass has finished when it returns.
+int collect_passes(Chunk &C, int mode) {
+	const ChunkImage &I = C.img;
+	if(mode == CRTHIP_TOPOLOGY_DEVICE) { for(uint32_t k : I.hostk) C.host_pass(k); C.topo_ms = ms_since(C.t_topo); }   // (the clouds' frames)
+	if(!I.devk.empty()) { const int e = collect_device_passes(C); if(e) return e; }
+	std::vector<uint8_t> up_quads(I.mquads_bytes), up_faces((size_t)I.faces_total*12);
+	for(uint32_t k = 0; k < C.n(); k++) {
+		{ const auto tw = Clock::now(); std::unique_lock<std::mutex> g(C.mu); C.cv.wait(g, [&] { return C.ready[k] != 0; }); C.S.topology_wait_ms += ms_since(tw); }
+		BatchItem &it = C.item(k);
 		if(!is_mesh(it) || it.topo_device) continue;
 		const auto t0 = Clock::now();
 		const size_t fb = std::min(it.faces.size()*4, (size_t)it.nface_in*12), qb = std::min(it.quads.size()*4, (size_t)it.nvert_in*16);
-		if(fb) memcpy(up_faces.data() + (size_t)slot[k].fbase*12, it.faces.data(), fb);
-		if(qb) memcpy(up_quads.data() + (slot[k].quads - o_mquads), it.quads.data(), qb);
-		S.host_stage_ms += ms_since(t0);
+		if(fb) memcpy(up_faces.data() + (size_t)I.slot[k].fbase*12, it.faces.data(), fb);
+		if(qb) memcpy(up_quads.data() + (I.slot[k].quads - I.mquads), it.quads.data(), qb);
+		C.S.host_stage_ms += ms_since(t0);
 	}
-	{
-		// one copy each per run of neighbouring meshes the host made (all of them, without a device pass)
-		const auto t0 = Clock::now();
-		std::vector<uint32_t> mk;
-		for(uint32_t k = 0; k < n; k++) if(is_mesh(items[ids[k]])) mk.push_back(k);
-		for(size_t a = 0; a < mk.size();) {
-			if(items[ids[mk[a]]].topo_device) { a++; continue; }
-			size_t b = a;
-			while(b + 1 < mk.size() && !items[ids[mk[b + 1]]].topo_device) b++;
-			const BatchItem &last = items[ids[mk[b]]];
-			const uint64_t q0 = slot[mk[a]].quads, q1 = slot[mk[b]].quads + (uint64_t)last.nvert_in*16;
-			const uint64_t f0 = (uint64_t)slot[mk[a]].fbase*12, f1 = ((uint64_t)slot[mk[b]].fbase + last.nface_in)*12;
-			if(q1 > q0) BT_TRY(hipMemcpyAsync(base + q0, up_quads.data() + (q0 - o_mquads), q1 - q0, hipMemcpyHostToDevice, st));
-			if(f1 > f0) BT_TRY(hipMemcpyAsync(base + o_faces + f0, up_faces.data() + f0, f1 - f0, hipMemcpyHostToDevice, st));
-			S.bytes_to_device += (q1 - q0) + (f1 - f0);
-			a = b + 1;
-		}
-		S.upload_ms += ms_since(t0);
+	const auto t0 = Clock::now();
+	std::vector<uint32_t> mk;
+	for(uint32_t k = 0; k < C.n(); k++) if(is_mesh(C.item(k))) mk.push_back(k);
+	for(size_t a = 0; a < mk.size();) {
+		if(C.item(mk[a]).topo_device) { a++; continue; }
+		size_t b = a;
+		while(b + 1 < mk.size() && !C.item(mk[b + 1]).topo_device) b++;
+		const BatchItem &last = C.item(mk[b]);
+		const uint64_t q0 = I.slot[mk[a]].quads, q1 = I.slot[mk[b]].quads + (uint64_t)last.nvert_in*16;
+		const uint64_t f0 = (uint64_t)I.slot[mk[a]].fbase*12, f1 = ((uint64_t)I.slot[mk[b]].fbase + last.nface_in)*12;
+		if(q1 > q0) ENC_TRY(hipMemcpyAsync(C.base + q0, up_quads.data() + (q0 - I.mquads), q1 - q0, hipMemcpyHostToDevice, C.st));
+		if(f1 > f0) ENC_TRY(hipMemcpyAsync(C.base + I.faces + f0, up_faces.data() + f0, f1 - f0, hipMemcpyHostToDevice, C.st));
+		C.S.bytes_to_device += (q1 - q0) + (f1 - f0);
+		a = b + 1;
 	}
-	BT_TRY(sync());
-	if(pool.joinable()) pool.join();
-	S.host_topology_ms += (float)topo_ms;
-	for(uint32_t k = 0; k < n; k++) {                                     // Tunstall streams over 2^23 symbols: the reference's count*255 overflow
-		BatchItem &it = items[ids[k]];
-		if(it.entropy == CRTHIP_ENTROPY_TUNSTALL && (it.nclers > (1u << 23) || it.nvert > (1u << 23)))
-			it.status = ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: a Tunstall stream longer than 2^23 symbols");
-	}
+	C.S.upload_ms += ms_since(t0);
+	ENC_TRY(C.sync());
+	return 0;
+}
 
-	// ---- K-ENC-EST ----
-	Timer te;
-	{
-		std::vector<EstJob> ej; std::vector<uint32_t> fstart, vstart;
-		uint32_t fb = 0, vb = 0, vbase = 0, cbase = 0;
-		for(uint32_t k = 0; k < n; k++) {
-			const BatchItem &it = items[ids[k]];
-			if(it.status) continue;
-			int pos = 0;
-			for(size_t a = 0; a < it.attrs.size(); a++) if(it.attrs[a].position) pos = (int)a;
-			for(size_t a = 0; a < it.attrs.size(); a++) {
-				if(!est_of(it, it.attrs[a])) continue;
-				EstJob J{};
-				J.faces = (const uint32_t *)(base + o_faces) + (size_t)slot[k].fbase*3;
-				J.coords = (const int32_t *)(base + slot[k].q[pos]);
-				J.normals = (int32_t *)(base + slot[k].q[a]);
-				J.boundary = it.attrs[a].prediction == 2 ? (int32_t *)(base + slot[k].boundary) : nullptr;
-				J.nface = it.nface; J.nvert = it.nvert_in;
-				J.vbase = vbase; J.fbase = slot[k].fbase; J.cbase = cbase; J.unit = it.attrs[a].quant.unit;
-				ej.push_back(J); fstart.push_back(fb); vstart.push_back(vb);
-				fb += (J.nface + 255)/256; vb += (J.nvert + 255)/256;
-				vbase += J.nvert; cbase += 3*J.nface;
-			}
-		}
-		if(!ej.empty()) {
-			fstart.push_back(fb); vstart.push_back(vb);
-			const EstJob *dj = (const EstJob *)put_jobs(ej.data(), ej.size()*sizeof(EstJob));
-			const uint32_t *dfs = (const uint32_t *)put_jobs(fstart.data(), fstart.size()*4);
-			const uint32_t *dvs = (const uint32_t *)put_jobs(vstart.data(), vstart.size()*4);
-			if(!jobs_fit) return ctx_fail(CRTHIP_E_DEVICE, "crthip_encode_batch: job tables");
-			uint32_t *ck0 = (uint32_t *)(base + o_ck[0]), *ck1 = (uint32_t *)(base + o_ck[1]);
-			uint32_t *cv0 = (uint32_t *)(base + o_cv[0]), *cv1 = (uint32_t *)(base + o_cv[1]);
-			if(te.begin(st)) return CRTHIP_E_DEVICE;
-			if(fb) hipLaunchKernelGGL(k_enc_corners, dim3(fb), dim3(256), 0, st, dj, dfs, (uint32_t)ej.size(), ck0, cv0);
-			uint32_t bits = 8, launches = 0;
-			while(bits < 32 && (vbase >> bits)) bits += 8;
-			int where = 0;
-			{ const int e = radix_sort(st, ck0, cv0, ck1, cv1, (uint32_t *)(base + o_chist), cbase, bits, where, launches); if(e) return e; }
-			if(vb) hipLaunchKernelGGL(k_enc_est_normal, dim3(vb), dim3(256), 0, st, dj, dvs, (uint32_t)ej.size(), (const uint32_t *)(where ? ck1 : ck0),
-			                          (const uint32_t *)(where ? cv1 : cv0), cbase, (const uint32_t *)(base + o_faces));
-			if(te.end(st)) return CRTHIP_E_DEVICE;
-			BT_TRY(hipGetLastError());
-			bt.n_est += launches + 2;
+// K-ENC-EST: the estimated normals of every mesh attribute that predicts from them (corners -> sort by vertex -> sum per vertex).
+// R: faces, slot.q of the position.  W: slot.q of the normals (the estimate is subtracted in place), slot.boundary, ck, cv, chist, job
+// tables.  Not synchronised.
+int stage_estimate(Chunk &C) {
+	std::vector<EstJob> ej; std::vector<uint32_t> fstart, vstart;
+	uint32_t fb = 0, vb = 0, vbase = 0, cbase = 0;
+	for(uint32_t k = 0; k < C.n(); k++) {
+		const BatchItem &it = C.item(k);
+		const Slot &s = C.img.slot[k];
+		if(it.status) continue;
+		for(size_t a = 0; a < it.attrs.size(); a++) {
+			if(!est_of(it, it.attrs[a])) continue;
+			EstJob J{};
+			J.faces = C.at<const uint32_t>(C.img.faces) + (size_t)s.fbase*3;
+			J.coords = C.at<const int32_t>(s.q[it.pos]);
+			J.normals = C.at<int32_t>(s.q[a]);
+			J.boundary = it.attrs[a].prediction == 2 ? C.at<int32_t>(s.boundary) : nullptr;
+			J.nface = it.nface; J.nvert = it.nvert_in;
+			J.vbase = vbase; J.fbase = s.fbase; J.cbase = cbase; J.unit = it.attrs[a].quant.unit;
+			ej.push_back(J); fstart.push_back(fb); vstart.push_back(vb);
+			fb += (J.nface + 255)/256; vb += (J.nvert + 255)/256;
+			vbase += J.nvert; cbase += 3*J.nface;
 		}
 	}
+	if(ej.empty()) return 0;
+	fstart.push_back(fb); vstart.push_back(vb);
+	uint32_t launches = 0;
+	const int e = launch_jobs(C, ej, {&fstart, &vstart}, K_EST, K_EST, [&](const EstJob *dj, const uint32_t *const *ds) {
+		uint32_t *ck0 = C.at<uint32_t>(C.img.ck[0]), *ck1 = C.at<uint32_t>(C.img.ck[1]);
+		uint32_t *cv0 = C.at<uint32_t>(C.img.cv[0]), *cv1 = C.at<uint32_t>(C.img.cv[1]);
+		if(fb) hipLaunchKernelGGL(k_enc_corners, dim3(fb), dim3(256), 0, C.st, dj, ds[0], (uint32_t)ej.size(), ck0, cv0);
+		uint32_t bits = 8;
+		while(bits < 32 && (vbase >> bits)) bits += 8;
+		int where = 0;
+		{ const int e = radix_sort(C.st, ck0, cv0, ck1, cv1, C.at<uint32_t>(C.img.chist), cbase, bits, where, launches); if(e) return e; }
+		if(vb) hipLaunchKernelGGL(k_enc_est_normal, dim3(vb), dim3(256), 0, C.st, dj, ds[1], (uint32_t)ej.size(), (const uint32_t *)(where ? ck1 : ck0),
+		                          (const uint32_t *)(where ? cv1 : cv0), cbase, C.at<const uint32_t>(C.img.faces));
+		return 0;
+	});
+	if(!e) C.bt.launches[K_EST] += launches + 2;
+	return e;
+}
 
-	// ---- clouds whose sorted keys have equal neighbours: the host's std::sort decides their order ----
-	std::vector<uint32_t> zflags(n, 0);
-	if(!clouds.empty()) {
-		BT_TRY(hipMemcpyAsync(zflags.data(), base + o_zflags, (size_t)n*4, hipMemcpyDeviceToHost, st));
-		BT_TRY(sync());
-		S.bytes_from_device += (uint64_t)n*4;
+// Clouds whose sorted keys have equal neighbours: the host's std::sort decides their order.  R: zflags, slot.q of the position.
+// W: slot.quads of those clouds.  Synchronised if the chunk has a cloud (every copy here is waited for: its buffer is a local).
+int resort_tied_clouds(Chunk &C) {
+	std::vector<uint32_t> zflags(C.n(), 0);
+	if(!C.img.clouds.empty()) {
+		ENC_TRY(hipMemcpyAsync(zflags.data(), C.base + C.img.zflags, (size_t)C.n()*4, hipMemcpyDeviceToHost, C.st));
+		ENC_TRY(C.sync());
+		C.S.bytes_from_device += (uint64_t)C.n()*4;
 	}
-	for(uint32_t k : clouds) {
-		BatchItem &it = items[ids[k]];
+	for(uint32_t k : C.img.clouds) {
+		BatchItem &it = C.item(k);
 		if(it.nvert_in == 0 || it.status) continue;
-		if(!zflags[k]) { S.clouds_device_sorted++; continue; }
-		int pos = 0;
-		for(size_t a = 0; a < it.attrs.size(); a++) if(it.attrs[a].position) pos = (int)a;
+		if(!zflags[k]) { C.S.clouds_device_sorted++; continue; }
 		std::vector<int32_t> coords((size_t)it.nvert_in*3);
-		BT_TRY(hipMemcpyAsync(coords.data(), base + slot[k].q[pos], coords.size()*4, hipMemcpyDeviceToHost, st));
-		BT_TRY(sync());
-		S.bytes_from_device += coords.size()*4;
+		ENC_TRY(hipMemcpyAsync(coords.data(), C.base + C.img.slot[k].q[it.pos], coords.size()*4, hipMemcpyDeviceToHost, C.st));
+		ENC_TRY(C.sync());
+		C.S.bytes_from_device += coords.size()*4;
 		std::vector<uint32_t> order;
 		morton_order_host(coords.data(), it.nvert_in, order);
 		std::vector<uint32_t> quads((size_t)it.nvert_in*4);
@@ -536,68 +560,72 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_list
 			const uint32_t prev = i ? order[i - 1] : 0xffffffffu;
 			quads[(size_t)i*4] = order[i]; quads[(size_t)i*4 + 1] = prev; quads[(size_t)i*4 + 2] = prev; quads[(size_t)i*4 + 3] = prev;
 		}
-		BT_TRY(hipMemcpyAsync(base + slot[k].quads, quads.data(), quads.size()*4, hipMemcpyHostToDevice, st));
-		BT_TRY(sync());
-		S.bytes_to_device += quads.size()*4;
-		S.clouds_host_sorted++;
+		ENC_TRY(hipMemcpyAsync(C.base + C.img.slot[k].quads, quads.data(), quads.size()*4, hipMemcpyHostToDevice, C.st));
+		ENC_TRY(C.sync());
+		C.S.bytes_to_device += quads.size()*4;
+		C.S.clouds_host_sorted++;
 	}
+	return 0;
+}
 
-	// ---- K-ENC-DELTA ----
-	Timer td;
-	{
-		std::vector<DeltaEncJob> dj; std::vector<uint32_t> start;
-		uint32_t blocks = 0;
-		for(uint32_t k = 0; k < n; k++) {
-			const BatchItem &it = items[ids[k]];
-			if(it.status) continue;
-			for(size_t a = 0; a < it.attrs.size(); a++) {
-				const BatchAttr &A = it.attrs[a];
-				DeltaEncJob J{};
-				J.values = base + slot[k].q[a]; J.quads = (const uint32_t *)(base + slot[k].quads); J.out = base + slot[k].d[a];
-				J.count = it.nvert; J.N = A.N; J.parallel = (A.strategy & CRTHIP_PARALLEL) ? 1u : 0u;
-				J.out_count = (uint32_t *)(base + slot[k].count) + a;
-				if(A.codec == CRTHIP_CODEC_COLOR) J.kind = DENC_U8;
-				else if(A.codec == CRTHIP_CODEC_NORMAL) {
-					J.N = 2;
-					J.kind = A.prediction == 0 ? DENC_NRM_DIFF : A.prediction == 1 ? DENC_NRM_EST : DENC_NRM_BORDER;
-					if(J.kind == DENC_NRM_BORDER) J.boundary = (const int32_t *)(base + slot[k].boundary);
-					if(J.kind == DENC_NRM_BORDER && !is_mesh(it)) { J.kind = DENC_NRM_EST; J.count = 0; }   // a cloud has no faces: no vertex is on a border
-				} else J.kind = DENC_I32;
-				if(J.kind != DENC_NRM_BORDER && J.count == 0) continue;
-				dj.push_back(J); start.push_back(blocks);
-				blocks += J.kind == DENC_NRM_BORDER ? 1u : (J.count + DENC_BLOCK - 1)/DENC_BLOCK;
-			}
-		}
-		if(!dj.empty()) {
-			start.push_back(blocks);
-			const DeltaEncJob *d = (const DeltaEncJob *)put_jobs(dj.data(), dj.size()*sizeof(DeltaEncJob));
-			const uint32_t *ds = (const uint32_t *)put_jobs(start.data(), start.size()*4);
-			if(!jobs_fit) return ctx_fail(CRTHIP_E_DEVICE, "crthip_encode_batch: job tables");
-			if(td.begin(st)) return CRTHIP_E_DEVICE;
-			hipLaunchKernelGGL(k_enc_delta, dim3(blocks), dim3(256), 0, st, d, ds, (uint32_t)dj.size());
-			if(td.end(st)) return CRTHIP_E_DEVICE;
-			BT_TRY(hipGetLastError());
-			bt.n_delta++;
+// K-ENC-DELTA: every attribute's residuals in one launch.  R: slot.q, slot.quads, slot.boundary.  W: slot.d, slot.count (BORDER normals:
+// how many residuals), job tables.  Not synchronised.
+int stage_delta(Chunk &C) {
+	std::vector<DeltaEncJob> dj; std::vector<uint32_t> start;
+	uint32_t blocks = 0;
+	for(uint32_t k = 0; k < C.n(); k++) {
+		const BatchItem &it = C.item(k);
+		const Slot &s = C.img.slot[k];
+		if(it.status) continue;
+		for(size_t a = 0; a < it.attrs.size(); a++) {
+			const BatchAttr &A = it.attrs[a];
+			DeltaEncJob J{};
+			J.values = C.base + s.q[a]; J.quads = C.at<const uint32_t>(s.quads); J.out = C.base + s.d[a];
+			J.count = it.nvert; J.N = A.N; J.parallel = (A.strategy & CRTHIP_PARALLEL) ? 1u : 0u;
+			J.out_count = C.at<uint32_t>(s.count) + a;
+			if(A.codec == CRTHIP_CODEC_COLOR) J.kind = DENC_U8;
+			else if(A.codec == CRTHIP_CODEC_NORMAL) {
+				J.N = 2;
+				J.kind = A.prediction == 0 ? DENC_NRM_DIFF : A.prediction == 1 ? DENC_NRM_EST : DENC_NRM_BORDER;
+				if(J.kind == DENC_NRM_BORDER) J.boundary = C.at<const int32_t>(s.boundary);
+				if(J.kind == DENC_NRM_BORDER && !is_mesh(it)) { J.kind = DENC_NRM_EST; J.count = 0; }   // a cloud has no faces: no vertex is on a border
+			} else J.kind = DENC_I32;
+			if(J.kind != DENC_NRM_BORDER && J.count == 0) continue;
+			dj.push_back(J); start.push_back(blocks);
+			blocks += J.kind == DENC_NRM_BORDER ? 1u : (J.count + DENC_BLOCK - 1)/DENC_BLOCK;
 		}
 	}
-	// BORDER counts back (mesh k's attributes from count_at[k] on)
-	std::vector<size_t> count_at(n + 1, 0);
-	for(uint32_t k = 0; k < n; k++) count_at[k + 1] = count_at[k] + items[ids[k]].attrs.size();
+	if(dj.empty()) return 0;
+	start.push_back(blocks);
+	const int e = launch_jobs(C, dj, {&start}, K_DELTA, K_DELTA, [&](const DeltaEncJob *d, const uint32_t *const *ds) {
+		hipLaunchKernelGGL(k_enc_delta, dim3(blocks), dim3(256), 0, C.st, d, ds[0], (uint32_t)dj.size());
+		return 0;
+	});
+	if(!e) C.bt.launches[K_DELTA]++;
+	return e;
+}
+
+// BORDER counts back, then value + entropy coding: every stream of every item in one call (encode_gpu.cpp).  With the counts the stream
+// is waited for, and the stages' times are read.  The host-made CLERS symbols then go up: into the image beside the device pass's (every
+// mode but HOST), else into an allocation of their own, in one copy.  R: slot.count, slot.d, slot.clers.  W: slot.clers of the host-made
+// meshes.  Synchronised (the value coder ends so).
+int code_values(Chunk &C, int mode, std::vector<EncValueResult> &res) {
+	const uint32_t n = C.n();
+	std::vector<size_t> count_at(n + 1, 0);                  // mesh k's attributes from count_at[k] on
+	for(uint32_t k = 0; k < n; k++) count_at[k + 1] = count_at[k] + C.item(k).attrs.size();
 	std::vector<uint32_t> counts(count_at[n] + 1, 0);
 	for(uint32_t k = 0; k < n; k++) {
-		const BatchItem &it = items[ids[k]];
+		const BatchItem &it = C.item(k);
 		if(it.status) continue;
-		for(const BatchAttr &A : it.attrs) if(A.codec == CRTHIP_CODEC_NORMAL && A.prediction == 2 && is_mesh(it)) {
-			BT_TRY(hipMemcpyAsync(&counts[count_at[k]], base + slot[k].count, 4*it.attrs.size(), hipMemcpyDeviceToHost, st));
-			S.bytes_from_device += 4*it.attrs.size();
+		for(const BatchAttr &A : it.attrs) if(border_of(it, A)) {
+			ENC_TRY(hipMemcpyAsync(&counts[count_at[k]], C.base + C.img.slot[k].count, 4*it.attrs.size(), hipMemcpyDeviceToHost, C.st));
+			C.S.bytes_from_device += 4*it.attrs.size();
 		}
 	}
-	BT_TRY(sync());
-	bt.quant += tq.ms(); bt.est += te.ms(); bt.delta += td.ms();
-	bt.topo_c += ttc.ms(); bt.topo_p += ttp.ms(); bt.topo_w += ttw.ms();
-	for(size_t c = 0; c < clouds.size(); c++) { bt.zkeys += tzk[c].ms(); bt.zsort += tzs[c].ms(); }
+	ENC_TRY(C.sync());
+	for(int i = 0; i < K_STAGES; i++) C.t[i].add_to(C.bt.ms[i]);
+	for(size_t c = 0; c < C.tzk.size(); c++) { C.tzk[c].add_to(C.bt.ms[K_ZKEYS]); C.tzs[c].add_to(C.bt.ms[K_ZSORT]); }
 
-	// ---- value + entropy coding: every stream of every mesh in one call; the CLERS symbols go up in one copy ----
 	std::vector<uint64_t> clers_at(n, 0);
 	uint64_t cl = 0;
 	const bool clers_in_image = mode != CRTHIP_TOPOLOGY_HOST;     // the device pass wrote its meshes' symbols there; the host's follow them
@@ -605,74 +633,98 @@ int run_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_list
 		const auto t0 = Clock::now();
 		bool any = false;
 		for(uint32_t k = 0; k < n; k++) {
-			const BatchItem &it = items[ids[k]];
+			const BatchItem &it = C.item(k);
 			if(it.topo_device || it.clers.empty() || !it.topo_image) continue;
-			BT_TRY(hipMemcpyAsync(base + slot[k].clers, it.clers.data(), it.clers.size(), hipMemcpyHostToDevice, st));
-			S.bytes_to_device += it.clers.size();
+			ENC_TRY(hipMemcpyAsync(C.base + C.img.slot[k].clers, it.clers.data(), it.clers.size(), hipMemcpyHostToDevice, C.st));
+			C.S.bytes_to_device += it.clers.size();
 			any = true;
 		}
-		S.upload_ms += ms_since(t0);
-		if(any) BT_TRY(sync());
-	} else for(uint32_t k = 0; k < n; k++) { clers_at[k] = cl; cl += al(items[ids[k]].clers.size()); }
+		C.S.upload_ms += ms_since(t0);
+		if(any) ENC_TRY(C.sync());
+	} else cl = clers_layout(C.items, C.img, clers_at);
 	DevMem dclers;
 	if(cl) {
 		const auto t0 = Clock::now();
 		std::vector<uint8_t> h(cl);
-		for(uint32_t k = 0; k < n; k++) if(!items[ids[k]].clers.empty()) memcpy(h.data() + clers_at[k], items[ids[k]].clers.data(), items[ids[k]].clers.size());
-		S.host_stage_ms += ms_since(t0);
-		BT_TRY(hipMalloc(&dclers.p, cl));
-		BT_TRY(hipMemcpyAsync(dclers.p, h.data(), cl, hipMemcpyHostToDevice, st));
-		BT_TRY(sync());
-		S.bytes_to_device += cl;
+		for(uint32_t k = 0; k < n; k++) if(!C.item(k).clers.empty()) memcpy(h.data() + clers_at[k], C.item(k).clers.data(), C.item(k).clers.size());
+		C.S.host_stage_ms += ms_since(t0);
+		ENC_TRY(hipMalloc(&dclers.p, cl));
+		ENC_TRY(hipMemcpyAsync(dclers.p, h.data(), cl, hipMemcpyHostToDevice, C.st));
+		ENC_TRY(C.sync());
+		C.S.bytes_to_device += cl;
 	}
 	std::vector<DevValueStream> vs;
 	for(uint32_t k = 0; k < n; k++) {
-		BatchItem &it = items[ids[k]];
+		BatchItem &it = C.item(k);
 		if(it.status) continue;
 		for(BatchStream &b : it.streams) {
 			if(b.kind == BATCH_BITS) continue;
 			DevValueStream v;
 			v.kind = b.kind; v.entropy = it.entropy; v.components = b.N;
-			if(b.attr == -1) { v.count = it.nclers; v.values = clers_in_image ? base + slot[k].clers : dclers.u8() + clers_at[k]; }
+			if(b.attr == -1) { v.count = it.nclers; v.values = clers_in_image ? C.base + C.img.slot[k].clers : dclers.u8() + clers_at[k]; }
 			else {
-				const BatchAttr &A = it.attrs[b.attr];
-				if(A.codec == CRTHIP_CODEC_NORMAL && A.prediction == 2 && is_mesh(it)) b.count = counts[count_at[k] + b.attr];
+				if(border_of(it, it.attrs[b.attr])) b.count = counts[count_at[k] + b.attr];
 				v.count = b.count;
-				v.values = base + slot[k].d[b.attr];
+				v.values = C.base + C.img.slot[k].d[b.attr];
 			}
 			vs.push_back(v);
 		}
 	}
-	std::vector<EncValueResult> res;
-	{
-		const auto t0 = Clock::now();
-		const int e = encode_value_streams_device(ctx, vs, res, tm);
-		S.value_coder_ms += ms_since(t0);
-		if(e) return e;
-	}
-	S.value_streams += (uint32_t)vs.size();
+	const auto t0 = Clock::now();
+	const int e = encode_value_streams_device(C.ctx, vs, res, C.tm);
+	C.S.value_coder_ms += ms_since(t0);
+	if(e) return e;
+	C.S.value_streams += (uint32_t)vs.size();
+	return 0;
+}
 
-	// ---- splice: the frame, with every stream where it belongs; zero padding to 4 bytes before a bit stream's words ----
+// the device half of one chunk: the items of img.ids have been set up; their topology passes run here, on the pool (overlapping the
+// device) or on the device
+int encode_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_list *extra, std::vector<BatchItem> &items, const ChunkImage &img, uint64_t budget,
+                 uint32_t threads, std::vector<std::vector<uint8_t>> &blobs, crthip_encode_batch_stats &S, BatchTimes &bt, EncStageTimes &tm) {
+	const int mode = ctx_encode_topology(ctx);
+	// the chunker sized this chunk by this very image, so only a single item can still be beyond the budget: nothing is allocated for it
+	if(img.total > budget) return ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: a mesh too big for the device image");
+	// Lifetimes, by declaration order (destruction runs upwards).  The pool thread's lambdas hold references to C (ready / mu / cv /
+	// topo_ms are its members) and through it to items and img: all declared before the thread, whose Joiner joins it on every way out.
+	// The image's memory is freed by DevMem only after Drain has waited for the work queued on it, and C's host buffers go after that.
+	Chunk C{ctx, ctx_stream(ctx), meshes, extra, items, img, S, bt, tm};
+	for(uint32_t k : img.devk) C.ready[k] = 1;
+	// topology passes (meshes) and frames (everything) on the pool, started first: they need the index alone
+	std::thread pool;
+	struct Joiner { std::thread &t; ~Joiner() { if(t.joinable()) t.join(); } } joiner{pool};
+	if(mode != CRTHIP_TOPOLOGY_DEVICE) pool = std::thread([&]() {      // (device mode starts no thread: the clouds' frames are made inline, collect_passes)
+		parallel_for((uint32_t)img.hostk.size(), threads, [&](uint32_t j) { C.host_pass(img.hostk[j]); });
+		std::lock_guard<std::mutex> g(C.mu);
+		C.topo_ms = ms_since(C.t_topo);
+	});
+	DevMem dev;
+	{ const auto t0 = Clock::now(); ENC_TRY(hipMalloc(&dev.p, img.total + 256)); S.alloc_ms += ms_since(t0); }
+	C.base = dev.u8();
+	struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{C.st};   // every way out waits for the work queued on the image first
+
+	int e = upload_inputs(C);
+	if(!e) e = stage_quantise(C);
+	if(!e) e = stage_topology(C);
+	if(!e) e = stage_cloud_sort(C);
+	if(!e) e = collect_passes(C, mode);
+	if(e) return e;
+	if(pool.joinable()) pool.join();
+	S.host_topology_ms += (float)C.topo_ms;
+	for(uint32_t id : img.ids)                                         // Tunstall streams over 2^23 symbols: the reference's count*255 overflow
+		if(items[id].entropy == CRTHIP_ENTROPY_TUNSTALL && (items[id].nclers > (1u << 23) || items[id].nvert > (1u << 23)))
+			items[id].status = ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: a Tunstall stream longer than 2^23 symbols");
+	e = stage_estimate(C);
+	if(!e) e = resort_tied_clouds(C);
+	if(!e) e = stage_delta(C);
+	std::vector<EncValueResult> res;
+	if(!e) e = code_values(C, mode, res);
+	if(e) return e;
+
+	// splice: every container from its frame and its streams' results, in item order
 	const auto t_frame = Clock::now();
 	size_t r = 0;
-	for(uint32_t k = 0; k < n; k++) {
-		BatchItem &it = items[ids[k]];
-		if(it.status) continue;
-		std::vector<uint8_t> &f = blobs[ids[k]];
-		f.clear();
-		f.reserve(it.frame.size() + 64);
-		auto u32 = [&](uint32_t v) { const uint8_t b[4] = {(uint8_t)v, (uint8_t)(v >> 8), (uint8_t)(v >> 16), (uint8_t)(v >> 24)}; f.insert(f.end(), b, b + 4); };
-		auto bits = [&](const std::vector<uint32_t> &w) { u32((uint32_t)w.size()); while(f.size() & 3) f.push_back(0); for(uint32_t x : w) u32(x); };
-		size_t prev = 0;
-		for(const BatchStream &b : it.streams) {
-			f.insert(f.end(), it.frame.begin() + prev, it.frame.begin() + b.at); prev = b.at;
-			if(b.kind == BATCH_BITS) { bits(it.split_words); continue; }
-			const EncValueResult &x = res[r++];
-			if(b.kind != CRTHIP_ENC_SYMBOLS) bits(x.words);
-			for(const std::vector<uint8_t> &blk : x.blocks) f.insert(f.end(), blk.begin(), blk.end());
-		}
-		f.insert(f.end(), it.frame.begin() + prev, it.frame.end());
-	}
+	for(uint32_t id : img.ids) if(!items[id].status) r += splice_container(items[id].frame, items[id].streams, res.data() + r, items[id].split_words, blobs[id]);
 	S.host_frame_ms += (float)ms_since(t_frame);
 	return CRTHIP_OK;
 }
@@ -691,7 +743,7 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 	blob_offset[0] = 0;
 	if(n == 0) { if(stats) *stats = S; return 0; }
 	const uint32_t threads = host_threads ? host_threads : default_threads();
-	BT_TRY(hipSetDevice(ctx_device(ctx)));
+	ENC_TRY(hipSetDevice(ctx_device(ctx)));
 	{ const int e = ctx_quiesce(ctx); if(e) return e; }
 
 	// per-mesh argument checks; what fails gets its code and an empty range
@@ -725,18 +777,20 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 
 	// chunks that fit the device
 	size_t free_b = 0, total_b = 0;
-	BT_TRY(hipMemGetInfo(&free_b, &total_b));
+	ENC_TRY(hipMemGetInfo(&free_b, &total_b));
 	const uint64_t budget = free_b/2;
 	std::vector<std::vector<uint8_t>> blobs(n);
 	BatchTimes bt;
 	EncStageTimes tm;
 	for(size_t k = 0; k < ok.size();) {
-		std::vector<uint32_t> ids;
-		uint64_t bytes = 0;
-		while(k < ok.size() && (ids.empty() || bytes + item_bytes(items[ok[k]]) <= budget)) { bytes += item_bytes(items[ok[k]]); ids.push_back(ok[k]); k++; }
-		if(bytes > budget) return ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: a mesh too big for the device image");
-		const int e = run_chunk(ctx, meshes, extra, items, ids, threads, blobs, S, bt, tm);
+		// a chunk is sized by building its image: of every item that is left (the usual case), else of half as many until the image fits
+		// (an image only grows with another item).  A single item beyond the budget fails where encode_chunk allocates.
+		size_t take = ok.size() - k;
+		ChunkImage img = build_image(meshes, items, std::vector<uint32_t>(ok.begin() + k, ok.end()));
+		while(img.total > budget && take > 1) { take = (take + 1)/2; img = build_image(meshes, items, std::vector<uint32_t>(ok.begin() + k, ok.begin() + k + take)); }
+		const int e = encode_chunk(ctx, meshes, extra, items, img, budget, threads, blobs, S, bt, tm);
 		if(e) return e;
+		k += take;
 	}
 
 	uint64_t w = 0;
@@ -755,15 +809,7 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 	if(stats) *stats = S;
 	if(times) {
 		uint32_t c = 0;
-		auto add = [&](const char *nm, float ms, uint32_t launches) { if(!launches) return; times->name[c] = nm; times->ms[c] = ms; times->launches[c] = launches; c++; };
-		add("enc_quantize_batch", bt.quant, bt.n_quant);
-		add("enc_topo_compact", bt.topo_c, bt.n_topo_c);
-		add("enc_topo_pair", bt.topo_p, bt.n_topo_p);
-		add("enc_topo_walk", bt.topo_w, bt.n_topo_w);
-		add("enc_est_normal", bt.est, bt.n_est);
-		add("enc_delta", bt.delta, bt.n_delta);
-		add("enc_zkeys", bt.zkeys, bt.n_zkeys);
-		add("enc_zsort", bt.zsort, bt.n_zsort);
+		for(int i = 0; i < K_COUNT; i++) if(bt.launches[i]) { times->name[c] = KERNEL_NAME[i]; times->ms[c] = bt.ms[i]; times->launches[c] = bt.launches[i]; c++; }
 		times->count = c;
 		enc_report_times(times, tm);
 	}

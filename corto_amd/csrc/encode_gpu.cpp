@@ -11,12 +11,11 @@
 // tun_encoder_tables = src/tunstall.cpp:83-115, 125-256, 335-382)  ->  greedy parse on the device (k_enc_tun_parse =
 // src/tunstall.cpp:384-428)  ->  block framing on the host.  Everything is byte-identical to the reference's output
 // (tests/test_gpu_parity.py::test_tunstall_encode_*, test_encode_values_*, test_gpu_encoder_*).  No CPU fallback.
+// The try macro, DevMem, the stage timer (EventTimer) and quant_job are encoder_internal.h's, shared with encode_batch.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
-#include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/corto_hip.h"
@@ -28,22 +27,10 @@ using namespace corto_hip;
 
 namespace {
 
-struct DevMem {                                   // freed on every way out
-	void *p = nullptr;
-	~DevMem() { if(p) (void)hipFree(p); }
-	uint8_t *u8() const { return (uint8_t *)p; }
-};
-struct Events {
-	hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-	~Events() { for(auto &x : e) if(x) (void)hipEventDestroy(x); }
-};
-using StageTimes = EncStageTimes;
-
-#define ENC_TRY(expr) do { hipError_t e_ = (expr); if(e_ != hipSuccess) return ctx_fail(CRTHIP_E_DEVICE, (std::string(#expr ": ") + hipGetErrorString(e_)).c_str()); } while(0)
 
 // Tunstall blocks of n DEVICE-resident byte streams.  blocks[i] = "u8 nsym | nsym x (symbol, probability) | i32 size | i32 csize | codewords"
 int tun_encode_device(hipStream_t st, uint32_t n, const uint8_t *const *d_src, const uint32_t *sizes,
-                      std::vector<std::vector<uint8_t>> &blocks, StageTimes &tm) {
+                      std::vector<std::vector<uint8_t>> &blocks, EncStageTimes &tm) {
 	blocks.assign(n, std::vector<uint8_t>());
 	for(uint32_t i = 0; i < n; i++)
 		if(sizes[i] > (1u << 23)) return ctx_fail(CRTHIP_E_LIMIT, "Tunstall encoder: stream longer than 2^23 symbols (the reference's count*255 overflows int)");
@@ -57,18 +44,18 @@ int tun_encode_device(hipStream_t st, uint32_t n, const uint8_t *const *d_src, c
 	for(uint32_t i = 0; i < n; i++)
 		for(uint32_t b = 0; b < sizes[i]; b += ENC_HIST_CHUNK) chunks.push_back(EncChunk{d_src[i] + b, std::min(ENC_HIST_CHUNK, sizes[i] - b), i});
 	o += (chunks.size()*sizeof(EncChunk) + 15) & ~15ull;
-	DevMem work; Events ev;
+	DevMem work;
+	EventTimer t_hist, t_tables, t_trie, t_parse;
 	ENC_TRY(hipMalloc(&work.p, o + 16));
 	uint8_t *base = work.u8();
-	for(auto &e : ev.e) ENC_TRY(hipEventCreate(&e));
 	if(n) ENC_TRY(hipMemsetAsync(base, 0, (size_t)n*256*4, st));
 	if(n) ENC_TRY(hipMemsetAsync(base + o_csize, 0, (size_t)(o_chunks - o_csize), st));
 	std::vector<uint32_t> counts((size_t)n*256);
 	if(!chunks.empty()) {
 		ENC_TRY(hipMemcpyAsync(base + o_chunks, chunks.data(), chunks.size()*sizeof(EncChunk), hipMemcpyHostToDevice, st));
-		ENC_TRY(hipEventRecord(ev.e[0], st));
+		if(t_hist.begin(st)) return CRTHIP_E_DEVICE;
 		hipLaunchKernelGGL(k_enc_hist, dim3((uint32_t)chunks.size()), dim3(256), 0, st, (const EncChunk *)(base + o_chunks), (uint32_t)chunks.size(), (uint32_t *)base);
-		ENC_TRY(hipEventRecord(ev.e[1], st));
+		if(t_hist.end(st)) return CRTHIP_E_DEVICE;
 	}
 
 	// device: probabilities (in std::sort's order), dictionary and - where it fits the LDS of one workgroup - the encoding trie of every
@@ -87,13 +74,13 @@ int tun_encode_device(hipStream_t st, uint32_t n, const uint8_t *const *d_src, c
 		ENC_TRY(hipMalloc(&dsizes.p, (size_t)n*4 + 16));
 		ENC_TRY(hipMalloc(&dtabs.p, (size_t)n*sizeof(EncTab) + 16));
 		ENC_TRY(hipMemcpyAsync(dsizes.p, sizes, (size_t)n*4, hipMemcpyHostToDevice, st));
-		ENC_TRY(hipEventRecord(ev.e[2], st));
+		if(t_tables.begin(st)) return CRTHIP_E_DEVICE;
 		hipLaunchKernelGGL(k_enc_tables, dim3(n), dim3(64), 0, st, (const uint32_t *)base, (const uint32_t *)dsizes.p, n, (EncTab *)dtabs.p);
-		ENC_TRY(hipEventRecord(ev.e[3], st));
+		if(t_tables.end(st)) return CRTHIP_E_DEVICE;
 		ENC_TRY(hipMemcpy2DAsync(heads.data(), HEAD, dtabs.p, sizeof(EncTab), HEAD, n, hipMemcpyDeviceToHost, st));
 		ENC_TRY(hipStreamSynchronize(st));
 		ENC_TRY(hipGetLastError());
-		if(hipEventElapsedTime(&ms_tables, ev.e[2], ev.e[3]) != hipSuccess) ms_tables = 0;
+		t_tables.add_to(ms_tables);
 	}
 	std::vector<uint64_t> trie_off(n, 0);
 	uint64_t trie_bytes = 0;
@@ -159,36 +146,31 @@ int tun_encode_device(hipStream_t st, uint32_t n, const uint8_t *const *d_src, c
 		ENC_TRY(hipMemcpyAsync(dstreams.p, h_tab.data(), tab_total, hipMemcpyHostToDevice, st));
 		if(!dev_ids.empty()) {
 			const uint32_t nd = (uint32_t)dev_ids.size();
-			ENC_TRY(hipEventRecord(ev.e[4], st));
+			if(t_trie.begin(st)) return CRTHIP_E_DEVICE;
 			hipLaunchKernelGGL(k_enc_trie, dim3(nd), dim3(64), ENC_TRIE_LDS_MAX*2, st, (const EncTab *)dtabs.p, (const uint32_t *)(tb + o_ids), (EncStream *)(tb + o_streams), nd, ENC_TRIE_LDS_MAX);
-			ENC_TRY(hipEventRecord(ev.e[5], st));
+			if(t_trie.end(st)) return CRTHIP_E_DEVICE;
 			ENC_TRY(hipMemcpyAsync(es.data(), tb + o_streams, (size_t)nd*sizeof(EncStream), hipMemcpyDeviceToHost, st));
 			ENC_TRY(hipStreamSynchronize(st));
 			ENC_TRY(hipGetLastError());
-			if(hipEventElapsedTime(&ms_trie, ev.e[4], ev.e[5]) != hipSuccess) ms_trie = 0;
+			t_trie.add_to(ms_trie);
 			for(uint32_t k = 0; k < nd; k++) {
 				if(es[k].ntrie == 0xFFFFFFFFu || es[k].ntrie == 0) return ctx_fail(CRTHIP_E_DEVICE, "k_enc_trie: a trie outgrew the bound the dictionary gives");
 				trie_lds = std::max(trie_lds, es[k].ntrie);
 			}
 		}
 		const uint32_t lds = enc_parse_lds(trie_lds);
-		hipEvent_t p0 = nullptr, p1 = nullptr;
-		ENC_TRY(hipEventCreate(&p0)); ENC_TRY(hipEventCreate(&p1));
-		ENC_TRY(hipEventRecord(p0, st));
+		if(t_parse.begin(st)) return CRTHIP_E_DEVICE;
 		hipLaunchKernelGGL(k_enc_tun_parse, dim3(ngpu), dim3(64), lds, st, (const EncStream *)(tb + o_streams), ngpu, trie_lds);
-		ENC_TRY(hipEventRecord(p1, st));
+		if(t_parse.end(st)) return CRTHIP_E_DEVICE;
 		ENC_TRY(hipMemcpyAsync(csize.data(), base + o_csize, (size_t)n*4, hipMemcpyDeviceToHost, st));
 		h_codes.resize(o_csize - dst_off[0]);
 		ENC_TRY(hipMemcpyAsync(h_codes.data(), base + dst_off[0], h_codes.size(), hipMemcpyDeviceToHost, st));
 		ENC_TRY(hipStreamSynchronize(st));
 		ENC_TRY(hipGetLastError());
-		float pm = 0;
-		if(hipEventElapsedTime(&pm, p0, p1) == hipSuccess) { tm.parse += pm; tm.any_parse = true; }
-		(void)hipEventDestroy(p0); (void)hipEventDestroy(p1);
+		if(t_parse.add_to(tm.parse)) tm.any_parse = true;
 	}
 	if(n) { tm.tables += ms_tables; tm.trie += ms_trie; tm.any_tables = true; tm.host_table_streams += (uint32_t)host_ids.size(); }
-	float ms = 0;
-	if(!chunks.empty() && hipEventElapsedTime(&ms, ev.e[0], ev.e[1]) == hipSuccess) { tm.hist += ms; tm.any_hist = true; }
+	if(t_hist.add_to(tm.hist)) tm.any_hist = true;
 
 	// block framing (src/cstream.cpp:96-107)
 	for(uint32_t i = 0; i < n; i++) {
@@ -239,7 +221,7 @@ extern "C" int64_t crthip_tunstall_encode_blocks(crthip_ctx *ctx, uint32_t n, co
 	std::vector<const uint8_t *> d_src(n);
 	for(uint32_t i = 0; i < n; i++) d_src[i] = dsrc.u8() + src_off[i];
 	std::vector<std::vector<uint8_t>> blocks;
-	StageTimes tm;
+	EncStageTimes tm;
 	{ const int e = tun_encode_device(st, n, d_src.data(), sizes, blocks, tm); if(e) return e; }
 	enc_report_times(times, tm);
 	uint64_t w = 0;
@@ -259,31 +241,27 @@ int corto_hip::quantize_device(crthip_ctx *ctx, const std::vector<QuantRequest> 
 	ENC_TRY(hipSetDevice(ctx_device(ctx)));
 	{ const int e = ctx_quiesce(ctx); if(e) return e; }
 	hipStream_t st = ctx_stream(ctx);
-	auto in_bytes = [](const QuantRequest &r) -> uint64_t { return quant_in_bytes(r); };      // every input 16-byte aligned (doubles: 8)
-	auto out_bytes = [](const QuantRequest &r) -> uint64_t { return quant_out_bytes(r); };
+	// every input 16-byte aligned (doubles: 8)
 	std::vector<uint64_t> ioff(reqs.size()), ooff(reqs.size());
 	uint64_t o = 0;
-	for(size_t k = 0; k < reqs.size(); k++) { ioff[k] = o; o += (in_bytes(reqs[k]) + 15) & ~15ull; }
+	for(size_t k = 0; k < reqs.size(); k++) { ioff[k] = o; o += (quant_in_bytes(reqs[k]) + 15) & ~15ull; }
 	const uint64_t in_total = o;
-	for(size_t k = 0; k < reqs.size(); k++) { ooff[k] = o; o += (out_bytes(reqs[k]) + 15) & ~15ull; }
+	for(size_t k = 0; k < reqs.size(); k++) { ooff[k] = o; o += (quant_out_bytes(reqs[k]) + 15) & ~15ull; }
 	if(o == 0) return CRTHIP_OK;
 	DevMem dev;
 	ENC_TRY(hipMalloc(&dev.p, o + 16));
 	std::vector<uint8_t> h(o);
-	for(size_t k = 0; k < reqs.size(); k++) if(in_bytes(reqs[k])) memcpy(h.data() + ioff[k], reqs[k].in, in_bytes(reqs[k]));
+	for(size_t k = 0; k < reqs.size(); k++) if(quant_in_bytes(reqs[k])) memcpy(h.data() + ioff[k], reqs[k].in, quant_in_bytes(reqs[k]));
 	ENC_TRY(hipMemcpyAsync(dev.p, h.data(), in_total, hipMemcpyHostToDevice, st));
 	for(size_t k = 0; k < reqs.size(); k++) {
 		const QuantRequest &r = reqs[k];
 		if(!r.count) continue;
-		QuantJob J{};
-		J.in = dev.u8() + ioff[k]; J.out = dev.u8() + ooff[k]; J.count = r.count; J.kind = r.kind; J.N = r.N; J.q = r.q; J.unit = r.unit; J.format = r.format;
-		for(int c = 0; c < 4; c++) J.qc[c] = r.qc[c] ? r.qc[c] : 1u;
-		hipLaunchKernelGGL(k_enc_quantize, dim3((r.count + 255)/256), dim3(256), 0, st, J);
+		hipLaunchKernelGGL(k_enc_quantize, dim3((r.count + 255)/256), dim3(256), 0, st, quant_job(r, dev.u8() + ioff[k], dev.u8() + ooff[k]));
 	}
 	ENC_TRY(hipMemcpyAsync(h.data() + in_total, dev.u8() + in_total, o - in_total, hipMemcpyDeviceToHost, st));
 	ENC_TRY(hipStreamSynchronize(st));
 	ENC_TRY(hipGetLastError());
-	for(size_t k = 0; k < reqs.size(); k++) if(out_bytes(reqs[k])) memcpy(reqs[k].out, h.data() + ooff[k], out_bytes(reqs[k]));
+	for(size_t k = 0; k < reqs.size(); k++) if(quant_out_bytes(reqs[k])) memcpy(reqs[k].out, h.data() + ooff[k], quant_out_bytes(reqs[k]));
 	return CRTHIP_OK;
 }
 
@@ -304,8 +282,8 @@ int corto_hip::encode_value_streams_device(crthip_ctx *ctx, const std::vector<De
 	const uint64_t o_jobs = o;
 	std::vector<PackJob> jobs;
 	std::vector<uint32_t> job_stream;
-	DevMem dev; Events ev;
-	for(auto &e : ev.e) ENC_TRY(hipEventCreate(&e));
+	DevMem dev;
+	EventTimer t_pack;
 	for(uint32_t i = 0; i < n; i++) if(nlogs[i] && in[i].count) { jobs.push_back(PackJob{}); job_stream.push_back(i); }
 	o += (jobs.size()*sizeof(PackJob) + 15) & ~15ull;
 	const uint64_t o_gather = o;                         // copy jobs of the compaction (at most one per stream + one per log array)
@@ -325,15 +303,14 @@ int corto_hip::encode_value_streams_device(crthip_ctx *ctx, const std::vector<De
 		}
 		ENC_TRY(hipMemcpyAsync(base + o_jobs, jobs.data(), jobs.size()*sizeof(PackJob), hipMemcpyHostToDevice, st));
 		tm.bytes_to_device += jobs.size()*sizeof(PackJob);
-		ENC_TRY(hipEventRecord(ev.e[4], st));
+		if(t_pack.begin(st)) return CRTHIP_E_DEVICE;
 		hipLaunchKernelGGL(k_enc_pack, dim3((uint32_t)jobs.size()), dim3(256), 0, st, (const PackJob *)(base + o_jobs), (uint32_t)jobs.size());
-		ENC_TRY(hipEventRecord(ev.e[5], st));
+		if(t_pack.end(st)) return CRTHIP_E_DEVICE;
 		ENC_TRY(hipMemcpyAsync(nwords.data(), base + o_nwords, (size_t)n*4, hipMemcpyDeviceToHost, st));
 		ENC_TRY(hipStreamSynchronize(st));
 		ENC_TRY(hipGetLastError());
 		tm.bytes_from_device += (uint64_t)n*4;
-		float ms = 0;
-		if(hipEventElapsedTime(&ms, ev.e[4], ev.e[5]) == hipSuccess) { tm.pack += ms; tm.any_pack = true; }
+		if(t_pack.add_to(tm.pack)) tm.any_pack = true;
 	}
 	// what comes back without the entropy coder - the bit words of every stream, the raw logs / symbols of entropy NONE - is
 	// compacted on the device behind the pack and copied back at once
@@ -425,7 +402,7 @@ int corto_hip::encode_value_streams(crthip_ctx *ctx, uint32_t entropy, const std
 	}
 	std::vector<DevValueStream> d(n);
 	for(uint32_t i = 0; i < n; i++) { d[i].kind = in[i].kind; d[i].count = in[i].count; d[i].components = in[i].components; d[i].entropy = entropy; d[i].values = dev.u8() + v_off[i]; }
-	StageTimes tm;
+	EncStageTimes tm;
 	{ const int e = encode_value_streams_device(ctx, d, res, tm); if(e) return e; }
 	enc_report_times(times, tm);
 	return CRTHIP_OK;

@@ -55,15 +55,12 @@ int32_t d2i(double x) {                                                         
 }
 
 // ---- streams left to the device (crthip_encode_gpu): recorded instead of written, spliced in at `at` afterwards ----
-struct Deferred {
-	size_t at = 0;                      // position in the sink's bytes where the stream belongs
-	uint32_t kind = 0;                  // CRTHIP_ENC_*, or DEFER_BITS for a bit stream that is already packed (CLERS split bits)
-	uint32_t count = 0, N = 1;
+struct Deferred : corto_hip::BatchStream {   // at: position in the sink's bytes where the stream belongs; kind: CRTHIP_ENC_*, or BATCH_BITS
+                                             // for a bit stream that is already packed (CLERS split bits); count, N
 	std::vector<uint8_t> bytes;         // symbols / int8 values
 	std::vector<int32_t> ints;          // int32 values
-	std::vector<uint32_t> words;        // DEFER_BITS
+	std::vector<uint32_t> words;        // BATCH_BITS
 };
-constexpr uint32_t DEFER_BITS = 0xFFu;
 
 // ---- byte sink (OutStream, include/corto/cstream.h:42-105) ----
 struct Sink {
@@ -96,7 +93,7 @@ struct BitWriter {
 	void flush() { if(bits != 32) { words.push_back(buff << bits); buff = 0; bits = 32; } }
 	void emit(Sink &s) {                // OutStream::write(BitStream&), cstream.h:79-89
 		flush();
-		if(s.defer) { Deferred d; d.at = s.b.size(); d.kind = DEFER_BITS; d.words = words; s.defer->push_back(std::move(d)); return; }
+		if(s.defer) { Deferred d; d.at = s.b.size(); d.kind = corto_hip::BATCH_BITS; d.words = words; s.defer->push_back(std::move(d)); return; }
 		s.u32((uint32_t)words.size());
 		while(s.b.size() & 3) s.u8(0);
 		for(uint32_t w : words) s.u32(w);
@@ -863,7 +860,7 @@ static int64_t encode_impl(const crthip_mesh *m, const crthip_attr_list *extra, 
 		// in front of every bit stream (OutStream::write(BitStream&), cstream.h:79-89) depends on the final position, so it is made here
 		std::vector<corto_hip::EncValueStream> in;
 		for(const Deferred &d : deferred) {
-			if(d.kind == DEFER_BITS) continue;
+			if(d.kind == corto_hip::BATCH_BITS) continue;
 			corto_hip::EncValueStream v;
 			v.kind = d.kind; v.count = d.count; v.components = d.N;
 			v.values = d.kind == CRTHIP_ENC_SYMBOLS || d.kind == CRTHIP_ENC_VALUES_I8 ? (const void *)d.bytes.data() : (const void *)d.ints.data();
@@ -872,18 +869,11 @@ static int64_t encode_impl(const crthip_mesh *m, const crthip_attr_list *extra, 
 		std::vector<corto_hip::EncValueResult> res;
 		const int err = corto_hip::encode_value_streams(gpu, E.entropy, in, res, nullptr);
 		if(err) return err;
-		Sink f;
-		size_t prev = 0, k = 0;
-		auto bits = [&](const std::vector<uint32_t> &w) { f.u32((uint32_t)w.size()); while(f.b.size() & 3) f.u8(0); for(uint32_t x : w) f.u32(x); };
-		for(const Deferred &d : deferred) {
-			f.raw(E.s.b.data() + prev, d.at - prev); prev = d.at;
-			if(d.kind == DEFER_BITS) { bits(d.words); continue; }
-			const corto_hip::EncValueResult &r = res[k++];
-			if(d.kind != CRTHIP_ENC_SYMBOLS) bits(r.words);
-			for(const std::vector<uint8_t> &b : r.blocks) f.raw(b.data(), b.size());
-		}
-		f.raw(E.s.b.data() + prev, E.s.b.size() - prev);
-		E.s.b.swap(f.b);
+		const std::vector<uint32_t> none, *split_words = &none;       // (a mesh records one packed bit stream, its CLERS split bits; a cloud none)
+		for(const Deferred &d : deferred) if(d.kind == corto_hip::BATCH_BITS) split_words = &d.words;
+		std::vector<uint8_t> f;
+		corto_hip::splice_container(E.s.b, deferred, res.data(), *split_words, f);
+		E.s.b.swap(f);
 	}
 	if(out && cap >= E.s.b.size()) memcpy(out, E.s.b.data(), E.s.b.size());
 	return (int64_t)E.s.b.size();
@@ -968,7 +958,7 @@ void corto_hip::batch_setup(const crthip_mesh *m, const crthip_attr_list *extra,
 		const Attr &a = kv.second;
 		BatchAttr b;
 		b.codec = (uint32_t)a.codec; b.N = (uint32_t)a.N; b.prediction = (uint32_t)a.prediction; b.strategy = (uint32_t)a.strategy;
-		b.position = kv.first == "position";
+		if(kv.first == "position") it.pos = (uint32_t)it.attrs.size();
 		for(const NamedQuant &q : named) if(q.name == kv.first) b.quant = q.r;
 		it.attrs.push_back(b);
 	}
@@ -981,10 +971,9 @@ static void batch_streams(const Encoder &E, const std::vector<Deferred> &deferre
 	const size_t first_attr = mesh ? 2 : 0;
 	for(size_t k = 0; k < deferred.size(); k++) {
 		const Deferred &d = deferred[k];
-		BatchStream b;
-		b.at = d.at; b.kind = d.kind; b.count = d.count; b.N = d.N;
+		BatchStream b = d;
 		b.attr = k < first_attr ? (k == 0 ? -1 : -2) : (int32_t)(k - first_attr);
-		if(d.kind == DEFER_BITS) { b.kind = BATCH_BITS; it.split_words = d.words; }
+		if(d.kind == BATCH_BITS) it.split_words = d.words;
 		else if(b.attr >= 0 && it.attrs[b.attr].codec == CRTHIP_CODEC_NORMAL)         // the residuals' count: every vertex, or (BORDER) the device's
 			b.count = it.attrs[b.attr].prediction == 2 ? 0u : E.nvert;
 		it.streams.push_back(b);
@@ -994,8 +983,7 @@ static void batch_streams(const Encoder &E, const std::vector<Deferred> &deferre
 void corto_hip::batch_topology(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it) {
 	Encoder E;
 	std::vector<NamedQuant> named;
-	float step = 0;
-	for(const BatchAttr &b : it.attrs) if(b.position) step = b.quant.q;
+	float step = it.attrs[it.pos].quant.q;
 	setup(m, extra, E, named, false, &step);
 	std::vector<Deferred> deferred;
 	E.s.defer = &deferred; E.s.shape_only = true;
@@ -1020,8 +1008,7 @@ void corto_hip::batch_frame(const crthip_mesh *m, const crthip_attr_list *extra,
                             const uint32_t *split_words) {
 	Encoder E;
 	std::vector<NamedQuant> named;
-	float step = 0;
-	for(const BatchAttr &b : it.attrs) if(b.position) step = b.quant.q;
+	float step = it.attrs[it.pos].quant.q;
 	setup(m, extra, E, named, false, &step);
 	std::vector<Deferred> deferred;
 	E.s.defer = &deferred; E.s.shape_only = true;

@@ -1,14 +1,39 @@
 // encoder_internal.h — pieces of the host encoder (encoder.cpp) and of the context (batch.cpp) that the GPU encoder
-// stages (encode_gpu.cpp, k_encode.hip) use.  Not part of the C ABI.
+// stages (encode_gpu.cpp, k_encode.hip) and the batch encoder (encode_batch.cpp) use, and the device helpers those two share: the
+// try macro, DevMem, EventTimer, quant_job, splice_container, Carver.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "../../include/corto_hip.h"
+#include "device_plan.h"
 
 namespace corto_hip {
+
+int ctx_fail(int code, const char *msg);
+
+// ---- device helpers of the encoder's host side (encode_gpu.cpp, encode_batch.cpp) ----
+#define ENC_TRY(expr) do { hipError_t e_ = (expr); if(e_ != hipSuccess) return corto_hip::ctx_fail(CRTHIP_E_DEVICE, (std::string(#expr ": ") + hipGetErrorString(e_)).c_str()); } while(0)
+
+struct DevMem { void *p = nullptr; ~DevMem() { if(p) (void)hipFree(p); } uint8_t *u8() const { return (uint8_t *)p; } };   // freed on every way out
+
+// a pair of events around a stage's launches, made on first use and destroyed on every way out
+struct EventTimer {
+	hipEvent_t a = nullptr, b = nullptr; bool used = false;
+	~EventTimer() { if(a) (void)hipEventDestroy(a); if(b) (void)hipEventDestroy(b); }
+	int begin(hipStream_t st) { if(!a) { ENC_TRY(hipEventCreate(&a)); ENC_TRY(hipEventCreate(&b)); } used = true; ENC_TRY(hipEventRecord(a, st)); return 0; }
+	int end(hipStream_t st) { ENC_TRY(hipEventRecord(b, st)); return 0; }
+	// after the stream has passed end(): adds the stage's milliseconds to `sum`; false if the timer never ran or the events give no time
+	bool add_to(float &sum) { float m = 0; if(!used || hipEventElapsedTime(&m, a, b) != hipSuccess) return false; sum += m; return true; }
+};
+
+struct Carver {                         // bump allocator over one device block (offsets only): the decode planner's scratch, the batch encoder's image
+	uint64_t off = 0;
+	uint64_t take(uint64_t bytes, uint64_t align = 256) { off = (off + align - 1) & ~(align - 1); const uint64_t r = off; off += bytes; return r; }
+};
 
 // What Tunstall::compress walks (src/tunstall.cpp:384-428), made from a byte histogram exactly as
 // getProbabilities + createDecodingTables2 + createEncodingTables make it (src/tunstall.cpp:83-115, 125-256, 335-382).
@@ -36,6 +61,12 @@ struct QuantRequest { uint32_t kind = 0, count = 0, N = 1, format = CRTHIP_FMT_F
 uint64_t quant_in_bytes(const QuantRequest &r);      // the raw input's bytes (format-aware)
 uint64_t quant_out_bytes(const QuantRequest &r);     // the quantised values' bytes
 int quantize_device(crthip_ctx *ctx, const std::vector<QuantRequest> &reqs);
+inline QuantJob quant_job(const QuantRequest &r, const void *in, void *out) {   // the kernels' job (k_enc_quantize, k_enc_quantize_batch) of a request
+	QuantJob J{};
+	J.in = in; J.out = out; J.count = r.count; J.kind = r.kind; J.N = r.N; J.q = r.q; J.unit = r.unit; J.format = r.format;
+	for(int c = 0; c < 4; c++) J.qc[c] = r.qc[c] ? r.qc[c] : 1u;
+	return J;
+}
 
 // the value coders + entropy coder over DEVICE-resident arrays (encode_gpu.cpp); each stream carries its mesh's entropy
 struct DevValueStream { uint32_t kind = 0, count = 0, components = 1, entropy = 0; const void *values = nullptr; };
@@ -49,13 +80,14 @@ int encode_check(const crthip_mesh *m);              // encode_checked's argumen
 // the rules of crthip_encode_attrs's extra list (sets the last error); device: also the value coder's bound on nvert*components
 int encode_check_attrs(const crthip_mesh *m, const crthip_attr_list *extra, bool device);
 constexpr uint32_t BATCH_BITS = 0xFFu;                // a stream that is the CLERS split bits, already packed
-struct BatchAttr { uint32_t codec = 0, N = 0, prediction = 0, strategy = 0; bool position = false; QuantRequest quant; };
+struct BatchAttr { uint32_t codec = 0, N = 0, prediction = 0, strategy = 0; QuantRequest quant; };
 struct BatchStream { size_t at = 0; uint32_t kind = 0, count = 0, N = 1; int32_t attr = 0; };   // attr: index in attrs, -1 CLERS symbols, -2 split bits
 struct BatchItem {
 	int32_t status = CRTHIP_OK;
 	uint32_t entropy = 0, nvert_in = 0, nface_in = 0;    // as given (nface_in 0: a point cloud)
 	uint32_t nvert = 0, nface = 0;                        // what the container says (after the topology pass)
 	std::vector<BatchAttr> attrs;                         // the container's order; quant.out unset
+	uint32_t pos = 0;                                     // which of them is the position
 	std::vector<uint32_t> faces;                          // meshes: degenerate faces dropped, original vertex ids
 	std::vector<uint32_t> quads;                          // meshes: the prediction, (t, a, b, c) per encoded vertex
 	std::vector<uint8_t> clers;
@@ -75,6 +107,29 @@ void batch_topology(const crthip_mesh *m, const crthip_attr_list *extra, BatchIt
 struct EncTopoRecord;
 void batch_frame(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it, const EncTopoRecord &rec, const uint32_t *group_end,
                  const uint32_t *split_words);
+// A container from its frame (the container without its streams), the slots its body recorded (Deferred, BatchStream: `at` in the frame,
+// `kind`) in order, and the device's result for every slot but the split bits (kind BATCH_BITS: split_words, packed already).  A bit
+// stream is its word count, zero padding to 4 bytes of the container written so far, its words (OutStream::write(BitStream&),
+// cstream.h:79-89); a value stream's bit words come before its blocks.  Returns how many results it used.
+template <class SlotT>
+size_t splice_container(const std::vector<uint8_t> &frame, const std::vector<SlotT> &slots, const EncValueResult *results,
+                        const std::vector<uint32_t> &split_words, std::vector<uint8_t> &out) {
+	out.clear();
+	out.reserve(frame.size() + 64);
+	auto u32 = [&](uint32_t v) { const uint8_t b[4] = {(uint8_t)v, (uint8_t)(v >> 8), (uint8_t)(v >> 16), (uint8_t)(v >> 24)}; out.insert(out.end(), b, b + 4); };
+	auto bits = [&](const std::vector<uint32_t> &w) { u32((uint32_t)w.size()); while(out.size() & 3) out.push_back(0); for(uint32_t x : w) u32(x); };
+	size_t prev = 0, r = 0;
+	for(const SlotT &s : slots) {
+		out.insert(out.end(), frame.begin() + prev, frame.begin() + s.at); prev = s.at;
+		if(s.kind == BATCH_BITS) { bits(split_words); continue; }
+		const EncValueResult &x = results[r++];
+		if(s.kind != CRTHIP_ENC_SYMBOLS) bits(x.words);
+		for(const std::vector<uint8_t> &blk : x.blocks) out.insert(out.end(), blk.begin(), blk.end());
+	}
+	out.insert(out.end(), frame.begin() + prev, frame.end());
+	return r;
+}
+
 // the host encoder's topology pass alone (crthip_encode_topology_model, which = 0); split_bits before the final flush
 struct TopologyModel { std::vector<uint32_t> faces, group_end, quads, split_words; std::vector<uint8_t> clers; uint32_t nvert = 0, nface = 0, max_front = 0; uint64_t split_bits = 0; };
 void topology_host_model(const crthip_mesh *m, TopologyModel &out);
@@ -95,8 +150,7 @@ struct HostDecodeReq {
 };
 int decode_host_many(crthip_ctx *ctx, uint32_t n, HostDecodeReq *reqs, bool copy_out);
 
-// context plumbing (batch.cpp)
-int ctx_fail(int code, const char *msg);
+// context plumbing (batch.cpp); ctx_fail is declared at the top
 int ctx_device(crthip_ctx *ctx);
 int ctx_encode_topology(crthip_ctx *ctx);   // CRTHIP_TOPOLOGY_* of crthip_ctx_set_encode_topology
 hipStream_t ctx_stream(crthip_ctx *ctx);
