@@ -167,6 +167,8 @@ def lib():
         L.crthip_batch_bind.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
         L.crthip_batch_bind_all.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.crthip_batch_decode.argtypes = [C.c_void_p]
+        L.crthip_batch_decode_with_next.argtypes = [C.c_void_p, C.c_void_p]
+        L.crthip_batch_set_parity.argtypes = [C.c_void_p, C.c_uint32]
         L.crthip_batch_sync.argtypes = [C.c_void_p, C.c_void_p]
         L.crthip_batch_get_stats.argtypes = [C.c_void_p, C.POINTER(BatchStats)]
         L.crthip_batch_kernel_times.argtypes = [C.c_void_p, C.POINTER(KernelTimes)]
@@ -774,6 +776,18 @@ class Batch:
     # -- run ---------------------------------------------------------------------------------------
     def decode(self):
         _check(lib().crthip_batch_decode(self.handle))
+
+    def set_parity(self, parity: int):
+        """crthip_batch_set_parity: which of the context's two sets of per-call blocks this object uses (before it is filled)"""
+        _check(lib().crthip_batch_set_parity(self.handle, parity))
+
+    def decode_with_next(self, nxt: Optional["Batch"] = None):
+        """crthip_batch_decode_with_next(self, nxt): this batch's mesh stage with `nxt`'s entropy stage; this batch was `nxt` one call ago"""
+        _check(lib().crthip_batch_decode_with_next(self.handle, nxt.handle if nxt is not None else None))
+
+    def decode_entropy(self):
+        """crthip_batch_decode_with_next(NULL, self): this batch's entropy stage alone (the first batch of a pipelined lane)"""
+        _check(lib().crthip_batch_decode_with_next(None, self.handle))
 
     def sync(self, raise_on_error=True) -> np.ndarray:
         st = np.zeros(max(len(self), 1), dtype=np.int32)

@@ -104,9 +104,19 @@ extern "C" uint64_t crthip_arena_layout(uint32_t nblobs, const uint32_t *lens, u
 // decode(A); decode(B); sync(A) sequence still reports A's failures (status used to be read only by crthip_batch_sync(A) and
 // was lost when another call had synchronised first).
 constexpr uint32_t TOPO_SLOTS_MAX = 4096;       // ring and pool slots of the automaton's LDS form (topo_lds_geometry's ring_max)
+static int harvest_selected(crthip_ctx *ctx);
 int harvest(crthip_ctx *ctx) {
 	crthip_batch *b = ctx->in_flight;
 	if(!b) return CRTHIP_OK;
+	// the status block and the upload bookkeeping of the batch in flight are its parity's; the caller goes on with the set it had selected
+	const uint8_t keep = ctx->active;
+	ctx_select(ctx, b->parity);
+	const int rc = harvest_selected(ctx);
+	ctx_select(ctx, keep);
+	return rc;
+}
+static int harvest_selected(crthip_ctx *ctx) {
+	crthip_batch *b = ctx->in_flight;
 	if(hipEventSynchronize(ctx->ev_done) != hipSuccess) { ctx->in_flight = nullptr; return CRTHIP_E_DEVICE; }
 	// (only an upload that sits in front of the event: one enqueued behind the decode is still on its way)
 	if(ctx->done_covers_seq == ctx->upload_seq) ctx->arena_upload_pending = false;
@@ -182,6 +192,9 @@ namespace corto_hip {
 int ctx_device(crthip_ctx *ctx) { return ctx->device; }
 int ctx_encode_topology(crthip_ctx *ctx) { return ctx->encode_topology; }
 hipStream_t ctx_stream(crthip_ctx *ctx) { return ctx->stream; }
+bool ctx_pipelines(crthip_ctx *ctx) { return ctx->single_stream && !ctx->dbg.carry_off; }
+bool batch_carriable(const crthip_batch *b) { return b && b->carriable; }
+bool batch_entropy_done(const crthip_batch *b) { return b && b->staged && b->staged->e_done; }
 // on the context's main stream, ordered before its next decode
 int ctx_fill_async(crthip_ctx *ctx, void *dst, size_t bytes, int value) {
 	if(!bytes) return CRTHIP_OK;
@@ -243,6 +256,7 @@ extern "C" int crthip_ctx_create(int device, crthip_ctx **out) {
 	if(hipFuncSetAttribute((const void *)k_topology_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TOPO_LDS_MAX) != hipSuccess ||
 	   hipFuncSetAttribute((const void *)k_topology_lds_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TOPO_LDS_MAX) != hipSuccess ||
 	   hipFuncSetAttribute((const void *)k_delta_lds16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DELTA16_LDS_MAX) != hipSuccess ||
+	   hipFuncSetAttribute((const void *)k_delta_lds16_carry, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DELTA16_LDS_MAX) != hipSuccess ||
 	   hipFuncSetAttribute((const void *)k_normal_blob, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NORMAL_LDS_MAX) != hipSuccess ||
 	   hipFuncSetAttribute((const void *)k_enc_topo_walk<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ENC_TOPO_LDS_MAX) != hipSuccess ||
 	   hipFuncSetAttribute((const void *)k_enc_tun_parse, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -260,6 +274,7 @@ extern "C" void crthip_ctx_destroy(crthip_ctx *c) {
 	c->timer.release();
 	if(c->host_batch) { crthip_batch *hb = c->host_batch; c->host_batch = nullptr; crthip_batch_destroy(hb); }
 	c->scratch.release(); c->staging.release(); c->arena_pin.release(); c->status_host.release(); c->host_out.release();
+	c->spare.scratch.release(); c->spare.staging.release(); c->spare.arena_pin.release(); c->spare.status_host.release();
 		c->host_pin.release();
 	c->walk_dev.release(); c->walk_pin.release();
 	if(c->ev_walk0) (void)hipEventDestroy(c->ev_walk0);
@@ -315,6 +330,8 @@ static int batch_fill(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs, const u
 	const void *device_arena) {
 	const double t_create = now_us();
 	b->ctx = ctx;
+	drop_staged(b);
+	ctx_select(ctx, b->parity);
 	b->blobs.resize(nblobs);
 	b->stats = crthip_batch_stats{};
 	b->walk = crthip_walk_stats{};
@@ -408,6 +425,8 @@ static int batch_fill_resident(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs
 	const uint32_t *lens) {
 	const double t_create = now_us();
 	b->ctx = ctx;
+	drop_staged(b);
+	ctx_select(ctx, b->parity);
 	b->blobs.clear(); b->status.clear(); b->d_arena = nullptr; b->arena_bytes = 0;
 	b->stats = crthip_batch_stats{};
 	b->walk = crthip_walk_stats{};
@@ -504,7 +523,9 @@ extern "C" void crthip_batch_destroy(crthip_batch *b) {
 		if(b->ctx->in_flight == b) { (void)hipStreamSynchronize(b->ctx->stream); b->ctx->in_flight = nullptr; }
 		if(b->ctx->last_decoded == b) b->ctx->last_decoded = nullptr;
 		if(b->ctx->host_batch == b) b->ctx->host_batch = nullptr;
+		if(b->staged) (void)hipStreamSynchronize(b->ctx->stream);           // (its entropy stage may be on the stream, reading the arena)
 	}
+	drop_staged(b);
 	b->own_arena.release();
 	delete b;
 }
@@ -610,6 +631,8 @@ extern "C" int crthip_batch_bind_all(crthip_batch *b, const crthip_attr_binding 
 }
 
 static int build_and_launch_inner(crthip_batch *b);
+static int decode_pair(crthip_batch *cur, crthip_batch *next);
+void drop_staged(crthip_batch *b) { delete b->staged; b->staged = nullptr; }
 // A decode call that fails half-way (a HIP error between two launches) may have kernels queued that write per-blob status into the
 // context's pinned block and into its scratch; in_flight is not set on that path, so nothing downstream would wait for them before the
 // next call clears or moves those blocks.  Drain the context's streams before the error is returned.
@@ -628,6 +651,8 @@ static int build_and_launch(crthip_batch *b) {
 static int build_and_launch_inner(crthip_batch *b) {
 	// host-side cost of a decode call (crthip_batch_stats::host_*_us)
 	const double t0 = now_us();
+	ctx_select(b->ctx, b->parity);
+	b->ctx->timer.reset();
 	b->ctx->plan.reset();
 	Planner P(b);
 	int err = P.carve();
@@ -638,6 +663,7 @@ static int build_and_launch_inner(crthip_batch *b) {
 	if((err = P.upload()) != CRTHIP_OK) return err;
 	const double t2 = now_us();
 	if((err = P.launch()) != CRTHIP_OK) return err;
+	if((err = P.mark_done()) != CRTHIP_OK) return err;
 	P.account();
 	const double t3 = now_us();
 	b->stats.host_plan_us = (float)(t1 - t0); b->stats.host_stage_us = (float)(t2 - t1); b->stats.host_launch_us = (float)(t3 - t2);
@@ -647,7 +673,102 @@ static int build_and_launch_inner(crthip_batch *b) {
 extern "C" int crthip_batch_decode(crthip_batch *b) {
 	if(!b || !b->ctx) return fail(CRTHIP_E_ARGUMENT);
 	HIP_TRY(hipSetDevice(b->ctx->device));
+	if(b->staged) return crthip_batch_decode_with_next(b, nullptr);        // planned by crthip_batch_decode_with_next: its mesh stage (and whatever else is due)
 	return build_and_launch(b);
+}
+
+// The two-stage schedule of a pipelined lane (plan_launch.cpp: PH_*).  `next` is planned and uploaded like any decode; `cur` was `next` one call ago.
+// Enqueued, in stream order: next's descriptor copy and zeroing | cur's stage M, with next's K-TAB inside k_front's grid and next's K-STREAM inside
+// k_delta_lds16's when both batches allow it (Planner::hosts_carry / carry_args) | else next's K-TAB and K-STREAM as launches of their own | next's
+// k_fill | the done-event.  A `next` whose schedule has no separate entropy stage (a context with two streams, long Tunstall streams) is only
+// planned and uploaded here: the call that has it as `cur` runs its whole schedule.  Same bytes whichever way.
+static int decode_pair(crthip_batch *cur, crthip_batch *next) {
+	crthip_ctx *ctx = (cur ? cur : next)->ctx;
+	const double t0 = now_us();
+	ctx->timer.reset();
+	int err;
+	Planner *N = nullptr;
+	Carry carry{}; bool carried = false, nsplit = false;                    // (a planner's answers hold while ITS batch's parity is selected)
+	double t1 = t0, t2 = t0;
+	if(next) {
+		drop_staged(next);
+		ctx_select(ctx, next->parity);
+		ctx->plan.reset();
+		next->staged = N = new Planner(next);
+		err = N->carve();
+		if(!err) err = N->jobs();
+		if(err) return err;
+		N->group();
+		t1 = now_us();
+		if((err = N->upload()) != CRTHIP_OK) return err;
+		t2 = now_us();
+		next->stats.host_plan_us = (float)(t1 - t0); next->stats.host_stage_us = (float)(t2 - t1);
+		nsplit = N->splits();
+		carried = cur && nsplit && N->carry_args(carry);
+	}
+	if(cur) {
+		ctx_select(ctx, cur->parity);
+		Planner *C = cur->staged;
+		carried = carried && C->hosts_carry();                                // (with or without its own entropy stage in front)
+	}
+	// the first batch of a lane runs its entropy stage alone; after that a stage that cannot be carried is not enqueued early at all - its launches
+	// behind cur's kernels cost the queue what they cost in front of its own mesh stage, and measured slower (profiles/pool_carry.md)
+	const bool early = nsplit && (carried || !cur);
+	if(early) {
+		ctx_select(ctx, next->parity);
+		if((err = N->launch(PH_UP)) != CRTHIP_OK) return err;
+	}
+	if(cur) {
+		ctx_select(ctx, cur->parity);
+		Planner *C = cur->staged;
+		if((err = C->launch(C->e_done ? (uint32_t)PH_MESH : (uint32_t)PH_ALL, carried ? &carry : nullptr)) != CRTHIP_OK) return err;
+	}
+	if(early) {
+		ctx_select(ctx, next->parity);
+		if((err = N->launch(carried ? (uint32_t)PH_FILL : (uint32_t)(PH_TUN | PH_FILL))) != CRTHIP_OK) return err;
+		N->e_done = true;
+	}
+	if(cur) {
+		ctx_select(ctx, cur->parity);
+		Planner *C = cur->staged;
+		if((err = C->mark_done()) != CRTHIP_OK) return err;
+		C->account();
+		cur->stats.host_launch_us = (float)(now_us() - t2);
+		drop_staged(cur);
+	} else HIP_TRY(hipEventRecord(ctx->ev_done, ctx->stream));
+	return CRTHIP_OK;
+}
+
+extern "C" int crthip_batch_decode_with_next(crthip_batch *cur, crthip_batch *next) {
+	if((!cur && !next) || cur == next) return fail(CRTHIP_E_ARGUMENT);
+	crthip_ctx *ctx = (cur ? cur : next)->ctx;
+	if(!ctx || (cur && next && (next->ctx != ctx || cur->parity == next->parity)))
+		return fail(CRTHIP_E_ARGUMENT, "crthip_batch_decode_with_next: two batches of one context and of different parity");
+	if(cur && !cur->staged) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_decode_with_next: `cur` has not been `next` of an earlier call");
+	HIP_TRY(hipSetDevice(ctx->device));
+	// one call in flight per context: the one before is harvested first (its status block is about to be cleared when it shares `next`'s parity)
+	if(harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE);
+	const int err = decode_pair(cur, next);
+	if(err) {                                                              // (as build_and_launch: nothing of a failed call stays queued)
+		(void)hipStreamSynchronize(ctx->stream);
+		if(ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
+		(void)hipGetLastError();
+		if(cur) { drop_staged(cur); cur->decoded = false; }
+		if(next) { drop_staged(next); next->decoded = false; }
+	}
+	return err;
+}
+
+extern "C" int crthip_batch_set_parity(crthip_batch *b, uint32_t parity) {
+	if(!b || !b->ctx || parity > 1) return fail(CRTHIP_E_ARGUMENT);
+	if(b->parity == parity) return CRTHIP_OK;
+	HIP_TRY(hipSetDevice(b->ctx->device));
+	// what the object has on its old parity's blocks - an arena image on its way, a decode in flight, a planned stage - is finished or dropped first
+	if(b->ctx->in_flight == b && harvest(b->ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE);
+	if(b->staged || b->ctx->last_decoded == b) { HIP_TRY(hipStreamSynchronize(b->ctx->stream)); drop_staged(b); }
+	if(b->ctx->last_decoded == b) b->ctx->last_decoded = nullptr;
+	b->parity = (uint8_t)parity; b->dirty = true; b->decoded = false;
+	return CRTHIP_OK;
 }
 
 extern "C" int crthip_batch_sync(crthip_batch *b, int32_t *status) {
@@ -706,6 +827,7 @@ extern "C" int64_t crthip_batch_debug_read(crthip_batch *b, uint32_t i, const ch
 	if(!b || i >= b->blobs.size() || !what || !host_out || !b->decoded) return fail(CRTHIP_E_ARGUMENT);
 	crthip_ctx *ctx = b->ctx;
 	if(ctx->last_decoded != b) return fail(CRTHIP_E_ARGUMENT, "the context's scratch block has been reused by a later call");
+	ctx_select(ctx, b->parity);
 	HIP_TRY(hipStreamSynchronize(ctx->stream));
 	BlobPlan &P = b->blobs[i];
 	const uint8_t *src = nullptr; size_t n = 0;

@@ -194,7 +194,27 @@ struct crthip_ctx {
 	uint32_t delta_calm = 0, delta_patience = 256;
 	// the narrow layout is on trial again after a wide spell (an overflow now doubles the patience)
 	bool delta_just_narrowed = false;
+	// crthip_batch_decode_with_next: two batches are alive on the context - one in its mesh stage, the next one's entropy stage beside it - so what
+	// ONE decode call owns exists twice, by the batch object's parity (crthip_batch_set_parity): its arena image, descriptor / staging block, status
+	// block, scratch and plan, and the bookkeeping of its arena upload.  The members above are the ACTIVE set, `spare` is the other one, and
+	// ctx_select() swaps them: every entry point that works on a batch's blocks selects that batch's parity first.  A context whose batches all
+	// have parity 0 (every lone context, the facade) never swaps.  Shared by both: the stream, in_flight / ev_done (one call in flight), and what
+	// harvest() learns - a batch planned before its predecessor's flags were read learns from them one batch late.
+	struct Half {
+		DeviceBuf scratch; PinnedBuf staging, arena_pin, status_host;
+		uint32_t upload_seq = 0, done_covers_seq = 0; bool arena_upload_pending = false;
+		Plan plan; std::vector<BlobScratch> plan_scratch;
+	} spare;
+	uint8_t active = 0;
 };
+inline void ctx_select(crthip_ctx *ctx, uint8_t parity) {
+	if(ctx->active == parity) return;
+	crthip_ctx::Half &h = ctx->spare;
+	std::swap(ctx->scratch, h.scratch); std::swap(ctx->staging, h.staging); std::swap(ctx->arena_pin, h.arena_pin); std::swap(ctx->status_host, h.status_host);
+	std::swap(ctx->upload_seq, h.upload_seq); std::swap(ctx->done_covers_seq, h.done_covers_seq); std::swap(ctx->arena_upload_pending, h.arena_upload_pending);
+	std::swap(ctx->plan, h.plan); std::swap(ctx->plan_scratch, h.plan_scratch);
+	ctx->active = parity;
+}
 
 // bytes per component of a generic attribute's caller buffer: upstream decodes in place as int32 whatever the format and DOUBLE widens
 // in place (include/corto/vertex_attribute.h:184-228), so every format's buffer is nvert*N*4 bytes but DOUBLE's
@@ -226,7 +246,13 @@ struct crthip_batch {
 	std::vector<int32_t> status;
 	bool decoded = false;
 	bool planned_wide = false;          // the decode in flight was planned with K-DELTA's 32-bit layout
+	bool carriable = false;             // (account) the decode's entropy stage fits another batch's grids AND its own grids can carry one: what a pool lane asks before it pipelines
+	uint8_t parity = 0;                 // which of the context's two sets of per-call blocks this object uses (crthip_batch_set_parity)
+	// crthip_batch_decode_with_next planned this batch as `next`: its planner, kept until the call that runs its mesh stage (e_done: its entropy
+	// stage has been enqueued; else that call runs the whole schedule)
+	struct Planner *staged = nullptr;
 };
+void drop_staged(crthip_batch *b);      // (batch.cpp)
 
 // The per-blob status block: four int32 words a blob in the context's pinned host memory (status_host), written by the kernels, zeroed by
 // Planner::upload, read by harvest
@@ -294,6 +320,13 @@ struct Launch {
 // SP(offset), the offset with bit 63 set, and upload() passes every pointer field through resolve(), which turns those into base + offset
 // and leaves every other pointer (the arena, the caller's buffers, the pinned status words, null) as it is.  A user-space address on
 // x86-64 never has bit 63 set.  The one exception: TopoJob.group_end holds a byte offset into aux_u32 (placed after jobs()).
+// the next batch's K-TAB / K-STREAM arguments, for the grids of the batch that carries them (plan_launch.cpp)
+struct Carry {
+	const TunStream *dicts; uint32_t ndicts; TunTable *tables;
+	const TunStream *streams; const uint32_t *ids; const TunGroup *groups; uint32_t ngroups;
+};
+// what Planner::launch enqueues: the descriptor copy and the zeroing | K-TAB, K-STREAM | k_fill (stage E) | everything else (stage M)
+enum : uint32_t { PH_UP = 1, PH_TUN = 2, PH_FILL = 4, PH_MESH = 8, PH_ENTROPY = PH_UP | PH_TUN | PH_FILL, PH_ALL = 15 };
 struct Planner {
 	crthip_batch *b; crthip_ctx *ctx; Plan &pl; std::vector<BlobScratch> &bs;
 	// wide: K-DELTA with 32-bit values in LDS (this context met values beyond int16)
@@ -314,6 +347,8 @@ struct Planner {
 		const uintptr_t v = (uintptr_t)p;
 		if(v >> 63) p = (T *)(base + (v & ~(1ull << 63)));
 	}
-	int carve(); int jobs(); void group(); int upload(); int launch(); void account();
+	bool e_done = false;                                                     // stage E has been enqueued (by an earlier call)
+	int carve(); int jobs(); void group(); int upload(); int launch(uint32_t phases = PH_ALL, const Carry *carry = nullptr); int mark_done(); void account();
+	bool splits() const; bool takes_front() const; bool carry_args(Carry &c) const; bool hosts_carry() const;
 };
 

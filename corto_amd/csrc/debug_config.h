@@ -31,6 +31,9 @@ struct DebugConfig {
 	                                // however small (tests/test_gpu_parity.py runs ragged sizes through both)
 	bool front_off = false;         // $CORTO_FRONT=0 (A/B and test hook): a single-stream context launches the automata and K-BIT as two kernels, one after the
 	                                // other, instead of k_front's one grid (plan_launch.cpp)
+	bool carry_off = false;         // $CORTO_CARRY=0 (A/B and test hook): crthip_batch_decode_with_next enqueues the next batch's entropy stage as launches of its
+	                                // own behind this batch's kernels instead of inside k_front's / k_delta_lds16's grids, and the pool runs one batch per
+	                                // lane and call as it did before it pipelined its lanes (plan_launch.cpp, pool.cpp)
 };
 
 inline DebugConfig debug_config_from_env() {
@@ -43,6 +46,7 @@ inline DebugConfig debug_config_from_env() {
 	c.delta_rounds = on("CORTO_DELTA_ROUNDS");
 	c.values_i32 = on("CORTO_VALUES_I32");
 	{ const char *e = getenv("CORTO_FRONT"); c.front_off = e && e[0] == '0'; }
+	{ const char *e = getenv("CORTO_CARRY"); c.carry_off = e && e[0] == '0'; }
 	return c;
 }
 

@@ -26,6 +26,8 @@
 // * The next window's graph words and raw values are fetched while the current pass gathers and scans.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "device_plan.h"
 #include "kernels.h"
 #include "kernels_common.h"
@@ -623,7 +625,7 @@ __device__ __forceinline__ void delta32_run(CRT_LDS uint8_t *rec, const DeltaJob
 // that has no attribute (by wave 0 in front of its own staging when all four have one).
 // LDS: records of attribute 0 | 1 | ... (each array a 16-byte multiple) | graph words (u32 x nvert) | a (u16 x nvert, unless it rides
 // in a three-component attribute's records): delta16_group_lds() in kernels.h is the same sum.
-__global__ __launch_bounds__(256) void k_delta_lds16(const DeltaJob *__restrict__ jobs, const DeltaGroup *__restrict__ groups, uint32_t ngroups) {
+__device__ __forceinline__ void delta_lds16_body(const DeltaJob *__restrict__ jobs, const DeltaGroup *__restrict__ groups, uint32_t ngroups) {
 	if(blockIdx.x >= ngroups) return;
 	const DeltaGroup G = groups[blockIdx.x];
 	extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -749,6 +751,25 @@ __global__ __launch_bounds__(256) void k_delta_lds16(const DeltaJob *__restrict_
 			for(uint32_t k = lane; k < n; k += 64) { const int32_t x = v[k]; ((CRT_GLOBAL float *)v)[k] = (float)x*J.q; }
 		}
 	}
+}
+
+__global__ __launch_bounds__(256) void k_delta_lds16(const DeltaJob *__restrict__ jobs, const DeltaGroup *__restrict__ groups, uint32_t ngroups) {
+	delta_lds16_body(jobs, groups, ngroups);
+}
+
+// K-DELTA of a pipelined lane (crthip_batch_decode_with_next): the same workgroups, and behind them the stream groups of the lane's NEXT batch -
+// k_tun_stream_grouped's body, 256 threads like these, decoding from the dictionaries the launch before (k_front_carry) finished into that
+// batch's own scratch.  The dictionary copy is carved from the head of the dynamic block; no workgroup waits for another.
+#include "tun_stream.h"
+static_assert(TUN_GROUP_LDS == TUN_CARRY_GROUP_LDS, "kernels.h: the carried stream groups' share of k_delta_lds16_carry's dynamic LDS");
+__global__ __launch_bounds__(256) void k_delta_lds16_carry(const DeltaJob *__restrict__ jobs, const DeltaGroup *__restrict__ groups, uint32_t ngroups,
+                                                           const TunStream *__restrict__ streams, const uint32_t *__restrict__ ids,
+                                                           const TunGroup *__restrict__ tun_groups, uint32_t ntun_groups, const TunTable *__restrict__ tables) {
+	if(blockIdx.x < ngroups) { delta_lds16_body(jobs, groups, ngroups); return; }
+	const uint32_t g = blockIdx.x - ngroups;
+	if(g >= ntun_groups) return;
+	extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+	tun_group_body(streams, ids, tun_groups[g], tables, lds);
 }
 
 

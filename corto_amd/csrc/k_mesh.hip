@@ -4,6 +4,8 @@
 //                                                                              src/normal_attribute.cpp:193-201
 // Both are chains of dependent reads per blob: the parallel unit is the blob.  One
 // wave per blob; many blobs per launch.
+#include <type_traits>
+
 #include "kernels_common.h"
 #include "kernels.h"
 #include "unpack_wave.h"
@@ -1973,6 +1975,28 @@ __global__ __launch_bounds__(64) void k_front(const TopoJob *__restrict__ jobs, 
 	const uint32_t tb = front_topo_blocks(ntopo);
 	if(blockIdx.x < tb) topo_lds_kernel<false>(jobs, topo_ids, ntopo);
 	else unpack_wave_body(ujobs, unpack_ids, nunpack, blockIdx.x - tb);
+}
+
+// K-FRONT of a pipelined lane (crthip_batch_decode_with_next): the same grid with the NEXT batch's dictionaries behind it - block ranges
+// [automata of this batch | K-BIT of this batch | K-TAB of the next].  A dictionary depends on its probability table alone, which the next
+// batch's upload put in the arena before this launch; its streams are decoded by the launch behind this one (k_delta_lds16_carry), so no
+// workgroup waits for another.  One wave a dictionary as in k_tun_tables, words straight to HBM (the host carries alphabets of up to 64
+// symbols only); the growth state is the head of the dynamic block - nothing static, or the automata's records would leave address 0.
+#include "tun_tables.h"
+static_assert(TUN_GROW_BYTES == TUN_CARRY_GROW_LDS, "kernels.h: the carried dictionaries' share of k_front_carry's dynamic LDS");
+__global__ __launch_bounds__(64) void k_front_carry(const TopoJob *__restrict__ jobs, const uint32_t *__restrict__ topo_ids, uint32_t ntopo,
+                                                    const UnpackJob *__restrict__ ujobs, const uint32_t *__restrict__ unpack_ids, uint32_t nunpack,
+                                                    const TunStream *__restrict__ dicts, uint32_t ndicts, TunTable *__restrict__ tables) {
+	const uint32_t tb = front_topo_blocks(ntopo), ub = xcd_grid(nunpack);
+	if(blockIdx.x < tb) topo_lds_kernel<false>(jobs, topo_ids, ntopo);
+	else if(blockIdx.x < tb + ub) unpack_wave_body(ujobs, unpack_ids, nunpack, blockIdx.x - tb);
+	else {
+		const uint32_t s = blockIdx.x - tb - ub;
+		if(s >= ndicts) return;
+		extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+		const TunStream st = dicts[s];
+		tun_tables_body<true, true>(st, &tables[st.table], nullptr, nullptr, nullptr, nullptr, lds);
+	}
 }
 
 } // namespace corto_hip

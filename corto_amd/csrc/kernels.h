@@ -23,7 +23,7 @@ __host__ __device__ inline uint32_t tun_width(uint32_t cpl, uint32_t maxlen) { r
 int launch_tun_decode_staged(hipStream_t stream, const TunStream *streams, const uint32_t *chunk_stream, uint32_t nchunks, const TunTable *tables,
                              uint64_t *chunk_out, uint32_t sums_only);    // words <= 4 bytes, <= 8 bytes, longer: three bodies of one kernel
 // blocks of a launch whose kernel takes its job by xcd_slot() (kernels_common.h: every XCD a contiguous eighth of the jobs)
-inline uint32_t xcd_grid(uint32_t n) { return 8u*((n + 7u) >> 3); }
+__host__ __device__ inline uint32_t xcd_grid(uint32_t n) { return 8u*((n + 7u) >> 3); }
 __global__ void k_fill(const FillJob *jobs, uint32_t njobs);
 __global__ void k_fill_block(uint8_t *dst, uint64_t bytes, uint32_t value);
 
@@ -48,6 +48,13 @@ __global__ void k_topology_lds_big(const TopoJob *jobs, const uint32_t *job_ids,
 // k_topology_lds and k_unpack_wave in one grid (single-stream contexts): front_topo_blocks(ntopo) automata first, then xcd_grid(nunpack) K-BIT waves
 __host__ __device__ inline uint32_t front_topo_blocks(uint32_t ntopo) { return (ntopo + 7u) & ~7u; }
 __global__ void k_front(const TopoJob *jobs, const uint32_t *topo_ids, uint32_t ntopo, const UnpackJob *ujobs, const uint32_t *unpack_ids, uint32_t nunpack);
+// ... and the dictionaries of the lane's NEXT batch behind them (crthip_batch_decode_with_next): ndicts more blocks, their growth state carved from
+// the automata's dynamic LDS request, which therefore has to be at least TUN_CARRY_GROW_LDS
+__global__ void k_front_carry(const TopoJob *jobs, const uint32_t *topo_ids, uint32_t ntopo, const UnpackJob *ujobs, const uint32_t *unpack_ids, uint32_t nunpack,
+                              const TunStream *dicts, uint32_t ndicts, TunTable *tables);
+constexpr uint32_t TUN_CARRY_GROW_LDS = TUN_ENTRY_CAP*6 + 3*512 + 256;       // sizeof(TunGrow), tun_tables.h
+constexpr uint32_t TUN_CARRY_DICTS_MAX = 512;                               // the most dictionaries a k_front grid carries (plan_launch.cpp: carry_args)
+constexpr uint32_t TUN_CARRY_GROUP_LDS = 512 + 256 + TUN_TABLE_BYTES;       // TUN_GROUP_LDS, tun_stream.h
 // (K-BIT's waves hold the automata's LDS request too: k_front only while that is small)
 constexpr uint32_t FRONT_LDS_MAX = 32*1024;
 // dynamic LDS bytes k_topology_lds needs for a front of `cap` edges and `nclers` symbols
@@ -109,6 +116,10 @@ __host__ __device__ inline uint32_t delta16_graph_lds(uint32_t nvert, bool a_emb
 	return ((4u*nvert + 15u) & ~15u) + (a_embedded ? 0u : ((2u*nvert + 15u) & ~15u)) + 16u;
 }
 __global__ void k_delta_lds16(const DeltaJob *jobs, const DeltaGroup *groups, uint32_t ngroups);
+// ... with the stream groups of the lane's NEXT batch behind this batch's blobs: block ranges [blobs | stream groups], the carried groups' dictionary
+// copy at the head of the dynamic block (the launch asks for at least TUN_CARRY_GROUP_LDS)
+__global__ void k_delta_lds16_carry(const DeltaJob *jobs, const DeltaGroup *groups, uint32_t ngroups, const TunStream *streams, const uint32_t *ids,
+                                    const TunGroup *tun_groups, uint32_t ntun_groups, const TunTable *tables);
 
 // k_normal.hip
 __global__ void k_normal_diff(const NormalJob *jobs, const uint32_t *block_job, const uint32_t *block_first, uint32_t nblocks);

@@ -37,14 +37,49 @@ int Planner::upload() {
 	return CRTHIP_OK;
 }
 
-int Planner::launch() {
+// The schedule has two stages (batch_internal.h: PH_*).  Stage E - the descriptor copy, the zeroing, K-TAB, K-STREAM, k_fill - reads the batch's arena and
+// descriptors and writes only the batch's own scratch; stage M is everything behind it and writes the caller's outputs and the status words.
+// crthip_batch_decode runs both in one call.  crthip_batch_decode_with_next runs stage M of one batch with stage E of the lane's next batch:
+// as launches of its own (PH_TUN), or - `carry`, the next batch's K-TAB / K-STREAM arguments - inside this batch's k_front / k_delta_lds16 grids.
+bool Planner::splits() const {
+	const uint32_t ntun = (uint32_t)pl.tun.v.size(), nfill = (uint32_t)pl.fill.v.size();
+	if(pl.tun_multi_chunk) return false;
+	return !(!pl.topo.v.empty() && (ntun > clers_tun || nfill > clers_fill || unpack_chunks || !pl.unpack_wave_ids.v.empty()) && !ctx->single_stream);
+}
+bool Planner::takes_front() const {
+	return ctx->single_stream && !ctx->dbg.front_off && !pl.topo_lds_ids.v.empty() && !pl.unpack_wave_ids.v.empty() && pl.topo_big_ids.v.empty() &&
+		pl.topo_glob_ids.v.empty() && !unpack_chunks && pl.topo_lds <= FRONT_LDS_MAX;
+}
+// every stream of the batch through shared dictionaries of up to 64 symbols, in one K-TAB and one K-STREAM launch: what another batch's grids can carry
+bool Planner::carry_args(Carry &c) const {
+	const uint32_t ntun = (uint32_t)pl.tun.v.size(), ndict = (uint32_t)pl.tun_dict.v.size(), ngroups = (uint32_t)pl.tun_groups.v.size();
+	if(ctx->dbg.carry_off || !ctx->single_stream || !splits() || !ntun || !ndict || !ngroups) return false;
+	if((clers_tun > 0 && !share_clers) || (ntun > clers_tun && !share_attrs)) return false;
+	for(const TunStream &d : pl.tun_dict.v) if(d.nsym > 64) return false;
+	// a carried dictionary holds k_front's LDS request (~10 KB) for its ~45 us beside other lanes' automata, which wait for LDS to come free: the ~250
+	// distinct tables of a batch whose blobs repeat one another's add 0.1 GB.us to the ~2.4 the step holds, a dictionary PER STREAM (2 304 a batch,
+	// $CORTO_TUN_SHARE=2) 1 GB.us - measured 10 % slower than not carrying (profiles/pool_carry.md)
+	if(ndict > TUN_CARRY_DICTS_MAX) return false;
+	c.dicts = (const TunStream *)(base + pl.tun_dict.dev_off); c.ndicts = ndict; c.tables = (TunTable *)(base + pl.tables_off);
+	c.streams = (const TunStream *)(base + pl.tun.dev_off); c.ids = (const uint32_t *)(base + pl.tun_group_ids.dev_off);
+	c.groups = (const TunGroup *)(base + pl.tun_groups.dev_off); c.ngroups = ngroups;
+	return true;
+}
+// ... and a batch whose grids can carry them: k_front with room for the dictionaries' growth state in the automata's LDS request, and k_delta_lds16
+bool Planner::hosts_carry() const {
+	return !ctx->dbg.carry_off && splits() && takes_front() && pl.topo_lds >= TUN_CARRY_GROW_LDS && !pl.delta.v.empty() && !pl.delta_groups.v.empty();
+}
+
+int Planner::launch(uint32_t phases, const Carry *carry) {
 	hipStream_t st = ctx->stream;
-	ctx->timer.reset();
 	Launch LT{ctx};
-	if(pl.jobs_bytes) HIP_TRY(hipMemcpyAsync(base + pl.jobs_begin, stage, pl.jobs_bytes, hipMemcpyHostToDevice, st));
-	if(pl.zero_end > pl.zero_begin) HIP_TRY(hipMemsetAsync(base + pl.zero_begin, 0, pl.zero_end - pl.zero_begin, st));
-	for(uint32_t i = 0; i < nblobs; i++)                                         // the progress words of big meshes (a handful a batch at most)
-		if(bs[i].progress != ~0ull) HIP_TRY(hipMemsetAsync(base + bs[i].progress, 0, TOPO_PROGRESS_BYTES, st));
+	if(phases != PH_ALL && !splits()) return fail(CRTHIP_E_ARGUMENT, "this batch's schedule has no separate entropy stage");
+	if(phases & PH_UP) {
+		if(pl.jobs_bytes) HIP_TRY(hipMemcpyAsync(base + pl.jobs_begin, stage, pl.jobs_bytes, hipMemcpyHostToDevice, st));
+		if(pl.zero_end > pl.zero_begin) HIP_TRY(hipMemsetAsync(base + pl.zero_begin, 0, pl.zero_end - pl.zero_begin, st));
+		for(uint32_t i = 0; i < nblobs; i++)                                         // the progress words of big meshes (a handful a batch at most)
+			if(bs[i].progress != ~0ull) HIP_TRY(hipMemsetAsync(base + bs[i].progress, 0, TOPO_PROGRESS_BYTES, st));
+	}
 
 	auto D = [&](auto &arr) { return (decltype(arr.v.data()))(base + arr.dev_off); };
 	TunTable *tables = (TunTable *)(base + pl.tables_off);
@@ -59,7 +94,7 @@ int Planner::launch() {
 	// matter: share_clers / share_attrs, decided where the groups were made)
 	stat_dicts = (share_clers ? clers_dict : clers_tun) + (share_attrs ? ndict - clers_dict : ntun - clers_tun);
 	auto tunstall = [&](hipStream_t s, uint32_t t0, uint32_t t1, uint32_t c0, uint32_t c1, uint32_t f0, uint32_t f1) {
-		if(t1 > t0) {                                        // every stream here is one chunk: one wave per stream
+		if(t1 > t0 && (phases & PH_TUN)) {                   // every stream here is one chunk: one wave per stream
 			(void)c0; (void)c1;
 			// [t0, t1) is the CLERS streams, the attribute streams, or both (dictionaries are numbered the same way)
 			const bool has_clers = t0 == 0 && clers_tun > 0, has_attrs = t1 == ntun && ntun > clers_tun;
@@ -80,7 +115,7 @@ int Planner::launch() {
 					LT.end();
 			}
 		}
-		if(f1 > f0) { LT.begin("fill", s); hipLaunchKernelGGL(k_fill, dim3(f1 - f0), dim3(256), 0, s, D(pl.fill) + f0, f1 - f0); LT.end(); }
+		if(f1 > f0 && (phases & PH_FILL)) { LT.begin("fill", s); hipLaunchKernelGGL(k_fill, dim3(f1 - f0), dim3(256), 0, s, D(pl.fill) + f0, f1 - f0); LT.end(); }
 	};
 	auto unpack = [&](hipStream_t s) {
 		const uint32_t nuw = (uint32_t)pl.unpack_wave_ids.v.size();
@@ -174,11 +209,14 @@ int Planner::launch() {
 		HIP_TRY(hipStreamWaitEvent(st, ctx->ev_join, 0));
 	} else {
 		tunstall(st, 0, ntun, 0, tun_chunks, 0, nfill);
+		if(!(phases & PH_MESH)) { HIP_TRY(hipGetLastError()); return CRTHIP_OK; }
 		// one stream: the automata and the attributes' bit-unpack in one grid (k_front) when the batch has nothing else for either -
 		// no big or HBM-front automaton, no chunked K-BIT - and the automata ask for little LDS (K-BIT's waves hold the same request)
 		const uint32_t nuw = (uint32_t)pl.unpack_wave_ids.v.size(), ntl = (uint32_t)pl.topo_lds_ids.v.size();
-		if(ctx->single_stream && !ctx->dbg.front_off && ntl && nuw && pl.topo_big_ids.v.empty() && pl.topo_glob_ids.v.empty() && !unpack_chunks &&
-			pl.topo_lds <= FRONT_LDS_MAX) {
+		if(takes_front() && carry) {                            // (hosts_carry(): the next batch's dictionaries behind K-BIT's waves)
+			LT.begin("front"); hipLaunchKernelGGL(k_front_carry, dim3(front_topo_blocks(ntl) + xcd_grid(nuw) + carry->ndicts), dim3(64), pl.topo_lds, st,
+				D(pl.topo), D(pl.topo_lds_ids), ntl, D(pl.unpack), D(pl.unpack_wave_ids), nuw, carry->dicts, carry->ndicts, carry->tables); LT.end();
+		} else if(takes_front()) {
 			LT.begin("front"); hipLaunchKernelGGL(k_front, dim3(front_topo_blocks(ntl) + xcd_grid(nuw)), dim3(64), pl.topo_lds, st, D(pl.topo),
 				D(pl.topo_lds_ids), ntl, D(pl.unpack), D(pl.unpack_wave_ids), nuw); LT.end();
 		} else {
@@ -189,7 +227,10 @@ int Planner::launch() {
 	if(!pl.delta.v.empty()) {
 		const uint32_t ngroups = (uint32_t)pl.delta_groups.v.size();
 		if(!tiles_launched) delta_tiles(st);                    // (too big for the LDS records, and not launched beside the automaton above)
-		if(ngroups) { LT.begin("delta_lds16"); hipLaunchKernelGGL(k_delta_lds16, dim3(ngroups), dim3(256), pl.delta16_lds, st, D(pl.delta), D(pl.delta_groups),
+		if(ngroups && carry) {                                  // ... and its stream groups behind this batch's blobs
+			LT.begin("delta_lds16"); hipLaunchKernelGGL(k_delta_lds16_carry, dim3(ngroups + carry->ngroups), dim3(256), std::max(pl.delta16_lds, TUN_CARRY_GROUP_LDS), st,
+				D(pl.delta), D(pl.delta_groups), ngroups, carry->streams, carry->ids, carry->groups, carry->ngroups, carry->tables); LT.end();
+		} else if(ngroups) { LT.begin("delta_lds16"); hipLaunchKernelGGL(k_delta_lds16, dim3(ngroups), dim3(256), pl.delta16_lds, st, D(pl.delta), D(pl.delta_groups),
 			ngroups); LT.end(); }
 	}
 	if(cloud_chunks) {
@@ -241,9 +282,13 @@ int Planner::launch() {
 
 	// (status: written by the kernels straight into the pinned block)
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(ctx->ev_done, st));
-	ctx->done_covers_seq = ctx->upload_seq;
+	return CRTHIP_OK;
+}
 
+// the event a call's sync / done wait for, behind everything the call enqueued (on the half of the batch whose stage M the call ran)
+int Planner::mark_done() {
+	HIP_TRY(hipEventRecord(ctx->ev_done, ctx->stream));
+	ctx->done_covers_seq = ctx->upload_seq;
 	return CRTHIP_OK;
 }
 
@@ -271,6 +316,7 @@ void Planner::account() {
 	}
 	b->stats.output_bytes = ob;
 	ctx->in_flight = b; ctx->last_decoded = b;
+	{ Carry c; b->carriable = carry_args(c) && hosts_carry(); }
 	b->decoded = true; b->planned_wide = wide;
 	b->dirty = false;
 }

@@ -8,6 +8,7 @@
 #include <pthread.h>
 #include <sched.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -25,24 +26,34 @@ using corto_hip::ctx_fail;
 
 namespace {
 
-struct Lane {                       // one context = one batch in flight
-	uint32_t slot = 0;              // pool device index
-	int device = 0;
-	crthip_ctx *ctx = nullptr;
+struct Slot {                       // a batch object and the item it is planned for
 	crthip_batch *batch = nullptr;
-	void *out = nullptr; size_t out_cap = 0;
-	void *host_out = nullptr; size_t host_cap = 0, out_used = 0;   // outputs_to_host: the pinned mirror of `out` (its first out_used bytes are copied behind every decode)
 	// bindings of the item the batch object is planned for
 	std::vector<crthip_attr_binding> binds;
 	std::vector<void *> index_ptr;
 	std::vector<uint32_t> index_fmt;
-	std::vector<size_t> attr_off, index_off;     // byte offsets inside `out` (attr_off: per binding entry)
+	std::vector<size_t> attr_off, index_off;     // byte offsets inside the lane's `out` (attr_off: per binding entry)
 	std::vector<uint32_t> first_attr;            // first binding entry of blob i
 	std::vector<int32_t> status;
-	int64_t item = -1;              // item of the step in flight / last executed
+	size_t out_used = 0;            // outputs_to_host: the first out_used bytes of `out` are copied behind the decode
+	int64_t item = -1;              // the item
 	uint64_t step = 0;              // its global step number
+};
+// One context = one call in flight.  A pipelined lane (crthip_batch_decode_with_next) holds TWO batch objects and one output block: s[cur] is the
+// batch whose mesh stage is in flight or ran last - the only one that writes `out` - and, `staged`, s[cur ^ 1] the next one, planned, uploaded and
+// with its entropy stage carried by the same call.  Any other lane uses s[cur] alone.
+struct Lane {
+	uint32_t slot = 0;              // pool device index
+	int device = 0;
+	crthip_ctx *ctx = nullptr;
+	Slot s[2]; uint32_t cur = 0; bool staged = false;
+	// A lane pipelines only while it pays: `pipe` - the batch it decoded last could be carried and could carry (a lane starts every run one batch a
+	// call); `drain` - the call just enqueued could NOT carry the planned batch, which then runs alone, whole, and the lane is back to one batch a call
+	bool pipe = false, drain = false;
+	void *out = nullptr; size_t out_cap = 0;
+	void *host_out = nullptr; size_t host_cap = 0;   // outputs_to_host: the pinned mirror of `out`
 	bool busy = false;
-	bool poisoned = false;          // the output block was filled with POISON on the context's stream right before the step in flight / last executed
+	bool poisoned = false;          // the output block was filled with POISON on the context's stream right before the mesh stage in flight / last executed
 };
 constexpr int POISON = 0xA5;
 
@@ -58,6 +69,8 @@ struct crthip_pool {
 	std::string warning;            // what crthip_pool_create had to say about hardware queues (empty: nothing)
 	bool render = false;            // crthip_pool_set_render_layouts: int16 normals, uint16 index where the blob's vertex ids fit
 	bool to_host = false;           // crthip_pool_set_outputs_to_host: every step ends with a D2H copy of its outputs into the lane's pinned block
+	bool pipelined = false;         // every lane is a single-stream context and $CORTO_CARRY is not 0: the lanes run two batches each (Lane)
+	size_t out_need = 0;            // the largest output block any item of the run asks for: a pipelined lane's block is not moved under a planned batch
 	// state of one run
 	std::atomic<uint64_t> next{0}, completed{0};
 	std::mutex m;
@@ -66,11 +79,11 @@ struct crthip_pool {
 
 static void destroy_lane(Lane &L) {
 	(void)hipSetDevice(L.device);
-	if(L.batch) crthip_batch_destroy(L.batch);
+	for(Slot &S : L.s) { if(S.batch) crthip_batch_destroy(S.batch); S.batch = nullptr; }
 	if(L.ctx) crthip_ctx_destroy(L.ctx);
 	if(L.out) (void)hipFree(L.out);
 	if(L.host_out) (void)hipHostFree(L.host_out);
-	L.batch = nullptr; L.ctx = nullptr; L.out = nullptr; L.out_cap = 0; L.host_out = nullptr; L.host_cap = 0;
+	L.ctx = nullptr; L.out = nullptr; L.out_cap = 0; L.host_out = nullptr; L.host_cap = 0;
 }
 
 extern "C" int crthip_pool_create(uint32_t ndevices, const int *devices, uint32_t threads_per_device, uint32_t depth, crthip_pool **out) {
@@ -97,6 +110,8 @@ extern "C" int crthip_pool_create(uint32_t ndevices, const int *devices, uint32_
 		if(!err && 2*ctx_per_gpu[L.device] > hw_queues) err = crthip_ctx_set_single_stream(L.ctx, 1);   // (+ the LDS-lean normals, profiles/r08_what_was_measured.txt)
 		if(err) { for(auto &x : p->lanes) destroy_lane(x); delete p; return err; }
 	}
+	p->pipelined = true;
+	for(auto &L : p->lanes) p->pipelined = p->pipelined && corto_hip::ctx_pipelines(L.ctx);
 	for(auto &kv : ctx_per_gpu)
 		if(kv.second > hw_queues && p->warning.empty()) {
 			char buf[320];
@@ -154,7 +169,7 @@ extern "C" int crthip_pool_set_outputs_to_host(crthip_pool *p, int on) {
 extern "C" int crthip_pool_set_render_layouts(crthip_pool *p, int on) {
 	if(!p) return ctx_fail(CRTHIP_E_ARGUMENT, nullptr);
 	p->render = on != 0;
-	for(auto &L : p->lanes) { L.binds.clear(); L.item = -1; }      // the lanes lay their outputs out again
+	for(auto &L : p->lanes) for(Slot &S : L.s) { S.binds.clear(); S.item = -1; }      // the lanes lay their outputs out again
 	return CRTHIP_OK;
 }
 extern "C" int crthip_pool_set_packed_host_blobs(crthip_pool *p, int on) {
@@ -170,49 +185,76 @@ extern "C" int crthip_pool_set_packed_host_blobs(crthip_pool *p, int on) {
 // running batch's kernels on the lane's own stream (0.15-0.20: a DMA copy queued behind kernels is started late), the same two with a
 // copy KERNEL reading the pinned buffer over PCIe (0.13 / 0.156).  All slower; removed.  What does help a little is one more lane per
 // thread's worth of contexts (5 x 4: 0.091): the lane whose blobs are on their way is idle for the GPU.
-// plan `item` on the lane's batch object, lay its outputs out in the lane's device block and bind them
-static int lane_plan(crthip_pool *p, Lane &L, const crthip_pool_item &it, int64_t item_id) {
+// bytes of one output array, and of a blob's index, in a lane's block
+static size_t attr_out_bytes(const crthip_pool *p, const crthip_blob_info &info, const crthip_attr_info &a) {
+	if(a.codec == CRTHIP_CODEC_NORMAL) return (size_t)info.nvert*(p->render ? 6 : 12);
+	if(a.codec == CRTHIP_CODEC_COLOR) return (size_t)info.nvert*4;
+	return (size_t)info.nvert*a.components*4;
+}
+static bool index_is_u16(const crthip_pool *p, const crthip_blob_info &info) { return info.nface && p->render && info.nvert < 65536; }
+static size_t take_out(size_t &off, size_t n) { off = (off + 255) & ~(size_t)255; const size_t r = off; off += n; return r; }
+// the block an item's outputs need, from the blobs' headers alone (lane_plan lays out the same way)
+static int item_out_bytes(const crthip_pool *p, const crthip_pool_item &it, size_t *total) {
+	size_t off = 0;
+	crthip_blob_info info;
+	for(uint32_t i = 0; i < it.nblobs; i++) {
+		const int err = crthip_probe(it.blobs[i], it.lens[i], &info);
+		if(err) return err;
+		for(uint32_t k = 0; k < info.nattr; k++) (void)take_out(off, attr_out_bytes(p, info, info.attr[k]));
+		if(info.nface) (void)take_out(off, (size_t)info.nface*(index_is_u16(p, info) ? 6 : 12));
+	}
+	*total = off + 256;
+	return CRTHIP_OK;
+}
+// plan `item` on one of the lane's batch objects, lay its outputs out in the lane's device block and bind them
+static int lane_plan(crthip_pool *p, Lane &L, Slot &S, const crthip_pool_item &it, int64_t item_id) {
 	const void *arena = it.device_arena ? it.device_arena[L.slot] : nullptr;
-	int err = L.batch ? crthip_batch_reset(L.batch, it.nblobs, it.blobs, it.lens, arena)
-	                  : crthip_batch_create(L.ctx, it.nblobs, it.blobs, it.lens, arena, &L.batch);
+	int err = CRTHIP_OK;
+	if(!S.batch && &S == &L.s[1]) {                              // the lane's second object lives on the context's other set of per-call blocks
+		err = crthip_batch_create(L.ctx, 0, nullptr, nullptr, nullptr, &S.batch);
+		if(!err) err = crthip_batch_set_parity(S.batch, 1);
+		if(err) return err;
+	}
+	err = S.batch ? crthip_batch_reset(S.batch, it.nblobs, it.blobs, it.lens, arena)
+	              : crthip_batch_create(L.ctx, it.nblobs, it.blobs, it.lens, arena, &S.batch);
 	if(err) return err;
-	if(L.item != item_id || L.binds.empty()) {                // the layout of an item's outputs depends on the item alone
-		L.binds.clear(); L.attr_off.clear(); L.first_attr.assign(it.nblobs, 0);
-		L.index_ptr.assign(it.nblobs, nullptr); L.index_fmt.assign(it.nblobs, CRTHIP_FMT_UINT32); L.index_off.assign(it.nblobs, 0);
+	if(S.item != item_id || S.binds.empty()) {                // the layout of an item's outputs depends on the item alone
+		S.binds.clear(); S.attr_off.clear(); S.first_attr.assign(it.nblobs, 0);
+		S.index_ptr.assign(it.nblobs, nullptr); S.index_fmt.assign(it.nblobs, CRTHIP_FMT_UINT32); S.index_off.assign(it.nblobs, 0);
 		size_t off = 0;
-		auto take = [&](size_t n) { off = (off + 255) & ~(size_t)255; const size_t r = off; off += n; return r; };
 		crthip_blob_info info;
 		for(uint32_t i = 0; i < it.nblobs; i++) {
-			if((err = crthip_batch_info(L.batch, i, &info)) != 0) return err;
-			L.first_attr[i] = (uint32_t)L.binds.size();
+			if((err = crthip_batch_info(S.batch, i, &info)) != 0) return err;
+			S.first_attr[i] = (uint32_t)S.binds.size();
 			for(uint32_t k = 0; k < info.nattr; k++) {
 				const crthip_attr_info &a = info.attr[k];
 				crthip_attr_binding b; b.buffer = nullptr; b.format = CRTHIP_FMT_FLOAT; b.out_components = 0; b.stride = 0; b.reserved = 0;
-				size_t n;
-				if(a.codec == CRTHIP_CODEC_NORMAL) { if(p->render) b.format = CRTHIP_FMT_INT16; n = (size_t)info.nvert*(p->render ? 6 : 12); }
-				else if(a.codec == CRTHIP_CODEC_COLOR) { b.format = CRTHIP_FMT_UINT8; b.out_components = 4; n = (size_t)info.nvert*4; }
-				else n = (size_t)info.nvert*a.components*4;
-				L.attr_off.push_back(take(n));
-				L.binds.push_back(b);
+				if(a.codec == CRTHIP_CODEC_NORMAL) { if(p->render) b.format = CRTHIP_FMT_INT16; }
+				else if(a.codec == CRTHIP_CODEC_COLOR) { b.format = CRTHIP_FMT_UINT8; b.out_components = 4; }
+				S.attr_off.push_back(take_out(off, attr_out_bytes(p, info, a)));
+				S.binds.push_back(b);
 			}
-			if(info.nface && p->render && info.nvert < 65536) L.index_fmt[i] = CRTHIP_FMT_UINT16;
-			if(info.nface) L.index_off[i] = take((size_t)info.nface*(L.index_fmt[i] == CRTHIP_FMT_UINT16 ? 6 : 12));
+			if(index_is_u16(p, info)) S.index_fmt[i] = CRTHIP_FMT_UINT16;
+			if(info.nface) S.index_off[i] = take_out(off, (size_t)info.nface*(S.index_fmt[i] == CRTHIP_FMT_UINT16 ? 6 : 12));
 		}
-		const size_t total = off + 256;
+		const size_t total = std::max(off + 256, p->out_need);
 		if(total > L.out_cap) {
+			// (never under a batch that is planned or running: out_need covers every item of the run, so a lane's block is made by its first plan)
+			if(L.busy || L.staged) return ctx_fail(CRTHIP_E_ARGUMENT, "corto_hip pool: a lane's output block would move under a planned batch");
 			if(L.out) (void)hipFree(L.out);
 			L.out = nullptr; L.out_cap = 0;
+			for(Slot &O : L.s) if(&O != &S) { O.binds.clear(); O.item = -1; }
 			if(hipMalloc(&L.out, total + total/8) != hipSuccess) return ctx_fail(CRTHIP_E_NOMEM, nullptr);
 			L.out_cap = total + total/8;
 		}
 		uint8_t *base = (uint8_t *)L.out;
-		for(size_t k = 0; k < L.binds.size(); k++) L.binds[k].buffer = base + L.attr_off[k];
+		for(size_t k = 0; k < S.binds.size(); k++) S.binds[k].buffer = base + S.attr_off[k];
 		for(uint32_t i = 0; i < it.nblobs; i++) {
-			if((err = crthip_batch_info(L.batch, i, &info)) != 0) return err;
-			L.index_ptr[i] = info.nface ? base + L.index_off[i] : nullptr;
+			if((err = crthip_batch_info(S.batch, i, &info)) != 0) return err;
+			S.index_ptr[i] = info.nface ? base + S.index_off[i] : nullptr;
 		}
-		L.status.assign(it.nblobs, 0);
-		L.out_used = off;
+		S.status.assign(it.nblobs, 0);
+		S.out_used = off;
 	}
 	if(p->to_host && L.host_cap < L.out_cap) {                 // (first use: 32 MB of pinned memory a lane for a C4 item)
 		if(L.host_out) (void)hipHostFree(L.host_out);
@@ -220,8 +262,8 @@ static int lane_plan(crthip_pool *p, Lane &L, const crthip_pool_item &it, int64_
 		if(hipHostMalloc(&L.host_out, L.out_cap, hipHostMallocDefault) != hipSuccess) return ctx_fail(CRTHIP_E_NOMEM, nullptr);
 		L.host_cap = L.out_cap;
 	}
-	L.item = item_id;
-	return crthip_batch_bind_all(L.batch, L.binds.data(), L.index_ptr.data(), L.index_fmt.data());
+	S.item = item_id;
+	return crthip_batch_bind_all(S.batch, S.binds.data(), S.index_ptr.data(), S.index_fmt.data());
 }
 
 extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_pool_item *items, uint64_t steps, uint64_t warmup,
@@ -238,9 +280,19 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 			item_tris[j] += info.nface; item_verts[j] += info.nvert;
 		}
 	const uint64_t timed_end = warmup + steps;
-	const uint64_t total = timed_end + p->lanes.size();      // the tail keeps every context busy until the last timed completion
+	// the tail keeps every context busy until the last timed completion (a pipelined lane has two tickets drawn and not completed)
+	const uint64_t total = timed_end + p->lanes.size()*(p->pipelined ? 2u : 1u);
 	p->next = 0; p->completed = 0; p->error = CRTHIP_OK; p->error_msg.clear();
-	for(auto &L : p->lanes) { L.busy = false; L.item = -1; L.binds.clear(); }   // (an item id means this call's items[] only)
+	for(auto &L : p->lanes) { L.busy = false; L.staged = false; L.poisoned = false; L.pipe = false; L.drain = false; for(Slot &S : L.s) { S.item = -1; S.binds.clear(); } }   // (an item id means this call's items[] only; `poisoned` a mesh stage of this run)
+	p->out_need = 0;
+	if(p->pipelined)
+		for(uint32_t j = 0; j < nitems; j++) {
+			size_t need = 0;
+			const int err = item_out_bytes(p, items[j], &need);
+			if(err) return err;
+			p->out_need = std::max(p->out_need, need);
+		}
+	const bool pipe = p->pipelined;
 	std::vector<double> stamps(timed_end + 1, 0.0);           // stamps[c] = time at which the c-th completion happened (1-based)
 	std::atomic<uint64_t> failed{0}, fallbacks{0}, tris{0}, verts{0};
 	std::vector<std::atomic<uint64_t>> per_dev(p->ndevices);
@@ -269,23 +321,36 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 		}
 		Lane *mine = &p->lanes[((size_t)slot*p->threads_per_device + t)*p->depth];
 		auto finish = [&](Lane &L) -> int {
-			const int rc = crthip_batch_sync(L.batch, L.status.data());
+			Slot &S = L.s[L.cur];
+			const int rc = crthip_batch_sync(S.batch, S.status.data());
 			L.busy = false;
 			const uint64_t c = ++p->completed;                   // completion order
 			if(c <= timed_end) stamps[c] = now_s();
 			uint64_t bad = 0;
-			for(int32_t s : L.status) if(s) { bad++; int32_t z = 0; first_error.compare_exchange_strong(z, s); }
+			for(int32_t st_ : S.status) if(st_) { bad++; int32_t z = 0; first_error.compare_exchange_strong(z, st_); }
 			failed += bad;
 			crthip_batch_stats st;
-			if(crthip_batch_get_stats(L.batch, &st) == CRTHIP_OK) fallbacks += st.topology_fallbacks;
-			if(c > warmup && c <= timed_end) { per_dev[slot]++; tris += item_tris[(size_t)L.item]; verts += item_verts[(size_t)L.item]; }
+			if(crthip_batch_get_stats(S.batch, &st) == CRTHIP_OK) fallbacks += st.topology_fallbacks;
+			if(c > warmup && c <= timed_end) { per_dev[slot]++; tris += item_tris[(size_t)S.item]; verts += item_verts[(size_t)S.item]; }
 			if(rc == CRTHIP_E_DEVICE || rc == CRTHIP_E_NOMEM) return rc;
+			return CRTHIP_OK;
+		};
+		// the outputs every lane holds after the run were written by a mesh stage that STARTED from a poisoned block: the post-run bit-exact
+		// check cannot pass on bytes an earlier step left behind (on the context's own stream: ordered before the stage's kernels)
+		auto poison = [&](Lane &L, bool due) -> int {
+			L.poisoned = false;
+			if(!due || !L.out) return CRTHIP_OK;
+			const int e = corto_hip::ctx_fill_async(L.ctx, L.out, L.out_cap, POISON);
+			if(e) return e;
+			if(p->to_host && L.host_out) memset(L.host_out, POISON, L.s[L.cur].out_used);
+			L.poisoned = true;
 			return CRTHIP_OK;
 		};
 		int err = CRTHIP_OK;
 		auto tick = [] { return std::chrono::steady_clock::now(); };
 		auto ns_since = [](std::chrono::steady_clock::time_point t0) { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); };
-		for(uint64_t n = 0; !err; n++) {
+		bool tickets = true;
+		for(uint64_t n = 0; !err && tickets; n++) {
 			const auto w0 = tick();
 			// the next lane to refill: a free one, else whichever of the busy ones finishes first (they mostly finish in the order they
 			// were launched, but a thread that waited on the oldest while a younger one was done left that context idle)
@@ -294,7 +359,7 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 			for(uint32_t spins = 0; pick == p->depth && !err; spins++) {
 				for(uint32_t k = 0; k < p->depth; k++) {
 					Lane &C = mine[(n + k) % p->depth];
-					const int d = crthip_batch_done(C.batch);
+					const int d = crthip_batch_done(C.s[C.cur].batch);
 					if(d < 0) { err = d; break; }
 					if(d) { pick = (uint32_t)((n + k) % p->depth); break; }
 				}
@@ -306,29 +371,57 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 			const auto f0 = tick();
 			if(L.busy) err = finish(L);
 			finish_ns += ns_since(f0);
-			if(err) break;
-			const uint64_t step = p->next.fetch_add(1);
-			if(step >= total) break;
-			uint32_t j;
-			if(!home[slot].empty()) j = home[slot][home_next[slot].fetch_add(1) % home[slot].size()];
-			else j = (uint32_t)(stolen.fetch_add(1) % nitems);
-			const auto h0 = std::chrono::steady_clock::now();
-			err = lane_plan(p, L, items[j], (int64_t)j);
-			{ const uint64_t ns_ = ns_since(h0); plan_ns += ns_; raise_max(plan_max_ns, ns_); }
-			// the outputs every lane holds after the run were written by a step that STARTED from a poisoned block: the post-run bit-exact
-			// check cannot pass on bytes an earlier step left behind (on the context's own stream: ordered before the step's kernels)
-			L.poisoned = false;
-			if(!err && step >= poison_from && L.out) {
-				err = corto_hip::ctx_fill_async(L.ctx, L.out, L.out_cap, POISON);
-				if(!err && p->to_host && L.host_out) memset(L.host_out, POISON, L.out_used);
-				if(!err) L.poisoned = true;
+			if(!err && pipe && !L.staged && L.s[L.cur].item >= 0) L.pipe = corto_hip::batch_carriable(L.s[L.cur].batch);
+			if(!err && L.staged && L.drain) {                   // the planned batch was not carried: its whole decode alone, no ticket drawn
+				L.cur ^= 1u; L.staged = false; L.drain = false; L.pipe = false;
+				err = poison(L, L.s[L.cur].step >= poison_from);
+				if(!err) err = crthip_batch_decode_with_next(L.s[L.cur].batch, nullptr);
+				if(!err && p->to_host) err = corto_hip::ctx_copy_to_host_async(L.ctx, L.host_out, L.out, L.s[L.cur].out_used);
+				if(!err) L.busy = true;
 			}
-			const auto d0 = std::chrono::steady_clock::now();
-			if(!err) err = crthip_batch_decode(L.batch);
-			if(!err && p->to_host) err = corto_hip::ctx_copy_to_host_async(L.ctx, L.host_out, L.out, L.out_used);
-			raise_max(launch_max_ns, ns_since(d0));
-			host_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - h0).count(); host_steps++;
-			if(!err) { L.busy = true; L.step = step; }
+			// refill.  A pipelined lane plans the ticket on its free batch object and enqueues [mesh stage of the batch planned one refill ago + entropy
+			// stage of this one]; its first ticket of a run only enqueues an entropy stage, and it draws the next one at once.
+			while(!err && !L.busy) {
+				const uint64_t step = p->next.fetch_add(1);
+				if(step >= total) { tickets = false; break; }
+				uint32_t j;
+				if(!home[slot].empty()) j = home[slot][home_next[slot].fetch_add(1) % home[slot].size()];
+				else j = (uint32_t)(stolen.fetch_add(1) % nitems);
+				const auto h0 = std::chrono::steady_clock::now();
+				const bool lp = pipe && (L.pipe || L.staged);                          // this refill pipelines
+				const uint32_t t = lp ? (L.staged ? L.cur : L.cur ^ 1u) : L.cur;        // the free batch object
+				Slot &T = L.s[t];
+				err = lane_plan(p, L, T, items[j], (int64_t)j);
+				T.step = step;
+				{ const uint64_t ns_ = ns_since(h0); plan_ns += ns_; raise_max(plan_max_ns, ns_); }
+				if(err) break;
+				const auto d0 = std::chrono::steady_clock::now();
+				if(lp && !L.staged) {
+					err = crthip_batch_decode_with_next(nullptr, T.batch);
+					L.staged = !err;
+				} else {
+					const uint32_t m = lp ? L.cur ^ 1u : t;                              // whose mesh stage runs now
+					L.cur = m;
+					err = poison(L, L.s[m].step >= poison_from);
+					if(!err) err = lp ? crthip_batch_decode_with_next(L.s[m].batch, T.batch) : crthip_batch_decode(T.batch);
+					if(!err && lp) L.drain = !corto_hip::batch_entropy_done(T.batch);
+					if(!err && p->to_host) err = corto_hip::ctx_copy_to_host_async(L.ctx, L.host_out, L.out, L.s[m].out_used);
+					if(!err) L.busy = true;
+				}
+				raise_max(launch_max_ns, ns_since(d0));
+				host_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - h0).count(); host_steps++;
+			}
+		}
+		for(uint32_t k = 0; k < p->depth; k++) if(mine[k].busy) { const int e2 = finish(mine[k]); if(!err) err = e2; }
+		// no ticket left: the mesh stage of every lane's planned batch, alone
+		for(uint32_t k = 0; k < p->depth && !err; k++) {
+			Lane &L = mine[k];
+			if(!L.staged) continue;
+			L.cur ^= 1u; L.staged = false;
+			err = poison(L, L.s[L.cur].step >= poison_from);
+			if(!err) err = crthip_batch_decode_with_next(L.s[L.cur].batch, nullptr);
+			if(!err && p->to_host) err = corto_hip::ctx_copy_to_host_async(L.ctx, L.host_out, L.out, L.s[L.cur].out_used);
+			if(!err) L.busy = true;
 		}
 		for(uint32_t k = 0; k < p->depth; k++) if(mine[k].busy) { const int e2 = finish(mine[k]); if(!err) err = e2; }
 		// a context whose thread drew none of the last 2 x lanes tickets (descheduled while the others emptied the queue: seen with
@@ -336,17 +429,17 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 		// a poisoned step's output, not only almost always
 		for(uint32_t k = 0; k < p->depth && !err; k++) {
 			Lane &L = mine[k];
-			if(L.item < 0) {                                     // ... and one that drew no ticket at all (a 28-step run on a cold box) decodes its device's first item
+			Slot &S = L.s[L.cur];
+			if(S.item < 0) {                                     // ... and one that drew no ticket at all (a 28-step run on a cold box) decodes its device's first item
 				const uint32_t j = home[slot].empty() ? 0u : home[slot][0];
-				err = lane_plan(p, L, items[j], (int64_t)j);
+				err = lane_plan(p, L, S, items[j], (int64_t)j);
 				if(err) break;
 			}
 			if(L.poisoned || !L.out) continue;
-			err = corto_hip::ctx_fill_async(L.ctx, L.out, L.out_cap, POISON);
-			if(!err && p->to_host && L.host_out) memset(L.host_out, POISON, L.out_used);
-			if(!err) err = crthip_batch_decode(L.batch);
-			if(!err && p->to_host) err = corto_hip::ctx_copy_to_host_async(L.ctx, L.host_out, L.out, L.out_used);
-			if(!err) { L.busy = true; L.poisoned = true; err = finish(L); }
+			err = poison(L, true);
+			if(!err) err = crthip_batch_decode(S.batch);
+			if(!err && p->to_host) err = corto_hip::ctx_copy_to_host_async(L.ctx, L.host_out, L.out, S.out_used);
+			if(!err) { L.busy = true; err = finish(L); }
 		}
 		if(err) {
 			std::lock_guard<std::mutex> lock(p->m);
@@ -363,7 +456,7 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 	report->steps = steps; report->triangles = tris; report->vertices = verts;
 	report->failed_blobs = failed; report->first_error = first_error; report->topology_fallbacks = fallbacks;
 	for(uint32_t d = 0; d < p->ndevices; d++) { report->steps_per_device[d] = per_dev[d]; if(per_dev[d]) report->devices_used++; }
-	for(auto &L : p->lanes) if(L.item >= 0 && L.poisoned) report->poisoned_lanes++;
+	for(auto &L : p->lanes) if(L.s[L.cur].item >= 0 && L.poisoned) report->poisoned_lanes++;
 	report->host_us_per_step = host_steps ? (float)((double)host_ns/1e3/(double)host_steps) : 0.f;
 	if(host_steps) {
 		report->host_wait_us = (float)((double)wait_ns/1e3/(double)host_steps); report->host_finish_us = (float)((double)finish_ns/1e3/(double)host_steps);
@@ -378,24 +471,25 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 extern "C" int64_t crthip_pool_lane_item(const crthip_pool *p, uint32_t lane, uint32_t *device_slot) {
 	if(!p || lane >= p->lanes.size()) return ctx_fail(CRTHIP_E_ARGUMENT, nullptr);
 	if(device_slot) *device_slot = p->lanes[lane].slot;
-	return p->lanes[lane].item;
+	return p->lanes[lane].s[p->lanes[lane].cur].item;           // (a pipelined lane: the batch whose mesh stage ran last)
 }
 
 extern "C" int64_t crthip_pool_lane_read(crthip_pool *p, uint32_t lane, uint32_t blob, const char *what, void *host_out, size_t cap) {
 	if(!p || lane >= p->lanes.size() || !what || !host_out) return ctx_fail(CRTHIP_E_ARGUMENT, nullptr);
 	Lane &L = p->lanes[lane];
-	if(!L.batch || L.item < 0 || blob >= crthip_batch_size(L.batch)) return ctx_fail(CRTHIP_E_ARGUMENT, nullptr);
+	Slot &S = L.s[L.cur];                                        // (a pipelined lane: the batch whose mesh stage ran last)
+	if(!S.batch || S.item < 0 || blob >= crthip_batch_size(S.batch)) return ctx_fail(CRTHIP_E_ARGUMENT, nullptr);
 	crthip_blob_info info;
-	int err = crthip_batch_info(L.batch, blob, &info);
+	int err = crthip_batch_info(S.batch, blob, &info);
 	if(err) return err;
 	const uint8_t *src = nullptr; size_t n = 0;
 	if(!strcmp(what, "#tail")) { n = L.out_cap < 256 ? L.out_cap : 256; src = (const uint8_t *)L.out + (L.out_cap - n); }   // the block's last bytes: behind every output array
-	else if(!strcmp(what, "index")) { if(!info.nface) return 0; src = (const uint8_t *)L.index_ptr[blob]; n = (size_t)info.nface*(L.index_fmt[blob] == CRTHIP_FMT_UINT16 ? 6 : 12); }
+	else if(!strcmp(what, "index")) { if(!info.nface) return 0; src = (const uint8_t *)S.index_ptr[blob]; n = (size_t)info.nface*(S.index_fmt[blob] == CRTHIP_FMT_UINT16 ? 6 : 12); }
 	else {
 		for(uint32_t k = 0; k < info.nattr; k++) if(!strcmp(info.attr[k].name, what)) {
 			const crthip_attr_info &a = info.attr[k];
-			src = (const uint8_t *)L.binds[L.first_attr[blob] + k].buffer;
-			n = a.codec == CRTHIP_CODEC_NORMAL ? (size_t)info.nvert*(L.binds[L.first_attr[blob] + k].format == CRTHIP_FMT_INT16 ? 6 : 12) : a.codec == CRTHIP_CODEC_COLOR ? (size_t)info.nvert*4 : (size_t)info.nvert*a.components*4;
+			src = (const uint8_t *)S.binds[S.first_attr[blob] + k].buffer;
+			n = a.codec == CRTHIP_CODEC_NORMAL ? (size_t)info.nvert*(S.binds[S.first_attr[blob] + k].format == CRTHIP_FMT_INT16 ? 6 : 12) : a.codec == CRTHIP_CODEC_COLOR ? (size_t)info.nvert*4 : (size_t)info.nvert*a.components*4;
 		}
 		if(!src) return ctx_fail(CRTHIP_E_ARGUMENT, "no such attribute");
 	}

@@ -24,8 +24,25 @@ __shared__ __attribute__((aligned(16))) uint8_t g_tun_words[TUN_TABLE_BYTES];   
 // kernel's LDS is the 6.4 KB of the growth bookkeeping instead of 15.6 KB (its LDS.time is what a batch's ~250 dictionaries cost the
 // pipelined decode).  Bigger alphabets copy parents' bytes: they use `big_words`, 9 KB of dynamic LDS the host adds to the
 // launch when a stream of the launch has more than 64 symbols.
-template <bool WORDS_TO_HBM = false>
-__device__ __forceinline__ TunBuilt tun_tables_body(const TunStream &st, TunTable *Tg, uint16_t *loff, uint8_t *llen, const uint8_t *probs_override = nullptr, uint8_t *big_words = nullptr) {
+// The growth bookkeeping (6.4 KB).  A kernel of its own keeps it in static LDS; a kernel that CARRIES dictionaries beside other work
+// (k_front: the next batch's K-TAB behind this batch's automata, whose records must stay at LDS address 0) hands in `grow`, a piece of its
+// dynamic block, and declares nothing static.
+struct TunGrow {
+	uint32_t epl[TUN_ENTRY_CAP];     // entry e (creation order) lives in FIFO row e % n.  Low half: its probability, 16-bit ((a*b) >> 16 of 16-bit
+	                                 // factors); high half: its length (n <= 64: | last symbol << 8) - one LDS read serves both
+	uint16_t eoff[TUN_ENTRY_CAP];
+	uint16_t head[256];              // oldest not-yet-expanded entry of each row
+	uint16_t P[256];                 // probability << 8  (16.16-ish fixed point)
+	uint16_t pw[256];                // P0^k (successive (a*b)>>16), low-entropy seed only
+	uint8_t sym[256];
+};
+constexpr uint32_t TUN_GROW_BYTES = (uint32_t)sizeof(TunGrow);
+template <bool CARVED> __device__ __forceinline__ TunGrow *tun_grow_state(uint8_t *grow) {
+	if constexpr(CARVED) return (TunGrow *)grow;
+	else { __shared__ __attribute__((aligned(16))) TunGrow g; return &g; }
+}
+template <bool WORDS_TO_HBM = false, bool CARVED = false>
+__device__ __forceinline__ TunBuilt tun_tables_body(const TunStream &st, TunTable *Tg, uint16_t *loff, uint8_t *llen, const uint8_t *probs_override = nullptr, uint8_t *big_words = nullptr, uint8_t *grow = nullptr) {
 	const uint8_t *probs = probs_override ? probs_override : st.probs;   // nsym x (symbol, probability), sorted as stored in the stream
 	TunTable &T = *Tg;                           // (only touched when Tg != null)
 	const bool to_hbm = WORDS_TO_HBM && st.nsym <= 64;
@@ -35,13 +52,8 @@ __device__ __forceinline__ TunBuilt tun_tables_body(const TunStream &st, TunTabl
 	const uint32_t n = st.nsym;                 // 2..255 (host guarantees)
 	const uint32_t lane = threadIdx.x;
 
-	__shared__ uint32_t epl[TUN_ENTRY_CAP];     // entry e (creation order) lives in FIFO row e % n.  Low half: its probability, 16-bit ((a*b) >> 16 of 16-bit
-	                                            // factors); high half: its length (n <= 64: | last symbol << 8) - one LDS read serves both
-	__shared__ uint16_t eoff[TUN_ENTRY_CAP];
-	__shared__ uint16_t head[256];              // oldest not-yet-expanded entry of each row
-	__shared__ uint16_t P[256];                 // probability << 8  (16.16-ish fixed point)
-	__shared__ uint16_t pw[256];                // P0^k (successive (a*b)>>16), low-entropy seed only
-	__shared__ uint8_t sym[256];
+	TunGrow &G = *tun_grow_state<CARVED>(grow);
+	uint32_t *const epl = G.epl; uint16_t *const eoff = G.eoff, *const head = G.head, *const P = G.P, *const pw = G.pw; uint8_t *const sym = G.sym;
 
 	TUN_STAMP(0);
 	for(uint32_t i = lane; i < n; i += 64) { sym[i] = probs[2*i]; P[i] = (uint32_t)probs[2*i + 1] << 8; }

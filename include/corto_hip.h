@@ -40,7 +40,8 @@ extern "C" {
                                   6: crthip_pool_set_render_layouts, crthip_kernel_times names are the kernels' (unpack_wave, delta_lds16);
                                      added within 6: crthip_generic_attr, crthip_attr_list, crthip_encode_attrs, crthip_encode_gpu_attrs,
                                      crthip_encode_batch_attrs, crthip_batch_create_resident, crthip_batch_reset_resident, crthip_batch_exif,
-                                     crthip_batch_groups, crthip_batch_group_props, crthip_batch_walk_stats */
+                                     crthip_batch_groups, crthip_batch_group_props, crthip_batch_walk_stats, crthip_batch_decode_with_next,
+                                     crthip_batch_set_parity */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -216,6 +217,20 @@ int crthip_batch_bind_all(crthip_batch *b, const crthip_attr_binding *attrs, voi
 
 /* Enqueue the whole decode of the batch on the context's stream (asynchronous). */
 int crthip_batch_decode(crthip_batch *b);
+/* A lane that decodes a STREAM of batches on one context, pipelined over two of them: the decode of a batch has an entropy stage (the
+ * Tunstall dictionaries and streams: reads the blobs, writes only the batch's own scratch) and a mesh stage (everything that writes the
+ * bound outputs and the status), and this call enqueues the mesh stage of `cur` together with the entropy stage of `next` - where both
+ * batches allow it INSIDE cur's kernels' grids, which leave most of the GPU empty, so that it costs the stream no time of its own (a pool's
+ * contexts share a few hardware queues, and a queue runs one kernel at a time).  `next` is planned here like any decode (create / reset and
+ * bind it first); `cur` must have been `next` of the call before.  next == NULL: cur's mesh stage alone (the last batch; crthip_batch_decode(cur)
+ * does the same); cur == NULL: next's entropy stage alone (the first).  crthip_batch_sync / _done (cur) cover everything the call enqueued.
+ * Two batch objects are alive on the context, so they must not share its per-call blocks: give one of them parity 1 (crthip_batch_set_parity,
+ * once, before it is filled: create it with no blobs, set, then crthip_batch_reset).  Outputs, statuses and statistics are those of
+ * crthip_batch_decode; what a context learns from a batch's flags (LDS slots of the automaton, the 32-bit delta layout) reaches the batch after
+ * the next one.  $CORTO_CARRY=0: the entropy stage is enqueued as launches of its own. */
+int crthip_batch_decode_with_next(crthip_batch *cur, crthip_batch *next);
+/* Which of the context's two sets of per-call blocks (arena image, descriptors, scratch, status) the object uses: 0 (default) or 1. */
+int crthip_batch_set_parity(crthip_batch *b, uint32_t parity);
 /* Wait for completion and collect per-blob status: status[i] = CRTHIP_OK or CRTHIP_E_* (may be NULL).
  * Returns CRTHIP_OK if every blob decoded, else the first failing blob's code. */
 int crthip_batch_sync(crthip_batch *b, int32_t *status);
