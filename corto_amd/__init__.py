@@ -183,6 +183,10 @@ def lib():
         L.crthip_encode_attrs.argtypes = [C.POINTER(MeshDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.crthip_encode_gpu_attrs.restype = C.c_int64
         L.crthip_encode_gpu_attrs.argtypes = [C.c_void_p, C.POINTER(MeshDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.crthip_encode_batch_resident.restype = C.c_int64
+        L.crthip_encode_batch_resident.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.crthip_encode_input_model.argtypes = [C.POINTER(MeshDesc), C.c_int, C.c_void_p]
         L.crthip_encode_batch_attrs.restype = C.c_int64
         L.crthip_encode_batch_attrs.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -276,49 +280,62 @@ _ATTR_FMT = {np.dtype(np.float32): FMT_FLOAT, np.dtype(np.float64): FMT_DOUBLE, 
              np.dtype(np.uint16): FMT_UINT16, np.dtype(np.uint8): FMT_UINT8}
 
 
-def _attr_list(attributes, nvert):
-    """crthip_attr_list of [(name, array (nvert, N), q, strategy), ...] (None: no list), and the objects it points into."""
+def _host_ptr(a):
+    return a.ctypes.data
+
+
+def _attr_list(attributes, nvert, ptr=None):
+    """crthip_attr_list of [(name, array (nvert, N), q, strategy), ...] (None: no list), and the objects it points into.
+    ptr: the address of an array; None: numpy arrays in host memory, else the arrays are taken as they are (device tensors)."""
     if attributes is None:
         return None, []
     attributes = list(attributes)
     arr = (GenericAttrDesc * max(len(attributes), 1))()
     keep = [arr]
     for k, (name, values, q, strategy) in enumerate(attributes):
-        v = np.ascontiguousarray(values)
+        v = np.ascontiguousarray(values) if ptr is None else values
         if v.ndim == 1:
             v = v.reshape(-1, 1)
         if v.ndim != 2 or v.shape[0] != nvert:
-            raise ValueError("attribute %r: expected an array of shape (%d, N), got %s" % (name, nvert, v.shape))
+            raise ValueError("attribute %r: expected an array of shape (%d, N), got %s" % (name, nvert, tuple(v.shape)))
         nm = name.encode() if isinstance(name, str) else bytes(name)
         keep += [v, nm]
         d = arr[k]
-        d.name = nm; d.values = v.ctypes.data if v.size else None
-        d.format = _ATTR_FMT.get(v.dtype, 0xFFFFFFFF); d.components = v.shape[1]; d.q = q; d.strategy = strategy
+        if ptr is None:
+            d.name = nm; d.values = v.ctypes.data if v.size else None
+            d.format = _ATTR_FMT.get(v.dtype, 0xFFFFFFFF)
+        else:
+            if not v.is_contiguous():
+                raise ValueError("attribute %r: the device array must be contiguous" % (name,))
+            d.name = nm; d.values = ptr(v) if v.numel() else None
+            d.format = _ATTR_FMT.get(np.dtype(str(v.dtype).replace("torch.", "")), 0xFFFFFFFF)
+        d.components = v.shape[1]; d.q = q; d.strategy = strategy
     lst = AttrList(len(attributes), C.cast(arr, C.c_void_p).value)
     keep.append(lst)
     return lst, keep
 
 
 def _mesh_desc(mesh, position_bits=14, position_q=0.0, normal_bits=10, normal_prediction=BORDER, color_bits=(6, 7, 6, 5),
-               uv_bits=12, radius_q=1.0, entropy=1, exif=None, with_normal=True, with_color=True, with_uv=True):
-    """crthip_mesh of a corto_amd.synth.Mesh, and the Python objects it points into (keep them alive while it is used)."""
+               uv_bits=12, radius_q=1.0, entropy=1, exif=None, with_normal=True, with_color=True, with_uv=True, ptr=_host_ptr):
+    """crthip_mesh of a corto_amd.synth.Mesh, and the Python objects it points into (keep them alive while it is used).
+    ptr: the address of a data array (numpy arrays in host memory; encode_batch_resident passes a device tensor's data_ptr)."""
     m = MeshDesc()
     m.nvert, m.nface = mesh.nvert, mesh.nface
     keep = []
-    m.position = mesh.position.ctypes.data
+    m.position = ptr(mesh.position)
     if mesh.index is not None:
-        m.index = mesh.index.ctypes.data
+        m.index = ptr(mesh.index)
     m.position_bits, m.position_q = position_bits, position_q
     if with_normal and mesh.normal is not None:
-        m.normal = mesh.normal.ctypes.data; m.normal_bits = normal_bits; m.normal_prediction = normal_prediction
+        m.normal = ptr(mesh.normal); m.normal_bits = normal_bits; m.normal_prediction = normal_prediction
     if with_color and mesh.color is not None:
-        m.color = mesh.color.ctypes.data; m.color_components = mesh.color.shape[1]
+        m.color = ptr(mesh.color); m.color_components = mesh.color.shape[1]
         for k in range(4):
             m.color_bits[k] = color_bits[k]
     if with_uv and mesh.uv is not None:
-        m.uv = mesh.uv.ctypes.data; m.uv_q = float(np.float32(2.0) ** np.float32(-uv_bits))
+        m.uv = ptr(mesh.uv); m.uv_q = float(np.float32(2.0) ** np.float32(-uv_bits))
     if mesh.radius is not None:
-        m.radius = mesh.radius.ctypes.data; m.radius_q = radius_q
+        m.radius = ptr(mesh.radius); m.radius_q = radius_q
     if mesh.groups is not None:
         g = np.ascontiguousarray(mesh.groups, dtype=np.uint32); keep.append(g)
         m.group_end = g.ctypes.data; m.ngroups = len(g)
@@ -414,11 +431,93 @@ def encode_topology_model(mesh, which, **kw):
                 max_front=int(r.max_front), split_bits=int(r.split_bits), lds=int(r.lds))
 
 
-def encode_batch(meshes, ctx, kw=None, host_threads=0, raise_on_error=True, with_stats=False):
+class EncodeInputResult(C.Structure):
+    """crthip_encode_input_result"""
+    _fields_ = [("index_out_of_range", C.c_uint32), ("recipe", C.c_uint32), ("mn", C.c_float * 3), ("mx", C.c_float * 3),
+                ("sum", C.c_double), ("step", C.c_float), ("reserved", C.c_uint32)]
+
+
+def encode_input_model(mesh, which, **kw):
+    """What the encoder reads from a mesh's arrays before it quantises (crthip_encode_input_model): which = 0 the host encoder's own
+    loops, which = 1 the source the kernels of encode_batch_resident run, on the host in the kernels' partition.  kw: encode()'s
+    keywords.  Returns a dict: index_out_of_range, recipe, mn and mx (float32 arrays of 3), sum (np.float64) and step (np.float32)."""
+    m, keep = _mesh_desc(mesh, **kw)
+    r = EncodeInputResult()
+    _check(lib().crthip_encode_input_model(C.byref(m), int(which), C.byref(r)))
+    return dict(index_out_of_range=int(r.index_out_of_range), recipe=int(r.recipe), mn=np.array(r.mn, dtype=np.float32),
+                mx=np.array(r.mx, dtype=np.float32), sum=np.float64(r.sum), step=np.float32(r.step))
+
+
+class DeviceMesh:
+    """A corto_amd.synth.Mesh whose data arrays are device tensors (mesh_to_device); groups and their properties stay on the host."""
+
+    def __init__(self, position, index=None, normal=None, color=None, uv=None, radius=None, groups=None, group_props=None):
+        self.position, self.index, self.normal, self.color, self.uv, self.radius = position, index, normal, color, uv, radius
+        self.groups, self.group_props = groups, group_props
+
+    @property
+    def nvert(self):
+        return self.position.shape[0]
+
+    @property
+    def nface(self):
+        return 0 if self.index is None else self.index.shape[0]
+
+
+def _to_device(a, device):
+    import torch
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.uint32:                         # (torch has no arithmetic on uint32: the bits travel as int32)
+        a = a.view(np.int32)
+    return torch.from_numpy(a).to(torch.device("cuda", device))
+
+
+def mesh_to_device(mesh, device=0):
+    """A copy of a corto_amd.synth.Mesh with its data arrays in the memory of `device` (a DeviceMesh), for encode_batch_resident."""
+    f = lambda a: None if a is None else _to_device(a, device)
+    d = DeviceMesh(f(mesh.position), f(mesh.index), f(mesh.normal), f(mesh.color), f(mesh.uv), f(mesh.radius), mesh.groups,
+                   getattr(mesh, "group_props", None))
+    _torch_ready(d.position.device)
+    return d
+
+
+def attributes_to_device(attributes, device=0):
+    """encode()'s `attributes` list with its arrays in the memory of `device`"""
+    if attributes is None:
+        return None
+    out = [(name, _to_device(values, device), q, strategy) for name, values, q, strategy in attributes]
+    import torch
+    _torch_ready(torch.device("cuda", device))
+    return out
+
+
+def encode_batch_resident(meshes, ctx, kw=None, host_threads=0, raise_on_error=True, with_stats=False):
+    """encode_batch for meshes whose data arrays live in device memory (crthip_encode_batch_resident): objects like corto_amd.synth.Mesh
+    whose position / index / normal / color / uv / radius - and the arrays of kw's `attributes` - are contiguous device tensors of the
+    context's device (anything with data_ptr(): mesh_to_device, attributes_to_device).  Nothing is copied to the host but, for meshes whose
+    topology pass runs there, the index.  Same bytes and same return values as encode_batch."""
+    meshes = list(meshes)
+    null = []
+
+    def ptr(t):
+        if t.numel():
+            if not t.is_contiguous():
+                raise ValueError("encode_batch_resident: device arrays must be contiguous")
+            return t.data_ptr()
+        if not null:                                 # an empty array has no address: any device word stands for it (it is never read)
+            import torch
+            null.append(torch.zeros(4, dtype=torch.int32, device=t.device))
+        return null[0].data_ptr()
+
+    _torch_ready(ctx.device)                         # (what torch queued on the arrays runs on its stream; the encoder on the context's own)
+    return encode_batch(meshes, ctx, kw=kw, host_threads=host_threads, raise_on_error=raise_on_error, with_stats=with_stats, _ptr=ptr)
+
+
+def encode_batch(meshes, ctx, kw=None, host_threads=0, raise_on_error=True, with_stats=False, _ptr=None):
     """.crt blobs of a batch of corto_amd.synth.Mesh in one crthip_encode_batch: each byte-identical to encode(mesh, **kw).
     kw: one dict of encode()'s keywords for all meshes, or one per mesh (`attributes` included: crthip_encode_batch_attrs).  Returns the list of uint8 blobs (empty for a mesh
     that failed); with raise_on_error=False also the per-mesh status codes; with_stats=True also a dict of the call's
-    statistics and per-kernel times."""
+    statistics and per-kernel times.  (_ptr: encode_batch_resident's pointer getter.)"""
     meshes = list(meshes)
     n = len(meshes)
     if kw is None:
@@ -437,12 +536,12 @@ def encode_batch(meshes, ctx, kw=None, host_threads=0, raise_on_error=True, with
     for i, (mesh, k) in enumerate(zip(meshes, kws)):
         k = dict(k)
         attributes = k.pop("attributes", None)
-        descs[i], kp = _mesh_desc(mesh, **k)
+        descs[i], kp = _mesh_desc(mesh, **k) if _ptr is None else _mesh_desc(mesh, ptr=_ptr, **k)
         keep.append(kp)
         if attributes is not None:
-            lst, ka = _attr_list(attributes, mesh.nvert)
+            lst, ka = _attr_list(attributes, mesh.nvert, _ptr)
             lists[i] = lst; keep.append(ka); with_attrs = True
-            extra_bytes += sum(8 * np.asarray(a[1]).size for a in attributes)
+            extra_bytes += sum(8 * int(np.prod(a[1].shape)) for a in attributes) if _ptr is not None else sum(8 * np.asarray(a[1]).size for a in attributes)
     offs = np.zeros(n + 1, dtype=np.uint64)
     status = np.zeros(max(n, 1), dtype=np.int32)
     st = EncodeBatchStats()
@@ -450,7 +549,10 @@ def encode_batch(meshes, ctx, kw=None, host_threads=0, raise_on_error=True, with
     cap = sum(64 * (m.nvert + m.nface) + 65536 for m in meshes) + extra_bytes
     for _ in range(2):
         out = np.zeros(cap + 16, dtype=np.uint8)
-        if with_attrs:
+        if _ptr is not None:
+            r = lib().crthip_encode_batch_resident(ctx.handle, n, descs, lists if with_attrs else None, host_threads, _np_ptr(out), cap,
+                                                   _np_ptr(offs), None, None, _np_ptr(status), C.byref(st), C.byref(t))
+        elif with_attrs:
             r = lib().crthip_encode_batch_attrs(ctx.handle, n, descs, lists, host_threads, _np_ptr(out), cap, _np_ptr(offs), None, None,
                                                 _np_ptr(status), C.byref(st), C.byref(t))
         else:

@@ -10,6 +10,11 @@
 // encode_value_streams_device).  The host splices every container from its frame and the coded streams (encoder_internal.h:
 // splice_container).  One device image per chunk of the batch; no allocation per mesh or per stream.
 //
+// crthip_encode_batch_resident is the same path for data arrays that live in device memory: the pointers are vouched for by the runtime
+// (resident_check), what the host would have read through them comes from K-ENC-CHECK (input_pass: k_encode_check.hip), the quantiser
+// and the device topology pass read the caller's arrays in place, and only the index of a mesh the host pool walks comes back
+// (fetch_indices).
+//
 // How the file is laid out: ChunkImage / build_image say where everything lives in a chunk's device image (the one place that does: the
 // chunker sizes a chunk by building its image); Chunk is what every stage works on; the stages follow, one function each, in the order
 // encode_chunk calls them.  Each stage's comment names the regions of the image it reads (R) and writes (W) and says whether it returns
@@ -103,12 +108,14 @@ struct ChunkImage {
 	uint64_t zero = 0, zflags = 0, back = 0, mquads = 0, faces = 0, ck[2] = {0, 0}, cv[2] = {0, 0}, chist = 0, spack = 0, jobs = 0, total = 0;
 	uint64_t staged_total = 0, zero_bytes = 0, back_bytes = 0, mquads_bytes = 0, split_cap_total = 0;
 	uint32_t faces_total = 0, corners_total = 0;
+	bool resident = false;                // crthip_encode_batch_resident: the caller's arrays are read where they are - raw holds the group ends alone
 	uint64_t rec(size_t j) const { return back + 256 + j*sizeof(EncTopoRecord); }   // the record of mesh devk[j]
 };
 
 // The image of items[ids], without touching the device.  Every region starts on 256 bytes unless it says otherwise.
-ChunkImage build_image(const crthip_mesh *meshes, const std::vector<BatchItem> &items, std::vector<uint32_t> ids) {
+ChunkImage build_image(const crthip_mesh *meshes, const std::vector<BatchItem> &items, std::vector<uint32_t> ids, bool resident) {
 	ChunkImage L;
+	L.resident = resident;
 	Carver c;
 	auto here = [&] { return c.take(0); };                  // where the next region starts
 	const uint32_t n = (uint32_t)ids.size();
@@ -122,18 +129,19 @@ ChunkImage build_image(const crthip_mesh *meshes, const std::vector<BatchItem> &
 		(it.topo_device ? L.devk : L.hostk).push_back(k);
 		if(!is_mesh(it)) L.clouds.push_back(k);
 		s.in.resize(it.attrs.size()); s.q.resize(it.attrs.size()); s.d.resize(it.attrs.size());
-		for(size_t a = 0; a < it.attrs.size(); a++) { L.raw.push_back(RawIn{it.attrs[a].quant.in, quant_in_bytes(it.attrs[a].quant), 0}); raw_off.push_back(&s.in[a]); }
+		if(!resident) for(size_t a = 0; a < it.attrs.size(); a++) { L.raw.push_back(RawIn{it.attrs[a].quant.in, quant_in_bytes(it.attrs[a].quant), 0}); raw_off.push_back(&s.in[a]); }
 		if(it.topo_device) {
 			const crthip_mesh &m = meshes[L.ids[k]];
-			L.raw.push_back(RawIn{m.index, (uint64_t)it.nface_in*12, 0}); raw_off.push_back(&s.idx);
+			if(!resident) { L.raw.push_back(RawIn{m.index, (uint64_t)it.nface_in*12, 0}); raw_off.push_back(&s.idx); }
 			L.raw.push_back(RawIn{m.ngroups ? (const void *)m.group_end : (const void *)&it.nface_in, (uint64_t)it.topo_groups*4, 0}); raw_off.push_back(&s.gend_in);
 		}
 		job_bytes += it.attrs.size()*(sizeof(QuantJob) + sizeof(DeltaEncJob) + sizeof(EstJob) + 8) + 16 + (it.topo_device ? sizeof(EncTopoJob) + 8 : 0);
 	}
 	// INVARIANT: the raw inputs below DIRECT_BYTES are contiguous at the front of the image - they go up staged, in one copy of
 	// staged_total bytes from offset 0 - and the large ones follow
+	// (a resident call's are the group ends alone: words, packed)
 	for(int big = 0; big < 2; big++)
-		for(size_t i = 0; i < L.raw.size(); i++) if((L.raw[i].bytes >= DIRECT_BYTES) == (big == 1)) *raw_off[i] = L.raw[i].off = c.take(L.raw[i].bytes);
+		for(size_t i = 0; i < L.raw.size(); i++) if((L.raw[i].bytes >= DIRECT_BYTES) == (big == 1)) *raw_off[i] = L.raw[i].off = c.take(L.raw[i].bytes, resident ? 4 : 256);
 	for(const RawIn &r : L.raw) if(r.bytes < DIRECT_BYTES) L.staged_total = std::max(L.staged_total, r.off + r.bytes);
 	// INVARIANT: the zeroed words (BORDER XORs, counts, cloud minima), the clouds' flags and the device topology pass's report are
 	// contiguous - one memset of zero_bytes from `zero` - and the report is one block: it comes back in one copy of back_bytes from `back`
@@ -206,8 +214,8 @@ uint64_t clers_layout(const std::vector<BatchItem> &items, const ChunkImage &img
 // ---- what every stage works on ----
 
 // the batch's kernels as crthip_kernel_times names them, in the order they are reported; up to K_STAGES one timer per chunk, then one per cloud
-enum { K_QUANT, K_TOPO_C, K_TOPO_P, K_TOPO_W, K_EST, K_DELTA, K_STAGES, K_ZKEYS = K_STAGES, K_ZSORT, K_COUNT };
-const char *const KERNEL_NAME[K_COUNT] = {"enc_quantize_batch", "enc_topo_compact", "enc_topo_pair", "enc_topo_walk", "enc_est_normal", "enc_delta", "enc_zkeys", "enc_zsort"};
+enum { K_IN_CHECK, K_IN_REDUCE, K_QUANT, K_TOPO_C, K_TOPO_P, K_TOPO_W, K_EST, K_DELTA, K_STAGES, K_ZKEYS = K_STAGES, K_ZSORT, K_COUNT };
+const char *const KERNEL_NAME[K_COUNT] = {"enc_input_check", "enc_input_reduce", "enc_quantize_batch", "enc_topo_compact", "enc_topo_pair", "enc_topo_walk", "enc_est_normal", "enc_delta", "enc_zkeys", "enc_zsort"};
 struct BatchTimes { float ms[K_COUNT] = {}; uint32_t launches[K_COUNT] = {}; };
 struct Event {
 	hipEvent_t e = nullptr;
@@ -236,10 +244,13 @@ struct Chunk {
 	Event ev_back;                                           // behind the copy of the device topology pass's report into `back`
 	std::vector<uint8_t> back = std::vector<uint8_t>(img.back_bytes);
 	Clock::time_point t_dtopo;
+	// a resident call: every item's descriptor again, with the index of a mesh the host pool walks pointing into host_index (fetch_indices)
+	std::vector<crthip_mesh> shadow;
+	std::vector<uint32_t> host_index;
 
 	uint32_t n() const { return (uint32_t)img.ids.size(); }
 	BatchItem &item(uint32_t k) const { return items[img.ids[k]]; }
-	const crthip_mesh *mesh(uint32_t k) const { return &meshes[img.ids[k]]; }
+	const crthip_mesh *mesh(uint32_t k) const { return shadow.empty() ? &meshes[img.ids[k]] : &shadow[k]; }
 	const crthip_attr_list *attrs(uint32_t k) const { return extra ? &extra[img.ids[k]] : nullptr; }
 	template <class T> T *at(uint64_t off) const { return (T *)(base + off); }
 	hipError_t sync() { const auto t0 = Clock::now(); const hipError_t e = hipStreamSynchronize(st); S.sync_wait_ms += ms_since(t0); return e; }
@@ -299,6 +310,29 @@ int radix_sort(hipStream_t st, K *k0, uint32_t *v0, K *k1, uint32_t *v1, uint32_
 
 // ---- the stages, in the order encode_chunk runs them ----
 
+// A resident call's meshes whose topology pass runs on the host pool (hostk) need their index there: one copy each into one host
+// buffer, one wait, and the pool works on descriptors whose index is that copy.  Attributes never come back.  R: the caller's index
+// arrays.  Synchronised on every way out (the buffer is the chunk's, the copies are queued).
+int fetch_indices(Chunk &C) {
+	struct Wait { hipStream_t st; ~Wait() { (void)hipStreamSynchronize(st); } } wait{C.st};
+	std::vector<uint64_t> at(C.n(), 0);
+	uint64_t words = 0;
+	for(uint32_t k : C.img.hostk) if(is_mesh(C.item(k))) { at[k] = words; words += (uint64_t)C.item(k).nface_in*3; }
+	C.host_index.resize(words);
+	std::vector<crthip_mesh> shadow(C.n());
+	for(uint32_t k = 0; k < C.n(); k++) shadow[k] = C.meshes[C.img.ids[k]];
+	for(uint32_t k : C.img.hostk) {
+		if(!is_mesh(C.item(k))) continue;
+		const uint64_t bytes = (uint64_t)C.item(k).nface_in*12;
+		ENC_TRY(hipMemcpyAsync(C.host_index.data() + at[k], shadow[k].index, bytes, hipMemcpyDeviceToHost, C.st));
+		shadow[k].index = C.host_index.data() + at[k];
+		C.S.bytes_from_device += bytes;
+	}
+	if(words) ENC_TRY(C.sync());
+	C.shadow.swap(shadow);
+	return 0;
+}
+
 // Raw inputs up: small ones staged into one copy, large ones straight from the caller; then the zeroed block is cleared.
 // W: every raw input (slot.in, idx, gend_in), [zero, zero + zero_bytes).  Synchronised after the copies (the staging buffer is a local);
 // the memset is left queued.
@@ -320,7 +354,7 @@ int upload_inputs(Chunk &C) {
 	return 0;
 }
 
-// K-ENC-Q: every attribute of every item in one launch.  R: slot.in.  W: slot.q, job tables.  Not synchronised.
+// K-ENC-Q: every attribute of every item in one launch.  R: slot.in (a resident call: the caller's arrays).  W: slot.q, job tables.  Not synchronised.
 int stage_quantise(Chunk &C) {
 	std::vector<QuantJob> qj; std::vector<uint32_t> start;
 	uint32_t blocks = 0;
@@ -329,7 +363,7 @@ int stage_quantise(Chunk &C) {
 		for(size_t a = 0; a < it.attrs.size(); a++) {
 			const QuantRequest &r = it.attrs[a].quant;
 			if(!r.count) continue;
-			qj.push_back(quant_job(r, C.base + C.img.slot[k].in[a], C.base + C.img.slot[k].q[a])); start.push_back(blocks); blocks += (r.count + 255)/256;
+			qj.push_back(quant_job(r, C.img.resident ? r.in : C.base + C.img.slot[k].in[a], C.base + C.img.slot[k].q[a])); start.push_back(blocks); blocks += (r.count + 255)/256;
 		}
 	}
 	if(qj.empty()) return 0;
@@ -343,7 +377,7 @@ int stage_quantise(Chunk &C) {
 }
 
 // K-ENC-TOPO: the topology pass of the meshes in devk, behind the quantiser; their report starts back at once.
-// R: slot.idx, gend_in.  W: faces, slot.quads, clers, gend_out, the records and the split cursor (the report), spack, the pass's scratch
+// R: slot.idx (a resident call: the caller's index), gend_in.  W: faces, slot.quads, clers, gend_out, the records and the split cursor (the report), spack, the pass's scratch
 // (first, cursor, sides, twin, state, split), job tables.  Not synchronised: ev_back says when the report is in C.back.
 int stage_topology(Chunk &C) {
 	C.t_dtopo = Clock::now();
@@ -358,7 +392,7 @@ int stage_topology(Chunk &C) {
 		const Slot &s = C.img.slot[C.img.devk[j]];
 		EncTopoJob &J = tj[j];
 		memset(&J, 0, sizeof(J));
-		J.index = C.at<const uint32_t>(s.idx); J.gend_in = C.at<const uint32_t>(s.gend_in);
+		J.index = C.img.resident ? C.mesh(C.img.devk[j])->index : C.at<const uint32_t>(s.idx); J.gend_in = C.at<const uint32_t>(s.gend_in);
 		J.faces = C.at<uint32_t>(C.img.faces) + (size_t)s.fbase*3; J.gend_out = C.at<uint32_t>(s.gend_out);
 		J.first = C.at<uint32_t>(s.first); J.cursor = C.at<uint32_t>(s.cursor);
 		J.sides = C.at<EncTopoSide>(s.sides); J.twin = C.at<uint32_t>(s.twin);
@@ -690,6 +724,7 @@ int encode_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_l
 	// The image's memory is freed by DevMem only after Drain has waited for the work queued on it, and C's host buffers go after that.
 	Chunk C{ctx, ctx_stream(ctx), meshes, extra, items, img, S, bt, tm};
 	for(uint32_t k : img.devk) C.ready[k] = 1;
+	if(img.resident) { const int e = fetch_indices(C); if(e) return e; }
 	// topology passes (meshes) and frames (everything) on the pool, started first: they need the index alone
 	std::thread pool;
 	struct Joiner { std::thread &t; ~Joiner() { if(t.joinable()) t.join(); } } joiner{pool};
@@ -729,11 +764,120 @@ int encode_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_l
 	return CRTHIP_OK;
 }
 
+// ---- a resident call's front: the caller's pointers, then what the host would have read through them ----
+
+// one array of a resident call: element-aligned device memory of the context's device, its whole extent inside one allocation
+bool resident_array_ok(const void *p, uint64_t bytes, uint32_t align, int device) {
+	if(!bytes) return true;
+	if(!p || ((uintptr_t)p & (align - 1))) return false;
+	hipPointerAttribute_t a;
+	memset(&a, 0, sizeof(a));
+	if(hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // (memory the runtime has never seen)
+	if(a.type != hipMemoryTypeDevice || a.device != device) return false;                          // pinned and managed memory included
+	hipDeviceptr_t base = nullptr;
+	size_t size = 0;
+	if(hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
+	const uintptr_t b = (uintptr_t)base, q = (uintptr_t)p;
+	return q >= b && bytes <= size && q - b <= size - bytes;
+}
+
+// every data array of one mesh (after encode_check / encode_check_attrs): no launch reads a pointer that has not passed here
+int resident_check(const crthip_mesh *m, const crthip_attr_list *extra, int device) {
+	const uint64_t nv = m->nvert;
+	bool ok = resident_array_ok(m->position, nv*12, 4, device);
+	if(m->index && m->nface) ok = ok && resident_array_ok(m->index, (uint64_t)m->nface*12, 4, device);
+	if(m->normal) ok = ok && resident_array_ok(m->normal, nv*12, 4, device);
+	if(m->color) ok = ok && resident_array_ok(m->color, nv*(uint64_t)m->color_components, 1, device);
+	if(m->uv) ok = ok && resident_array_ok(m->uv, nv*8, 4, device);
+	if(m->radius) ok = ok && resident_array_ok(m->radius, nv*4, 4, device);
+	if(extra) for(uint32_t k = 0; k < extra->nattr && ok; k++) {
+		const crthip_generic_attr &g = extra->attr[k];
+		const uint32_t esize = g.format == CRTHIP_FMT_DOUBLE ? 8u : g.format == CRTHIP_FMT_INT16 ? 2u : g.format == CRTHIP_FMT_INT8 ? 1u : 4u;
+		ok = resident_array_ok(g.values, nv*g.components*esize, esize, device);
+	}
+	return ok ? CRTHIP_OK : ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch_resident: a data array is not element-aligned device memory of the context's device, "
+	                                                    "or leaves its allocation");
+}
+
+// K-ENC-CHECK (k_encode_check.hip): the index range, the bounding boxes and the first-edge sums of meshes[ok[..]], whichever its step's
+// recipe needs, in two launches; recs[k] is item ok[k]'s record.  The pass has a small allocation of its own - records, partial boxes,
+// job tables - because a chunk's image is laid out from what batch_setup leaves, and batch_setup needs the step.  One copy back, one wait.
+int input_pass(crthip_ctx *ctx, const crthip_mesh *meshes, const std::vector<uint32_t> &ok, std::vector<EncInputRecord> &recs,
+               crthip_encode_batch_stats &S, BatchTimes &bt) {
+	const uint32_t n = (uint32_t)ok.size();
+	recs.assign(n, EncInputRecord{});
+	std::vector<EncInputJob> jobs;
+	std::vector<uint32_t> tables, box_ids;                        // tables: block_start, then box_ids
+	std::vector<uint64_t> rec_of, part_of;                        // per job: its item's place in ok, its first partial
+	uint64_t blocks = 0, nparts = 0;
+	for(uint32_t k = 0; k < n; k++) {
+		const crthip_mesh &m = meshes[ok[k]];
+		const uint32_t nface = m.index ? m.nface : 0;
+		EncInputJob J{};
+		J.position = m.position; J.index = m.index; J.nvert = m.nvert; J.nface = nface;
+		J.recipe = enc_in_recipe(m.position_bits, m.position_q, m.nvert, nface);
+		auto add = [&](uint32_t kind, uint64_t nblocks) {
+			J.kind = kind;
+			jobs.push_back(J); rec_of.push_back(k); part_of.push_back(nparts); tables.push_back((uint32_t)blocks);
+			blocks += nblocks;
+		};
+		if(nface) add(EIN_JOB_RANGE, (uint64_t)nface*3/EIN_INDEX_TILE + 1);
+		if((J.recipe == EIN_STEP_BOX_FIRST || J.recipe == EIN_STEP_BOX_MAX) && m.nvert) {
+			const uint64_t tiles = ((uint64_t)m.nvert + EIN_TILE - 1)/EIN_TILE;
+			box_ids.push_back((uint32_t)jobs.size());
+			add(EIN_JOB_BOX, tiles);
+			nparts += tiles;
+		}
+		if(J.recipe == EIN_STEP_EDGE) add(EIN_JOB_EDGE, 1);
+	}
+	if(jobs.empty()) return 0;
+	if(blocks >= (1ull << 31)) return ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch_resident: too many workgroups for the input pass");
+	tables.push_back((uint32_t)blocks);
+	const size_t ids_at = tables.size();
+	tables.insert(tables.end(), box_ids.begin(), box_ids.end());
+
+	Carver c;
+	const uint64_t rec_off = c.take((uint64_t)n*sizeof(EncInputRecord)), part_off = c.take(nparts*sizeof(EncInputBox));
+	const uint64_t job_off = c.take(jobs.size()*sizeof(EncInputJob)), tab_off = c.take(tables.size()*4);
+	DevMem dev;
+	{ const auto t0 = Clock::now(); ENC_TRY(hipMalloc(&dev.p, c.take(0) + 256)); S.alloc_ms += ms_since(t0); }
+	const hipStream_t st = ctx_stream(ctx);
+	struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};
+	for(size_t j = 0; j < jobs.size(); j++) {
+		jobs[j].rec = (EncInputRecord *)(dev.u8() + rec_off) + rec_of[j];
+		jobs[j].partials = (EncInputBox *)(dev.u8() + part_off) + part_of[j];
+	}
+	const EncInputJob *dj = (const EncInputJob *)(dev.u8() + job_off);
+	const uint32_t *dt = (const uint32_t *)(dev.u8() + tab_off);
+	ENC_TRY(hipMemsetAsync(dev.u8() + rec_off, 0, (size_t)n*sizeof(EncInputRecord), st));
+	ENC_TRY(hipMemcpyAsync(dev.u8() + job_off, jobs.data(), jobs.size()*sizeof(EncInputJob), hipMemcpyHostToDevice, st));
+	ENC_TRY(hipMemcpyAsync(dev.u8() + tab_off, tables.data(), tables.size()*4, hipMemcpyHostToDevice, st));
+	S.bytes_to_device += jobs.size()*sizeof(EncInputJob) + tables.size()*4;
+	EventTimer t_check, t_reduce;
+	if(t_check.begin(st)) return CRTHIP_E_DEVICE;
+	hipLaunchKernelGGL(k_enc_input_check, dim3((uint32_t)blocks), dim3(EIN_THREADS), 0, st, dj, dt, (uint32_t)jobs.size());
+	if(t_check.end(st)) return CRTHIP_E_DEVICE;
+	bt.launches[K_IN_CHECK]++;
+	if(!box_ids.empty()) {
+		if(t_reduce.begin(st)) return CRTHIP_E_DEVICE;
+		hipLaunchKernelGGL(k_enc_input_reduce, dim3((uint32_t)box_ids.size()), dim3(EIN_FOLD_LANES), 0, st, dj, dt + ids_at, (uint32_t)box_ids.size());
+		if(t_reduce.end(st)) return CRTHIP_E_DEVICE;
+		bt.launches[K_IN_REDUCE]++;
+	}
+	ENC_TRY(hipGetLastError());
+	ENC_TRY(hipMemcpyAsync(recs.data(), dev.u8() + rec_off, (size_t)n*sizeof(EncInputRecord), hipMemcpyDeviceToHost, st));
+	{ const auto t0 = Clock::now(); ENC_TRY(hipStreamSynchronize(st)); S.sync_wait_ms += ms_since(t0); }
+	S.bytes_from_device += (uint64_t)n*sizeof(EncInputRecord);
+	t_check.add_to(bt.ms[K_IN_CHECK]); t_reduce.add_to(bt.ms[K_IN_REDUCE]);
+	return 0;
+}
+
 } // namespace
 
+// resident: the data arrays of meshes / extra are DEVICE pointers (crthip_encode_batch_resident); everything else is the one path
 static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra, uint32_t host_threads,
                                  uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert, uint32_t *out_nface,
-                                 int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times) {
+                                 int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times, bool resident) {
 	const auto t0 = Clock::now();
 	if(!ctx) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch: null context (there is no CPU fallback: use crthip_encode for the host encoder)");
 	if(!blob_offset || (n && !meshes)) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch: null argument");
@@ -751,16 +895,33 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 	std::vector<uint32_t> ok;
 	for(uint32_t i = 0; i < n; i++) {
 		const crthip_mesh *m = &meshes[i];
-		int e = encode_check(m);
+		int e = encode_check(m, !resident);
 		if(!e) e = encode_check_attrs(m, extra ? &extra[i] : nullptr, true);
+		if(!e && resident) e = resident_check(m, extra ? &extra[i] : nullptr, ctx_device(ctx));
 		if(!e && (uint64_t)m->nvert*3 > (1u << 26)) e = ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: too many vertices for the value coder");
 		if(!e && m->entropy == CRTHIP_ENTROPY_TUNSTALL && m->nvert > (1u << 23))
 			e = ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: a Tunstall stream longer than 2^23 symbols");
 		items[i].status = e;
 		if(!e) ok.push_back(i);
 	}
-	// position steps and attribute tables (the steps' sums are the host's, in its order)
-	parallel_for((uint32_t)ok.size(), threads, [&](uint32_t k) { items[ok[k]].status = item_guard([&] { batch_setup(&meshes[ok[k]], extra ? &extra[ok[k]] : nullptr, items[ok[k]]); }); });
+	// position steps and attribute tables (the steps' sums are the host's, in its order: a resident call gets them, and the index check
+	// encode_check left out, from the device's records)
+	BatchTimes bt;
+	std::vector<float> steps;
+	if(resident) {
+		std::vector<EncInputRecord> recs;
+		{ const int e = input_pass(ctx, meshes, ok, recs, S, bt); if(e) return e; }
+		steps.resize(ok.size());
+		for(size_t k = 0; k < ok.size(); k++) {
+			const crthip_mesh &m = meshes[ok[k]];
+			if(recs[k].bad_index) items[ok[k]].status = ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: face index out of range");
+			else steps[k] = position_step(&m, enc_in_recipe(m.position_bits, m.position_q, m.nvert, m.index ? m.nface : 0), recs[k]);
+		}
+	}
+	parallel_for((uint32_t)ok.size(), threads, [&](uint32_t k) {
+		if(items[ok[k]].status) return;
+		items[ok[k]].status = item_guard([&] { batch_setup(&meshes[ok[k]], extra ? &extra[ok[k]] : nullptr, items[ok[k]], resident ? &steps[k] : nullptr); });
+	});
 	ok.erase(std::remove_if(ok.begin(), ok.end(), [&](uint32_t i) { return items[i].status != CRTHIP_OK; }), ok.end());
 	// where each mesh's topology pass runs: from the context's mode and the mesh's sizes alone
 	const int topo_mode = ctx_encode_topology(ctx);
@@ -780,14 +941,13 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 	ENC_TRY(hipMemGetInfo(&free_b, &total_b));
 	const uint64_t budget = free_b/2;
 	std::vector<std::vector<uint8_t>> blobs(n);
-	BatchTimes bt;
 	EncStageTimes tm;
 	for(size_t k = 0; k < ok.size();) {
 		// a chunk is sized by building its image: of every item that is left (the usual case), else of half as many until the image fits
 		// (an image only grows with another item).  A single item beyond the budget fails where encode_chunk allocates.
 		size_t take = ok.size() - k;
-		ChunkImage img = build_image(meshes, items, std::vector<uint32_t>(ok.begin() + k, ok.end()));
-		while(img.total > budget && take > 1) { take = (take + 1)/2; img = build_image(meshes, items, std::vector<uint32_t>(ok.begin() + k, ok.begin() + k + take)); }
+		ChunkImage img = build_image(meshes, items, std::vector<uint32_t>(ok.begin() + k, ok.end()), resident);
+		while(img.total > budget && take > 1) { take = (take + 1)/2; img = build_image(meshes, items, std::vector<uint32_t>(ok.begin() + k, ok.begin() + k + take), resident); }
 		const int e = encode_chunk(ctx, meshes, extra, items, img, budget, threads, blobs, S, bt, tm);
 		if(e) return e;
 		k += take;
@@ -821,7 +981,19 @@ extern "C" int64_t crthip_encode_batch_attrs(crthip_ctx *ctx, uint32_t n, const 
                                              uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert, uint32_t *out_nface,
                                              int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times) {
 	try {
-		return encode_batch_impl(ctx, n, meshes, extra, host_threads, out, cap, blob_offset, out_nvert, out_nface, status, stats, times);
+		return encode_batch_impl(ctx, n, meshes, extra, host_threads, out, cap, blob_offset, out_nvert, out_nface, status, stats, times, false);
+	} catch(const std::bad_alloc &) {
+		return ctx_fail(CRTHIP_E_NOMEM, nullptr);
+	} catch(...) {
+		return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch: internal error");
+	}
+}
+
+extern "C" int64_t crthip_encode_batch_resident(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra, uint32_t host_threads,
+                                                uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert, uint32_t *out_nface,
+                                                int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times) {
+	try {
+		return encode_batch_impl(ctx, n, meshes, extra, host_threads, out, cap, blob_offset, out_nvert, out_nface, status, stats, times, true);
 	} catch(const std::bad_alloc &) {
 		return ctx_fail(CRTHIP_E_NOMEM, nullptr);
 	} catch(...) {

@@ -643,12 +643,13 @@ struct ZPoint { uint64_t bits; uint32_t pos; bool operator<(const ZPoint &z) con
 
 // Arguments are checked before anything is indexed with them (upstream trusts its caller: an index >= nvert writes past its
 // vectors, src/encoder.cpp:341-347).
-int corto_hip::encode_check(const crthip_mesh *m) {
+int corto_hip::encode_check(const crthip_mesh *m, bool index_on_host) {
 	if(!m || !m->position) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: no mesh / no positions");
 	if(m->index && m->nface) {
 		if((uint64_t)m->nface*3 > 0xFFFFFFFFull) return corto_hip::ctx_fail(CRTHIP_E_LIMIT, "crthip_encode: too many faces");
-		for(size_t i = 0; i < (size_t)m->nface*3; i++)
-			if(m->index[i] >= m->nvert) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: face index out of range");
+		if(index_on_host)                                           // (else the device compares them: k_encode_check.hip)
+			for(size_t i = 0; i < (size_t)m->nface*3; i++)
+				if(m->index[i] >= m->nvert) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: face index out of range");
 	}
 	if(m->color) {
 		if(m->color_components != 3 && m->color_components != 4) return corto_hip::ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: color_components must be 3 or 4");
@@ -704,6 +705,44 @@ int corto_hip::encode_check_attrs(const crthip_mesh *m, const crthip_attr_list *
 	return CRTHIP_OK;
 }
 
+// The position step's two halves (src/encoder.cpp:49-100): the loops over the mesh's arrays, and the formulas over what they leave.  The
+// loops are upstream's, in upstream's order; crthip_encode_batch_resident runs them on the device (enc_input_check.h) and the formulas here.
+void corto_hip::input_stats_host(const crthip_mesh *m, uint32_t recipe, EncInputRecord &r) {
+	memset(&r, 0, sizeof(r));
+	const uint32_t nv = m->nvert, nface = m->index ? m->nface : 0;
+	float *mn = r.box.mn, *mx = r.box.mx;
+	if(recipe == EIN_STEP_BOX_FIRST) {
+		for(int k = 0; k < 3; k++) mn[k] = mx[k] = m->position[k];
+		for(uint32_t i = 0; i < nv; i++) for(int k = 0; k < 3; k++) { const float v = m->position[(size_t)i*3 + k]; if(v < mn[k]) mn[k] = v; if(v > mx[k]) mx[k] = v; }
+	} else if(recipe == EIN_STEP_EDGE) {                        // the length of each face's first edge (src/encoder.cpp:105-110)
+		double average = 0;
+		for(uint32_t f = 0; f < nface; f++) {
+			const float *a = m->position + (size_t)m->index[(size_t)f*3]*3, *b = m->position + (size_t)m->index[(size_t)f*3 + 1]*3;
+			const float d[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]};
+			average += (float)sqrt((double)(d[0]*d[0] + d[1]*d[1] + d[2]*d[2]));   // Point3f::norm, include/corto/point.h:111
+		}
+		r.sum = average;
+	} else if(recipe == EIN_STEP_BOX_MAX) {                     // point cloud: the bounding box (src/encoder.cpp:83-91)
+		for(int k = 0; k < 3; k++) { mn[k] = FLT_MAX; mx[k] = -FLT_MAX; }
+		for(uint32_t i = 0; i < nv; i++) for(int k = 0; k < 3; k++) { const float v = m->position[(size_t)i*3 + k] - 0.0f; if(v < mn[k]) mn[k] = v; if(v > mx[k]) mx[k] = v; }
+	}
+}
+
+float corto_hip::position_step(const crthip_mesh *m, uint32_t recipe, const EncInputRecord &r) {
+	const uint32_t nv = m->nvert, nface = m->index ? m->nface : 0;
+	if(recipe == EIN_STEP_BOX_FIRST) {
+		const float intervals = powf(2.0f, (float)m->position_bits);
+		float e[3]; for(int k = 0; k < 3; k++) { e[k] = r.box.mx[k] - r.box.mn[k]; e[k] /= intervals; }
+		return std::max(std::max(e[0], e[1]), e[2]);
+	}
+	if(recipe == EIN_STEP_EDGE) return (float)(r.sum/nface)/20.0f;   // a twentieth of the mean
+	if(recipe == EIN_STEP_BOX_MAX) {                            // from the bounding box volume
+		float mx[3]; for(int k = 0; k < 3; k++) { mx[k] = r.box.mx[k]; mx[k] -= r.box.mn[k]; }
+		return (float)(0.02*pow(mx[0]*mx[1]*mx[2], 2.0/3.0)/nv);
+	}
+	return m->position_q;
+}
+
 uint64_t corto_hip::quant_in_bytes(const QuantRequest &r) {
 	const uint64_t n = r.count;
 	switch(r.kind) {
@@ -730,7 +769,8 @@ extern "C" {
 // `step`: the position step when the caller has it already (crthip_encode_batch: computed once, before the device quantises).
 struct NamedQuant { std::string name; corto_hip::QuantRequest r; };
 // `extra`: the caller's generic attributes (Encoder::addAttribute, src/encoder.cpp:187-197), checked by encode_check_attrs.
-static void setup(const crthip_mesh *m, const crthip_attr_list *extra, Encoder &E, std::vector<NamedQuant> &quant, bool alloc, const float *step) {
+// `faces`: copy the index into E.faces (only the host's topology pass reads it; with faces == false and a step m's data arrays are not read at all).
+static void setup(const crthip_mesh *m, const crthip_attr_list *extra, Encoder &E, std::vector<NamedQuant> &quant, bool alloc, const float *step, bool faces = true) {
 	E.nvert = m->nvert; E.nface = m->index ? m->nface : 0; E.entropy = (uint32_t)m->entropy;
 	const char *p = m->exif;
 	for(uint32_t i = 0; i < m->nexif; i++) { std::string k(p); p += k.size() + 1; std::string v(p); p += v.size() + 1; E.exif[k] = v; }
@@ -745,7 +785,7 @@ static void setup(const crthip_mesh *m, const crthip_attr_list *extra, Encoder &
 				E.group_props[g][k] = v;
 			}
 	}
-	if(E.nface) E.faces.assign(m->index, m->index + (size_t)E.nface*3);
+	if(E.nface && faces) E.faces.assign(m->index, m->index + (size_t)E.nface*3);
 	const uint32_t nv = m->nvert;
 	auto request = [&](const char *name, Attr &a, corto_hip::QuantRequest r, size_t elems, size_t esize) {
 		if(alloc) { if(esize == 1) a.cvalues.resize(elems); else a.values.resize(elems); r.out = esize == 1 ? (void *)a.cvalues.data() : (void *)a.values.data(); }
@@ -754,25 +794,11 @@ static void setup(const crthip_mesh *m, const crthip_attr_list *extra, Encoder &
 	{	// positions (src/encoder.cpp:49-100, vertex_attribute.h:79-128)
 		float q = m->position_q;
 		if(step) q = *step;
-		else if(m->position_bits > 0) {
-			float mn[3] = {m->position[0], m->position[1], m->position[2]}, mx[3] = {mn[0], mn[1], mn[2]};
-			for(uint32_t i = 0; i < nv; i++) for(int k = 0; k < 3; k++) { const float v = m->position[(size_t)i*3 + k]; if(v < mn[k]) mn[k] = v; if(v > mx[k]) mx[k] = v; }
-			const float intervals = powf(2.0f, (float)m->position_bits);
-			float e[3]; for(int k = 0; k < 3; k++) { e[k] = mx[k] - mn[k]; e[k] /= intervals; }
-			q = std::max(std::max(e[0], e[1]), e[2]);
-		} else if(q == 0.0f && E.nface) {                       // a twentieth of the mean length of each face's first edge (src/encoder.cpp:105-110)
-			double average = 0;
-			for(uint32_t f = 0; f < E.nface; f++) {
-				const float *a = m->position + (size_t)m->index[(size_t)f*3]*3, *b = m->position + (size_t)m->index[(size_t)f*3 + 1]*3;
-				const float d[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]};
-				average += (float)sqrt((double)(d[0]*d[0] + d[1]*d[1] + d[2]*d[2]));   // Point3f::norm, include/corto/point.h:111
-			}
-			q = (float)(average/E.nface)/20.0f;
-		} else if(q == 0.0f && nv) {                            // point cloud: from the bounding box volume (src/encoder.cpp:83-91)
-			float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-			for(uint32_t i = 0; i < nv; i++) for(int k = 0; k < 3; k++) { const float v = m->position[(size_t)i*3 + k] - 0.0f; if(v < mn[k]) mn[k] = v; if(v > mx[k]) mx[k] = v; }
-			for(int k = 0; k < 3; k++) mx[k] -= mn[k];
-			q = (float)(0.02*pow(mx[0]*mx[1]*mx[2], 2.0/3.0)/nv);
+		else {
+			const uint32_t recipe = corto_hip::enc_in_recipe(m->position_bits, m->position_q, nv, E.nface);
+			corto_hip::EncInputRecord r;
+			corto_hip::input_stats_host(m, recipe, r);
+			q = corto_hip::position_step(m, recipe, r);
 		}
 		Attr &a = E.data["position"];
 		a.name = "position"; a.N = 3; a.q = q; a.format = CRTHIP_FMT_FLOAT;
@@ -948,10 +974,10 @@ void corto_hip::morton_order_host(const int32_t *coords, uint32_t nvert, std::ve
 	for(uint32_t i = 0; i < nvert; i++) order[i] = z[i].pos;
 }
 
-void corto_hip::batch_setup(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it) {
+void corto_hip::batch_setup(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it, const float *step) {
 	Encoder E;
 	std::vector<NamedQuant> named;
-	setup(m, extra, E, named, false, nullptr);
+	setup(m, extra, E, named, false, step, false);
 	it.entropy = E.entropy; it.nvert_in = m->nvert; it.nface_in = E.nface;
 	it.attrs.clear();
 	for(auto &kv : E.data) {                                     // the container's order (std::map)
@@ -1009,7 +1035,7 @@ void corto_hip::batch_frame(const crthip_mesh *m, const crthip_attr_list *extra,
 	Encoder E;
 	std::vector<NamedQuant> named;
 	float step = it.attrs[it.pos].quant.q;
-	setup(m, extra, E, named, false, &step);
+	setup(m, extra, E, named, false, &step, false);           // (the device pass has the faces: m->index may be a device pointer)
 	std::vector<Deferred> deferred;
 	E.s.defer = &deferred; E.s.shape_only = true;
 	E.header();

@@ -10,6 +10,7 @@
 
 #include "../../include/corto_hip.h"
 #include "device_plan.h"
+#include "enc_input_check.h"
 
 namespace corto_hip {
 
@@ -76,7 +77,11 @@ int encode_value_streams_device(crthip_ctx *ctx, const std::vector<DevValueStrea
 void enc_report_times(crthip_kernel_times *times, const EncStageTimes &tm);   // appends the stages' entries behind times->count
 
 // ---- crthip_encode_batch (encoder.cpp: checks, topology pass and container; encode_batch.cpp: the device half) ----
-int encode_check(const crthip_mesh *m);              // encode_checked's argument checks (sets the last error)
+// encode_checked's argument checks (sets the last error); index_on_host == false: m->index is a DEVICE pointer, its entries are not read
+int encode_check(const crthip_mesh *m, bool index_on_host = true);
+// the position step's loops over the mesh's HOST arrays as setup runs them (recipe: enc_in_recipe), and the formulas over what they leave
+void input_stats_host(const crthip_mesh *m, uint32_t recipe, EncInputRecord &r);
+float position_step(const crthip_mesh *m, uint32_t recipe, const EncInputRecord &r);
 // the rules of crthip_encode_attrs's extra list (sets the last error); device: also the value coder's bound on nvert*components
 int encode_check_attrs(const crthip_mesh *m, const crthip_attr_list *extra, bool device);
 constexpr uint32_t BATCH_BITS = 0xFFu;                // a stream that is the CLERS split bits, already packed
@@ -100,7 +105,9 @@ struct BatchItem {
 	std::vector<BatchStream> streams;                     // where they belong in it, in order (a BORDER normal's count: 0 until the device has it)
 };
 // extra: the mesh's generic attributes (or null), checked by encode_check_attrs
-void batch_setup(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it);      // position step + attribute table (after encode_check)
+// position step + attribute table (after encode_check); step: the position step where the caller has it (crthip_encode_batch_resident:
+// from the device's record) - m's data arrays are then not read
+void batch_setup(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it, const float *step = nullptr);
 void batch_topology(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it);   // topology pass (meshes) + frame; reads the index alone
 // a mesh's frame from what the device topology pass reports (its record, the new group ends, the packed split words): header, counts,
 // groups, max_front and the stream slots, without running the pass

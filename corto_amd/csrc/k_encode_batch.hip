@@ -17,13 +17,6 @@
 
 namespace corto_hip {
 
-// the job of workgroup b: the last j with block_start[j] <= b
-__device__ __forceinline__ uint32_t enc_job_of(const uint32_t *block_start, uint32_t njobs, uint32_t b) {
-	uint32_t lo = 0, hi = njobs;
-	while(hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if(block_start[mid] <= b) lo = mid; else hi = mid; }
-	return lo;
-}
-
 __global__ __launch_bounds__(256) void k_enc_gather(const CopyJob *__restrict__ jobs, uint32_t njobs) {
 	if(blockIdx.x >= njobs) return;
 	const CopyJob J = jobs[blockIdx.x];

@@ -180,4 +180,10 @@ __global__ void k_enc_topo_compact(const EncTopoJob *jobs, uint32_t njobs);
 __global__ void k_enc_topo_pair(const EncTopoJob *jobs, uint32_t njobs);
 template <bool LDS> __global__ void k_enc_topo_walk(const EncTopoJob *jobs, const uint32_t *ids, uint32_t nids);
 
+// k_encode_check.hip (crthip_encode_batch_resident): index range, bounding boxes and first-edge sums of arrays in device memory
+// (enc_input_check.h); workgroups of EIN_THREADS from a job table, then one wave per item with a box
+struct EncInputJob;
+__global__ void k_enc_input_check(const EncInputJob *jobs, const uint32_t *block_start, uint32_t njobs);
+__global__ void k_enc_input_reduce(const EncInputJob *jobs, const uint32_t *ids, uint32_t nids);
+
 } // namespace corto_hip

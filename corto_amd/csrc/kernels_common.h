@@ -159,6 +159,13 @@ __device__ __forceinline__ uint64_t chain_lookback(uint64_t *state, uint32_t c, 
 	return prefix;
 }
 
+// the batch encoder's job tables (k_encode_batch.hip, k_encode_check.hip): the job of workgroup b is the last j with block_start[j] <= b
+__device__ __forceinline__ uint32_t enc_job_of(const uint32_t *block_start, uint32_t njobs, uint32_t b) {
+	uint32_t lo = 0, hi = njobs;
+	while(hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if(block_start[mid] <= b) lo = mid; else hi = mid; }
+	return lo;
+}
+
 // x86 cvttss2si: out-of-range / NaN -> INT_MIN (what the reference's (int) casts do on its CPU)
 __device__ __forceinline__ int32_t f2i_x86(float x) {
 	if(!(x > -2147483904.0f && x < 2147483648.0f)) return (int32_t)0x80000000;

@@ -41,7 +41,7 @@ extern "C" {
                                      added within 6: crthip_generic_attr, crthip_attr_list, crthip_encode_attrs, crthip_encode_gpu_attrs,
                                      crthip_encode_batch_attrs, crthip_batch_create_resident, crthip_batch_reset_resident, crthip_batch_exif,
                                      crthip_batch_groups, crthip_batch_group_props, crthip_batch_walk_stats, crthip_batch_decode_with_next,
-                                     crthip_batch_set_parity */
+                                     crthip_batch_set_parity, crthip_encode_batch_resident, crthip_encode_input_model */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -383,7 +383,7 @@ int64_t crthip_encode(const crthip_mesh *mesh, uint8_t *out, size_t cap, uint32_
  * upstream (encodeValues writes a 64-bit field, include/corto/cstream.h:128-133): no bytes are promised for it. */
 typedef struct {
 	const char *name;             /* NUL-terminated, 1..63 bytes */
-	const void *values;           /* HOST, nvert*components elements of `format`, packed (vertex-major) */
+	const void *values;           /* HOST (crthip_encode_batch_resident: DEVICE), nvert*components elements of `format`, packed (vertex-major) */
 	uint32_t format;              /* CRTHIP_FMT_FLOAT, _DOUBLE, _INT32, _INT16 or _INT8 */
 	uint32_t components;          /* 1..16 */
 	float q;                      /* quantisation step */
@@ -541,7 +541,36 @@ int64_t crthip_encode_batch_attrs(crthip_ctx *ctx, uint32_t n, const crthip_mesh
                                   uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert, uint32_t *out_nface,
                                   int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times);
 
-/* Where crthip_encode_batch / crthip_encode_batch_attrs on this context run a mesh's CLERS topology pass (degenerate faces, half-edge
+/* crthip_encode_batch_attrs for meshes that live in DEVICE memory (ABI 6 addition): a simulation's or a reconstruction's output, a
+ * decoded batch being re-quantised.  Arguments and results are those of crthip_encode_batch_attrs (extra: n lists or NULL), and blob i is
+ * byte-identical to crthip_encode_attrs of the same arrays held in host memory.  What differs: the DATA arrays are device pointers on the
+ * context's device - position, index, normal, color, uv, radius and every crthip_generic_attr.values.  The metadata stays in host memory:
+ * group_end, group_nprops, group_props, exif, the names and the structs themselves; out, blob_offset, out_nvert, out_nface and status
+ * are host memory as before.  Nothing of the arrays is staged or copied up: the quantiser and the device topology pass read them where
+ * they are, and what the host encoder reads from them before it quantises - the index range check, the bounding box or the mean first-edge
+ * length behind the position step - is computed on the device (kernels enc_input_check, enc_input_reduce in crthip_kernel_times; upstream's
+ * arithmetic in upstream's order, NaN, infinities and the sign of a zero included) and comes back as one record per item.  Meshes whose
+ * topology pass runs on the host pool (crthip_ctx_set_encode_topology: all of them by default, under SPLIT those beyond LDS) have their index
+ * copied back for it (bytes_from_device); attributes never come back.  The three modes give the same bytes.
+ * The caller's rules:
+ *   - every array is aligned to its element size: 4 bytes for float / uint32 / int32, 8 for double, 2 for int16 (colours and int8: none),
+ *     else CRTHIP_E_ARGUMENT in status[i];
+ *   - every non-empty array is device memory of the context's device (pinned or managed host memory is refused: host arrays belong to
+ *     crthip_encode_batch) and its whole extent lies inside one allocation, else CRTHIP_E_ARGUMENT in status[i]: both are checked with
+ *     the runtime's pointer queries before the first launch (their cost, about five queries a mesh, is part of host_check_ms, as is the
+ *     input pass), so a wrong pointer is an error code and never a device fault;
+ *   - the caller's writes to the arrays have completed before the call ("Device buffers" above); the call returns with everything it
+ *     queued drained, as crthip_encode_batch does;
+ *   - the library never writes to the caller's arrays;
+ *   - with nvert == 0 the position pointer only has to be non-NULL and is never dereferenced: the step of position_bits > 0 is then 0.0f,
+ *     which is what the host computes from any finite position[0].
+ * Per-mesh errors keep their codes: a face index >= nvert, now found on the device, is CRTHIP_E_ARGUMENT with an empty range, and the
+ * neighbouring meshes are still encoded.  The blobs are spliced on the host and returned in host memory. */
+int64_t crthip_encode_batch_resident(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra /* n lists or NULL */,
+                                     uint32_t host_threads, uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert,
+                                     uint32_t *out_nface, int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times);
+
+/* Where crthip_encode_batch / crthip_encode_batch_attrs / crthip_encode_batch_resident on this context run a mesh's CLERS topology pass (degenerate faces, half-edge
  * pairing, the walk that writes the CLERS symbols, split bits, vertex numbering and prediction quads).  Same bytes in every mode.
  *   CRTHIP_TOPOLOGY_HOST    (default) on the host_threads pool, overlapping the device's quantisation
  *   CRTHIP_TOPOLOGY_DEVICE  every mesh on the device (kernels enc_topo_compact, enc_topo_pair, enc_topo_walk): no host thread is started,
@@ -575,6 +604,25 @@ typedef struct {
 	uint32_t lds;               /* out: which = 1 walked with the 16-bit (LDS) state */
 } crthip_topology_result;
 int crthip_encode_topology_model(const crthip_mesh *m, int which, crthip_topology_result *r);
+
+
+/* (test hook, no device needed)  What the encoder reads from a mesh's HOST arrays before it quantises: which = 0 the host encoder's own
+ * loops (what crthip_encode runs), which = 1 the source the kernels of crthip_encode_batch_resident run (csrc/enc_input_check.h),
+ * compiled for the host and walked in the kernels' partition (the same runs, tiles, merge order and sequential sum).  recipe says how the
+ * position step is derived: 0 position_q as given, 1 the bounding box seeded from vertex 0 (position_bits > 0), 2 the mean length of the
+ * faces' first edges, 3 the bounding box seeded from +-FLT_MAX (a cloud); mn / mx / sum are what that recipe's loop leaves (0 where it has
+ * none) and step the resulting q.  Neither model gathers through an index entry >= nvert or reads position[0] of an empty mesh: with
+ * index_out_of_range set, sum and step are reported as 0.  CRTHIP_E_ARGUMENT for another `which` or a mesh crthip_encode would refuse for
+ * anything but its index entries. */
+typedef struct {
+	uint32_t index_out_of_range;  /* 1: an index entry >= nvert */
+	uint32_t recipe;
+	float mn[3], mx[3];
+	double sum;
+	float step;
+	uint32_t reserved;
+} crthip_encode_input_result;
+int crthip_encode_input_model(const crthip_mesh *m, int which, crthip_encode_input_result *r);
 
 #ifdef __cplusplus
 }

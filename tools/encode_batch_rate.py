@@ -8,6 +8,14 @@
 where the library has no such switch) and host_threads (1, 4, 16); one record per combination with every repetition's time, the best one's
 stats and kernel times, and whether the blobs equal the host mode's.
 
+    python tools/encode_batch_rate.py --resident [--out FILE] [--reps 3]
+
+--resident: what a producer whose meshes are in device memory pays, over the five workloads and under host and device topology, the legs
+taken in turn within every repetition and every repetition recorded: (a) crthip_encode_batch from host arrays; (b)
+crthip_encode_batch_resident on the same arrays in one device buffer; (c) what such a producer had to do before - one device-to-host
+copy of all inputs, then (a), or then crthip_encode on 16 host threads.  With the device time of the input pass's kernels, both calls'
+stats, and whether (b)'s blobs equal (a)'s.  Needs a device: there is nothing to fall back to.
+
 For each workload: the batch call's wall time, its stats and per-kernel times (of the same run), beside crthip_encode on one
 host thread and on 16 (ctypes releases the GIL), crthip_encode_gpu mesh by mesh, and the reference encoder on one core when
 oracle/_ref is present; every leg is the best of --reps runs.  Every batch blob is checked against crthip_encode's bytes."""
@@ -76,14 +84,99 @@ def topology_axis(reps):
     return recs
 
 
+def place_on_device(meshes):
+    """Every data array of the meshes in ONE device byte tensor (16-byte aligned starts): (buffer, device meshes, rebuild), where
+    rebuild(host_bytes) gives the meshes again as views of a host copy of the buffer."""
+    import numpy as np
+    import torch
+    names = ("position", "index", "normal", "color", "uv", "radius")
+    plan, pos = [], 0
+    for m in meshes:
+        d = {}
+        for a in names:
+            v = getattr(m, a)
+            if v is not None:
+                d[a] = (pos, v.dtype, v.shape, v.nbytes)
+                pos += (v.nbytes + 15) // 16 * 16
+        plan.append(d)
+    host = np.zeros(pos + 16, dtype=np.uint8)
+    for m, d in zip(meshes, plan):
+        for a, (at, _, _, nb) in d.items():
+            host[at:at + nb] = getattr(m, a).view(np.uint8).reshape(-1)
+    buf = torch.from_numpy(host).to("cuda:0")
+    tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.uint32): torch.int32, np.dtype(np.uint8): torch.uint8}
+    dev = [ca.DeviceMesh(**{a: buf[at:at + nb].view(tdt[np.dtype(dt)]).reshape(shape) for a, (at, dt, shape, nb) in d.items()}, groups=m.groups,
+                         group_props=getattr(m, "group_props", None)) for m, d in zip(meshes, plan)]
+    torch.cuda.synchronize()
+
+    def rebuild(h):
+        out = []
+        for m, d in zip(meshes, plan):
+            r = synth.Mesh(**{a: h[at:at + nb].view(dt).reshape(shape) for a, (at, dt, shape, nb) in d.items()}, groups=m.groups)
+            r.group_props = getattr(m, "group_props", None)
+            out.append(r)
+        return out
+    return buf, dev, rebuild
+
+
+def resident_axis(reps):
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("encode_batch_rate.py --resident: no device (the resident encoder has no CPU fallback)")
+    recs = []
+    clock = time.perf_counter
+
+    def timed(f):
+        t0 = clock(); r = f(); return (clock() - t0) * 1e3, r
+
+    for name, meshes, kw in workloads():
+        buf, dev, rebuild = place_on_device(meshes)
+        input_bytes = int(buf.numel())
+        for mode in ("host", "device"):
+            ctx = ca.Context(0)
+            ctx.set_profiling(True)
+            ctx.set_encode_topology(mode)
+            ca.encode_batch(meshes[:1], ctx, kw=kw); ca.encode_batch_resident(dev[:1], ctx, kw=kw)      # warm the context and the kernels
+            legs = {k: [] for k in ("a_host_arrays", "b_resident", "c_copy_then_batch", "c_copy_then_16_threads", "c_copy_alone")}
+            best_a = best_b = None
+            identical = True
+            with ThreadPoolExecutor(16) as ex:
+                for _ in range(reps):
+                    t, (blobs_a, st_a) = timed(lambda: ca.encode_batch(meshes, ctx, kw=kw, with_stats=True))
+                    legs["a_host_arrays"].append(round(t, 3))
+                    if best_a is None or t < best_a[0]:
+                        best_a = (t, st_a)
+                    t, (blobs_b, st_b) = timed(lambda: ca.encode_batch_resident(dev, ctx, kw=kw, with_stats=True))
+                    legs["b_resident"].append(round(t, 3))
+                    if best_b is None or t < best_b[0]:
+                        best_b = (t, st_b)
+                    identical = identical and [b.tobytes() for b in blobs_a] == [b.tobytes() for b in blobs_b]
+                    t0 = clock(); back = rebuild(buf.cpu().numpy()); t_copy = (clock() - t0) * 1e3
+                    t, _ = timed(lambda: ca.encode_batch(back, ctx, kw=kw))
+                    legs["c_copy_then_batch"].append(round(t_copy + t, 3)); legs["c_copy_alone"].append(round(t_copy, 3))
+                    t0 = clock(); back = rebuild(buf.cpu().numpy()); t_copy = (clock() - t0) * 1e3
+                    t, _ = timed(lambda: list(ex.map(lambda m: ca.encode(m, **kw), back)))
+                    legs["c_copy_then_16_threads"].append(round(t_copy + t, 3))
+            pick = lambda st: {k: (round(v, 3) if isinstance(v, float) else v) for k, v in st.items() if k != "kernel_times"}
+            rec = dict(workload=name, mode=mode, items=len(meshes), input_bytes=input_bytes, reps_ms=legs, best_ms={k: min(v) for k, v in legs.items()},
+                       resident_identical_to_host_arrays=identical, stats_host_arrays=pick(best_a[1]), stats_resident=pick(best_b[1]),
+                       input_kernels={k: dict(ms=round(v["ms"], 4), launches=v["launches"]) for k, v in best_b[1]["kernel_times"].items() if k.startswith("enc_input")})
+            print(json.dumps(rec), flush=True)
+            recs.append(rec)
+            ctx.close()
+        del buf, dev
+    return recs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--topology", action="store_true", help="the topology mode x host_threads table of the mesh workloads")
+    ap.add_argument("--resident", action="store_true", help="host arrays against arrays in device memory against copying those back first")
     a = ap.parse_args()
-    if a.topology:
-        recs = topology_axis(a.reps)
+    if a.topology or a.resident:
+        recs = resident_axis(a.reps) if a.resident else topology_axis(a.reps)
         if a.out:
             with open(a.out, "w") as f:
                 for r in recs:
