@@ -67,6 +67,15 @@ class WalkStats(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class SpliceStats(C.Structure):
+    """crthip_splice_stats: the splice of the last encode_batch_to_device on a context"""
+    _fields_ = [("pieces", C.c_uint32), ("jobs", C.c_uint32), ("literal_bytes", C.c_uint64), ("device_bytes", C.c_uint64),
+                ("arena_bytes", C.c_uint64), ("splice_kernel_us", C.c_float), ("launches", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class MeshDesc(C.Structure):
     _fields_ = [
         ("nvert", C.c_uint32), ("nface", C.c_uint32),
@@ -187,6 +196,17 @@ def lib():
         L.crthip_encode_batch_resident.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.crthip_encode_input_model.argtypes = [C.POINTER(MeshDesc), C.c_int, C.c_void_p]
+        L.crthip_encode_batch_to_device.restype = C.c_int64
+        L.crthip_encode_batch_to_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.crthip_encode_batch_bound.restype = C.c_uint64
+        L.crthip_encode_batch_bound.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
+        L.crthip_ctx_encode_splice_stats.argtypes = [C.c_void_p, C.POINTER(SpliceStats)]
+        L.crthip_encode_splice_model.restype = C.c_int64
+        L.crthip_encode_splice_model.argtypes = [C.POINTER(MeshDesc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
+        L.crthip_splice_copy_model.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
+        L.crthip_encode_splice_plan_model.restype = C.c_int64
+        L.crthip_encode_splice_plan_model.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SpliceStats), C.c_void_p, C.c_size_t, C.c_uint32]
         L.crthip_encode_batch_attrs.restype = C.c_int64
         L.crthip_encode_batch_attrs.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -513,12 +533,9 @@ def encode_batch_resident(meshes, ctx, kw=None, host_threads=0, raise_on_error=T
     return encode_batch(meshes, ctx, kw=kw, host_threads=host_threads, raise_on_error=raise_on_error, with_stats=with_stats, _ptr=ptr)
 
 
-def encode_batch(meshes, ctx, kw=None, host_threads=0, raise_on_error=True, with_stats=False, _ptr=None):
-    """.crt blobs of a batch of corto_amd.synth.Mesh in one crthip_encode_batch: each byte-identical to encode(mesh, **kw).
-    kw: one dict of encode()'s keywords for all meshes, or one per mesh (`attributes` included: crthip_encode_batch_attrs).  Returns the list of uint8 blobs (empty for a mesh
-    that failed); with raise_on_error=False also the per-mesh status codes; with_stats=True also a dict of the call's
-    statistics and per-kernel times.  (_ptr: encode_batch_resident's pointer getter.)"""
-    meshes = list(meshes)
+def _batch_descs(meshes, kw, _ptr=None):
+    """the crthip_mesh array and the crthip_attr_list array of a batch (kw: one dict of encode()'s keywords for all meshes, or one per mesh),
+    whether any mesh has a list, the objects the arrays point into, and the bytes the lists add to a size estimate"""
     n = len(meshes)
     if kw is None:
         kws = [{}] * n
@@ -542,6 +559,132 @@ def encode_batch(meshes, ctx, kw=None, host_threads=0, raise_on_error=True, with
             lst, ka = _attr_list(attributes, mesh.nvert, _ptr)
             lists[i] = lst; keep.append(ka); with_attrs = True
             extra_bytes += sum(8 * int(np.prod(a[1].shape)) for a in attributes) if _ptr is not None else sum(8 * np.asarray(a[1]).size for a in attributes)
+    return n, descs, lists, with_attrs, keep, extra_bytes
+
+
+def _device_ptr_getter(what):
+    """the address of a device tensor for a crthip_mesh (an empty one has none: any device word stands for it, it is never read)"""
+    null = []
+
+    def ptr(t):
+        if t.numel():
+            if not t.is_contiguous():
+                raise ValueError("%s: device arrays must be contiguous" % what)
+            return t.data_ptr()
+        if not null:
+            import torch
+            null.append(torch.zeros(4, dtype=torch.int32, device=t.device))
+        return null[0].data_ptr()
+    return ptr
+
+
+def encode_batch_bound(meshes, kw=None, resident=None) -> int:
+    """crthip_encode_batch_bound: bytes that the arena of encode_batch_to_device(meshes, kw=kw) can never exceed, from the descriptors alone
+    (no device work; the data arrays are not read)."""
+    meshes = list(meshes)
+    if resident is None:
+        resident = any(isinstance(m, DeviceMesh) for m in meshes)
+    n, descs, lists, with_attrs, keep, _ = _batch_descs(meshes, kw, _device_ptr_getter("encode_batch_bound") if resident else None)
+    return int(lib().crthip_encode_batch_bound(n, descs, lists if with_attrs else None))
+
+
+def encode_batch_to_device(meshes, ctx, kw=None, host_threads=0, resident=None, out=None, raise_on_error=True, with_stats=False, cap=None):
+    """encode_batch with the blobs left in device memory (crthip_encode_batch_to_device): returns (out, offsets, lens) - `out` a device uint8
+    tensor, blob i its lens[i] bytes at offsets[i], byte-identical to encode(mesh, **kw); offsets are arena_layout(lens), so
+    Batch.resident(ctx, out, offsets, lens) takes the three as they are.  resident: the meshes' data arrays (and kw's `attributes`) are device
+    tensors (default: the meshes are DeviceMesh objects), else numpy arrays.  out: a 16-byte aligned device uint8 tensor to write into (None:
+    one of encode_batch_bound bytes is allocated); cap: bytes of it that may be written (default: all).  An arena that is too small raises.
+    With raise_on_error=False also the per-mesh status codes; with_stats=True also a dict of the call's statistics, kernel times and splice
+    statistics (`total`: the arena's bytes)."""
+    import torch
+    meshes = list(meshes)
+    if resident is None:
+        resident = any(isinstance(m, DeviceMesh) for m in meshes)
+    n, descs, lists, with_attrs, keep, _ = _batch_descs(meshes, kw, _device_ptr_getter("encode_batch_to_device") if resident else None)
+    if out is None:
+        bound = int(lib().crthip_encode_batch_bound(n, descs, lists if with_attrs else None))
+        out = torch.empty(max(bound, 16), dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+    if out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError("encode_batch_to_device: out must be a contiguous uint8 device tensor")
+    cap = out.numel() if cap is None else int(cap)
+    _torch_ready(ctx.device)
+    offs = np.zeros(max(n, 1), dtype=np.uint64)
+    lens = np.zeros(max(n, 1), dtype=np.uint32)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    st = EncodeBatchStats()
+    t = KernelTimes()
+    r = lib().crthip_encode_batch_to_device(ctx.handle, n, descs, lists if with_attrs else None, host_threads, 1 if resident else 0,
+                                            out.data_ptr(), cap, _np_ptr(offs), _np_ptr(lens), None, None, _np_ptr(status), C.byref(st), C.byref(t))
+    if r < 0:
+        _check(int(r))
+    if r > cap:
+        raise CortoError(-9, "encode_batch_to_device: the arena needs %d bytes, out holds %d (nothing was written)" % (r, cap))
+    offs, lens, status = offs[:n], lens[:n], status[:n]
+    if raise_on_error and (status != 0).any():
+        i = int(np.nonzero(status)[0][0])
+        raise CortoError(int(status[i]), "encode_batch_to_device: mesh %d: %s" % (i, lib().crthip_strerror(int(status[i])).decode()))
+    res = [out, offs, lens]
+    if not raise_on_error:
+        res.append(status)
+    if with_stats:
+        d = st.as_dict()
+        d["kernel_times"] = t.as_dict()
+        d["splice"] = ctx.encode_splice_stats()
+        d["total"] = int(r)
+        res.append(d)
+    return tuple(res)
+
+
+def encode_splice_model(mesh, dst_misalign=0, attributes=None, **kw) -> np.ndarray:
+    """crthip_encode_splice_model: encode() through the plan and the mover of the device splice (csrc/enc_splice.h) on the host, in the kernel's
+    partition, with the arena dst_misalign bytes off a 16-byte boundary.  Returns (blob, padding): the blob's bytes and the bytes written
+    from its end to the next 16-byte multiple."""
+    m, keep = _mesh_desc(mesh, **kw)
+    lst, keep_attrs = _attr_list(attributes, mesh.nvert)
+    extra = C.byref(lst) if lst is not None else None
+    size = lib().crthip_encode_attrs(C.byref(m), extra, None, 0, None, None)      # (the host encoder sizes the buffer)
+    if size < 0:
+        _check(int(size))
+    cap = int(size) + 32
+    out = np.full(cap, 0x5A, dtype=np.uint8)
+    n = lib().crthip_encode_splice_model(C.byref(m), extra, int(dst_misalign), _np_ptr(out), cap)
+    if n < 0:
+        _check(int(n))
+    n = int(n)
+    return out[:n].copy(), out[n:(n + 15) & ~15].copy()
+
+
+def splice_copy_model(src: np.ndarray, src_at: int, dst: np.ndarray, dst_at: int, nbytes: int, seed: int = 1):
+    """crthip_splice_copy_model: nbytes bytes from src[src_at:] to dst[dst_at:] with the device splice's mover on the host (tiles shuffled by
+    `seed`).  The mover reads up to 3 bytes on either side of the source: keep src_at >= 3 and 3 bytes behind the range."""
+    assert src.dtype == np.uint8 and dst.dtype == np.uint8 and src_at >= 3 and src_at + nbytes + 3 <= src.size and dst_at + nbytes <= dst.size
+    _check(lib().crthip_splice_copy_model(src.ctypes.data + src_at, dst.ctypes.data + dst_at, int(nbytes), int(seed)))
+
+
+def encode_splice_plan_model(meshes, kw=None, chunk_items=0):
+    """crthip_encode_splice_plan_model: the device splice's plan of a batch on the host, in chunks of chunk_items meshes (0: one chunk) that
+    continue the arena as the chunks of a batch beyond one device image do.  Returns (offsets, lens, stats dict, pieces): pieces an
+    (npieces, 3) uint64 array of (arena offset, bytes, 1 literal | 0 device)."""
+    meshes = list(meshes)
+    n, descs, lists, with_attrs, keep, _ = _batch_descs(meshes, kw)
+    offs = np.zeros(max(n, 1), dtype=np.uint64)
+    lens = np.zeros(max(n, 1), dtype=np.uint32)
+    st = SpliceStats()
+    np_ = lib().crthip_encode_splice_plan_model(n, descs, lists if with_attrs else None, _np_ptr(offs), _np_ptr(lens), C.byref(st), None, 0, int(chunk_items))
+    if np_ < 0:
+        _check(int(np_))
+    pieces = np.zeros((max(int(np_), 1), 3), dtype=np.uint64)
+    lib().crthip_encode_splice_plan_model(n, descs, lists if with_attrs else None, _np_ptr(offs), _np_ptr(lens), C.byref(st), _np_ptr(pieces), int(np_), int(chunk_items))
+    return offs[:n], lens[:n], st.as_dict(), pieces[:int(np_)]
+
+
+def encode_batch(meshes, ctx, kw=None, host_threads=0, raise_on_error=True, with_stats=False, _ptr=None):
+    """.crt blobs of a batch of corto_amd.synth.Mesh in one crthip_encode_batch: each byte-identical to encode(mesh, **kw).
+    kw: one dict of encode()'s keywords for all meshes, or one per mesh (`attributes` included: crthip_encode_batch_attrs).  Returns the list of uint8 blobs (empty for a mesh
+    that failed); with raise_on_error=False also the per-mesh status codes; with_stats=True also a dict of the call's
+    statistics and per-kernel times.  (_ptr: encode_batch_resident's pointer getter.)"""
+    meshes = list(meshes)
+    n, descs, lists, with_attrs, keep, extra_bytes = _batch_descs(meshes, kw, _ptr)
     offs = np.zeros(n + 1, dtype=np.uint64)
     status = np.zeros(max(n, 1), dtype=np.int32)
     st = EncodeBatchStats()
@@ -601,6 +744,13 @@ class Context:
         if where not in TOPOLOGY_MODES:
             raise ValueError("set_encode_topology: %r is not one of %s" % (where, sorted(TOPOLOGY_MODES)))
         _check(lib().crthip_ctx_set_encode_topology(self.handle, TOPOLOGY_MODES[where]))
+
+    def encode_splice_stats(self) -> dict:
+        """crthip_ctx_encode_splice_stats: pieces, jobs, literal_bytes, device_bytes, arena_bytes and the kernel's time of the last
+        encode_batch_to_device on this context"""
+        s = SpliceStats()
+        _check(lib().crthip_ctx_encode_splice_stats(self.handle, C.byref(s)))
+        return s.as_dict()
 
     def set_packed_host_blobs(self, on: bool = True):
         """blobs laid out as an arena in ONE pinned host buffer (pinned_host_arena) are uploaded straight from there (corto_hip.h)"""

@@ -191,6 +191,8 @@ static int harvest_selected(crthip_ctx *ctx) {
 namespace corto_hip {
 int ctx_device(crthip_ctx *ctx) { return ctx->device; }
 int ctx_encode_topology(crthip_ctx *ctx) { return ctx->encode_topology; }
+crthip_splice_stats &ctx_splice_stats(crthip_ctx *ctx) { return ctx->enc_splice; }
+uint64_t ctx_encode_image_budget(crthip_ctx *ctx) { return ctx->dbg.encode_image_budget; }
 hipStream_t ctx_stream(crthip_ctx *ctx) { return ctx->stream; }
 bool ctx_pipelines(crthip_ctx *ctx) { return ctx->single_stream && !ctx->dbg.carry_off; }
 bool batch_carriable(const crthip_batch *b) { return b && b->carriable; }
@@ -295,6 +297,12 @@ extern "C" int crthip_ctx_set_profiling(crthip_ctx *c, int enable) {
 extern "C" int crthip_ctx_set_packed_host_blobs(crthip_ctx *c, int on) {
 	if(!c) return fail(CRTHIP_E_ARGUMENT);
 	c->packed_host = on != 0;
+	return CRTHIP_OK;
+}
+
+extern "C" int crthip_ctx_encode_splice_stats(const crthip_ctx *c, crthip_splice_stats *s) {
+	if(!c || !s) return fail(CRTHIP_E_ARGUMENT, "crthip_ctx_encode_splice_stats: null argument");
+	*s = c->enc_splice;
 	return CRTHIP_OK;
 }
 

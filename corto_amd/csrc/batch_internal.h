@@ -167,6 +167,7 @@ struct crthip_ctx {
 	crthip_batch *in_flight = nullptr;   // decode enqueued, status not harvested yet
 	// crthip_ctx_set_packed_host_blobs: blobs laid out as an arena in the caller's pinned memory go up from there
 	bool packed_host = false;
+	crthip_splice_stats enc_splice{};                 // crthip_ctx_encode_splice_stats: the last crthip_encode_batch_to_device
 	int encode_topology = CRTHIP_TOPOLOGY_HOST;       // crthip_ctx_set_encode_topology: where crthip_encode_batch runs the CLERS topology pass
 	// a batch's blobs are (perhaps still) on their way from arena_pin: cleared by whoever synchronises the stream
 	bool arena_upload_pending = false;

@@ -1,4 +1,4 @@
-// debug_config.h — every environment switch of the decode path in one struct, filled when a context is made
+// debug_config.h — every environment switch of the decode path (and the batch encoders' one) in one struct, filled when a context is made
 // (crthip_ctx_create) and never consulted anywhere else: no getenv in the planner, no function-local statics.
 //
 // These are deployment settings and test hooks (documented in INTEGRATION.md); none changes results, only which kernels produce them.
@@ -34,6 +34,9 @@ struct DebugConfig {
 	bool carry_off = false;         // $CORTO_CARRY=0 (A/B and test hook): crthip_batch_decode_with_next enqueues the next batch's entropy stage as launches of its
 	                                // own behind this batch's kernels instead of inside k_front's / k_delta_lds16's grids, and the pool runs one batch per
 	                                // lane and call as it did before it pipelined its lanes (plan_launch.cpp, pool.cpp)
+	uint64_t encode_image_budget = 0; // $CORTO_ENCODE_IMAGE_BUDGET=<bytes> (test hook): the batch encoders cut a batch into chunks whose device image stays within
+	                                // this many bytes instead of within half the free device memory - a batch of small meshes then runs in several chunks, the
+	                                // path a batch beyond one device image takes (tests/test_encode_device_out_gpu.py); never above that half
 };
 
 inline DebugConfig debug_config_from_env() {
@@ -47,6 +50,7 @@ inline DebugConfig debug_config_from_env() {
 	c.values_i32 = on("CORTO_VALUES_I32");
 	{ const char *e = getenv("CORTO_FRONT"); c.front_off = e && e[0] == '0'; }
 	{ const char *e = getenv("CORTO_CARRY"); c.carry_off = e && e[0] == '0'; }
+	if(const char *e = getenv("CORTO_ENCODE_IMAGE_BUDGET")) c.encode_image_budget = strtoull(e, nullptr, 10);
 	return c;
 }
 

@@ -262,6 +262,12 @@ struct ZJob {
 	uint32_t *quads;               // out: the prediction (t, prev, prev, prev)
 	uint32_t n, pad;
 };
+// ---- crthip_encode_batch_to_device (k_encode_splice.hip, enc_splice.h) ----
+// one piece of the arena: `bytes` bytes from a library allocation (the value coder's image, the chunk image, the literal buffer) to their
+// place in the caller's arena, any alignment on both sides; tile_start[j] is the first tile (wave) of job j, as block_start is elsewhere
+struct SpliceJob { const uint8_t *src; uint8_t *dst; uint64_t bytes; };
+static_assert(sizeof(SpliceJob) == 24, "splice job layout");
+
 constexpr uint32_t RS_THREADS = 256, RS_ITEMS = 16, RS_TILE = RS_THREADS*RS_ITEMS;   // radix sort: 8-bit digits, a tile of 4 096 records a workgroup
 constexpr uint32_t DENC_BLOCK = 1024;                                                  // encoded vertices a workgroup of k_enc_delta
 

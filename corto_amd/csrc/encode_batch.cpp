@@ -10,6 +10,10 @@
 // encode_value_streams_device).  The host splices every container from its frame and the coded streams (encoder_internal.h:
 // splice_container).  One device image per chunk of the batch; no allocation per mesh or per stream.
 //
+// crthip_encode_batch_to_device shares every stage up to code_values and differs in the tail: the coders leave their payload on the device
+// (encode_value_streams_resident), the host plans where every byte of every container goes in the caller's device arena (enc_splice.h),
+// uploads what it made itself as one literal buffer beside the job table, and k_enc_splice moves the pieces (splice_to_device).
+//
 // crthip_encode_batch_resident is the same path for data arrays that live in device memory: the pointers are vouched for by the runtime
 // (resident_check), what the host would have read through them comes from K-ENC-CHECK (input_pass: k_encode_check.hip), the quantiser
 // and the device topology pass read the caller's arrays in place, and only the index of a mesh the host pool walks comes back
@@ -34,6 +38,7 @@
 
 #include "../../include/corto_hip.h"
 #include "device_plan.h"
+#include "enc_splice.h"
 #include "enc_topology.h"
 #include "encoder_internal.h"
 #include "kernels.h"
@@ -643,7 +648,8 @@ int stage_delta(Chunk &C) {
 // is waited for, and the stages' times are read.  The host-made CLERS symbols then go up: into the image beside the device pass's (every
 // mode but HOST), else into an allocation of their own, in one copy.  R: slot.count, slot.d, slot.clers.  W: slot.clers of the host-made
 // meshes.  Synchronised (the value coder ends so).
-int code_values(Chunk &C, int mode, std::vector<EncValueResult> &res) {
+// keep != null (crthip_encode_batch_to_device): the coded payload stays on the device, keep says where (res stays empty).
+int code_values(Chunk &C, int mode, std::vector<EncValueResult> &res, DevCoded *keep = nullptr) {
 	const uint32_t n = C.n();
 	std::vector<size_t> count_at(n + 1, 0);                  // mesh k's attributes from count_at[k] on
 	for(uint32_t k = 0; k < n; k++) count_at[k + 1] = count_at[k] + C.item(k).attrs.size();
@@ -676,13 +682,14 @@ int code_values(Chunk &C, int mode, std::vector<EncValueResult> &res) {
 		C.S.upload_ms += ms_since(t0);
 		if(any) ENC_TRY(C.sync());
 	} else cl = clers_layout(C.items, C.img, clers_at);
-	DevMem dclers;
+	DevMem dclers_local;
+	DevMem &dclers = keep ? keep->clers : dclers_local;           // under entropy NONE the symbols are a source of the device splice
 	if(cl) {
 		const auto t0 = Clock::now();
 		std::vector<uint8_t> h(cl);
 		for(uint32_t k = 0; k < n; k++) if(!C.item(k).clers.empty()) memcpy(h.data() + clers_at[k], C.item(k).clers.data(), C.item(k).clers.size());
 		C.S.host_stage_ms += ms_since(t0);
-		ENC_TRY(hipMalloc(&dclers.p, cl));
+		ENC_TRY(hipMalloc(&dclers.p, cl + 16));                   // (a source of the device splice: enc_splice.h, SOURCES)
 		ENC_TRY(hipMemcpyAsync(dclers.p, h.data(), cl, hipMemcpyHostToDevice, C.st));
 		ENC_TRY(C.sync());
 		C.S.bytes_to_device += cl;
@@ -705,23 +712,104 @@ int code_values(Chunk &C, int mode, std::vector<EncValueResult> &res) {
 		}
 	}
 	const auto t0 = Clock::now();
-	const int e = encode_value_streams_device(C.ctx, vs, res, C.tm);
+	const int e = keep ? encode_value_streams_resident(C.ctx, vs, *keep, C.tm) : encode_value_streams_device(C.ctx, vs, res, C.tm);
 	C.S.value_coder_ms += ms_since(t0);
 	if(e) return e;
 	C.S.value_streams += (uint32_t)vs.size();
 	return 0;
 }
 
+// crthip_encode_batch_to_device: where the blobs go and what the call has to say about them
+struct DeviceOut {
+	uint8_t *arena = nullptr;                                // the caller's device_out, checked; null: the call only sizes
+	uint64_t cap = 0;
+	uint64_t at = 0;                                         // the arena's running offset: chunks continue it
+	std::vector<uint32_t> len;                               // per item of the batch (0: failed)
+	crthip_splice_stats st{};
+	float kernel_ms = 0;
+};
+
+// The tail of a device-output chunk: the plan of every container (enc_splice.h) from the frames and from where `coded` says the payload
+// lies, one upload of job table + literal buffer, one launch of k_enc_splice.  Nothing is launched when the call only sizes or the arena
+// would not hold the chunk.  R: the value coder's images, slot.clers (entropy NONE).  W: the caller's arena.  Synchronised.
+int splice_to_device(Chunk &C, const DevCoded &coded, DeviceOut &D) {
+	const auto t_plan = Clock::now();
+	SplicePlan P(D.at);
+	size_t r = 0;
+	std::vector<SpliceSlot> slots;
+	std::vector<SpliceStream> streams;
+	for(uint32_t k = 0; k < C.n(); k++) {
+		const BatchItem &it = C.item(k);
+		if(it.status) continue;
+		slots.clear(); streams.clear();
+		for(const BatchStream &b : it.streams) {
+			slots.push_back(SpliceSlot{b.at, b.kind == BATCH_BITS});
+			if(b.kind == BATCH_BITS) continue;
+			const DevCodedStream &x = coded.streams[r++];
+			SpliceStream y;
+			y.bits = b.kind != CRTHIP_ENC_SYMBOLS; y.nwords = x.nwords; y.words = x.words;
+			for(const DevCodedBlock &blk : x.blocks) {
+				SplicePart h; h.host = blk.head.data(); h.bytes = blk.head.size(); y.parts.push_back(h);
+				if(blk.bytes) { SplicePart p; p.dev = blk.payload; p.bytes = blk.bytes; y.parts.push_back(p); }
+			}
+			streams.push_back(std::move(y));
+		}
+		const uint64_t len = P.item(it.frame.data(), it.frame.size(), slots.data(), slots.size(), streams.data(), it.split_words.data(), (uint32_t)it.split_words.size());
+		if(len > 0xFFFFFFFFull) return ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch_to_device: a blob of 4 GiB or more");
+		D.len[C.img.ids[k]] = (uint32_t)len;
+	}
+	D.at = P.at;
+	std::vector<SpliceJob> jobs;
+	std::vector<uint32_t> tile_start;
+	const bool write = D.arena && P.at <= D.cap && !P.pieces.empty();
+	// one host image, packed: jobs | tile_start | literal - what goes up is the job table and the literal bytes, nothing else (the jobs are
+	// multiples of 8 bytes, the tile starts of 4; the literal buffer follows the tables, so its first piece's aligned reads stay inside)
+	const uint64_t o_tiles = P.pieces.size()*sizeof(SpliceJob), o_lit = o_tiles + (P.pieces.size() + 1)*4;
+	const uint64_t up_bytes = o_lit + P.literal.size();
+	DevMem dev;
+	std::vector<uint8_t> h;
+	// `h` and `dev` are read by the queued copy and the launch: every way out below waits for the stream before they go
+	struct Wait { hipStream_t st; ~Wait() { (void)hipStreamSynchronize(st); } } wait{C.st};
+	uint64_t tiles = 0;
+	if(write) {
+		ENC_TRY(hipMalloc(&dev.p, up_bytes + 16));
+		tiles = splice_jobs(P, dev.u8() + o_lit, D.arena, jobs, tile_start);
+		if(tiles >= (1ull << 32) - 4) return ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch_to_device: too many tiles");
+		h.resize(up_bytes);
+		memcpy(h.data(), jobs.data(), jobs.size()*sizeof(SpliceJob));
+		memcpy(h.data() + o_tiles, tile_start.data(), tile_start.size()*4);
+		if(!P.literal.empty()) memcpy(h.data() + o_lit, P.literal.data(), P.literal.size());
+	} else tiles = splice_jobs(P, nullptr, nullptr, jobs, tile_start);       // (the statistics of a sizing call: the arena's alignment is the one promised)
+	C.S.host_frame_ms += (float)ms_since(t_plan);
+	D.st.pieces += (uint32_t)P.pieces.size(); D.st.jobs += (uint32_t)tiles;
+	D.st.literal_bytes += P.literal_bytes; D.st.device_bytes += P.device_bytes;
+	if(!write) return 0;
+	EventTimer t;
+	ENC_TRY(hipMemcpyAsync(dev.p, h.data(), up_bytes, hipMemcpyHostToDevice, C.st));
+	C.S.bytes_to_device += up_bytes;
+	if(t.begin(C.st)) return CRTHIP_E_DEVICE;
+	hipLaunchKernelGGL(k_enc_splice, dim3((uint32_t)((tiles + ESP_THREADS/ESP_LANES - 1)/(ESP_THREADS/ESP_LANES))), dim3(ESP_THREADS), 0, C.st,
+	                   (const SpliceJob *)dev.p, (const uint32_t *)(dev.u8() + o_tiles), (uint32_t)jobs.size());
+	if(t.end(C.st)) return CRTHIP_E_DEVICE;
+	ENC_TRY(hipGetLastError());
+	ENC_TRY(C.sync());
+	t.add_to(D.kernel_ms);
+	D.st.launches++;
+	return 0;
+}
+
 // the device half of one chunk: the items of img.ids have been set up; their topology passes run here, on the pool (overlapping the
 // device) or on the device
 int encode_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_list *extra, std::vector<BatchItem> &items, const ChunkImage &img, uint64_t budget,
-                 uint32_t threads, std::vector<std::vector<uint8_t>> &blobs, crthip_encode_batch_stats &S, BatchTimes &bt, EncStageTimes &tm) {
+                 uint32_t threads, std::vector<std::vector<uint8_t>> &blobs, crthip_encode_batch_stats &S, BatchTimes &bt, EncStageTimes &tm,
+                 DeviceOut *dout = nullptr) {
 	const int mode = ctx_encode_topology(ctx);
 	// the chunker sized this chunk by this very image, so only a single item can still be beyond the budget: nothing is allocated for it
 	if(img.total > budget) return ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: a mesh too big for the device image");
 	// Lifetimes, by declaration order (destruction runs upwards).  The pool thread's lambdas hold references to C (ready / mu / cv /
 	// topo_ms are its members) and through it to items and img: all declared before the thread, whose Joiner joins it on every way out.
 	// The image's memory is freed by DevMem only after Drain has waited for the work queued on it, and C's host buffers go after that.
+	DevCoded coded;                                                     // (device output) the coders' images: freed after the Drain
 	Chunk C{ctx, ctx_stream(ctx), meshes, extra, items, img, S, bt, tm};
 	for(uint32_t k : img.devk) C.ready[k] = 1;
 	if(img.resident) { const int e = fetch_indices(C); if(e) return e; }
@@ -753,8 +841,9 @@ int encode_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_l
 	if(!e) e = resort_tied_clouds(C);
 	if(!e) e = stage_delta(C);
 	std::vector<EncValueResult> res;
-	if(!e) e = code_values(C, mode, res);
+	if(!e) e = code_values(C, mode, res, dout ? &coded : nullptr);
 	if(e) return e;
+	if(dout) return splice_to_device(C, coded, *dout);
 
 	// splice: every container from its frame and its streams' results, in item order
 	const auto t_frame = Clock::now();
@@ -874,10 +963,21 @@ int input_pass(crthip_ctx *ctx, const crthip_mesh *meshes, const std::vector<uin
 
 } // namespace
 
-// resident: the data arrays of meshes / extra are DEVICE pointers (crthip_encode_batch_resident); everything else is the one path
+// what encode_batch_impl refuses a mesh for before any device work, but for the resident pointers
+static int batch_item_check(const crthip_mesh *m, const crthip_attr_list *extra, bool index_on_host) {
+	int e = encode_check(m, index_on_host);
+	if(!e) e = encode_check_attrs(m, extra, true);
+	if(!e && (uint64_t)m->nvert*3 > (1u << 26)) e = ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: too many vertices for the value coder");
+	if(!e && m->entropy == CRTHIP_ENTROPY_TUNSTALL && m->nvert > (1u << 23))
+		e = ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: a Tunstall stream longer than 2^23 symbols");
+	return e;
+}
+
+// resident: the data arrays of meshes / extra are DEVICE pointers (crthip_encode_batch_resident); dout: the blobs stay on the device
+// (crthip_encode_batch_to_device: out / cap / blob_offset are then unused); everything else is the one path
 static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra, uint32_t host_threads,
                                  uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert, uint32_t *out_nface,
-                                 int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times, bool resident) {
+                                 int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times, bool resident, DeviceOut *dout = nullptr) {
 	const auto t0 = Clock::now();
 	if(!ctx) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch: null context (there is no CPU fallback: use crthip_encode for the host encoder)");
 	if(!blob_offset || (n && !meshes)) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch: null argument");
@@ -939,16 +1039,26 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 	// chunks that fit the device
 	size_t free_b = 0, total_b = 0;
 	ENC_TRY(hipMemGetInfo(&free_b, &total_b));
-	const uint64_t budget = free_b/2;
+	uint64_t budget = free_b/2;
+	if(const uint64_t b = ctx_encode_image_budget(ctx)) budget = std::min(budget, b);   // (test hook: several chunks from a small batch)
 	std::vector<std::vector<uint8_t>> blobs(n);
 	EncStageTimes tm;
+	// Device output in several chunks: a chunk is spliced before the next one is coded, so the total is not known when the first one is
+	// written.  Where the arena is not known to hold any outcome (cap below crthip_encode_batch_bound) the call sizes first - the batch
+	// is encoded twice - and writes only if the total fits: nothing is written to an arena that proves too small.
+	if(dout && dout->arena && ok.size() > 1 && build_image(meshes, items, ok, resident).total > budget && dout->cap < crthip_encode_batch_bound(n, meshes, extra)) {
+		DeviceOut sizing;
+		sizing.cap = dout->cap; sizing.len.assign(n, 0);
+		const int64_t total = encode_batch_impl(ctx, n, meshes, extra, host_threads, nullptr, 0, blob_offset, out_nvert, out_nface, status, stats, times, resident, &sizing);
+		if(total < 0 || (uint64_t)total > dout->cap) { dout->len = sizing.len; dout->at = sizing.at; dout->st = sizing.st; return total; }
+	}
 	for(size_t k = 0; k < ok.size();) {
 		// a chunk is sized by building its image: of every item that is left (the usual case), else of half as many until the image fits
 		// (an image only grows with another item).  A single item beyond the budget fails where encode_chunk allocates.
 		size_t take = ok.size() - k;
 		ChunkImage img = build_image(meshes, items, std::vector<uint32_t>(ok.begin() + k, ok.end()), resident);
 		while(img.total > budget && take > 1) { take = (take + 1)/2; img = build_image(meshes, items, std::vector<uint32_t>(ok.begin() + k, ok.begin() + k + take), resident); }
-		const int e = encode_chunk(ctx, meshes, extra, items, img, budget, threads, blobs, S, bt, tm);
+		const int e = encode_chunk(ctx, meshes, extra, items, img, budget, threads, blobs, S, bt, tm, dout);
 		if(e) return e;
 		k += take;
 	}
@@ -959,11 +1069,12 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 		if(status) status[i] = items[i].status;
 		if(out_nvert) out_nvert[i] = items[i].status ? 0 : items[i].nvert;
 		if(out_nface) out_nface[i] = items[i].status ? 0 : items[i].nface;
-		if(items[i].status) continue;
+		if(items[i].status) { if(dout) dout->len[i] = 0; continue; }
 		if(out && w + blobs[i].size() <= cap) memcpy(out + w, blobs[i].data(), blobs[i].size());
 		w += blobs[i].size();
 	}
 	blob_offset[n] = w;
+	if(dout) w = dout->at;
 	S.bytes_to_device += tm.bytes_to_device; S.bytes_from_device += tm.bytes_from_device;
 	S.wall_ms = (float)ms_since(t0);
 	if(stats) *stats = S;
@@ -972,6 +1083,10 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 		for(int i = 0; i < K_COUNT; i++) if(bt.launches[i]) { times->name[c] = KERNEL_NAME[i]; times->ms[c] = bt.ms[i]; times->launches[c] = bt.launches[i]; c++; }
 		times->count = c;
 		enc_report_times(times, tm);
+		if(dout && dout->st.launches && times->count < CRTHIP_MAX_KERNELS) {
+			const uint32_t k = times->count++;
+			times->name[k] = "enc_splice"; times->ms[k] = dout->kernel_ms; times->launches[k] = dout->st.launches;
+		}
 	}
 	return (int64_t)w;
 }
@@ -1005,4 +1120,80 @@ extern "C" int64_t crthip_encode_batch(crthip_ctx *ctx, uint32_t n, const crthip
                                        uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert, uint32_t *out_nface,
                                        int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times) {
 	return crthip_encode_batch_attrs(ctx, n, meshes, nullptr, host_threads, out, cap, blob_offset, out_nvert, out_nface, status, stats, times);
+}
+
+// ---- crthip_encode_batch_to_device ----
+
+extern "C" int64_t crthip_encode_batch_to_device(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra, uint32_t host_threads,
+                                                 uint32_t flags, void *device_out, size_t cap, uint64_t *blob_offset, uint32_t *blob_len,
+                                                 uint32_t *out_nvert, uint32_t *out_nface, int32_t *status, crthip_encode_batch_stats *stats,
+                                                 crthip_kernel_times *times) {
+	try {
+		if(flags & ~CRTHIP_ENCODE_INPUTS_RESIDENT) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch_to_device: unknown flag bits");
+		if(n == 0) {                                                    // nothing is read or written, the context included
+			if(stats) memset(stats, 0, sizeof(*stats));
+			if(times) memset(times, 0, sizeof(*times));
+			if(ctx) ctx_splice_stats(ctx) = crthip_splice_stats{};
+			return 0;
+		}
+		if(!ctx) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch_to_device: null context (there is no CPU fallback)");
+		if(!blob_offset || !blob_len || !meshes) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch_to_device: null argument");
+		ctx_splice_stats(ctx) = crthip_splice_stats{};
+		ENC_TRY(hipSetDevice(ctx_device(ctx)));
+		if(device_out && !resident_array_ok(device_out, cap ? cap : 1, 16, ctx_device(ctx)))
+			return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch_to_device: device_out is not 16-byte aligned device memory of the context's device, "
+			                                   "or [device_out, device_out + cap) leaves its allocation");
+		DeviceOut D;
+		D.arena = (uint8_t *)device_out; D.cap = cap; D.len.assign(n, 0);
+		std::vector<uint64_t> unused(n + 1, 0);
+		const int64_t total = encode_batch_impl(ctx, n, meshes, extra, host_threads, nullptr, 0, unused.data(), out_nvert, out_nface, status, stats, times,
+		                                        (flags & CRTHIP_ENCODE_INPUTS_RESIDENT) != 0, &D);
+		if(total < 0) return total;
+		memcpy(blob_len, D.len.data(), (size_t)n*4);
+		const uint64_t laid = crthip_arena_layout(n, blob_len, blob_offset);
+		if(laid != (uint64_t)total) return ctx_fail(CRTHIP_E_DEVICE, "crthip_encode_batch_to_device: the plan and crthip_arena_layout disagree");
+		D.st.arena_bytes = (uint64_t)total; D.st.splice_kernel_us = D.kernel_ms*1000.0f;
+		ctx_splice_stats(ctx) = D.st;
+		return total;
+	} catch(const std::bad_alloc &) {
+		return ctx_fail(CRTHIP_E_NOMEM, nullptr);
+	} catch(...) {
+		return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch_to_device: internal error");
+	}
+}
+
+// one item's share of crthip_encode_batch_bound: its frame as batch_frame / batch_topology make it from the descriptor (every field of it has
+// a fixed width), and per slot the bounds the coders themselves check
+static uint64_t item_bound(const crthip_mesh *m, const crthip_attr_list *extra) {
+	if(batch_item_check(m, extra, false)) return 0;
+	BatchItem it;
+	const float step = 1.0f;                                           // (its four bytes are in the frame whatever it is; no array is read)
+	batch_setup(m, extra, it, &step);
+	if(is_mesh(it)) {
+		EncTopoRecord R;
+		memset(&R, 0, sizeof(R));
+		R.nvert = m->nvert; R.nface = m->nface;
+		std::vector<uint32_t> gend(std::max(m->ngroups, 1u), m->nface);
+		batch_frame(m, extra, it, R, m->ngroups ? m->group_end : gend.data(), gend.data());
+	} else batch_topology(m, extra, it);
+	const bool tun = it.entropy == CRTHIP_ENTROPY_TUNSTALL;
+	auto block = [&](uint64_t size) { return tun ? 9 + 2*256 + size + 1 : 4 + size; };
+	auto bits = [&](uint64_t words) { return 4 + 3 + 4*words; };
+	uint64_t b = it.frame.size() + 15;
+	for(const BatchStream &s : it.streams) {
+		if(s.kind == BATCH_BITS) b += bits(CRTHIP_TOPOLOGY_SPLIT_CAP(m->nface));
+		else if(s.attr == -1) b += block(CRTHIP_TOPOLOGY_CLERS_CAP(m->nface));
+		else if(s.kind == CRTHIP_ENC_SYMBOLS) b += block(m->nvert);
+		else b += bits((uint64_t)m->nvert*s.N + 1) + (s.kind == CRTHIP_ENC_ARRAY ? 1u : s.N)*block(m->nvert);
+	}
+	return (b + 15) & ~15ull;
+}
+
+extern "C" uint64_t crthip_encode_batch_bound(uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra) {
+	if(!meshes) return 0;
+	uint64_t total = 0;
+	for(uint32_t i = 0; i < n; i++) {
+		try { total += item_bound(&meshes[i], extra ? &extra[i] : nullptr); } catch(...) {}
+	}
+	return total;
 }

@@ -29,8 +29,10 @@ namespace {
 
 
 // Tunstall blocks of n DEVICE-resident byte streams.  blocks[i] = "u8 nsym | nsym x (symbol, probability) | i32 size | i32 csize | codewords"
+// keep != null (crthip_encode_batch_to_device): the codewords stay on the device, in an image that `keep` then owns - blocks[i] is the
+// header alone, payload[i] the codewords' device address, and their count is the header's csize field
 int tun_encode_device(hipStream_t st, uint32_t n, const uint8_t *const *d_src, const uint32_t *sizes,
-                      std::vector<std::vector<uint8_t>> &blocks, EncStageTimes &tm) {
+                      std::vector<std::vector<uint8_t>> &blocks, EncStageTimes &tm, DevMem *keep = nullptr, std::vector<const uint8_t *> *payload = nullptr) {
 	blocks.assign(n, std::vector<uint8_t>());
 	for(uint32_t i = 0; i < n; i++)
 		if(sizes[i] > (1u << 23)) return ctx_fail(CRTHIP_E_LIMIT, "Tunstall encoder: stream longer than 2^23 symbols (the reference's count*255 overflows int)");
@@ -44,7 +46,8 @@ int tun_encode_device(hipStream_t st, uint32_t n, const uint8_t *const *d_src, c
 	for(uint32_t i = 0; i < n; i++)
 		for(uint32_t b = 0; b < sizes[i]; b += ENC_HIST_CHUNK) chunks.push_back(EncChunk{d_src[i] + b, std::min(ENC_HIST_CHUNK, sizes[i] - b), i});
 	o += (chunks.size()*sizeof(EncChunk) + 15) & ~15ull;
-	DevMem work;
+	DevMem work_local;
+	DevMem &work = keep ? *keep : work_local;
 	EventTimer t_hist, t_tables, t_trie, t_parse;
 	ENC_TRY(hipMalloc(&work.p, o + 16));
 	uint8_t *base = work.u8();
@@ -163,8 +166,10 @@ int tun_encode_device(hipStream_t st, uint32_t n, const uint8_t *const *d_src, c
 		hipLaunchKernelGGL(k_enc_tun_parse, dim3(ngpu), dim3(64), lds, st, (const EncStream *)(tb + o_streams), ngpu, trie_lds);
 		if(t_parse.end(st)) return CRTHIP_E_DEVICE;
 		ENC_TRY(hipMemcpyAsync(csize.data(), base + o_csize, (size_t)n*4, hipMemcpyDeviceToHost, st));
-		h_codes.resize(o_csize - dst_off[0]);
-		ENC_TRY(hipMemcpyAsync(h_codes.data(), base + dst_off[0], h_codes.size(), hipMemcpyDeviceToHost, st));
+		if(!keep) {
+			h_codes.resize(o_csize - dst_off[0]);
+			ENC_TRY(hipMemcpyAsync(h_codes.data(), base + dst_off[0], h_codes.size(), hipMemcpyDeviceToHost, st));
+		}
 		ENC_TRY(hipStreamSynchronize(st));
 		ENC_TRY(hipGetLastError());
 		if(t_parse.add_to(tm.parse)) tm.any_parse = true;
@@ -173,17 +178,19 @@ int tun_encode_device(hipStream_t st, uint32_t n, const uint8_t *const *d_src, c
 	if(t_hist.add_to(tm.hist)) tm.any_hist = true;
 
 	// block framing (src/cstream.cpp:96-107)
+	if(payload) payload->assign(n, nullptr);
 	for(uint32_t i = 0; i < n; i++) {
 		const TunEncoderTables &T = tabs[i];
 		const uint32_t cs = T.nsym >= 2 ? csize[i] : 0u;
 		if(cs > sizes[i] + 1) return ctx_fail(CRTHIP_E_DEVICE, "k_enc_tun_parse produced an impossible codeword count");
 		std::vector<uint8_t> &b = blocks[i];
-		b.resize(9 + (size_t)T.nsym*2 + cs);
+		b.resize(9 + (size_t)T.nsym*2 + (keep ? 0u : cs));
 		b[0] = (uint8_t)T.nsym;
 		memcpy(&b[1], T.probs, (size_t)T.nsym*2);
 		memcpy(&b[1 + T.nsym*2], &sizes[i], 4);
 		memcpy(&b[5 + T.nsym*2], &cs, 4);
-		if(cs) memcpy(&b[9 + T.nsym*2], h_codes.data() + (dst_off[i] - dst_off[0]), cs);
+		if(cs && !keep) memcpy(&b[9 + T.nsym*2], h_codes.data() + (dst_off[i] - dst_off[0]), cs);
+		if(cs && payload) (*payload)[i] = base + dst_off[i];
 	}
 	return CRTHIP_OK;
 }
@@ -266,10 +273,12 @@ int corto_hip::quantize_device(crthip_ctx *ctx, const std::vector<QuantRequest> 
 }
 
 // bit-width logs + bit packing of n DEVICE-resident value arrays, then the Tunstall coder over the logs (or raw logs for entropy NONE).
-// The caller has set the device and quiesced the context.  Words and raw logs come back compacted, in one copy each.
-int corto_hip::encode_value_streams_device(crthip_ctx *ctx, const std::vector<DevValueStream> &in, std::vector<EncValueResult> &res, EncStageTimes &tm) {
+// The caller has set the device and quiesced the context.  Words and raw logs come back compacted, in one copy each - or, with keep
+// (encode_value_streams_resident), nothing of them comes back: keep gets their device addresses and owns the images.
+static int value_streams_impl(crthip_ctx *ctx, const std::vector<DevValueStream> &in, std::vector<EncValueResult> &res, EncStageTimes &tm, DevCoded *keep) {
 	const uint32_t n = (uint32_t)in.size();
 	res.assign(n, EncValueResult());
+	if(keep) keep->streams.assign(n, DevCodedStream());
 	hipStream_t st = ctx_stream(ctx);
 	// device image: logs | words | word counts | jobs
 	std::vector<uint64_t> l_off(n), w_off(n);
@@ -282,7 +291,8 @@ int corto_hip::encode_value_streams_device(crthip_ctx *ctx, const std::vector<De
 	const uint64_t o_jobs = o;
 	std::vector<PackJob> jobs;
 	std::vector<uint32_t> job_stream;
-	DevMem dev;
+	DevMem dev_local;
+	DevMem &dev = keep ? keep->image : dev_local;
 	EventTimer t_pack;
 	for(uint32_t i = 0; i < n; i++) if(nlogs[i] && in[i].count) { jobs.push_back(PackJob{}); job_stream.push_back(i); }
 	o += (jobs.size()*sizeof(PackJob) + 15) & ~15ull;
@@ -320,6 +330,7 @@ int corto_hip::encode_value_streams_device(crthip_ctx *ctx, const std::vector<De
 	for(uint32_t i = 0; i < n; i++) {
 		if(!nlogs[i]) continue;
 		if((uint64_t)nwords[i] > (uint64_t)in[i].count*in[i].components + 1) return ctx_fail(CRTHIP_E_DEVICE, "k_enc_pack produced an impossible word count");
+		if(keep) { keep->streams[i].nwords = nwords[i]; keep->streams[i].words = base + w_off[i]; continue; }
 		res[i].words.resize(nwords[i]);
 		at_words[i] = back;
 		if(nwords[i]) { gather.push_back(CopyJob{base + w_off[i], nullptr, (uint64_t)nwords[i]*4, back}); back += (uint64_t)nwords[i]*4; }
@@ -330,11 +341,18 @@ int corto_hip::encode_value_streams_device(crthip_ctx *ctx, const std::vector<De
 	for(uint32_t i = 0; i < n; i++) {
 		const uint32_t nb = nlogs[i] ? nlogs[i] : 1u;
 		res[i].blocks.resize(nb);
+		if(keep) keep->streams[i].blocks.resize(nb);
 		for(uint32_t c = 0; c < nb; c++) {
 			const uint8_t *src = nlogs[i] ? base + l_off[i] + (uint64_t)c*in[i].count : (const uint8_t *)in[i].values;
 			const uint32_t size = in[i].count;
 			if(in[i].entropy == CRTHIP_ENTROPY_TUNSTALL) { d_src.push_back(src); sizes.push_back(size); owner.push_back({i, c}); }
 			else {                                                     // OutStream::compress with entropy NONE: i32 size | bytes (cstream.cpp:43-64)
+				if(keep) {
+					DevCodedBlock &k = keep->streams[i].blocks[c];
+					k.head.resize(4); memcpy(k.head.data(), &size, 4);
+					k.payload = src; k.bytes = size;
+					continue;
+				}
 				std::vector<uint8_t> &b = res[i].blocks[c];
 				b.resize(4 + (size_t)size);
 				memcpy(b.data(), &size, 4);
@@ -363,11 +381,28 @@ int corto_hip::encode_value_streams_device(crthip_ctx *ctx, const std::vector<De
 	}
 	if(!d_src.empty()) {
 		std::vector<std::vector<uint8_t>> blocks;
-		{ const int e = tun_encode_device(st, (uint32_t)d_src.size(), d_src.data(), sizes.data(), blocks, tm); if(e) return e; }
-		for(size_t k = 0; k < blocks.size(); k++) { tm.bytes_from_device += blocks[k].size(); res[owner[k].first].blocks[owner[k].second] = std::move(blocks[k]); }
+		std::vector<const uint8_t *> payload;
+		{ const int e = tun_encode_device(st, (uint32_t)d_src.size(), d_src.data(), sizes.data(), blocks, tm, keep ? &keep->tun_image : nullptr, keep ? &payload : nullptr); if(e) return e; }
+		for(size_t k = 0; k < blocks.size(); k++) {
+			tm.bytes_from_device += blocks[k].size();                 // (keep: the header alone - its table and its two counts)
+			if(keep) {
+				DevCodedBlock &b = keep->streams[owner[k].first].blocks[owner[k].second];
+				memcpy(&b.bytes, blocks[k].data() + blocks[k].size() - 4, 4);   // csize
+				b.payload = payload[k]; b.head = std::move(blocks[k]);
+			} else res[owner[k].first].blocks[owner[k].second] = std::move(blocks[k]);
+		}
 	}
 	ENC_TRY(hipStreamSynchronize(st));
 	return CRTHIP_OK;
+}
+
+int corto_hip::encode_value_streams_device(crthip_ctx *ctx, const std::vector<DevValueStream> &in, std::vector<EncValueResult> &res, EncStageTimes &tm) {
+	return value_streams_impl(ctx, in, res, tm, nullptr);
+}
+
+int corto_hip::encode_value_streams_resident(crthip_ctx *ctx, const std::vector<DevValueStream> &in, DevCoded &out, EncStageTimes &tm) {
+	std::vector<EncValueResult> none;
+	return value_streams_impl(ctx, in, none, tm, &out);
 }
 
 // the same over HOST arrays, one entropy for all of them (crthip_encode_values, crthip_encode_gpu): the values go up in one copy

@@ -957,6 +957,52 @@ void corto_hip::tun_encoder_tables(const uint32_t counts[256], uint32_t size, Tu
 	out.offsets.assign(t.offsets.begin(), t.offsets.end());
 }
 
+// crthip_encode_splice_model's front: crthip_encode_gpu's deferred run with the quantisation on the host, then every recorded stream through
+// the writers crthip_encode itself uses (put_symbols / put_array / put_values into a sink of its own: at position 0 a bit stream needs no
+// padding), taken apart again into bit words and blocks
+int corto_hip::encode_host_coded(const crthip_mesh *m, const crthip_attr_list *extra, HostCodedItem &o) {
+	{ const int e = encode_check(m); if(e) return e; }
+	{ const int e = encode_check_attrs(m, extra, false); if(e) return e; }
+	Encoder E;
+	std::vector<Deferred> deferred;
+	E.s.defer = &deferred;
+	std::vector<NamedQuant> named;
+	setup(m, extra, E, named, true, nullptr);
+	for(const NamedQuant &q : named) quantize_host(q.r);
+	E.header();
+	if(E.nface > 0) E.encode_mesh(); else E.encode_cloud();
+	o = HostCodedItem();
+	o.entropy = E.entropy; o.nvert = E.nvert; o.nface = E.nface;
+	for(const Deferred &d : deferred) {
+		o.slots.push_back(d);
+		if(d.kind == BATCH_BITS) { o.split_words = d.words; continue; }
+		Sink t;
+		if(d.kind == CRTHIP_ENC_SYMBOLS) put_symbols(t, E.entropy, d.bytes.data(), d.count);
+		else if(d.kind == CRTHIP_ENC_ARRAY) put_array(t, E.entropy, d.count, d.ints.data(), (int)d.N);
+		else if(d.kind == CRTHIP_ENC_VALUES_I8) put_values<int8_t>(t, E.entropy, d.count, (const int8_t *)d.bytes.data(), (int)d.N);
+		else put_values<int32_t>(t, E.entropy, d.count, d.ints.data(), (int)d.N);
+		EncValueResult r;
+		size_t p = 0;
+		auto u32 = [&](size_t at) { uint32_t v; memcpy(&v, &t.b[at], 4); return v; };
+		if(d.kind != CRTHIP_ENC_SYMBOLS) {
+			const uint32_t nw = u32(0);
+			r.words.resize(nw);
+			if(nw) memcpy(r.words.data(), &t.b[4], (size_t)nw*4);
+			p = 4 + (size_t)nw*4;
+		}
+		while(p < t.b.size()) {                                   // the blocks, one after another
+			size_t len;
+			if(E.entropy == CRTHIP_ENTROPY_NONE) len = 4 + (size_t)u32(p);
+			else { const size_t nsym = t.b[p]; len = 9 + 2*nsym + (size_t)u32(p + 5 + 2*nsym); }
+			r.blocks.emplace_back(t.b.begin() + p, t.b.begin() + p + len);
+			p += len;
+		}
+		o.res.push_back(std::move(r));
+	}
+	o.frame.swap(E.s.b);
+	return CRTHIP_OK;
+}
+
 // ---- crthip_encode_batch's host half (encode_batch.cpp runs the rest on the device) ----
 
 void corto_hip::morton_order_host(const int32_t *coords, uint32_t nvert, std::vector<uint32_t> &order) {   // src/encoder.cpp:238-262

@@ -74,6 +74,15 @@ struct DevValueStream { uint32_t kind = 0, count = 0, components = 1, entropy = 
 struct EncStageTimes { float hist = 0, parse = 0, pack = 0, tables = 0, trie = 0; bool any_hist = false, any_parse = false, any_pack = false, any_tables = false;
                        uint32_t host_table_streams = 0; uint64_t bytes_to_device = 0, bytes_from_device = 0; };
 int encode_value_streams_device(crthip_ctx *ctx, const std::vector<DevValueStream> &in, std::vector<EncValueResult> &res, EncStageTimes &tm);
+// ... with the payload left where the coders made it (crthip_encode_batch_to_device): per stream the device addresses and sizes of its bit
+// words and of every block's payload (codewords; raw logs / symbols under entropy NONE), and the blocks' headers, which the host makes.
+// Only the word counts, the codeword counts and what the host-made tables need come back: no k_enc_gather, no copy of words, logs or
+// codewords.  `out` owns the allocations the addresses point into and must outlive whoever reads them; each has 16 bytes behind its last
+// region and a 256-byte aligned base (enc_splice.h: SOURCES).
+struct DevCodedBlock { std::vector<uint8_t> head; const uint8_t *payload = nullptr; uint32_t bytes = 0; };
+struct DevCodedStream { uint32_t nwords = 0; const uint8_t *words = nullptr; std::vector<DevCodedBlock> blocks; };   // words: null for a symbol stream
+struct DevCoded { std::vector<DevCodedStream> streams; DevMem image, tun_image, clers; };   // clers: the batch's host-mode CLERS block (encode_batch.cpp)
+int encode_value_streams_resident(crthip_ctx *ctx, const std::vector<DevValueStream> &in, DevCoded &out, EncStageTimes &tm);
 void enc_report_times(crthip_kernel_times *times, const EncStageTimes &tm);   // appends the stages' entries behind times->count
 
 // ---- crthip_encode_batch (encoder.cpp: checks, topology pass and container; encode_batch.cpp: the device half) ----
@@ -137,6 +146,13 @@ size_t splice_container(const std::vector<uint8_t> &frame, const std::vector<Slo
 	return r;
 }
 
+// One item through the host encoder in its deferred mode, each recorded stream then coded by the host encoder's own writers
+// (crthip_encode_splice_model): the frame, the slots, a result per slot but the split bits (blocks whole, header included), the split words.
+// Runs encode_check / encode_check_attrs first; returns their code.
+struct HostCodedItem { std::vector<uint8_t> frame; std::vector<BatchStream> slots; std::vector<EncValueResult> res; std::vector<uint32_t> split_words;
+                       uint32_t entropy = 0, nvert = 0, nface = 0; };
+int encode_host_coded(const crthip_mesh *m, const crthip_attr_list *extra, HostCodedItem &out);
+
 // the host encoder's topology pass alone (crthip_encode_topology_model, which = 0); split_bits before the final flush
 struct TopologyModel { std::vector<uint32_t> faces, group_end, quads, split_words; std::vector<uint8_t> clers; uint32_t nvert = 0, nface = 0, max_front = 0; uint64_t split_bits = 0; };
 void topology_host_model(const crthip_mesh *m, TopologyModel &out);
@@ -159,6 +175,8 @@ int decode_host_many(crthip_ctx *ctx, uint32_t n, HostDecodeReq *reqs, bool copy
 
 // context plumbing (batch.cpp); ctx_fail is declared at the top
 int ctx_device(crthip_ctx *ctx);
+crthip_splice_stats &ctx_splice_stats(crthip_ctx *ctx);   // of the last crthip_encode_batch_to_device on the context
+uint64_t ctx_encode_image_budget(crthip_ctx *ctx);   // $CORTO_ENCODE_IMAGE_BUDGET (debug_config.h), 0: none
 int ctx_encode_topology(crthip_ctx *ctx);   // CRTHIP_TOPOLOGY_* of crthip_ctx_set_encode_topology
 hipStream_t ctx_stream(crthip_ctx *ctx);
 int ctx_quiesce(crthip_ctx *ctx);       // wait for whatever batch is in flight on the context

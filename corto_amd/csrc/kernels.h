@@ -186,4 +186,10 @@ struct EncInputJob;
 __global__ void k_enc_input_check(const EncInputJob *jobs, const uint32_t *block_start, uint32_t njobs);
 __global__ void k_enc_input_reduce(const EncInputJob *jobs, const uint32_t *ids, uint32_t nids);
 
+
+// k_encode_splice.hip (crthip_encode_batch_to_device): the containers' pieces into the caller's device arena (enc_splice.h); one wave per
+// tile of ESP_TILE destination bytes, tile_start[j]: the first tile of job j (njobs + 1 entries)
+struct SpliceJob;
+__global__ void k_enc_splice(const SpliceJob *jobs, const uint32_t *tile_start, uint32_t njobs);
+
 } // namespace corto_hip

@@ -41,7 +41,8 @@ extern "C" {
                                      added within 6: crthip_generic_attr, crthip_attr_list, crthip_encode_attrs, crthip_encode_gpu_attrs,
                                      crthip_encode_batch_attrs, crthip_batch_create_resident, crthip_batch_reset_resident, crthip_batch_exif,
                                      crthip_batch_groups, crthip_batch_group_props, crthip_batch_walk_stats, crthip_batch_decode_with_next,
-                                     crthip_batch_set_parity, crthip_encode_batch_resident, crthip_encode_input_model */
+                                     crthip_batch_set_parity, crthip_encode_batch_resident, crthip_encode_input_model,
+                                     crthip_encode_batch_to_device, crthip_encode_batch_bound, crthip_ctx_encode_splice_stats */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -565,10 +566,56 @@ int64_t crthip_encode_batch_attrs(crthip_ctx *ctx, uint32_t n, const crthip_mesh
  *   - with nvert == 0 the position pointer only has to be non-NULL and is never dereferenced: the step of position_bits > 0 is then 0.0f,
  *     which is what the host computes from any finite position[0].
  * Per-mesh errors keep their codes: a face index >= nvert, now found on the device, is CRTHIP_E_ARGUMENT with an empty range, and the
- * neighbouring meshes are still encoded.  The blobs are spliced on the host and returned in host memory. */
+ * neighbouring meshes are still encoded.  The blobs are spliced on the host and returned in host memory (crthip_encode_batch_to_device
+ * below leaves them in device memory). */
 int64_t crthip_encode_batch_resident(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra /* n lists or NULL */,
                                      uint32_t host_threads, uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert,
                                      uint32_t *out_nface, int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times);
+
+/* crthip_encode_batch_attrs / crthip_encode_batch_resident with the blobs left in DEVICE memory (ABI 6 addition): the containers are
+ * spliced on the GPU (kernel enc_splice in crthip_kernel_times) from where the coders made their payload, so a producer on the GPU can hand
+ * its blobs to crthip_batch_create_resident without a copy back and a copy up.  Only what the host needs to lay the containers out comes
+ * back (the streams' word and codeword counts, the Tunstall tables' records); what the host makes itself - frames, word counts, padding,
+ * split words, block headers - goes up once, as one literal buffer beside the job table.
+ *   flags       0: the data arrays of meshes / extra are HOST arrays, as in crthip_encode_batch_attrs;
+ *               CRTHIP_ENCODE_INPUTS_RESIDENT: they are DEVICE arrays - the rules, checks and per-mesh errors of crthip_encode_batch_resident;
+ *               any other bit: CRTHIP_E_ARGUMENT
+ *   device_out  16-byte aligned device memory of the context's device, [device_out, device_out + cap) inside one allocation: checked with
+ *               the runtime's pointer queries before the first launch, else CRTHIP_E_ARGUMENT for the call and never a fault.  NULL sizes only.
+ *   blob_offset, blob_len   n entries each, HOST memory: blob i is the blob_len[i] bytes at device_out + blob_offset[i], byte-identical to
+ *               crthip_encode_attrs of that item.  The offsets are crthip_arena_layout(n, blob_len, ...): every blob starts on a 16-byte multiple,
+ *               and the bytes from a blob's end to the next multiple are written as zeros - crthip_batch_create_resident(ctx, n, device_out,
+ *               blob_offset, blob_len, ...) takes the three arrays as they are.
+ * Returns the arena's total (what crthip_arena_layout returns).  When it exceeds cap nothing is written to device_out and the total is still
+ * returned, as crthip_encode_batch does.  A failed mesh gets its code in status[i] and blob_len[i] = 0; its neighbours are still encoded.
+ * The three topology modes give the same bytes.  The call returns with everything it queued drained.  out_nvert, out_nface, status,
+ * stats and times are crthip_encode_batch's (host_frame_ms: the plan; bytes_to_device includes the literal buffer, literal_bytes, and the
+ * job table: 24 bytes a piece and 4 a tile start, pieces + 1 of them - nothing else goes up for the splice).
+ * When not to use it: a caller who wants the blobs in host memory anyway (a file, a socket) - crthip_encode_batch copies back once;
+ * this call followed by a copy back moves the same bytes and adds a launch. */
+#define CRTHIP_ENCODE_INPUTS_RESIDENT 1u   /* the data arrays are DEVICE pointers: the rules of crthip_encode_batch_resident */
+int64_t crthip_encode_batch_to_device(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra /* n lists or NULL */,
+                                      uint32_t host_threads, uint32_t flags, void *device_out, size_t cap,
+                                      uint64_t *blob_offset /* n */, uint32_t *blob_len /* n */, uint32_t *out_nvert, uint32_t *out_nface,
+                                      int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times);
+/* Bytes that the arena total of crthip_encode_batch_to_device with the same arguments can never exceed, from the descriptors alone (host
+ * only, no device; with resident inputs the data arrays are not read): allocate once instead of encoding twice.  Per item: the container
+ * without its streams (header, attribute table, groups with their properties, exif) + CRTHIP_TOPOLOGY_CLERS_CAP(nface) symbols +
+ * CRTHIP_TOPOLOGY_SPLIT_CAP(nface) words + per value stream count*N + 1 bit words (the value coder's own check) + per Tunstall block
+ * 9 + 2*256 + size + 1 bytes (the Tunstall coder's own check; 4 + size under entropy NONE) + 15 bytes of padding.  A mesh the checks of
+ * crthip_encode_batch would refuse from its descriptor contributes 0. */
+uint64_t crthip_encode_batch_bound(uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra);
+/* The splice of the last crthip_encode_batch_to_device on the context (all of its chunks). */
+typedef struct {
+	uint32_t pieces;             /* stretches of the arena with one source: a run of host-made bytes, or one payload on the device */
+	uint32_t jobs;               /* the pieces after tiling: waves of enc_splice */
+	uint64_t literal_bytes;      /* host-made bytes: the literal buffer, uploaded once and packed (this is its size on the link) */
+	uint64_t device_bytes;       /* bytes moved from device sources */
+	uint64_t arena_bytes;        /* literal_bytes + device_bytes = the call's return value */
+	float splice_kernel_us;      /* device time of enc_splice */
+	uint32_t launches;           /* launches of enc_splice: one a chunk */
+} crthip_splice_stats;
+int crthip_ctx_encode_splice_stats(const crthip_ctx *ctx, crthip_splice_stats *s);
 
 /* Where crthip_encode_batch / crthip_encode_batch_attrs / crthip_encode_batch_resident on this context run a mesh's CLERS topology pass (degenerate faces, half-edge
  * pairing, the walk that writes the CLERS symbols, split bits, vertex numbering and prediction quads).  Same bytes in every mode.
@@ -623,6 +670,22 @@ typedef struct {
 	uint32_t reserved;
 } crthip_encode_input_result;
 int crthip_encode_input_model(const crthip_mesh *m, int which, crthip_encode_input_result *r);
+
+/* (test hooks, no device needed)  The splice of crthip_encode_batch_to_device on the host.  crthip_encode_splice_model runs the host encoder
+ * in its deferred mode, codes each recorded stream with the host encoder's own writers, then runs the plan and the mover of csrc/enc_splice.h
+ * in the kernel's partition - the same tiles, lanes walked in a loop, tiles in a shuffled order - with the payload in buffers of its own
+ * and the arena at an address that is dst_misalign (0..15) bytes off a 16-byte boundary.  Writes the blob and the zeros to the next
+ * 16-byte multiple to out (cap >= that) and returns the blob's length, which must equal crthip_encode_attrs byte for byte; < 0 on error.
+ * crthip_splice_copy_model moves `bytes` bytes from src to dst with the mover alone, tiles shuffled; it reads up to 3 bytes on either
+ * side of the source (enc_splice.h: SOURCES).
+ * crthip_encode_splice_plan_model plans n items in chunks of chunk_items (0: one chunk), each chunk a plan of its own that continues
+ * the arena where the one before it ended, as a batch beyond one device image does: blob_offset / blob_len as
+ * crthip_encode_batch_to_device gives them, the statistics summed over the chunks, and up to piece_cap pieces as (arena offset, bytes,
+ * 1 literal | 0 device) triples; returns the pieces' count. */
+int64_t crthip_encode_splice_model(const crthip_mesh *mesh, const crthip_attr_list *extra, uint32_t dst_misalign, uint8_t *out, size_t cap);
+int crthip_splice_copy_model(const uint8_t *src, uint8_t *dst, uint64_t bytes, uint32_t seed);
+int64_t crthip_encode_splice_plan_model(uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra, uint64_t *blob_offset, uint32_t *blob_len,
+                                        crthip_splice_stats *stats, uint64_t *pieces /* 3 per piece */, size_t piece_cap, uint32_t chunk_items);
 
 #ifdef __cplusplus
 }

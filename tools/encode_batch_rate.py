@@ -16,6 +16,13 @@ crthip_encode_batch_resident on the same arrays in one device buffer; (c) what s
 copy of all inputs, then (a), or then crthip_encode on 16 host threads.  With the device time of the input pass's kernels, both calls'
 stats, and whether (b)'s blobs equal (a)'s.  Needs a device: there is nothing to fall back to.
 
+    python tools/encode_batch_rate.py --device-out [--out FILE] [--reps 3]
+
+--device-out: two routes from meshes in device memory to a decodable resident batch, over the five workloads and the three topology modes,
+taken in turn within every repetition and every repetition recorded: (a) crthip_encode_batch_resident (blobs to the host), upload_arena,
+Batch.resident - what such a producer had to do before; (b) crthip_encode_batch_to_device, Batch.resident.  With each route's parts, the
+device time of enc_splice, the splice statistics, both calls' stats, and whether (b)'s arena holds (a)'s blobs.  Needs a device.
+
 For each workload: the batch call's wall time, its stats and per-kernel times (of the same run), beside crthip_encode on one
 host thread and on 16 (ctypes releases the GIL), crthip_encode_gpu mesh by mesh, and the reference encoder on one core when
 oracle/_ref is present; every leg is the best of --reps runs.  Every batch blob is checked against crthip_encode's bytes."""
@@ -168,15 +175,73 @@ def resident_axis(reps):
     return recs
 
 
+def device_out_axis(reps):
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("encode_batch_rate.py --device-out: no device (the device encoder has no CPU fallback)")
+    recs = []
+    clock = time.perf_counter
+    for name, meshes, kw in workloads():
+        buf, dev, _ = place_on_device(meshes)
+        out = torch.empty(max(ca.encode_batch_bound(dev, kw=kw), 16), dtype=torch.uint8, device="cuda:0")   # allocated once: a producer reuses its arena
+        for mode in ("host", "device", "split"):
+            ctx = ca.Context(0)
+            ctx.set_profiling(True)
+            ctx.set_encode_topology(mode)
+            ca.encode_batch_resident(dev[:1], ctx, kw=kw); ca.encode_batch_to_device(dev[:1], ctx, kw=kw, out=out)      # warm the context and the kernels
+            legs = {k: [] for k in ("a_total", "a_encode_resident", "a_upload_arena", "a_batch_resident", "b_total", "b_encode_to_device", "b_batch_resident")}
+            best_a = best_b = None
+            identical = True
+            for _ in range(reps):
+                t0 = clock()
+                blobs, st_a = ca.encode_batch_resident(dev, ctx, kw=kw, with_stats=True)
+                t1 = clock()
+                arena = ca.upload_arena(blobs)
+                t2 = clock()
+                offs_a, _ = ca.arena_layout([len(b) for b in blobs])
+                ba = ca.Batch.resident(ctx, arena, offs_a, [len(b) for b in blobs])
+                t3 = clock()
+                ba.close()
+                for k, v in (("a_total", t3 - t0), ("a_encode_resident", t1 - t0), ("a_upload_arena", t2 - t1), ("a_batch_resident", t3 - t2)):
+                    legs[k].append(round(v * 1e3, 3))
+                if best_a is None or t3 - t0 < best_a[0]:
+                    best_a = (t3 - t0, st_a)
+                t0 = clock()
+                o, offs, lens, st_b = ca.encode_batch_to_device(dev, ctx, kw=kw, out=out, with_stats=True)
+                t1 = clock()
+                bb = ca.Batch.resident(ctx, o, offs, lens)
+                t2 = clock()
+                bb.close()
+                for k, v in (("b_total", t2 - t0), ("b_encode_to_device", t1 - t0), ("b_batch_resident", t2 - t1)):
+                    legs[k].append(round(v * 1e3, 3))
+                if best_b is None or t2 - t0 < best_b[0]:
+                    best_b = (t2 - t0, st_b)
+                identical = identical and offs.tolist() == offs_a.tolist() and bool(torch.equal(o[:st_b["total"]], arena[:st_b["total"]]))
+            pick = lambda st: {k: (round(v, 3) if isinstance(v, float) else v) for k, v in st.items() if k not in ("kernel_times", "splice")}
+            sb = best_b[1]
+            rec = dict(workload=name, mode=mode, items=len(meshes), arena_bytes=sb["total"], reps_ms=legs, best_ms={k: min(v) for k, v in legs.items()},
+                       a_spread_ms=round(max(legs["a_total"]) - min(legs["a_total"]), 3), b_minus_a_ms=round(min(legs["b_total"]) - min(legs["a_total"]), 3),
+                       arena_identical_to_route_a=identical, enc_splice=sb["kernel_times"].get("enc_splice"),
+                       splice={k: (round(v, 3) if isinstance(v, float) else v) for k, v in sb["splice"].items()},
+                       stats_resident=pick(best_a[1]), stats_to_device=pick(sb))
+            print(json.dumps(rec), flush=True)
+            recs.append(rec)
+            ctx.close()
+        del buf, dev, out
+    return recs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--topology", action="store_true", help="the topology mode x host_threads table of the mesh workloads")
     ap.add_argument("--resident", action="store_true", help="host arrays against arrays in device memory against copying those back first")
+    ap.add_argument("--device-out", action="store_true", help="blobs to the host and back up against blobs spliced on the device, up to a resident batch")
     a = ap.parse_args()
-    if a.topology or a.resident:
-        recs = resident_axis(a.reps) if a.resident else topology_axis(a.reps)
+    if a.topology or a.resident or a.device_out:
+        recs = device_out_axis(a.reps) if a.device_out else resident_axis(a.reps) if a.resident else topology_axis(a.reps)
         if a.out:
             with open(a.out, "w") as f:
                 for r in recs:
