@@ -16,12 +16,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 class Probe:
-    """tests/cpp/size_class_probe.cpp, built into `workdir` and kept running: one query a line"""
+    """tests/cpp/size_class_probe.cpp (or another probe of tests/cpp: `source`), built into `workdir` and kept running: one query a line"""
 
-    def __init__(self, workdir):
-        exe = os.path.join(str(workdir), "size_class_probe")
+    def __init__(self, workdir, source="size_class_probe"):
+        exe = os.path.join(str(workdir), source)
         subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-I", os.path.join(ROOT, "corto_amd", "csrc"),
-                               os.path.join(ROOT, "tests", "cpp", "size_class_probe.cpp"), "-o", exe])
+                               os.path.join(ROOT, "tests", "cpp", source + ".cpp"), "-o", exe])
         self.p = subprocess.Popen([exe], stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
 
     def ask(self, *q):

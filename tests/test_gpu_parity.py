@@ -9,6 +9,7 @@ import pytest
 
 import corto_amd as ca
 from conftest import ALL_CASES, CLOUD_CASES, MESH_CASES, GOLDEN, aligned, load_golden
+from cstream_model import model_array as _model_array, model_values as _model_values      # (shared with the encode size-class modules)
 from oracle import oracle as oc
 
 pytestmark = pytest.mark.gpu
@@ -1261,46 +1262,6 @@ def test_tunstall_encoder_tables_made_on_the_device(ctx):
     assert t2["enc_trie"]["launches"] == 1
     if rc.available():
         assert b2[0].tobytes() == rc.tunstall_compress_block(big).tobytes() and b2[1].tobytes() == blocks[3].tobytes()
-
-
-def _model_bits(fields):
-    """MSB-first bit writer (src/bitstream.cpp:86-101): fields = iterable of (value, nbits) -> uint32 words"""
-    acc, nb, words = 0, 0, []
-    for v, n in fields:
-        acc = (acc << n) | (int(v) & ((1 << n) - 1)); nb += n
-        while nb >= 32:
-            words.append((acc >> (nb - 32)) & 0xFFFFFFFF); nb -= 32; acc &= (1 << nb) - 1
-    if nb:
-        words.append((acc << (32 - nb)) & 0xFFFFFFFF)
-    return np.array(words, dtype=np.uint32)
-
-
-def _model_array(a):
-    """OutStream::encodeArray<int> (include/corto/cstream.h:143-164): one width per element -> (words, [logs])"""
-    def needed(x):
-        x = int(x)
-        if x == 0: return 0
-        if x == -1: return 1
-        if x < 0: x = -x - 1
-        return 1 + x.bit_length()
-    logs = np.array([max(needed(x) for x in row) for row in a], dtype=np.uint8)
-    fields = [(int(x) + (1 << (int(d) - 1)), int(d)) for row, d in zip(a, logs) if d for x in row]
-    return _model_bits(fields), [logs]
-
-
-def _model_values(a):
-    """OutStream::encodeValues (include/corto/cstream.h:115-141): component-major, one width per value, sign folded"""
-    logs, fields = [], []
-    for c in range(a.shape[1]):
-        lg = np.zeros(len(a), dtype=np.uint8)
-        for i, x in enumerate(a[:, c]):
-            x = int(x)
-            if x == 0: continue
-            r = abs(x).bit_length()
-            lg[i] = r
-            fields.append((x if x > 0 else -x - (1 << (r - 1)), r))
-        logs.append(lg)
-    return _model_bits(fields), logs
 
 
 def test_encode_values_stage_against_the_cstream_model(ctx):
