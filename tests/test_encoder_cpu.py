@@ -88,6 +88,17 @@ def test_random_corpus_against_reference():
     assert ca.encode(m, **kw).tobytes() == rc.encode(m, **kw).tobytes()
 
 
+def test_value_range_corners_against_reference():
+    """the corners of tests/value_ranges.py - normal_bits 1 .. 16 on noisy normals, every color_bits tuple on random bytes, position_bits 22 .. 28
+    and 1 .. 3 - byte for byte against the reference encoder (the random corpus above stops at 14 normal bits and never varies color_bits)"""
+    from oracle import refcodec as rc
+    if not rc.available():
+        pytest.skip("oracle/_ref not built (needs /root/reference)")
+    import value_ranges as vr
+    for cid, m, kw in vr.encoder_corners():
+        assert ca.encode(m, **kw).tobytes() == np.asarray(rc.encode(m, **kw)).tobytes(), cid
+
+
 def test_non_manifold_input_pairs_like_the_reference():
     """Duplicated faces, reversed duplicates, fins on an edge and a 120-side fan around vertex 0: WHICH faces upstream's buildTopology
     pairs there depends on the order std::sort leaves equal keys in (src/encoder.cpp:450-504).  The repo's adjacency builder sorts

@@ -1827,7 +1827,8 @@ def test_delta_values_beyond_int16_are_redone_and_the_context_learns():
     refs = [oc.decode(b_, color_components=4) for b_ in blobs]
     b = run_batch(c, blobs, color_components=4)
     st = b.stats()
-    assert st.delta_wide == 0 and 2 <= st.delta_redone <= 3, (st.delta_wide, st.delta_redone)     # 17 and 20 bits for sure; 16 bits by its extent
+    # 17 and 20 bits, and the 16-bit disc: a result of its positions leaves int16 (tests/test_value_ranges_cpu.py works its side out by the host rule)
+    assert st.delta_wide == 0 and st.delta_redone == 3, (st.delta_wide, st.delta_redone)
     for i, r in enumerate(refs):
         assert_same(b.host_outputs(i), r, KEYS, "blob %d, %d bits, narrow plan" % (i, meshes[i][1]))
     b.decode(); b.sync()                                                     # the same batch again: planned wide now, nothing redone

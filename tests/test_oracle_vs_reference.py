@@ -54,6 +54,23 @@ def test_meshes_all_normal_modes(pred):
             assert same(r16, o16) == [], (name, bits, "i16")
 
 
+def test_value_range_corners():
+    """the corners of tests/value_ranges.py through the reference encoder and decoder: normal_bits 1 .. 16 with noisy normals under every prediction
+    (closed mesh, open mesh, cloud; the unfused sizes too), every color_bits tuple on random bytes with 3 and 4 stored components, position_bits
+    22 .. 28 under estimated normals and 1 .. 3 under DIFF - f32 and int16 normals, every normal finite"""
+    import value_ranges as vr
+    for cid, m, kw in vr.encoder_corners():
+        blob = rc.encode(m, **kw)
+        r = rc.decode(blob, color_components=4)
+        o = oc.decode(blob, color_components=4)
+        assert same(r, o) == [], cid
+        if "normal" in r:
+            assert np.isfinite(r["normal"]).all(), cid
+        r16 = rc.decode(blob, normal_format=rc.INT16, color_components=4, index16=True)
+        o16 = oc.decode(blob, normal_format=oc.FMT_INT16, color_components=4, index16=True)
+        assert same(r16, o16) == [], (cid, "i16")
+
+
 def test_point_clouds():
     for seed, (nu, nv) in enumerate([(3, 2), (17, 9), (64, 40), (200, 90)]):
         m = synth.point_cloud(nu, nv, seed)
