@@ -3,13 +3,17 @@
 // tile, crthip_encode_splice_model / crthip_splice_copy_model walk the same source on the host, lanes in a loop, tiles in a shuffled order;
 // tests/test_encode_device_out_cpu.py holds both against crthip_encode_attrs).
 //
-// The plan.  A container is its frame (the container without its streams) with the coded streams put in at their slots, by the rules
-// of splice_container (encoder_internal.h): a bit stream is its word count, zeros to a 4-byte position OF THE CONTAINER, its words; a
-// value stream's words come before its blocks; the slot of the CLERS split bits takes the split words.  The host knows every size
-// without a payload byte: it writes what it makes itself - frame bytes, word counts, the padding zeros, the split words, the block
-// headers (Tunstall: u8 nsym | nsym x (sym, prob) | i32 size | i32 csize; entropy NONE: i32 size), the zeros between a blob's end and
-// the next 16-byte multiple - into ONE literal buffer for the chunk, and names the payload (bit words, codewords, raw logs and symbols)
-// by its device address.  The result is a list of pieces {source, arena offset, bytes} in destination order that covers the arena once.
+// THE RULE.  A container is its frame (the container without its streams) with the coded streams (encoder_internal.h: Coded) put in at
+// the slots its body recorded (Deferred, BatchStream: `at` in the frame, `kind`), in order: a bit stream is its word count, zeros to a
+// 4-byte position OF THE CONTAINER, its words (OutStream::write(BitStream&), cstream.h:79-89); a value stream's words come before its
+// blocks; a block is its header, then its payload; the slot of the CLERS split bits (kind BATCH_BITS) takes the split words, which the
+// host has packed.  write_container below is the only place that knows this, for every encoder: it emits host-made bytes, zeros and
+// payload by address into an output - a SplicePlan, or a ByteOut where the payload is in host memory.
+//
+// The plan.  The host knows every size without a payload byte: what it makes itself - frame bytes, word counts, the padding zeros, the
+// split words, the block headers, the zeros between a blob's end and the next 16-byte multiple (the plan's own business, not the
+// writer's) - goes into ONE literal buffer for the chunk, and the payload (bit words, codewords, raw logs and symbols) is named by its
+// device address.  The result is a list of pieces {source, arena offset, bytes} in destination order that covers the arena once.
 // Neighbouring literal bytes are one piece.  The literal buffer is packed: it holds the host-made bytes and nothing else, so what goes up
 // is literal_bytes exactly, and a literal piece is moved from whatever alignment it has, like any other.
 //
@@ -23,8 +27,8 @@
 //
 // SOURCES.  The aligned reads of a body touch up to 3 bytes before a piece's first body byte and up to 3 behind its last.  Every source
 // is a library allocation whose base is 256-byte aligned and which is allocated with at least 16 bytes behind its last region: the value
-// coder's image and the Tunstall coder's (encode_gpu.cpp), the chunk image and host mode's CLERS block (encode_batch.cpp), the literal
-// buffer (below: 16 bytes of slack).  No piece ever sources from a caller's array.  Keep this true when a region moves.
+// coder's image and the Tunstall coder's (encode_gpu.cpp) and host mode's CLERS block (encode_batch.cpp), all three owned by the Coded
+// object, the chunk image (encode_batch.cpp), the literal buffer (splice_to_device: 16 bytes of slack).  No piece ever sources from a caller's array.  Keep this true when a region moves.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -35,6 +39,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_plan.h"
+#include "encoder_internal.h"
 
 #define ESP_HD __host__ __device__ inline
 
@@ -121,19 +126,37 @@ ESP_HD void esp_copy_lane(const SpliceJob &J, uint32_t t, uint32_t lane) {
 	}
 }
 
+// ---- the container writer (host) ----
+
+// One container into `o`: o.lit(p, n) takes host-made bytes (p == nullptr: zeros), o.payload(p, n) payload that lies at p.  Returns how
+// many of `streams` it used: one per slot but the split bits.
+template <class Out, class SlotT>
+size_t write_container(Out &o, const std::vector<uint8_t> &frame, const std::vector<SlotT> &slots, const CodedStream *streams,
+                       const std::vector<uint32_t> &split_words) {
+	uint64_t n = 0;                                       // bytes of this container so far
+	auto lit = [&](const void *p, uint64_t b) { o.lit(p, b); n += b; };
+	auto count = [&](uint32_t nwords) { lit(&nwords, 4); lit(nullptr, (4u - (n & 3u)) & 3u); };
+	size_t prev = 0, r = 0;
+	for(const SlotT &s : slots) {
+		lit(frame.data() + prev, s.at - prev); prev = s.at;
+		if(s.kind == BATCH_BITS) { count((uint32_t)split_words.size()); lit(split_words.data(), split_words.size()*4); continue; }
+		const CodedStream &x = streams[r++];
+		if(s.kind != CRTHIP_ENC_SYMBOLS) { count(x.nwords); o.payload(x.words, (uint64_t)x.nwords*4); n += (uint64_t)x.nwords*4; }
+		for(const CodedBlock &b : x.blocks) { lit(b.head.data(), b.head.size()); o.payload(b.payload, b.bytes); n += b.bytes; }
+	}
+	lit(frame.data() + prev, frame.size() - prev);
+	return r;
+}
+
+// the output over host memory: every payload pointer is a host pointer (Coded::on_device == false)
+struct ByteOut {
+	std::vector<uint8_t> &b;
+	void lit(const void *p, uint64_t n) { if(p) b.insert(b.end(), (const uint8_t *)p, (const uint8_t *)p + n); else b.insert(b.end(), (size_t)n, (uint8_t)0); }
+	void payload(const uint8_t *p, uint64_t n) { if(n) b.insert(b.end(), p, p + n); }
+};
+
 // ---- the plan (host) ----
 
-struct SplicePart {                                       // host bytes, or a device address with a length
-	const uint8_t *host = nullptr, *dev = nullptr;
-	uint64_t bytes = 0;
-};
-struct SpliceStream {                                     // one coded stream: its bit words (a value stream), then its blocks' parts in order
-	bool bits = false;
-	uint32_t nwords = 0;
-	const uint8_t *words = nullptr;                       // device: nwords*4 bytes
-	std::vector<SplicePart> parts;                        // per block: its header (host), its payload (device)
-};
-struct SpliceSlot { uint64_t at; bool split; };          // where a stream belongs in the frame; split: the CLERS split bits (host words)
 struct SplicePiece { uint64_t src, dst, bytes; uint32_t literal, pad; };   // src: an offset in the literal buffer, or a device address
 
 struct SplicePlan {
@@ -149,30 +172,17 @@ struct SplicePlan {
 		if(p) literal.insert(literal.end(), (const uint8_t *)p, (const uint8_t *)p + n); else literal.insert(literal.end(), (size_t)n, (uint8_t)0);
 		pieces.back().bytes += n; at += n; literal_bytes += n;
 	}
-	void dev(const uint8_t *p, uint64_t n) {
+	void payload(const uint8_t *p, uint64_t n) {          // p: a device address (Coded::on_device)
 		if(!n) return;
 		pieces.push_back(SplicePiece{(uint64_t)(uintptr_t)p, at, n, 0u, 0u});
 		at += n; device_bytes += n;
 	}
-	void u32(uint32_t v) { const uint8_t b[4] = {(uint8_t)v, (uint8_t)(v >> 8), (uint8_t)(v >> 16), (uint8_t)(v >> 24)}; lit(b, 4); }
-	// one container at the running offset (a multiple of 16), then the zeros to the next one; returns the blob's length
-	uint64_t item(const uint8_t *frame, size_t frame_bytes, const SpliceSlot *slots, size_t nslots, const SpliceStream *streams,
-	              const uint32_t *split_words, uint32_t nsplit) {
+	// one container at the running offset (a multiple of 16), then the zeros to the next one; returns the blob's length and adds the
+	// streams it used to `used`
+	template <class SlotT>
+	uint64_t item(const std::vector<uint8_t> &frame, const std::vector<SlotT> &slots, const CodedStream *streams, const std::vector<uint32_t> &split_words, size_t &used) {
 		const uint64_t begin = at;
-		size_t prev = 0, r = 0;
-		for(size_t k = 0; k < nslots; k++) {
-			lit(frame + prev, slots[k].at - prev); prev = (size_t)slots[k].at;
-			if(slots[k].split) {
-				u32(nsplit);
-				lit(nullptr, (4u - ((at - begin) & 3u)) & 3u);
-				for(uint32_t i = 0; i < nsplit; i++) u32(split_words[i]);
-				continue;
-			}
-			const SpliceStream &x = streams[r++];
-			if(x.bits) { u32(x.nwords); lit(nullptr, (4u - ((at - begin) & 3u)) & 3u); dev(x.words, (uint64_t)x.nwords*4); }
-			for(const SplicePart &p : x.parts) { if(p.dev) dev(p.dev, p.bytes); else lit(p.host, p.bytes); }
-		}
-		lit(frame + prev, frame_bytes - prev);
+		used += write_container(*this, frame, slots, streams, split_words);
 		const uint64_t len = at - begin;
 		lit(nullptr, (16u - (at & 15u)) & 15u);
 		return len;

@@ -48,22 +48,11 @@ struct Payload {
 	}
 };
 
-// one item's plan input from the host-coded streams; under TUNSTALL a block's header is 9 + 2*nsym bytes, under NONE 4
-void item_streams(const HostCodedItem &h, Payload &pay, std::vector<SpliceSlot> &slots, std::vector<SpliceStream> &streams) {
-	size_t r = 0;
-	for(const BatchStream &b : h.slots) {
-		slots.push_back(SpliceSlot{b.at, b.kind == BATCH_BITS});
-		if(b.kind == BATCH_BITS) continue;
-		const EncValueResult &x = h.res[r++];
-		SpliceStream y;
-		y.bits = b.kind != CRTHIP_ENC_SYMBOLS;
-		if(y.bits) { y.nwords = (uint32_t)x.words.size(); y.words = pay.put(x.words.data(), x.words.size()*4); }
-		for(const std::vector<uint8_t> &blk : x.blocks) {
-			const size_t head = h.entropy == CRTHIP_ENTROPY_NONE ? 4 : 9 + 2*(size_t)blk[0];
-			SplicePart hp; hp.host = blk.data(); hp.bytes = head; y.parts.push_back(hp);
-			if(blk.size() > head) { SplicePart p; p.dev = pay.put(blk.data() + head, blk.size() - head); p.bytes = blk.size() - head; y.parts.push_back(p); }
-		}
-		streams.push_back(std::move(y));
+// one item's payload out of the host encoder's buffers into the place of device memory
+void rehome(HostCodedItem &h, Payload &pay) {
+	for(CodedStream &x : h.coded.streams) {
+		if(x.words) x.words = pay.put(x.words, (size_t)x.nwords*4);
+		for(CodedBlock &b : x.blocks) if(b.bytes) b.payload = pay.put(b.payload, b.bytes);
 	}
 }
 
@@ -71,11 +60,10 @@ int64_t splice_model(const crthip_mesh *m, const crthip_attr_list *extra, uint32
 	HostCodedItem h;
 	{ const int e = encode_host_coded(m, extra, h); if(e) return e; }
 	Payload pay;
-	std::vector<SpliceSlot> slots;
-	std::vector<SpliceStream> streams;
-	item_streams(h, pay, slots, streams);
+	rehome(h, pay);
 	SplicePlan P;
-	const uint64_t len = P.item(h.frame.data(), h.frame.size(), slots.data(), slots.size(), streams.data(), h.split_words.data(), (uint32_t)h.split_words.size());
+	size_t used = 0;
+	const uint64_t len = P.item(h.frame, h.slots, h.coded.streams.data(), h.split_words, used);
 	const uint64_t total = P.at;
 	if(!out || cap < total) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_splice_model: output buffer too small");
 	// the literal buffer on a 4-byte boundary (all the device promises it: it follows the job table) with slack; the arena `misalign`
@@ -108,10 +96,9 @@ int64_t plan_model(uint32_t n, const crthip_mesh *meshes, const crthip_attr_list
 			blob_len[i] = 0;
 			HostCodedItem &h = items[i - first];
 			if(encode_host_coded(&meshes[i], extra ? &extra[i] : nullptr, h)) continue;
-			std::vector<SpliceSlot> slots;
-			std::vector<SpliceStream> streams;
-			item_streams(h, pay, slots, streams);
-			blob_len[i] = (uint32_t)P.item(h.frame.data(), h.frame.size(), slots.data(), slots.size(), streams.data(), h.split_words.data(), (uint32_t)h.split_words.size());
+			rehome(h, pay);
+			size_t used = 0;
+			blob_len[i] = (uint32_t)P.item(h.frame, h.slots, h.coded.streams.data(), h.split_words, used);
 		}
 		std::vector<SpliceJob> jobs;
 		std::vector<uint32_t> tile_start;

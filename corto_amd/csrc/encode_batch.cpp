@@ -7,12 +7,13 @@
 // kernels read them, and one record per mesh comes back for its frame (encoder.cpp: batch_frame).  Everything per vertex runs on the
 // device and stays resident until the coded streams come back (k_encode_batch.hip): quantisation, estimated normals, residuals, the
 // point clouds' Morton sort (one cloud after another: each has its own launches), then the value and Tunstall coders (encode_gpu.cpp:
-// encode_value_streams_device).  The host splices every container from its frame and the coded streams (encoder_internal.h:
-// splice_container).  One device image per chunk of the batch; no allocation per mesh or per stream.
+// encode_value_streams_device), which bring their payload back.  The host writes every container from its frame and the coded streams
+// (enc_splice.h: write_container, into a ByteOut).  One device image per chunk of the batch; no allocation per mesh or per stream.
 //
-// crthip_encode_batch_to_device shares every stage up to code_values and differs in the tail: the coders leave their payload on the device
-// (encode_value_streams_resident), the host plans where every byte of every container goes in the caller's device arena (enc_splice.h),
-// uploads what it made itself as one literal buffer beside the job table, and k_enc_splice moves the pieces (splice_to_device).
+// crthip_encode_batch_to_device shares every stage and differs in one argument of code_values and in the tail: the coders leave their
+// payload on the device, the same writer runs into a SplicePlan - where every byte of every container goes in the caller's device arena
+// (enc_splice.h) - the host uploads what it made itself as one literal buffer beside the job table, and k_enc_splice moves the pieces
+// (splice_to_device).
 //
 // crthip_encode_batch_resident is the same path for data arrays that live in device memory: the pointers are vouched for by the runtime
 // (resident_check), what the host would have read through them comes from K-ENC-CHECK (input_pass: k_encode_check.hip), the quantiser
@@ -647,9 +648,9 @@ int stage_delta(Chunk &C) {
 // BORDER counts back, then value + entropy coding: every stream of every item in one call (encode_gpu.cpp).  With the counts the stream
 // is waited for, and the stages' times are read.  The host-made CLERS symbols then go up: into the image beside the device pass's (every
 // mode but HOST), else into an allocation of their own, in one copy.  R: slot.count, slot.d, slot.clers.  W: slot.clers of the host-made
-// meshes.  Synchronised (the value coder ends so).
-// keep != null (crthip_encode_batch_to_device): the coded payload stays on the device, keep says where (res stays empty).
-int code_values(Chunk &C, int mode, std::vector<EncValueResult> &res, DevCoded *keep = nullptr) {
+// meshes, coded.clers.  Synchronised (the value coder ends so).
+// fetch == false (crthip_encode_batch_to_device): the coded payload stays on the device.
+int code_values(Chunk &C, int mode, bool fetch, Coded &coded) {
 	const uint32_t n = C.n();
 	std::vector<size_t> count_at(n + 1, 0);                  // mesh k's attributes from count_at[k] on
 	for(uint32_t k = 0; k < n; k++) count_at[k + 1] = count_at[k] + C.item(k).attrs.size();
@@ -682,8 +683,7 @@ int code_values(Chunk &C, int mode, std::vector<EncValueResult> &res, DevCoded *
 		C.S.upload_ms += ms_since(t0);
 		if(any) ENC_TRY(C.sync());
 	} else cl = clers_layout(C.items, C.img, clers_at);
-	DevMem dclers_local;
-	DevMem &dclers = keep ? keep->clers : dclers_local;           // under entropy NONE the symbols are a source of the device splice
+	DevMem &dclers = coded.clers;                                 // under entropy NONE the symbols are a source of the device splice
 	if(cl) {
 		const auto t0 = Clock::now();
 		std::vector<uint8_t> h(cl);
@@ -712,7 +712,7 @@ int code_values(Chunk &C, int mode, std::vector<EncValueResult> &res, DevCoded *
 		}
 	}
 	const auto t0 = Clock::now();
-	const int e = keep ? encode_value_streams_resident(C.ctx, vs, *keep, C.tm) : encode_value_streams_device(C.ctx, vs, res, C.tm);
+	const int e = encode_value_streams_device(C.ctx, vs, fetch, coded, C.tm);
 	C.S.value_coder_ms += ms_since(t0);
 	if(e) return e;
 	C.S.value_streams += (uint32_t)vs.size();
@@ -732,29 +732,14 @@ struct DeviceOut {
 // The tail of a device-output chunk: the plan of every container (enc_splice.h) from the frames and from where `coded` says the payload
 // lies, one upload of job table + literal buffer, one launch of k_enc_splice.  Nothing is launched when the call only sizes or the arena
 // would not hold the chunk.  R: the value coder's images, slot.clers (entropy NONE).  W: the caller's arena.  Synchronised.
-int splice_to_device(Chunk &C, const DevCoded &coded, DeviceOut &D) {
+int splice_to_device(Chunk &C, const Coded &coded, DeviceOut &D) {
 	const auto t_plan = Clock::now();
 	SplicePlan P(D.at);
 	size_t r = 0;
-	std::vector<SpliceSlot> slots;
-	std::vector<SpliceStream> streams;
 	for(uint32_t k = 0; k < C.n(); k++) {
 		const BatchItem &it = C.item(k);
 		if(it.status) continue;
-		slots.clear(); streams.clear();
-		for(const BatchStream &b : it.streams) {
-			slots.push_back(SpliceSlot{b.at, b.kind == BATCH_BITS});
-			if(b.kind == BATCH_BITS) continue;
-			const DevCodedStream &x = coded.streams[r++];
-			SpliceStream y;
-			y.bits = b.kind != CRTHIP_ENC_SYMBOLS; y.nwords = x.nwords; y.words = x.words;
-			for(const DevCodedBlock &blk : x.blocks) {
-				SplicePart h; h.host = blk.head.data(); h.bytes = blk.head.size(); y.parts.push_back(h);
-				if(blk.bytes) { SplicePart p; p.dev = blk.payload; p.bytes = blk.bytes; y.parts.push_back(p); }
-			}
-			streams.push_back(std::move(y));
-		}
-		const uint64_t len = P.item(it.frame.data(), it.frame.size(), slots.data(), slots.size(), streams.data(), it.split_words.data(), (uint32_t)it.split_words.size());
+		const uint64_t len = P.item(it.frame, it.streams, coded.streams.data() + r, it.split_words, r);
 		if(len > 0xFFFFFFFFull) return ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch_to_device: a blob of 4 GiB or more");
 		D.len[C.img.ids[k]] = (uint32_t)len;
 	}
@@ -809,7 +794,9 @@ int encode_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_l
 	// Lifetimes, by declaration order (destruction runs upwards).  The pool thread's lambdas hold references to C (ready / mu / cv /
 	// topo_ms are its members) and through it to items and img: all declared before the thread, whose Joiner joins it on every way out.
 	// The image's memory is freed by DevMem only after Drain has waited for the work queued on it, and C's host buffers go after that.
-	DevCoded coded;                                                     // (device output) the coders' images: freed after the Drain
+	// `coded` comes first: its device images are read by the splice's launch and its host buffers written by the value coder's queued
+	// copies, so it goes last, after the Drain.
+	Coded coded;
 	Chunk C{ctx, ctx_stream(ctx), meshes, extra, items, img, S, bt, tm};
 	for(uint32_t k : img.devk) C.ready[k] = 1;
 	if(img.resident) { const int e = fetch_indices(C); if(e) return e; }
@@ -840,15 +827,19 @@ int encode_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_l
 	e = stage_estimate(C);
 	if(!e) e = resort_tied_clouds(C);
 	if(!e) e = stage_delta(C);
-	std::vector<EncValueResult> res;
-	if(!e) e = code_values(C, mode, res, dout ? &coded : nullptr);
+	if(!e) e = code_values(C, mode, !dout, coded);
 	if(e) return e;
-	if(dout) return splice_to_device(C, coded, *dout);
+	if(coded.on_device) return splice_to_device(C, coded, *dout);
 
-	// splice: every container from its frame and its streams' results, in item order
+	// every container from its frame and its coded streams, in item order
 	const auto t_frame = Clock::now();
 	size_t r = 0;
-	for(uint32_t id : img.ids) if(!items[id].status) r += splice_container(items[id].frame, items[id].streams, res.data() + r, items[id].split_words, blobs[id]);
+	for(uint32_t id : img.ids) {
+		if(items[id].status) continue;
+		blobs[id].clear();
+		ByteOut o{blobs[id]};
+		r += write_container(o, items[id].frame, items[id].streams, coded.streams.data() + r, items[id].split_words);
+	}
 	S.host_frame_ms += (float)ms_since(t_frame);
 	return CRTHIP_OK;
 }
@@ -963,10 +954,11 @@ int input_pass(crthip_ctx *ctx, const crthip_mesh *meshes, const std::vector<uin
 
 } // namespace
 
-// what encode_batch_impl refuses a mesh for before any device work, but for the resident pointers
-static int batch_item_check(const crthip_mesh *m, const crthip_attr_list *extra, bool index_on_host) {
+// what encode_batch_impl refuses a mesh for before any device work; resident_device >= 0: its data arrays are that device's memory
+static int batch_item_check(const crthip_mesh *m, const crthip_attr_list *extra, bool index_on_host, int resident_device = -1) {
 	int e = encode_check(m, index_on_host);
 	if(!e) e = encode_check_attrs(m, extra, true);
+	if(!e && resident_device >= 0) e = resident_check(m, extra, resident_device);
 	if(!e && (uint64_t)m->nvert*3 > (1u << 26)) e = ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: too many vertices for the value coder");
 	if(!e && m->entropy == CRTHIP_ENTROPY_TUNSTALL && m->nvert > (1u << 23))
 		e = ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: a Tunstall stream longer than 2^23 symbols");
@@ -994,15 +986,8 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 	std::vector<BatchItem> items(n);
 	std::vector<uint32_t> ok;
 	for(uint32_t i = 0; i < n; i++) {
-		const crthip_mesh *m = &meshes[i];
-		int e = encode_check(m, !resident);
-		if(!e) e = encode_check_attrs(m, extra ? &extra[i] : nullptr, true);
-		if(!e && resident) e = resident_check(m, extra ? &extra[i] : nullptr, ctx_device(ctx));
-		if(!e && (uint64_t)m->nvert*3 > (1u << 26)) e = ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: too many vertices for the value coder");
-		if(!e && m->entropy == CRTHIP_ENTROPY_TUNSTALL && m->nvert > (1u << 23))
-			e = ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: a Tunstall stream longer than 2^23 symbols");
-		items[i].status = e;
-		if(!e) ok.push_back(i);
+		items[i].status = batch_item_check(&meshes[i], extra ? &extra[i] : nullptr, !resident, resident ? ctx_device(ctx) : -1);
+		if(!items[i].status) ok.push_back(i);
 	}
 	// position steps and attribute tables (the steps' sums are the host's, in its order: a resident call gets them, and the index check
 	// encode_check left out, from the device's records)

@@ -12,6 +12,10 @@
 // src/tunstall.cpp:384-428)  ->  block framing on the host.  Everything is byte-identical to the reference's output
 // (tests/test_gpu_parity.py::test_tunstall_encode_*, test_encode_values_*, test_gpu_encoder_*).  No CPU fallback.
 // The try macro, DevMem, the stage timer (EventTimer) and quant_job are encoder_internal.h's, shared with encode_batch.cpp.
+//
+// Both coders give their result in one form (encoder_internal.h: Coded): host-made block headers, and the payload - bit words, codewords,
+// raw logs and symbols - by address.  Whether the payload is brought back to the host is one argument of each; the device work up to
+// that point is the same, and the addresses are rebased to the host buffers behind the copies.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +24,7 @@
 
 #include "../../include/corto_hip.h"
 #include "device_plan.h"
+#include "enc_splice.h"
 #include "encoder_internal.h"
 #include "kernels.h"
 
@@ -28,12 +33,12 @@ using namespace corto_hip;
 namespace {
 
 
-// Tunstall blocks of n DEVICE-resident byte streams.  blocks[i] = "u8 nsym | nsym x (symbol, probability) | i32 size | i32 csize | codewords"
-// keep != null (crthip_encode_batch_to_device): the codewords stay on the device, in an image that `keep` then owns - blocks[i] is the
-// header alone, payload[i] the codewords' device address, and their count is the header's csize field
-int tun_encode_device(hipStream_t st, uint32_t n, const uint8_t *const *d_src, const uint32_t *sizes,
-                      std::vector<std::vector<uint8_t>> &blocks, EncStageTimes &tm, DevMem *keep = nullptr, std::vector<const uint8_t *> *payload = nullptr) {
-	blocks.assign(n, std::vector<uint8_t>());
+// Tunstall blocks of n DEVICE-resident byte streams: blocks[i].head = "u8 nsym | nsym x (symbol, probability) | i32 size | i32 csize", its
+// payload the csize codewords, which lie in `work`.  fetch != null: the codeword region comes back into *fetch and the payload pointers
+// point there; else they are device addresses.
+int tun_encode_device(hipStream_t st, uint32_t n, const uint8_t *const *d_src, const uint32_t *sizes, std::vector<CodedBlock> &blocks,
+                      EncStageTimes &tm, DevMem &work, std::vector<uint8_t> *fetch) {
+	blocks.assign(n, CodedBlock());
 	for(uint32_t i = 0; i < n; i++)
 		if(sizes[i] > (1u << 23)) return ctx_fail(CRTHIP_E_LIMIT, "Tunstall encoder: stream longer than 2^23 symbols (the reference's count*255 overflows int)");
 	// device image: counts | codewords | csize | histogram chunks
@@ -46,8 +51,6 @@ int tun_encode_device(hipStream_t st, uint32_t n, const uint8_t *const *d_src, c
 	for(uint32_t i = 0; i < n; i++)
 		for(uint32_t b = 0; b < sizes[i]; b += ENC_HIST_CHUNK) chunks.push_back(EncChunk{d_src[i] + b, std::min(ENC_HIST_CHUNK, sizes[i] - b), i});
 	o += (chunks.size()*sizeof(EncChunk) + 15) & ~15ull;
-	DevMem work_local;
-	DevMem &work = keep ? *keep : work_local;
 	EventTimer t_hist, t_tables, t_trie, t_parse;
 	ENC_TRY(hipMalloc(&work.p, o + 16));
 	uint8_t *base = work.u8();
@@ -66,7 +69,6 @@ int tun_encode_device(hipStream_t st, uint32_t n, const uint8_t *const *d_src, c
 	// whose trie could outgrow ENC_TRIE_LDS_MAX entries (large alphabets) gets its tables from the host routine instead.
 	std::vector<TunEncoderTables> tabs(n);
 	std::vector<uint32_t> csize(n, 0);
-	std::vector<uint8_t> h_codes;
 	DevMem dtabs, dtrie, dstreams;
 	constexpr size_t HEAD = 16 + 512;                                     // EncTab: four words + the probabilities
 	std::vector<uint8_t> heads((size_t)n*HEAD);
@@ -166,9 +168,9 @@ int tun_encode_device(hipStream_t st, uint32_t n, const uint8_t *const *d_src, c
 		hipLaunchKernelGGL(k_enc_tun_parse, dim3(ngpu), dim3(64), lds, st, (const EncStream *)(tb + o_streams), ngpu, trie_lds);
 		if(t_parse.end(st)) return CRTHIP_E_DEVICE;
 		ENC_TRY(hipMemcpyAsync(csize.data(), base + o_csize, (size_t)n*4, hipMemcpyDeviceToHost, st));
-		if(!keep) {
-			h_codes.resize(o_csize - dst_off[0]);
-			ENC_TRY(hipMemcpyAsync(h_codes.data(), base + dst_off[0], h_codes.size(), hipMemcpyDeviceToHost, st));
+		if(fetch) {
+			fetch->resize(o_csize - dst_off[0]);
+			ENC_TRY(hipMemcpyAsync(fetch->data(), base + dst_off[0], fetch->size(), hipMemcpyDeviceToHost, st));
 		}
 		ENC_TRY(hipStreamSynchronize(st));
 		ENC_TRY(hipGetLastError());
@@ -178,19 +180,18 @@ int tun_encode_device(hipStream_t st, uint32_t n, const uint8_t *const *d_src, c
 	if(t_hist.add_to(tm.hist)) tm.any_hist = true;
 
 	// block framing (src/cstream.cpp:96-107)
-	if(payload) payload->assign(n, nullptr);
 	for(uint32_t i = 0; i < n; i++) {
 		const TunEncoderTables &T = tabs[i];
 		const uint32_t cs = T.nsym >= 2 ? csize[i] : 0u;
 		if(cs > sizes[i] + 1) return ctx_fail(CRTHIP_E_DEVICE, "k_enc_tun_parse produced an impossible codeword count");
-		std::vector<uint8_t> &b = blocks[i];
-		b.resize(9 + (size_t)T.nsym*2 + (keep ? 0u : cs));
+		std::vector<uint8_t> &b = blocks[i].head;
+		b.resize(9 + (size_t)T.nsym*2);
 		b[0] = (uint8_t)T.nsym;
 		memcpy(&b[1], T.probs, (size_t)T.nsym*2);
 		memcpy(&b[1 + T.nsym*2], &sizes[i], 4);
 		memcpy(&b[5 + T.nsym*2], &cs, 4);
-		if(cs && !keep) memcpy(&b[9 + T.nsym*2], h_codes.data() + (dst_off[i] - dst_off[0]), cs);
-		if(cs && payload) (*payload)[i] = base + dst_off[i];
+		blocks[i].bytes = cs;
+		if(cs) blocks[i].payload = fetch ? fetch->data() + (dst_off[i] - dst_off[0]) : base + dst_off[i];
 	}
 	return CRTHIP_OK;
 }
@@ -227,15 +228,21 @@ extern "C" int64_t crthip_tunstall_encode_blocks(crthip_ctx *ctx, uint32_t n, co
 	if(o) ENC_TRY(hipMemcpy(dsrc.p, h_src.data(), o, hipMemcpyHostToDevice));
 	std::vector<const uint8_t *> d_src(n);
 	for(uint32_t i = 0; i < n; i++) d_src[i] = dsrc.u8() + src_off[i];
-	std::vector<std::vector<uint8_t>> blocks;
+	std::vector<CodedBlock> blocks;
+	std::vector<uint8_t> codes;
+	DevMem image;
 	EncStageTimes tm;
-	{ const int e = tun_encode_device(st, n, d_src.data(), sizes, blocks, tm); if(e) return e; }
+	{ const int e = tun_encode_device(st, n, d_src.data(), sizes, blocks, tm, image, &codes); if(e) return e; }
 	enc_report_times(times, tm);
 	uint64_t w = 0;
 	for(uint32_t i = 0; i < n; i++) {
+		const CodedBlock &b = blocks[i];
 		block_offset[i] = w;
-		if(out && w + blocks[i].size() <= cap) memcpy(out + w, blocks[i].data(), blocks[i].size());
-		w += blocks[i].size();
+		if(out && w + b.head.size() + b.bytes <= cap) {
+			memcpy(out + w, b.head.data(), b.head.size());
+			if(b.bytes) memcpy(out + w + b.head.size(), b.payload, b.bytes);
+		}
+		w += b.head.size() + b.bytes;
 	}
 	block_offset[n] = w;
 	if(out && w > cap) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_tunstall_encode_blocks: output buffer too small");
@@ -273,12 +280,13 @@ int corto_hip::quantize_device(crthip_ctx *ctx, const std::vector<QuantRequest> 
 }
 
 // bit-width logs + bit packing of n DEVICE-resident value arrays, then the Tunstall coder over the logs (or raw logs for entropy NONE).
-// The caller has set the device and quiesced the context.  Words and raw logs come back compacted, in one copy each - or, with keep
-// (encode_value_streams_resident), nothing of them comes back: keep gets their device addresses and owns the images.
-static int value_streams_impl(crthip_ctx *ctx, const std::vector<DevValueStream> &in, std::vector<EncValueResult> &res, EncStageTimes &tm, DevCoded *keep) {
+// The caller has set the device and quiesced the context.  The payload stays where the coders made it, in images `out` owns; with
+// fetch, words and raw logs are compacted on the device and come back in one copy, the codewords in another, and the pointers are
+// rebased to those host buffers.
+int corto_hip::encode_value_streams_device(crthip_ctx *ctx, const std::vector<DevValueStream> &in, bool fetch, Coded &out, EncStageTimes &tm) {
 	const uint32_t n = (uint32_t)in.size();
-	res.assign(n, EncValueResult());
-	if(keep) keep->streams.assign(n, DevCodedStream());
+	out.streams.assign(n, CodedStream());
+	out.on_device = !fetch;
 	hipStream_t st = ctx_stream(ctx);
 	// device image: logs | words | word counts | jobs
 	std::vector<uint64_t> l_off(n), w_off(n);
@@ -291,8 +299,7 @@ static int value_streams_impl(crthip_ctx *ctx, const std::vector<DevValueStream>
 	const uint64_t o_jobs = o;
 	std::vector<PackJob> jobs;
 	std::vector<uint32_t> job_stream;
-	DevMem dev_local;
-	DevMem &dev = keep ? keep->image : dev_local;
+	DevMem &dev = out.image;
 	EventTimer t_pack;
 	for(uint32_t i = 0; i < n; i++) if(nlogs[i] && in[i].count) { jobs.push_back(PackJob{}); job_stream.push_back(i); }
 	o += (jobs.size()*sizeof(PackJob) + 15) & ~15ull;
@@ -322,43 +329,34 @@ static int value_streams_impl(crthip_ctx *ctx, const std::vector<DevValueStream>
 		tm.bytes_from_device += (uint64_t)n*4;
 		if(t_pack.add_to(tm.pack)) tm.any_pack = true;
 	}
-	// what comes back without the entropy coder - the bit words of every stream, the raw logs / symbols of entropy NONE - is
-	// compacted on the device behind the pack and copied back at once
+	// what has its payload without the entropy coder - the bit words of every stream, the raw logs / symbols of entropy NONE.  fetch: each
+	// is a job of the compaction, and `moved` says which pointer it is and where in the buffer that comes back it will lie
 	std::vector<CopyJob> gather;
-	std::vector<uint64_t> at_words(n, 0);
+	std::vector<std::pair<const uint8_t **, uint64_t>> moved;
 	uint64_t back = 0;
+	auto payload = [&](const uint8_t *&p, const uint8_t *src, uint64_t bytes, uint64_t step) {
+		if(!bytes) return;
+		p = src;
+		if(fetch) { gather.push_back(CopyJob{src, nullptr, bytes, back}); moved.push_back({&p, back}); back += step; }
+	};
 	for(uint32_t i = 0; i < n; i++) {
 		if(!nlogs[i]) continue;
 		if((uint64_t)nwords[i] > (uint64_t)in[i].count*in[i].components + 1) return ctx_fail(CRTHIP_E_DEVICE, "k_enc_pack produced an impossible word count");
-		if(keep) { keep->streams[i].nwords = nwords[i]; keep->streams[i].words = base + w_off[i]; continue; }
-		res[i].words.resize(nwords[i]);
-		at_words[i] = back;
-		if(nwords[i]) { gather.push_back(CopyJob{base + w_off[i], nullptr, (uint64_t)nwords[i]*4, back}); back += (uint64_t)nwords[i]*4; }
+		out.streams[i].nwords = nwords[i];
+		payload(out.streams[i].words, base + w_off[i], (uint64_t)nwords[i]*4, (uint64_t)nwords[i]*4);
 	}
 	// entropy coder over the log arrays (device resident) and the symbol streams
-	std::vector<const uint8_t *> d_src; std::vector<uint32_t> sizes; std::vector<std::pair<uint32_t, uint32_t>> owner;
-	std::vector<uint64_t> at_raw;
+	std::vector<const uint8_t *> d_src; std::vector<uint32_t> sizes; std::vector<CodedBlock *> owner;
 	for(uint32_t i = 0; i < n; i++) {
-		const uint32_t nb = nlogs[i] ? nlogs[i] : 1u;
-		res[i].blocks.resize(nb);
-		if(keep) keep->streams[i].blocks.resize(nb);
-		for(uint32_t c = 0; c < nb; c++) {
-			const uint8_t *src = nlogs[i] ? base + l_off[i] + (uint64_t)c*in[i].count : (const uint8_t *)in[i].values;
+		out.streams[i].blocks.resize(nlogs[i] ? nlogs[i] : 1u);
+		uint32_t c = 0;
+		for(CodedBlock &b : out.streams[i].blocks) {
+			const uint8_t *src = nlogs[i] ? base + l_off[i] + (uint64_t)(c++)*in[i].count : (const uint8_t *)in[i].values;
 			const uint32_t size = in[i].count;
-			if(in[i].entropy == CRTHIP_ENTROPY_TUNSTALL) { d_src.push_back(src); sizes.push_back(size); owner.push_back({i, c}); }
-			else {                                                     // OutStream::compress with entropy NONE: i32 size | bytes (cstream.cpp:43-64)
-				if(keep) {
-					DevCodedBlock &k = keep->streams[i].blocks[c];
-					k.head.resize(4); memcpy(k.head.data(), &size, 4);
-					k.payload = src; k.bytes = size;
-					continue;
-				}
-				std::vector<uint8_t> &b = res[i].blocks[c];
-				b.resize(4 + (size_t)size);
-				memcpy(b.data(), &size, 4);
-				if(size) { gather.push_back(CopyJob{src, nullptr, size, back}); at_raw.push_back(back); back += (size + 15) & ~15ull; }
-				else at_raw.push_back(back);
-			}
+			if(in[i].entropy == CRTHIP_ENTROPY_TUNSTALL) { d_src.push_back(src); sizes.push_back(size); owner.push_back(&b); continue; }
+			b.head.resize(4); memcpy(b.head.data(), &size, 4);           // OutStream::compress with entropy NONE: i32 size | bytes (cstream.cpp:43-64)
+			b.bytes = size;
+			payload(b.payload, src, size, ((uint64_t)size + 15) & ~15ull);
 		}
 	}
 	if(!gather.empty()) {
@@ -367,49 +365,28 @@ static int value_streams_impl(crthip_ctx *ctx, const std::vector<DevValueStream>
 		for(CopyJob &g : gather) g.dst = dback.u8() + g.dst_off;
 		ENC_TRY(hipMemcpyAsync(base + o_gather, gather.data(), gather.size()*sizeof(CopyJob), hipMemcpyHostToDevice, st));
 		hipLaunchKernelGGL(k_enc_gather, dim3((uint32_t)gather.size()), dim3(256), 0, st, (const CopyJob *)(base + o_gather), (uint32_t)gather.size());
-		std::vector<uint8_t> h(back + 16);
-		ENC_TRY(hipMemcpyAsync(h.data(), dback.p, back, hipMemcpyDeviceToHost, st));
+		out.h_back.resize(back + 16);
+		ENC_TRY(hipMemcpyAsync(out.h_back.data(), dback.p, back, hipMemcpyDeviceToHost, st));
 		ENC_TRY(hipStreamSynchronize(st));
 		ENC_TRY(hipGetLastError());
 		tm.bytes_to_device += gather.size()*sizeof(CopyJob); tm.bytes_from_device += back;
-		size_t r = 0;
-		for(uint32_t i = 0; i < n; i++) {
-			if(nlogs[i] && nwords[i]) memcpy(res[i].words.data(), h.data() + at_words[i], (size_t)nwords[i]*4);
-			if(in[i].entropy == CRTHIP_ENTROPY_TUNSTALL) continue;
-			for(std::vector<uint8_t> &b : res[i].blocks) { if(b.size() > 4) memcpy(b.data() + 4, h.data() + at_raw[r], b.size() - 4); r++; }
-		}
+		for(const auto &m : moved) *m.first = out.h_back.data() + m.second;
 	}
 	if(!d_src.empty()) {
-		std::vector<std::vector<uint8_t>> blocks;
-		std::vector<const uint8_t *> payload;
-		{ const int e = tun_encode_device(st, (uint32_t)d_src.size(), d_src.data(), sizes.data(), blocks, tm, keep ? &keep->tun_image : nullptr, keep ? &payload : nullptr); if(e) return e; }
+		std::vector<CodedBlock> blocks;
+		{ const int e = tun_encode_device(st, (uint32_t)d_src.size(), d_src.data(), sizes.data(), blocks, tm, out.tun_image, fetch ? &out.h_codes : nullptr); if(e) return e; }
 		for(size_t k = 0; k < blocks.size(); k++) {
-			tm.bytes_from_device += blocks[k].size();                 // (keep: the header alone - its table and its two counts)
-			if(keep) {
-				DevCodedBlock &b = keep->streams[owner[k].first].blocks[owner[k].second];
-				memcpy(&b.bytes, blocks[k].data() + blocks[k].size() - 4, 4);   // csize
-				b.payload = payload[k]; b.head = std::move(blocks[k]);
-			} else res[owner[k].first].blocks[owner[k].second] = std::move(blocks[k]);
+			tm.bytes_from_device += blocks[k].head.size() + (fetch ? blocks[k].bytes : 0u);   // (on the device: the header alone - its table and its two counts)
+			*owner[k] = std::move(blocks[k]);
 		}
 	}
 	ENC_TRY(hipStreamSynchronize(st));
 	return CRTHIP_OK;
 }
 
-int corto_hip::encode_value_streams_device(crthip_ctx *ctx, const std::vector<DevValueStream> &in, std::vector<EncValueResult> &res, EncStageTimes &tm) {
-	return value_streams_impl(ctx, in, res, tm, nullptr);
-}
-
-int corto_hip::encode_value_streams_resident(crthip_ctx *ctx, const std::vector<DevValueStream> &in, DevCoded &out, EncStageTimes &tm) {
-	std::vector<EncValueResult> none;
-	return value_streams_impl(ctx, in, none, tm, &out);
-}
-
 // the same over HOST arrays, one entropy for all of them (crthip_encode_values, crthip_encode_gpu): the values go up in one copy
-int corto_hip::encode_value_streams(crthip_ctx *ctx, uint32_t entropy, const std::vector<EncValueStream> &in, std::vector<EncValueResult> &res,
-                                    crthip_kernel_times *times) {
+int corto_hip::encode_value_streams(crthip_ctx *ctx, uint32_t entropy, const std::vector<EncValueStream> &in, Coded &res, crthip_kernel_times *times) {
 	const uint32_t n = (uint32_t)in.size();
-	res.assign(n, EncValueResult());
 	if(!ctx) return ctx_fail(CRTHIP_E_ARGUMENT, "encode_value_streams: null context");
 	if(entropy != CRTHIP_ENTROPY_NONE && entropy != CRTHIP_ENTROPY_TUNSTALL) return ctx_fail(CRTHIP_E_ENTROPY, nullptr);
 	if(times) memset(times, 0, sizeof(*times));
@@ -438,7 +415,7 @@ int corto_hip::encode_value_streams(crthip_ctx *ctx, uint32_t entropy, const std
 	std::vector<DevValueStream> d(n);
 	for(uint32_t i = 0; i < n; i++) { d[i].kind = in[i].kind; d[i].count = in[i].count; d[i].components = in[i].components; d[i].entropy = entropy; d[i].values = dev.u8() + v_off[i]; }
 	EncStageTimes tm;
-	{ const int e = encode_value_streams_device(ctx, d, res, tm); if(e) return e; }
+	{ const int e = encode_value_streams_device(ctx, d, true, res, tm); if(e) return e; }
 	enc_report_times(times, tm);
 	return CRTHIP_OK;
 }
@@ -448,19 +425,19 @@ extern "C" int64_t crthip_encode_values(crthip_ctx *ctx, uint32_t entropy, uint3
 	if(!ctx || (n && !streams) || !stream_offset) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_values: null argument");
 	std::vector<EncValueStream> in(n);
 	for(uint32_t i = 0; i < n; i++) { in[i].kind = streams[i].kind; in[i].count = streams[i].count; in[i].components = streams[i].components; in[i].values = streams[i].values; }
-	std::vector<EncValueResult> res;
+	Coded res;
 	{ const int e = encode_value_streams(ctx, entropy, in, res, times); if(e) return e; }
-	uint64_t w = 0;
-	auto put = [&](const void *p, size_t len) { if(out && w + len <= cap) memcpy(out + w, p, len); w += len; };
+	// each stream is a container of its own - no frame, one slot: word count and words (at position 0 nothing pads), then the blocks
+	std::vector<uint8_t> all;
+	ByteOut o{all};
+	std::vector<BatchStream> slot(1);
 	for(uint32_t i = 0; i < n; i++) {
-		stream_offset[i] = w;
-		if(in[i].kind != CRTHIP_ENC_SYMBOLS) {
-			const uint32_t nw = (uint32_t)res[i].words.size();
-			put(&nw, 4);
-			put(res[i].words.data(), (size_t)nw*4);
-		}
-		for(auto &b : res[i].blocks) put(b.data(), b.size());
+		stream_offset[i] = all.size();
+		slot[0].kind = in[i].kind;
+		write_container(o, std::vector<uint8_t>(), slot, &res.streams[i], std::vector<uint32_t>());
 	}
+	const uint64_t w = all.size();
+	if(out && w <= cap && w) memcpy(out, all.data(), w);
 	stream_offset[n] = w;
 	if(out && w > cap) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_values: output buffer too small");
 	return (int64_t)w;

@@ -32,6 +32,7 @@
 #include "../../include/corto_hip.h"
 #include "encoder_internal.h"
 #include "device_plan.h"
+#include "enc_splice.h"
 #include "enc_topology.h"
 
 using corto_hip::QK_FLOAT;
@@ -67,6 +68,8 @@ struct Sink {
 	std::vector<uint8_t> b;
 	std::vector<Deferred> *defer = nullptr;   // non-null: value / symbol / bit streams are recorded, not written
 	bool shape_only = false;                  // (crthip_encode_batch) ... and only their kind and size: the values live on the device
+	struct Block { size_t at, head, payload; };
+	std::vector<Block> *blocks = nullptr;     // non-null: where every entropy-coded block lies in b, and where its header ends (encode_host_coded)
 	void u8(uint32_t v) { b.push_back((uint8_t)v); }
 	void u16(uint32_t v) { u8(v); u8(v >> 8); }
 	void u32(uint32_t v) { u8(v); u8(v >> 8); u8(v >> 16); u8(v >> 24); }
@@ -219,7 +222,8 @@ struct Tunstall {
 // entropy-coded byte array (OutStream::compress / tunstall_compress, cstream.cpp:43-64, 89-109)
 void put_symbols(Sink &s, uint32_t entropy, const uint8_t *data, uint32_t size) {
 	if(s.defer) { Deferred d; d.at = s.b.size(); d.kind = CRTHIP_ENC_SYMBOLS; d.count = size; if(!s.shape_only) d.bytes.assign(data, data + size); s.defer->push_back(std::move(d)); return; }
-	if(entropy == CRTHIP_ENTROPY_NONE) { s.u32(size); s.raw(data, size); return; }
+	const size_t at = s.b.size();
+	if(entropy == CRTHIP_ENTROPY_NONE) { s.u32(size); if(s.blocks) s.blocks->push_back({at, 4, size}); s.raw(data, size); return; }
 	Tunstall t;
 	t.probabilities(data, (int)size);
 	t.build();
@@ -229,6 +233,7 @@ void put_symbols(Sink &s, uint32_t entropy, const uint8_t *data, uint32_t size) 
 	for(const Sym &p : t.probs) { s.u8(p.symbol); s.u8(p.probability); }
 	s.u32(size);
 	s.u32((uint32_t)c.size());
+	if(s.blocks) s.blocks->push_back({at, s.b.size() - at, c.size()});
 	s.raw(c.data(), c.size());
 }
 
@@ -882,8 +887,8 @@ static int64_t encode_impl(const crthip_mesh *m, const crthip_attr_list *extra, 
 	if(out_nvert) *out_nvert = E.nvert;
 	if(out_nface) *out_nface = E.nface;
 	if(gpu) {
-		// the recorded streams go through the device stages in one call, then everything is spliced together; the zero padding
-		// in front of every bit stream (OutStream::write(BitStream&), cstream.h:79-89) depends on the final position, so it is made here
+		// the recorded streams go through the device stages in one call, then the container is written from the frame and their results
+		// (enc_splice.h: write_container - the zero padding in front of every bit stream depends on the final position)
 		std::vector<corto_hip::EncValueStream> in;
 		for(const Deferred &d : deferred) {
 			if(d.kind == corto_hip::BATCH_BITS) continue;
@@ -892,13 +897,14 @@ static int64_t encode_impl(const crthip_mesh *m, const crthip_attr_list *extra, 
 			v.values = d.kind == CRTHIP_ENC_SYMBOLS || d.kind == CRTHIP_ENC_VALUES_I8 ? (const void *)d.bytes.data() : (const void *)d.ints.data();
 			in.push_back(v);
 		}
-		std::vector<corto_hip::EncValueResult> res;
+		corto_hip::Coded res;
 		const int err = corto_hip::encode_value_streams(gpu, E.entropy, in, res, nullptr);
 		if(err) return err;
 		const std::vector<uint32_t> none, *split_words = &none;       // (a mesh records one packed bit stream, its CLERS split bits; a cloud none)
 		for(const Deferred &d : deferred) if(d.kind == corto_hip::BATCH_BITS) split_words = &d.words;
 		std::vector<uint8_t> f;
-		corto_hip::splice_container(E.s.b, deferred, res.data(), *split_words, f);
+		corto_hip::ByteOut o{f};
+		corto_hip::write_container(o, E.s.b, deferred, res.streams.data(), *split_words);
 		E.s.b.swap(f);
 	}
 	if(out && cap >= E.s.b.size()) memcpy(out, E.s.b.data(), E.s.b.size());
@@ -959,7 +965,8 @@ void corto_hip::tun_encoder_tables(const uint32_t counts[256], uint32_t size, Tu
 
 // crthip_encode_splice_model's front: crthip_encode_gpu's deferred run with the quantisation on the host, then every recorded stream through
 // the writers crthip_encode itself uses (put_symbols / put_array / put_values into a sink of its own: at position 0 a bit stream needs no
-// padding), taken apart again into bit words and blocks
+// padding, so its words follow its count).  The sink's bytes become a buffer of o.coded, the stream points into it: the words behind the
+// count, each block where put_symbols wrote it, cut where put_symbols ended its header.  `o` comes fresh.
 int corto_hip::encode_host_coded(const crthip_mesh *m, const crthip_attr_list *extra, HostCodedItem &o) {
 	{ const int e = encode_check(m); if(e) return e; }
 	{ const int e = encode_check_attrs(m, extra, false); if(e) return e; }
@@ -971,33 +978,27 @@ int corto_hip::encode_host_coded(const crthip_mesh *m, const crthip_attr_list *e
 	for(const NamedQuant &q : named) quantize_host(q.r);
 	E.header();
 	if(E.nface > 0) E.encode_mesh(); else E.encode_cloud();
-	o = HostCodedItem();
 	o.entropy = E.entropy; o.nvert = E.nvert; o.nface = E.nface;
 	for(const Deferred &d : deferred) {
 		o.slots.push_back(d);
 		if(d.kind == BATCH_BITS) { o.split_words = d.words; continue; }
 		Sink t;
+		std::vector<Sink::Block> blocks;
+		t.blocks = &blocks;
 		if(d.kind == CRTHIP_ENC_SYMBOLS) put_symbols(t, E.entropy, d.bytes.data(), d.count);
 		else if(d.kind == CRTHIP_ENC_ARRAY) put_array(t, E.entropy, d.count, d.ints.data(), (int)d.N);
 		else if(d.kind == CRTHIP_ENC_VALUES_I8) put_values<int8_t>(t, E.entropy, d.count, (const int8_t *)d.bytes.data(), (int)d.N);
 		else put_values<int32_t>(t, E.entropy, d.count, d.ints.data(), (int)d.N);
-		EncValueResult r;
-		size_t p = 0;
-		auto u32 = [&](size_t at) { uint32_t v; memcpy(&v, &t.b[at], 4); return v; };
-		if(d.kind != CRTHIP_ENC_SYMBOLS) {
-			const uint32_t nw = u32(0);
-			r.words.resize(nw);
-			if(nw) memcpy(r.words.data(), &t.b[4], (size_t)nw*4);
-			p = 4 + (size_t)nw*4;
+		CodedStream x;
+		if(d.kind != CRTHIP_ENC_SYMBOLS) { memcpy(&x.nwords, t.b.data(), 4); x.words = t.b.data() + 4; }
+		for(const Sink::Block &k : blocks) {
+			CodedBlock b;
+			b.head.assign(t.b.begin() + k.at, t.b.begin() + k.at + k.head);
+			b.payload = t.b.data() + k.at + k.head; b.bytes = (uint32_t)k.payload;
+			x.blocks.push_back(std::move(b));
 		}
-		while(p < t.b.size()) {                                   // the blocks, one after another
-			size_t len;
-			if(E.entropy == CRTHIP_ENTROPY_NONE) len = 4 + (size_t)u32(p);
-			else { const size_t nsym = t.b[p]; len = 9 + 2*nsym + (size_t)u32(p + 5 + 2*nsym); }
-			r.blocks.emplace_back(t.b.begin() + p, t.b.begin() + p + len);
-			p += len;
-		}
-		o.res.push_back(std::move(r));
+		o.coded.streams.push_back(std::move(x));
+		o.coded.h_made.push_back(std::move(t.b));                 // (the bytes stay where they are: the pointers hold)
 	}
 	o.frame.swap(E.s.b);
 	return CRTHIP_OK;

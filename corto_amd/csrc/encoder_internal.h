@@ -1,6 +1,7 @@
 // encoder_internal.h — pieces of the host encoder (encoder.cpp) and of the context (batch.cpp) that the GPU encoder
 // stages (encode_gpu.cpp, k_encode.hip) and the batch encoder (encode_batch.cpp) use, and the device helpers those two share: the
-// try macro, DevMem, EventTimer, quant_job, splice_container, Carver.  Not part of the C ABI.
+// try macro, DevMem, EventTimer, quant_job, Carver, and the one form a coded stream has between the coders and the container writer
+// (Coded; the writer is enc_splice.h's write_container).  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -47,14 +48,27 @@ struct TunEncoderTables {
 };
 void tun_encoder_tables(const uint32_t counts[256], uint32_t size, TunEncoderTables &out);
 
-// value arrays for the device stages (encode_gpu.cpp); values are HOST pointers
-struct EncValueStream { uint32_t kind = 0, count = 0, components = 1; const void *values = nullptr; };   // kind: CRTHIP_ENC_*
-struct EncValueResult {
-	std::vector<uint32_t> words;                    // the bit stream (empty for a symbol stream); the writer pads to 4 bytes before it
-	std::vector<std::vector<uint8_t>> blocks;       // entropy-coded log arrays (1 for ARRAY, components for VALUES) or the symbol block
+// What the value coders and the entropy coder make of a batch of streams, in the one form every container writer takes
+// (enc_splice.h: write_container).  A stream is its bit words (a symbol stream has none: words is null) and its blocks: the entropy-coded
+// log arrays (1 for ARRAY, components for VALUES) or the symbol block.  A block is its header, which the host makes (Tunstall: u8 nsym |
+// nsym x (sym, prob) | i32 size | i32 csize; entropy NONE: i32 size), and its payload (codewords; raw logs / symbols under NONE) by address
+// and length; an empty payload has no address.  on_device says where EVERY words / payload pointer of the object points: into device
+// memory, where the coders left it (crthip_encode_batch_to_device), or into the host buffers it was brought back to.  The object owns
+// what they point into and must outlive whoever reads them; each device allocation has a 256-byte aligned base and 16 bytes behind its
+// last region (enc_splice.h: SOURCES).
+struct CodedBlock { std::vector<uint8_t> head; const uint8_t *payload = nullptr; uint32_t bytes = 0; };
+struct CodedStream { uint32_t nwords = 0; const uint8_t *words = nullptr; std::vector<CodedBlock> blocks; };
+struct Coded {
+	std::vector<CodedStream> streams;
+	bool on_device = false;
+	DevMem image, tun_image, clers;                 // the value coder's image, the Tunstall coder's, the batch's host-mode CLERS block (encode_batch.cpp)
+	std::vector<uint8_t> h_back, h_codes;           // brought back: words and raw logs / symbols compacted, the Tunstall coder's codeword region
+	std::vector<std::vector<uint8_t>> h_made;       // made on the host (encoder.cpp: encode_host_coded): a buffer per stream
 };
-int encode_value_streams(crthip_ctx *ctx, uint32_t entropy, const std::vector<EncValueStream> &in, std::vector<EncValueResult> &res,
-                         crthip_kernel_times *times);
+
+// value arrays for the device stages (encode_gpu.cpp); values are HOST pointers: they go up in one copy, the payload comes back
+struct EncValueStream { uint32_t kind = 0, count = 0, components = 1; const void *values = nullptr; };   // kind: CRTHIP_ENC_*
+int encode_value_streams(crthip_ctx *ctx, uint32_t entropy, const std::vector<EncValueStream> &in, Coded &out, crthip_kernel_times *times);
 
 // quantisation on the device (encode_gpu.cpp: k_enc_quantize): HOST arrays in, HOST arrays out, one upload / download for all of them.
 // kind: QK_FLOAT, QK_NORMAL, QK_COLOR, QK_INT (format: CRTHIP_FMT_INT32 / INT16 / INT8), QK_DOUBLE - device_plan.h
@@ -73,16 +87,10 @@ inline QuantJob quant_job(const QuantRequest &r, const void *in, void *out) {   
 struct DevValueStream { uint32_t kind = 0, count = 0, components = 1, entropy = 0; const void *values = nullptr; };
 struct EncStageTimes { float hist = 0, parse = 0, pack = 0, tables = 0, trie = 0; bool any_hist = false, any_parse = false, any_pack = false, any_tables = false;
                        uint32_t host_table_streams = 0; uint64_t bytes_to_device = 0, bytes_from_device = 0; };
-int encode_value_streams_device(crthip_ctx *ctx, const std::vector<DevValueStream> &in, std::vector<EncValueResult> &res, EncStageTimes &tm);
-// ... with the payload left where the coders made it (crthip_encode_batch_to_device): per stream the device addresses and sizes of its bit
-// words and of every block's payload (codewords; raw logs / symbols under entropy NONE), and the blocks' headers, which the host makes.
-// Only the word counts, the codeword counts and what the host-made tables need come back: no k_enc_gather, no copy of words, logs or
-// codewords.  `out` owns the allocations the addresses point into and must outlive whoever reads them; each has 16 bytes behind its last
-// region and a 256-byte aligned base (enc_splice.h: SOURCES).
-struct DevCodedBlock { std::vector<uint8_t> head; const uint8_t *payload = nullptr; uint32_t bytes = 0; };
-struct DevCodedStream { uint32_t nwords = 0; const uint8_t *words = nullptr; std::vector<DevCodedBlock> blocks; };   // words: null for a symbol stream
-struct DevCoded { std::vector<DevCodedStream> streams; DevMem image, tun_image, clers; };   // clers: the batch's host-mode CLERS block (encode_batch.cpp)
-int encode_value_streams_resident(crthip_ctx *ctx, const std::vector<DevValueStream> &in, DevCoded &out, EncStageTimes &tm);
+// fetch: the payload comes back (one gather launch, one copy of words and raw logs, one of codewords) and the pointers are host pointers;
+// else only the word counts, the codeword counts and what the host-made tables need come back: no k_enc_gather, no copy of words, logs
+// or codewords.  Ends with the stream synchronised.
+int encode_value_streams_device(crthip_ctx *ctx, const std::vector<DevValueStream> &in, bool fetch, Coded &out, EncStageTimes &tm);
 void enc_report_times(crthip_kernel_times *times, const EncStageTimes &tm);   // appends the stages' entries behind times->count
 
 // ---- crthip_encode_batch (encoder.cpp: checks, topology pass and container; encode_batch.cpp: the device half) ----
@@ -123,33 +131,10 @@ void batch_topology(const crthip_mesh *m, const crthip_attr_list *extra, BatchIt
 struct EncTopoRecord;
 void batch_frame(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it, const EncTopoRecord &rec, const uint32_t *group_end,
                  const uint32_t *split_words);
-// A container from its frame (the container without its streams), the slots its body recorded (Deferred, BatchStream: `at` in the frame,
-// `kind`) in order, and the device's result for every slot but the split bits (kind BATCH_BITS: split_words, packed already).  A bit
-// stream is its word count, zero padding to 4 bytes of the container written so far, its words (OutStream::write(BitStream&),
-// cstream.h:79-89); a value stream's bit words come before its blocks.  Returns how many results it used.
-template <class SlotT>
-size_t splice_container(const std::vector<uint8_t> &frame, const std::vector<SlotT> &slots, const EncValueResult *results,
-                        const std::vector<uint32_t> &split_words, std::vector<uint8_t> &out) {
-	out.clear();
-	out.reserve(frame.size() + 64);
-	auto u32 = [&](uint32_t v) { const uint8_t b[4] = {(uint8_t)v, (uint8_t)(v >> 8), (uint8_t)(v >> 16), (uint8_t)(v >> 24)}; out.insert(out.end(), b, b + 4); };
-	auto bits = [&](const std::vector<uint32_t> &w) { u32((uint32_t)w.size()); while(out.size() & 3) out.push_back(0); for(uint32_t x : w) u32(x); };
-	size_t prev = 0, r = 0;
-	for(const SlotT &s : slots) {
-		out.insert(out.end(), frame.begin() + prev, frame.begin() + s.at); prev = s.at;
-		if(s.kind == BATCH_BITS) { bits(split_words); continue; }
-		const EncValueResult &x = results[r++];
-		if(s.kind != CRTHIP_ENC_SYMBOLS) bits(x.words);
-		for(const std::vector<uint8_t> &blk : x.blocks) out.insert(out.end(), blk.begin(), blk.end());
-	}
-	out.insert(out.end(), frame.begin() + prev, frame.end());
-	return r;
-}
-
 // One item through the host encoder in its deferred mode, each recorded stream then coded by the host encoder's own writers
-// (crthip_encode_splice_model): the frame, the slots, a result per slot but the split bits (blocks whole, header included), the split words.
-// Runs encode_check / encode_check_attrs first; returns their code.
-struct HostCodedItem { std::vector<uint8_t> frame; std::vector<BatchStream> slots; std::vector<EncValueResult> res; std::vector<uint32_t> split_words;
+// (crthip_encode_splice_model): the frame, the slots, a coded stream per slot but the split bits (host pointers into coded.h_made), the
+// split words.  Runs encode_check / encode_check_attrs first; returns their code.
+struct HostCodedItem { std::vector<uint8_t> frame; std::vector<BatchStream> slots; Coded coded; std::vector<uint32_t> split_words;
                        uint32_t entropy = 0, nvert = 0, nface = 0; };
 int encode_host_coded(const crthip_mesh *m, const crthip_attr_list *extra, HostCodedItem &out);
 

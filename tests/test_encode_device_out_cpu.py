@@ -61,6 +61,39 @@ def _host_encode(m, k):
     return m, ca.encode(m, **k)
 
 
+def _first(m, n, index=None):
+    """the first n vertices of m with every attribute it has, as a cloud or with the index given"""
+    backing = np.zeros((4, 3), dtype=np.float32)                    # (an empty position array still has an address: the host encoder forms &position[0])
+    c = synth.Mesh(position=backing[:0], index=index)
+    c.position = np.ascontiguousarray(m.position[:n]) if n else backing[:0]
+    for a in ("normal", "color", "uv", "radius"):
+        if getattr(m, a) is not None:
+            setattr(c, a, np.ascontiguousarray(getattr(m, a)[:n]))
+    return c
+
+
+def _tiny_items():
+    """The shapes at which a coded block's header, its payload and the payload's address can disagree, TUNSTALL (1) and NONE (0) side by
+    side: a 1-vertex cloud (every stream one symbol: under TUNSTALL header-only blocks, csize 0, no payload address; under NONE 1 byte
+    of payload), a 0-vertex cloud (zero-length streams, zero words), a single triangle, a small mesh whose colour is constant (its logs
+    are all zero: a one-symbol Tunstall block next to multi-symbol ones), and a small mesh with one generic attribute of 16 PARALLEL
+    components (sixteen blocks in one stream)."""
+    base = synth.bumpy_sphere(8, 4, seed=7)
+    items = []
+    for e in (1, 0):
+        items.append((_first(base, 1), dict(entropy=e)))
+        items.append((_first(base, 0), dict(entropy=e)))
+        items.append((_first(base, 3, index=np.array([[0, 1, 2]], dtype=np.uint32)), dict(entropy=e)))
+    flat = synth.bumpy_sphere(8, 4, seed=8)
+    flat.color[:] = flat.color[0]
+    wide = synth.bumpy_sphere(6, 4, seed=9)
+    w16 = np.random.default_rng(9).integers(-2000, 2000, (wide.nvert, 16)).astype(np.int16)
+    for e in (1, 0):
+        items.append((flat, dict(entropy=e)))
+        items.append((wide, dict(entropy=e, attributes=[("w16", w16, 1.0, ca.PARALLEL)])))
+    return items
+
+
 def test_symbols_and_header(L):
     hdr = open(os.path.join(ROOT, "include", "corto_hip.h")).read()
     for name in ("crthip_encode_batch_to_device", "crthip_encode_batch_bound", "crthip_ctx_encode_splice_stats"):
@@ -145,6 +178,17 @@ def test_splice_model_equals_the_host_encoder():
     for i, (m, k) in enumerate(items):
         m, expect = _host_encode(m, k)
         for mis in ((0, 1 + i % 15) if i % 8 else (0, 1, 4, 15)):
+            blob, pad = ca.encode_splice_model(m, dst_misalign=mis, **k)
+            assert blob.tobytes() == expect.tobytes(), (i, mis)
+            assert len(pad) == (-len(blob)) % 16 and not pad.any(), (i, mis)
+
+
+def test_splice_model_equals_the_host_encoder_on_tiny_shapes():
+    items = _tiny_items()
+    assert sorted({m.nvert for m, _ in items})[:3] == [0, 1, 3] and {k["entropy"] for _, k in items} == {0, 1}
+    for i, (m, k) in enumerate(items):
+        expect = ca.encode(m, **k)
+        for mis in (0, 1, 15):
             blob, pad = ca.encode_splice_model(m, dst_misalign=mis, **k)
             assert blob.tobytes() == expect.tobytes(), (i, mis)
             assert len(pad) == (-len(blob)) % 16 and not pad.any(), (i, mis)

@@ -17,11 +17,13 @@ import corto_amd as ca
 from corto_amd import synth
 from conftest import GOLDEN, aligned, load_golden
 from test_encode_batch_gpu import _corpus
+from test_encode_device_out_cpu import _tiny_items
 from test_encode_resident_gpu import _Unaligned, _dev, _host_encode
 
 pytestmark = pytest.mark.gpu
 
 E_ARGUMENT = -8
+E_LIMIT = -11
 MODES = ("host", "device", "split")
 SPLICE_JOB_BYTES = 24                                               # sizeof(SpliceJob), csrc/device_plan.h
 
@@ -94,6 +96,42 @@ def test_mixed_corpus_in_every_topology_mode(ctx):
     out, offs, lens, st = _to_device(ctx, items, False, with_stats=True)
     _check_arena(out, offs, lens, expect, st["total"], "host inputs")
     ctx.set_encode_topology("host")
+
+
+def test_tiny_shapes_three_ways(ctx, monkeypatch):
+    """One batch of the shapes where a block's header, payload and address can disagree (_tiny_items: TUNSTALL and NONE items side by
+    side in one chunk, so both kinds of block header meet in one plan and one gather) through crthip_encode_batch, through
+    crthip_encode_batch_to_device and, item by item, through the host encoder: the same bytes, in every topology mode; then to the
+    device once more in several chunks.  The host encoder takes the 0-vertex cloud, so it is in."""
+    items = _tiny_items()
+    ms, ks = [m for m, _ in items], [k for _, k in items]
+    expect = [ca.encode(m, **k).tobytes() for m, k in items]
+    for mode in MODES:
+        ctx.set_encode_topology(mode)
+        blobs, bs = ca.encode_batch(ms, ctx, kw=ks, with_stats=True)
+        assert [b.tobytes() for b in blobs] == expect, mode
+        out, offs, lens, st = ca.encode_batch_to_device(ms, ctx, kw=ks, with_stats=True)
+        _check_arena(out, offs, lens, expect, st["total"], ("tiny", mode))
+        assert st["splice"]["launches"] == 1 and st["value_streams"] == bs["value_streams"], mode
+    ctx.set_encode_topology("host")
+    # In several chunks: a chunk's image is its job region (64 KiB) and a few 256-byte regions per attribute of every item.  The first
+    # budget, in steps of 8 KiB, that holds every item alone (a smaller one refuses the call before any device work: E_LIMIT) cannot hold
+    # the ten together: the other nine take far more than one step.
+    st = None
+    for budget in range(72 << 10, 160 << 10, 8 << 10):
+        monkeypatch.setenv("CORTO_ENCODE_IMAGE_BUDGET", str(budget))
+        small = ca.Context(0)
+        monkeypatch.delenv("CORTO_ENCODE_IMAGE_BUDGET")
+        try:
+            out, offs, lens, st = ca.encode_batch_to_device(ms, small, kw=ks, with_stats=True)
+        except ca.CortoError as e:
+            assert e.code == E_LIMIT, e
+            continue
+        finally:
+            small.close()
+        break
+    assert st is not None and 2 <= st["splice"]["launches"] <= len(items), (budget, st and st["splice"])
+    _check_arena(out, offs, lens, expect, st["total"], ("tiny, chunks", budget))
 
 
 def test_tied_clouds(ctx):
