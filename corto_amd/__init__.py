@@ -114,6 +114,21 @@ class PoolReport(C.Structure):
                 ("host_wait_us", C.c_float), ("host_finish_us", C.c_float), ("host_plan_us", C.c_float), ("host_launch_max_us", C.c_float)]
 
 
+class OutArray(C.Structure):
+    """crthip_out_array: one array of crthip_output_layout"""
+    _fields_ = [("offset", C.c_uint64), ("bytes", C.c_uint64), ("format", C.c_uint32), ("out_components", C.c_uint32)]
+
+
+class PoolDest(C.Structure):
+    """crthip_pool_dest: where crthip_pool_decode delivers one item"""
+    _fields_ = [("out", C.c_void_p), ("cap", C.c_uint64), ("device_slot", C.c_int32), ("reserved", C.c_uint32)]
+
+
+POOL_DEST_HOST = -1
+LAYOUT_RENDER = 1
+PoolDoneFn = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32))
+
+
 class KernelTimes(C.Structure):
     _fields_ = [("count", C.c_uint32), ("name", C.c_char_p * MAX_KERNELS), ("ms", C.c_float * MAX_KERNELS),
                 ("launches", C.c_uint32 * MAX_KERNELS)]
@@ -230,6 +245,8 @@ def lib():
         L.crthip_pool_set_outputs_to_host.argtypes = [C.c_void_p, C.c_int]
         L.crthip_pool_set_render_layouts.argtypes = [C.c_void_p, C.c_int]
         L.crthip_pool_run.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(PoolReport), C.c_void_p]
+        L.crthip_pool_decode.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, PoolDoneFn, C.c_void_p, C.POINTER(PoolReport)]
+        L.crthip_output_layout.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
         L.crthip_pool_lane_item.restype = C.c_int64
         L.crthip_pool_lane_item.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.crthip_pool_lane_read.restype = C.c_int64
@@ -281,6 +298,33 @@ def probe_groups(blob: np.ndarray) -> List[int]:
     g = np.zeros(max(int(n), 1), dtype=np.uint32)
     lib().crthip_probe_groups(_np_ptr(blob), len(blob), _np_ptr(g), int(n))
     return [int(x) for x in g[:n]]
+
+
+_LAYOUT_DT = {FMT_FLOAT: np.float32, FMT_INT16: np.int16, FMT_UINT8: np.uint8, FMT_UINT32: np.uint32, FMT_UINT16: np.uint16}
+
+
+def output_layout(blobs: Sequence[np.ndarray], render: bool = False):
+    """crthip_output_layout: where the decoded arrays of `blobs` lie in ONE output block (what Pool.decode delivers; host only, no GPU
+    needed).  Returns (per blob {name: (byte offset, numpy dtype, shape)} with the index under "index", the block's bytes)."""
+    n = len(blobs)
+    ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in blobs])
+    lens = np.array([len(b) for b in blobs], dtype=np.uint32)
+    total = C.c_uint64()
+    _check(lib().crthip_output_layout(n, ptrs, _np_ptr(lens), LAYOUT_RENDER if render else 0, None, None, C.byref(total)))   # (names the failing blob)
+    infos = [probe(b) for b in blobs]
+    attr = (OutArray * max(sum(i.nattr for i in infos), 1))()
+    index = (OutArray * max(n, 1))()
+    _check(lib().crthip_output_layout(n, ptrs, _np_ptr(lens), LAYOUT_RENDER if render else 0, attr, index, C.byref(total)))
+    out, k = [], 0
+    for i, info in enumerate(infos):
+        d = {}
+        for a in info.attrs():
+            d[a["name"]] = (int(attr[k].offset), np.dtype(_LAYOUT_DT[attr[k].format]), (info.nvert, int(attr[k].out_components)))
+            k += 1
+        if index[i].bytes:
+            d["index"] = (int(index[i].offset), np.dtype(_LAYOUT_DT[index[i].format]), (info.nface, 3))
+        out.append(d)
+    return out, int(total.value)
 
 
 def arena_layout(lens: Sequence[int]):
@@ -1077,6 +1121,26 @@ class Batch:
             pass
 
 
+class PoolDecoded:
+    """one item of Pool.decode: its block, the layout's bytes, the destination slot (POOL_DEST_HOST for a host block), the per-blob
+    status codes and, per blob, {name: a typed view into the block}"""
+
+    def __init__(self, block, total, slot):
+        self.block, self.total, self.slot = block, total, slot
+        self.status = np.zeros(0, dtype=np.int32)
+        self.outputs = []
+
+    def _view(self, offset, dtype, shape):
+        nbytes = int(np.prod(shape)) * dtype.itemsize
+        if isinstance(self.block, np.ndarray):
+            return self.block[offset:offset + nbytes].view(dtype).reshape(shape)
+        import torch
+        tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.int16): torch.int16, np.dtype(np.uint8): torch.uint8,
+               np.dtype(np.uint32): torch.int32, np.dtype(np.uint16): torch.int16}[dtype]      # (torch has no unsigned 16 / 32: the bits)
+        t = self.block[offset:offset + nbytes].view(tdt).view(*shape)
+        return t if self.block.is_cuda else t.numpy().view(dtype)
+
+
 class Pool:
     """crthip_pool: the multi-GPU decode pool - `devices` GPUs, `threads` host threads per GPU with `depth` batches in flight each,
     one shared work queue over the submitted batches, no collective (include/corto_hip.h)."""
@@ -1089,6 +1153,7 @@ class Pool:
         self.lanes = int(lib().crthip_pool_lanes(self.handle))
         self.warning = lib().crthip_pool_warning(self.handle).decode()
         self._keep = None
+        self._render = False
 
     def device_cpus(self, slot: int) -> List[int]:
         """host CPUs of pool device `slot`'s NUMA node (what its worker threads are pinned to); [] when sysfs names none"""
@@ -1113,13 +1178,11 @@ class Pool:
     def set_render_layouts(self, on: bool = True):
         """int16 normals and uint16 indices (blobs of fewer than 65 536 vertices) in every lane's outputs: SURVEY 8f3's layouts, 22 % fewer output bytes a C4 blob"""
         _check(lib().crthip_pool_set_render_layouts(self.handle, int(on)))
+        self._render = bool(on)
 
-    def run(self, items, steps: int, warmup: int = 0, arenas=None):
-        """items: list of batches (each a list of aligned uint8 blobs).  arenas: None (every step uploads its blobs) or, per item, a
-        list with one device tensor per pool device (the item's blobs resident there in arena_layout order).
-        Returns (PoolReport, completion times of the timed steps in seconds since the timed region began)."""
-        n = len(items)
-        arr = (PoolItem * n)()
+    def _pool_items(self, items, arenas):
+        """the crthip_pool_item array of a call and what it points into"""
+        arr = (PoolItem * max(len(items), 1))()
         keep = []
         for j, blobs in enumerate(items):
             ptrs = (C.c_void_p * max(len(blobs), 1))(*[b.ctypes.data for b in blobs])
@@ -1130,6 +1193,82 @@ class Pool:
             keep.append((ptrs, lens, ar))
             arr[j].nblobs = len(blobs); arr[j].blobs = C.cast(ptrs, C.c_void_p); arr[j].lens = lens.ctypes.data
             arr[j].device_arena = C.cast(ar, C.c_void_p) if ar is not None else None
+        return arr, keep
+
+    def decode(self, items, dest="device", slots=None, arenas=None, on_done=None, raise_on_error=False, blocks=None, caps=None):
+        """crthip_pool_decode: every item (a list of aligned uint8 blobs) decoded exactly once into a block of its own, laid out as
+        output_layout(item, render) says.  dest - one word, or one per item: "device" (a torch uint8 tensor on the GPU of pool device
+        slots[j], default j % ndevices; only that slot's lanes decode the item), "host" (a pinned torch tensor) or "pageable" (a numpy
+        array); any device decodes a host item.  blocks: ready-made blocks instead (256-byte aligned, at least the layout's bytes;
+        caps: what to tell the library about their sizes, default their own).  arenas: as for run().  on_done(item, slot, status)
+        is called on a worker thread as each item becomes final and must not call into the pool.
+        Returns (per item a PoolDecoded: .block, .status, .outputs[i][name] - views into the block, torch for a device block, numpy
+        for a host one -, .total, .slot; the PoolReport).  raise_on_error: a blob that failed raises its code after the call."""
+        n = len(items)
+        kinds = [dest] * n if isinstance(dest, str) else list(dest)
+        arr, keep = self._pool_items(items, arenas)
+        layouts = []
+        for j, blobs in enumerate(items):
+            try:
+                layouts.append(output_layout(blobs, self._render))
+            except CortoError:                              # a blob the header parse refuses: the call reports it in the item's statuses
+                layouts.append((None, 0))
+        res, dests = [], (PoolDest * max(n, 1))()
+        for j in range(n):
+            total = layouts[j][1]
+            slot = POOL_DEST_HOST
+            if kinds[j] == "device":
+                slot = int(slots[j]) if slots is not None else j % len(self.devices)
+            elif kinds[j] not in ("host", "pageable"):
+                raise ValueError("dest: device, host or pageable")
+            if blocks is not None:
+                block = blocks[j]
+            elif kinds[j] == "pageable":
+                raw = np.zeros(max(total, 256) + 256, dtype=np.uint8)
+                block = raw[(-raw.ctypes.data) % 256:][:max(total, 256)]
+            else:
+                import torch
+                if kinds[j] == "device":
+                    block = torch.empty(max(total, 256), dtype=torch.uint8, device=torch.device("cuda", self.devices[slot]))
+                else:
+                    block = torch.empty(max(total, 256), dtype=torch.uint8).pin_memory()
+            is_np = isinstance(block, np.ndarray)
+            if not is_np and block.is_cuda:
+                _torch_ready(block.device)                   # (whatever torch queued on the block has run before the pool's streams write it)
+            dests[j].out = block.ctypes.data if is_np else block.data_ptr()
+            dests[j].cap = int(caps[j]) if caps is not None and caps[j] is not None else (block.nbytes if is_np else block.numel() * block.element_size())
+            dests[j].device_slot = slot
+            res.append(PoolDecoded(block, total, slot))
+        nblobs = [len(b) for b in items]
+        status = np.zeros(max(sum(nblobs), 1), dtype=np.int32)
+        raised = []
+
+        def _done(_user, item, slot, st):
+            try:
+                on_done(int(item), int(slot), np.ctypeslib.as_array(st, shape=(max(nblobs[item], 1),))[:nblobs[item]].copy())
+            except BaseException as e:                      # (an exception cannot cross the C frames of a worker thread: after the call)
+                raised.append(e)
+        cb = PoolDoneFn(_done) if on_done is not None else PoolDoneFn()
+        self._keep = (arr, keep, items, arenas, dests, res, cb)      # (alive for the call: the callback's thunk above all)
+        rep = PoolReport()
+        _check(lib().crthip_pool_decode(self.handle, n, arr, dests, _np_ptr(status), cb, None, C.byref(rep)))
+        if raised:
+            raise raised[0]
+        first = np.cumsum([0] + nblobs)
+        for j, r in enumerate(res):
+            r.status = status[first[j]:first[j + 1]].copy()
+            if layouts[j][0] is not None:
+                r.outputs = [{name: r._view(o, dt, shape) for name, (o, dt, shape) in d.items()} for d in layouts[j][0]]
+            if raise_on_error and r.status.any():
+                _check(int(r.status[np.flatnonzero(r.status)[0]]))
+        return res, rep
+
+    def run(self, items, steps: int, warmup: int = 0, arenas=None):
+        """items: list of batches (each a list of aligned uint8 blobs).  arenas: None (every step uploads its blobs) or, per item, a
+        list with one device tensor per pool device (the item's blobs resident there in arena_layout order).
+        Returns (PoolReport, completion times of the timed steps in seconds since the timed region began)."""
+        n = len(items)
+        arr, keep = self._pool_items(items, arenas)
         self._keep = (arr, keep, items, arenas)
         rep = PoolReport()
         stamps = np.zeros(max(steps, 1), dtype=np.float64)

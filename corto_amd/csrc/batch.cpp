@@ -7,58 +7,11 @@
 #include "batch_internal.h"
 #include "crt_walk.h"
 
-// ------------------------------------------------------------------------------------------------
-static thread_local std::string g_error;
-int fail(int code, const std::string &msg) { g_error = msg; return code; }
-
-extern "C" const char *crthip_strerror(int code) {
-	switch(code) {
-	case CRTHIP_OK: return "ok";
-	case CRTHIP_E_ALIGN: return "Memory must be alignegned on 4 bytes.";
-	case CRTHIP_E_MAGIC: return "Not a crt file.";
-	case CRTHIP_E_TRUNCATED: return "Truncated or inconsistent crt stream.";
-	case CRTHIP_E_ENTROPY: return "Unknown entropy";
-	case CRTHIP_E_TOPOLOGY: return "Decoding topology failed";
-	case CRTHIP_E_NORMAL_NEEDS_POSITION: return "No position attribute found. Use DIFF normal strategy instead.";
-	case CRTHIP_E_FORMAT: return "Format not supported for this attribute on the device path";
-	case CRTHIP_E_ARGUMENT: return "Invalid argument";
-	case CRTHIP_E_DEVICE: return "No usable HIP device (the MI355X path has no CPU fallback)";
-	case CRTHIP_E_NOMEM: return "Out of memory";
-	case CRTHIP_E_LIMIT: return "Too many attributes or components for this build";
-	}
-	return "unknown error";
-}
-int fail(int code) { return fail(code, crthip_strerror(code)); }
-// context plumbing for the encoder stages (encoder_internal.h)
-namespace corto_hip { int ctx_fail(int code, const char *msg) { return fail(code, msg ? std::string(msg) :
-	std::string(crthip_strerror(code))); } }
-extern "C" const char *crthip_last_error(void) { return g_error.c_str(); }
+// (the thread's last error, crthip_strerror and crthip_probe are host_probe.cpp's: no HIP there)
 extern "C" uint32_t crthip_abi_version(void) { return CRTHIP_ABI_VERSION; }
-
 
 // ------------------------------------------------------------------------------------------------
 // host-only probes
-static void fill_info(const BlobHeader &h, crthip_blob_info *info) {
-	memset(info, 0, sizeof(*info));
-	info->version = h.version; info->entropy = h.entropy; info->nvert = h.nvert; info->nface = h.nface;
-	info->nattr = (uint32_t)h.attrs.size(); info->nexif = (uint32_t)h.exif.size(); info->body_offset = h.body_offset;
-	for(size_t i = 0; i < h.attrs.size(); i++) {
-		crthip_attr_info &a = info->attr[i];
-		strncpy(a.name, h.attrs[i].name.c_str(), CRTHIP_NAME_MAX - 1);
-		a.codec = h.attrs[i].codec; a.q = h.attrs[i].q; a.components = h.attrs[i].N;
-		a.format = h.attrs[i].format; a.strategy = h.attrs[i].strategy;
-	}
-}
-
-extern "C" int crthip_probe(const uint8_t *blob, size_t len, crthip_blob_info *info) {
-	if(!blob || !info) return fail(CRTHIP_E_ARGUMENT);
-	BlobHeader h;
-	int err = parse_header(blob, len, h);
-	if(err) return fail(err);
-	fill_info(h, info);
-	return CRTHIP_OK;
-}
-
 // key\0value\0... into out when it fits; the bytes needed
 static int64_t flat_pairs(const std::vector<std::pair<std::string, std::string>> &kvs, char *out, size_t cap) {
 	std::string flat;

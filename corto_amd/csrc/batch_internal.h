@@ -27,6 +27,7 @@ using namespace corto_hip;
 // errors: the thread's last message (crthip_last_error) and the code handed back
 int fail(int code, const std::string &msg);
 int fail(int code);
+void fill_info(const BlobHeader &h, crthip_blob_info *info);   // host_probe.cpp: what crthip_probe / crthip_batch_info hand out
 #define HIP_TRY(expr) \
 	do { hipError_t e_ = (expr); if(e_ != hipSuccess) return fail(CRTHIP_E_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); } while(0)
 inline double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }

@@ -21,6 +21,7 @@
 
 #include "../../include/corto_hip.h"
 #include "encoder_internal.h"
+#include "output_layout.h"
 
 using corto_hip::ctx_fail;
 
@@ -32,10 +33,13 @@ struct Slot {                       // a batch object and the item it is planned
 	std::vector<crthip_attr_binding> binds;
 	std::vector<void *> index_ptr;
 	std::vector<uint32_t> index_fmt;
-	std::vector<size_t> attr_off, index_off;     // byte offsets inside the lane's `out` (attr_off: per binding entry)
 	std::vector<uint32_t> first_attr;            // first binding entry of blob i
 	std::vector<int32_t> status;
-	size_t out_used = 0;            // outputs_to_host: the first out_used bytes of `out` are copied behind the decode
+	uint8_t *base = nullptr;        // the block the bindings point into: the lane's `out`, or (crthip_pool_decode) the item's device destination
+	size_t out_used = 0;            // a step that ends with a D2H copy: the first out_used bytes of the lane's `out` are copied behind the decode
+	bool to_host = false;           // ... it does: crthip_pool_set_outputs_to_host, or a host destination
+	void *pinned_dst = nullptr;     // crthip_pool_decode: the copy goes straight here (a pinned destination); else into the lane's pinned mirror,
+	void *pageable_dst = nullptr;   // ... from where the worker moves it here when it harvests the step
 	int64_t item = -1;              // the item
 	uint64_t step = 0;              // its global step number
 };
@@ -71,6 +75,7 @@ struct crthip_pool {
 	bool to_host = false;           // crthip_pool_set_outputs_to_host: every step ends with a D2H copy of its outputs into the lane's pinned block
 	bool pipelined = false;         // every lane is a single-stream context and $CORTO_CARRY is not 0: the lanes run two batches each (Lane)
 	size_t out_need = 0;            // the largest output block any item of the run asks for: a pipelined lane's block is not moved under a planned batch
+	bool decoded = false;           // the last call was crthip_pool_decode: the lanes hold nothing for crthip_pool_lane_item / _read
 	// state of one run
 	std::atomic<uint64_t> next{0}, completed{0};
 	std::mutex m;
@@ -185,78 +190,73 @@ extern "C" int crthip_pool_set_packed_host_blobs(crthip_pool *p, int on) {
 // running batch's kernels on the lane's own stream (0.15-0.20: a DMA copy queued behind kernels is started late), the same two with a
 // copy KERNEL reading the pinned buffer over PCIe (0.13 / 0.156).  All slower; removed.  What does help a little is one more lane per
 // thread's worth of contexts (5 x 4: 0.091): the lane whose blobs are on their way is idle for the GPU.
-// bytes of one output array, and of a blob's index, in a lane's block
-static size_t attr_out_bytes(const crthip_pool *p, const crthip_blob_info &info, const crthip_attr_info &a) {
-	if(a.codec == CRTHIP_CODEC_NORMAL) return (size_t)info.nvert*(p->render ? 6 : 12);
-	if(a.codec == CRTHIP_CODEC_COLOR) return (size_t)info.nvert*4;
-	return (size_t)info.nvert*a.components*4;
-}
-static bool index_is_u16(const crthip_pool *p, const crthip_blob_info &info) { return info.nface && p->render && info.nvert < 65536; }
-static size_t take_out(size_t &off, size_t n) { off = (off + 255) & ~(size_t)255; const size_t r = off; off += n; return r; }
-// the block an item's outputs need, from the blobs' headers alone (lane_plan lays out the same way)
-static int item_out_bytes(const crthip_pool *p, const crthip_pool_item &it, size_t *total) {
-	size_t off = 0;
+// An item's outputs, from the blobs' headers alone: where every array lies in the item's block - corto_hip::layout_blob, the rule of
+// crthip_output_layout - and what a call reports for it.  Made once per item in front of a call; lane_plan binds from it.
+struct ItemPlan {
+	int err = CRTHIP_OK;                         // the first failing blob's code: the item cannot be planned
+	std::string err_msg;
+	uint64_t total = 0;                          // crthip_output_layout's total
+	uint64_t tris = 0, verts = 0;
+	std::vector<crthip_out_array> attr, index;   // sum(nattr) / nblobs entries
+	std::vector<uint32_t> first_attr;            // first attr entry of blob i
+	// crthip_pool_decode
+	size_t status_at = 0;                        // the item's first entry in the call's status array
+	bool pinned = false;                         // a host destination that is pinned memory
+};
+static int item_plan(const crthip_pool *p, const crthip_pool_item &it, ItemPlan &P) {
+	const uint32_t flags = p->render ? CRTHIP_LAYOUT_RENDER : 0u;
+	uint64_t off = 0;
 	crthip_blob_info info;
+	P.index.resize(it.nblobs); P.first_attr.resize(it.nblobs);
 	for(uint32_t i = 0; i < it.nblobs; i++) {
 		const int err = crthip_probe(it.blobs[i], it.lens[i], &info);
-		if(err) return err;
-		for(uint32_t k = 0; k < info.nattr; k++) (void)take_out(off, attr_out_bytes(p, info, info.attr[k]));
-		if(info.nface) (void)take_out(off, (size_t)info.nface*(index_is_u16(p, info) ? 6 : 12));
+		if(err) { P.err = err; P.err_msg = std::string(crthip_strerror(err)) + " (blob " + std::to_string(i) + ")"; return ctx_fail(err, P.err_msg.c_str()); }
+		P.first_attr[i] = (uint32_t)P.attr.size();
+		P.attr.resize(P.attr.size() + info.nattr);
+		corto_hip::layout_blob(info, flags, off, P.attr.data() + P.first_attr[i], &P.index[i]);
+		P.tris += info.nface; P.verts += info.nvert;
 	}
-	*total = off + 256;
+	P.total = corto_hip::layout_total(off);
 	return CRTHIP_OK;
 }
-// plan `item` on one of the lane's batch objects, lay its outputs out in the lane's device block and bind them
-static int lane_plan(crthip_pool *p, Lane &L, Slot &S, const crthip_pool_item &it, int64_t item_id) {
+
+// plan `item` on one of the lane's batch objects and bind its outputs: into the lane's device block (`dest` null; the block holds at least
+// `block_need` bytes afterwards) or straight into `dest`.  *item_fault: the failure is the item's own - a blob the host walk refuses - and
+// the lane is as it was, but for an empty-handed batch object
+static int lane_plan(crthip_pool *p, Lane &L, Slot &S, const crthip_pool_item &it, int64_t item_id, const ItemPlan &P, uint8_t *dest,
+                     size_t block_need, bool *item_fault) {
 	const void *arena = it.device_arena ? it.device_arena[L.slot] : nullptr;
 	int err = CRTHIP_OK;
+	*item_fault = false;
 	if(!S.batch && &S == &L.s[1]) {                              // the lane's second object lives on the context's other set of per-call blocks
 		err = crthip_batch_create(L.ctx, 0, nullptr, nullptr, nullptr, &S.batch);
 		if(!err) err = crthip_batch_set_parity(S.batch, 1);
 		if(err) return err;
 	}
+	S.item = -1;
 	err = S.batch ? crthip_batch_reset(S.batch, it.nblobs, it.blobs, it.lens, arena)
 	              : crthip_batch_create(L.ctx, it.nblobs, it.blobs, it.lens, arena, &S.batch);
-	if(err) return err;
-	if(S.item != item_id || S.binds.empty()) {                // the layout of an item's outputs depends on the item alone
-		S.binds.clear(); S.attr_off.clear(); S.first_attr.assign(it.nblobs, 0);
-		S.index_ptr.assign(it.nblobs, nullptr); S.index_fmt.assign(it.nblobs, CRTHIP_FMT_UINT32); S.index_off.assign(it.nblobs, 0);
-		size_t off = 0;
-		crthip_blob_info info;
-		for(uint32_t i = 0; i < it.nblobs; i++) {
-			if((err = crthip_batch_info(S.batch, i, &info)) != 0) return err;
-			S.first_attr[i] = (uint32_t)S.binds.size();
-			for(uint32_t k = 0; k < info.nattr; k++) {
-				const crthip_attr_info &a = info.attr[k];
-				crthip_attr_binding b; b.buffer = nullptr; b.format = CRTHIP_FMT_FLOAT; b.out_components = 0; b.stride = 0; b.reserved = 0;
-				if(a.codec == CRTHIP_CODEC_NORMAL) { if(p->render) b.format = CRTHIP_FMT_INT16; }
-				else if(a.codec == CRTHIP_CODEC_COLOR) { b.format = CRTHIP_FMT_UINT8; b.out_components = 4; }
-				S.attr_off.push_back(take_out(off, attr_out_bytes(p, info, a)));
-				S.binds.push_back(b);
-			}
-			if(index_is_u16(p, info)) S.index_fmt[i] = CRTHIP_FMT_UINT16;
-			if(info.nface) S.index_off[i] = take_out(off, (size_t)info.nface*(S.index_fmt[i] == CRTHIP_FMT_UINT16 ? 6 : 12));
-		}
-		const size_t total = std::max(off + 256, p->out_need);
-		if(total > L.out_cap) {
-			// (never under a batch that is planned or running: out_need covers every item of the run, so a lane's block is made by its first plan)
-			if(L.busy || L.staged) return ctx_fail(CRTHIP_E_ARGUMENT, "corto_hip pool: a lane's output block would move under a planned batch");
-			if(L.out) (void)hipFree(L.out);
-			L.out = nullptr; L.out_cap = 0;
-			for(Slot &O : L.s) if(&O != &S) { O.binds.clear(); O.item = -1; }
-			if(hipMalloc(&L.out, total + total/8) != hipSuccess) return ctx_fail(CRTHIP_E_NOMEM, nullptr);
-			L.out_cap = total + total/8;
-		}
-		uint8_t *base = (uint8_t *)L.out;
-		for(size_t k = 0; k < S.binds.size(); k++) S.binds[k].buffer = base + S.attr_off[k];
-		for(uint32_t i = 0; i < it.nblobs; i++) {
-			if((err = crthip_batch_info(S.batch, i, &info)) != 0) return err;
-			S.index_ptr[i] = info.nface ? base + S.index_off[i] : nullptr;
-		}
-		S.status.assign(it.nblobs, 0);
-		S.out_used = off;
+	if(err) { *item_fault = err != CRTHIP_E_DEVICE && err != CRTHIP_E_NOMEM; return err; }
+	if(block_need > L.out_cap) {
+		// (never under a batch that is planned or running: out_need covers every item of the call, so a lane's block is made by its first plan)
+		if(L.busy || L.staged) return ctx_fail(CRTHIP_E_ARGUMENT, "corto_hip pool: a lane's output block would move under a planned batch");
+		if(L.out) (void)hipFree(L.out);
+		L.out = nullptr; L.out_cap = 0;
+		if(hipMalloc(&L.out, block_need + block_need/8) != hipSuccess) return ctx_fail(CRTHIP_E_NOMEM, nullptr);
+		L.out_cap = block_need + block_need/8;
 	}
-	if(p->to_host && L.host_cap < L.out_cap) {                 // (first use: 32 MB of pinned memory a lane for a C4 item)
+	S.base = dest ? dest : (uint8_t *)L.out;
+	S.first_attr = P.first_attr;
+	S.binds.resize(P.attr.size()); S.index_ptr.resize(it.nblobs); S.index_fmt.resize(it.nblobs);
+	for(size_t k = 0; k < P.attr.size(); k++) {
+		crthip_attr_binding &b = S.binds[k];
+		b.buffer = S.base + P.attr[k].offset; b.format = P.attr[k].format; b.stride = 0; b.reserved = 0;
+		b.out_components = P.attr[k].format == CRTHIP_FMT_UINT8 ? P.attr[k].out_components : 0;   // (colour: 4 of them, whatever the stream holds)
+	}
+	for(uint32_t i = 0; i < it.nblobs; i++) { S.index_ptr[i] = P.index[i].bytes ? S.base + P.index[i].offset : nullptr; S.index_fmt[i] = P.index[i].format; }
+	S.status.assign(it.nblobs, 0);
+	S.out_used = (size_t)P.total;
+	if(S.to_host && !S.pinned_dst && L.host_cap < L.out_cap) {   // (first use: 32 MB of pinned memory a lane for a C4 item)
 		if(L.host_out) (void)hipHostFree(L.host_out);
 		L.host_out = nullptr; L.host_cap = 0;
 		if(hipHostMalloc(&L.host_out, L.out_cap, hipHostMallocDefault) != hipSuccess) return ctx_fail(CRTHIP_E_NOMEM, nullptr);
@@ -266,32 +266,32 @@ static int lane_plan(crthip_pool *p, Lane &L, Slot &S, const crthip_pool_item &i
 	return crthip_batch_bind_all(S.batch, S.binds.data(), S.index_ptr.data(), S.index_fmt.data());
 }
 
-extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_pool_item *items, uint64_t steps, uint64_t warmup,
-                               crthip_pool_report *report, double *completion_s) {
-	if(!p || !items || nitems == 0 || !report) return ctx_fail(CRTHIP_E_ARGUMENT, nullptr);
-	memset(report, 0, sizeof(*report));
-	// triangles / vertices of every item (header parse only)
-	std::vector<uint64_t> item_tris(nitems, 0), item_verts(nitems, 0);
-	for(uint32_t j = 0; j < nitems; j++)
-		for(uint32_t i = 0; i < items[j].nblobs; i++) {
-			crthip_blob_info info;
-			const int err = crthip_probe(items[j].blobs[i], items[j].lens[i], &info);
-			if(err) return err;
-			item_tris[j] += info.nface; item_verts[j] += info.nvert;
-		}
-	const uint64_t timed_end = warmup + steps;
+// One call's work.  crthip_pool_run (dests null): warmup + steps + a tail of tickets, items drawn cyclically, every lane's block poisoned
+// in front of its last steps.  crthip_pool_decode (dests set): every item once, into its destination.  The workers, their pinning, the
+// lane they refill next and the pipelining of a lane are the same code for both.
+struct PoolJob {
+	uint32_t nitems = 0;
+	const crthip_pool_item *items = nullptr;
+	std::vector<ItemPlan> plans;
+	// crthip_pool_run
+	uint64_t steps = 0, warmup = 0;
+	double *completion_s = nullptr;
+	// crthip_pool_decode
+	const crthip_pool_dest *dests = nullptr;
+	int32_t *status = nullptr;
+	crthip_pool_done_fn done = nullptr; void *user = nullptr;
+};
+
+static int pool_work(crthip_pool *p, PoolJob &job, crthip_pool_report *report) {
+	const uint32_t nitems = job.nitems;
+	const crthip_pool_item *items = job.items;
+	const bool dec = job.dests != nullptr;
+	const uint64_t steps = job.steps, warmup = job.warmup;
+	const uint64_t timed_end = dec ? 0 : warmup + steps;
 	// the tail keeps every context busy until the last timed completion (a pipelined lane has two tickets drawn and not completed)
-	const uint64_t total = timed_end + p->lanes.size()*(p->pipelined ? 2u : 1u);
+	const uint64_t total = dec ? nitems : timed_end + p->lanes.size()*(p->pipelined ? 2u : 1u);
 	p->next = 0; p->completed = 0; p->error = CRTHIP_OK; p->error_msg.clear();
 	for(auto &L : p->lanes) { L.busy = false; L.staged = false; L.poisoned = false; L.pipe = false; L.drain = false; for(Slot &S : L.s) { S.item = -1; S.binds.clear(); } }   // (an item id means this call's items[] only; `poisoned` a mesh stage of this run)
-	p->out_need = 0;
-	if(p->pipelined)
-		for(uint32_t j = 0; j < nitems; j++) {
-			size_t need = 0;
-			const int err = item_out_bytes(p, items[j], &need);
-			if(err) return err;
-			p->out_need = std::max(p->out_need, need);
-		}
 	const bool pipe = p->pipelined;
 	std::vector<double> stamps(timed_end + 1, 0.0);           // stamps[c] = time at which the c-th completion happened (1-based)
 	std::atomic<uint64_t> failed{0}, fallbacks{0}, tris{0}, verts{0};
@@ -301,14 +301,32 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 	std::atomic<uint64_t> host_ns{0}, host_steps{0}, wait_ns{0}, finish_ns{0}, plan_ns{0}, plan_max_ns{0}, launch_max_ns{0};
 	auto raise_max = [](std::atomic<uint64_t> &m, uint64_t v) { uint64_t cur = m.load(); while(v > cur && !m.compare_exchange_weak(cur, v)) { } };
 	// home shard first: pool device d owns the items j with j % ndevices == d (its shard is resident there), and a device without a home
-	// item takes from the others' ("stealing" in a cyclic run: it is the work list that is shared, a faster GPU simply draws more tickets)
-	std::vector<std::vector<uint32_t>> home(p->ndevices);
-	for(uint32_t j = 0; j < nitems; j++) home[j % p->ndevices].push_back(j);
-	std::vector<std::atomic<uint64_t>> home_next(p->ndevices);
+	// item takes from the others' ("stealing" in a cyclic run: it is the work list that is shared, a faster GPU simply draws more tickets).
+	// crthip_pool_decode: the home lists hold the host-destination items, `bound` a slot's device-destination items, which nobody else may
+	// draw; every list is drawn once, front to back, and a slot whose own lists are empty takes from the other slots' home lists
+	std::vector<std::vector<uint32_t>> home(p->ndevices), bound(p->ndevices);
+	for(uint32_t j = 0; j < nitems; j++) {
+		if(dec && job.dests[j].device_slot >= 0) bound[(uint32_t)job.dests[j].device_slot].push_back(j);
+		else home[j % p->ndevices].push_back(j);
+	}
+	std::vector<std::atomic<uint64_t>> home_next(p->ndevices), bound_next(p->ndevices);
 	for(auto &x : home_next) x = 0;
+	for(auto &x : bound_next) x = 0;
 	std::atomic<uint64_t> stolen{0};
+	auto take = [](const std::vector<uint32_t> &q, std::atomic<uint64_t> &at, uint32_t &j) {
+		if(at.load() >= q.size()) return false;
+		const uint64_t k = at.fetch_add(1);
+		if(k >= q.size()) return false;
+		j = q[k];
+		return true;
+	};
+	auto draw_once = [&](uint32_t slot, uint32_t &j) {
+		if(take(bound[slot], bound_next[slot], j) || take(home[slot], home_next[slot], j)) return true;
+		for(uint32_t d = 1; d < p->ndevices; d++) { const uint32_t o = (slot + d) % p->ndevices; if(take(home[o], home_next[o], j)) return true; }
+		return false;
+	};
 	// the last round of timed steps and the tail behind them (outputs_to_host: the tail only - poisoning the pinned mirror is 32 MB of memset on the worker thread)
-	const uint64_t poison_from = p->to_host ? timed_end : timed_end > p->lanes.size() ? timed_end - p->lanes.size() : 0;
+	const uint64_t poison_from = dec ? ~0ull : p->to_host ? timed_end : timed_end > p->lanes.size() ? timed_end - p->lanes.size() : 0;
 	const double t_launch = now_s();
 	stamps[0] = t_launch;
 
@@ -320,6 +338,18 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 			(void)pthread_setaffinity_np(pthread_self(), sizeof set, &set);   // (a cpuset that forbids them: stay where we are)
 		}
 		Lane *mine = &p->lanes[((size_t)slot*p->threads_per_device + t)*p->depth];
+		// crthip_pool_decode: item j is final - `code` in every status entry (it could not be planned, or holds no blob), or S's statuses
+		auto settle = [&](uint32_t j, int32_t code, const Slot *S) {
+			const ItemPlan &P = job.plans[j];
+			int32_t *st = job.status + P.status_at;
+			for(uint32_t i = 0; i < items[j].nblobs; i++) st[i] = S ? S->status[i] : code;
+			if(!S) {
+				++p->completed;
+				if(code) { failed += items[j].nblobs; int32_t z = 0; first_error.compare_exchange_strong(z, code); }
+			}
+			per_dev[slot]++;
+			if(job.done) job.done(job.user, j, slot, st);
+		};
 		auto finish = [&](Lane &L) -> int {
 			Slot &S = L.s[L.cur];
 			const int rc = crthip_batch_sync(S.batch, S.status.data());
@@ -331,8 +361,13 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 			failed += bad;
 			crthip_batch_stats st;
 			if(crthip_batch_get_stats(S.batch, &st) == CRTHIP_OK) fallbacks += st.topology_fallbacks;
-			if(c > warmup && c <= timed_end) { per_dev[slot]++; tris += item_tris[(size_t)S.item]; verts += item_verts[(size_t)S.item]; }
+			if(!dec && c > warmup && c <= timed_end) { per_dev[slot]++; tris += job.plans[(size_t)S.item].tris; verts += job.plans[(size_t)S.item].verts; }
 			if(rc == CRTHIP_E_DEVICE || rc == CRTHIP_E_NOMEM) return rc;
+			if(dec) {
+				if(S.pageable_dst) memcpy(S.pageable_dst, L.host_out, S.out_used);   // (the copy into the lane's mirror is what the sync waited for)
+				tris += job.plans[(size_t)S.item].tris; verts += job.plans[(size_t)S.item].verts;
+				settle((uint32_t)S.item, 0, &S);
+			}
 			return CRTHIP_OK;
 		};
 		// the outputs every lane holds after the run were written by a mesh stage that STARTED from a poisoned block: the post-run bit-exact
@@ -345,6 +380,11 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 			if(p->to_host && L.host_out) memset(L.host_out, POISON, L.s[L.cur].out_used);
 			L.poisoned = true;
 			return CRTHIP_OK;
+		};
+		// the D2H copy behind the mesh stage just enqueued: a step of outputs_to_host, an item with a host destination
+		auto copy_out = [&](Lane &L, Slot &S) -> int {
+			if(!S.to_host) return CRTHIP_OK;
+			return corto_hip::ctx_copy_to_host_async(L.ctx, S.pinned_dst ? S.pinned_dst : L.host_out, L.out, S.out_used);
 		};
 		int err = CRTHIP_OK;
 		auto tick = [] { return std::chrono::steady_clock::now(); };
@@ -376,24 +416,45 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 				L.cur ^= 1u; L.staged = false; L.drain = false; L.pipe = false;
 				err = poison(L, L.s[L.cur].step >= poison_from);
 				if(!err) err = crthip_batch_decode_with_next(L.s[L.cur].batch, nullptr);
-				if(!err && p->to_host) err = corto_hip::ctx_copy_to_host_async(L.ctx, L.host_out, L.out, L.s[L.cur].out_used);
+				if(!err) err = copy_out(L, L.s[L.cur]);
 				if(!err) L.busy = true;
 			}
 			// refill.  A pipelined lane plans the ticket on its free batch object and enqueues [mesh stage of the batch planned one refill ago + entropy
 			// stage of this one]; its first ticket of a run only enqueues an entropy stage, and it draws the next one at once.
+			// (crthip_pool_decode: the two objects are then bound to two different items' blocks.  That is safe: an entropy stage writes its
+			// batch's own scratch and nothing else - corto_hip.h, crthip_batch_decode_with_next - so only the mesh stage in flight writes a block.)
 			while(!err && !L.busy) {
-				const uint64_t step = p->next.fetch_add(1);
-				if(step >= total) { tickets = false; break; }
+				uint64_t step;
 				uint32_t j;
-				if(!home[slot].empty()) j = home[slot][home_next[slot].fetch_add(1) % home[slot].size()];
-				else j = (uint32_t)(stolen.fetch_add(1) % nitems);
+				if(!dec) {
+					step = p->next.fetch_add(1);
+					if(step >= total) { tickets = false; break; }
+					if(!home[slot].empty()) j = home[slot][home_next[slot].fetch_add(1) % home[slot].size()];
+					else j = (uint32_t)(stolen.fetch_add(1) % nitems);
+				} else {
+					if(p->next.load() >= total || !draw_once(slot, j)) { tickets = false; break; }
+					step = p->next.fetch_add(1);
+					if(job.plans[j].err || items[j].nblobs == 0) { settle(j, job.plans[j].err, nullptr); continue; }   // nothing to launch
+				}
 				const auto h0 = std::chrono::steady_clock::now();
 				const bool lp = pipe && (L.pipe || L.staged);                          // this refill pipelines
 				const uint32_t t = lp ? (L.staged ? L.cur : L.cur ^ 1u) : L.cur;        // the free batch object
 				Slot &T = L.s[t];
-				err = lane_plan(p, L, T, items[j], (int64_t)j);
+				const ItemPlan &P = job.plans[j];
+				uint8_t *dest = nullptr;
+				T.to_host = p->to_host; T.pinned_dst = nullptr; T.pageable_dst = nullptr;
+				if(dec) {
+					const crthip_pool_dest &D = job.dests[j];
+					T.to_host = D.device_slot < 0;
+					if(!T.to_host) dest = (uint8_t *)D.out;
+					else if(P.pinned) T.pinned_dst = D.out;
+					else T.pageable_dst = D.out;
+				}
+				bool item_fault = false;
+				err = lane_plan(p, L, T, items[j], (int64_t)j, P, dest, dec ? p->out_need : std::max((size_t)P.total + 256, p->out_need), &item_fault);
 				T.step = step;
 				{ const uint64_t ns_ = ns_since(h0); plan_ns += ns_; raise_max(plan_max_ns, ns_); }
+				if(err && dec && item_fault) { settle(j, err, nullptr); err = CRTHIP_OK; continue; }   // the item's own failure: the lane draws the next one
 				if(err) break;
 				const auto d0 = std::chrono::steady_clock::now();
 				if(lp && !L.staged) {
@@ -405,7 +466,7 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 					err = poison(L, L.s[m].step >= poison_from);
 					if(!err) err = lp ? crthip_batch_decode_with_next(L.s[m].batch, T.batch) : crthip_batch_decode(T.batch);
 					if(!err && lp) L.drain = !corto_hip::batch_entropy_done(T.batch);
-					if(!err && p->to_host) err = corto_hip::ctx_copy_to_host_async(L.ctx, L.host_out, L.out, L.s[m].out_used);
+					if(!err) err = copy_out(L, L.s[m]);
 					if(!err) L.busy = true;
 				}
 				raise_max(launch_max_ns, ns_since(d0));
@@ -420,25 +481,27 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 			L.cur ^= 1u; L.staged = false;
 			err = poison(L, L.s[L.cur].step >= poison_from);
 			if(!err) err = crthip_batch_decode_with_next(L.s[L.cur].batch, nullptr);
-			if(!err && p->to_host) err = corto_hip::ctx_copy_to_host_async(L.ctx, L.host_out, L.out, L.s[L.cur].out_used);
+			if(!err) err = copy_out(L, L.s[L.cur]);
 			if(!err) L.busy = true;
 		}
 		for(uint32_t k = 0; k < p->depth; k++) if(mine[k].busy) { const int e2 = finish(mine[k]); if(!err) err = e2; }
 		// a context whose thread drew none of the last 2 x lanes tickets (descheduled while the others emptied the queue: seen with
 		// 32-blob items) repeats its last step from a poisoned block, behind the timed region: what lane_read returns is then ALWAYS
 		// a poisoned step's output, not only almost always
-		for(uint32_t k = 0; k < p->depth && !err; k++) {
+		for(uint32_t k = 0; k < p->depth && !err && !dec; k++) {
 			Lane &L = mine[k];
 			Slot &S = L.s[L.cur];
 			if(S.item < 0) {                                     // ... and one that drew no ticket at all (a 28-step run on a cold box) decodes its device's first item
 				const uint32_t j = home[slot].empty() ? 0u : home[slot][0];
-				err = lane_plan(p, L, S, items[j], (int64_t)j);
+				bool item_fault = false;
+				S.to_host = p->to_host; S.pinned_dst = nullptr; S.pageable_dst = nullptr;
+				err = lane_plan(p, L, S, items[j], (int64_t)j, job.plans[j], nullptr, std::max((size_t)job.plans[j].total + 256, p->out_need), &item_fault);
 				if(err) break;
 			}
 			if(L.poisoned || !L.out) continue;
 			err = poison(L, true);
 			if(!err) err = crthip_batch_decode(S.batch);
-			if(!err && p->to_host) err = corto_hip::ctx_copy_to_host_async(L.ctx, L.host_out, L.out, S.out_used);
+			if(!err) err = copy_out(L, S);
 			if(!err) { L.busy = true; err = finish(L); }
 		}
 		if(err) {
@@ -451,12 +514,15 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 	for(uint32_t d = 0; d < p->ndevices; d++)
 		for(uint32_t t = 0; t < p->threads_per_device; t++) threads.emplace_back(worker, d, t);
 	for(auto &th : threads) th.join();
+	const double t_joined = now_s();
+	if(dec) for(auto &L : p->lanes) for(Slot &S : L.s) { S.item = -1; S.binds.clear(); }   // (the destinations are the caller's again)
 	if(p->error) return ctx_fail(p->error, p->error_msg.c_str());
-	report->elapsed_s = stamps[timed_end] - stamps[warmup];
-	report->steps = steps; report->triangles = tris; report->vertices = verts;
+	if(!report) return CRTHIP_OK;
+	report->elapsed_s = dec ? t_joined - t_launch : stamps[timed_end] - stamps[warmup];
+	report->steps = dec ? nitems : steps; report->triangles = tris; report->vertices = verts;
 	report->failed_blobs = failed; report->first_error = first_error; report->topology_fallbacks = fallbacks;
 	for(uint32_t d = 0; d < p->ndevices; d++) { report->steps_per_device[d] = per_dev[d]; if(per_dev[d]) report->devices_used++; }
-	for(auto &L : p->lanes) if(L.s[L.cur].item >= 0 && L.poisoned) report->poisoned_lanes++;
+	if(!dec) for(auto &L : p->lanes) if(L.s[L.cur].item >= 0 && L.poisoned) report->poisoned_lanes++;
 	report->host_us_per_step = host_steps ? (float)((double)host_ns/1e3/(double)host_steps) : 0.f;
 	if(host_steps) {
 		report->host_wait_us = (float)((double)wait_ns/1e3/(double)host_steps); report->host_finish_us = (float)((double)finish_ns/1e3/(double)host_steps);
@@ -464,18 +530,97 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 		report->host_plan_max_us = (float)((double)plan_max_ns/1e3); report->host_launch_max_us = (float)((double)launch_max_ns/1e3);
 	}
 	for(uint32_t d = 0; d < p->ndevices; d++) if(!p->cpus[d].empty()) report->pinned_devices++;
-	if(completion_s) for(uint64_t c = 0; c < steps; c++) completion_s[c] = stamps[warmup + 1 + c] - stamps[warmup];
+	if(job.completion_s) for(uint64_t c = 0; c < steps; c++) job.completion_s[c] = stamps[warmup + 1 + c] - stamps[warmup];
 	return CRTHIP_OK;
+}
+
+extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_pool_item *items, uint64_t steps, uint64_t warmup,
+                               crthip_pool_report *report, double *completion_s) {
+	if(!p || !items || nitems == 0 || !report) return ctx_fail(CRTHIP_E_ARGUMENT, nullptr);
+	memset(report, 0, sizeof(*report));
+	PoolJob job;
+	job.nitems = nitems; job.items = items; job.steps = steps; job.warmup = warmup; job.completion_s = completion_s;
+	// triangles / vertices and the output layout of every item (header parse only)
+	job.plans.resize(nitems);
+	p->out_need = 0;
+	for(uint32_t j = 0; j < nitems; j++) {
+		const int err = item_plan(p, items[j], job.plans[j]);
+		if(err) return err;
+		// (crthip_pool_run's own 256 bytes behind the block: what "#tail" reads)
+		if(p->pipelined) p->out_need = std::max(p->out_need, (size_t)job.plans[j].total + 256);
+	}
+	p->decoded = false;
+	return pool_work(p, job, report);
+}
+
+// a device destination: device memory of `device`, [q, q + bytes) inside one allocation (the resident encoder's check, encode_batch.cpp)
+static bool device_block_ok(const void *q, uint64_t bytes, int device) {
+	hipPointerAttribute_t a;
+	memset(&a, 0, sizeof(a));
+	if(hipPointerGetAttributes(&a, q) != hipSuccess) { (void)hipGetLastError(); return false; }   // (memory the runtime has never seen)
+	if(a.type != hipMemoryTypeDevice || a.device != device) return false;                          // pinned and managed memory included
+	hipDeviceptr_t base = nullptr;
+	size_t size = 0;
+	if(hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)q) != hipSuccess) { (void)hipGetLastError(); return false; }
+	const uintptr_t b = (uintptr_t)base, x = (uintptr_t)q;
+	return x >= b && bytes <= size && x - b <= size - bytes;
+}
+
+extern "C" int crthip_pool_decode(crthip_pool *p, uint32_t nitems, const crthip_pool_item *items, const crthip_pool_dest *dests,
+                                  int32_t *status, crthip_pool_done_fn done, void *user, crthip_pool_report *report) {
+	if(!p || (nitems && (!items || !dests))) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_pool_decode: null argument");
+	if(report) memset(report, 0, sizeof(*report));
+	PoolJob job;
+	job.nitems = nitems; job.items = items; job.dests = dests; job.done = done; job.user = user;
+	job.plans.resize(nitems);
+	size_t nstatus = 0;
+	p->out_need = 0;
+	auto bad = [](uint32_t j, const char *what) {
+		const std::string msg = "crthip_pool_decode: item " + std::to_string(j) + ": " + what;
+		return ctx_fail(CRTHIP_E_ARGUMENT, msg.c_str());
+	};
+	// every destination before the first launch: a refused call has written nothing
+	for(uint32_t j = 0; j < nitems; j++) {
+		ItemPlan &P = job.plans[j];
+		const crthip_pool_dest &D = dests[j];
+		if(items[j].nblobs && (!items[j].blobs || !items[j].lens)) return bad(j, "null blob list");
+		P.status_at = nstatus; nstatus += items[j].nblobs;
+		if(D.reserved) return bad(j, "reserved must be 0");
+		if(D.device_slot != CRTHIP_POOL_DEST_HOST && (D.device_slot < 0 || (uint32_t)D.device_slot >= p->ndevices)) return bad(j, "device_slot names no pool device");
+		if((uintptr_t)D.out & 255) return bad(j, "out is not 256-byte aligned");
+		if(item_plan(p, items[j], P)) continue;                  // the item's own failure: reported in its statuses, its destination is not written
+		if(P.total && !D.out) return bad(j, "null out");
+		if(D.cap < P.total) return bad(j, "cap is smaller than the layout's total");
+		if(!P.total) continue;
+		if(D.device_slot >= 0) {
+			if(!device_block_ok(D.out, P.total, p->devices[(uint32_t)D.device_slot]))
+				return bad(j, "out is not device memory of the slot's GPU, or [out, out + total) leaves its allocation");
+		} else {
+			hipPointerAttribute_t a;
+			memset(&a, 0, sizeof(a));
+			if(hipPointerGetAttributes(&a, D.out) != hipSuccess) { (void)hipGetLastError(); a.type = hipMemoryTypeUnregistered; }   // (plain host memory)
+			if(a.type == hipMemoryTypeDevice) return bad(j, "a host destination that is device memory");
+			P.pinned = a.type == hipMemoryTypeHost;
+			p->out_need = std::max(p->out_need, (size_t)P.total);   // the lanes' blocks: sized once for the largest host item
+		}
+	}
+	std::vector<int32_t> own_status;
+	if(!status) { own_status.assign(std::max<size_t>(nstatus, 1), 0); status = own_status.data(); }
+	job.status = status;
+	p->decoded = true;
+	if(nitems == 0) return CRTHIP_OK;
+	return pool_work(p, job, report);
 }
 
 extern "C" int64_t crthip_pool_lane_item(const crthip_pool *p, uint32_t lane, uint32_t *device_slot) {
 	if(!p || lane >= p->lanes.size()) return ctx_fail(CRTHIP_E_ARGUMENT, nullptr);
 	if(device_slot) *device_slot = p->lanes[lane].slot;
+	if(p->decoded) return -1;                                    // (crthip_pool_decode delivered every item: a lane holds nothing)
 	return p->lanes[lane].s[p->lanes[lane].cur].item;           // (a pipelined lane: the batch whose mesh stage ran last)
 }
 
 extern "C" int64_t crthip_pool_lane_read(crthip_pool *p, uint32_t lane, uint32_t blob, const char *what, void *host_out, size_t cap) {
-	if(!p || lane >= p->lanes.size() || !what || !host_out) return ctx_fail(CRTHIP_E_ARGUMENT, nullptr);
+	if(!p || lane >= p->lanes.size() || !what || !host_out || p->decoded) return ctx_fail(CRTHIP_E_ARGUMENT, nullptr);
 	Lane &L = p->lanes[lane];
 	Slot &S = L.s[L.cur];                                        // (a pipelined lane: the batch whose mesh stage ran last)
 	if(!S.batch || S.item < 0 || blob >= crthip_batch_size(S.batch)) return ctx_fail(CRTHIP_E_ARGUMENT, nullptr);

@@ -42,7 +42,8 @@ extern "C" {
                                      crthip_encode_batch_attrs, crthip_batch_create_resident, crthip_batch_reset_resident, crthip_batch_exif,
                                      crthip_batch_groups, crthip_batch_group_props, crthip_batch_walk_stats, crthip_batch_decode_with_next,
                                      crthip_batch_set_parity, crthip_encode_batch_resident, crthip_encode_input_model,
-                                     crthip_encode_batch_to_device, crthip_encode_batch_bound, crthip_ctx_encode_splice_stats */
+                                     crthip_encode_batch_to_device, crthip_encode_batch_bound, crthip_ctx_encode_splice_stats,
+                                     crthip_output_layout, crthip_pool_decode (crthip_pool_dest, crthip_pool_done_fn) */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -247,6 +248,22 @@ int crthip_batch_done(crthip_batch *b);
 int crthip_decode_host(crthip_ctx *ctx, const uint8_t *blob, size_t len, const crthip_attr_binding *attrs,
                        void *index, uint32_t index_format);
 
+/* Where the decoded arrays of a list of blobs lie in ONE output block: the layout crthip_pool_decode writes, and the one the pool's own lanes
+ * use.  Host-only, needs no device: it reads the headers (crthip_probe) and returns the first failing blob's code, "(blob i)" in
+ * crthip_last_error().  The rule:
+ *   - every array starts on the next 256-byte multiple, blob after blob, a blob's attributes in info.attr order and its index behind them;
+ *   - generic attributes (position, uv, radius, ...) are FLOAT, nvert*N*4 bytes; normals FLOAT, nvert*12 bytes - INT16, nvert*6 bytes,
+ *     under CRTHIP_LAYOUT_RENDER; colour is UINT8 x 4, nvert*4 bytes;
+ *   - the index is UINT32, nface*12 bytes - UINT16, nface*6 bytes, under CRTHIP_LAYOUT_RENDER where nvert < 65536; a cloud has none;
+ *   - *total is the end of the last array rounded up to 256 (0 for no blobs).
+ * attr: NULL, or sum(nattr) entries, blob after blob; index: NULL, or nblobs entries (bytes == 0 for a cloud).  out_components is what a
+ * vertex holds in the array (N, 3 for a normal, 4 for colour; 3 for the index).  Any flag bit but CRTHIP_LAYOUT_RENDER: CRTHIP_E_ARGUMENT.
+ * (No reference counterpart: upstream's callers size one buffer per attribute from nvert / nface, src/main.cpp:266-300.) */
+#define CRTHIP_LAYOUT_RENDER 1u   /* crthip_pool_set_render_layouts' formats */
+typedef struct { uint64_t offset, bytes; uint32_t format, out_components; } crthip_out_array;
+int crthip_output_layout(uint32_t nblobs, const uint8_t *const *blobs, const uint32_t *lens, uint32_t flags,
+                         crthip_out_array *attr, crthip_out_array *index, uint64_t *total);
+
 /* ---- multi-GPU decode pool ------------------------------------------------------------------------
  * Upstream decodes one blob on one thread; its Decoder objects are independent (src/decoder.cpp:126-196 touches nothing
  * shared), so a list of blobs shards by blob with NO collective.  The pool is that, for the GPUs of one node: `ndevices`
@@ -283,7 +300,7 @@ int crthip_pool_set_outputs_to_host(crthip_pool *pool, int on);
  * output bytes for a C4 blob, which is what the secondary region's D2H copy moves.  crthip_pool_lane_read returns those bytes. */
 int crthip_pool_set_render_layouts(crthip_pool *pool, int on);
 
-/* One work item = one batch of blobs (HOST pointers, borrowed for the duration of crthip_pool_run).
+/* One work item = one batch of blobs (HOST pointers, borrowed for the duration of crthip_pool_run / crthip_pool_decode).
  * device_arena: NULL -> every execution uploads the blobs (pageable or pinned host memory -> HBM) inside the step (SURVEY.md 8d's primary
  *                       region): one DMA copy at the head of the context's own stream, as crthip_batch_create does;
  *               else ndevices DEVICE pointers, entry d = the item's blobs already resident on pool device d in
@@ -316,7 +333,49 @@ typedef struct {
 	float host_launch_max_us;    /* ... and the longest single crthip_batch_decode call: a host thread that blocks inside the runtime shows here */
 } crthip_pool_report;
 
-/* Decode warmup + steps batches drawn cyclically from the items (each device from its home items, see above; + a few more steps to
+/* Decode every item exactly ONCE into memory the caller owns: the pool as a service.  No warm-up, no tail, no poisoning; the call blocks
+ * until every item's outputs are complete and visible in dests[j].out (a host destination: the copy included) and the per-blob codes are
+ * in `status`.  An item's block is laid out as crthip_output_layout says for its blobs, under CRTHIP_LAYOUT_RENDER when
+ * crthip_pool_set_render_layouts is on (crthip_pool_set_outputs_to_host has no bearing: the destination decides).
+ *   device destination (device_slot >= 0): `out` is device memory of pool device device_slot's GPU and only lanes of that slot draw the
+ *     item.  The kernels write straight into it and nothing outside the arrays' extents: the gaps between arrays and [total, cap) keep
+ *     the caller's bytes.  The caller's own work on the block has completed before the call ("Device buffers" above).
+ *   host destination (CRTHIP_POOL_DEST_HOST): the item is drawn home-first (pool device j % ndevices), then by whichever device is free;
+ *     it decodes into the lane's device block and ONE device-to-host copy of [0, total) follows the kernels on the context's stream -
+ *     straight into `out` where that is pinned memory (hipPointerGetAttributes decides), else into the lane's pinned mirror and from there
+ *     with a memcpy on the worker thread.  Bytes of [0, total) outside the arrays are unspecified; [total, cap) is untouched.
+ *   items[j].device_arena[slot] is used as in crthip_pool_run when the decoding slot has one.
+ * Scheduling is crthip_pool_run's: the same worker threads and pinning, lanes pipelined two batches a call where they are there
+ * ($CORTO_CARRY=0 honoured); a worker takes its slot's device-destination items first, then its home host items, then the other slots'.
+ * Before the first launch every destination is checked - CRTHIP_E_ARGUMENT for the call, the item named in crthip_last_error(), nothing
+ * written: a NULL `out` with total > 0, `out` not 256-byte aligned, cap < total, a device_slot that is neither a pool device nor
+ * CRTHIP_POOL_DEST_HOST, reserved != 0, a device destination that is not device memory of that slot's GPU or whose [out, out + total)
+ * leaves its allocation (the runtime's pointer queries), a host destination that is device memory.  Overlapping destinations are the
+ * caller's business.
+ * Failures of one item do not stop the call: an item whose layout or planning fails (a blob the host walk refuses: magic, truncation,
+ * alignment) gets that code in every one of its status entries and its destination is not written; a blob that fails on the device gets
+ * its own code.  The call returns CRTHIP_OK in both cases; only CRTHIP_E_DEVICE, CRTHIP_E_NOMEM and the checks above fail it.
+ *   status: NULL, or sum(nblobs) codes, item after item.
+ *   done:   NULL, or called on a worker thread once per item - one that failed to plan included - after the item's outputs and statuses
+ *           are final, with the slot that handled it and the item's nblobs codes.  Calls from different threads may overlap; it must
+ *           not call into the pool.
+ *   report: NULL, or the struct of crthip_pool_run: steps = nitems, elapsed_s the wall time from the first plan to the last completion,
+ *           triangles / vertices of the items decoded, poisoned_lanes 0, the other fields as there.
+ * Afterwards crthip_pool_lane_item returns -1 and crthip_pool_lane_read CRTHIP_E_ARGUMENT until the next crthip_pool_run; the two calls
+ * may alternate freely on one pool. */
+#define CRTHIP_POOL_DEST_HOST (-1)
+typedef struct {
+	void *out;                   /* the item's output block, laid out as crthip_output_layout says */
+	uint64_t cap;                /* >= that layout's total */
+	int32_t device_slot;         /* >= 0: `out` is device memory of pool device `device_slot`, and a lane of that slot decodes the item;
+	                                CRTHIP_POOL_DEST_HOST: `out` is host memory (pinned or not), any device may decode the item */
+	uint32_t reserved;           /* 0 */
+} crthip_pool_dest;
+typedef void (*crthip_pool_done_fn)(void *user, uint32_t item, uint32_t device_slot, const int32_t *status /* the item's nblobs codes */);
+int crthip_pool_decode(crthip_pool *pool, uint32_t nitems, const crthip_pool_item *items, const crthip_pool_dest *dests,
+                       int32_t *status, crthip_pool_done_fn done, void *user, crthip_pool_report *report);
+
+/* The measuring loop (bench.py): decode warmup + steps batches drawn cyclically from the items (each device from its home items, see above; + a few more steps to
  * keep every context busy until the last timed completion), outputs into the contexts' own device blocks: every attribute bound in its natural format
  * (generic FLOAT, normal FLOAT, colour UINT8 x 4, index UINT32).  completion_s: NULL, or `steps` doubles that receive the
  * completion time of every timed step in seconds since the start of the timed region, in completion order.
