@@ -102,6 +102,45 @@ class AttrList(C.Structure):
     _fields_ = [("nattr", C.c_uint32), ("attr", C.c_void_p)]
 
 
+class MeshLayout(C.Structure):
+    """crthip_mesh_layout: how a mesh's data arrays are read - index16 / normal16 (upstream's addPositions(uint16_t *) / addNormals(int16_t *)
+    inputs), byte strides (0 = packed), attr_stride (one per entry of `attributes`), origin (upstream's `o`: input - o in float).  All
+    defaults: exactly what the packed float / uint32 arrays mean."""
+    _fields_ = [("flags", C.c_uint32), ("position_stride", C.c_uint32), ("normal_stride", C.c_uint32), ("color_stride", C.c_uint32),
+                ("uv_stride", C.c_uint32), ("radius_stride", C.c_uint32), ("attr_stride", C.c_void_p), ("origin", C.c_float * 3)]
+
+    def __init__(self, index16=False, normal16=False, position_stride=0, normal_stride=0, color_stride=0, uv_stride=0, radius_stride=0,
+                 attr_stride=None, origin=(0.0, 0.0, 0.0), flags=None):
+        super().__init__()
+        self.flags = (IN_INDEX_UINT16 if index16 else 0) | (IN_NORMAL_INT16 if normal16 else 0) if flags is None else flags
+        self.position_stride, self.normal_stride, self.color_stride = position_stride, normal_stride, color_stride
+        self.uv_stride, self.radius_stride = uv_stride, radius_stride
+        if attr_stride is not None:
+            self._attr = np.ascontiguousarray(attr_stride, dtype=np.uint32)
+            self.attr_stride = self._attr.ctypes.data
+        for k in range(3):
+            self.origin[k] = origin[k]
+
+    @classmethod
+    def of(cls, mesh, attributes=None, origin=(0.0, 0.0, 0.0)):
+        """The layout of a mesh whose arrays are numpy or torch VIEWS, read off the arrays themselves: the byte stride of the first axis,
+        a uint16 / int16 dtype of index / normal."""
+        def stride(a):
+            if a is None:
+                return 0
+            return int(a.strides[0]) if isinstance(a, np.ndarray) else int(a.stride(0)) * a.element_size()
+        name = lambda a: "" if a is None else str(a.dtype).replace("torch.", "")
+        # (torch has no arithmetic on uint16: a device index of 16-bit entries travels as int16, as a uint32 one does as int32)
+        index16 = name(mesh.index) == "uint16" or (name(mesh.index) == "int16" and not isinstance(mesh.index, np.ndarray))
+        return cls(index16=index16, normal16=name(mesh.normal) == "int16", position_stride=stride(mesh.position), normal_stride=stride(mesh.normal),
+                   color_stride=stride(mesh.color), uv_stride=stride(mesh.uv), radius_stride=stride(mesh.radius),
+                   attr_stride=None if attributes is None else [stride(a[1]) for a in attributes], origin=origin)
+
+
+IN_INDEX_UINT16, IN_NORMAL_INT16 = 1, 2
+ENCODE_INPUTS_RESIDENT, ENCODE_OUTPUT_DEVICE = 1, 2
+
+
 class PoolItem(C.Structure):
     _fields_ = [("nblobs", C.c_uint32), ("blobs", C.c_void_p), ("lens", C.c_void_p), ("device_arena", C.c_void_p)]
 
@@ -222,6 +261,13 @@ def lib():
         L.crthip_splice_copy_model.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.crthip_encode_splice_plan_model.restype = C.c_int64
         L.crthip_encode_splice_plan_model.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SpliceStats), C.c_void_p, C.c_size_t, C.c_uint32]
+        L.crthip_encode_layout.restype = C.c_int64
+        L.crthip_encode_layout.argtypes = [C.POINTER(MeshDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.crthip_encode_batch_layout.restype = C.c_int64
+        L.crthip_encode_batch_layout.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.crthip_encode_input_model_layout.argtypes = [C.POINTER(MeshDesc), C.c_void_p, C.c_int, C.c_void_p]
+        L.crthip_encode_topology_model_layout.argtypes = [C.POINTER(MeshDesc), C.c_void_p, C.c_int, C.c_void_p]
         L.crthip_encode_batch_attrs.restype = C.c_int64
         L.crthip_encode_batch_attrs.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -348,16 +394,17 @@ def _host_ptr(a):
     return a.ctypes.data
 
 
-def _attr_list(attributes, nvert, ptr=None):
+def _attr_list(attributes, nvert, ptr=None, as_views=False):
     """crthip_attr_list of [(name, array (nvert, N), q, strategy), ...] (None: no list), and the objects it points into.
-    ptr: the address of an array; None: numpy arrays in host memory, else the arrays are taken as they are (device tensors)."""
+    ptr: the address of an array; None: numpy arrays in host memory, else the arrays are taken as they are (device tensors).
+    as_views: strided arrays are taken where they lie (a crthip_mesh_layout says how they are read)."""
     if attributes is None:
         return None, []
     attributes = list(attributes)
     arr = (GenericAttrDesc * max(len(attributes), 1))()
     keep = [arr]
     for k, (name, values, q, strategy) in enumerate(attributes):
-        v = np.ascontiguousarray(values) if ptr is None else values
+        v = (values if as_views else np.ascontiguousarray(values)) if ptr is None else values
         if v.ndim == 1:
             v = v.reshape(-1, 1)
         if v.ndim != 2 or v.shape[0] != nvert:
@@ -369,7 +416,7 @@ def _attr_list(attributes, nvert, ptr=None):
             d.name = nm; d.values = v.ctypes.data if v.size else None
             d.format = _ATTR_FMT.get(v.dtype, 0xFFFFFFFF)
         else:
-            if not v.is_contiguous():
+            if not as_views and not v.is_contiguous():
                 raise ValueError("attribute %r: the device array must be contiguous" % (name,))
             d.name = nm; d.values = ptr(v) if v.numel() else None
             d.format = _ATTR_FMT.get(np.dtype(str(v.dtype).replace("torch.", "")), 0xFFFFFFFF)
@@ -476,10 +523,11 @@ def encode_topology_fits_lds(mesh) -> bool:
     return bool(lib().crthip_encode_topology_fits_lds(C.byref(m)))
 
 
-def encode_topology_model(mesh, which, **kw):
+def encode_topology_model(mesh, which, layout=None, **kw):
     """The CLERS topology pass of one mesh on the host (crthip_encode_topology_model): which = 0 the host encoder's pass, which = 1 the
     source the device kernels run, compiled for the host.  kw: encode()'s keywords.  Returns a dict: faces (nface, 3), group_end, quads
-    (nvert, 4), clers, split_words, and the counts nvert, nface, max_front, split_bits, lds."""
+    (nvert, 4), clers, split_words, and the counts nvert, nface, max_front, split_bits, lds.  layout: a MeshLayout the mesh's arrays are read
+    through (crthip_encode_topology_model_layout: the index's width is what matters to the pass)."""
     m, keep = _mesh_desc(mesh, **kw)
     nface, nvert = int(mesh.nface), int(mesh.nvert)
     faces = np.zeros(max(nface, 1) * 3, dtype=np.uint32)
@@ -489,7 +537,7 @@ def encode_topology_model(mesh, which, **kw):
     words = np.zeros(4 * nface + 4, dtype=np.uint32)              # CRTHIP_TOPOLOGY_SPLIT_CAP
     r = TopologyResult()
     r.faces, r.group_end, r.quads, r.clers, r.split_words = (a.ctypes.data for a in (faces, gend, quads, clers, words))
-    _check(lib().crthip_encode_topology_model(C.byref(m), int(which), C.byref(r)))
+    _check(lib().crthip_encode_topology_model_layout(C.byref(m), C.byref(layout) if layout is not None else None, int(which), C.byref(r)))
     return dict(faces=faces[:r.nface * 3].reshape(-1, 3).copy(), group_end=gend[:r.ngroups].copy(), quads=quads[:r.nvert * 4].reshape(-1, 4).copy(),
                 clers=clers[:r.nclers].copy(), split_words=words[:r.nsplit_words].copy(), nvert=int(r.nvert), nface=int(r.nface),
                 max_front=int(r.max_front), split_bits=int(r.split_bits), lds=int(r.lds))
@@ -501,13 +549,14 @@ class EncodeInputResult(C.Structure):
                 ("sum", C.c_double), ("step", C.c_float), ("reserved", C.c_uint32)]
 
 
-def encode_input_model(mesh, which, **kw):
+def encode_input_model(mesh, which, layout=None, **kw):
     """What the encoder reads from a mesh's arrays before it quantises (crthip_encode_input_model): which = 0 the host encoder's own
     loops, which = 1 the source the kernels of encode_batch_resident run, on the host in the kernels' partition.  kw: encode()'s
-    keywords.  Returns a dict: index_out_of_range, recipe, mn and mx (float32 arrays of 3), sum (np.float64) and step (np.float32)."""
+    keywords.  Returns a dict: index_out_of_range, recipe, mn and mx (float32 arrays of 3), sum (np.float64) and step (np.float32).
+    layout: a MeshLayout the mesh's arrays (numpy views, taken where they lie) are read through (crthip_encode_input_model_layout)."""
     m, keep = _mesh_desc(mesh, **kw)
     r = EncodeInputResult()
-    _check(lib().crthip_encode_input_model(C.byref(m), int(which), C.byref(r)))
+    _check(lib().crthip_encode_input_model_layout(C.byref(m), C.byref(layout) if layout is not None else None, int(which), C.byref(r)))
     return dict(index_out_of_range=int(r.index_out_of_range), recipe=int(r.recipe), mn=np.array(r.mn, dtype=np.float32),
                 mx=np.array(r.mx, dtype=np.float32), sum=np.float64(r.sum), step=np.float32(r.step))
 
@@ -674,6 +723,117 @@ def encode_batch_to_device(meshes, ctx, kw=None, host_threads=0, resident=None, 
         d = st.as_dict()
         d["kernel_times"] = t.as_dict()
         d["splice"] = ctx.encode_splice_stats()
+        d["total"] = int(r)
+        res.append(d)
+    return tuple(res)
+
+
+class MeshView(DeviceMesh):
+    """A mesh whose data arrays are VIEWS taken where they lie - numpy views of one record array, torch views into an interleaved vertex
+    buffer - for encode_layout / encode_batch_layout with a MeshLayout (MeshLayout.of reads it off the views)."""
+
+
+def _view_ptr(t):
+    """the address of a view's first element (numpy or torch; an empty one has none and is never read)"""
+    if isinstance(t, np.ndarray):
+        return t.ctypes.data if t.size else t.ctypes.data or 16
+    return t.data_ptr() if t.numel() else 16
+
+
+def encode_layout(mesh, layout=None, attributes=None, **kw) -> np.ndarray:
+    """crthip_encode_layout: encode() of a mesh whose HOST arrays (numpy views, a MeshView) are read through `layout` (None: MeshLayout.of
+    (mesh, attributes)) - byte-identical to encode() of the same data converted into packed float / uint32 arrays."""
+    if layout is None:
+        layout = MeshLayout.of(mesh, attributes)
+    m, keep = _mesh_desc(mesh, ptr=_view_ptr, **kw)
+    lst, keep_attrs = _attr_list(attributes, mesh.nvert, as_views=True)
+    extra = C.byref(lst) if lst is not None else None
+    cap = 64 * (mesh.nvert + mesh.nface) + 65536 + (sum(8 * int(np.prod(a[1].shape)) for a in attributes) if attributes is not None else 0)
+    for _ in range(2):
+        out = np.zeros(cap + 16, dtype=np.uint8)
+        off = (-out.ctypes.data) % 16
+        n = lib().crthip_encode_layout(C.byref(m), extra, C.byref(layout), out[off:].ctypes.data_as(C.c_void_p), cap, None, None)
+        if n < 0:
+            _check(int(n))
+        if n <= cap:
+            return out[off:off + int(n)]
+        cap = int(n)
+    raise CortoError(-9, "encode_layout: size changed between calls")
+
+
+def encode_batch_layout(meshes, ctx, layouts=None, kw=None, resident=None, device_out=False, out=None, host_threads=0, raise_on_error=True,
+                        with_stats=False, cap=None):
+    """crthip_encode_batch_layout: the batch encoder on arrays read where they lie through one MeshLayout per mesh (None: MeshLayout.of each
+    mesh).  resident: the arrays are device tensors (default: torch views), else numpy views.  Returns (out, offsets, lens): blob i is the
+    lens[i] bytes at offsets[i] of `out`, the offsets arena_layout(lens) and the padding zeros - a device uint8 tensor with device_out=True
+    (Batch.resident(ctx, out, offsets, lens) takes the three as they are), else a 16-byte aligned numpy array.  out: a buffer to write into
+    (None: one of encode_batch_bound bytes); cap: bytes of it that may be written.  raise_on_error / with_stats as encode_batch_to_device."""
+    meshes = list(meshes)
+    n = len(meshes)
+    if resident is None:
+        resident = any(not isinstance(m.position, np.ndarray) for m in meshes)
+    kws = [{}] * n if kw is None else [kw] * n if isinstance(kw, dict) else list(kw)
+    if layouts is None:
+        layouts = [MeshLayout.of(m, k.get("attributes")) for m, k in zip(meshes, kws)]
+    if len(layouts) != n or len(kws) != n:
+        raise ValueError("encode_batch_layout: %d layouts and %d keyword dicts for %d meshes" % (len(layouts), len(kws), n))
+    descs = (MeshDesc * max(n, 1))()
+    lists = (AttrList * max(n, 1))()
+    lays = (MeshLayout * max(n, 1))()
+    keep, with_attrs = [list(layouts)], False
+    for i, (mesh, k) in enumerate(zip(meshes, kws)):
+        k = dict(k)
+        attributes = k.pop("attributes", None)
+        descs[i], kp = _mesh_desc(mesh, ptr=_view_ptr, **k)
+        keep.append(kp)
+        if attributes is not None:
+            lst, ka = _attr_list(attributes, mesh.nvert, _view_ptr if resident else None, as_views=True)
+            lists[i] = lst; keep.append(ka); with_attrs = True
+        C.memmove(C.byref(lays[i]), C.byref(layouts[i]), C.sizeof(MeshLayout))
+    extra = lists if with_attrs else None
+    if out is None:
+        bound = max(int(lib().crthip_encode_batch_bound(n, descs, extra)), 16)
+        if device_out:
+            import torch
+            out = torch.empty(bound, dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+        else:
+            out = aligned_blob(np.zeros(bound, dtype=np.uint8))
+    if device_out:
+        import torch
+        if out.dtype != torch.uint8 or not out.is_contiguous():
+            raise ValueError("encode_batch_layout: out must be a contiguous uint8 device tensor")
+        dst, size = out.data_ptr(), out.numel()
+    else:
+        if out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise ValueError("encode_batch_layout: out must be a contiguous uint8 numpy array")
+        dst, size = out.ctypes.data, out.size
+    cap = size if cap is None else int(cap)
+    if resident or device_out:
+        _torch_ready(ctx.device)
+    offs = np.zeros(max(n, 1), dtype=np.uint64)
+    lens = np.zeros(max(n, 1), dtype=np.uint32)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    st = EncodeBatchStats()
+    t = KernelTimes()
+    flags = (ENCODE_INPUTS_RESIDENT if resident else 0) | (ENCODE_OUTPUT_DEVICE if device_out else 0)
+    r = lib().crthip_encode_batch_layout(ctx.handle, n, descs, extra, lays, host_threads, flags, dst, cap, _np_ptr(offs), _np_ptr(lens), None, None,
+                                         _np_ptr(status), C.byref(st), C.byref(t))
+    if r < 0:
+        _check(int(r))
+    if r > cap:
+        raise CortoError(-9, "encode_batch_layout: the arena needs %d bytes, out holds %d (nothing was written)" % (r, cap))
+    offs, lens, status = offs[:n], lens[:n], status[:n]
+    if raise_on_error and (status != 0).any():
+        i = int(np.nonzero(status)[0][0])
+        raise CortoError(int(status[i]), "encode_batch_layout: mesh %d: %s" % (i, lib().crthip_strerror(int(status[i])).decode()))
+    res = [out, offs, lens]
+    if not raise_on_error:
+        res.append(status)
+    if with_stats:
+        d = st.as_dict()
+        d["kernel_times"] = t.as_dict()
+        if device_out:
+            d["splice"] = ctx.encode_splice_stats()
         d["total"] = int(r)
         res.append(d)
     return tuple(res)
@@ -1037,6 +1197,38 @@ class Batch:
         self.outputs = [dict() for _ in self.infos]
         self.rebind()
         return metas
+
+    def interleaved_meshes(self):
+        """After allocate_interleaved and a synced decode: per blob (MeshView, MeshLayout) - the mesh's arrays are torch views INTO the
+        interleaved vertex buffer and the index buffer, the layout says how they lie (strides, int16 normals, a uint16 index) - what
+        encode_batch_layout takes as it is.  Generic attributes beyond position / uv / radius come as mesh.attributes, encode()'s list with
+        the blob's own q and strategy."""
+        import torch
+        metas = getattr(self, "_interleaved", None)
+        if metas is None:
+            raise ValueError("interleaved_meshes: call allocate_interleaved first")
+        buf = self._keep[0]
+        tdt = {"f32": torch.float32, "i16": torch.int16, "u8": torch.uint8}
+        res = []
+        for i, (vb, rec, layout, ib, i16) in enumerate(metas):
+            nv, nf = self.infos[i].nvert, self.infos[i].nface
+            raw = buf[vb:vb + nv * rec].view(nv, rec) if nv * rec else buf[:0].view(0, max(rec, 1))
+            attrs = self.infos[i].attrs()
+            fields, extra = {}, []
+            for name, (o, dt, comps, k, fmt, oc) in layout.items():
+                v = raw[:, o:o + comps * np.dtype(_DT[dt]).itemsize].view(tdt[dt])
+                if name in ("position", "normal", "color", "uv", "radius"):
+                    fields[name] = v
+                else:
+                    extra.append((name, v, attrs[k]["q"], attrs[k]["strategy"]))
+            index = None
+            if ib is not None:
+                index = buf[ib:ib + nf * 3 * (2 if i16 else 4)].view(torch.int16 if i16 else torch.int32).view(nf, 3)
+            mesh = MeshView(fields["position"], index, fields.get("normal"), fields.get("color"), fields.get("uv"), fields.get("radius"))
+            mesh.attributes = extra or None
+            lay = MeshLayout.of(mesh, mesh.attributes)
+            res.append((mesh, lay))
+        return res
 
     def rebind(self):
         """(Re)apply the bindings prepared by allocate_outputs: one C call for the whole batch."""

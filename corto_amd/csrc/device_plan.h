@@ -202,7 +202,13 @@ struct QuantJob {
 	int32_t unit;                  // NORMAL: (int)q
 	uint32_t qc[4];                // COLOR: per-channel divisors
 	uint32_t format;               // QK_INT: CRTHIP_FMT_INT32 / INT16 / INT8
+	// crthip_mesh_layout (all zero: the packed arrays above, read as before)
+	uint32_t stride;               // bytes from one vertex's elements to the next's; 0: packed
+	uint32_t comps;                // FLOAT / INT / DOUBLE with a stride or an origin: elements a vertex has (count = vertices * comps)
+	uint32_t flags;                // QF_*
+	float origin[3];               // QF_ORIGIN (FLOAT, comps == 3): x - origin[component], upstream's coords[i] = input[i] - o
 };
+enum : uint32_t { QF_ORIGIN = 1, QF_NORMAL_I16 = 2 };   // QF_NORMAL_I16: NORMAL reads int16 triples, (float)v/32767.0f (src/encoder.cpp:151-158)
 // what k_enc_tables leaves per stream for the Tunstall coder: the block header (probabilities) and the encoder tables
 struct EncTab {
 	uint32_t nsym;                 // symbols that occur (0: empty stream, 1: no payload)

@@ -15,6 +15,8 @@
 //   edge sum       the mesh recipe (:105-110): float norms of every face's first edge added into a double IN FACE ORDER - the terms are
 //                  made in parallel, the sum is one lane's.  sqrtf(s) is the host's (float)sqrt((double)s) (tests/cpp/sqrt_equiv.hip).
 //                  A face whose first edge names a vertex >= nvert is never gathered through: its term is 0 and the record's bit is set.
+// A crthip_mesh_layout changes where a value is read - a stride between vertices, uint16 index entries - and, for a cloud's box, subtracts the
+// origin from each component first; partition, merge order and the in-order sum are untouched, so the argument above holds as it stands.
 // The library is built with -ffp-contract=off: no product here is fused into a sum.
 #pragma once
 #include <float.h>
@@ -58,12 +60,34 @@ static_assert(sizeof(EncInputRecord) == 64, "one record is 64 bytes");
 
 enum { EIN_JOB_RANGE = 0, EIN_JOB_BOX = 1, EIN_JOB_EDGE = 2 };
 struct EncInputJob {                                      // one kind of work on one item; its workgroups are counted from block_start
-	const float *position;                                // nvert*3, 4-byte aligned
-	const uint32_t *index;                                // nface*3, 4-byte aligned (RANGE, EDGE)
+	const float *position;                                // vertex v's three floats at (bytes) position + v*pos_stride, 4-byte aligned
+	const void *index;                                    // nface*3 uint32 (4-byte aligned), or uint16 (index16; 2-byte aligned) (RANGE, EDGE)
 	EncInputBox *partials;                                // BOX: one per tile of EIN_TILE vertices
 	EncInputRecord *rec;
 	uint32_t nvert, nface, kind, recipe;
+	// crthip_mesh_layout
+	uint32_t pos_stride;                                  // bytes from one vertex to the next; 12: packed
+	uint32_t index16;                                     // != 0: the index entries are uint16, widened as they are read
+	uint32_t has_origin, pad;                             // != 0: the cloud's box runs on position - origin (src/encoder.cpp:80-88)
+	float origin[4];
 };
+// how a job reads its arrays, for the kernels and for the host's walk of their partition alike
+EIN_HD uint32_t enc_in_index(const EncInputJob &J, uint64_t i) {
+	return J.index16 ? (uint32_t)((const uint16_t *)J.index)[i] : ((const uint32_t *)J.index)[i];
+}
+EIN_HD const float *enc_in_vertex(const EncInputJob &J, uint64_t v) { return (const float *)((const uint8_t *)J.position + v*J.pos_stride); }
+// what the box loop sees of a vertex: the position, minus the origin where there is one (one float subtraction a component)
+EIN_HD void enc_in_box_value(const EncInputJob &J, const float *p, float out[3]) {
+	for(int k = 0; k < 3; k++) out[k] = J.has_origin ? p[k] - J.origin[k] : p[k];
+}
+// the range pass's cut of n entries: `head` entries up to the first 16-byte boundary, then groups of `per` (16 bytes), then the tail
+EIN_HD void enc_in_range_cut(const EncInputJob &J, uint64_t n, uint32_t &per, uint64_t &head, uint64_t &groups, uint64_t &tail) {
+	const uint32_t esize = J.index16 ? 2u : 4u;
+	per = 16u/esize;
+	const uint64_t to_boundary = ((16u - (uint32_t)((uintptr_t)J.index & 15u)) & 15u)/esize;
+	head = to_boundary < n ? to_boundary : n;
+	groups = (n - head)/per; tail = n - head - groups*per;
+}
 
 EIN_HD void enc_in_box_empty(EncInputBox &b) { for(int k = 0; k < 3; k++) { b.mn[k] = INFINITY; b.mx[k] = -INFINITY; } }
 EIN_HD void enc_in_box_add(EncInputBox &b, const float *v) {                     // the host loop's body
@@ -95,10 +119,11 @@ EIN_HD void enc_in_fold_stretch(EncInputBox &b, const EncInputBox *parts, uint32
 }
 
 // the length of face f's first edge, as Point3f::norm makes it (include/corto/point.h:111); never reads a vertex >= nvert
-EIN_HD float enc_in_edge_term(const float *position, const uint32_t *index, uint32_t f, uint32_t nvert, uint32_t &bad) {
-	const uint32_t ia = index[(size_t)f*3], ib = index[(size_t)f*3 + 1];
-	if(ia >= nvert || ib >= nvert) { bad = 1; return 0.0f; }
-	const float *a = position + (size_t)ia*3, *b = position + (size_t)ib*3;
+// (the raw positions: a mesh's recipe knows no origin, src/encoder.cpp:101-111)
+EIN_HD float enc_in_edge_term(const EncInputJob &J, uint32_t f, uint32_t &bad) {
+	const uint32_t ia = enc_in_index(J, (uint64_t)f*3), ib = enc_in_index(J, (uint64_t)f*3 + 1);
+	if(ia >= J.nvert || ib >= J.nvert) { bad = 1; return 0.0f; }
+	const float *a = enc_in_vertex(J, ia), *b = enc_in_vertex(J, ib);
 	const float d[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]};
 	return sqrtf(d[0]*d[0] + d[1]*d[1] + d[2]*d[2]);
 }

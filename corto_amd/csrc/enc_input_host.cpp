@@ -24,8 +24,8 @@ void tree64(EncInputBox *lanes) {
 	}
 }
 
-void box_in_kernel_partition(const crthip_mesh *m, uint32_t recipe, EncInputBox &out) {
-	const uint32_t nvert = m->nvert;
+void box_in_kernel_partition(const EncInputJob &J, EncInputBox &out) {
+	const uint32_t nvert = J.nvert, recipe = J.recipe;
 	const uint32_t ntiles = (uint32_t)(((uint64_t)nvert + EIN_TILE - 1)/EIN_TILE);
 	std::vector<EncInputBox> parts(ntiles);
 	for(uint32_t b = 0; b < ntiles; b++) {
@@ -34,7 +34,7 @@ void box_in_kernel_partition(const crthip_mesh *m, uint32_t recipe, EncInputBox 
 			const uint64_t v0 = (uint64_t)b*EIN_TILE + (uint64_t)t*EIN_RUN;
 			const uint32_t count = v0 + EIN_RUN <= nvert ? EIN_RUN : v0 < nvert ? (uint32_t)(nvert - v0) : 0u;
 			float v[3*EIN_RUN] = {};
-			if(count) memcpy(v, m->position + v0*3, (size_t)count*12);
+			for(uint32_t r = 0; r < count; r++) enc_in_box_value(J, enc_in_vertex(J, v0 + r), v + 3*r);
 			enc_in_box_run(lanes[t], v, count);
 		}
 		for(uint32_t w = 0; w < EIN_THREADS/64; w++) tree64(lanes + 64*w);
@@ -44,37 +44,44 @@ void box_in_kernel_partition(const crthip_mesh *m, uint32_t recipe, EncInputBox 
 	EncInputBox fold[EIN_FOLD_LANES];
 	for(uint32_t l = 0; l < EIN_FOLD_LANES; l++) enc_in_fold_stretch(fold[l], parts.data(), ntiles, l);
 	tree64(fold);
-	enc_in_box_seed(out, recipe, m->position);
+	enc_in_box_seed(out, recipe, J.position);
 	enc_in_box_merge(out, fold[0]);
 }
 
-uint32_t range_flag(const crthip_mesh *m, uint32_t nface) {
+// which = 0: the host's scan; which = 1: range_blocks' cut - head, 16-byte groups, tail - each part flagged on its own, as the kernel's lanes do
+uint32_t range_flag(const EncInputJob &J, int which) {
+	const uint64_t n = (uint64_t)J.nface*3;
 	uint32_t bad = 0;
-	for(uint64_t i = 0; i < (uint64_t)nface*3; i++) bad |= m->index[i] >= m->nvert;
+	if(which == 0) { for(uint64_t i = 0; i < n; i++) bad |= enc_in_index(J, i) >= J.nvert; return bad; }
+	uint32_t per; uint64_t head, groups, tail;
+	enc_in_range_cut(J, n, per, head, groups, tail);
+	for(uint64_t i = 0; i < head; i++) bad |= enc_in_index(J, i) >= J.nvert;
+	for(uint64_t g = groups; g-- > 0;) for(uint32_t k = 0; k < per; k++) bad |= enc_in_index(J, head + g*per + k) >= J.nvert;
+	for(uint64_t i = 0; i < tail; i++) bad |= enc_in_index(J, head + groups*per + i) >= J.nvert;
 	return bad;
 }
 
-void model(const crthip_mesh *m, int which, crthip_encode_input_result *r) {
+void model(const crthip_mesh *m, const MeshRead *rd, int which, crthip_encode_input_result *r) {
 	memset(r, 0, sizeof(*r));
-	const uint32_t nface = m->index ? m->nface : 0;
-	const uint32_t recipe = enc_in_recipe(m->position_bits, m->position_q, m->nvert, nface);
+	const EncInputJob J = enc_input_job(m, rd);
+	const uint32_t nface = J.nface, recipe = J.recipe;
 	r->recipe = recipe;
-	r->index_out_of_range = range_flag(m, nface);
+	r->index_out_of_range = range_flag(J, which);
 	EncInputRecord rec;
 	memset(&rec, 0, sizeof(rec));
 	if(which == 0) {
 		// the host's loops trust the index (encode_check has scanned it before setup runs) and read position[0] of an empty mesh: neither here
 		const bool box = recipe == EIN_STEP_BOX_FIRST || recipe == EIN_STEP_BOX_MAX;
-		if((box && m->nvert) || (recipe == EIN_STEP_EDGE && !r->index_out_of_range)) input_stats_host(m, recipe, rec);
+		if((box && m->nvert) || (recipe == EIN_STEP_EDGE && !r->index_out_of_range)) input_stats_host(m, recipe, rec, rd);
 	} else {
-		if((recipe == EIN_STEP_BOX_FIRST || recipe == EIN_STEP_BOX_MAX) && m->nvert) box_in_kernel_partition(m, recipe, rec.box);
+		if((recipe == EIN_STEP_BOX_FIRST || recipe == EIN_STEP_BOX_MAX) && m->nvert) box_in_kernel_partition(J, rec.box);
 		if(recipe == EIN_STEP_EDGE) {
 			uint32_t bad = 0;
 			double sum = 0;
 			std::vector<float> terms(EIN_EDGE_TILE);
 			for(uint32_t first = 0; first < nface; first += EIN_EDGE_TILE) {
 				const uint32_t cnt = nface - first < EIN_EDGE_TILE ? nface - first : EIN_EDGE_TILE;
-				for(uint32_t i = cnt; i-- > 0;) terms[i] = enc_in_edge_term(m->position, m->index, first + i, m->nvert, bad);   // (any order: they are independent)
+				for(uint32_t i = cnt; i-- > 0;) terms[i] = enc_in_edge_term(J, first + i, bad);   // (any order: they are independent)
 				for(uint32_t i = 0; i < cnt; i++) sum += (double)terms[i];
 				if(first + EIN_EDGE_TILE < first) break;
 			}
@@ -92,11 +99,17 @@ void model(const crthip_mesh *m, int which, crthip_encode_input_result *r) {
 } // namespace
 
 extern "C" int crthip_encode_input_model(const crthip_mesh *m, int which, crthip_encode_input_result *r) {
+	return crthip_encode_input_model_layout(m, nullptr, which, r);
+}
+
+extern "C" int crthip_encode_input_model_layout(const crthip_mesh *m, const crthip_mesh_layout *layout, int which, crthip_encode_input_result *r) {
 	if(which != 0 && which != 1) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_input_model: which must be 0 (host loops) or 1 (device source)");
 	if(!r) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_input_model: null result");
 	{ const int e = encode_check(m, false); if(e) return e; }
+	MeshRead rd;
+	{ const int e = layout_resolve(m, nullptr, layout, rd); if(e) return e; }
 	try {
-		model(m, which, r);
+		model(m, layout ? &rd : nullptr, which, r);
 		return CRTHIP_OK;
 	} catch(const std::bad_alloc &) {
 		return ctx_fail(CRTHIP_E_NOMEM, nullptr);

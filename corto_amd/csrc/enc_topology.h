@@ -51,7 +51,7 @@ struct EncTopoRecord {                                 // what comes back per me
 static_assert(sizeof(EncTopoRecord) == 64, "one record is 64 bytes");
 
 struct EncTopoJob {
-	const uint32_t *index;       // nface*3, as given
+	const void *index;           // nface*3 as given: uint32, or uint16 (index16) - stage 1 widens as it reads, everything behind it sees faces
 	const uint32_t *gend_in;     // ngroups >= 1 ascending ends, each <= nface
 	uint32_t *faces;             // out: compacted faces
 	uint32_t *gend_out;          // out: ngroups new ends
@@ -65,8 +65,9 @@ struct EncTopoJob {
 	uint32_t *split_packed;      // the batch's split words back to back ...
 	uint32_t *split_cursor;      // ... and how many are there (atomic); null: leave them in split
 	EncTopoRecord *rec;          // zeroed before the first stage
-	uint32_t nvert, nface, ngroups, pad;
+	uint32_t nvert, nface, ngroups, index16;
 };
+ETOPO_HD uint32_t enc_topo_index(const EncTopoJob &J, size_t i) { return J.index16 ? (uint32_t)((const uint16_t *)J.index)[i] : ((const uint32_t *)J.index)[i]; }
 
 template <class L> struct EncTopoState {
 	L *before, *after, *twin, *gates, *postponed, *encoded;
@@ -105,7 +106,7 @@ template <class Team> ETOPO_HD void enc_topo_compact(Team &T, const EncTopoJob &
 			const uint32_t i = base + T.tid;
 			uint32_t f0 = 0, f1 = 0, f2 = 0, keep = 0;
 			if(i < end && i >= base) {
-				f0 = J.index[(size_t)i*3]; f1 = J.index[(size_t)i*3 + 1]; f2 = J.index[(size_t)i*3 + 2];
+				f0 = enc_topo_index(J, (size_t)i*3); f1 = enc_topo_index(J, (size_t)i*3 + 1); f2 = enc_topo_index(J, (size_t)i*3 + 2);
 				keep = !(f0 == f1 || f0 == f2 || f1 == f2);
 			}
 			uint32_t total = 0;

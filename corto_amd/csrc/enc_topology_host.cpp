@@ -16,7 +16,7 @@ static_assert(CRTHIP_TOPOLOGY_CLERS_CAP(1000u) == 7064ull && CRTHIP_TOPOLOGY_SPL
 
 namespace {
 
-int model_device_source(const crthip_mesh *m, crthip_topology_result *r) {
+int model_device_source(const crthip_mesh *m, bool index16, crthip_topology_result *r) {
 	const uint32_t nvert = m->nvert, nface = m->nface;
 	if(enc_topo_clers_cap(nface) != CRTHIP_TOPOLOGY_CLERS_CAP(nface) || enc_topo_split_cap(nface) != CRTHIP_TOPOLOGY_SPLIT_CAP(nface)) return CRTHIP_E_ARGUMENT;
 	const uint32_t one_group[1] = {nface};
@@ -33,7 +33,7 @@ int model_device_source(const crthip_mesh *m, crthip_topology_result *r) {
 	J.first = first.data(); J.cursor = cursor.data(); J.sides = sides.data(); J.twin = twin.data();
 	J.state = image.data(); J.quads = r->quads; J.clers = r->clers; J.split = split.data();
 	J.split_packed = r->split_words; J.split_cursor = nullptr;
-	J.rec = &rec; J.nvert = nvert; J.nface = nface;
+	J.rec = &rec; J.nvert = nvert; J.nface = nface; J.index16 = index16;
 	EncTopoHostTeam T;
 	enc_topo_compact(T, J);
 	enc_topo_pair(T, J);
@@ -68,12 +68,26 @@ extern "C" int crthip_encode_topology_fits_lds(const crthip_mesh *m) {
 }
 
 extern "C" int crthip_encode_topology_model(const crthip_mesh *m, int which, crthip_topology_result *r) {
+	return crthip_encode_topology_model_layout(m, nullptr, which, r);
+}
+
+// the index alone matters to the pass: a uint16 one is widened for the host pass and read as it is by the device source
+extern "C" int crthip_encode_topology_model_layout(const crthip_mesh *m, const crthip_mesh_layout *layout, int which, crthip_topology_result *r) {
 	if(which != 0 && which != 1) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_topology_model: which must be 0 (host pass) or 1 (device source)");
 	if(!r || !r->faces || !r->group_end || !r->quads || !r->clers || !r->split_words) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_topology_model: null buffer");
-	{ const int e = encode_check(m); if(e) return e; }
+	{ const int e = encode_check(m, false); if(e) return e; }
+	MeshRead rd;
+	{ const int e = layout_resolve(m, nullptr, layout, rd); if(e) return e; }
+	{ const int e = index_range_host(m, rd); if(e) return e; }
 	if(!m->index || !m->nface) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_topology_model: a point cloud has no topology pass");
 	try {
-		return which == 0 ? model_host_pass(m, r) : model_device_source(m, r);
+		if(which == 1) return model_device_source(m, rd.index16, r);
+		if(!rd.index16) return model_host_pass(m, r);
+		std::vector<uint32_t> wide((size_t)m->nface*3);
+		for(size_t i = 0; i < wide.size(); i++) wide[i] = ((const uint16_t *)m->index)[i];
+		crthip_mesh w = *m;
+		w.index = wide.data();
+		return model_host_pass(&w, r);
 	} catch(const std::bad_alloc &) {
 		return ctx_fail(CRTHIP_E_NOMEM, nullptr);
 	} catch(...) {

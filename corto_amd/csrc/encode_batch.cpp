@@ -20,6 +20,10 @@
 // and the device topology pass read the caller's arrays in place, and only the index of a mesh the host pool walks comes back
 // (fetch_indices).
 //
+// crthip_encode_batch_layout is the same path again for arrays read through a crthip_mesh_layout (strides, a uint16 index, int16 normals, an
+// origin): layout_resolve leaves a MeshRead per item, the requests and jobs carry its fields, host arrays are packed by upload_inputs'
+// staging copy and resident ones are read where they lie; its host output is the device arena's form (HostArena).
+//
 // How the file is laid out: ChunkImage / build_image say where everything lives in a chunk's device image (the one place that does: the
 // chunker sizes a chunk by building its image); Chunk is what every stage works on; the stages follow, one function each, in the order
 // encode_chunk calls them.  Each stage's comment names the regions of the image it reads (R) and writes (W) and says whether it returns
@@ -100,7 +104,11 @@ struct Slot {
 	uint64_t idx = 0, gend_in = 0, gend_out = 0, first = 0, cursor = 0, sides = 0, twin = 0, state = 0, split = 0;   // the device topology pass
 	uint32_t fbase = 0;                   // first face in the faces region (faces units)
 };
-struct RawIn { const void *src; uint64_t bytes, off; };
+// stride != 0: a host array read through a crthip_mesh_layout - `elem` bytes a vertex, `stride` apart - that the staging copy packs
+struct RawIn {
+	const void *src; uint64_t bytes, off; uint32_t stride = 0, elem = 0;
+	bool direct() const { return bytes >= DIRECT_BYTES && !stride; }    // goes up straight from the caller's array
+};
 
 // Every offset of one chunk's image and the totals its copies need.  Items are named by k, their place in ids.
 struct ChunkImage {
@@ -135,10 +143,14 @@ ChunkImage build_image(const crthip_mesh *meshes, const std::vector<BatchItem> &
 		(it.topo_device ? L.devk : L.hostk).push_back(k);
 		if(!is_mesh(it)) L.clouds.push_back(k);
 		s.in.resize(it.attrs.size()); s.q.resize(it.attrs.size()); s.d.resize(it.attrs.size());
-		if(!resident) for(size_t a = 0; a < it.attrs.size(); a++) { L.raw.push_back(RawIn{it.attrs[a].quant.in, quant_in_bytes(it.attrs[a].quant), 0}); raw_off.push_back(&s.in[a]); }
+		if(!resident) for(size_t a = 0; a < it.attrs.size(); a++) {
+			const QuantRequest &r = it.attrs[a].quant;
+			const uint32_t elem = (uint32_t)quant_vertex_bytes(r);
+			L.raw.push_back(RawIn{r.in, quant_in_bytes(r), 0, r.stride == elem ? 0u : r.stride, elem}); raw_off.push_back(&s.in[a]);
+		}
 		if(it.topo_device) {
 			const crthip_mesh &m = meshes[L.ids[k]];
-			if(!resident) { L.raw.push_back(RawIn{m.index, (uint64_t)it.nface_in*12, 0}); raw_off.push_back(&s.idx); }
+			if(!resident) { L.raw.push_back(RawIn{m.index, (uint64_t)it.nface_in*(it.index16 ? 6 : 12), 0}); raw_off.push_back(&s.idx); }
 			L.raw.push_back(RawIn{m.ngroups ? (const void *)m.group_end : (const void *)&it.nface_in, (uint64_t)it.topo_groups*4, 0}); raw_off.push_back(&s.gend_in);
 		}
 		job_bytes += it.attrs.size()*(sizeof(QuantJob) + sizeof(DeltaEncJob) + sizeof(EstJob) + 8) + 16 + (it.topo_device ? sizeof(EncTopoJob) + 8 : 0);
@@ -147,8 +159,8 @@ ChunkImage build_image(const crthip_mesh *meshes, const std::vector<BatchItem> &
 	// staged_total bytes from offset 0 - and the large ones follow
 	// (a resident call's are the group ends alone: words, packed)
 	for(int big = 0; big < 2; big++)
-		for(size_t i = 0; i < L.raw.size(); i++) if((L.raw[i].bytes >= DIRECT_BYTES) == (big == 1)) *raw_off[i] = L.raw[i].off = c.take(L.raw[i].bytes, resident ? 4 : 256);
-	for(const RawIn &r : L.raw) if(r.bytes < DIRECT_BYTES) L.staged_total = std::max(L.staged_total, r.off + r.bytes);
+		for(size_t i = 0; i < L.raw.size(); i++) if(L.raw[i].direct() == (big == 1)) *raw_off[i] = L.raw[i].off = c.take(L.raw[i].bytes, resident ? 4 : 256);
+	for(const RawIn &r : L.raw) if(!r.direct()) L.staged_total = std::max(L.staged_total, r.off + r.bytes);
 	// INVARIANT: the zeroed words (BORDER XORs, counts, cloud minima), the clouds' flags and the device topology pass's report are
 	// contiguous - one memset of zero_bytes from `zero` - and the report is one block: it comes back in one copy of back_bytes from `back`
 	L.zero = here();
@@ -253,6 +265,7 @@ struct Chunk {
 	// a resident call: every item's descriptor again, with the index of a mesh the host pool walks pointing into host_index (fetch_indices)
 	std::vector<crthip_mesh> shadow;
 	std::vector<uint32_t> host_index;
+	std::vector<uint16_t> host_index16;                      // a resident call's uint16 indices as they came back, before they are widened
 
 	uint32_t n() const { return (uint32_t)img.ids.size(); }
 	BatchItem &item(uint32_t k) const { return items[img.ids[k]]; }
@@ -316,25 +329,44 @@ int radix_sort(hipStream_t st, K *k0, uint32_t *v0, K *k1, uint32_t *v1, uint32_
 
 // ---- the stages, in the order encode_chunk runs them ----
 
-// A resident call's meshes whose topology pass runs on the host pool (hostk) need their index there: one copy each into one host
-// buffer, one wait, and the pool works on descriptors whose index is that copy.  Attributes never come back.  R: the caller's index
-// arrays.  Synchronised on every way out (the buffer is the chunk's, the copies are queued).
+// Meshes whose topology pass runs on the host pool (hostk) need a uint32 index in host memory.  A resident call's is copied back - one copy
+// each into one host buffer, a uint16 index as it is - and after one wait the 16-bit ones are widened; a host call's uint16 index is
+// widened where it lies.  The pool works on descriptors whose index is that copy.  Attributes never come back.  R: the caller's index
+// arrays.  Synchronised on every way out (the buffers are the chunk's, the copies are queued).
 int fetch_indices(Chunk &C) {
 	struct Wait { hipStream_t st; ~Wait() { (void)hipStreamSynchronize(st); } } wait{C.st};
-	std::vector<uint64_t> at(C.n(), 0);
-	uint64_t words = 0;
-	for(uint32_t k : C.img.hostk) if(is_mesh(C.item(k))) { at[k] = words; words += (uint64_t)C.item(k).nface_in*3; }
-	C.host_index.resize(words);
+	std::vector<uint64_t> at(C.n(), 0), at16(C.n(), 0);
+	uint64_t words = 0, narrow = 0;
+	for(uint32_t k : C.img.hostk) {
+		const BatchItem &it = C.item(k);
+		if(!is_mesh(it) || !(C.img.resident || it.index16)) continue;
+		at[k] = words; words += (uint64_t)it.nface_in*3;
+		if(C.img.resident && it.index16) { at16[k] = narrow; narrow += (uint64_t)it.nface_in*3; }
+	}
+	C.host_index.resize(words); C.host_index16.resize(narrow);
 	std::vector<crthip_mesh> shadow(C.n());
 	for(uint32_t k = 0; k < C.n(); k++) shadow[k] = C.meshes[C.img.ids[k]];
 	for(uint32_t k : C.img.hostk) {
-		if(!is_mesh(C.item(k))) continue;
-		const uint64_t bytes = (uint64_t)C.item(k).nface_in*12;
-		ENC_TRY(hipMemcpyAsync(C.host_index.data() + at[k], shadow[k].index, bytes, hipMemcpyDeviceToHost, C.st));
+		const BatchItem &it = C.item(k);
+		if(!is_mesh(it) || !(C.img.resident || it.index16)) continue;
+		const uint64_t entries = (uint64_t)it.nface_in*3;
+		if(!C.img.resident) {
+			const uint16_t *ix = (const uint16_t *)shadow[k].index;
+			for(uint64_t i = 0; i < entries; i++) C.host_index[at[k] + i] = ix[i];
+		} else {
+			const uint64_t bytes = entries*(it.index16 ? 2 : 4);
+			void *dst = it.index16 ? (void *)(C.host_index16.data() + at16[k]) : (void *)(C.host_index.data() + at[k]);
+			ENC_TRY(hipMemcpyAsync(dst, shadow[k].index, bytes, hipMemcpyDeviceToHost, C.st));
+			C.S.bytes_from_device += bytes;
+		}
 		shadow[k].index = C.host_index.data() + at[k];
-		C.S.bytes_from_device += bytes;
 	}
-	if(words) ENC_TRY(C.sync());
+	if(words && C.img.resident) ENC_TRY(C.sync());
+	for(uint32_t k : C.img.hostk) {
+		const BatchItem &it = C.item(k);
+		if(!is_mesh(it) || !C.img.resident || !it.index16) continue;
+		for(uint64_t i = 0; i < (uint64_t)it.nface_in*3; i++) C.host_index[at[k] + i] = C.host_index16[at16[k] + i];
+	}
 	C.shadow.swap(shadow);
 	return 0;
 }
@@ -348,9 +380,10 @@ int upload_inputs(Chunk &C) {
 	for(const RawIn &r : C.img.raw) {
 		const uint64_t b = r.bytes;
 		if(!b) continue;
-		if(b < DIRECT_BYTES) memcpy(stage.data() + r.off, r.src, b);
+		if(r.stride) for(uint64_t v = 0; v < b/r.elem; v++) memcpy(stage.data() + r.off + v*r.elem, (const uint8_t *)r.src + v*r.stride, r.elem);   // (packed here)
+		else if(b < DIRECT_BYTES) memcpy(stage.data() + r.off, r.src, b);
 		else { const auto t0 = Clock::now(); ENC_TRY(hipMemcpyAsync(C.base + r.off, r.src, b, hipMemcpyHostToDevice, C.st)); C.S.upload_ms += ms_since(t0); }
-		if(b >= DIRECT_BYTES) C.S.bytes_to_device += b;
+		if(r.direct()) C.S.bytes_to_device += b;
 	}
 	C.S.host_stage_ms += ms_since(t_stage);
 	{ const auto t0 = Clock::now(); if(C.img.staged_total) ENC_TRY(hipMemcpyAsync(C.base, stage.data(), C.img.staged_total, hipMemcpyHostToDevice, C.st)); C.S.upload_ms += ms_since(t0); }
@@ -369,7 +402,7 @@ int stage_quantise(Chunk &C) {
 		for(size_t a = 0; a < it.attrs.size(); a++) {
 			const QuantRequest &r = it.attrs[a].quant;
 			if(!r.count) continue;
-			qj.push_back(quant_job(r, C.img.resident ? r.in : C.base + C.img.slot[k].in[a], C.base + C.img.slot[k].q[a])); start.push_back(blocks); blocks += (r.count + 255)/256;
+			qj.push_back(quant_job(r, C.img.resident ? r.in : C.base + C.img.slot[k].in[a], C.base + C.img.slot[k].q[a], !C.img.resident)); start.push_back(blocks); blocks += (r.count + 255)/256;
 		}
 	}
 	if(qj.empty()) return 0;
@@ -398,7 +431,7 @@ int stage_topology(Chunk &C) {
 		const Slot &s = C.img.slot[C.img.devk[j]];
 		EncTopoJob &J = tj[j];
 		memset(&J, 0, sizeof(J));
-		J.index = C.img.resident ? C.mesh(C.img.devk[j])->index : C.at<const uint32_t>(s.idx); J.gend_in = C.at<const uint32_t>(s.gend_in);
+		J.index = C.img.resident ? (const void *)C.mesh(C.img.devk[j])->index : C.at<const void>(s.idx); J.index16 = it.index16; J.gend_in = C.at<const uint32_t>(s.gend_in);
 		J.faces = C.at<uint32_t>(C.img.faces) + (size_t)s.fbase*3; J.gend_out = C.at<uint32_t>(s.gend_out);
 		J.first = C.at<uint32_t>(s.first); J.cursor = C.at<uint32_t>(s.cursor);
 		J.sides = C.at<EncTopoSide>(s.sides); J.twin = C.at<uint32_t>(s.twin);
@@ -799,7 +832,9 @@ int encode_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_l
 	Coded coded;
 	Chunk C{ctx, ctx_stream(ctx), meshes, extra, items, img, S, bt, tm};
 	for(uint32_t k : img.devk) C.ready[k] = 1;
-	if(img.resident) { const int e = fetch_indices(C); if(e) return e; }
+	bool widen = img.resident;
+	for(uint32_t k : img.hostk) widen = widen || C.item(k).index16;
+	if(widen) { const int e = fetch_indices(C); if(e) return e; }
 	// topology passes (meshes) and frames (everything) on the pool, started first: they need the index alone
 	std::thread pool;
 	struct Joiner { std::thread &t; ~Joiner() { if(t.joinable()) t.join(); } } joiner{pool};
@@ -861,19 +896,21 @@ bool resident_array_ok(const void *p, uint64_t bytes, uint32_t align, int device
 	return q >= b && bytes <= size && q - b <= size - bytes;
 }
 
-// every data array of one mesh (after encode_check / encode_check_attrs): no launch reads a pointer that has not passed here
-int resident_check(const crthip_mesh *m, const crthip_attr_list *extra, int device) {
+// every data array of one mesh (after encode_check / encode_check_attrs / layout_resolve): no launch reads a pointer that has not passed
+// here.  An array's extent is what the kernels touch of it: [ptr, ptr + (nvert - 1)*stride + one vertex's bytes).
+int resident_check(const crthip_mesh *m, const crthip_attr_list *extra, const MeshRead &rd, int device) {
 	const uint64_t nv = m->nvert;
-	bool ok = resident_array_ok(m->position, nv*12, 4, device);
-	if(m->index && m->nface) ok = ok && resident_array_ok(m->index, (uint64_t)m->nface*12, 4, device);
-	if(m->normal) ok = ok && resident_array_ok(m->normal, nv*12, 4, device);
-	if(m->color) ok = ok && resident_array_ok(m->color, nv*(uint64_t)m->color_components, 1, device);
-	if(m->uv) ok = ok && resident_array_ok(m->uv, nv*8, 4, device);
-	if(m->radius) ok = ok && resident_array_ok(m->radius, nv*4, 4, device);
+	auto extent = [&](uint32_t stride, uint64_t vertex_bytes) { return nv ? (nv - 1)*stride + vertex_bytes : 0; };
+	bool ok = resident_array_ok(m->position, extent(rd.position, 12), 4, device);
+	if(m->index && m->nface) ok = ok && resident_array_ok(m->index, (uint64_t)m->nface*(rd.index16 ? 6 : 12), rd.index16 ? 2 : 4, device);
+	if(m->normal) ok = ok && resident_array_ok(m->normal, extent(rd.normal, rd.normal16 ? 6 : 12), rd.normal16 ? 2 : 4, device);
+	if(m->color) ok = ok && resident_array_ok(m->color, extent(rd.color, (uint64_t)m->color_components), 1, device);
+	if(m->uv) ok = ok && resident_array_ok(m->uv, extent(rd.uv, 8), 4, device);
+	if(m->radius) ok = ok && resident_array_ok(m->radius, extent(rd.radius, 4), 4, device);
 	if(extra) for(uint32_t k = 0; k < extra->nattr && ok; k++) {
 		const crthip_generic_attr &g = extra->attr[k];
-		const uint32_t esize = g.format == CRTHIP_FMT_DOUBLE ? 8u : g.format == CRTHIP_FMT_INT16 ? 2u : g.format == CRTHIP_FMT_INT8 ? 1u : 4u;
-		ok = resident_array_ok(g.values, nv*g.components*esize, esize, device);
+		const uint32_t esize = generic_esize(g.format);
+		ok = resident_array_ok(g.values, extent(rd.attr[k], (uint64_t)g.components*esize), esize, device);
 	}
 	return ok ? CRTHIP_OK : ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch_resident: a data array is not element-aligned device memory of the context's device, "
 	                                                    "or leaves its allocation");
@@ -882,7 +919,7 @@ int resident_check(const crthip_mesh *m, const crthip_attr_list *extra, int devi
 // K-ENC-CHECK (k_encode_check.hip): the index range, the bounding boxes and the first-edge sums of meshes[ok[..]], whichever its step's
 // recipe needs, in two launches; recs[k] is item ok[k]'s record.  The pass has a small allocation of its own - records, partial boxes,
 // job tables - because a chunk's image is laid out from what batch_setup leaves, and batch_setup needs the step.  One copy back, one wait.
-int input_pass(crthip_ctx *ctx, const crthip_mesh *meshes, const std::vector<uint32_t> &ok, std::vector<EncInputRecord> &recs,
+int input_pass(crthip_ctx *ctx, const crthip_mesh *meshes, const std::vector<MeshRead> &reads, const std::vector<uint32_t> &ok, std::vector<EncInputRecord> &recs,
                crthip_encode_batch_stats &S, BatchTimes &bt) {
 	const uint32_t n = (uint32_t)ok.size();
 	recs.assign(n, EncInputRecord{});
@@ -893,9 +930,7 @@ int input_pass(crthip_ctx *ctx, const crthip_mesh *meshes, const std::vector<uin
 	for(uint32_t k = 0; k < n; k++) {
 		const crthip_mesh &m = meshes[ok[k]];
 		const uint32_t nface = m.index ? m.nface : 0;
-		EncInputJob J{};
-		J.position = m.position; J.index = m.index; J.nvert = m.nvert; J.nface = nface;
-		J.recipe = enc_in_recipe(m.position_bits, m.position_q, m.nvert, nface);
+		EncInputJob J = enc_input_job(&m, &reads[ok[k]]);
 		auto add = [&](uint32_t kind, uint64_t nblocks) {
 			J.kind = kind;
 			jobs.push_back(J); rec_of.push_back(k); part_of.push_back(nparts); tables.push_back((uint32_t)blocks);
@@ -954,22 +989,32 @@ int input_pass(crthip_ctx *ctx, const crthip_mesh *meshes, const std::vector<uin
 
 } // namespace
 
-// what encode_batch_impl refuses a mesh for before any device work; resident_device >= 0: its data arrays are that device's memory
-static int batch_item_check(const crthip_mesh *m, const crthip_attr_list *extra, bool index_on_host, int resident_device = -1) {
-	int e = encode_check(m, index_on_host);
+// what encode_batch_impl refuses a mesh for before any device work; rd: the mesh's layout, resolved here; resident_device >= 0: its data
+// arrays are that device's memory
+static int batch_item_check(const crthip_mesh *m, const crthip_attr_list *extra, const crthip_mesh_layout *layout, MeshRead &rd, bool index_on_host,
+                            int resident_device = -1) {
+	const bool index16 = layout && (layout->flags & CRTHIP_IN_INDEX_UINT16);   // (encode_check scans uint32 entries: a uint16 index is scanned behind the layout's own checks)
+	int e = encode_check(m, index_on_host && !index16);
 	if(!e) e = encode_check_attrs(m, extra, true);
-	if(!e && resident_device >= 0) e = resident_check(m, extra, resident_device);
+	if(!e) e = layout_resolve(m, extra, layout, rd);
+	if(!e && index_on_host && index16) e = index_range_host(m, rd);
+	if(!e && resident_device >= 0) e = resident_check(m, extra, rd, resident_device);
 	if(!e && (uint64_t)m->nvert*3 > (1u << 26)) e = ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: too many vertices for the value coder");
 	if(!e && m->entropy == CRTHIP_ENTROPY_TUNSTALL && m->nvert > (1u << 23))
 		e = ctx_fail(CRTHIP_E_LIMIT, "crthip_encode_batch: a Tunstall stream longer than 2^23 symbols");
 	return e;
 }
 
+// crthip_encode_batch_layout with host output: where the blobs go in the caller's host arena
+struct HostArena { uint8_t *out = nullptr; size_t cap = 0; std::vector<uint32_t> len; };
+
 // resident: the data arrays of meshes / extra are DEVICE pointers (crthip_encode_batch_resident); dout: the blobs stay on the device
-// (crthip_encode_batch_to_device: out / cap / blob_offset are then unused); everything else is the one path
+// (crthip_encode_batch_to_device: out / cap / blob_offset are then unused); layouts: n crthip_mesh_layout or null; harena: the blobs go
+// into a host arena laid out as the device one (crthip_encode_batch_layout; out / cap unused); everything else is the one path
 static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra, uint32_t host_threads,
                                  uint8_t *out, size_t cap, uint64_t *blob_offset, uint32_t *out_nvert, uint32_t *out_nface,
-                                 int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times, bool resident, DeviceOut *dout = nullptr) {
+                                 int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times, bool resident, DeviceOut *dout = nullptr,
+                                 const crthip_mesh_layout *layouts = nullptr, HostArena *harena = nullptr) {
 	const auto t0 = Clock::now();
 	if(!ctx) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch: null context (there is no CPU fallback: use crthip_encode for the host encoder)");
 	if(!blob_offset || (n && !meshes)) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch: null argument");
@@ -984,9 +1029,10 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 
 	// per-mesh argument checks; what fails gets its code and an empty range
 	std::vector<BatchItem> items(n);
+	std::vector<MeshRead> reads(n);
 	std::vector<uint32_t> ok;
 	for(uint32_t i = 0; i < n; i++) {
-		items[i].status = batch_item_check(&meshes[i], extra ? &extra[i] : nullptr, !resident, resident ? ctx_device(ctx) : -1);
+		items[i].status = batch_item_check(&meshes[i], extra ? &extra[i] : nullptr, layouts ? &layouts[i] : nullptr, reads[i], !resident, resident ? ctx_device(ctx) : -1);
 		if(!items[i].status) ok.push_back(i);
 	}
 	// position steps and attribute tables (the steps' sums are the host's, in its order: a resident call gets them, and the index check
@@ -995,7 +1041,7 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 	std::vector<float> steps;
 	if(resident) {
 		std::vector<EncInputRecord> recs;
-		{ const int e = input_pass(ctx, meshes, ok, recs, S, bt); if(e) return e; }
+		{ const int e = input_pass(ctx, meshes, reads, ok, recs, S, bt); if(e) return e; }
 		steps.resize(ok.size());
 		for(size_t k = 0; k < ok.size(); k++) {
 			const crthip_mesh &m = meshes[ok[k]];
@@ -1005,7 +1051,7 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 	}
 	parallel_for((uint32_t)ok.size(), threads, [&](uint32_t k) {
 		if(items[ok[k]].status) return;
-		items[ok[k]].status = item_guard([&] { batch_setup(&meshes[ok[k]], extra ? &extra[ok[k]] : nullptr, items[ok[k]], resident ? &steps[k] : nullptr); });
+		items[ok[k]].status = item_guard([&] { batch_setup(&meshes[ok[k]], extra ? &extra[ok[k]] : nullptr, items[ok[k]], resident ? &steps[k] : nullptr, &reads[ok[k]]); });
 	});
 	ok.erase(std::remove_if(ok.begin(), ok.end(), [&](uint32_t i) { return items[i].status != CRTHIP_OK; }), ok.end());
 	// where each mesh's topology pass runs: from the context's mode and the mesh's sizes alone
@@ -1034,7 +1080,7 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 	if(dout && dout->arena && ok.size() > 1 && build_image(meshes, items, ok, resident).total > budget && dout->cap < crthip_encode_batch_bound(n, meshes, extra)) {
 		DeviceOut sizing;
 		sizing.cap = dout->cap; sizing.len.assign(n, 0);
-		const int64_t total = encode_batch_impl(ctx, n, meshes, extra, host_threads, nullptr, 0, blob_offset, out_nvert, out_nface, status, stats, times, resident, &sizing);
+		const int64_t total = encode_batch_impl(ctx, n, meshes, extra, host_threads, nullptr, 0, blob_offset, out_nvert, out_nface, status, stats, times, resident, &sizing, layouts);
 		if(total < 0 || (uint64_t)total > dout->cap) { dout->len = sizing.len; dout->at = sizing.at; dout->st = sizing.st; return total; }
 	}
 	for(size_t k = 0; k < ok.size();) {
@@ -1060,6 +1106,18 @@ static int64_t encode_batch_impl(crthip_ctx *ctx, uint32_t n, const crthip_mesh 
 	}
 	blob_offset[n] = w;
 	if(dout) w = dout->at;
+	if(harena) {                                                       // the device arena's form in host memory: crthip_arena_layout, zeros to each next 16
+		harena->len.assign(n, 0);
+		for(uint32_t i = 0; i < n; i++) if(!items[i].status) harena->len[i] = (uint32_t)blobs[i].size();
+		std::vector<uint64_t> at(n);
+		w = crthip_arena_layout(n, harena->len.data(), at.data());
+		if(harena->out && w <= harena->cap)
+			for(uint32_t i = 0; i < n; i++) {
+				const uint64_t len = harena->len[i];
+				if(len) memcpy(harena->out + at[i], blobs[i].data(), len);
+				memset(harena->out + at[i] + len, 0, ((len + 15) & ~15ull) - len);
+			}
+	}
 	S.bytes_to_device += tm.bytes_to_device; S.bytes_from_device += tm.bytes_from_device;
 	S.wall_ms = (float)ms_since(t0);
 	if(stats) *stats = S;
@@ -1147,10 +1205,57 @@ extern "C" int64_t crthip_encode_batch_to_device(crthip_ctx *ctx, uint32_t n, co
 	}
 }
 
+// ---- crthip_encode_batch_layout ----
+
+extern "C" int64_t crthip_encode_batch_layout(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra, const crthip_mesh_layout *layouts,
+                                              uint32_t host_threads, uint32_t flags, void *out, size_t cap, uint64_t *blob_offset, uint32_t *blob_len,
+                                              uint32_t *out_nvert, uint32_t *out_nface, int32_t *status, crthip_encode_batch_stats *stats,
+                                              crthip_kernel_times *times) {
+	try {
+		if(flags & ~(CRTHIP_ENCODE_INPUTS_RESIDENT | CRTHIP_ENCODE_OUTPUT_DEVICE)) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch_layout: unknown flag bits");
+		const bool resident = (flags & CRTHIP_ENCODE_INPUTS_RESIDENT) != 0, device_out = (flags & CRTHIP_ENCODE_OUTPUT_DEVICE) != 0;
+		if(n == 0) {                                                    // nothing is read or written, the context included
+			if(stats) memset(stats, 0, sizeof(*stats));
+			if(times) memset(times, 0, sizeof(*times));
+			if(ctx && device_out) ctx_splice_stats(ctx) = crthip_splice_stats{};
+			return 0;
+		}
+		if(!ctx) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch_layout: null context (there is no CPU fallback: crthip_encode_layout is the host encoder)");
+		if(!blob_offset || !blob_len || !meshes) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch_layout: null argument");
+		std::vector<uint64_t> unused(n + 1, 0);
+		DeviceOut D;
+		HostArena H;
+		if(device_out) {
+			ctx_splice_stats(ctx) = crthip_splice_stats{};
+			ENC_TRY(hipSetDevice(ctx_device(ctx)));
+			if(out && !resident_array_ok(out, cap ? cap : 1, 16, ctx_device(ctx)))
+				return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch_layout: out is not 16-byte aligned device memory of the context's device, "
+				                                   "or [out, out + cap) leaves its allocation");
+			D.arena = (uint8_t *)out; D.cap = cap; D.len.assign(n, 0);
+		} else { H.out = (uint8_t *)out; H.cap = cap; }
+		const int64_t total = encode_batch_impl(ctx, n, meshes, extra, host_threads, nullptr, 0, unused.data(), out_nvert, out_nface, status, stats, times,
+		                                        resident, device_out ? &D : nullptr, layouts, device_out ? nullptr : &H);
+		if(total < 0) return total;
+		memcpy(blob_len, device_out ? D.len.data() : H.len.data(), (size_t)n*4);
+		const uint64_t laid = crthip_arena_layout(n, blob_len, blob_offset);
+		if(laid != (uint64_t)total) return ctx_fail(CRTHIP_E_DEVICE, "crthip_encode_batch_layout: the plan and crthip_arena_layout disagree");
+		if(device_out) {
+			D.st.arena_bytes = (uint64_t)total; D.st.splice_kernel_us = D.kernel_ms*1000.0f;
+			ctx_splice_stats(ctx) = D.st;
+		}
+		return total;
+	} catch(const std::bad_alloc &) {
+		return ctx_fail(CRTHIP_E_NOMEM, nullptr);
+	} catch(...) {
+		return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_batch_layout: internal error");
+	}
+}
+
 // one item's share of crthip_encode_batch_bound: its frame as batch_frame / batch_topology make it from the descriptor (every field of it has
 // a fixed width), and per slot the bounds the coders themselves check
 static uint64_t item_bound(const crthip_mesh *m, const crthip_attr_list *extra) {
-	if(batch_item_check(m, extra, false)) return 0;
+	MeshRead rd;
+	if(batch_item_check(m, extra, nullptr, rd, false)) return 0;
 	BatchItem it;
 	const float step = 1.0f;                                           // (its four bytes are in the frame whatever it is; no array is read)
 	batch_setup(m, extra, it, &step);

@@ -710,26 +710,92 @@ int corto_hip::encode_check_attrs(const crthip_mesh *m, const crthip_attr_list *
 	return CRTHIP_OK;
 }
 
+uint32_t corto_hip::generic_esize(uint32_t format) {
+	return format == CRTHIP_FMT_DOUBLE ? 8u : format == CRTHIP_FMT_INT16 ? 2u : format == CRTHIP_FMT_INT8 ? 1u : 4u;
+}
+
+// crthip_mesh_layout's rules (include/corto_hip.h).  Strides have no upstream counterpart; the flags and the origin are upstream's overloads
+// (src/encoder.cpp:77-81, 114-119, 151-158), whose addPositionsBits takes no origin.
+int corto_hip::layout_resolve(const crthip_mesh *m, const crthip_attr_list *extra, const crthip_mesh_layout *L, MeshRead &rd) {
+	rd = MeshRead{};
+	rd.color = m->color ? (uint32_t)m->color_components : 0u;
+	const uint32_t nattr = extra ? extra->nattr : 0;
+	for(uint32_t k = 0; k < nattr; k++) rd.attr.push_back(extra->attr[k].components*generic_esize(extra->attr[k].format));
+	if(!L) return CRTHIP_OK;
+	if(L->flags & ~(uint32_t)(CRTHIP_IN_INDEX_UINT16 | CRTHIP_IN_NORMAL_INT16)) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_mesh_layout: unknown flag bits");
+	for(int k = 0; k < 3; k++) if(!std::isfinite(L->origin[k])) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_mesh_layout: the origin must be finite");
+	rd.has_origin = L->origin[0] != 0.0f || L->origin[1] != 0.0f || L->origin[2] != 0.0f;
+	if(rd.has_origin && m->position_bits > 0) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_mesh_layout: position_bits > 0 takes no origin (Encoder::addPositionsBits has none)");
+	for(int k = 0; k < 3; k++) rd.origin[k] = L->origin[k];
+	rd.index16 = (L->flags & CRTHIP_IN_INDEX_UINT16) && m->index && m->nface;
+	rd.normal16 = (L->flags & CRTHIP_IN_NORMAL_INT16) && m->normal;
+	if(rd.index16 && ((uintptr_t)m->index & 1u)) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_mesh_layout: a uint16 index must be 2-byte aligned");
+	if(rd.normal16 && ((uintptr_t)m->normal & 1u)) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_mesh_layout: int16 normals must be 2-byte aligned");
+	if(rd.normal16) rd.normal = 6;
+	bool ok = true, strided = false;
+	auto stride = [&](uint32_t given, uint32_t &resolved, uint32_t align, bool present) {   // resolved comes in as one vertex's bytes
+		if(!given || !present) return;
+		if(given % align || given < resolved) ok = false;
+		strided = strided || given != resolved;
+		resolved = given;
+	};
+	stride(L->position_stride, rd.position, 4, true);
+	stride(L->normal_stride, rd.normal, rd.normal16 ? 2 : 4, m->normal != nullptr);
+	stride(L->color_stride, rd.color, 1, m->color != nullptr);
+	stride(L->uv_stride, rd.uv, 4, m->uv != nullptr);
+	stride(L->radius_stride, rd.radius, 4, m->radius != nullptr);
+	if(L->attr_stride) for(uint32_t k = 0; k < nattr; k++) stride(L->attr_stride[k], rd.attr[k], generic_esize(extra->attr[k].format), true);
+	if(!ok) return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_mesh_layout: a stride must be a multiple of the element's alignment and at least one vertex's bytes");
+	rd.plain = !(rd.index16 || rd.normal16 || rd.has_origin || strided);
+	return CRTHIP_OK;
+}
+
+int corto_hip::index_range_host(const crthip_mesh *m, const MeshRead &rd) {
+	if(!m->index || !m->nface) return CRTHIP_OK;
+	const size_t n = (size_t)m->nface*3;
+	bool bad = false;
+	if(rd.index16) { const uint16_t *ix = (const uint16_t *)m->index; for(size_t i = 0; i < n; i++) bad |= ix[i] >= m->nvert; }
+	else for(size_t i = 0; i < n; i++) bad |= m->index[i] >= m->nvert;
+	return bad ? ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode: face index out of range") : CRTHIP_OK;
+}
+
+corto_hip::EncInputJob corto_hip::enc_input_job(const crthip_mesh *m, const MeshRead *rd) {
+	EncInputJob J{};
+	J.position = m->position; J.index = m->index; J.nvert = m->nvert; J.nface = m->index ? m->nface : 0;
+	J.recipe = enc_in_recipe(m->position_bits, m->position_q, m->nvert, J.nface);
+	J.pos_stride = rd ? rd->position : 12u;
+	J.index16 = rd && rd->index16;
+	J.has_origin = rd && rd->has_origin;
+	if(rd) for(int k = 0; k < 3; k++) J.origin[k] = rd->origin[k];
+	return J;
+}
+
 // The position step's two halves (src/encoder.cpp:49-100): the loops over the mesh's arrays, and the formulas over what they leave.  The
 // loops are upstream's, in upstream's order; crthip_encode_batch_resident runs them on the device (enc_input_check.h) and the formulas here.
-void corto_hip::input_stats_host(const crthip_mesh *m, uint32_t recipe, EncInputRecord &r) {
+void corto_hip::input_stats_host(const crthip_mesh *m, uint32_t recipe, EncInputRecord &r, const MeshRead *rd) {
 	memset(&r, 0, sizeof(r));
 	const uint32_t nv = m->nvert, nface = m->index ? m->nface : 0;
 	float *mn = r.box.mn, *mx = r.box.mx;
+	// the arrays as the layout says they lie (none: packed floats, uint32 entries, origin 0)
+	const size_t stride = rd ? rd->position : 12;
+	const bool i16 = rd && rd->index16;
+	const float zero[3] = {0.0f, 0.0f, 0.0f}, *o = rd ? rd->origin : zero;
+	auto P = [&](size_t i) { return (const float *)((const uint8_t *)m->position + i*stride); };
+	auto I = [&](size_t i) { return i16 ? (uint32_t)((const uint16_t *)m->index)[i] : m->index[i]; };
 	if(recipe == EIN_STEP_BOX_FIRST) {
-		for(int k = 0; k < 3; k++) mn[k] = mx[k] = m->position[k];
-		for(uint32_t i = 0; i < nv; i++) for(int k = 0; k < 3; k++) { const float v = m->position[(size_t)i*3 + k]; if(v < mn[k]) mn[k] = v; if(v > mx[k]) mx[k] = v; }
-	} else if(recipe == EIN_STEP_EDGE) {                        // the length of each face's first edge (src/encoder.cpp:105-110)
+		for(int k = 0; k < 3; k++) mn[k] = mx[k] = P(0)[k];
+		for(uint32_t i = 0; i < nv; i++) for(int k = 0; k < 3; k++) { const float v = P(i)[k]; if(v < mn[k]) mn[k] = v; if(v > mx[k]) mx[k] = v; }
+	} else if(recipe == EIN_STEP_EDGE) {                        // the length of each face's first edge (src/encoder.cpp:105-110), on the raw positions
 		double average = 0;
 		for(uint32_t f = 0; f < nface; f++) {
-			const float *a = m->position + (size_t)m->index[(size_t)f*3]*3, *b = m->position + (size_t)m->index[(size_t)f*3 + 1]*3;
+			const float *a = P(I((size_t)f*3)), *b = P(I((size_t)f*3 + 1));
 			const float d[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]};
 			average += (float)sqrt((double)(d[0]*d[0] + d[1]*d[1] + d[2]*d[2]));   // Point3f::norm, include/corto/point.h:111
 		}
 		r.sum = average;
-	} else if(recipe == EIN_STEP_BOX_MAX) {                     // point cloud: the bounding box (src/encoder.cpp:83-91)
+	} else if(recipe == EIN_STEP_BOX_MAX) {                     // point cloud: the bounding box of input - o (src/encoder.cpp:80-91)
 		for(int k = 0; k < 3; k++) { mn[k] = FLT_MAX; mx[k] = -FLT_MAX; }
-		for(uint32_t i = 0; i < nv; i++) for(int k = 0; k < 3; k++) { const float v = m->position[(size_t)i*3 + k] - 0.0f; if(v < mn[k]) mn[k] = v; if(v > mx[k]) mx[k] = v; }
+		for(uint32_t i = 0; i < nv; i++) for(int k = 0; k < 3; k++) { const float v = P(i)[k] - o[k]; if(v < mn[k]) mn[k] = v; if(v > mx[k]) mx[k] = v; }
 	}
 }
 
@@ -751,12 +817,18 @@ float corto_hip::position_step(const crthip_mesh *m, uint32_t recipe, const EncI
 uint64_t corto_hip::quant_in_bytes(const QuantRequest &r) {
 	const uint64_t n = r.count;
 	switch(r.kind) {
-	case QK_NORMAL: return n*12;
+	case QK_NORMAL: return n*((r.flags & corto_hip::QF_NORMAL_I16) ? 6 : 12);
 	case QK_COLOR: return n*r.N;
 	case QK_DOUBLE: return n*8;
 	case QK_INT: return n*(r.format == CRTHIP_FMT_INT8 ? 1 : r.format == CRTHIP_FMT_INT16 ? 2 : 4);
 	default: return n*4;
 	}
+}
+
+uint64_t corto_hip::quant_vertex_bytes(const QuantRequest &r) {
+	QuantRequest one = r;
+	one.count = r.kind == QK_NORMAL || r.kind == QK_COLOR ? 1u : r.comps;
+	return quant_in_bytes(one);
 }
 
 uint64_t corto_hip::quant_out_bytes(const QuantRequest &r) {
@@ -775,7 +847,10 @@ extern "C" {
 struct NamedQuant { std::string name; corto_hip::QuantRequest r; };
 // `extra`: the caller's generic attributes (Encoder::addAttribute, src/encoder.cpp:187-197), checked by encode_check_attrs.
 // `faces`: copy the index into E.faces (only the host's topology pass reads it; with faces == false and a step m's data arrays are not read at all).
-static void setup(const crthip_mesh *m, const crthip_attr_list *extra, Encoder &E, std::vector<NamedQuant> &quant, bool alloc, const float *step, bool faces = true) {
+// `rd`: the mesh's arrays are read through this layout (the batch encoder: the requests carry it to the staging copies and the quantiser;
+// with faces == true the index must be uint32 all the same).
+static void setup(const crthip_mesh *m, const crthip_attr_list *extra, Encoder &E, std::vector<NamedQuant> &quant, bool alloc, const float *step, bool faces = true,
+                  const corto_hip::MeshRead *rd = nullptr) {
 	E.nvert = m->nvert; E.nface = m->index ? m->nface : 0; E.entropy = (uint32_t)m->entropy;
 	const char *p = m->exif;
 	for(uint32_t i = 0; i < m->nexif; i++) { std::string k(p); p += k.size() + 1; std::string v(p); p += v.size() + 1; E.exif[k] = v; }
@@ -792,7 +867,8 @@ static void setup(const crthip_mesh *m, const crthip_attr_list *extra, Encoder &
 	}
 	if(E.nface && faces) E.faces.assign(m->index, m->index + (size_t)E.nface*3);
 	const uint32_t nv = m->nvert;
-	auto request = [&](const char *name, Attr &a, corto_hip::QuantRequest r, size_t elems, size_t esize) {
+	auto request = [&](const char *name, Attr &a, corto_hip::QuantRequest r, size_t elems, size_t esize, uint32_t stride = 0, uint32_t comps = 1) {
+		if(rd) { r.stride = stride; r.comps = comps; }
 		if(alloc) { if(esize == 1) a.cvalues.resize(elems); else a.values.resize(elems); r.out = esize == 1 ? (void *)a.cvalues.data() : (void *)a.values.data(); }
 		quant.push_back(NamedQuant{name, r});
 	};
@@ -802,21 +878,23 @@ static void setup(const crthip_mesh *m, const crthip_attr_list *extra, Encoder &
 		else {
 			const uint32_t recipe = corto_hip::enc_in_recipe(m->position_bits, m->position_q, nv, E.nface);
 			corto_hip::EncInputRecord r;
-			corto_hip::input_stats_host(m, recipe, r);
+			corto_hip::input_stats_host(m, recipe, r, rd);
 			q = corto_hip::position_step(m, recipe, r);
 		}
 		Attr &a = E.data["position"];
 		a.name = "position"; a.N = 3; a.q = q; a.format = CRTHIP_FMT_FLOAT;
 		a.strategy = CRTHIP_CORRELATED | (E.nface > 0 ? CRTHIP_PARALLEL : 0);
 		corto_hip::QuantRequest r; r.kind = QK_FLOAT; r.count = nv*3; r.in = m->position; r.q = q;
-		request("position", a, r, (size_t)nv*3, 4);
+		if(rd && rd->has_origin) { r.flags |= corto_hip::QF_ORIGIN; for(int k = 0; k < 3; k++) r.origin[k] = rd->origin[k]; }
+		request("position", a, r, (size_t)nv*3, 4, rd ? rd->position : 0, 3);
 	}
 	if(m->normal) {
 		Attr &a = E.data["normal"];
 		a.name = "normal"; a.codec = CRTHIP_CODEC_NORMAL; a.N = 3; a.q = powf(2.0f, (float)(m->normal_bits - 1));
 		a.format = CRTHIP_FMT_FLOAT; a.strategy = CRTHIP_CORRELATED; a.prediction = m->normal_prediction;
 		corto_hip::QuantRequest r; r.kind = QK_NORMAL; r.count = nv; r.in = m->normal; r.unit = f2i(a.q);
-		request("normal", a, r, (size_t)nv*2, 4);
+		if(rd && rd->normal16) r.flags |= corto_hip::QF_NORMAL_I16;                    // (the format byte stays FLOAT: upstream converts, then addNormals(float *))
+		request("normal", a, r, (size_t)nv*2, 4, rd ? rd->normal : 0);
 	}
 	if(m->color) {
 		Attr &a = E.data["color"];
@@ -824,23 +902,23 @@ static void setup(const crthip_mesh *m, const crthip_attr_list *extra, Encoder &
 		for(int k = 0; k < 3; k++) a.qc[k] = 1 << (8 - m->color_bits[k]);
 		a.qc[3] = m->color_components == 3 ? 1 : 1 << (8 - m->color_bits[3]);           // addColors3: setQ(r, g, b, 8)
 		corto_hip::QuantRequest r; r.kind = QK_COLOR; r.count = nv; r.N = (uint32_t)a.N; r.in = m->color; for(int k = 0; k < 4; k++) r.qc[k] = (uint32_t)a.qc[k];
-		request("color", a, r, (size_t)nv*a.N, 1);
+		request("color", a, r, (size_t)nv*a.N, 1, rd ? rd->color : 0);
 	}
 	// GenericAttr<int>::quantize (vertex_attribute.h:79-104): the recipe follows the input format, the header keeps it as the format byte
-	auto generic = [&](const char *name, const void *buf, int N, float q, uint32_t format, uint32_t strategy) {
+	auto generic = [&](const char *name, const void *buf, int N, float q, uint32_t format, uint32_t strategy, uint32_t stride) {
 		Attr &a = E.data[name];
 		a.name = name; a.N = N; a.q = q; a.format = (int)format; a.strategy = (int)strategy;
 		corto_hip::QuantRequest r;
 		r.kind = format == CRTHIP_FMT_FLOAT ? QK_FLOAT : format == CRTHIP_FMT_DOUBLE ? QK_DOUBLE : QK_INT;
 		r.format = format; r.count = nv*(uint32_t)N; r.in = buf; r.q = q;
-		request(name, a, r, (size_t)nv*N, 4);
+		request(name, a, r, (size_t)nv*N, 4, stride, (uint32_t)N);
 	};
-	if(m->uv) generic("uv", m->uv, 2, m->uv_q, CRTHIP_FMT_FLOAT, 0);
-	if(m->radius) generic("radius", m->radius, 1, m->radius_q, CRTHIP_FMT_FLOAT, 0);
+	if(m->uv) generic("uv", m->uv, 2, m->uv_q, CRTHIP_FMT_FLOAT, 0, rd ? rd->uv : 0);
+	if(m->radius) generic("radius", m->radius, 1, m->radius_q, CRTHIP_FMT_FLOAT, 0, rd ? rd->radius : 0);
 	if(extra)
 		for(uint32_t k = 0; k < extra->nattr; k++) {
 			const crthip_generic_attr &g = extra->attr[k];
-			generic(g.name, g.values, (int)g.components, g.q, g.format, g.strategy);
+			generic(g.name, g.values, (int)g.components, g.q, g.format, g.strategy, rd && k < rd->attr.size() ? rd->attr[k] : 0);
 		}
 }
 
@@ -872,13 +950,13 @@ static void quantize_host(const corto_hip::QuantRequest &r) {
 }
 
 static int64_t encode_impl(const crthip_mesh *m, const crthip_attr_list *extra, uint8_t *out, size_t cap, uint32_t *out_nvert, uint32_t *out_nface,
-                           crthip_ctx *gpu) {
+                           crthip_ctx *gpu, const float *step = nullptr) {
 	if(!m || !m->position) return CRTHIP_E_ARGUMENT;
 	Encoder E;
 	std::vector<Deferred> deferred;
 	if(gpu) E.s.defer = &deferred;
 	std::vector<NamedQuant> named;
-	setup(m, extra, E, named, true, nullptr);
+	setup(m, extra, E, named, true, step);
 	std::vector<corto_hip::QuantRequest> quant;                     // (device path) the attributes' quantisation, collected and run in one call
 	for(const NamedQuant &q : named) { if(gpu) quant.push_back(q.r); else quantize_host(q.r); }
 	if(gpu) { const int qerr = corto_hip::quantize_device(gpu, quant); if(qerr) return qerr; }   // every attribute's quantisation in one device call (k_enc_quantize)
@@ -931,6 +1009,88 @@ int64_t crthip_encode_attrs(const crthip_mesh *m, const crthip_attr_list *extra,
 
 int64_t crthip_encode(const crthip_mesh *m, uint8_t *out, size_t cap, uint32_t *out_nvert, uint32_t *out_nface) {
 	return crthip_encode_attrs(m, nullptr, out, cap, out_nvert, out_nface);
+}
+
+// crthip_encode_layout: the mesh's HOST arrays converted into packed ones - upstream's own conversions, each one float operation
+// (src/encoder.cpp:80-81, 116-117, 156) - and handed to the encoder above.  A mesh's first-edge step is taken from the raw positions
+// (:105-110 runs before the origin is subtracted), so it is computed here and passed along.
+namespace {
+struct PackedMesh {
+	crthip_mesh m;
+	crthip_attr_list list{0, nullptr};
+	std::vector<crthip_generic_attr> attrs;
+	std::vector<float> pos, nrm, uv, rad;
+	std::vector<uint32_t> idx;
+	std::vector<uint8_t> col;
+	std::vector<std::vector<uint8_t>> extra;
+};
+void gather(void *dst, const void *src, size_t n, size_t stride, size_t bytes) {
+	for(size_t i = 0; i < n; i++) memcpy((uint8_t *)dst + i*bytes, (const uint8_t *)src + i*stride, bytes);
+}
+void pack_layout_host(const crthip_mesh *m, const crthip_attr_list *extra, const corto_hip::MeshRead &rd, PackedMesh &P) {
+	const size_t nv = m->nvert;
+	P.m = *m;
+	P.pos.resize(nv*3);
+	gather(P.pos.data(), m->position, nv, rd.position, 12);
+	if(rd.has_origin) for(size_t i = 0; i < nv*3; i++) P.pos[i] = P.pos[i] - rd.origin[i%3];
+	P.pos.resize(nv*3 + 3);                                     // (position stays non-null for an empty mesh)
+	P.m.position = P.pos.data();
+	if(m->index && m->nface) {
+		P.idx.resize((size_t)m->nface*3);
+		if(rd.index16) { const uint16_t *ix = (const uint16_t *)m->index; for(size_t i = 0; i < P.idx.size(); i++) P.idx[i] = ix[i]; }
+		else memcpy(P.idx.data(), m->index, P.idx.size()*4);
+		P.m.index = P.idx.data();
+	}
+	if(m->normal) {
+		P.nrm.resize(nv*3 + 3);
+		if(rd.normal16) {
+			for(size_t i = 0; i < nv; i++) {
+				int16_t v[3];
+				memcpy(v, (const uint8_t *)m->normal + i*rd.normal, 6);
+				for(int k = 0; k < 3; k++) P.nrm[i*3 + k] = (float)v[k]/32767.0f;
+			}
+		} else gather(P.nrm.data(), m->normal, nv, rd.normal, 12);
+		P.m.normal = P.nrm.data();
+	}
+	if(m->color) { P.col.resize(nv*m->color_components + 4); gather(P.col.data(), m->color, nv, rd.color, (size_t)m->color_components); P.m.color = P.col.data(); }
+	if(m->uv) { P.uv.resize(nv*2 + 2); gather(P.uv.data(), m->uv, nv, rd.uv, 8); P.m.uv = P.uv.data(); }
+	if(m->radius) { P.rad.resize(nv + 1); gather(P.rad.data(), m->radius, nv, rd.radius, 4); P.m.radius = P.rad.data(); }
+	if(extra && extra->nattr) {
+		P.attrs.assign(extra->attr, extra->attr + extra->nattr);
+		P.extra.resize(extra->nattr);
+		for(uint32_t k = 0; k < extra->nattr; k++) {
+			const size_t bytes = (size_t)P.attrs[k].components*corto_hip::generic_esize(P.attrs[k].format);
+			P.extra[k].resize(nv*bytes + 8);
+			gather(P.extra[k].data(), P.attrs[k].values, nv, rd.attr[k], bytes);
+			P.attrs[k].values = P.extra[k].data();
+		}
+		P.list.nattr = extra->nattr; P.list.attr = P.attrs.data();
+	}
+}
+} // namespace
+
+int64_t crthip_encode_layout(const crthip_mesh *m, const crthip_attr_list *extra, const crthip_mesh_layout *layout, uint8_t *out, size_t cap,
+                             uint32_t *out_nvert, uint32_t *out_nface) {
+	using namespace corto_hip;
+	{ const int e = encode_check(m, false); if(e) return e; }
+	{ const int e = encode_check_attrs(m, extra, false); if(e) return e; }
+	MeshRead rd;
+	{ const int e = layout_resolve(m, extra, layout, rd); if(e) return e; }
+	if(rd.plain) return encode_checked(m, extra, out, cap, out_nvert, out_nface, nullptr);
+	{ const int e = index_range_host(m, rd); if(e) return e; }
+	try {
+		float step = 0;
+		const uint32_t recipe = enc_in_recipe(m->position_bits, m->position_q, m->nvert, m->index ? m->nface : 0);
+		const bool raw_step = recipe == EIN_STEP_EDGE && rd.has_origin;
+		if(raw_step) { EncInputRecord r; input_stats_host(m, recipe, r, &rd); step = position_step(m, recipe, r); }
+		PackedMesh P;
+		pack_layout_host(m, extra, rd, P);
+		return encode_impl(&P.m, extra ? &P.list : nullptr, out, cap, out_nvert, out_nface, nullptr, raw_step ? &step : nullptr);
+	} catch(const std::bad_alloc &) {
+		return ctx_fail(CRTHIP_E_NOMEM, nullptr);
+	} catch(...) {
+		return ctx_fail(CRTHIP_E_ARGUMENT, "crthip_encode_layout: internal error");
+	}
 }
 
 // crthip_encode with the value coding (bit widths, bit packing) and the entropy coder on the device (encode_gpu.cpp)
@@ -1021,10 +1181,11 @@ void corto_hip::morton_order_host(const int32_t *coords, uint32_t nvert, std::ve
 	for(uint32_t i = 0; i < nvert; i++) order[i] = z[i].pos;
 }
 
-void corto_hip::batch_setup(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it, const float *step) {
+void corto_hip::batch_setup(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it, const float *step, const MeshRead *rd) {
 	Encoder E;
 	std::vector<NamedQuant> named;
-	setup(m, extra, E, named, false, step, false);
+	setup(m, extra, E, named, false, step, false, rd);
+	it.index16 = rd && rd->index16;
 	it.entropy = E.entropy; it.nvert_in = m->nvert; it.nface_in = E.nface;
 	it.attrs.clear();
 	for(auto &kv : E.data) {                                     // the container's order (std::map)

@@ -72,14 +72,21 @@ int encode_value_streams(crthip_ctx *ctx, uint32_t entropy, const std::vector<En
 
 // quantisation on the device (encode_gpu.cpp: k_enc_quantize): HOST arrays in, HOST arrays out, one upload / download for all of them.
 // kind: QK_FLOAT, QK_NORMAL, QK_COLOR, QK_INT (format: CRTHIP_FMT_INT32 / INT16 / INT8), QK_DOUBLE - device_plan.h
-struct QuantRequest { uint32_t kind = 0, count = 0, N = 1, format = CRTHIP_FMT_FLOAT; const void *in = nullptr; void *out = nullptr; float q = 0; int32_t unit = 0; uint32_t qc[4] = {1, 1, 1, 1}; };
-uint64_t quant_in_bytes(const QuantRequest &r);      // the raw input's bytes (format-aware)
+// stride / comps / flags / origin: how `in` is read through a crthip_mesh_layout (QuantJob's fields of the same names)
+struct QuantRequest { uint32_t kind = 0, count = 0, N = 1, format = CRTHIP_FMT_FLOAT; const void *in = nullptr; void *out = nullptr; float q = 0; int32_t unit = 0; uint32_t qc[4] = {1, 1, 1, 1};
+                      uint32_t stride = 0, comps = 1, flags = 0; float origin[3] = {0, 0, 0}; };
+uint64_t quant_in_bytes(const QuantRequest &r);      // the raw input's bytes when packed (format-aware)
+uint64_t quant_vertex_bytes(const QuantRequest &r);  // one vertex's bytes of the raw input
 uint64_t quant_out_bytes(const QuantRequest &r);     // the quantised values' bytes
 int quantize_device(crthip_ctx *ctx, const std::vector<QuantRequest> &reqs);
-inline QuantJob quant_job(const QuantRequest &r, const void *in, void *out) {   // the kernels' job (k_enc_quantize, k_enc_quantize_batch) of a request
+// the kernels' job (k_enc_quantize, k_enc_quantize_batch) of a request; packed: `in` is a packed copy of the request's array (a staged
+// upload), else the caller's array with the request's stride
+inline QuantJob quant_job(const QuantRequest &r, const void *in, void *out, bool packed = true) {
 	QuantJob J{};
 	J.in = in; J.out = out; J.count = r.count; J.kind = r.kind; J.N = r.N; J.q = r.q; J.unit = r.unit; J.format = r.format;
 	for(int c = 0; c < 4; c++) J.qc[c] = r.qc[c] ? r.qc[c] : 1u;
+	J.stride = packed || r.stride == quant_vertex_bytes(r) ? 0u : r.stride; J.comps = r.comps; J.flags = r.flags;
+	for(int c = 0; c < 3; c++) J.origin[c] = r.origin[c];
 	return J;
 }
 
@@ -93,11 +100,27 @@ struct EncStageTimes { float hist = 0, parse = 0, pack = 0, tables = 0, trie = 0
 int encode_value_streams_device(crthip_ctx *ctx, const std::vector<DevValueStream> &in, bool fetch, Coded &out, EncStageTimes &tm);
 void enc_report_times(crthip_kernel_times *times, const EncStageTimes &tm);   // appends the stages' entries behind times->count
 
+// ---- crthip_mesh_layout (encoder.cpp) ----
+// A layout resolved against its mesh: how every data array is read.  Strides are bytes and never 0 (a packed array's is one vertex's bytes).
+struct MeshRead {
+	bool plain = true;                                    // nothing differs from what crthip_mesh means by itself
+	bool index16 = false, normal16 = false, has_origin = false;
+	uint32_t position = 12, normal = 12, color = 0, uv = 8, radius = 4;
+	std::vector<uint32_t> attr;                           // one per entry of the mesh's crthip_attr_list
+	float origin[3] = {0, 0, 0};
+};
+uint32_t generic_esize(uint32_t format);                  // bytes of one element of a crthip_generic_attr
+// the rules of crthip_mesh_layout (sets the last error); m and extra have passed encode_check / encode_check_attrs
+int layout_resolve(const crthip_mesh *m, const crthip_attr_list *extra, const crthip_mesh_layout *layout, MeshRead &rd);
+// the index range check over HOST entries of either width
+int index_range_host(const crthip_mesh *m, const MeshRead &rd);
+EncInputJob enc_input_job(const crthip_mesh *m, const MeshRead *rd);   // position, index, sizes, recipe and the layout's fields; kind, partials, rec unset
+
 // ---- crthip_encode_batch (encoder.cpp: checks, topology pass and container; encode_batch.cpp: the device half) ----
 // encode_checked's argument checks (sets the last error); index_on_host == false: m->index is a DEVICE pointer, its entries are not read
 int encode_check(const crthip_mesh *m, bool index_on_host = true);
 // the position step's loops over the mesh's HOST arrays as setup runs them (recipe: enc_in_recipe), and the formulas over what they leave
-void input_stats_host(const crthip_mesh *m, uint32_t recipe, EncInputRecord &r);
+void input_stats_host(const crthip_mesh *m, uint32_t recipe, EncInputRecord &r, const MeshRead *rd = nullptr);   // rd: the arrays are read through it
 float position_step(const crthip_mesh *m, uint32_t recipe, const EncInputRecord &r);
 // the rules of crthip_encode_attrs's extra list (sets the last error); device: also the value coder's bound on nvert*components
 int encode_check_attrs(const crthip_mesh *m, const crthip_attr_list *extra, bool device);
@@ -117,6 +140,7 @@ struct BatchItem {
 	bool topo_device = false, topo_lds = false;           // meshes: the topology pass runs on the device / with its walk state in LDS
 	bool topo_image = false;                              // meshes: the CLERS symbols have their place in the chunk's device image (every mode but HOST)
 	uint32_t topo_groups = 1;                             // groups the device pass walks (a mesh given without groups: one)
+	bool index16 = false;                                 // meshes: the caller's index entries are uint16 (crthip_mesh_layout)
 	std::vector<uint32_t> split_words;
 	std::vector<uint8_t> frame;                           // the container without its streams
 	std::vector<BatchStream> streams;                     // where they belong in it, in order (a BORDER normal's count: 0 until the device has it)
@@ -124,7 +148,8 @@ struct BatchItem {
 // extra: the mesh's generic attributes (or null), checked by encode_check_attrs
 // position step + attribute table (after encode_check); step: the position step where the caller has it (crthip_encode_batch_resident:
 // from the device's record) - m's data arrays are then not read
-void batch_setup(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it, const float *step = nullptr);
+// rd: the mesh's resolved layout (or null): the requests carry its strides, origin and int16 flag, and a step computed here reads through it
+void batch_setup(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it, const float *step = nullptr, const MeshRead *rd = nullptr);
 void batch_topology(const crthip_mesh *m, const crthip_attr_list *extra, BatchItem &it);   // topology pass (meshes) + frame; reads the index alone
 // a mesh's frame from what the device topology pass reports (its record, the new group ends, the packed split words): header, counts,
 // groups, max_front and the stream slots, without running the pass
@@ -140,7 +165,7 @@ int encode_host_coded(const crthip_mesh *m, const crthip_attr_list *extra, HostC
 
 // the host encoder's topology pass alone (crthip_encode_topology_model, which = 0); split_bits before the final flush
 struct TopologyModel { std::vector<uint32_t> faces, group_end, quads, split_words; std::vector<uint8_t> clers; uint32_t nvert = 0, nface = 0, max_front = 0; uint64_t split_bits = 0; };
-void topology_host_model(const crthip_mesh *m, TopologyModel &out);
+void topology_host_model(const crthip_mesh *m, TopologyModel &out);   // (m->index: uint32)
 void morton_order_host(const int32_t *coords, uint32_t nvert, std::vector<uint32_t> &order);   // encode_cloud's std::sort of the Morton records
 
 // several blobs with HOST output buffers in one batch (batch.cpp): what crthip_decode_host is one of, and what the crt::Decoder facade's

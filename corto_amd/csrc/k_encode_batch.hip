@@ -1,6 +1,7 @@
 // k_encode_batch.hip — the per-vertex stages of crthip_encode_batch for gfx950: every mesh of a batch in one set of launches (each point cloud's sort in launches of its own).
 //
-//   K-ENC-Q      k_enc_quantize_batch   quantisation of every attribute of every mesh, from a job table (k_enc_quantize's recipes)
+//   K-ENC-Q      k_enc_quantize_batch   quantisation of every attribute of every mesh, from a job table (k_enc_quantize's recipes; a job with
+//                                       a stride, an origin or int16 normals reads the caller's array where it lies: enc_quant.h)
 //   K-ENC-EST    k_enc_corners          corners keyed by vertex for the incidence sort; BORDER's neighbour XORs (integer atomics)
 //                k_enc_est_normal       NormalAttr::preDelta (src/normal_attribute.cpp:113-143): the face normals of a vertex summed in
 //                                       INCREASING FACE ORDER - the corners were sorted stably by vertex, so a vertex's run of the sorted

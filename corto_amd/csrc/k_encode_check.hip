@@ -10,7 +10,8 @@
 //                                 order while the workgroup fills the other buffer
 //   k_enc_input_reduce   one wave per BOX item: its partials folded in block order onto the host's seed -> the record
 // Loads are 16 bytes wide where the caller's pointer allows: only element alignment is promised, so a lane's 48 bytes (an index
-// group's 16) are reached through a scalar head and tail when the array starts off a 16-byte boundary.  Nothing is read beyond
+// group's 16: four uint32 entries or eight uint16) are reached through a scalar head and tail when the array starts off a 16-byte
+// boundary; a strided position (crthip_mesh_layout) is one 16-byte load a vertex where base and stride are multiples of 16.  Nothing is read beyond
 // nvert*3 floats / nface*3 entries, nothing is gathered through an entry >= nvert, and the caller's arrays are never written.
 // No float atomics (k_encode_batch.hip's rule).
 #include "kernels_common.h"
@@ -45,22 +46,34 @@ __device__ __forceinline__ void wave_merge_in_lane_order(EncInputBox &b) {      
 	}
 }
 
-__device__ __forceinline__ void range_blocks(const EncInputJob &J, uint32_t b) {
-	const uint64_t n = (uint64_t)J.nface*3;
-	const uint32_t *ix = J.index;
-	const uint64_t to_boundary = (4u - (uint32_t)(((uintptr_t)ix >> 2) & 3u)) & 3u, head = to_boundary < n ? to_boundary : n;
-	const uint64_t groups = (n - head)/4, tail = n - head - groups*4;
+// PER entries of T in one 16-byte load: 4 uint32 or 8 uint16
+template <class T> __device__ __forceinline__ uint32_t group_bad(const T *p, uint32_t nvert);
+template <> __device__ __forceinline__ uint32_t group_bad<uint32_t>(const uint32_t *p, uint32_t nvert) {
+	const uint4 x = *(const uint4 *)p;
+	return (x.x >= nvert) | (x.y >= nvert) | (x.z >= nvert) | (x.w >= nvert);
+}
+template <> __device__ __forceinline__ uint32_t group_bad<uint16_t>(const uint16_t *p, uint32_t nvert) {
+	const uint4 x = *(const uint4 *)p;
+	const uint32_t w[4] = {x.x, x.y, x.z, x.w};
 	uint32_t bad = 0;
-	for(uint32_t p = 0; p < EIN_INDEX_TILE/4/EIN_THREADS; p++) {
+#pragma unroll
+	for(int k = 0; k < 4; k++) bad |= ((w[k] & 0xFFFFu) >= nvert) | ((w[k] >> 16) >= nvert);
+	return bad;
+}
+
+template <class T> __device__ __forceinline__ void range_blocks(const EncInputJob &J, uint32_t b) {
+	const uint64_t n = (uint64_t)J.nface*3;
+	const T *ix = (const T *)J.index;
+	uint32_t per; uint64_t head, groups, tail;
+	enc_in_range_cut(J, n, per, head, groups, tail);                             // (per == 16/sizeof(T): head and tail are below it)
+	uint32_t bad = 0;
+	for(uint32_t p = 0; p < EIN_INDEX_TILE/4/EIN_THREADS; p++) {                  // (uint16: the same trip count covers a tile's entries twice over)
 		const uint64_t g = (uint64_t)b*(EIN_INDEX_TILE/4) + p*EIN_THREADS + threadIdx.x;
-		if(g < groups) {
-			const uint4 x = *(const uint4 *)(ix + head + g*4);
-			bad |= (x.x >= J.nvert) | (x.y >= J.nvert) | (x.z >= J.nvert) | (x.w >= J.nvert);
-		}
+		if(g < groups) bad |= group_bad<T>(ix + head + g*per, J.nvert);
 	}
 	if(b == 0) {                                                                 // the entries before and behind the 16-byte groups
 		if(threadIdx.x < head) bad |= ix[threadIdx.x] >= J.nvert;
-		if(threadIdx.x >= 64 && threadIdx.x - 64 < tail) bad |= ix[head + groups*4 + (threadIdx.x - 64)] >= J.nvert;
+		if(threadIdx.x >= 64 && threadIdx.x - 64 < tail) bad |= ix[head + groups*per + (threadIdx.x - 64)] >= J.nvert;
 	}
 	if(bad) atomicOr(&J.rec->bad_index, 1u);
 }
@@ -70,7 +83,20 @@ __device__ __forceinline__ void box_block(const EncInputJob &J, uint32_t b, EncI
 	const float *p = J.position + v0*3;
 	float v[12];
 	uint32_t count = 0;
-	if(v0 + EIN_RUN <= J.nvert) {
+	if(J.pos_stride != 12) {
+		// a strided array: a vertex's record, one 16-byte load where base and stride keep every record on a boundary - but never the
+		// array's last vertex, whose record may end with its position (the checked extent does) - else three words
+		const bool wide = (((uintptr_t)J.position | J.pos_stride) & 15u) == 0;
+		count = v0 + EIN_RUN <= J.nvert ? EIN_RUN : v0 < J.nvert ? (uint32_t)(J.nvert - v0) : 0u;
+#pragma unroll
+		for(uint32_t r = 0; r < EIN_RUN; r++) {
+			if(r < count) {
+				const float *q = enc_in_vertex(J, v0 + r);
+				if(wide && v0 + r + 1 < J.nvert) { const float4 x = *(const float4 *)q; v[3*r] = x.x; v[3*r + 1] = x.y; v[3*r + 2] = x.z; }
+				else { v[3*r] = q[0]; v[3*r + 1] = q[1]; v[3*r + 2] = q[2]; }
+			} else v[3*r] = v[3*r + 1] = v[3*r + 2] = 0.0f;
+		}
+	} else if(v0 + EIN_RUN <= J.nvert) {
 		count = EIN_RUN;
 		switch((uint32_t)(((uintptr_t)J.position >> 2) & 3u)) {                  // (a lane's 48 bytes keep the array's offset from a boundary)
 		case 0: load12<0>(p, v); break;
@@ -82,6 +108,10 @@ __device__ __forceinline__ void box_block(const EncInputJob &J, uint32_t b, EncI
 		count = v0 < J.nvert ? (uint32_t)(J.nvert - v0) : 0u;
 #pragma unroll
 		for(int k = 0; k < 12; k++) v[k] = (uint32_t)k < count*3 ? p[k] : 0.0f;
+	}
+	if(J.has_origin) {
+#pragma unroll
+		for(int r = 0; r < (int)EIN_RUN; r++) enc_in_box_value(J, v + 3*r, v + 3*r);
 	}
 	EncInputBox box;
 	enc_in_box_run(box, v, count);
@@ -100,7 +130,7 @@ __device__ __forceinline__ void edge_block(const EncInputJob &J, float (*terms)[
 	double sum = 0;
 	auto fill = [&](uint32_t t) {
 		const uint32_t first = t*EIN_EDGE_TILE, cnt = min(EIN_EDGE_TILE, J.nface - first);
-		for(uint32_t i = threadIdx.x; i < cnt; i += EIN_THREADS) terms[t & 1][i] = enc_in_edge_term(J.position, J.index, first + i, J.nvert, bad);
+		for(uint32_t i = threadIdx.x; i < cnt; i += EIN_THREADS) terms[t & 1][i] = enc_in_edge_term(J, first + i, bad);
 	};
 	if(ntiles) fill(0);
 	__syncthreads();
@@ -131,7 +161,7 @@ __global__ __launch_bounds__(256) void k_enc_input_check(const EncInputJob *__re
 	const uint32_t j = enc_job_of(block_start, njobs, blockIdx.x);
 	const EncInputJob J = jobs[j];
 	const uint32_t b = blockIdx.x - block_start[j];
-	if(J.kind == EIN_JOB_RANGE) range_blocks(J, b);
+	if(J.kind == EIN_JOB_RANGE) { if(J.index16) range_blocks<uint16_t>(J, b); else range_blocks<uint32_t>(J, b); }
 	else if(J.kind == EIN_JOB_BOX) box_block(J, b, waves);
 	else edge_block(J, terms);
 }

@@ -43,7 +43,9 @@ extern "C" {
                                      crthip_batch_groups, crthip_batch_group_props, crthip_batch_walk_stats, crthip_batch_decode_with_next,
                                      crthip_batch_set_parity, crthip_encode_batch_resident, crthip_encode_input_model,
                                      crthip_encode_batch_to_device, crthip_encode_batch_bound, crthip_ctx_encode_splice_stats,
-                                     crthip_output_layout, crthip_pool_decode (crthip_pool_dest, crthip_pool_done_fn) */
+                                     crthip_output_layout, crthip_pool_decode (crthip_pool_dest, crthip_pool_done_fn), crthip_mesh_layout,
+                                     crthip_encode_layout, crthip_encode_batch_layout, crthip_encode_input_model_layout,
+                                     crthip_encode_topology_model_layout */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -662,8 +664,66 @@ int64_t crthip_encode_batch_to_device(crthip_ctx *ctx, uint32_t n, const crthip_
  * without its streams (header, attribute table, groups with their properties, exif) + CRTHIP_TOPOLOGY_CLERS_CAP(nface) symbols +
  * CRTHIP_TOPOLOGY_SPLIT_CAP(nface) words + per value stream count*N + 1 bit words (the value coder's own check) + per Tunstall block
  * 9 + 2*256 + size + 1 bytes (the Tunstall coder's own check; 4 + size under entropy NONE) + 15 bytes of padding.  A mesh the checks of
- * crthip_encode_batch would refuse from its descriptor contributes 0. */
+ * crthip_encode_batch would refuse from its descriptor contributes 0.
+ * The bound of crthip_encode_batch_layout is this one: a crthip_mesh_layout changes neither nvert nor nface nor any attribute's
+ * component count, and nothing else enters the sum. */
 uint64_t crthip_encode_batch_bound(uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra);
+
+/* ---- render-ready inputs (additions within ABI 6) ------------------------------------------------------------------
+ * How the DATA arrays of a crthip_mesh are read, for callers who keep their meshes in the form the decoder writes through
+ * crthip_attr_binding.stride: one interleaved vertex buffer (position f32x3, normal i16x3, uv f32x2, rgba8), a uint16 index.  The
+ * conversions are upstream's own, each ONE IEEE float operation:
+ *   CRTHIP_IN_INDEX_UINT16   Encoder::addPositions(buffer, const uint16_t *index, q, o), src/encoder.cpp:114-119: every entry widened to
+ *                            uint32.  The range check stays `entry >= nvert`; nvert may exceed 65536.  The array is 2-byte aligned.
+ *   CRTHIP_IN_NORMAL_INT16   Encoder::addNormals(const int16_t *, bits, prediction), src/encoder.cpp:151-158: each component becomes
+ *                            (float)v / 32767.0f, then the float path runs; the header's format byte stays FLOAT.  2-byte aligned.
+ *   origin                   the `o` of every addPositions overload, src/encoder.cpp:77-81: coords[i] = input[i] - o per component, in
+ *                            float, before quantisation.  A cloud's position_q == 0 recipe (the bounding box, :83-91) runs on input - o;
+ *                            a mesh's (the first edges, :101-111) on the raw positions.  Upstream's addPositionsBits has no origin:
+ *                            position_bits > 0 with a non-zero origin is CRTHIP_E_ARGUMENT, as is an origin that is not finite.
+ *   strides                  (no upstream counterpart: the mirror of crthip_attr_binding.stride) element i of an array lies at
+ *                            base + i*stride.  A stride is a multiple of the element's alignment - 4 for float / int32, 8 for double, 2 for
+ *                            int16, 1 for colours and int8 - and at least one vertex's bytes of that array (12 for a float position, 6 for
+ *                            an int16 normal, components * element size for a generic attribute), else CRTHIP_E_ARGUMENT.
+ * A blob is byte-identical to crthip_encode_attrs of the same data converted as above into packed arrays.  An all-zero layout (or a NULL
+ * one) is exactly what crthip_mesh means today. */
+#define CRTHIP_IN_INDEX_UINT16  1u   /* crthip_mesh.index points at nface*3 uint16_t */
+#define CRTHIP_IN_NORMAL_INT16  2u   /* crthip_mesh.normal points at int16_t triples */
+typedef struct {
+	uint32_t flags;                  /* the two bits above; any other bit: CRTHIP_E_ARGUMENT */
+	uint32_t position_stride, normal_stride, color_stride, uv_stride, radius_stride;
+	                                 /* bytes from one vertex to the next, 0 = packed */
+	const uint32_t *attr_stride;     /* NULL, or one stride per entry of the mesh's crthip_attr_list */
+	float origin[3];                 /* upstream's `o`: coords[i] = input[i] - o, per component, in float */
+} crthip_mesh_layout;
+/* crthip_encode_attrs on HOST arrays read through `layout` (NULL or all zero: crthip_encode_attrs' bytes).  A refused layout returns its code
+ * and writes nothing. */
+int64_t crthip_encode_layout(const crthip_mesh *mesh, const crthip_attr_list *extra, const crthip_mesh_layout *layout, uint8_t *out, size_t cap,
+                             uint32_t *out_nvert, uint32_t *out_nface);
+/* The batch encoder on arrays read through layouts[i] (layouts: n entries, or NULL for none).
+ *   flags   CRTHIP_ENCODE_INPUTS_RESIDENT: the data arrays are DEVICE arrays (the rules of crthip_encode_batch_resident), read WHERE THEY LIE:
+ *             nothing is de-interleaved, widened or staged on the device - enc_quantize_batch reads through the stride, subtracts the
+ *             origin and converts int16 normals; enc_input_check compares uint16 entries (16-byte groups of eight behind a scalar head and
+ *             tail), folds the box over strided positions minus the origin and gathers first edges through either index width;
+ *             enc_topo_compact reads either width.  The runtime's pointer queries cover the strided extent
+ *             [ptr, ptr + (nvert-1)*stride + one vertex's bytes) inside one allocation of the context's device, else CRTHIP_E_ARGUMENT in
+ *             status[i] and nothing is launched on that mesh.  A mesh whose topology pass runs on the host pool has its uint16 index
+ *             copied back as it is and widened there.
+ *             Clear: HOST arrays, packed by the staging copies; int16 normals and uint16 indices go up as they are and are converted by
+ *             the same kernels.
+ *           CRTHIP_ENCODE_OUTPUT_DEVICE: `out` is device memory and the blobs are spliced on the GPU, with the rules of
+ *             crthip_encode_batch_to_device's device_out.  Clear: `out` is HOST memory.
+ *           Any other bit: CRTHIP_E_ARGUMENT.
+ * Either way the result is laid out as crthip_encode_batch_to_device lays it out: blob i is the blob_len[i] bytes at out + blob_offset[i]
+ * (n entries each), the offsets are crthip_arena_layout's, the bytes up to the next 16-byte multiple are zeros, and the total is returned
+ * even when it exceeds cap (nothing is written then).  Per-mesh failures - crthip_encode_batch's, a refused layout, an index entry >= nvert -
+ * go into status[i] with blob_len[i] = 0; the neighbouring meshes are still encoded.  The three topology modes give the same bytes.
+ * When not to use it: INTEGRATION.md 3c. */
+#define CRTHIP_ENCODE_OUTPUT_DEVICE 2u
+int64_t crthip_encode_batch_layout(crthip_ctx *ctx, uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra /* n lists or NULL */,
+                                   const crthip_mesh_layout *layouts /* n or NULL */, uint32_t host_threads, uint32_t flags, void *out, size_t cap,
+                                   uint64_t *blob_offset /* n */, uint32_t *blob_len /* n */, uint32_t *out_nvert, uint32_t *out_nface,
+                                   int32_t *status, crthip_encode_batch_stats *stats, crthip_kernel_times *times);
 /* The splice of the last crthip_encode_batch_to_device on the context (all of its chunks). */
 typedef struct {
 	uint32_t pieces;             /* stretches of the arena with one source: a run of host-made bytes, or one payload on the device */
@@ -729,6 +789,12 @@ typedef struct {
 	uint32_t reserved;
 } crthip_encode_input_result;
 int crthip_encode_input_model(const crthip_mesh *m, int which, crthip_encode_input_result *r);
+/* (test hooks, no device needed)  The two models above with the mesh's HOST arrays read through a crthip_mesh_layout (NULL: as above):
+ * which = 0 the host loops, which = 1 the kernels' source in the kernels' partition - for a uint16 index the head, the 16-byte groups of
+ * eight and the tail of enc_input_check's range pass, and enc_topo_compact reading 16-bit entries.  A refused layout: CRTHIP_E_ARGUMENT,
+ * nothing written. */
+int crthip_encode_input_model_layout(const crthip_mesh *m, const crthip_mesh_layout *layout, int which, crthip_encode_input_result *r);
+int crthip_encode_topology_model_layout(const crthip_mesh *m, const crthip_mesh_layout *layout, int which, crthip_topology_result *r);
 
 /* (test hooks, no device needed)  The splice of crthip_encode_batch_to_device on the host.  crthip_encode_splice_model runs the host encoder
  * in its deferred mode, codes each recorded stream with the host encoder's own writers, then runs the plan and the mover of csrc/enc_splice.h
