@@ -58,7 +58,8 @@ class BatchStats(C.Structure):
                 ("total_nvert", C.c_uint64), ("total_nface", C.c_uint64), ("scratch_bytes", C.c_uint64),
                 ("clers_symbols", C.c_uint64), ("split_bytes", C.c_uint64), ("topology_fallbacks", C.c_uint64),
                 ("host_plan_us", C.c_float), ("host_stage_us", C.c_float), ("host_launch_us", C.c_float), ("host_create_us", C.c_float),
-                ("topology_scale", C.c_uint32), ("tunstall_dictionaries", C.c_uint32), ("delta_redone", C.c_uint32), ("delta_walked", C.c_uint32), ("delta_wide", C.c_uint32), ("descriptor_bytes", C.c_uint32), ("int16_streams", C.c_uint32)]
+                ("topology_scale", C.c_uint32), ("tunstall_dictionaries", C.c_uint32), ("delta_redone", C.c_uint32), ("delta_walked", C.c_uint32), ("delta_wide", C.c_uint32), ("descriptor_bytes", C.c_uint32), ("int16_streams", C.c_uint32),
+                ("upload_copies", C.c_uint32), ("upload_gathered_bytes", C.c_uint64)]
 
 
 class WalkStats(C.Structure):
@@ -150,7 +151,8 @@ class PoolReport(C.Structure):
                 ("failed_blobs", C.c_uint64), ("first_error", C.c_int32), ("devices_used", C.c_uint32),
                 ("steps_per_device", C.c_uint64 * 16), ("topology_fallbacks", C.c_uint64),
                 ("poisoned_lanes", C.c_uint32), ("pinned_devices", C.c_uint32), ("host_us_per_step", C.c_float), ("host_plan_max_us", C.c_float),
-                ("host_wait_us", C.c_float), ("host_finish_us", C.c_float), ("host_plan_us", C.c_float), ("host_launch_max_us", C.c_float)]
+                ("host_wait_us", C.c_float), ("host_finish_us", C.c_float), ("host_plan_us", C.c_float), ("host_launch_max_us", C.c_float),
+                ("grouped_steps", C.c_uint64)]
 
 
 class OutArray(C.Structure):
@@ -957,7 +959,8 @@ class Context:
         return s.as_dict()
 
     def set_packed_host_blobs(self, on: bool = True):
-        """blobs laid out as an arena in ONE pinned host buffer (pinned_host_arena) are uploaded straight from there (corto_hip.h)"""
+        """blobs laid out as an arena in pinned host memory (pinned_host_arena) are uploaded straight from there, one copy per run of blobs that
+        are adjacent in host memory - the views of two such buffers are two copies; beyond 8 runs the blobs are gathered (corto_hip.h)"""
         _check(lib().crthip_ctx_set_packed_host_blobs(self.handle, int(on)))
 
     def sync(self):
@@ -1359,7 +1362,8 @@ class Pool:
         return [int(x) for x in buf[:min(n, buf.size)]]
 
     def set_packed_host_blobs(self, on: bool = True):
-        """items run without device arenas whose blobs are views of ONE pinned host buffer (pinned_host_arena) go up straight from it"""
+        """items run without device arenas whose blobs are views of a pinned host buffer (pinned_host_arena) go up straight from it: a copy
+        per run of blobs adjacent in host memory, so a lane call that decodes a group of items uploads each from its own buffer"""
         _check(lib().crthip_pool_set_packed_host_blobs(self.handle, int(on)))
 
     def set_outputs_to_host(self, on: bool = True):

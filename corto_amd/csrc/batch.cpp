@@ -287,8 +287,9 @@ extern "C" int crthip_ctx_sync(crthip_ctx *c) {
 // ------------------------------------------------------------------------------------------------
 
 // (re)fill a batch object from a list of blobs: header parse + bounds-checked walk of each, arena layout, upload unless resident
+// (dev_off: null, or - device_arena set - where every blob lies relative to it; without it the blobs follow one another in arena layout)
 static int batch_fill(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs, const uint8_t *const *blobs, const uint32_t *lens,
-	const void *device_arena) {
+	const void *device_arena, const uint64_t *dev_off = nullptr) {
 	const double t_create = now_us();
 	b->ctx = ctx;
 	drop_staged(b);
@@ -304,7 +305,7 @@ static int batch_fill(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs, const u
 		reset_layout(P.L);
 		int err = walk_blob(blobs[i], lens[i], P.L);
 		if(err) return fail(err, std::string(crthip_strerror(err)) + " (blob " + std::to_string(i) + ")");
-		P.arena_off = off; P.len = lens[i];
+		P.arena_off = device_arena && dev_off ? dev_off[i] : off; P.len = lens[i];
 		P.bind.assign(P.L.h.attrs.size(), Binding{});
 		P.index = nullptr; P.index_u16 = 0; P.host_status = 0;
 		P.dbg_clers = P.dbg_pred = ~0ull; P.dbg_nclers = 0; P.clers_in_arena = false;
@@ -322,22 +323,32 @@ static int batch_fill(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs, const u
 		// read them - and nobody waits for it (round 3: the hipStreamSynchronize that stood here was 100 us of every from-host step, on the
 		// host thread): the image is this context's own buffer, reused only after harvest() has seen the batch it fed complete
 		if(harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE);
-		bool in_place = ctx->packed_host && nblobs > 0;                        // the caller's buffer IS the arena's image (corto_hip.h)
-		for(uint32_t i = 0; in_place && i < nblobs; i++) in_place = blobs[i] == blobs[0] + b->blobs[i].arena_off;
+		// packed host blobs (corto_hip.h): the caller's buffers ARE the arena's image, in pieces.  A run is a stretch of blobs that follow one another in
+		// host memory as they do in the arena; every run goes up with a copy of its own, straight from the caller's memory.  One run is one copy of
+		// one buffer; a pool lane's group of items is a run an item.  Beyond PACKED_RUNS_MAX runs the copies' own cost (a few us of enqueue and a DMA
+		// descriptor each) is no longer small beside the memcpy they save, and the blobs are gathered as if the switch were off
+		constexpr uint32_t PACKED_RUNS_MAX = 8;
+		uint32_t run_first[PACKED_RUNS_MAX], nruns = 0;
+		bool in_place = ctx->packed_host && nblobs > 0;
+		for(uint32_t i = 0; in_place && i < nblobs; i++) {
+			if(i && blobs[i] == blobs[i - 1] + (b->blobs[i].arena_off - b->blobs[i - 1].arena_off)) continue;
+			if(nruns == PACKED_RUNS_MAX) in_place = false; else run_first[nruns++] = i;
+		}
 		if(in_place) {
-			const uint64_t bytes = b->blobs[nblobs - 1].arena_off + lens[nblobs - 1];
-			// the copy below reads the caller's buffer whenever the DMA engine gets to it: nothing here snapshots it or waits (corto_hip.h:
-			// the
-			// caller keeps it alive and unchanged until the batch is synced).  A pageable buffer would still work (HIP stages it), a pinned
-			// one
-			// is what the switch promises: on request, check
-			if(ctx->dbg.check_pinned) {
-				hipPointerAttribute_t pa;
-				if(hipPointerGetAttributes(&pa, blobs[0]) != hipSuccess || pa.type != hipMemoryTypeHost) { (void)hipGetLastError();
-					return fail(CRTHIP_E_ARGUMENT, "packed host blobs: the buffer is not pinned host memory ($CORTO_HIP_CHECK_PINNED)"); }
+			// the copies below read the caller's buffers whenever the DMA engine gets to them: nothing here snapshots them or waits (corto_hip.h:
+			// the caller keeps them alive and unchanged until the batch is synced).  A pageable buffer would still work (HIP stages it), a pinned
+			// one is what the switch promises: on request, check
+			for(uint32_t r = 0; r < nruns; r++) {
+				const uint32_t i0 = run_first[r], i1 = r + 1 < nruns ? run_first[r + 1] : nblobs;
+				const uint64_t at = b->blobs[i0].arena_off, bytes = b->blobs[i1 - 1].arena_off + lens[i1 - 1] - at;
+				if(ctx->dbg.check_pinned) {
+					hipPointerAttribute_t pa;
+					if(hipPointerGetAttributes(&pa, blobs[i0]) != hipSuccess || pa.type != hipMemoryTypeHost) { (void)hipGetLastError();
+						return fail(CRTHIP_E_ARGUMENT, "packed host blobs: the buffer is not pinned host memory ($CORTO_HIP_CHECK_PINNED)"); }
+				}
+				if(hipMemcpyAsync((uint8_t *)b->own_arena.p + at, blobs[i0], bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(CRTHIP_E_DEVICE);
 			}
-			if(hipMemcpyAsync(b->own_arena.p, blobs[0], bytes, hipMemcpyHostToDevice,
-				ctx->stream) != hipSuccess) return fail(CRTHIP_E_DEVICE);
+			b->stats.upload_copies = nruns;
 		} else {
 		// (a batch that was created and not decoded yet: its upload has to be through before the image is reused)
 		if(ctx->arena_upload_pending) {
@@ -350,6 +361,7 @@ static int batch_fill(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs, const u
 		if(hipMemcpyAsync(b->own_arena.p, h, off, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(CRTHIP_E_DEVICE);
 		ctx->arena_upload_pending = true;
 		ctx->upload_seq++;
+		b->stats.upload_copies = 1; b->stats.upload_gathered_bytes = off;
 		}
 		b->d_arena = (const uint8_t *)b->own_arena.p;
 	}
@@ -377,6 +389,18 @@ extern "C" int crthip_batch_reset(crthip_batch *b, uint32_t nblobs, const uint8_
 	if(ctx->in_flight == b) { if(harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE); }
 	if(ctx->last_decoded == b) ctx->last_decoded = nullptr;
 	return batch_fill(ctx, b, nblobs, blobs, lens, device_arena);       // on failure the batch is left empty-handed: reset or destroy it
+}
+
+namespace corto_hip {
+// crthip_batch_reset for blobs resident in SEVERAL device arenas (a pool lane's group of items): blob i lies at device_base + dev_off[i]
+int batch_reset_at(crthip_batch *b, uint32_t nblobs, const uint8_t *const *blobs, const uint32_t *lens, const void *device_base, const uint64_t *dev_off) {
+	if(!b || !b->ctx || !nblobs || !blobs || !lens || !device_base || !dev_off) return fail(CRTHIP_E_ARGUMENT);
+	crthip_ctx *ctx = b->ctx;
+	HIP_TRY(hipSetDevice(ctx->device));
+	if(ctx->in_flight == b) { if(harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE); }
+	if(ctx->last_decoded == b) ctx->last_decoded = nullptr;
+	return batch_fill(ctx, b, nblobs, blobs, lens, device_base, dev_off);
+}
 }
 
 // (re)fill a batch object from blobs that live in device memory: k_walk_blobs walks them on the context's main stream (one wave and one

@@ -27,21 +27,31 @@ using corto_hip::ctx_fail;
 
 namespace {
 
-struct Slot {                       // a batch object and the item it is planned for
+// One item of a group: a Slot's batch object decodes up to `group` items (crthip_pool) as ONE batch, their blobs concatenated, first member first
+struct Member {
+	int64_t item = -1;              // the item
+	uint64_t step = 0;              // its global step number
+	uint32_t first = 0, nblobs = 0; // its blobs in the batch object
+	uint8_t *base = nullptr;        // the block its bindings point into: the lane's `out` + lane_off, or (crthip_pool_decode) the item's device destination
+	size_t lane_off = 0;            // member k's place in the lane's block (and its pinned mirror): k strides in
+	size_t out_used = 0;            // a member that ends with a D2H copy: the first out_used bytes of its part of the lane's block are copied behind the decode
+	bool to_host = false;           // ... it does: crthip_pool_set_outputs_to_host, or a host destination
+	void *pinned_dst = nullptr;     // crthip_pool_decode: the copy goes straight here (a pinned destination); else into the lane's pinned mirror,
+	void *pageable_dst = nullptr;   // ... from where the worker moves it here when it harvests the step
+};
+struct Ticket { uint32_t j = 0; uint64_t step = 0; bool solo = false; };   // a drawn item; solo: it was in a group that could not be planned and is planned alone
+struct Slot {                       // a batch object and the group of items it is planned for
 	crthip_batch *batch = nullptr;
-	// bindings of the item the batch object is planned for
+	std::vector<Member> mem;
+	std::vector<const uint8_t *> gblobs; std::vector<uint32_t> glens; std::vector<uint64_t> goff;   // a group of several: its members' blob lists, joined
+	// bindings of the items the batch object is planned for
 	std::vector<crthip_attr_binding> binds;
 	std::vector<void *> index_ptr;
 	std::vector<uint32_t> index_fmt;
 	std::vector<uint32_t> first_attr;            // first binding entry of blob i
 	std::vector<int32_t> status;
-	uint8_t *base = nullptr;        // the block the bindings point into: the lane's `out`, or (crthip_pool_decode) the item's device destination
-	size_t out_used = 0;            // a step that ends with a D2H copy: the first out_used bytes of the lane's `out` are copied behind the decode
-	bool to_host = false;           // ... it does: crthip_pool_set_outputs_to_host, or a host destination
-	void *pinned_dst = nullptr;     // crthip_pool_decode: the copy goes straight here (a pinned destination); else into the lane's pinned mirror,
-	void *pageable_dst = nullptr;   // ... from where the worker moves it here when it harvests the step
-	int64_t item = -1;              // the item
-	uint64_t step = 0;              // its global step number
+	int64_t item = -1;              // member 0's item (-1: planned for nothing)
+	uint64_t step = 0;              // the LAST member's global step number (the highest)
 };
 // One context = one call in flight.  A pipelined lane (crthip_batch_decode_with_next) holds TWO batch objects and one output block: s[cur] is the
 // batch whose mesh stage is in flight or ran last - the only one that writes `out` - and, `staged`, s[cur ^ 1] the next one, planned, uploaded and
@@ -54,12 +64,17 @@ struct Lane {
 	// A lane pipelines only while it pays: `pipe` - the batch it decoded last could be carried and could carry (a lane starts every run one batch a
 	// call); `drain` - the call just enqueued could NOT carry the planned batch, which then runs alone, whole, and the lane is back to one batch a call
 	bool pipe = false, drain = false;
+	// ... and groups only while that pays: `single_ok` - the last batch of ONE item it decoded was carriable (a pipelined lane's first batch of a run is
+	// one item, so it knows); `alone` - a group then came out not carriable (two items' dictionaries can be too many): one item a call for the rest of the run
+	bool single_ok = false, alone = false;
 	void *out = nullptr; size_t out_cap = 0;
 	void *host_out = nullptr; size_t host_cap = 0;   // outputs_to_host: the pinned mirror of `out`
 	bool busy = false;
 	bool poisoned = false;          // the output block was filled with POISON on the context's stream right before the mesh stage in flight / last executed
 };
 constexpr int POISON = 0xA5;
+constexpr uint32_t PACKED_RUNS_MAX = 8;   // batch.cpp's: packed host blobs in more runs than this are gathered on the worker thread
+constexpr uint32_t GROUP_MAX = 4;   // the most items a lane call decodes as one batch object ($CORTO_POOL_GROUP)
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -74,6 +89,11 @@ struct crthip_pool {
 	bool render = false;            // crthip_pool_set_render_layouts: int16 normals, uint16 index where the blob's vertex ids fit
 	bool to_host = false;           // crthip_pool_set_outputs_to_host: every step ends with a D2H copy of its outputs into the lane's pinned block
 	bool pipelined = false;         // every lane is a single-stream context and $CORTO_CARRY is not 0: the lanes run two batches each (Lane)
+	// Items a lane call decodes as one batch object.  A hardware queue runs one kernel at a time and a launch lasts as long as its slowest blob's
+	// chain, whatever the number of blobs: lanes that share queues pay a launch set's queue time once per GROUP (profiles/pool_group.md).  2 where
+	// the lanes are pipelined (they outnumber the queues), else 1; $CORTO_POOL_GROUP = 1 .. 4 overrides
+	uint32_t group = 1;
+	bool packed = false;            // crthip_pool_set_packed_host_blobs: the contexts upload runs of adjacent host blobs in place
 	size_t out_need = 0;            // the largest output block any item of the run asks for: a pipelined lane's block is not moved under a planned batch
 	bool decoded = false;           // the last call was crthip_pool_decode: the lanes hold nothing for crthip_pool_lane_item / _read
 	// state of one run
@@ -117,6 +137,8 @@ extern "C" int crthip_pool_create(uint32_t ndevices, const int *devices, uint32_
 	}
 	p->pipelined = true;
 	for(auto &L : p->lanes) p->pipelined = p->pipelined && corto_hip::ctx_pipelines(L.ctx);
+	p->group = p->pipelined ? 2u : 1u;
+	{ const char *e = getenv("CORTO_POOL_GROUP"); if(e && atoi(e) >= 1 && atoi(e) <= (int)GROUP_MAX) p->group = (uint32_t)atoi(e); }
 	for(auto &kv : ctx_per_gpu)
 		if(kv.second > hw_queues && p->warning.empty()) {
 			char buf[320];
@@ -180,6 +202,7 @@ extern "C" int crthip_pool_set_render_layouts(crthip_pool *p, int on) {
 extern "C" int crthip_pool_set_packed_host_blobs(crthip_pool *p, int on) {
 	if(!p) return ctx_fail(CRTHIP_E_ARGUMENT, nullptr);
 	for(auto &L : p->lanes) { const int err = crthip_ctx_set_packed_host_blobs(L.ctx, on); if(err) return err; }
+	p->packed = on != 0;
 	return CRTHIP_OK;
 }
 
@@ -199,6 +222,7 @@ struct ItemPlan {
 	uint64_t tris = 0, verts = 0;
 	std::vector<crthip_out_array> attr, index;   // sum(nattr) / nblobs entries
 	std::vector<uint32_t> first_attr;            // first attr entry of blob i
+	uint32_t runs = 0;                           // stretches of blobs adjacent in host memory in arena layout (batch.cpp: a copy each when packed host blobs are on)
 	// crthip_pool_decode
 	size_t status_at = 0;                        // the item's first entry in the call's status array
 	bool pinned = false;                         // a host destination that is pinned memory
@@ -211,6 +235,7 @@ static int item_plan(const crthip_pool *p, const crthip_pool_item &it, ItemPlan 
 	for(uint32_t i = 0; i < it.nblobs; i++) {
 		const int err = crthip_probe(it.blobs[i], it.lens[i], &info);
 		if(err) { P.err = err; P.err_msg = std::string(crthip_strerror(err)) + " (blob " + std::to_string(i) + ")"; return ctx_fail(err, P.err_msg.c_str()); }
+		if(i == 0 || it.blobs[i] != it.blobs[i - 1] + (((size_t)it.lens[i - 1] + 15) & ~(size_t)15)) P.runs++;
 		P.first_attr[i] = (uint32_t)P.attr.size();
 		P.attr.resize(P.attr.size() + info.nattr);
 		corto_hip::layout_blob(info, flags, off, P.attr.data() + P.first_attr[i], &P.index[i]);
@@ -220,51 +245,12 @@ static int item_plan(const crthip_pool *p, const crthip_pool_item &it, ItemPlan 
 	return CRTHIP_OK;
 }
 
-// plan `item` on one of the lane's batch objects and bind its outputs: into the lane's device block (`dest` null; the block holds at least
-// `block_need` bytes afterwards) or straight into `dest`.  *item_fault: the failure is the item's own - a blob the host walk refuses - and
+struct PoolJob;
+// plan the group S.mem (the members' item, step and destination filled in; one member is an item alone) on one of the lane's batch objects
+// and bind its outputs: member k into the lane's device block, k strides in (the block holds `group` strides and the call's slack
+// afterwards), or straight into its device destination.  *item_fault: the failure is an item's own - a blob the host walk refuses - and
 // the lane is as it was, but for an empty-handed batch object
-static int lane_plan(crthip_pool *p, Lane &L, Slot &S, const crthip_pool_item &it, int64_t item_id, const ItemPlan &P, uint8_t *dest,
-                     size_t block_need, bool *item_fault) {
-	const void *arena = it.device_arena ? it.device_arena[L.slot] : nullptr;
-	int err = CRTHIP_OK;
-	*item_fault = false;
-	if(!S.batch && &S == &L.s[1]) {                              // the lane's second object lives on the context's other set of per-call blocks
-		err = crthip_batch_create(L.ctx, 0, nullptr, nullptr, nullptr, &S.batch);
-		if(!err) err = crthip_batch_set_parity(S.batch, 1);
-		if(err) return err;
-	}
-	S.item = -1;
-	err = S.batch ? crthip_batch_reset(S.batch, it.nblobs, it.blobs, it.lens, arena)
-	              : crthip_batch_create(L.ctx, it.nblobs, it.blobs, it.lens, arena, &S.batch);
-	if(err) { *item_fault = err != CRTHIP_E_DEVICE && err != CRTHIP_E_NOMEM; return err; }
-	if(block_need > L.out_cap) {
-		// (never under a batch that is planned or running: out_need covers every item of the call, so a lane's block is made by its first plan)
-		if(L.busy || L.staged) return ctx_fail(CRTHIP_E_ARGUMENT, "corto_hip pool: a lane's output block would move under a planned batch");
-		if(L.out) (void)hipFree(L.out);
-		L.out = nullptr; L.out_cap = 0;
-		if(hipMalloc(&L.out, block_need + block_need/8) != hipSuccess) return ctx_fail(CRTHIP_E_NOMEM, nullptr);
-		L.out_cap = block_need + block_need/8;
-	}
-	S.base = dest ? dest : (uint8_t *)L.out;
-	S.first_attr = P.first_attr;
-	S.binds.resize(P.attr.size()); S.index_ptr.resize(it.nblobs); S.index_fmt.resize(it.nblobs);
-	for(size_t k = 0; k < P.attr.size(); k++) {
-		crthip_attr_binding &b = S.binds[k];
-		b.buffer = S.base + P.attr[k].offset; b.format = P.attr[k].format; b.stride = 0; b.reserved = 0;
-		b.out_components = P.attr[k].format == CRTHIP_FMT_UINT8 ? P.attr[k].out_components : 0;   // (colour: 4 of them, whatever the stream holds)
-	}
-	for(uint32_t i = 0; i < it.nblobs; i++) { S.index_ptr[i] = P.index[i].bytes ? S.base + P.index[i].offset : nullptr; S.index_fmt[i] = P.index[i].format; }
-	S.status.assign(it.nblobs, 0);
-	S.out_used = (size_t)P.total;
-	if(S.to_host && !S.pinned_dst && L.host_cap < L.out_cap) {   // (first use: 32 MB of pinned memory a lane for a C4 item)
-		if(L.host_out) (void)hipHostFree(L.host_out);
-		L.host_out = nullptr; L.host_cap = 0;
-		if(hipHostMalloc(&L.host_out, L.out_cap, hipHostMallocDefault) != hipSuccess) return ctx_fail(CRTHIP_E_NOMEM, nullptr);
-		L.host_cap = L.out_cap;
-	}
-	S.item = item_id;
-	return crthip_batch_bind_all(S.batch, S.binds.data(), S.index_ptr.data(), S.index_fmt.data());
-}
+static int lane_plan(crthip_pool *p, Lane &L, Slot &S, const PoolJob &job, bool *item_fault);
 
 // One call's work.  crthip_pool_run (dests null): warmup + steps + a tail of tickets, items drawn cyclically, every lane's block poisoned
 // in front of its last steps.  crthip_pool_decode (dests set): every item once, into its destination.  The workers, their pinning, the
@@ -282,6 +268,90 @@ struct PoolJob {
 	crthip_pool_done_fn done = nullptr; void *user = nullptr;
 };
 
+static int lane_plan(crthip_pool *p, Lane &L, Slot &S, const PoolJob &job, bool *item_fault) {
+	const bool dec = job.dests != nullptr;
+	const size_t n = S.mem.size();
+	const crthip_pool_item &it0 = job.items[S.mem[0].item];
+	const ItemPlan &P0 = job.plans[(size_t)S.mem[0].item];
+	int err = CRTHIP_OK;
+	*item_fault = false;
+	if(!S.batch && (&S == &L.s[1] || n > 1)) {                   // the lane's second object lives on the context's other set of per-call blocks
+		err = crthip_batch_create(L.ctx, 0, nullptr, nullptr, nullptr, &S.batch);
+		if(!err && &S == &L.s[1]) err = crthip_batch_set_parity(S.batch, 1);
+		if(err) return err;
+	}
+	S.item = -1;
+	uint32_t nblobs = it0.nblobs;
+	if(n == 1) {
+		const void *arena = it0.device_arena ? it0.device_arena[L.slot] : nullptr;
+		err = S.batch ? crthip_batch_reset(S.batch, it0.nblobs, it0.blobs, it0.lens, arena)
+		              : crthip_batch_create(L.ctx, it0.nblobs, it0.blobs, it0.lens, arena, &S.batch);
+	} else {
+		// the members' blob lists, joined.  Host blobs: packed ones go up as a run a member (crthip_ctx_set_packed_host_blobs).  Resident blobs (every
+		// member has an arena on this device, or none has: the draw sees to it): the lowest arena is the batch's, the others' blobs lie 64-bit offsets above it
+		S.gblobs.clear(); S.glens.clear(); S.goff.clear();
+		const uint8_t *lowest = nullptr;
+		for(const Member &m : S.mem) {
+			const crthip_pool_item &it = job.items[m.item];
+			const uint8_t *a = it.device_arena ? (const uint8_t *)it.device_arena[L.slot] : nullptr;
+			if(a && (!lowest || a < lowest)) lowest = a;
+		}
+		for(const Member &m : S.mem) {
+			const crthip_pool_item &it = job.items[m.item];
+			uint64_t off = lowest ? (uint64_t)((const uint8_t *)it.device_arena[L.slot] - lowest) : 0;
+			for(uint32_t i = 0; i < it.nblobs; i++) {
+				S.gblobs.push_back(it.blobs[i]); S.glens.push_back(it.lens[i]);
+				if(lowest) { S.goff.push_back(off); off += ((uint64_t)it.lens[i] + 15) & ~15ull; }
+			}
+		}
+		nblobs = (uint32_t)S.gblobs.size();
+		err = lowest ? corto_hip::batch_reset_at(S.batch, nblobs, S.gblobs.data(), S.glens.data(), lowest, S.goff.data())
+		             : crthip_batch_reset(S.batch, nblobs, S.gblobs.data(), S.glens.data(), nullptr);
+	}
+	if(err) { *item_fault = err != CRTHIP_E_DEVICE && err != CRTHIP_E_NOMEM; return err; }
+	const size_t stride = (p->out_need + 255) & ~(size_t)255;
+	const size_t block_need = (size_t)(p->group - 1)*stride + (dec ? p->out_need : std::max((size_t)P0.total + 256, p->out_need));
+	if(block_need > L.out_cap) {
+		// (never under a batch that is planned or running: out_need covers every item of the call, so a lane's block is made by its first plan)
+		if(L.busy || L.staged) return ctx_fail(CRTHIP_E_ARGUMENT, "corto_hip pool: a lane's output block would move under a planned batch");
+		if(L.out) (void)hipFree(L.out);
+		L.out = nullptr; L.out_cap = 0;
+		if(hipMalloc(&L.out, block_need + block_need/8) != hipSuccess) return ctx_fail(CRTHIP_E_NOMEM, nullptr);
+		L.out_cap = block_need + block_need/8;
+	}
+	S.first_attr.clear(); S.binds.clear(); S.index_ptr.clear(); S.index_fmt.clear();
+	bool mirror = false;
+	uint32_t first = 0;
+	for(size_t k = 0; k < n; k++) {
+		Member &m = S.mem[k];
+		const crthip_pool_item &it = job.items[m.item];
+		const ItemPlan &P = job.plans[(size_t)m.item];
+		m.first = first; m.nblobs = it.nblobs; first += it.nblobs;
+		m.lane_off = k*stride;
+		if(!m.base) m.base = (uint8_t *)L.out + m.lane_off;
+		m.out_used = (size_t)P.total;
+		mirror = mirror || (m.to_host && !m.pinned_dst);
+		const uint32_t attr0 = (uint32_t)S.binds.size();
+		for(uint32_t f : P.first_attr) S.first_attr.push_back(attr0 + f);
+		for(size_t a = 0; a < P.attr.size(); a++) {
+			crthip_attr_binding b;
+			b.buffer = m.base + P.attr[a].offset; b.format = P.attr[a].format; b.stride = 0; b.reserved = 0;
+			b.out_components = P.attr[a].format == CRTHIP_FMT_UINT8 ? P.attr[a].out_components : 0;   // (colour: 4 of them, whatever the stream holds)
+			S.binds.push_back(b);
+		}
+		for(uint32_t i = 0; i < it.nblobs; i++) { S.index_ptr.push_back(P.index[i].bytes ? m.base + P.index[i].offset : nullptr); S.index_fmt.push_back(P.index[i].format); }
+	}
+	S.status.assign(nblobs, 0);
+	if(mirror && L.host_cap < L.out_cap) {                        // (first use: 32 MB of pinned memory a lane for a C4 item)
+		if(L.host_out) (void)hipHostFree(L.host_out);
+		L.host_out = nullptr; L.host_cap = 0;
+		if(hipHostMalloc(&L.host_out, L.out_cap, hipHostMallocDefault) != hipSuccess) return ctx_fail(CRTHIP_E_NOMEM, nullptr);
+		L.host_cap = L.out_cap;
+	}
+	S.item = S.mem[0].item; S.step = S.mem[n - 1].step;
+	return crthip_batch_bind_all(S.batch, S.binds.data(), S.index_ptr.data(), S.index_fmt.data());
+}
+
 static int pool_work(crthip_pool *p, PoolJob &job, crthip_pool_report *report) {
 	const uint32_t nitems = job.nitems;
 	const crthip_pool_item *items = job.items;
@@ -291,10 +361,10 @@ static int pool_work(crthip_pool *p, PoolJob &job, crthip_pool_report *report) {
 	// the tail keeps every context busy until the last timed completion (a pipelined lane has two tickets drawn and not completed)
 	const uint64_t total = dec ? nitems : timed_end + p->lanes.size()*(p->pipelined ? 2u : 1u);
 	p->next = 0; p->completed = 0; p->error = CRTHIP_OK; p->error_msg.clear();
-	for(auto &L : p->lanes) { L.busy = false; L.staged = false; L.poisoned = false; L.pipe = false; L.drain = false; for(Slot &S : L.s) { S.item = -1; S.binds.clear(); } }   // (an item id means this call's items[] only; `poisoned` a mesh stage of this run)
+	for(auto &L : p->lanes) { L.busy = false; L.staged = false; L.poisoned = false; L.pipe = false; L.drain = false; L.single_ok = false; L.alone = false; for(Slot &S : L.s) { S.item = -1; S.binds.clear(); S.mem.clear(); } }   // (an item id means this call's items[] only; `poisoned` a mesh stage of this run)
 	const bool pipe = p->pipelined;
 	std::vector<double> stamps(timed_end + 1, 0.0);           // stamps[c] = time at which the c-th completion happened (1-based)
-	std::atomic<uint64_t> failed{0}, fallbacks{0}, tris{0}, verts{0};
+	std::atomic<uint64_t> failed{0}, fallbacks{0}, tris{0}, verts{0}, grouped{0};
 	std::vector<std::atomic<uint64_t>> per_dev(p->ndevices);
 	for(auto &x : per_dev) x = 0;
 	std::atomic<int32_t> first_error{0};
@@ -339,10 +409,11 @@ static int pool_work(crthip_pool *p, PoolJob &job, crthip_pool_report *report) {
 		}
 		Lane *mine = &p->lanes[((size_t)slot*p->threads_per_device + t)*p->depth];
 		// crthip_pool_decode: item j is final - `code` in every status entry (it could not be planned, or holds no blob), or S's statuses
-		auto settle = [&](uint32_t j, int32_t code, const Slot *S) {
+		// (the statuses of its blobs, which begin at `first` in the group's batch object)
+		auto settle = [&](uint32_t j, int32_t code, const Slot *S, uint32_t first) {
 			const ItemPlan &P = job.plans[j];
 			int32_t *st = job.status + P.status_at;
-			for(uint32_t i = 0; i < items[j].nblobs; i++) st[i] = S ? S->status[i] : code;
+			for(uint32_t i = 0; i < items[j].nblobs; i++) st[i] = S ? S->status[first + i] : code;
 			if(!S) {
 				++p->completed;
 				if(code) { failed += items[j].nblobs; int32_t z = 0; first_error.compare_exchange_strong(z, code); }
@@ -354,19 +425,24 @@ static int pool_work(crthip_pool *p, PoolJob &job, crthip_pool_report *report) {
 			Slot &S = L.s[L.cur];
 			const int rc = crthip_batch_sync(S.batch, S.status.data());
 			L.busy = false;
-			const uint64_t c = ++p->completed;                   // completion order
-			if(c <= timed_end) stamps[c] = now_s();
+			// every member of the group is a step of its own: a completion and a stamp each (the same instant), counted by its own step number
+			const double t_done = now_s();
+			if(S.mem.size() > 1) grouped += S.mem.size();
+			for(const Member &m : S.mem) {
+				const uint64_t c = ++p->completed;               // completion order
+				if(c <= timed_end) stamps[c] = t_done;
+				if(!dec && m.step >= warmup && m.step < timed_end) { per_dev[slot]++; tris += job.plans[(size_t)m.item].tris; verts += job.plans[(size_t)m.item].verts; }
+			}
 			uint64_t bad = 0;
 			for(int32_t st_ : S.status) if(st_) { bad++; int32_t z = 0; first_error.compare_exchange_strong(z, st_); }
 			failed += bad;
 			crthip_batch_stats st;
 			if(crthip_batch_get_stats(S.batch, &st) == CRTHIP_OK) fallbacks += st.topology_fallbacks;
-			if(!dec && c > warmup && c <= timed_end) { per_dev[slot]++; tris += job.plans[(size_t)S.item].tris; verts += job.plans[(size_t)S.item].verts; }
 			if(rc == CRTHIP_E_DEVICE || rc == CRTHIP_E_NOMEM) return rc;
-			if(dec) {
-				if(S.pageable_dst) memcpy(S.pageable_dst, L.host_out, S.out_used);   // (the copy into the lane's mirror is what the sync waited for)
-				tris += job.plans[(size_t)S.item].tris; verts += job.plans[(size_t)S.item].verts;
-				settle((uint32_t)S.item, 0, &S);
+			if(dec) for(const Member &m : S.mem) {
+				if(m.pageable_dst) memcpy(m.pageable_dst, (const uint8_t *)L.host_out + m.lane_off, m.out_used);   // (the copy into the lane's mirror is what the sync waited for)
+				tris += job.plans[(size_t)m.item].tris; verts += job.plans[(size_t)m.item].verts;
+				settle((uint32_t)m.item, 0, &S, m.first);
 			}
 			return CRTHIP_OK;
 		};
@@ -377,15 +453,54 @@ static int pool_work(crthip_pool *p, PoolJob &job, crthip_pool_report *report) {
 			if(!due || !L.out) return CRTHIP_OK;
 			const int e = corto_hip::ctx_fill_async(L.ctx, L.out, L.out_cap, POISON);
 			if(e) return e;
-			if(p->to_host && L.host_out) memset(L.host_out, POISON, L.s[L.cur].out_used);
+			if(p->to_host && L.host_out) for(const Member &m : L.s[L.cur].mem) memset((uint8_t *)L.host_out + m.lane_off, POISON, m.out_used);
 			L.poisoned = true;
 			return CRTHIP_OK;
 		};
 		// the D2H copy behind the mesh stage just enqueued: a step of outputs_to_host, an item with a host destination
 		auto copy_out = [&](Lane &L, Slot &S) -> int {
-			if(!S.to_host) return CRTHIP_OK;
-			return corto_hip::ctx_copy_to_host_async(L.ctx, S.pinned_dst ? S.pinned_dst : L.host_out, L.out, S.out_used);
+			for(const Member &m : S.mem) {                       // (one copy a member: each has its own destination)
+				if(!m.to_host) continue;
+				const int e = corto_hip::ctx_copy_to_host_async(L.ctx, m.pinned_dst ? m.pinned_dst : (uint8_t *)L.host_out + m.lane_off, (const uint8_t *)L.out + m.lane_off, m.out_used);
+				if(e) return e;
+			}
+			return CRTHIP_OK;
 		};
+		// a drawn ticket as a group member: where its outputs go
+		auto member_of = [&](const Ticket &k) {
+			Member m;
+			m.item = (int64_t)k.j; m.step = k.step; m.to_host = p->to_host;
+			if(dec) {
+				const crthip_pool_dest &D = job.dests[k.j];
+				m.to_host = D.device_slot < 0;
+				if(!m.to_host) m.base = (uint8_t *)D.out;
+				else if(job.plans[k.j].pinned) m.pinned_dst = D.out;
+				else m.pageable_dst = D.out;
+			}
+			return m;
+		};
+		// one ticket from the work lists.  0: none left; 1: `k` is drawn; 2 (crthip_pool_decode): an item with nothing to launch was drawn and settled
+		auto draw = [&](Ticket &k) -> int {
+			k.solo = false;
+			if(!dec) {
+				k.step = p->next.fetch_add(1);
+				if(k.step >= total) return 0;
+				if(!home[slot].empty()) k.j = home[slot][home_next[slot].fetch_add(1) % home[slot].size()];
+				else k.j = (uint32_t)(stolen.fetch_add(1) % nitems);
+				return 1;
+			}
+			if(p->next.load() >= total || !draw_once(slot, k.j)) return 0;
+			k.step = p->next.fetch_add(1);
+			if(job.plans[k.j].err || items[k.j].nblobs == 0) { settle(k.j, job.plans[k.j].err, nullptr, 0); return 2; }
+			return 1;
+		};
+		auto resident = [&](uint32_t j) { return items[j].device_arena && items[j].device_arena[slot]; };
+		// Blobs that must be gathered (scattered host blobs, or packed host blobs off) are not grouped: the gathering is a memcpy on this thread
+		// while its other lanes wait, and two items' worth of it in one piece cost `scattered_pageable_blobs` 29 % (profiles/pool_group.md)
+		auto runs_of = [&](uint32_t j) { return resident(j) ? 0u : p->packed ? job.plans[j].runs : PACKED_RUNS_MAX + 1; };
+		// `held` is consumed before the work lists and `tickets` goes false only when it is empty and the lists are dry: no drawn ticket is lost.
+		// Solo tickets (a refused group's members) and tickets that did not fit a group wait here alike; a solo one is never joined to a group
+		std::vector<Ticket> held;                                // drawn and not planned yet: a ticket that did not fit the group it was drawn for, the members of a group that was refused
 		int err = CRTHIP_OK;
 		auto tick = [] { return std::chrono::steady_clock::now(); };
 		auto ns_since = [](std::chrono::steady_clock::time_point t0) { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); };
@@ -411,7 +526,11 @@ static int pool_work(crthip_pool *p, PoolJob &job, crthip_pool_report *report) {
 			const auto f0 = tick();
 			if(L.busy) err = finish(L);
 			finish_ns += ns_since(f0);
-			if(!err && pipe && !L.staged && L.s[L.cur].item >= 0) L.pipe = corto_hip::batch_carriable(L.s[L.cur].batch);
+			if(!err && pipe && !L.staged && L.s[L.cur].item >= 0) {
+				L.pipe = corto_hip::batch_carriable(L.s[L.cur].batch);
+				if(L.s[L.cur].mem.size() == 1) L.single_ok = L.pipe;
+				else if(!L.pipe && L.single_ok) L.alone = true;   // (one item a call pipelines again)
+			}
 			if(!err && L.staged && L.drain) {                   // the planned batch was not carried: its whole decode alone, no ticket drawn
 				L.cur ^= 1u; L.staged = false; L.drain = false; L.pipe = false;
 				err = poison(L, L.s[L.cur].step >= poison_from);
@@ -424,37 +543,49 @@ static int pool_work(crthip_pool *p, PoolJob &job, crthip_pool_report *report) {
 			// (crthip_pool_decode: the two objects are then bound to two different items' blocks.  That is safe: an entropy stage writes its
 			// batch's own scratch and nothing else - corto_hip.h, crthip_batch_decode_with_next - so only the mesh stage in flight writes a block.)
 			while(!err && !L.busy) {
-				uint64_t step;
-				uint32_t j;
-				if(!dec) {
-					step = p->next.fetch_add(1);
-					if(step >= total) { tickets = false; break; }
-					if(!home[slot].empty()) j = home[slot][home_next[slot].fetch_add(1) % home[slot].size()];
-					else j = (uint32_t)(stolen.fetch_add(1) % nitems);
-				} else {
-					if(p->next.load() >= total || !draw_once(slot, j)) { tickets = false; break; }
-					step = p->next.fetch_add(1);
-					if(job.plans[j].err || items[j].nblobs == 0) { settle(j, job.plans[j].err, nullptr); continue; }   // nothing to launch
+				// the group: a first ticket, then up to group - 1 more while the lists are long - at least 2 x lanes x group tickets undrawn, so that the end
+				// of a run and a short crthip_pool_decode still spread over all lanes, one item a call.  Members are all resident on this device or all
+				// uploaded; crthip_pool_decode's lists hold this slot's own device-destination items and host items only, so no group mixes slots
+				Ticket tk[GROUP_MAX];
+				uint32_t ntk = 0;
+				if(!held.empty()) { tk[0] = held.front(); held.erase(held.begin()); ntk = 1; }
+				else {
+					const int d = draw(tk[0]);
+					if(d == 0) { tickets = false; break; }
+					if(d == 2) continue;
+					ntk = 1;
+				}
+				const bool first_batch = pipe && !L.staged && L.s[L.cur].item < 0;      // (of this lane in this run: one item, to learn whether such a batch can be carried)
+				uint32_t runs = runs_of(tk[0].j);
+				const uint32_t want = tk[0].solo || L.alone || first_batch || runs > PACKED_RUNS_MAX ? 1u : p->group;
+				while(ntk < want) {
+					Ticket x;
+					if(!held.empty()) { if(held.front().solo) break; x = held.front(); held.erase(held.begin()); }
+					else {
+						const uint64_t nx = p->next.load();
+						if(nx >= total || total - nx < 2ull*p->lanes.size()*p->group) break;
+						const int d = draw(x);
+						if(d == 0) break;
+						if(d == 2) continue;
+					}
+					if(resident(x.j) != resident(tk[0].j) || runs + runs_of(x.j) > PACKED_RUNS_MAX) { held.push_back(x); break; }
+					runs += runs_of(x.j);
+					tk[ntk++] = x;
 				}
 				const auto h0 = std::chrono::steady_clock::now();
 				const bool lp = pipe && (L.pipe || L.staged);                          // this refill pipelines
 				const uint32_t t = lp ? (L.staged ? L.cur : L.cur ^ 1u) : L.cur;        // the free batch object
 				Slot &T = L.s[t];
-				const ItemPlan &P = job.plans[j];
-				uint8_t *dest = nullptr;
-				T.to_host = p->to_host; T.pinned_dst = nullptr; T.pageable_dst = nullptr;
-				if(dec) {
-					const crthip_pool_dest &D = job.dests[j];
-					T.to_host = D.device_slot < 0;
-					if(!T.to_host) dest = (uint8_t *)D.out;
-					else if(P.pinned) T.pinned_dst = D.out;
-					else T.pageable_dst = D.out;
-				}
+				T.mem.clear();
+				for(uint32_t k = 0; k < ntk; k++) T.mem.push_back(member_of(tk[k]));
 				bool item_fault = false;
-				err = lane_plan(p, L, T, items[j], (int64_t)j, P, dest, dec ? p->out_need : std::max((size_t)P.total + 256, p->out_need), &item_fault);
-				T.step = step;
+				err = lane_plan(p, L, T, job, &item_fault);
 				{ const uint64_t ns_ = ns_since(h0); plan_ns += ns_; raise_max(plan_max_ns, ns_); }
-				if(err && dec && item_fault) { settle(j, err, nullptr); err = CRTHIP_OK; continue; }   // the item's own failure: the lane draws the next one
+				if(err && item_fault && ntk > 1) {                   // one member's own failure: each of them alone, so that the bad item alone gets the code
+					for(uint32_t k = 0; k < ntk; k++) { tk[k].solo = true; held.push_back(tk[k]); }
+					err = CRTHIP_OK; continue;
+				}
+				if(err && dec && item_fault) { settle(tk[0].j, err, nullptr, 0); err = CRTHIP_OK; continue; }   // the item's own failure: the lane draws the next one
 				if(err) break;
 				const auto d0 = std::chrono::steady_clock::now();
 				if(lp && !L.staged) {
@@ -470,7 +601,7 @@ static int pool_work(crthip_pool *p, PoolJob &job, crthip_pool_report *report) {
 					if(!err) L.busy = true;
 				}
 				raise_max(launch_max_ns, ns_since(d0));
-				host_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - h0).count(); host_steps++;
+				host_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - h0).count(); host_steps += ntk;   // (per ticket)
 			}
 		}
 		for(uint32_t k = 0; k < p->depth; k++) if(mine[k].busy) { const int e2 = finish(mine[k]); if(!err) err = e2; }
@@ -494,11 +625,13 @@ static int pool_work(crthip_pool *p, PoolJob &job, crthip_pool_report *report) {
 			if(S.item < 0) {                                     // ... and one that drew no ticket at all (a 28-step run on a cold box) decodes its device's first item
 				const uint32_t j = home[slot].empty() ? 0u : home[slot][0];
 				bool item_fault = false;
-				S.to_host = p->to_host; S.pinned_dst = nullptr; S.pageable_dst = nullptr;
-				err = lane_plan(p, L, S, items[j], (int64_t)j, job.plans[j], nullptr, std::max((size_t)job.plans[j].total + 256, p->out_need), &item_fault);
+				Ticket k0; k0.j = j; k0.step = total;
+				S.mem.assign(1, member_of(k0));
+				err = lane_plan(p, L, S, job, &item_fault);
 				if(err) break;
 			}
 			if(L.poisoned || !L.out) continue;
+			for(Member &m : S.mem) m.step = total;               // (a repeat is nobody's timed step)
 			err = poison(L, true);
 			if(!err) err = crthip_batch_decode(S.batch);
 			if(!err) err = copy_out(L, S);
@@ -520,7 +653,7 @@ static int pool_work(crthip_pool *p, PoolJob &job, crthip_pool_report *report) {
 	if(!report) return CRTHIP_OK;
 	report->elapsed_s = dec ? t_joined - t_launch : stamps[timed_end] - stamps[warmup];
 	report->steps = dec ? nitems : steps; report->triangles = tris; report->vertices = verts;
-	report->failed_blobs = failed; report->first_error = first_error; report->topology_fallbacks = fallbacks;
+	report->failed_blobs = failed; report->first_error = first_error; report->topology_fallbacks = fallbacks; report->grouped_steps = grouped;
 	for(uint32_t d = 0; d < p->ndevices; d++) { report->steps_per_device[d] = per_dev[d]; if(per_dev[d]) report->devices_used++; }
 	if(!dec) for(auto &L : p->lanes) if(L.s[L.cur].item >= 0 && L.poisoned) report->poisoned_lanes++;
 	report->host_us_per_step = host_steps ? (float)((double)host_ns/1e3/(double)host_steps) : 0.f;
@@ -547,7 +680,7 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 		const int err = item_plan(p, items[j], job.plans[j]);
 		if(err) return err;
 		// (crthip_pool_run's own 256 bytes behind the block: what "#tail" reads)
-		if(p->pipelined) p->out_need = std::max(p->out_need, (size_t)job.plans[j].total + 256);
+		if(p->pipelined || p->group > 1) p->out_need = std::max(p->out_need, (size_t)job.plans[j].total + 256);
 	}
 	p->decoded = false;
 	return pool_work(p, job, report);

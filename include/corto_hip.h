@@ -45,7 +45,8 @@ extern "C" {
                                      crthip_encode_batch_to_device, crthip_encode_batch_bound, crthip_ctx_encode_splice_stats,
                                      crthip_output_layout, crthip_pool_decode (crthip_pool_dest, crthip_pool_done_fn), crthip_mesh_layout,
                                      crthip_encode_layout, crthip_encode_batch_layout, crthip_encode_input_model_layout,
-                                     crthip_encode_topology_model_layout */
+                                     crthip_encode_topology_model_layout; crthip_batch_stats and crthip_pool_report grew at their ends
+                                     (upload_copies, upload_gathered_bytes; grouped_steps) */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -153,12 +154,17 @@ void crthip_ctx_destroy(crthip_ctx *ctx);
  * The same switch selects the LDS-lean layout of the normals kernel (29 KB instead of 78 KB per blob: slower alone, but with many
  * batches in flight a kernel's wait for LDS is what its latency is made of: +10 %). */
 int crthip_ctx_set_single_stream(crthip_ctx *ctx, int on);
-/* Blobs that already sit in ONE pinned host buffer (hipHostMalloc / hipHostRegister / torch pin_memory), laid out as
- * crthip_arena_layout says (blob i at blobs[0] + offset i): with this switch on, crthip_batch_create / _reset upload them with one
- * DMA copy straight from there - no gathering into the library's own pinned image first (3.7 MB of memcpy per C4 batch: 150 us of a
- * from-host step's host time).  The caller's promise: the buffer stays valid and unchanged until the batch has been synced.  Blob
- * pointers that are NOT laid out that way take the gathering path as before, whatever the switch says.  (No reference counterpart:
- * crt::Decoder reads its one blob from the caller's memory in place, src/decoder.cpp:41-48.) */
+/* Blobs that already sit in pinned host memory (hipHostMalloc / hipHostRegister / torch pin_memory) in the arena's own layout: with this
+ * switch on, crthip_batch_create / _reset upload them straight from there - no gathering into the library's own pinned image first (3.7 MB
+ * of memcpy per C4 batch: 150 us of a from-host step's host time).  The blob list is cut into RUNS: a run is a stretch of consecutive
+ * blobs that follow one another in host memory as crthip_arena_layout places them (blob i + 1 at blob i + its length rounded up to 16).
+ * Every run goes up with ONE DMA copy from the caller's memory to its place in the device arena.  All blobs in one buffer laid out by
+ * crthip_arena_layout are one run and one copy; the blobs of two such buffers, one list after the other, are two.  A list that falls
+ * into more than 8 runs takes the gathering path, as does every list while the switch is off (crthip_batch_stats: upload_copies,
+ * upload_gathered_bytes say which path ran).  The caller's promise, for EVERY buffer a run lies in: it stays valid and unchanged until the
+ * batch has been synced, the padding between a run's blobs included (it is copied along).  A run in pageable memory is still decoded
+ * correctly (the runtime stages it), but its copy may block the calling thread.  (No reference counterpart: crt::Decoder reads its one
+ * blob from the caller's memory in place, src/decoder.cpp:41-48.) */
 int crthip_ctx_set_packed_host_blobs(crthip_ctx *ctx, int on);
 int crthip_device_count(void);
 
@@ -276,6 +282,24 @@ int crthip_output_layout(uint32_t nblobs, const uint8_t *const *blobs, const uin
  * j % ndevices == d (the shard resident in ITS HBM: give device_arena[d] for those and NULL elsewhere), and a device without a home
  * item takes the others' (and uploads them, since they are not resident there).  Worker threads are pinned to the CPUs of their GPU's
  * NUMA node when sysfs names one.
+ * Groups.  A hardware queue runs one kernel at a time, and a decode's kernels last as long as their slowest blob's chain of dependent steps,
+ * hardly longer for 512 blobs than for 256.  Where the pool's lanes outnumber the queues (single-stream, pipelined lanes) the rate is
+ * queues / (a launch set's kernel time), so the pool pays that time once per GROUP: a lane call draws up to G tickets and decodes their items
+ * as ONE batch object - the blob lists joined, first ticket first, every item's outputs bound into a block of its own (the lane's block holds G
+ * of them; crthip_pool_decode: the item's destination).  G is 2 on such lanes and 1 elsewhere; $CORTO_POOL_GROUP = 1 .. 4, read by
+ * crthip_pool_create, overrides it.  Every member remains a step of its own: one completion and one completion time (the group's members share
+ * the instant), its own statuses, its own `done` call, its own device-to-host copy.  Extra tickets are drawn only while at least 2 x lanes x G
+ * tickets are undrawn, so the end of a crthip_pool_run - the steps crthip_pool_lane_read shows - and a short crthip_pool_decode run one item a
+ * call on all lanes.  A group's members are all resident on the lane's device (their device arenas may be separate allocations) or all
+ * uploaded IN PLACE (crthip_pool_set_packed_host_blobs on and the members' blobs in at most 8 runs together: a copy a run,
+ * crthip_ctx_set_packed_host_blobs); items whose blobs have to be gathered on the worker thread - scattered host blobs, or the switch off -
+ * are decoded one a call as before.  A ticket that does not fit the group it was drawn for waits for the thread's next call.  A group that planning refuses for a blob's own fault is planned again one item a call, so that the bad item alone carries the code.
+ * A lane whose groups turn out not to pipeline where its single items did (two items' dictionaries can exceed what a grid carries) returns to
+ * one item a call for the rest of the run.  Nothing is deduplicated: two tickets that name the same item are uploaded and decoded twice.
+ * Memory: every lane's output block holds G strides of the call's largest item block (plus an eighth), whether or not the call ever forms a
+ * group - a short crthip_pool_decode and a lane back at one item a call keep the larger block - and with crthip_pool_set_outputs_to_host or
+ * pageable host destinations the lane's pinned mirror is as large: for C4 items (32 MB a block) 72 MB of HBM a lane at G = 2 against 36 at
+ * G = 1, and as much pinned host memory again where there is a mirror.  $CORTO_POOL_GROUP=1 gives the smaller blocks back.
  * devices == NULL: devices 0 .. ndevices-1.  A device id may repeat (several pool "devices" on one GPU: how the N > 1 path
  * is exercised on a one-GPU box). */
 typedef struct crthip_pool crthip_pool;
@@ -318,7 +342,10 @@ typedef struct {
 	double elapsed_s;            /* wall time from the completion of the last warm-up step to the completion of the last timed step:
 	                                the pipeline is full at both ends (extra steps are queued behind the timed ones and drained untimed) */
 	uint64_t steps;              /* timed steps completed (= the `steps` asked for) */
-	uint64_t triangles, vertices;/* decoded by the timed steps */
+	uint64_t triangles, vertices;/* decoded by the timed steps: the steps whose TICKET number lies in [warmup, warmup + steps), whichever order they completed in
+	                                (steps_per_device likewise).  elapsed_s is taken between COMPLETIONS number warmup and warmup + steps.  With equal items the
+	                                two windows hold the same work; with items that differ, triangles / elapsed_s mixes them by the few steps that completed
+	                                out of ticket order at either end (at most the batches in flight).  This holds at every group size, 1 included */
 	uint64_t failed_blobs;       /* blobs (over all executed steps) whose status was not CRTHIP_OK */
 	int32_t first_error;         /* first failing status seen, or CRTHIP_OK */
 	uint32_t devices_used;       /* pool devices that completed at least one timed step */
@@ -328,11 +355,14 @@ typedef struct {
 	                                context's stream: the last round of timed steps and the tail behind them are run that way, so what
 	                                crthip_pool_lane_read returns afterwards was written by those steps and by nothing earlier */
 	uint32_t pinned_devices;     /* pool devices whose worker threads were pinned to the CPUs of the GPU's NUMA node */
-	float host_us_per_step;      /* host time per step and thread: plan (walk + bind) + enqueue, averaged over every executed step */
+	float host_us_per_step;      /* host time per step and thread: plan (walk + bind) + enqueue, averaged over every executed step (a group's time is shared
+	                                by its members: the host_*_us figures stay per step) */
 	float host_plan_max_us;      /* the LONGEST single plan call (walk + the upload's enqueue + bind) of the run ... */
 	float host_wait_us, host_finish_us, host_plan_us;   /* of a worker thread's time per step: waiting for one of its contexts to finish; harvesting it
 	                                (sync, status); the walk + bind part of host_us_per_step */
 	float host_launch_max_us;    /* ... and the longest single crthip_batch_decode call: a host thread that blocks inside the runtime shows here */
+	uint64_t grouped_steps;      /* steps (over all executed ones, warm-up and tail included) that a lane decoded together with another step, as members of
+	                                one batch object ("Groups" above); 0 when every call decoded one item */
 } crthip_pool_report;
 
 /* Decode every item exactly ONCE into memory the caller owns: the pool as a service.  No warm-up, no tail, no poisoning; the call blocks
@@ -347,7 +377,8 @@ typedef struct {
  *     straight into `out` where that is pinned memory (hipPointerGetAttributes decides), else into the lane's pinned mirror and from there
  *     with a memcpy on the worker thread.  Bytes of [0, total) outside the arrays are unspecified; [total, cap) is untouched.
  *   items[j].device_arena[slot] is used as in crthip_pool_run when the decoding slot has one.
- * Scheduling is crthip_pool_run's: the same worker threads and pinning, lanes pipelined two batches a call where they are there
+ * Scheduling is crthip_pool_run's: the same worker threads and pinning, groups of items a lane call where the list is long enough ("Groups"
+ * above: a call of fewer than 2 x lanes x G items runs one item a call), lanes pipelined two batches a call where they are there
  * ($CORTO_CARRY=0 honoured); a worker takes its slot's device-destination items first, then its home host items, then the other slots'.
  * Before the first launch every destination is checked - CRTHIP_E_ARGUMENT for the call, the item named in crthip_last_error(), nothing
  * written: a NULL `out` with total > 0, `out` not 256-byte aligned, cap < total, a device_slot that is neither a pool device nor
@@ -493,6 +524,9 @@ typedef struct {
 	uint32_t descriptor_bytes;  /* the job descriptors of the last decode: one host -> HBM copy beside the blobs' own bytes (it shares their PCIe link) */
 	uint32_t int16_streams;     /* log streams of the last decode whose values K-BIT handed on as int16 instead of int32: the stream's probability table holds no
 	                               width above 16 bits (15 for per-component streams), and the reader is the LDS-resident K-DELTA / K-NRM ($CORTO_VALUES_I32=1: none) */
+	uint32_t upload_copies;     /* host -> HBM copies crthip_batch_create / _reset enqueued for the blobs' bytes: 0 for resident blobs, 1 for gathered ones, the
+	                               number of runs for packed host blobs (crthip_ctx_set_packed_host_blobs) */
+	uint64_t upload_gathered_bytes; /* ... and the bytes it gathered into the context's pinned image first (0: every copy read the caller's memory in place) */
 } crthip_batch_stats;
 int crthip_batch_get_stats(const crthip_batch *b, crthip_batch_stats *s);
 

@@ -1,9 +1,11 @@
 """What crthip_pool_decode costs beside crthip_pool_run, on the batch and the pool shape bench.py uses.
 
-    python tools/pool_decode_rate.py [--items 40] [--reps 5] [--host-threads 5] [--depth 4] [--out FILE]
+    python tools/pool_decode_rate.py [--items 40] [--reps 5] [--host-threads 5] [--depth 4] [--distinct 1] [--out FILE]
 
 The C4 batch (256 blobs x 4 096 triangles, bench.py: load_blobs) is handed over as --items items with a device block each, so a call writes
---items distinct output blocks where crthip_pool_run reuses its lanes' own.  Measured, --reps times each on ONE pool, in turn:
+--items distinct output blocks where crthip_pool_run reuses its lanes' own.  --distinct K: the items cycle through K different batches (seeds 256 k ..
+256 k + 255, a pinned buffer and a device arena each) instead of naming one - what a lane call that decodes a GROUP of items meets in real use: two
+items' dictionaries, two uploads from two buffers (profiles/pool_group.md).  Measured, --reps times each on ONE pool, in turn:
     decode/host      crthip_pool_decode, blobs in one pinned host buffer (packed: uploaded inside the step)
     run/host         crthip_pool_run for --items steps (warmup 0) on the same items
     decode/resident  crthip_pool_decode, blobs resident in HBM (device arenas)
@@ -31,22 +33,27 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-threads", type=int, default=5)
     ap.add_argument("--depth", type=int, default=4)
+    ap.add_argument("--distinct", type=int, default=1)
     ap.add_argument("--out")
     args = ap.parse_args()
     import torch
     import corto_amd as ca
     from corto_amd import synth
     from oracle import oracle as oc
-    blobs = [ca.encode(synth.bumpy_sphere(64, 32, seed=i), position_bits=14, uv_bits=12, normal_bits=10, normal_prediction=ca.BORDER)
-             for i in range(NBLOBS)]
-    arena = ca.upload_arena([ca.aligned_blob(b) for b in blobs], 0)
+    K = max(1, args.distinct)
+    batches = [[ca.encode(synth.bumpy_sphere(64, 32, seed=k * NBLOBS + i), position_bits=14, uv_bits=12, normal_bits=10, normal_prediction=ca.BORDER)
+                for i in range(NBLOBS)] for k in range(K)]
+    blobs = batches[0]
+    arena_k = [ca.upload_arena([ca.aligned_blob(b) for b in bl], 0) for bl in batches]
     pool = ca.Pool([0], threads=args.host_threads, depth=args.depth)
     lines = []
     try:
-        pin, views = ca.pinned_host_arena(blobs)
+        pins = [ca.pinned_host_arena(bl) for bl in batches]
+        views = pins[0][1]
         n = args.items
-        legs = {"host": dict(items=[views] * n, arenas=None, packed=True),
-                "resident": dict(items=[views] * n, arenas=[[arena]] * n, packed=False)}
+        its = [pins[j % K][1] for j in range(n)]
+        legs = {"host": dict(items=its, arenas=None, packed=True),
+                "resident": dict(items=its, arenas=[[arena_k[j % K]] for j in range(n)], packed=False)}
         total = ca.output_layout(views)[1]
         blocks = [torch.empty(total, dtype=torch.uint8, device="cuda:0") for _ in range(n)]
         torch.cuda.synchronize()
@@ -70,11 +77,11 @@ def main():
         for j in (0, n // 2, n - 1):
             raw = res[j].block.cpu().numpy()
             for i in (0, 101, 255):
-                ref = oc.decode(ca.aligned_blob(blobs[i]))
+                ref = oc.decode(ca.aligned_blob(batches[j % K][i]))
                 for name, (o, dt, shape) in lay[i].items():
                     assert raw[o:o + ref[name].nbytes].tobytes() == ref[name].tobytes(), (j, i, name)
-        lines.append("pool %d x %d lanes (%d), %d items of %d blobs x 4096 triangles, %d repetitions, GPU_MAX_HW_QUEUES=%s" % (
-            args.host_threads, args.depth, pool.lanes, n, NBLOBS, args.reps, os.environ.get("GPU_MAX_HW_QUEUES", "unset")))
+        lines.append("pool %d x %d lanes (%d), %d items of %d blobs x 4096 triangles (%d distinct), %d repetitions, GPU_MAX_HW_QUEUES=%s" % (
+            args.host_threads, args.depth, pool.lanes, n, NBLOBS, K, args.reps, os.environ.get("GPU_MAX_HW_QUEUES", "unset")))
         lines.append("| leg | Gtri/s median | range | ms a call | host_plan_us | host_wait_us | host_finish_us | host_us_per_step |")
         lines.append("|---|---|---|---|---|---|---|---|")
         for name in ("decode/host", "run/host", "decode/resident", "run/resident"):
