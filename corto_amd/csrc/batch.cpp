@@ -6,6 +6,7 @@
 //   decode-all (Tunstall + bit-unpack) -> topology -> delta-all -> postDelta (normals) -> dequantize-all.
 #include "batch_internal.h"
 #include "crt_walk.h"
+#include "pool_internal.h"
 
 // (the thread's last error, crthip_strerror and crthip_probe are host_probe.cpp's: no HIP there)
 extern "C" uint32_t crthip_abi_version(void) { return CRTHIP_ABI_VERSION; }
@@ -325,13 +326,13 @@ static int batch_fill(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs, const u
 		if(harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE);
 		// packed host blobs (corto_hip.h): the caller's buffers ARE the arena's image, in pieces.  A run is a stretch of blobs that follow one another in
 		// host memory as they do in the arena; every run goes up with a copy of its own, straight from the caller's memory.  One run is one copy of
-		// one buffer; a pool lane's group of items is a run an item.  Beyond PACKED_RUNS_MAX runs the copies' own cost (a few us of enqueue and a DMA
+		// one buffer; a pool lane's group of items is a run an item.  Beyond PACKED_RUNS_MAX (pool_internal.h) runs the copies' own cost (a few us of enqueue and a DMA
 		// descriptor each) is no longer small beside the memcpy they save, and the blobs are gathered as if the switch were off
-		constexpr uint32_t PACKED_RUNS_MAX = 8;
+		using corto_hip::PACKED_RUNS_MAX;
 		uint32_t run_first[PACKED_RUNS_MAX], nruns = 0;
 		bool in_place = ctx->packed_host && nblobs > 0;
 		for(uint32_t i = 0; in_place && i < nblobs; i++) {
-			if(i && blobs[i] == blobs[i - 1] + (b->blobs[i].arena_off - b->blobs[i - 1].arena_off)) continue;
+			if(!corto_hip::packed_run_starts(blobs, lens, i)) continue;
 			if(nruns == PACKED_RUNS_MAX) in_place = false; else run_first[nruns++] = i;
 		}
 		if(in_place) {

@@ -47,6 +47,7 @@
 #include "enc_topology.h"
 #include "encoder_internal.h"
 #include "kernels.h"
+#include "pool_internal.h"
 
 using namespace corto_hip;
 
@@ -881,21 +882,6 @@ int encode_chunk(crthip_ctx *ctx, const crthip_mesh *meshes, const crthip_attr_l
 
 // ---- a resident call's front: the caller's pointers, then what the host would have read through them ----
 
-// one array of a resident call: element-aligned device memory of the context's device, its whole extent inside one allocation
-bool resident_array_ok(const void *p, uint64_t bytes, uint32_t align, int device) {
-	if(!bytes) return true;
-	if(!p || ((uintptr_t)p & (align - 1))) return false;
-	hipPointerAttribute_t a;
-	memset(&a, 0, sizeof(a));
-	if(hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // (memory the runtime has never seen)
-	if(a.type != hipMemoryTypeDevice || a.device != device) return false;                          // pinned and managed memory included
-	hipDeviceptr_t base = nullptr;
-	size_t size = 0;
-	if(hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
-	const uintptr_t b = (uintptr_t)base, q = (uintptr_t)p;
-	return q >= b && bytes <= size && q - b <= size - bytes;
-}
-
 // every data array of one mesh (after encode_check / encode_check_attrs / layout_resolve): no launch reads a pointer that has not passed
 // here.  An array's extent is what the kernels touch of it: [ptr, ptr + (nvert - 1)*stride + one vertex's bytes).
 int resident_check(const crthip_mesh *m, const crthip_attr_list *extra, const MeshRead &rd, int device) {
@@ -988,6 +974,22 @@ int input_pass(crthip_ctx *ctx, const crthip_mesh *meshes, const std::vector<Mes
 }
 
 } // namespace
+
+// one array of a resident call: element-aligned device memory of the context's device, its whole extent inside one allocation
+// (pool_internal.h: crthip_pool_decode checks its device destinations with it too)
+bool corto_hip::resident_array_ok(const void *p, uint64_t bytes, uint32_t align, int device) {
+	if(!bytes) return true;
+	if(!p || ((uintptr_t)p & (align - 1))) return false;
+	hipPointerAttribute_t a;
+	memset(&a, 0, sizeof(a));
+	if(hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // (memory the runtime has never seen)
+	if(a.type != hipMemoryTypeDevice || a.device != device) return false;                          // pinned and managed memory included
+	hipDeviceptr_t base = nullptr;
+	size_t size = 0;
+	if(hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
+	const uintptr_t b = (uintptr_t)base, q = (uintptr_t)p;
+	return q >= b && bytes <= size && q - b <= size - bytes;
+}
 
 // what encode_batch_impl refuses a mesh for before any device work; rd: the mesh's layout, resolved here; resident_device >= 0: its data
 // arrays are that device's memory

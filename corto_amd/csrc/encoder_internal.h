@@ -190,11 +190,6 @@ uint64_t ctx_encode_image_budget(crthip_ctx *ctx);   // $CORTO_ENCODE_IMAGE_BUDG
 int ctx_encode_topology(crthip_ctx *ctx);   // CRTHIP_TOPOLOGY_* of crthip_ctx_set_encode_topology
 hipStream_t ctx_stream(crthip_ctx *ctx);
 int ctx_quiesce(crthip_ctx *ctx);       // wait for whatever batch is in flight on the context
-bool ctx_pipelines(crthip_ctx *ctx);    // a single-stream context without $CORTO_CARRY=0: crthip_batch_decode_with_next can carry a batch's entropy stage in another's grids
-bool batch_carriable(const crthip_batch *b);      // its last decode could have been carried by a batch like itself, and could have carried one
-bool batch_entropy_done(const crthip_batch *b);   // planned as `next` of crthip_batch_decode_with_next, and that call enqueued (carried) its entropy stage
-int batch_reset_at(crthip_batch *b, uint32_t nblobs, const uint8_t *const *blobs, const uint32_t *lens, const void *device_base, const uint64_t *dev_off);   // crthip_batch_reset, blob i resident at device_base + dev_off[i]
-int ctx_fill_async(crthip_ctx *ctx, void *dst, size_t bytes, int value);   // k_fill_block on the context's main stream
-int ctx_copy_to_host_async(crthip_ctx *ctx, void *host_dst, const void *dev_src, size_t bytes);   // D2H behind the decode in flight; sync / done then cover the copy
+// (what the pool uses of the context and of a batch: pool_internal.h)
 
 } // namespace corto_hip

@@ -1,6 +1,6 @@
 // pool.cpp — the multi-GPU decode pool of include/corto_hip.h: a list of independent batches of .crt blobs
-// decoded by every GPU of the node, one shared work queue, no collective.  Built on the public C ABI only (crthip_ctx /
-// crthip_batch_*), plus hipMalloc for the lanes' output blocks.
+// decoded by every GPU of the node, one shared work queue, no collective.  Built on the public C ABI (crthip_ctx / crthip_batch_*), the
+// few helpers of pool_internal.h and hipMalloc for the lanes' output blocks: tests/cpp/pool_fake_backend.cpp stands in for all three.
 //
 // Reference anchor: independent crt::Decoder objects, src/decoder.cpp:126-196 (nothing shared between two decodes).
 #include <cstdlib>
@@ -20,8 +20,8 @@
 #include <vector>
 
 #include "../../include/corto_hip.h"
-#include "encoder_internal.h"
 #include "output_layout.h"
+#include "pool_internal.h"
 
 using corto_hip::ctx_fail;
 
@@ -71,9 +71,12 @@ struct Lane {
 	void *host_out = nullptr; size_t host_cap = 0;   // outputs_to_host: the pinned mirror of `out`
 	bool busy = false;
 	bool poisoned = false;          // the output block was filled with POISON on the context's stream right before the mesh stage in flight / last executed
+	void begin_run() {                  // (an item id means this call's items[] only; `poisoned` a mesh stage of this run)
+		busy = staged = poisoned = pipe = drain = single_ok = alone = false;
+		for(Slot &S : s) { S.item = -1; S.binds.clear(); S.mem.clear(); }
+	}
 };
 constexpr int POISON = 0xA5;
-constexpr uint32_t PACKED_RUNS_MAX = 8;   // batch.cpp's: packed host blobs in more runs than this are gathered on the worker thread
 constexpr uint32_t GROUP_MAX = 4;   // the most items a lane call decodes as one batch object ($CORTO_POOL_GROUP)
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -109,6 +112,29 @@ static void destroy_lane(Lane &L) {
 	if(L.out) (void)hipFree(L.out);
 	if(L.host_out) (void)hipHostFree(L.host_out);
 	L.ctx = nullptr; L.out = nullptr; L.out_cap = 0; L.host_out = nullptr; L.host_cap = 0;
+}
+
+// the host CPUs next to a GPU: PCI bus id -> /sys/bus/pci/devices/<id>/numa_node -> /sys/devices/system/node/node<N>/cpulist (empty: unknown)
+static std::vector<int> numa_cpus(int device) {
+	std::vector<int> cpus; char bus[64] = {0};
+	if(hipDeviceGetPCIBusId(bus, (int)sizeof bus, device) != hipSuccess) { (void)hipGetLastError(); return cpus; }
+	for(char *c = bus; *c; c++) if(*c >= 'A' && *c <= 'F') *c = (char)(*c - 'A' + 'a');
+	char path[192]; int node = -1;
+	snprintf(path, sizeof path, "/sys/bus/pci/devices/%s/numa_node", bus);
+	if(FILE *f = fopen(path, "r")) { if(fscanf(f, "%d", &node) != 1) node = -1; fclose(f); }
+	if(node < 0) return cpus;
+	snprintf(path, sizeof path, "/sys/devices/system/node/node%d/cpulist", node);
+	if(FILE *f = fopen(path, "r")) {
+		int a, b; char sep;
+		while(fscanf(f, "%d", &a) == 1) {
+			b = a;
+			if(fscanf(f, "%c", &sep) == 1 && sep == '-') { if(fscanf(f, "%d", &b) != 1) b = a; if(fscanf(f, "%c", &sep) != 1) sep = 0; }
+			for(int c = a; c <= b && c < CPU_SETSIZE; c++) cpus.push_back(c);
+			if(sep != ',') break;
+		}
+		fclose(f);
+	}
+	return cpus;
 }
 
 extern "C" int crthip_pool_create(uint32_t ndevices, const int *devices, uint32_t threads_per_device, uint32_t depth, crthip_pool **out) {
@@ -148,28 +174,7 @@ extern "C" int crthip_pool_create(uint32_t ndevices, const int *devices, uint32_
 			p->warning = buf;
 			fprintf(stderr, "%s\n", buf);
 		}
-	// the host CPUs next to each GPU: PCI bus id -> /sys/bus/pci/devices/<id>/numa_node -> /sys/devices/system/node/node<N>/cpulist
-	p->cpus.resize(ndevices);
-	for(uint32_t d = 0; d < ndevices; d++) {
-		char bus[64] = {0};
-		if(hipDeviceGetPCIBusId(bus, (int)sizeof bus, p->devices[d]) != hipSuccess) { (void)hipGetLastError(); continue; }
-		for(char *c = bus; *c; c++) if(*c >= 'A' && *c <= 'F') *c = (char)(*c - 'A' + 'a');
-		char path[192]; int node = -1;
-		snprintf(path, sizeof path, "/sys/bus/pci/devices/%s/numa_node", bus);
-		if(FILE *f = fopen(path, "r")) { if(fscanf(f, "%d", &node) != 1) node = -1; fclose(f); }
-		if(node < 0) continue;
-		snprintf(path, sizeof path, "/sys/devices/system/node/node%d/cpulist", node);
-		if(FILE *f = fopen(path, "r")) {
-			int a, b; char sep;
-			while(fscanf(f, "%d", &a) == 1) {
-				b = a;
-				if(fscanf(f, "%c", &sep) == 1 && sep == '-') { if(fscanf(f, "%d", &b) != 1) b = a; if(fscanf(f, "%c", &sep) != 1) sep = 0; }
-				for(int c = a; c <= b && c < CPU_SETSIZE; c++) p->cpus[d].push_back(c);
-				if(sep != ',') break;
-			}
-			fclose(f);
-		}
-	}
+	for(uint32_t d = 0; d < ndevices; d++) p->cpus.push_back(numa_cpus(p->devices[d]));
 	*out = p;
 	return CRTHIP_OK;
 }
@@ -235,7 +240,7 @@ static int item_plan(const crthip_pool *p, const crthip_pool_item &it, ItemPlan 
 	for(uint32_t i = 0; i < it.nblobs; i++) {
 		const int err = crthip_probe(it.blobs[i], it.lens[i], &info);
 		if(err) { P.err = err; P.err_msg = std::string(crthip_strerror(err)) + " (blob " + std::to_string(i) + ")"; return ctx_fail(err, P.err_msg.c_str()); }
-		if(i == 0 || it.blobs[i] != it.blobs[i - 1] + (((size_t)it.lens[i - 1] + 15) & ~(size_t)15)) P.runs++;
+		if(corto_hip::packed_run_starts(it.blobs, it.lens, i)) P.runs++;
 		P.first_attr[i] = (uint32_t)P.attr.size();
 		P.attr.resize(P.attr.size() + info.nattr);
 		corto_hip::layout_blob(info, flags, off, P.attr.data() + P.first_attr[i], &P.index[i]);
@@ -244,13 +249,6 @@ static int item_plan(const crthip_pool *p, const crthip_pool_item &it, ItemPlan 
 	P.total = corto_hip::layout_total(off);
 	return CRTHIP_OK;
 }
-
-struct PoolJob;
-// plan the group S.mem (the members' item, step and destination filled in; one member is an item alone) on one of the lane's batch objects
-// and bind its outputs: member k into the lane's device block, k strides in (the block holds `group` strides and the call's slack
-// afterwards), or straight into its device destination.  *item_fault: the failure is an item's own - a blob the host walk refuses - and
-// the lane is as it was, but for an empty-handed batch object
-static int lane_plan(crthip_pool *p, Lane &L, Slot &S, const PoolJob &job, bool *item_fault);
 
 // One call's work.  crthip_pool_run (dests null): warmup + steps + a tail of tickets, items drawn cyclically, every lane's block poisoned
 // in front of its last steps.  crthip_pool_decode (dests set): every item once, into its destination.  The workers, their pinning, the
@@ -268,6 +266,10 @@ struct PoolJob {
 	crthip_pool_done_fn done = nullptr; void *user = nullptr;
 };
 
+// plan the group S.mem (the members' item, step and destination filled in; one member is an item alone) on one of the lane's batch objects
+// and bind its outputs: member k into the lane's device block, k strides in (the block holds `group` strides and the call's slack
+// afterwards), or straight into its device destination.  *item_fault: the failure is an item's own - a blob the host walk refuses - and
+// the lane is as it was, but for an empty-handed batch object
 static int lane_plan(crthip_pool *p, Lane &L, Slot &S, const PoolJob &job, bool *item_fault) {
 	const bool dec = job.dests != nullptr;
 	const size_t n = S.mem.size();
@@ -352,318 +354,329 @@ static int lane_plan(crthip_pool *p, Lane &L, Slot &S, const PoolJob &job, bool 
 	return crthip_batch_bind_all(S.batch, S.binds.data(), S.index_ptr.data(), S.index_fmt.data());
 }
 
-static int pool_work(crthip_pool *p, PoolJob &job, crthip_pool_report *report) {
-	const uint32_t nitems = job.nitems;
-	const crthip_pool_item *items = job.items;
-	const bool dec = job.dests != nullptr;
-	const uint64_t steps = job.steps, warmup = job.warmup;
-	const uint64_t timed_end = dec ? 0 : warmup + steps;
-	// the tail keeps every context busy until the last timed completion (a pipelined lane has two tickets drawn and not completed)
-	const uint64_t total = dec ? nitems : timed_end + p->lanes.size()*(p->pipelined ? 2u : 1u);
-	p->next = 0; p->completed = 0; p->error = CRTHIP_OK; p->error_msg.clear();
-	for(auto &L : p->lanes) { L.busy = false; L.staged = false; L.poisoned = false; L.pipe = false; L.drain = false; L.single_ok = false; L.alone = false; for(Slot &S : L.s) { S.item = -1; S.binds.clear(); S.mem.clear(); } }   // (an item id means this call's items[] only; `poisoned` a mesh stage of this run)
-	const bool pipe = p->pipelined;
-	std::vector<double> stamps(timed_end + 1, 0.0);           // stamps[c] = time at which the c-th completion happened (1-based)
-	std::atomic<uint64_t> failed{0}, fallbacks{0}, tris{0}, verts{0}, grouped{0};
-	std::vector<std::atomic<uint64_t>> per_dev(p->ndevices);
-	for(auto &x : per_dev) x = 0;
-	std::atomic<int32_t> first_error{0};
-	std::atomic<uint64_t> host_ns{0}, host_steps{0}, wait_ns{0}, finish_ns{0}, plan_ns{0}, plan_max_ns{0}, launch_max_ns{0};
-	auto raise_max = [](std::atomic<uint64_t> &m, uint64_t v) { uint64_t cur = m.load(); while(v > cur && !m.compare_exchange_weak(cur, v)) { } };
+// One call's shared state: the work lists and their cursors, the completion stamps, the counters of the report.  Nothing here belongs to a thread.
+struct Run {
+	crthip_pool *const p; PoolJob &job;
+	const bool dec;                                              // crthip_pool_decode
+	uint64_t timed_end, total, poison_from;                      // total: the tickets of the call (the constructor sets them; constant afterwards)
 	// home shard first: pool device d owns the items j with j % ndevices == d (its shard is resident there), and a device without a home
 	// item takes from the others' ("stealing" in a cyclic run: it is the work list that is shared, a faster GPU simply draws more tickets).
 	// crthip_pool_decode: the home lists hold the host-destination items, `bound` a slot's device-destination items, which nobody else may
 	// draw; every list is drawn once, front to back, and a slot whose own lists are empty takes from the other slots' home lists
-	std::vector<std::vector<uint32_t>> home(p->ndevices), bound(p->ndevices);
-	for(uint32_t j = 0; j < nitems; j++) {
-		if(dec && job.dests[j].device_slot >= 0) bound[(uint32_t)job.dests[j].device_slot].push_back(j);
-		else home[j % p->ndevices].push_back(j);
-	}
-	std::vector<std::atomic<uint64_t>> home_next(p->ndevices), bound_next(p->ndevices);
-	for(auto &x : home_next) x = 0;
-	for(auto &x : bound_next) x = 0;
+	std::vector<std::vector<uint32_t>> home, bound;
+	std::vector<std::atomic<uint64_t>> home_next, bound_next;
 	std::atomic<uint64_t> stolen{0};
-	auto take = [](const std::vector<uint32_t> &q, std::atomic<uint64_t> &at, uint32_t &j) {
+	std::vector<double> stamps;                                  // stamps[c] = time at which the c-th completion happened (1-based)
+	std::atomic<uint64_t> failed{0}, fallbacks{0}, tris{0}, verts{0}, grouped{0};
+	std::vector<std::atomic<uint64_t>> per_dev;
+	std::atomic<int32_t> first_error{0};
+	std::atomic<uint64_t> host_ns{0}, host_steps{0}, wait_ns{0}, finish_ns{0}, plan_ns{0}, plan_max_ns{0}, launch_max_ns{0};
+	Run(crthip_pool *pool, PoolJob &j) : p(pool), job(j), dec(j.dests != nullptr), home(pool->ndevices), bound(pool->ndevices),
+		home_next(pool->ndevices), bound_next(pool->ndevices), per_dev(pool->ndevices) {
+		timed_end = dec ? 0 : j.warmup + j.steps;
+		// the tail keeps every context busy until the last timed completion (a pipelined lane has two tickets drawn and not completed)
+		total = dec ? j.nitems : timed_end + p->lanes.size()*(p->pipelined ? 2u : 1u);
+		// the last round of timed steps and the tail behind them (outputs_to_host: the tail only - poisoning the pinned mirror is 32 MB of memset on the worker thread)
+		poison_from = dec ? ~0ull : p->to_host ? timed_end : timed_end > p->lanes.size() ? timed_end - p->lanes.size() : 0;
+		stamps.assign(timed_end + 1, 0.0);
+		for(uint32_t i = 0; i < j.nitems; i++) {
+			if(dec && j.dests[i].device_slot >= 0) bound[(uint32_t)j.dests[i].device_slot].push_back(i);
+			else home[i % p->ndevices].push_back(i);
+		}
+		for(auto *v : {&home_next, &bound_next, &per_dev}) for(auto &x : *v) x = 0;
+	}
+	static void raise_max(std::atomic<uint64_t> &m, uint64_t v) { uint64_t cur = m.load(); while(v > cur && !m.compare_exchange_weak(cur, v)) { } }
+	static bool take(const std::vector<uint32_t> &q, std::atomic<uint64_t> &at, uint32_t &j) {
 		if(at.load() >= q.size()) return false;
 		const uint64_t k = at.fetch_add(1);
 		if(k >= q.size()) return false;
 		j = q[k];
 		return true;
-	};
-	auto draw_once = [&](uint32_t slot, uint32_t &j) {
+	}
+	bool draw_once(uint32_t slot, uint32_t &j) {
 		if(take(bound[slot], bound_next[slot], j) || take(home[slot], home_next[slot], j)) return true;
 		for(uint32_t d = 1; d < p->ndevices; d++) { const uint32_t o = (slot + d) % p->ndevices; if(take(home[o], home_next[o], j)) return true; }
 		return false;
-	};
-	// the last round of timed steps and the tail behind them (outputs_to_host: the tail only - poisoning the pinned mirror is 32 MB of memset on the worker thread)
-	const uint64_t poison_from = dec ? ~0ull : p->to_host ? timed_end : timed_end > p->lanes.size() ? timed_end - p->lanes.size() : 0;
-	const double t_launch = now_s();
-	stamps[0] = t_launch;
+	}
+	// crthip_pool_decode: item j is final - `code` in every status entry (it could not be planned, or holds no blob), or S's statuses
+	// (the statuses of its blobs, which begin at `first` in the group's batch object)
+	void settle(uint32_t slot, uint32_t j, int32_t code, const Slot *S, uint32_t first) {
+		const ItemPlan &P = job.plans[j];
+		int32_t *st = job.status + P.status_at;
+		for(uint32_t i = 0; i < job.items[j].nblobs; i++) st[i] = S ? S->status[first + i] : code;
+		if(!S) {
+			++p->completed;
+			if(code) { failed += job.items[j].nblobs; int32_t z = 0; first_error.compare_exchange_strong(z, code); }
+		}
+		per_dev[slot]++;
+		if(job.done) job.done(job.user, j, slot, st);
+	}
+	// one ticket from the work lists for a thread of `slot`.  0: none left; 1: `k` is drawn; 2 (crthip_pool_decode): an item with nothing to
+	// launch was drawn and settled
+	int draw(uint32_t slot, Ticket &k) {
+		k.solo = false;
+		if(!dec) {
+			k.step = p->next.fetch_add(1);
+			if(k.step >= total) return 0;
+			if(!home[slot].empty()) k.j = home[slot][home_next[slot].fetch_add(1) % home[slot].size()];
+			else k.j = (uint32_t)(stolen.fetch_add(1) % job.nitems);
+			return 1;
+		}
+		if(p->next.load() >= total || !draw_once(slot, k.j)) return 0;
+		k.step = p->next.fetch_add(1);
+		if(job.plans[k.j].err || job.items[k.j].nblobs == 0) { settle(slot, k.j, job.plans[k.j].err, nullptr, 0); return 2; }
+		return 1;
+	}
+	// a drawn ticket as a group member: where its outputs go
+	Member member_of(const Ticket &k) const {
+		Member m;
+		m.item = (int64_t)k.j; m.step = k.step; m.to_host = p->to_host;
+		if(!dec) return m;
+		const crthip_pool_dest &D = job.dests[k.j];
+		m.to_host = D.device_slot < 0;
+		if(!m.to_host) m.base = (uint8_t *)D.out;
+		else if(job.plans[k.j].pinned) m.pinned_dst = D.out;
+		else m.pageable_dst = D.out;
+		return m;
+	}
+	void fill_report(crthip_pool_report &rep, double call_s) const {
+		rep.elapsed_s = dec ? call_s : stamps[timed_end] - stamps[job.warmup];
+		rep.steps = dec ? job.nitems : job.steps; rep.triangles = tris; rep.vertices = verts;
+		rep.failed_blobs = failed; rep.first_error = first_error; rep.topology_fallbacks = fallbacks; rep.grouped_steps = grouped;
+		for(uint32_t d = 0; d < p->ndevices; d++) { rep.steps_per_device[d] = per_dev[d]; if(per_dev[d]) rep.devices_used++; }
+		if(!dec) for(auto &L : p->lanes) if(L.s[L.cur].item >= 0 && L.poisoned) rep.poisoned_lanes++;
+		rep.host_us_per_step = host_steps ? (float)((double)host_ns/1e3/(double)host_steps) : 0.f;
+		if(host_steps) {
+			rep.host_wait_us = (float)((double)wait_ns/1e3/(double)host_steps); rep.host_finish_us = (float)((double)finish_ns/1e3/(double)host_steps);
+			rep.host_plan_us = (float)((double)plan_ns/1e3/(double)host_steps);
+			rep.host_plan_max_us = (float)((double)plan_max_ns/1e3); rep.host_launch_max_us = (float)((double)launch_max_ns/1e3);
+		}
+		for(uint32_t d = 0; d < p->ndevices; d++) if(!p->cpus[d].empty()) rep.pinned_devices++;
+		if(job.completion_s) for(uint64_t c = 0; c < job.steps; c++) job.completion_s[c] = stamps[job.warmup + 1 + c] - stamps[job.warmup];
+	}
+};
 
-	auto worker = [&](uint32_t slot, uint32_t t) {
+using Clock = std::chrono::steady_clock;
+static uint64_t ns_since(Clock::time_point t0) { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now() - t0).count(); }
+
+// One host thread of a run: `depth` lanes of one pool device, refilled in turn.  A pipelined lane plans a ticket on its free batch object and
+// enqueues [mesh stage of the batch planned one refill ago + entropy stage of this one]; its first ticket of a run only enqueues an entropy
+// stage, and it draws the next one at once.  (crthip_pool_decode: the two objects are then bound to two different items' blocks.  That is
+// safe: an entropy stage writes its batch's own scratch and nothing else - corto_hip.h, crthip_batch_decode_with_next - so only the mesh
+// stage in flight writes a block.)
+struct Worker {
+	Run &r; crthip_pool *const p; const uint32_t slot; Lane *const mine;   // `mine`: the thread's `depth` lanes
+	// `held` is consumed before the work lists and `tickets` goes false only when it is empty and the lists are dry: no drawn ticket is lost.
+	// Solo tickets (a refused group's members) and tickets that did not fit a group wait here alike; a solo one is never joined to a group
+	std::vector<Ticket> held;                                    // drawn and not planned yet: a ticket that did not fit the group it was drawn for, the members of a group that was refused
+	bool tickets = true; int err = CRTHIP_OK;
+	Worker(Run &run, uint32_t slot_, uint32_t t) : r(run), p(run.p), slot(slot_), mine(&run.p->lanes[((size_t)slot_*run.p->threads_per_device + t)*run.p->depth]) { }
+	// the next lane to refill: a free one, else whichever of the busy ones finishes first (they mostly finish in the order they
+	// were launched, but a thread that waited on the oldest while a younger one was done left that context idle)
+	Lane *pick_lane(uint64_t n) {
+		for(uint32_t k = 0; k < p->depth; k++) if(!mine[(n + k) % p->depth].busy) return &mine[(n + k) % p->depth];
+		for(uint32_t spins = 0; ; spins++) {
+			for(uint32_t k = 0; k < p->depth; k++) {
+				Lane &C = mine[(n + k) % p->depth];
+				const int d = crthip_batch_done(C.s[C.cur].batch);
+				if(d < 0) { err = d; return nullptr; }
+				if(d) return &C;
+			}
+			if(spins < 64) std::this_thread::yield(); else std::this_thread::sleep_for(std::chrono::microseconds(5));
+		}
+	}
+	// harvest the lane's batch in flight: every member of the group is a step of its own
+	int finish(Lane &L) {
+		Slot &S = L.s[L.cur];
+		const int rc = crthip_batch_sync(S.batch, S.status.data());
+		L.busy = false;
+		// a completion and a stamp each (the same instant), counted by its own step number
+		const double t_done = now_s();
+		if(S.mem.size() > 1) r.grouped += S.mem.size();
+		for(const Member &m : S.mem) {
+			const uint64_t c = ++p->completed;                   // completion order
+			if(c <= r.timed_end) r.stamps[c] = t_done;
+			if(!r.dec && m.step >= r.job.warmup && m.step < r.timed_end) { r.per_dev[slot]++; r.tris += r.job.plans[(size_t)m.item].tris; r.verts += r.job.plans[(size_t)m.item].verts; }
+		}
+		uint64_t bad = 0;
+		for(int32_t st_ : S.status) if(st_) { bad++; int32_t z = 0; r.first_error.compare_exchange_strong(z, st_); }
+		r.failed += bad;
+		crthip_batch_stats st;
+		if(crthip_batch_get_stats(S.batch, &st) == CRTHIP_OK) r.fallbacks += st.topology_fallbacks;
+		if(rc == CRTHIP_E_DEVICE || rc == CRTHIP_E_NOMEM) return rc;
+		if(r.dec) for(const Member &m : S.mem) {
+			if(m.pageable_dst) memcpy(m.pageable_dst, (const uint8_t *)L.host_out + m.lane_off, m.out_used);   // (the copy into the lane's mirror is what the sync waited for)
+			r.tris += r.job.plans[(size_t)m.item].tris; r.verts += r.job.plans[(size_t)m.item].verts;
+			r.settle(slot, (uint32_t)m.item, 0, &S, m.first);
+		}
+		return CRTHIP_OK;
+	}
+	// what the batch just synced says about the lane's next calls (Lane: pipe, single_ok, alone)
+	void note_carry(Lane &L) {
+		if(!p->pipelined || L.staged || L.s[L.cur].item < 0) return;
+		L.pipe = corto_hip::batch_carriable(L.s[L.cur].batch);
+		if(L.s[L.cur].mem.size() == 1) L.single_ok = L.pipe;
+		else if(!L.pipe && L.single_ok) L.alone = true;          // (one item a call pipelines again)
+	}
+	// The mesh stage of s[cur] and, behind it, the D2H copies of a step of outputs_to_host or of items with host destinations.  DECODE: s[cur]'s
+	// whole decode; ALONE: its mesh stage (its whole decode, had its entropy stage not been carried) and nothing else; WITH_NEXT: its mesh
+	// stage + the entropy stage of s[cur ^ 1], and `drain` says whether that was carried.
+	// A step that is due one starts from a poisoned block: the outputs every lane holds after the run were written by a mesh stage that STARTED
+	// from one, so the post-run bit-exact check cannot pass on bytes an earlier step left behind (on the context's own stream: ordered before
+	// the stage's kernels)
+	enum class Mesh { DECODE, ALONE, WITH_NEXT };
+	int enqueue_mesh(Lane &L, Mesh how) {
+		Slot &S = L.s[L.cur];
+		crthip_batch *const next = L.s[L.cur ^ 1u].batch;
+		int e = CRTHIP_OK;
+		L.poisoned = false;
+		if(S.step >= r.poison_from && L.out) {
+			e = corto_hip::ctx_fill_async(L.ctx, L.out, L.out_cap, POISON);
+			if(!e && p->to_host && L.host_out) for(const Member &m : S.mem) memset((uint8_t *)L.host_out + m.lane_off, POISON, m.out_used);
+			L.poisoned = !e;
+		}
+		if(!e) e = how == Mesh::DECODE ? crthip_batch_decode(S.batch) : crthip_batch_decode_with_next(S.batch, how == Mesh::WITH_NEXT ? next : nullptr);
+		if(!e && how == Mesh::WITH_NEXT) L.drain = !corto_hip::batch_entropy_done(next);
+		for(const Member &m : S.mem) {                           // (one copy a member: each has its own destination)
+			if(e || !m.to_host) continue;
+			e = corto_hip::ctx_copy_to_host_async(L.ctx, m.pinned_dst ? m.pinned_dst : (uint8_t *)L.host_out + m.lane_off, (const uint8_t *)L.out + m.lane_off, m.out_used);
+		}
+		if(!e) L.busy = true;
+		return e;
+	}
+	// the lane's planned batch becomes its current one and runs its mesh stage alone
+	int launch_staged(Lane &L) { L.cur ^= 1u; L.staged = false; return enqueue_mesh(L, Mesh::ALONE); }
+	bool resident(uint32_t j) const { return r.job.items[j].device_arena && r.job.items[j].device_arena[slot]; }
+	// Blobs that must be gathered (scattered host blobs, or packed host blobs off) are not grouped: the gathering is a memcpy on this thread
+	// while its other lanes wait, and two items' worth of it in one piece cost `scattered_pageable_blobs` 29 % (profiles/pool_group.md)
+	uint32_t runs_of(uint32_t j) const { return resident(j) ? 0u : p->packed ? r.job.plans[j].runs : corto_hip::PACKED_RUNS_MAX + 1; }
+	// The tickets of the lane's next call, 0: none left.  A first ticket, then up to group - 1 more while the lists are long - at least
+	// 2 x lanes x group tickets undrawn, so that the end of a run and a short crthip_pool_decode still spread over all lanes, one item a call.
+	// Members are all resident on this device or all uploaded; crthip_pool_decode's lists hold this slot's own device-destination items and
+	// host items only, so no group mixes slots
+	uint32_t gather(const Lane &L, Ticket *tk) {
+		if(!held.empty()) { tk[0] = held.front(); held.erase(held.begin()); }
+		else for(int d = 2; d == 2; ) { d = r.draw(slot, tk[0]); if(d == 0) return 0; }
+		uint32_t ntk = 1;
+		const bool first_batch = p->pipelined && !L.staged && L.s[L.cur].item < 0;   // (of this lane in this run: one item, to learn whether such a batch can be carried)
+		uint32_t runs = runs_of(tk[0].j);
+		const uint32_t want = tk[0].solo || L.alone || first_batch || runs > corto_hip::PACKED_RUNS_MAX ? 1u : p->group;
+		while(ntk < want) {
+			Ticket x;
+			if(!held.empty()) { if(held.front().solo) break; x = held.front(); held.erase(held.begin()); }
+			else {
+				const uint64_t nx = p->next.load();
+				if(nx >= r.total || r.total - nx < 2ull*p->lanes.size()*p->group) break;
+				const int d = r.draw(slot, x);
+				if(d == 0) break;
+				if(d == 2) continue;
+			}
+			if(resident(x.j) != resident(tk[0].j) || runs + runs_of(x.j) > corto_hip::PACKED_RUNS_MAX) { held.push_back(x); break; }
+			runs += runs_of(x.j);
+			tk[ntk++] = x;
+		}
+		return ntk;
+	}
+	// one call on a lane that is not busy: gather its tickets, plan them on the free batch object, enqueue.  false: no ticket is left
+	bool refill(Lane &L) {
+		Ticket tk[GROUP_MAX];
+		const uint32_t ntk = gather(L, tk);
+		if(!ntk) { tickets = false; return false; }
+		const auto h0 = Clock::now();
+		const bool lp = p->pipelined && (L.pipe || L.staged);       // this refill pipelines
+		const uint32_t t = lp ? (L.staged ? L.cur : L.cur ^ 1u) : L.cur;   // the free batch object
+		Slot &T = L.s[t];
+		T.mem.clear();
+		for(uint32_t k = 0; k < ntk; k++) T.mem.push_back(r.member_of(tk[k]));
+		bool item_fault = false;
+		err = lane_plan(p, L, T, r.job, &item_fault);
+		{ const uint64_t ns_ = ns_since(h0); r.plan_ns += ns_; Run::raise_max(r.plan_max_ns, ns_); }
+		if(err && item_fault && ntk > 1) {                           // one member's own failure: each of them alone, so that the bad item alone gets the code
+			for(uint32_t k = 0; k < ntk; k++) { tk[k].solo = true; held.push_back(tk[k]); }
+			err = CRTHIP_OK; return true;
+		}
+		if(err && r.dec && item_fault) { r.settle(slot, tk[0].j, err, nullptr, 0); err = CRTHIP_OK; return true; }   // the item's own failure: the lane draws the next one
+		if(err) return true;
+		const auto d0 = Clock::now();
+		if(lp && !L.staged) { err = crthip_batch_decode_with_next(nullptr, T.batch); L.staged = !err; }   // the lane's first ticket of a run: its entropy stage alone
+		else {
+			L.cur = lp ? L.cur ^ 1u : t;                             // whose mesh stage runs now: the batch planned one refill ago, else this one
+			err = enqueue_mesh(L, lp ? Mesh::WITH_NEXT : Mesh::DECODE);
+		}
+		Run::raise_max(r.launch_max_ns, ns_since(d0));
+		r.host_ns += ns_since(h0); r.host_steps += ntk;             // (per ticket)
+		return true;
+	}
+	void flush() { for(uint32_t k = 0; k < p->depth; k++) if(mine[k].busy) { const int e2 = finish(mine[k]); if(!err) err = e2; } }
+	// A context whose thread drew none of the last 2 x lanes tickets (descheduled while the others emptied the queue: seen with
+	// 32-blob items) repeats its last step from a poisoned block, behind the timed region: what lane_read returns is then ALWAYS
+	// a poisoned step's output, not only almost always
+	void repeat_unpoisoned() {
+		for(uint32_t k = 0; k < p->depth && !err; k++) {
+			Lane &L = mine[k];
+			Slot &S = L.s[L.cur];
+			if(S.item < 0) {                                         // ... and one that drew no ticket at all (a 28-step run on a cold box) decodes its device's first item
+				bool item_fault = false;
+				Ticket k0; k0.j = r.home[slot].empty() ? 0u : r.home[slot][0]; k0.step = r.total;
+				S.mem.assign(1, r.member_of(k0));
+				err = lane_plan(p, L, S, r.job, &item_fault);
+				if(err) break;
+			}
+			if(L.poisoned || !L.out) continue;
+			S.step = r.total;                                        // (a repeat is nobody's timed step, and past poison_from)
+			for(Member &m : S.mem) m.step = r.total;
+			err = enqueue_mesh(L, Mesh::DECODE);
+			if(!err) err = finish(L);
+		}
+	}
+	void run() {
 		(void)hipSetDevice(p->devices[slot]);
-		if(!p->cpus[slot].empty()) {                             // next to the GPU: plan + launch are ~200 us of host work per step and thread
+		if(!p->cpus[slot].empty()) {                                 // next to the GPU: plan + launch are ~200 us of host work per step and thread
 			cpu_set_t set; CPU_ZERO(&set);
 			for(int c : p->cpus[slot]) CPU_SET(c, &set);
 			(void)pthread_setaffinity_np(pthread_self(), sizeof set, &set);   // (a cpuset that forbids them: stay where we are)
 		}
-		Lane *mine = &p->lanes[((size_t)slot*p->threads_per_device + t)*p->depth];
-		// crthip_pool_decode: item j is final - `code` in every status entry (it could not be planned, or holds no blob), or S's statuses
-		// (the statuses of its blobs, which begin at `first` in the group's batch object)
-		auto settle = [&](uint32_t j, int32_t code, const Slot *S, uint32_t first) {
-			const ItemPlan &P = job.plans[j];
-			int32_t *st = job.status + P.status_at;
-			for(uint32_t i = 0; i < items[j].nblobs; i++) st[i] = S ? S->status[first + i] : code;
-			if(!S) {
-				++p->completed;
-				if(code) { failed += items[j].nblobs; int32_t z = 0; first_error.compare_exchange_strong(z, code); }
-			}
-			per_dev[slot]++;
-			if(job.done) job.done(job.user, j, slot, st);
-		};
-		auto finish = [&](Lane &L) -> int {
-			Slot &S = L.s[L.cur];
-			const int rc = crthip_batch_sync(S.batch, S.status.data());
-			L.busy = false;
-			// every member of the group is a step of its own: a completion and a stamp each (the same instant), counted by its own step number
-			const double t_done = now_s();
-			if(S.mem.size() > 1) grouped += S.mem.size();
-			for(const Member &m : S.mem) {
-				const uint64_t c = ++p->completed;               // completion order
-				if(c <= timed_end) stamps[c] = t_done;
-				if(!dec && m.step >= warmup && m.step < timed_end) { per_dev[slot]++; tris += job.plans[(size_t)m.item].tris; verts += job.plans[(size_t)m.item].verts; }
-			}
-			uint64_t bad = 0;
-			for(int32_t st_ : S.status) if(st_) { bad++; int32_t z = 0; first_error.compare_exchange_strong(z, st_); }
-			failed += bad;
-			crthip_batch_stats st;
-			if(crthip_batch_get_stats(S.batch, &st) == CRTHIP_OK) fallbacks += st.topology_fallbacks;
-			if(rc == CRTHIP_E_DEVICE || rc == CRTHIP_E_NOMEM) return rc;
-			if(dec) for(const Member &m : S.mem) {
-				if(m.pageable_dst) memcpy(m.pageable_dst, (const uint8_t *)L.host_out + m.lane_off, m.out_used);   // (the copy into the lane's mirror is what the sync waited for)
-				tris += job.plans[(size_t)m.item].tris; verts += job.plans[(size_t)m.item].verts;
-				settle((uint32_t)m.item, 0, &S, m.first);
-			}
-			return CRTHIP_OK;
-		};
-		// the outputs every lane holds after the run were written by a mesh stage that STARTED from a poisoned block: the post-run bit-exact
-		// check cannot pass on bytes an earlier step left behind (on the context's own stream: ordered before the stage's kernels)
-		auto poison = [&](Lane &L, bool due) -> int {
-			L.poisoned = false;
-			if(!due || !L.out) return CRTHIP_OK;
-			const int e = corto_hip::ctx_fill_async(L.ctx, L.out, L.out_cap, POISON);
-			if(e) return e;
-			if(p->to_host && L.host_out) for(const Member &m : L.s[L.cur].mem) memset((uint8_t *)L.host_out + m.lane_off, POISON, m.out_used);
-			L.poisoned = true;
-			return CRTHIP_OK;
-		};
-		// the D2H copy behind the mesh stage just enqueued: a step of outputs_to_host, an item with a host destination
-		auto copy_out = [&](Lane &L, Slot &S) -> int {
-			for(const Member &m : S.mem) {                       // (one copy a member: each has its own destination)
-				if(!m.to_host) continue;
-				const int e = corto_hip::ctx_copy_to_host_async(L.ctx, m.pinned_dst ? m.pinned_dst : (uint8_t *)L.host_out + m.lane_off, (const uint8_t *)L.out + m.lane_off, m.out_used);
-				if(e) return e;
-			}
-			return CRTHIP_OK;
-		};
-		// a drawn ticket as a group member: where its outputs go
-		auto member_of = [&](const Ticket &k) {
-			Member m;
-			m.item = (int64_t)k.j; m.step = k.step; m.to_host = p->to_host;
-			if(dec) {
-				const crthip_pool_dest &D = job.dests[k.j];
-				m.to_host = D.device_slot < 0;
-				if(!m.to_host) m.base = (uint8_t *)D.out;
-				else if(job.plans[k.j].pinned) m.pinned_dst = D.out;
-				else m.pageable_dst = D.out;
-			}
-			return m;
-		};
-		// one ticket from the work lists.  0: none left; 1: `k` is drawn; 2 (crthip_pool_decode): an item with nothing to launch was drawn and settled
-		auto draw = [&](Ticket &k) -> int {
-			k.solo = false;
-			if(!dec) {
-				k.step = p->next.fetch_add(1);
-				if(k.step >= total) return 0;
-				if(!home[slot].empty()) k.j = home[slot][home_next[slot].fetch_add(1) % home[slot].size()];
-				else k.j = (uint32_t)(stolen.fetch_add(1) % nitems);
-				return 1;
-			}
-			if(p->next.load() >= total || !draw_once(slot, k.j)) return 0;
-			k.step = p->next.fetch_add(1);
-			if(job.plans[k.j].err || items[k.j].nblobs == 0) { settle(k.j, job.plans[k.j].err, nullptr, 0); return 2; }
-			return 1;
-		};
-		auto resident = [&](uint32_t j) { return items[j].device_arena && items[j].device_arena[slot]; };
-		// Blobs that must be gathered (scattered host blobs, or packed host blobs off) are not grouped: the gathering is a memcpy on this thread
-		// while its other lanes wait, and two items' worth of it in one piece cost `scattered_pageable_blobs` 29 % (profiles/pool_group.md)
-		auto runs_of = [&](uint32_t j) { return resident(j) ? 0u : p->packed ? job.plans[j].runs : PACKED_RUNS_MAX + 1; };
-		// `held` is consumed before the work lists and `tickets` goes false only when it is empty and the lists are dry: no drawn ticket is lost.
-		// Solo tickets (a refused group's members) and tickets that did not fit a group wait here alike; a solo one is never joined to a group
-		std::vector<Ticket> held;                                // drawn and not planned yet: a ticket that did not fit the group it was drawn for, the members of a group that was refused
-		int err = CRTHIP_OK;
-		auto tick = [] { return std::chrono::steady_clock::now(); };
-		auto ns_since = [](std::chrono::steady_clock::time_point t0) { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); };
-		bool tickets = true;
 		for(uint64_t n = 0; !err && tickets; n++) {
-			const auto w0 = tick();
-			// the next lane to refill: a free one, else whichever of the busy ones finishes first (they mostly finish in the order they
-			// were launched, but a thread that waited on the oldest while a younger one was done left that context idle)
-			uint32_t pick = p->depth;
-			for(uint32_t k = 0; k < p->depth && pick == p->depth; k++) if(!mine[(n + k) % p->depth].busy) pick = (uint32_t)((n + k) % p->depth);
-			for(uint32_t spins = 0; pick == p->depth && !err; spins++) {
-				for(uint32_t k = 0; k < p->depth; k++) {
-					Lane &C = mine[(n + k) % p->depth];
-					const int d = crthip_batch_done(C.s[C.cur].batch);
-					if(d < 0) { err = d; break; }
-					if(d) { pick = (uint32_t)((n + k) % p->depth); break; }
-				}
-				if(pick == p->depth && !err) { if(spins < 64) std::this_thread::yield(); else std::this_thread::sleep_for(std::chrono::microseconds(5)); }
-			}
-			if(err) break;
-			wait_ns += ns_since(w0);
-			Lane &L = mine[pick];
-			const auto f0 = tick();
+			const auto w0 = Clock::now();
+			Lane *const picked = pick_lane(n);
+			if(!picked) break;
+			Lane &L = *picked;
+			r.wait_ns += ns_since(w0);
+			const auto f0 = Clock::now();
 			if(L.busy) err = finish(L);
-			finish_ns += ns_since(f0);
-			if(!err && pipe && !L.staged && L.s[L.cur].item >= 0) {
-				L.pipe = corto_hip::batch_carriable(L.s[L.cur].batch);
-				if(L.s[L.cur].mem.size() == 1) L.single_ok = L.pipe;
-				else if(!L.pipe && L.single_ok) L.alone = true;   // (one item a call pipelines again)
+			r.finish_ns += ns_since(f0);
+			if(!err) note_carry(L);
+			if(!err && L.staged && L.drain) {                        // the planned batch was not carried: its whole decode alone, no ticket drawn
+				L.drain = false; L.pipe = false;
+				err = launch_staged(L);
 			}
-			if(!err && L.staged && L.drain) {                   // the planned batch was not carried: its whole decode alone, no ticket drawn
-				L.cur ^= 1u; L.staged = false; L.drain = false; L.pipe = false;
-				err = poison(L, L.s[L.cur].step >= poison_from);
-				if(!err) err = crthip_batch_decode_with_next(L.s[L.cur].batch, nullptr);
-				if(!err) err = copy_out(L, L.s[L.cur]);
-				if(!err) L.busy = true;
-			}
-			// refill.  A pipelined lane plans the ticket on its free batch object and enqueues [mesh stage of the batch planned one refill ago + entropy
-			// stage of this one]; its first ticket of a run only enqueues an entropy stage, and it draws the next one at once.
-			// (crthip_pool_decode: the two objects are then bound to two different items' blocks.  That is safe: an entropy stage writes its
-			// batch's own scratch and nothing else - corto_hip.h, crthip_batch_decode_with_next - so only the mesh stage in flight writes a block.)
-			while(!err && !L.busy) {
-				// the group: a first ticket, then up to group - 1 more while the lists are long - at least 2 x lanes x group tickets undrawn, so that the end
-				// of a run and a short crthip_pool_decode still spread over all lanes, one item a call.  Members are all resident on this device or all
-				// uploaded; crthip_pool_decode's lists hold this slot's own device-destination items and host items only, so no group mixes slots
-				Ticket tk[GROUP_MAX];
-				uint32_t ntk = 0;
-				if(!held.empty()) { tk[0] = held.front(); held.erase(held.begin()); ntk = 1; }
-				else {
-					const int d = draw(tk[0]);
-					if(d == 0) { tickets = false; break; }
-					if(d == 2) continue;
-					ntk = 1;
-				}
-				const bool first_batch = pipe && !L.staged && L.s[L.cur].item < 0;      // (of this lane in this run: one item, to learn whether such a batch can be carried)
-				uint32_t runs = runs_of(tk[0].j);
-				const uint32_t want = tk[0].solo || L.alone || first_batch || runs > PACKED_RUNS_MAX ? 1u : p->group;
-				while(ntk < want) {
-					Ticket x;
-					if(!held.empty()) { if(held.front().solo) break; x = held.front(); held.erase(held.begin()); }
-					else {
-						const uint64_t nx = p->next.load();
-						if(nx >= total || total - nx < 2ull*p->lanes.size()*p->group) break;
-						const int d = draw(x);
-						if(d == 0) break;
-						if(d == 2) continue;
-					}
-					if(resident(x.j) != resident(tk[0].j) || runs + runs_of(x.j) > PACKED_RUNS_MAX) { held.push_back(x); break; }
-					runs += runs_of(x.j);
-					tk[ntk++] = x;
-				}
-				const auto h0 = std::chrono::steady_clock::now();
-				const bool lp = pipe && (L.pipe || L.staged);                          // this refill pipelines
-				const uint32_t t = lp ? (L.staged ? L.cur : L.cur ^ 1u) : L.cur;        // the free batch object
-				Slot &T = L.s[t];
-				T.mem.clear();
-				for(uint32_t k = 0; k < ntk; k++) T.mem.push_back(member_of(tk[k]));
-				bool item_fault = false;
-				err = lane_plan(p, L, T, job, &item_fault);
-				{ const uint64_t ns_ = ns_since(h0); plan_ns += ns_; raise_max(plan_max_ns, ns_); }
-				if(err && item_fault && ntk > 1) {                   // one member's own failure: each of them alone, so that the bad item alone gets the code
-					for(uint32_t k = 0; k < ntk; k++) { tk[k].solo = true; held.push_back(tk[k]); }
-					err = CRTHIP_OK; continue;
-				}
-				if(err && dec && item_fault) { settle(tk[0].j, err, nullptr, 0); err = CRTHIP_OK; continue; }   // the item's own failure: the lane draws the next one
-				if(err) break;
-				const auto d0 = std::chrono::steady_clock::now();
-				if(lp && !L.staged) {
-					err = crthip_batch_decode_with_next(nullptr, T.batch);
-					L.staged = !err;
-				} else {
-					const uint32_t m = lp ? L.cur ^ 1u : t;                              // whose mesh stage runs now
-					L.cur = m;
-					err = poison(L, L.s[m].step >= poison_from);
-					if(!err) err = lp ? crthip_batch_decode_with_next(L.s[m].batch, T.batch) : crthip_batch_decode(T.batch);
-					if(!err && lp) L.drain = !corto_hip::batch_entropy_done(T.batch);
-					if(!err) err = copy_out(L, L.s[m]);
-					if(!err) L.busy = true;
-				}
-				raise_max(launch_max_ns, ns_since(d0));
-				host_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - h0).count(); host_steps += ntk;   // (per ticket)
-			}
+			while(!err && !L.busy && refill(L)) { }
 		}
-		for(uint32_t k = 0; k < p->depth; k++) if(mine[k].busy) { const int e2 = finish(mine[k]); if(!err) err = e2; }
-		// no ticket left: the mesh stage of every lane's planned batch, alone
-		for(uint32_t k = 0; k < p->depth && !err; k++) {
-			Lane &L = mine[k];
-			if(!L.staged) continue;
-			L.cur ^= 1u; L.staged = false;
-			err = poison(L, L.s[L.cur].step >= poison_from);
-			if(!err) err = crthip_batch_decode_with_next(L.s[L.cur].batch, nullptr);
-			if(!err) err = copy_out(L, L.s[L.cur]);
-			if(!err) L.busy = true;
-		}
-		for(uint32_t k = 0; k < p->depth; k++) if(mine[k].busy) { const int e2 = finish(mine[k]); if(!err) err = e2; }
-		// a context whose thread drew none of the last 2 x lanes tickets (descheduled while the others emptied the queue: seen with
-		// 32-blob items) repeats its last step from a poisoned block, behind the timed region: what lane_read returns is then ALWAYS
-		// a poisoned step's output, not only almost always
-		for(uint32_t k = 0; k < p->depth && !err && !dec; k++) {
-			Lane &L = mine[k];
-			Slot &S = L.s[L.cur];
-			if(S.item < 0) {                                     // ... and one that drew no ticket at all (a 28-step run on a cold box) decodes its device's first item
-				const uint32_t j = home[slot].empty() ? 0u : home[slot][0];
-				bool item_fault = false;
-				Ticket k0; k0.j = j; k0.step = total;
-				S.mem.assign(1, member_of(k0));
-				err = lane_plan(p, L, S, job, &item_fault);
-				if(err) break;
-			}
-			if(L.poisoned || !L.out) continue;
-			for(Member &m : S.mem) m.step = total;               // (a repeat is nobody's timed step)
-			err = poison(L, true);
-			if(!err) err = crthip_batch_decode(S.batch);
-			if(!err) err = copy_out(L, S);
-			if(!err) { L.busy = true; err = finish(L); }
-		}
+		flush();
+		for(uint32_t k = 0; k < p->depth && !err; k++) if(mine[k].staged) err = launch_staged(mine[k]);   // no ticket left: the mesh stage of every lane's planned batch, alone
+		flush();
+		if(!r.dec) repeat_unpoisoned();
 		if(err) {
 			std::lock_guard<std::mutex> lock(p->m);
 			if(!p->error) { p->error = err; p->error_msg = crthip_last_error(); }
-			p->next = total;                                     // stop handing out work
+			p->next = r.total;                                       // stop handing out work
 		}
-	};
+	}
+};
+
+static int pool_work(crthip_pool *p, PoolJob &job, crthip_pool_report *report) {
+	p->next = 0; p->completed = 0; p->error = CRTHIP_OK; p->error_msg.clear();
+	for(auto &L : p->lanes) L.begin_run();
+	Run r(p, job);
+	const double t_launch = r.stamps[0] = now_s();
 	std::vector<std::thread> threads;
 	for(uint32_t d = 0; d < p->ndevices; d++)
-		for(uint32_t t = 0; t < p->threads_per_device; t++) threads.emplace_back(worker, d, t);
+		for(uint32_t t = 0; t < p->threads_per_device; t++) threads.emplace_back([&r, d, t] { Worker(r, d, t).run(); });
 	for(auto &th : threads) th.join();
 	const double t_joined = now_s();
-	if(dec) for(auto &L : p->lanes) for(Slot &S : L.s) { S.item = -1; S.binds.clear(); }   // (the destinations are the caller's again)
+	if(r.dec) for(auto &L : p->lanes) for(Slot &S : L.s) { S.item = -1; S.binds.clear(); }   // (the destinations are the caller's again)
 	if(p->error) return ctx_fail(p->error, p->error_msg.c_str());
-	if(!report) return CRTHIP_OK;
-	report->elapsed_s = dec ? t_joined - t_launch : stamps[timed_end] - stamps[warmup];
-	report->steps = dec ? nitems : steps; report->triangles = tris; report->vertices = verts;
-	report->failed_blobs = failed; report->first_error = first_error; report->topology_fallbacks = fallbacks; report->grouped_steps = grouped;
-	for(uint32_t d = 0; d < p->ndevices; d++) { report->steps_per_device[d] = per_dev[d]; if(per_dev[d]) report->devices_used++; }
-	if(!dec) for(auto &L : p->lanes) if(L.s[L.cur].item >= 0 && L.poisoned) report->poisoned_lanes++;
-	report->host_us_per_step = host_steps ? (float)((double)host_ns/1e3/(double)host_steps) : 0.f;
-	if(host_steps) {
-		report->host_wait_us = (float)((double)wait_ns/1e3/(double)host_steps); report->host_finish_us = (float)((double)finish_ns/1e3/(double)host_steps);
-		report->host_plan_us = (float)((double)plan_ns/1e3/(double)host_steps);
-		report->host_plan_max_us = (float)((double)plan_max_ns/1e3); report->host_launch_max_us = (float)((double)launch_max_ns/1e3);
-	}
-	for(uint32_t d = 0; d < p->ndevices; d++) if(!p->cpus[d].empty()) report->pinned_devices++;
-	if(job.completion_s) for(uint64_t c = 0; c < steps; c++) job.completion_s[c] = stamps[warmup + 1 + c] - stamps[warmup];
+	if(report) r.fill_report(*report, t_joined - t_launch);
 	return CRTHIP_OK;
 }
 
@@ -684,19 +697,6 @@ extern "C" int crthip_pool_run(crthip_pool *p, uint32_t nitems, const crthip_poo
 	}
 	p->decoded = false;
 	return pool_work(p, job, report);
-}
-
-// a device destination: device memory of `device`, [q, q + bytes) inside one allocation (the resident encoder's check, encode_batch.cpp)
-static bool device_block_ok(const void *q, uint64_t bytes, int device) {
-	hipPointerAttribute_t a;
-	memset(&a, 0, sizeof(a));
-	if(hipPointerGetAttributes(&a, q) != hipSuccess) { (void)hipGetLastError(); return false; }   // (memory the runtime has never seen)
-	if(a.type != hipMemoryTypeDevice || a.device != device) return false;                          // pinned and managed memory included
-	hipDeviceptr_t base = nullptr;
-	size_t size = 0;
-	if(hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)q) != hipSuccess) { (void)hipGetLastError(); return false; }
-	const uintptr_t b = (uintptr_t)base, x = (uintptr_t)q;
-	return x >= b && bytes <= size && x - b <= size - bytes;
 }
 
 extern "C" int crthip_pool_decode(crthip_pool *p, uint32_t nitems, const crthip_pool_item *items, const crthip_pool_dest *dests,
@@ -726,7 +726,8 @@ extern "C" int crthip_pool_decode(crthip_pool *p, uint32_t nitems, const crthip_
 		if(D.cap < P.total) return bad(j, "cap is smaller than the layout's total");
 		if(!P.total) continue;
 		if(D.device_slot >= 0) {
-			if(!device_block_ok(D.out, P.total, p->devices[(uint32_t)D.device_slot]))
+			// device memory of the slot's GPU, [out, out + total) inside one allocation (the resident encoder's check, encode_batch.cpp)
+			if(!corto_hip::resident_array_ok(D.out, P.total, 1, p->devices[(uint32_t)D.device_slot]))
 				return bad(j, "out is not device memory of the slot's GPU, or [out, out + total) leaves its allocation");
 		} else {
 			hipPointerAttribute_t a;
@@ -760,15 +761,14 @@ extern "C" int64_t crthip_pool_lane_read(crthip_pool *p, uint32_t lane, uint32_t
 	crthip_blob_info info;
 	int err = crthip_batch_info(S.batch, blob, &info);
 	if(err) return err;
+	// what the arrays hold is the layout's business (output_layout.h): the blob's entries under the pool's flags give the byte counts
+	crthip_out_array arrays[CRTHIP_MAX_ATTRS], index; uint64_t end = 0;
+	corto_hip::layout_blob(info, p->render ? CRTHIP_LAYOUT_RENDER : 0u, end, arrays, &index);
 	const uint8_t *src = nullptr; size_t n = 0;
 	if(!strcmp(what, "#tail")) { n = L.out_cap < 256 ? L.out_cap : 256; src = (const uint8_t *)L.out + (L.out_cap - n); }   // the block's last bytes: behind every output array
-	else if(!strcmp(what, "index")) { if(!info.nface) return 0; src = (const uint8_t *)S.index_ptr[blob]; n = (size_t)info.nface*(S.index_fmt[blob] == CRTHIP_FMT_UINT16 ? 6 : 12); }
+	else if(!strcmp(what, "index")) { if(!info.nface) return 0; src = (const uint8_t *)S.index_ptr[blob]; n = (size_t)index.bytes; }
 	else {
-		for(uint32_t k = 0; k < info.nattr; k++) if(!strcmp(info.attr[k].name, what)) {
-			const crthip_attr_info &a = info.attr[k];
-			src = (const uint8_t *)S.binds[S.first_attr[blob] + k].buffer;
-			n = a.codec == CRTHIP_CODEC_NORMAL ? (size_t)info.nvert*(S.binds[S.first_attr[blob] + k].format == CRTHIP_FMT_INT16 ? 6 : 12) : a.codec == CRTHIP_CODEC_COLOR ? (size_t)info.nvert*4 : (size_t)info.nvert*a.components*4;
-		}
+		for(uint32_t k = 0; k < info.nattr; k++) if(!strcmp(info.attr[k].name, what)) { src = (const uint8_t *)S.binds[S.first_attr[blob] + k].buffer; n = (size_t)arrays[k].bytes; }
 		if(!src) return ctx_fail(CRTHIP_E_ARGUMENT, "no such attribute");
 	}
 	if(n > cap) n = cap;
