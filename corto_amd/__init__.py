@@ -231,6 +231,7 @@ def lib():
         L.crthip_batch_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BlobInfo)]
         L.crthip_batch_bind.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
         L.crthip_batch_bind_all.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.crthip_batch_bind_computed_normals.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
         L.crthip_batch_decode.argtypes = [C.c_void_p]
         L.crthip_batch_decode_with_next.argtypes = [C.c_void_p, C.c_void_p]
         L.crthip_batch_set_parity.argtypes = [C.c_void_p, C.c_uint32]
@@ -1051,6 +1052,7 @@ class Batch:
             self.infos.append(info)
         self.outputs: List[Dict[str, object]] = []
         self._keep = None
+        self._computed = []                          # (blob, pointer, format, stride): what rebind() applies again behind crthip_batch_bind_all
         self._interleaved = None
 
     def __len__(self):
@@ -1094,9 +1096,11 @@ class Batch:
 
     # -- outputs -----------------------------------------------------------------------------------
     def allocate_outputs(self, normal_format=FMT_FLOAT, color_components: Optional[int] = None, index16=False,
-                         only: Optional[set] = None, fill: Optional[int] = None):
+                         only: Optional[set] = None, fill: Optional[int] = None, computed_normals=False):
         """Allocate every output of every blob inside ONE device buffer (torch.uint8) and bind them.
-        Returns a list (per blob) of dicts name -> torch tensor view."""
+        Returns a list (per blob) of dicts name -> torch tensor view.
+        computed_normals: every mesh blob WITHOUT a normal attribute gets a "normal" tensor of normal_format all the same, bound
+        through crthip_batch_bind_computed_normals - upstream's estimate at every vertex (include/corto_hip.h)."""
         import torch
         dev = torch.device("cuda", self.ctx.device)
         plan = []   # (blob, name, offset, nbytes, dtype, shape, binding_slot)
@@ -1121,6 +1125,10 @@ class Batch:
                     plan.append((i, a["name"], take(nv * oc), "u8", (nv, oc), k, FMT_UINT8, oc))
                 else:
                     plan.append((i, a["name"], take(nv * a["components"] * 4), "f32", (nv, a["components"]), k, FMT_FLOAT, 0))
+            if (computed_normals and nf and (only is None or "normal" in only)
+                    and not any(a["codec"] == CODEC_NORMAL or a["name"] == "normal" for a in info.attrs())):
+                dt = "f32" if normal_format == FMT_FLOAT else "i16"
+                plan.append((i, "normal", take(nv * 3 * np.dtype(_DT[dt]).itemsize), dt, (nv, 3), -2, normal_format, 0))
             if nf and (only is None or "index" in only):
                 dt = "u16" if index16 else "u32"
                 plan.append((i, "index", take(nf * 3 * np.dtype(_DT[dt]).itemsize), dt, (nf, 3), -1, FMT_UINT16 if index16 else FMT_UINT32, 0))
@@ -1134,6 +1142,7 @@ class Batch:
         index_ptrs = (C.c_void_p * max(len(self), 1))()
         index_fmt = np.full(max(len(self), 1), FMT_UINT32, dtype=np.uint32)
         outs = [dict() for _ in self.infos]
+        computed = []
         tdt = {"f32": torch.float32, "i16": torch.int16, "u8": torch.uint8, "u32": torch.int32, "u16": torch.int16}
         for (i, name, o, dt, shape, slot, fmt, oc) in plan:
             nbytes = int(np.prod(shape)) * np.dtype(_DT[dt]).itemsize
@@ -1142,9 +1151,12 @@ class Batch:
             if slot >= 0:
                 bd = binds[int(first[i]) + slot]
                 bd.buffer = base + o; bd.format = fmt; bd.out_components = oc
+            elif slot == -2:
+                computed.append((i, base + o, fmt, 0))
             else:
                 index_ptrs[i] = base + o; index_fmt[i] = fmt
         self._keep = (buf, binds, index_ptrs, index_fmt)
+        self._computed = computed
         self._interleaved = None
         self.outputs = outs
         self.rebind()
@@ -1196,6 +1208,7 @@ class Batch:
             if ib is not None:
                 index_ptrs[i] = base + ib; index_fmt[i] = FMT_UINT16 if i16 else FMT_UINT32
         self._keep = (buf, binds, index_ptrs, index_fmt)
+        self._computed = []
         self._interleaved = metas
         self.outputs = [dict() for _ in self.infos]
         self.rebind()
@@ -1237,10 +1250,18 @@ class Batch:
         """(Re)apply the bindings prepared by allocate_outputs: one C call for the whole batch."""
         buf, binds, index_ptrs, index_fmt = self._keep
         _check(lib().crthip_batch_bind_all(self.handle, binds, index_ptrs, _np_ptr(index_fmt)))
+        for (i, ptr, fmt, stride) in self._computed:          # (a bind drops a blob's computed-normals binding)
+            _check(lib().crthip_batch_bind_computed_normals(self.handle, i, C.c_void_p(ptr), fmt, stride))
 
     def bind(self, i: int, bindings: Sequence[AttrBinding], index_ptr: Optional[int] = None, index_format=FMT_UINT32):
         arr = (AttrBinding * max(len(bindings), 1))(*bindings)
         _check(lib().crthip_batch_bind(self.handle, i, arr, C.c_void_p(index_ptr) if index_ptr else None, index_format))
+
+    def bind_computed_normals(self, i: int, ptr: Optional[int], fmt=FMT_FLOAT, stride: int = 0):
+        """crthip_batch_bind_computed_normals: blob i stores no normals (or leaves them unbound) - upstream's estimate at every vertex goes
+        to the device pointer `ptr` (nvert*3 f32 or i16; stride as for a stored normal).  After bind() / rebind() of that blob, which drop
+        it; ptr None or 0 removes it."""
+        _check(lib().crthip_batch_bind_computed_normals(self.handle, i, C.c_void_p(ptr) if ptr else None, fmt, stride))
 
     def host_outputs(self, i: int) -> Dict[str, np.ndarray]:
         """Copy blob i's outputs to the host as numpy arrays with the reference's dtypes."""

@@ -213,7 +213,8 @@ extern "C" int crthip_ctx_create(int device, crthip_ctx **out) {
 	   hipFuncSetAttribute((const void *)k_topology_lds_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TOPO_LDS_MAX) != hipSuccess ||
 	   hipFuncSetAttribute((const void *)k_delta_lds16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DELTA16_LDS_MAX) != hipSuccess ||
 	   hipFuncSetAttribute((const void *)k_delta_lds16_carry, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DELTA16_LDS_MAX) != hipSuccess ||
-	   hipFuncSetAttribute((const void *)k_normal_blob, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NORMAL_LDS_MAX) != hipSuccess ||
+	   hipFuncSetAttribute((const void *)k_normal_blob<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NORMAL_LDS_MAX) != hipSuccess ||
+	   hipFuncSetAttribute((const void *)k_normal_blob<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NORMAL_LDS_MAX) != hipSuccess ||
 	   hipFuncSetAttribute((const void *)k_enc_topo_walk<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ENC_TOPO_LDS_MAX) != hipSuccess ||
 	   hipFuncSetAttribute((const void *)k_enc_tun_parse, hipFuncAttributeMaxDynamicSharedMemorySize,
 	   	(int)enc_parse_lds(ENC_TRIE_LDS_MAX)) != hipSuccess) {
@@ -308,7 +309,7 @@ static int batch_fill(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs, const u
 		if(err) return fail(err, std::string(crthip_strerror(err)) + " (blob " + std::to_string(i) + ")");
 		P.arena_off = device_arena && dev_off ? dev_off[i] : off; P.len = lens[i];
 		P.bind.assign(P.L.h.attrs.size(), Binding{});
-		P.index = nullptr; P.index_u16 = 0; P.host_status = 0;
+		P.index = nullptr; P.index_u16 = 0; P.host_status = 0; P.computed = Binding{};
 		P.dbg_clers = P.dbg_pred = ~0ull; P.dbg_nclers = 0; P.clers_in_arena = false;
 		off += ((uint64_t)lens[i] + 15) & ~15ull;
 		b->stats.total_nvert += P.L.h.nvert; b->stats.total_nface += P.L.h.nface;
@@ -467,7 +468,7 @@ static int batch_fill_resident(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs
 		if(err) { b->blobs.clear(); return fail(err, std::string(crthip_strerror(err)) + " (blob " + std::to_string(i) + ")"); }
 		P.arena_off = offsets[i]; P.len = lens[i];
 		P.bind.assign(P.L.h.attrs.size(), Binding{});
-		P.index = nullptr; P.index_u16 = 0; P.host_status = 0;
+		P.index = nullptr; P.index_u16 = 0; P.host_status = 0; P.computed = Binding{};
 		P.dbg_clers = P.dbg_pred = ~0ull; P.dbg_nclers = 0; P.clers_in_arena = false;
 		bytes += ((uint64_t)lens[i] + 15) & ~15ull;
 		b->stats.total_nvert += P.L.h.nvert; b->stats.total_nface += P.L.h.nface;
@@ -600,6 +601,35 @@ extern "C" int crthip_batch_bind(crthip_batch *b, uint32_t i, const crthip_attr_
 		P.bind[k].stream_values = (attrs[k].reserved & CRTHIP_BIND_STREAM_VALUES) != 0;
 	}
 	P.index = index; P.index_u16 = index && index_format == CRTHIP_FMT_UINT16;
+	P.computed = Binding{};                                                 // (crthip_batch_bind_computed_normals comes after the bind)
+	b->dirty = true;
+	return CRTHIP_OK;
+}
+
+// Normals for a mesh whose blob stores none (or leaves its stored ones unbound): every check is made here, so that the decode has nothing new to fail on
+extern "C" int crthip_batch_bind_computed_normals(crthip_batch *b, uint32_t i, void *buffer, uint32_t format, uint32_t stride) {
+	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_computed_normals: no such blob");
+	BlobPlan &P = b->blobs[i];
+	const std::string who = " (blob " + std::to_string(i) + ")";
+	if(!buffer) { P.computed = Binding{}; b->dirty = true; return CRTHIP_OK; }
+	if(P.L.h.nface == 0) return fail(CRTHIP_E_ARGUMENT, "computed normals need faces: a point cloud has none" + who);
+	int pos_k = -1;
+	for(size_t k = 0; k < P.bind.size(); k++) {
+		const AttrHeader &a = P.L.h.attrs[k];
+		if(a.name == "normal" && P.bind[k].buffer) return fail(CRTHIP_E_ARGUMENT, "the blob's stored normals are bound: computed normals take an unbound or absent attribute" + who);
+		if(a.name == "position") pos_k = (int)k;
+	}
+	// what a stored normal's binding must be (check_binding)
+	AttrHeader as_normal; as_normal.codec = CRTHIP_CODEC_NORMAL;
+	crthip_attr_binding bd{};
+	bd.buffer = buffer; bd.format = format; bd.stride = stride;
+	const int err = check_binding(as_normal, bd);
+	if(err) return fail(err, std::string(crthip_strerror(err)) + " (computed normals)" + who);
+	// ... and what a stored ESTIMATED normal asks of the position (plan_jobs.cpp; src/normal_attribute.cpp:210-227)
+	if(pos_k < 0 || P.L.h.attrs[pos_k].codec != CRTHIP_CODEC_GENERIC || P.L.h.attrs[pos_k].N != 3 || !P.bind[pos_k].buffer || P.bind[pos_k].stream_values)
+		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "computed normals need a bound three-component \"position\" (bind the blob first)" + who);
+	P.computed.buffer = buffer; P.computed.format = format;
+	P.computed.stride = stride == (format == CRTHIP_FMT_INT16 ? 6u : 12u) ? 0u : stride;
 	b->dirty = true;
 	return CRTHIP_OK;
 }

@@ -84,9 +84,10 @@ struct BlobScratch {
 	uint64_t clers = ~0ull, pred = ~0ull, front_a = ~0ull, front_b = ~0ull, order = ~0ull, delayed = ~0ull, faces = ~0ull;
 	uint64_t progress = ~0ull;                              // the automaton's progress word (zeroed): blobs with an attribute too big for K-DELTA's LDS records
 	uint32_t front_cap = 0, aux_groups = 0;
+	uint64_t cn_facen = ~0ull;                              // computed normals (BlobPlan::computed) by the fused kernel without its face normals in LDS: AttrScratch::facen's counterpart
 	std::vector<AttrScratch> attr;
 	size_t nattr = 0;                                       // attr[0..nattr) are this decode's (the vector only grows)
-	void reset() { clers = pred = front_a = front_b = order = delayed = faces = progress = ~0ull; front_cap = 0; aux_groups = 0; nattr = 0; }
+	void reset() { clers = pred = front_a = front_b = order = delayed = faces = progress = cn_facen = ~0ull; front_cap = 0; aux_groups = 0; nattr = 0; }
 	void set_attrs(size_t n) { if(attr.size() < n) attr.resize(n); for(size_t k = nattr; k < n; k++) attr[k].reset();
 		if(n > nattr) nattr = n; }
 };
@@ -108,8 +109,8 @@ struct Plan {
 	HostArr<DeltaJob> delta;
 	HostArr<DeltaGroup> delta_groups;                       // blobs whose attributes share one k_delta_lds16 workgroup
 	HostArr<CloudJob> cloud; HostArr<uint32_t> cloud_chunk_job;
-	HostArr<NormalJob> normal; HostArr<uint32_t> nv_block_job, nv_block_first, nf_block_job, nf_block_first, normal_fused_ids;
-	uint32_t normal_fused_lds = 0;
+	HostArr<NormalJob> normal; HostArr<uint32_t> nv_block_job, nv_block_first, nf_block_job, nf_block_first, normal_fused_ids, normal_computed_ids;
+	uint32_t normal_fused_lds = 0, normal_computed_lds = 0;   // (computed: k_normal_blob<true>'s id list and LDS request)
 	HostArr<DequantJob> dequant; HostArr<uint32_t> dequant_block_job;
 	// scratch regions (offsets)
 	uint64_t zero_begin = 0, zero_end = 0;
@@ -127,12 +128,12 @@ struct Plan {
 		f(tun); f(tun_dict); f(tun_chunk_stream); f(tun_group_ids); f(tun_groups); f(fill); f(topo); f(aux_u32); f(topo_lds_ids); f(topo_big_ids);
 		f(topo_glob_ids); f(unpack); f(unpack_chunk_job); f(unpack_wave_ids);
 		f(delta); f(delta_groups); f(cloud); f(cloud_chunk_job); f(normal); f(nv_block_job); f(nv_block_first); f(nf_block_job); f(nf_block_first);
-		f(normal_fused_ids); f(dequant); f(dequant_block_job);
+		f(normal_fused_ids); f(normal_computed_ids); f(dequant); f(dequant_block_job);
 	}
 	void reset() {                                          // keep every vector's capacity
 		each_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
 		clers_groups = 0; topo_need.clear();
-		topo_lds = topo_big_lds = normal_fused_lds = 0;
+		topo_lds = topo_big_lds = normal_fused_lds = normal_computed_lds = 0;
 		zero_begin = zero_end = tables_off = tun_partial_off = unpack_partial_off = cloud_partial_off = 0;
 		facen_off = cnt_off = cursor_off = bnd_off = start_off = flag_off = slot_off = adj_off = nscan_partial_off = 0;
 		jobs_begin = jobs_bytes = 0; est_nvert = est_nface = 0; delta16_lds = 0;
@@ -230,6 +231,7 @@ struct BlobPlan {
 	uint32_t len = 0;
 	std::vector<Binding> bind;
 	void *index = nullptr; uint32_t index_u16 = 0;
+	Binding computed;          // crthip_batch_bind_computed_normals: where the normals of a blob that stores (or binds) none go; dropped by every bind / reset
 	int32_t host_status = 0;   // set by the planner (e.g. unsupported format), overrides device status
 	// debug handles (scratch offsets valid after decode)
 	uint64_t dbg_clers = ~0ull, dbg_pred = ~0ull; uint32_t dbg_nclers = 0;
@@ -292,6 +294,12 @@ static inline uint64_t delta_lds_need(const DeltaJob &d, bool wide) {          /
 	return (uint64_t)delta_vbytes(d.nvert, d.N, d.is_u8 != 0, wide) + delta16_graph_lds(d.nvert, delta_hosts_a(d));
 }
 static inline bool delta_in_lds(const DeltaJob &d, bool wide) { return delta_lds_need(d, wide) <= DELTA16_LDS_MAX; }
+// the computed normals of a blob: bound, a mesh, and no stored "normal" attribute bound beside them (the bind call sees to all three)
+static inline bool computes_normals(const BlobPlan &P) {
+	if(!P.computed.buffer || P.L.h.nface == 0) return false;
+	for(size_t k = 0; k < P.bind.size(); k++) if(P.L.h.attrs[k].name == "normal" && P.bind[k].buffer) return false;
+	return true;
+}
 static bool normal_fused(uint32_t nvert, uint32_t nface) { return nvert <= 32767 && (uint64_t)3*nface <= 65535 && normal_blob_lds(nvert,
 	nface) <= NORMAL_LDS_MAX; }
 

@@ -141,7 +141,8 @@ struct NormalJob {
 	uint32_t nvert, nface, ndiffs;
 	uint32_t vbase, fbase;         // offsets into the batch-wide per-vertex / per-face scratch arrays
 	int32_t unit;                  // (int)q
-	uint8_t prediction, out_i16, faces_u16, fused;   // fused: handled by k_normal_blob (whole pipeline in one workgroup)
+	uint8_t prediction, out_i16, faces_u16, fused;   // prediction: 0 DIFF, 1 ESTIMATED, 2 BORDER as stored; 3 COMPUTED: no stored attribute, no diffs (crthip_batch_bind_computed_normals)
+	                                                 // fused: handled by k_normal_blob<false> / <true> (whole pipeline in one workgroup)
 	int32_t *status;
 	uint32_t out_stride;           // bytes from one vertex's normal to the next (12 or 6 when packed)
 	// k_normal_blob is the last reader of the integer positions and turns them into floats itself (no k_dequant launch):

@@ -5,6 +5,8 @@
 //                              in face order (float addition order is part of the result)
 //     markBoundary    :24-37   XOR of neighbour ids (order-free -> atomicXor)
 //     computeNormals  :281-325 toOcta(est) + diff[slot] -> toSphere, or est/|est|
+//   COMPUTED (prediction 3, crthip_batch_bind_computed_normals): no stored attribute at all - every vertex takes computeNormals'
+//     no-correction branch (:294-302, :320-323), and a vertex whose estimate is zero gets (0,0,1)
 //
 // Ordered accumulation without a serial pass over faces: build a CSR of incident faces per vertex with
 // atomics (arbitrary order), then each vertex walks its own short list in ascending face id.  All float
@@ -134,7 +136,7 @@ __global__ __launch_bounds__(256) void k_normal_flags(const NormalJob *__restric
 	if(J.prediction == 0 || J.fused) return;            // DIFF / fused jobs own no slice of the per-vertex scratch
 	const uint32_t i = (blockIdx.x - block_first[block_job[blockIdx.x]])*256 + threadIdx.x;
 	if(i >= J.nvert) return;
-	flag[J.vbase + i] = (J.prediction == 1 || bnd[J.vbase + i] != 0) ? 1u : 0u;
+	flag[J.vbase + i] = (J.prediction == 1 || (J.prediction == 2 && bnd[J.vbase + i] != 0)) ? 1u : 0u;   // (COMPUTED: no vertex takes a correction)
 }
 
 // ---- step 4: per vertex ordered accumulation + computeNormals ----
@@ -179,15 +181,16 @@ __global__ __launch_bounds__(256) void k_normal_vertex(const NormalJob *__restri
 		store_normal(J, i, nx, ny, nz);
 	} else if(J.out_i16) {                              // normal_attribute.cpp:294-302
 		float len = norm3(ex, ey, ez);
+		int16_t *o = (int16_t *)((uint8_t *)J.out + (size_t)i*J.out_stride);
 		if(!(len < 0.00001f)) {
 			len = 32767.0f/len;
-			int16_t *o = (int16_t *)((uint8_t *)J.out + (size_t)i*J.out_stride);
 			o[0] = f2s_x86(ex*len); o[1] = f2s_x86(ey*len); o[2] = f2s_x86(ez*len);
-		}
+		} else if(J.prediction == 3) { o[0] = 0; o[1] = 0; o[2] = 32767; }   // COMPUTED: upstream sets (0,0,1) here and never stores it
 	} else {                                            // normal_attribute.cpp:317-322
 		const float len = norm3(ex, ey, ez);
 		float *o = (float *)((uint8_t *)J.out + (size_t)i*J.out_stride);
-		o[0] = ex/len; o[1] = ey/len; o[2] = ez/len;
+		if(J.prediction == 3 && len < 0.00001f) { o[0] = 0.f; o[1] = 0.f; o[2] = 1.f; }   // COMPUTED: no 0/0 for a renderer
+		else { o[0] = ex/len; o[1] = ey/len; o[2] = ez/len; }
 	}
 }
 
@@ -204,7 +207,12 @@ __global__ __launch_bounds__(256) void k_normal_vertex(const NormalJob *__restri
 // their exclusive scan IN PLACE, the fill cursors - and, after the fill, cur[i] is where vertex i's list ENDS, i.e. where vertex i+1's
 // starts: no separate offset array.  The vertices that take a correction (ESTIMATED: all; BORDER: the boundary) are a bitmap with a
 // prefix count per dword; a vertex' slot in the diff stream is a popcount away.  The adjacency takes the boundary XORs' place.
-__global__ __launch_bounds__(256) void k_normal_blob(const NormalJob *__restrict__ jobs, const uint32_t *__restrict__ job_ids, uint32_t njobs, uint32_t lds_bytes) {
+// COMPUTED (k_normal_blob<true>: prediction 3, normals for a blob that stores none): the same counts, scan, fill, ordered accumulation and
+// positions-to-float pass in the same LDS layout, without what a correction needs - no boundary XORs, no bitmap / prefix counts, no diff reads, no
+// octahedral round trip - and every vertex normalised, (0,0,1) where the estimate is zero.  A template parameter of the kernel (k_delta_tiles' idiom)
+// and a launch of its own over its own id list: <false> is the kernel as it was, instruction for instruction (through a shared __device__ body
+// the same source came out with 4 more VGPRs and three times the SGPR spills).
+template <bool COMPUTED> __global__ __launch_bounds__(256) void k_normal_blob(const NormalJob *__restrict__ jobs, const uint32_t *__restrict__ job_ids, uint32_t njobs, uint32_t lds_bytes) {
 	if(blockIdx.x >= njobs) return;
 	const NormalJob J = jobs[job_ids[blockIdx.x]];
 	extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
@@ -244,7 +252,7 @@ __global__ __launch_bounds__(256) void k_normal_blob(const NormalJob *__restrict
 		if(diffs_i16) { const uint32_t w = ((CRT_GLOBAL const uint32_t *)as_global(J.diffs))[rank]; dx = (int32_t)(int16_t)(w & 0xFFFFu); dy = (int32_t)(int16_t)(w >> 16); }
 		else { CRT_GLOBAL const int32_t *dp = as_global(J.diffs) + 2*(size_t)rank; dx = dp[0]; dy = dp[1]; }
 	};
-	for(uint32_t i = tid; i < nv; i += 256) bnd[i] = 0;
+	if constexpr(!COMPUTED) for(uint32_t i = tid; i < nv; i += 256) bnd[i] = 0;
 	for(uint32_t i = tid; i < ncur/2; i += 256) cur32[i] = 0;
 	__syncthreads();
 	// incidence counts + boundary XOR (markBoundary, normal_attribute.cpp:24-37)
@@ -284,7 +292,7 @@ __global__ __launch_bounds__(256) void k_normal_blob(const NormalJob *__restrict
 				if(fn_lds) { fn[3*f] = nx; fn[3*f + 1] = ny; fn[3*f + 2] = nz; }
 				else { fng[3*(size_t)f] = nx; fng[3*(size_t)f + 1] = ny; fng[3*(size_t)f + 2] = nz; }
 			}
-			if(J.prediction == 2) { atomicXor((uint32_t *)&bnd[a], b ^ c); atomicXor((uint32_t *)&bnd[b], c ^ a); atomicXor((uint32_t *)&bnd[c], a ^ b); }
+			if constexpr(!COMPUTED) if(J.prediction == 2) { atomicXor((uint32_t *)&bnd[a], b ^ c); atomicXor((uint32_t *)&bnd[b], c ^ a); atomicXor((uint32_t *)&bnd[c], a ^ b); }
 		}
 	}
 	if(bad) *as_global(J.status) = -5;
@@ -355,6 +363,7 @@ __global__ __launch_bounds__(256) void k_normal_blob(const NormalJob *__restrict
 			for(uint32_t k = 0; k < per; k++) { const uint32_t i = i0 + k; if(i < nv) { const uint32_t x = cur[i]; cur[i] = (uint16_t)o; o += x; } }
 		}
 	}
+	if constexpr(!COMPUTED) {                                              // (the two blocks below keep their indentation: no vertex of a COMPUTED job takes a correction)
 	for(uint32_t b0 = 0; b0 < nv; b0 += 256) {                               // (uniform trip count) 64 vertices' flags are one ballot
 		const uint32_t i = b0 + tid;
 		const uint64_t m = __ballot(i < nv && (J.prediction == 1 || bnd[i] != 0));
@@ -368,7 +377,8 @@ __global__ __launch_bounds__(256) void k_normal_blob(const NormalJob *__restrict
 		uint32_t o = block256_exclusive_scan<uint32_t>(s, scan_s, &total);
 		for(uint32_t k = 0; k < pd; k++) if(d0 + k < ndw) { fpre[d0 + k] = (uint16_t)o; if(32u*(d0 + k) < nv) o += (uint32_t)__popc(fbits[d0 + k]); }
 	}
-	__syncthreads();                                                       // (bnd has been read for the last time: the adjacency takes its place)
+	}                                                                      // !COMPUTED
+	__syncthreads();                                                       // (bnd has been read for the last time: the adjacency takes its place; COMPUTED: the offsets are in place)
 	for(uint32_t f0 = tid; f0 < nf; f0 += 1024) {                           // four faces per thread and pass, as above; the twelve cursor bumps in flight together
 		uint32_t V[4][3], at[4][3];                                          // (a face that is out or malformed bumps the spare counter cur[nv] and stores nothing)
 #pragma unroll
@@ -394,6 +404,19 @@ __global__ __launch_bounds__(256) void k_normal_blob(const NormalJob *__restrict
 	// per vertex: ordered accumulation (estimateNormals :40-59) + computeNormals (:281-325)
 	// what a vertex' sum of face normals becomes (its correction: fetched by the caller ahead of the sum)
 	auto finish = [&](uint32_t i, float ex, float ey, float ez, bool flagged, bool has_diff, int32_t pdx, int32_t pdy) {
+		if constexpr(COMPUTED) {                                         // normal_attribute.cpp:294-302 / 320-323 at every vertex; a zero estimate: (0,0,1)
+			const float len = norm3(ex, ey, ez);
+			const bool zero = len < 0.00001f;                            // (integer positions: len is 0 or >= 1)
+			if(J.out_i16) {
+				const float l = 32767.0f/len;
+				CRT_GLOBAL int16_t *o = (CRT_GLOBAL int16_t *)(as_global((uint8_t *)J.out) + (size_t)i*J.out_stride);
+				o[0] = zero ? (int16_t)0 : f2s_x86(ex*l); o[1] = zero ? (int16_t)0 : f2s_x86(ey*l); o[2] = zero ? (int16_t)32767 : f2s_x86(ez*l);
+			} else {
+				CRT_GLOBAL float *o = (CRT_GLOBAL float *)(as_global((uint8_t *)J.out) + (size_t)i*J.out_stride);
+				o[0] = zero ? 0.f : ex/len; o[1] = zero ? 0.f : ey/len; o[2] = zero ? 1.f : ez/len;
+			}
+			return;
+		}
 		if(flagged) {                                                    // ESTIMATED: every vertex; BORDER: boundary vertices
 			int32_t qx, qy;
 			to_octa(ex, ey, ez, J.unit, qx, qy);
@@ -424,7 +447,8 @@ __global__ __launch_bounds__(256) void k_normal_blob(const NormalJob *__restrict
 	// round in registers, and the sum taken in id order through v_readlane.
 	const uint32_t HEAVY = 16;
 	for(uint32_t i = tid; i < nv; i += 256) {
-		uint32_t s0 = cur[i ? i - 1u : 0u], fw = fbits[i >> 5], fp = fpre[i >> 5];
+		uint32_t s0 = cur[i ? i - 1u : 0u], fw = 0, fp = 0;
+		if constexpr(!COMPUTED) { fw = fbits[i >> 5]; fp = fpre[i >> 5]; }
 		const uint32_t e0 = cur[i];
 		asm volatile("" : "+v"(s0), "+v"(fw), "+v"(fp));
 		s0 = i ? s0 : 0u;
@@ -434,7 +458,7 @@ __global__ __launch_bounds__(256) void k_normal_blob(const NormalJob *__restrict
 		const uint32_t rank = fp + (uint32_t)__popc(fw & ((1u << (i & 31u)) - 1u));
 		const bool has_diff = flagged && rank < J.ndiffs;
 		int32_t pdx = 0, pdy = 0;
-		if(J.ndiffs) diff_at(has_diff ? rank : 0u, pdx, pdy);
+		if constexpr(!COMPUTED) if(J.ndiffs) diff_at(has_diff ? rank : 0u, pdx, pdy);
 		float ex = 0.f, ey = 0.f, ez = 0.f;
 		const bool wide = fn_any && __any(deg > 8 && deg <= HEAVY);          // (uniform) somebody in this wave needs the 16-wide network
 		if(fn_any && deg > HEAVY) continue;                                  // the wave's job, below
@@ -626,12 +650,13 @@ __global__ __launch_bounds__(256) void k_normal_blob(const NormalJob *__restrict
 					}
 				}
 				if(lane == 0) {
-					const uint32_t fw = fbits[v >> 5], fp = fpre[v >> 5];
+					uint32_t fw = 0, fp = 0;
+					if constexpr(!COMPUTED) { fw = fbits[v >> 5]; fp = fpre[v >> 5]; }
 					const bool flagged = (fw >> (v & 31u)) & 1u;
 					const uint32_t rank = fp + (uint32_t)__popc(fw & ((1u << (v & 31u)) - 1u));
 					const bool has_diff = flagged && rank < J.ndiffs;
 					int32_t pdx = 0, pdy = 0;
-					if(has_diff) diff_at(rank, pdx, pdy);
+					if constexpr(!COMPUTED) if(has_diff) diff_at(rank, pdx, pdy);
 					finish(v, ex, ey, ez, flagged, has_diff, pdx, pdy);
 				}
 			}
@@ -639,5 +664,7 @@ __global__ __launch_bounds__(256) void k_normal_blob(const NormalJob *__restrict
 	}
 	if(!fn_any) { __syncthreads(); positions_out(); }
 }
+template __global__ void k_normal_blob<false>(const NormalJob *, const uint32_t *, uint32_t, uint32_t);
+template __global__ void k_normal_blob<true>(const NormalJob *, const uint32_t *, uint32_t, uint32_t);
 
 } // namespace corto_hip

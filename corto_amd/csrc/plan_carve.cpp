@@ -18,6 +18,7 @@ int Planner::carve() {
 		for(size_t k = 0; k < L.attrs.size(); k++)
 			if(L.h.attrs[k].codec == CRTHIP_CODEC_NORMAL && P.bind[k].buffer && L.attrs[k].normal_prediction != 0 &&
 				!normal_fused(L.h.nvert, L.h.nface)) { est_v += L.h.nvert; est_f += L.h.nface; }
+		if(computes_normals(P) && !normal_fused(L.h.nvert, L.h.nface)) { est_v += L.h.nvert; est_f += L.h.nface; }   // (crthip_batch_bind_computed_normals)
 	}
 	// Per-blob status and flags live in the context's PINNED HOST block: the kernels write there directly (only a failing or
 	// redone blob does), the host zeroes it before the launch and reads it after the sync - no memset kernel in front of a step
@@ -98,6 +99,8 @@ int Planner::carve() {
 					A.facen = cv.take((uint64_t)L.h.nface*12 + 16, 16);
 			}
 		}
+		if(computes_normals(P) && normal_fused(L.h.nvert, L.h.nface) && normal_blob_lds_fn(L.h.nvert, L.h.nface) > ctx->normal_fn_max)
+			S.cn_facen = cv.take((uint64_t)L.h.nface*12 + 16, 16);
 	}
 	if(est_v) {
 		pl.start_off = cv.take(est_v*4 + 16); pl.flag_off = cv.take(est_v*4 + 16); pl.slot_off = cv.take(est_v*4 + 16);

@@ -134,6 +134,7 @@ int Planner::jobs() {
 			for(size_t k = 0; k < L.attrs.size(); k++)
 				if(mesh && L.h.attrs[k].codec == CRTHIP_CODEC_NORMAL && P.bind[k].buffer && (L.attrs[k].normal_prediction == 1 ||
 					L.attrs[k].normal_prediction == 2)) readers++;
+			if(computes_normals(P)) readers++;                        // computed normals read the integer positions as a stored estimate does
 			pos_ints_needed = readers > 0;
 			pos_by_normal = readers == 1 && normal_fused(nvert, nface) && pos_k >= 0 && P.bind[pos_k].format == CRTHIP_FMT_FLOAT;
 		}
@@ -289,6 +290,37 @@ int Planner::jobs() {
 				for(uint32_t c = 0; c < nb; c++) pl.dequant_block_job.v.push_back((uint32_t)pl.dequant.v.size());
 				pl.dequant.v.push_back(q);
 			}
+		}
+		// normals for a blob that stores (or binds) none: crthip_batch_bind_computed_normals.  An ESTIMATED job without corrections - no stream, no
+		// K-BIT job, nothing of the entropy stage; position, faces, the fused kernel's last-reader duty and the batch-wide slices as above
+		if(computes_normals(P)) {
+			const Binding &bd = P.computed;
+			NormalJob n{};
+			n.out = bd.buffer; n.nvert = nvert; n.nface = nface;
+			n.out_stride = bd.stride ? bd.stride : (bd.format == CRTHIP_FMT_INT16 ? 6u : 12u);
+			n.prediction = 3; n.out_i16 = bd.format == CRTHIP_FMT_INT16;
+			n.status = hs_base + hs.status(i);
+			// (the bind call checked this; a blob that fails it decodes nothing into the buffer)
+			const bool pos_ok = pos_k >= 0 && L.h.attrs[pos_k].codec == CRTHIP_CODEC_GENERIC && L.h.attrs[pos_k].N == 3 &&
+				P.bind[pos_k].buffer && !P.bind[pos_k].stream_values;
+			if(!pos_ok) { P.host_status = CRTHIP_E_NORMAL_NEEDS_POSITION; continue; }
+			const bool pos_scratch = P.bind[pos_k].stride != 0 || P.bind[pos_k].format == CRTHIP_FMT_DOUBLE;
+			n.position = pos_scratch ? (const int32_t *)SP(S.attr[pos_k].vals) : (const int32_t *)P.bind[pos_k].buffer;
+			n.faces = P.index ? P.index : (void *)SP(S.faces);
+			n.faces_u16 = P.index ? (uint8_t)P.index_u16 : 0;
+			if(normal_fused(nvert, nface)) {
+				n.fused = 1;
+				n.fn_scratch = S.cn_facen != ~0ull ? (float *)SP(S.cn_facen) : nullptr;
+				if(pos_by_normal) { n.pos_out = P.bind[pos_k].buffer; n.pos_stride = P.bind[pos_k].stride ? P.bind[pos_k].stride : 12u;
+					n.pos_q = L.h.attrs[pos_k].q; }
+				pl.normal_computed_ids.v.push_back((uint32_t)pl.normal.v.size());
+				pl.normal_computed_lds = std::max(pl.normal_computed_lds, normal_blob_lds_fn(nvert, nface) <= ctx->normal_fn_max ?
+					normal_blob_lds_fn(nvert, nface) : normal_blob_lds(nvert, nface));
+			} else {
+				n.vbase = est_vbase; n.fbase = est_fbase; est_vbase += nvert; est_fbase += nface;
+				pl.any_est_normal = true;
+			}
+			pl.normal.v.push_back(n);
 		}
 	}
 	return CRTHIP_OK;

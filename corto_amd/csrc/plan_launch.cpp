@@ -243,8 +243,13 @@ int Planner::launch(uint32_t phases, const Carry *carry) {
 	const uint32_t nvb = (uint32_t)pl.nv_block_job.v.size(), nfb = (uint32_t)pl.nf_block_job.v.size();
 	if(!pl.normal_fused_ids.v.empty()) {
 		const uint32_t nj = (uint32_t)pl.normal_fused_ids.v.size();
-		LT.begin("normal_blob"); hipLaunchKernelGGL(k_normal_blob, dim3(nj), dim3(256), pl.normal_fused_lds, st, D(pl.normal),
+		LT.begin("normal_blob"); hipLaunchKernelGGL(k_normal_blob<false>, dim3(nj), dim3(256), pl.normal_fused_lds, st, D(pl.normal),
 			D(pl.normal_fused_ids), nj, pl.normal_fused_lds); LT.end();
+	}
+	if(!pl.normal_computed_ids.v.empty()) {                     // blobs that store no normals (crthip_batch_bind_computed_normals)
+		const uint32_t nj = (uint32_t)pl.normal_computed_ids.v.size();
+		LT.begin("normal_blob_computed"); hipLaunchKernelGGL(k_normal_blob<true>, dim3(nj), dim3(256), pl.normal_computed_lds, st, D(pl.normal),
+			D(pl.normal_computed_ids), nj, pl.normal_computed_lds); LT.end();
 	}
 	if(pl.any_est_normal) {
 		float *facen = (float *)(base + pl.facen_off);
@@ -313,6 +318,7 @@ void Planner::account() {
 			else if(a.codec == CRTHIP_CODEC_COLOR) ob += (uint64_t)L.h.nvert*P.bind[k].out_components;
 			else ob += (uint64_t)L.h.nvert*a.N*generic_work_bytes(P.bind[k].format);
 		}
+		if(computes_normals(P)) ob += (uint64_t)L.h.nvert*3*(P.computed.format == CRTHIP_FMT_INT16 ? 2 : 4);
 	}
 	b->stats.output_bytes = ob;
 	ctx->in_flight = b; ctx->last_decoded = b;

@@ -46,7 +46,8 @@ extern "C" {
                                      crthip_output_layout, crthip_pool_decode (crthip_pool_dest, crthip_pool_done_fn), crthip_mesh_layout,
                                      crthip_encode_layout, crthip_encode_batch_layout, crthip_encode_input_model_layout,
                                      crthip_encode_topology_model_layout; crthip_batch_stats and crthip_pool_report grew at their ends
-                                     (upload_copies, upload_gathered_bytes; grouped_steps) */
+                                     (upload_copies, upload_gathered_bytes; grouped_steps); crthip_batch_bind_computed_normals (a new
+                                     call and nothing else: the number stays 6) */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -224,6 +225,26 @@ int crthip_batch_walk_stats(const crthip_batch *b, crthip_walk_stats *s);
 int crthip_batch_bind(crthip_batch *b, uint32_t i, const crthip_attr_binding *attrs, void *index, uint32_t index_format);
 /* Bind every blob in one call: attrs holds sum(nattr) entries blob after blob; index/index_format have nblobs entries. */
 int crthip_batch_bind_all(crthip_batch *b, const crthip_attr_binding *attrs, void *const *index, const uint32_t *index_format);
+/* Normals for a mesh whose blob stores none, or whose stored "normal" is left unbound: what upstream's decoder leaves at a vertex
+ * that takes no correction (src/normal_attribute.cpp:294-302, 320-323), at EVERY vertex - the GPU's answer to what upstream's callers
+ * do after such a decode (README.md: if(!geometry.attributes.normal) geometry.computeVertexNormals()).  Added within ABI 6.
+ *   est[v] = sum over the faces f incident to v, in ascending f, of cross(P[b]-P[a], P[c]-P[a])      (estimateNormals, :40-59)
+ *   len    = sqrtf((ex*ex + ey*ey) + ez*ez)
+ * over the INTEGER (delta-decoded, not dequantised) positions as floats, without FMA; a face that lists v twice adds twice.
+ *   CRTHIP_FMT_FLOAT: nvert*3 f32, est/len;   CRTHIP_FMT_INT16: nvert*3 i16, (int16_t)(est*(32767.0f/len)) per component.
+ * One deliberate difference from upstream's branch: a vertex whose estimate is zero (no face, or faces that cancel; with integer positions
+ * len is 0 or at least 1) gets (0,0,1) / (0,0,32767) - upstream's evident intention - where upstream's FLOAT path divides 0 by 0 and its
+ * INT16 path sets (0,0,1) and never stores it.  A renderer gets neither NaNs nor stale bytes: every element of the array is written.
+ * buffer: DEVICE pointer; stride and alignment exactly as for a stored normal's crthip_attr_binding.  Call it AFTER crthip_batch_bind /
+ * _bind_all for blob i: a later bind of that blob drops it, as does crthip_batch_reset*; buffer == NULL removes it.  Every error is
+ * returned here and nothing new can fail at decode time:
+ *   CRTHIP_E_ARGUMENT  i out of range; a point cloud; the blob has a "normal" attribute with a bound buffer; a stride or an alignment a
+ *                      normal binding would refuse
+ *   CRTHIP_E_FORMAT    a format other than FLOAT / INT16
+ *   CRTHIP_E_NORMAL_NEEDS_POSITION  "position" missing, not generic with 3 components, unbound, or bound with CRTHIP_BIND_STREAM_VALUES
+ *                      (the rule of a stored ESTIMATED normal)
+ * crthip_last_error() names the blob.  Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host or the crt::Decoder facade. */
+int crthip_batch_bind_computed_normals(crthip_batch *b, uint32_t i, void *buffer, uint32_t format, uint32_t stride);
 
 /* Enqueue the whole decode of the batch on the context's stream (asynchronous). */
 int crthip_batch_decode(crthip_batch *b);

@@ -9,12 +9,12 @@ import csv, glob
 f = glob.glob("$OUT/t/**/*kernel_trace.csv", recursive=True)[0]
 rows = [r for r in csv.DictReader(open(f)) if "corto_hip" in r["Kernel_Name"]]
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-# batches: split at k_tun_tables launches that follow a k_normal_blob
+# batches: split behind a k_normal_blob<false> (a template kernel: its name comes as "void corto_hip::k_normal_blob<false>")
 batches, cur = [], []
 for r in rows:
     n = r["Kernel_Name"].split("(")[0].replace("corto_hip::", "")
     cur.append((n, int(r["Start_Timestamp"]), int(r["End_Timestamp"])))
-    if n == "k_normal_blob": batches.append(cur); cur = []
+    if n.endswith("k_normal_blob<false>"): batches.append(cur); cur = []
 for b in batches[-3:]:
     t0 = b[0][1]
     print("batch: span %.1f us, kernels' own time %.1f us" % ((b[-1][2] - t0) / 1e3, sum(e - s for _, s, e in b) / 1e3))
