@@ -25,6 +25,7 @@ LIB_PATH = os.environ.get("CORTO_HIP_LIB_PATH") or os.path.join(_HERE, "lib", "l
 FMT_UINT32, FMT_INT32, FMT_UINT16, FMT_INT16, FMT_UINT8, FMT_INT8, FMT_FLOAT, FMT_DOUBLE = range(8)
 CODEC_GENERIC, CODEC_NORMAL, CODEC_COLOR = 1, 2, 3
 MAX_ATTRS, NAME_MAX, MAX_KERNELS = 16, 64, 32
+BIND_STREAM_VALUES, BIND_QUANTIZED = 1, 2          # crthip_attr_binding.reserved
 
 
 class CortoError(RuntimeError):
@@ -50,6 +51,16 @@ class BlobInfo(C.Structure):
 
 class AttrBinding(C.Structure):
     _fields_ = [("buffer", C.c_void_p), ("format", C.c_uint32), ("out_components", C.c_uint32), ("stride", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class QuantTransform(C.Structure):
+    """crthip_quant_transform: (float)(int32)(base[c] + out[i][c]) * q is the FLOAT output of a CRTHIP_BIND_QUANTIZED attribute, bit for bit"""
+    _fields_ = [("base", C.c_int32 * 4), ("span", C.c_uint32 * 4), ("q", C.c_float), ("components", C.c_uint32), ("written", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        n = self.components
+        return dict(base=[int(x) for x in self.base[:n]], span=[int(x) for x in self.span[:n]], q=float(self.q), components=int(n), written=int(self.written))
 
 
 class BatchStats(C.Structure):
@@ -232,6 +243,9 @@ def lib():
         L.crthip_batch_bind.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
         L.crthip_batch_bind_all.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.crthip_batch_bind_computed_normals.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.crthip_batch_quant_transform.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QuantTransform)]
+        L.crthip_batch_bind_quant_transforms.argtypes = [C.c_void_p, C.c_void_p]
+        L.crthip_quant_out_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(QuantTransform), C.c_int, C.c_uint32]
         L.crthip_batch_decode.argtypes = [C.c_void_p]
         L.crthip_batch_decode_with_next.argtypes = [C.c_void_p, C.c_void_p]
         L.crthip_batch_set_parity.argtypes = [C.c_void_p, C.c_uint32]
@@ -868,6 +882,22 @@ def splice_copy_model(src: np.ndarray, src_at: int, dst: np.ndarray, dst_at: int
     _check(lib().crthip_splice_copy_model(src.ctypes.data + src_at, dst.ctypes.data + dst_at, int(nbytes), int(seed)))
 
 
+def quant_out_model(values: np.ndarray, stride: int = 0, which: int = 0, seed: int = 0, q: float = 1.0, out: Optional[np.ndarray] = None, offset: int = 0):
+    """crthip_quant_out_model: the two passes of CRTHIP_BIND_QUANTIZED on the host in the kernels' partition (which 0: one workgroup;
+    1: the blocks of the two-kernel path, shuffled by seed).  values: (nvert, N) int32.  out: a uint8 array the halfwords go into from byte
+    `offset` on (made here when None: exactly the bytes the last vertex ends at).  Returns (out, QuantTransform)."""
+    v = np.ascontiguousarray(values, dtype=np.int32)
+    nvert, N = v.shape
+    st = stride or 2 * N
+    if out is None:
+        out = np.zeros(offset + (max(nvert, 1) - 1) * st + 2 * N, np.uint8)
+    assert out.dtype == np.uint8 and out.flags.c_contiguous and len(out) >= offset + ((nvert - 1) * st + 2 * N if nvert else 0)
+    t = QuantTransform()
+    t.q = q
+    _check(lib().crthip_quant_out_model(_np_ptr(v), nvert, N, stride, C.c_void_p(out.ctypes.data + offset), C.byref(t), which, seed))
+    return out, t
+
+
 def encode_splice_plan_model(meshes, kw=None, chunk_items=0):
     """crthip_encode_splice_plan_model: the device splice's plan of a batch on the host, in chunks of chunk_items meshes (0: one chunk) that
     continue the arena as the chunks of a batch beyond one device image do.  Returns (offsets, lens, stats dict, pieces): pieces an
@@ -1096,14 +1126,17 @@ class Batch:
 
     # -- outputs -----------------------------------------------------------------------------------
     def allocate_outputs(self, normal_format=FMT_FLOAT, color_components: Optional[int] = None, index16=False,
-                         only: Optional[set] = None, fill: Optional[int] = None, computed_normals=False):
+                         only: Optional[set] = None, fill: Optional[int] = None, computed_normals=False, quantized=()):
         """Allocate every output of every blob inside ONE device buffer (torch.uint8) and bind them.
         Returns a list (per blob) of dicts name -> torch tensor view.
         computed_normals: every mesh blob WITHOUT a normal attribute gets a "normal" tensor of normal_format all the same, bound
-        through crthip_batch_bind_computed_normals - upstream's estimate at every vertex (include/corto_hip.h)."""
+        through crthip_batch_bind_computed_normals - upstream's estimate at every vertex (include/corto_hip.h).
+        quantized: names of generic attributes to bind as uint16 grid values (CRTHIP_BIND_QUANTIZED) in place of floats; their
+        transforms come from quant_transform(i, name) after sync()."""
         import torch
         dev = torch.device("cuda", self.ctx.device)
         plan = []   # (blob, name, offset, nbytes, dtype, shape, binding_slot)
+        as_u16 = set()                               # (blob, binding slot) of the attributes named in `quantized`
         off = 0
 
         def take(nbytes):
@@ -1123,6 +1156,9 @@ class Batch:
                 elif a["codec"] == CODEC_COLOR:
                     oc = color_components or a["components"]
                     plan.append((i, a["name"], take(nv * oc), "u8", (nv, oc), k, FMT_UINT8, oc))
+                elif a["name"] in quantized:
+                    plan.append((i, a["name"], take(nv * a["components"] * 2), "u16", (nv, a["components"]), k, FMT_UINT16, 0))
+                    as_u16.add((i, k))
                 else:
                     plan.append((i, a["name"], take(nv * a["components"] * 4), "f32", (nv, a["components"]), k, FMT_FLOAT, 0))
             if (computed_normals and nf and (only is None or "normal" in only)
@@ -1150,7 +1186,7 @@ class Batch:
             outs[i][name] = (view, dt)
             if slot >= 0:
                 bd = binds[int(first[i]) + slot]
-                bd.buffer = base + o; bd.format = fmt; bd.out_components = oc
+                bd.buffer = base + o; bd.format = fmt; bd.out_components = oc; bd.reserved = BIND_QUANTIZED if (i, slot) in as_u16 else 0
             elif slot == -2:
                 computed.append((i, base + o, fmt, 0))
             else:
@@ -1262,6 +1298,18 @@ class Batch:
         to the device pointer `ptr` (nvert*3 f32 or i16; stride as for a stored normal).  After bind() / rebind() of that blob, which drop
         it; ptr None or 0 removes it."""
         _check(lib().crthip_batch_bind_computed_normals(self.handle, i, C.c_void_p(ptr) if ptr else None, fmt, stride))
+
+    def quant_transform(self, i: int, name) -> QuantTransform:
+        """crthip_batch_quant_transform: the record of blob i's attribute `name` (or index), bound quantised; after sync()"""
+        k = name if isinstance(name, int) else [a["name"] for a in self.infos[i].attrs()].index(name)
+        t = QuantTransform()
+        _check(lib().crthip_batch_quant_transform(self.handle, i, k, C.byref(t)))
+        return t
+
+    def bind_quant_transforms(self, ptr: Optional[int]):
+        """crthip_batch_bind_quant_transforms: a device array of sum(nattr) 48-byte records (16-byte aligned) that the decode fills for the
+        quantised attributes, in bind_all's order; None or 0 removes it.  The caller keeps the memory alive."""
+        _check(lib().crthip_batch_bind_quant_transforms(self.handle, C.c_void_p(ptr) if ptr else None))
 
     def host_outputs(self, i: int) -> Dict[str, np.ndarray]:
         """Copy blob i's outputs to the host as numpy arrays with the reference's dtypes."""

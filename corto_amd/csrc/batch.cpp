@@ -78,6 +78,10 @@ static int harvest_selected(crthip_ctx *ctx) {
 	const size_t n = b->blobs.size();
 	const StatusWords W{n};
 	for(size_t i = 0; i < n; i++) b->status[i] = b->blobs[i].host_status ? b->blobs[i].host_status : hs[W.status(i)];
+	if(!b->quant_bound.empty()) {                                         // CRTHIP_BIND_QUANTIZED: the records the kernels wrote behind the status words
+		const crthip_quant_transform *rec = (const crthip_quant_transform *)((const uint8_t *)hs + W.records());
+		b->quant_recs.assign(rec, rec + b->quant_bound.size());
+	}
 	b->stats.topology_fallbacks = 0;
 	for(size_t i = 0; i < n; i++) b->stats.topology_fallbacks += (uint64_t)(hs[W.topo_flags(i)] & 1);
 	// K-DELTA keeps values in LDS as int16 relative to vertex 0 and redoes an attribute that does not fit in HBM (slow, exact): a context
@@ -301,6 +305,7 @@ static int batch_fill(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs, const u
 	b->walk = crthip_walk_stats{};
 	b->walk.host_walked = nblobs;
 	b->dirty = true; b->decoded = false;
+	b->quant_dev = nullptr; b->quant_bound.clear(); b->quant_recs.clear();
 	uint64_t off = 0;
 	for(uint32_t i = 0; i < nblobs; i++) {
 		BlobPlan &P = b->blobs[i];
@@ -418,6 +423,7 @@ static int batch_fill_resident(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs
 	b->stats = crthip_batch_stats{};
 	b->walk = crthip_walk_stats{};
 	b->dirty = true; b->decoded = false;
+	b->quant_dev = nullptr; b->quant_bound.clear(); b->quant_recs.clear();
 	for(uint32_t i = 0; i < nblobs; i++)
 		if(offsets[i] & 15) return fail(CRTHIP_E_ARGUMENT, "resident blob offsets must be multiples of 16 (blob " + std::to_string(i) + ")");
 	const uint32_t cap = WALK_RECORD_BYTES;
@@ -551,7 +557,18 @@ extern "C" int crthip_batch_walk_stats(const crthip_batch *b, crthip_walk_stats 
 static int check_binding(const AttrHeader &a, const crthip_attr_binding &bd) {
 	if(!bd.buffer) return CRTHIP_OK;
 	const uint32_t st = bd.stride;
-	if(bd.reserved & ~CRTHIP_BIND_STREAM_VALUES) return CRTHIP_E_ARGUMENT;
+	if(bd.reserved & ~(CRTHIP_BIND_STREAM_VALUES | CRTHIP_BIND_QUANTIZED)) return CRTHIP_E_ARGUMENT;
+	if(bd.reserved & CRTHIP_BIND_QUANTIZED) {                              // uint16 grid values of a generic attribute (corto_hip.h)
+		// (INT32 is the format of the OTHER flag's stream values: with this bit it stays the argument error it was before the bit had a meaning)
+		if(a.codec == CRTHIP_CODEC_GENERIC && bd.format == CRTHIP_FMT_INT32) return CRTHIP_E_ARGUMENT;
+		if(a.codec == CRTHIP_CODEC_NORMAL || a.codec == CRTHIP_CODEC_COLOR || bd.format != CRTHIP_FMT_UINT16 || a.N < 1) return CRTHIP_E_FORMAT;
+		if(bd.reserved & CRTHIP_BIND_STREAM_VALUES) return CRTHIP_E_ARGUMENT;
+		if(a.N > 4) return CRTHIP_E_LIMIT;
+		if(bd.out_components && bd.out_components != a.N) return CRTHIP_E_ARGUMENT;
+		if(((uintptr_t)bd.buffer) % 2) return CRTHIP_E_ARGUMENT;
+		if(st && (st < 2*a.N || st % 2)) return CRTHIP_E_ARGUMENT;
+		return CRTHIP_OK;
+	}
 	if((bd.reserved & CRTHIP_BIND_STREAM_VALUES) && a.codec != CRTHIP_CODEC_GENERIC) return CRTHIP_E_FORMAT;   // normals / colours have codecs of their own upstream too
 	if(a.codec == CRTHIP_CODEC_NORMAL) {
 		if(bd.format != CRTHIP_FMT_FLOAT && bd.format != CRTHIP_FMT_INT16) return CRTHIP_E_FORMAT;
@@ -595,10 +612,11 @@ extern "C" int crthip_batch_bind(crthip_batch *b, uint32_t i, const crthip_attr_
 		P.bind[k].out_components = attrs[k].out_components ? attrs[k].out_components : 4;
 		// a stride equal to the packed element size is the packed layout (the buffer then doubles as int32 workspace, as upstream's does)
 		const AttrHeader &a = P.L.h.attrs[k];
-		const uint32_t packed = a.codec == CRTHIP_CODEC_NORMAL ? (attrs[k].format == CRTHIP_FMT_INT16 ? 6u : 12u)
-		                      : a.codec == CRTHIP_CODEC_COLOR ? P.bind[k].out_components : 4u*a.N;
-		P.bind[k].stride = attrs[k].stride == packed ? 0u : attrs[k].stride;
 		P.bind[k].stream_values = (attrs[k].reserved & CRTHIP_BIND_STREAM_VALUES) != 0;
+		P.bind[k].quantized = attrs[k].buffer && (attrs[k].reserved & CRTHIP_BIND_QUANTIZED) != 0;
+		const uint32_t packed = a.codec == CRTHIP_CODEC_NORMAL ? (attrs[k].format == CRTHIP_FMT_INT16 ? 6u : 12u)
+		                      : a.codec == CRTHIP_CODEC_COLOR ? P.bind[k].out_components : P.bind[k].quantized ? 2u*a.N : 4u*a.N;
+		P.bind[k].stride = attrs[k].stride == packed ? 0u : attrs[k].stride;
 	}
 	P.index = index; P.index_u16 = index && index_format == CRTHIP_FMT_UINT16;
 	P.computed = Binding{};                                                 // (crthip_batch_bind_computed_normals comes after the bind)
@@ -630,6 +648,26 @@ extern "C" int crthip_batch_bind_computed_normals(crthip_batch *b, uint32_t i, v
 		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "computed normals need a bound three-component \"position\" (bind the blob first)" + who);
 	P.computed.buffer = buffer; P.computed.format = format;
 	P.computed.stride = stride == (format == CRTHIP_FMT_INT16 ? 6u : 12u) ? 0u : stride;
+	b->dirty = true;
+	return CRTHIP_OK;
+}
+
+// CRTHIP_BIND_QUANTIZED: the record of one attribute as the last synced decode left it; the caller's device copy of the records
+extern "C" int crthip_batch_quant_transform(const crthip_batch *b, uint32_t i, uint32_t attr, crthip_quant_transform *out) {
+	if(!b || !out || i >= b->blobs.size() || attr >= b->blobs[i].bind.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_quant_transform: no such blob or attribute");
+	if(!b->decoded || (b->ctx && b->ctx->in_flight == b) || b->staged) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_quant_transform: decode and sync the batch first");
+	size_t r = attr;
+	for(uint32_t k = 0; k < i; k++) r += b->blobs[k].bind.size();
+	if(r >= b->quant_bound.size() || r >= b->quant_recs.size() || !b->quant_bound[r])
+		return fail(CRTHIP_E_ARGUMENT, "crthip_batch_quant_transform: the attribute was not bound with CRTHIP_BIND_QUANTIZED (blob " + std::to_string(i) + ")");
+	*out = b->quant_recs[r];
+	return CRTHIP_OK;
+}
+
+extern "C" int crthip_batch_bind_quant_transforms(crthip_batch *b, void *device_records) {
+	if(!b) return fail(CRTHIP_E_ARGUMENT);
+	if((uintptr_t)device_records & 15) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_quant_transforms: the record array must be 16-byte aligned");
+	b->quant_dev = device_records;
 	b->dirty = true;
 	return CRTHIP_OK;
 }

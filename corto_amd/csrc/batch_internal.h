@@ -21,6 +21,7 @@
 #include "device_plan.h"
 #include "encoder_internal.h"
 #include "kernels.h"
+#include "quant_out.h"
 
 using namespace corto_hip;
 
@@ -77,8 +78,9 @@ template <typename T> struct HostArr {  // host image of a device array + where 
 
 struct AttrScratch {
 	// vals: int32 workspace of a generic attribute bound with a stride; facen: the fused normal kernel's face normals when not in LDS
-	uint64_t color = ~0ull, diffs = ~0ull, vals = ~0ull, facen = ~0ull; std::vector<uint64_t> sym;
-	void reset() { color = diffs = vals = facen = ~0ull; sym.clear(); }
+	// qrange: the eight min | max words of a quantised attribute beyond QOUT_BLOB_MAX (k_quant_range)
+	uint64_t color = ~0ull, diffs = ~0ull, vals = ~0ull, facen = ~0ull, qrange = ~0ull; std::vector<uint64_t> sym;
+	void reset() { color = diffs = vals = facen = qrange = ~0ull; sym.clear(); }
 };
 struct BlobScratch {
 	uint64_t clers = ~0ull, pred = ~0ull, front_a = ~0ull, front_b = ~0ull, order = ~0ull, delayed = ~0ull, faces = ~0ull;
@@ -112,6 +114,9 @@ struct Plan {
 	HostArr<NormalJob> normal; HostArr<uint32_t> nv_block_job, nv_block_first, nf_block_job, nf_block_first, normal_fused_ids, normal_computed_ids;
 	uint32_t normal_fused_lds = 0, normal_computed_lds = 0;   // (computed: k_normal_blob<true>'s id list and LDS request)
 	HostArr<DequantJob> dequant; HostArr<uint32_t> dequant_block_job;
+	// CRTHIP_BIND_QUANTIZED: jobs of up to QOUT_BLOB_MAX vertices by id (k_quant_out_blob), the others by block (k_quant_range, k_quant_store)
+	HostArr<QuantOutJob> quant; HostArr<uint32_t> quant_blob_ids, quant_block_job;
+	uint32_t quant_records = 0;                             // records behind the status words: sum(nattr) of a batch with a quantised binding, else 0
 	// scratch regions (offsets)
 	uint64_t zero_begin = 0, zero_end = 0;
 	uint64_t tables_off = 0, tun_partial_off = 0, unpack_partial_off = 0, cloud_partial_off = 0;
@@ -128,11 +133,11 @@ struct Plan {
 		f(tun); f(tun_dict); f(tun_chunk_stream); f(tun_group_ids); f(tun_groups); f(fill); f(topo); f(aux_u32); f(topo_lds_ids); f(topo_big_ids);
 		f(topo_glob_ids); f(unpack); f(unpack_chunk_job); f(unpack_wave_ids);
 		f(delta); f(delta_groups); f(cloud); f(cloud_chunk_job); f(normal); f(nv_block_job); f(nv_block_first); f(nf_block_job); f(nf_block_first);
-		f(normal_fused_ids); f(normal_computed_ids); f(dequant); f(dequant_block_job);
+		f(normal_fused_ids); f(normal_computed_ids); f(dequant); f(dequant_block_job); f(quant); f(quant_blob_ids); f(quant_block_job);
 	}
 	void reset() {                                          // keep every vector's capacity
 		each_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
-		clers_groups = 0; topo_need.clear();
+		clers_groups = 0; topo_need.clear(); quant_records = 0;
 		topo_lds = topo_big_lds = normal_fused_lds = normal_computed_lds = 0;
 		zero_begin = zero_end = tables_off = tun_partial_off = unpack_partial_off = cloud_partial_off = 0;
 		facen_off = cnt_off = cursor_off = bnd_off = start_off = flag_off = slot_off = adj_off = nscan_partial_off = 0;
@@ -223,7 +228,9 @@ inline void ctx_select(crthip_ctx *ctx, uint8_t parity) {
 // in place (include/corto/vertex_attribute.h:184-228), so every format's buffer is nvert*N*4 bytes but DOUBLE's
 static inline size_t generic_work_bytes(uint32_t format) { return format == CRTHIP_FMT_DOUBLE ? 8u : 4u; }
 
-struct Binding { void *buffer = nullptr; uint32_t format = CRTHIP_FMT_FLOAT, out_components = 4, stride = 0; bool stream_values = false; };   // stream_values: CRTHIP_BIND_STREAM_VALUES
+struct Binding { void *buffer = nullptr; uint32_t format = CRTHIP_FMT_FLOAT, out_components = 4, stride = 0; bool stream_values = false, quantized = false; };   // stream_values: CRTHIP_BIND_STREAM_VALUES; quantized: CRTHIP_BIND_QUANTIZED
+// a generic attribute decoded as int32 in device scratch and finished by a job of its own: a stride, DOUBLE, or uint16 grid values
+static inline bool generic_in_scratch(const Binding &bd) { return bd.stride || bd.format == CRTHIP_FMT_DOUBLE || bd.quantized; }
 
 struct BlobPlan {
 	BlobLayout L;
@@ -255,6 +262,10 @@ struct crthip_batch {
 	// crthip_batch_decode_with_next planned this batch as `next`: its planner, kept until the call that runs its mesh stage (e_done: its entropy
 	// stage has been enqueued; else that call runs the whole schedule)
 	struct Planner *staged = nullptr;
+	// CRTHIP_BIND_QUANTIZED: the caller's device record array (crthip_batch_bind_quant_transforms); the last decode's records as harvest
+	// found them in the status block and which of them belong to a quantised binding (crthip_batch_bind_all's order)
+	void *quant_dev = nullptr;
+	std::vector<crthip_quant_transform> quant_recs; std::vector<uint8_t> quant_bound;
 };
 void drop_staged(crthip_batch *b);      // (batch.cpp)
 
@@ -266,6 +277,8 @@ struct StatusWords {
 	size_t topo_flags(size_t i) const { return n + i; }            // bit 0: the automaton was redone on the HBM front; above it the slots it needed
 	size_t delta_flags(size_t i) const { return 2*n + 2*i; }       // two words: an attribute's values left int16 / an attribute took the walk
 	size_t bytes() const { return n*16; }
+	// behind them (16-byte aligned): the crthip_quant_transform records of a batch with a quantised binding, one an attribute
+	size_t records() const { return n*16; }
 };
 
 int harvest(crthip_ctx *ctx);     // wait for the batch in flight on the context, keep its per-blob status, learn from its flags (batch.cpp)
@@ -359,6 +372,7 @@ struct Planner {
 	}
 	bool e_done = false;                                                     // stage E has been enqueued (by an earlier call)
 	int carve(); int jobs(); void group(); int upload(); int launch(uint32_t phases = PH_ALL, const Carry *carry = nullptr); int mark_done(); void account();
+	uint32_t qout_blob_max() const { return ctx->dbg.qout_blob_max ? ctx->dbg.qout_blob_max : QOUT_BLOB_MAX; }   // a quantised attribute's size class
 	bool splits() const; bool takes_front() const; bool carry_args(Carry &c) const; bool hosts_carry() const;
 };
 

@@ -34,6 +34,8 @@ struct DebugConfig {
 	bool carry_off = false;         // $CORTO_CARRY=0 (A/B and test hook): crthip_batch_decode_with_next enqueues the next batch's entropy stage as launches of its
 	                                // own behind this batch's kernels instead of inside k_front's / k_delta_lds16's grids, and the pool runs one batch per
 	                                // lane and call as it did before it pipelined its lanes (plan_launch.cpp, pool.cpp)
+	uint32_t qout_blob_max = 0;     // $CORTO_QOUT_BLOB_MAX=<vertices> (A/B hook, tools/quant_out_rate.py): the largest quantised attribute k_quant_out_blob takes, in place
+	                                // of QOUT_BLOB_MAX (kernels.h); beyond it k_quant_range / k_quant_store.  Either kernel takes any size: the same bytes
 	uint64_t encode_image_budget = 0; // $CORTO_ENCODE_IMAGE_BUDGET=<bytes> (test hook): the batch encoders cut a batch into chunks whose device image stays within
 	                                // this many bytes instead of within half the free device memory - a batch of small meshes then runs in several chunks, the
 	                                // path a batch beyond one device image takes (tests/test_encode_device_out_gpu.py); never above that half
@@ -50,6 +52,7 @@ inline DebugConfig debug_config_from_env() {
 	c.values_i32 = on("CORTO_VALUES_I32");
 	{ const char *e = getenv("CORTO_FRONT"); c.front_off = e && e[0] == '0'; }
 	{ const char *e = getenv("CORTO_CARRY"); c.carry_off = e && e[0] == '0'; }
+	if(const char *e = getenv("CORTO_QOUT_BLOB_MAX")) c.qout_blob_max = (uint32_t)strtoul(e, nullptr, 10);
 	if(const char *e = getenv("CORTO_ENCODE_IMAGE_BUDGET")) c.encode_image_budget = strtoull(e, nullptr, 10);
 	return c;
 }

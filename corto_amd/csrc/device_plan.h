@@ -168,9 +168,26 @@ struct DequantJob {
 	uint32_t pad2;
 };
 
+// a generic attribute bound with CRTHIP_BIND_QUANTIZED (k_quant_out.hip, quant_out.h): the delta-decoded integers -> uint16 relative to the
+// per-component minimum, and the record that takes them back
+struct QuantOutRecord;                                   // = crthip_quant_transform (include/corto_hip.h), 48 bytes
+struct QuantOutJob {
+	const int32_t *values;         // nvert*N int32, packed (scratch)
+	void *buffer;                  // the caller's uint16 destination
+	QuantOutRecord *rec_host;      // the record in the batch's pinned status block
+	QuantOutRecord *rec_dev;       // ... and in the caller's device array (crthip_batch_bind_quant_transforms), or null
+	int32_t *status;               // the blob's status word
+	uint32_t *range;               // k_quant_range / k_quant_store: eight words of scratch, min | max a component (seeded by FillJobs), else null
+	uint32_t stride;               // bytes from one vertex to the next in `buffer`; 0 = packed
+	uint32_t nvert, N;
+	uint32_t block0;               // first block of this job in the block->job map (jobs beyond QOUT_BLOB_MAX)
+	float q;
+	uint32_t pad;
+};
+
 // the layout the kernels read, pinned (TopoJob's size is performance-critical: TOPO_OPT_PROGRESS above)
 static_assert(sizeof(TunStream) == 64 && sizeof(FillJob) == 16 && sizeof(TopoJob) == 136 && sizeof(UnpackJob) == 56 && sizeof(DeltaJob) == 96 &&
-              sizeof(CloudJob) == 24 && sizeof(NormalJob) == 104 && sizeof(DequantJob) == 64, "decode job layout");
+              sizeof(CloudJob) == 24 && sizeof(NormalJob) == 104 && sizeof(DequantJob) == 64 && sizeof(QuantOutJob) == 72, "decode job layout");
 static_assert(offsetof(TopoJob, opts) == 116 && offsetof(UnpackJob, out_kind) == 51 && offsetof(NormalJob, faces_u16) == 58, "decode job layout");
 static_assert(offsetof(DeltaJob, in_i16) == 34 && offsetof(DeltaJob, wide) == 35 && offsetof(DeltaJob, rounds) == 88 &&
               offsetof(DeltaJob, status_back) == 92, "decode job layout");

@@ -41,6 +41,15 @@ __global__ void k_cloud_sums(const CloudJob *jobs, const uint32_t *chunk_job, ui
 __global__ void k_cloud_apply(const CloudJob *jobs, const uint32_t *chunk_job, uint32_t nchunks, const uint64_t *partial);
 __global__ void k_dequant(const DequantJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 
+// k_quant_out.hip (CRTHIP_BIND_QUANTIZED): jobs of up to QOUT_BLOB_MAX vertices by one workgroup each, from an id list (both passes, the values
+// re-read through L2); bigger ones - big meshes, clouds - in blocks of QOUT_BLOCK vertices (quant_out.h) from a block -> job map, the range
+// by integer atomics into the job's scratch words, then the store.  Measured on one lone job (profiles/quantized_outputs.md): the one-workgroup
+// kernel costs 9 us at 1 024 vertices and 4 us more every 1 024, the two launches 13 us whatever the size up to 16 384: it wins at 2 048, loses at 3 072
+constexpr uint32_t QOUT_BLOB_MAX = 2304;
+__global__ void k_quant_out_blob(const QuantOutJob *jobs, const uint32_t *job_ids, uint32_t njobs);
+__global__ void k_quant_range(const QuantOutJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_quant_store(const QuantOutJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+
 // k_mesh.hip
 __global__ void k_topology(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);
 __global__ void k_topology_lds(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);

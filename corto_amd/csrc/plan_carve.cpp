@@ -90,8 +90,9 @@ int Planner::carve() {
 			A.sym.resize(L.attrs[k].logs.size());
 			for(size_t j = 0; j < A.sym.size(); j++) need_stream(L.attrs[k].logs[j], A.sym[j]);
 			if(a.codec == CRTHIP_CODEC_COLOR) A.color = cv.take((uint64_t)L.h.nvert*a.N + 16, 16);
-			if(a.codec != CRTHIP_CODEC_COLOR && a.codec != CRTHIP_CODEC_NORMAL && (bd.stride || bd.format == CRTHIP_FMT_DOUBLE)) A.vals =
+			if(a.codec != CRTHIP_CODEC_COLOR && a.codec != CRTHIP_CODEC_NORMAL && generic_in_scratch(bd)) A.vals =
 				cv.take((uint64_t)L.h.nvert*a.N*4 + 16, 16);
+			if(bd.quantized && L.h.nvert > qout_blob_max()) A.qrange = cv.take(sizeof(QuantRangeWords), 16);
 			if(a.codec == CRTHIP_CODEC_NORMAL) {
 				A.diffs = cv.take((uint64_t)L.h.nvert*8 + 16, 16);
 				if(mesh && L.attrs[k].normal_prediction != 0 && normal_fused(L.h.nvert, L.h.nface) && normal_blob_lds_fn(L.h.nvert,

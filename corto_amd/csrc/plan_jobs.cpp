@@ -4,9 +4,17 @@
 
 int Planner::jobs() {
 	// the status block is about to move: the batch in flight writes to it
-	if(hs.bytes() + 16 > ctx->status_host.cap && harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE);
-	if(ctx->status_host.reserve(hs.bytes() + 16) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
+	// (a batch with a quantised binding keeps a crthip_quant_transform an attribute behind the status words)
+	{
+		uint32_t nattr = 0; bool any = false;
+		for(const BlobPlan &P : b->blobs) { nattr += (uint32_t)P.bind.size(); for(const Binding &bd : P.bind) any = any || (bd.buffer && bd.quantized); }
+		pl.quant_records = any ? nattr : 0u;
+	}
+	const size_t status_bytes = hs.records() + (size_t)pl.quant_records*sizeof(crthip_quant_transform) + 16;
+	if(status_bytes > ctx->status_host.cap && harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE);
+	if(ctx->status_host.reserve(status_bytes) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
 	hs_base = (int32_t *)ctx->status_host.p;
+	QuantOutRecord *const rec_host = (QuantOutRecord *)((uint8_t *)hs_base + hs.records());
 
 	// the dictionary (TunTable slot) of a stream: a new one, or the one an earlier stream of this launch group with the same table got
 	if(ctx->dict_slots.size() != 8192) ctx->dict_slots.assign(8192, 0u);
@@ -71,7 +79,8 @@ int Planner::jobs() {
 	dict_group0 = clers_dict;
 
 	uint32_t est_vbase = 0, est_fbase = 0;
-	for(uint32_t i = 0; i < nblobs; i++) {
+	size_t rec0 = 0;                                                         // the blob's first record (crthip_batch_bind_all's order)
+	for(uint32_t i = 0; i < nblobs; rec0 += b->blobs[i].bind.size(), i++) {
 		BlobPlan &P = b->blobs[i];
 		const BlobLayout &L = P.L;
 		BlobScratch &S = bs[i];
@@ -204,7 +213,7 @@ int Planner::jobs() {
 				// packed output: the caller's buffer is the int32 workspace (like upstream, vertex_attribute.h:190-193); with a stride, or
 				// as
 				// DOUBLE (eight bytes a value: upstream widens in place, front to back): scratch
-				const bool in_scratch = bd.stride || bd.format == CRTHIP_FMT_DOUBLE;
+				const bool in_scratch = generic_in_scratch(bd);                  // (or as uint16 grid values: CRTHIP_BIND_QUANTIZED)
 				void *work = in_scratch ? (void *)SP(A.vals) : bd.buffer;
 				if(a.strategy & CRTHIP_CORRELATED) push_unpack(as.logs[0], logs[0], work, 0, (uint16_t)a.N, (uint16_t)a.N, 0, val_fmt);
 				else for(uint32_t c = 0; c < a.N; c++) push_unpack(as.logs[c], logs[c], work, 1, 1, (uint16_t)a.N, (uint16_t)c, val_fmt);
@@ -256,7 +265,7 @@ int Planner::jobs() {
 							P.bind[pos_k].buffer && !P.bind[pos_k].stream_values;
 						if(!pos_ok) { P.host_status = CRTHIP_E_NORMAL_NEEDS_POSITION; continue; }
 						// the integer positions: in the caller's packed buffer, or in scratch
-						const bool pos_scratch = P.bind[pos_k].stride != 0 || P.bind[pos_k].format == CRTHIP_FMT_DOUBLE;
+						const bool pos_scratch = generic_in_scratch(P.bind[pos_k]);
 						n.position = pos_scratch ? (const int32_t *)SP(S.attr[pos_k].vals) : (const int32_t *)P.bind[pos_k].buffer;
 						n.faces = P.index ? P.index : (void *)SP(S.faces);
 						n.faces_u16 = P.index ? (uint8_t)P.index_u16 : 0;
@@ -275,6 +284,23 @@ int Planner::jobs() {
 					} else pl.any_diff_normal = true;
 					pl.normal.v.push_back(n);
 				}
+			} else if(bd.quantized) {
+				// the second finisher of the scratch path: uint16 relative to the minimum + the record (k_quant_out.hip).  No vertex: no job (upload fills the record)
+				if(nvert == 0) continue;
+				QuantOutJob q{};
+				q.values = (const int32_t *)SP(A.vals); q.buffer = bd.buffer; q.stride = bd.stride; q.nvert = nvert; q.N = a.N; q.q = a.q;
+				q.rec_host = (QuantOutRecord *)((crthip_quant_transform *)rec_host + rec0 + k);
+				q.rec_dev = b->quant_dev ? (QuantOutRecord *)((crthip_quant_transform *)b->quant_dev + rec0 + k) : nullptr;
+				q.status = hs_base + hs.status(i);
+				if(nvert <= qout_blob_max()) pl.quant_blob_ids.v.push_back((uint32_t)pl.quant.v.size());
+				else {
+					q.range = (uint32_t *)SP(A.qrange);
+					q.block0 = (uint32_t)pl.quant_block_job.v.size();
+					for(uint32_t c = 0; c < (nvert + QOUT_BLOCK - 1)/QOUT_BLOCK; c++) pl.quant_block_job.v.push_back((uint32_t)pl.quant.v.size());
+					// the seed of k_quant_range's integer atomics rides with the entropy stage's fills: 0xFF.. the minima, 0 the maxima (quant_out.h: qout_bias)
+					pl.fill.v.push_back(FillJob{SP(A.qrange), 16u, 0xFFu}); pl.fill.v.push_back(FillJob{SP(A.qrange + 16), 16u, 0u});
+				}
+				pl.quant.v.push_back(q);
 			} else if(!dequantised && !((int)k == pos_k && pos_by_normal)) {
 				DequantJob q{};
 				q.buffer = bd.buffer; q.q = a.q; q.nvert = nvert; q.N = a.N; q.out_components = bd.out_components;
@@ -304,7 +330,7 @@ int Planner::jobs() {
 			const bool pos_ok = pos_k >= 0 && L.h.attrs[pos_k].codec == CRTHIP_CODEC_GENERIC && L.h.attrs[pos_k].N == 3 &&
 				P.bind[pos_k].buffer && !P.bind[pos_k].stream_values;
 			if(!pos_ok) { P.host_status = CRTHIP_E_NORMAL_NEEDS_POSITION; continue; }
-			const bool pos_scratch = P.bind[pos_k].stride != 0 || P.bind[pos_k].format == CRTHIP_FMT_DOUBLE;
+			const bool pos_scratch = generic_in_scratch(P.bind[pos_k]);
 			n.position = pos_scratch ? (const int32_t *)SP(S.attr[pos_k].vals) : (const int32_t *)P.bind[pos_k].buffer;
 			n.faces = P.index ? P.index : (void *)SP(S.faces);
 			n.faces_u16 = P.index ? (uint8_t)P.index_u16 : 0;

@@ -26,12 +26,20 @@ int Planner::upload() {
 		resolve(n.diffs); resolve(n.out); resolve(n.position); resolve(n.faces); resolve(n.status); resolve(n.pos_out); resolve(n.fn_scratch);
 	}
 	for(auto &q : pl.dequant.v) { resolve(q.buffer); resolve(q.src); }
+	for(auto &q : pl.quant.v) { resolve(q.values); resolve(q.range); }
 
 	// host image -> device (one copy)
 	stage = (uint8_t *)ctx->staging.p;
 	memset(stage + (pl.unpack_partial_off - pl.jobs_begin), 0, unpack_state_words*8);
 	// (after the harvest above: the previous batch's words have been read)
-	memset(ctx->status_host.p, 0, hs.bytes());
+	memset(ctx->status_host.p, 0, hs.records() + (size_t)pl.quant_records*sizeof(crthip_quant_transform));
+	if(pl.quant_records) {                                               // a quantised attribute of a blob without vertices has no job: its record is all zero, written
+		crthip_quant_transform *rec = (crthip_quant_transform *)((uint8_t *)ctx->status_host.p + hs.records());
+		for(const BlobPlan &P : b->blobs) {
+			for(size_t k = 0; k < P.bind.size(); k++) if(P.bind[k].buffer && P.bind[k].quantized && P.L.h.nvert == 0) rec[k].written = 1;
+			rec += P.bind.size();
+		}
+	}
 	pl.each_array([&](auto &arr) { if(!arr.v.empty()) memcpy(stage + (arr.dev_off - pl.jobs_begin), arr.v.data(), arr.v.size()*sizeof(arr.v[0])); });
 
 	return CRTHIP_OK;
@@ -284,6 +292,16 @@ int Planner::launch(uint32_t phases, const Carry *carry) {
 	const uint32_t ndq = (uint32_t)pl.dequant_block_job.v.size();
 	if(ndq) { LT.begin("dequantize"); hipLaunchKernelGGL(k_dequant, dim3(ndq), dim3(256), 0, st, D(pl.dequant), D(pl.dequant_block_job),
 		ndq); LT.end(); }
+	// CRTHIP_BIND_QUANTIZED: the scratch path's other finisher, where k_dequant sits
+	if(!pl.quant_blob_ids.v.empty()) {
+		const uint32_t nj = (uint32_t)pl.quant_blob_ids.v.size();
+		LT.begin("quant_out_blob"); hipLaunchKernelGGL(k_quant_out_blob, dim3(nj), dim3(256), 0, st, D(pl.quant), D(pl.quant_blob_ids), nj); LT.end();
+	}
+	if(!pl.quant_block_job.v.empty()) {
+		const uint32_t nqb = (uint32_t)pl.quant_block_job.v.size();
+		LT.begin("quant_range"); hipLaunchKernelGGL(k_quant_range, dim3(nqb), dim3(256), 0, st, D(pl.quant), D(pl.quant_block_job), nqb); LT.end();
+		LT.begin("quant_store"); hipLaunchKernelGGL(k_quant_store, dim3(nqb), dim3(256), 0, st, D(pl.quant), D(pl.quant_block_job), nqb); LT.end();
+	}
 
 	// (status: written by the kernels straight into the pinned block)
 	HIP_TRY(hipGetLastError());
@@ -316,7 +334,7 @@ void Planner::account() {
 			const AttrHeader &a = L.h.attrs[k];
 			if(a.codec == CRTHIP_CODEC_NORMAL) ob += (uint64_t)L.h.nvert*3*(P.bind[k].format == CRTHIP_FMT_INT16 ? 2 : 4);
 			else if(a.codec == CRTHIP_CODEC_COLOR) ob += (uint64_t)L.h.nvert*P.bind[k].out_components;
-			else ob += (uint64_t)L.h.nvert*a.N*generic_work_bytes(P.bind[k].format);
+			else ob += (uint64_t)L.h.nvert*a.N*(P.bind[k].quantized ? 2u : generic_work_bytes(P.bind[k].format));
 		}
 		if(computes_normals(P)) ob += (uint64_t)L.h.nvert*3*(P.computed.format == CRTHIP_FMT_INT16 ? 2 : 4);
 	}
@@ -324,5 +342,7 @@ void Planner::account() {
 	ctx->in_flight = b; ctx->last_decoded = b;
 	{ Carry c; b->carriable = carry_args(c) && hosts_carry(); }
 	b->decoded = true; b->planned_wide = wide;
+	b->quant_bound.assign(pl.quant_records, 0); b->quant_recs.clear();        // (the records: harvest)
+	if(pl.quant_records) { size_t r = 0; for(auto &P : b->blobs) for(const Binding &bd : P.bind) b->quant_bound[r++] = bd.buffer && bd.quantized; }
 	b->dirty = false;
 }

@@ -47,7 +47,9 @@ extern "C" {
                                      crthip_encode_layout, crthip_encode_batch_layout, crthip_encode_input_model_layout,
                                      crthip_encode_topology_model_layout; crthip_batch_stats and crthip_pool_report grew at their ends
                                      (upload_copies, upload_gathered_bytes; grouped_steps); crthip_batch_bind_computed_normals (a new
-                                     call and nothing else: the number stays 6) */
+                                     call and nothing else: the number stays 6); CRTHIP_BIND_QUANTIZED, crthip_quant_transform,
+                                     crthip_batch_quant_transform, crthip_batch_bind_quant_transforms (a flag that was refused before and
+                                     two new calls: the number stays 6) */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -116,7 +118,7 @@ typedef struct {
 	                                setIndex(uint16_t*) (include/corto/decoder.h:53,61).  Must be a multiple of 4 for FLOAT outputs, of 2
 	                                for INT16 normals, and at least the element's size; with a stride the attribute is decoded in device
 	                                scratch and only its final values touch the buffer (a packed generic buffer doubles as int32 workspace) */
-	uint32_t reserved;           /* flags: 0, or CRTHIP_BIND_STREAM_VALUES */
+	uint32_t reserved;           /* flags: 0, CRTHIP_BIND_STREAM_VALUES or CRTHIP_BIND_QUANTIZED */
 } crthip_attr_binding;
 /* crthip_attr_binding.reserved, generic attributes only (ABI 6): stop behind the stream decode - `buffer` (nvert*N int32, packed, format
  * CRTHIP_FMT_INT32) receives the values as the stream holds them, i.e. what upstream's GenericAttr<int>::decode leaves in the buffer
@@ -126,6 +128,40 @@ typedef struct {
  * way cannot feed ESTIMATED / BORDER normals (upstream throws "Position attr has been overloaded" there, src/normal_attribute.cpp:210-213):
  * the blob fails with CRTHIP_E_NORMAL_NEEDS_POSITION. */
 #define CRTHIP_BIND_STREAM_VALUES 1u
+
+/* crthip_attr_binding.reserved, generic attributes only (added within ABI 6): quantised output.  `buffer` receives, for vertex i and
+ * component c, (uint16_t)(v[i][c] - base[c]): v is the delta-decoded integer value - what upstream's GenericAttr::deltaDecode leaves
+ * before dequantize (include/corto/vertex_attribute.h:160-193) - and base[c] the minimum of component c over the blob's vertices, as
+ * signed int32.  These are the 16-bit integer attributes of a KHR_mesh_quantization-style vertex buffer; the per-blob scale and offset the
+ * vertex shader applies are in the blob's crthip_quant_transform (below), which also holds the attribute's exact bounding box.
+ * Checked when the blob is bound:
+ *   CRTHIP_E_FORMAT    a format other than CRTHIP_FMT_UINT16; a normal or a colour
+ *   CRTHIP_E_ARGUMENT  together with CRTHIP_BIND_STREAM_VALUES, or with its format CRTHIP_FMT_INT32 (the code that combination had before the
+ *                      flag existed); out_components other than 0 or the stored N; a buffer that is not 2-byte
+ *                      aligned; a stride that is non-zero and below 2*N, or odd
+ *   CRTHIP_E_LIMIT     more than four stored components
+ * stride 0 (or exactly 2*N) is the packed layout, nvert*N halfwords.  With a stride only the 2*N bytes of each vertex are written - the
+ * rule of every strided binding - so a position uint16 x 3 at stride 8 lands in an interleaved record.
+ * One error is left to decode time, because it depends on the values: if max - min of any component exceeds 65535, nothing is written to
+ * that attribute's buffer, its record is filled with written = 0, and the blob's status becomes CRTHIP_E_FORMAT unless the blob already
+ * failed (an earlier code stays).  The blob's other arrays and the batch's other blobs decode as usual.
+ * A quantised position feeds stored ESTIMATED / BORDER normals and crthip_batch_bind_computed_normals as a FLOAT one does: they read the
+ * integers.  Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host (the flag is ignored there), the crt::Decoder facade or
+ * the veneers, which keep upstream's host contract; no INT16 / UINT8 / UINT32 variant. */
+#define CRTHIP_BIND_QUANTIZED 2u
+/* What takes a quantised attribute's halfwords back, one record per (blob, attribute).  The contract:
+ *   (float)(int32_t)(base[c] + out[i][c]) * q   is bit for bit the CRTHIP_FMT_FLOAT output of the same attribute,
+ * so a shader computes position = (float(base) + float(out)) * q where that sum is exact in float (|values| < 2^24), and
+ * [base*q, (base + span)*q] is the attribute's bounding box.  span[c] = max - min of component c (computed in 64 bits, always fits);
+ * components beyond `components` are zero.  nvert == 1: base = the value, span 0.  nvert == 0: the record is all zero but written = 1. */
+typedef struct {
+	int32_t base[4];
+	uint32_t span[4];
+	float q;                     /* the attribute's step as stored */
+	uint32_t components;         /* N as stored */
+	uint32_t written;            /* 1: the halfwords were stored; 0: a span beyond 65535, the buffer was left alone */
+	uint32_t reserved;
+} crthip_quant_transform;
 
 typedef struct crthip_ctx crthip_ctx;       /* one per device; owns streams + scratch pool */
 typedef struct crthip_batch crthip_batch;   /* a planned batch of independent .crt blobs */
@@ -245,6 +281,15 @@ int crthip_batch_bind_all(crthip_batch *b, const crthip_attr_binding *attrs, voi
  *                      (the rule of a stored ESTIMATED normal)
  * crthip_last_error() names the blob.  Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host or the crt::Decoder facade. */
 int crthip_batch_bind_computed_normals(crthip_batch *b, uint32_t i, void *buffer, uint32_t format, uint32_t stride);
+
+/* The record of attribute `attr` of blob i, bound with CRTHIP_BIND_QUANTIZED.  Valid after crthip_batch_sync of a decode: the kernels write
+ * the records into the batch's pinned status block, beside the status words.  CRTHIP_E_ARGUMENT if that attribute was not bound
+ * quantised in that decode, or the batch has not been decoded and synced. */
+int crthip_batch_quant_transform(const crthip_batch *b, uint32_t i, uint32_t attr, crthip_quant_transform *out);
+/* Optional: a DEVICE copy of the records for GPU-driven consumers.  device_records: room for sum(nattr) records, 16-byte aligned (else
+ * CRTHIP_E_ARGUMENT); the record of blob i, attribute k is at index sum(nattr of blobs < i) + k - crthip_batch_bind_all's order.  Entries
+ * of attributes not bound quantised are not touched.  NULL removes it; crthip_batch_reset* drops it. */
+int crthip_batch_bind_quant_transforms(crthip_batch *b, void *device_records);
 
 /* Enqueue the whole decode of the batch on the context's stream (asynchronous). */
 int crthip_batch_decode(crthip_batch *b);
@@ -866,6 +911,14 @@ int64_t crthip_encode_splice_model(const crthip_mesh *mesh, const crthip_attr_li
 int crthip_splice_copy_model(const uint8_t *src, uint8_t *dst, uint64_t bytes, uint32_t seed);
 int64_t crthip_encode_splice_plan_model(uint32_t n, const crthip_mesh *meshes, const crthip_attr_list *extra, uint64_t *blob_offset, uint32_t *blob_len,
                                         crthip_splice_stats *stats, uint64_t *pieces /* 3 per piece */, size_t piece_cap, uint32_t chunk_items);
+
+/* (test hook, no device needed)  The two passes of CRTHIP_BIND_QUANTIZED (csrc/quant_out.h) on the host, in the kernels' partition, lanes walked
+ * in a loop from the last to the first.  values: nvert*N int32, packed; out: the destination as a binding's buffer would be (2-byte aligned;
+ * stride as in the binding, 0 = packed); transform->q on entry is the attribute's step, the whole record on return.  which 0: the
+ * one-workgroup partition of k_quant_out_blob; which 1: the blocks of k_quant_range / k_quant_store, each pass visiting its blocks in an
+ * order shuffled by `seed`.  1 <= N <= 4, else CRTHIP_E_ARGUMENT. */
+int crthip_quant_out_model(const int32_t *values, uint32_t nvert, uint32_t N, uint32_t stride, void *out, crthip_quant_transform *transform,
+                           int which, uint32_t seed);
 
 #ifdef __cplusplus
 }
