@@ -57,24 +57,14 @@ extern "C" uint64_t crthip_arena_layout(uint32_t nblobs, const uint32_t *lens, u
 // batch object.  EVERY place that is about to reuse the context's stream, scratch or status buffer goes through here, so a
 // decode(A); decode(B); sync(A) sequence still reports A's failures (status used to be read only by crthip_batch_sync(A) and
 // was lost when another call had synchronised first).
-constexpr uint32_t TOPO_SLOTS_MAX = 4096;       // ring and pool slots of the automaton's LDS form (topo_lds_geometry's ring_max)
-static int harvest_selected(crthip_ctx *ctx);
 int harvest(crthip_ctx *ctx) {
 	crthip_batch *b = ctx->in_flight;
 	if(!b) return CRTHIP_OK;
-	// the status block and the upload bookkeeping of the batch in flight are its parity's; the caller goes on with the set it had selected
-	const uint8_t keep = ctx->active;
-	ctx_select(ctx, b->parity);
-	const int rc = harvest_selected(ctx);
-	ctx_select(ctx, keep);
-	return rc;
-}
-static int harvest_selected(crthip_ctx *ctx) {
-	crthip_batch *b = ctx->in_flight;
+	crthip_ctx::Half &set = ctx_set(ctx, b);                               // the status block and the upload bookkeeping are its parity's
 	if(hipEventSynchronize(ctx->ev_done) != hipSuccess) { ctx->in_flight = nullptr; return CRTHIP_E_DEVICE; }
 	// (only an upload that sits in front of the event: one enqueued behind the decode is still on its way)
-	if(ctx->done_covers_seq == ctx->upload_seq) ctx->arena_upload_pending = false;
-	const int32_t *hs = (const int32_t *)ctx->status_host.p;
+	if(set.done_covers_seq == set.upload_seq) set.arena_upload_pending = false;
+	const int32_t *hs = (const int32_t *)set.status_host.p;
 	const size_t n = b->blobs.size();
 	const StatusWords W{n};
 	for(size_t i = 0; i < n; i++) b->status[i] = b->blobs[i].host_status ? b->blobs[i].host_status : hs[W.status(i)];
@@ -82,66 +72,16 @@ static int harvest_selected(crthip_ctx *ctx) {
 		const crthip_quant_transform *rec = (const crthip_quant_transform *)((const uint8_t *)hs + W.records());
 		b->quant_recs.assign(rec, rec + b->quant_bound.size());
 	}
-	b->stats.topology_fallbacks = 0;
-	for(size_t i = 0; i < n; i++) b->stats.topology_fallbacks += (uint64_t)(hs[W.topo_flags(i)] & 1);
-	// K-DELTA keeps values in LDS as int16 relative to vertex 0 and redoes an attribute that does not fit in HBM (slow, exact): a context
-	// that meets such blobs (positions quantised beyond 15 bits) plans its next batches with 32-bit values; a long run of batches later it
-	// tries the narrow layout again, with growing patience if that turns out wrong
-	b->stats.delta_redone = 0; b->stats.delta_walked = 0;
-	for(size_t i = 0; i < n; i++) b->stats.delta_walked += (uint32_t)(hs[W.delta_flags(i) + 1] != 0);
-	if(!b->planned_wide) {
-		for(size_t i = 0; i < n; i++) b->stats.delta_redone += (uint64_t)(hs[W.delta_flags(i)] != 0);
-		if(b->stats.delta_redone) {
-			ctx->delta_wide = true;
-			// overflowed right after narrowing again (never on a context's first overflow)
-			if(ctx->delta_just_narrowed && ctx->delta_patience < (1u << 20)) ctx->delta_patience *= 2;
-			ctx->delta_calm = 0;
-		}
-		ctx->delta_just_narrowed = false;                                   // (narrow and fine, or wide from here on)
-	} else if(!ctx->dbg.delta_wide && ++ctx->delta_calm >= ctx->delta_patience) { ctx->delta_wide = false; ctx->delta_calm = 0;
-		ctx->delta_just_narrowed = true; }
-	// more than one blob in twenty redone on the HBM front (5x slower): more edge slots from the next batch on - as many as the redone
-	// blobs say they
-	// would have needed (k_topology_lds' redo reports ring and pool slots above bit 0 of the flags word; round 4 went up four-fold whatever
-	// was
-	// missing, and a batch of Delaunay discs that needed 600 pool slots of its 512 got 2 048 + 2 048: 72 KB of LDS a blob, two automata a
-	// CU, the
-	// pipeline at a third of its rate); a long run without any: try less again, and be more patient the next time that turns out to be too
-	// little
-	if(b->stats.topology_fallbacks*20 > n) {
-		uint32_t ring_m = 1, pool_q8 = 8;
-		const uint32_t cap_before = ctx->topo_pool_cap;
-		uint32_t learnable = 0;
-		for(size_t i = 0; i < n; i++) if(hs[W.topo_flags(i)] & 1) {
-			const uint32_t tf = (uint32_t)hs[W.topo_flags(i)];
-			// a redo that ended in an error (an untrusted stream runs its pool dry before it fails) teaches nothing, and a front beyond the LDS
-			// form's 4 096 + 4 096 records is on the HBM path by design: neither may scale every OTHER blob's request up
-			if(b->status[i]) continue;
-			if(((tf >> 1) & 0x7FFFu) > TOPO_SLOTS_MAX || (tf >> 16) > TOPO_SLOTS_MAX) continue;
-			learnable++;
-			const auto &h = b->blobs[i].L.h;
-			uint32_t ring, pool, symwin;
-			topo_lds_geometry(h.nface, b->blobs[i].L.clers.size, 4096, 1, 8, n >= 32 ? 4u : 8u, ring, pool, symwin);
-			const uint32_t need_ring = (tf >> 1) & 0x7FFFu, need_pool = tf >> 16;
-			uint32_t m = 1;
-			while(ring*m < need_ring && m < 16) m <<= 1;
-			ring_m = std::max(ring_m, m);
-			pool_q8 = std::max(pool_q8, std::min(128u, (need_pool*8 + pool - 1)/pool + 1u));      // (an eighth on top)
-			ctx->topo_pool_cap = std::max(ctx->topo_pool_cap, need_pool + need_pool/8);
-		}
-		const bool grew = ring_m > ctx->topo_scale || pool_q8 > ctx->topo_pool_q8 || ctx->topo_pool_cap > cap_before;
-		ctx->topo_scale = std::max(ctx->topo_scale, ring_m); ctx->topo_pool_q8 = std::max(ctx->topo_pool_q8, pool_q8);
-		// (they fell back with what they asked for: capacity, or a need the redo cannot see)
-		if(!grew && learnable) { ctx->topo_scale = std::min(16u, ctx->topo_scale*2); ctx->topo_pool_q8 = std::min(128u, ctx->topo_pool_q8*2);
-			ctx->topo_pool_cap *= 2; }
-		ctx->topo_pool_cap = std::min(ctx->topo_pool_cap, TOPO_SLOTS_MAX + TOPO_SLOTS_MAX/8);      // (a uint32 that doubled without a bound wrapped to 0 = "no cap")
-		if(ctx->topo_calm == 0 && ctx->topo_patience < (1u << 20)) ctx->topo_patience *= 2;    // fell back right after scaling down
-		ctx->topo_calm = 0;
-	} else if(b->stats.topology_fallbacks == 0 && (ctx->topo_scale > 1 || ctx->topo_pool_q8 > 8) &&
-		++ctx->topo_calm >= ctx->topo_patience) {
-		ctx->topo_scale = std::max(1u, ctx->topo_scale/2); ctx->topo_pool_q8 = std::max(8u, ctx->topo_pool_q8*3/4); ctx->topo_pool_cap =
-			ctx->topo_pool_cap*3/4; ctx->topo_calm = 0;
+	b->stats.topology_fallbacks = 0; b->stats.delta_redone = 0; b->stats.delta_walked = 0;
+	for(size_t i = 0; i < n; i++) {
+		b->stats.topology_fallbacks += (uint64_t)(hs[W.topo_flags(i)] & 1);
+		b->stats.delta_walked += (uint32_t)(hs[W.delta_flags(i) + 1] != 0);
+		if(!b->planned_wide) b->stats.delta_redone += (uint64_t)(hs[W.delta_flags(i)] != 0);
 	}
+	// what the context learns from them (plan_feedback.h)
+	ctx->delta.update(b->planned_wide, b->stats.delta_redone, ctx->dbg.delta_wide != 0);
+	ctx->topo.update(n, [&](size_t i) { const auto &L = b->blobs[i].L;
+		return TopoBlob{L.h.nface, L.clers.size, (uint32_t)hs[W.topo_flags(i)], b->status[i]}; });
 	ctx->in_flight = nullptr;
 	return CRTHIP_OK;
 }
@@ -210,7 +150,7 @@ extern "C" int crthip_ctx_create(int device, crthip_ctx **out) {
 	   hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
 	   hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming) != hipSuccess) { delete c; return fail(CRTHIP_E_DEVICE); }
 	c->dbg = debug_config_from_env();
-	c->delta_wide = c->dbg.delta_wide != 0;
+	c->delta.wide = c->dbg.delta_wide != 0;
 	// kernels that may ask for more than 64 KiB of dynamic LDS: raise their limit on this device, once per context
 	// (function attributes are per device; doing it here keeps the launch paths free of shared state between host threads)
 	if(hipFuncSetAttribute((const void *)k_topology_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TOPO_LDS_MAX) != hipSuccess ||
@@ -234,9 +174,8 @@ extern "C" void crthip_ctx_destroy(crthip_ctx *c) {
 	(void)hipStreamSynchronize(c->stream);
 	c->timer.release();
 	if(c->host_batch) { crthip_batch *hb = c->host_batch; c->host_batch = nullptr; crthip_batch_destroy(hb); }
-	c->scratch.release(); c->staging.release(); c->arena_pin.release(); c->status_host.release(); c->host_out.release();
-	c->spare.scratch.release(); c->spare.staging.release(); c->spare.arena_pin.release(); c->spare.status_host.release();
-		c->host_pin.release();
+	for(crthip_ctx::Half &h : c->set) h.release();
+	c->host_out.release(); c->host_pin.release();
 	c->walk_dev.release(); c->walk_pin.release();
 	if(c->ev_walk0) (void)hipEventDestroy(c->ev_walk0);
 	if(c->ev_walk1) (void)hipEventDestroy(c->ev_walk1);
@@ -292,39 +231,63 @@ extern "C" int crthip_ctx_sync(crthip_ctx *c) {
 
 // ------------------------------------------------------------------------------------------------
 
+// What batch_fill and batch_fill_resident share.  begin_fill: the object forgets its last life (a planned stage, stats, quantised records) and
+// its set of per-call blocks is the one of its parity; adopt_blob: a blob whose layout is known takes its place in the arena, unbound, and is
+// counted (its bytes in the arena layout are returned); end_fill: the arena and the status words of a fill that went through
+static crthip_ctx::Half &begin_fill(crthip_ctx *ctx, crthip_batch *b) {
+	b->ctx = ctx;
+	drop_staged(b);
+	b->stats = crthip_batch_stats{};
+	b->walk = crthip_walk_stats{};
+	b->dirty = true; b->decoded = false;
+	b->d_arena = nullptr;
+	b->quant_dev = nullptr; b->quant_bound.clear(); b->quant_recs.clear();
+	return ctx_set(ctx, b);
+}
+static uint64_t adopt_blob(BlobPlan &P, uint64_t arena_off, uint32_t len, crthip_batch_stats &stats) {
+	P.arena_off = arena_off; P.len = len;
+	P.bind.assign(P.L.h.attrs.size(), Binding{});
+	P.index = nullptr; P.index_u16 = 0; P.host_status = 0; P.computed = Binding{};
+	P.dbg_clers = P.dbg_pred = ~0ull; P.dbg_nclers = 0; P.clers_in_arena = false;
+	stats.total_nvert += P.L.h.nvert; stats.total_nface += P.L.h.nface;
+	if(P.L.h.nface) { stats.clers_symbols += P.L.clers.size; stats.split_bytes += (uint64_t)P.L.split.nwords*4; }
+	return ((uint64_t)len + 15) & ~15ull;
+}
+static int end_fill(crthip_batch *b, const uint8_t *d_arena, uint64_t bytes, double t_create) {
+	b->arena_bytes = bytes;
+	b->stats.arena_bytes = bytes;
+	b->d_arena = d_arena;
+	b->status.assign(b->blobs.size(), 0);
+	b->stats.host_create_us = (float)(now_us() - t_create);
+	return CRTHIP_OK;
+}
+// the guards of every reset: the device, the object's decode in flight harvested, its intermediates no longer the context's last
+static int begin_reset(crthip_batch *b) {
+	crthip_ctx *ctx = b->ctx;
+	HIP_TRY(hipSetDevice(ctx->device));
+	if(ctx->in_flight == b) { if(harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE); }
+	if(ctx->last_decoded == b) ctx->last_decoded = nullptr;
+	return CRTHIP_OK;
+}
+
 // (re)fill a batch object from a list of blobs: header parse + bounds-checked walk of each, arena layout, upload unless resident
 // (dev_off: null, or - device_arena set - where every blob lies relative to it; without it the blobs follow one another in arena layout)
 static int batch_fill(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs, const uint8_t *const *blobs, const uint32_t *lens,
 	const void *device_arena, const uint64_t *dev_off = nullptr) {
 	const double t_create = now_us();
-	b->ctx = ctx;
-	drop_staged(b);
-	ctx_select(ctx, b->parity);
+	crthip_ctx::Half &set = begin_fill(ctx, b);
 	b->blobs.resize(nblobs);
-	b->stats = crthip_batch_stats{};
-	b->walk = crthip_walk_stats{};
 	b->walk.host_walked = nblobs;
-	b->dirty = true; b->decoded = false;
-	b->quant_dev = nullptr; b->quant_bound.clear(); b->quant_recs.clear();
 	uint64_t off = 0;
 	for(uint32_t i = 0; i < nblobs; i++) {
 		BlobPlan &P = b->blobs[i];
 		reset_layout(P.L);
 		int err = walk_blob(blobs[i], lens[i], P.L);
 		if(err) return fail(err, std::string(crthip_strerror(err)) + " (blob " + std::to_string(i) + ")");
-		P.arena_off = device_arena && dev_off ? dev_off[i] : off; P.len = lens[i];
-		P.bind.assign(P.L.h.attrs.size(), Binding{});
-		P.index = nullptr; P.index_u16 = 0; P.host_status = 0; P.computed = Binding{};
-		P.dbg_clers = P.dbg_pred = ~0ull; P.dbg_nclers = 0; P.clers_in_arena = false;
-		off += ((uint64_t)lens[i] + 15) & ~15ull;
-		b->stats.total_nvert += P.L.h.nvert; b->stats.total_nface += P.L.h.nface;
-		if(P.L.h.nface) { b->stats.clers_symbols += P.L.clers.size; b->stats.split_bytes += (uint64_t)P.L.split.nwords*4; }
+		off += adopt_blob(P, device_arena && dev_off ? dev_off[i] : off, lens[i], b->stats);
 	}
-	b->arena_bytes = off;
-	b->stats.arena_bytes = off;
-	b->d_arena = nullptr;
-	if(device_arena) b->d_arena = (const uint8_t *)device_arena;
-	else if(off) {
+	const uint8_t *d_arena = (const uint8_t *)device_arena;
+	if(!device_arena && off) {
 		if(b->own_arena.reserve(off) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
 		// the blobs are gathered in a pinned image of the arena and go up in ONE copy on the context's stream, in front of the kernels that
 		// read them - and nobody waits for it (round 3: the hipStreamSynchronize that stood here was 100 us of every from-host step, on the
@@ -358,23 +321,21 @@ static int batch_fill(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs, const u
 			b->stats.upload_copies = nruns;
 		} else {
 		// (a batch that was created and not decoded yet: its upload has to be through before the image is reused)
-		if(ctx->arena_upload_pending) {
+		if(set.arena_upload_pending) {
 			if(hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(CRTHIP_E_DEVICE);
-			ctx->arena_upload_pending = false; ctx->done_covers_seq = ctx->upload_seq;
+			set.arena_upload_pending = false; set.done_covers_seq = set.upload_seq;
 		}
-		if(ctx->arena_pin.reserve(off) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
-		uint8_t *h = (uint8_t *)ctx->arena_pin.p;
+		if(set.arena_pin.reserve(off) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
+		uint8_t *h = (uint8_t *)set.arena_pin.p;
 		for(uint32_t i = 0; i < nblobs; i++) memcpy(h + b->blobs[i].arena_off, blobs[i], lens[i]);
 		if(hipMemcpyAsync(b->own_arena.p, h, off, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(CRTHIP_E_DEVICE);
-		ctx->arena_upload_pending = true;
-		ctx->upload_seq++;
+		set.arena_upload_pending = true;
+		set.upload_seq++;
 		b->stats.upload_copies = 1; b->stats.upload_gathered_bytes = off;
 		}
-		b->d_arena = (const uint8_t *)b->own_arena.p;
+		d_arena = (const uint8_t *)b->own_arena.p;
 	}
-	b->status.assign(nblobs, 0);
-	b->stats.host_create_us = (float)(now_us() - t_create);
-	return CRTHIP_OK;
+	return end_fill(b, d_arena, off, t_create);
 }
 
 extern "C" int crthip_batch_create(crthip_ctx *ctx, uint32_t nblobs, const uint8_t *const *blobs, const uint32_t *lens,
@@ -391,22 +352,16 @@ extern "C" int crthip_batch_create(crthip_ctx *ctx, uint32_t nblobs, const uint8
 extern "C" int crthip_batch_reset(crthip_batch *b, uint32_t nblobs, const uint8_t *const *blobs, const uint32_t *lens,
 	const void *device_arena) {
 	if(!b || !b->ctx || (nblobs && (!blobs || !lens))) return fail(CRTHIP_E_ARGUMENT);
-	crthip_ctx *ctx = b->ctx;
-	HIP_TRY(hipSetDevice(ctx->device));
-	if(ctx->in_flight == b) { if(harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE); }
-	if(ctx->last_decoded == b) ctx->last_decoded = nullptr;
-	return batch_fill(ctx, b, nblobs, blobs, lens, device_arena);       // on failure the batch is left empty-handed: reset or destroy it
+	if(const int err = begin_reset(b)) return err;
+	return batch_fill(b->ctx, b, nblobs, blobs, lens, device_arena);    // on failure the batch is left empty-handed: reset or destroy it
 }
 
 namespace corto_hip {
 // crthip_batch_reset for blobs resident in SEVERAL device arenas (a pool lane's group of items): blob i lies at device_base + dev_off[i]
 int batch_reset_at(crthip_batch *b, uint32_t nblobs, const uint8_t *const *blobs, const uint32_t *lens, const void *device_base, const uint64_t *dev_off) {
 	if(!b || !b->ctx || !nblobs || !blobs || !lens || !device_base || !dev_off) return fail(CRTHIP_E_ARGUMENT);
-	crthip_ctx *ctx = b->ctx;
-	HIP_TRY(hipSetDevice(ctx->device));
-	if(ctx->in_flight == b) { if(harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE); }
-	if(ctx->last_decoded == b) ctx->last_decoded = nullptr;
-	return batch_fill(ctx, b, nblobs, blobs, lens, device_base, dev_off);
+	if(const int err = begin_reset(b)) return err;
+	return batch_fill(b->ctx, b, nblobs, blobs, lens, device_base, dev_off);
 }
 }
 
@@ -416,14 +371,8 @@ int batch_reset_at(crthip_batch *b, uint32_t nblobs, const uint8_t *const *blobs
 static int batch_fill_resident(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs, const uint8_t *base, const uint64_t *offsets,
 	const uint32_t *lens) {
 	const double t_create = now_us();
-	b->ctx = ctx;
-	drop_staged(b);
-	ctx_select(ctx, b->parity);
-	b->blobs.clear(); b->status.clear(); b->d_arena = nullptr; b->arena_bytes = 0;
-	b->stats = crthip_batch_stats{};
-	b->walk = crthip_walk_stats{};
-	b->dirty = true; b->decoded = false;
-	b->quant_dev = nullptr; b->quant_bound.clear(); b->quant_recs.clear();
+	crthip_ctx::Half &set = begin_fill(ctx, b);
+	b->blobs.clear(); b->status.clear(); b->arena_bytes = 0;
 	for(uint32_t i = 0; i < nblobs; i++)
 		if(offsets[i] & 15) return fail(CRTHIP_E_ARGUMENT, "resident blob offsets must be multiples of 16 (blob " + std::to_string(i) + ")");
 	const uint32_t cap = WALK_RECORD_BYTES;
@@ -448,7 +397,7 @@ static int batch_fill_resident(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs
 		}
 		const bool synced = hipStreamSynchronize(st) == hipSuccess;
 		if(!ok || !synced) { (void)hipGetLastError(); return fail(CRTHIP_E_DEVICE, "the device walk of resident blobs failed"); }
-		ctx->arena_upload_pending = false; ctx->done_covers_seq = ctx->upload_seq;
+		set.arena_upload_pending = false; set.done_covers_seq = set.upload_seq;
 		float ms = 0.f;
 		if(hipEventElapsedTime(&ms, ctx->ev_walk0, ctx->ev_walk1) == hipSuccess) b->walk.walk_kernel_us = ms*1000.f;
 		b->walk.bytes_to_host = rec_bytes;
@@ -472,20 +421,9 @@ static int batch_fill_resident(crthip_ctx *ctx, crthip_batch *b, uint32_t nblobs
 			err = walk_blob((const uint8_t *)copy.data(), lens[i], P.L);
 		} else b->walk.device_walked++;
 		if(err) { b->blobs.clear(); return fail(err, std::string(crthip_strerror(err)) + " (blob " + std::to_string(i) + ")"); }
-		P.arena_off = offsets[i]; P.len = lens[i];
-		P.bind.assign(P.L.h.attrs.size(), Binding{});
-		P.index = nullptr; P.index_u16 = 0; P.host_status = 0; P.computed = Binding{};
-		P.dbg_clers = P.dbg_pred = ~0ull; P.dbg_nclers = 0; P.clers_in_arena = false;
-		bytes += ((uint64_t)lens[i] + 15) & ~15ull;
-		b->stats.total_nvert += P.L.h.nvert; b->stats.total_nface += P.L.h.nface;
-		if(P.L.h.nface) { b->stats.clers_symbols += P.L.clers.size; b->stats.split_bytes += (uint64_t)P.L.split.nwords*4; }
+		bytes += adopt_blob(P, offsets[i], lens[i], b->stats);
 	}
-	b->arena_bytes = bytes;
-	b->stats.arena_bytes = bytes;
-	b->d_arena = base;
-	b->status.assign(nblobs, 0);
-	b->stats.host_create_us = (float)(now_us() - t_create);
-	return CRTHIP_OK;
+	return end_fill(b, base, bytes, t_create);
 }
 
 extern "C" int crthip_batch_create_resident(crthip_ctx *ctx, uint32_t nblobs, const void *device_base, const uint64_t *offsets,
@@ -502,11 +440,8 @@ extern "C" int crthip_batch_create_resident(crthip_ctx *ctx, uint32_t nblobs, co
 extern "C" int crthip_batch_reset_resident(crthip_batch *b, uint32_t nblobs, const void *device_base, const uint64_t *offsets,
                                            const uint32_t *lens) {
 	if(!b || !b->ctx || (nblobs && (!device_base || !offsets || !lens)) || ((uintptr_t)device_base & 15)) return fail(CRTHIP_E_ARGUMENT);
-	crthip_ctx *ctx = b->ctx;
-	HIP_TRY(hipSetDevice(ctx->device));
-	if(ctx->in_flight == b) { if(harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE); }
-	if(ctx->last_decoded == b) ctx->last_decoded = nullptr;
-	return batch_fill_resident(ctx, b, nblobs, (const uint8_t *)device_base, offsets, lens);
+	if(const int err = begin_reset(b)) return err;
+	return batch_fill_resident(b->ctx, b, nblobs, (const uint8_t *)device_base, offsets, lens);
 }
 
 extern "C" void crthip_batch_destroy(crthip_batch *b) {
@@ -705,9 +640,8 @@ static int build_and_launch(crthip_batch *b) {
 static int build_and_launch_inner(crthip_batch *b) {
 	// host-side cost of a decode call (crthip_batch_stats::host_*_us)
 	const double t0 = now_us();
-	ctx_select(b->ctx, b->parity);
 	b->ctx->timer.reset();
-	b->ctx->plan.reset();
+	ctx_set(b->ctx, b).plan.reset();
 	Planner P(b);
 	int err = P.carve();
 	if(!err) err = P.jobs();
@@ -742,12 +676,12 @@ static int decode_pair(crthip_batch *cur, crthip_batch *next) {
 	ctx->timer.reset();
 	int err;
 	Planner *N = nullptr;
-	Carry carry{}; bool carried = false, nsplit = false;                    // (a planner's answers hold while ITS batch's parity is selected)
+	Planner *const C = cur ? cur->staged : nullptr;
+	Carry carry{}; bool carried = false, nsplit = false;
 	double t1 = t0, t2 = t0;
 	if(next) {
 		drop_staged(next);
-		ctx_select(ctx, next->parity);
-		ctx->plan.reset();
+		ctx_set(ctx, next).plan.reset();
 		next->staged = N = new Planner(next);
 		err = N->carve();
 		if(!err) err = N->jobs();
@@ -758,33 +692,18 @@ static int decode_pair(crthip_batch *cur, crthip_batch *next) {
 		t2 = now_us();
 		next->stats.host_plan_us = (float)(t1 - t0); next->stats.host_stage_us = (float)(t2 - t1);
 		nsplit = N->splits();
-		carried = cur && nsplit && N->carry_args(carry);
-	}
-	if(cur) {
-		ctx_select(ctx, cur->parity);
-		Planner *C = cur->staged;
-		carried = carried && C->hosts_carry();                                // (with or without its own entropy stage in front)
+		carried = cur && nsplit && N->carry_args(carry) && C->hosts_carry();  // (with or without its own entropy stage in front)
 	}
 	// the first batch of a lane runs its entropy stage alone; after that a stage that cannot be carried is not enqueued early at all - its launches
 	// behind cur's kernels cost the queue what they cost in front of its own mesh stage, and measured slower (profiles/pool_carry.md)
 	const bool early = nsplit && (carried || !cur);
+	if(early && (err = N->launch(PH_UP)) != CRTHIP_OK) return err;
+	if(cur && (err = C->launch(C->e_done ? (uint32_t)PH_MESH : (uint32_t)PH_ALL, carried ? &carry : nullptr)) != CRTHIP_OK) return err;
 	if(early) {
-		ctx_select(ctx, next->parity);
-		if((err = N->launch(PH_UP)) != CRTHIP_OK) return err;
-	}
-	if(cur) {
-		ctx_select(ctx, cur->parity);
-		Planner *C = cur->staged;
-		if((err = C->launch(C->e_done ? (uint32_t)PH_MESH : (uint32_t)PH_ALL, carried ? &carry : nullptr)) != CRTHIP_OK) return err;
-	}
-	if(early) {
-		ctx_select(ctx, next->parity);
 		if((err = N->launch(carried ? (uint32_t)PH_FILL : (uint32_t)(PH_TUN | PH_FILL))) != CRTHIP_OK) return err;
 		N->e_done = true;
 	}
 	if(cur) {
-		ctx_select(ctx, cur->parity);
-		Planner *C = cur->staged;
 		if((err = C->mark_done()) != CRTHIP_OK) return err;
 		C->account();
 		cur->stats.host_launch_us = (float)(now_us() - t2);
@@ -881,16 +800,16 @@ extern "C" int64_t crthip_batch_debug_read(crthip_batch *b, uint32_t i, const ch
 	if(!b || i >= b->blobs.size() || !what || !host_out || !b->decoded) return fail(CRTHIP_E_ARGUMENT);
 	crthip_ctx *ctx = b->ctx;
 	if(ctx->last_decoded != b) return fail(CRTHIP_E_ARGUMENT, "the context's scratch block has been reused by a later call");
-	ctx_select(ctx, b->parity);
 	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	const uint8_t *scratch = (const uint8_t *)ctx_set(ctx, b).scratch.p;
 	BlobPlan &P = b->blobs[i];
 	const uint8_t *src = nullptr; size_t n = 0;
 	if(!strcmp(what, "clers")) {
 		if(P.dbg_clers == ~0ull) return 0;
-		src = P.clers_in_arena ? b->d_arena + P.dbg_clers : (const uint8_t *)ctx->scratch.p + P.dbg_clers; n = P.dbg_nclers;
+		src = P.clers_in_arena ? b->d_arena + P.dbg_clers : scratch + P.dbg_clers; n = P.dbg_nclers;
 	} else if(!strcmp(what, "prediction")) {
 		if(P.dbg_pred == ~0ull) return 0;
-		src = (const uint8_t *)ctx->scratch.p + P.dbg_pred; n = (size_t)P.L.h.nvert*12;
+		src = scratch + P.dbg_pred; n = (size_t)P.L.h.nvert*12;
 	} else return fail(CRTHIP_E_ARGUMENT);
 	n = std::min(n, cap);
 	HIP_TRY(hipMemcpy(host_out, src, n, hipMemcpyDeviceToHost));
@@ -999,7 +918,7 @@ int decode_host_many(crthip_ctx *ctx, uint32_t n, HostDecodeReq *reqs, bool copy
 	if(!err) err = crthip_batch_decode(b);
 	for(auto &pp : pred_piece) {
 		const BlobPlan &P = b->blobs[pp.first];
-		if(!err && P.dbg_pred != ~0ull && hipMemcpyAsync(dbase + pp.second, (const uint8_t *)ctx->scratch.p + P.dbg_pred, (size_t)P.L.h.nvert*12,
+		if(!err && P.dbg_pred != ~0ull && hipMemcpyAsync(dbase + pp.second, (const uint8_t *)ctx_set(ctx, b).scratch.p + P.dbg_pred, (size_t)P.L.h.nvert*12,
 			hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) err = fail(CRTHIP_E_DEVICE);
 	}
 	if(!err && total && hipMemcpyAsync(hbase, dbase, total, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) err = fail(CRTHIP_E_DEVICE);
@@ -1070,9 +989,10 @@ extern "C" int crthip_tunstall_decode_blocks(crthip_ctx *ctx, uint32_t n, const 
 	const uint64_t o_tun = cv.take(tun.size()*sizeof(TunStream) + 16, 16), o_cs = cv.take(chunk_stream.size()*4 + 16, 16), o_fill =
 		cv.take(fills.size()*sizeof(FillJob) + 16, 16);
 	const uint64_t total = cv.take(0);
-	if(ctx->scratch.reserve(total + 256) != CRTHIP_OK || ctx->staging.reserve(total - o_jobs +
+	crthip_ctx::Half &set = ctx->set[0];                                   // (no batch object: the blocks of a lone context's decodes)
+	if(set.scratch.reserve(total + 256) != CRTHIP_OK || set.staging.reserve(total - o_jobs +
 		256) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
-	uint8_t *base = (uint8_t *)ctx->scratch.p, *stage = (uint8_t *)ctx->staging.p;
+	uint8_t *base = (uint8_t *)set.scratch.p, *stage = (uint8_t *)set.staging.p;
 	if(!tun.empty()) memcpy(stage + (o_tun - o_jobs), tun.data(), tun.size()*sizeof(TunStream));
 	if(!chunk_stream.empty()) memcpy(stage + (o_cs - o_jobs), chunk_stream.data(), chunk_stream.size()*4);
 	if(!fills.empty()) memcpy(stage + (o_fill - o_jobs), fills.data(), fills.size()*sizeof(FillJob));

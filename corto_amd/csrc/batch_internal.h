@@ -21,6 +21,7 @@
 #include "device_plan.h"
 #include "encoder_internal.h"
 #include "kernels.h"
+#include "plan_feedback.h"
 #include "quant_out.h"
 
 using namespace corto_hip;
@@ -153,18 +154,12 @@ struct crthip_ctx {
 	                                // the first launch that forks (ctx_stream2), never on a context that stays single-stream
 	hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 	// recorded behind a decode's last kernel: what sync / done wait for, so that work a caller queues on the stream BEHIND a decode
+	// does not delay the harvest of this one
 	hipEvent_t ev_done = nullptr;
-	                                // does not delay the harvest of this one
-	// arena_pin uploads enqueued so far / how many of them sit IN FRONT of ev_done (harvest may only call those complete)
-	uint32_t upload_seq = 0, done_covers_seq = 0;
 	DebugConfig dbg;                // every environment switch, read once when the context is made (debug_config.h)
 	// largest LDS request for which K-NRM keeps its face normals in LDS (0 for a context that is one of many: crthip_ctx_set_single_stream)
 	uint32_t normal_fn_max = NORMAL_FN_LDS_MAX;
 	uint8_t single_stream = 0;                        // crthip_ctx_set_single_stream: no second HIP stream for the attribute streams
-	DeviceBuf scratch;        // symbols, tables, fronts, predictions, job arrays ... (one batch in flight at a time)
-	PinnedBuf staging;        // host image of the job arrays
-	PinnedBuf arena_pin;      // host image of a batch's blobs on their way to the device (batch_fill: one H2D copy, not waited for)
-	PinnedBuf status_host;
 	// crthip_batch_create_resident: the walk's jobs + records on the device and their pinned host image; its two timing events (made on first use)
 	DeviceBuf walk_dev;
 	PinnedBuf walk_pin;
@@ -176,8 +171,6 @@ struct crthip_ctx {
 	bool packed_host = false;
 	crthip_splice_stats enc_splice{};                 // crthip_ctx_encode_splice_stats: the last crthip_encode_batch_to_device
 	int encode_topology = CRTHIP_TOPOLOGY_HOST;       // crthip_ctx_set_encode_topology: where crthip_encode_batch runs the CLERS topology pass
-	// a batch's blobs are (perhaps still) on their way from arena_pin: cleared by whoever synchronises the stream
-	bool arena_upload_pending = false;
 	crthip_batch *last_decoded = nullptr;// whose intermediates the scratch block holds (crthip_batch_debug_read)
 	// crthip_decode_host: everything a one-blob decode with host buffers needs, kept from call to call (no hipMalloc / create in the
 	// steady state) and guarded by a mutex so that callers may share a context between threads
@@ -185,44 +178,34 @@ struct crthip_ctx {
 	crthip_batch *host_batch = nullptr;
 	DeviceBuf host_out;       // decoded outputs of the one blob, back to back
 	PinnedBuf host_pin;       // ... and their landing zone in pinned host memory (one async D2H copy)
-	// feedback on the LDS edge slots of the CLERS automaton: raised after a batch with fallbacks, lowered after a long calm run
-	// K-TOPO's learnt slots: ring x topo_scale (a power of two), pool x topo_pool_q8 / 8 (kernels.h: topo_lds_geometry)
-	uint32_t topo_scale = 1, topo_pool_q8 = 8, topo_pool_cap = 0, topo_calm = 0, topo_patience = 64;
+	// what harvest() learns from a batch's flags (plan_feedback.h): K-DELTA's layout, the automaton's LDS edge slots
+	DeltaFeedback delta;
+	TopoFeedback topo;
 	// planner state reused from one decode call to the next (batch.cpp: build_and_launch)
-	Plan plan;
-	std::vector<BlobScratch> plan_scratch;
 	std::vector<const uint8_t *> plan_clers, plan_logs;
 	// streams of a batch that carry the same probability table share one dictionary: exact match on the table's bytes (alphabets of up
 	// to 16 symbols; bigger ones hardly ever repeat and are quick to build), open addressing on a hash of them
 	struct DictKey { uint8_t n, bytes[32]; };
 	std::vector<DictKey> dict_keys;
 	std::vector<uint32_t> dict_slots, dict_used, dict_ids, dict_count;
-	// K-DELTA keeps 32-bit values in LDS: $CORTO_DELTA_WIDE=1, or learnt from a batch whose 16-bit relative values overflowed
-	bool delta_wide = false;
-	uint32_t delta_calm = 0, delta_patience = 256;
-	// the narrow layout is on trial again after a wide spell (an overflow now doubles the patience)
-	bool delta_just_narrowed = false;
-	// crthip_batch_decode_with_next: two batches are alive on the context - one in its mesh stage, the next one's entropy stage beside it - so what
-	// ONE decode call owns exists twice, by the batch object's parity (crthip_batch_set_parity): its arena image, descriptor / staging block, status
-	// block, scratch and plan, and the bookkeeping of its arena upload.  The members above are the ACTIVE set, `spare` is the other one, and
-	// ctx_select() swaps them: every entry point that works on a batch's blocks selects that batch's parity first.  A context whose batches all
-	// have parity 0 (every lone context, the facade) never swaps.  Shared by both: the stream, in_flight / ev_done (one call in flight), and what
-	// harvest() learns - a batch planned before its predecessor's flags were read learns from them one batch late.
+	// What ONE decode call owns, by the batch object's parity (crthip_batch_set_parity).  crthip_batch_decode_with_next keeps two batches alive on
+	// the context - one in its mesh stage, the next one's entropy stage beside it - so there are two sets, and every use names the batch whose set
+	// it means: ctx_set(ctx, b).  A Planner binds its batch's set for life.  A context whose batches all have parity 0 (every lone context, the
+	// facade) never touches set[1], whose buffers are allocated on first use.  Shared by both: the stream, in_flight / ev_done (one call in
+	// flight), and what harvest() learns - a batch planned before its predecessor's flags were read learns from them one batch late.
 	struct Half {
-		DeviceBuf scratch; PinnedBuf staging, arena_pin, status_host;
-		uint32_t upload_seq = 0, done_covers_seq = 0; bool arena_upload_pending = false;
+		DeviceBuf scratch;        // symbols, tables, fronts, predictions, job arrays ...
+		PinnedBuf staging;        // host image of the job arrays
+		PinnedBuf arena_pin;      // host image of a batch's blobs on their way to the device (batch_fill: one H2D copy, not waited for)
+		PinnedBuf status_host;    // StatusWords, and the quant records behind them
+		// arena_pin uploads enqueued so far / how many of them sit IN FRONT of ev_done (harvest may only call those complete)
+		uint32_t upload_seq = 0, done_covers_seq = 0;
+		// a batch's blobs are (perhaps still) on their way from arena_pin: cleared by whoever synchronises the stream
+		bool arena_upload_pending = false;
 		Plan plan; std::vector<BlobScratch> plan_scratch;
-	} spare;
-	uint8_t active = 0;
+		void release() { scratch.release(); staging.release(); arena_pin.release(); status_host.release(); }
+	} set[2];
 };
-inline void ctx_select(crthip_ctx *ctx, uint8_t parity) {
-	if(ctx->active == parity) return;
-	crthip_ctx::Half &h = ctx->spare;
-	std::swap(ctx->scratch, h.scratch); std::swap(ctx->staging, h.staging); std::swap(ctx->arena_pin, h.arena_pin); std::swap(ctx->status_host, h.status_host);
-	std::swap(ctx->upload_seq, h.upload_seq); std::swap(ctx->done_covers_seq, h.done_covers_seq); std::swap(ctx->arena_upload_pending, h.arena_upload_pending);
-	std::swap(ctx->plan, h.plan); std::swap(ctx->plan_scratch, h.plan_scratch);
-	ctx->active = parity;
-}
 
 // bytes per component of a generic attribute's caller buffer: upstream decodes in place as int32 whatever the format and DOUBLE widens
 // in place (include/corto/vertex_attribute.h:184-228), so every format's buffer is nvert*N*4 bytes but DOUBLE's
@@ -268,8 +251,9 @@ struct crthip_batch {
 	std::vector<crthip_quant_transform> quant_recs; std::vector<uint8_t> quant_bound;
 };
 void drop_staged(crthip_batch *b);      // (batch.cpp)
+inline crthip_ctx::Half &ctx_set(crthip_ctx *ctx, const crthip_batch *b) { return ctx->set[b->parity]; }   // the batch's set of per-call blocks
 
-// The per-blob status block: four int32 words a blob in the context's pinned host memory (status_host), written by the kernels, zeroed by
+// The per-blob status block: four int32 words a blob in the pinned host memory of the batch's set (status_host), written by the kernels, zeroed by
 // Planner::upload, read by harvest
 struct StatusWords {
 	size_t n;                                                      // blobs
@@ -285,18 +269,8 @@ int harvest(crthip_ctx *ctx);     // wait for the batch in flight on the context
 int ctx_stream2(crthip_ctx *ctx, hipStream_t *out);   // the context's second stream, made on first use (batch.cpp)
 
 // ------------------------------------------------------------------------------------------------
-// planner: everything below turns the walked layouts + bindings into job arrays inside one scratch block
-
+// planner: what turns the walked layouts + bindings into job arrays inside one scratch block
 // (Carver, the bump allocator over the scratch block: encoder_internal.h - the batch encoder carves its image with it too)
-
-
-static int32_t f2i_x86_host(float x) {
-	if(!(x > -2147483904.0f && x < 2147483648.0f)) return (int32_t)0x80000000;
-	return (int32_t)x;
-}
-
-
-
 
 // the two launch classes of K-DELTA (k_delta.hip): values + prediction graph fit LDS, one wave per attribute (k_delta_lds16) - as int16 relative to
 // vertex 0, or - `wide`: a context that met values beyond int16 - as int32; else tiles out of an LDS ring (k_delta_tiles: meshes beyond LDS,
@@ -351,7 +325,7 @@ struct Carry {
 // what Planner::launch enqueues: the descriptor copy and the zeroing | K-TAB, K-STREAM | k_fill (stage E) | everything else (stage M)
 enum : uint32_t { PH_UP = 1, PH_TUN = 2, PH_FILL = 4, PH_MESH = 8, PH_ENTROPY = PH_UP | PH_TUN | PH_FILL, PH_ALL = 15 };
 struct Planner {
-	crthip_batch *b; crthip_ctx *ctx; Plan &pl; std::vector<BlobScratch> &bs;
+	crthip_batch *b; crthip_ctx *ctx; crthip_ctx::Half &set; Plan &pl; std::vector<BlobScratch> &bs;   // set: the batch's (ctx_set); pl, bs: its plan and scratch offsets
 	// wide: K-DELTA with 32-bit values in LDS (this context met values beyond int16)
 	const uint32_t nblobs; const bool wide; const uint8_t *arena;
 	Carver cv;
@@ -363,8 +337,8 @@ struct Planner {
 	int32_t *hs_base = nullptr; StatusWords hs;                              // per-blob status words in pinned host memory
 	uint8_t *base = nullptr, *stage = nullptr;                               // the scratch block; the host image of the job arrays
 
-	Planner(crthip_batch *b_) : b(b_), ctx(b_->ctx), pl(b_->ctx->plan), bs(b_->ctx->plan_scratch), nblobs((uint32_t)b_->blobs.size()),
-		wide(b_->ctx->delta_wide), arena(b_->d_arena), hs{b_->blobs.size()} {}
+	Planner(crthip_batch *b_) : b(b_), ctx(b_->ctx), set(ctx_set(b_->ctx, b_)), pl(set.plan), bs(set.plan_scratch), nblobs((uint32_t)b_->blobs.size()),
+		wide(b_->ctx->delta.wide), arena(b_->d_arena), hs{b_->blobs.size()} {}
 	static uint8_t *SP(uint64_t off) { return (uint8_t *)(uintptr_t)(off | (1ull << 63)); }   // a scratch offset in a pointer field
 	template <class T> void resolve(T *&p) const {
 		const uintptr_t v = (uintptr_t)p;

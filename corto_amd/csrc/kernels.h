@@ -103,6 +103,8 @@ inline void topo_lds_geometry(uint32_t nface, uint32_t nclers, uint32_t ring_max
 	const uint32_t all = (nclers + 64 + 31) & ~31u;       // whole 16-byte vectors of nibbles (k_mesh.hip: TOPO_FILL_WINDOW)
 	symwin = all < TOPO_SYMWIN_MAX ? all : TOPO_SYMWIN_MAX;
 }
+constexpr uint32_t TOPO_SLOTS_MAX = 4096;       // ring and pool slots of the automaton's LDS form: the planner's and the feedback's `ring_max`
+inline uint32_t topo_slots(uint32_t nblobs) { return nblobs >= 32 ? 4u : 8u; }   // ... and their `slots`: a batch of many blobs keeps them small
 constexpr uint32_t TOPO_LDS_MAX = 156*1024;     // of the CU's 160 KiB
 // k_delta.hip: every K-DELTA job beyond the LDS records below - big meshes, attributes of more than four components - in tiles of DELTA_THREADS
 // vertices out of an LDS ring of recent values, one workgroup a job (round 6).  SLICES: the jobs of attributes of more than four components, a slice

@@ -2,6 +2,12 @@
 // resolved by upload(); every other pointer goes in as the real address (the Planner's comment, batch_internal.h).
 #include "batch_internal.h"
 
+// float -> int32 as x86's cvttss2si does it (out of range, NaN: INT_MIN): the unit of a normal attribute as upstream's host code computes it
+static int32_t f2i_x86_host(float x) {
+	if(!(x > -2147483904.0f && x < 2147483648.0f)) return (int32_t)0x80000000;
+	return (int32_t)x;
+}
+
 int Planner::jobs() {
 	// the status block is about to move: the batch in flight writes to it
 	// (a batch with a quantised binding keeps a crthip_quant_transform an attribute behind the status words)
@@ -11,9 +17,9 @@ int Planner::jobs() {
 		pl.quant_records = any ? nattr : 0u;
 	}
 	const size_t status_bytes = hs.records() + (size_t)pl.quant_records*sizeof(crthip_quant_transform) + 16;
-	if(status_bytes > ctx->status_host.cap && harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE);
-	if(ctx->status_host.reserve(status_bytes) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
-	hs_base = (int32_t *)ctx->status_host.p;
+	if(status_bytes > set.status_host.cap && harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE);
+	if(set.status_host.reserve(status_bytes) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
+	hs_base = (int32_t *)set.status_host.p;
 	QuantOutRecord *const rec_host = (QuantOutRecord *)((uint8_t *)hs_base + hs.records());
 
 	// the dictionary (TunTable slot) of a stream: a new one, or the one an earlier stream of this launch group with the same table got
@@ -110,10 +116,10 @@ int Planner::jobs() {
 			{
 				// every mesh takes the LDS path; a lone big mesh may use most of a CU's LDS, a batch keeps its blobs small
 				uint32_t ring, pool, symwin;
-				uint32_t scale = ctx->topo_scale, pool_q8 = ctx->topo_pool_q8, need;
+				uint32_t scale = ctx->topo.scale, pool_q8 = ctx->topo.pool_q8, need;
 				// as much of what the context has learnt as fits a CU
 				for(;;) {
-					topo_lds_geometry(nface, L.clers.size, 4096, scale, pool_q8, nblobs >= 32 ? 4u : 8u, ring, pool, symwin, ctx->topo_pool_cap);
+					topo_lds_geometry(nface, L.clers.size, TOPO_SLOTS_MAX, scale, pool_q8, topo_slots(nblobs), ring, pool, symwin, ctx->topo.pool_cap);
 					// every delayed edge is a pool record: same capacity
 					need = topo_lds_bytes(ring, pool, pool, symwin);
 #ifdef CORTO_TOPO_STAMPS

@@ -7,9 +7,9 @@ int Planner::upload() {
 	// ---- reserve device + pinned memory; one batch in flight per context ----
 	// one batch in flight per context: the previous one's status is kept in its object
 	if(harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE);
-	if(ctx->scratch.reserve(pl.total + 256) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
-	if(ctx->staging.reserve(pl.jobs_bytes + 256) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
-	base = (uint8_t *)ctx->scratch.p;
+	if(set.scratch.reserve(pl.total + 256) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
+	if(set.staging.reserve(pl.jobs_bytes + 256) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
+	base = (uint8_t *)set.scratch.p;
 	// every pointer field of every descriptor (SP offsets become base + offset; TopoJob.group_end: bytes into aux_u32)
 	for(auto &t : pl.tun.v) { resolve(t.src); resolve(t.dst); resolve(t.probs); }
 	for(auto &t : pl.tun_dict.v) { resolve(t.src); resolve(t.dst); resolve(t.probs); }
@@ -29,12 +29,12 @@ int Planner::upload() {
 	for(auto &q : pl.quant.v) { resolve(q.values); resolve(q.range); }
 
 	// host image -> device (one copy)
-	stage = (uint8_t *)ctx->staging.p;
+	stage = (uint8_t *)set.staging.p;
 	memset(stage + (pl.unpack_partial_off - pl.jobs_begin), 0, unpack_state_words*8);
 	// (after the harvest above: the previous batch's words have been read)
-	memset(ctx->status_host.p, 0, hs.records() + (size_t)pl.quant_records*sizeof(crthip_quant_transform));
+	memset(set.status_host.p, 0, hs.records() + (size_t)pl.quant_records*sizeof(crthip_quant_transform));
 	if(pl.quant_records) {                                               // a quantised attribute of a blob without vertices has no job: its record is all zero, written
-		crthip_quant_transform *rec = (crthip_quant_transform *)((uint8_t *)ctx->status_host.p + hs.records());
+		crthip_quant_transform *rec = (crthip_quant_transform *)((uint8_t *)set.status_host.p + hs.records());
 		for(const BlobPlan &P : b->blobs) {
 			for(size_t k = 0; k < P.bind.size(); k++) if(P.bind[k].buffer && P.bind[k].quantized && P.L.h.nvert == 0) rec[k].written = 1;
 			rec += P.bind.size();
@@ -308,10 +308,10 @@ int Planner::launch(uint32_t phases, const Carry *carry) {
 	return CRTHIP_OK;
 }
 
-// the event a call's sync / done wait for, behind everything the call enqueued (on the half of the batch whose stage M the call ran)
+// the event a call's sync / done wait for, behind everything the call enqueued (on the set of the batch whose stage M the call ran)
 int Planner::mark_done() {
 	HIP_TRY(hipEventRecord(ctx->ev_done, ctx->stream));
-	ctx->done_covers_seq = ctx->upload_seq;
+	set.done_covers_seq = set.upload_seq;
 	return CRTHIP_OK;
 }
 
@@ -324,7 +324,7 @@ void Planner::account() {
 	b->stats.descriptor_bytes = (uint32_t)pl.jobs_bytes;
 	b->stats.int16_streams = 0;
 	for(const UnpackJob &u : pl.unpack.v) b->stats.int16_streams += u.out_kind == UNPACK_OUT_I16;
-	b->stats.topology_scale = std::max(ctx->topo_scale, (ctx->topo_pool_q8 + 7)/8); b->stats.delta_wide = wide ? 1u : 0u;
+	b->stats.topology_scale = std::max(ctx->topo.scale, (ctx->topo.pool_q8 + 7)/8); b->stats.delta_wide = wide ? 1u : 0u;
 	uint64_t ob = 0;
 	for(auto &P : b->blobs) {
 		const BlobLayout &L = P.L;

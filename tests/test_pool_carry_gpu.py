@@ -281,3 +281,85 @@ def test_decode_with_next_argument_errors():
         a.close(); b.close()
     finally:
         c.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(120)
+def test_two_parities_keep_their_own_blocks():
+    """a context's two sets of per-call blocks, told apart by everything that differs between them: batch P0 (parity 0, three blobs) and P1
+    (parity 1, five blobs - so the status words' offsets differ - one of which fails alone with CRTHIP_E_FORMAT on a quantised position of
+    span 65536, which also puts quant records behind P1's status words), then P0 again with two other blobs.  P1 is synced after the
+    context has moved on.  Every sync returns its own batch's statuses, every output written is the oracle's, P1's transforms are those
+    of a lone decode, and the prediction triples are read from the set of the batch decoded last and refused for the others."""
+    import quantized_outputs as qo
+    from conftest import load_golden
+    FILL, BAD = 0xA5, 2
+    sphere = lambda seed: enc(synth.bumpy_sphere(24, 12, seed=seed))
+    p0 = [sphere(31), sphere(32), sphere(33)]
+    p1 = [sphere(41), sphere(42), qo.traced("edge_65536")[0], sphere(43), sphere(44)]
+    p0b = [ca.aligned_blob(load_golden("c4_unit")["crt"]), sphere(51)]
+    qo.assert_edge("edge_65536")
+    traces = {}
+
+    def trace(blob):
+        return traces.setdefault(blob.tobytes(), oc.decode(blob, trace=True))
+
+    def prediction(b, i, blob):
+        want = trace(blob)["_prediction"]
+        got = b.debug_read(i, "prediction", want.size * 4).view(np.uint32).reshape(-1, 3)
+        assert np.array_equal(got[1:], want[1:]), i
+
+    def refused(b):
+        with pytest.raises(ca.CortoError) as ei:
+            b.debug_read(0, "prediction", 12)
+        assert ei.value.code == qo.E_ARGUMENT
+
+    def plain(b, blobs, tag):
+        for i, blob in enumerate(blobs):
+            assert_blob(b.host_outputs(i), ref_of(blob), (tag, i))
+
+    c = ca.Context(0)
+    A, B = ca.Batch(c, []), ca.Batch(c, [])
+    try:
+        c.set_single_stream(True)
+        B.set_parity(1)
+        A.reset(p0); A.allocate_outputs(fill=FILL)
+        B.reset(p1); B.allocate_outputs(fill=FILL, quantized=("position",))
+        A.decode_entropy()
+        A.decode_with_next(B)
+        prediction(A, 2, p0[2]); refused(B)
+        assert list(A.sync(raise_on_error=False)) == [0, 0, 0]
+        plain(A, p0, "P0")
+        A.reset(p0b); A.allocate_outputs(fill=FILL)
+        B.decode_with_next(A)
+        prediction(B, 4, p1[4]); refused(A)                  # (parity 1's scratch block)
+        A.decode_with_next(None)
+        prediction(A, 1, p0b[1]); refused(B)
+        st1 = B.sync(raise_on_error=False)                   # harvested when the context moved on to P0'
+        assert list(st1) == [0, 0, qo.E_FORMAT, 0, 0], st1
+        assert list(A.sync(raise_on_error=False)) == [0, 0]
+        plain(A, p0b, "P0'")
+        recs = {}
+        for i, blob in enumerate(p1):
+            got, ref, e = B.host_outputs(i), ref_of(blob), qo.Expected(blob, trace(blob), "position")
+            t = B.quant_transform(i, "position")
+            e.check_record(t, ("P1", i))
+            recs[i] = bytes(t)
+            assert e.written == (i != BAD)
+            if e.written:
+                assert got["position"].dtype == np.uint16 and got["position"].tobytes() == e.out.tobytes(), i
+            else:
+                assert (got["position"].view(np.uint8) == FILL).all()      # the refused attribute: nothing written
+            for k in ("normal", "color", "uv", "grid", "index"):
+                if k in ref:
+                    assert got[k].tobytes() == ref[k].tobytes(), ("P1", i, k)
+        lone = ca.Batch(c, p1)
+        lone.allocate_outputs(fill=FILL, quantized=("position",))
+        lone.decode()
+        assert list(lone.sync(raise_on_error=False)) == list(st1)
+        for i in range(len(p1)):
+            if i != BAD:
+                assert bytes(lone.quant_transform(i, "position")) == recs[i], i
+        lone.close()
+    finally:
+        A.close(); B.close(); c.close()
