@@ -243,6 +243,9 @@ def lib():
         L.crthip_batch_bind.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
         L.crthip_batch_bind_all.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.crthip_batch_bind_computed_normals.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.crthip_batch_bind_computed_tangents.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.crthip_tangent_model.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                           C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32]
         L.crthip_batch_quant_transform.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QuantTransform)]
         L.crthip_batch_bind_quant_transforms.argtypes = [C.c_void_p, C.c_void_p]
         L.crthip_quant_out_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(QuantTransform), C.c_int, C.c_uint32]
@@ -898,6 +901,31 @@ def quant_out_model(values: np.ndarray, stride: int = 0, which: int = 0, seed: i
     return out, t
 
 
+def tangent_model(position: np.ndarray, uv: np.ndarray, index: np.ndarray, normal: np.ndarray, fmt=FMT_FLOAT, stride: int = 0, which: int = 0, seed: int = 0,
+                  out: Optional[np.ndarray] = None, offset: int = 0):
+    """crthip_tangent_model: the value of crthip_batch_bind_computed_tangents on the host in the kernels' partition (which 0: one workgroup;
+    1: the blocks of the batch-wide kernels; blocks and lanes shuffled by seed).  position (nvert, 3) and uv (nvert, 2): the delta-decoded
+    integers; index (nface, 3) uint32 or uint16; normal (nvert, 3) float32 or int16.  out: a uint8 array the records go into from byte
+    `offset` on (made here when None: exactly the bytes the last vertex ends at).  Returns the tangents as (nvert, 4) float32 / int16."""
+    p = np.ascontiguousarray(position, dtype=np.int32).reshape(-1, 3)
+    t = np.ascontiguousarray(uv, dtype=np.int32).reshape(-1, 2)
+    idx = np.ascontiguousarray(index)
+    if idx.dtype != np.uint16:
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    idx = idx.reshape(-1, 3)
+    n = np.ascontiguousarray(normal)
+    assert n.dtype in (np.float32, np.int16) and n.shape == (len(p), 3) and len(t) == len(p), (n.dtype, n.shape, p.shape, t.shape)
+    nvert, el = len(p), (2 if fmt == FMT_INT16 else 4)
+    st = stride or 4 * el
+    if out is None:
+        out = np.zeros(offset + ((nvert - 1) * st + 4 * el if nvert else 0), np.uint8)
+    assert out.dtype == np.uint8 and out.flags.c_contiguous and len(out) >= offset + ((nvert - 1) * st + 4 * el if nvert else 0)
+    _check(lib().crthip_tangent_model(_np_ptr(p), _np_ptr(t), _np_ptr(idx), int(idx.dtype == np.uint16), nvert, len(idx), _np_ptr(n),
+                                      FMT_INT16 if n.dtype == np.int16 else FMT_FLOAT, 0, C.c_void_p(out.ctypes.data + offset), fmt, stride, which, seed))
+    rec = np.lib.stride_tricks.as_strided(out[offset:], shape=(nvert, 4 * el), strides=(st, 1)) if nvert else np.zeros((0, 4 * el), np.uint8)
+    return np.ascontiguousarray(rec).view(np.int16 if fmt == FMT_INT16 else np.float32).reshape(nvert, 4)
+
+
 def encode_splice_plan_model(meshes, kw=None, chunk_items=0):
     """crthip_encode_splice_plan_model: the device splice's plan of a batch on the host, in chunks of chunk_items meshes (0: one chunk) that
     continue the arena as the chunks of a batch beyond one device image do.  Returns (offsets, lens, stats dict, pieces): pieces an
@@ -1083,6 +1111,7 @@ class Batch:
         self.outputs: List[Dict[str, object]] = []
         self._keep = None
         self._computed = []                          # (blob, pointer, format, stride): what rebind() applies again behind crthip_batch_bind_all
+        self._tangents = []                          # ... and behind those, through crthip_batch_bind_computed_tangents
         self._interleaved = None
 
     def __len__(self):
@@ -1126,13 +1155,17 @@ class Batch:
 
     # -- outputs -----------------------------------------------------------------------------------
     def allocate_outputs(self, normal_format=FMT_FLOAT, color_components: Optional[int] = None, index16=False,
-                         only: Optional[set] = None, fill: Optional[int] = None, computed_normals=False, quantized=()):
+                         only: Optional[set] = None, fill: Optional[int] = None, computed_normals=False, quantized=(),
+                         computed_tangents=False, tangent_format=FMT_FLOAT):
         """Allocate every output of every blob inside ONE device buffer (torch.uint8) and bind them.
         Returns a list (per blob) of dicts name -> torch tensor view.
         computed_normals: every mesh blob WITHOUT a normal attribute gets a "normal" tensor of normal_format all the same, bound
         through crthip_batch_bind_computed_normals - upstream's estimate at every vertex (include/corto_hip.h).
         quantized: names of generic attributes to bind as uint16 grid values (CRTHIP_BIND_QUANTIZED) in place of floats; their
-        transforms come from quant_transform(i, name) after sync()."""
+        transforms come from quant_transform(i, name) after sync().
+        computed_tangents: every mesh blob with a bound two-component generic "uv", a bound "position", a normal source (stored or computed
+        here) and no stored attribute named "tangent" gets a "tangent" tensor (nvert, 4) of tangent_format, bound through
+        crthip_batch_bind_computed_tangents (include/corto_hip.h: xyz and the handedness w)."""
         import torch
         dev = torch.device("cuda", self.ctx.device)
         plan = []   # (blob, name, offset, nbytes, dtype, shape, binding_slot)
@@ -1165,6 +1198,13 @@ class Batch:
                     and not any(a["codec"] == CODEC_NORMAL or a["name"] == "normal" for a in info.attrs())):
                 dt = "f32" if normal_format == FMT_FLOAT else "i16"
                 plan.append((i, "normal", take(nv * 3 * np.dtype(_DT[dt]).itemsize), dt, (nv, 3), -2, normal_format, 0))
+            if computed_tangents and nf:
+                names = {p_[1] for p_ in plan if p_[0] == i}          # what this blob binds
+                attrs = info.attrs()
+                uv_ok = any(a["name"] == "uv" and a["codec"] == CODEC_GENERIC and a["components"] == 2 for a in attrs)
+                if uv_ok and {"uv", "position", "normal"} <= names and not any(a["name"] == "tangent" for a in attrs):
+                    dt = "f32" if tangent_format == FMT_FLOAT else "i16"
+                    plan.append((i, "tangent", take(nv * 4 * np.dtype(_DT[dt]).itemsize), dt, (nv, 4), -3, tangent_format, 0))
             if nf and (only is None or "index" in only):
                 dt = "u16" if index16 else "u32"
                 plan.append((i, "index", take(nf * 3 * np.dtype(_DT[dt]).itemsize), dt, (nf, 3), -1, FMT_UINT16 if index16 else FMT_UINT32, 0))
@@ -1178,7 +1218,7 @@ class Batch:
         index_ptrs = (C.c_void_p * max(len(self), 1))()
         index_fmt = np.full(max(len(self), 1), FMT_UINT32, dtype=np.uint32)
         outs = [dict() for _ in self.infos]
-        computed = []
+        computed, tangents = [], []
         tdt = {"f32": torch.float32, "i16": torch.int16, "u8": torch.uint8, "u32": torch.int32, "u16": torch.int16}
         for (i, name, o, dt, shape, slot, fmt, oc) in plan:
             nbytes = int(np.prod(shape)) * np.dtype(_DT[dt]).itemsize
@@ -1189,10 +1229,13 @@ class Batch:
                 bd.buffer = base + o; bd.format = fmt; bd.out_components = oc; bd.reserved = BIND_QUANTIZED if (i, slot) in as_u16 else 0
             elif slot == -2:
                 computed.append((i, base + o, fmt, 0))
+            elif slot == -3:
+                tangents.append((i, base + o, fmt, 0))
             else:
                 index_ptrs[i] = base + o; index_fmt[i] = fmt
         self._keep = (buf, binds, index_ptrs, index_fmt)
         self._computed = computed
+        self._tangents = tangents
         self._interleaved = None
         self.outputs = outs
         self.rebind()
@@ -1245,6 +1288,7 @@ class Batch:
                 index_ptrs[i] = base + ib; index_fmt[i] = FMT_UINT16 if i16 else FMT_UINT32
         self._keep = (buf, binds, index_ptrs, index_fmt)
         self._computed = []
+        self._tangents = []
         self._interleaved = metas
         self.outputs = [dict() for _ in self.infos]
         self.rebind()
@@ -1288,6 +1332,8 @@ class Batch:
         _check(lib().crthip_batch_bind_all(self.handle, binds, index_ptrs, _np_ptr(index_fmt)))
         for (i, ptr, fmt, stride) in self._computed:          # (a bind drops a blob's computed-normals binding)
             _check(lib().crthip_batch_bind_computed_normals(self.handle, i, C.c_void_p(ptr), fmt, stride))
+        for (i, ptr, fmt, stride) in self._tangents:          # (... and its tangents, whose normal source is bound by now)
+            _check(lib().crthip_batch_bind_computed_tangents(self.handle, i, C.c_void_p(ptr), fmt, stride))
 
     def bind(self, i: int, bindings: Sequence[AttrBinding], index_ptr: Optional[int] = None, index_format=FMT_UINT32):
         arr = (AttrBinding * max(len(bindings), 1))(*bindings)
@@ -1298,6 +1344,11 @@ class Batch:
         to the device pointer `ptr` (nvert*3 f32 or i16; stride as for a stored normal).  After bind() / rebind() of that blob, which drop
         it; ptr None or 0 removes it."""
         _check(lib().crthip_batch_bind_computed_normals(self.handle, i, C.c_void_p(ptr) if ptr else None, fmt, stride))
+
+    def bind_computed_tangents(self, i: int, ptr: Optional[int], fmt=FMT_FLOAT, stride: int = 0):
+        """crthip_batch_bind_computed_tangents: blob i's tangents (xyz and the handedness w: nvert*4 f32 or i16; stride 0 = packed) go to the
+        device pointer `ptr`.  After bind() / rebind() and bind_computed_normals() of that blob, which drop it; ptr None or 0 removes it."""
+        _check(lib().crthip_batch_bind_computed_tangents(self.handle, i, C.c_void_p(ptr) if ptr else None, fmt, stride))
 
     def quant_transform(self, i: int, name) -> QuantTransform:
         """crthip_batch_quant_transform: the record of blob i's attribute `name` (or index), bound quantised; after sync()"""

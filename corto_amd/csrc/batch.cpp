@@ -247,7 +247,7 @@ static crthip_ctx::Half &begin_fill(crthip_ctx *ctx, crthip_batch *b) {
 static uint64_t adopt_blob(BlobPlan &P, uint64_t arena_off, uint32_t len, crthip_batch_stats &stats) {
 	P.arena_off = arena_off; P.len = len;
 	P.bind.assign(P.L.h.attrs.size(), Binding{});
-	P.index = nullptr; P.index_u16 = 0; P.host_status = 0; P.computed = Binding{};
+	P.index = nullptr; P.index_u16 = 0; P.host_status = 0; P.computed = Binding{}; P.tangent = Binding{};
 	P.dbg_clers = P.dbg_pred = ~0ull; P.dbg_nclers = 0; P.clers_in_arena = false;
 	stats.total_nvert += P.L.h.nvert; stats.total_nface += P.L.h.nface;
 	if(P.L.h.nface) { stats.clers_symbols += P.L.clers.size; stats.split_bytes += (uint64_t)P.L.split.nwords*4; }
@@ -555,6 +555,7 @@ extern "C" int crthip_batch_bind(crthip_batch *b, uint32_t i, const crthip_attr_
 	}
 	P.index = index; P.index_u16 = index && index_format == CRTHIP_FMT_UINT16;
 	P.computed = Binding{};                                                 // (crthip_batch_bind_computed_normals comes after the bind)
+	P.tangent = Binding{};                                                  // (... and crthip_batch_bind_computed_tangents after both)
 	b->dirty = true;
 	return CRTHIP_OK;
 }
@@ -564,6 +565,7 @@ extern "C" int crthip_batch_bind_computed_normals(crthip_batch *b, uint32_t i, v
 	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_computed_normals: no such blob");
 	BlobPlan &P = b->blobs[i];
 	const std::string who = " (blob " + std::to_string(i) + ")";
+	P.tangent = Binding{};                                                  // the tangents' normal source may change here: they are bound behind this call
 	if(!buffer) { P.computed = Binding{}; b->dirty = true; return CRTHIP_OK; }
 	if(P.L.h.nface == 0) return fail(CRTHIP_E_ARGUMENT, "computed normals need faces: a point cloud has none" + who);
 	int pos_k = -1;
@@ -583,6 +585,37 @@ extern "C" int crthip_batch_bind_computed_normals(crthip_batch *b, uint32_t i, v
 		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "computed normals need a bound three-component \"position\" (bind the blob first)" + who);
 	P.computed.buffer = buffer; P.computed.format = format;
 	P.computed.stride = stride == (format == CRTHIP_FMT_INT16 ? 6u : 12u) ? 0u : stride;
+	b->dirty = true;
+	return CRTHIP_OK;
+}
+
+// Tangents from the blob's integer positions and uvs, its index and its final normals (corto_hip.h has the value): every check is made here
+extern "C" int crthip_batch_bind_computed_tangents(crthip_batch *b, uint32_t i, void *buffer, uint32_t format, uint32_t stride) {
+	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_computed_tangents: no such blob");
+	BlobPlan &P = b->blobs[i];
+	const std::string who = " (blob " + std::to_string(i) + ")";
+	if(!buffer) { P.tangent = Binding{}; b->dirty = true; return CRTHIP_OK; }
+	if(P.L.h.nface == 0) return fail(CRTHIP_E_ARGUMENT, "computed tangents need faces: a point cloud has none" + who);
+	if(format != CRTHIP_FMT_FLOAT && format != CRTHIP_FMT_INT16) return fail(CRTHIP_E_FORMAT, "computed tangents are FLOAT or INT16" + who);
+	const uint32_t el = format == CRTHIP_FMT_INT16 ? 2u : 4u;
+	if(((uintptr_t)buffer) % el || (stride && (stride < 4*el || stride % el)))
+		return fail(CRTHIP_E_ARGUMENT, "computed tangents: the buffer is not aligned to its element, or the stride is below four elements or no multiple of one" + who);
+	int pos_k = -1, uv_k = -1, nrm_k = -1;
+	for(size_t k = 0; k < P.bind.size(); k++) {
+		const AttrHeader &a = P.L.h.attrs[k];
+		if(a.name == "position") pos_k = (int)k;
+		if(a.name == "uv") uv_k = (int)k;
+		if(a.name == "normal" && a.codec == CRTHIP_CODEC_NORMAL && P.bind[k].buffer) nrm_k = (int)k;
+	}
+	// (what computed normals ask of the position)
+	if(pos_k < 0 || P.L.h.attrs[pos_k].codec != CRTHIP_CODEC_GENERIC || P.L.h.attrs[pos_k].N != 3 || !P.bind[pos_k].buffer || P.bind[pos_k].stream_values)
+		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "computed tangents need a bound three-component \"position\" (bind the blob first)" + who);
+	if(uv_k < 0 || P.L.h.attrs[uv_k].codec != CRTHIP_CODEC_GENERIC || P.L.h.attrs[uv_k].N != 2 || !P.bind[uv_k].buffer || P.bind[uv_k].stream_values)
+		return fail(CRTHIP_E_ARGUMENT, "computed tangents need a bound two-component generic \"uv\" (bind the blob first)" + who);
+	if(nrm_k < 0 && !computes_normals(P))
+		return fail(CRTHIP_E_ARGUMENT, "computed tangents need a normal source: a stored \"normal\" bound as FLOAT or INT16, or crthip_batch_bind_computed_normals before this call" + who);
+	P.tangent.buffer = buffer; P.tangent.format = format; P.tangent.out_components = 4;
+	P.tangent.stride = stride == 4*el ? 0u : stride;
 	b->dirty = true;
 	return CRTHIP_OK;
 }

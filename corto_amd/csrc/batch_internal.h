@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "plan_feedback.h"
 #include "quant_out.h"
+#include "tangent.h"
 
 using namespace corto_hip;
 
@@ -87,10 +88,11 @@ struct BlobScratch {
 	uint64_t clers = ~0ull, pred = ~0ull, front_a = ~0ull, front_b = ~0ull, order = ~0ull, delayed = ~0ull, faces = ~0ull;
 	uint64_t progress = ~0ull;                              // the automaton's progress word (zeroed): blobs with an attribute too big for K-DELTA's LDS records
 	uint32_t front_cap = 0, aux_groups = 0;
+	uint64_t tan_acc = ~0ull;                               // computed tangents (BlobPlan::tangent) of a blob beyond TANGENT_BLOB_MAX: 6 x int64 a vertex, inside the zeroed region
 	uint64_t cn_facen = ~0ull;                              // computed normals (BlobPlan::computed) by the fused kernel without its face normals in LDS: AttrScratch::facen's counterpart
 	std::vector<AttrScratch> attr;
 	size_t nattr = 0;                                       // attr[0..nattr) are this decode's (the vector only grows)
-	void reset() { clers = pred = front_a = front_b = order = delayed = faces = progress = cn_facen = ~0ull; front_cap = 0; aux_groups = 0; nattr = 0; }
+	void reset() { clers = pred = front_a = front_b = order = delayed = faces = progress = cn_facen = tan_acc = ~0ull; front_cap = 0; aux_groups = 0; nattr = 0; }
 	void set_attrs(size_t n) { if(attr.size() < n) attr.resize(n); for(size_t k = nattr; k < n; k++) attr[k].reset();
 		if(n > nattr) nattr = n; }
 };
@@ -117,6 +119,8 @@ struct Plan {
 	HostArr<DequantJob> dequant; HostArr<uint32_t> dequant_block_job;
 	// CRTHIP_BIND_QUANTIZED: jobs of up to QOUT_BLOB_MAX vertices by id (k_quant_out_blob), the others by block (k_quant_range, k_quant_store)
 	HostArr<QuantOutJob> quant; HostArr<uint32_t> quant_blob_ids, quant_block_job;
+	// crthip_batch_bind_computed_tangents: blobs of up to TANGENT_BLOB_MAX vertices by id (k_tangent_blob), the others by block (k_tangent_faces, k_tangent_vertex)
+	HostArr<TangentJob> tangent; HostArr<uint32_t> tangent_blob_ids, tan_fblock_job, tan_vblock_job; uint32_t tangent_lds = 0;
 	uint32_t quant_records = 0;                             // records behind the status words: sum(nattr) of a batch with a quantised binding, else 0
 	// scratch regions (offsets)
 	uint64_t zero_begin = 0, zero_end = 0;
@@ -135,11 +139,12 @@ struct Plan {
 		f(topo_glob_ids); f(unpack); f(unpack_chunk_job); f(unpack_wave_ids);
 		f(delta); f(delta_groups); f(cloud); f(cloud_chunk_job); f(normal); f(nv_block_job); f(nv_block_first); f(nf_block_job); f(nf_block_first);
 		f(normal_fused_ids); f(normal_computed_ids); f(dequant); f(dequant_block_job); f(quant); f(quant_blob_ids); f(quant_block_job);
+		f(tangent); f(tangent_blob_ids); f(tan_fblock_job); f(tan_vblock_job);
 	}
 	void reset() {                                          // keep every vector's capacity
 		each_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
 		clers_groups = 0; topo_need.clear(); quant_records = 0;
-		topo_lds = topo_big_lds = normal_fused_lds = normal_computed_lds = 0;
+		topo_lds = topo_big_lds = normal_fused_lds = normal_computed_lds = tangent_lds = 0;
 		zero_begin = zero_end = tables_off = tun_partial_off = unpack_partial_off = cloud_partial_off = 0;
 		facen_off = cnt_off = cursor_off = bnd_off = start_off = flag_off = slot_off = adj_off = nscan_partial_off = 0;
 		jobs_begin = jobs_bytes = 0; est_nvert = est_nface = 0; delta16_lds = 0;
@@ -222,6 +227,7 @@ struct BlobPlan {
 	std::vector<Binding> bind;
 	void *index = nullptr; uint32_t index_u16 = 0;
 	Binding computed;          // crthip_batch_bind_computed_normals: where the normals of a blob that stores (or binds) none go; dropped by every bind / reset
+	Binding tangent;           // crthip_batch_bind_computed_tangents: where the blob's tangents go (out_components 4); dropped by every bind, computed-normals call and reset
 	int32_t host_status = 0;   // set by the planner (e.g. unsupported format), overrides device status
 	// debug handles (scratch offsets valid after decode)
 	uint64_t dbg_clers = ~0ull, dbg_pred = ~0ull; uint32_t dbg_nclers = 0;
@@ -289,6 +295,13 @@ static inline bool computes_normals(const BlobPlan &P) {
 }
 static bool normal_fused(uint32_t nvert, uint32_t nface) { return nvert <= 32767 && (uint64_t)3*nface <= 65535 && normal_blob_lds(nvert,
 	nface) <= NORMAL_LDS_MAX; }
+
+// computed tangents (crthip_batch_bind_computed_tangents): blobs of up to TANGENT_BLOB_MAX vertices take k_tangent_blob - one workgroup and 24 bytes of
+// LDS a vertex, 54 KB at the limit, which holds a 2 112-vertex C4 blob and is what a lane of TAN_BLOB_SLOTS vertices in registers covers - the
+// others k_tangent_faces / k_tangent_vertex.  The bind call made sure of a mesh, a position, a uv and a normal source
+constexpr uint32_t TANGENT_BLOB_MAX = TAN_BLOB_SLOTS*TAN_THREADS;          // 2 304
+static inline bool computes_tangents(const BlobPlan &P) { return P.tangent.buffer && P.L.h.nface > 0; }
+static inline bool tangent_in_blob(uint32_t nvert) { return nvert <= TANGENT_BLOB_MAX; }
 
 struct Launch {
 	crthip_ctx *ctx;

@@ -185,9 +185,23 @@ struct QuantOutJob {
 	uint32_t pad;
 };
 
+// a blob bound with crthip_batch_bind_computed_tangents (k_tangent.hip, tangent.h): the integer positions and uvs, the index and the blob's final
+// normals -> a tangent and its handedness a vertex
+struct TangentJob {
+	const int32_t *position, *uv;  // delta-decoded integers, packed: the caller's packed buffer before k_dequant, or scratch
+	const void *faces;             // u32 or, with faces_u16, u16 triples
+	const void *normal;            // the normal's bound buffer (stored or computed)
+	void *out;                     // 4 f32 or 4 i16 a vertex
+	uint64_t *acc;                 // tangent_faces / tangent_vertex: 6 x int64 a vertex of zeroed scratch (T | B), else null
+	uint32_t nvert, nface;
+	uint32_t normal_stride, out_stride;   // bytes from one vertex to the next (never 0 here)
+	uint32_t fblock0, vblock0;     // first block of this job in the face / vertex block->job maps (jobs beyond TANGENT_BLOB_MAX)
+	uint8_t faces_u16, normal_i16, out_i16, pad[5];
+};
+
 // the layout the kernels read, pinned (TopoJob's size is performance-critical: TOPO_OPT_PROGRESS above)
 static_assert(sizeof(TunStream) == 64 && sizeof(FillJob) == 16 && sizeof(TopoJob) == 136 && sizeof(UnpackJob) == 56 && sizeof(DeltaJob) == 96 &&
-              sizeof(CloudJob) == 24 && sizeof(NormalJob) == 104 && sizeof(DequantJob) == 64 && sizeof(QuantOutJob) == 72, "decode job layout");
+              sizeof(CloudJob) == 24 && sizeof(NormalJob) == 104 && sizeof(DequantJob) == 64 && sizeof(QuantOutJob) == 72 && sizeof(TangentJob) == 80, "decode job layout");
 static_assert(offsetof(TopoJob, opts) == 116 && offsetof(UnpackJob, out_kind) == 51 && offsetof(NormalJob, faces_u16) == 58, "decode job layout");
 static_assert(offsetof(DeltaJob, in_i16) == 34 && offsetof(DeltaJob, wide) == 35 && offsetof(DeltaJob, rounds) == 88 &&
               offsetof(DeltaJob, status_back) == 92, "decode job layout");

@@ -50,6 +50,14 @@ __global__ void k_quant_out_blob(const QuantOutJob *jobs, const uint32_t *job_id
 __global__ void k_quant_range(const QuantOutJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 __global__ void k_quant_store(const QuantOutJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 
+// k_tangent.hip (crthip_batch_bind_computed_tangents; tangent.h has the arithmetic): blobs of up to TANGENT_BLOB_MAX vertices (batch_internal.h) by one
+// workgroup each, from an id list, with one 3 x int64 accumulator a vertex in `lds_bytes` of dynamic LDS (tangent_blob_lds); bigger ones in blocks of
+// TAN_BLOCK faces, then of TAN_BLOCK vertices, from block -> job maps, the sums in the job's zeroed scratch words
+__global__ void k_tangent_blob(const TangentJob *jobs, const uint32_t *job_ids, uint32_t njobs);
+__global__ void k_tangent_faces(const TangentJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_tangent_vertex(const TangentJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__host__ __device__ inline uint32_t tangent_blob_lds(uint32_t nvert) { return (nvert*24u + 15u) & ~15u; }
+
 // k_mesh.hip
 __global__ void k_topology(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);
 __global__ void k_topology_lds(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);

@@ -34,6 +34,10 @@ int Planner::carve() {
 	if(est_v) {
 		pl.cnt_off = cv.take(est_v*4 + 16); pl.cursor_off = cv.take(est_v*4 + 16); pl.bnd_off = cv.take(est_v*4 + 16);
 	}
+	for(uint32_t i = 0; i < nblobs; i++) {                           // ... and the integer sums of computed tangents beyond TANGENT_BLOB_MAX (k_tangent_faces)
+		const BlobPlan &P = b->blobs[i];
+		if(computes_tangents(P) && !tangent_in_blob(P.L.h.nvert)) bs[i].tan_acc = cv.take((uint64_t)P.L.h.nvert*TAN_ACC_WORDS*8, 16);
+	}
 	pl.zero_end = cv.take(0);
 	for(uint32_t i = 0; i < nblobs; i++) {                           // k_delta_tiles: one progress word a blob, kept by the automaton
 		const BlobPlan &P = b->blobs[i];

@@ -138,8 +138,11 @@ int Planner::jobs() {
 			pl.topo.v.push_back(t);
 		}
 		// position attribute (needed by ESTIMATED/BORDER normals)
-		int pos_k = -1;
-		for(size_t k = 0; k < L.attrs.size(); k++) if(L.h.attrs[k].name == "position") pos_k = (int)k;
+		int pos_k = -1, uv_k = -1;
+		for(size_t k = 0; k < L.attrs.size(); k++) { if(L.h.attrs[k].name == "position") pos_k = (int)k; if(L.h.attrs[k].name == "uv") uv_k = (int)k; }
+		// computed tangents read the integer positions AND the integer uvs, behind every normal kernel: neither K-DELTA nor the fused normal
+		// kernel may turn them into floats on the way - both fall to k_dequant, which runs behind the tangent kernels
+		const bool tangents = computes_tangents(P);
 		// who turns the integer positions into floats: estimated normals read them as integers after K-DELTA, so the fused normal
 		// kernel does it as their last reader (pos_by_normal), the separate normal kernels leave it to k_dequant behind them, and
 		// without such normals K-DELTA does it on the way out of LDS like for every other attribute
@@ -150,8 +153,8 @@ int Planner::jobs() {
 				if(mesh && L.h.attrs[k].codec == CRTHIP_CODEC_NORMAL && P.bind[k].buffer && (L.attrs[k].normal_prediction == 1 ||
 					L.attrs[k].normal_prediction == 2)) readers++;
 			if(computes_normals(P)) readers++;                        // computed normals read the integer positions as a stored estimate does
-			pos_ints_needed = readers > 0;
-			pos_by_normal = readers == 1 && normal_fused(nvert, nface) && pos_k >= 0 && P.bind[pos_k].format == CRTHIP_FMT_FLOAT;
+			pos_ints_needed = readers > 0 || tangents;
+			pos_by_normal = !tangents && readers == 1 && normal_fused(nvert, nface) && pos_k >= 0 && P.bind[pos_k].format == CRTHIP_FMT_FLOAT;
 		}
 
 		for(size_t k = 0; k < L.attrs.size(); k++) {
@@ -243,7 +246,7 @@ int Planner::jobs() {
 							d.deq = 2; d.out = bd.buffer; d.out_components = bd.out_components; d.out_stride = bd.stride;
 							for(int c = 0; c < 4; c++) d.qc[c] = as.qc[c];
 							dequantised = true;
-						} else if(!bd.stride && bd.format == CRTHIP_FMT_FLOAT && !((int)k == pos_k && pos_ints_needed)) { d.deq = 1; d.q =
+						} else if(!bd.stride && bd.format == CRTHIP_FMT_FLOAT && !((int)k == pos_k && pos_ints_needed) && !((int)k == uv_k && tangents)) { d.deq = 1; d.q =
 							a.q; dequantised = true; }
 					}
 					for(uint32_t f = 0; f < N; f += 4) { d.first = f; pl.delta.v.push_back(d); }   // more than four components: k_delta_tiles jobs of four
@@ -353,6 +356,35 @@ int Planner::jobs() {
 				pl.any_est_normal = true;
 			}
 			pl.normal.v.push_back(n);
+		}
+		// tangents: crthip_batch_bind_computed_tangents.  The integers where K-DELTA left them (the caller's packed buffer, or scratch), the index, the
+		// normals where their binding puts them.  (The bind call checked all of it; a blob that fails it here gets no job)
+		if(tangents) {
+			const Binding &bd = P.tangent;
+			auto generic_ok = [&](int k, uint32_t N) { return k >= 0 && L.h.attrs[k].codec == CRTHIP_CODEC_GENERIC && L.h.attrs[k].N == N && P.bind[k].buffer && !P.bind[k].stream_values; };
+			const Binding *nb = computes_normals(P) ? &P.computed : nullptr;
+			for(size_t k = 0; k < L.attrs.size() && !nb; k++)
+				if(L.h.attrs[k].name == "normal" && L.h.attrs[k].codec == CRTHIP_CODEC_NORMAL && P.bind[k].buffer) nb = &P.bind[k];
+			if(!generic_ok(pos_k, 3)) { P.host_status = CRTHIP_E_NORMAL_NEEDS_POSITION; continue; }
+			if(!generic_ok(uv_k, 2) || !nb) { P.host_status = CRTHIP_E_ARGUMENT; continue; }
+			auto ints_of = [&](int k) { return generic_in_scratch(P.bind[k]) ? (const int32_t *)SP(S.attr[k].vals) : (const int32_t *)P.bind[k].buffer; };
+			TangentJob t{};
+			t.position = ints_of(pos_k); t.uv = ints_of(uv_k);
+			t.faces = P.index ? P.index : (void *)SP(S.faces); t.faces_u16 = P.index ? (uint8_t)P.index_u16 : 0;
+			t.normal = nb->buffer; t.normal_i16 = nb->format == CRTHIP_FMT_INT16;
+			t.normal_stride = nb->stride ? nb->stride : (t.normal_i16 ? 6u : 12u);
+			t.out = bd.buffer; t.out_i16 = bd.format == CRTHIP_FMT_INT16; t.out_stride = bd.stride ? bd.stride : (t.out_i16 ? 8u : 16u);
+			t.nvert = nvert; t.nface = nface;
+			if(tangent_in_blob(nvert)) {
+				pl.tangent_blob_ids.v.push_back((uint32_t)pl.tangent.v.size());
+				pl.tangent_lds = std::max(pl.tangent_lds, tangent_blob_lds(nvert));
+			} else {
+				t.acc = (uint64_t *)SP(S.tan_acc);
+				t.fblock0 = (uint32_t)pl.tan_fblock_job.v.size(); t.vblock0 = (uint32_t)pl.tan_vblock_job.v.size();
+				for(uint32_t c = 0; c < (nface + TAN_BLOCK - 1)/TAN_BLOCK; c++) pl.tan_fblock_job.v.push_back((uint32_t)pl.tangent.v.size());
+				for(uint32_t c = 0; c < (nvert + TAN_BLOCK - 1)/TAN_BLOCK; c++) pl.tan_vblock_job.v.push_back((uint32_t)pl.tangent.v.size());
+			}
+			pl.tangent.v.push_back(t);
 		}
 	}
 	return CRTHIP_OK;

@@ -27,6 +27,7 @@ int Planner::upload() {
 	}
 	for(auto &q : pl.dequant.v) { resolve(q.buffer); resolve(q.src); }
 	for(auto &q : pl.quant.v) { resolve(q.values); resolve(q.range); }
+	for(auto &t : pl.tangent.v) { resolve(t.position); resolve(t.uv); resolve(t.faces); resolve(t.acc); }
 
 	// host image -> device (one copy)
 	stage = (uint8_t *)set.staging.p;
@@ -289,6 +290,16 @@ int Planner::launch(uint32_t phases, const Carry *carry) {
 	}
 	if(pl.any_diff_normal) { LT.begin("normal_diff"); hipLaunchKernelGGL(k_normal_diff, dim3(nvb), dim3(256), 0, st, D(pl.normal),
 		D(pl.nv_block_job), D(pl.nv_block_first), nvb); LT.end(); }
+	// computed tangents: behind every normal kernel (the normals are final), in front of k_dequant (packed position and uv buffers hold integers)
+	if(!pl.tangent_blob_ids.v.empty()) {
+		const uint32_t nj = (uint32_t)pl.tangent_blob_ids.v.size();
+		LT.begin("tangent_blob"); hipLaunchKernelGGL(k_tangent_blob, dim3(nj), dim3(TAN_THREADS), pl.tangent_lds, st, D(pl.tangent), D(pl.tangent_blob_ids), nj); LT.end();
+	}
+	if(!pl.tan_fblock_job.v.empty()) {
+		const uint32_t ntf = (uint32_t)pl.tan_fblock_job.v.size(), ntv = (uint32_t)pl.tan_vblock_job.v.size();
+		LT.begin("tangent_faces"); hipLaunchKernelGGL(k_tangent_faces, dim3(ntf), dim3(TAN_THREADS), 0, st, D(pl.tangent), D(pl.tan_fblock_job), ntf); LT.end();
+		LT.begin("tangent_vertex"); hipLaunchKernelGGL(k_tangent_vertex, dim3(ntv), dim3(TAN_THREADS), 0, st, D(pl.tangent), D(pl.tan_vblock_job), ntv); LT.end();
+	}
 	const uint32_t ndq = (uint32_t)pl.dequant_block_job.v.size();
 	if(ndq) { LT.begin("dequantize"); hipLaunchKernelGGL(k_dequant, dim3(ndq), dim3(256), 0, st, D(pl.dequant), D(pl.dequant_block_job),
 		ndq); LT.end(); }
@@ -337,6 +348,7 @@ void Planner::account() {
 			else ob += (uint64_t)L.h.nvert*a.N*(P.bind[k].quantized ? 2u : generic_work_bytes(P.bind[k].format));
 		}
 		if(computes_normals(P)) ob += (uint64_t)L.h.nvert*3*(P.computed.format == CRTHIP_FMT_INT16 ? 2 : 4);
+		if(computes_tangents(P)) ob += (uint64_t)L.h.nvert*4*(P.tangent.format == CRTHIP_FMT_INT16 ? 2 : 4);
 	}
 	b->stats.output_bytes = ob;
 	ctx->in_flight = b; ctx->last_decoded = b;

@@ -49,7 +49,8 @@ extern "C" {
                                      (upload_copies, upload_gathered_bytes; grouped_steps); crthip_batch_bind_computed_normals (a new
                                      call and nothing else: the number stays 6); CRTHIP_BIND_QUANTIZED, crthip_quant_transform,
                                      crthip_batch_quant_transform, crthip_batch_bind_quant_transforms (a flag that was refused before and
-                                     two new calls: the number stays 6) */
+                                     two new calls: the number stays 6); crthip_batch_bind_computed_tangents, crthip_tangent_model (two
+                                     new calls and nothing else: the number stays 6) */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -281,6 +282,48 @@ int crthip_batch_bind_all(crthip_batch *b, const crthip_attr_binding *attrs, voi
  *                      (the rule of a stored ESTIMATED normal)
  * crthip_last_error() names the blob.  Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host or the crt::Decoder facade. */
 int crthip_batch_bind_computed_normals(crthip_batch *b, uint32_t i, void *buffer, uint32_t format, uint32_t stride);
+
+/* Tangents for a mesh blob: the one vertex attribute a normal-mapped material needs that .crt does not store (upstream computes none).
+ * Added within ABI 6.  The decoder holds what a caller's own pass no longer has - positions and uvs as INTEGERS - so the per-face terms are
+ * summed exactly and the result does not depend on the order in which faces are visited.
+ * Inputs: p[v], the delta-decoded integer position (3 x int32); t[v], the delta-decoded integer value of the attribute named "uv"
+ * (2 x int32); the decoded index; n[v], the vertex's final normal as the decode leaves it in its bound buffer, as three floats (bound as
+ * INT16: the three int16 values converted to float, not rescaled).
+ * Per face f = (a, b, c), on 64-bit two's-complement integers - differences are widened first, products and sums wrap modulo 2^64:
+ *   e1 = p[b]-p[a]   e2 = p[c]-p[a]   (s1,r1) = t[b]-t[a]   (s2,r2) = t[c]-t[a]
+ *   det = s1*r2 - s2*r1      sg = (det>0) - (det<0)
+ *   Tf = sg*(e1*r2 - e2*r1)  Bf = sg*(e2*s1 - e1*s2)
+ * Tf and Bf are added to the accumulators T[v], B[v] of a, b and c (modulo 2^64); a face that names a vertex twice adds twice; a face
+ * with det == 0 adds nothing.  This is the uv-area-weighted tangent.  No intermediate exceeds 63 bits for positions and uvs of up to 24
+ * bits at any realistic valence, and then the sums are exact; the wrap rule defines the value for every other input.
+ * Per vertex, in float32, every product, sum and difference rounded on its own (no FMA):
+ *   scale       k = max(0, bitlength(max |x| over the six components of T[v], B[v]) - 24); every component becomes
+ *               sign(x)*(|x| >> k) - truncated toward zero, so that mirrored uvs give mirrored tangents - and then a float, exactly
+ *   Gram-Schmidt, invariant to the scale of n (INT16 normals need no division):
+ *               nn = (nx*nx + ny*ny) + nz*nz      nt = (nx*Tx + ny*Ty) + nz*Tz
+ *               u = T*nn - n*nt   (a component: two products, one subtraction)      len = sqrtf((ux*ux + uy*uy) + uz*uz)
+ *   handedness  c = cross(n, u) = (ny*uz - nz*uy, nz*ux - nx*uz, nx*uy - ny*ux);  h = (cx*Bx + cy*By) + cz*Bz;  w = h < 0 ? -1 : +1
+ *               - glTF's meaning: bitangent = cross(normal, tangent.xyz)*w.  The uv v-flip convention is the caller's.
+ *   fallback    len not a finite value greater than 0 (a vertex no face names, uvs without area, a tangent parallel to the normal, a NaN
+ *               normal): (1, 0, 0, +1).  Every element of the array is written, and never with a NaN.
+ *   CRTHIP_FMT_FLOAT: 4 x f32 a vertex, (u/len, w).   CRTHIP_FMT_INT16: 4 x i16 a vertex, l = 32767.0f/len, (int16_t)(u*l) a component
+ *   by truncation (the rule of the INT16 normals), w = +-32767; the fallback is (32767, 0, 0, 32767).
+ * buffer: DEVICE pointer.  stride 0 = packed, 16 bytes a vertex (FLOAT) or 8 (INT16).  FLOAT: a 4-byte aligned buffer, a stride that is a
+ * multiple of 4 and at least 16; INT16: 2-byte aligned, an even stride of at least 8.  With a stride only the vertex's own 16 or 8 bytes
+ * are written, as by every strided binding.
+ * Call it AFTER crthip_batch_bind / _bind_all for blob i and AFTER crthip_batch_bind_computed_normals if that is the normals' source: a
+ * later bind or computed-normals call for blob i drops it, as does crthip_batch_reset*; buffer == NULL removes it.  position and uv may
+ * be bound as FLOAT (packed or strided), in any integer format or with CRTHIP_BIND_QUANTIZED - the kernels read the integers in every
+ * case, as estimated normals do; the index may be uint32, uint16 or unbound.  Every error is returned here and nothing new can fail at
+ * decode time:
+ *   CRTHIP_E_ARGUMENT  b NULL or i out of range; a point cloud; no attribute named "uv" that is generic with 2 stored components and bound
+ *                      without CRTHIP_BIND_STREAM_VALUES; no normal source (neither a stored "normal" bound as FLOAT or INT16 nor a
+ *                      computed-normals binding); a stride or an alignment that breaks the rules above
+ *   CRTHIP_E_FORMAT    a format other than FLOAT / INT16
+ *   CRTHIP_E_NORMAL_NEEDS_POSITION  "position" missing, not generic with 3 components, unbound, or bound with CRTHIP_BIND_STREAM_VALUES
+ * crthip_last_error() names the blob.  Kernels tangent_blob (blobs of up to 2 304 vertices) and tangent_faces, tangent_vertex in
+ * crthip_kernel_times.  Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host, the crt::Decoder facade or the veneers. */
+int crthip_batch_bind_computed_tangents(crthip_batch *b, uint32_t i, void *buffer, uint32_t format, uint32_t stride);
 
 /* The record of attribute `attr` of blob i, bound with CRTHIP_BIND_QUANTIZED.  Valid after crthip_batch_sync of a decode: the kernels write
  * the records into the batch's pinned status block, beside the status words.  CRTHIP_E_ARGUMENT if that attribute was not bound
@@ -919,6 +962,15 @@ int64_t crthip_encode_splice_plan_model(uint32_t n, const crthip_mesh *meshes, c
  * order shuffled by `seed`.  1 <= N <= 4, else CRTHIP_E_ARGUMENT. */
 int crthip_quant_out_model(const int32_t *values, uint32_t nvert, uint32_t N, uint32_t stride, void *out, crthip_quant_transform *transform,
                            int which, uint32_t seed);
+
+/* (test hook, no device needed)  The value of crthip_batch_bind_computed_tangents (csrc/tangent.h) on the host, in the kernels' partition.
+ * position: nvert*3 int32, uv: nvert*2 int32, packed; index: nface*3 uint32, or uint16 with index_u16; normal: the normals as a binding of
+ * normal_format (FLOAT / INT16) and normal_stride (0 = packed) leaves them; out, format, stride: as in the binding.  which 0: the
+ * one-workgroup partition of tangent_blob (nvert <= 2 304, else CRTHIP_E_ARGUMENT); which 1: the blocks of tangent_faces /
+ * tangent_vertex.  Blocks and lanes are visited in an order shuffled by `seed`. */
+int crthip_tangent_model(const int32_t *position, const int32_t *uv, const void *index, uint32_t index_u16, uint32_t nvert, uint32_t nface,
+                         const void *normal, uint32_t normal_format, uint32_t normal_stride, void *out, uint32_t format, uint32_t stride,
+                         int which, uint32_t seed);
 
 #ifdef __cplusplus
 }
