@@ -305,7 +305,8 @@ int crthip_batch_bind_computed_normals(crthip_batch *b, uint32_t i, void *buffer
  *   handedness  c = cross(n, u) = (ny*uz - nz*uy, nz*ux - nx*uz, nx*uy - ny*ux);  h = (cx*Bx + cy*By) + cz*Bz;  w = h < 0 ? -1 : +1
  *               - glTF's meaning: bitangent = cross(normal, tangent.xyz)*w.  The uv v-flip convention is the caller's.
  *   fallback    len not a finite value greater than 0 (a vertex no face names, uvs without area, a tangent parallel to the normal, a NaN
- *               normal): (1, 0, 0, +1).  Every element of the array is written, and never with a NaN.
+ *               normal, a T that the common shift k leaves at zero - every component of T[v] 2^24 times below the largest of B[v]):
+ *               (1, 0, 0, +1).  Every element of the array is written, and never with a NaN.
  *   CRTHIP_FMT_FLOAT: 4 x f32 a vertex, (u/len, w).   CRTHIP_FMT_INT16: 4 x i16 a vertex, l = 32767.0f/len, (int16_t)(u*l) a component
  *   by truncation (the rule of the INT16 normals), w = +-32767; the fallback is (32767, 0, 0, 32767).
  * buffer: DEVICE pointer.  stride 0 = packed, 16 bytes a vertex (FLOAT) or 8 (INT16).  FLOAT: a 4-byte aligned buffer, a stride that is a
