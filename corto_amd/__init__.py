@@ -63,6 +63,26 @@ class QuantTransform(C.Structure):
         return dict(base=[int(x) for x in self.base[:n]], span=[int(x) for x in self.span[:n]], q=float(self.q), components=int(n), written=int(self.written))
 
 
+class Meshlet(C.Structure):
+    """crthip_meshlet (meshopt_Meshlet's fields)"""
+    _fields_ = [("vertex_offset", C.c_uint32), ("triangle_offset", C.c_uint32), ("vertex_count", C.c_uint32), ("triangle_count", C.c_uint32)]
+
+
+class MeshletCounts(C.Structure):
+    """crthip_meshlet_counts: a blob's totals (or, from meshlet_bound, its capacities)"""
+    _fields_ = [("meshlets", C.c_uint32), ("vertices", C.c_uint32), ("triangle_bytes", C.c_uint32), ("segments", C.c_uint32)]
+
+    def as_tuple(self):
+        return (self.meshlets, self.vertices, self.triangle_bytes, self.segments)
+
+
+class MeshletBinding(C.Structure):
+    """crthip_meshlet_binding: three device arrays with their capacities, the optional device counts record, the builder's parameters"""
+    _fields_ = [("meshlets", C.c_void_p), ("vertices", C.c_void_p), ("triangles", C.c_void_p), ("counts", C.c_void_p),
+                ("meshlet_capacity", C.c_uint32), ("vertex_capacity", C.c_uint32), ("triangle_capacity", C.c_uint32),
+                ("max_vertices", C.c_uint32), ("max_triangles", C.c_uint32), ("segment_faces", C.c_uint32)]
+
+
 class BatchStats(C.Structure):
     _fields_ = [("arena_bytes", C.c_uint64), ("output_bytes", C.c_uint64), ("tunstall_in", C.c_uint64),
                 ("tunstall_out", C.c_uint64), ("tunstall_tables", C.c_uint64), ("tunstall_streams", C.c_uint32),
@@ -246,6 +266,11 @@ def lib():
         L.crthip_batch_bind_computed_tangents.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
         L.crthip_tangent_model.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
                                            C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32]
+        L.crthip_batch_bind_meshlets.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshletBinding)]
+        L.crthip_batch_meshlet_counts.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshletCounts)]
+        L.crthip_meshlet_bound.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(MeshletCounts)]
+        L.crthip_meshlet_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(MeshletBinding), C.POINTER(MeshletCounts),
+                                           C.c_int, C.c_uint32]
         L.crthip_batch_quant_transform.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(QuantTransform)]
         L.crthip_batch_bind_quant_transforms.argtypes = [C.c_void_p, C.c_void_p]
         L.crthip_quant_out_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(QuantTransform), C.c_int, C.c_uint32]
@@ -926,6 +951,49 @@ def tangent_model(position: np.ndarray, uv: np.ndarray, index: np.ndarray, norma
     return np.ascontiguousarray(rec).view(np.int16 if fmt == FMT_INT16 else np.float32).reshape(nvert, 4)
 
 
+def meshlet_bound(nface: int, groups=(), max_vertices: int = 64, max_triangles: int = 124, segment_faces: int = 0) -> MeshletCounts:
+    """crthip_meshlet_bound: the capacities (records, words, bytes) a meshlet binding of such an index needs, and its exact segment count"""
+    g = np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1)
+    out = MeshletCounts()
+    _check(lib().crthip_meshlet_bound(nface, len(g), _np_ptr(g) if len(g) else None, max_vertices, max_triangles, segment_faces, C.byref(out)))
+    return out
+
+
+def cut_meshlets(meshlets: np.ndarray, vertices: np.ndarray, triangles: np.ndarray, counts):
+    """the three arrays of a meshlet binding cut to a counts record: (meshlets (n, 4) uint32, vertices uint32, triangles uint8)"""
+    return (np.ascontiguousarray(meshlets).view(np.uint32).reshape(-1, 4)[:counts.meshlets], np.ascontiguousarray(vertices).view(np.uint32)[:counts.vertices],
+            np.ascontiguousarray(triangles).view(np.uint8)[:counts.triangle_bytes])
+
+
+def meshlet_model(index: np.ndarray, groups=(), max_vertices: int = 64, max_triangles: int = 124, segment_faces: int = 0, which: int = 0, seed: int = 0,
+                  capacity=None, fill: int = 0xCD, raw: bool = False):
+    """crthip_meshlet_model: crthip_batch_bind_meshlets on the host in the kernels' partition (which 0: meshlet_blob; 1: meshlet_segments /
+    meshlet_place; segments, workgroups and lanes shuffled by seed).  index (nface, 3) uint32 or uint16.  The arrays are made here at
+    `capacity` (meshlets, vertices, triangle bytes; None: exactly the bound) and filled with `fill` first.  Returns (meshlets, vertices, triangles,
+    counts) cut to the counts, or with raw the whole arrays as uint8."""
+    idx = np.ascontiguousarray(index)
+    if idx.dtype != np.uint16:
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    idx = idx.reshape(-1, 3)
+    g = np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1)
+    if capacity is None:
+        bd = meshlet_bound(len(idx), g, max_vertices, max_triangles, segment_faces)
+        capacity = (bd.meshlets, bd.vertices, bd.triangle_bytes)
+    # (uint32-backed blocks: 4-byte aligned at least; the records' 16 from the slice below)
+    mraw = np.full(capacity[0] * 16 + 16, fill, np.uint8)
+    mo = (-mraw.ctypes.data) % 16
+    m = mraw[mo:mo + capacity[0] * 16]
+    v = np.full(capacity[1] + 1, fill * 0x01010101, np.uint32)[:capacity[1]].view(np.uint8)
+    t = np.full((capacity[2] + 7) // 4, fill * 0x01010101, np.uint32).view(np.uint8)[:capacity[2]]
+    b = MeshletBinding(m.ctypes.data, v.ctypes.data, t.ctypes.data, None, capacity[0], capacity[1], capacity[2], max_vertices, max_triangles, segment_faces)
+    counts = MeshletCounts()
+    _check(lib().crthip_meshlet_model(_np_ptr(idx) if len(idx) else None, int(idx.dtype == np.uint16), len(idx), len(g), _np_ptr(g) if len(g) else None,
+                                      C.byref(b), C.byref(counts), which, seed))
+    if raw:
+        return m, v, t, counts
+    return cut_meshlets(m, v, t, counts) + (counts,)
+
+
 def encode_splice_plan_model(meshes, kw=None, chunk_items=0):
     """crthip_encode_splice_plan_model: the device splice's plan of a batch on the host, in chunks of chunk_items meshes (0: one chunk) that
     continue the arena as the chunks of a batch beyond one device image do.  Returns (offsets, lens, stats dict, pieces): pieces an
@@ -1112,6 +1180,7 @@ class Batch:
         self._keep = None
         self._computed = []                          # (blob, pointer, format, stride): what rebind() applies again behind crthip_batch_bind_all
         self._tangents = []                          # ... and behind those, through crthip_batch_bind_computed_tangents
+        self._meshlets = {}                          # blob -> (MeshletBinding, the tensors it points into): applied again by rebind() too
         self._interleaved = None
 
     def __len__(self):
@@ -1156,7 +1225,7 @@ class Batch:
     # -- outputs -----------------------------------------------------------------------------------
     def allocate_outputs(self, normal_format=FMT_FLOAT, color_components: Optional[int] = None, index16=False,
                          only: Optional[set] = None, fill: Optional[int] = None, computed_normals=False, quantized=(),
-                         computed_tangents=False, tangent_format=FMT_FLOAT):
+                         computed_tangents=False, tangent_format=FMT_FLOAT, meshlets=None):
         """Allocate every output of every blob inside ONE device buffer (torch.uint8) and bind them.
         Returns a list (per blob) of dicts name -> torch tensor view.
         computed_normals: every mesh blob WITHOUT a normal attribute gets a "normal" tensor of normal_format all the same, bound
@@ -1165,7 +1234,9 @@ class Batch:
         transforms come from quant_transform(i, name) after sync().
         computed_tangents: every mesh blob with a bound two-component generic "uv", a bound "position", a normal source (stored or computed
         here) and no stored attribute named "tangent" gets a "tangent" tensor (nvert, 4) of tangent_format, bound through
-        crthip_batch_bind_computed_tangents (include/corto_hip.h: xyz and the handedness w)."""
+        crthip_batch_bind_computed_tangents (include/corto_hip.h: xyz and the handedness w).
+        meshlets: (max_vertices, max_triangles, segment_faces) - every mesh blob gets its three meshlet arrays at crthip_meshlet_bound and a
+        device counts record, bound through crthip_batch_bind_meshlets; read them with meshlets(i) after sync()."""
         import torch
         dev = torch.device("cuda", self.ctx.device)
         plan = []   # (blob, name, offset, nbytes, dtype, shape, binding_slot)
@@ -1208,6 +1279,12 @@ class Batch:
             if nf and (only is None or "index" in only):
                 dt = "u16" if index16 else "u32"
                 plan.append((i, "index", take(nf * 3 * np.dtype(_DT[dt]).itemsize), dt, (nf, 3), -1, FMT_UINT16 if index16 else FMT_UINT32, 0))
+        mplan = []                                   # (blob, the bound, offsets of the records, the words, the bytes, the counts record)
+        if meshlets is not None:
+            for i, info in enumerate(self.infos):
+                if info.nface:
+                    bd = meshlet_bound(info.nface, self.groups(i), *meshlets)
+                    mplan.append((i, bd, take(bd.meshlets * 16), take(bd.vertices * 4), take(bd.triangle_bytes), take(16)))
         total = max(off, 256)
         buf = torch.empty(total, dtype=torch.uint8, device=dev) if fill is None else torch.full((total,), fill, dtype=torch.uint8, device=dev)
         _torch_ready(dev)                            # (the fill runs on torch's stream; the decode on the context's own)
@@ -1218,6 +1295,10 @@ class Batch:
         index_ptrs = (C.c_void_p * max(len(self), 1))()
         index_fmt = np.full(max(len(self), 1), FMT_UINT32, dtype=np.uint32)
         outs = [dict() for _ in self.infos]
+        self._meshlets = {}
+        for (i, bd, mo, vo, to, co) in mplan:
+            mb = MeshletBinding(base + mo, base + vo, base + to, base + co, bd.meshlets, bd.vertices, bd.triangle_bytes, *meshlets)
+            self._meshlets[i] = (mb, (buf[mo:mo + bd.meshlets * 16], buf[vo:vo + bd.vertices * 4], buf[to:to + bd.triangle_bytes], buf[co:co + 16]))
         computed, tangents = [], []
         tdt = {"f32": torch.float32, "i16": torch.int16, "u8": torch.uint8, "u32": torch.int32, "u16": torch.int16}
         for (i, name, o, dt, shape, slot, fmt, oc) in plan:
@@ -1289,6 +1370,7 @@ class Batch:
         self._keep = (buf, binds, index_ptrs, index_fmt)
         self._computed = []
         self._tangents = []
+        self._meshlets = {}
         self._interleaved = metas
         self.outputs = [dict() for _ in self.infos]
         self.rebind()
@@ -1334,6 +1416,8 @@ class Batch:
             _check(lib().crthip_batch_bind_computed_normals(self.handle, i, C.c_void_p(ptr), fmt, stride))
         for (i, ptr, fmt, stride) in self._tangents:          # (... and its tangents, whose normal source is bound by now)
             _check(lib().crthip_batch_bind_computed_tangents(self.handle, i, C.c_void_p(ptr), fmt, stride))
+        for i, (mb, _) in self._meshlets.items():              # (... and its meshlets)
+            _check(lib().crthip_batch_bind_meshlets(self.handle, i, C.byref(mb)))
 
     def bind(self, i: int, bindings: Sequence[AttrBinding], index_ptr: Optional[int] = None, index_format=FMT_UINT32):
         arr = (AttrBinding * max(len(bindings), 1))(*bindings)
@@ -1349,6 +1433,30 @@ class Batch:
         """crthip_batch_bind_computed_tangents: blob i's tangents (xyz and the handedness w: nvert*4 f32 or i16; stride 0 = packed) go to the
         device pointer `ptr`.  After bind() / rebind() and bind_computed_normals() of that blob, which drop it; ptr None or 0 removes it."""
         _check(lib().crthip_batch_bind_computed_tangents(self.handle, i, C.c_void_p(ptr) if ptr else None, fmt, stride))
+
+    def bind_meshlets(self, i: int, binding: Optional[MeshletBinding] = None, keep=None):
+        """crthip_batch_bind_meshlets: blob i's meshlets go to the binding's device arrays (capacities at least meshlet_bound's).  After bind() /
+        rebind() of that blob, which drop it; None removes it.  keep: whatever owns the arrays (device tensors), held with the binding - a
+        tuple (meshlets, vertices, triangles, counts or None) makes meshlets(i) work."""
+        if binding is None:
+            self._meshlets.pop(i, None)
+            _check(lib().crthip_batch_bind_meshlets(self.handle, i, None))
+            return
+        _check(lib().crthip_batch_bind_meshlets(self.handle, i, C.byref(binding)))
+        self._meshlets[i] = (binding, keep)
+
+    def meshlet_counts(self, i: int) -> MeshletCounts:
+        """crthip_batch_meshlet_counts: blob i's totals (meshlets, vertex words, triangle bytes, segments); after sync()"""
+        out = MeshletCounts()
+        _check(lib().crthip_batch_meshlet_counts(self.handle, i, C.byref(out)))
+        return out
+
+    def meshlets(self, i: int):
+        """Blob i's meshlets on the host, cut to the counts: (meshlets (n, 4) uint32 - vertex_offset, triangle_offset, vertex_count,
+        triangle_count - , vertices uint32, triangles uint8).  After sync(); for bindings made by allocate_outputs(meshlets=) or bind_meshlets(keep=)."""
+        c = self.meshlet_counts(i)
+        _, keep = self._meshlets[i]
+        return cut_meshlets(*[k.cpu().numpy() for k in keep[:3]], c)
 
     def quant_transform(self, i: int, name) -> QuantTransform:
         """crthip_batch_quant_transform: the record of blob i's attribute `name` (or index), bound quantised; after sync()"""

@@ -72,6 +72,10 @@ int harvest(crthip_ctx *ctx) {
 		const crthip_quant_transform *rec = (const crthip_quant_transform *)((const uint8_t *)hs + W.records());
 		b->quant_recs.assign(rec, rec + b->quant_bound.size());
 	}
+	if(!b->meshlet_bound.empty()) {                                       // crthip_batch_bind_meshlets: a record a blob behind those
+		const crthip_meshlet_counts *rec = (const crthip_meshlet_counts *)((const uint8_t *)hs + W.meshlet_records(b->quant_bound.size()));
+		b->meshlet_recs.assign(rec, rec + n);
+	}
 	b->stats.topology_fallbacks = 0; b->stats.delta_redone = 0; b->stats.delta_walked = 0;
 	for(size_t i = 0; i < n; i++) {
 		b->stats.topology_fallbacks += (uint64_t)(hs[W.topo_flags(i)] & 1);
@@ -242,12 +246,13 @@ static crthip_ctx::Half &begin_fill(crthip_ctx *ctx, crthip_batch *b) {
 	b->dirty = true; b->decoded = false;
 	b->d_arena = nullptr;
 	b->quant_dev = nullptr; b->quant_bound.clear(); b->quant_recs.clear();
+	b->meshlet_bound.clear(); b->meshlet_recs.clear();
 	return ctx_set(ctx, b);
 }
 static uint64_t adopt_blob(BlobPlan &P, uint64_t arena_off, uint32_t len, crthip_batch_stats &stats) {
 	P.arena_off = arena_off; P.len = len;
 	P.bind.assign(P.L.h.attrs.size(), Binding{});
-	P.index = nullptr; P.index_u16 = 0; P.host_status = 0; P.computed = Binding{}; P.tangent = Binding{};
+	P.index = nullptr; P.index_u16 = 0; P.host_status = 0; P.computed = Binding{}; P.tangent = Binding{}; P.meshlets = crthip_meshlet_binding{};
 	P.dbg_clers = P.dbg_pred = ~0ull; P.dbg_nclers = 0; P.clers_in_arena = false;
 	stats.total_nvert += P.L.h.nvert; stats.total_nface += P.L.h.nface;
 	if(P.L.h.nface) { stats.clers_symbols += P.L.clers.size; stats.split_bytes += (uint64_t)P.L.split.nwords*4; }
@@ -556,6 +561,7 @@ extern "C" int crthip_batch_bind(crthip_batch *b, uint32_t i, const crthip_attr_
 	P.index = index; P.index_u16 = index && index_format == CRTHIP_FMT_UINT16;
 	P.computed = Binding{};                                                 // (crthip_batch_bind_computed_normals comes after the bind)
 	P.tangent = Binding{};                                                  // (... and crthip_batch_bind_computed_tangents after both)
+	P.meshlets = crthip_meshlet_binding{};                                  // (... and crthip_batch_bind_meshlets)
 	b->dirty = true;
 	return CRTHIP_OK;
 }
@@ -617,6 +623,30 @@ extern "C" int crthip_batch_bind_computed_tangents(crthip_batch *b, uint32_t i, 
 	P.tangent.buffer = buffer; P.tangent.format = format; P.tangent.out_components = 4;
 	P.tangent.stride = stride == 4*el ? 0u : stride;
 	b->dirty = true;
+	return CRTHIP_OK;
+}
+
+// Meshlets from the blob's decoded index (corto_hip.h has the contract): every check is made here, against the bound of this blob's index
+extern "C" int crthip_batch_bind_meshlets(crthip_batch *b, uint32_t i, const crthip_meshlet_binding *m) {
+	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_meshlets: no such blob");
+	BlobPlan &P = b->blobs[i];
+	const std::string who = " (blob " + std::to_string(i) + ")";
+	if(!m) { P.meshlets = crthip_meshlet_binding{}; b->dirty = true; return CRTHIP_OK; }
+	if(P.L.h.nface == 0) return fail(CRTHIP_E_ARGUMENT, "meshlets need faces: a point cloud has none" + who);
+	crthip_meshlet_counts bound;
+	const bool ok = mlt_plan(P.L.h.nface, (uint32_t)P.L.group_end.size(), P.L.group_end.data(), m->max_vertices, m->max_triangles, m->segment_faces, nullptr, bound);
+	if(const char *why = meshlet_binding_error(m, ok, bound)) return fail(CRTHIP_E_ARGUMENT, why + who);
+	P.meshlets = *m;
+	b->dirty = true;
+	return CRTHIP_OK;
+}
+
+extern "C" int crthip_batch_meshlet_counts(const crthip_batch *b, uint32_t i, crthip_meshlet_counts *out) {
+	if(!b || !out || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_meshlet_counts: no such blob");
+	if(!b->decoded || (b->ctx && b->ctx->in_flight == b) || b->staged) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_meshlet_counts: decode and sync the batch first");
+	if(i >= b->meshlet_bound.size() || i >= b->meshlet_recs.size() || !b->meshlet_bound[i])
+		return fail(CRTHIP_E_ARGUMENT, "crthip_batch_meshlet_counts: the blob had no meshlet binding in that decode (blob " + std::to_string(i) + ")");
+	*out = b->meshlet_recs[i];
 	return CRTHIP_OK;
 }
 

@@ -24,6 +24,7 @@
 #include "plan_feedback.h"
 #include "quant_out.h"
 #include "tangent.h"
+#include "meshlet.h"
 
 using namespace corto_hip;
 
@@ -89,10 +90,11 @@ struct BlobScratch {
 	uint64_t progress = ~0ull;                              // the automaton's progress word (zeroed): blobs with an attribute too big for K-DELTA's LDS records
 	uint32_t front_cap = 0, aux_groups = 0;
 	uint64_t tan_acc = ~0ull;                               // computed tangents (BlobPlan::tangent) of a blob beyond TANGENT_BLOB_MAX: 6 x int64 a vertex, inside the zeroed region
+	uint64_t mlt = ~0ull;                                   // meshlets (BlobPlan::meshlets) of a blob of more than one segment: mlt_scratch_layout's block
 	uint64_t cn_facen = ~0ull;                              // computed normals (BlobPlan::computed) by the fused kernel without its face normals in LDS: AttrScratch::facen's counterpart
 	std::vector<AttrScratch> attr;
 	size_t nattr = 0;                                       // attr[0..nattr) are this decode's (the vector only grows)
-	void reset() { clers = pred = front_a = front_b = order = delayed = faces = progress = cn_facen = tan_acc = ~0ull; front_cap = 0; aux_groups = 0; nattr = 0; }
+	void reset() { clers = pred = front_a = front_b = order = delayed = faces = progress = cn_facen = tan_acc = mlt = ~0ull; front_cap = 0; aux_groups = 0; nattr = 0; }
 	void set_attrs(size_t n) { if(attr.size() < n) attr.resize(n); for(size_t k = nattr; k < n; k++) attr[k].reset();
 		if(n > nattr) nattr = n; }
 };
@@ -121,6 +123,10 @@ struct Plan {
 	HostArr<QuantOutJob> quant; HostArr<uint32_t> quant_blob_ids, quant_block_job;
 	// crthip_batch_bind_computed_tangents: blobs of up to TANGENT_BLOB_MAX vertices by id (k_tangent_blob), the others by block (k_tangent_faces, k_tangent_vertex)
 	HostArr<TangentJob> tangent; HostArr<uint32_t> tangent_blob_ids, tan_fblock_job, tan_vblock_job; uint32_t tangent_lds = 0;
+	// crthip_batch_bind_meshlets: blobs of up to MESHLET_BLOB_SEGS segments by id (k_meshlet_blob, meshlet_waves the most segments among them), the
+	// others a block a segment (k_meshlet_segments, k_meshlet_place); the segment tables are in aux_u32
+	HostArr<MeshletJob> meshlet; HostArr<uint32_t> meshlet_blob_ids, mlt_block_job; uint32_t meshlet_waves = 0;
+	bool meshlet_records = false;                           // a crthip_meshlet_counts a blob behind the quant records: a batch with a meshlet binding
 	uint32_t quant_records = 0;                             // records behind the status words: sum(nattr) of a batch with a quantised binding, else 0
 	// scratch regions (offsets)
 	uint64_t zero_begin = 0, zero_end = 0;
@@ -140,10 +146,11 @@ struct Plan {
 		f(delta); f(delta_groups); f(cloud); f(cloud_chunk_job); f(normal); f(nv_block_job); f(nv_block_first); f(nf_block_job); f(nf_block_first);
 		f(normal_fused_ids); f(normal_computed_ids); f(dequant); f(dequant_block_job); f(quant); f(quant_blob_ids); f(quant_block_job);
 		f(tangent); f(tangent_blob_ids); f(tan_fblock_job); f(tan_vblock_job);
+		f(meshlet); f(meshlet_blob_ids); f(mlt_block_job);
 	}
 	void reset() {                                          // keep every vector's capacity
 		each_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
-		clers_groups = 0; topo_need.clear(); quant_records = 0;
+		clers_groups = 0; topo_need.clear(); quant_records = 0; meshlet_waves = 0; meshlet_records = false;
 		topo_lds = topo_big_lds = normal_fused_lds = normal_computed_lds = tangent_lds = 0;
 		zero_begin = zero_end = tables_off = tun_partial_off = unpack_partial_off = cloud_partial_off = 0;
 		facen_off = cnt_off = cursor_off = bnd_off = start_off = flag_off = slot_off = adj_off = nscan_partial_off = 0;
@@ -228,6 +235,7 @@ struct BlobPlan {
 	void *index = nullptr; uint32_t index_u16 = 0;
 	Binding computed;          // crthip_batch_bind_computed_normals: where the normals of a blob that stores (or binds) none go; dropped by every bind / reset
 	Binding tangent;           // crthip_batch_bind_computed_tangents: where the blob's tangents go (out_components 4); dropped by every bind, computed-normals call and reset
+	crthip_meshlet_binding meshlets{};   // crthip_batch_bind_meshlets: meshlets.meshlets != null - where the blob's meshlets go; dropped by every bind and reset
 	int32_t host_status = 0;   // set by the planner (e.g. unsupported format), overrides device status
 	// debug handles (scratch offsets valid after decode)
 	uint64_t dbg_clers = ~0ull, dbg_pred = ~0ull; uint32_t dbg_nclers = 0;
@@ -255,6 +263,8 @@ struct crthip_batch {
 	// found them in the status block and which of them belong to a quantised binding (crthip_batch_bind_all's order)
 	void *quant_dev = nullptr;
 	std::vector<crthip_quant_transform> quant_recs; std::vector<uint8_t> quant_bound;
+	// crthip_batch_bind_meshlets: which blobs of the last decode had a binding, and their records as harvest found them
+	std::vector<uint8_t> meshlet_bound; std::vector<crthip_meshlet_counts> meshlet_recs;
 };
 void drop_staged(crthip_batch *b);      // (batch.cpp)
 inline crthip_ctx::Half &ctx_set(crthip_ctx *ctx, const crthip_batch *b) { return ctx->set[b->parity]; }   // the batch's set of per-call blocks
@@ -269,6 +279,8 @@ struct StatusWords {
 	size_t bytes() const { return n*16; }
 	// behind them (16-byte aligned): the crthip_quant_transform records of a batch with a quantised binding, one an attribute
 	size_t records() const { return n*16; }
+	// ... and behind those (16-byte aligned) a crthip_meshlet_counts a blob of a batch with a meshlet binding
+	size_t meshlet_records(size_t quant_records) const { return (n*16 + quant_records*sizeof(crthip_quant_transform) + 15) & ~(size_t)15; }
 };
 
 int harvest(crthip_ctx *ctx);     // wait for the batch in flight on the context, keep its per-blob status, learn from its flags (batch.cpp)
@@ -302,6 +314,13 @@ static bool normal_fused(uint32_t nvert, uint32_t nface) { return nvert <= 32767
 constexpr uint32_t TANGENT_BLOB_MAX = TAN_BLOB_SLOTS*TAN_THREADS;          // 2 304
 static inline bool computes_tangents(const BlobPlan &P) { return P.tangent.buffer && P.L.h.nface > 0; }
 static inline bool tangent_in_blob(uint32_t nvert) { return nvert <= TANGENT_BLOB_MAX; }
+
+// meshlets (crthip_batch_bind_meshlets): a blob of up to MESHLET_BLOB_SEGS segments takes k_meshlet_blob - one workgroup, a wave a segment, so a
+// workgroup's four waves; more segments would queue behind one another in a workgroup while the chip has idle CUs - the others
+// k_meshlet_segments / k_meshlet_place, a workgroup a segment
+constexpr uint32_t MESHLET_BLOB_SEGS = 4;
+static inline bool builds_meshlets(const BlobPlan &P) { return P.meshlets.meshlets && P.L.h.nface > 0; }
+namespace corto_hip { const char *meshlet_binding_error(const crthip_meshlet_binding *m, bool have_bound, const crthip_meshlet_counts &bound); }
 
 struct Launch {
 	crthip_ctx *ctx;

@@ -199,9 +199,24 @@ struct TangentJob {
 	uint8_t faces_u16, normal_i16, out_i16, pad[5];
 };
 
+// a blob bound with crthip_batch_bind_meshlets (k_meshlet.hip, meshlet.h): the index and the host's segment table -> the caller's three arrays
+// and the blob's record.  A blob of one segment is written in place; the others go through `scratch` (mlt_scratch_layout) and are moved
+struct MeshletJob {
+	const void *faces;             // u32 or, with faces_u16, u16 triples: the caller's index, or scratch
+	const void *segs;              // nseg MltSeg (in aux_u32; a byte offset into it until upload)
+	void *meshlets, *vertices, *triangles;   // the binding's arrays
+	uint8_t *scratch;              // provisional arrays and a count a segment; null for a blob of one segment
+	void *rec_host, *rec_dev;      // crthip_meshlet_counts: the pinned status block's, and the binding's optional device copy
+	uint32_t nface, nseg, max_vertices, max_triangles;
+	uint32_t sc_vertices, sc_triangles, sc_counts;   // byte offsets of scratch's parts (its meshlet records are at 0)
+	uint32_t block0;               // first block of this job in the block -> job map (meshlet_segments, meshlet_place)
+	uint8_t faces_u16, pad[7];
+};
+
 // the layout the kernels read, pinned (TopoJob's size is performance-critical: TOPO_OPT_PROGRESS above)
 static_assert(sizeof(TunStream) == 64 && sizeof(FillJob) == 16 && sizeof(TopoJob) == 136 && sizeof(UnpackJob) == 56 && sizeof(DeltaJob) == 96 &&
-              sizeof(CloudJob) == 24 && sizeof(NormalJob) == 104 && sizeof(DequantJob) == 64 && sizeof(QuantOutJob) == 72 && sizeof(TangentJob) == 80, "decode job layout");
+              sizeof(CloudJob) == 24 && sizeof(NormalJob) == 104 && sizeof(DequantJob) == 64 && sizeof(QuantOutJob) == 72 && sizeof(TangentJob) == 80 &&
+              sizeof(MeshletJob) == 104, "decode job layout");
 static_assert(offsetof(TopoJob, opts) == 116 && offsetof(UnpackJob, out_kind) == 51 && offsetof(NormalJob, faces_u16) == 58, "decode job layout");
 static_assert(offsetof(DeltaJob, in_i16) == 34 && offsetof(DeltaJob, wide) == 35 && offsetof(DeltaJob, rounds) == 88 &&
               offsetof(DeltaJob, status_back) == 92, "decode job layout");

@@ -58,6 +58,13 @@ __global__ void k_tangent_faces(const TangentJob *jobs, const uint32_t *block_jo
 __global__ void k_tangent_vertex(const TangentJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 __host__ __device__ inline uint32_t tangent_blob_lds(uint32_t nvert) { return (nvert*24u + 15u) & ~15u; }
 
+// k_meshlet.hip (crthip_batch_bind_meshlets; meshlet.h has the builder): blobs of up to MESHLET_BLOB_SEGS segments (batch_internal.h) by one workgroup
+// each, a wave a segment, from an id list, with sizeof(MltWaveMem) of dynamic LDS a wave (launch 64 x the most segments a listed blob has); bigger
+// ones a wave a segment from a block -> job map into the job's scratch, then a workgroup a segment moves the pieces
+__global__ void k_meshlet_blob(const MeshletJob *jobs, const uint32_t *job_ids, uint32_t njobs);
+__global__ void k_meshlet_segments(const MeshletJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_meshlet_place(const MeshletJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+
 // k_mesh.hip
 __global__ void k_topology(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);
 __global__ void k_topology_lds(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);

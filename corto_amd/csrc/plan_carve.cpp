@@ -107,6 +107,14 @@ int Planner::carve() {
 		if(computes_normals(P) && normal_fused(L.h.nvert, L.h.nface) && normal_blob_lds_fn(L.h.nvert, L.h.nface) > ctx->normal_fn_max)
 			S.cn_facen = cv.take((uint64_t)L.h.nface*12 + 16, 16);
 	}
+	for(uint32_t i = 0; i < nblobs; i++) {                           // meshlets of more than one segment: the provisional arrays and a count a segment
+		const BlobPlan &P = b->blobs[i];
+		if(!builds_meshlets(P)) continue;
+		crthip_meshlet_counts bound;
+		if(!mlt_plan(P.L.h.nface, (uint32_t)P.L.group_end.size(), P.L.group_end.data(), P.meshlets.max_vertices, P.meshlets.max_triangles,
+			P.meshlets.segment_faces, nullptr, bound)) continue;                   // (the bind call made sure; jobs() gives such a blob no job)
+		if(bound.segments > 1) bs[i].mlt = cv.take(mlt_scratch_layout(P.L.h.nface, bound).total, 16);
+	}
 	if(est_v) {
 		pl.start_off = cv.take(est_v*4 + 16); pl.flag_off = cv.take(est_v*4 + 16); pl.slot_off = cv.take(est_v*4 + 16);
 		pl.adj_off = cv.take(est_f*12 + 16); pl.facen_off = cv.take(est_f*12 + 16);

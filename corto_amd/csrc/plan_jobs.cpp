@@ -15,8 +15,9 @@ int Planner::jobs() {
 		uint32_t nattr = 0; bool any = false;
 		for(const BlobPlan &P : b->blobs) { nattr += (uint32_t)P.bind.size(); for(const Binding &bd : P.bind) any = any || (bd.buffer && bd.quantized); }
 		pl.quant_records = any ? nattr : 0u;
+		for(const BlobPlan &P : b->blobs) pl.meshlet_records = pl.meshlet_records || builds_meshlets(P);
 	}
-	const size_t status_bytes = hs.records() + (size_t)pl.quant_records*sizeof(crthip_quant_transform) + 16;
+	const size_t status_bytes = hs.meshlet_records(pl.quant_records) + (pl.meshlet_records ? b->blobs.size()*sizeof(crthip_meshlet_counts) : 0) + 16;
 	if(status_bytes > set.status_host.cap && harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE);
 	if(set.status_host.reserve(status_bytes) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
 	hs_base = (int32_t *)set.status_host.p;
@@ -385,6 +386,34 @@ int Planner::jobs() {
 				for(uint32_t c = 0; c < (nvert + TAN_BLOCK - 1)/TAN_BLOCK; c++) pl.tan_vblock_job.v.push_back((uint32_t)pl.tangent.v.size());
 			}
 			pl.tangent.v.push_back(t);
+		}
+		// meshlets: crthip_batch_bind_meshlets.  The index where the automaton leaves it, the cuts made here from the group table (in aux_u32 behind
+		// the group lists), the caller's arrays; scratch for a blob of more than one segment.  (The bind call checked all of it)
+		if(builds_meshlets(P)) {
+			const crthip_meshlet_binding &mb = P.meshlets;
+			std::vector<MltSeg> segs; crthip_meshlet_counts bound;
+			if(!mlt_plan(nface, (uint32_t)L.group_end.size(), L.group_end.data(), mb.max_vertices, mb.max_triangles, mb.segment_faces, &segs, bound) ||
+				meshlet_binding_error(&mb, true, bound) || (bound.segments > 1 && S.mlt == ~0ull)) { P.host_status = CRTHIP_E_ARGUMENT; continue; }
+			MeshletJob m{};
+			m.faces = P.index ? P.index : (void *)SP(S.faces); m.faces_u16 = P.index ? (uint8_t)P.index_u16 : 0;
+			while(pl.aux_u32.v.size() % 4) pl.aux_u32.v.push_back(0);             // (an MltSeg is read as one 16-byte word)
+			m.segs = (const void *)(uintptr_t)(pl.aux_u32.v.size()*4);            // bytes into aux_u32 (resolved by upload)
+			for(const MltSeg &sg : segs) { pl.aux_u32.v.push_back(sg.f0); pl.aux_u32.v.push_back(sg.f1); pl.aux_u32.v.push_back(sg.mbase); pl.aux_u32.v.push_back(sg.tbase); }
+			m.meshlets = mb.meshlets; m.vertices = mb.vertices; m.triangles = mb.triangles;
+			m.rec_host = (uint8_t *)hs_base + hs.meshlet_records(pl.quant_records) + (size_t)i*sizeof(crthip_meshlet_counts); m.rec_dev = mb.counts;
+			m.nface = nface; m.nseg = bound.segments; m.max_vertices = mb.max_vertices; m.max_triangles = mb.max_triangles;
+			if(bound.segments > 1) {
+				const MltScratchLayout lay = mlt_scratch_layout(nface, bound);
+				m.scratch = SP(S.mlt); m.sc_vertices = (uint32_t)lay.vertices; m.sc_triangles = (uint32_t)lay.triangles; m.sc_counts = (uint32_t)lay.counts;
+			}
+			if(bound.segments <= MESHLET_BLOB_SEGS) {
+				pl.meshlet_blob_ids.v.push_back((uint32_t)pl.meshlet.v.size());
+				pl.meshlet_waves = std::max(pl.meshlet_waves, bound.segments);
+			} else {
+				m.block0 = (uint32_t)pl.mlt_block_job.v.size();
+				for(uint32_t c = 0; c < bound.segments; c++) pl.mlt_block_job.v.push_back((uint32_t)pl.meshlet.v.size());
+			}
+			pl.meshlet.v.push_back(m);
 		}
 	}
 	return CRTHIP_OK;

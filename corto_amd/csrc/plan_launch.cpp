@@ -28,12 +28,13 @@ int Planner::upload() {
 	for(auto &q : pl.dequant.v) { resolve(q.buffer); resolve(q.src); }
 	for(auto &q : pl.quant.v) { resolve(q.values); resolve(q.range); }
 	for(auto &t : pl.tangent.v) { resolve(t.position); resolve(t.uv); resolve(t.faces); resolve(t.acc); }
+	for(auto &m : pl.meshlet.v) { m.segs = base + pl.aux_u32.dev_off + (uintptr_t)m.segs; resolve(m.faces); resolve(m.scratch); }
 
 	// host image -> device (one copy)
 	stage = (uint8_t *)set.staging.p;
 	memset(stage + (pl.unpack_partial_off - pl.jobs_begin), 0, unpack_state_words*8);
 	// (after the harvest above: the previous batch's words have been read)
-	memset(set.status_host.p, 0, hs.records() + (size_t)pl.quant_records*sizeof(crthip_quant_transform));
+	memset(set.status_host.p, 0, hs.meshlet_records(pl.quant_records) + (pl.meshlet_records ? b->blobs.size()*sizeof(crthip_meshlet_counts) : 0));
 	if(pl.quant_records) {                                               // a quantised attribute of a blob without vertices has no job: its record is all zero, written
 		crthip_quant_transform *rec = (crthip_quant_transform *)((uint8_t *)set.status_host.p + hs.records());
 		for(const BlobPlan &P : b->blobs) {
@@ -300,6 +301,17 @@ int Planner::launch(uint32_t phases, const Carry *carry) {
 		LT.begin("tangent_faces"); hipLaunchKernelGGL(k_tangent_faces, dim3(ntf), dim3(TAN_THREADS), 0, st, D(pl.tangent), D(pl.tan_fblock_job), ntf); LT.end();
 		LT.begin("tangent_vertex"); hipLaunchKernelGGL(k_tangent_vertex, dim3(ntv), dim3(TAN_THREADS), 0, st, D(pl.tangent), D(pl.tan_vblock_job), ntv); LT.end();
 	}
+	// meshlets: the index has been final since the automata
+	if(!pl.meshlet_blob_ids.v.empty()) {
+		const uint32_t nj = (uint32_t)pl.meshlet_blob_ids.v.size();
+		LT.begin("meshlet_blob"); hipLaunchKernelGGL(k_meshlet_blob, dim3(nj), dim3(64*pl.meshlet_waves), pl.meshlet_waves*(uint32_t)sizeof(MltWaveMem), st, D(pl.meshlet),
+			D(pl.meshlet_blob_ids), nj); LT.end();
+	}
+	if(!pl.mlt_block_job.v.empty()) {
+		const uint32_t nb = (uint32_t)pl.mlt_block_job.v.size();
+		LT.begin("meshlet_segments"); hipLaunchKernelGGL(k_meshlet_segments, dim3(nb), dim3(64), 0, st, D(pl.meshlet), D(pl.mlt_block_job), nb); LT.end();
+		LT.begin("meshlet_place"); hipLaunchKernelGGL(k_meshlet_place, dim3(nb), dim3(MLT_PLACE_THREADS), 0, st, D(pl.meshlet), D(pl.mlt_block_job), nb); LT.end();
+	}
 	const uint32_t ndq = (uint32_t)pl.dequant_block_job.v.size();
 	if(ndq) { LT.begin("dequantize"); hipLaunchKernelGGL(k_dequant, dim3(ndq), dim3(256), 0, st, D(pl.dequant), D(pl.dequant_block_job),
 		ndq); LT.end(); }
@@ -356,5 +368,7 @@ void Planner::account() {
 	b->decoded = true; b->planned_wide = wide;
 	b->quant_bound.assign(pl.quant_records, 0); b->quant_recs.clear();        // (the records: harvest)
 	if(pl.quant_records) { size_t r = 0; for(auto &P : b->blobs) for(const Binding &bd : P.bind) b->quant_bound[r++] = bd.buffer && bd.quantized; }
+	b->meshlet_bound.clear(); b->meshlet_recs.clear();                        // (the records: harvest)
+	if(pl.meshlet_records) for(auto &P : b->blobs) b->meshlet_bound.push_back(builds_meshlets(P) && !P.host_status);
 	b->dirty = false;
 }

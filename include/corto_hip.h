@@ -50,7 +50,9 @@ extern "C" {
                                      call and nothing else: the number stays 6); CRTHIP_BIND_QUANTIZED, crthip_quant_transform,
                                      crthip_batch_quant_transform, crthip_batch_bind_quant_transforms (a flag that was refused before and
                                      two new calls: the number stays 6); crthip_batch_bind_computed_tangents, crthip_tangent_model (two
-                                     new calls and nothing else: the number stays 6) */
+                                     new calls and nothing else: the number stays 6); crthip_meshlet, crthip_meshlet_counts,
+                                     crthip_meshlet_binding, crthip_meshlet_bound, crthip_batch_bind_meshlets, crthip_batch_meshlet_counts,
+                                     crthip_meshlet_model (new calls and their structs, nothing else: the number stays 6) */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -325,6 +327,57 @@ int crthip_batch_bind_computed_normals(crthip_batch *b, uint32_t i, void *buffer
  * crthip_last_error() names the blob.  Kernels tangent_blob (blobs of up to 2 304 vertices) and tangent_faces, tangent_vertex in
  * crthip_kernel_times.  Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host, the crt::Decoder facade or the veneers. */
 int crthip_batch_bind_computed_tangents(crthip_batch *b, uint32_t i, void *buffer, uint32_t format, uint32_t stride);
+
+/* Meshlets from the blob's decoded index, built on the GPU in the decode call (kernels meshlet_blob, meshlet_segments, meshlet_place in
+ * crthip_kernel_times; csrc/meshlet.h has the source the kernels and the test hook share).  Pure integer work on the index: the bytes are
+ * defined exactly, need no position, uv or float, and no vertex id is ever used as an address - any index content gives defined output,
+ * that of a blob whose topology failed included.
+ * Inputs: the blob's nface triples of vertex ids, read as uint32 whether the index is bound as uint32, as uint16 or not at all (then from
+ * scratch); the blob's group table (crthip_batch_groups); max_vertices 3..255; max_triangles 1..512; segment_faces 0 (= 4096) or 1..65536.
+ * Cuts: sort the set {nface} + {min(group_end[g], nface)}; with 0 in front, every stretch [s, e) between neighbouring values is cut further
+ *   at s + k*segment_faces, k >= 1, while that is below e.  A SEGMENT is a non-empty stretch between neighbouring cuts; no meshlet crosses a
+ *   cut.  So a group (a draw range) is a whole number of meshlets, segments are independent (what makes a big mesh parallel), and the
+ *   price is at most one under-filled meshlet a segment.
+ * Within a segment faces are taken in index order.  The state is an ordered list V (empty) and a count t (0).  For face f = (a, b, c):
+ *   1. d = the distinct ids among a, b, c that are not in V, in corner order;
+ *   2. if t + 1 > max_triangles or |V| + |d| > max_vertices: emit the meshlet, clear V and t, recompute d;
+ *   3. append d to V;   4. the face's three bytes are the positions of a, b, c in V;   5. t += 1.
+ *   At the segment's end, emit if t > 0.  A face that names a vertex twice references it once and repeats the local id; max_vertices >= 3
+ *   guarantees that a lone face fits.
+ * Emission: meshlets in face order over the whole blob.  Meshlet k is a crthip_meshlet with meshopt_Meshlet's field meanings:
+ *   vertex_offset = the sum of vertex_count of the earlier meshlets; triangle_offset = the sum of (3*triangle_count + 3) & ~3 of the earlier
+ *   meshlets, a 4-byte aligned BYTE offset into triangles; vertices[vertex_offset + j] = V[j], uint32 ids into the blob's vertex arrays;
+ *   triangles[triangle_offset + 3*i + c] = the local id of corner c of the meshlet's face i; the pad bytes are written as 0.
+ *   A crthip_meshlet_counts a blob holds the totals.  Nothing beyond `meshlets` records, `vertices` words and `triangle_bytes` bytes is touched.
+ * Capacity (derived): a meshlet that is not the last of its segment was closed by the triangle limit (t == max_triangles) or by the vertex
+ *   limit (|V| >= max_vertices - 2 as |d| <= 3, and |V| <= 3t, so t >= ceil((max_vertices - 2)/3)).  With tmin = min(max_triangles,
+ *   ceil((max_vertices - 2)/3)):  meshlets <= sum over segments of ceil(len/tmin);  vertices <= 3*nface;
+ *   triangle_bytes <= 3*nface + 3*(that meshlet bound).  crthip_meshlet_bound computes it; it is reached at (3, 1, 1). */
+typedef struct crthip_meshlet { uint32_t vertex_offset, triangle_offset, vertex_count, triangle_count; } crthip_meshlet;
+typedef struct crthip_meshlet_counts { uint32_t meshlets, vertices, triangle_bytes, segments; } crthip_meshlet_counts;
+typedef struct crthip_meshlet_binding {
+	crthip_meshlet *meshlets;          /* DEVICE, 16-byte aligned, room for meshlet_capacity records */
+	uint32_t *vertices;                /* DEVICE, 4-byte aligned, room for vertex_capacity words */
+	uint8_t *triangles;                /* DEVICE, 4-byte aligned, room for triangle_capacity bytes */
+	crthip_meshlet_counts *counts;     /* optional DEVICE copy of the blob's record for GPU-driven consumers: 16 bytes, 16-byte aligned; or NULL */
+	uint32_t meshlet_capacity, vertex_capacity, triangle_capacity;   /* records, words, bytes: each at least crthip_meshlet_bound's */
+	uint32_t max_vertices, max_triangles, segment_faces;
+} crthip_meshlet_binding;
+/* Host only, no device: the capacity bound above for an index of nface faces and a group table (group_end may be NULL when ngroups is 0;
+ * ends beyond nface and repeated ones are allowed).  out->segments is the exact number of segments.  CRTHIP_E_ARGUMENT: out NULL, group_end
+ * NULL with ngroups > 0, a parameter outside its range, or a bound beyond 32 bits. */
+int crthip_meshlet_bound(uint32_t nface, uint32_t ngroups, const uint32_t *group_end, uint32_t max_vertices, uint32_t max_triangles,
+                         uint32_t segment_faces, crthip_meshlet_counts *out);
+/* Blob i's meshlets go to m's buffers in the decode.  Call it AFTER crthip_batch_bind / _bind_all for blob i: a later bind of that blob
+ * drops it, as does crthip_batch_reset*; m == NULL removes it.  Independent of the computed-normals and tangent bindings.  Every error is
+ * returned here and nothing new can fail at decode time.  CRTHIP_E_ARGUMENT: b NULL or i out of range; a point cloud; a parameter outside
+ * the ranges above; a NULL or misaligned buffer (meshlets 16-byte aligned, vertices and triangles 4-byte aligned, counts 16-byte aligned
+ * when given); any capacity below crthip_meshlet_bound for that blob.  crthip_last_error() names the blob.  Blobs without a meshlet
+ * binding launch nothing new.  Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host, the crt::Decoder facade or the veneers. */
+int crthip_batch_bind_meshlets(crthip_batch *b, uint32_t i, const crthip_meshlet_binding *m);
+/* Blob i's totals.  Valid after crthip_batch_sync of a decode in which blob i had a meshlet binding: the kernels write the record into the
+ * batch's pinned status block, behind the quant records.  Otherwise CRTHIP_E_ARGUMENT. */
+int crthip_batch_meshlet_counts(const crthip_batch *b, uint32_t i, crthip_meshlet_counts *out);
 
 /* The record of attribute `attr` of blob i, bound with CRTHIP_BIND_QUANTIZED.  Valid after crthip_batch_sync of a decode: the kernels write
  * the records into the batch's pinned status block, beside the status words.  CRTHIP_E_ARGUMENT if that attribute was not bound
@@ -972,6 +1025,14 @@ int crthip_quant_out_model(const int32_t *values, uint32_t nvert, uint32_t N, ui
 int crthip_tangent_model(const int32_t *position, const int32_t *uv, const void *index, uint32_t index_u16, uint32_t nvert, uint32_t nface,
                          const void *normal, uint32_t normal_format, uint32_t normal_stride, void *out, uint32_t format, uint32_t stride,
                          int which, uint32_t seed);
+
+/* (test hook, no device needed)  crthip_batch_bind_meshlets on the host: csrc/meshlet.h, the kernels' source, in their partition.  index:
+ * nface*3 uint32, or uint16 with index_u16; group_end / ngroups: the group table; the three arrays and their capacities as in the binding
+ * (host memory); counts: the blob's record.  which 0: meshlet_blob (one workgroup, a wave a segment, a blob of one segment written in
+ * place; any number of segments is taken here); which 1: meshlet_segments / meshlet_place.  Segments, workgroups and the lanes of every
+ * step are visited in an order shuffled by `seed`.  The errors of the bind call and of crthip_meshlet_bound apply. */
+int crthip_meshlet_model(const void *index, uint32_t index_u16, uint32_t nface, uint32_t ngroups, const uint32_t *group_end,
+                         const crthip_meshlet_binding *m, crthip_meshlet_counts *counts, int which, uint32_t seed);
 
 #ifdef __cplusplus
 }
