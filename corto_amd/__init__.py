@@ -83,6 +83,18 @@ class MeshletBinding(C.Structure):
                 ("max_vertices", C.c_uint32), ("max_triangles", C.c_uint32), ("segment_faces", C.c_uint32)]
 
 
+class MeshletBounds(C.Structure):
+    """crthip_meshlet_bounds: a meshlet's box, sphere (grid units) and normal cone; 48 bytes"""
+    _fields_ = [("box_min", C.c_int32 * 3), ("box_max", C.c_int32 * 3), ("center", C.c_int32 * 3), ("radius", C.c_uint32),
+                ("cone_axis", C.c_int8 * 3), ("cone_cutoff", C.c_int8), ("reserved", C.c_uint32)]
+
+
+# ... and as a numpy record: what Batch.meshlet_bounds and meshlet_bounds_model return
+MESHLET_BOUNDS_DTYPE = np.dtype([("box_min", "<i4", 3), ("box_max", "<i4", 3), ("center", "<i4", 3), ("radius", "<u4"),
+                                 ("cone_axis", "i1", 3), ("cone_cutoff", "i1"), ("reserved", "<u4")])
+assert MESHLET_BOUNDS_DTYPE.itemsize == 48 == C.sizeof(MeshletBounds)
+
+
 class BatchStats(C.Structure):
     _fields_ = [("arena_bytes", C.c_uint64), ("output_bytes", C.c_uint64), ("tunstall_in", C.c_uint64),
                 ("tunstall_out", C.c_uint64), ("tunstall_tables", C.c_uint64), ("tunstall_streams", C.c_uint32),
@@ -267,6 +279,9 @@ def lib():
         L.crthip_tangent_model.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
                                            C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32]
         L.crthip_batch_bind_meshlets.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshletBinding)]
+        L.crthip_batch_bind_meshlet_bounds.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.crthip_meshlet_bounds_model.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MeshletCounts), C.c_void_p,
+                                                  C.c_uint32, C.c_uint32]
         L.crthip_batch_meshlet_counts.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshletCounts)]
         L.crthip_meshlet_bound.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(MeshletCounts)]
         L.crthip_meshlet_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(MeshletBinding), C.POINTER(MeshletCounts),
@@ -994,6 +1009,36 @@ def meshlet_model(index: np.ndarray, groups=(), max_vertices: int = 64, max_tria
     return cut_meshlets(m, v, t, counts) + (counts,)
 
 
+def meshlet_bounds_model(position: np.ndarray, index, meshlets: np.ndarray, vertices: np.ndarray, triangles: np.ndarray, counts, seed: int = 0,
+                         capacity=None, fill: int = 0xCD, raw: bool = False):
+    """crthip_meshlet_bounds_model: crthip_batch_bind_meshlet_bounds on the host in the kernel's partition (workgroups, waves and the lanes of
+    every step shuffled by seed).  position (nvert, 3) delta-decoded integers; meshlets, vertices, triangles, counts: a finished meshlet
+    build (meshlet_model's, or Batch.meshlets' with meshlet_counts; counts a MeshletCounts or a tuple).  index: the index the meshlets were
+    built from - they carry its faces, so it is not read (None is fine).  The records are made here at `capacity` (None: exactly the
+    counts) and filled with `fill` first.  Returns a MESHLET_BOUNDS_DTYPE array cut to the counts, or with raw the whole block as uint8."""
+    del index
+    pos = np.ascontiguousarray(position, dtype=np.int32).reshape(-1, 3)
+    m = np.ascontiguousarray(meshlets, dtype=np.uint32).reshape(-1, 4)
+    v = np.ascontiguousarray(vertices, dtype=np.uint32).reshape(-1)
+    t = np.ascontiguousarray(triangles, dtype=np.uint8).reshape(-1)
+    c = counts if isinstance(counts, MeshletCounts) else MeshletCounts(*[int(x) for x in counts])
+    if c.meshlets > len(m) or c.vertices > len(v) or c.triangle_bytes > len(t):
+        raise ValueError("meshlet_bounds_model: the counts are beyond the arrays")
+    maln = np.zeros(len(m) * 16 + 16, np.uint8)                  # (the records are read as 16-byte words)
+    mo = (-maln.ctypes.data) % 16
+    maln[mo:mo + len(m) * 16] = m.view(np.uint8).reshape(-1)
+    if capacity is None:
+        capacity = c.meshlets
+    braw = np.full(capacity * 48 + 16, fill, np.uint8)
+    bo = (-braw.ctypes.data) % 16
+    b = braw[bo:bo + capacity * 48]
+    _check(lib().crthip_meshlet_bounds_model(_np_ptr(pos) if len(pos) else None, len(pos), maln[mo:].ctypes.data, _np_ptr(v) if len(v) else None,
+                                             _np_ptr(t) if len(t) else None, C.byref(c), b.ctypes.data if capacity else None, capacity, seed))
+    if raw:
+        return b
+    return b[:c.meshlets * 48].view(MESHLET_BOUNDS_DTYPE).copy()
+
+
 def encode_splice_plan_model(meshes, kw=None, chunk_items=0):
     """crthip_encode_splice_plan_model: the device splice's plan of a batch on the host, in chunks of chunk_items meshes (0: one chunk) that
     continue the arena as the chunks of a batch beyond one device image do.  Returns (offsets, lens, stats dict, pieces): pieces an
@@ -1181,6 +1226,7 @@ class Batch:
         self._computed = []                          # (blob, pointer, format, stride): what rebind() applies again behind crthip_batch_bind_all
         self._tangents = []                          # ... and behind those, through crthip_batch_bind_computed_tangents
         self._meshlets = {}                          # blob -> (MeshletBinding, the tensors it points into): applied again by rebind() too
+        self._meshlet_bounds = {}                    # blob -> (pointer, capacity, the tensor or None): applied again behind those
         self._interleaved = None
 
     def __len__(self):
@@ -1225,7 +1271,7 @@ class Batch:
     # -- outputs -----------------------------------------------------------------------------------
     def allocate_outputs(self, normal_format=FMT_FLOAT, color_components: Optional[int] = None, index16=False,
                          only: Optional[set] = None, fill: Optional[int] = None, computed_normals=False, quantized=(),
-                         computed_tangents=False, tangent_format=FMT_FLOAT, meshlets=None):
+                         computed_tangents=False, tangent_format=FMT_FLOAT, meshlets=None, meshlet_bounds=False):
         """Allocate every output of every blob inside ONE device buffer (torch.uint8) and bind them.
         Returns a list (per blob) of dicts name -> torch tensor view.
         computed_normals: every mesh blob WITHOUT a normal attribute gets a "normal" tensor of normal_format all the same, bound
@@ -1236,7 +1282,11 @@ class Batch:
         here) and no stored attribute named "tangent" gets a "tangent" tensor (nvert, 4) of tangent_format, bound through
         crthip_batch_bind_computed_tangents (include/corto_hip.h: xyz and the handedness w).
         meshlets: (max_vertices, max_triangles, segment_faces) - every mesh blob gets its three meshlet arrays at crthip_meshlet_bound and a
-        device counts record, bound through crthip_batch_bind_meshlets; read them with meshlets(i) after sync()."""
+        device counts record, bound through crthip_batch_bind_meshlets; read them with meshlets(i) after sync().
+        meshlet_bounds: with meshlets=, every mesh blob also gets a crthip_meshlet_bounds array at the bound's meshlets, bound through
+        crthip_batch_bind_meshlet_bounds; read it with meshlet_bounds(i) after sync()."""
+        if meshlet_bounds and meshlets is None:
+            raise ValueError("allocate_outputs: meshlet_bounds needs meshlets=")
         import torch
         dev = torch.device("cuda", self.ctx.device)
         plan = []   # (blob, name, offset, nbytes, dtype, shape, binding_slot)
@@ -1284,7 +1334,8 @@ class Batch:
             for i, info in enumerate(self.infos):
                 if info.nface:
                     bd = meshlet_bound(info.nface, self.groups(i), *meshlets)
-                    mplan.append((i, bd, take(bd.meshlets * 16), take(bd.vertices * 4), take(bd.triangle_bytes), take(16)))
+                    mplan.append((i, bd, take(bd.meshlets * 16), take(bd.vertices * 4), take(bd.triangle_bytes), take(16),
+                                  take(bd.meshlets * 48) if meshlet_bounds else None))
         total = max(off, 256)
         buf = torch.empty(total, dtype=torch.uint8, device=dev) if fill is None else torch.full((total,), fill, dtype=torch.uint8, device=dev)
         _torch_ready(dev)                            # (the fill runs on torch's stream; the decode on the context's own)
@@ -1295,8 +1346,10 @@ class Batch:
         index_ptrs = (C.c_void_p * max(len(self), 1))()
         index_fmt = np.full(max(len(self), 1), FMT_UINT32, dtype=np.uint32)
         outs = [dict() for _ in self.infos]
-        self._meshlets = {}
-        for (i, bd, mo, vo, to, co) in mplan:
+        self._meshlets, self._meshlet_bounds = {}, {}
+        for (i, bd, mo, vo, to, co, bo) in mplan:
+            if bo is not None:
+                self._meshlet_bounds[i] = (base + bo, bd.meshlets, buf[bo:bo + bd.meshlets * 48])
             mb = MeshletBinding(base + mo, base + vo, base + to, base + co, bd.meshlets, bd.vertices, bd.triangle_bytes, *meshlets)
             self._meshlets[i] = (mb, (buf[mo:mo + bd.meshlets * 16], buf[vo:vo + bd.vertices * 4], buf[to:to + bd.triangle_bytes], buf[co:co + 16]))
         computed, tangents = [], []
@@ -1370,7 +1423,7 @@ class Batch:
         self._keep = (buf, binds, index_ptrs, index_fmt)
         self._computed = []
         self._tangents = []
-        self._meshlets = {}
+        self._meshlets, self._meshlet_bounds = {}, {}
         self._interleaved = metas
         self.outputs = [dict() for _ in self.infos]
         self.rebind()
@@ -1418,6 +1471,8 @@ class Batch:
             _check(lib().crthip_batch_bind_computed_tangents(self.handle, i, C.c_void_p(ptr), fmt, stride))
         for i, (mb, _) in self._meshlets.items():              # (... and its meshlets)
             _check(lib().crthip_batch_bind_meshlets(self.handle, i, C.byref(mb)))
+        for i, (ptr, cap, _) in self._meshlet_bounds.items():   # (... and their bounds)
+            _check(lib().crthip_batch_bind_meshlet_bounds(self.handle, i, C.c_void_p(ptr), cap))
 
     def bind(self, i: int, bindings: Sequence[AttrBinding], index_ptr: Optional[int] = None, index_format=FMT_UINT32):
         arr = (AttrBinding * max(len(bindings), 1))(*bindings)
@@ -1440,10 +1495,30 @@ class Batch:
         tuple (meshlets, vertices, triangles, counts or None) makes meshlets(i) work."""
         if binding is None:
             self._meshlets.pop(i, None)
+            self._meshlet_bounds.pop(i, None)
             _check(lib().crthip_batch_bind_meshlets(self.handle, i, None))
             return
+        self._meshlet_bounds.pop(i, None)                     # (every meshlet binding call drops the blob's bounds, a refused one too)
         _check(lib().crthip_batch_bind_meshlets(self.handle, i, C.byref(binding)))
         self._meshlets[i] = (binding, keep)
+
+    def bind_meshlet_bounds(self, i: int, ptr: Optional[int], capacity: int = 0, keep=None):
+        """crthip_batch_bind_meshlet_bounds: blob i's meshlet bounds go to `capacity` records at the 16-byte aligned device pointer `ptr`
+        (capacity at least meshlet_bound's meshlets).  After bind_meshlets() of that blob; whatever drops that binding drops this one; ptr None
+        or 0 removes it.  keep: the device tensor that owns the records - it makes meshlet_bounds(i) work."""
+        if not ptr:
+            self._meshlet_bounds.pop(i, None)
+            _check(lib().crthip_batch_bind_meshlet_bounds(self.handle, i, None, 0))
+            return
+        _check(lib().crthip_batch_bind_meshlet_bounds(self.handle, i, C.c_void_p(ptr), capacity))
+        self._meshlet_bounds[i] = (ptr, capacity, keep)
+
+    def meshlet_bounds(self, i: int) -> np.ndarray:
+        """Blob i's meshlet bounds on the host, cut to the counts: a MESHLET_BOUNDS_DTYPE array.  After sync(); for bindings made by
+        allocate_outputs(meshlet_bounds=True) or bind_meshlet_bounds(keep=)."""
+        c = self.meshlet_counts(i)
+        _, _, keep = self._meshlet_bounds[i]
+        return keep.cpu().numpy().view(np.uint8).reshape(-1)[:c.meshlets * 48].view(MESHLET_BOUNDS_DTYPE).copy()
 
     def meshlet_counts(self, i: int) -> MeshletCounts:
         """crthip_batch_meshlet_counts: blob i's totals (meshlets, vertex words, triangle bytes, segments); after sync()"""

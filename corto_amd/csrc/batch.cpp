@@ -252,7 +252,7 @@ static crthip_ctx::Half &begin_fill(crthip_ctx *ctx, crthip_batch *b) {
 static uint64_t adopt_blob(BlobPlan &P, uint64_t arena_off, uint32_t len, crthip_batch_stats &stats) {
 	P.arena_off = arena_off; P.len = len;
 	P.bind.assign(P.L.h.attrs.size(), Binding{});
-	P.index = nullptr; P.index_u16 = 0; P.host_status = 0; P.computed = Binding{}; P.tangent = Binding{}; P.meshlets = crthip_meshlet_binding{};
+	P.index = nullptr; P.index_u16 = 0; P.host_status = 0; P.computed = Binding{}; P.tangent = Binding{}; P.meshlets = crthip_meshlet_binding{}; P.meshlet_bounds = nullptr;
 	P.dbg_clers = P.dbg_pred = ~0ull; P.dbg_nclers = 0; P.clers_in_arena = false;
 	stats.total_nvert += P.L.h.nvert; stats.total_nface += P.L.h.nface;
 	if(P.L.h.nface) { stats.clers_symbols += P.L.clers.size; stats.split_bytes += (uint64_t)P.L.split.nwords*4; }
@@ -562,6 +562,7 @@ extern "C" int crthip_batch_bind(crthip_batch *b, uint32_t i, const crthip_attr_
 	P.computed = Binding{};                                                 // (crthip_batch_bind_computed_normals comes after the bind)
 	P.tangent = Binding{};                                                  // (... and crthip_batch_bind_computed_tangents after both)
 	P.meshlets = crthip_meshlet_binding{};                                  // (... and crthip_batch_bind_meshlets)
+	P.meshlet_bounds = nullptr;                                             // (... and crthip_batch_bind_meshlet_bounds behind that)
 	b->dirty = true;
 	return CRTHIP_OK;
 }
@@ -631,12 +632,35 @@ extern "C" int crthip_batch_bind_meshlets(crthip_batch *b, uint32_t i, const crt
 	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_meshlets: no such blob");
 	BlobPlan &P = b->blobs[i];
 	const std::string who = " (blob " + std::to_string(i) + ")";
+	P.meshlet_bounds = nullptr;                                             // the bounds' arrays and capacity change here: they are bound behind this call
 	if(!m) { P.meshlets = crthip_meshlet_binding{}; b->dirty = true; return CRTHIP_OK; }
 	if(P.L.h.nface == 0) return fail(CRTHIP_E_ARGUMENT, "meshlets need faces: a point cloud has none" + who);
 	crthip_meshlet_counts bound;
 	const bool ok = mlt_plan(P.L.h.nface, (uint32_t)P.L.group_end.size(), P.L.group_end.data(), m->max_vertices, m->max_triangles, m->segment_faces, nullptr, bound);
 	if(const char *why = meshlet_binding_error(m, ok, bound)) return fail(CRTHIP_E_ARGUMENT, why + who);
 	P.meshlets = *m;
+	b->dirty = true;
+	return CRTHIP_OK;
+}
+
+// A box, a sphere and a normal cone a meshlet (corto_hip.h has the record): every check is made here, against the meshlet binding of this blob
+extern "C" int crthip_batch_bind_meshlet_bounds(crthip_batch *b, uint32_t i, crthip_meshlet_bounds *bounds, uint32_t capacity) {
+	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_meshlet_bounds: no such blob");
+	BlobPlan &P = b->blobs[i];
+	const std::string who = " (blob " + std::to_string(i) + ")";
+	if(!bounds) { P.meshlet_bounds = nullptr; b->dirty = true; return CRTHIP_OK; }
+	if(!builds_meshlets(P)) return fail(CRTHIP_E_ARGUMENT, "meshlet bounds need a meshlet binding: crthip_batch_bind_meshlets comes first" + who);
+	if((uintptr_t)bounds % 16) return fail(CRTHIP_E_ARGUMENT, "meshlet bounds: the records are 16-byte aligned" + who);
+	crthip_meshlet_counts bound;
+	const crthip_meshlet_binding &m = P.meshlets;
+	if(!mlt_plan(P.L.h.nface, (uint32_t)P.L.group_end.size(), P.L.group_end.data(), m.max_vertices, m.max_triangles, m.segment_faces, nullptr, bound) ||
+		capacity < bound.meshlets) return fail(CRTHIP_E_ARGUMENT, "meshlet bounds: capacity is below crthip_meshlet_bound's meshlets" + who);
+	// (what computed tangents ask of the position)
+	int pos_k = -1;
+	for(size_t k = 0; k < P.bind.size(); k++) if(P.L.h.attrs[k].name == "position") pos_k = (int)k;
+	if(pos_k < 0 || P.L.h.attrs[pos_k].codec != CRTHIP_CODEC_GENERIC || P.L.h.attrs[pos_k].N != 3 || !P.bind[pos_k].buffer || P.bind[pos_k].stream_values)
+		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "meshlet bounds need a bound three-component \"position\" (bind the blob first)" + who);
+	P.meshlet_bounds = bounds;
 	b->dirty = true;
 	return CRTHIP_OK;
 }

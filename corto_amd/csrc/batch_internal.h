@@ -25,6 +25,7 @@
 #include "quant_out.h"
 #include "tangent.h"
 #include "meshlet.h"
+#include "meshlet_bounds.h"
 
 using namespace corto_hip;
 
@@ -91,10 +92,11 @@ struct BlobScratch {
 	uint32_t front_cap = 0, aux_groups = 0;
 	uint64_t tan_acc = ~0ull;                               // computed tangents (BlobPlan::tangent) of a blob beyond TANGENT_BLOB_MAX: 6 x int64 a vertex, inside the zeroed region
 	uint64_t mlt = ~0ull;                                   // meshlets (BlobPlan::meshlets) of a blob of more than one segment: mlt_scratch_layout's block
+	uint64_t mlt_counts = ~0ull;                            // meshlet bounds (BlobPlan::meshlet_bounds) over a meshlet binding without a device counts record: 16 bytes for one
 	uint64_t cn_facen = ~0ull;                              // computed normals (BlobPlan::computed) by the fused kernel without its face normals in LDS: AttrScratch::facen's counterpart
 	std::vector<AttrScratch> attr;
 	size_t nattr = 0;                                       // attr[0..nattr) are this decode's (the vector only grows)
-	void reset() { clers = pred = front_a = front_b = order = delayed = faces = progress = cn_facen = tan_acc = mlt = ~0ull; front_cap = 0; aux_groups = 0; nattr = 0; }
+	void reset() { clers = pred = front_a = front_b = order = delayed = faces = progress = cn_facen = tan_acc = mlt = mlt_counts = ~0ull; front_cap = 0; aux_groups = 0; nattr = 0; }
 	void set_attrs(size_t n) { if(attr.size() < n) attr.resize(n); for(size_t k = nattr; k < n; k++) attr[k].reset();
 		if(n > nattr) nattr = n; }
 };
@@ -126,6 +128,8 @@ struct Plan {
 	// crthip_batch_bind_meshlets: blobs of up to MESHLET_BLOB_SEGS segments by id (k_meshlet_blob, meshlet_waves the most segments among them), the
 	// others a block a segment (k_meshlet_segments, k_meshlet_place); the segment tables are in aux_u32
 	HostArr<MeshletJob> meshlet; HostArr<uint32_t> meshlet_blob_ids, mlt_block_job; uint32_t meshlet_waves = 0;
+	// crthip_batch_bind_meshlet_bounds: (capacity + 3)/4 blocks a blob (k_meshlet_bounds)
+	HostArr<MeshletBoundsJob> meshlet_bounds; HostArr<uint32_t> mlb_block_job;
 	bool meshlet_records = false;                           // a crthip_meshlet_counts a blob behind the quant records: a batch with a meshlet binding
 	uint32_t quant_records = 0;                             // records behind the status words: sum(nattr) of a batch with a quantised binding, else 0
 	// scratch regions (offsets)
@@ -146,7 +150,7 @@ struct Plan {
 		f(delta); f(delta_groups); f(cloud); f(cloud_chunk_job); f(normal); f(nv_block_job); f(nv_block_first); f(nf_block_job); f(nf_block_first);
 		f(normal_fused_ids); f(normal_computed_ids); f(dequant); f(dequant_block_job); f(quant); f(quant_blob_ids); f(quant_block_job);
 		f(tangent); f(tangent_blob_ids); f(tan_fblock_job); f(tan_vblock_job);
-		f(meshlet); f(meshlet_blob_ids); f(mlt_block_job);
+		f(meshlet); f(meshlet_blob_ids); f(mlt_block_job); f(meshlet_bounds); f(mlb_block_job);
 	}
 	void reset() {                                          // keep every vector's capacity
 		each_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
@@ -236,6 +240,7 @@ struct BlobPlan {
 	Binding computed;          // crthip_batch_bind_computed_normals: where the normals of a blob that stores (or binds) none go; dropped by every bind / reset
 	Binding tangent;           // crthip_batch_bind_computed_tangents: where the blob's tangents go (out_components 4); dropped by every bind, computed-normals call and reset
 	crthip_meshlet_binding meshlets{};   // crthip_batch_bind_meshlets: meshlets.meshlets != null - where the blob's meshlets go; dropped by every bind and reset
+	crthip_meshlet_bounds *meshlet_bounds = nullptr;   // crthip_batch_bind_meshlet_bounds: a record a meshlet; dropped with the meshlet binding and by every call that sets it
 	int32_t host_status = 0;   // set by the planner (e.g. unsupported format), overrides device status
 	// debug handles (scratch offsets valid after decode)
 	uint64_t dbg_clers = ~0ull, dbg_pred = ~0ull; uint32_t dbg_nclers = 0;
@@ -320,6 +325,7 @@ static inline bool tangent_in_blob(uint32_t nvert) { return nvert <= TANGENT_BLO
 // k_meshlet_segments / k_meshlet_place, a workgroup a segment
 constexpr uint32_t MESHLET_BLOB_SEGS = 4;
 static inline bool builds_meshlets(const BlobPlan &P) { return P.meshlets.meshlets && P.L.h.nface > 0; }
+static inline bool bounds_meshlets(const BlobPlan &P) { return P.meshlet_bounds && builds_meshlets(P); }
 namespace corto_hip { const char *meshlet_binding_error(const crthip_meshlet_binding *m, bool have_bound, const crthip_meshlet_counts &bound); }
 
 struct Launch {

@@ -213,10 +213,22 @@ struct MeshletJob {
 	uint8_t faces_u16, pad[7];
 };
 
+// a blob bound with crthip_batch_bind_meshlet_bounds (k_meshlet_bounds.hip, meshlet_bounds.h): the integer positions and the meshlet binding's final
+// arrays -> a record a meshlet.  The grid is sized by `capacity`, the bound; the blob's count is read on the device
+struct MeshletBoundsJob {
+	const int32_t *position;       // nvert x 3 delta-decoded integers, packed: the caller's FLOAT buffer in front of k_dequant, or scratch
+	const void *meshlets, *vertices, *triangles;   // the meshlet binding's arrays, final behind the meshlet kernels
+	const void *counts;            // the blob's crthip_meshlet_counts in DEVICE memory: MeshletJob::rec_dev
+	void *out;                     // crthip_meshlet_bounds records
+	uint32_t nvert, capacity;      // capacity: crthip_meshlet_bound's .meshlets (the records the caller's array has at least)
+	uint32_t block0;               // first block of this job in the block -> job map
+	uint32_t pad;
+};
+
 // the layout the kernels read, pinned (TopoJob's size is performance-critical: TOPO_OPT_PROGRESS above)
 static_assert(sizeof(TunStream) == 64 && sizeof(FillJob) == 16 && sizeof(TopoJob) == 136 && sizeof(UnpackJob) == 56 && sizeof(DeltaJob) == 96 &&
               sizeof(CloudJob) == 24 && sizeof(NormalJob) == 104 && sizeof(DequantJob) == 64 && sizeof(QuantOutJob) == 72 && sizeof(TangentJob) == 80 &&
-              sizeof(MeshletJob) == 104, "decode job layout");
+              sizeof(MeshletJob) == 104 && sizeof(MeshletBoundsJob) == 64, "decode job layout");
 static_assert(offsetof(TopoJob, opts) == 116 && offsetof(UnpackJob, out_kind) == 51 && offsetof(NormalJob, faces_u16) == 58, "decode job layout");
 static_assert(offsetof(DeltaJob, in_i16) == 34 && offsetof(DeltaJob, wide) == 35 && offsetof(DeltaJob, rounds) == 88 &&
               offsetof(DeltaJob, status_back) == 92, "decode job layout");

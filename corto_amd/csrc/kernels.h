@@ -65,6 +65,10 @@ __global__ void k_meshlet_blob(const MeshletJob *jobs, const uint32_t *job_ids, 
 __global__ void k_meshlet_segments(const MeshletJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 __global__ void k_meshlet_place(const MeshletJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 
+// k_meshlet_bounds.hip (crthip_batch_bind_meshlet_bounds; meshlet_bounds.h has the arithmetic): a wave a meshlet, four waves a workgroup, from a
+// block -> job map with (capacity + 3)/4 blocks a job; waves at or past the blob's count on the device return
+__global__ void k_meshlet_bounds(const MeshletBoundsJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+
 // k_mesh.hip
 __global__ void k_topology(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);
 __global__ void k_topology_lds(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);

@@ -144,6 +144,8 @@ int Planner::jobs() {
 		// computed tangents read the integer positions AND the integer uvs, behind every normal kernel: neither K-DELTA nor the fused normal
 		// kernel may turn them into floats on the way - both fall to k_dequant, which runs behind the tangent kernels
 		const bool tangents = computes_tangents(P);
+		// ... and so do meshlet bounds, behind the meshlet kernels: the integer positions last until k_dequant
+		const bool bounds = bounds_meshlets(P);
 		// who turns the integer positions into floats: estimated normals read them as integers after K-DELTA, so the fused normal
 		// kernel does it as their last reader (pos_by_normal), the separate normal kernels leave it to k_dequant behind them, and
 		// without such normals K-DELTA does it on the way out of LDS like for every other attribute
@@ -154,8 +156,8 @@ int Planner::jobs() {
 				if(mesh && L.h.attrs[k].codec == CRTHIP_CODEC_NORMAL && P.bind[k].buffer && (L.attrs[k].normal_prediction == 1 ||
 					L.attrs[k].normal_prediction == 2)) readers++;
 			if(computes_normals(P)) readers++;                        // computed normals read the integer positions as a stored estimate does
-			pos_ints_needed = readers > 0 || tangents;
-			pos_by_normal = !tangents && readers == 1 && normal_fused(nvert, nface) && pos_k >= 0 && P.bind[pos_k].format == CRTHIP_FMT_FLOAT;
+			pos_ints_needed = readers > 0 || tangents || bounds;
+			pos_by_normal = !tangents && !bounds && readers == 1 && normal_fused(nvert, nface) && pos_k >= 0 && P.bind[pos_k].format == CRTHIP_FMT_FLOAT;
 		}
 
 		for(size_t k = 0; k < L.attrs.size(); k++) {
@@ -412,6 +414,22 @@ int Planner::jobs() {
 			} else {
 				m.block0 = (uint32_t)pl.mlt_block_job.v.size();
 				for(uint32_t c = 0; c < bound.segments; c++) pl.mlt_block_job.v.push_back((uint32_t)pl.meshlet.v.size());
+			}
+			// meshlet bounds: crthip_batch_bind_meshlet_bounds.  The integer positions as the tangents take them, the arrays above, and the blob's counts
+			// in DEVICE memory: the binding's own copy, or one in scratch that the meshlet kernels write in its place.  (The bind call checked all of it)
+			if(bounds) {
+				const bool pos_ok = pos_k >= 0 && L.h.attrs[pos_k].codec == CRTHIP_CODEC_GENERIC && L.h.attrs[pos_k].N == 3 && P.bind[pos_k].buffer && !P.bind[pos_k].stream_values;
+				if(!pos_ok || (!mb.counts && S.mlt_counts == ~0ull)) P.host_status = pos_ok ? CRTHIP_E_ARGUMENT : CRTHIP_E_NORMAL_NEEDS_POSITION;
+			}
+			if(bounds && !P.host_status) {
+				if(!mb.counts) m.rec_dev = SP(S.mlt_counts);
+				MeshletBoundsJob q{};
+				q.position = generic_in_scratch(P.bind[pos_k]) ? (const int32_t *)SP(S.attr[pos_k].vals) : (const int32_t *)P.bind[pos_k].buffer;
+				q.meshlets = mb.meshlets; q.vertices = mb.vertices; q.triangles = mb.triangles; q.counts = m.rec_dev; q.out = P.meshlet_bounds;
+				q.nvert = nvert; q.capacity = bound.meshlets;
+				q.block0 = (uint32_t)pl.mlb_block_job.v.size();
+				for(uint32_t c = 0; c < (bound.meshlets + MB_WAVES - 1)/MB_WAVES; c++) pl.mlb_block_job.v.push_back((uint32_t)pl.meshlet_bounds.v.size());
+				pl.meshlet_bounds.v.push_back(q);
 			}
 			pl.meshlet.v.push_back(m);
 		}

@@ -28,7 +28,8 @@ int Planner::upload() {
 	for(auto &q : pl.dequant.v) { resolve(q.buffer); resolve(q.src); }
 	for(auto &q : pl.quant.v) { resolve(q.values); resolve(q.range); }
 	for(auto &t : pl.tangent.v) { resolve(t.position); resolve(t.uv); resolve(t.faces); resolve(t.acc); }
-	for(auto &m : pl.meshlet.v) { m.segs = base + pl.aux_u32.dev_off + (uintptr_t)m.segs; resolve(m.faces); resolve(m.scratch); }
+	for(auto &q : pl.meshlet_bounds.v) { resolve(q.position); resolve(q.counts); }
+	for(auto &m : pl.meshlet.v) { m.segs = base + pl.aux_u32.dev_off + (uintptr_t)m.segs; resolve(m.faces); resolve(m.scratch); resolve(m.rec_dev); }
 
 	// host image -> device (one copy)
 	stage = (uint8_t *)set.staging.p;
@@ -311,6 +312,11 @@ int Planner::launch(uint32_t phases, const Carry *carry) {
 		const uint32_t nb = (uint32_t)pl.mlt_block_job.v.size();
 		LT.begin("meshlet_segments"); hipLaunchKernelGGL(k_meshlet_segments, dim3(nb), dim3(64), 0, st, D(pl.meshlet), D(pl.mlt_block_job), nb); LT.end();
 		LT.begin("meshlet_place"); hipLaunchKernelGGL(k_meshlet_place, dim3(nb), dim3(MLT_PLACE_THREADS), 0, st, D(pl.meshlet), D(pl.mlt_block_job), nb); LT.end();
+	}
+	// meshlet bounds: the meshlets are final, the positions still integers
+	if(!pl.mlb_block_job.v.empty()) {
+		const uint32_t nb = (uint32_t)pl.mlb_block_job.v.size();
+		LT.begin("meshlet_bounds"); hipLaunchKernelGGL(k_meshlet_bounds, dim3(nb), dim3(64*MB_WAVES), 0, st, D(pl.meshlet_bounds), D(pl.mlb_block_job), nb); LT.end();
 	}
 	const uint32_t ndq = (uint32_t)pl.dequant_block_job.v.size();
 	if(ndq) { LT.begin("dequantize"); hipLaunchKernelGGL(k_dequant, dim3(ndq), dim3(256), 0, st, D(pl.dequant), D(pl.dequant_block_job),

@@ -52,7 +52,9 @@ extern "C" {
                                      two new calls: the number stays 6); crthip_batch_bind_computed_tangents, crthip_tangent_model (two
                                      new calls and nothing else: the number stays 6); crthip_meshlet, crthip_meshlet_counts,
                                      crthip_meshlet_binding, crthip_meshlet_bound, crthip_batch_bind_meshlets, crthip_batch_meshlet_counts,
-                                     crthip_meshlet_model (new calls and their structs, nothing else: the number stays 6) */
+                                     crthip_meshlet_model (new calls and their structs, nothing else: the number stays 6);
+                                     crthip_meshlet_bounds, crthip_batch_bind_meshlet_bounds, crthip_meshlet_bounds_model (a struct and two
+                                     new calls, nothing else: the number stays 6) */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -378,6 +380,56 @@ int crthip_batch_bind_meshlets(crthip_batch *b, uint32_t i, const crthip_meshlet
 /* Blob i's totals.  Valid after crthip_batch_sync of a decode in which blob i had a meshlet binding: the kernels write the record into the
  * batch's pinned status block, behind the quant records.  Otherwise CRTHIP_E_ARGUMENT. */
 int crthip_batch_meshlet_counts(const crthip_batch *b, uint32_t i, crthip_meshlet_counts *out);
+
+/* Culling data a meshlet - a bounding box, a bounding sphere and a normal cone, what meshopt_computeMeshletBounds gives - computed on the GPU
+ * in the decode call from the blob's delta-decoded INTEGER positions and its final meshlet arrays (kernel meshlet_bounds in
+ * crthip_kernel_times; csrc/meshlet_bounds.h has the source the kernel and the test hook share).  A decoded position is int * q with the one
+ * positive scalar q of the position attribute, so box, centre and radius in grid units scale to world units by q - the world sphere has the
+ * centre (float)center*q and the radius (float)radius*q - and directions are the same in both spaces.  The record is defined to the byte.
+ * Record k belongs to meshlet k of the blob's final `meshlets` array; exactly counts.meshlets records are written and nothing behind them
+ * is touched.  V is the meshlet's vertex list, p[v] the integer position of vertex v.  A vertex id >= nvert is ABSENT: it is never used as an
+ * address (such ids exist only in blobs whose topology failed and in the hook's synthetic inputs).  A meshlet without a present vertex gets
+ * a record that is all zero except cone_cutoff = 127.
+ * Box: box_min[c] / box_max[c] are the minimum and maximum of p[v][c] over the present v in V.
+ * Sphere: span[c] = (uint32)box_max[c] - (uint32)box_min[c]; center[c] = (int32)((uint32)box_min[c] + (span[c] >> 1));
+ *   r2 = the maximum over the present v of the sum over c of ((int64)p[v][c] - center[c])^2, computed on uint64 modulo 2^64 (exact whenever
+ *   every span is below 2^31; defined but meaningless beyond); radius = the smallest r in [0, 2^32 - 1] with r*r >= r2 as uint64, or
+ *   2^32 - 1 if there is none.  The sphere holds every present vertex.
+ * Cone: a face (a, b, c) of the meshlet (global ids through V) is a CONE FACE if all three ids are present and
+ *   N = cross(p[b] - p[a], p[c] - p[a]) != 0, with the differences widened to 64 bits and products and sums on uint64 modulo 2^64 (exact
+ *   whenever every coordinate difference is below 2^31 in magnitude).  Step 1 is integer work, the others float32, every operation rounded
+ *   on its own:
+ *   1. S = the sum of N over the cone faces, modulo 2^64 (associative: no order changes it);
+ *   2. kS = max(0, bitlength(max_c |S[c]|) - 24), where |INT64_MIN| is 2^63;   3. s[c] = (float)(sign(S[c]) * (|S[c]| >> kS));
+ *   4. L = sqrtf((s0*s0 + s1*s1) + s2*s2);
+ *   5. without a cone face, or if !(L > 0): cone_axis = (0, 0, 0), cone_cutoff = 127, done;
+ *   6. t = (s[c] / L) * 127.0f; cone_axis[c] = (int8)(int32)(t + (t < 0 ? -0.5f : 0.5f)), the conversion truncating;
+ *   7. with A[c] = (float)cone_axis[c], the STORED axis (so the cutoff accounts for its quantisation), for every cone face: n[c] = N scaled
+ *      by its own shift kN as in 2-3; d = ((A0*n0 + A1*n1) + A2*n2) / (sqrtf((A0*A0 + A1*A1) + A2*A2) * sqrtf((n0*n0 + n1*n1) + n2*n2));
+ *   8. m = the minimum of d over the cone faces (every d is finite; a float minimum is exact in any order);
+ *   9. if !(m > 0.1f): cone_cutoff = 127; else w = 1.0f - m*m, taken as 0 if !(w > 0) (m can round to a step above 1), and
+ *      cone_cutoff = min(127, (int32)(sqrtf(w) * 127.0f) + 2).  Truncation plus 2 leaves a margin between 1/127 and 2/127 above the true
+ *      value, orders of magnitude above the float error of step 7: the cone is conservative by construction.
+ * Meaning: every non-degenerate face normal lies within the angle acos(m) of the stored axis.  With v the unit direction from the eye to
+ *   the meshlet, all its faces are back-facing if dot(normalize(cone_axis), v) >= cone_cutoff/127; for perspective this is meshoptimizer's
+ *   sphere form, dot(center - eye, axis) >= cutoff*|center - eye| + radius with the normalised axis, cutoff = cone_cutoff/127 and the world
+ *   sphere above.  cone_cutoff 127 means "do not cull".  No cone apex is given. */
+typedef struct crthip_meshlet_bounds {      /* 48 bytes; arrays of them are 16-byte aligned */
+	int32_t  box_min[3], box_max[3];        /* grid units */
+	int32_t  center[3];  uint32_t radius;   /* grid units: a sphere that holds every vertex */
+	int8_t   cone_axis[3]; int8_t cone_cutoff;
+	uint32_t reserved;                      /* written as 0 */
+} crthip_meshlet_bounds;
+/* Blob i's records go to `bounds` (DEVICE, 16-byte aligned, room for `capacity` records) in the decode.  Call it AFTER
+ * crthip_batch_bind_meshlets for blob i: whatever drops the meshlet binding drops this one too - a later crthip_batch_bind of that blob,
+ * crthip_batch_bind_meshlets(b, i, NULL), a new meshlet binding, crthip_batch_reset* - and bounds == NULL removes it.  Every error is
+ * returned here and nothing new can fail at decode time; crthip_last_error() names the blob.  CRTHIP_E_ARGUMENT: b NULL or i out of range;
+ * no meshlet binding on blob i; bounds not 16-byte aligned; capacity below crthip_meshlet_bound's .meshlets for this blob and the meshlet
+ * binding's parameters.  CRTHIP_E_NORMAL_NEEDS_POSITION: "position" missing, not generic with 3 components, unbound, or bound with
+ * CRTHIP_BIND_STREAM_VALUES (the rule of crthip_batch_bind_computed_tangents).  A packed FLOAT position is read in place in front of its
+ * dequantisation, every other binding from scratch; the position's own output is unchanged.  Blobs without the binding launch nothing new.
+ * Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host, the crt::Decoder facade or the veneers. */
+int crthip_batch_bind_meshlet_bounds(crthip_batch *b, uint32_t i, crthip_meshlet_bounds *bounds, uint32_t capacity);
 
 /* The record of attribute `attr` of blob i, bound with CRTHIP_BIND_QUANTIZED.  Valid after crthip_batch_sync of a decode: the kernels write
  * the records into the batch's pinned status block, beside the status words.  CRTHIP_E_ARGUMENT if that attribute was not bound
@@ -1033,6 +1085,17 @@ int crthip_tangent_model(const int32_t *position, const int32_t *uv, const void 
  * step are visited in an order shuffled by `seed`.  The errors of the bind call and of crthip_meshlet_bound apply. */
 int crthip_meshlet_model(const void *index, uint32_t index_u16, uint32_t nface, uint32_t ngroups, const uint32_t *group_end,
                          const crthip_meshlet_binding *m, crthip_meshlet_counts *counts, int which, uint32_t seed);
+
+/* (test hook, no device needed)  crthip_batch_bind_meshlet_bounds on the host: csrc/meshlet_bounds.h, the kernel's source, in its partition.
+ * position: nvert*3 delta-decoded integers (may be NULL when nvert is 0); meshlets, vertices, triangles, counts: the host arrays of a
+ * finished meshlet build (crthip_meshlet_model's), in which vertex ids may be >= nvert; bounds: host memory, 16-byte aligned, room for
+ * `capacity` records, of which counts->meshlets are written.  The grid is sized by `capacity` as the kernel's is by the bound; workgroups,
+ * their waves and the lanes of every step are visited in an order shuffled by `seed`.  CRTHIP_E_ARGUMENT: a NULL or misaligned array,
+ * capacity below counts->meshlets, a meshlet of more than 255 vertices or 512 triangles or one that reaches outside the counts, or a local
+ * id that is not below its meshlet's vertex_count. */
+int crthip_meshlet_bounds_model(const int32_t *position, uint32_t nvert, const crthip_meshlet *meshlets, const uint32_t *vertices,
+                                const uint8_t *triangles, const crthip_meshlet_counts *counts, crthip_meshlet_bounds *bounds, uint32_t capacity,
+                                uint32_t seed);
 
 #ifdef __cplusplus
 }
