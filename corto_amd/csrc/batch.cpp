@@ -66,14 +66,14 @@ int harvest(crthip_ctx *ctx) {
 	if(set.done_covers_seq == set.upload_seq) set.arena_upload_pending = false;
 	const int32_t *hs = (const int32_t *)set.status_host.p;
 	const size_t n = b->blobs.size();
-	const StatusWords W{n};
+	const StatusWords W{n, b->quant_bound.size(), !b->meshlet_bound.empty()};
 	for(size_t i = 0; i < n; i++) b->status[i] = b->blobs[i].host_status ? b->blobs[i].host_status : hs[W.status(i)];
 	if(!b->quant_bound.empty()) {                                         // CRTHIP_BIND_QUANTIZED: the records the kernels wrote behind the status words
 		const crthip_quant_transform *rec = (const crthip_quant_transform *)((const uint8_t *)hs + W.records());
 		b->quant_recs.assign(rec, rec + b->quant_bound.size());
 	}
 	if(!b->meshlet_bound.empty()) {                                       // crthip_batch_bind_meshlets: a record a blob behind those
-		const crthip_meshlet_counts *rec = (const crthip_meshlet_counts *)((const uint8_t *)hs + W.meshlet_records(b->quant_bound.size()));
+		const crthip_meshlet_counts *rec = (const crthip_meshlet_counts *)((const uint8_t *)hs + W.meshlet_record(0));
 		b->meshlet_recs.assign(rec, rec + n);
 	}
 	b->stats.topology_fallbacks = 0; b->stats.delta_redone = 0; b->stats.delta_walked = 0;
@@ -252,7 +252,7 @@ static crthip_ctx::Half &begin_fill(crthip_ctx *ctx, crthip_batch *b) {
 static uint64_t adopt_blob(BlobPlan &P, uint64_t arena_off, uint32_t len, crthip_batch_stats &stats) {
 	P.arena_off = arena_off; P.len = len;
 	P.bind.assign(P.L.h.attrs.size(), Binding{});
-	P.index = nullptr; P.index_u16 = 0; P.host_status = 0; P.computed = Binding{}; P.tangent = Binding{}; P.meshlets = crthip_meshlet_binding{}; P.meshlet_bounds = nullptr;
+	P.index = nullptr; P.index_u16 = 0; P.host_status = 0; P.derived.clear();
 	P.dbg_clers = P.dbg_pred = ~0ull; P.dbg_nclers = 0; P.clers_in_arena = false;
 	stats.total_nvert += P.L.h.nvert; stats.total_nface += P.L.h.nface;
 	if(P.L.h.nface) { stats.clers_symbols += P.L.clers.size; stats.split_bytes += (uint64_t)P.L.split.nwords*4; }
@@ -494,218 +494,6 @@ extern "C" int crthip_batch_walk_stats(const crthip_batch *b, crthip_walk_stats 
 	return CRTHIP_OK;
 }
 
-static int check_binding(const AttrHeader &a, const crthip_attr_binding &bd) {
-	if(!bd.buffer) return CRTHIP_OK;
-	const uint32_t st = bd.stride;
-	if(bd.reserved & ~(CRTHIP_BIND_STREAM_VALUES | CRTHIP_BIND_QUANTIZED)) return CRTHIP_E_ARGUMENT;
-	if(bd.reserved & CRTHIP_BIND_QUANTIZED) {                              // uint16 grid values of a generic attribute (corto_hip.h)
-		// (INT32 is the format of the OTHER flag's stream values: with this bit it stays the argument error it was before the bit had a meaning)
-		if(a.codec == CRTHIP_CODEC_GENERIC && bd.format == CRTHIP_FMT_INT32) return CRTHIP_E_ARGUMENT;
-		if(a.codec == CRTHIP_CODEC_NORMAL || a.codec == CRTHIP_CODEC_COLOR || bd.format != CRTHIP_FMT_UINT16 || a.N < 1) return CRTHIP_E_FORMAT;
-		if(bd.reserved & CRTHIP_BIND_STREAM_VALUES) return CRTHIP_E_ARGUMENT;
-		if(a.N > 4) return CRTHIP_E_LIMIT;
-		if(bd.out_components && bd.out_components != a.N) return CRTHIP_E_ARGUMENT;
-		if(((uintptr_t)bd.buffer) % 2) return CRTHIP_E_ARGUMENT;
-		if(st && (st < 2*a.N || st % 2)) return CRTHIP_E_ARGUMENT;
-		return CRTHIP_OK;
-	}
-	if((bd.reserved & CRTHIP_BIND_STREAM_VALUES) && a.codec != CRTHIP_CODEC_GENERIC) return CRTHIP_E_FORMAT;   // normals / colours have codecs of their own upstream too
-	if(a.codec == CRTHIP_CODEC_NORMAL) {
-		if(bd.format != CRTHIP_FMT_FLOAT && bd.format != CRTHIP_FMT_INT16) return CRTHIP_E_FORMAT;
-		const uint32_t el = bd.format == CRTHIP_FMT_INT16 ? 2u : 4u;
-		if(((uintptr_t)bd.buffer) % el) return CRTHIP_E_ARGUMENT;            // a float* / int16_t* (decoder.h:52-53) is aligned by its type
-		if(st && (st < 3*el || st % el)) return CRTHIP_E_ARGUMENT;
-		return CRTHIP_OK;
-	}
-	if(a.codec == CRTHIP_CODEC_COLOR) {
-		// FLOAT colour output is broken upstream (color_attribute.cpp:96-110)
-		if(bd.format != CRTHIP_FMT_UINT8) return CRTHIP_E_FORMAT;
-		uint32_t oc = bd.out_components ? bd.out_components : 4;
-		if(a.N < 1 || a.N > 4 || oc > 4 || oc < a.N) return CRTHIP_E_FORMAT;
-		if(st && st < oc) return CRTHIP_E_ARGUMENT;
-		return CRTHIP_OK;
-	}
-	if(a.N < 1 || bd.format > CRTHIP_FMT_DOUBLE) return CRTHIP_E_FORMAT;
-	// the device half of a caller-supplied codec object: int32 stream values, packed (corto_hip.h: CRTHIP_BIND_STREAM_VALUES)
-	if(bd.reserved & CRTHIP_BIND_STREAM_VALUES) return bd.format == CRTHIP_FMT_INT32 && !st && ((uintptr_t)bd.buffer) % 4 == 0 ? CRTHIP_OK : CRTHIP_E_ARGUMENT;
-	// a packed buffer doubles as the int32 workspace and K-DELTA turns it into floats with dword / 16-byte accesses: a float* that is
-	// not 4-byte aligned (never one a C++ caller's setPositions(float*) could pass) is refused, not decoded into integers
-	if(((uintptr_t)bd.buffer) % (bd.format == CRTHIP_FMT_DOUBLE ? 8 : 4)) return CRTHIP_E_ARGUMENT;
-	// the integer formats and DOUBLE (setAttribute(name, buffer, format): vertex_attribute.h:195-228) are upstream's in-place layouts:
-	// packed only
-	if(bd.format != CRTHIP_FMT_FLOAT) return st ? CRTHIP_E_ARGUMENT : CRTHIP_OK;
-	if(st && (st < 4*a.N || st % 4)) return CRTHIP_E_ARGUMENT;
-	return CRTHIP_OK;
-}
-
-extern "C" int crthip_batch_bind(crthip_batch *b, uint32_t i, const crthip_attr_binding *attrs, void *index, uint32_t index_format) {
-	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT);
-	BlobPlan &P = b->blobs[i];
-	if(P.bind.size() && !attrs) return fail(CRTHIP_E_ARGUMENT);
-	if(index && index_format != CRTHIP_FMT_UINT32 && index_format != CRTHIP_FMT_UINT16) return fail(CRTHIP_E_FORMAT);
-	for(size_t k = 0; k < P.bind.size(); k++) {
-		int err = check_binding(P.L.h.attrs[k], attrs[k]);
-		if(err) return fail(err, std::string(crthip_strerror(err)) + " (attribute '" + P.L.h.attrs[k].name + "')");
-	}
-	for(size_t k = 0; k < P.bind.size(); k++) {
-		P.bind[k].buffer = attrs[k].buffer; P.bind[k].format = attrs[k].format;
-		P.bind[k].out_components = attrs[k].out_components ? attrs[k].out_components : 4;
-		// a stride equal to the packed element size is the packed layout (the buffer then doubles as int32 workspace, as upstream's does)
-		const AttrHeader &a = P.L.h.attrs[k];
-		P.bind[k].stream_values = (attrs[k].reserved & CRTHIP_BIND_STREAM_VALUES) != 0;
-		P.bind[k].quantized = attrs[k].buffer && (attrs[k].reserved & CRTHIP_BIND_QUANTIZED) != 0;
-		const uint32_t packed = a.codec == CRTHIP_CODEC_NORMAL ? (attrs[k].format == CRTHIP_FMT_INT16 ? 6u : 12u)
-		                      : a.codec == CRTHIP_CODEC_COLOR ? P.bind[k].out_components : P.bind[k].quantized ? 2u*a.N : 4u*a.N;
-		P.bind[k].stride = attrs[k].stride == packed ? 0u : attrs[k].stride;
-	}
-	P.index = index; P.index_u16 = index && index_format == CRTHIP_FMT_UINT16;
-	P.computed = Binding{};                                                 // (crthip_batch_bind_computed_normals comes after the bind)
-	P.tangent = Binding{};                                                  // (... and crthip_batch_bind_computed_tangents after both)
-	P.meshlets = crthip_meshlet_binding{};                                  // (... and crthip_batch_bind_meshlets)
-	P.meshlet_bounds = nullptr;                                             // (... and crthip_batch_bind_meshlet_bounds behind that)
-	b->dirty = true;
-	return CRTHIP_OK;
-}
-
-// Normals for a mesh whose blob stores none (or leaves its stored ones unbound): every check is made here, so that the decode has nothing new to fail on
-extern "C" int crthip_batch_bind_computed_normals(crthip_batch *b, uint32_t i, void *buffer, uint32_t format, uint32_t stride) {
-	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_computed_normals: no such blob");
-	BlobPlan &P = b->blobs[i];
-	const std::string who = " (blob " + std::to_string(i) + ")";
-	P.tangent = Binding{};                                                  // the tangents' normal source may change here: they are bound behind this call
-	if(!buffer) { P.computed = Binding{}; b->dirty = true; return CRTHIP_OK; }
-	if(P.L.h.nface == 0) return fail(CRTHIP_E_ARGUMENT, "computed normals need faces: a point cloud has none" + who);
-	int pos_k = -1;
-	for(size_t k = 0; k < P.bind.size(); k++) {
-		const AttrHeader &a = P.L.h.attrs[k];
-		if(a.name == "normal" && P.bind[k].buffer) return fail(CRTHIP_E_ARGUMENT, "the blob's stored normals are bound: computed normals take an unbound or absent attribute" + who);
-		if(a.name == "position") pos_k = (int)k;
-	}
-	// what a stored normal's binding must be (check_binding)
-	AttrHeader as_normal; as_normal.codec = CRTHIP_CODEC_NORMAL;
-	crthip_attr_binding bd{};
-	bd.buffer = buffer; bd.format = format; bd.stride = stride;
-	const int err = check_binding(as_normal, bd);
-	if(err) return fail(err, std::string(crthip_strerror(err)) + " (computed normals)" + who);
-	// ... and what a stored ESTIMATED normal asks of the position (plan_jobs.cpp; src/normal_attribute.cpp:210-227)
-	if(pos_k < 0 || P.L.h.attrs[pos_k].codec != CRTHIP_CODEC_GENERIC || P.L.h.attrs[pos_k].N != 3 || !P.bind[pos_k].buffer || P.bind[pos_k].stream_values)
-		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "computed normals need a bound three-component \"position\" (bind the blob first)" + who);
-	P.computed.buffer = buffer; P.computed.format = format;
-	P.computed.stride = stride == (format == CRTHIP_FMT_INT16 ? 6u : 12u) ? 0u : stride;
-	b->dirty = true;
-	return CRTHIP_OK;
-}
-
-// Tangents from the blob's integer positions and uvs, its index and its final normals (corto_hip.h has the value): every check is made here
-extern "C" int crthip_batch_bind_computed_tangents(crthip_batch *b, uint32_t i, void *buffer, uint32_t format, uint32_t stride) {
-	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_computed_tangents: no such blob");
-	BlobPlan &P = b->blobs[i];
-	const std::string who = " (blob " + std::to_string(i) + ")";
-	if(!buffer) { P.tangent = Binding{}; b->dirty = true; return CRTHIP_OK; }
-	if(P.L.h.nface == 0) return fail(CRTHIP_E_ARGUMENT, "computed tangents need faces: a point cloud has none" + who);
-	if(format != CRTHIP_FMT_FLOAT && format != CRTHIP_FMT_INT16) return fail(CRTHIP_E_FORMAT, "computed tangents are FLOAT or INT16" + who);
-	const uint32_t el = format == CRTHIP_FMT_INT16 ? 2u : 4u;
-	if(((uintptr_t)buffer) % el || (stride && (stride < 4*el || stride % el)))
-		return fail(CRTHIP_E_ARGUMENT, "computed tangents: the buffer is not aligned to its element, or the stride is below four elements or no multiple of one" + who);
-	int pos_k = -1, uv_k = -1, nrm_k = -1;
-	for(size_t k = 0; k < P.bind.size(); k++) {
-		const AttrHeader &a = P.L.h.attrs[k];
-		if(a.name == "position") pos_k = (int)k;
-		if(a.name == "uv") uv_k = (int)k;
-		if(a.name == "normal" && a.codec == CRTHIP_CODEC_NORMAL && P.bind[k].buffer) nrm_k = (int)k;
-	}
-	// (what computed normals ask of the position)
-	if(pos_k < 0 || P.L.h.attrs[pos_k].codec != CRTHIP_CODEC_GENERIC || P.L.h.attrs[pos_k].N != 3 || !P.bind[pos_k].buffer || P.bind[pos_k].stream_values)
-		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "computed tangents need a bound three-component \"position\" (bind the blob first)" + who);
-	if(uv_k < 0 || P.L.h.attrs[uv_k].codec != CRTHIP_CODEC_GENERIC || P.L.h.attrs[uv_k].N != 2 || !P.bind[uv_k].buffer || P.bind[uv_k].stream_values)
-		return fail(CRTHIP_E_ARGUMENT, "computed tangents need a bound two-component generic \"uv\" (bind the blob first)" + who);
-	if(nrm_k < 0 && !computes_normals(P))
-		return fail(CRTHIP_E_ARGUMENT, "computed tangents need a normal source: a stored \"normal\" bound as FLOAT or INT16, or crthip_batch_bind_computed_normals before this call" + who);
-	P.tangent.buffer = buffer; P.tangent.format = format; P.tangent.out_components = 4;
-	P.tangent.stride = stride == 4*el ? 0u : stride;
-	b->dirty = true;
-	return CRTHIP_OK;
-}
-
-// Meshlets from the blob's decoded index (corto_hip.h has the contract): every check is made here, against the bound of this blob's index
-extern "C" int crthip_batch_bind_meshlets(crthip_batch *b, uint32_t i, const crthip_meshlet_binding *m) {
-	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_meshlets: no such blob");
-	BlobPlan &P = b->blobs[i];
-	const std::string who = " (blob " + std::to_string(i) + ")";
-	P.meshlet_bounds = nullptr;                                             // the bounds' arrays and capacity change here: they are bound behind this call
-	if(!m) { P.meshlets = crthip_meshlet_binding{}; b->dirty = true; return CRTHIP_OK; }
-	if(P.L.h.nface == 0) return fail(CRTHIP_E_ARGUMENT, "meshlets need faces: a point cloud has none" + who);
-	crthip_meshlet_counts bound;
-	const bool ok = mlt_plan(P.L.h.nface, (uint32_t)P.L.group_end.size(), P.L.group_end.data(), m->max_vertices, m->max_triangles, m->segment_faces, nullptr, bound);
-	if(const char *why = meshlet_binding_error(m, ok, bound)) return fail(CRTHIP_E_ARGUMENT, why + who);
-	P.meshlets = *m;
-	b->dirty = true;
-	return CRTHIP_OK;
-}
-
-// A box, a sphere and a normal cone a meshlet (corto_hip.h has the record): every check is made here, against the meshlet binding of this blob
-extern "C" int crthip_batch_bind_meshlet_bounds(crthip_batch *b, uint32_t i, crthip_meshlet_bounds *bounds, uint32_t capacity) {
-	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_meshlet_bounds: no such blob");
-	BlobPlan &P = b->blobs[i];
-	const std::string who = " (blob " + std::to_string(i) + ")";
-	if(!bounds) { P.meshlet_bounds = nullptr; b->dirty = true; return CRTHIP_OK; }
-	if(!builds_meshlets(P)) return fail(CRTHIP_E_ARGUMENT, "meshlet bounds need a meshlet binding: crthip_batch_bind_meshlets comes first" + who);
-	if((uintptr_t)bounds % 16) return fail(CRTHIP_E_ARGUMENT, "meshlet bounds: the records are 16-byte aligned" + who);
-	crthip_meshlet_counts bound;
-	const crthip_meshlet_binding &m = P.meshlets;
-	if(!mlt_plan(P.L.h.nface, (uint32_t)P.L.group_end.size(), P.L.group_end.data(), m.max_vertices, m.max_triangles, m.segment_faces, nullptr, bound) ||
-		capacity < bound.meshlets) return fail(CRTHIP_E_ARGUMENT, "meshlet bounds: capacity is below crthip_meshlet_bound's meshlets" + who);
-	// (what computed tangents ask of the position)
-	int pos_k = -1;
-	for(size_t k = 0; k < P.bind.size(); k++) if(P.L.h.attrs[k].name == "position") pos_k = (int)k;
-	if(pos_k < 0 || P.L.h.attrs[pos_k].codec != CRTHIP_CODEC_GENERIC || P.L.h.attrs[pos_k].N != 3 || !P.bind[pos_k].buffer || P.bind[pos_k].stream_values)
-		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "meshlet bounds need a bound three-component \"position\" (bind the blob first)" + who);
-	P.meshlet_bounds = bounds;
-	b->dirty = true;
-	return CRTHIP_OK;
-}
-
-extern "C" int crthip_batch_meshlet_counts(const crthip_batch *b, uint32_t i, crthip_meshlet_counts *out) {
-	if(!b || !out || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_meshlet_counts: no such blob");
-	if(!b->decoded || (b->ctx && b->ctx->in_flight == b) || b->staged) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_meshlet_counts: decode and sync the batch first");
-	if(i >= b->meshlet_bound.size() || i >= b->meshlet_recs.size() || !b->meshlet_bound[i])
-		return fail(CRTHIP_E_ARGUMENT, "crthip_batch_meshlet_counts: the blob had no meshlet binding in that decode (blob " + std::to_string(i) + ")");
-	*out = b->meshlet_recs[i];
-	return CRTHIP_OK;
-}
-
-// CRTHIP_BIND_QUANTIZED: the record of one attribute as the last synced decode left it; the caller's device copy of the records
-extern "C" int crthip_batch_quant_transform(const crthip_batch *b, uint32_t i, uint32_t attr, crthip_quant_transform *out) {
-	if(!b || !out || i >= b->blobs.size() || attr >= b->blobs[i].bind.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_quant_transform: no such blob or attribute");
-	if(!b->decoded || (b->ctx && b->ctx->in_flight == b) || b->staged) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_quant_transform: decode and sync the batch first");
-	size_t r = attr;
-	for(uint32_t k = 0; k < i; k++) r += b->blobs[k].bind.size();
-	if(r >= b->quant_bound.size() || r >= b->quant_recs.size() || !b->quant_bound[r])
-		return fail(CRTHIP_E_ARGUMENT, "crthip_batch_quant_transform: the attribute was not bound with CRTHIP_BIND_QUANTIZED (blob " + std::to_string(i) + ")");
-	*out = b->quant_recs[r];
-	return CRTHIP_OK;
-}
-
-extern "C" int crthip_batch_bind_quant_transforms(crthip_batch *b, void *device_records) {
-	if(!b) return fail(CRTHIP_E_ARGUMENT);
-	if((uintptr_t)device_records & 15) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_quant_transforms: the record array must be 16-byte aligned");
-	b->quant_dev = device_records;
-	b->dirty = true;
-	return CRTHIP_OK;
-}
-
-extern "C" int crthip_batch_bind_all(crthip_batch *b, const crthip_attr_binding *attrs, void *const *index, const uint32_t *index_format) {
-	if(!b) return fail(CRTHIP_E_ARGUMENT);
-	size_t k = 0;
-	for(uint32_t i = 0; i < b->blobs.size(); i++) {
-		int err = crthip_batch_bind(b, i, attrs ? attrs + k : nullptr, index ? index[i] : nullptr, index_format ? index_format[i] :
-			CRTHIP_FMT_UINT32);
-		if(err) return err;
-		k += b->blobs[i].bind.size();
-	}
-	return CRTHIP_OK;
-}
-
 static int build_and_launch_inner(crthip_batch *b);
 static int decode_pair(crthip_batch *cur, crthip_batch *next);
 void drop_staged(crthip_batch *b) { delete b->staged; b->staged = nullptr; }
@@ -863,19 +651,25 @@ extern "C" int crthip_batch_get_stats(const crthip_batch *b, crthip_batch_stats 
 	return CRTHIP_OK;
 }
 
-extern "C" int crthip_batch_kernel_times(crthip_batch *b, crthip_kernel_times *t) {
-	if(!b || !t) return fail(CRTHIP_E_ARGUMENT);
-	crthip_ctx *ctx = b->ctx;
+// the timer's records of the (synced) stream folded by kernel name
+static void fold_kernel_times(const KernelTimer &timer, crthip_kernel_times *t) {
 	memset(t, 0, sizeof(*t));
-	HIP_TRY(hipStreamSynchronize(ctx->stream));
-	for(auto &r : ctx->timer.recs) {
+	for(auto &r : timer.recs) {
 		float ms = 0;
-		if(hipEventElapsedTime(&ms, ctx->timer.pool[r.e0], ctx->timer.pool[r.e1]) != hipSuccess) continue;
+		if(hipEventElapsedTime(&ms, timer.pool[r.e0], timer.pool[r.e1]) != hipSuccess) continue;
 		uint32_t k = 0;
 		for(; k < t->count; k++) if(strcmp(t->name[k], r.name) == 0) break;
 		if(k == t->count) { if(t->count == CRTHIP_MAX_KERNELS) continue; t->name[k] = r.name; t->count++; }
 		t->ms[k] += ms; t->launches[k]++;
 	}
+}
+
+extern "C" int crthip_batch_kernel_times(crthip_batch *b, crthip_kernel_times *t) {
+	if(!b || !t) return fail(CRTHIP_E_ARGUMENT);
+	crthip_ctx *ctx = b->ctx;
+	memset(t, 0, sizeof(*t));
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	fold_kernel_times(ctx->timer, t);
 	return CRTHIP_OK;
 }
 
@@ -1111,16 +905,6 @@ extern "C" int crthip_tunstall_decode_blocks(crthip_ctx *ctx, uint32_t n, const 
 		o_fill), (uint32_t)fills.size()); LT.end(); }
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(st));
-	if(times) {
-		memset(times, 0, sizeof(*times));
-		for(auto &r : ctx->timer.recs) {
-			float ms = 0;
-			if(hipEventElapsedTime(&ms, ctx->timer.pool[r.e0], ctx->timer.pool[r.e1]) != hipSuccess) continue;
-			uint32_t k = 0;
-			for(; k < times->count; k++) if(strcmp(times->name[k], r.name) == 0) break;
-			if(k == times->count) { if(times->count == CRTHIP_MAX_KERNELS) continue; times->name[k] = r.name; times->count++; }
-			times->ms[k] += ms; times->launches[k]++;
-		}
-	}
+	if(times) fold_kernel_times(ctx->timer, times);
 	return CRTHIP_OK;
 }

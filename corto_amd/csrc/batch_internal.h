@@ -1,8 +1,9 @@
 // batch_internal.h — what the pieces of the decode path's host side share: the context and batch objects, the plan of one decode call and
 // the
-// staged Planner (batch.cpp: the C ABI, context, harvest; plan_carve.cpp / plan_jobs.cpp / plan_group.cpp: the planner's stages;
-// plan_launch.cpp:
-// upload, the kernel schedule, the stats).  Round 5 split batch.cpp (1 640 lines) along the Planner's stages.  Not part of the C ABI.
+// staged Planner (batch.cpp: the C ABI, context, harvest; batch_bind.cpp: the bind calls and what reads a decode's records - no HIP call, so a
+// program without the runtime links them; plan_carve.cpp / plan_jobs.cpp / plan_group.cpp: the planner's stages; plan_launch.cpp:
+// upload, the kernel schedule, the stats).  Round 5 split batch.cpp (1 640 lines) along the Planner's stages.  A blob's derived bindings -
+// computed normals, tangents, meshlets, meshlet bounds - are one record, DerivedBindings.  Not part of the C ABI.
 #pragma once
 #include <chrono>
 #include <hip/hip_runtime.h>
@@ -90,10 +91,10 @@ struct BlobScratch {
 	uint64_t clers = ~0ull, pred = ~0ull, front_a = ~0ull, front_b = ~0ull, order = ~0ull, delayed = ~0ull, faces = ~0ull;
 	uint64_t progress = ~0ull;                              // the automaton's progress word (zeroed): blobs with an attribute too big for K-DELTA's LDS records
 	uint32_t front_cap = 0, aux_groups = 0;
-	uint64_t tan_acc = ~0ull;                               // computed tangents (BlobPlan::tangent) of a blob beyond TANGENT_BLOB_MAX: 6 x int64 a vertex, inside the zeroed region
-	uint64_t mlt = ~0ull;                                   // meshlets (BlobPlan::meshlets) of a blob of more than one segment: mlt_scratch_layout's block
-	uint64_t mlt_counts = ~0ull;                            // meshlet bounds (BlobPlan::meshlet_bounds) over a meshlet binding without a device counts record: 16 bytes for one
-	uint64_t cn_facen = ~0ull;                              // computed normals (BlobPlan::computed) by the fused kernel without its face normals in LDS: AttrScratch::facen's counterpart
+	uint64_t tan_acc = ~0ull;                               // computed tangents (DerivedBindings::tangents) of a blob beyond TANGENT_BLOB_MAX: 6 x int64 a vertex, inside the zeroed region
+	uint64_t mlt = ~0ull;                                   // meshlets (DerivedBindings::meshlets) of a blob of more than one segment: mlt_scratch_layout's block
+	uint64_t mlt_counts = ~0ull;                            // meshlet bounds (DerivedBindings::bounds) over a meshlet binding without a device counts record: 16 bytes for one
+	uint64_t cn_facen = ~0ull;                              // computed normals (DerivedBindings::normals) by the fused kernel without its face normals in LDS: AttrScratch::facen's counterpart
 	std::vector<AttrScratch> attr;
 	size_t nattr = 0;                                       // attr[0..nattr) are this decode's (the vector only grows)
 	void reset() { clers = pred = front_a = front_b = order = delayed = faces = progress = cn_facen = tan_acc = mlt = mlt_counts = ~0ull; front_cap = 0; aux_groups = 0; nattr = 0; }
@@ -231,16 +232,25 @@ struct Binding { void *buffer = nullptr; uint32_t format = CRTHIP_FMT_FLOAT, out
 // a generic attribute decoded as int32 in device scratch and finished by a job of its own: a stride, DOUBLE, or uint16 grid values
 static inline bool generic_in_scratch(const Binding &bd) { return bd.stride || bd.format == CRTHIP_FMT_DOUBLE || bd.quantized; }
 
+// The outputs derived from a blob's decoded data, each bound by a call of its own behind crthip_batch_bind.  A call drops what was bound on top of what
+// it changes: the three functions are that rule, and the only place it is written
+struct DerivedBindings {
+	Binding normals;                       // crthip_batch_bind_computed_normals: where the normals of a blob that stores (or binds) none go
+	Binding tangents;                      // crthip_batch_bind_computed_tangents: where the blob's tangents go (out_components 4)
+	crthip_meshlet_binding meshlets{};     // crthip_batch_bind_meshlets: meshlets.meshlets != null - where the blob's meshlets go
+	crthip_meshlet_bounds *bounds = nullptr;   // crthip_batch_bind_meshlet_bounds: a record a meshlet
+	void clear() { *this = DerivedBindings{}; }       // a bind (and a blob adopted by a fill): all of them read what it binds
+	void normals_change() { tangents = Binding{}; }   // a normals call: the tangents' normal source may change
+	void meshlets_change() { bounds = nullptr; }      // a meshlets call: the bounds' arrays and capacity change
+};
+
 struct BlobPlan {
 	BlobLayout L;
 	uint64_t arena_off = 0;
 	uint32_t len = 0;
 	std::vector<Binding> bind;
 	void *index = nullptr; uint32_t index_u16 = 0;
-	Binding computed;          // crthip_batch_bind_computed_normals: where the normals of a blob that stores (or binds) none go; dropped by every bind / reset
-	Binding tangent;           // crthip_batch_bind_computed_tangents: where the blob's tangents go (out_components 4); dropped by every bind, computed-normals call and reset
-	crthip_meshlet_binding meshlets{};   // crthip_batch_bind_meshlets: meshlets.meshlets != null - where the blob's meshlets go; dropped by every bind and reset
-	crthip_meshlet_bounds *meshlet_bounds = nullptr;   // crthip_batch_bind_meshlet_bounds: a record a meshlet; dropped with the meshlet binding and by every call that sets it
+	DerivedBindings derived;
 	int32_t host_status = 0;   // set by the planner (e.g. unsupported format), overrides device status
 	// debug handles (scratch offsets valid after decode)
 	uint64_t dbg_clers = ~0ull, dbg_pred = ~0ull; uint32_t dbg_nclers = 0;
@@ -277,15 +287,15 @@ inline crthip_ctx::Half &ctx_set(crthip_ctx *ctx, const crthip_batch *b) { retur
 // The per-blob status block: four int32 words a blob in the pinned host memory of the batch's set (status_host), written by the kernels, zeroed by
 // Planner::upload, read by harvest
 struct StatusWords {
-	size_t n;                                                      // blobs
+	size_t n, quant_records = 0; bool meshlets = false;            // blobs; Plan::quant_records; Plan::meshlet_records
 	size_t status(size_t i) const { return i; }                    // the blob's CRTHIP_* code (k_topology*, k_normal*, k_delta_tiles)
 	size_t topo_flags(size_t i) const { return n + i; }            // bit 0: the automaton was redone on the HBM front; above it the slots it needed
 	size_t delta_flags(size_t i) const { return 2*n + 2*i; }       // two words: an attribute's values left int16 / an attribute took the walk
-	size_t bytes() const { return n*16; }
 	// behind them (16-byte aligned): the crthip_quant_transform records of a batch with a quantised binding, one an attribute
 	size_t records() const { return n*16; }
 	// ... and behind those (16-byte aligned) a crthip_meshlet_counts a blob of a batch with a meshlet binding
-	size_t meshlet_records(size_t quant_records) const { return (n*16 + quant_records*sizeof(crthip_quant_transform) + 15) & ~(size_t)15; }
+	size_t meshlet_record(size_t i) const { return ((n*16 + quant_records*sizeof(crthip_quant_transform) + 15) & ~(size_t)15) + i*sizeof(crthip_meshlet_counts); }
+	size_t bytes() const { return meshlet_record(meshlets ? n : 0); }  // the whole block
 };
 
 int harvest(crthip_ctx *ctx);     // wait for the batch in flight on the context, keep its per-blob status, learn from its flags (batch.cpp)
@@ -306,7 +316,7 @@ static inline uint64_t delta_lds_need(const DeltaJob &d, bool wide) {          /
 static inline bool delta_in_lds(const DeltaJob &d, bool wide) { return delta_lds_need(d, wide) <= DELTA16_LDS_MAX; }
 // the computed normals of a blob: bound, a mesh, and no stored "normal" attribute bound beside them (the bind call sees to all three)
 static inline bool computes_normals(const BlobPlan &P) {
-	if(!P.computed.buffer || P.L.h.nface == 0) return false;
+	if(!P.derived.normals.buffer || P.L.h.nface == 0) return false;
 	for(size_t k = 0; k < P.bind.size(); k++) if(P.L.h.attrs[k].name == "normal" && P.bind[k].buffer) return false;
 	return true;
 }
@@ -317,16 +327,38 @@ static bool normal_fused(uint32_t nvert, uint32_t nface) { return nvert <= 32767
 // LDS a vertex, 54 KB at the limit, which holds a 2 112-vertex C4 blob and is what a lane of TAN_BLOB_SLOTS vertices in registers covers - the
 // others k_tangent_faces / k_tangent_vertex.  The bind call made sure of a mesh, a position, a uv and a normal source
 constexpr uint32_t TANGENT_BLOB_MAX = TAN_BLOB_SLOTS*TAN_THREADS;          // 2 304
-static inline bool computes_tangents(const BlobPlan &P) { return P.tangent.buffer && P.L.h.nface > 0; }
+static inline bool computes_tangents(const BlobPlan &P) { return P.derived.tangents.buffer && P.L.h.nface > 0; }
 static inline bool tangent_in_blob(uint32_t nvert) { return nvert <= TANGENT_BLOB_MAX; }
 
 // meshlets (crthip_batch_bind_meshlets): a blob of up to MESHLET_BLOB_SEGS segments takes k_meshlet_blob - one workgroup, a wave a segment, so a
 // workgroup's four waves; more segments would queue behind one another in a workgroup while the chip has idle CUs - the others
 // k_meshlet_segments / k_meshlet_place, a workgroup a segment
 constexpr uint32_t MESHLET_BLOB_SEGS = 4;
-static inline bool builds_meshlets(const BlobPlan &P) { return P.meshlets.meshlets && P.L.h.nface > 0; }
-static inline bool bounds_meshlets(const BlobPlan &P) { return P.meshlet_bounds && builds_meshlets(P); }
+static inline bool builds_meshlets(const BlobPlan &P) { return P.derived.meshlets.meshlets && P.L.h.nface > 0; }
+static inline bool bounds_meshlets(const BlobPlan &P) { return P.derived.bounds && builds_meshlets(P); }
 namespace corto_hip { const char *meshlet_binding_error(const crthip_meshlet_binding *m, bool have_bound, const crthip_meshlet_counts &bound); }
+// the cuts and the capacity bound of a blob's index under a meshlet binding (the blob's own, or the one a bind call is about to take)
+static inline bool mlt_plan_of(const BlobPlan &P, const crthip_meshlet_binding &m, std::vector<MltSeg> *segs, crthip_meshlet_counts &bound) {
+	return mlt_plan(P.L.h.nface, (uint32_t)P.L.group_end.size(), P.L.group_end.data(), m.max_vertices, m.max_triangles, m.segment_faces, segs, bound);
+}
+
+// where the derived outputs and the estimated normals take their inputs.  An attribute by name: the last one of that name, or -1
+static inline int attr_named(const BlobPlan &P, const char *name) {
+	int k = -1;
+	for(size_t j = 0; j < P.bind.size(); j++) if(P.L.h.attrs[j].name == name) k = (int)j;
+	return k;
+}
+// attribute k can serve as an integer source: generic, N components, bound, and not as stream values (upstream throws there too, normal_attribute.cpp:210-213)
+static inline bool generic_source_ok(const BlobPlan &P, int k, uint32_t N) {
+	return k >= 0 && P.L.h.attrs[k].codec == CRTHIP_CODEC_GENERIC && P.L.h.attrs[k].N == N && P.bind[k].buffer && !P.bind[k].stream_values;
+}
+// the normals a blob's tangents read: the computed binding, else the first bound attribute named "normal" that is coded as one; or null
+static inline const Binding *tangent_normal_source(const BlobPlan &P) {
+	if(computes_normals(P)) return &P.derived.normals;
+	for(size_t k = 0; k < P.bind.size(); k++)
+		if(P.L.h.attrs[k].name == "normal" && P.L.h.attrs[k].codec == CRTHIP_CODEC_NORMAL && P.bind[k].buffer) return &P.bind[k];
+	return nullptr;
+}
 
 struct Launch {
 	crthip_ctx *ctx;
@@ -375,6 +407,7 @@ struct Planner {
 	int32_t *hs_base = nullptr; StatusWords hs;                              // per-blob status words in pinned host memory
 	uint8_t *base = nullptr, *stage = nullptr;                               // the scratch block; the host image of the job arrays
 
+	uint32_t dict_group0 = 0; QuantOutRecord *quant_rec_host = nullptr;      // jobs(): first dictionary of the current launch group (CLERS / attribute streams); the quant records behind the status words
 	Planner(crthip_batch *b_) : b(b_), ctx(b_->ctx), set(ctx_set(b_->ctx, b_)), pl(set.plan), bs(set.plan_scratch), nblobs((uint32_t)b_->blobs.size()),
 		wide(b_->ctx->delta.wide), arena(b_->d_arena), hs{b_->blobs.size()} {}
 	static uint8_t *SP(uint64_t off) { return (uint8_t *)(uintptr_t)(off | (1ull << 63)); }   // a scratch offset in a pointer field
@@ -386,5 +419,19 @@ struct Planner {
 	int carve(); int jobs(); void group(); int upload(); int launch(uint32_t phases = PH_ALL, const Carry *carry = nullptr); int mark_done(); void account();
 	uint32_t qout_blob_max() const { return ctx->dbg.qout_blob_max ? ctx->dbg.qout_blob_max : QOUT_BLOB_MAX; }   // a quantised attribute's size class
 	bool splits() const; bool takes_front() const; bool carry_args(Carry &c) const; bool hosts_carry() const;
+	// a blob's integer sources as a job takes them: attribute k's values where K-DELTA leaves them and the index where the automaton does - the caller's, or scratch
+	int32_t *ints_of(uint32_t i, size_t k) const { const Binding &bd = b->blobs[i].bind[k]; return (int32_t *)(generic_in_scratch(bd) ? SP(bs[i].attr[k].vals) : bd.buffer); }
+	struct Faces { void *p; uint8_t u16; };
+	Faces faces_of(uint32_t i) const { const BlobPlan &P = b->blobs[i]; return P.index ? Faces{P.index, (uint8_t)P.index_u16} : Faces{SP(bs[i].faces), 0}; }
+	// jobs() by stage (plan_jobs.cpp): the streams of the entropy stage, then what one blob contributes
+	struct BlobView; struct BitBlock;
+	uint32_t est_vbase = 0, est_fbase = 0;                                   // the unfused normal jobs' slices of the batch-wide arrays, in job order
+	void clear_dict_table(); uint32_t dict_of(const StreamRef &s, const TunStream &t); const uint8_t *add_stream(const StreamRef &s, uint64_t sym_off, uint64_t blob_off);
+	void push_unpack(const BitBlock &bb, const StreamRef &s, const uint8_t *logs, void *out, uint8_t mode, uint16_t fields, uint16_t stride, uint16_t comp, uint8_t out_kind);
+	BlobView view_of(uint32_t i, size_t rec0); void topo_job(const BlobView &v); void attr_jobs(const BlobView &v, size_t k);
+	bool inverse_job(const BlobView &v, size_t k, void *values, uint32_t N, bool para, uint8_t is_u8, bool hand_i16);
+	void stored_normal_job(const BlobView &v, size_t k, bool hand_i16); void quant_job(const BlobView &v, size_t k); void dequant_job(const BlobView &v, size_t k);
+	bool estimated_normal_tail(const BlobView &v, NormalJob &n, HostArr<uint32_t> &fused_ids, uint32_t &fused_lds, uint64_t facen);
+	bool computed_normal_job(const BlobView &v); bool tangent_job(const BlobView &v); void meshlet_jobs(const BlobView &v);
 };
 

@@ -111,10 +111,9 @@ int Planner::carve() {
 		const BlobPlan &P = b->blobs[i];
 		if(!builds_meshlets(P)) continue;
 		crthip_meshlet_counts bound;
-		if(!mlt_plan(P.L.h.nface, (uint32_t)P.L.group_end.size(), P.L.group_end.data(), P.meshlets.max_vertices, P.meshlets.max_triangles,
-			P.meshlets.segment_faces, nullptr, bound)) continue;                   // (the bind call made sure; jobs() gives such a blob no job)
+		if(!mlt_plan_of(P, P.derived.meshlets, nullptr, bound)) continue;       // (the bind call made sure; jobs() gives such a blob no job)
 		if(bound.segments > 1) bs[i].mlt = cv.take(mlt_scratch_layout(P.L.h.nface, bound).total, 16);
-		if(bounds_meshlets(P) && !P.meshlets.counts) bs[i].mlt_counts = cv.take(16, 16);   // the device copy of the counts k_meshlet_bounds reads
+		if(bounds_meshlets(P) && !P.derived.meshlets.counts) bs[i].mlt_counts = cv.take(16, 16);   // the device copy of the counts k_meshlet_bounds reads
 	}
 	if(est_v) {
 		pl.start_off = cv.take(est_v*4 + 16); pl.flag_off = cv.take(est_v*4 + 16); pl.slot_off = cv.take(est_v*4 + 16);

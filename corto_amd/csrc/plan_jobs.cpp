@@ -1,11 +1,91 @@
 // plan_jobs.cpp — Planner::jobs: pass 2 - the job descriptors of every stage.  A pointer into scratch is written as SP(offset) and
 // resolved by upload(); every other pointer goes in as the real address (the Planner's comment, batch_internal.h).
+// jobs() keeps the status block, the CLERS streams and the loop over the blobs; what one blob contributes is made by the members below it.
 #include "batch_internal.h"
 
 // float -> int32 as x86's cvttss2si does it (out of range, NaN: INT_MIN): the unit of a normal attribute as upstream's host code computes it
 static int32_t f2i_x86_host(float x) {
 	if(!(x > -2147483904.0f && x < 2147483648.0f)) return (int32_t)0x80000000;
 	return (int32_t)x;
+}
+
+// what the stages share about one blob
+struct Planner::BlobView {
+	uint32_t i; BlobPlan &P; const BlobLayout &L; BlobScratch &S;
+	bool mesh; uint32_t nvert, nface;
+	int pos_k, uv_k;                                     // the attributes named "position" and "uv", or -1
+	bool tangents, bounds;                               // computes_tangents / bounds_meshlets
+	bool pos_ints_needed, pos_by_normal;                 // who turns the integer positions into floats (view_of)
+	size_t rec0;                                         // the blob's first quant record (crthip_batch_bind_all's order)
+};
+// the bit block of one attribute, shared by the K-BIT jobs of its streams
+struct Planner::BitBlock { const uint32_t *words; uint32_t nwords, out_limit, chain0, first_job; bool by_wave; };
+
+// the dictionary table is per launch group: the attribute streams' dictionaries are not shared with the CLERS streams' (different HIP streams)
+void Planner::clear_dict_table() {
+	if(ctx->dict_slots.size() != 8192) ctx->dict_slots.assign(8192, 0u);
+	for(uint32_t u : ctx->dict_used) ctx->dict_slots[u] = 0;
+	ctx->dict_used.clear(); ctx->dict_keys.clear(); ctx->dict_ids.clear();
+	dict_group0 = (uint32_t)pl.tun_dict.v.size();
+}
+
+// the dictionary (TunTable slot) of a stream: a new one, or the one an earlier stream of this launch group with the same table got
+uint32_t Planner::dict_of(const StreamRef &s, const TunStream &t) {
+	std::vector<uint32_t> &dict_ids = ctx->dict_ids;
+	const uint32_t fresh = (uint32_t)pl.tun_dict.v.size();
+	auto make = [&]() { TunStream d = t; d.dst = nullptr; d.table = fresh; d.dict = fresh; d.nchunks = 1; pl.tun_dict.v.push_back(d); return fresh; };
+	// (0 / 2: one dictionary per stream, whatever repeats)
+	if(s.nsym > 16 || fresh - dict_group0 >= 4096 || ctx->dbg.tun_share == 0 || ctx->dbg.tun_share == 2) return make();
+	uint64_t h = 0x9E3779B97F4A7C15ull ^ s.nsym;
+	for(uint32_t k = 0; k < 2*s.nsym; k += 8) { uint64_t w; memcpy(&w, s.probs16 + k, 8); h = (h ^ w)*0xFF51AFD7ED558CCDull;
+		h ^= h >> 32; }
+	for(uint32_t pos = (uint32_t)h & 8191u;; pos = (pos + 1) & 8191u) {
+		const uint32_t e = ctx->dict_slots[pos];
+		if(!e) {
+			ctx->dict_slots[pos] = (uint32_t)ctx->dict_keys.size() + 1; ctx->dict_used.push_back(pos);
+			crthip_ctx::DictKey key; key.n = (uint8_t)s.nsym; memcpy(key.bytes, s.probs16, 32);
+			ctx->dict_keys.push_back(key);
+			const uint32_t d = make();
+			dict_ids.push_back(d);
+			return d;
+		}
+		const crthip_ctx::DictKey &key = ctx->dict_keys[e - 1];
+		if(key.n == s.nsym && memcmp(key.bytes, s.probs16, 2*s.nsym) == 0) return dict_ids[e - 1];
+	}
+}
+
+// where the decoded symbols of a stream will be: in the arena, or in scratch
+const uint8_t *Planner::add_stream(const StreamRef &s, uint64_t sym_off, uint64_t blob_off) {
+	if(s.mode == STREAM_RAW) return arena + blob_off + s.payload_off;
+	if(s.mode == STREAM_EMPTY) return SP(0);
+	if(s.mode == STREAM_FILL) { pl.fill.v.push_back(FillJob{SP(sym_off), s.size, s.fill}); return SP(sym_off); }
+	TunStream t{};
+	t.src = arena + blob_off + s.payload_off; t.dst = SP(sym_off); t.probs = arena + blob_off + s.probs_off;
+	t.csize = s.csize; t.size = s.size; t.nsym = s.nsym; t.table = (uint32_t)pl.tun.v.size();
+	t.chunk0 = tun_chunks; tun_pick_geometry(t);
+	if(t.nchunks > 1) pl.tun_multi_chunk = true;
+	pl.tun_max_nchunks = std::max(pl.tun_max_nchunks, t.nchunks);
+	for(uint32_t c = 0; c < t.nchunks; c++) pl.tun_chunk_stream.v.push_back((uint32_t)pl.tun.v.size());
+	tun_chunks += t.nchunks;
+	t.dict = dict_of(s, t);
+	pl.tun.v.push_back(t);
+	return SP(sym_off);
+}
+
+void Planner::push_unpack(const BitBlock &bb, const StreamRef &s, const uint8_t *logs, void *out, uint8_t mode, uint16_t fields, uint16_t stride,
+	uint16_t comp, uint8_t out_kind) {
+	if(s.size == 0) return;
+	UnpackJob u{};
+	u.logs = logs; u.words = bb.words; u.out = out; u.count = s.size; u.nwords = bb.nwords; u.out_limit = bb.out_limit;
+	u.chunk0 = unpack_chunks; u.chain_chunk0 = bb.chain0; u.fields = fields; u.stride = stride; u.comp = comp; u.mode = mode;
+	u.out_kind = out_kind;
+	if(bb.by_wave) { u.chain_chunk0 = bb.first_job; pl.unpack_wave_ids.v.push_back((uint32_t)pl.unpack.v.size()); }
+	else {
+		const uint32_t nc = (s.size + CHUNK - 1)/CHUNK;
+		for(uint32_t c = 0; c < nc; c++) pl.unpack_chunk_job.v.push_back((uint32_t)pl.unpack.v.size());
+		unpack_chunks += nc;
+	}
+	pl.unpack.v.push_back(u);
 }
 
 int Planner::jobs() {
@@ -16,62 +96,17 @@ int Planner::jobs() {
 		for(const BlobPlan &P : b->blobs) { nattr += (uint32_t)P.bind.size(); for(const Binding &bd : P.bind) any = any || (bd.buffer && bd.quantized); }
 		pl.quant_records = any ? nattr : 0u;
 		for(const BlobPlan &P : b->blobs) pl.meshlet_records = pl.meshlet_records || builds_meshlets(P);
+		hs = StatusWords{b->blobs.size(), pl.quant_records, pl.meshlet_records};
 	}
-	const size_t status_bytes = hs.meshlet_records(pl.quant_records) + (pl.meshlet_records ? b->blobs.size()*sizeof(crthip_meshlet_counts) : 0) + 16;
+	const size_t status_bytes = hs.bytes() + 16;
 	if(status_bytes > set.status_host.cap && harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE);
 	if(set.status_host.reserve(status_bytes) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
 	hs_base = (int32_t *)set.status_host.p;
-	QuantOutRecord *const rec_host = (QuantOutRecord *)((uint8_t *)hs_base + hs.records());
-
-	// the dictionary (TunTable slot) of a stream: a new one, or the one an earlier stream of this launch group with the same table got
-	if(ctx->dict_slots.size() != 8192) ctx->dict_slots.assign(8192, 0u);
-	for(uint32_t u : ctx->dict_used) ctx->dict_slots[u] = 0;
-	ctx->dict_used.clear(); ctx->dict_keys.clear();
-	std::vector<uint32_t> &dict_ids = ctx->dict_ids; dict_ids.clear();
-	// first dictionary of the current group (CLERS streams / attribute streams)
-	uint32_t dict_group0 = 0;
-	auto dict_of = [&](const StreamRef &s, const TunStream &t) -> uint32_t {
-		const uint32_t fresh = (uint32_t)pl.tun_dict.v.size();
-		auto make = [&]() { TunStream d = t; d.dst = nullptr; d.table = fresh; d.dict = fresh; d.nchunks = 1; pl.tun_dict.v.push_back(d); return fresh; };
-		// (0 / 2: one dictionary per stream, whatever repeats)
-		if(s.nsym > 16 || fresh - dict_group0 >= 4096 || ctx->dbg.tun_share == 0 || ctx->dbg.tun_share == 2) return make();
-		uint64_t h = 0x9E3779B97F4A7C15ull ^ s.nsym;
-		for(uint32_t k = 0; k < 2*s.nsym; k += 8) { uint64_t w; memcpy(&w, s.probs16 + k, 8); h = (h ^ w)*0xFF51AFD7ED558CCDull;
-			h ^= h >> 32; }
-		for(uint32_t pos = (uint32_t)h & 8191u;; pos = (pos + 1) & 8191u) {
-			const uint32_t e = ctx->dict_slots[pos];
-			if(!e) {
-				ctx->dict_slots[pos] = (uint32_t)ctx->dict_keys.size() + 1; ctx->dict_used.push_back(pos);
-				crthip_ctx::DictKey key; key.n = (uint8_t)s.nsym; memcpy(key.bytes, s.probs16, 32);
-				ctx->dict_keys.push_back(key);
-				const uint32_t d = make();
-				dict_ids.push_back(d);
-				return d;
-			}
-			const crthip_ctx::DictKey &key = ctx->dict_keys[e - 1];
-			if(key.n == s.nsym && memcmp(key.bytes, s.probs16, 2*s.nsym) == 0) return dict_ids[e - 1];
-		}
-	};
-	auto add_stream = [&](const StreamRef &s, uint64_t sym_off, uint64_t blob_off) -> const uint8_t * {
-		// where the decoded symbols will be: in the arena, or in scratch
-		if(s.mode == STREAM_RAW) return arena + blob_off + s.payload_off;
-		if(s.mode == STREAM_EMPTY) return SP(0);
-		if(s.mode == STREAM_FILL) { pl.fill.v.push_back(FillJob{SP(sym_off), s.size, s.fill}); return SP(sym_off); }
-		TunStream t{};
-		t.src = arena + blob_off + s.payload_off; t.dst = SP(sym_off); t.probs = arena + blob_off + s.probs_off;
-		t.csize = s.csize; t.size = s.size; t.nsym = s.nsym; t.table = (uint32_t)pl.tun.v.size();
-		t.chunk0 = tun_chunks; tun_pick_geometry(t);
-		if(t.nchunks > 1) pl.tun_multi_chunk = true;
-		pl.tun_max_nchunks = std::max(pl.tun_max_nchunks, t.nchunks);
-		for(uint32_t c = 0; c < t.nchunks; c++) pl.tun_chunk_stream.v.push_back((uint32_t)pl.tun.v.size());
-		tun_chunks += t.nchunks;
-		t.dict = dict_of(s, t);
-		pl.tun.v.push_back(t);
-		return SP(sym_off);
-	};
+	quant_rec_host = (QuantOutRecord *)((uint8_t *)hs_base + hs.records());
 
 	// the CLERS streams come first in every stream/chunk/fill array: they are what the topology kernel waits for, the
 	// attribute streams are decoded on the second HIP stream while topology runs
+	clear_dict_table();
 	std::vector<const uint8_t *> &clers_ptrs = ctx->plan_clers;
 	clers_ptrs.assign(nblobs, nullptr);
 	for(uint32_t i = 0; i < nblobs; i++) {
@@ -80,360 +115,346 @@ int Planner::jobs() {
 	}
 	clers_tun = (uint32_t)pl.tun.v.size(); clers_chunks = tun_chunks; clers_fill = (uint32_t)pl.fill.v.size();
 	clers_dict = (uint32_t)pl.tun_dict.v.size();
-	// the attribute streams are a launch of their own: their dictionaries are not shared with the CLERS streams' (different HIP streams)
-	for(uint32_t u : ctx->dict_used) ctx->dict_slots[u] = 0;
-	ctx->dict_used.clear(); ctx->dict_keys.clear(); dict_ids.clear();
-	dict_group0 = clers_dict;
+	clear_dict_table();                                                      // the attribute streams are a launch of their own
 
-	uint32_t est_vbase = 0, est_fbase = 0;
-	size_t rec0 = 0;                                                         // the blob's first record (crthip_batch_bind_all's order)
+	est_vbase = est_fbase = 0;
+	size_t rec0 = 0;
 	for(uint32_t i = 0; i < nblobs; rec0 += b->blobs[i].bind.size(), i++) {
-		BlobPlan &P = b->blobs[i];
-		const BlobLayout &L = P.L;
-		BlobScratch &S = bs[i];
-		const bool mesh = L.h.nface > 0;
-		const uint32_t nvert = L.h.nvert, nface = L.h.nface;
-		const uint64_t bo = P.arena_off;
-		const uint8_t *clers_ptr = nullptr;
-		if(mesh) {
-			clers_ptr = clers_ptrs[i];
-			P.clers_in_arena = L.clers.mode == STREAM_RAW;
-			P.dbg_clers = L.clers.mode == STREAM_RAW ? bo + L.clers.payload_off : S.clers;
-			P.dbg_nclers = L.clers.size; P.dbg_pred = S.pred;
-			TopoJob t{};
-			t.clers = clers_ptr;
-			t.split_words = (const uint32_t *)(arena + bo + L.split.words_off);
-			t.group_end = (const uint32_t *)(uintptr_t)(pl.aux_u32.v.size()*4);   // bytes into aux_u32 (resolved by upload)
-			for(uint32_t ge : L.group_end) pl.aux_u32.v.push_back(ge);
-			t.faces = P.index ? P.index : (void *)SP(S.faces);
-			t.pred = (uint32_t *)SP(S.pred);
-			t.front_a = (uint4 *)SP(S.front_a); t.front_b = (uint2 *)SP(S.front_b);
-			t.order = (uint32_t *)SP(S.order); t.delayed = (uint32_t *)SP(S.delayed);
-			t.status = hs_base + hs.status(i);
-			t.flags = hs_base + hs.topo_flags(i);
-			t.nclers = L.clers.size; t.split_nwords = L.split.nwords; t.ngroups = (uint32_t)L.group_end.size();
-			t.nvert = nvert; t.nface = nface; t.front_cap = S.front_cap; t.faces_u16 = P.index ? P.index_u16 : 0;
-			t.opts = S.progress != ~0ull ? TOPO_OPT_PROGRESS : 0u;
-			{
-				// every mesh takes the LDS path; a lone big mesh may use most of a CU's LDS, a batch keeps its blobs small
-				uint32_t ring, pool, symwin;
-				uint32_t scale = ctx->topo.scale, pool_q8 = ctx->topo.pool_q8, need;
-				// as much of what the context has learnt as fits a CU
-				for(;;) {
-					topo_lds_geometry(nface, L.clers.size, TOPO_SLOTS_MAX, scale, pool_q8, topo_slots(nblobs), ring, pool, symwin, ctx->topo.pool_cap);
-					// every delayed edge is a pool record: same capacity
-					need = topo_lds_bytes(ring, pool, pool, symwin);
-#ifdef CORTO_TOPO_STAMPS
-					if(need <= 32768 && L.clers.size < 8190) need = 65536;              // (the dispatch trace: k_mesh.hip TOPO_ASM_STAMP)
-#endif
-					if(need <= TOPO_LDS_MAX || (scale == 1 && pool_q8 == 8)) break;
-					if(pool_q8 > 8 && (pool > ring || scale == 1)) pool_q8 = std::max(8u, pool_q8/2); else scale >>= 1;
-				}
-				if(need <= TOPO_LDS_MAX) {
-					t.lds_ring = ring; t.lds_pool = pool; t.lds_delayed_cap = pool; t.lds_symwin = symwin;
-					// (split into two launches below)
-					pl.topo_lds_ids.v.push_back((uint32_t)pl.topo.v.size()); pl.topo_need.push_back(need);
-				}
-				else pl.topo_glob_ids.v.push_back((uint32_t)pl.topo.v.size());
-			}
-			pl.topo.v.push_back(t);
-		}
-		// position attribute (needed by ESTIMATED/BORDER normals)
-		int pos_k = -1, uv_k = -1;
-		for(size_t k = 0; k < L.attrs.size(); k++) { if(L.h.attrs[k].name == "position") pos_k = (int)k; if(L.h.attrs[k].name == "uv") uv_k = (int)k; }
-		// computed tangents read the integer positions AND the integer uvs, behind every normal kernel: neither K-DELTA nor the fused normal
-		// kernel may turn them into floats on the way - both fall to k_dequant, which runs behind the tangent kernels
-		const bool tangents = computes_tangents(P);
-		// ... and so do meshlet bounds, behind the meshlet kernels: the integer positions last until k_dequant
-		const bool bounds = bounds_meshlets(P);
-		// who turns the integer positions into floats: estimated normals read them as integers after K-DELTA, so the fused normal
-		// kernel does it as their last reader (pos_by_normal), the separate normal kernels leave it to k_dequant behind them, and
-		// without such normals K-DELTA does it on the way out of LDS like for every other attribute
-		bool pos_ints_needed = false, pos_by_normal = false;
-		{
-			uint32_t readers = 0;
-			for(size_t k = 0; k < L.attrs.size(); k++)
-				if(mesh && L.h.attrs[k].codec == CRTHIP_CODEC_NORMAL && P.bind[k].buffer && (L.attrs[k].normal_prediction == 1 ||
-					L.attrs[k].normal_prediction == 2)) readers++;
-			if(computes_normals(P)) readers++;                        // computed normals read the integer positions as a stored estimate does
-			pos_ints_needed = readers > 0 || tangents || bounds;
-			pos_by_normal = !tangents && !bounds && readers == 1 && normal_fused(nvert, nface) && pos_k >= 0 && P.bind[pos_k].format == CRTHIP_FMT_FLOAT;
-		}
-
-		for(size_t k = 0; k < L.attrs.size(); k++) {
-			const AttrHeader &a = L.h.attrs[k];
-			const AttrStreams &as = L.attrs[k];
-			const Binding &bd = P.bind[k];
-			if(!bd.buffer) continue;
-			AttrScratch &A = S.attr[k];
-			const uint32_t *words = (const uint32_t *)(arena + bo + as.bits.words_off);
-			const uint32_t chain0 = unpack_chunks;
-			uint64_t attr_logs = 0;
-			for(const StreamRef &lg : as.logs) attr_logs += lg.size;
-			// one wave per stream, no look-back; its bit cursors are 32-bit (k_stream.hip)
-			const bool by_wave = attr_logs <= UNPACK_WAVE_MAX_LOGS && as.bits.nwords < (1u << 26) && !ctx->dbg.unpack_chunked;
-			const uint32_t attr_first = (uint32_t)pl.unpack.v.size();
-			auto push_unpack = [&](const StreamRef &s, const uint8_t *logs, void *out, uint8_t mode, uint16_t fields, uint16_t stride,
-				uint16_t comp, uint8_t out_kind) {
-				if(s.size == 0) return;
-				UnpackJob u{};
-				u.logs = logs; u.words = words; u.out = out; u.count = s.size; u.nwords = as.bits.nwords; u.out_limit = nvert;
-				u.chunk0 = unpack_chunks; u.chain_chunk0 = chain0; u.fields = fields; u.stride = stride; u.comp = comp; u.mode = mode;
-				u.out_kind = out_kind;
-				if(by_wave) { u.chain_chunk0 = attr_first; pl.unpack_wave_ids.v.push_back((uint32_t)pl.unpack.v.size()); }
-				else {
-					const uint32_t nc = (s.size + CHUNK - 1)/CHUNK;
-					for(uint32_t c = 0; c < nc; c++) pl.unpack_chunk_job.v.push_back((uint32_t)pl.unpack.v.size());
-					unpack_chunks += nc;
-				}
-				pl.unpack.v.push_back(u);
-			};
-			// K-BIT hands its values on as int16 where that is PROVEN to hold them: the attribute's log streams are Tunstall-coded and no width in their tables
-			// exceeds 16 bits (decodeArray: v in [-2^(d-1), 2^(d-1)); decodeValues folds the sign the other way: |v| < 2^d, 15 bits), the consumer reads
-			// halfwords (k_delta_lds16 on 16-bit records, k_normal_blob), and the stream goes a wave a stream.  Half the bytes of that round trip through HBM
-			auto widths_fit = [&](const StreamRef &s, uint32_t bits) { return s.mode != STREAM_RAW && s.max_sym <= bits; };
-			bool hand_i16 = false;
-			if(mesh && by_wave && !wide && !ctx->dbg.values_i32 && nvert > 1) {
-				if(a.codec == CRTHIP_CODEC_NORMAL) hand_i16 = as.normal_prediction != 0 && normal_fused(nvert, nface) && widths_fit(as.logs[0], 16);
-				else if(a.codec != CRTHIP_CODEC_COLOR && !bd.stream_values) {
-					DeltaJob probe{};
-					probe.nvert = nvert; probe.N = a.N;
-					hand_i16 = delta_in_lds(probe, wide);
-					if(a.strategy & CRTHIP_CORRELATED) hand_i16 = hand_i16 && widths_fit(as.logs[0], 16);
-					else for(uint32_t c = 0; c < a.N && hand_i16; c++) hand_i16 = widths_fit(as.logs[c], 15);
-				}
-			}
-			const uint8_t val_fmt = hand_i16 ? UNPACK_OUT_I16 : UNPACK_OUT_I32;
-			std::vector<const uint8_t *> &logs = ctx->plan_logs;
-			logs.assign(as.logs.size(), nullptr);
-			for(size_t j = 0; j < as.logs.size(); j++) logs[j] = add_stream(as.logs[j], A.sym[j], bo);
-
-			void *values = nullptr; uint8_t is_u8 = 0; uint32_t N = a.N; bool para = false; bool do_delta = true;
-			if(a.codec == CRTHIP_CODEC_NORMAL) {
-				push_unpack(as.logs[0], logs[0], SP(A.diffs), 0, 2, 2, 0, val_fmt);
-				// a (malformed) stream with fewer diffs than vertices: upstream's vector is zero-filled behind them
-				// (normal_attribute.cpp:180-184)
-				// (only DIFF reads all nvert entries; the other predictions stop at ndiffs)
-				if(as.normal_prediction == 0 && as.logs[0].size < nvert) pl.fill.v.push_back(FillJob{SP(A.diffs +
-					(uint64_t)as.logs[0].size*8), (nvert - as.logs[0].size)*8u, 0u});
-				values = SP(A.diffs); N = 2; para = false;
-				do_delta = as.normal_prediction == 0;                     // DIFF only (normal_attribute.cpp:190-191)
-			} else if(a.codec == CRTHIP_CODEC_COLOR) {
-				for(uint32_t c = 0; c < a.N; c++) push_unpack(as.logs[c], logs[c], SP(A.color), 1, 1, (uint16_t)a.N, (uint16_t)c, UNPACK_OUT_U8);
-				values = SP(A.color); is_u8 = 1; para = (a.strategy & CRTHIP_PARALLEL) != 0;
-			} else {
-				// packed output: the caller's buffer is the int32 workspace (like upstream, vertex_attribute.h:190-193); with a stride, or
-				// as
-				// DOUBLE (eight bytes a value: upstream widens in place, front to back): scratch
-				const bool in_scratch = generic_in_scratch(bd);                  // (or as uint16 grid values: CRTHIP_BIND_QUANTIZED)
-				void *work = in_scratch ? (void *)SP(A.vals) : bd.buffer;
-				if(a.strategy & CRTHIP_CORRELATED) push_unpack(as.logs[0], logs[0], work, 0, (uint16_t)a.N, (uint16_t)a.N, 0, val_fmt);
-				else for(uint32_t c = 0; c < a.N; c++) push_unpack(as.logs[c], logs[c], work, 1, 1, (uint16_t)a.N, (uint16_t)c, val_fmt);
-				values = work; para = (a.strategy & CRTHIP_PARALLEL) != 0;
-				// the device half of a caller-supplied codec object (CRTHIP_BIND_STREAM_VALUES): the stream's int32 values stay as they are -
-				// GenericAttr<int>::decode's result (vertex_attribute.h:151-156); deltaDecode / dequantize are the caller's, on the host
-				if(bd.stream_values) continue;
-			}
-			bool dequantised = false;                                // by K-DELTA or by the fused normal kernel: no k_dequant job
-			if(do_delta && nvert > 1) {
-				if(mesh) {
-					DeltaJob d{};
-					d.values = values; d.pred = (const uint32_t *)SP(S.pred); d.nvert = nvert; d.N = N;
-					d.parallelogram = para; d.is_u8 = is_u8; d.in_i16 = hand_i16; d.wide = wide; d.rounds = ctx->dbg.delta_rounds ? 1u : 0u;
-					d.progress = S.progress != ~0ull ? SP(S.progress) : nullptr;   // (k_delta_tiles)
-					d.flags = hs_base + hs.delta_flags(i);
-					// (k_delta_tiles reports a progress word that never came in the blob's status word)
-					d.status_back = (uint32_t)(hs.delta_flags(i) - hs.status(i));
-					if(a.codec != CRTHIP_CODEC_NORMAL && delta_in_lds(d, wide)) {
-						if(a.codec == CRTHIP_CODEC_COLOR) {
-							d.deq = 2; d.out = bd.buffer; d.out_components = bd.out_components; d.out_stride = bd.stride;
-							for(int c = 0; c < 4; c++) d.qc[c] = as.qc[c];
-							dequantised = true;
-						} else if(!bd.stride && bd.format == CRTHIP_FMT_FLOAT && !((int)k == pos_k && pos_ints_needed) && !((int)k == uv_k && tangents)) { d.deq = 1; d.q =
-							a.q; dequantised = true; }
-					}
-					for(uint32_t f = 0; f < N; f += 4) { d.first = f; pl.delta.v.push_back(d); }   // more than four components: k_delta_tiles jobs of four
-				} else {
-					CloudJob c{};
-					c.values = values; c.nvert = nvert; c.N = N; c.chunk0 = cloud_chunks; c.is_u8 = is_u8;
-					const uint32_t nc = N*((nvert + CHUNK - 1)/CHUNK);
-					for(uint32_t q = 0; q < nc; q++) pl.cloud_chunk_job.v.push_back((uint32_t)pl.cloud.v.size());
-					cloud_chunks += nc;
-					pl.cloud.v.push_back(c);
-				}
-			}
-			if(a.codec == CRTHIP_CODEC_NORMAL) {
-				const uint32_t pr = as.normal_prediction;
-				if(pr == 0 || (mesh && (pr == 1 || pr == 2))) {       // clouds: postDelta never runs (decoder.cpp:142-143)
-					NormalJob n{};
-					n.diffs = (int32_t *)SP(A.diffs); n.out = bd.buffer; n.nvert = nvert; n.nface = nface;
-					n.out_stride = bd.stride ? bd.stride : (bd.format == CRTHIP_FMT_INT16 ? 6u : 12u);
-					n.ndiffs = std::min(as.logs[0].size, nvert); n.unit = f2i_x86_host(a.q);
-					n.prediction = (uint8_t)pr; n.out_i16 = bd.format == CRTHIP_FMT_INT16;
-					n.status = hs_base + hs.status(i);
-					if(pr != 0) {
-						// (a position under a caller-supplied codec holds stream values, not positions: upstream throws there too, normal_attribute.cpp:210-213)
-						const bool pos_ok = pos_k >= 0 && L.h.attrs[pos_k].codec == CRTHIP_CODEC_GENERIC && L.h.attrs[pos_k].N == 3 &&
-							P.bind[pos_k].buffer && !P.bind[pos_k].stream_values;
-						if(!pos_ok) { P.host_status = CRTHIP_E_NORMAL_NEEDS_POSITION; continue; }
-						// the integer positions: in the caller's packed buffer, or in scratch
-						const bool pos_scratch = generic_in_scratch(P.bind[pos_k]);
-						n.position = pos_scratch ? (const int32_t *)SP(S.attr[pos_k].vals) : (const int32_t *)P.bind[pos_k].buffer;
-						n.faces = P.index ? P.index : (void *)SP(S.faces);
-						n.faces_u16 = P.index ? (uint8_t)P.index_u16 : 0;
-						if(normal_fused(nvert, nface)) {
-							n.fused = 1; n.diffs_i16 = hand_i16;
-							n.fn_scratch = A.facen != ~0ull ? (float *)SP(A.facen) : nullptr;
-							if(pos_by_normal) { n.pos_out = P.bind[pos_k].buffer; n.pos_stride = P.bind[pos_k].stride ?
-								P.bind[pos_k].stride : 12u; n.pos_q = L.h.attrs[pos_k].q; }
-							pl.normal_fused_ids.v.push_back((uint32_t)pl.normal.v.size());
-							pl.normal_fused_lds = std::max(pl.normal_fused_lds, normal_blob_lds_fn(nvert, nface) <= ctx->normal_fn_max ?
-								normal_blob_lds_fn(nvert, nface) : normal_blob_lds(nvert, nface));
-						} else {
-							n.vbase = est_vbase; n.fbase = est_fbase; est_vbase += nvert; est_fbase += nface;
-							pl.any_est_normal = true;
-						}
-					} else pl.any_diff_normal = true;
-					pl.normal.v.push_back(n);
-				}
-			} else if(bd.quantized) {
-				// the second finisher of the scratch path: uint16 relative to the minimum + the record (k_quant_out.hip).  No vertex: no job (upload fills the record)
-				if(nvert == 0) continue;
-				QuantOutJob q{};
-				q.values = (const int32_t *)SP(A.vals); q.buffer = bd.buffer; q.stride = bd.stride; q.nvert = nvert; q.N = a.N; q.q = a.q;
-				q.rec_host = (QuantOutRecord *)((crthip_quant_transform *)rec_host + rec0 + k);
-				q.rec_dev = b->quant_dev ? (QuantOutRecord *)((crthip_quant_transform *)b->quant_dev + rec0 + k) : nullptr;
-				q.status = hs_base + hs.status(i);
-				if(nvert <= qout_blob_max()) pl.quant_blob_ids.v.push_back((uint32_t)pl.quant.v.size());
-				else {
-					q.range = (uint32_t *)SP(A.qrange);
-					q.block0 = (uint32_t)pl.quant_block_job.v.size();
-					for(uint32_t c = 0; c < (nvert + QOUT_BLOCK - 1)/QOUT_BLOCK; c++) pl.quant_block_job.v.push_back((uint32_t)pl.quant.v.size());
-					// the seed of k_quant_range's integer atomics rides with the entropy stage's fills: 0xFF.. the minima, 0 the maxima (quant_out.h: qout_bias)
-					pl.fill.v.push_back(FillJob{SP(A.qrange), 16u, 0xFFu}); pl.fill.v.push_back(FillJob{SP(A.qrange + 16), 16u, 0u});
-				}
-				pl.quant.v.push_back(q);
-			} else if(!dequantised && !((int)k == pos_k && pos_by_normal)) {
-				DequantJob q{};
-				q.buffer = bd.buffer; q.q = a.q; q.nvert = nvert; q.N = a.N; q.out_components = bd.out_components;
-				for(int c = 0; c < 4; c++) q.qc[c] = as.qc[c];
-				q.block0 = (uint32_t)pl.dequant_block_job.v.size();
-				q.is_color = a.codec == CRTHIP_CODEC_COLOR;
-				q.format = q.is_color ? (uint8_t)CRTHIP_FMT_FLOAT : (uint8_t)bd.format;
-				q.stride = bd.stride;
-				if(q.is_color) q.src = SP(A.color);
-				else if(bd.stride || bd.format == CRTHIP_FMT_DOUBLE) q.src = SP(A.vals);
-				const uint64_t elems = q.is_color ? nvert : (uint64_t)nvert*a.N;
-				const uint32_t nb = (uint32_t)((elems + CHUNK - 1)/CHUNK);
-				for(uint32_t c = 0; c < nb; c++) pl.dequant_block_job.v.push_back((uint32_t)pl.dequant.v.size());
-				pl.dequant.v.push_back(q);
-			}
-		}
-		// normals for a blob that stores (or binds) none: crthip_batch_bind_computed_normals.  An ESTIMATED job without corrections - no stream, no
-		// K-BIT job, nothing of the entropy stage; position, faces, the fused kernel's last-reader duty and the batch-wide slices as above
-		if(computes_normals(P)) {
-			const Binding &bd = P.computed;
-			NormalJob n{};
-			n.out = bd.buffer; n.nvert = nvert; n.nface = nface;
-			n.out_stride = bd.stride ? bd.stride : (bd.format == CRTHIP_FMT_INT16 ? 6u : 12u);
-			n.prediction = 3; n.out_i16 = bd.format == CRTHIP_FMT_INT16;
-			n.status = hs_base + hs.status(i);
-			// (the bind call checked this; a blob that fails it decodes nothing into the buffer)
-			const bool pos_ok = pos_k >= 0 && L.h.attrs[pos_k].codec == CRTHIP_CODEC_GENERIC && L.h.attrs[pos_k].N == 3 &&
-				P.bind[pos_k].buffer && !P.bind[pos_k].stream_values;
-			if(!pos_ok) { P.host_status = CRTHIP_E_NORMAL_NEEDS_POSITION; continue; }
-			const bool pos_scratch = generic_in_scratch(P.bind[pos_k]);
-			n.position = pos_scratch ? (const int32_t *)SP(S.attr[pos_k].vals) : (const int32_t *)P.bind[pos_k].buffer;
-			n.faces = P.index ? P.index : (void *)SP(S.faces);
-			n.faces_u16 = P.index ? (uint8_t)P.index_u16 : 0;
-			if(normal_fused(nvert, nface)) {
-				n.fused = 1;
-				n.fn_scratch = S.cn_facen != ~0ull ? (float *)SP(S.cn_facen) : nullptr;
-				if(pos_by_normal) { n.pos_out = P.bind[pos_k].buffer; n.pos_stride = P.bind[pos_k].stride ? P.bind[pos_k].stride : 12u;
-					n.pos_q = L.h.attrs[pos_k].q; }
-				pl.normal_computed_ids.v.push_back((uint32_t)pl.normal.v.size());
-				pl.normal_computed_lds = std::max(pl.normal_computed_lds, normal_blob_lds_fn(nvert, nface) <= ctx->normal_fn_max ?
-					normal_blob_lds_fn(nvert, nface) : normal_blob_lds(nvert, nface));
-			} else {
-				n.vbase = est_vbase; n.fbase = est_fbase; est_vbase += nvert; est_fbase += nface;
-				pl.any_est_normal = true;
-			}
-			pl.normal.v.push_back(n);
-		}
-		// tangents: crthip_batch_bind_computed_tangents.  The integers where K-DELTA left them (the caller's packed buffer, or scratch), the index, the
-		// normals where their binding puts them.  (The bind call checked all of it; a blob that fails it here gets no job)
-		if(tangents) {
-			const Binding &bd = P.tangent;
-			auto generic_ok = [&](int k, uint32_t N) { return k >= 0 && L.h.attrs[k].codec == CRTHIP_CODEC_GENERIC && L.h.attrs[k].N == N && P.bind[k].buffer && !P.bind[k].stream_values; };
-			const Binding *nb = computes_normals(P) ? &P.computed : nullptr;
-			for(size_t k = 0; k < L.attrs.size() && !nb; k++)
-				if(L.h.attrs[k].name == "normal" && L.h.attrs[k].codec == CRTHIP_CODEC_NORMAL && P.bind[k].buffer) nb = &P.bind[k];
-			if(!generic_ok(pos_k, 3)) { P.host_status = CRTHIP_E_NORMAL_NEEDS_POSITION; continue; }
-			if(!generic_ok(uv_k, 2) || !nb) { P.host_status = CRTHIP_E_ARGUMENT; continue; }
-			auto ints_of = [&](int k) { return generic_in_scratch(P.bind[k]) ? (const int32_t *)SP(S.attr[k].vals) : (const int32_t *)P.bind[k].buffer; };
-			TangentJob t{};
-			t.position = ints_of(pos_k); t.uv = ints_of(uv_k);
-			t.faces = P.index ? P.index : (void *)SP(S.faces); t.faces_u16 = P.index ? (uint8_t)P.index_u16 : 0;
-			t.normal = nb->buffer; t.normal_i16 = nb->format == CRTHIP_FMT_INT16;
-			t.normal_stride = nb->stride ? nb->stride : (t.normal_i16 ? 6u : 12u);
-			t.out = bd.buffer; t.out_i16 = bd.format == CRTHIP_FMT_INT16; t.out_stride = bd.stride ? bd.stride : (t.out_i16 ? 8u : 16u);
-			t.nvert = nvert; t.nface = nface;
-			if(tangent_in_blob(nvert)) {
-				pl.tangent_blob_ids.v.push_back((uint32_t)pl.tangent.v.size());
-				pl.tangent_lds = std::max(pl.tangent_lds, tangent_blob_lds(nvert));
-			} else {
-				t.acc = (uint64_t *)SP(S.tan_acc);
-				t.fblock0 = (uint32_t)pl.tan_fblock_job.v.size(); t.vblock0 = (uint32_t)pl.tan_vblock_job.v.size();
-				for(uint32_t c = 0; c < (nface + TAN_BLOCK - 1)/TAN_BLOCK; c++) pl.tan_fblock_job.v.push_back((uint32_t)pl.tangent.v.size());
-				for(uint32_t c = 0; c < (nvert + TAN_BLOCK - 1)/TAN_BLOCK; c++) pl.tan_vblock_job.v.push_back((uint32_t)pl.tangent.v.size());
-			}
-			pl.tangent.v.push_back(t);
-		}
-		// meshlets: crthip_batch_bind_meshlets.  The index where the automaton leaves it, the cuts made here from the group table (in aux_u32 behind
-		// the group lists), the caller's arrays; scratch for a blob of more than one segment.  (The bind call checked all of it)
-		if(builds_meshlets(P)) {
-			const crthip_meshlet_binding &mb = P.meshlets;
-			std::vector<MltSeg> segs; crthip_meshlet_counts bound;
-			if(!mlt_plan(nface, (uint32_t)L.group_end.size(), L.group_end.data(), mb.max_vertices, mb.max_triangles, mb.segment_faces, &segs, bound) ||
-				meshlet_binding_error(&mb, true, bound) || (bound.segments > 1 && S.mlt == ~0ull)) { P.host_status = CRTHIP_E_ARGUMENT; continue; }
-			MeshletJob m{};
-			m.faces = P.index ? P.index : (void *)SP(S.faces); m.faces_u16 = P.index ? (uint8_t)P.index_u16 : 0;
-			while(pl.aux_u32.v.size() % 4) pl.aux_u32.v.push_back(0);             // (an MltSeg is read as one 16-byte word)
-			m.segs = (const void *)(uintptr_t)(pl.aux_u32.v.size()*4);            // bytes into aux_u32 (resolved by upload)
-			for(const MltSeg &sg : segs) { pl.aux_u32.v.push_back(sg.f0); pl.aux_u32.v.push_back(sg.f1); pl.aux_u32.v.push_back(sg.mbase); pl.aux_u32.v.push_back(sg.tbase); }
-			m.meshlets = mb.meshlets; m.vertices = mb.vertices; m.triangles = mb.triangles;
-			m.rec_host = (uint8_t *)hs_base + hs.meshlet_records(pl.quant_records) + (size_t)i*sizeof(crthip_meshlet_counts); m.rec_dev = mb.counts;
-			m.nface = nface; m.nseg = bound.segments; m.max_vertices = mb.max_vertices; m.max_triangles = mb.max_triangles;
-			if(bound.segments > 1) {
-				const MltScratchLayout lay = mlt_scratch_layout(nface, bound);
-				m.scratch = SP(S.mlt); m.sc_vertices = (uint32_t)lay.vertices; m.sc_triangles = (uint32_t)lay.triangles; m.sc_counts = (uint32_t)lay.counts;
-			}
-			if(bound.segments <= MESHLET_BLOB_SEGS) {
-				pl.meshlet_blob_ids.v.push_back((uint32_t)pl.meshlet.v.size());
-				pl.meshlet_waves = std::max(pl.meshlet_waves, bound.segments);
-			} else {
-				m.block0 = (uint32_t)pl.mlt_block_job.v.size();
-				for(uint32_t c = 0; c < bound.segments; c++) pl.mlt_block_job.v.push_back((uint32_t)pl.meshlet.v.size());
-			}
-			// meshlet bounds: crthip_batch_bind_meshlet_bounds.  The integer positions as the tangents take them, the arrays above, and the blob's counts
-			// in DEVICE memory: the binding's own copy, or one in scratch that the meshlet kernels write in its place.  (The bind call checked all of it)
-			if(bounds) {
-				const bool pos_ok = pos_k >= 0 && L.h.attrs[pos_k].codec == CRTHIP_CODEC_GENERIC && L.h.attrs[pos_k].N == 3 && P.bind[pos_k].buffer && !P.bind[pos_k].stream_values;
-				if(!pos_ok || (!mb.counts && S.mlt_counts == ~0ull)) P.host_status = pos_ok ? CRTHIP_E_ARGUMENT : CRTHIP_E_NORMAL_NEEDS_POSITION;
-			}
-			if(bounds && !P.host_status) {
-				if(!mb.counts) m.rec_dev = SP(S.mlt_counts);
-				MeshletBoundsJob q{};
-				q.position = generic_in_scratch(P.bind[pos_k]) ? (const int32_t *)SP(S.attr[pos_k].vals) : (const int32_t *)P.bind[pos_k].buffer;
-				q.meshlets = mb.meshlets; q.vertices = mb.vertices; q.triangles = mb.triangles; q.counts = m.rec_dev; q.out = P.meshlet_bounds;
-				q.nvert = nvert; q.capacity = bound.meshlets;
-				q.block0 = (uint32_t)pl.mlb_block_job.v.size();
-				for(uint32_t c = 0; c < (bound.meshlets + MB_WAVES - 1)/MB_WAVES; c++) pl.mlb_block_job.v.push_back((uint32_t)pl.meshlet_bounds.v.size());
-				pl.meshlet_bounds.v.push_back(q);
-			}
-			pl.meshlet.v.push_back(m);
-		}
+		const BlobView v = view_of(i, rec0);
+		if(v.mesh) topo_job(v);
+		for(size_t k = 0; k < v.L.attrs.size(); k++) attr_jobs(v, k);       // (a refused stored normal skips that attribute alone)
+		// the derived outputs, each behind what it reads.  The bind calls checked them; one that is refused here all the same has set the blob's
+		// host_status, and the blob gets no later derived job
+		if(computes_normals(v.P) && !computed_normal_job(v)) continue;
+		if(v.tangents && !tangent_job(v)) continue;
+		if(builds_meshlets(v.P)) meshlet_jobs(v);
 	}
 	return CRTHIP_OK;
 }
 
+Planner::BlobView Planner::view_of(uint32_t i, size_t rec0) {
+	BlobPlan &P = b->blobs[i]; const BlobLayout &L = P.L;
+	const bool mesh = L.h.nface > 0; const uint32_t nvert = L.h.nvert, nface = L.h.nface;
+	// position attribute (needed by ESTIMATED/BORDER normals)
+	const int pos_k = attr_named(P, "position"), uv_k = attr_named(P, "uv");
+	// computed tangents read the integer positions AND the integer uvs, behind every normal kernel: neither K-DELTA nor the fused normal
+	// kernel may turn them into floats on the way - both fall to k_dequant, which runs behind the tangent kernels
+	const bool tangents = computes_tangents(P);
+	// ... and so do meshlet bounds, behind the meshlet kernels: the integer positions last until k_dequant
+	const bool bounds = bounds_meshlets(P);
+	// who turns the integer positions into floats: estimated normals read them as integers after K-DELTA, so the fused normal
+	// kernel does it as their last reader (pos_by_normal), the separate normal kernels leave it to k_dequant behind them, and
+	// without such normals K-DELTA does it on the way out of LDS like for every other attribute
+	uint32_t readers = 0;
+	for(size_t k = 0; k < L.attrs.size(); k++)
+		if(mesh && L.h.attrs[k].codec == CRTHIP_CODEC_NORMAL && P.bind[k].buffer && (L.attrs[k].normal_prediction == 1 ||
+			L.attrs[k].normal_prediction == 2)) readers++;
+	if(computes_normals(P)) readers++;                        // computed normals read the integer positions as a stored estimate does
+	const bool pos_ints_needed = readers > 0 || tangents || bounds;
+	const bool pos_by_normal = !tangents && !bounds && readers == 1 && normal_fused(nvert, nface) && pos_k >= 0 && P.bind[pos_k].format == CRTHIP_FMT_FLOAT;
+	return BlobView{i, P, L, bs[i], mesh, nvert, nface, pos_k, uv_k, tangents, bounds, pos_ints_needed, pos_by_normal, rec0};
+}
+
+void Planner::topo_job(const BlobView &v) {
+	BlobPlan &P = v.P; const BlobLayout &L = v.L; BlobScratch &S = v.S;
+	const uint64_t bo = P.arena_off;
+	P.clers_in_arena = L.clers.mode == STREAM_RAW;
+	P.dbg_clers = L.clers.mode == STREAM_RAW ? bo + L.clers.payload_off : S.clers;
+	P.dbg_nclers = L.clers.size; P.dbg_pred = S.pred;
+	TopoJob t{};
+	t.clers = ctx->plan_clers[v.i];
+	t.split_words = (const uint32_t *)(arena + bo + L.split.words_off);
+	t.group_end = (const uint32_t *)(uintptr_t)(pl.aux_u32.v.size()*4);   // bytes into aux_u32 (resolved by upload)
+	for(uint32_t ge : L.group_end) pl.aux_u32.v.push_back(ge);
+	const Faces f = faces_of(v.i); t.faces = f.p; t.faces_u16 = f.u16;
+	t.pred = (uint32_t *)SP(S.pred);
+	t.front_a = (uint4 *)SP(S.front_a); t.front_b = (uint2 *)SP(S.front_b);
+	t.order = (uint32_t *)SP(S.order); t.delayed = (uint32_t *)SP(S.delayed);
+	t.status = hs_base + hs.status(v.i);
+	t.flags = hs_base + hs.topo_flags(v.i);
+	t.nclers = L.clers.size; t.split_nwords = L.split.nwords; t.ngroups = (uint32_t)L.group_end.size();
+	t.nvert = v.nvert; t.nface = v.nface; t.front_cap = S.front_cap;
+	t.opts = S.progress != ~0ull ? TOPO_OPT_PROGRESS : 0u;
+	// every mesh takes the LDS path; a lone big mesh may use most of a CU's LDS, a batch keeps its blobs small
+	uint32_t ring, pool, symwin;
+	uint32_t scale = ctx->topo.scale, pool_q8 = ctx->topo.pool_q8, need;
+	// as much of what the context has learnt as fits a CU
+	for(;;) {
+		topo_lds_geometry(v.nface, L.clers.size, TOPO_SLOTS_MAX, scale, pool_q8, topo_slots(nblobs), ring, pool, symwin, ctx->topo.pool_cap);
+		// every delayed edge is a pool record: same capacity
+		need = topo_lds_bytes(ring, pool, pool, symwin);
+#ifdef CORTO_TOPO_STAMPS
+		if(need <= 32768 && L.clers.size < 8190) need = 65536;              // (the dispatch trace: k_mesh.hip TOPO_ASM_STAMP)
+#endif
+		if(need <= TOPO_LDS_MAX || (scale == 1 && pool_q8 == 8)) break;
+		if(pool_q8 > 8 && (pool > ring || scale == 1)) pool_q8 = std::max(8u, pool_q8/2); else scale >>= 1;
+	}
+	if(need <= TOPO_LDS_MAX) {
+		t.lds_ring = ring; t.lds_pool = pool; t.lds_delayed_cap = pool; t.lds_symwin = symwin;
+		// (split into two launches below)
+		pl.topo_lds_ids.v.push_back((uint32_t)pl.topo.v.size()); pl.topo_need.push_back(need);
+	}
+	else pl.topo_glob_ids.v.push_back((uint32_t)pl.topo.v.size());
+	pl.topo.v.push_back(t);
+}
+
+// one bound attribute: its log streams, the K-BIT jobs of its bit block, the inverse of its prediction, its finisher
+void Planner::attr_jobs(const BlobView &v, size_t k) {
+	const AttrHeader &a = v.L.h.attrs[k]; const AttrStreams &as = v.L.attrs[k]; const Binding &bd = v.P.bind[k];
+	if(!bd.buffer) return;
+	AttrScratch &A = v.S.attr[k];
+	const uint64_t bo = v.P.arena_off; const uint32_t nvert = v.nvert;
+	uint64_t attr_logs = 0;
+	for(const StreamRef &lg : as.logs) attr_logs += lg.size;
+	// one wave per stream, no look-back; its bit cursors are 32-bit (k_stream.hip)
+	const bool by_wave = attr_logs <= UNPACK_WAVE_MAX_LOGS && as.bits.nwords < (1u << 26) && !ctx->dbg.unpack_chunked;
+	const BitBlock bb{(const uint32_t *)(arena + bo + as.bits.words_off), as.bits.nwords, nvert, unpack_chunks, (uint32_t)pl.unpack.v.size(), by_wave};
+	// K-BIT hands its values on as int16 where that is PROVEN to hold them: the attribute's log streams are Tunstall-coded and no width in their tables
+	// exceeds 16 bits (decodeArray: v in [-2^(d-1), 2^(d-1)); decodeValues folds the sign the other way: |v| < 2^d, 15 bits), the consumer reads
+	// halfwords (k_delta_lds16 on 16-bit records, k_normal_blob), and the stream goes a wave a stream.  Half the bytes of that round trip through HBM
+	auto widths_fit = [&](const StreamRef &s, uint32_t bits) { return s.mode != STREAM_RAW && s.max_sym <= bits; };
+	bool hand_i16 = false;
+	if(v.mesh && by_wave && !wide && !ctx->dbg.values_i32 && nvert > 1) {
+		if(a.codec == CRTHIP_CODEC_NORMAL) hand_i16 = as.normal_prediction != 0 && normal_fused(nvert, v.nface) && widths_fit(as.logs[0], 16);
+		else if(a.codec != CRTHIP_CODEC_COLOR && !bd.stream_values) {
+			DeltaJob probe{};
+			probe.nvert = nvert; probe.N = a.N;
+			hand_i16 = delta_in_lds(probe, wide);
+			if(a.strategy & CRTHIP_CORRELATED) hand_i16 = hand_i16 && widths_fit(as.logs[0], 16);
+			else for(uint32_t c = 0; c < a.N && hand_i16; c++) hand_i16 = widths_fit(as.logs[c], 15);
+		}
+	}
+	const uint8_t val_fmt = hand_i16 ? UNPACK_OUT_I16 : UNPACK_OUT_I32;
+	std::vector<const uint8_t *> &logs = ctx->plan_logs;
+	logs.assign(as.logs.size(), nullptr);
+	for(size_t j = 0; j < as.logs.size(); j++) logs[j] = add_stream(as.logs[j], A.sym[j], bo);
+
+	if(a.codec == CRTHIP_CODEC_NORMAL) {
+		push_unpack(bb, as.logs[0], logs[0], SP(A.diffs), 0, 2, 2, 0, val_fmt);
+		// a (malformed) stream with fewer diffs than vertices: upstream's vector is zero-filled behind them (normal_attribute.cpp:180-184)
+		// (only DIFF reads all nvert entries; the other predictions stop at ndiffs)
+		if(as.normal_prediction == 0 && as.logs[0].size < nvert) pl.fill.v.push_back(FillJob{SP(A.diffs +
+			(uint64_t)as.logs[0].size*8), (nvert - as.logs[0].size)*8u, 0u});
+		// DIFF only (normal_attribute.cpp:190-191)
+		if(as.normal_prediction == 0) inverse_job(v, k, SP(A.diffs), 2, false, 0, hand_i16);
+		stored_normal_job(v, k, hand_i16);
+		return;
+	}
+	bool dequantised;                                        // by K-DELTA (or, the position, by the fused normal kernel): no k_dequant job
+	if(a.codec == CRTHIP_CODEC_COLOR) {
+		for(uint32_t c = 0; c < a.N; c++) push_unpack(bb, as.logs[c], logs[c], SP(A.color), 1, 1, (uint16_t)a.N, (uint16_t)c, UNPACK_OUT_U8);
+		dequantised = inverse_job(v, k, SP(A.color), a.N, (a.strategy & CRTHIP_PARALLEL) != 0, 1, hand_i16);
+	} else {
+		// packed output: the caller's buffer is the int32 workspace (like upstream, vertex_attribute.h:190-193); with a stride, as
+		// DOUBLE (eight bytes a value: upstream widens in place, front to back) or as uint16 grid values (CRTHIP_BIND_QUANTIZED): scratch
+		void *work = ints_of(v.i, k);
+		if(a.strategy & CRTHIP_CORRELATED) push_unpack(bb, as.logs[0], logs[0], work, 0, (uint16_t)a.N, (uint16_t)a.N, 0, val_fmt);
+		else for(uint32_t c = 0; c < a.N; c++) push_unpack(bb, as.logs[c], logs[c], work, 1, 1, (uint16_t)a.N, (uint16_t)c, val_fmt);
+		// the device half of a caller-supplied codec object (CRTHIP_BIND_STREAM_VALUES): the stream's int32 values stay as they are -
+		// GenericAttr<int>::decode's result (vertex_attribute.h:151-156); deltaDecode / dequantize are the caller's, on the host
+		if(bd.stream_values) return;
+		dequantised = inverse_job(v, k, work, a.N, (a.strategy & CRTHIP_PARALLEL) != 0, 0, hand_i16);
+	}
+	if(bd.quantized) quant_job(v, k);
+	else if(!dequantised && !((int)k == v.pos_k && v.pos_by_normal)) dequant_job(v, k);
+}
+
+// the inverse of an attribute's prediction: K-DELTA along the automaton's graph for a mesh, a scan for a cloud.  True: K-DELTA finishes the attribute
+// on its way out of LDS (no k_dequant job)
+bool Planner::inverse_job(const BlobView &v, size_t k, void *values, uint32_t N, bool para, uint8_t is_u8, bool hand_i16) {
+	const AttrHeader &a = v.L.h.attrs[k]; const AttrStreams &as = v.L.attrs[k]; const Binding &bd = v.P.bind[k];
+	const uint32_t nvert = v.nvert;
+	if(nvert <= 1) return false;
+	if(!v.mesh) {
+		CloudJob c{};
+		c.values = values; c.nvert = nvert; c.N = N; c.chunk0 = cloud_chunks; c.is_u8 = is_u8;
+		const uint32_t nc = N*((nvert + CHUNK - 1)/CHUNK);
+		for(uint32_t q = 0; q < nc; q++) pl.cloud_chunk_job.v.push_back((uint32_t)pl.cloud.v.size());
+		cloud_chunks += nc;
+		pl.cloud.v.push_back(c);
+		return false;
+	}
+	bool dequantised = false;
+	DeltaJob d{};
+	d.values = values; d.pred = (const uint32_t *)SP(v.S.pred); d.nvert = nvert; d.N = N;
+	d.parallelogram = para; d.is_u8 = is_u8; d.in_i16 = hand_i16; d.wide = wide; d.rounds = ctx->dbg.delta_rounds ? 1u : 0u;
+	d.progress = v.S.progress != ~0ull ? SP(v.S.progress) : nullptr;   // (k_delta_tiles)
+	d.flags = hs_base + hs.delta_flags(v.i);
+	// (k_delta_tiles reports a progress word that never came in the blob's status word)
+	d.status_back = (uint32_t)(hs.delta_flags(v.i) - hs.status(v.i));
+	if(a.codec != CRTHIP_CODEC_NORMAL && delta_in_lds(d, wide)) {
+		if(a.codec == CRTHIP_CODEC_COLOR) {
+			d.deq = 2; d.out = bd.buffer; d.out_components = bd.out_components; d.out_stride = bd.stride;
+			for(int c = 0; c < 4; c++) d.qc[c] = as.qc[c];
+			dequantised = true;
+		} else if(!bd.stride && bd.format == CRTHIP_FMT_FLOAT && !((int)k == v.pos_k && v.pos_ints_needed) && !((int)k == v.uv_k && v.tangents)) {
+			d.deq = 1; d.q = a.q; dequantised = true;
+		}
+	}
+	for(uint32_t f = 0; f < N; f += 4) { d.first = f; pl.delta.v.push_back(d); }   // more than four components: k_delta_tiles jobs of four
+	return dequantised;
+}
+
+// what ESTIMATED / BORDER normals - stored or computed - share behind their own fields: the integer positions and the index, then either the fused
+// kernel (its id list and LDS request are the caller's: stored and computed normals are two launches; its face normals in `facen` when not in LDS; its
+// duty as the positions' last reader) or a slice of the batch-wide arrays of the separate kernels.  False: no usable position, host_status is set
+bool Planner::estimated_normal_tail(const BlobView &v, NormalJob &n, HostArr<uint32_t> &fused_ids, uint32_t &fused_lds, uint64_t facen) {
+	if(!generic_source_ok(v.P, v.pos_k, 3)) { v.P.host_status = CRTHIP_E_NORMAL_NEEDS_POSITION; return false; }
+	const Binding &pos = v.P.bind[v.pos_k];
+	n.position = ints_of(v.i, v.pos_k);
+	const Faces f = faces_of(v.i); n.faces = f.p; n.faces_u16 = f.u16;
+	if(normal_fused(v.nvert, v.nface)) {
+		n.fused = 1;
+		n.fn_scratch = facen != ~0ull ? (float *)SP(facen) : nullptr;
+		if(v.pos_by_normal) { n.pos_out = pos.buffer; n.pos_stride = pos.stride ? pos.stride : 12u; n.pos_q = v.L.h.attrs[v.pos_k].q; }
+		fused_ids.v.push_back((uint32_t)pl.normal.v.size());
+		fused_lds = std::max(fused_lds, normal_blob_lds_fn(v.nvert, v.nface) <= ctx->normal_fn_max ? normal_blob_lds_fn(v.nvert, v.nface) :
+			normal_blob_lds(v.nvert, v.nface));
+	} else {
+		n.vbase = est_vbase; n.fbase = est_fbase; est_vbase += v.nvert; est_fbase += v.nface;
+		pl.any_est_normal = true;
+	}
+	return true;
+}
+
+void Planner::stored_normal_job(const BlobView &v, size_t k, bool hand_i16) {
+	const AttrStreams &as = v.L.attrs[k]; const Binding &bd = v.P.bind[k]; AttrScratch &A = v.S.attr[k];
+	const uint32_t pr = as.normal_prediction;
+	if(!(pr == 0 || (v.mesh && (pr == 1 || pr == 2)))) return;       // clouds: postDelta never runs (decoder.cpp:142-143)
+	NormalJob n{};
+	n.diffs = (int32_t *)SP(A.diffs); n.out = bd.buffer; n.nvert = v.nvert; n.nface = v.nface;
+	n.out_stride = bd.stride ? bd.stride : (bd.format == CRTHIP_FMT_INT16 ? 6u : 12u);
+	n.ndiffs = std::min(as.logs[0].size, v.nvert); n.unit = f2i_x86_host(v.L.h.attrs[k].q);
+	n.prediction = (uint8_t)pr; n.out_i16 = bd.format == CRTHIP_FMT_INT16;
+	n.status = hs_base + hs.status(v.i);
+	n.diffs_i16 = hand_i16;                                          // (only ever set for a fused estimate: attr_jobs)
+	if(pr == 0) pl.any_diff_normal = true;
+	else if(!estimated_normal_tail(v, n, pl.normal_fused_ids, pl.normal_fused_lds, A.facen)) return;
+	pl.normal.v.push_back(n);
+}
+
+// the second finisher of the scratch path: uint16 relative to the minimum + the record (k_quant_out.hip).  No vertex: no job (upload fills the record)
+void Planner::quant_job(const BlobView &v, size_t k) {
+	const Binding &bd = v.P.bind[k]; AttrScratch &A = v.S.attr[k];
+	const uint32_t nvert = v.nvert;
+	if(nvert == 0) return;
+	QuantOutJob q{};
+	q.values = (const int32_t *)SP(A.vals); q.buffer = bd.buffer; q.stride = bd.stride; q.nvert = nvert; q.N = v.L.h.attrs[k].N; q.q = v.L.h.attrs[k].q;
+	q.rec_host = (QuantOutRecord *)((crthip_quant_transform *)quant_rec_host + v.rec0 + k);
+	q.rec_dev = b->quant_dev ? (QuantOutRecord *)((crthip_quant_transform *)b->quant_dev + v.rec0 + k) : nullptr;
+	q.status = hs_base + hs.status(v.i);
+	if(nvert <= qout_blob_max()) pl.quant_blob_ids.v.push_back((uint32_t)pl.quant.v.size());
+	else {
+		q.range = (uint32_t *)SP(A.qrange);
+		q.block0 = (uint32_t)pl.quant_block_job.v.size();
+		for(uint32_t c = 0; c < (nvert + QOUT_BLOCK - 1)/QOUT_BLOCK; c++) pl.quant_block_job.v.push_back((uint32_t)pl.quant.v.size());
+		// the seed of k_quant_range's integer atomics rides with the entropy stage's fills: 0xFF.. the minima, 0 the maxima (quant_out.h: qout_bias)
+		pl.fill.v.push_back(FillJob{SP(A.qrange), 16u, 0xFFu}); pl.fill.v.push_back(FillJob{SP(A.qrange + 16), 16u, 0u});
+	}
+	pl.quant.v.push_back(q);
+}
+
+void Planner::dequant_job(const BlobView &v, size_t k) {
+	const AttrHeader &a = v.L.h.attrs[k]; const Binding &bd = v.P.bind[k]; AttrScratch &A = v.S.attr[k];
+	DequantJob q{};
+	q.buffer = bd.buffer; q.q = a.q; q.nvert = v.nvert; q.N = a.N; q.out_components = bd.out_components;
+	for(int c = 0; c < 4; c++) q.qc[c] = v.L.attrs[k].qc[c];
+	q.block0 = (uint32_t)pl.dequant_block_job.v.size();
+	q.is_color = a.codec == CRTHIP_CODEC_COLOR;
+	q.format = q.is_color ? (uint8_t)CRTHIP_FMT_FLOAT : (uint8_t)bd.format;
+	q.stride = bd.stride;
+	if(q.is_color) q.src = SP(A.color);
+	else if(bd.stride || bd.format == CRTHIP_FMT_DOUBLE) q.src = SP(A.vals);
+	const uint64_t elems = q.is_color ? v.nvert : (uint64_t)v.nvert*a.N;
+	const uint32_t nb = (uint32_t)((elems + CHUNK - 1)/CHUNK);
+	for(uint32_t c = 0; c < nb; c++) pl.dequant_block_job.v.push_back((uint32_t)pl.dequant.v.size());
+	pl.dequant.v.push_back(q);
+}
+
+// normals for a blob that stores (or binds) none: crthip_batch_bind_computed_normals.  An ESTIMATED job without corrections - no stream, no
+// K-BIT job, nothing of the entropy stage; position, faces, the fused kernel's last-reader duty and the batch-wide slices as for a stored estimate
+bool Planner::computed_normal_job(const BlobView &v) {
+	const Binding &bd = v.P.derived.normals;
+	NormalJob n{};
+	n.out = bd.buffer; n.nvert = v.nvert; n.nface = v.nface;
+	n.out_stride = bd.stride ? bd.stride : (bd.format == CRTHIP_FMT_INT16 ? 6u : 12u);
+	n.prediction = 3; n.out_i16 = bd.format == CRTHIP_FMT_INT16;
+	n.status = hs_base + hs.status(v.i);
+	if(!estimated_normal_tail(v, n, pl.normal_computed_ids, pl.normal_computed_lds, v.S.cn_facen)) return false;
+	pl.normal.v.push_back(n);
+	return true;
+}
+
+// tangents: crthip_batch_bind_computed_tangents.  The integers where K-DELTA left them (the caller's packed buffer, or scratch), the index, the
+// normals where their binding puts them
+bool Planner::tangent_job(const BlobView &v) {
+	const Binding &bd = v.P.derived.tangents;
+	const Binding *nb = tangent_normal_source(v.P);
+	if(!generic_source_ok(v.P, v.pos_k, 3)) { v.P.host_status = CRTHIP_E_NORMAL_NEEDS_POSITION; return false; }
+	if(!generic_source_ok(v.P, v.uv_k, 2) || !nb) { v.P.host_status = CRTHIP_E_ARGUMENT; return false; }
+	const uint32_t nvert = v.nvert, nface = v.nface;
+	TangentJob t{};
+	t.position = ints_of(v.i, v.pos_k); t.uv = ints_of(v.i, v.uv_k);
+	const Faces f = faces_of(v.i); t.faces = f.p; t.faces_u16 = f.u16;
+	t.normal = nb->buffer; t.normal_i16 = nb->format == CRTHIP_FMT_INT16;
+	t.normal_stride = nb->stride ? nb->stride : (t.normal_i16 ? 6u : 12u);
+	t.out = bd.buffer; t.out_i16 = bd.format == CRTHIP_FMT_INT16; t.out_stride = bd.stride ? bd.stride : (t.out_i16 ? 8u : 16u);
+	t.nvert = nvert; t.nface = nface;
+	if(tangent_in_blob(nvert)) {
+		pl.tangent_blob_ids.v.push_back((uint32_t)pl.tangent.v.size());
+		pl.tangent_lds = std::max(pl.tangent_lds, tangent_blob_lds(nvert));
+	} else {
+		t.acc = (uint64_t *)SP(v.S.tan_acc);
+		t.fblock0 = (uint32_t)pl.tan_fblock_job.v.size(); t.vblock0 = (uint32_t)pl.tan_vblock_job.v.size();
+		for(uint32_t c = 0; c < (nface + TAN_BLOCK - 1)/TAN_BLOCK; c++) pl.tan_fblock_job.v.push_back((uint32_t)pl.tangent.v.size());
+		for(uint32_t c = 0; c < (nvert + TAN_BLOCK - 1)/TAN_BLOCK; c++) pl.tan_vblock_job.v.push_back((uint32_t)pl.tangent.v.size());
+	}
+	pl.tangent.v.push_back(t);
+	return true;
+}
+
+// meshlets: crthip_batch_bind_meshlets.  The index where the automaton leaves it, the cuts made here from the group table (in aux_u32 behind
+// the group lists), the caller's arrays; scratch for a blob of more than one segment.  A refused blob gets neither job
+void Planner::meshlet_jobs(const BlobView &v) {
+	const crthip_meshlet_binding &mb = v.P.derived.meshlets;
+	BlobScratch &S = v.S;
+	std::vector<MltSeg> segs; crthip_meshlet_counts bound;
+	if(!mlt_plan_of(v.P, mb, &segs, bound) || meshlet_binding_error(&mb, true, bound) || (bound.segments > 1 && S.mlt == ~0ull)) { v.P.host_status = CRTHIP_E_ARGUMENT; return; }
+	MeshletJob m{};
+	const Faces f = faces_of(v.i); m.faces = f.p; m.faces_u16 = f.u16;
+	while(pl.aux_u32.v.size() % 4) pl.aux_u32.v.push_back(0);             // (an MltSeg is read as one 16-byte word)
+	m.segs = (const void *)(uintptr_t)(pl.aux_u32.v.size()*4);            // bytes into aux_u32 (resolved by upload)
+	for(const MltSeg &sg : segs) { pl.aux_u32.v.push_back(sg.f0); pl.aux_u32.v.push_back(sg.f1); pl.aux_u32.v.push_back(sg.mbase); pl.aux_u32.v.push_back(sg.tbase); }
+	m.meshlets = mb.meshlets; m.vertices = mb.vertices; m.triangles = mb.triangles;
+	m.rec_host = (uint8_t *)hs_base + hs.meshlet_record(v.i); m.rec_dev = mb.counts;
+	m.nface = v.nface; m.nseg = bound.segments; m.max_vertices = mb.max_vertices; m.max_triangles = mb.max_triangles;
+	if(bound.segments > 1) {
+		const MltScratchLayout lay = mlt_scratch_layout(v.nface, bound);
+		m.scratch = SP(S.mlt); m.sc_vertices = (uint32_t)lay.vertices; m.sc_triangles = (uint32_t)lay.triangles; m.sc_counts = (uint32_t)lay.counts;
+	}
+	if(bound.segments <= MESHLET_BLOB_SEGS) {
+		pl.meshlet_blob_ids.v.push_back((uint32_t)pl.meshlet.v.size());
+		pl.meshlet_waves = std::max(pl.meshlet_waves, bound.segments);
+	} else {
+		m.block0 = (uint32_t)pl.mlt_block_job.v.size();
+		for(uint32_t c = 0; c < bound.segments; c++) pl.mlt_block_job.v.push_back((uint32_t)pl.meshlet.v.size());
+	}
+	// meshlet bounds: crthip_batch_bind_meshlet_bounds.  The integer positions as the tangents take them, the arrays above, and the blob's counts
+	// in DEVICE memory: the binding's own copy, or one in scratch that the meshlet kernels write in its place.  Skipped when the blob's host_status
+	// is set, by this check or by anything before it; the meshlet job is pushed all the same
+	if(v.bounds) {
+		const bool pos_ok = generic_source_ok(v.P, v.pos_k, 3);
+		if(!pos_ok || (!mb.counts && S.mlt_counts == ~0ull)) v.P.host_status = pos_ok ? CRTHIP_E_ARGUMENT : CRTHIP_E_NORMAL_NEEDS_POSITION;
+	}
+	if(v.bounds && !v.P.host_status) {
+		if(!mb.counts) m.rec_dev = SP(S.mlt_counts);
+		MeshletBoundsJob q{};
+		q.position = ints_of(v.i, v.pos_k);
+		q.meshlets = mb.meshlets; q.vertices = mb.vertices; q.triangles = mb.triangles; q.counts = m.rec_dev; q.out = v.P.derived.bounds;
+		q.nvert = v.nvert; q.capacity = bound.meshlets;
+		q.block0 = (uint32_t)pl.mlb_block_job.v.size();
+		for(uint32_t c = 0; c < (bound.meshlets + MB_WAVES - 1)/MB_WAVES; c++) pl.mlb_block_job.v.push_back((uint32_t)pl.meshlet_bounds.v.size());
+		pl.meshlet_bounds.v.push_back(q);
+	}
+	pl.meshlet.v.push_back(m);
+}

@@ -35,7 +35,7 @@ int Planner::upload() {
 	stage = (uint8_t *)set.staging.p;
 	memset(stage + (pl.unpack_partial_off - pl.jobs_begin), 0, unpack_state_words*8);
 	// (after the harvest above: the previous batch's words have been read)
-	memset(set.status_host.p, 0, hs.meshlet_records(pl.quant_records) + (pl.meshlet_records ? b->blobs.size()*sizeof(crthip_meshlet_counts) : 0));
+	memset(set.status_host.p, 0, hs.bytes());
 	if(pl.quant_records) {                                               // a quantised attribute of a blob without vertices has no job: its record is all zero, written
 		crthip_quant_transform *rec = (crthip_quant_transform *)((uint8_t *)set.status_host.p + hs.records());
 		for(const BlobPlan &P : b->blobs) {
@@ -365,8 +365,8 @@ void Planner::account() {
 			else if(a.codec == CRTHIP_CODEC_COLOR) ob += (uint64_t)L.h.nvert*P.bind[k].out_components;
 			else ob += (uint64_t)L.h.nvert*a.N*(P.bind[k].quantized ? 2u : generic_work_bytes(P.bind[k].format));
 		}
-		if(computes_normals(P)) ob += (uint64_t)L.h.nvert*3*(P.computed.format == CRTHIP_FMT_INT16 ? 2 : 4);
-		if(computes_tangents(P)) ob += (uint64_t)L.h.nvert*4*(P.tangent.format == CRTHIP_FMT_INT16 ? 2 : 4);
+		if(computes_normals(P)) ob += (uint64_t)L.h.nvert*3*(P.derived.normals.format == CRTHIP_FMT_INT16 ? 2 : 4);
+		if(computes_tangents(P)) ob += (uint64_t)L.h.nvert*4*(P.derived.tangents.format == CRTHIP_FMT_INT16 ? 2 : 4);
 	}
 	b->stats.output_bytes = ob;
 	ctx->in_flight = b; ctx->last_decoded = b;
