@@ -1,6 +1,7 @@
 """crthip_pool_decode: the pool decodes every item exactly once into a block the caller owns.  Everything here is raw-byte equality with the
 oracle (tolerance 0), on items that DIFFER in size and content - with equal items a mix-up of two blocks would be invisible.  Blocks are
 pre-filled with 0xA5: a device block keeps that byte everywhere outside its arrays, any block from the layout's total on."""
+import gc
 import threading
 
 import numpy as np
@@ -83,6 +84,20 @@ def make_blocks(pool, item_list, kinds, slots=None, render=False):
             raw = np.full(n + 256, FILL, dtype=np.uint8)
             blocks.append(raw[(-raw.ctypes.data) % 256:][:n])
     return blocks
+
+
+def own_allocation(n):
+    """a device tensor of n bytes, every byte 0xA5, that is an allocation of its own to the runtime.  torch's cache serves a request from the
+    smallest free block that holds it, and a segment that a live tensor shares - a block that the pool keeps from its last call, say - can have
+    one: such a tensor lies in an allocation larger than itself.  Each one found so is held, so that it fills its hole, until the request
+    reaches the runtime"""
+    plugs = []
+    for _ in range(16):
+        t = torch.full((n,), FILL, dtype=torch.uint8, device="cuda:0")
+        if any(s["address"] == t.data_ptr() and s["total_size"] == n for s in torch.cuda.memory_snapshot()):
+            return t
+        plugs.append(t)
+    raise AssertionError("no allocation of exactly %d bytes after %d tries" % (n, len(plugs)))
 
 
 def block_bytes(block):
@@ -350,14 +365,16 @@ def test_argument_errors_before_any_launch(items):
         refused(pinned, "a pinned host tensor as a device destination", slots=[0, 0, 0])
         del pinned
         # a device tensor too short for the layout, its size overstated.  The runtime's pointer queries see ALLOCATIONS: torch gives a tensor of
-        # 10 MiB or more, a multiple of 2 MiB, an allocation of exactly its size once its cache holds no larger free block
+        # 10 MiB or more, a multiple of 2 MiB, an allocation of exactly its size once its cache holds no larger free block - which own_allocation
+        # sees to, whatever this process allocated before
         short = list(blocks)
         short[1] = None
         del blocks
+        gc.collect()                                                                 # (the refusals' tracebacks are cycles that hold the blocks)
         torch.cuda.empty_cache()
         n_short = totals[1] // (2 << 20) * (2 << 20)
         assert 10 << 20 <= n_short < totals[1]
-        short[1] = torch.full((n_short,), FILL, dtype=torch.uint8, device="cuda:0")
+        short[1] = own_allocation(n_short)
         refused(short, "a device tensor too short for the layout", caps=[None, totals[1] + SPARE, None])
         del short
         res, rep, _, _ = decode_round(pool, sub, "device", "after the refusals")
