@@ -76,6 +76,22 @@ class MeshletCounts(C.Structure):
         return (self.meshlets, self.vertices, self.triangle_bytes, self.segments)
 
 
+NO_TWIN = 0xFFFFFFFF                                 # CRTHIP_NO_TWIN
+
+
+class AdjacencyCounts(C.Structure):
+    """crthip_adjacency_counts: a blob's half-edges, and how many are boundary, duplicate, invalid"""
+    _fields_ = [("halfedges", C.c_uint32), ("boundary", C.c_uint32), ("duplicate", C.c_uint32), ("invalid", C.c_uint32)]
+
+    def as_tuple(self):
+        return (self.halfedges, self.boundary, self.duplicate, self.invalid)
+
+
+class AdjacencyBinding(C.Structure):
+    """crthip_adjacency_binding: the device twin array with its capacity in words, the optional device counts record"""
+    _fields_ = [("twin", C.c_void_p), ("counts", C.c_void_p), ("capacity", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class MeshletBinding(C.Structure):
     """crthip_meshlet_binding: three device arrays with their capacities, the optional device counts record, the builder's parameters"""
     _fields_ = [("meshlets", C.c_void_p), ("vertices", C.c_void_p), ("triangles", C.c_void_p), ("counts", C.c_void_p),
@@ -282,6 +298,8 @@ def lib():
         L.crthip_batch_bind_meshlet_bounds.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.crthip_meshlet_bounds_model.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MeshletCounts), C.c_void_p,
                                                   C.c_uint32, C.c_uint32]
+        L.crthip_batch_bind_adjacency.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(AdjacencyBinding)]
+        L.crthip_adjacency_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(AdjacencyCounts), C.c_int, C.c_uint32]
         L.crthip_batch_meshlet_counts.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshletCounts)]
         L.crthip_meshlet_bound.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(MeshletCounts)]
         L.crthip_meshlet_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(MeshletBinding), C.POINTER(MeshletCounts),
@@ -1009,6 +1027,21 @@ def meshlet_model(index: np.ndarray, groups=(), max_vertices: int = 64, max_tria
     return cut_meshlets(m, v, t, counts) + (counts,)
 
 
+def adjacency_model(index: np.ndarray, nvert: int, which: int = 0, seed: int = 0, fill: int = 0xCD):
+    """crthip_adjacency_model: crthip_batch_bind_adjacency on the host in the kernels' partition (which 0: adjacency_blob; 1: adjacency_count /
+    _offsets / _fill / _twin; workgroups, waves and lanes, and so every atomic's order, shuffled by seed).  index (nface, 3) uint32 or
+    uint16.  The twin array is made here at exactly 3*nface words and filled with `fill` first.  Returns (twin uint32 (3*nface,), AdjacencyCounts)."""
+    idx = np.ascontiguousarray(index)
+    if idx.dtype != np.uint16:
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    idx = idx.reshape(-1, 3)
+    twin = np.full(len(idx) * 3, fill * 0x01010101, np.uint32)
+    counts = AdjacencyCounts()
+    _check(lib().crthip_adjacency_model(_np_ptr(idx) if len(idx) else None, int(idx.dtype == np.uint16), len(idx), nvert, _np_ptr(twin) if len(twin) else None,
+                                        C.byref(counts), which, seed))
+    return twin, counts
+
+
 def meshlet_bounds_model(position: np.ndarray, index, meshlets: np.ndarray, vertices: np.ndarray, triangles: np.ndarray, counts, seed: int = 0,
                          capacity=None, fill: int = 0xCD, raw: bool = False):
     """crthip_meshlet_bounds_model: crthip_batch_bind_meshlet_bounds on the host in the kernel's partition (workgroups, waves and the lanes of
@@ -1227,6 +1260,7 @@ class Batch:
         self._tangents = []                          # ... and behind those, through crthip_batch_bind_computed_tangents
         self._meshlets = {}                          # blob -> (MeshletBinding, the tensors it points into): applied again by rebind() too
         self._meshlet_bounds = {}                    # blob -> (pointer, capacity, the tensor or None): applied again behind those
+        self._adjacency = {}                         # blob -> (AdjacencyBinding, (twin tensor, counts tensor or None) or None): applied again by rebind() too
         self._interleaved = None
 
     def __len__(self):
@@ -1271,7 +1305,7 @@ class Batch:
     # -- outputs -----------------------------------------------------------------------------------
     def allocate_outputs(self, normal_format=FMT_FLOAT, color_components: Optional[int] = None, index16=False,
                          only: Optional[set] = None, fill: Optional[int] = None, computed_normals=False, quantized=(),
-                         computed_tangents=False, tangent_format=FMT_FLOAT, meshlets=None, meshlet_bounds=False):
+                         computed_tangents=False, tangent_format=FMT_FLOAT, meshlets=None, meshlet_bounds=False, adjacency=False):
         """Allocate every output of every blob inside ONE device buffer (torch.uint8) and bind them.
         Returns a list (per blob) of dicts name -> torch tensor view.
         computed_normals: every mesh blob WITHOUT a normal attribute gets a "normal" tensor of normal_format all the same, bound
@@ -1284,7 +1318,9 @@ class Batch:
         meshlets: (max_vertices, max_triangles, segment_faces) - every mesh blob gets its three meshlet arrays at crthip_meshlet_bound and a
         device counts record, bound through crthip_batch_bind_meshlets; read them with meshlets(i) after sync().
         meshlet_bounds: with meshlets=, every mesh blob also gets a crthip_meshlet_bounds array at the bound's meshlets, bound through
-        crthip_batch_bind_meshlet_bounds; read it with meshlet_bounds(i) after sync()."""
+        crthip_batch_bind_meshlet_bounds; read it with meshlet_bounds(i) after sync().
+        adjacency: every mesh blob gets a twin array of 3*nface words and a device counts record, bound through crthip_batch_bind_adjacency;
+        read them with adjacency(i) after sync()."""
         if meshlet_bounds and meshlets is None:
             raise ValueError("allocate_outputs: meshlet_bounds needs meshlets=")
         import torch
@@ -1336,6 +1372,7 @@ class Batch:
                     bd = meshlet_bound(info.nface, self.groups(i), *meshlets)
                     mplan.append((i, bd, take(bd.meshlets * 16), take(bd.vertices * 4), take(bd.triangle_bytes), take(16),
                                   take(bd.meshlets * 48) if meshlet_bounds else None))
+        aplan = [(i, info.nface, take(info.nface * 12), take(16)) for i, info in enumerate(self.infos) if info.nface] if adjacency else []
         total = max(off, 256)
         buf = torch.empty(total, dtype=torch.uint8, device=dev) if fill is None else torch.full((total,), fill, dtype=torch.uint8, device=dev)
         _torch_ready(dev)                            # (the fill runs on torch's stream; the decode on the context's own)
@@ -1352,6 +1389,9 @@ class Batch:
                 self._meshlet_bounds[i] = (base + bo, bd.meshlets, buf[bo:bo + bd.meshlets * 48])
             mb = MeshletBinding(base + mo, base + vo, base + to, base + co, bd.meshlets, bd.vertices, bd.triangle_bytes, *meshlets)
             self._meshlets[i] = (mb, (buf[mo:mo + bd.meshlets * 16], buf[vo:vo + bd.vertices * 4], buf[to:to + bd.triangle_bytes], buf[co:co + 16]))
+        self._adjacency = {}
+        for (i, nf, to, co) in aplan:
+            self._adjacency[i] = (AdjacencyBinding(base + to, base + co, nf * 3, 0), (buf[to:to + nf * 12], buf[co:co + 16]))
         computed, tangents = [], []
         tdt = {"f32": torch.float32, "i16": torch.int16, "u8": torch.uint8, "u32": torch.int32, "u16": torch.int16}
         for (i, name, o, dt, shape, slot, fmt, oc) in plan:
@@ -1424,6 +1464,7 @@ class Batch:
         self._computed = []
         self._tangents = []
         self._meshlets, self._meshlet_bounds = {}, {}
+        self._adjacency = {}
         self._interleaved = metas
         self.outputs = [dict() for _ in self.infos]
         self.rebind()
@@ -1473,6 +1514,8 @@ class Batch:
             _check(lib().crthip_batch_bind_meshlets(self.handle, i, C.byref(mb)))
         for i, (ptr, cap, _) in self._meshlet_bounds.items():   # (... and their bounds)
             _check(lib().crthip_batch_bind_meshlet_bounds(self.handle, i, C.c_void_p(ptr), cap))
+        for i, (ab, _) in self._adjacency.items():              # (... and its adjacency)
+            _check(lib().crthip_batch_bind_adjacency(self.handle, i, C.byref(ab)))
 
     def bind(self, i: int, bindings: Sequence[AttrBinding], index_ptr: Optional[int] = None, index_format=FMT_UINT32):
         arr = (AttrBinding * max(len(bindings), 1))(*bindings)
@@ -1519,6 +1562,25 @@ class Batch:
         c = self.meshlet_counts(i)
         _, _, keep = self._meshlet_bounds[i]
         return keep.cpu().numpy().view(np.uint8).reshape(-1)[:c.meshlets * 48].view(MESHLET_BOUNDS_DTYPE).copy()
+
+    def bind_adjacency(self, i: int, binding: Optional[AdjacencyBinding] = None, keep=None):
+        """crthip_batch_bind_adjacency: blob i's half-edge twins go to the binding's device array (capacity at least 3*nface words).  After bind() /
+        rebind() of that blob, which drop it; None removes it.  keep: whatever owns the memory (device tensors), held with the binding - a
+        tuple (twin, counts or None) makes adjacency(i) work."""
+        if binding is None:
+            self._adjacency.pop(i, None)
+            _check(lib().crthip_batch_bind_adjacency(self.handle, i, None))
+            return
+        _check(lib().crthip_batch_bind_adjacency(self.handle, i, C.byref(binding)))
+        self._adjacency[i] = (binding, keep)
+
+    def adjacency(self, i: int):
+        """Blob i's adjacency on the host: (twin uint32 (3*nface,), the counts as a tuple (halfedges, boundary, duplicate, invalid), or None
+        where the binding has no device record).  After sync(); for bindings made by allocate_outputs(adjacency=True) or bind_adjacency(keep=)."""
+        _, keep = self._adjacency[i]
+        twin = keep[0].cpu().numpy().view(np.uint8).reshape(-1)[:self.infos[i].nface * 12].view(np.uint32).copy()
+        counts = None if len(keep) < 2 or keep[1] is None else tuple(int(x) for x in keep[1].cpu().numpy().view(np.uint8).reshape(-1)[:16].view(np.uint32))
+        return twin, counts
 
     def meshlet_counts(self, i: int) -> MeshletCounts:
         """crthip_batch_meshlet_counts: blob i's totals (meshlets, vertex words, triangle bytes, segments); after sync()"""

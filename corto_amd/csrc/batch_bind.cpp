@@ -1,5 +1,5 @@
-// batch_bind.cpp — what a caller binds to a batch's blobs and what reads a decode's records back: crthip_batch_bind / _bind_all, the four derived
-// outputs (computed normals, computed tangents, meshlets, meshlet bounds: DerivedBindings, batch_internal.h), the quantised attributes' records and the
+// batch_bind.cpp — what a caller binds to a batch's blobs and what reads a decode's records back: crthip_batch_bind / _bind_all, the five derived
+// outputs (computed normals, computed tangents, meshlets, meshlet bounds, adjacency: DerivedBindings, batch_internal.h), the quantised attributes' records and the
 // meshlet counts.  Every check of a binding is made here, in the order corto_hip.h lists its errors, so that a decode has nothing new to fail on.
 // No HIP call: a program without the runtime links these (tests/cpp/plan_dump.cpp).
 #include "batch_internal.h"
@@ -157,6 +157,20 @@ extern "C" int crthip_batch_bind_meshlet_bounds(crthip_batch *b, uint32_t i, crt
 	if(!generic_source_ok(P, attr_named(P, "position"), 3))
 		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "meshlet bounds need a bound three-component \"position\" (bind the blob first)" + who);
 	P.derived.bounds = bounds;
+	b->dirty = true;
+	return CRTHIP_OK;
+}
+
+// The half-edge twins of the blob's decoded index (corto_hip.h has the contract): every check is made here, in the header's order.  It reads the
+// index alone, so no other derived binding drops it and it drops none
+extern "C" int crthip_batch_bind_adjacency(crthip_batch *b, uint32_t i, const crthip_adjacency_binding *a) {
+	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_adjacency: no such blob");
+	BlobPlan &P = b->blobs[i];
+	const std::string who = " (blob " + std::to_string(i) + ")";
+	if(!a) { P.derived.adjacency = crthip_adjacency_binding{}; b->dirty = true; return CRTHIP_OK; }
+	if(P.L.h.nface == 0) return fail(CRTHIP_E_ARGUMENT, "adjacency needs faces: a point cloud has none" + who);
+	if(const char *why = adjacency_binding_error(a, P.L.h.nface)) return fail(CRTHIP_E_ARGUMENT, why + who);
+	P.derived.adjacency = *a;
 	b->dirty = true;
 	return CRTHIP_OK;
 }

@@ -225,10 +225,22 @@ struct MeshletBoundsJob {
 	uint32_t pad;
 };
 
+// a blob bound with crthip_batch_bind_adjacency (k_adjacency.hip, adjacency.h): the index -> the caller's twin array and the blob's record.  A
+// blob whose lists fit LDS (adj_in_blob) needs nothing else; the others keep their ends and entries in scratch
+struct AdjacencyJob {
+	const void *index;             // u32 or, with index_u16, u16 triples: the caller's index, or scratch
+	uint32_t *twin;                // the binding's 3*nface words
+	void *counts;                  // crthip_adjacency_counts in DEVICE memory: the binding's, or (bigger blobs only) scratch; null: none wanted
+	uint32_t *ends, *list;         // bigger blobs: nvert + 1 words zeroed by a FillJob, and 3*nface entries
+	uint32_t nface, nvert;
+	uint32_t block0;               // first block of this job in the block -> job map (adjacency_count, _fill, _twin)
+	uint8_t index_u16, pad[3];
+};
+
 // the layout the kernels read, pinned (TopoJob's size is performance-critical: TOPO_OPT_PROGRESS above)
 static_assert(sizeof(TunStream) == 64 && sizeof(FillJob) == 16 && sizeof(TopoJob) == 136 && sizeof(UnpackJob) == 56 && sizeof(DeltaJob) == 96 &&
               sizeof(CloudJob) == 24 && sizeof(NormalJob) == 104 && sizeof(DequantJob) == 64 && sizeof(QuantOutJob) == 72 && sizeof(TangentJob) == 80 &&
-              sizeof(MeshletJob) == 104 && sizeof(MeshletBoundsJob) == 64, "decode job layout");
+              sizeof(MeshletJob) == 104 && sizeof(MeshletBoundsJob) == 64 && sizeof(AdjacencyJob) == 56, "decode job layout");
 static_assert(offsetof(TopoJob, opts) == 116 && offsetof(UnpackJob, out_kind) == 51 && offsetof(NormalJob, faces_u16) == 58, "decode job layout");
 static_assert(offsetof(DeltaJob, in_i16) == 34 && offsetof(DeltaJob, wide) == 35 && offsetof(DeltaJob, rounds) == 88 &&
               offsetof(DeltaJob, status_back) == 92, "decode job layout");

@@ -69,6 +69,15 @@ __global__ void k_meshlet_place(const MeshletJob *jobs, const uint32_t *block_jo
 // block -> job map with (capacity + 3)/4 blocks a job; waves at or past the blob's count on the device return
 __global__ void k_meshlet_bounds(const MeshletBoundsJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 
+// k_adjacency.hip (crthip_batch_bind_adjacency; adjacency.h has the rule and both partitions): blobs whose lists fit ADJ_BLOB_LDS_MAX by one
+// workgroup each from an id list, with adj_blob_lds(nvert, nface) of dynamic LDS (the launch asks for the largest among them); bigger ones
+// 256 half-edges a block from a block -> job map, with one workgroup a blob (an id list) for the scan between count and fill
+__global__ void k_adjacency_blob(const AdjacencyJob *jobs, const uint32_t *job_ids, uint32_t njobs);
+__global__ void k_adjacency_count(const AdjacencyJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_adjacency_offsets(const AdjacencyJob *jobs, const uint32_t *job_ids, uint32_t njobs);
+__global__ void k_adjacency_fill(const AdjacencyJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_adjacency_twin(const AdjacencyJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+
 // k_mesh.hip
 __global__ void k_topology(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);
 __global__ void k_topology_lds(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);

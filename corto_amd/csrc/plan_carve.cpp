@@ -115,6 +115,10 @@ int Planner::carve() {
 		if(bound.segments > 1) bs[i].mlt = cv.take(mlt_scratch_layout(P.L.h.nface, bound).total, 16);
 		if(bounds_meshlets(P) && !P.derived.meshlets.counts) bs[i].mlt_counts = cv.take(16, 16);   // the device copy of the counts k_meshlet_bounds reads
 	}
+	for(uint32_t i = 0; i < nblobs; i++) {                           // adjacency beyond LDS: the ends (zeroed by a FillJob), the entries, a record
+		const BlobPlan &P = b->blobs[i];
+		if(binds_adjacency(P) && !adj_in_blob(P.L.h.nvert, P.L.h.nface)) bs[i].adj = cv.take(adj_scratch_layout(P.L.h.nvert, P.L.h.nface).total, 16);
+	}
 	if(est_v) {
 		pl.start_off = cv.take(est_v*4 + 16); pl.flag_off = cv.take(est_v*4 + 16); pl.slot_off = cv.take(est_v*4 + 16);
 		pl.adj_off = cv.take(est_f*12 + 16); pl.facen_off = cv.take(est_f*12 + 16);

@@ -94,6 +94,7 @@ void Planner::group() {
 	unpack_state_words = (uint64_t)unpack_chunks + 1;                    // (plan_carve's count was every bound stream's; the bit blocks that go a wave a stream keep no state)
 	pl.unpack_partial_off = cv.take(unpack_state_words*8, 16);           // (first thing in the uploaded block: zeros)
 	pl.each_array([&](auto &arr) { arr.dev_off = cv.take(arr.v.size()*sizeof(arr.v[0]) + 16, 16); });
+	pl.each_optional_array([&](auto &arr) { if(!arr.v.empty()) arr.dev_off = cv.take(arr.v.size()*sizeof(arr.v[0]) + 16, 16); });
 	pl.jobs_bytes = cv.take(0) - pl.jobs_begin;
 	pl.total = cv.take(0);
 }

@@ -128,6 +128,7 @@ int Planner::jobs() {
 		if(computes_normals(v.P) && !computed_normal_job(v)) continue;
 		if(v.tangents && !tangent_job(v)) continue;
 		if(builds_meshlets(v.P)) meshlet_jobs(v);
+		if(binds_adjacency(v.P) && !v.P.host_status) adjacency_jobs(v);
 	}
 	return CRTHIP_OK;
 }
@@ -457,4 +458,31 @@ void Planner::meshlet_jobs(const BlobView &v) {
 		pl.meshlet_bounds.v.push_back(q);
 	}
 	pl.meshlet.v.push_back(m);
+}
+
+// adjacency: crthip_batch_bind_adjacency.  The index where the automaton leaves it and the caller's twin array; a blob whose lists fit LDS needs no
+// more.  The others keep their ends - zeroed by a FillJob in stage E - and their entries in scratch, and a record there if the binding has none.
+// (The bind call checked all of it)
+void Planner::adjacency_jobs(const BlobView &v) {
+	const crthip_adjacency_binding &ab = v.P.derived.adjacency;
+	const bool blob = adj_in_blob(v.nvert, v.nface);
+	if(adjacency_binding_error(&ab, v.nface) || (!blob && v.S.adj == ~0ull)) { v.P.host_status = CRTHIP_E_ARGUMENT; return; }
+	AdjacencyJob a{};
+	const Faces f = faces_of(v.i); a.index = f.p; a.index_u16 = f.u16;
+	a.twin = ab.twin; a.counts = ab.counts; a.nface = v.nface; a.nvert = v.nvert;
+	const uint32_t id = (uint32_t)pl.adjacency.v.size();
+	if(blob) {
+		pl.adjacency_blob_ids.v.push_back(id);
+		pl.adjacency_lds = std::max(pl.adjacency_lds, (uint32_t)adj_blob_lds(v.nvert, v.nface));
+	} else {
+		const AdjScratchLayout lay = adj_scratch_layout(v.nvert, v.nface);
+		a.ends = (uint32_t *)SP(v.S.adj); a.list = (uint32_t *)SP(v.S.adj + lay.list);
+		if(!ab.counts) a.counts = SP(v.S.adj + lay.record);
+		for(uint64_t o = 0, n = ((uint64_t)v.nvert + 1)*4; o < n; o += 1u << 30)   // (a FillJob's size is 32 bits)
+			pl.fill.v.push_back(FillJob{SP(v.S.adj + o), (uint32_t)std::min<uint64_t>(n - o, 1u << 30), 0u});
+		pl.adj_big_ids.v.push_back(id);
+		a.block0 = (uint32_t)pl.adj_block_job.v.size();
+		for(uint32_t c = 0; c < adj_blocks(v.nface); c++) pl.adj_block_job.v.push_back(id);
+	}
+	pl.adjacency.v.push_back(a);
 }

@@ -30,6 +30,7 @@ int Planner::upload() {
 	for(auto &t : pl.tangent.v) { resolve(t.position); resolve(t.uv); resolve(t.faces); resolve(t.acc); }
 	for(auto &q : pl.meshlet_bounds.v) { resolve(q.position); resolve(q.counts); }
 	for(auto &m : pl.meshlet.v) { m.segs = base + pl.aux_u32.dev_off + (uintptr_t)m.segs; resolve(m.faces); resolve(m.scratch); resolve(m.rec_dev); }
+	for(auto &a : pl.adjacency.v) { resolve(a.index); resolve(a.counts); resolve(a.ends); resolve(a.list); }
 
 	// host image -> device (one copy)
 	stage = (uint8_t *)set.staging.p;
@@ -43,7 +44,8 @@ int Planner::upload() {
 			rec += P.bind.size();
 		}
 	}
-	pl.each_array([&](auto &arr) { if(!arr.v.empty()) memcpy(stage + (arr.dev_off - pl.jobs_begin), arr.v.data(), arr.v.size()*sizeof(arr.v[0])); });
+	auto stage_array = [&](auto &arr) { if(!arr.v.empty()) memcpy(stage + (arr.dev_off - pl.jobs_begin), arr.v.data(), arr.v.size()*sizeof(arr.v[0])); };
+	pl.each_array(stage_array); pl.each_optional_array(stage_array);
 
 	return CRTHIP_OK;
 }
@@ -317,6 +319,18 @@ int Planner::launch(uint32_t phases, const Carry *carry) {
 	if(!pl.mlb_block_job.v.empty()) {
 		const uint32_t nb = (uint32_t)pl.mlb_block_job.v.size();
 		LT.begin("meshlet_bounds"); hipLaunchKernelGGL(k_meshlet_bounds, dim3(nb), dim3(64*MB_WAVES), 0, st, D(pl.meshlet_bounds), D(pl.mlb_block_job), nb); LT.end();
+	}
+	// adjacency: the index alone, final since the automata
+	if(!pl.adjacency_blob_ids.v.empty()) {
+		const uint32_t nj = (uint32_t)pl.adjacency_blob_ids.v.size();
+		LT.begin("adjacency_blob"); hipLaunchKernelGGL(k_adjacency_blob, dim3(nj), dim3(ADJ_THREADS), pl.adjacency_lds, st, D(pl.adjacency), D(pl.adjacency_blob_ids), nj); LT.end();
+	}
+	if(!pl.adj_big_ids.v.empty()) {
+		const uint32_t nj = (uint32_t)pl.adj_big_ids.v.size(), nb = (uint32_t)pl.adj_block_job.v.size();
+		LT.begin("adjacency_count"); hipLaunchKernelGGL(k_adjacency_count, dim3(nb), dim3(ADJ_THREADS), 0, st, D(pl.adjacency), D(pl.adj_block_job), nb); LT.end();
+		LT.begin("adjacency_offsets"); hipLaunchKernelGGL(k_adjacency_offsets, dim3(nj), dim3(ADJ_THREADS), 0, st, D(pl.adjacency), D(pl.adj_big_ids), nj); LT.end();
+		LT.begin("adjacency_fill"); hipLaunchKernelGGL(k_adjacency_fill, dim3(nb), dim3(ADJ_THREADS), 0, st, D(pl.adjacency), D(pl.adj_block_job), nb); LT.end();
+		LT.begin("adjacency_twin"); hipLaunchKernelGGL(k_adjacency_twin, dim3(nb), dim3(ADJ_THREADS), 0, st, D(pl.adjacency), D(pl.adj_block_job), nb); LT.end();
 	}
 	const uint32_t ndq = (uint32_t)pl.dequant_block_job.v.size();
 	if(ndq) { LT.begin("dequantize"); hipLaunchKernelGGL(k_dequant, dim3(ndq), dim3(256), 0, st, D(pl.dequant), D(pl.dequant_block_job),

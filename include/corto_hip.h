@@ -54,6 +54,8 @@ extern "C" {
                                      crthip_meshlet_binding, crthip_meshlet_bound, crthip_batch_bind_meshlets, crthip_batch_meshlet_counts,
                                      crthip_meshlet_model (new calls and their structs, nothing else: the number stays 6);
                                      crthip_meshlet_bounds, crthip_batch_bind_meshlet_bounds, crthip_meshlet_bounds_model (a struct and two
+                                     new calls, nothing else: the number stays 6); CRTHIP_NO_TWIN, crthip_adjacency_counts,
+                                     crthip_adjacency_binding, crthip_batch_bind_adjacency, crthip_adjacency_model (two structs and two
                                      new calls, nothing else: the number stays 6) */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
@@ -430,6 +432,36 @@ typedef struct crthip_meshlet_bounds {      /* 48 bytes; arrays of them are 16-b
  * dequantisation, every other binding from scratch; the position's own output is unchanged.  Blobs without the binding launch nothing new.
  * Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host, the crt::Decoder facade or the veneers. */
 int crthip_batch_bind_meshlet_bounds(crthip_batch *b, uint32_t i, crthip_meshlet_bounds *bounds, uint32_t capacity);
+
+/* Connectivity: the half-edge twins of the blob's decoded index, found on the GPU in the decode call (kernels adjacency_blob, and
+ * adjacency_count, adjacency_offsets, adjacency_fill, adjacency_twin in crthip_kernel_times; csrc/adjacency.h has the source the kernels and
+ * the test hook share).  Pure integer work on the final index: no position, no float, no hash of coordinates; the bytes are defined exactly.
+ * A HALF-EDGE is h = 3*f + s, face f, side s in 0..2.  It runs from index[3f + s] to index[3f + (s + 1) % 3].
+ * A face is INVALID if two of its corners are equal or a corner is >= nvert (such an index comes only from a blob whose topology failed;
+ *   an id >= nvert is never used as an address); its three half-edges are INVALID.
+ * twin[h] of a valid half-edge a -> b is the LEAST valid half-edge that runs b -> a, or CRTHIP_NO_TWIN if there is none.
+ * twin[h] of an invalid half-edge is CRTHIP_NO_TWIN, and invalid half-edges are nobody's twin.
+ * Groups play no part: a twin may lie in another group.
+ * crthip_adjacency_counts: halfedges = 3*nface; boundary = the valid half-edges without a twin; duplicate = the valid half-edges whose
+ *   directed edge a -> b is also that of a LOWER valid half-edge; invalid = the invalid half-edges.
+ * What this buys: if duplicate == 0 every directed edge occurs once, so twin is an involution on the paired half-edges
+ *   (twin[twin[h]] == h) and the blob is an oriented manifold with border; it is closed if also boundary == 0.
+ * Exactly 3*nface words of twin and the 16 bytes of counts are written, nothing beyond them. */
+#define CRTHIP_NO_TWIN 0xFFFFFFFFu
+typedef struct crthip_adjacency_counts { uint32_t halfedges, boundary, duplicate, invalid; } crthip_adjacency_counts;
+typedef struct crthip_adjacency_binding {
+	uint32_t *twin;                    /* DEVICE, 4-byte aligned, room for `capacity` words */
+	crthip_adjacency_counts *counts;   /* optional DEVICE record for GPU-driven consumers: 16 bytes, 16-byte aligned; or NULL.  There is no host record */
+	uint32_t capacity;                 /* words of twin: at least 3*nface */
+	uint32_t reserved;                 /* 0 */
+} crthip_adjacency_binding;
+/* Blob i's twins go to a's buffers in the decode.  a == NULL removes the binding; a later crthip_batch_bind of that blob drops it, as does
+ * crthip_batch_reset*.  It needs neither the index nor any attribute to be bound (an unbound index is read from scratch) and is independent
+ * of every other derived binding.  Every error is returned here, in this order, and nothing new can fail at decode time.
+ * CRTHIP_E_ARGUMENT: b NULL or i out of range; a point cloud (nface == 0); twin NULL or not 4-byte aligned, or counts not 16-byte aligned;
+ * reserved != 0; capacity < 3*nface.  crthip_last_error() names the blob.  Blobs without the binding launch nothing new.
+ * Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host, the crt::Decoder facade or the veneers. */
+int crthip_batch_bind_adjacency(crthip_batch *b, uint32_t i, const crthip_adjacency_binding *a);
 
 /* The record of attribute `attr` of blob i, bound with CRTHIP_BIND_QUANTIZED.  Valid after crthip_batch_sync of a decode: the kernels write
  * the records into the batch's pinned status block, beside the status words.  CRTHIP_E_ARGUMENT if that attribute was not bound
@@ -1096,6 +1128,15 @@ int crthip_meshlet_model(const void *index, uint32_t index_u16, uint32_t nface, 
 int crthip_meshlet_bounds_model(const int32_t *position, uint32_t nvert, const crthip_meshlet *meshlets, const uint32_t *vertices,
                                 const uint8_t *triangles, const crthip_meshlet_counts *counts, crthip_meshlet_bounds *bounds, uint32_t capacity,
                                 uint32_t seed);
+
+/* (test hook, no device needed)  crthip_batch_bind_adjacency on the host: csrc/adjacency.h, the kernels' source, in their partition.  index:
+ * nface*3 uint32, or uint16 with index_u16 (may be NULL when nface is 0); twin: host memory, 3*nface words; counts: the record, or NULL.
+ * which 0: adjacency_blob, one workgroup with 16-bit list entries (a blob beyond its limit - 3*nface > 65 536 or more than 64 KiB of lists -
+ * is CRTHIP_E_LIMIT here; the decode sends such a blob down the other path); which 1: adjacency_count, adjacency_offsets, adjacency_fill,
+ * adjacency_twin.  Workgroups, waves and lanes, and so the order of every atomic, are shuffled by `seed`.  CRTHIP_E_ARGUMENT: an unknown
+ * partition, a NULL or misaligned twin (4 bytes) with nface > 0, 3*nface beyond 32 bits.  nface == 0 writes the all-zero record. */
+int crthip_adjacency_model(const void *index, uint32_t index_u16, uint32_t nface, uint32_t nvert, uint32_t *twin, crthip_adjacency_counts *counts,
+                           int which, uint32_t seed);
 
 #ifdef __cplusplus
 }
