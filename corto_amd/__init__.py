@@ -92,6 +92,23 @@ class AdjacencyBinding(C.Structure):
     _fields_ = [("twin", C.c_void_p), ("counts", C.c_void_p), ("capacity", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+WELD_ADJACENCY = 1                                   # CRTHIP_WELD_ADJACENCY
+
+
+class WeldCounts(C.Structure):
+    """crthip_weld_counts: a blob's vertices, how many are their own representative, and the faces the weld makes degenerate"""
+    _fields_ = [("vertices", C.c_uint32), ("unique", C.c_uint32), ("degenerate", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_tuple(self):
+        return (self.vertices, self.unique, self.degenerate, self.reserved)
+
+
+class WeldBinding(C.Structure):
+    """crthip_weld_binding: the device remap array, the optional device welded index and counts record, the two capacities in words, the flags"""
+    _fields_ = [("remap", C.c_void_p), ("index", C.c_void_p), ("counts", C.c_void_p), ("remap_capacity", C.c_uint32), ("index_capacity", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class MeshletBinding(C.Structure):
     """crthip_meshlet_binding: three device arrays with their capacities, the optional device counts record, the builder's parameters"""
     _fields_ = [("meshlets", C.c_void_p), ("vertices", C.c_void_p), ("triangles", C.c_void_p), ("counts", C.c_void_p),
@@ -300,6 +317,9 @@ def lib():
                                                   C.c_uint32, C.c_uint32]
         L.crthip_batch_bind_adjacency.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(AdjacencyBinding)]
         L.crthip_adjacency_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(AdjacencyCounts), C.c_int, C.c_uint32]
+        L.crthip_batch_bind_weld.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(WeldBinding)]
+        L.crthip_weld_model.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(WeldCounts), C.c_void_p,
+                                        C.c_int, C.c_uint32]
         L.crthip_batch_meshlet_counts.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshletCounts)]
         L.crthip_meshlet_bound.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(MeshletCounts)]
         L.crthip_meshlet_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(MeshletBinding), C.POINTER(MeshletCounts),
@@ -1042,6 +1062,26 @@ def adjacency_model(index: np.ndarray, nvert: int, which: int = 0, seed: int = 0
     return twin, counts
 
 
+def weld_model(position: np.ndarray, index: np.ndarray, which: int = 0, seed: int = 0, fill: int = 0xCD, with_index: bool = True):
+    """crthip_weld_model: crthip_batch_bind_weld on the host in the kernels' partition (which 0: weld_blob; 1: weld_insert / _lookup / _index;
+    workgroups and threads, and so every atomic's order, shuffled by seed).  position (nvert, 3) int32; index (nface, 3) uint32 or uint16.  The
+    arrays are made here at exactly nvert and 3*nface words and filled with `fill` first.  Returns (remap uint32 (nvert,), welded index uint32
+    (3*nface,) or None without with_index, WeldCounts, (total, longest) of the insert walks in slots)."""
+    pos = np.ascontiguousarray(position, dtype=np.int32).reshape(-1, 3)
+    idx = np.ascontiguousarray(index)
+    if idx.dtype != np.uint16:
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    idx = idx.reshape(-1, 3)
+    remap = np.full(len(pos), fill * 0x01010101, np.uint32)
+    windex = np.full(len(idx) * 3, fill * 0x01010101, np.uint32) if with_index else None
+    counts = WeldCounts()
+    stats = np.zeros(2, np.uint64)
+    _check(lib().crthip_weld_model(_np_ptr(pos) if len(pos) else None, _np_ptr(idx) if len(idx) else None, int(idx.dtype == np.uint16), len(idx), len(pos),
+                                   _np_ptr(remap) if len(remap) else None, _np_ptr(windex) if with_index and len(windex) else None, C.byref(counts),
+                                   _np_ptr(stats), which, seed))
+    return remap, windex, counts, (int(stats[0]), int(stats[1]))
+
+
 def meshlet_bounds_model(position: np.ndarray, index, meshlets: np.ndarray, vertices: np.ndarray, triangles: np.ndarray, counts, seed: int = 0,
                          capacity=None, fill: int = 0xCD, raw: bool = False):
     """crthip_meshlet_bounds_model: crthip_batch_bind_meshlet_bounds on the host in the kernel's partition (workgroups, waves and the lanes of
@@ -1261,6 +1301,7 @@ class Batch:
         self._meshlets = {}                          # blob -> (MeshletBinding, the tensors it points into): applied again by rebind() too
         self._meshlet_bounds = {}                    # blob -> (pointer, capacity, the tensor or None): applied again behind those
         self._adjacency = {}                         # blob -> (AdjacencyBinding, (twin tensor, counts tensor or None) or None): applied again by rebind() too
+        self._weld = {}                              # blob -> (WeldBinding, (remap tensor, index tensor or None, counts tensor or None) or None): applied again by rebind() too
         self._interleaved = None
 
     def __len__(self):
@@ -1305,7 +1346,7 @@ class Batch:
     # -- outputs -----------------------------------------------------------------------------------
     def allocate_outputs(self, normal_format=FMT_FLOAT, color_components: Optional[int] = None, index16=False,
                          only: Optional[set] = None, fill: Optional[int] = None, computed_normals=False, quantized=(),
-                         computed_tangents=False, tangent_format=FMT_FLOAT, meshlets=None, meshlet_bounds=False, adjacency=False):
+                         computed_tangents=False, tangent_format=FMT_FLOAT, meshlets=None, meshlet_bounds=False, adjacency=False, weld=False):
         """Allocate every output of every blob inside ONE device buffer (torch.uint8) and bind them.
         Returns a list (per blob) of dicts name -> torch tensor view.
         computed_normals: every mesh blob WITHOUT a normal attribute gets a "normal" tensor of normal_format all the same, bound
@@ -1320,7 +1361,10 @@ class Batch:
         meshlet_bounds: with meshlets=, every mesh blob also gets a crthip_meshlet_bounds array at the bound's meshlets, bound through
         crthip_batch_bind_meshlet_bounds; read it with meshlet_bounds(i) after sync().
         adjacency: every mesh blob gets a twin array of 3*nface words and a device counts record, bound through crthip_batch_bind_adjacency;
-        read them with adjacency(i) after sync()."""
+        read them with adjacency(i) after sync().
+        weld: True - every mesh blob gets a remap array of nvert words, a welded index of 3*nface words and a device counts record, bound
+        through crthip_batch_bind_weld; read them with weld(i) after sync().  "adjacency": the same with CRTHIP_WELD_ADJACENCY, so that the
+        twins of adjacency=True are those of the welded index."""
         if meshlet_bounds and meshlets is None:
             raise ValueError("allocate_outputs: meshlet_bounds needs meshlets=")
         import torch
@@ -1373,6 +1417,9 @@ class Batch:
                     mplan.append((i, bd, take(bd.meshlets * 16), take(bd.vertices * 4), take(bd.triangle_bytes), take(16),
                                   take(bd.meshlets * 48) if meshlet_bounds else None))
         aplan = [(i, info.nface, take(info.nface * 12), take(16)) for i, info in enumerate(self.infos) if info.nface] if adjacency else []
+        if not (weld is False or weld is True or weld == "adjacency"):
+            raise ValueError("allocate_outputs: weld is False, True or \"adjacency\"")
+        wplan = [(i, info.nvert, info.nface, take(max(info.nvert, 1) * 4), take(info.nface * 12), take(16)) for i, info in enumerate(self.infos) if info.nface] if weld else []
         total = max(off, 256)
         buf = torch.empty(total, dtype=torch.uint8, device=dev) if fill is None else torch.full((total,), fill, dtype=torch.uint8, device=dev)
         _torch_ready(dev)                            # (the fill runs on torch's stream; the decode on the context's own)
@@ -1392,6 +1439,10 @@ class Batch:
         self._adjacency = {}
         for (i, nf, to, co) in aplan:
             self._adjacency[i] = (AdjacencyBinding(base + to, base + co, nf * 3, 0), (buf[to:to + nf * 12], buf[co:co + 16]))
+        self._weld = {}
+        for (i, nv, nf, ro, io, co) in wplan:
+            self._weld[i] = (WeldBinding(base + ro, base + io, base + co, nv, nf * 3, WELD_ADJACENCY if weld == "adjacency" else 0, 0),
+                             (buf[ro:ro + nv * 4], buf[io:io + nf * 12], buf[co:co + 16]))
         computed, tangents = [], []
         tdt = {"f32": torch.float32, "i16": torch.int16, "u8": torch.uint8, "u32": torch.int32, "u16": torch.int16}
         for (i, name, o, dt, shape, slot, fmt, oc) in plan:
@@ -1465,6 +1516,7 @@ class Batch:
         self._tangents = []
         self._meshlets, self._meshlet_bounds = {}, {}
         self._adjacency = {}
+        self._weld = {}
         self._interleaved = metas
         self.outputs = [dict() for _ in self.infos]
         self.rebind()
@@ -1516,6 +1568,8 @@ class Batch:
             _check(lib().crthip_batch_bind_meshlet_bounds(self.handle, i, C.c_void_p(ptr), cap))
         for i, (ab, _) in self._adjacency.items():              # (... and its adjacency)
             _check(lib().crthip_batch_bind_adjacency(self.handle, i, C.byref(ab)))
+        for i, (wb, _) in self._weld.items():                   # (... and its weld)
+            _check(lib().crthip_batch_bind_weld(self.handle, i, C.byref(wb)))
 
     def bind(self, i: int, bindings: Sequence[AttrBinding], index_ptr: Optional[int] = None, index_format=FMT_UINT32):
         arr = (AttrBinding * max(len(bindings), 1))(*bindings)
@@ -1581,6 +1635,28 @@ class Batch:
         twin = keep[0].cpu().numpy().view(np.uint8).reshape(-1)[:self.infos[i].nface * 12].view(np.uint32).copy()
         counts = None if len(keep) < 2 or keep[1] is None else tuple(int(x) for x in keep[1].cpu().numpy().view(np.uint8).reshape(-1)[:16].view(np.uint32))
         return twin, counts
+
+    def bind_weld(self, i: int, binding: Optional[WeldBinding] = None, keep=None):
+        """crthip_batch_bind_weld: blob i's weld map goes to the binding's device arrays (remap at least nvert words, the optional index at least
+        3*nface).  After bind() / rebind() of that blob, which drop it; None removes it.  keep: whatever owns the memory (device tensors), held
+        with the binding - a tuple (remap, index or None, counts or None) makes weld(i) work."""
+        if binding is None:
+            self._weld.pop(i, None)
+            _check(lib().crthip_batch_bind_weld(self.handle, i, None))
+            return
+        _check(lib().crthip_batch_bind_weld(self.handle, i, C.byref(binding)))
+        self._weld[i] = (binding, keep)
+
+    def weld(self, i: int):
+        """Blob i's weld on the host: (remap uint32 (nvert,), the welded index uint32 (3*nface,) or None, the counts as a tuple (vertices,
+        unique, degenerate, reserved) or None where the binding has no device record).  After sync(); for bindings made by
+        allocate_outputs(weld=) or bind_weld(keep=)."""
+        _, keep = self._weld[i]
+        words = lambda t, n: t.cpu().numpy().view(np.uint8).reshape(-1)[:n * 4].view(np.uint32).copy()   # noqa: E731
+        remap = words(keep[0], self.infos[i].nvert)
+        index = None if len(keep) < 2 or keep[1] is None else words(keep[1], self.infos[i].nface * 3)
+        counts = None if len(keep) < 3 or keep[2] is None else tuple(int(x) for x in words(keep[2], 4))
+        return remap, index, counts
 
     def meshlet_counts(self, i: int) -> MeshletCounts:
         """crthip_batch_meshlet_counts: blob i's totals (meshlets, vertex words, triangle bytes, segments); after sync()"""

@@ -1,5 +1,5 @@
-// batch_bind.cpp — what a caller binds to a batch's blobs and what reads a decode's records back: crthip_batch_bind / _bind_all, the five derived
-// outputs (computed normals, computed tangents, meshlets, meshlet bounds, adjacency: DerivedBindings, batch_internal.h), the quantised attributes' records and the
+// batch_bind.cpp — what a caller binds to a batch's blobs and what reads a decode's records back: crthip_batch_bind / _bind_all, the six derived
+// outputs (computed normals, computed tangents, meshlets, meshlet bounds, adjacency, weld: DerivedBindings, batch_internal.h), the quantised attributes' records and the
 // meshlet counts.  Every check of a binding is made here, in the order corto_hip.h lists its errors, so that a decode has nothing new to fail on.
 // No HIP call: a program without the runtime links these (tests/cpp/plan_dump.cpp).
 #include "batch_internal.h"
@@ -171,6 +171,24 @@ extern "C" int crthip_batch_bind_adjacency(crthip_batch *b, uint32_t i, const cr
 	if(P.L.h.nface == 0) return fail(CRTHIP_E_ARGUMENT, "adjacency needs faces: a point cloud has none" + who);
 	if(const char *why = adjacency_binding_error(a, P.L.h.nface)) return fail(CRTHIP_E_ARGUMENT, why + who);
 	P.derived.adjacency = *a;
+	b->dirty = true;
+	return CRTHIP_OK;
+}
+
+// The weld map of the blob's integer positions and its welded index (corto_hip.h has the contract): every check is made here, in the header's
+// order.  It reads what the bind binds, like every derived binding; no other derived binding drops it and it drops none (CRTHIP_WELD_ADJACENCY is
+// looked at when a decode is planned)
+extern "C" int crthip_batch_bind_weld(crthip_batch *b, uint32_t i, const crthip_weld_binding *w) {
+	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_weld: no such blob");
+	BlobPlan &P = b->blobs[i];
+	const std::string who = " (blob " + std::to_string(i) + ")";
+	if(!w) { P.derived.weld = crthip_weld_binding{}; b->dirty = true; return CRTHIP_OK; }
+	if(P.L.h.nface == 0) return fail(CRTHIP_E_ARGUMENT, "a weld needs faces: a point cloud has none" + who);
+	if(const char *why = weld_binding_error(w, P.L.h.nvert, P.L.h.nface)) return fail(CRTHIP_E_ARGUMENT, why + who);
+	// (what meshlet bounds ask of the position)
+	if(!generic_source_ok(P, attr_named(P, "position"), 3))
+		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "a weld needs a bound three-component \"position\" (bind the blob first)" + who);
+	P.derived.weld = *w;
 	b->dirty = true;
 	return CRTHIP_OK;
 }

@@ -237,10 +237,24 @@ struct AdjacencyJob {
 	uint8_t index_u16, pad[3];
 };
 
+// a blob bound with crthip_batch_bind_weld (k_weld.hip, weld.h): the integer positions and the index -> the caller's remap, its welded index and
+// the blob's record.  A blob whose table fits LDS (weld_in_blob) needs nothing else; the others keep their table in scratch
+struct WeldJob {
+	const int32_t *position;       // nvert x 3 int32 as K-DELTA leaves them: the caller's packed buffer, or scratch
+	const void *index;             // u32 or, with index_u16, u16 triples: the caller's index, or scratch
+	uint32_t *remap;               // the binding's nvert words
+	uint32_t *windex;              // the binding's 3*nface words; null: no welded index
+	void *counts;                  // crthip_weld_counts in DEVICE memory: the binding's, or (bigger blobs only) scratch; null: none wanted
+	uint32_t *table;               // bigger blobs: weld_slots(nvert) words zeroed by a FillJob
+	uint32_t nface, nvert;
+	uint32_t vblock0, cblock0;     // first block of this job in the two block -> job maps (weld_insert and _lookup; weld_index)
+	uint8_t index_u16, pad[7];
+};
+
 // the layout the kernels read, pinned (TopoJob's size is performance-critical: TOPO_OPT_PROGRESS above)
 static_assert(sizeof(TunStream) == 64 && sizeof(FillJob) == 16 && sizeof(TopoJob) == 136 && sizeof(UnpackJob) == 56 && sizeof(DeltaJob) == 96 &&
               sizeof(CloudJob) == 24 && sizeof(NormalJob) == 104 && sizeof(DequantJob) == 64 && sizeof(QuantOutJob) == 72 && sizeof(TangentJob) == 80 &&
-              sizeof(MeshletJob) == 104 && sizeof(MeshletBoundsJob) == 64 && sizeof(AdjacencyJob) == 56, "decode job layout");
+              sizeof(MeshletJob) == 104 && sizeof(MeshletBoundsJob) == 64 && sizeof(AdjacencyJob) == 56 && sizeof(WeldJob) == 72, "decode job layout");
 static_assert(offsetof(TopoJob, opts) == 116 && offsetof(UnpackJob, out_kind) == 51 && offsetof(NormalJob, faces_u16) == 58, "decode job layout");
 static_assert(offsetof(DeltaJob, in_i16) == 34 && offsetof(DeltaJob, wide) == 35 && offsetof(DeltaJob, rounds) == 88 &&
               offsetof(DeltaJob, status_back) == 92, "decode job layout");

@@ -78,6 +78,14 @@ __global__ void k_adjacency_offsets(const AdjacencyJob *jobs, const uint32_t *jo
 __global__ void k_adjacency_fill(const AdjacencyJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 __global__ void k_adjacency_twin(const AdjacencyJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 
+// k_weld.hip (crthip_batch_bind_weld; weld.h has the method and both partitions): blobs whose table fits WELD_BLOB_LDS_MAX by one workgroup each
+// from an id list, with weld_slots(nvert)*4 bytes of dynamic LDS (the launch asks for the largest among them); bigger ones 256 vertices a block
+// from a block -> job map (insert, lookup) and 256 corners a block from a second one (index: blobs with an index output only)
+__global__ void k_weld_blob(const WeldJob *jobs, const uint32_t *job_ids, uint32_t njobs);
+__global__ void k_weld_insert(const WeldJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_weld_lookup(const WeldJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_weld_index(const WeldJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+
 // k_mesh.hip
 __global__ void k_topology(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);
 __global__ void k_topology_lds(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);

@@ -119,6 +119,10 @@ int Planner::carve() {
 		const BlobPlan &P = b->blobs[i];
 		if(binds_adjacency(P) && !adj_in_blob(P.L.h.nvert, P.L.h.nface)) bs[i].adj = cv.take(adj_scratch_layout(P.L.h.nvert, P.L.h.nface).total, 16);
 	}
+	for(uint32_t i = 0; i < nblobs; i++) {                           // a weld beyond LDS: the table (zeroed by a FillJob), a record
+		const BlobPlan &P = b->blobs[i];
+		if(binds_weld(P) && !weld_in_blob(P.L.h.nvert)) bs[i].weld = cv.take(weld_scratch_layout(P.L.h.nvert).total, 16);
+	}
 	if(est_v) {
 		pl.start_off = cv.take(est_v*4 + 16); pl.flag_off = cv.take(est_v*4 + 16); pl.slot_off = cv.take(est_v*4 + 16);
 		pl.adj_off = cv.take(est_f*12 + 16); pl.facen_off = cv.take(est_f*12 + 16);

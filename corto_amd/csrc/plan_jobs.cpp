@@ -128,6 +128,7 @@ int Planner::jobs() {
 		if(computes_normals(v.P) && !computed_normal_job(v)) continue;
 		if(v.tangents && !tangent_job(v)) continue;
 		if(builds_meshlets(v.P)) meshlet_jobs(v);
+		if(binds_weld(v.P) && !v.P.host_status) weld_jobs(v);
 		if(binds_adjacency(v.P) && !v.P.host_status) adjacency_jobs(v);
 	}
 	return CRTHIP_OK;
@@ -143,6 +144,8 @@ Planner::BlobView Planner::view_of(uint32_t i, size_t rec0) {
 	const bool tangents = computes_tangents(P);
 	// ... and so do meshlet bounds, behind the meshlet kernels: the integer positions last until k_dequant
 	const bool bounds = bounds_meshlets(P);
+	// ... and so does the weld, in front of the adjacency kernels
+	const bool weld = binds_weld(P);
 	// who turns the integer positions into floats: estimated normals read them as integers after K-DELTA, so the fused normal
 	// kernel does it as their last reader (pos_by_normal), the separate normal kernels leave it to k_dequant behind them, and
 	// without such normals K-DELTA does it on the way out of LDS like for every other attribute
@@ -151,8 +154,8 @@ Planner::BlobView Planner::view_of(uint32_t i, size_t rec0) {
 		if(mesh && L.h.attrs[k].codec == CRTHIP_CODEC_NORMAL && P.bind[k].buffer && (L.attrs[k].normal_prediction == 1 ||
 			L.attrs[k].normal_prediction == 2)) readers++;
 	if(computes_normals(P)) readers++;                        // computed normals read the integer positions as a stored estimate does
-	const bool pos_ints_needed = readers > 0 || tangents || bounds;
-	const bool pos_by_normal = !tangents && !bounds && readers == 1 && normal_fused(nvert, nface) && pos_k >= 0 && P.bind[pos_k].format == CRTHIP_FMT_FLOAT;
+	const bool pos_ints_needed = readers > 0 || tangents || bounds || weld;
+	const bool pos_by_normal = !tangents && !bounds && !weld && readers == 1 && normal_fused(nvert, nface) && pos_k >= 0 && P.bind[pos_k].format == CRTHIP_FMT_FLOAT;
 	return BlobView{i, P, L, bs[i], mesh, nvert, nface, pos_k, uv_k, tangents, bounds, pos_ints_needed, pos_by_normal, rec0};
 }
 
@@ -460,7 +463,40 @@ void Planner::meshlet_jobs(const BlobView &v) {
 	pl.meshlet.v.push_back(m);
 }
 
-// adjacency: crthip_batch_bind_adjacency.  The index where the automaton leaves it and the caller's twin array; a blob whose lists fit LDS needs no
+// the weld: crthip_batch_bind_weld.  The integer positions as the tangents take them, the index where the automaton leaves it, the caller's
+// arrays; a blob whose table fits LDS needs no more.  The others keep their table - zeroed by a FillJob in stage E, so that a second decode starts
+// clean - in scratch, and a record there if the binding has none.  (The bind call checked all of it)
+void Planner::weld_jobs(const BlobView &v) {
+	const crthip_weld_binding &wb = v.P.derived.weld;
+	const bool blob = weld_in_blob(v.nvert);
+	if(!generic_source_ok(v.P, v.pos_k, 3)) { v.P.host_status = CRTHIP_E_NORMAL_NEEDS_POSITION; return; }
+	if(weld_binding_error(&wb, v.nvert, v.nface) || (!blob && v.S.weld == ~0ull)) { v.P.host_status = CRTHIP_E_ARGUMENT; return; }
+	WeldJob w{};
+	w.position = ints_of(v.i, v.pos_k);
+	const Faces f = faces_of(v.i); w.index = f.p; w.index_u16 = f.u16;
+	w.remap = wb.remap; w.windex = wb.index; w.counts = wb.counts; w.nface = v.nface; w.nvert = v.nvert;
+	const uint32_t id = (uint32_t)pl.weld.v.size();
+	if(blob) {
+		pl.weld_blob_ids.v.push_back(id);
+		pl.weld_lds = std::max(pl.weld_lds, (uint32_t)(weld_slots(v.nvert)*4));
+	} else {
+		const WeldScratchLayout lay = weld_scratch_layout(v.nvert);
+		w.table = (uint32_t *)SP(v.S.weld);
+		if(!wb.counts) w.counts = SP(v.S.weld + lay.record);
+		for(uint64_t o = 0, n = lay.record; o < n; o += 1u << 30)                  // (a FillJob's size is 32 bits)
+			pl.fill.v.push_back(FillJob{SP(v.S.weld + o), (uint32_t)std::min<uint64_t>(n - o, 1u << 30), 0u});
+		w.vblock0 = (uint32_t)pl.weld_vblock_job.v.size();
+		for(uint32_t c = 0; c < weld_vblocks(v.nvert); c++) pl.weld_vblock_job.v.push_back(id);
+		if(wb.index) {
+			w.cblock0 = (uint32_t)pl.weld_cblock_job.v.size();
+			for(uint32_t c = 0; c < weld_cblocks(v.nface); c++) pl.weld_cblock_job.v.push_back(id);
+		}
+	}
+	pl.weld.v.push_back(w);
+}
+
+// adjacency: crthip_batch_bind_adjacency.  The index where the automaton leaves it - or, under CRTHIP_WELD_ADJACENCY, the welded index of the blob's
+// weld binding, which weld_jobs has just given a job - and the caller's twin array; a blob whose lists fit LDS needs no
 // more.  The others keep their ends - zeroed by a FillJob in stage E - and their entries in scratch, and a record there if the binding has none.
 // (The bind call checked all of it)
 void Planner::adjacency_jobs(const BlobView &v) {
@@ -469,6 +505,7 @@ void Planner::adjacency_jobs(const BlobView &v) {
 	if(adjacency_binding_error(&ab, v.nface) || (!blob && v.S.adj == ~0ull)) { v.P.host_status = CRTHIP_E_ARGUMENT; return; }
 	AdjacencyJob a{};
 	const Faces f = faces_of(v.i); a.index = f.p; a.index_u16 = f.u16;
+	if(welds_adjacency(v.P)) { a.index = v.P.derived.weld.index; a.index_u16 = 0; }
 	a.twin = ab.twin; a.counts = ab.counts; a.nface = v.nface; a.nvert = v.nvert;
 	const uint32_t id = (uint32_t)pl.adjacency.v.size();
 	if(blob) {

@@ -31,6 +31,7 @@ int Planner::upload() {
 	for(auto &q : pl.meshlet_bounds.v) { resolve(q.position); resolve(q.counts); }
 	for(auto &m : pl.meshlet.v) { m.segs = base + pl.aux_u32.dev_off + (uintptr_t)m.segs; resolve(m.faces); resolve(m.scratch); resolve(m.rec_dev); }
 	for(auto &a : pl.adjacency.v) { resolve(a.index); resolve(a.counts); resolve(a.ends); resolve(a.list); }
+	for(auto &w : pl.weld.v) { resolve(w.position); resolve(w.index); resolve(w.counts); resolve(w.table); }
 
 	// host image -> device (one copy)
 	stage = (uint8_t *)set.staging.p;
@@ -319,6 +320,17 @@ int Planner::launch(uint32_t phases, const Carry *carry) {
 	if(!pl.mlb_block_job.v.empty()) {
 		const uint32_t nb = (uint32_t)pl.mlb_block_job.v.size();
 		LT.begin("meshlet_bounds"); hipLaunchKernelGGL(k_meshlet_bounds, dim3(nb), dim3(64*MB_WAVES), 0, st, D(pl.meshlet_bounds), D(pl.mlb_block_job), nb); LT.end();
+	}
+	// the weld: the integer positions (k_dequant runs behind) and the index; in front of adjacency, which may read the welded index
+	if(!pl.weld_blob_ids.v.empty()) {
+		const uint32_t nj = (uint32_t)pl.weld_blob_ids.v.size();
+		LT.begin("weld_blob"); hipLaunchKernelGGL(k_weld_blob, dim3(nj), dim3(WELD_THREADS), pl.weld_lds, st, D(pl.weld), D(pl.weld_blob_ids), nj); LT.end();
+	}
+	if(!pl.weld_vblock_job.v.empty()) {
+		const uint32_t nb = (uint32_t)pl.weld_vblock_job.v.size(), nc = (uint32_t)pl.weld_cblock_job.v.size();
+		LT.begin("weld_insert"); hipLaunchKernelGGL(k_weld_insert, dim3(nb), dim3(WELD_THREADS), 0, st, D(pl.weld), D(pl.weld_vblock_job), nb); LT.end();
+		LT.begin("weld_lookup"); hipLaunchKernelGGL(k_weld_lookup, dim3(nb), dim3(WELD_THREADS), 0, st, D(pl.weld), D(pl.weld_vblock_job), nb); LT.end();
+		if(nc) { LT.begin("weld_index"); hipLaunchKernelGGL(k_weld_index, dim3(nc), dim3(WELD_THREADS), 0, st, D(pl.weld), D(pl.weld_cblock_job), nc); LT.end(); }
 	}
 	// adjacency: the index alone, final since the automata
 	if(!pl.adjacency_blob_ids.v.empty()) {

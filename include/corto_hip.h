@@ -56,7 +56,9 @@ extern "C" {
                                      crthip_meshlet_bounds, crthip_batch_bind_meshlet_bounds, crthip_meshlet_bounds_model (a struct and two
                                      new calls, nothing else: the number stays 6); CRTHIP_NO_TWIN, crthip_adjacency_counts,
                                      crthip_adjacency_binding, crthip_batch_bind_adjacency, crthip_adjacency_model (two structs and two
-                                     new calls, nothing else: the number stays 6) */
+                                     new calls, nothing else: the number stays 6); CRTHIP_WELD_ADJACENCY, crthip_weld_counts,
+                                     crthip_weld_binding, crthip_batch_bind_weld, crthip_weld_model (two structs and two new calls,
+                                     nothing else: the number stays 6) */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -446,7 +448,8 @@ int crthip_batch_bind_meshlet_bounds(crthip_batch *b, uint32_t i, crthip_meshlet
  *   directed edge a -> b is also that of a LOWER valid half-edge; invalid = the invalid half-edges.
  * What this buys: if duplicate == 0 every directed edge occurs once, so twin is an involution on the paired half-edges
  *   (twin[twin[h]] == h) and the blob is an oriented manifold with border; it is closed if also boundary == 0.
- * Exactly 3*nface words of twin and the 16 bytes of counts are written, nothing beyond them. */
+ * Exactly 3*nface words of twin and the 16 bytes of counts are written, nothing beyond them.
+ * In a decode where the blob also has a weld binding with CRTHIP_WELD_ADJACENCY (below), "the index" is that binding's welded index. */
 #define CRTHIP_NO_TWIN 0xFFFFFFFFu
 typedef struct crthip_adjacency_counts { uint32_t halfedges, boundary, duplicate, invalid; } crthip_adjacency_counts;
 typedef struct crthip_adjacency_binding {
@@ -462,6 +465,48 @@ typedef struct crthip_adjacency_binding {
  * reserved != 0; capacity < 3*nface.  crthip_last_error() names the blob.  Blobs without the binding launch nothing new.
  * Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host, the crt::Decoder facade or the veneers. */
 int crthip_batch_bind_adjacency(crthip_batch *b, uint32_t i, const crthip_adjacency_binding *a);
+
+/* A weld by position: for every vertex the least vertex at the same position, and the blob's index through that map, found on the GPU in the
+ * decode call (kernels weld_blob, and weld_insert, weld_lookup, weld_index in crthip_kernel_times; csrc/weld.h has the source the kernels and
+ * the test hook share).  A mesh that carries uvs or hard normals has its vertices split along every seam: crthip_batch_bind_adjacency
+ * reports each seam as a border, and the welded index is what silhouettes, crack-free subdivision, a depth-only or shadow index
+ * (meshopt_generateShadowIndexBuffer) and a closedness test need.  Integer work only; the bytes are defined exactly.
+ * p[v] is the delta-decoded INTEGER position of vertex v, three int32: what crthip_batch_bind_computed_tangents and
+ *   crthip_batch_bind_meshlet_bounds read.  Every decoded float position is int * q, so equality of the integers is the meaningful one.
+ * remap[v] = the LEAST u with p[u] == p[v] in all three components, for every v < nvert: remap[v] <= v and remap[remap[v]] == remap[v].
+ * index[k] (optional, always uint32, 3*nface words) = remap[id] if id < nvert, else id unchanged, where id is corner k of the blob's final
+ *   index.  An id >= nvert is compared and never used as an address, as in adjacency.
+ * crthip_weld_counts: vertices = nvert; unique = the number of v with remap[v] == v; degenerate = the number of faces whose WELDED triple
+ *   has two equal corners or a corner >= nvert - adjacency's "invalid" rule on the welded index - and 0 for a binding without `index`, which
+ *   forms no welded triple; reserved is written as 0.
+ * Exactly nvert words of remap, 3*nface words of index and the 16 bytes of counts are written, nothing beyond them.  The position's own
+ * output is unchanged, whatever its format (FLOAT packed or strided, an integer format, CRTHIP_BIND_QUANTIZED).
+ * CRTHIP_WELD_ADJACENCY: in a decode where the blob has both this flag and an adjacency binding, the adjacency kernels read the welded index
+ *   instead of the blob's own: twin and crthip_adjacency_counts are those of the welded index by adjacency's unchanged rule, and a face the
+ *   weld collapses is an invalid face there (adjacency.invalid == 3 * weld.degenerate).  The flag is looked at when the decode is planned:
+ *   the order of the two bind calls does not matter, and removing either binding removes the effect. */
+#define CRTHIP_WELD_ADJACENCY 1u
+typedef struct crthip_weld_counts { uint32_t vertices, unique, degenerate, reserved; } crthip_weld_counts;
+typedef struct crthip_weld_binding {
+	uint32_t *remap;                   /* DEVICE, 4-byte aligned, room for `remap_capacity` words */
+	uint32_t *index;                   /* optional DEVICE array of the welded index, 4-byte aligned, room for `index_capacity` words; or NULL */
+	crthip_weld_counts *counts;        /* optional DEVICE record for GPU-driven consumers: 16 bytes, 16-byte aligned; or NULL.  There is no host record */
+	uint32_t remap_capacity;           /* words of remap: at least nvert */
+	uint32_t index_capacity;           /* words of index: at least 3*nface when index is given */
+	uint32_t flags;                    /* 0 or CRTHIP_WELD_ADJACENCY */
+	uint32_t reserved;                 /* 0 */
+} crthip_weld_binding;
+/* Blob i's weld goes to w's buffers in the decode.  Call it after crthip_batch_bind of blob i; w == NULL removes the binding; a later
+ * crthip_batch_bind of that blob drops it, as does crthip_batch_reset*.  The index itself may be bound as uint32, as uint16 or not at all (it
+ * is then read from scratch).  Independent of every other derived binding's lifetime.  Every error is returned here, in this order, and
+ * nothing new can fail at decode time.
+ * CRTHIP_E_ARGUMENT: b NULL or i out of range; a point cloud (nface == 0); remap NULL or not 4-byte aligned; index not 4-byte aligned or
+ * counts not 16-byte aligned; remap_capacity < nvert, or index given and index_capacity < 3*nface; unknown flag bits; reserved != 0;
+ * CRTHIP_WELD_ADJACENCY without index.  CRTHIP_E_NORMAL_NEEDS_POSITION: no bound three-component generic "position", or one bound with
+ * CRTHIP_BIND_STREAM_VALUES (the rule of crthip_batch_bind_meshlet_bounds).  crthip_last_error() names the blob.  Blobs without the binding
+ * launch nothing new.
+ * Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host, the crt::Decoder facade or the veneers. */
+int crthip_batch_bind_weld(crthip_batch *b, uint32_t i, const crthip_weld_binding *w);
 
 /* The record of attribute `attr` of blob i, bound with CRTHIP_BIND_QUANTIZED.  Valid after crthip_batch_sync of a decode: the kernels write
  * the records into the batch's pinned status block, beside the status words.  CRTHIP_E_ARGUMENT if that attribute was not bound
@@ -1137,6 +1182,17 @@ int crthip_meshlet_bounds_model(const int32_t *position, uint32_t nvert, const c
  * partition, a NULL or misaligned twin (4 bytes) with nface > 0, 3*nface beyond 32 bits.  nface == 0 writes the all-zero record. */
 int crthip_adjacency_model(const void *index, uint32_t index_u16, uint32_t nface, uint32_t nvert, uint32_t *twin, crthip_adjacency_counts *counts,
                            int which, uint32_t seed);
+
+/* (test hook, no device needed)  crthip_batch_bind_weld on the host: csrc/weld.h, the kernels' source, in their partition.  position: nvert*3
+ * int32 (may be NULL when nvert is 0); index: nface*3 uint32, or uint16 with index_u16 (may be NULL when nface is 0); remap: host memory,
+ * nvert words; windex: host memory, 3*nface words, or NULL (no welded index: degenerate is 0); counts: the record, or NULL; stats: two words,
+ * or NULL - the slots all insert walks visited and the longest walk's.
+ * which 0: weld_blob, one workgroup with its table where the kernel has LDS (a blob beyond its limit - more than 8 192 vertices - is
+ * CRTHIP_E_LIMIT here; the decode sends such a blob down the other path); which 1: weld_insert, weld_lookup, weld_index.  Workgroups and
+ * threads, and so the order of every atomic, are shuffled by `seed`.  CRTHIP_E_ARGUMENT: an unknown partition, a NULL position, index or
+ * remap where there is something to read or write, a misaligned remap or windex (4 bytes), 3*nface beyond 32 bits. */
+int crthip_weld_model(const int32_t *position, const void *index, uint32_t index_u16, uint32_t nface, uint32_t nvert, uint32_t *remap, uint32_t *windex,
+                      crthip_weld_counts *counts, uint64_t *stats, int which, uint32_t seed);
 
 #ifdef __cplusplus
 }
