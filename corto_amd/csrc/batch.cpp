@@ -883,28 +883,8 @@ extern "C" int crthip_tunstall_decode_blocks(crthip_ctx *ctx, uint32_t n, const 
 	HIP_TRY(hipMemcpyAsync(base + o_jobs, stage, total - o_jobs, hipMemcpyHostToDevice, st));
 	ctx->timer.reset();
 	Launch LT{ctx};
-	TunStream *dt = (TunStream *)(base + o_tun); uint32_t *dcs = (uint32_t *)(base + o_cs);
-	TunTable *tables = (TunTable *)(base + o_tab); uint64_t *part = (uint64_t *)(base + o_part);
-	const uint32_t ntun = (uint32_t)tun.size();
-	if(ntun) {
-		uint32_t big = 0;
-		for(auto &t : tun) if(t.nsym > 64) big = TUN_TABLE_BYTES;
-		LT.begin("tunstall_tables"); hipLaunchKernelGGL(k_tun_tables, dim3(ntun), dim3(64), big, st, dt, ntun, tables); LT.end();
-		const bool scanned = max_nchunks > 256;
-		if(multi) {
-			LT.begin("tunstall_chunk_sums"); hipLaunchKernelGGL(k_tun_chunk_sums, dim3(chunks), dim3(256), 0, st, dt, dcs, chunks, tables,
-				part, 0u); LT.end();
-			if(scanned) { LT.begin("tunstall_stream_scan"); hipLaunchKernelGGL(k_tun_stream_scan, dim3(ntun), dim3(256), 0, st, dt, ntun,
-				part); LT.end(); }
-		// (up to 256 chunks a stream: every decode wave adds up the sums in front of it itself)
-		}
-		LT.begin("tunstall_decode");
-		if(multi) { if(launch_tun_decode_staged(st, dt, dcs, chunks, tables, part, scanned ? 0u : 1u)) return fail(CRTHIP_E_DEVICE); }
-		else hipLaunchKernelGGL(k_tun_decode, dim3(chunks), dim3(256), 0, st, dt, dcs, chunks, tables, part, 0u);
-		LT.end();
-	}
-	if(!fills.empty()) { LT.begin("fill"); hipLaunchKernelGGL(k_fill, dim3((uint32_t)fills.size()), dim3(256), 0, st, (FillJob *)(base +
-		o_fill), (uint32_t)fills.size()); LT.end(); }
+	{ int e_ = tun_chain(LT, st, tun, (TunStream *)(base + o_tun), (uint32_t *)(base + o_cs), chunks, (TunTable *)(base + o_tab), (uint64_t *)(base + o_part),
+		max_nchunks, multi, (FillJob *)(base + o_fill), (uint32_t)fills.size()); if(e_) return e_; }
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(st));
 	if(times) fold_kernel_times(ctx->timer, times);

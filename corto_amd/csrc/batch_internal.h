@@ -1,8 +1,9 @@
 // batch_internal.h — what the pieces of the decode path's host side share: the context and batch objects, the plan of one decode call and
 // the
 // staged Planner (batch.cpp: the C ABI, context, harvest; batch_bind.cpp: the bind calls and what reads a decode's records - no HIP call, so a
-// program without the runtime links them; plan_carve.cpp / plan_jobs.cpp / plan_group.cpp: the planner's stages; plan_launch.cpp:
-// upload, the kernel schedule, the stats).  Round 5 split batch.cpp (1 640 lines) along the Planner's stages.  A blob's derived bindings -
+// program without the runtime links them; plan_carve.cpp / plan_jobs.cpp / plan_group.cpp: the planner's stages up to and with upload(), which
+// calls no kernel and no stream either; plan_launch.cpp: the schedule's shape (Planner::shape), launch() and its stage members - entropy, front,
+// delta, cloud, normals, derived, finish -, tun_chain, the stats).  Round 5 split batch.cpp (1 640 lines) along the Planner's stages.  A blob's derived bindings -
 // computed normals, tangents, meshlets, meshlet bounds, adjacency, weld - are one record, DerivedBindings.  Not part of the C ABI.
 #pragma once
 #include <chrono>
@@ -82,6 +83,7 @@ struct KernelTimer {
 template <typename T> struct HostArr {  // host image of a device array + where it goes
 	std::vector<T> v; uint64_t dev_off = 0;
 };
+static inline void push_blocks(HostArr<uint32_t> &map, uint32_t id, uint32_t count) { map.v.insert(map.v.end(), count, id); }   // `count` blocks of job `id` on a block -> job map
 
 struct AttrScratch {
 	// vals: int32 workspace of a generic attribute bound with a stride; facen: the fused normal kernel's face normals when not in LDS
@@ -401,7 +403,15 @@ struct Launch {
 		(void)hipEventRecord(e, cur);
 		ctx->timer.recs.back().e1 = ctx->timer.used - 1;
 	}
+	// one kernel under one record (a record that spans several launches keeps its own begin / end around them)
+	template <class K, class... A> void run(const char *name, K kernel, dim3 grid, dim3 block, uint32_t lds, hipStream_t s, A... args) {
+		begin(name, s); hipLaunchKernelGGL(kernel, grid, block, lds, s, args...); end();
+	}
 };
+// the long-stream Tunstall chain (plan_launch.cpp): K-TAB, and for streams of several chunks (`multi`) the chunk sums, the stream scan beyond 256
+// chunks a stream and the staged decode - else k_tun_decode, a chunk a stream; then k_fill.  `tun`: the host image of `streams`
+int tun_chain(Launch &LT, hipStream_t st, const std::vector<TunStream> &tun, const TunStream *streams, const uint32_t *chunk_stream, uint32_t chunks,
+	TunTable *tables, uint64_t *partial, uint32_t max_nchunks, bool multi, const FillJob *fill, uint32_t nfill);
 
 // The planner of one decode call, stage by stage (round 4: this was one function of 660 lines).  carve() lays the batch's scratch out
 // (pass 1: sizes and offsets only), jobs() writes the job descriptors of every stage (pass 2), group() sorts streams by dictionary and
@@ -440,10 +450,31 @@ struct Planner {
 		const uintptr_t v = (uintptr_t)p;
 		if(v >> 63) p = (T *)(base + (v & ~(1ull << 63)));
 	}
+	// FillJobs that zero the scratch range [off, off + bytes) in stage E (a FillJob's size is 32 bits: 2^30 bytes a job at most)
+	void zero_fill(uint64_t off, uint64_t bytes) { for(uint64_t o = 0; o < bytes; o += 1u << 30) pl.fill.v.push_back(FillJob{SP(off + o), (uint32_t)std::min<uint64_t>(bytes - o, 1u << 30), 0u}); }
 	bool e_done = false;                                                     // stage E has been enqueued (by an earlier call)
 	int carve(); int jobs(); void group(); int upload(); int launch(uint32_t phases = PH_ALL, const Carry *carry = nullptr); int mark_done(); void account();
 	uint32_t qout_blob_max() const { return ctx->dbg.qout_blob_max ? ctx->dbg.qout_blob_max : QOUT_BLOB_MAX; }   // a quantised attribute's size class
-	bool splits() const; bool takes_front() const; bool carry_args(Carry &c) const; bool hosts_carry() const;
+	// The schedule's shape, decided in one place (plan_launch.cpp).  LongStreams: a stream of several chunks - one scan over all chunks, no separate
+	// entropy stage.  Forked: a mesh batch with attribute work on a context with two streams - the attribute streams beside the automata.  OneStream:
+	// everything else - the entropy stage (PH_*) in front of the mesh stage on the main stream; the only shape that splits() and that carries
+	enum class Shape { LongStreams, Forked, OneStream };
+	Shape shape() const;
+	bool splits() const { return shape() == Shape::OneStream; }
+	bool takes_front() const; bool carry_args(Carry &c) const; bool hosts_carry() const;
+	// launch() by stage (plan_launch.cpp), in the order they are enqueued
+	Launch LT{ctx};
+	uint32_t nbig = 0, nslices = 0; bool tiles_launched = false;             // K-DELTA's jobs too big for the LDS records (sorted to the front; the slices: the last nslices of them)
+	template <class T> T *D(HostArr<T> &arr) const { return (T *)(base + arr.dev_off); }   // a job array on the device
+	// the (jobs, ids, n) launch on the main stream: a workgroup an id, nothing for an empty list
+	template <class K, class J, class... A> void by_ids(const char *name, K kernel, uint32_t threads, uint32_t lds, HostArr<J> &jobs, HostArr<uint32_t> &ids, A... more) {
+		const uint32_t n = (uint32_t)ids.v.size();
+		if(n) LT.run(name, kernel, dim3(n), dim3(threads), lds, ctx->stream, D(jobs), D(ids), n, more...);
+	}
+	int fork(hipStream_t *s2); int join(hipStream_t s2);
+	void entropy(hipStream_t s, uint32_t phases, uint32_t t0, uint32_t t1, uint32_t f0, uint32_t f1); int long_streams(); int forked();
+	void topology(); void unpack(hipStream_t s); void front(const Carry *carry); void delta_tiles(hipStream_t s); void delta(const Carry *carry);
+	void cloud(); void normals(); void derived(); void finish();
 	// a blob's integer sources as a job takes them: attribute k's values where K-DELTA leaves them and the index where the automaton does - the caller's, or scratch
 	int32_t *ints_of(uint32_t i, size_t k) const { const Binding &bd = b->blobs[i].bind[k]; return (int32_t *)(generic_in_scratch(bd) ? SP(bs[i].attr[k].vals) : bd.buffer); }
 	struct Faces { void *p; uint8_t u16; };

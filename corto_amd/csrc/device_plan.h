@@ -39,10 +39,10 @@ struct TunStream {
 // balanced by OUTPUT bytes (a two-symbol dictionary expands 60x, a flat one 2x), and a wave's step of 64*cpl codewords
 // is sized so that its decoded bytes fit the wave's LDS window (k_tunstall.hip).
 constexpr uint32_t TUN_CHUNK_CODES = 32768;   // largest chunk
-inline void tun_pick_geometry(TunStream &t, uint32_t chunk_cap = TUN_CHUNK_CODES) {   // chunk_cap: DebugConfig::tun_chunk_cap (debug_config.h)
+inline void tun_pick_geometry(TunStream &t) {
 	const uint32_t avg = t.csize ? (uint32_t)(((uint64_t)t.size + t.csize - 1)/t.csize) : 1;
 	t.cpl = avg <= 8 ? 8 : avg <= 16 ? 4 : avg <= 32 ? 2 : 1;
-	uint32_t codes = chunk_cap;
+	uint32_t codes = TUN_CHUNK_CODES;
 	while(codes > 256*t.cpl && (uint64_t)codes*avg > 256*1024) codes >>= 1;   // a wave's quarter chunk stays whole steps of 64*cpl
 	t.chunk_codes = codes;
 	t.nchunks = (t.csize + codes - 1)/codes;

@@ -1,5 +1,5 @@
 // plan_group.cpp — Planner::group: streams sorted by dictionary, attributes into K-DELTA workgroups, the automata into launch classes, the
-// job arrays placed.
+// job arrays placed; Planner::upload: the blocks reserved, the scratch pointers resolved, the arrays staged.
 #include "batch_internal.h"
 
 void Planner::group() {
@@ -37,9 +37,9 @@ void Planner::group() {
 	for(uint32_t j = 0; j < pl.normal.v.size(); j++) {
 		const NormalJob &n = pl.normal.v[j];
 		pl.nv_block_first.v.push_back((uint32_t)pl.nv_block_job.v.size());
-		for(uint32_t c = 0; c < (n.nvert + 255)/256; c++) pl.nv_block_job.v.push_back(j);
+		push_blocks(pl.nv_block_job, j, (n.nvert + 255)/256);
 		pl.nf_block_first.v.push_back((uint32_t)pl.nf_block_job.v.size());
-		if(n.prediction != 0 && !n.fused) for(uint32_t c = 0; c < (n.nface + 255)/256; c++) pl.nf_block_job.v.push_back(j);
+		if(n.prediction != 0 && !n.fused) push_blocks(pl.nf_block_job, j, (n.nface + 255)/256);
 	}
 
 	// the LDS automata go up in ONE launch whose LDS request is the largest of theirs - unless some ask for much more than the others (a
@@ -97,5 +97,56 @@ void Planner::group() {
 	pl.each_optional_array([&](auto &arr) { if(!arr.v.empty()) arr.dev_off = cv.take(arr.v.size()*sizeof(arr.v[0]) + 16, 16); });
 	pl.jobs_bytes = cv.take(0) - pl.jobs_begin;
 	pl.total = cv.take(0);
+}
+
+// upload() finishes the placing: the blocks reserved, the descriptors' scratch pointers resolved (SP: batch_internal.h), the arrays staged.  No kernel
+// and no stream call, so a program without the HIP runtime links it and scans the staged image (tests/cpp/plan_dump.cpp): a pointer field missing from
+// the list below would hand a kernel an address with bit 63 set
+int Planner::upload() {
+	// ---- reserve device + pinned memory; one batch in flight per context ----
+	// one batch in flight per context: the previous one's status is kept in its object
+	if(harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE);
+	if(set.scratch.reserve(pl.total + 256) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
+	if(set.staging.reserve(pl.jobs_bytes + 256) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
+	base = (uint8_t *)set.scratch.p;
+	// every pointer field of every descriptor (SP offsets become base + offset; TopoJob.group_end: bytes into aux_u32)
+	for(auto &t : pl.tun.v) { resolve(t.src); resolve(t.dst); resolve(t.probs); }
+	for(auto &t : pl.tun_dict.v) { resolve(t.src); resolve(t.dst); resolve(t.probs); }
+	for(auto &f : pl.fill.v) resolve(f.dst);
+	for(auto &t : pl.topo.v) {
+		t.group_end = (const uint32_t *)(base + pl.aux_u32.dev_off + (uintptr_t)t.group_end);
+		resolve(t.clers); resolve(t.split_words); resolve(t.faces); resolve(t.pred); resolve(t.front_a); resolve(t.front_b); resolve(t.order);
+		resolve(t.delayed); resolve(t.status); resolve(t.flags);
+	}
+	for(auto &u : pl.unpack.v) { resolve(u.logs); resolve(u.words); resolve(u.out); }
+	for(auto &d : pl.delta.v) { resolve(d.values); resolve(d.pred); resolve(d.progress); resolve(d.out); resolve(d.flags); }
+	for(auto &c : pl.cloud.v) resolve(c.values);
+	for(auto &n : pl.normal.v) {
+		resolve(n.diffs); resolve(n.out); resolve(n.position); resolve(n.faces); resolve(n.status); resolve(n.pos_out); resolve(n.fn_scratch);
+	}
+	for(auto &q : pl.dequant.v) { resolve(q.buffer); resolve(q.src); }
+	for(auto &q : pl.quant.v) { resolve(q.values); resolve(q.range); }
+	for(auto &t : pl.tangent.v) { resolve(t.position); resolve(t.uv); resolve(t.faces); resolve(t.acc); }
+	for(auto &q : pl.meshlet_bounds.v) { resolve(q.position); resolve(q.counts); }
+	for(auto &m : pl.meshlet.v) { m.segs = base + pl.aux_u32.dev_off + (uintptr_t)m.segs; resolve(m.faces); resolve(m.scratch); resolve(m.rec_dev); }
+	for(auto &a : pl.adjacency.v) { resolve(a.index); resolve(a.counts); resolve(a.ends); resolve(a.list); }
+	for(auto &w : pl.weld.v) { resolve(w.position); resolve(w.index); resolve(w.counts); resolve(w.table); }
+
+	// host image -> device (one copy)
+	stage = (uint8_t *)set.staging.p;
+	memset(stage + (pl.unpack_partial_off - pl.jobs_begin), 0, unpack_state_words*8);
+	// (after the harvest above: the previous batch's words have been read)
+	memset(set.status_host.p, 0, hs.bytes());
+	if(pl.quant_records) {                                               // a quantised attribute of a blob without vertices has no job: its record is all zero, written
+		crthip_quant_transform *rec = (crthip_quant_transform *)((uint8_t *)set.status_host.p + hs.records());
+		for(const BlobPlan &P : b->blobs) {
+			for(size_t k = 0; k < P.bind.size(); k++) if(P.bind[k].buffer && P.bind[k].quantized && P.L.h.nvert == 0) rec[k].written = 1;
+			rec += P.bind.size();
+		}
+	}
+	auto stage_array = [&](auto &arr) { if(!arr.v.empty()) memcpy(stage + (arr.dev_off - pl.jobs_begin), arr.v.data(), arr.v.size()*sizeof(arr.v[0])); };
+	pl.each_array(stage_array); pl.each_optional_array(stage_array);
+
+	return CRTHIP_OK;
 }
 

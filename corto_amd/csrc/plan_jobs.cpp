@@ -65,7 +65,7 @@ const uint8_t *Planner::add_stream(const StreamRef &s, uint64_t sym_off, uint64_
 	t.chunk0 = tun_chunks; tun_pick_geometry(t);
 	if(t.nchunks > 1) pl.tun_multi_chunk = true;
 	pl.tun_max_nchunks = std::max(pl.tun_max_nchunks, t.nchunks);
-	for(uint32_t c = 0; c < t.nchunks; c++) pl.tun_chunk_stream.v.push_back((uint32_t)pl.tun.v.size());
+	push_blocks(pl.tun_chunk_stream, (uint32_t)pl.tun.v.size(), t.nchunks);
 	tun_chunks += t.nchunks;
 	t.dict = dict_of(s, t);
 	pl.tun.v.push_back(t);
@@ -82,7 +82,7 @@ void Planner::push_unpack(const BitBlock &bb, const StreamRef &s, const uint8_t 
 	if(bb.by_wave) { u.chain_chunk0 = bb.first_job; pl.unpack_wave_ids.v.push_back((uint32_t)pl.unpack.v.size()); }
 	else {
 		const uint32_t nc = (s.size + CHUNK - 1)/CHUNK;
-		for(uint32_t c = 0; c < nc; c++) pl.unpack_chunk_job.v.push_back((uint32_t)pl.unpack.v.size());
+		push_blocks(pl.unpack_chunk_job, (uint32_t)pl.unpack.v.size(), nc);
 		unpack_chunks += nc;
 	}
 	pl.unpack.v.push_back(u);
@@ -351,7 +351,7 @@ void Planner::quant_job(const BlobView &v, size_t k) {
 	else {
 		q.range = (uint32_t *)SP(A.qrange);
 		q.block0 = (uint32_t)pl.quant_block_job.v.size();
-		for(uint32_t c = 0; c < (nvert + QOUT_BLOCK - 1)/QOUT_BLOCK; c++) pl.quant_block_job.v.push_back((uint32_t)pl.quant.v.size());
+		push_blocks(pl.quant_block_job, (uint32_t)pl.quant.v.size(), (nvert + QOUT_BLOCK - 1)/QOUT_BLOCK);
 		// the seed of k_quant_range's integer atomics rides with the entropy stage's fills: 0xFF.. the minima, 0 the maxima (quant_out.h: qout_bias)
 		pl.fill.v.push_back(FillJob{SP(A.qrange), 16u, 0xFFu}); pl.fill.v.push_back(FillJob{SP(A.qrange + 16), 16u, 0u});
 	}
@@ -371,7 +371,7 @@ void Planner::dequant_job(const BlobView &v, size_t k) {
 	else if(bd.stride || bd.format == CRTHIP_FMT_DOUBLE) q.src = SP(A.vals);
 	const uint64_t elems = q.is_color ? v.nvert : (uint64_t)v.nvert*a.N;
 	const uint32_t nb = (uint32_t)((elems + CHUNK - 1)/CHUNK);
-	for(uint32_t c = 0; c < nb; c++) pl.dequant_block_job.v.push_back((uint32_t)pl.dequant.v.size());
+	push_blocks(pl.dequant_block_job, (uint32_t)pl.dequant.v.size(), nb);
 	pl.dequant.v.push_back(q);
 }
 
@@ -410,8 +410,8 @@ bool Planner::tangent_job(const BlobView &v) {
 	} else {
 		t.acc = (uint64_t *)SP(v.S.tan_acc);
 		t.fblock0 = (uint32_t)pl.tan_fblock_job.v.size(); t.vblock0 = (uint32_t)pl.tan_vblock_job.v.size();
-		for(uint32_t c = 0; c < (nface + TAN_BLOCK - 1)/TAN_BLOCK; c++) pl.tan_fblock_job.v.push_back((uint32_t)pl.tangent.v.size());
-		for(uint32_t c = 0; c < (nvert + TAN_BLOCK - 1)/TAN_BLOCK; c++) pl.tan_vblock_job.v.push_back((uint32_t)pl.tangent.v.size());
+		push_blocks(pl.tan_fblock_job, (uint32_t)pl.tangent.v.size(), (nface + TAN_BLOCK - 1)/TAN_BLOCK);
+		push_blocks(pl.tan_vblock_job, (uint32_t)pl.tangent.v.size(), (nvert + TAN_BLOCK - 1)/TAN_BLOCK);
 	}
 	pl.tangent.v.push_back(t);
 	return true;
@@ -441,7 +441,7 @@ void Planner::meshlet_jobs(const BlobView &v) {
 		pl.meshlet_waves = std::max(pl.meshlet_waves, bound.segments);
 	} else {
 		m.block0 = (uint32_t)pl.mlt_block_job.v.size();
-		for(uint32_t c = 0; c < bound.segments; c++) pl.mlt_block_job.v.push_back((uint32_t)pl.meshlet.v.size());
+		push_blocks(pl.mlt_block_job, (uint32_t)pl.meshlet.v.size(), bound.segments);
 	}
 	// meshlet bounds: crthip_batch_bind_meshlet_bounds.  The integer positions as the tangents take them, the arrays above, and the blob's counts
 	// in DEVICE memory: the binding's own copy, or one in scratch that the meshlet kernels write in its place.  Skipped when the blob's host_status
@@ -457,7 +457,7 @@ void Planner::meshlet_jobs(const BlobView &v) {
 		q.meshlets = mb.meshlets; q.vertices = mb.vertices; q.triangles = mb.triangles; q.counts = m.rec_dev; q.out = v.P.derived.bounds;
 		q.nvert = v.nvert; q.capacity = bound.meshlets;
 		q.block0 = (uint32_t)pl.mlb_block_job.v.size();
-		for(uint32_t c = 0; c < (bound.meshlets + MB_WAVES - 1)/MB_WAVES; c++) pl.mlb_block_job.v.push_back((uint32_t)pl.meshlet_bounds.v.size());
+		push_blocks(pl.mlb_block_job, (uint32_t)pl.meshlet_bounds.v.size(), (bound.meshlets + MB_WAVES - 1)/MB_WAVES);
 		pl.meshlet_bounds.v.push_back(q);
 	}
 	pl.meshlet.v.push_back(m);
@@ -483,13 +483,12 @@ void Planner::weld_jobs(const BlobView &v) {
 		const WeldScratchLayout lay = weld_scratch_layout(v.nvert);
 		w.table = (uint32_t *)SP(v.S.weld);
 		if(!wb.counts) w.counts = SP(v.S.weld + lay.record);
-		for(uint64_t o = 0, n = lay.record; o < n; o += 1u << 30)                  // (a FillJob's size is 32 bits)
-			pl.fill.v.push_back(FillJob{SP(v.S.weld + o), (uint32_t)std::min<uint64_t>(n - o, 1u << 30), 0u});
+		zero_fill(v.S.weld, lay.record);
 		w.vblock0 = (uint32_t)pl.weld_vblock_job.v.size();
-		for(uint32_t c = 0; c < weld_vblocks(v.nvert); c++) pl.weld_vblock_job.v.push_back(id);
+		push_blocks(pl.weld_vblock_job, id, weld_vblocks(v.nvert));
 		if(wb.index) {
 			w.cblock0 = (uint32_t)pl.weld_cblock_job.v.size();
-			for(uint32_t c = 0; c < weld_cblocks(v.nface); c++) pl.weld_cblock_job.v.push_back(id);
+			push_blocks(pl.weld_cblock_job, id, weld_cblocks(v.nface));
 		}
 	}
 	pl.weld.v.push_back(w);
@@ -515,11 +514,10 @@ void Planner::adjacency_jobs(const BlobView &v) {
 		const AdjScratchLayout lay = adj_scratch_layout(v.nvert, v.nface);
 		a.ends = (uint32_t *)SP(v.S.adj); a.list = (uint32_t *)SP(v.S.adj + lay.list);
 		if(!ab.counts) a.counts = SP(v.S.adj + lay.record);
-		for(uint64_t o = 0, n = ((uint64_t)v.nvert + 1)*4; o < n; o += 1u << 30)   // (a FillJob's size is 32 bits)
-			pl.fill.v.push_back(FillJob{SP(v.S.adj + o), (uint32_t)std::min<uint64_t>(n - o, 1u << 30), 0u});
+		zero_fill(v.S.adj, ((uint64_t)v.nvert + 1)*4);
 		pl.adj_big_ids.v.push_back(id);
 		a.block0 = (uint32_t)pl.adj_block_job.v.size();
-		for(uint32_t c = 0; c < adj_blocks(v.nface); c++) pl.adj_block_job.v.push_back(id);
+		push_blocks(pl.adj_block_job, id, adj_blocks(v.nface));
 	}
 	pl.adjacency.v.push_back(a);
 }

@@ -1,68 +1,21 @@
-// plan_launch.cpp — Planner::upload / launch / account: the blocks reserved, the descriptors' scratch pointers resolved (SP: batch_internal.h)
-// and the arrays staged, the kernels enqueued in the order of crt::Decoder::decodeMesh / decodePointCloud (src/decoder.cpp:133-196),
-// crthip_batch_stats filled.
+// plan_launch.cpp — Planner::launch / account: the schedule's shape, the kernels enqueued stage by stage in the order of crt::Decoder::decodeMesh /
+// decodePointCloud (src/decoder.cpp:133-196), crthip_batch_stats filled.  (Planner::upload: plan_group.cpp)
 #include "batch_internal.h"
-
-int Planner::upload() {
-	// ---- reserve device + pinned memory; one batch in flight per context ----
-	// one batch in flight per context: the previous one's status is kept in its object
-	if(harvest(ctx) != CRTHIP_OK) return fail(CRTHIP_E_DEVICE);
-	if(set.scratch.reserve(pl.total + 256) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
-	if(set.staging.reserve(pl.jobs_bytes + 256) != CRTHIP_OK) return fail(CRTHIP_E_NOMEM);
-	base = (uint8_t *)set.scratch.p;
-	// every pointer field of every descriptor (SP offsets become base + offset; TopoJob.group_end: bytes into aux_u32)
-	for(auto &t : pl.tun.v) { resolve(t.src); resolve(t.dst); resolve(t.probs); }
-	for(auto &t : pl.tun_dict.v) { resolve(t.src); resolve(t.dst); resolve(t.probs); }
-	for(auto &f : pl.fill.v) resolve(f.dst);
-	for(auto &t : pl.topo.v) {
-		t.group_end = (const uint32_t *)(base + pl.aux_u32.dev_off + (uintptr_t)t.group_end);
-		resolve(t.clers); resolve(t.split_words); resolve(t.faces); resolve(t.pred); resolve(t.front_a); resolve(t.front_b); resolve(t.order);
-		resolve(t.delayed); resolve(t.status); resolve(t.flags);
-	}
-	for(auto &u : pl.unpack.v) { resolve(u.logs); resolve(u.words); resolve(u.out); }
-	for(auto &d : pl.delta.v) { resolve(d.values); resolve(d.pred); resolve(d.progress); resolve(d.out); resolve(d.flags); }
-	for(auto &c : pl.cloud.v) resolve(c.values);
-	for(auto &n : pl.normal.v) {
-		resolve(n.diffs); resolve(n.out); resolve(n.position); resolve(n.faces); resolve(n.status); resolve(n.pos_out); resolve(n.fn_scratch);
-	}
-	for(auto &q : pl.dequant.v) { resolve(q.buffer); resolve(q.src); }
-	for(auto &q : pl.quant.v) { resolve(q.values); resolve(q.range); }
-	for(auto &t : pl.tangent.v) { resolve(t.position); resolve(t.uv); resolve(t.faces); resolve(t.acc); }
-	for(auto &q : pl.meshlet_bounds.v) { resolve(q.position); resolve(q.counts); }
-	for(auto &m : pl.meshlet.v) { m.segs = base + pl.aux_u32.dev_off + (uintptr_t)m.segs; resolve(m.faces); resolve(m.scratch); resolve(m.rec_dev); }
-	for(auto &a : pl.adjacency.v) { resolve(a.index); resolve(a.counts); resolve(a.ends); resolve(a.list); }
-	for(auto &w : pl.weld.v) { resolve(w.position); resolve(w.index); resolve(w.counts); resolve(w.table); }
-
-	// host image -> device (one copy)
-	stage = (uint8_t *)set.staging.p;
-	memset(stage + (pl.unpack_partial_off - pl.jobs_begin), 0, unpack_state_words*8);
-	// (after the harvest above: the previous batch's words have been read)
-	memset(set.status_host.p, 0, hs.bytes());
-	if(pl.quant_records) {                                               // a quantised attribute of a blob without vertices has no job: its record is all zero, written
-		crthip_quant_transform *rec = (crthip_quant_transform *)((uint8_t *)set.status_host.p + hs.records());
-		for(const BlobPlan &P : b->blobs) {
-			for(size_t k = 0; k < P.bind.size(); k++) if(P.bind[k].buffer && P.bind[k].quantized && P.L.h.nvert == 0) rec[k].written = 1;
-			rec += P.bind.size();
-		}
-	}
-	auto stage_array = [&](auto &arr) { if(!arr.v.empty()) memcpy(stage + (arr.dev_off - pl.jobs_begin), arr.v.data(), arr.v.size()*sizeof(arr.v[0])); };
-	pl.each_array(stage_array); pl.each_optional_array(stage_array);
-
-	return CRTHIP_OK;
-}
 
 // The schedule has two stages (batch_internal.h: PH_*).  Stage E - the descriptor copy, the zeroing, K-TAB, K-STREAM, k_fill - reads the batch's arena and
 // descriptors and writes only the batch's own scratch; stage M is everything behind it and writes the caller's outputs and the status words.
 // crthip_batch_decode runs both in one call.  crthip_batch_decode_with_next runs stage M of one batch with stage E of the lane's next batch:
 // as launches of its own (PH_TUN), or - `carry`, the next batch's K-TAB / K-STREAM arguments - inside this batch's k_front / k_delta_lds16 grids.
-bool Planner::splits() const {
-	const uint32_t ntun = (uint32_t)pl.tun.v.size(), nfill = (uint32_t)pl.fill.v.size();
-	if(pl.tun_multi_chunk) return false;
-	return !(!pl.topo.v.empty() && (ntun > clers_tun || nfill > clers_fill || unpack_chunks || !pl.unpack_wave_ids.v.empty()) && !ctx->single_stream);
+Planner::Shape Planner::shape() const {
+	if(pl.tun_multi_chunk) return Shape::LongStreams;
+	const bool attr_work = pl.tun.v.size() > clers_tun || pl.fill.v.size() > clers_fill || unpack_chunks || !pl.unpack_wave_ids.v.empty();
+	return !pl.topo.v.empty() && attr_work && !ctx->single_stream ? Shape::Forked : Shape::OneStream;
 }
+// one stream: the automata and the attributes' bit-unpack in one grid (k_front) when the batch has nothing else for either -
+// no big or HBM-front automaton, no chunked K-BIT - and the automata ask for little LDS (K-BIT's waves hold the same request)
 bool Planner::takes_front() const {
-	return ctx->single_stream && !ctx->dbg.front_off && !pl.topo_lds_ids.v.empty() && !pl.unpack_wave_ids.v.empty() && pl.topo_big_ids.v.empty() &&
-		pl.topo_glob_ids.v.empty() && !unpack_chunks && pl.topo_lds <= FRONT_LDS_MAX;
+	return shape() == Shape::OneStream && ctx->single_stream && !ctx->dbg.front_off && !pl.topo_lds_ids.v.empty() && !pl.unpack_wave_ids.v.empty() &&
+		pl.topo_big_ids.v.empty() && pl.topo_glob_ids.v.empty() && !unpack_chunks && pl.topo_lds <= FRONT_LDS_MAX;
 }
 // every stream of the batch through shared dictionaries of up to 64 symbols, in one K-TAB and one K-STREAM launch: what another batch's grids can carry
 bool Planner::carry_args(Carry &c) const {
@@ -81,12 +34,222 @@ bool Planner::carry_args(Carry &c) const {
 }
 // ... and a batch whose grids can carry them: k_front with room for the dictionaries' growth state in the automata's LDS request, and k_delta_lds16
 bool Planner::hosts_carry() const {
-	return !ctx->dbg.carry_off && splits() && takes_front() && pl.topo_lds >= TUN_CARRY_GROW_LDS && !pl.delta.v.empty() && !pl.delta_groups.v.empty();
+	return !ctx->dbg.carry_off && takes_front() && pl.topo_lds >= TUN_CARRY_GROW_LDS && !pl.delta.v.empty() && !pl.delta_groups.v.empty();
+}
+
+int tun_chain(Launch &LT, hipStream_t st, const std::vector<TunStream> &tun, const TunStream *streams, const uint32_t *chunk_stream, uint32_t chunks,
+	TunTable *tables, uint64_t *partial, uint32_t max_nchunks, bool multi, const FillJob *fill, uint32_t nfill) {
+	const uint32_t ntun = (uint32_t)tun.size();
+	if(ntun) {
+		// (an alphabet of more than 64 symbols builds its words in LDS: tun_tables.h)
+		uint32_t big = 0;
+		for(auto &t : tun) if(t.nsym > 64) big = TUN_TABLE_BYTES;
+		LT.run("tunstall_tables", k_tun_tables, dim3(ntun), dim3(64), big, st, streams, ntun, tables);
+		// (up to 256 chunks a stream: every decode wave adds up the sums in front of it itself; longer streams: one workgroup per stream
+		// scans them)
+		const bool scanned = max_nchunks > 256;
+		if(multi) LT.run("tunstall_chunk_sums", k_tun_chunk_sums, dim3(chunks), dim3(256), 0, st, streams, chunk_stream, chunks, tables, partial, 0u);
+		if(multi && scanned) LT.run("tunstall_stream_scan", k_tun_stream_scan, dim3(ntun), dim3(256), 0, st, streams, ntun, partial);
+		LT.begin("tunstall_decode", st);
+		if(multi) { if(launch_tun_decode_staged(st, streams, chunk_stream, chunks, tables, partial, scanned ? 0u : 1u)) return fail(CRTHIP_E_DEVICE); }
+		else hipLaunchKernelGGL(k_tun_decode, dim3(chunks), dim3(256), 0, st, streams, chunk_stream, chunks, tables, partial, 0u);
+		LT.end();
+	}
+	if(nfill) LT.run("fill", k_fill, dim3(nfill), dim3(256), 0, st, fill, nfill);
+	return CRTHIP_OK;
+}
+
+// the attribute streams' side of a fork: the context's second stream behind everything on the main one so far, and the main one behind it again
+int Planner::fork(hipStream_t *s2) {
+	{ int e_ = ctx_stream2(ctx, s2); if(e_) return e_; }
+	HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
+	HIP_TRY(hipStreamWaitEvent(*s2, ctx->ev_fork, 0));
+	return CRTHIP_OK;
+}
+int Planner::join(hipStream_t s2) {
+	HIP_TRY(hipEventRecord(ctx->ev_join, s2));
+	HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+	return CRTHIP_OK;
+}
+
+// K-TAB / K-STREAM of the streams [t0, t1) and k_fill of the fills [f0, f1): every stream here is one chunk, one wave per stream
+void Planner::entropy(hipStream_t s, uint32_t phases, uint32_t t0, uint32_t t1, uint32_t f0, uint32_t f1) {
+	const uint32_t ntun = (uint32_t)pl.tun.v.size(), ndict = (uint32_t)pl.tun_dict.v.size();
+	if(t1 > t0 && (phases & PH_TUN)) {
+		// [t0, t1) is the CLERS streams, the attribute streams, or both (dictionaries are numbered the same way)
+		const bool has_clers = t0 == 0 && clers_tun > 0, has_attrs = t1 == ntun && ntun > clers_tun;
+		const bool share = (!has_clers || share_clers) && (!has_attrs || share_attrs) && (has_clers || has_attrs);
+		// distinct tables first, then every stream decodes from its (shared) dictionary
+		if(share) {
+			const uint32_t d0 = has_clers ? 0u : clers_dict, d1 = has_attrs ? ndict : clers_dict;
+			// (an alphabet of more than 64 symbols builds its words in LDS: tun_tables.h)
+			uint32_t big = 0;
+			for(uint32_t d = d0; d < d1; d++) if(pl.tun_dict.v[d].nsym > 64) big = TUN_TABLE_BYTES;
+			TunTable *tables = (TunTable *)(base + pl.tables_off);
+			LT.run("tunstall_tables", k_tun_tables, dim3(d1 - d0), dim3(64), big, s, D(pl.tun_dict) + d0, d1 - d0, tables);
+			const uint32_t g0 = has_clers ? 0u : pl.clers_groups, g1 = has_attrs ? (uint32_t)pl.tun_groups.v.size() : pl.clers_groups;
+			LT.run("tunstall_stream", k_tun_stream_grouped, dim3(g1 - g0), dim3(256), 0, s, D(pl.tun), D(pl.tun_group_ids), D(pl.tun_groups) + g0, g1 - g0, tables);
+		} else LT.run("tunstall_stream", k_tun_stream, dim3(t1 - t0), dim3(64), 0, s, D(pl.tun) + t0, t1 - t0);   // dictionary + decode in one kernel
+	}
+	if(f1 > f0 && (phases & PH_FILL)) LT.run("fill", k_fill, dim3(f1 - f0), dim3(256), 0, s, D(pl.fill) + f0, f1 - f0);
+}
+void Planner::unpack(hipStream_t s) {
+	const uint32_t nuw = (uint32_t)pl.unpack_wave_ids.v.size();
+	if(nuw) LT.run("unpack_wave", k_unpack_wave, dim3(xcd_grid(nuw)), dim3(64), 0, s, D(pl.unpack), D(pl.unpack_wave_ids), nuw);
+	if(unpack_chunks) LT.run("unpack_extract", k_unpack_extract, dim3(unpack_chunks), dim3(256), 0, s, D(pl.unpack), D(pl.unpack_chunk_job), unpack_chunks,
+		(uint64_t *)(base + pl.unpack_partial_off));
+}
+// the automata: the two LDS size classes under one record, then those on the HBM front
+void Planner::topology() {
+	hipStream_t st = ctx->stream;
+	if(!pl.topo_lds_ids.v.empty() || !pl.topo_big_ids.v.empty()) {
+		const uint32_t nbg = (uint32_t)pl.topo_big_ids.v.size(), nl = (uint32_t)pl.topo_lds_ids.v.size();
+		LT.begin("topology_lds");
+		if(nbg) hipLaunchKernelGGL(k_topology_lds_big, dim3(nbg), dim3(64), pl.topo_big_lds, st, D(pl.topo), D(pl.topo_big_ids), nbg);
+		if(nl) hipLaunchKernelGGL(k_topology_lds, dim3(nl), dim3(64), pl.topo_lds, st, D(pl.topo), D(pl.topo_lds_ids), nl);
+		LT.end();
+	}
+	by_ids("topology", k_topology, 64, 0, pl.topo, pl.topo_glob_ids);
+}
+// K-DELTA's big jobs in tiles of 1 024 vertices (k_delta_tiles).  On a lone context this goes to the SECOND stream, behind the attribute streams' bit-unpack
+// and BESIDE the automaton, whose progress word the tiles wait for: a single big mesh's delta inversion trails its topology instead of following it
+// (config C2: 1.5 of 4.0 ms).  The automaton is enqueued first on its own stream and waits for nothing of this kernel.
+// BESIDE the automaton only a handful of workgroups: they hold 66 KB of LDS each while they wait, and a batch of hundreds of big meshes' tiles, resident
+// first, could keep the automata (up to 156 KB a workgroup) from ever finding a CU - the tiles would wait for a progress word nobody can write.  Up to 48
+// (sixteen big meshes' three attributes; a slice of an attribute of more than four components counts as one) leave most of the chip free; more run
+// behind the automaton as on a pool context.
+constexpr uint32_t TILES_BESIDE_MAX = 48;
+void Planner::delta_tiles(hipStream_t s) {
+	if(!nbig) return;
+	if(s != ctx->stream && nbig > TILES_BESIDE_MAX) return;
+	LT.begin("delta_tiles", s);
+	if(nbig > nslices) hipLaunchKernelGGL(k_delta_tiles<false>, dim3(nbig - nslices), dim3(DELTA_THREADS), 0, s, D(pl.delta), nbig - nslices);
+	if(nslices) hipLaunchKernelGGL(k_delta_tiles<true>, dim3(nslices), dim3(DELTA_THREADS), 0, s, D(pl.delta) + (nbig - nslices), nslices);
+	LT.end();
+	tiles_launched = true;
+}
+// long streams (scaled Tunstall runs, very large meshes): chunk offsets need one scan over all chunks; single stream
+int Planner::long_streams() {
+	hipStream_t st = ctx->stream;
+	const uint32_t nfill = (uint32_t)pl.fill.v.size();
+	{ int e_ = tun_chain(LT, st, pl.tun.v, D(pl.tun), D(pl.tun_chunk_stream), tun_chunks, (TunTable *)(base + pl.tables_off), (uint64_t *)(base + pl.tun_partial_off),
+		pl.tun_max_nchunks, true, D(pl.fill), nfill); if(e_) return e_; }
+	if(ctx->single_stream || !nbig || nbig > TILES_BESIDE_MAX || pl.topo.v.empty()) { topology(); unpack(st); return CRTHIP_OK; }
+	// a big mesh alone: every stream is decoded; the automaton (one serial chain: 2.2 of C2's 4 ms) goes on on the main stream, the attributes'
+	// bit-unpack and their delta inversion in tiles on the second one, the tiles trailing the automaton's progress word
+	hipStream_t s2;
+	{ int e_ = fork(&s2); if(e_) return e_; }
+	topology();
+	unpack(s2);
+	delta_tiles(s2);
+	return join(s2);
+}
+// fork: attribute streams on stream2, CLERS + topology on the main stream
+int Planner::forked() {
+	const uint32_t ntun = (uint32_t)pl.tun.v.size(), nfill = (uint32_t)pl.fill.v.size();
+	hipStream_t s2;
+	{ int e_ = fork(&s2); if(e_) return e_; }
+	entropy(ctx->stream, PH_ALL, 0, clers_tun, 0, clers_fill);
+	topology();
+	entropy(s2, PH_ALL, clers_tun, ntun, clers_fill, nfill);
+	unpack(s2);
+	delta_tiles(s2);
+	return join(s2);
+}
+// the automata and K-BIT of a one-stream batch: k_front where it takes them (takes_front; with `carry`, hosts_carry(): the next batch's dictionaries
+// behind K-BIT's waves), else the two launches
+void Planner::front(const Carry *carry) {
+	hipStream_t st = ctx->stream;
+	const uint32_t nuw = (uint32_t)pl.unpack_wave_ids.v.size(), ntl = (uint32_t)pl.topo_lds_ids.v.size();
+	if(!takes_front()) { topology(); unpack(st); }
+	else if(carry) LT.run("front", k_front_carry, dim3(front_topo_blocks(ntl) + xcd_grid(nuw) + carry->ndicts), dim3(64), pl.topo_lds, st, D(pl.topo),
+		D(pl.topo_lds_ids), ntl, D(pl.unpack), D(pl.unpack_wave_ids), nuw, carry->dicts, carry->ndicts, carry->tables);
+	else LT.run("front", k_front, dim3(front_topo_blocks(ntl) + xcd_grid(nuw)), dim3(64), pl.topo_lds, st, D(pl.topo), D(pl.topo_lds_ids), ntl, D(pl.unpack),
+		D(pl.unpack_wave_ids), nuw);
+}
+void Planner::delta(const Carry *carry) {
+	if(pl.delta.v.empty()) return;
+	hipStream_t st = ctx->stream;
+	const uint32_t ngroups = (uint32_t)pl.delta_groups.v.size();
+	if(!tiles_launched) delta_tiles(st);                    // (too big for the LDS records, and not launched beside the automaton above)
+	if(ngroups && carry)                                    // ... and the next batch's stream groups behind this batch's blobs
+		LT.run("delta_lds16", k_delta_lds16_carry, dim3(ngroups + carry->ngroups), dim3(256), std::max(pl.delta16_lds, TUN_CARRY_GROUP_LDS), st, D(pl.delta),
+			D(pl.delta_groups), ngroups, carry->streams, carry->ids, carry->groups, carry->ngroups, carry->tables);
+	else if(ngroups) LT.run("delta_lds16", k_delta_lds16, dim3(ngroups), dim3(256), pl.delta16_lds, st, D(pl.delta), D(pl.delta_groups), ngroups);
+}
+void Planner::cloud() {
+	if(!cloud_chunks) return;
+	hipStream_t st = ctx->stream;
+	uint64_t *cloud_partial = (uint64_t *)(base + pl.cloud_partial_off);
+	LT.run("cloud_sums", k_cloud_sums, dim3(cloud_chunks), dim3(256), 0, st, D(pl.cloud), D(pl.cloud_chunk_job), cloud_chunks, cloud_partial);
+	LT.run("scan", k_scan_u64, dim3(1), dim3(1024), 0, st, cloud_partial, cloud_chunks);
+	LT.run("cloud_apply", k_cloud_apply, dim3(cloud_chunks), dim3(256), 0, st, D(pl.cloud), D(pl.cloud_chunk_job), cloud_chunks, cloud_partial);
+}
+// the normals: the fused kernel over stored estimates, over blobs that store none (crthip_batch_bind_computed_normals), the unfused chain over the
+// batch-wide arrays, the stored differences
+void Planner::normals() {
+	hipStream_t st = ctx->stream;
+	by_ids("normal_blob", k_normal_blob<false>, 256, pl.normal_fused_lds, pl.normal, pl.normal_fused_ids, pl.normal_fused_lds);
+	by_ids("normal_blob_computed", k_normal_blob<true>, 256, pl.normal_computed_lds, pl.normal, pl.normal_computed_ids, pl.normal_computed_lds);
+	const uint32_t nvb = (uint32_t)pl.nv_block_job.v.size(), nfb = (uint32_t)pl.nf_block_job.v.size();
+	if(pl.any_est_normal) {
+		float *facen = (float *)(base + pl.facen_off);
+		uint32_t *cnt = (uint32_t *)(base + pl.cnt_off), *cursor = (uint32_t *)(base + pl.cursor_off), *bnd = (uint32_t *)(base + pl.bnd_off);
+		uint32_t *start = (uint32_t *)(base + pl.start_off), *flag = (uint32_t *)(base + pl.flag_off), *slot = (uint32_t *)(base + pl.slot_off);
+		uint32_t *adj = (uint32_t *)(base + pl.adj_off);
+		uint64_t *npart = (uint64_t *)(base + pl.nscan_partial_off);
+		const uint32_t nv = pl.est_nvert, nch = (nv + CHUNK - 1)/CHUNK;
+		auto scan = [&](uint32_t *in, uint32_t *out) {          // an exclusive scan over the batch's vertices: three launches, one record
+			LT.begin("normal_scan");
+			hipLaunchKernelGGL(k_u32_chunk_sums, dim3(nch), dim3(256), 0, st, in, nv, npart);
+			hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, st, npart, nch);
+			hipLaunchKernelGGL(k_u32_chunk_apply, dim3(nch), dim3(256), 0, st, in, out, nv, npart);
+			LT.end();
+		};
+		LT.run("normal_faces", k_normal_faces, dim3(nfb), dim3(256), 0, st, D(pl.normal), D(pl.nf_block_job), D(pl.nf_block_first), nfb, facen, cnt, bnd);
+		scan(cnt, start);
+		LT.run("normal_fill", k_normal_fill, dim3(nfb), dim3(256), 0, st, D(pl.normal), D(pl.nf_block_job), D(pl.nf_block_first), nfb, start, cursor, adj);
+		LT.run("normal_flags", k_normal_flags, dim3(nvb), dim3(256), 0, st, D(pl.normal), D(pl.nv_block_job), D(pl.nv_block_first), nvb, bnd, flag);
+		scan(flag, slot);
+		LT.run("normal_vertex", k_normal_vertex, dim3(nvb), dim3(256), 0, st, D(pl.normal), D(pl.nv_block_job), D(pl.nv_block_first), nvb, facen, start, cnt, adj,
+			flag, slot);
+	}
+	if(pl.any_diff_normal) LT.run("normal_diff", k_normal_diff, dim3(nvb), dim3(256), 0, st, D(pl.normal), D(pl.nv_block_job), D(pl.nv_block_first), nvb);
+}
+// the derived outputs, each in its blob kernel or in its kernels over scratch
+void Planner::derived() {
+	// computed tangents: behind every normal kernel (the normals are final), in front of k_dequant (packed position and uv buffers hold integers)
+	by_ids("tangent_blob", k_tangent_blob, TAN_THREADS, pl.tangent_lds, pl.tangent, pl.tangent_blob_ids);
+	by_ids("tangent_faces", k_tangent_faces, TAN_THREADS, 0, pl.tangent, pl.tan_fblock_job);
+	by_ids("tangent_vertex", k_tangent_vertex, TAN_THREADS, 0, pl.tangent, pl.tan_vblock_job);
+	// meshlets: the index has been final since the automata
+	by_ids("meshlet_blob", k_meshlet_blob, 64*pl.meshlet_waves, pl.meshlet_waves*(uint32_t)sizeof(MltWaveMem), pl.meshlet, pl.meshlet_blob_ids);
+	by_ids("meshlet_segments", k_meshlet_segments, 64, 0, pl.meshlet, pl.mlt_block_job);
+	by_ids("meshlet_place", k_meshlet_place, MLT_PLACE_THREADS, 0, pl.meshlet, pl.mlt_block_job);
+	// meshlet bounds: the meshlets are final, the positions still integers
+	by_ids("meshlet_bounds", k_meshlet_bounds, 64*MB_WAVES, 0, pl.meshlet_bounds, pl.mlb_block_job);
+	// the weld: the integer positions (k_dequant runs behind) and the index; in front of adjacency, which may read the welded index
+	by_ids("weld_blob", k_weld_blob, WELD_THREADS, pl.weld_lds, pl.weld, pl.weld_blob_ids);
+	by_ids("weld_insert", k_weld_insert, WELD_THREADS, 0, pl.weld, pl.weld_vblock_job);
+	by_ids("weld_lookup", k_weld_lookup, WELD_THREADS, 0, pl.weld, pl.weld_vblock_job);
+	by_ids("weld_index", k_weld_index, WELD_THREADS, 0, pl.weld, pl.weld_cblock_job);
+	// adjacency: the index alone, final since the automata
+	by_ids("adjacency_blob", k_adjacency_blob, ADJ_THREADS, pl.adjacency_lds, pl.adjacency, pl.adjacency_blob_ids);
+	by_ids("adjacency_count", k_adjacency_count, ADJ_THREADS, 0, pl.adjacency, pl.adj_block_job);
+	by_ids("adjacency_offsets", k_adjacency_offsets, ADJ_THREADS, 0, pl.adjacency, pl.adj_big_ids);
+	by_ids("adjacency_fill", k_adjacency_fill, ADJ_THREADS, 0, pl.adjacency, pl.adj_block_job);
+	by_ids("adjacency_twin", k_adjacency_twin, ADJ_THREADS, 0, pl.adjacency, pl.adj_block_job);
+}
+// the scratch path's finishers: k_dequant, and where it would sit the kernels of CRTHIP_BIND_QUANTIZED
+void Planner::finish() {
+	by_ids("dequantize", k_dequant, 256, 0, pl.dequant, pl.dequant_block_job);
+	by_ids("quant_out_blob", k_quant_out_blob, 256, 0, pl.quant, pl.quant_blob_ids);
+	by_ids("quant_range", k_quant_range, 256, 0, pl.quant, pl.quant_block_job);
+	by_ids("quant_store", k_quant_store, 256, 0, pl.quant, pl.quant_block_job);
 }
 
 int Planner::launch(uint32_t phases, const Carry *carry) {
 	hipStream_t st = ctx->stream;
-	Launch LT{ctx};
 	if(phases != PH_ALL && !splits()) return fail(CRTHIP_E_ARGUMENT, "this batch's schedule has no separate entropy stage");
 	if(phases & PH_UP) {
 		if(pl.jobs_bytes) HIP_TRY(hipMemcpyAsync(base + pl.jobs_begin, stage, pl.jobs_bytes, hipMemcpyHostToDevice, st));
@@ -94,270 +257,25 @@ int Planner::launch(uint32_t phases, const Carry *carry) {
 		for(uint32_t i = 0; i < nblobs; i++)                                         // the progress words of big meshes (a handful a batch at most)
 			if(bs[i].progress != ~0ull) HIP_TRY(hipMemsetAsync(base + bs[i].progress, 0, TOPO_PROGRESS_BYTES, st));
 	}
-
-	auto D = [&](auto &arr) { return (decltype(arr.v.data()))(base + arr.dev_off); };
-	TunTable *tables = (TunTable *)(base + pl.tables_off);
-	uint64_t *tun_partial = (uint64_t *)(base + pl.tun_partial_off);
-	uint64_t *unpack_partial = (uint64_t *)(base + pl.unpack_partial_off);
-	uint64_t *cloud_partial = (uint64_t *)(base + pl.cloud_partial_off);
-
-	const uint32_t ntun = (uint32_t)pl.tun.v.size();
-	const uint32_t nfill = (uint32_t)pl.fill.v.size();
-	const uint32_t ndict = (uint32_t)pl.tun_dict.v.size();
+	const uint32_t ntun = (uint32_t)pl.tun.v.size(), nfill = (uint32_t)pl.fill.v.size(), ndict = (uint32_t)pl.tun_dict.v.size();
 	// (a launch's streams share dictionaries when at least half of them repeat another one's table and there are enough of them for it to
 	// matter: share_clers / share_attrs, decided where the groups were made)
 	stat_dicts = (share_clers ? clers_dict : clers_tun) + (share_attrs ? ndict - clers_dict : ntun - clers_tun);
-	auto tunstall = [&](hipStream_t s, uint32_t t0, uint32_t t1, uint32_t c0, uint32_t c1, uint32_t f0, uint32_t f1) {
-		if(t1 > t0 && (phases & PH_TUN)) {                   // every stream here is one chunk: one wave per stream
-			(void)c0; (void)c1;
-			// [t0, t1) is the CLERS streams, the attribute streams, or both (dictionaries are numbered the same way)
-			const bool has_clers = t0 == 0 && clers_tun > 0, has_attrs = t1 == ntun && ntun > clers_tun;
-			const bool share = (!has_clers || share_clers) && (!has_attrs || share_attrs) && (has_clers || has_attrs);
-			// distinct tables first, then every stream decodes from its (shared) dictionary
-			if(share) {
-				const uint32_t d0 = has_clers ? 0u : clers_dict, d1 = has_attrs ? ndict : clers_dict;
-				// (an alphabet of more than 64 symbols builds its words in LDS: tun_tables.h)
-				uint32_t big = 0;
-				for(uint32_t d = d0; d < d1; d++) if(pl.tun_dict.v[d].nsym > 64) big = TUN_TABLE_BYTES;
-				LT.begin("tunstall_tables", s); hipLaunchKernelGGL(k_tun_tables, dim3(d1 - d0), dim3(64), big, s, D(pl.tun_dict) + d0,
-					d1 - d0, tables); LT.end();
-				const uint32_t g0 = has_clers ? 0u : pl.clers_groups, g1 = has_attrs ? (uint32_t)pl.tun_groups.v.size() : pl.clers_groups;
-				LT.begin("tunstall_stream", s); hipLaunchKernelGGL(k_tun_stream_grouped, dim3(g1 - g0), dim3(256), 0, s, D(pl.tun),
-					D(pl.tun_group_ids), D(pl.tun_groups) + g0, g1 - g0, tables); LT.end();
-			} else {                                           // dictionary + decode in one kernel
-				LT.begin("tunstall_stream", s); hipLaunchKernelGGL(k_tun_stream, dim3(t1 - t0), dim3(64), 0, s, D(pl.tun) + t0, t1 - t0);
-					LT.end();
-			}
-		}
-		if(f1 > f0 && (phases & PH_FILL)) { LT.begin("fill", s); hipLaunchKernelGGL(k_fill, dim3(f1 - f0), dim3(256), 0, s, D(pl.fill) + f0, f1 - f0); LT.end(); }
-	};
-	auto unpack = [&](hipStream_t s) {
-		const uint32_t nuw = (uint32_t)pl.unpack_wave_ids.v.size();
-		if(nuw) { LT.begin("unpack_wave", s); hipLaunchKernelGGL(k_unpack_wave, dim3(xcd_grid(nuw)), dim3(64), 0, s, D(pl.unpack),
-			D(pl.unpack_wave_ids), nuw); LT.end(); }
-		if(!unpack_chunks) return;
-		LT.begin("unpack_extract", s); hipLaunchKernelGGL(k_unpack_extract, dim3(unpack_chunks), dim3(256), 0, s, D(pl.unpack),
-			D(pl.unpack_chunk_job), unpack_chunks, unpack_partial); LT.end();
-	};
-	// K-DELTA's jobs too big for the LDS records (sorted to the front; behind them the groups of k_delta_lds16)
-	uint32_t nbig = 0, nslices = 0;                                              // (the slices: the last nslices of the nbig)
+	nbig = nslices = 0; tiles_launched = false;
 	for(auto &d : pl.delta.v) if(!delta_in_lds(d, wide)) { nbig++; nslices += d.N > 4 ? 1u : 0u; }
-	bool tiles_launched = false;
-	// the big ones in tiles of 1 024 vertices (k_delta_tiles).  On a lone context this goes to the SECOND stream, behind the attribute streams' bit-unpack
-	// and BESIDE the automaton, whose progress word the tiles wait for: a single big mesh's delta inversion trails its topology instead of following it
-	// (config C2: 1.5 of 4.0 ms).  The automaton is enqueued first on its own stream and waits for nothing of this kernel.
-	// BESIDE the automaton only a handful of workgroups: they hold 66 KB of LDS each while they wait, and a batch of hundreds of big meshes' tiles, resident
-	// first, could keep the automata (up to 156 KB a workgroup) from ever finding a CU - the tiles would wait for a progress word nobody can write.  Up to 48
-	// (sixteen big meshes' three attributes; a slice of an attribute of more than four components counts as one) leave most of the chip free; more run
-	// behind the automaton as on a pool context.
-	constexpr uint32_t TILES_BESIDE_MAX = 48;
-	auto delta_tiles = [&](hipStream_t s) {
-		if(!nbig) return;
-		if(s != st && nbig > TILES_BESIDE_MAX) return;
-		LT.begin("delta_tiles", s);
-		if(nbig > nslices) hipLaunchKernelGGL(k_delta_tiles<false>, dim3(nbig - nslices), dim3(DELTA_THREADS), 0, s, D(pl.delta), nbig - nslices);
-		if(nslices) hipLaunchKernelGGL(k_delta_tiles<true>, dim3(nslices), dim3(DELTA_THREADS), 0, s, D(pl.delta) + (nbig - nslices), nslices);
-		LT.end();
-		tiles_launched = true;
-	};
-	auto topology = [&]() -> int {
-		if(!pl.topo_lds_ids.v.empty() || !pl.topo_big_ids.v.empty()) {
-			LT.begin("topology_lds");
-			if(!pl.topo_big_ids.v.empty()) { const uint32_t nj = (uint32_t)pl.topo_big_ids.v.size(); hipLaunchKernelGGL(k_topology_lds_big,
-				dim3(nj), dim3(64), pl.topo_big_lds, st, D(pl.topo), D(pl.topo_big_ids), nj); }
-			if(!pl.topo_lds_ids.v.empty()) { const uint32_t nj = (uint32_t)pl.topo_lds_ids.v.size(); hipLaunchKernelGGL(k_topology_lds,
-				dim3(nj), dim3(64), pl.topo_lds, st, D(pl.topo), D(pl.topo_lds_ids), nj); }
-			LT.end();
-		}
-		if(!pl.topo_glob_ids.v.empty()) {
-			const uint32_t nj = (uint32_t)pl.topo_glob_ids.v.size();
-			LT.begin("topology"); hipLaunchKernelGGL(k_topology, dim3(nj), dim3(64), 0, st, D(pl.topo), D(pl.topo_glob_ids), nj); LT.end();
-		}
-		return CRTHIP_OK;
-	};
-	if(pl.tun_multi_chunk) {
-		// long streams (scaled Tunstall runs, very large meshes): chunk offsets need one scan over all chunks; single stream
-		uint32_t big = 0;
-		for(auto &t : pl.tun.v) if(t.nsym > 64) big = TUN_TABLE_BYTES;
-		LT.begin("tunstall_tables"); hipLaunchKernelGGL(k_tun_tables, dim3(ntun), dim3(64), big, st, D(pl.tun), ntun, tables); LT.end();
-		LT.begin("tunstall_chunk_sums"); hipLaunchKernelGGL(k_tun_chunk_sums, dim3(tun_chunks), dim3(256), 0, st, D(pl.tun),
-			D(pl.tun_chunk_stream), tun_chunks, tables, tun_partial, 0u); LT.end();
-		// (up to 256 chunks a stream: every decode wave adds up the sums in front of it itself; longer streams: one workgroup per stream
-		// scans them)
-		const bool scanned = pl.tun_max_nchunks > 256;
-		if(scanned) { LT.begin("tunstall_stream_scan"); hipLaunchKernelGGL(k_tun_stream_scan, dim3(ntun), dim3(256), 0, st, D(pl.tun),
-			ntun, tun_partial); LT.end(); }
-		LT.begin("tunstall_decode");
-		if(launch_tun_decode_staged(st, D(pl.tun), D(pl.tun_chunk_stream), tun_chunks, tables, tun_partial, scanned ? 0u : 1u)) return fail(CRTHIP_E_DEVICE);
-		LT.end();
-		if(nfill) { LT.begin("fill"); hipLaunchKernelGGL(k_fill, dim3(nfill), dim3(256), 0, st, D(pl.fill), nfill); LT.end(); }
-		if(!ctx->single_stream && nbig && nbig <= TILES_BESIDE_MAX && !pl.topo.v.empty()) {
-			// a big mesh alone: every stream is decoded; the automaton (one serial chain: 2.2 of C2's 4 ms) goes on on the main stream, the attributes'
-			// bit-unpack and their delta inversion in tiles on the second one, the tiles trailing the automaton's progress word
-			hipStream_t s2;
-			{ int e_ = ctx_stream2(ctx, &s2); if(e_) return e_; }
-			HIP_TRY(hipEventRecord(ctx->ev_fork, st));
-			HIP_TRY(hipStreamWaitEvent(s2, ctx->ev_fork, 0));
-			{ int e_ = topology(); if(e_) return e_; }
-			unpack(s2);
-			delta_tiles(s2);
-			HIP_TRY(hipEventRecord(ctx->ev_join, s2));
-			HIP_TRY(hipStreamWaitEvent(st, ctx->ev_join, 0));
-		} else {
-			{ int e_ = topology(); if(e_) return e_; }
-			unpack(st);
-		}
-	} else if(!pl.topo.v.empty() && (ntun > clers_tun || nfill > clers_fill || unpack_chunks || !pl.unpack_wave_ids.v.empty()) &&
-		!ctx->single_stream) {
-		// fork: attribute streams on stream2, CLERS + topology on the main stream
-		hipStream_t s2;
-		{ int e_ = ctx_stream2(ctx, &s2); if(e_) return e_; }
-		HIP_TRY(hipEventRecord(ctx->ev_fork, st));
-		HIP_TRY(hipStreamWaitEvent(s2, ctx->ev_fork, 0));
-		tunstall(st, 0, clers_tun, 0, clers_chunks, 0, clers_fill);
-		{ int e_ = topology(); if(e_) return e_; }
-		tunstall(s2, clers_tun, ntun, clers_chunks, tun_chunks, clers_fill, nfill);
-		unpack(s2);
-		delta_tiles(s2);
-		HIP_TRY(hipEventRecord(ctx->ev_join, s2));
-		HIP_TRY(hipStreamWaitEvent(st, ctx->ev_join, 0));
-	} else {
-		tunstall(st, 0, ntun, 0, tun_chunks, 0, nfill);
+	switch(shape()) {
+	case Shape::LongStreams: { int e_ = long_streams(); if(e_) return e_; } break;
+	case Shape::Forked: { int e_ = forked(); if(e_) return e_; } break;
+	case Shape::OneStream:
+		entropy(st, phases, 0, ntun, 0, nfill);
 		if(!(phases & PH_MESH)) { HIP_TRY(hipGetLastError()); return CRTHIP_OK; }
-		// one stream: the automata and the attributes' bit-unpack in one grid (k_front) when the batch has nothing else for either -
-		// no big or HBM-front automaton, no chunked K-BIT - and the automata ask for little LDS (K-BIT's waves hold the same request)
-		const uint32_t nuw = (uint32_t)pl.unpack_wave_ids.v.size(), ntl = (uint32_t)pl.topo_lds_ids.v.size();
-		if(takes_front() && carry) {                            // (hosts_carry(): the next batch's dictionaries behind K-BIT's waves)
-			LT.begin("front"); hipLaunchKernelGGL(k_front_carry, dim3(front_topo_blocks(ntl) + xcd_grid(nuw) + carry->ndicts), dim3(64), pl.topo_lds, st,
-				D(pl.topo), D(pl.topo_lds_ids), ntl, D(pl.unpack), D(pl.unpack_wave_ids), nuw, carry->dicts, carry->ndicts, carry->tables); LT.end();
-		} else if(takes_front()) {
-			LT.begin("front"); hipLaunchKernelGGL(k_front, dim3(front_topo_blocks(ntl) + xcd_grid(nuw)), dim3(64), pl.topo_lds, st, D(pl.topo),
-				D(pl.topo_lds_ids), ntl, D(pl.unpack), D(pl.unpack_wave_ids), nuw); LT.end();
-		} else {
-			{ int e_ = topology(); if(e_) return e_; }
-			unpack(st);
-		}
+		front(carry);
 	}
-	if(!pl.delta.v.empty()) {
-		const uint32_t ngroups = (uint32_t)pl.delta_groups.v.size();
-		if(!tiles_launched) delta_tiles(st);                    // (too big for the LDS records, and not launched beside the automaton above)
-		if(ngroups && carry) {                                  // ... and its stream groups behind this batch's blobs
-			LT.begin("delta_lds16"); hipLaunchKernelGGL(k_delta_lds16_carry, dim3(ngroups + carry->ngroups), dim3(256), std::max(pl.delta16_lds, TUN_CARRY_GROUP_LDS), st,
-				D(pl.delta), D(pl.delta_groups), ngroups, carry->streams, carry->ids, carry->groups, carry->ngroups, carry->tables); LT.end();
-		} else if(ngroups) { LT.begin("delta_lds16"); hipLaunchKernelGGL(k_delta_lds16, dim3(ngroups), dim3(256), pl.delta16_lds, st, D(pl.delta), D(pl.delta_groups),
-			ngroups); LT.end(); }
-	}
-	if(cloud_chunks) {
-		LT.begin("cloud_sums"); hipLaunchKernelGGL(k_cloud_sums, dim3(cloud_chunks), dim3(256), 0, st, D(pl.cloud), D(pl.cloud_chunk_job),
-			cloud_chunks, cloud_partial); LT.end();
-		LT.begin("scan"); hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, st, cloud_partial, cloud_chunks); LT.end();
-		LT.begin("cloud_apply"); hipLaunchKernelGGL(k_cloud_apply, dim3(cloud_chunks), dim3(256), 0, st, D(pl.cloud),
-			D(pl.cloud_chunk_job), cloud_chunks, cloud_partial); LT.end();
-	}
-	const uint32_t nvb = (uint32_t)pl.nv_block_job.v.size(), nfb = (uint32_t)pl.nf_block_job.v.size();
-	if(!pl.normal_fused_ids.v.empty()) {
-		const uint32_t nj = (uint32_t)pl.normal_fused_ids.v.size();
-		LT.begin("normal_blob"); hipLaunchKernelGGL(k_normal_blob<false>, dim3(nj), dim3(256), pl.normal_fused_lds, st, D(pl.normal),
-			D(pl.normal_fused_ids), nj, pl.normal_fused_lds); LT.end();
-	}
-	if(!pl.normal_computed_ids.v.empty()) {                     // blobs that store no normals (crthip_batch_bind_computed_normals)
-		const uint32_t nj = (uint32_t)pl.normal_computed_ids.v.size();
-		LT.begin("normal_blob_computed"); hipLaunchKernelGGL(k_normal_blob<true>, dim3(nj), dim3(256), pl.normal_computed_lds, st, D(pl.normal),
-			D(pl.normal_computed_ids), nj, pl.normal_computed_lds); LT.end();
-	}
-	if(pl.any_est_normal) {
-		float *facen = (float *)(base + pl.facen_off);
-		uint32_t *cnt = (uint32_t *)(base + pl.cnt_off), *cursor = (uint32_t *)(base + pl.cursor_off), *bnd = (uint32_t *)(base +
-			pl.bnd_off);
-		uint32_t *start = (uint32_t *)(base + pl.start_off), *flag = (uint32_t *)(base + pl.flag_off), *slot = (uint32_t *)(base +
-			pl.slot_off);
-		uint32_t *adj = (uint32_t *)(base + pl.adj_off);
-		uint64_t *npart = (uint64_t *)(base + pl.nscan_partial_off);
-		const uint32_t nv = pl.est_nvert, nch = (nv + CHUNK - 1)/CHUNK;
-		LT.begin("normal_faces"); hipLaunchKernelGGL(k_normal_faces, dim3(nfb), dim3(256), 0, st, D(pl.normal), D(pl.nf_block_job),
-			D(pl.nf_block_first), nfb, facen, cnt, bnd); LT.end();
-		LT.begin("normal_scan");
-		hipLaunchKernelGGL(k_u32_chunk_sums, dim3(nch), dim3(256), 0, st, cnt, nv, npart);
-		hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, st, npart, nch);
-		hipLaunchKernelGGL(k_u32_chunk_apply, dim3(nch), dim3(256), 0, st, cnt, start, nv, npart);
-		LT.end();
-		LT.begin("normal_fill"); hipLaunchKernelGGL(k_normal_fill, dim3(nfb), dim3(256), 0, st, D(pl.normal), D(pl.nf_block_job),
-			D(pl.nf_block_first), nfb, start, cursor, adj); LT.end();
-		LT.begin("normal_flags"); hipLaunchKernelGGL(k_normal_flags, dim3(nvb), dim3(256), 0, st, D(pl.normal), D(pl.nv_block_job),
-			D(pl.nv_block_first), nvb, bnd, flag); LT.end();
-		LT.begin("normal_scan");
-		hipLaunchKernelGGL(k_u32_chunk_sums, dim3(nch), dim3(256), 0, st, flag, nv, npart);
-		hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, st, npart, nch);
-		hipLaunchKernelGGL(k_u32_chunk_apply, dim3(nch), dim3(256), 0, st, flag, slot, nv, npart);
-		LT.end();
-		LT.begin("normal_vertex"); hipLaunchKernelGGL(k_normal_vertex, dim3(nvb), dim3(256), 0, st, D(pl.normal), D(pl.nv_block_job),
-			D(pl.nv_block_first), nvb, facen, start, cnt, adj, flag, slot); LT.end();
-	}
-	if(pl.any_diff_normal) { LT.begin("normal_diff"); hipLaunchKernelGGL(k_normal_diff, dim3(nvb), dim3(256), 0, st, D(pl.normal),
-		D(pl.nv_block_job), D(pl.nv_block_first), nvb); LT.end(); }
-	// computed tangents: behind every normal kernel (the normals are final), in front of k_dequant (packed position and uv buffers hold integers)
-	if(!pl.tangent_blob_ids.v.empty()) {
-		const uint32_t nj = (uint32_t)pl.tangent_blob_ids.v.size();
-		LT.begin("tangent_blob"); hipLaunchKernelGGL(k_tangent_blob, dim3(nj), dim3(TAN_THREADS), pl.tangent_lds, st, D(pl.tangent), D(pl.tangent_blob_ids), nj); LT.end();
-	}
-	if(!pl.tan_fblock_job.v.empty()) {
-		const uint32_t ntf = (uint32_t)pl.tan_fblock_job.v.size(), ntv = (uint32_t)pl.tan_vblock_job.v.size();
-		LT.begin("tangent_faces"); hipLaunchKernelGGL(k_tangent_faces, dim3(ntf), dim3(TAN_THREADS), 0, st, D(pl.tangent), D(pl.tan_fblock_job), ntf); LT.end();
-		LT.begin("tangent_vertex"); hipLaunchKernelGGL(k_tangent_vertex, dim3(ntv), dim3(TAN_THREADS), 0, st, D(pl.tangent), D(pl.tan_vblock_job), ntv); LT.end();
-	}
-	// meshlets: the index has been final since the automata
-	if(!pl.meshlet_blob_ids.v.empty()) {
-		const uint32_t nj = (uint32_t)pl.meshlet_blob_ids.v.size();
-		LT.begin("meshlet_blob"); hipLaunchKernelGGL(k_meshlet_blob, dim3(nj), dim3(64*pl.meshlet_waves), pl.meshlet_waves*(uint32_t)sizeof(MltWaveMem), st, D(pl.meshlet),
-			D(pl.meshlet_blob_ids), nj); LT.end();
-	}
-	if(!pl.mlt_block_job.v.empty()) {
-		const uint32_t nb = (uint32_t)pl.mlt_block_job.v.size();
-		LT.begin("meshlet_segments"); hipLaunchKernelGGL(k_meshlet_segments, dim3(nb), dim3(64), 0, st, D(pl.meshlet), D(pl.mlt_block_job), nb); LT.end();
-		LT.begin("meshlet_place"); hipLaunchKernelGGL(k_meshlet_place, dim3(nb), dim3(MLT_PLACE_THREADS), 0, st, D(pl.meshlet), D(pl.mlt_block_job), nb); LT.end();
-	}
-	// meshlet bounds: the meshlets are final, the positions still integers
-	if(!pl.mlb_block_job.v.empty()) {
-		const uint32_t nb = (uint32_t)pl.mlb_block_job.v.size();
-		LT.begin("meshlet_bounds"); hipLaunchKernelGGL(k_meshlet_bounds, dim3(nb), dim3(64*MB_WAVES), 0, st, D(pl.meshlet_bounds), D(pl.mlb_block_job), nb); LT.end();
-	}
-	// the weld: the integer positions (k_dequant runs behind) and the index; in front of adjacency, which may read the welded index
-	if(!pl.weld_blob_ids.v.empty()) {
-		const uint32_t nj = (uint32_t)pl.weld_blob_ids.v.size();
-		LT.begin("weld_blob"); hipLaunchKernelGGL(k_weld_blob, dim3(nj), dim3(WELD_THREADS), pl.weld_lds, st, D(pl.weld), D(pl.weld_blob_ids), nj); LT.end();
-	}
-	if(!pl.weld_vblock_job.v.empty()) {
-		const uint32_t nb = (uint32_t)pl.weld_vblock_job.v.size(), nc = (uint32_t)pl.weld_cblock_job.v.size();
-		LT.begin("weld_insert"); hipLaunchKernelGGL(k_weld_insert, dim3(nb), dim3(WELD_THREADS), 0, st, D(pl.weld), D(pl.weld_vblock_job), nb); LT.end();
-		LT.begin("weld_lookup"); hipLaunchKernelGGL(k_weld_lookup, dim3(nb), dim3(WELD_THREADS), 0, st, D(pl.weld), D(pl.weld_vblock_job), nb); LT.end();
-		if(nc) { LT.begin("weld_index"); hipLaunchKernelGGL(k_weld_index, dim3(nc), dim3(WELD_THREADS), 0, st, D(pl.weld), D(pl.weld_cblock_job), nc); LT.end(); }
-	}
-	// adjacency: the index alone, final since the automata
-	if(!pl.adjacency_blob_ids.v.empty()) {
-		const uint32_t nj = (uint32_t)pl.adjacency_blob_ids.v.size();
-		LT.begin("adjacency_blob"); hipLaunchKernelGGL(k_adjacency_blob, dim3(nj), dim3(ADJ_THREADS), pl.adjacency_lds, st, D(pl.adjacency), D(pl.adjacency_blob_ids), nj); LT.end();
-	}
-	if(!pl.adj_big_ids.v.empty()) {
-		const uint32_t nj = (uint32_t)pl.adj_big_ids.v.size(), nb = (uint32_t)pl.adj_block_job.v.size();
-		LT.begin("adjacency_count"); hipLaunchKernelGGL(k_adjacency_count, dim3(nb), dim3(ADJ_THREADS), 0, st, D(pl.adjacency), D(pl.adj_block_job), nb); LT.end();
-		LT.begin("adjacency_offsets"); hipLaunchKernelGGL(k_adjacency_offsets, dim3(nj), dim3(ADJ_THREADS), 0, st, D(pl.adjacency), D(pl.adj_big_ids), nj); LT.end();
-		LT.begin("adjacency_fill"); hipLaunchKernelGGL(k_adjacency_fill, dim3(nb), dim3(ADJ_THREADS), 0, st, D(pl.adjacency), D(pl.adj_block_job), nb); LT.end();
-		LT.begin("adjacency_twin"); hipLaunchKernelGGL(k_adjacency_twin, dim3(nb), dim3(ADJ_THREADS), 0, st, D(pl.adjacency), D(pl.adj_block_job), nb); LT.end();
-	}
-	const uint32_t ndq = (uint32_t)pl.dequant_block_job.v.size();
-	if(ndq) { LT.begin("dequantize"); hipLaunchKernelGGL(k_dequant, dim3(ndq), dim3(256), 0, st, D(pl.dequant), D(pl.dequant_block_job),
-		ndq); LT.end(); }
-	// CRTHIP_BIND_QUANTIZED: the scratch path's other finisher, where k_dequant sits
-	if(!pl.quant_blob_ids.v.empty()) {
-		const uint32_t nj = (uint32_t)pl.quant_blob_ids.v.size();
-		LT.begin("quant_out_blob"); hipLaunchKernelGGL(k_quant_out_blob, dim3(nj), dim3(256), 0, st, D(pl.quant), D(pl.quant_blob_ids), nj); LT.end();
-	}
-	if(!pl.quant_block_job.v.empty()) {
-		const uint32_t nqb = (uint32_t)pl.quant_block_job.v.size();
-		LT.begin("quant_range"); hipLaunchKernelGGL(k_quant_range, dim3(nqb), dim3(256), 0, st, D(pl.quant), D(pl.quant_block_job), nqb); LT.end();
-		LT.begin("quant_store"); hipLaunchKernelGGL(k_quant_store, dim3(nqb), dim3(256), 0, st, D(pl.quant), D(pl.quant_block_job), nqb); LT.end();
-	}
-
+	delta(carry);
+	cloud();
+	normals();
+	derived();
+	finish();
 	// (status: written by the kernels straight into the pinned block)
 	HIP_TRY(hipGetLastError());
 	return CRTHIP_OK;

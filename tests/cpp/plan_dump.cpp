@@ -1,12 +1,14 @@
 // plan_dump.cpp — the decode planner without a GPU: a stand-alone program built from plan_carve.cpp, plan_jobs.cpp, plan_group.cpp, batch_bind.cpp,
 // meshlet_host.cpp, crt_format.cpp and host_probe.cpp as plain C++ (no HIP runtime is linked: the stubs below stand in for harvest, drop_staged
-// and the four allocation calls; the pinned status block is mapped at a fixed address, so a plan's bytes are the same from run to run).
+// and the four allocation calls; the pinned blocks are mapped at fixed addresses and the scratch block has a fixed fake one, so a plan's bytes are
+// the same from run to run).
 // It walks a corpus of real blobs (tests/test_plan_jobs_cpu.py encodes them), fills crthip_batch::blobs as batch.cpp's fill does, binds through the
-// C ABI with constant fake addresses - the planner never dereferences the arena or a caller's buffer - and runs carve(), jobs(), group() for
-// every scenario.  Two things come of it:
+// C ABI with constant fake addresses - the planner never dereferences the arena, the scratch block or a caller's buffer - and runs carve(), jobs(),
+// group() and upload() for every scenario.  Two things come of it:
 //   - the invariants of the plan that no other CPU test sees (checked always; the exit code says whether they held), and
-//   - with --dump FILE, every job array as raw bytes, the Plan's scalars, every scratch offset, the Planner's counters, each blob's host status
-//     and the code and message of every bind call: what two builds of the planner are compared by (profiles/plan_jobs.md).
+//   - with --dump FILE, every job array as raw bytes, the Plan's scalars, every scratch offset, the Planner's counters, each blob's host status,
+//     the staged image and the status block as upload() leaves them, and the code and message of every bind call: what two builds of the planner
+//     are compared by (profiles/plan_jobs.md, profiles/plan_launch.md).
 // The program names no field that holds a derived binding: it builds against any tree that has these files.
 #include "batch_internal.h"
 
@@ -32,7 +34,8 @@ extern "C" hipError_t hipHostFree(void *ptr) {
 	munmap(ptr, pin_bytes[s]); pin_bytes[s] = 0;
 	return hipSuccess;
 }
-extern "C" hipError_t hipMalloc(void **ptr, size_t) { *ptr = nullptr; return hipErrorOutOfMemory; }
+static const uintptr_t DEV_BASE = 0x300000000000ull, ARENA_BASE = 0x400000000000ull, CALLER_BASE = 0x500000000000ull;
+extern "C" hipError_t hipMalloc(void **ptr, size_t) { *ptr = (void *)DEV_BASE; return hipSuccess; }   // the scratch block: upload() only adds to its address
 extern "C" hipError_t hipFree(void *) { return hipSuccess; }
 
 // ---- the corpus (tests/test_plan_jobs_cpu.py writes it in this order) ----
@@ -46,7 +49,7 @@ static int nscenes = 0, narrays = 0, nfailed = 0;
 struct Options { int tun_share = -1; bool wide = false, single_stream = false; uint32_t qout_blob_max = 0; };
 // what a scenario expects of its plan beyond the checks every plan gets (-1: not looked at)
 struct Expect {
-	int computed = -1, tangent = -1, meshlet = -1, bounds = -1;
+	int computed = -1, tangent = -1, meshlet = -1, bounds = -1, adjacency = -1, weld = -1;
 	bool no_derived = false;
 	bool no_pos_out = false;                // a position that is not FLOAT: no normal kernel finishes it
 	std::vector<uint32_t> ints_kept;        // blobs with tangents or bounds: the position's integers last until k_dequant
@@ -62,7 +65,7 @@ static void put(std::string &s, const char *key, uint64_t v) { char t[96]; snpri
 struct Scene {
 	std::string name, log;
 	crthip_ctx ctx; crthip_batch b;
-	uintptr_t next = 0x500000000000ull;
+	uintptr_t next = CALLER_BASE;
 	std::vector<std::vector<crthip_attr_binding>> at;    // what bind() hands over for each blob
 	std::vector<void *> index;
 
@@ -70,7 +73,7 @@ struct Scene {
 		ctx.dbg = DebugConfig{}; ctx.dbg.tun_share = o.tun_share; ctx.dbg.qout_blob_max = o.qout_blob_max;
 		ctx.delta.wide = o.wide;
 		if(o.single_stream) { ctx.single_stream = 1; ctx.normal_fn_max = 0; }            // (crthip_ctx_set_single_stream)
-		b.ctx = &ctx; b.d_arena = (const uint8_t *)0x400000000000ull;
+		b.ctx = &ctx; b.d_arena = (const uint8_t *)ARENA_BASE;
 		b.blobs.resize(which.size()); at.resize(which.size()); index.assign(which.size(), nullptr);
 		uint64_t off = 0;
 		for(size_t i = 0; i < which.size(); i++) {
@@ -117,9 +120,54 @@ struct Scene {
 	}
 	int meshlets(uint32_t i, const crthip_meshlet_binding *m) { return call("meshlets", i, crthip_batch_bind_meshlets(&b, i, m)); }
 	int meshlets(uint32_t i, uint32_t segment_faces = 0, bool counts = true) { const crthip_meshlet_binding m = meshlet_binding(i, segment_faces, counts); return meshlets(i, &m); }
+	crthip_adjacency_binding adjacency_binding(uint32_t i, bool counts) {
+		crthip_adjacency_binding a{};
+		a.twin = (uint32_t *)addr(); a.counts = counts ? (crthip_adjacency_counts *)addr() : nullptr; a.capacity = 3*L(i).h.nface;
+		return a;
+	}
+	int adjacency(uint32_t i, const crthip_adjacency_binding *a) { return call("adjacency", i, crthip_batch_bind_adjacency(&b, i, a)); }
+	int adjacency(uint32_t i, bool counts = true) { const crthip_adjacency_binding a = adjacency_binding(i, counts); return adjacency(i, &a); }
+	crthip_weld_binding weld_binding(uint32_t i, bool index, bool counts, uint32_t flags = 0) {
+		crthip_weld_binding w{};
+		w.remap = (uint32_t *)addr(); w.index = index ? (uint32_t *)addr() : nullptr; w.counts = counts ? (crthip_weld_counts *)addr() : nullptr;
+		w.remap_capacity = L(i).h.nvert; w.index_capacity = index ? 3*L(i).h.nface : 0; w.flags = flags;
+		return w;
+	}
+	int weld(uint32_t i, const crthip_weld_binding *w) { return call("weld", i, crthip_batch_bind_weld(&b, i, w)); }
+	int weld(uint32_t i, bool index = true, bool counts = true, uint32_t flags = 0) { const crthip_weld_binding w = weld_binding(i, index, counts, flags); return weld(i, &w); }
 	int bounds(uint32_t i, bool on = true, uint32_t capacity = ~0u) { return call("bounds", i, crthip_batch_bind_meshlet_bounds(&b, i, on ? (crthip_meshlet_bounds *)addr() : nullptr, capacity)); }
 
-	// carve, jobs, group; the plan as text (returned, and written to the dump behind the scenario's calls); the checks
+	// The staged image, word by word (8-byte words at 8-byte aligned device addresses).  No word is an unresolved scratch pointer - bit 63 set, the
+	// rest below the block's size: a pointer field that upload() does not resolve would hand a kernel that address.  (Two adjacent uint32 fields
+	// whose upper one is exactly 0x80000000 would look like one; no descriptor of this corpus holds such a pair.)  A word that upload() changed is a
+	// resolved pointer - an SP offset, TopoJob::group_end, MeshletJob::segs: it lies in the scratch block.  (A word it left alone is a pointer to the
+	// arena, a caller's buffer or the pinned block, null, or a pair of integers: without a list of the pointer fields - upload()'s own list over
+	// again - nothing tells them apart, and pairs like (nvert, nface) = (0x8100, 0x4f7d) do fall among this program's fake addresses.)
+	void check_image(const Planner &P, const Plan &pl, const std::vector<uint8_t> &before) {
+		const uintptr_t base = (uintptr_t)P.base;
+		CHECK(base == DEV_BASE, "the scratch block is at %llx", (unsigned long long)base);
+		auto in = [](uint64_t w, uint64_t lo, uint64_t bytes) { return w >= lo && w < lo + bytes; };
+		for(size_t o = (8 - pl.jobs_begin % 8) % 8; o + 8 <= pl.jobs_bytes; o += 8) {
+			uint64_t w, w0; memcpy(&w, P.stage + o, 8); memcpy(&w0, before.data() + o, 8);
+			CHECK(!((w >> 63) && (w & ~(1ull << 63)) < pl.total), "byte %zu of the staged image is the unresolved scratch pointer %016llx", o, (unsigned long long)w);
+			if(w != w0) CHECK(in(w, base, pl.total), "byte %zu of the staged image was resolved to %016llx, outside the scratch block of %llu bytes", o, (unsigned long long)w, (unsigned long long)pl.total);
+		}
+		// the zeroing FillJobs of a scratch table cover it exactly: adjacency's ends of a blob beyond LDS, the weld's table of one
+		auto zeroed = [&](const char *what, const void *table, uint64_t bytes) {
+			uint64_t cur = (uintptr_t)table, sum = 0;
+			for(bool more = true; more && cur < (uintptr_t)table + bytes;) {
+				more = false;
+				for(const FillJob &f : pl.fill.v) if((uintptr_t)f.dst == cur && f.value == 0 && f.size) { cur += f.size; more = true; break; }
+			}
+			for(const FillJob &f : pl.fill.v) if(in((uintptr_t)f.dst, (uintptr_t)table, bytes)) sum += f.size;
+			CHECK(cur == (uintptr_t)table + bytes && sum == bytes, "the zero fills of %s end %lld bytes from the table's end and write %llu of its %llu bytes", what,
+				(long long)((uintptr_t)table + bytes - cur), (unsigned long long)sum, (unsigned long long)bytes);
+		};
+		for(const AdjacencyJob &a : pl.adjacency.v) if(a.ends) zeroed("an adjacency job's ends", a.ends, ((uint64_t)a.nvert + 1)*4);
+		for(const WeldJob &w : pl.weld.v) if(w.table) zeroed("a weld job's table", w.table, weld_scratch_layout(w.nvert).record);
+	}
+
+	// carve, jobs, group, upload; the plan as text (returned, and written to the dump behind the scenario's calls); the checks
 	std::string plan(const Expect &ex = Expect{}) {
 		crthip_ctx::Half &set = ctx_set(&ctx, &b);
 		set.plan.reset();
@@ -142,6 +190,16 @@ struct Scene {
 			k++; narrays++;
 		});
 		CHECK(k == sizeof names/sizeof *names, "each_array has %zu arrays", k);
+		static const char *optional[] = {"adjacency", "adjacency_blob_ids", "adj_big_ids", "adj_block_job", "weld", "weld_blob_ids", "weld_vblock_job", "weld_cblock_job"};
+		k = 0;
+		pl.each_optional_array([&](auto &arr) {
+			s += "O "; s += k < sizeof optional/sizeof *optional ? optional[k] : "?";
+			put(s, "size", sizeof(arr.v[0])); put(s, "n", arr.v.size()); put(s, "dev_off", arr.dev_off); s += " ";
+			hex(s, arr.v.data(), arr.v.size()*sizeof(arr.v[0])); s += "\n";
+			CHECK(!arr.v.empty() || arr.dev_off == 0, "the empty optional array %s is placed at %llu", optional[k < 8 ? k : 7], (unsigned long long)arr.dev_off);
+			k++; narrays++;
+		});
+		CHECK(k == sizeof optional/sizeof *optional, "each_optional_array has %zu arrays", k);
 		s += "P";
 		put(s, "clers_groups", pl.clers_groups); put(s, "topo_lds", pl.topo_lds); put(s, "topo_big_lds", pl.topo_big_lds); put(s, "normal_fused_lds", pl.normal_fused_lds);
 		put(s, "normal_computed_lds", pl.normal_computed_lds); put(s, "tangent_lds", pl.tangent_lds); put(s, "meshlet_waves", pl.meshlet_waves);
@@ -165,7 +223,7 @@ struct Scene {
 			put(s, "dbg_nclers", B.dbg_nclers); put(s, "clers_in_arena", B.clers_in_arena);
 			put(s, "clers", S.clers); put(s, "pred", S.pred); put(s, "front_a", S.front_a); put(s, "front_b", S.front_b); put(s, "order", S.order); put(s, "delayed", S.delayed);
 			put(s, "faces", S.faces); put(s, "progress", S.progress); put(s, "front_cap", S.front_cap); put(s, "aux_groups", S.aux_groups); put(s, "tan_acc", S.tan_acc);
-			put(s, "mlt", S.mlt); put(s, "mlt_counts", S.mlt_counts); put(s, "cn_facen", S.cn_facen); s += "\n";
+			put(s, "mlt", S.mlt); put(s, "mlt_counts", S.mlt_counts); put(s, "cn_facen", S.cn_facen); put(s, "adj", S.adj); put(s, "weld", S.weld); s += "\n";
 			for(size_t a = 0; a < S.nattr; a++) {
 				const AttrScratch &T = S.attr[a];
 				s += " T"; put(s, "attr", a); put(s, "color", T.color); put(s, "diffs", T.diffs); put(s, "vals", T.vals); put(s, "facen", T.facen); put(s, "qrange", T.qrange);
@@ -173,9 +231,22 @@ struct Scene {
 				s += "\n";
 			}
 		}
+		// upload(): the image of the job arrays before it (SP offsets) and as it staged them (addresses), the status block as it prefilled it
+		std::vector<uint8_t> before;
+		if(!rc) {
+			before.assign(pl.jobs_bytes, 0);
+			auto image = [&](auto &arr) { if(!arr.v.empty()) memcpy(before.data() + (arr.dev_off - pl.jobs_begin), arr.v.data(), arr.v.size()*sizeof(arr.v[0])); };
+			pl.each_array(image); pl.each_optional_array(image);
+			if(set.staging.p) memset(set.staging.p, 0, set.staging.cap);      // (upload() never writes the gaps between the arrays: an earlier plan's bytes would show)
+			rc = P.upload();
+			s += "U"; put(s, "upload_rc", (uint64_t)(int64_t)rc); put(s, "base", (uint64_t)(uintptr_t)P.base); put(s, "stage", (uint64_t)(uintptr_t)P.stage);
+			if(!rc) { s += "\nI "; hex(s, P.stage, pl.jobs_bytes); s += "\nH "; hex(s, set.status_host.p, P.hs.bytes()); }
+			s += "\n";
+		}
 		if(dump) { fprintf(dump, "S %s\n%s%s", name.c_str(), log.c_str(), s.c_str()); }
 		log.clear(); nscenes++;
 		if(rc) { CHECK(rc == 0, "the plan failed with %d", rc); return s; }
+		check_image(P, pl, before);
 
 		// every id below its job array's size
 		auto ids = [&](const char *what, const std::vector<uint32_t> &v, size_t n) { for(uint32_t id : v) CHECK(id < n, "%s holds %u, the job array has %zu", what, id, n); };
@@ -190,6 +261,8 @@ struct Scene {
 		ids("tangent_blob_ids", pl.tangent_blob_ids.v, pl.tangent.v.size()); ids("tan_fblock_job", pl.tan_fblock_job.v, pl.tangent.v.size()); ids("tan_vblock_job", pl.tan_vblock_job.v, pl.tangent.v.size());
 		ids("meshlet_blob_ids", pl.meshlet_blob_ids.v, pl.meshlet.v.size()); ids("mlt_block_job", pl.mlt_block_job.v, pl.meshlet.v.size());
 		ids("mlb_block_job", pl.mlb_block_job.v, pl.meshlet_bounds.v.size());
+		ids("adjacency_blob_ids", pl.adjacency_blob_ids.v, pl.adjacency.v.size()); ids("adj_big_ids", pl.adj_big_ids.v, pl.adjacency.v.size()); ids("adj_block_job", pl.adj_block_job.v, pl.adjacency.v.size());
+		ids("weld_blob_ids", pl.weld_blob_ids.v, pl.weld.v.size()); ids("weld_vblock_job", pl.weld_vblock_job.v, pl.weld.v.size()); ids("weld_cblock_job", pl.weld_cblock_job.v, pl.weld.v.size());
 		for(const TunStream &t : pl.tun.v) CHECK(t.dict < pl.tun_dict.v.size(), "a stream's dictionary %u of %zu", t.dict, pl.tun_dict.v.size());
 		for(const TunGroup &g : pl.tun_groups.v) CHECK((size_t)g.first + g.count <= pl.tun_group_ids.v.size(), "a stream group ends at %u", g.first + g.count);
 		for(const DeltaGroup &g : pl.delta_groups.v) CHECK((size_t)g.first + g.count <= pl.delta.v.size(), "a delta group ends at %u", g.first + g.count);
@@ -216,11 +289,14 @@ struct Scene {
 			CHECK(pl.meshlet.v.empty() && pl.meshlet_blob_ids.v.empty() && pl.mlt_block_job.v.empty(), "%zu meshlet jobs", pl.meshlet.v.size());
 			CHECK(pl.meshlet_bounds.v.empty() && pl.mlb_block_job.v.empty(), "%zu bounds jobs", pl.meshlet_bounds.v.size());
 			CHECK(!pl.meshlet_records && !pl.quant_records, "records behind the status words: %u quant, meshlet %d", pl.quant_records, (int)pl.meshlet_records);
+			pl.each_optional_array([&](auto &arr) { CHECK(arr.v.empty() && arr.dev_off == 0, "an optional array of %zu entries at %llu", arr.v.size(), (unsigned long long)arr.dev_off); });
 		}
 		if(ex.computed >= 0) CHECK(computed == ex.computed, "%d computed normal jobs, expected %d", computed, ex.computed);
 		if(ex.tangent >= 0) CHECK((int)pl.tangent.v.size() == ex.tangent, "%zu tangent jobs, expected %d", pl.tangent.v.size(), ex.tangent);
 		if(ex.meshlet >= 0) CHECK((int)pl.meshlet.v.size() == ex.meshlet && pl.meshlet_records == (ex.meshlet > 0), "%zu meshlet jobs, expected %d", pl.meshlet.v.size(), ex.meshlet);
 		if(ex.bounds >= 0) CHECK((int)pl.meshlet_bounds.v.size() == ex.bounds, "%zu bounds jobs, expected %d", pl.meshlet_bounds.v.size(), ex.bounds);
+		if(ex.adjacency >= 0) CHECK((int)pl.adjacency.v.size() == ex.adjacency && pl.adjacency.v.size() == pl.adjacency_blob_ids.v.size() + pl.adj_big_ids.v.size(), "%zu adjacency jobs, expected %d", pl.adjacency.v.size(), ex.adjacency);
+		if(ex.weld >= 0) CHECK((int)pl.weld.v.size() == ex.weld, "%zu weld jobs, expected %d", pl.weld.v.size(), ex.weld);
 		for(uint32_t i : ex.ints_kept) {
 			const void *pos = b.blobs[i].bind[attr(i, "position")].buffer;
 			int dq = 0;
@@ -325,7 +401,52 @@ static void scenarios() {
 	  for(uint32_t i = 0; i < 3; i++) { s.normals(i); s.tangents(i); s.meshlets(i, i ? 8 : 0); s.bounds(i); }
 	  Expect e; e.computed = 3; e.tangent = e.meshlet = e.bounds = 3; e.ints_kept = {0, 1, 2}; e.pos_by_normal = {3}; s.plan(e); }
 
+	// adjacency and the weld: the 40-vertex sphere inside LDS, 33 024 vertices beyond adj_in_blob and weld_in_blob
+	{ Scene s("adjacency alone, with and without a counts record", {B_EST, B_NONORMAL, B_BEYOND16, B_BEYOND16, B_CLOUD});
+	  s.adjacency(0); s.adjacency(1, false); s.adjacency(2); s.adjacency(3, false);
+	  Expect e; e.computed = e.tangent = e.meshlet = e.bounds = e.weld = 0; e.adjacency = 4; e.pos_by_normal = {0}; s.plan(e);
+	  const Plan &pl = s.ctx.set[0].plan;
+	  CHECK(pl.adjacency_blob_ids.v.size() == 2 && pl.adj_big_ids.v.size() == 2, "%zu adjacency jobs in LDS, %zu beyond it", pl.adjacency_blob_ids.v.size(), pl.adj_big_ids.v.size());
+	  for(const AdjacencyJob &a : pl.adjacency.v) CHECK(!a.ends == !a.list && (a.counts || !a.ends), "an adjacency job with one of its two scratch arrays, or beyond LDS without a counts record"); }
+	{ Scene s("weld alone, with and without the welded index and a counts record", {B_EST, B_EST, B_BEYOND16, B_BEYOND16, B_UNFUSED, B_CLOUD});
+	  s.weld(0); s.weld(1, false, false); s.weld(2, true, false); s.weld(3, false, true); s.weld(4);
+	  Expect e; e.computed = e.tangent = e.meshlet = e.bounds = e.adjacency = 0; e.weld = 5; e.ints_kept = {0, 1, 2, 3, 4}; s.plan(e);
+	  const Plan &pl = s.ctx.set[0].plan;
+	  CHECK(pl.weld_blob_ids.v.size() == 2 && !pl.weld_vblock_job.v.empty() && !pl.weld_cblock_job.v.empty(), "%zu weld jobs in LDS", pl.weld_blob_ids.v.size());
+	  for(const WeldJob &w : pl.weld.v) CHECK(w.position && w.index && w.remap && (w.table ? w.counts != nullptr : true), "a weld job without an input, or one beyond LDS without a counts record"); }
+	{ Scene s("CRTHIP_WELD_ADJACENCY", {B_EST, B_BEYOND16, B_EST, B_BEYOND16});
+	  std::vector<const void *> welded;
+	  for(uint32_t i = 0; i < 4; i++) {
+		const crthip_weld_binding w = s.weld_binding(i, true, i & 1, i < 2 ? CRTHIP_WELD_ADJACENCY : 0u);
+		welded.push_back(i < 2 ? (const void *)w.index : s.index[i]);
+		if(i & 1) { s.adjacency(i); s.weld(i, &w); } else { s.weld(i, &w); s.adjacency(i, false); }     // (the order of the two calls does not matter)
+	  }
+	  Expect e; e.adjacency = e.weld = 4; s.plan(e);
+	  const Plan &pl = s.ctx.set[0].plan;
+	  for(size_t j = 0; j < pl.adjacency.v.size() && j < 4; j++)
+		CHECK(pl.adjacency.v[j].index == welded[j] && (j >= 2 || !pl.adjacency.v[j].index_u16), "adjacency job %zu does not read the index its weld flag says", j); }
+
+	// all six together
+	{ Scene s("all six, tangents over stored and over computed normals", {B_EST, B_BORDER, B_TANBIG, B_BEYOND16, B_NONORMAL});
+	  s.normals(4);
+	  for(uint32_t i = 0; i < 5; i++) { s.tangents(i); s.meshlets(i, i == 3 ? 4096 : 0, i != 1); s.bounds(i); s.weld(i, i != 2, i != 0, i & 1 ? CRTHIP_WELD_ADJACENCY : 0u); s.adjacency(i, i != 4); }
+	  Expect e; e.computed = 1; e.tangent = e.meshlet = e.bounds = e.adjacency = e.weld = 5; e.ints_kept = {0, 1, 2, 3, 4}; s.plan(e); }
+
 	// the cascades: what each call drops
+	{ Scene s("binding and unbinding adjacency and the weld", small);
+	  s.adjacency(0); s.weld(0); s.adjacency(3, false); s.weld(3, true, false, CRTHIP_WELD_ADJACENCY);
+	  { Expect e; e.adjacency = e.weld = 2; e.computed = e.tangent = e.meshlet = e.bounds = 0; s.plan(e); }
+	  s.adjacency(0, nullptr); s.adjacency(3, nullptr);
+	  { Expect e; e.adjacency = 0; e.weld = 2; s.plan(e); }
+	  s.weld(0, nullptr); s.weld(3, nullptr);
+	  Expect after = none; after.pos_by_normal = {0, 1};
+	  CHECK(s.plan(after) == plain_small, "binding and then unbinding adjacency and the weld does not give the plan of a batch that never bound them"); }
+	{ Scene s("a bind drops adjacency and the weld", small);
+	  s.adjacency(0); s.weld(0); s.adjacency(3); s.weld(3);
+	  { Expect e; e.adjacency = e.weld = 2; s.plan(e); }
+	  s.bind(0); s.bind(3);
+	  Expect after = none; after.pos_by_normal = {0, 1};
+	  CHECK(s.plan(after) == plain_small, "a bind behind adjacency and the weld does not give the plan of a batch that never had them"); }
 	{ Scene s("bind after everything derived", small);
 	  s.normals(3); s.tangents(3); s.meshlets(3); s.bounds(3); s.tangents(0); s.meshlets(0); s.bounds(0);
 	  Expect e; e.computed = 1; e.tangent = 2; e.meshlet = 2; e.bounds = 2; s.plan(e);
@@ -402,6 +523,28 @@ static void scenarios() {
 	  s.b.decoded = true;
 	  s.call("meshlet_counts", 2, crthip_batch_meshlet_counts(&s.b, 2, &mc)); s.call("quant_transform", 0, crthip_batch_quant_transform(&s.b, 0, 0, &qt));
 	  Expect e; e.computed = 0; e.tangent = 0; e.meshlet = 1; e.bounds = 0; s.plan(e); }
+	{ Scene s("refusals of adjacency and the weld", {B_EST, B_CLOUD, B_EST});
+	  { const crthip_adjacency_binding a{}; const crthip_weld_binding w{}; s.adjacency(9, &a); s.weld(9, &w); s.adjacency(9, nullptr); s.weld(9, nullptr); }
+	  s.adjacency(1); s.weld(1);                                                            // a point cloud
+	  { const crthip_adjacency_binding a = s.adjacency_binding(0, true);
+		crthip_adjacency_binding x = a; x.twin = nullptr; s.adjacency(0, &x);
+		x = a; x.twin = (uint32_t *)((uintptr_t)a.twin + 2); s.adjacency(0, &x);
+		x = a; x.counts = (crthip_adjacency_counts *)((uintptr_t)a.counts + 8); s.adjacency(0, &x);
+		x = a; x.reserved = 1; s.adjacency(0, &x);
+		x = a; x.capacity--; s.adjacency(0, &x); }
+	  { const crthip_weld_binding w = s.weld_binding(0, true, true);
+		crthip_weld_binding x = w; x.remap = nullptr; s.weld(0, &x);
+		x = w; x.remap = (uint32_t *)((uintptr_t)w.remap + 2); s.weld(0, &x);
+		x = w; x.index = (uint32_t *)((uintptr_t)w.index + 2); s.weld(0, &x);
+		x = w; x.counts = (crthip_weld_counts *)((uintptr_t)w.counts + 8); s.weld(0, &x);
+		x = w; x.remap_capacity--; s.weld(0, &x);
+		x = w; x.index_capacity--; s.weld(0, &x);
+		x = w; x.flags = 2; s.weld(0, &x);
+		x = w; x.reserved = 1; s.weld(0, &x);
+		x = w; x.index = nullptr; x.index_capacity = 0; x.flags = CRTHIP_WELD_ADJACENCY; s.weld(0, &x); }
+	  { crthip_attr_binding keep = s.A(2, "position"); s.A(2, "position").buffer = nullptr; s.A(2, "normal").buffer = nullptr; s.bind(2); s.weld(2); s.adjacency(2); s.A(2, "position") = keep; }
+	  { crthip_attr_binding keep = s.A(2, "position"); s.A(2, "position").format = CRTHIP_FMT_INT32; s.A(2, "position").reserved = CRTHIP_BIND_STREAM_VALUES; s.bind(2); s.weld(2); s.adjacency(2); s.A(2, "position") = keep; }
+	  Expect e; e.adjacency = 1; e.weld = 0; s.plan(e); }                                   // (adjacency needs no attribute: blob 2 keeps the one call that was taken)
 	{ Scene s("bind_all", small);
 	  std::vector<crthip_attr_binding> flat; std::vector<uint32_t> fmt;
 	  for(uint32_t i = 0; i < small.size(); i++) { flat.insert(flat.end(), s.at[i].begin(), s.at[i].end()); fmt.push_back(i & 1 ? CRTHIP_FMT_UINT16 : CRTHIP_FMT_UINT32); }

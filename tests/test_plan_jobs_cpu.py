@@ -1,11 +1,13 @@
 """The decode planner without a GPU: tests/cpp/plan_dump.cpp, a stand-alone program with its own main, is built from the planner's stage files
 (plan_carve.cpp, plan_jobs.cpp, plan_group.cpp), batch_bind.cpp, meshlet_host.cpp, crt_format.cpp and host_probe.cpp as plain C++ - no HIP
 runtime is linked - once plain and once under AddressSanitizer and UBSan, and run directly.  It binds real blobs from the host encoder through the C
-ABI's bind calls with constant fake addresses, runs carve(), jobs() and group() for every scenario and asserts what only the GPU suite saw before:
-binding and unbinding every derived output leaves the plan of a batch that never bound them; a batch without derived bindings has no tangent,
-meshlet or bounds job and no record behind the status words; after each cascade call (a bind, a normals call, a meshlets call) the dropped outputs have
-no jobs; with tangents or bounds the position's integers last until k_dequant, with one fused reader and neither the normal kernel writes the float
-positions; every id in every id and block map is below its job array's size.  profiles/plan_jobs.md: the same program compares two trees."""
+ABI's bind calls with constant fake addresses, runs carve(), jobs(), group() and upload() for every scenario and asserts what only the GPU suite saw
+before: binding and unbinding every derived output leaves the plan of a batch that never bound them; a batch without derived bindings has no tangent,
+meshlet, bounds, adjacency or weld job, no optional array placed and no record behind the status words; after each cascade call (a bind, a normals
+call, a meshlets call) the dropped outputs have no jobs; with tangents, bounds or a weld the position's integers last until k_dequant, with one fused
+reader and none of them the normal kernel writes the float positions; every id in every id and block map is below its job array's size; the zero
+fills of a scratch table cover it exactly; and, of the image upload() stages, no word is a scratch pointer left unresolved and every word upload()
+changed lies in the scratch block.  profiles/plan_jobs.md, profiles/plan_launch.md: the same program compares two trees."""
 import os
 import subprocess
 
