@@ -109,6 +109,29 @@ class WeldBinding(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+LOD_MAX_LEVELS = 4                                   # CRTHIP_LOD_MAX_LEVELS
+
+
+class LodCounts(C.Structure):
+    """crthip_lod_counts: a level's cells (vertices that are their cell's least), its kept, degenerate and duplicate faces"""
+    _fields_ = [("cells", C.c_uint32), ("faces", C.c_uint32), ("degenerate", C.c_uint32), ("duplicate", C.c_uint32)]
+
+    def as_tuple(self):
+        return (self.cells, self.faces, self.degenerate, self.duplicate)
+
+
+class LodLevel(C.Structure):
+    """crthip_lod_level: the device remap array, the device index of kept faces, the optional device counts record, the two capacities in words,
+    the shift"""
+    _fields_ = [("remap", C.c_void_p), ("index", C.c_void_p), ("counts", C.c_void_p), ("remap_capacity", C.c_uint32), ("index_capacity", C.c_uint32),
+                ("shift", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LodBinding(C.Structure):
+    """crthip_lod_binding: up to four levels of strictly increasing shift"""
+    _fields_ = [("level", LodLevel * LOD_MAX_LEVELS), ("levels", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class MeshletBinding(C.Structure):
     """crthip_meshlet_binding: three device arrays with their capacities, the optional device counts record, the builder's parameters"""
     _fields_ = [("meshlets", C.c_void_p), ("vertices", C.c_void_p), ("triangles", C.c_void_p), ("counts", C.c_void_p),
@@ -320,6 +343,9 @@ def lib():
         L.crthip_batch_bind_weld.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(WeldBinding)]
         L.crthip_weld_model.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(WeldCounts), C.c_void_p,
                                         C.c_int, C.c_uint32]
+        L.crthip_batch_bind_lod.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(LodBinding)]
+        L.crthip_lod_model.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(LodCounts),
+                                       C.c_void_p, C.c_int, C.c_uint32]
         L.crthip_batch_meshlet_counts.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshletCounts)]
         L.crthip_meshlet_bound.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(MeshletCounts)]
         L.crthip_meshlet_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(MeshletBinding), C.POINTER(MeshletCounts),
@@ -1082,6 +1108,27 @@ def weld_model(position: np.ndarray, index: np.ndarray, which: int = 0, seed: in
     return remap, windex, counts, (int(stats[0]), int(stats[1]))
 
 
+def lod_model(position: np.ndarray, index: np.ndarray, shift: int, which: int = 0, seed: int = 0, fill: int = 0xCD):
+    """crthip_lod_model: one level of crthip_batch_bind_lod on the host in the kernels' partition (which 0: lod_blob; 1: lod_insert / _lookup /
+    _faces / _keep / _offsets / _scatter; workgroups and threads, and so every atomic's order, shuffled by seed).  position (nvert, 3) int32;
+    index (nface, 3) uint32 or uint16.  The arrays are made here at exactly nvert and 3*nface words and filled with `fill` first.  Returns
+    (remap uint32 (nvert,), the level's index uint32 (3*nface,) of which 3*faces words are written, LodCounts, (vertex total, vertex longest,
+    face total, face longest) of the insert walks in slots)."""
+    pos = np.ascontiguousarray(position, dtype=np.int32).reshape(-1, 3)
+    idx = np.ascontiguousarray(index)
+    if idx.dtype != np.uint16:
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    idx = idx.reshape(-1, 3)
+    remap = np.full(len(pos), fill * 0x01010101, np.uint32)
+    lindex = np.full(len(idx) * 3, fill * 0x01010101, np.uint32)
+    counts = LodCounts()
+    stats = np.zeros(4, np.uint64)
+    _check(lib().crthip_lod_model(_np_ptr(pos) if len(pos) else None, _np_ptr(idx) if len(idx) else None, int(idx.dtype == np.uint16), len(idx), len(pos),
+                                  int(shift), _np_ptr(remap) if len(remap) else None, _np_ptr(lindex) if len(lindex) else None, C.byref(counts),
+                                  _np_ptr(stats), which, seed))
+    return remap, lindex, counts, tuple(int(x) for x in stats)
+
+
 def meshlet_bounds_model(position: np.ndarray, index, meshlets: np.ndarray, vertices: np.ndarray, triangles: np.ndarray, counts, seed: int = 0,
                          capacity=None, fill: int = 0xCD, raw: bool = False):
     """crthip_meshlet_bounds_model: crthip_batch_bind_meshlet_bounds on the host in the kernel's partition (workgroups, waves and the lanes of
@@ -1302,6 +1349,7 @@ class Batch:
         self._meshlet_bounds = {}                    # blob -> (pointer, capacity, the tensor or None): applied again behind those
         self._adjacency = {}                         # blob -> (AdjacencyBinding, (twin tensor, counts tensor or None) or None): applied again by rebind() too
         self._weld = {}                              # blob -> (WeldBinding, (remap tensor, index tensor or None, counts tensor or None) or None): applied again by rebind() too
+        self._lod = {}                               # blob -> (LodBinding, a list of (remap tensor, index tensor, counts tensor or None) a level, or None): applied again by rebind() too
         self._interleaved = None
 
     def __len__(self):
@@ -1346,7 +1394,7 @@ class Batch:
     # -- outputs -----------------------------------------------------------------------------------
     def allocate_outputs(self, normal_format=FMT_FLOAT, color_components: Optional[int] = None, index16=False,
                          only: Optional[set] = None, fill: Optional[int] = None, computed_normals=False, quantized=(),
-                         computed_tangents=False, tangent_format=FMT_FLOAT, meshlets=None, meshlet_bounds=False, adjacency=False, weld=False):
+                         computed_tangents=False, tangent_format=FMT_FLOAT, meshlets=None, meshlet_bounds=False, adjacency=False, weld=False, lod=None):
         """Allocate every output of every blob inside ONE device buffer (torch.uint8) and bind them.
         Returns a list (per blob) of dicts name -> torch tensor view.
         computed_normals: every mesh blob WITHOUT a normal attribute gets a "normal" tensor of normal_format all the same, bound
@@ -1364,7 +1412,9 @@ class Batch:
         read them with adjacency(i) after sync().
         weld: True - every mesh blob gets a remap array of nvert words, a welded index of 3*nface words and a device counts record, bound
         through crthip_batch_bind_weld; read them with weld(i) after sync().  "adjacency": the same with CRTHIP_WELD_ADJACENCY, so that the
-        twins of adjacency=True are those of the welded index."""
+        twins of adjacency=True are those of the welded index.
+        lod: a tuple of strictly increasing shifts, e.g. (9, 11) - every mesh blob gets, a level, a remap array of nvert words, an index of
+        3*nface words and a device counts record, bound through crthip_batch_bind_lod; read them with lod(i) after sync()."""
         if meshlet_bounds and meshlets is None:
             raise ValueError("allocate_outputs: meshlet_bounds needs meshlets=")
         import torch
@@ -1420,6 +1470,8 @@ class Batch:
         if not (weld is False or weld is True or weld == "adjacency"):
             raise ValueError("allocate_outputs: weld is False, True or \"adjacency\"")
         wplan = [(i, info.nvert, info.nface, take(max(info.nvert, 1) * 4), take(info.nface * 12), take(16)) for i, info in enumerate(self.infos) if info.nface] if weld else []
+        lplan = [(i, info.nvert, info.nface, [(int(s), take(max(info.nvert, 1) * 4), take(info.nface * 12), take(16)) for s in lod])
+                 for i, info in enumerate(self.infos) if info.nface] if lod else []
         total = max(off, 256)
         buf = torch.empty(total, dtype=torch.uint8, device=dev) if fill is None else torch.full((total,), fill, dtype=torch.uint8, device=dev)
         _torch_ready(dev)                            # (the fill runs on torch's stream; the decode on the context's own)
@@ -1443,6 +1495,13 @@ class Batch:
         for (i, nv, nf, ro, io, co) in wplan:
             self._weld[i] = (WeldBinding(base + ro, base + io, base + co, nv, nf * 3, WELD_ADJACENCY if weld == "adjacency" else 0, 0),
                              (buf[ro:ro + nv * 4], buf[io:io + nf * 12], buf[co:co + 16]))
+        self._lod = {}
+        for (i, nv, nf, levels) in lplan:
+            lb = LodBinding()
+            lb.levels = len(levels)
+            for k, (s, ro, io, co) in enumerate(levels[:LOD_MAX_LEVELS]):
+                lb.level[k] = LodLevel(base + ro, base + io, base + co, nv, nf * 3, s, 0)
+            self._lod[i] = (lb, [(buf[ro:ro + nv * 4], buf[io:io + nf * 12], buf[co:co + 16]) for (s, ro, io, co) in levels])
         computed, tangents = [], []
         tdt = {"f32": torch.float32, "i16": torch.int16, "u8": torch.uint8, "u32": torch.int32, "u16": torch.int16}
         for (i, name, o, dt, shape, slot, fmt, oc) in plan:
@@ -1517,6 +1576,7 @@ class Batch:
         self._meshlets, self._meshlet_bounds = {}, {}
         self._adjacency = {}
         self._weld = {}
+        self._lod = {}
         self._interleaved = metas
         self.outputs = [dict() for _ in self.infos]
         self.rebind()
@@ -1570,6 +1630,8 @@ class Batch:
             _check(lib().crthip_batch_bind_adjacency(self.handle, i, C.byref(ab)))
         for i, (wb, _) in self._weld.items():                   # (... and its weld)
             _check(lib().crthip_batch_bind_weld(self.handle, i, C.byref(wb)))
+        for i, (lb, _) in self._lod.items():                    # (... and its levels of detail)
+            _check(lib().crthip_batch_bind_lod(self.handle, i, C.byref(lb)))
 
     def bind(self, i: int, bindings: Sequence[AttrBinding], index_ptr: Optional[int] = None, index_format=FMT_UINT32):
         arr = (AttrBinding * max(len(bindings), 1))(*bindings)
@@ -1657,6 +1719,31 @@ class Batch:
         index = None if len(keep) < 2 or keep[1] is None else words(keep[1], self.infos[i].nface * 3)
         counts = None if len(keep) < 3 or keep[2] is None else tuple(int(x) for x in words(keep[2], 4))
         return remap, index, counts
+
+    def bind_lod(self, i: int, binding: Optional[LodBinding] = None, keep=None):
+        """crthip_batch_bind_lod: blob i's levels of detail go to the binding's device arrays (a level: remap at least nvert words, index at least
+        3*nface).  After bind() / rebind() of that blob, which drop it; None removes it.  keep: whatever owns the memory (device tensors), held
+        with the binding - a list of (remap, index, counts or None) a level makes lod(i) work."""
+        if binding is None:
+            self._lod.pop(i, None)
+            _check(lib().crthip_batch_bind_lod(self.handle, i, None))
+            return
+        _check(lib().crthip_batch_bind_lod(self.handle, i, C.byref(binding)))
+        self._lod[i] = (binding, keep)
+
+    def lod(self, i: int):
+        """Blob i's levels of detail on the host: a list, a level, of (remap uint32 (nvert,), the level's index uint32 cut to its 3*faces words - or
+        whole, all 3*nface words, where the level has no device record to say how many -, the counts as a tuple (cells, faces, degenerate,
+        duplicate) or None).  After sync(); for bindings made by allocate_outputs(lod=) or bind_lod(keep=)."""
+        _, keep = self._lod[i]
+        words = lambda t, n: t.cpu().numpy().view(np.uint8).reshape(-1)[:n * 4].view(np.uint32).copy()   # noqa: E731
+        out = []
+        for lv in keep:
+            remap = words(lv[0], self.infos[i].nvert)
+            counts = None if len(lv) < 3 or lv[2] is None else tuple(int(x) for x in words(lv[2], 4))
+            index = words(lv[1], self.infos[i].nface * 3)
+            out.append((remap, index if counts is None else index[:3 * counts[1]], counts))
+        return out
 
     def meshlet_counts(self, i: int) -> MeshletCounts:
         """crthip_batch_meshlet_counts: blob i's totals (meshlets, vertex words, triangle bytes, segments); after sync()"""

@@ -1,5 +1,5 @@
-// batch_bind.cpp — what a caller binds to a batch's blobs and what reads a decode's records back: crthip_batch_bind / _bind_all, the six derived
-// outputs (computed normals, computed tangents, meshlets, meshlet bounds, adjacency, weld: DerivedBindings, batch_internal.h), the quantised attributes' records and the
+// batch_bind.cpp — what a caller binds to a batch's blobs and what reads a decode's records back: crthip_batch_bind / _bind_all, the seven derived
+// outputs (computed normals, computed tangents, meshlets, meshlet bounds, adjacency, weld, levels of detail: DerivedBindings, batch_internal.h), the quantised attributes' records and the
 // meshlet counts.  Every check of a binding is made here, in the order corto_hip.h lists its errors, so that a decode has nothing new to fail on.
 // No HIP call: a program without the runtime links these (tests/cpp/plan_dump.cpp).
 #include "batch_internal.h"
@@ -189,6 +189,23 @@ extern "C" int crthip_batch_bind_weld(crthip_batch *b, uint32_t i, const crthip_
 	if(!generic_source_ok(P, attr_named(P, "position"), 3))
 		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "a weld needs a bound three-component \"position\" (bind the blob first)" + who);
 	P.derived.weld = *w;
+	b->dirty = true;
+	return CRTHIP_OK;
+}
+
+// Clustered levels of detail of the blob's index (corto_hip.h has the contract): every check is made here, in the header's order.  It reads what
+// the bind binds, like every derived binding; no other derived binding drops it and it drops none
+extern "C" int crthip_batch_bind_lod(crthip_batch *b, uint32_t i, const crthip_lod_binding *l) {
+	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_lod: no such blob");
+	BlobPlan &P = b->blobs[i];
+	const std::string who = " (blob " + std::to_string(i) + ")";
+	if(!l) { P.derived.lod = crthip_lod_binding{}; b->dirty = true; return CRTHIP_OK; }
+	if(P.L.h.nface == 0) return fail(CRTHIP_E_ARGUMENT, "levels of detail need faces: a point cloud has none" + who);
+	if(const char *why = lod_binding_error(l, P.L.h.nvert, P.L.h.nface)) return fail(CRTHIP_E_ARGUMENT, why + who);
+	// (what the weld asks of the position)
+	if(!generic_source_ok(P, attr_named(P, "position"), 3))
+		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "levels of detail need a bound three-component \"position\" (bind the blob first)" + who);
+	P.derived.lod = *l;
 	b->dirty = true;
 	return CRTHIP_OK;
 }

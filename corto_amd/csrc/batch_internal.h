@@ -4,7 +4,7 @@
 // program without the runtime links them; plan_carve.cpp / plan_jobs.cpp / plan_group.cpp: the planner's stages up to and with upload(), which
 // calls no kernel and no stream either; plan_launch.cpp: the schedule's shape (Planner::shape), launch() and its stage members - entropy, front,
 // delta, cloud, normals, derived, finish -, tun_chain, the stats).  Round 5 split batch.cpp (1 640 lines) along the Planner's stages.  A blob's derived bindings -
-// computed normals, tangents, meshlets, meshlet bounds, adjacency, weld - are one record, DerivedBindings.  Not part of the C ABI.
+// computed normals, tangents, meshlets, meshlet bounds, adjacency, weld, levels of detail - are one record, DerivedBindings.  Not part of the C ABI.
 #pragma once
 #include <chrono>
 #include <hip/hip_runtime.h>
@@ -30,6 +30,7 @@
 #include "meshlet_bounds.h"
 #include "adjacency.h"
 #include "weld.h"
+#include "lod.h"
 
 using namespace corto_hip;
 
@@ -100,10 +101,11 @@ struct BlobScratch {
 	uint64_t mlt_counts = ~0ull;                            // meshlet bounds (DerivedBindings::bounds) over a meshlet binding without a device counts record: 16 bytes for one
 	uint64_t adj = ~0ull;                                   // adjacency (DerivedBindings::adjacency) of a blob beyond adj_in_blob: adj_scratch_layout's block
 	uint64_t weld = ~0ull;                                  // weld (DerivedBindings::weld) of a blob beyond weld_in_blob: weld_scratch_layout's block
+	uint64_t lod[CRTHIP_LOD_MAX_LEVELS] = {~0ull, ~0ull, ~0ull, ~0ull};   // levels of detail (DerivedBindings::lod): a level's lod_scratch_layout block
 	uint64_t cn_facen = ~0ull;                              // computed normals (DerivedBindings::normals) by the fused kernel without its face normals in LDS: AttrScratch::facen's counterpart
 	std::vector<AttrScratch> attr;
 	size_t nattr = 0;                                       // attr[0..nattr) are this decode's (the vector only grows)
-	void reset() { clers = pred = front_a = front_b = order = delayed = faces = progress = cn_facen = tan_acc = mlt = mlt_counts = adj = weld = ~0ull; front_cap = 0; aux_groups = 0; nattr = 0; }
+	void reset() { clers = pred = front_a = front_b = order = delayed = faces = progress = cn_facen = tan_acc = mlt = mlt_counts = adj = weld = ~0ull; for(uint64_t &l : lod) l = ~0ull; front_cap = 0; aux_groups = 0; nattr = 0; }
 	void set_attrs(size_t n) { if(attr.size() < n) attr.resize(n); for(size_t k = nattr; k < n; k++) attr[k].reset();
 		if(n > nattr) nattr = n; }
 };
@@ -143,6 +145,9 @@ struct Plan {
 	// crthip_batch_bind_weld: blobs whose table fits LDS by id (k_weld_blob, weld_lds the largest request among them), the others 256 vertices a
 	// block (k_weld_insert, _lookup) and, those with an index output, 256 corners a block (k_weld_index)
 	HostArr<WeldJob> weld; HostArr<uint32_t> weld_blob_ids, weld_vblock_job, weld_cblock_job; uint32_t weld_lds = 0;
+	// crthip_batch_bind_lod: a job a bound level.  Jobs whose tables fit LDS by id (k_lod_blob, lod_lds the largest request among them), the others
+	// by id for the scan (k_lod_offsets), 256 vertices a block (k_lod_insert, _lookup) and 256 faces a block (k_lod_faces, _keep, _scatter)
+	HostArr<LodJob> lod; HostArr<uint32_t> lod_blob_ids, lod_big_ids, lod_vblock_job, lod_fblock_job; uint32_t lod_lds = 0;
 	bool meshlet_records = false;                           // a crthip_meshlet_counts a blob behind the quant records: a batch with a meshlet binding
 	uint32_t quant_records = 0;                             // records behind the status words: sum(nattr) of a batch with a quantised binding, else 0
 	// scratch regions (offsets)
@@ -165,14 +170,18 @@ struct Plan {
 		f(tangent); f(tangent_blob_ids); f(tan_fblock_job); f(tan_vblock_job);
 		f(meshlet); f(meshlet_blob_ids); f(mlt_block_job); f(meshlet_bounds); f(mlb_block_job);
 	}
-	// ... and behind them the arrays that are placed only where a batch has them: a batch without an adjacency or a weld binding keeps its block byte for byte
+	// ... and behind them the arrays that are placed only where a batch has them: a batch without an adjacency, a weld or a level-of-detail binding keeps its block byte for byte
 	// (an empty array of each_array's still takes 16 bytes of the block; tests/cpp/plan_dump.cpp names those one by one)
 	template <class F> void each_optional_array(F f) { f(adjacency); f(adjacency_blob_ids); f(adj_big_ids); f(adj_block_job); f(weld); f(weld_blob_ids); f(weld_vblock_job); f(weld_cblock_job); }
+	// ... and, by the same rule, the arrays of the levels of detail.  They are a list of their own because tests/cpp/plan_dump.cpp names
+	// each_optional_array's eight one by one
+	template <class F> void each_lod_array(F f) { f(lod); f(lod_blob_ids); f(lod_big_ids); f(lod_vblock_job); f(lod_fblock_job); }
 	void reset() {                                          // keep every vector's capacity
 		each_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
 		each_optional_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
+		each_lod_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
 		clers_groups = 0; topo_need.clear(); quant_records = 0; meshlet_waves = 0; meshlet_records = false;
-		topo_lds = topo_big_lds = normal_fused_lds = normal_computed_lds = tangent_lds = adjacency_lds = weld_lds = 0;
+		topo_lds = topo_big_lds = normal_fused_lds = normal_computed_lds = tangent_lds = adjacency_lds = weld_lds = lod_lds = 0;
 		zero_begin = zero_end = tables_off = tun_partial_off = unpack_partial_off = cloud_partial_off = 0;
 		facen_off = cnt_off = cursor_off = bnd_off = start_off = flag_off = slot_off = adj_off = nscan_partial_off = 0;
 		jobs_begin = jobs_bytes = 0; est_nvert = est_nface = 0; delta16_lds = 0;
@@ -257,6 +266,7 @@ struct DerivedBindings {
 	crthip_meshlet_bounds *bounds = nullptr;   // crthip_batch_bind_meshlet_bounds: a record a meshlet
 	crthip_adjacency_binding adjacency{};  // crthip_batch_bind_adjacency: adjacency.twin != null - where the blob's twins go (reads the index alone)
 	crthip_weld_binding weld{};            // crthip_batch_bind_weld: weld.remap != null - where the blob's weld map goes (reads the integer positions and the index)
+	crthip_lod_binding lod{};              // crthip_batch_bind_lod: lod.levels != 0 - where the blob's levels of detail go (reads the integer positions and the index)
 	void clear() { *this = DerivedBindings{}; }       // a bind (and a blob adopted by a fill): all of them read what it binds
 	void normals_change() { tangents = Binding{}; }   // a normals call: the tangents' normal source may change
 	void meshlets_change() { bounds = nullptr; }      // a meshlets call: the bounds' arrays and capacity change
@@ -368,6 +378,10 @@ static inline bool binds_adjacency(const BlobPlan &P) { return P.derived.adjacen
 // weld_in_blob).  welds_adjacency: the blob's adjacency kernels read the welded index (CRTHIP_WELD_ADJACENCY, looked at when a decode is planned)
 static inline bool binds_weld(const BlobPlan &P) { return P.derived.weld.remap && P.L.h.nface > 0; }
 static inline bool welds_adjacency(const BlobPlan &P) { return binds_weld(P) && binds_adjacency(P) && (P.derived.weld.flags & CRTHIP_WELD_ADJACENCY) && P.derived.weld.index; }
+
+// levels of detail (crthip_batch_bind_lod): a job a level; one whose tables fit LOD_BLOB_LDS_MAX takes k_lod_blob, the others the six kernels over
+// scratch (lod.h: lod_in_blob)
+static inline bool binds_lod(const BlobPlan &P) { return P.derived.lod.levels && P.L.h.nface > 0; }
 
 // where the derived outputs and the estimated normals take their inputs.  An attribute by name: the last one of that name, or -1
 static inline int attr_named(const BlobPlan &P, const char *name) {
@@ -488,6 +502,6 @@ struct Planner {
 	bool inverse_job(const BlobView &v, size_t k, void *values, uint32_t N, bool para, uint8_t is_u8, bool hand_i16);
 	void stored_normal_job(const BlobView &v, size_t k, bool hand_i16); void quant_job(const BlobView &v, size_t k); void dequant_job(const BlobView &v, size_t k);
 	bool estimated_normal_tail(const BlobView &v, NormalJob &n, HostArr<uint32_t> &fused_ids, uint32_t &fused_lds, uint64_t facen);
-	bool computed_normal_job(const BlobView &v); bool tangent_job(const BlobView &v); void meshlet_jobs(const BlobView &v); void weld_jobs(const BlobView &v); void adjacency_jobs(const BlobView &v);
+	bool computed_normal_job(const BlobView &v); bool tangent_job(const BlobView &v); void meshlet_jobs(const BlobView &v); void weld_jobs(const BlobView &v); void adjacency_jobs(const BlobView &v); void lod_jobs(const BlobView &v);
 };
 

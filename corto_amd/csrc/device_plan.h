@@ -251,10 +251,28 @@ struct WeldJob {
 	uint8_t index_u16, pad[7];
 };
 
+// one LEVEL of a blob bound with crthip_batch_bind_lod (k_lod.hip, lod.h): the integer positions and the index -> the level's remap, its index of
+// kept faces and its record.  The clustered triples are in scratch for every job; a job beyond lod_in_blob keeps its two tables and its block
+// counts there too
+struct LodJob {
+	const int32_t *position;       // nvert x 3 int32 as K-DELTA leaves them: the caller's packed buffer, or scratch
+	const void *index;             // u32 or, with index_u16, u16 triples: the caller's index, or scratch
+	uint32_t *remap;               // the level's nvert words
+	uint32_t *lod_index;           // the level's index: 3*faces words are written
+	void *counts;                  // crthip_lod_counts in DEVICE memory: the level's, or (bigger jobs only) scratch; null: none wanted
+	uint32_t *triples;             // scratch: 3*nface words
+	uint32_t *vtable, *ftable;     // bigger jobs: weld_slots(nvert) and weld_slots(nface) words zeroed by one FillJob
+	uint32_t *blocks;              // bigger jobs: a word a block of LOD_BLOCK faces - its kept count, then its base
+	uint32_t nface, nvert;
+	uint32_t vblock0, fblock0;     // first block of this job in the two block -> job maps (lod_insert and _lookup; lod_faces, _keep and _scatter)
+	uint32_t shift;
+	uint8_t index_u16, pad[3];
+};
+
 // the layout the kernels read, pinned (TopoJob's size is performance-critical: TOPO_OPT_PROGRESS above)
 static_assert(sizeof(TunStream) == 64 && sizeof(FillJob) == 16 && sizeof(TopoJob) == 136 && sizeof(UnpackJob) == 56 && sizeof(DeltaJob) == 96 &&
               sizeof(CloudJob) == 24 && sizeof(NormalJob) == 104 && sizeof(DequantJob) == 64 && sizeof(QuantOutJob) == 72 && sizeof(TangentJob) == 80 &&
-              sizeof(MeshletJob) == 104 && sizeof(MeshletBoundsJob) == 64 && sizeof(AdjacencyJob) == 56 && sizeof(WeldJob) == 72, "decode job layout");
+              sizeof(MeshletJob) == 104 && sizeof(MeshletBoundsJob) == 64 && sizeof(AdjacencyJob) == 56 && sizeof(WeldJob) == 72 && sizeof(LodJob) == 96, "decode job layout");
 static_assert(offsetof(TopoJob, opts) == 116 && offsetof(UnpackJob, out_kind) == 51 && offsetof(NormalJob, faces_u16) == 58, "decode job layout");
 static_assert(offsetof(DeltaJob, in_i16) == 34 && offsetof(DeltaJob, wide) == 35 && offsetof(DeltaJob, rounds) == 88 &&
               offsetof(DeltaJob, status_back) == 92, "decode job layout");

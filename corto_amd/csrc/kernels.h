@@ -86,6 +86,18 @@ __global__ void k_weld_insert(const WeldJob *jobs, const uint32_t *block_job, ui
 __global__ void k_weld_lookup(const WeldJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 __global__ void k_weld_index(const WeldJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 
+// k_lod.hip (crthip_batch_bind_lod; lod.h has the method and both partitions): a job is one level of one blob.  Jobs whose tables fit
+// LOD_BLOB_LDS_MAX by one workgroup each from an id list, with 4*max(weld_slots(nvert), weld_slots(nface)) bytes of dynamic LDS (the launch asks
+// for the largest among them); bigger ones 256 vertices a block from a block -> job map (insert, lookup), 256 faces a block from a second one
+// (faces, keep, scatter) and one workgroup a job from an id list (offsets)
+__global__ void k_lod_blob(const LodJob *jobs, const uint32_t *job_ids, uint32_t njobs);
+__global__ void k_lod_insert(const LodJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_lod_lookup(const LodJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_lod_faces(const LodJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_lod_keep(const LodJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_lod_offsets(const LodJob *jobs, const uint32_t *job_ids, uint32_t njobs);
+__global__ void k_lod_scatter(const LodJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+
 // k_mesh.hip
 __global__ void k_topology(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);
 __global__ void k_topology_lds(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);

@@ -95,6 +95,7 @@ void Planner::group() {
 	pl.unpack_partial_off = cv.take(unpack_state_words*8, 16);           // (first thing in the uploaded block: zeros)
 	pl.each_array([&](auto &arr) { arr.dev_off = cv.take(arr.v.size()*sizeof(arr.v[0]) + 16, 16); });
 	pl.each_optional_array([&](auto &arr) { if(!arr.v.empty()) arr.dev_off = cv.take(arr.v.size()*sizeof(arr.v[0]) + 16, 16); });
+	pl.each_lod_array([&](auto &arr) { if(!arr.v.empty()) arr.dev_off = cv.take(arr.v.size()*sizeof(arr.v[0]) + 16, 16); });
 	pl.jobs_bytes = cv.take(0) - pl.jobs_begin;
 	pl.total = cv.take(0);
 }
@@ -131,6 +132,7 @@ int Planner::upload() {
 	for(auto &m : pl.meshlet.v) { m.segs = base + pl.aux_u32.dev_off + (uintptr_t)m.segs; resolve(m.faces); resolve(m.scratch); resolve(m.rec_dev); }
 	for(auto &a : pl.adjacency.v) { resolve(a.index); resolve(a.counts); resolve(a.ends); resolve(a.list); }
 	for(auto &w : pl.weld.v) { resolve(w.position); resolve(w.index); resolve(w.counts); resolve(w.table); }
+	for(auto &l : pl.lod.v) { resolve(l.position); resolve(l.index); resolve(l.counts); resolve(l.triples); resolve(l.vtable); resolve(l.ftable); resolve(l.blocks); }
 
 	// host image -> device (one copy)
 	stage = (uint8_t *)set.staging.p;
@@ -145,7 +147,7 @@ int Planner::upload() {
 		}
 	}
 	auto stage_array = [&](auto &arr) { if(!arr.v.empty()) memcpy(stage + (arr.dev_off - pl.jobs_begin), arr.v.data(), arr.v.size()*sizeof(arr.v[0])); };
-	pl.each_array(stage_array); pl.each_optional_array(stage_array);
+	pl.each_array(stage_array); pl.each_optional_array(stage_array); pl.each_lod_array(stage_array);
 
 	return CRTHIP_OK;
 }

@@ -130,6 +130,7 @@ int Planner::jobs() {
 		if(builds_meshlets(v.P)) meshlet_jobs(v);
 		if(binds_weld(v.P) && !v.P.host_status) weld_jobs(v);
 		if(binds_adjacency(v.P) && !v.P.host_status) adjacency_jobs(v);
+		if(binds_lod(v.P) && !v.P.host_status) lod_jobs(v);
 	}
 	return CRTHIP_OK;
 }
@@ -144,8 +145,8 @@ Planner::BlobView Planner::view_of(uint32_t i, size_t rec0) {
 	const bool tangents = computes_tangents(P);
 	// ... and so do meshlet bounds, behind the meshlet kernels: the integer positions last until k_dequant
 	const bool bounds = bounds_meshlets(P);
-	// ... and so does the weld, in front of the adjacency kernels
-	const bool weld = binds_weld(P);
+	// ... and so do the weld, in front of the adjacency kernels, and the levels of detail behind them
+	const bool weld = binds_weld(P) || binds_lod(P);
 	// who turns the integer positions into floats: estimated normals read them as integers after K-DELTA, so the fused normal
 	// kernel does it as their last reader (pos_by_normal), the separate normal kernels leave it to k_dequant behind them, and
 	// without such normals K-DELTA does it on the way out of LDS like for every other attribute
@@ -492,6 +493,43 @@ void Planner::weld_jobs(const BlobView &v) {
 		}
 	}
 	pl.weld.v.push_back(w);
+}
+
+// levels of detail: crthip_batch_bind_lod.  A job a LEVEL: the integer positions as the weld takes them, the index where the automaton leaves it, the
+// level's arrays, its clustered triples in scratch; a job whose tables fit LDS needs no more.  The others keep both tables - zeroed by ONE FillJob in
+// stage E, so that a second decode starts clean -, a word a block of faces and, if the level has none, a record in scratch.  (The bind call
+// checked all of it)
+void Planner::lod_jobs(const BlobView &v) {
+	const crthip_lod_binding &lb = v.P.derived.lod;
+	const bool blob = lod_in_blob(v.nvert, v.nface);
+	if(!generic_source_ok(v.P, v.pos_k, 3)) { v.P.host_status = CRTHIP_E_NORMAL_NEEDS_POSITION; return; }
+	if(lod_binding_error(&lb, v.nvert, v.nface)) { v.P.host_status = CRTHIP_E_ARGUMENT; return; }
+	for(uint32_t k = 0; k < lb.levels; k++) if(v.S.lod[k] == ~0ull) { v.P.host_status = CRTHIP_E_ARGUMENT; return; }
+	const LodScratchLayout lay = lod_scratch_layout(v.nvert, v.nface);
+	const Faces f = faces_of(v.i);
+	for(uint32_t k = 0; k < lb.levels; k++) {
+		const crthip_lod_level &lv = lb.level[k];
+		const uint64_t S = v.S.lod[k];
+		LodJob l{};
+		l.position = ints_of(v.i, v.pos_k); l.index = f.p; l.index_u16 = f.u16;
+		l.remap = lv.remap; l.lod_index = lv.index; l.counts = lv.counts; l.nface = v.nface; l.nvert = v.nvert; l.shift = lv.shift;
+		l.triples = (uint32_t *)SP(S + lay.triples);
+		const uint32_t id = (uint32_t)pl.lod.v.size();
+		if(blob) {
+			pl.lod_blob_ids.v.push_back(id);
+			pl.lod_lds = std::max(pl.lod_lds, (uint32_t)(lod_table_slots(v.nvert, v.nface)*4));
+		} else {
+			l.vtable = (uint32_t *)SP(S + lay.vtable); l.ftable = (uint32_t *)SP(S + lay.ftable); l.blocks = (uint32_t *)SP(S + lay.blocks);
+			if(!lv.counts) l.counts = SP(S + lay.record);
+			zero_fill(S + lay.vtable, lay.tables_bytes);
+			pl.lod_big_ids.v.push_back(id);
+			l.vblock0 = (uint32_t)pl.lod_vblock_job.v.size();
+			for(uint32_t c = 0; c < weld_vblocks(v.nvert); c++) pl.lod_vblock_job.v.push_back(id);
+			l.fblock0 = (uint32_t)pl.lod_fblock_job.v.size();
+			for(uint32_t c = 0; c < lod_fblocks(v.nface); c++) pl.lod_fblock_job.v.push_back(id);
+		}
+		pl.lod.v.push_back(l);
+	}
 }
 
 // adjacency: crthip_batch_bind_adjacency.  The index where the automaton leaves it - or, under CRTHIP_WELD_ADJACENCY, the welded index of the blob's

@@ -239,6 +239,14 @@ void Planner::derived() {
 	by_ids("adjacency_offsets", k_adjacency_offsets, ADJ_THREADS, 0, pl.adjacency, pl.adj_big_ids);
 	by_ids("adjacency_fill", k_adjacency_fill, ADJ_THREADS, 0, pl.adjacency, pl.adj_block_job);
 	by_ids("adjacency_twin", k_adjacency_twin, ADJ_THREADS, 0, pl.adjacency, pl.adj_block_job);
+	// levels of detail: a job a level; the integer positions (k_dequant runs behind) and the index
+	by_ids("lod_blob", k_lod_blob, LOD_THREADS, pl.lod_lds, pl.lod, pl.lod_blob_ids);
+	by_ids("lod_insert", k_lod_insert, LOD_THREADS, 0, pl.lod, pl.lod_vblock_job);
+	by_ids("lod_lookup", k_lod_lookup, LOD_THREADS, 0, pl.lod, pl.lod_vblock_job);
+	by_ids("lod_faces", k_lod_faces, LOD_THREADS, 0, pl.lod, pl.lod_fblock_job);
+	by_ids("lod_keep", k_lod_keep, LOD_THREADS, 0, pl.lod, pl.lod_fblock_job);
+	by_ids("lod_offsets", k_lod_offsets, LOD_THREADS, 0, pl.lod, pl.lod_big_ids);
+	by_ids("lod_scatter", k_lod_scatter, LOD_THREADS, 0, pl.lod, pl.lod_fblock_job);
 }
 // the scratch path's finishers: k_dequant, and where it would sit the kernels of CRTHIP_BIND_QUANTIZED
 void Planner::finish() {

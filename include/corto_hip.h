@@ -58,6 +58,8 @@ extern "C" {
                                      crthip_adjacency_binding, crthip_batch_bind_adjacency, crthip_adjacency_model (two structs and two
                                      new calls, nothing else: the number stays 6); CRTHIP_WELD_ADJACENCY, crthip_weld_counts,
                                      crthip_weld_binding, crthip_batch_bind_weld, crthip_weld_model (two structs and two new calls,
+                                     nothing else: the number stays 6); CRTHIP_LOD_MAX_LEVELS, crthip_lod_counts, crthip_lod_level,
+                                     crthip_lod_binding, crthip_batch_bind_lod, crthip_lod_model (three structs and two new calls,
                                      nothing else: the number stays 6) */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
@@ -507,6 +509,50 @@ typedef struct crthip_weld_binding {
  * launch nothing new.
  * Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host, the crt::Decoder facade or the veneers. */
 int crthip_batch_bind_weld(crthip_batch *b, uint32_t i, const crthip_weld_binding *w);
+
+/* Clustered levels of detail: up to CRTHIP_LOD_MAX_LEVELS coarser INDEX buffers into the blob's unchanged vertex buffers, built on the GPU in the
+ * decode call by vertex clustering (meshopt_simplifySloppy's contract; kernels lod_blob, and lod_insert, lod_lookup, lod_faces, lod_keep,
+ * lod_offsets, lod_scatter in crthip_kernel_times; csrc/lod.h has the source the kernels and the test hook share).  Integer work only; the bytes
+ * are defined exactly.  p[v] is the delta-decoded INTEGER position of vertex v, as the weld reads it.
+ * A binding has 1 to CRTHIP_LOD_MAX_LEVELS levels, each with a `shift` in 0..31, strictly increasing.  For one level of shift s:
+ * cell(v) = (floor(p[v].x / 2^s), floor(p[v].y / 2^s), floor(p[v].z / 2^s)): an arithmetic shift of the signed coordinate.  -1 and 0 are never
+ *   in one cell; -1 and -2^s are.
+ * remap[v] (nvert words) = the LEAST vertex in v's cell.  With shift 0 it is the weld's remap to the byte.
+ * The CLUSTERED TRIPLE of face f: each corner's id goes to remap[id] if id < nvert, else it stays as it is (compared, never used as an
+ *   address); the face's own corner order is kept.  f is DEGENERATE if two of the three are equal or one is >= nvert.  Otherwise its KEY is the
+ *   triple rotated so that its least id comes first, the orientation kept: (a,b,c), (b,c,a) and (c,a,b) are one key, (a,c,b) is another.  f is
+ *   a DUPLICATE if a face below f has the same key.  Otherwise f is KEPT.
+ * index holds the kept faces in increasing f, three uint32 words each: the clustered triple, not rotated.  Exactly 3*faces words are written
+ *   and no word beyond them; every written word is < nvert.  The capacity must be at least 3*nface all the same.
+ * crthip_lod_counts: cells = the number of v with remap[v] == v; faces, degenerate, duplicate as above: faces + degenerate + duplicate == nface.
+ *   The record is optional and device-only, for indirect draws; as with the weld there is no host record.
+ * The position's own output and every other output are unchanged. */
+#define CRTHIP_LOD_MAX_LEVELS 4
+typedef struct crthip_lod_counts { uint32_t cells, faces, degenerate, duplicate; } crthip_lod_counts;
+typedef struct crthip_lod_level {
+	uint32_t *remap;                   /* DEVICE, 4-byte aligned, room for `remap_capacity` words */
+	uint32_t *index;                   /* DEVICE, 4-byte aligned, room for `index_capacity` words */
+	crthip_lod_counts *counts;         /* optional DEVICE record: 16 bytes, 16-byte aligned; or NULL */
+	uint32_t remap_capacity;           /* words of remap: at least nvert */
+	uint32_t index_capacity;           /* words of index: at least 3*nface */
+	uint32_t shift;                    /* 0..31, above the level's before */
+	uint32_t reserved;                 /* 0 */
+} crthip_lod_level;
+typedef struct crthip_lod_binding {
+	crthip_lod_level level[CRTHIP_LOD_MAX_LEVELS];
+	uint32_t levels;                   /* 1..CRTHIP_LOD_MAX_LEVELS: level[0..levels) are read */
+	uint32_t flags;                    /* 0 */
+	uint32_t reserved[2];              /* 0 */
+} crthip_lod_binding;
+/* Blob i's levels go to l's buffers in the decode.  Call it after crthip_batch_bind of blob i; l == NULL removes the binding; a later
+ * crthip_batch_bind of that blob drops it, as does crthip_batch_reset*.  The index itself may be bound as uint32, as uint16 or not at all.
+ * Independent of every other derived binding.  Every error is returned here, in this order, and nothing new can fail at decode time.
+ * CRTHIP_E_ARGUMENT: b NULL or i out of range; a point cloud (nface == 0); levels not in 1..CRTHIP_LOD_MAX_LEVELS; then per level, in level
+ * order: remap or index NULL or not 4-byte aligned; counts not 16-byte aligned; remap_capacity < nvert or index_capacity < 3*nface; shift > 31;
+ * shift not above the level's before; reserved != 0; then unknown flags or a reserved word not 0.  CRTHIP_E_NORMAL_NEEDS_POSITION: by the
+ * weld's rule.  crthip_last_error() names the blob.  Blobs without the binding launch nothing new.
+ * Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host, the crt::Decoder facade or the veneers. */
+int crthip_batch_bind_lod(crthip_batch *b, uint32_t i, const crthip_lod_binding *l);
 
 /* The record of attribute `attr` of blob i, bound with CRTHIP_BIND_QUANTIZED.  Valid after crthip_batch_sync of a decode: the kernels write
  * the records into the batch's pinned status block, beside the status words.  CRTHIP_E_ARGUMENT if that attribute was not bound
@@ -1193,6 +1239,16 @@ int crthip_adjacency_model(const void *index, uint32_t index_u16, uint32_t nface
  * remap where there is something to read or write, a misaligned remap or windex (4 bytes), 3*nface beyond 32 bits. */
 int crthip_weld_model(const int32_t *position, const void *index, uint32_t index_u16, uint32_t nface, uint32_t nvert, uint32_t *remap, uint32_t *windex,
                       crthip_weld_counts *counts, uint64_t *stats, int which, uint32_t seed);
+
+/* (test hook, no device needed)  ONE level of crthip_batch_bind_lod on the host: csrc/lod.h, the kernels' source, in their partition.  position:
+ * nvert*3 int32; index: nface*3 ids, uint16 if index_u16 else uint32 (ids >= nvert are allowed); remap: host memory, nvert words; lod_index:
+ * host memory, 3*nface words of which 3*faces are written; counts: the record, or NULL; stats: four words, the slots all vertex insert walks
+ * visited and the longest of them, then the same for the face inserts; or NULL.
+ * which 0: lod_blob, one workgroup with its table where the kernel has LDS (a job beyond its limit - more than 8 192 vertices or faces - is
+ * CRTHIP_E_LIMIT here; the decode sends such a job down the other path); which 1: lod_insert, lod_lookup, lod_faces, lod_keep, lod_offsets,
+ * lod_scatter.  Workgroups and threads, and with them every atomic, are walked in an order shuffled by seed: the bytes do not depend on it. */
+int crthip_lod_model(const int32_t *position, const void *index, uint32_t index_u16, uint32_t nface, uint32_t nvert, uint32_t shift, uint32_t *remap,
+                     uint32_t *lod_index, crthip_lod_counts *counts, uint64_t *stats, int which, uint32_t seed);
 
 #ifdef __cplusplus
 }
