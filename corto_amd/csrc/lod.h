@@ -266,7 +266,8 @@ template <class G> WELD_HD void lod_faces_block(G &g, const LodIn &J, const Weld
 	lod_triples(g, J, remap, tri, f0, f1);
 	lod_face_insert(g, J, ftb, weld_slots(J.w.nface), LodFaceKeyFromIndex{J.w, remap}, tri, f0, f1, stats);
 }
-// the verdicts: a dropped face is marked, the workgroup's kept faces go to its word, its other two counts to the record (9 bits each in one sum)
+// the verdicts: a dropped face is marked, the workgroup's kept faces go to its word, its other two counts to the record (three
+// fields of 10 bits in one sum, at bits 0, 10 and 20: a field reaches 256 where every face of a full block has one verdict, which needs 9 bits)
 template <class G> WELD_HD void lod_keep_block(G &g, const LodIn &J, const WeldMemTable &ftb, WELD_MEM uint32_t *tri, WELD_MEM uint32_t *blocks, WELD_MEM crthip_lod_counts *rec, uint32_t k) {
 	const uint64_t T = weld_slots(J.w.nface);
 	g.each([&](uint32_t tid, LodLane &L) {
