@@ -132,6 +132,38 @@ class LodBinding(C.Structure):
     _fields_ = [("level", LodLevel * LOD_MAX_LEVELS), ("levels", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+CLOUD_LOD_MAX_LEVELS = 4                             # CRTHIP_CLOUD_LOD_MAX_LEVELS
+
+
+class CloudLodCounts(C.Structure):
+    """crthip_cloud_lod_counts: a level's points (nvert), its cells (the kept points) and its chunks (0 for a level without a chunks array)"""
+    _fields_ = [("points", C.c_uint32), ("cells", C.c_uint32), ("chunks", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_tuple(self):
+        return (self.points, self.cells, self.chunks, self.reserved)
+
+
+class CloudChunk(C.Structure):
+    """crthip_cloud_chunk: the box of the kept points [first, first + count) of a level"""
+    _fields_ = [("min", C.c_int32 * 3), ("first", C.c_uint32), ("max", C.c_int32 * 3), ("count", C.c_uint32)]
+
+
+CLOUD_CHUNK_DTYPE = np.dtype([("min", "<i4", 3), ("first", "<u4"), ("max", "<i4", 3), ("count", "<u4")])   # crthip_cloud_chunk as a numpy record
+
+
+class CloudLodLevel(C.Structure):
+    """crthip_cloud_lod_level: the device remap and points arrays, the optional device weight array, chunk records and counts record, the
+    capacity of the first three in words and of the chunks in records, the shift"""
+    _fields_ = [("remap", C.c_void_p), ("points", C.c_void_p), ("weight", C.c_void_p), ("chunks", C.c_void_p), ("counts", C.c_void_p),
+                ("capacity", C.c_uint32), ("chunks_capacity", C.c_uint32), ("shift", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CloudLodBinding(C.Structure):
+    """crthip_cloud_lod_binding: up to four levels of strictly increasing shift, and the chunk size K of all of them"""
+    _fields_ = [("level", CloudLodLevel * CLOUD_LOD_MAX_LEVELS), ("levels", C.c_uint32), ("chunk_points", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class MeshletBinding(C.Structure):
     """crthip_meshlet_binding: three device arrays with their capacities, the optional device counts record, the builder's parameters"""
     _fields_ = [("meshlets", C.c_void_p), ("vertices", C.c_void_p), ("triangles", C.c_void_p), ("counts", C.c_void_p),
@@ -344,6 +376,9 @@ def lib():
         L.crthip_weld_model.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(WeldCounts), C.c_void_p,
                                         C.c_int, C.c_uint32]
         L.crthip_batch_bind_lod.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(LodBinding)]
+        L.crthip_batch_bind_cloud_lod.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(CloudLodBinding)]
+        L.crthip_cloud_lod_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(CloudLodCounts), C.c_void_p, C.c_int, C.c_uint32]
         L.crthip_lod_model.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(LodCounts),
                                        C.c_void_p, C.c_int, C.c_uint32]
         L.crthip_batch_meshlet_counts.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshletCounts)]
@@ -1129,6 +1164,27 @@ def lod_model(position: np.ndarray, index: np.ndarray, shift: int, which: int = 
     return remap, lindex, counts, tuple(int(x) for x in stats)
 
 
+def cloud_lod_model(position: np.ndarray, shift: int, chunk_points: int = 0, which: int = 0, seed: int = 0, weights: bool = True, fill: int = 0xCD):
+    """crthip_cloud_lod_model: one level of crthip_batch_bind_cloud_lod on the host in the kernels' partition (which 0: cloud_lod_blob; 1:
+    cloud_lod_insert / _lookup / _offsets / _scatter / _chunks; workgroups and threads, and so every atomic's order, shuffled by seed).
+    position (nvert, 3) int32, nvert >= 1; chunk_points 0: no chunks.  The arrays are made here at exactly nvert words and ceil(nvert /
+    chunk_points) records and filled with `fill` first.  Returns (remap uint32 (nvert,), points uint32 (nvert,) of which `cells` words are
+    written, weight uint32 (nvert,) likewise or None, chunks CLOUD_CHUNK_DTYPE (ceil(nvert / chunk_points),) of which `chunks` records are
+    written or None, CloudLodCounts, (total, longest) of the insert walks in slots)."""
+    pos = np.ascontiguousarray(position, dtype=np.int32).reshape(-1, 3)
+    nv = len(pos)
+    remap = np.full(nv, fill * 0x01010101, np.uint32)
+    points = np.full(nv, fill * 0x01010101, np.uint32)
+    weight = np.full(nv, fill * 0x01010101, np.uint32) if weights else None
+    chunks = np.frombuffer(bytearray([fill]) * (32 * ((nv + chunk_points - 1) // chunk_points)), CLOUD_CHUNK_DTYPE).copy() if chunk_points else None
+    counts = CloudLodCounts()
+    stats = np.zeros(2, np.uint64)
+    ptr = lambda a: _np_ptr(a) if a is not None and len(a) else None   # noqa: E731
+    _check(lib().crthip_cloud_lod_model(ptr(pos), nv, int(shift), int(chunk_points), ptr(remap), ptr(points), ptr(weight), ptr(chunks), C.byref(counts),
+                                        _np_ptr(stats), which, seed))
+    return remap, points, weight, chunks, counts, (int(stats[0]), int(stats[1]))
+
+
 def meshlet_bounds_model(position: np.ndarray, index, meshlets: np.ndarray, vertices: np.ndarray, triangles: np.ndarray, counts, seed: int = 0,
                          capacity=None, fill: int = 0xCD, raw: bool = False):
     """crthip_meshlet_bounds_model: crthip_batch_bind_meshlet_bounds on the host in the kernel's partition (workgroups, waves and the lanes of
@@ -1350,6 +1406,7 @@ class Batch:
         self._adjacency = {}                         # blob -> (AdjacencyBinding, (twin tensor, counts tensor or None) or None): applied again by rebind() too
         self._weld = {}                              # blob -> (WeldBinding, (remap tensor, index tensor or None, counts tensor or None) or None): applied again by rebind() too
         self._lod = {}                               # blob -> (LodBinding, a list of (remap tensor, index tensor, counts tensor or None) a level, or None): applied again by rebind() too
+        self._cloud_lod = {}                         # blob -> (CloudLodBinding, a list of (remap, points, weight or None, chunks or None, counts or None) tensors a level, or None): applied again by rebind() too
         self._interleaved = None
 
     def __len__(self):
@@ -1394,7 +1451,8 @@ class Batch:
     # -- outputs -----------------------------------------------------------------------------------
     def allocate_outputs(self, normal_format=FMT_FLOAT, color_components: Optional[int] = None, index16=False,
                          only: Optional[set] = None, fill: Optional[int] = None, computed_normals=False, quantized=(),
-                         computed_tangents=False, tangent_format=FMT_FLOAT, meshlets=None, meshlet_bounds=False, adjacency=False, weld=False, lod=None):
+                         computed_tangents=False, tangent_format=FMT_FLOAT, meshlets=None, meshlet_bounds=False, adjacency=False, weld=False, lod=None,
+                         cloud_lod=None):
         """Allocate every output of every blob inside ONE device buffer (torch.uint8) and bind them.
         Returns a list (per blob) of dicts name -> torch tensor view.
         computed_normals: every mesh blob WITHOUT a normal attribute gets a "normal" tensor of normal_format all the same, bound
@@ -1414,7 +1472,10 @@ class Batch:
         through crthip_batch_bind_weld; read them with weld(i) after sync().  "adjacency": the same with CRTHIP_WELD_ADJACENCY, so that the
         twins of adjacency=True are those of the welded index.
         lod: a tuple of strictly increasing shifts, e.g. (9, 11) - every mesh blob gets, a level, a remap array of nvert words, an index of
-        3*nface words and a device counts record, bound through crthip_batch_bind_lod; read them with lod(i) after sync()."""
+        3*nface words and a device counts record, bound through crthip_batch_bind_lod; read them with lod(i) after sync().
+        cloud_lod: (shifts, chunk_points), e.g. ((9, 11), 64) - every point cloud with points gets, a level, a remap, a points and a weight
+        array of nvert words, ceil(nvert / chunk_points) chunk records and a device counts record, placed behind all other arrays and bound
+        through crthip_batch_bind_cloud_lod; meshes are skipped; read them with cloud_lod(i) after sync()."""
         if meshlet_bounds and meshlets is None:
             raise ValueError("allocate_outputs: meshlet_bounds needs meshlets=")
         import torch
@@ -1472,6 +1533,13 @@ class Batch:
         wplan = [(i, info.nvert, info.nface, take(max(info.nvert, 1) * 4), take(info.nface * 12), take(16)) for i, info in enumerate(self.infos) if info.nface] if weld else []
         lplan = [(i, info.nvert, info.nface, [(int(s), take(max(info.nvert, 1) * 4), take(info.nface * 12), take(16)) for s in lod])
                  for i, info in enumerate(self.infos) if info.nface] if lod else []
+        cplan = []                                   # (blob, nvert, chunk records, [(shift, remap, points, weight, chunks, counts offsets) a level])
+        if cloud_lod:
+            cshifts, ck = cloud_lod
+            for i, info in enumerate(self.infos):
+                if not info.nface and info.nvert:
+                    nch = (info.nvert + ck - 1) // ck
+                    cplan.append((i, info.nvert, nch, [(int(s), take(info.nvert * 4), take(info.nvert * 4), take(info.nvert * 4), take(nch * 32), take(16)) for s in cshifts]))
         total = max(off, 256)
         buf = torch.empty(total, dtype=torch.uint8, device=dev) if fill is None else torch.full((total,), fill, dtype=torch.uint8, device=dev)
         _torch_ready(dev)                            # (the fill runs on torch's stream; the decode on the context's own)
@@ -1482,6 +1550,14 @@ class Batch:
         index_ptrs = (C.c_void_p * max(len(self), 1))()
         index_fmt = np.full(max(len(self), 1), FMT_UINT32, dtype=np.uint32)
         outs = [dict() for _ in self.infos]
+        self._cloud_lod = {}
+        for (i, nv, nch, levels) in cplan:
+            cb = CloudLodBinding()
+            cb.levels, cb.chunk_points = len(levels), ck
+            for k, (s, ro, po, wo, ho, co) in enumerate(levels[:CLOUD_LOD_MAX_LEVELS]):
+                cb.level[k] = CloudLodLevel(base + ro, base + po, base + wo, base + ho, base + co, nv, nch, s, 0)
+            self._cloud_lod[i] = (cb, [(buf[ro:ro + nv * 4], buf[po:po + nv * 4], buf[wo:wo + nv * 4], buf[ho:ho + nch * 32], buf[co:co + 16])
+                                       for (s, ro, po, wo, ho, co) in levels])
         self._meshlets, self._meshlet_bounds = {}, {}
         for (i, bd, mo, vo, to, co, bo) in mplan:
             if bo is not None:
@@ -1577,6 +1653,7 @@ class Batch:
         self._adjacency = {}
         self._weld = {}
         self._lod = {}
+        self._cloud_lod = {}
         self._interleaved = metas
         self.outputs = [dict() for _ in self.infos]
         self.rebind()
@@ -1632,6 +1709,8 @@ class Batch:
             _check(lib().crthip_batch_bind_weld(self.handle, i, C.byref(wb)))
         for i, (lb, _) in self._lod.items():                    # (... and its levels of detail)
             _check(lib().crthip_batch_bind_lod(self.handle, i, C.byref(lb)))
+        for i, (cb, _) in self._cloud_lod.items():              # (... and a cloud's levels of detail)
+            _check(lib().crthip_batch_bind_cloud_lod(self.handle, i, C.byref(cb)))
 
     def bind(self, i: int, bindings: Sequence[AttrBinding], index_ptr: Optional[int] = None, index_format=FMT_UINT32):
         arr = (AttrBinding * max(len(bindings), 1))(*bindings)
@@ -1743,6 +1822,32 @@ class Batch:
             counts = None if len(lv) < 3 or lv[2] is None else tuple(int(x) for x in words(lv[2], 4))
             index = words(lv[1], self.infos[i].nface * 3)
             out.append((remap, index if counts is None else index[:3 * counts[1]], counts))
+        return out
+
+    def bind_cloud_lod(self, i: int, binding: Optional[CloudLodBinding] = None, keep=None):
+        """crthip_batch_bind_cloud_lod: cloud i's levels of detail go to the binding's device arrays (a level: remap and points at least nvert
+        words, optionally weight, chunk records and a counts record).  After bind() / rebind() of that blob, which drop it; None removes it.
+        keep: whatever owns the memory (device tensors), held with the binding - a list of (remap, points, weight or None, chunks or None,
+        counts or None) a level makes cloud_lod(i) work."""
+        if binding is None:
+            self._cloud_lod.pop(i, None)
+            _check(lib().crthip_batch_bind_cloud_lod(self.handle, i, None))
+            return
+        _check(lib().crthip_batch_bind_cloud_lod(self.handle, i, C.byref(binding)))
+        self._cloud_lod[i] = (binding, keep)
+
+    def cloud_lod(self, i: int):
+        """Cloud i's levels of detail on the host: a list, a level, of (remap uint32 (nvert,), points uint32 cut to its `cells` words, weight
+        likewise or None, chunks CLOUD_CHUNK_DTYPE cut to its `chunks` records or None, the counts as a tuple (points, cells, chunks, 0)).
+        After sync(); for bindings with a device counts record a level, made by allocate_outputs(cloud_lod=) or bind_cloud_lod(keep=)."""
+        _, keep = self._cloud_lod[i]
+        raw = lambda t, n: t.cpu().numpy().view(np.uint8).reshape(-1)[:n].copy()   # noqa: E731
+        out = []
+        for (remap, points, weight, chunks, counts) in keep:
+            rec = tuple(int(x) for x in raw(counts, 16).view(np.uint32))
+            out.append((raw(remap, self.infos[i].nvert * 4).view(np.uint32), raw(points, rec[1] * 4).view(np.uint32),
+                        None if weight is None else raw(weight, rec[1] * 4).view(np.uint32),
+                        None if chunks is None else raw(chunks, rec[2] * 32).view(CLOUD_CHUNK_DTYPE), rec))
         return out
 
     def meshlet_counts(self, i: int) -> MeshletCounts:

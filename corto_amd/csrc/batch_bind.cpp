@@ -1,5 +1,5 @@
-// batch_bind.cpp — what a caller binds to a batch's blobs and what reads a decode's records back: crthip_batch_bind / _bind_all, the seven derived
-// outputs (computed normals, computed tangents, meshlets, meshlet bounds, adjacency, weld, levels of detail: DerivedBindings, batch_internal.h), the quantised attributes' records and the
+// batch_bind.cpp — what a caller binds to a batch's blobs and what reads a decode's records back: crthip_batch_bind / _bind_all, the eight derived
+// outputs (computed normals, computed tangents, meshlets, meshlet bounds, adjacency, weld, levels of detail of meshes and of clouds: DerivedBindings, batch_internal.h), the quantised attributes' records and the
 // meshlet counts.  Every check of a binding is made here, in the order corto_hip.h lists its errors, so that a decode has nothing new to fail on.
 // No HIP call: a program without the runtime links these (tests/cpp/plan_dump.cpp).
 #include "batch_internal.h"
@@ -206,6 +206,24 @@ extern "C" int crthip_batch_bind_lod(crthip_batch *b, uint32_t i, const crthip_l
 	if(!generic_source_ok(P, attr_named(P, "position"), 3))
 		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "levels of detail need a bound three-component \"position\" (bind the blob first)" + who);
 	P.derived.lod = *l;
+	b->dirty = true;
+	return CRTHIP_OK;
+}
+
+// Levels of detail of a point cloud (corto_hip.h has the contract): every check is made here, in the header's order.  It reads what the bind
+// binds, like every derived binding; no other derived binding drops it and it drops none
+extern "C" int crthip_batch_bind_cloud_lod(crthip_batch *b, uint32_t i, const crthip_cloud_lod_binding *l) {
+	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_cloud_lod: no such blob");
+	BlobPlan &P = b->blobs[i];
+	const std::string who = " (blob " + std::to_string(i) + ")";
+	if(!l) { P.derived.cloud_lod = crthip_cloud_lod_binding{}; b->dirty = true; return CRTHIP_OK; }
+	if(P.L.h.nface > 0) return fail(CRTHIP_E_ARGUMENT, "a cloud's levels of detail: the blob has faces, it is not a point cloud" + who);
+	if(P.L.h.nvert == 0) return fail(CRTHIP_E_ARGUMENT, "a cloud's levels of detail: the cloud has no points" + who);
+	if(const char *why = cloud_lod_binding_error(l, P.L.h.nvert)) return fail(CRTHIP_E_ARGUMENT, why + who);
+	// (what the weld asks of the position)
+	if(!generic_source_ok(P, attr_named(P, "position"), 3))
+		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "a cloud's levels of detail need a bound three-component \"position\" (bind the blob first)" + who);
+	P.derived.cloud_lod = *l;
 	b->dirty = true;
 	return CRTHIP_OK;
 }

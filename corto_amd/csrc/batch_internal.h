@@ -31,6 +31,7 @@
 #include "adjacency.h"
 #include "weld.h"
 #include "lod.h"
+#include "cloud_lod.h"
 
 using namespace corto_hip;
 
@@ -102,10 +103,11 @@ struct BlobScratch {
 	uint64_t adj = ~0ull;                                   // adjacency (DerivedBindings::adjacency) of a blob beyond adj_in_blob: adj_scratch_layout's block
 	uint64_t weld = ~0ull;                                  // weld (DerivedBindings::weld) of a blob beyond weld_in_blob: weld_scratch_layout's block
 	uint64_t lod[CRTHIP_LOD_MAX_LEVELS] = {~0ull, ~0ull, ~0ull, ~0ull};   // levels of detail (DerivedBindings::lod): a level's lod_scratch_layout block
+	uint64_t cloud_lod[CRTHIP_CLOUD_LOD_MAX_LEVELS] = {~0ull, ~0ull, ~0ull, ~0ull};   // a cloud's levels of detail (DerivedBindings::cloud_lod) beyond weld_in_blob: a level's cloud_lod_scratch_layout block
 	uint64_t cn_facen = ~0ull;                              // computed normals (DerivedBindings::normals) by the fused kernel without its face normals in LDS: AttrScratch::facen's counterpart
 	std::vector<AttrScratch> attr;
 	size_t nattr = 0;                                       // attr[0..nattr) are this decode's (the vector only grows)
-	void reset() { clers = pred = front_a = front_b = order = delayed = faces = progress = cn_facen = tan_acc = mlt = mlt_counts = adj = weld = ~0ull; for(uint64_t &l : lod) l = ~0ull; front_cap = 0; aux_groups = 0; nattr = 0; }
+	void reset() { clers = pred = front_a = front_b = order = delayed = faces = progress = cn_facen = tan_acc = mlt = mlt_counts = adj = weld = ~0ull; for(uint64_t &l : lod) l = ~0ull; for(uint64_t &l : cloud_lod) l = ~0ull; front_cap = 0; aux_groups = 0; nattr = 0; }
 	void set_attrs(size_t n) { if(attr.size() < n) attr.resize(n); for(size_t k = nattr; k < n; k++) attr[k].reset();
 		if(n > nattr) nattr = n; }
 };
@@ -148,6 +150,10 @@ struct Plan {
 	// crthip_batch_bind_lod: a job a bound level.  Jobs whose tables fit LDS by id (k_lod_blob, lod_lds the largest request among them), the others
 	// by id for the scan (k_lod_offsets), 256 vertices a block (k_lod_insert, _lookup) and 256 faces a block (k_lod_faces, _keep, _scatter)
 	HostArr<LodJob> lod; HostArr<uint32_t> lod_blob_ids, lod_big_ids, lod_vblock_job, lod_fblock_job; uint32_t lod_lds = 0;
+	// crthip_batch_bind_cloud_lod: a job a bound level of a cloud.  Jobs whose table fits LDS by id (k_cloud_lod_blob, cloud_lod_lds the largest request
+	// among them), the others by id for the scan (k_cloud_lod_offsets), 256 vertices a block (k_cloud_lod_insert, _lookup, _scatter) and, those with
+	// a chunks array, a block a chunk of the capacity (k_cloud_lod_chunks)
+	HostArr<CloudLodJob> cloud_lod; HostArr<uint32_t> cloud_lod_blob_ids, cloud_lod_big_ids, cloud_lod_vblock_job, cloud_lod_cblock_job; uint32_t cloud_lod_lds = 0;
 	bool meshlet_records = false;                           // a crthip_meshlet_counts a blob behind the quant records: a batch with a meshlet binding
 	uint32_t quant_records = 0;                             // records behind the status words: sum(nattr) of a batch with a quantised binding, else 0
 	// scratch regions (offsets)
@@ -176,12 +182,15 @@ struct Plan {
 	// ... and, by the same rule, the arrays of the levels of detail.  They are a list of their own because tests/cpp/plan_dump.cpp names
 	// each_optional_array's eight one by one
 	template <class F> void each_lod_array(F f) { f(lod); f(lod_blob_ids); f(lod_big_ids); f(lod_vblock_job); f(lod_fblock_job); }
+	// ... and of the clouds' levels of detail, behind them
+	template <class F> void each_cloud_lod_array(F f) { f(cloud_lod); f(cloud_lod_blob_ids); f(cloud_lod_big_ids); f(cloud_lod_vblock_job); f(cloud_lod_cblock_job); }
 	void reset() {                                          // keep every vector's capacity
 		each_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
 		each_optional_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
 		each_lod_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
+		each_cloud_lod_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
 		clers_groups = 0; topo_need.clear(); quant_records = 0; meshlet_waves = 0; meshlet_records = false;
-		topo_lds = topo_big_lds = normal_fused_lds = normal_computed_lds = tangent_lds = adjacency_lds = weld_lds = lod_lds = 0;
+		topo_lds = topo_big_lds = normal_fused_lds = normal_computed_lds = tangent_lds = adjacency_lds = weld_lds = lod_lds = cloud_lod_lds = 0;
 		zero_begin = zero_end = tables_off = tun_partial_off = unpack_partial_off = cloud_partial_off = 0;
 		facen_off = cnt_off = cursor_off = bnd_off = start_off = flag_off = slot_off = adj_off = nscan_partial_off = 0;
 		jobs_begin = jobs_bytes = 0; est_nvert = est_nface = 0; delta16_lds = 0;
@@ -267,6 +276,7 @@ struct DerivedBindings {
 	crthip_adjacency_binding adjacency{};  // crthip_batch_bind_adjacency: adjacency.twin != null - where the blob's twins go (reads the index alone)
 	crthip_weld_binding weld{};            // crthip_batch_bind_weld: weld.remap != null - where the blob's weld map goes (reads the integer positions and the index)
 	crthip_lod_binding lod{};              // crthip_batch_bind_lod: lod.levels != 0 - where the blob's levels of detail go (reads the integer positions and the index)
+	crthip_cloud_lod_binding cloud_lod{};  // crthip_batch_bind_cloud_lod: cloud_lod.levels != 0 - where a cloud's levels of detail go (reads the integer positions)
 	void clear() { *this = DerivedBindings{}; }       // a bind (and a blob adopted by a fill): all of them read what it binds
 	void normals_change() { tangents = Binding{}; }   // a normals call: the tangents' normal source may change
 	void meshlets_change() { bounds = nullptr; }      // a meshlets call: the bounds' arrays and capacity change
@@ -382,6 +392,10 @@ static inline bool welds_adjacency(const BlobPlan &P) { return binds_weld(P) && 
 // levels of detail (crthip_batch_bind_lod): a job a level; one whose tables fit LOD_BLOB_LDS_MAX takes k_lod_blob, the others the six kernels over
 // scratch (lod.h: lod_in_blob)
 static inline bool binds_lod(const BlobPlan &P) { return P.derived.lod.levels && P.L.h.nface > 0; }
+
+// a cloud's levels of detail (crthip_batch_bind_cloud_lod): a job a level; one whose table fits WELD_BLOB_LDS_MAX takes k_cloud_lod_blob, the
+// others the five kernels over scratch (cloud_lod.h; weld.h: weld_in_blob)
+static inline bool binds_cloud_lod(const BlobPlan &P) { return P.derived.cloud_lod.levels && P.L.h.nface == 0 && P.L.h.nvert > 0; }
 
 // where the derived outputs and the estimated normals take their inputs.  An attribute by name: the last one of that name, or -1
 static inline int attr_named(const BlobPlan &P, const char *name) {
@@ -502,6 +516,6 @@ struct Planner {
 	bool inverse_job(const BlobView &v, size_t k, void *values, uint32_t N, bool para, uint8_t is_u8, bool hand_i16);
 	void stored_normal_job(const BlobView &v, size_t k, bool hand_i16); void quant_job(const BlobView &v, size_t k); void dequant_job(const BlobView &v, size_t k);
 	bool estimated_normal_tail(const BlobView &v, NormalJob &n, HostArr<uint32_t> &fused_ids, uint32_t &fused_lds, uint64_t facen);
-	bool computed_normal_job(const BlobView &v); bool tangent_job(const BlobView &v); void meshlet_jobs(const BlobView &v); void weld_jobs(const BlobView &v); void adjacency_jobs(const BlobView &v); void lod_jobs(const BlobView &v);
+	bool computed_normal_job(const BlobView &v); bool tangent_job(const BlobView &v); void meshlet_jobs(const BlobView &v); void weld_jobs(const BlobView &v); void adjacency_jobs(const BlobView &v); void lod_jobs(const BlobView &v); void cloud_lod_jobs(const BlobView &v);
 };
 

@@ -269,6 +269,25 @@ struct LodJob {
 	uint8_t index_u16, pad[3];
 };
 
+// one LEVEL of a cloud bound with crthip_batch_bind_cloud_lod (k_cloud_lod.hip, cloud_lod.h): the integer positions -> the level's remap, its kept
+// points, their weights, a box a chunk of them and its record.  A job within weld_in_blob needs nothing else; the others keep their table, their
+// weight words and their block counts in scratch
+struct CloudLodJob {
+	const int32_t *position;       // nvert x 3 int32 as k_cloud_apply leaves them: the caller's packed buffer, or scratch
+	uint32_t *remap;               // the level's nvert words
+	uint32_t *points;              // the level's kept points: `cells` words are written
+	uint32_t *weight;              // ... and their weights; null: none wanted
+	void *chunks;                  // crthip_cloud_chunk records; null: none wanted
+	void *counts;                  // crthip_cloud_lod_counts in DEVICE memory: the level's, or (bigger jobs only) scratch; null: none wanted
+	uint32_t *table, *wacc;        // bigger jobs: weld_slots(nvert) words and nvert weight words, one range zeroed by one FillJob
+	uint32_t *blocks;              // bigger jobs: a word a block of LOD_BLOCK vertices - its kept count, then its base
+	uint32_t nvert, shift;
+	uint32_t chunk_points;         // K (read only with chunks)
+	uint32_t vblock0, cblock0;     // first block of this job in the two block -> job maps (cloud_lod_insert, _lookup and _scatter; cloud_lod_chunks)
+	uint32_t pad;
+};
+static_assert(sizeof(CloudLodJob) == 96, "decode job layout");
+
 // the layout the kernels read, pinned (TopoJob's size is performance-critical: TOPO_OPT_PROGRESS above)
 static_assert(sizeof(TunStream) == 64 && sizeof(FillJob) == 16 && sizeof(TopoJob) == 136 && sizeof(UnpackJob) == 56 && sizeof(DeltaJob) == 96 &&
               sizeof(CloudJob) == 24 && sizeof(NormalJob) == 104 && sizeof(DequantJob) == 64 && sizeof(QuantOutJob) == 72 && sizeof(TangentJob) == 80 &&

@@ -1,7 +1,7 @@
 // k_lod.hip — K-LOD: clustered levels of detail of the index for gfx950 (crthip_batch_bind_lod).  lod.h has the method, the phases and both
-// partitions; here are the workgroup (DPP scan, readlane, the barrier, the carry over the four waves) and the seven grids.  A job is one LEVEL of
-// one blob, so no kernel loops over levels.  Launched in stage M behind the adjacency kernels and in front of k_dequant: the integer positions
-// have been final since K-DELTA, the index since the automata.
+// partitions; here are the seven grids, over the workgroup of lod_group.h (DPP scan, readlane, the barrier, the carry over the four waves:
+// k_cloud_lod.hip's too).  A job is one LEVEL of one blob, so no kernel loops over levels.  Launched in stage M behind the adjacency kernels and
+// in front of k_dequant: the integer positions have been final since K-DELTA, the index since the automata.
 //
 //   k_lod_blob      one workgroup a job whose tables fit LOD_BLOB_LDS_MAX (nvert <= 8 192 and nface <= 8 192), from an id list:
 //                   max(weld_slots(nvert), weld_slots(nface)) words of dynamic LDS, used twice; zero, insert the vertices by cell, barrier, lookup
@@ -23,36 +23,11 @@
 #include "kernels_common.h"
 #include "kernels.h"
 #include "lod.h"
+#include "lod_group.h"                                                       // (LodGroupDev: the workgroup as lod.h sees it)
 
 namespace corto_hip {
 
 namespace {
-
-// the workgroup as lod.h sees it: one thread's state, and four words of LDS for what the waves tell one another
-struct LodGroupDev {
-	LodLane L;
-	WELD_LDS uint32_t *part;                                                 // a wave's sum (block_sum, block_scan)
-	template <class F> __device__ __forceinline__ void each(F f) { f(threadIdx.x, L); }
-	__device__ __forceinline__ void sync() { __syncthreads(); }
-	__device__ __forceinline__ void block_sum() {
-		const uint32_t s = (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan_u32(L.c), 63);
-		__syncthreads();                                                     // (the sums before these have been read)
-		if(lane_id() == 0) part[wave_id()] = s;
-		__syncthreads();
-		if(threadIdx.x == 0) L.c = part[0] + part[1] + part[2] + part[3];
-	}
-	__device__ __forceinline__ void block_scan() {
-		const uint32_t incl = wave_inclusive_scan_u32(L.c);
-		const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-		__syncthreads();                                                     // (the sums before these have been read)
-		if(lane_id() == 0) part[wave_id()] = tot;
-		__syncthreads();
-		const uint32_t p0 = part[0], p1 = part[1], p2 = part[2], p3 = part[3], w = wave_id();
-		L.x = incl - L.c + (w > 0 ? p0 : 0u) + (w > 1 ? p1 : 0u) + (w > 2 ? p2 : 0u);
-		L.t = p0 + p1 + p2 + p3;
-	}
-	template <class F> __device__ __forceinline__ void thread0(F f) { if(threadIdx.x == 0) f(L); }
-};
 
 __device__ __forceinline__ LodIn in_of(const LodJob &j) {
 	LodIn J; J.w.position = (WELD_MEM const int32_t *)j.position; J.w.index = (WELD_MEM const void *)j.index; J.w.index_u16 = j.index_u16;

@@ -98,6 +98,17 @@ __global__ void k_lod_keep(const LodJob *jobs, const uint32_t *block_job, uint32
 __global__ void k_lod_offsets(const LodJob *jobs, const uint32_t *job_ids, uint32_t njobs);
 __global__ void k_lod_scatter(const LodJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 
+// k_cloud_lod.hip (crthip_batch_bind_cloud_lod; cloud_lod.h has the method and both partitions): a job is one level of one cloud.  Jobs whose
+// table fits WELD_BLOB_LDS_MAX by one workgroup each from an id list, with weld_slots(nvert)*4 bytes of dynamic LDS (the launch asks for the
+// largest among them); bigger ones 256 vertices a block from a block -> job map (insert, lookup, scatter), one workgroup a job from an id list
+// (offsets) and a workgroup a chunk of the capacity from a second map (chunks: jobs with a chunks array only)
+__global__ void k_cloud_lod_blob(const CloudLodJob *jobs, const uint32_t *job_ids, uint32_t njobs);
+__global__ void k_cloud_lod_insert(const CloudLodJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_cloud_lod_lookup(const CloudLodJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_cloud_lod_offsets(const CloudLodJob *jobs, const uint32_t *job_ids, uint32_t njobs);
+__global__ void k_cloud_lod_scatter(const CloudLodJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_cloud_lod_chunks(const CloudLodJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+
 // k_mesh.hip
 __global__ void k_topology(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);
 __global__ void k_topology_lds(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);

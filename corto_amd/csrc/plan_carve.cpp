@@ -127,6 +127,11 @@ int Planner::carve() {
 		const BlobPlan &P = b->blobs[i];
 		if(binds_lod(P)) for(uint32_t k = 0; k < P.derived.lod.levels && k < CRTHIP_LOD_MAX_LEVELS; k++) bs[i].lod[k] = cv.take(lod_scratch_layout(P.L.h.nvert, P.L.h.nface).total, 16);
 	}
+	for(uint32_t i = 0; i < nblobs; i++) {                           // a cloud's levels of detail beyond LDS: a level's table and weight words (zeroed by a FillJob), block counts and record
+		const BlobPlan &P = b->blobs[i];
+		if(binds_cloud_lod(P) && !weld_in_blob(P.L.h.nvert))
+			for(uint32_t k = 0; k < P.derived.cloud_lod.levels && k < CRTHIP_CLOUD_LOD_MAX_LEVELS; k++) bs[i].cloud_lod[k] = cv.take(cloud_lod_scratch_layout(P.L.h.nvert).total, 16);
+	}
 	if(est_v) {
 		pl.start_off = cv.take(est_v*4 + 16); pl.flag_off = cv.take(est_v*4 + 16); pl.slot_off = cv.take(est_v*4 + 16);
 		pl.adj_off = cv.take(est_f*12 + 16); pl.facen_off = cv.take(est_f*12 + 16);

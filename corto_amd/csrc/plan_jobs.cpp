@@ -131,6 +131,7 @@ int Planner::jobs() {
 		if(binds_weld(v.P) && !v.P.host_status) weld_jobs(v);
 		if(binds_adjacency(v.P) && !v.P.host_status) adjacency_jobs(v);
 		if(binds_lod(v.P) && !v.P.host_status) lod_jobs(v);
+		if(binds_cloud_lod(v.P) && !v.P.host_status) cloud_lod_jobs(v);
 	}
 	return CRTHIP_OK;
 }
@@ -529,6 +530,45 @@ void Planner::lod_jobs(const BlobView &v) {
 			for(uint32_t c = 0; c < lod_fblocks(v.nface); c++) pl.lod_fblock_job.v.push_back(id);
 		}
 		pl.lod.v.push_back(l);
+	}
+}
+
+// a cloud's levels of detail: crthip_batch_bind_cloud_lod.  A job a LEVEL: the integer positions as the weld takes them and the level's arrays; a job
+// whose table fits LDS needs no more.  The others keep the table and the weight words - one range, zeroed by ONE FillJob in stage E, so that a
+// second decode starts clean -, a word a block of vertices and, if the level has none, a record in scratch.  A cloud's inverse_job never turns
+// integers into floats on its way (that is dequant_job's or quant_job's, in finish()), so view_of has no reader to count: a packed buffer holds
+// the integers until k_dequant, a strided, DOUBLE or quantised one keeps them in scratch.  (The bind call checked all of it)
+void Planner::cloud_lod_jobs(const BlobView &v) {
+	const crthip_cloud_lod_binding &lb = v.P.derived.cloud_lod;
+	const bool blob = weld_in_blob(v.nvert);
+	if(!generic_source_ok(v.P, v.pos_k, 3)) { v.P.host_status = CRTHIP_E_NORMAL_NEEDS_POSITION; return; }
+	if(v.mesh || !v.nvert || cloud_lod_binding_error(&lb, v.nvert)) { v.P.host_status = CRTHIP_E_ARGUMENT; return; }
+	for(uint32_t k = 0; k < lb.levels; k++) if(!blob && v.S.cloud_lod[k] == ~0ull) { v.P.host_status = CRTHIP_E_ARGUMENT; return; }
+	const CloudLodScratchLayout lay = cloud_lod_scratch_layout(v.nvert);
+	for(uint32_t k = 0; k < lb.levels; k++) {
+		const crthip_cloud_lod_level &lv = lb.level[k];
+		CloudLodJob c{};
+		c.position = ints_of(v.i, v.pos_k);
+		c.remap = lv.remap; c.points = lv.points; c.weight = lv.weight; c.chunks = lv.chunks; c.counts = lv.counts;
+		c.nvert = v.nvert; c.shift = lv.shift; c.chunk_points = lb.chunk_points;
+		const uint32_t id = (uint32_t)pl.cloud_lod.v.size();
+		if(blob) {
+			pl.cloud_lod_blob_ids.v.push_back(id);
+			pl.cloud_lod_lds = std::max(pl.cloud_lod_lds, (uint32_t)(weld_slots(v.nvert)*4));
+		} else {
+			const uint64_t S = v.S.cloud_lod[k];
+			c.table = (uint32_t *)SP(S + lay.table); c.wacc = (uint32_t *)SP(S + lay.weights); c.blocks = (uint32_t *)SP(S + lay.blocks);
+			if(!lv.counts) c.counts = SP(S + lay.record);
+			zero_fill(S + lay.table, lv.weight ? lay.zero_bytes : lay.weights);   // (no weights: the table alone)
+			pl.cloud_lod_big_ids.v.push_back(id);
+			c.vblock0 = (uint32_t)pl.cloud_lod_vblock_job.v.size();
+			push_blocks(pl.cloud_lod_vblock_job, id, weld_vblocks(v.nvert));
+			if(lv.chunks) {
+				c.cblock0 = (uint32_t)pl.cloud_lod_cblock_job.v.size();
+				push_blocks(pl.cloud_lod_cblock_job, id, cloud_lod_chunks_of(v.nvert, lb.chunk_points));
+			}
+		}
+		pl.cloud_lod.v.push_back(c);
 	}
 }
 

@@ -247,6 +247,13 @@ void Planner::derived() {
 	by_ids("lod_keep", k_lod_keep, LOD_THREADS, 0, pl.lod, pl.lod_fblock_job);
 	by_ids("lod_offsets", k_lod_offsets, LOD_THREADS, 0, pl.lod, pl.lod_big_ids);
 	by_ids("lod_scatter", k_lod_scatter, LOD_THREADS, 0, pl.lod, pl.lod_fblock_job);
+	// a cloud's levels of detail: a job a level; the integer positions, final since cloud() (k_dequant runs behind)
+	by_ids("cloud_lod_blob", k_cloud_lod_blob, LOD_THREADS, pl.cloud_lod_lds, pl.cloud_lod, pl.cloud_lod_blob_ids);
+	by_ids("cloud_lod_insert", k_cloud_lod_insert, LOD_THREADS, 0, pl.cloud_lod, pl.cloud_lod_vblock_job);
+	by_ids("cloud_lod_lookup", k_cloud_lod_lookup, LOD_THREADS, 0, pl.cloud_lod, pl.cloud_lod_vblock_job);
+	by_ids("cloud_lod_offsets", k_cloud_lod_offsets, LOD_THREADS, 0, pl.cloud_lod, pl.cloud_lod_big_ids);
+	by_ids("cloud_lod_scatter", k_cloud_lod_scatter, LOD_THREADS, 0, pl.cloud_lod, pl.cloud_lod_vblock_job);
+	by_ids("cloud_lod_chunks", k_cloud_lod_chunks, LOD_THREADS, 0, pl.cloud_lod, pl.cloud_lod_cblock_job);
 }
 // the scratch path's finishers: k_dequant, and where it would sit the kernels of CRTHIP_BIND_QUANTIZED
 void Planner::finish() {

@@ -60,7 +60,9 @@ extern "C" {
                                      crthip_weld_binding, crthip_batch_bind_weld, crthip_weld_model (two structs and two new calls,
                                      nothing else: the number stays 6); CRTHIP_LOD_MAX_LEVELS, crthip_lod_counts, crthip_lod_level,
                                      crthip_lod_binding, crthip_batch_bind_lod, crthip_lod_model (three structs and two new calls,
-                                     nothing else: the number stays 6) */
+                                     nothing else: the number stays 6); CRTHIP_CLOUD_LOD_MAX_LEVELS, crthip_cloud_lod_counts,
+                                     crthip_cloud_chunk, crthip_cloud_lod_level, crthip_cloud_lod_binding, crthip_batch_bind_cloud_lod,
+                                     crthip_cloud_lod_model (four structs and two new calls, nothing else: the number stays 6) */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -553,6 +555,59 @@ typedef struct crthip_lod_binding {
  * weld's rule.  crthip_last_error() names the blob.  Blobs without the binding launch nothing new.
  * Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host, the crt::Decoder facade or the veneers. */
 int crthip_batch_bind_lod(crthip_batch *b, uint32_t i, const crthip_lod_binding *l);
+
+/* Levels of detail of a POINT CLOUD: up to CRTHIP_CLOUD_LOD_MAX_LEVELS coarser point lists into the blob's unchanged vertex buffers, each a
+ * subset of the points chosen on the integer grid, with a weight a kept point and a bounding box a run of kept points for GPU-driven culling,
+ * built on the GPU in the decode call (kernels cloud_lod_blob, and cloud_lod_insert, cloud_lod_lookup, cloud_lod_offsets, cloud_lod_scatter,
+ * cloud_lod_chunks in crthip_kernel_times; csrc/cloud_lod.h has the source the kernels and the test hook share).  Integer work only; the
+ * bytes are defined exactly, for any order of the points.  p[v] is the delta-decoded INTEGER position of vertex v, as the weld reads it.
+ * A binding has 1 to CRTHIP_CLOUD_LOD_MAX_LEVELS levels, each with a `shift` in 0..31, strictly increasing, and one chunk size K =
+ * chunk_points for all of them.  For one level of shift s:
+ * cell(v) is crthip_batch_bind_lod's: the arithmetic p[v] >> s a component.  -1 and 0 are never in one cell; -1 and -2^s are.
+ * remap[v] (nvert words) = the LEAST vertex in v's cell: to the byte what crthip_lod_model gives as remap for the same positions, and with
+ *   shift 0 the weld's remap.
+ * points[j], j < cells: the vertices with remap[v] == v in increasing v.  Exactly `cells` words are written.
+ * weight[j] (optional) = the number of v with remap[v] == points[j].  Exactly `cells` words are written; their sum is nvert.
+ * chunks[c] (optional), c < ceil(cells / K): first = c*K; count = min(K, cells - first); min and max = the signed minimum and maximum a
+ *   component of p[points[j]] over first <= j < first + count.  Exactly that many records are written.  A box over EVERY original point of
+ *   those cells follows from it without another pass: (min >> s) << s and ((max >> s) << s) + 2^s - 1, a component.
+ * counts (optional) = {points: nvert, cells, chunks: ceil(cells / K) if the level has a `chunks` array, else 0, reserved: 0}.  The record is
+ *   device-only, for indirect draws; as with the weld there is no host record.
+ * Nothing beyond the words named is written.  The position's own output and every other output are unchanged, whatever the position's
+ * format (FLOAT packed or strided, an integer format, CRTHIP_BIND_QUANTIZED).
+ * Across the levels k, k + 1 of one binding: remap_{k+1}[v] == remap_{k+1}[remap_k[v]], and the set points_{k+1} is a subset of points_k. */
+#define CRTHIP_CLOUD_LOD_MAX_LEVELS 4
+typedef struct crthip_cloud_lod_counts { uint32_t points, cells, chunks, reserved; } crthip_cloud_lod_counts;
+typedef struct crthip_cloud_chunk { int32_t min[3]; uint32_t first; int32_t max[3]; uint32_t count; } crthip_cloud_chunk;
+typedef struct crthip_cloud_lod_level {
+	uint32_t *remap;                   /* DEVICE, 4-byte aligned, room for `capacity` words */
+	uint32_t *points;                  /* DEVICE, 4-byte aligned, room for `capacity` words */
+	uint32_t *weight;                  /* optional DEVICE array, 4-byte aligned, room for `capacity` words; or NULL */
+	crthip_cloud_chunk *chunks;        /* optional DEVICE array, 16-byte aligned, room for `chunks_capacity` records; or NULL */
+	crthip_cloud_lod_counts *counts;   /* optional DEVICE record: 16 bytes, 16-byte aligned; or NULL.  There is no host record */
+	uint32_t capacity;                 /* words of remap, points and weight: at least nvert */
+	uint32_t chunks_capacity;          /* records of chunks: at least ceil(nvert / chunk_points) when chunks is given */
+	uint32_t shift;                    /* 0..31, above the level's before */
+	uint32_t reserved;                 /* 0 */
+} crthip_cloud_lod_level;
+typedef struct crthip_cloud_lod_binding {
+	crthip_cloud_lod_level level[CRTHIP_CLOUD_LOD_MAX_LEVELS];
+	uint32_t levels;                   /* 1..CRTHIP_CLOUD_LOD_MAX_LEVELS: level[0..levels) are read */
+	uint32_t chunk_points;             /* K: 32..65536, any integer; read only if some level has chunks, else it must be 0 or in that range */
+	uint32_t flags;                    /* 0 */
+	uint32_t reserved;                 /* 0 */
+} crthip_cloud_lod_binding;
+/* Blob i's levels go to l's buffers in the decode.  Call it after crthip_batch_bind of blob i; l == NULL removes the binding; a later
+ * crthip_batch_bind of that blob drops it, as does crthip_batch_reset*.  Independent of every other derived binding.  Every error is returned
+ * here, in this order, and nothing new can fail at decode time.
+ * CRTHIP_E_ARGUMENT: b NULL or i out of range; a mesh (nface > 0: not a point cloud); nvert == 0; levels not in
+ * 1..CRTHIP_CLOUD_LOD_MAX_LEVELS; chunk_points neither 0 nor in 32..65536, or 0 while some level has chunks; then per level, in level order:
+ * remap or points NULL or not 4-byte aligned; weight not 4-byte aligned; chunks or counts not 16-byte aligned; capacity < nvert; chunks given
+ * and chunks_capacity < ceil(nvert / chunk_points); shift > 31; shift not above the level's before; reserved != 0; then unknown flags or a
+ * reserved word not 0.  CRTHIP_E_NORMAL_NEEDS_POSITION: by the weld's rule.  crthip_last_error() names the blob.  Blobs without the binding
+ * launch nothing new; crthip_batch_bind_lod and the other derived bindings keep refusing a point cloud.
+ * Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host, the crt::Decoder facade or the veneers. */
+int crthip_batch_bind_cloud_lod(crthip_batch *b, uint32_t i, const crthip_cloud_lod_binding *l);
 
 /* The record of attribute `attr` of blob i, bound with CRTHIP_BIND_QUANTIZED.  Valid after crthip_batch_sync of a decode: the kernels write
  * the records into the batch's pinned status block, beside the status words.  CRTHIP_E_ARGUMENT if that attribute was not bound
@@ -1249,6 +1304,18 @@ int crthip_weld_model(const int32_t *position, const void *index, uint32_t index
  * lod_scatter.  Workgroups and threads, and with them every atomic, are walked in an order shuffled by seed: the bytes do not depend on it. */
 int crthip_lod_model(const int32_t *position, const void *index, uint32_t index_u16, uint32_t nface, uint32_t nvert, uint32_t shift, uint32_t *remap,
                      uint32_t *lod_index, crthip_lod_counts *counts, uint64_t *stats, int which, uint32_t seed);
+
+/* (test hook, no device needed)  ONE level of crthip_batch_bind_cloud_lod on the host: csrc/cloud_lod.h, the kernels' source, in their
+ * partition.  position: nvert*3 int32, nvert >= 1; chunk_points: K, or 0 with chunks NULL; remap, points: host memory, nvert words, of points
+ * `cells` are written; weight: nvert words of which `cells` are written, or NULL; chunks: ceil(nvert / K) records of which ceil(cells / K) are
+ * written, or NULL; counts: the record, or NULL; stats: two words, the slots all insert walks visited and the longest walk's, or NULL.
+ * which 0: cloud_lod_blob, one workgroup with its table where the kernel has LDS (a job beyond its limit - more than 8 192 vertices - is
+ * CRTHIP_E_LIMIT here; the decode sends such a job down the other path); which 1: cloud_lod_insert, cloud_lod_lookup, cloud_lod_offsets,
+ * cloud_lod_scatter, cloud_lod_chunks.  Workgroups and threads, and with them every atomic, are walked in an order shuffled by seed: the bytes
+ * do not depend on it.  CRTHIP_E_ARGUMENT: an unknown partition, a NULL position, and whatever crthip_batch_bind_cloud_lod refuses of a binding
+ * of this one level at capacities of exactly nvert and ceil(nvert / K), in its order. */
+int crthip_cloud_lod_model(const int32_t *position, uint32_t nvert, uint32_t shift, uint32_t chunk_points, uint32_t *remap, uint32_t *points,
+                           uint32_t *weight, crthip_cloud_chunk *chunks, crthip_cloud_lod_counts *counts, uint64_t *stats, int which, uint32_t seed);
 
 #ifdef __cplusplus
 }
