@@ -164,6 +164,45 @@ class CloudLodBinding(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+COMPACT_MAX_SETS, COMPACT_MAX_GATHERS = 4, 8         # CRTHIP_COMPACT_MAX_SETS, CRTHIP_COMPACT_MAX_GATHERS
+NO_VERTEX = 0xFFFFFFFF                               # CRTHIP_NO_VERTEX
+COMPACT_INDEX, COMPACT_WELD, COMPACT_LOD, COMPACT_CLOUD_LOD = 0, 1, 2, 3   # a set's source
+COMPACT_COMPUTED_NORMALS, COMPACT_COMPUTED_TANGENTS = 0xFFFFFFFE, 0xFFFFFFFD   # a gather's source beside an attribute number
+
+
+class CompactCounts(C.Structure):
+    """crthip_compact_counts: a set's vertices (nvert), the used ones, the faces of its source and whether a capacity left anything out"""
+    _fields_ = [("vertices", C.c_uint32), ("used", C.c_uint32), ("faces", C.c_uint32), ("clipped", C.c_uint32)]
+
+    def as_tuple(self):
+        return (self.vertices, self.used, self.faces, self.clipped)
+
+
+class CompactGather(C.Structure):
+    """crthip_compact_gather: the device array, the source (an attribute number or COMPACT_COMPUTED_*), the stride (0: packed)"""
+    _fields_ = [("dst", C.c_void_p), ("source", C.c_uint32), ("dst_stride", C.c_uint32)]
+
+
+class CompactSet(C.Structure):
+    """crthip_compact_set: the optional device newid, order and index arrays and counts record, their capacities, the source with its level,
+    the gathers"""
+    _fields_ = [("newid", C.c_void_p), ("order", C.c_void_p), ("index", C.c_void_p), ("counts", C.c_void_p),
+                ("newid_capacity", C.c_uint32), ("vertex_capacity", C.c_uint32), ("index_capacity", C.c_uint32),
+                ("source", C.c_uint32), ("level", C.c_uint32), ("ngather", C.c_uint32), ("reserved", C.c_uint32 * 2),
+                ("gather", CompactGather * COMPACT_MAX_GATHERS)]
+
+
+class CompactBinding(C.Structure):
+    """crthip_compact_binding: up to four independent sets"""
+    _fields_ = [("set", CompactSet * COMPACT_MAX_SETS), ("sets", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class CompactModelGather(C.Structure):
+    """crthip_compact_model_gather: host source and destination, the element bytes, the two strides (0: packed)"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("E", C.c_uint32), ("src_stride", C.c_uint32), ("dst_stride", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class MeshletBinding(C.Structure):
     """crthip_meshlet_binding: three device arrays with their capacities, the optional device counts record, the builder's parameters"""
     _fields_ = [("meshlets", C.c_void_p), ("vertices", C.c_void_p), ("triangles", C.c_void_p), ("counts", C.c_void_p),
@@ -377,6 +416,9 @@ def lib():
                                         C.c_int, C.c_uint32]
         L.crthip_batch_bind_lod.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(LodBinding)]
         L.crthip_batch_bind_cloud_lod.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(CloudLodBinding)]
+        L.crthip_batch_bind_compact.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(CompactBinding)]
+        L.crthip_compact_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                           C.c_uint32, C.POINTER(CompactCounts), C.POINTER(CompactModelGather), C.c_uint32, C.c_int, C.c_uint32]
         L.crthip_cloud_lod_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.POINTER(CloudLodCounts), C.c_void_p, C.c_int, C.c_uint32]
         L.crthip_lod_model.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(LodCounts),
@@ -1185,6 +1227,37 @@ def cloud_lod_model(position: np.ndarray, shift: int, chunk_points: int = 0, whi
     return remap, points, weight, chunks, counts, (int(stats[0]), int(stats[1]))
 
 
+def compact_model(src: np.ndarray, nvert: int, faces: Optional[int] = None, which: int = 0, seed: int = 0, newid=True, order=True, index=True,
+                  vertex_capacity: Optional[int] = None, index_capacity: Optional[int] = None, gathers=(), fill: int = 0xCD):
+    """crthip_compact_model: one set of crthip_batch_bind_compact on the host in the kernels' partition (which 0: compact_blob; 1: compact_mark /
+    _count / _offsets / _place / _index; 2: a cloud set, src its level's points; then compact_gather; workgroups and threads shuffled by seed).
+    src: the id list, uint32 or uint16, 3*nface words (which 2: the points' capacity); faces: how many of its faces (which 2: points) the
+    source's record names, default all.  newid / order / index: whether the set has them; they are made here at exactly nvert,
+    vertex_capacity and index_capacity words (defaults nvert and len(src)) and filled with `fill` first.  gathers: (source bytes, E,
+    src_stride, dst bytes, dst_stride) with writable uint8 arrays (slices at any offset) - the destination is written in place.  Returns
+    (newid or None, order or None, index or None, CompactCounts)."""
+    src = np.ascontiguousarray(src)
+    if src.dtype not in (np.uint16, np.uint32):
+        src = src.astype(np.uint32)
+    src = src.reshape(-1)
+    nface = len(src) if which == 2 else len(src) // 3
+    faces = nface if faces is None else int(faces)
+    vcap = int(nvert) if vertex_capacity is None else int(vertex_capacity)
+    icap = len(src) if index_capacity is None else int(index_capacity)
+    mk = lambda n: np.full(max(n, 1), fill * 0x01010101, np.uint32)[:n]   # noqa: E731  (a capacity of 0 is still an array: the pointer is not NULL)
+    nid = mk(nvert) if newid and which != 2 else None
+    orde = mk(vcap) if order and which != 2 else None
+    idx = mk(icap) if index and which != 2 else None
+    gs = (CompactModelGather * max(len(gathers), 1))()
+    for q, (gsrc, E, sst, gdst, dst_) in enumerate(gathers):
+        gs[q] = CompactModelGather(gsrc.ctypes.data, gdst.ctypes.data, int(E), int(sst), int(dst_), 0)
+    counts = CompactCounts()
+    ptr = lambda a: a.ctypes.data if a is not None else None   # noqa: E731
+    _check(lib().crthip_compact_model(ptr(src) if len(src) else None, 1 if src.dtype == np.uint16 else 0, nface, faces, int(nvert), ptr(nid), ptr(orde), ptr(idx), vcap, icap,
+                                      C.byref(counts), gs, len(gathers), which, seed))
+    return nid, orde, idx, counts
+
+
 def meshlet_bounds_model(position: np.ndarray, index, meshlets: np.ndarray, vertices: np.ndarray, triangles: np.ndarray, counts, seed: int = 0,
                          capacity=None, fill: int = 0xCD, raw: bool = False):
     """crthip_meshlet_bounds_model: crthip_batch_bind_meshlet_bounds on the host in the kernel's partition (workgroups, waves and the lanes of
@@ -1406,6 +1479,7 @@ class Batch:
         self._adjacency = {}                         # blob -> (AdjacencyBinding, (twin tensor, counts tensor or None) or None): applied again by rebind() too
         self._weld = {}                              # blob -> (WeldBinding, (remap tensor, index tensor or None, counts tensor or None) or None): applied again by rebind() too
         self._lod = {}                               # blob -> (LodBinding, a list of (remap tensor, index tensor, counts tensor or None) a level, or None): applied again by rebind() too
+        self._compact = {}                           # blob -> (CompactBinding, a list of dicts a set (newid, order, index, counts and the gathered arrays by name as tensors, "dtypes"), or None): applied again by rebind() too
         self._cloud_lod = {}                         # blob -> (CloudLodBinding, a list of (remap, points, weight or None, chunks or None, counts or None) tensors a level, or None): applied again by rebind() too
         self._interleaved = None
 
@@ -1452,7 +1526,7 @@ class Batch:
     def allocate_outputs(self, normal_format=FMT_FLOAT, color_components: Optional[int] = None, index16=False,
                          only: Optional[set] = None, fill: Optional[int] = None, computed_normals=False, quantized=(),
                          computed_tangents=False, tangent_format=FMT_FLOAT, meshlets=None, meshlet_bounds=False, adjacency=False, weld=False, lod=None,
-                         cloud_lod=None):
+                         cloud_lod=None, compact=False):
         """Allocate every output of every blob inside ONE device buffer (torch.uint8) and bind them.
         Returns a list (per blob) of dicts name -> torch tensor view.
         computed_normals: every mesh blob WITHOUT a normal attribute gets a "normal" tensor of normal_format all the same, bound
@@ -1475,7 +1549,10 @@ class Batch:
         3*nface words and a device counts record, bound through crthip_batch_bind_lod; read them with lod(i) after sync().
         cloud_lod: (shifts, chunk_points), e.g. ((9, 11), 64) - every point cloud with points gets, a level, a remap, a points and a weight
         array of nvert words, ceil(nvert / chunk_points) chunk records and a device counts record, placed behind all other arrays and bound
-        through crthip_batch_bind_cloud_lod; meshes are skipped; read them with cloud_lod(i) after sync()."""
+        through crthip_batch_bind_cloud_lod; meshes are skipped; read them with cloud_lod(i) after sync().
+        compact: every blob gets, through crthip_batch_bind_compact, one set a level bound by lod= or cloud_lod= (a mesh without levels: one
+        set over its own index).  A mesh set has newid, order (nvert words each), index (3*nface words) and a device counts record; every
+        set gathers every vertex output bound above (eight at most) into packed arrays of nvert records; read them with compact(i) after sync()."""
         if meshlet_bounds and meshlets is None:
             raise ValueError("allocate_outputs: meshlet_bounds needs meshlets=")
         import torch
@@ -1540,6 +1617,25 @@ class Batch:
                 if not info.nface and info.nvert:
                     nch = (info.nvert + ck - 1) // ck
                     cplan.append((i, info.nvert, nch, [(int(s), take(info.nvert * 4), take(info.nvert * 4), take(info.nvert * 4), take(nch * 32), take(16)) for s in cshifts]))
+        kplan = []                                   # (blob, [(source, level, newid, order, index, counts offsets, [(name, gather source, offset, E, dtype, components)]) a set])
+        if compact:
+            for i, info in enumerate(self.infos):
+                nv, nf = info.nvert, info.nface
+                nlev = len(lod) if (lod and nf) else len(cloud_lod[0]) if (cloud_lod and not nf and nv) else 0
+                srcs = [(COMPACT_LOD if nf else COMPACT_CLOUD_LOD, k) for k in range(min(nlev, COMPACT_MAX_SETS))] or ([(COMPACT_INDEX, 0)] if nf else [])
+                mine = [p_ for p_ in plan if p_[0] == i and p_[5] != -1][:COMPACT_MAX_GATHERS]
+                sets = []
+                for (source, level) in srcs:
+                    mesh = source != COMPACT_CLOUD_LOD
+                    arrays = (take(max(nv, 1) * 4), take(max(nv, 1) * 4), take(nf * 12)) if mesh else (None, None, None)
+                    co = take(16)
+                    gl = []
+                    for (_, name, _, dt, shape, slot, _, _) in mine:
+                        E = shape[1] * np.dtype(_DT[dt]).itemsize
+                        gl.append((name, {-2: COMPACT_COMPUTED_NORMALS, -3: COMPACT_COMPUTED_TANGENTS}.get(slot, slot), take(nv * E), E, dt, shape[1]))
+                    sets.append((source, level) + arrays + (co, gl))
+                if sets:
+                    kplan.append((i, sets))
         total = max(off, 256)
         buf = torch.empty(total, dtype=torch.uint8, device=dev) if fill is None else torch.full((total,), fill, dtype=torch.uint8, device=dev)
         _torch_ready(dev)                            # (the fill runs on torch's stream; the decode on the context's own)
@@ -1550,6 +1646,25 @@ class Batch:
         index_ptrs = (C.c_void_p * max(len(self), 1))()
         index_fmt = np.full(max(len(self), 1), FMT_UINT32, dtype=np.uint32)
         outs = [dict() for _ in self.infos]
+        self._compact = {}
+        for (i, sets) in kplan:
+            nv, nf = self.infos[i].nvert, self.infos[i].nface
+            kb = CompactBinding()
+            kb.sets = len(sets)
+            keep = []
+            for s_, (source, level, no, oo, io, co, gl) in enumerate(sets):
+                t = kb.set[s_]
+                t.source, t.level, t.counts, t.vertex_capacity, t.ngather = source, level, base + co, nv, len(gl)
+                d = {"counts": buf[co:co + 16], "dtypes": {}}
+                if no is not None:
+                    t.newid, t.order, t.index, t.newid_capacity, t.index_capacity = base + no, base + oo, base + io, nv, nf * 3
+                    d.update(newid=buf[no:no + nv * 4], order=buf[oo:oo + nv * 4], index=buf[io:io + nf * 12])
+                for q, (name, gsrc, go, E, dt, comps) in enumerate(gl):
+                    t.gather[q] = CompactGather(base + go, gsrc, 0)
+                    d[name] = buf[go:go + nv * E]
+                    d["dtypes"][name] = (dt, comps)
+                keep.append(d)
+            self._compact[i] = (kb, keep)
         self._cloud_lod = {}
         for (i, nv, nch, levels) in cplan:
             cb = CloudLodBinding()
@@ -1654,6 +1769,7 @@ class Batch:
         self._weld = {}
         self._lod = {}
         self._cloud_lod = {}
+        self._compact = {}
         self._interleaved = metas
         self.outputs = [dict() for _ in self.infos]
         self.rebind()
@@ -1711,6 +1827,8 @@ class Batch:
             _check(lib().crthip_batch_bind_lod(self.handle, i, C.byref(lb)))
         for i, (cb, _) in self._cloud_lod.items():              # (... and a cloud's levels of detail)
             _check(lib().crthip_batch_bind_cloud_lod(self.handle, i, C.byref(cb)))
+        for i, (kb, _) in self._compact.items():                # (... and, behind everything it names, its compaction)
+            _check(lib().crthip_batch_bind_compact(self.handle, i, C.byref(kb)))
 
     def bind(self, i: int, bindings: Sequence[AttrBinding], index_ptr: Optional[int] = None, index_format=FMT_UINT32):
         arr = (AttrBinding * max(len(bindings), 1))(*bindings)
@@ -1848,6 +1966,41 @@ class Batch:
             out.append((raw(remap, self.infos[i].nvert * 4).view(np.uint32), raw(points, rec[1] * 4).view(np.uint32),
                         None if weight is None else raw(weight, rec[1] * 4).view(np.uint32),
                         None if chunks is None else raw(chunks, rec[2] * 32).view(CLOUD_CHUNK_DTYPE), rec))
+        return out
+
+    def bind_compact(self, i: int, binding: Optional[CompactBinding] = None, keep=None):
+        """crthip_batch_bind_compact: blob i's compact sets go to the binding's device arrays.  After bind() / rebind() of that blob and after
+        every weld, lod, cloud lod, computed normals or tangents call it names, all of which drop it; None removes it.  keep: whatever owns
+        the memory (device tensors), held with the binding - a list of dicts a set as allocate_outputs(compact=) makes them ("counts" and any
+        of "newid", "order", "index" as uint8 tensors, gathered arrays by name, "dtypes": name -> (dtype key, components)) makes compact(i) work."""
+        if binding is None:
+            self._compact.pop(i, None)
+            _check(lib().crthip_batch_bind_compact(self.handle, i, None))
+            return
+        _check(lib().crthip_batch_bind_compact(self.handle, i, C.byref(binding)))
+        self._compact[i] = (binding, keep)
+
+    def compact(self, i: int):
+        """Blob i's compact sets on the host: a list, a set, of dicts - "counts": (vertices, used, faces, clipped); for a mesh set "newid"
+        uint32 (nvert,), "order" uint32 cut to min(used, vertex_capacity) words, "index" uint32 cut to min(3*faces, index_capacity) words;
+        and every gathered array by name, cut to min(used, vertex_capacity) records.  After sync(); for bindings with a device counts record
+        a set, made by allocate_outputs(compact=) or bind_compact(keep=)."""
+        kb, keep = self._compact[i]
+        raw = lambda t, n: t.cpu().numpy().view(np.uint8).reshape(-1)[:n].copy()   # noqa: E731
+        out = []
+        for s_, d in enumerate(keep):
+            rec = tuple(int(x) for x in raw(d["counts"], 16).view(np.uint32))
+            n = min(rec[1], kb.set[s_].vertex_capacity)
+            o = {"counts": rec}
+            if "newid" in d:
+                o["newid"] = raw(d["newid"], self.infos[i].nvert * 4).view(np.uint32)
+            if "order" in d:
+                o["order"] = raw(d["order"], n * 4).view(np.uint32)
+            if "index" in d:
+                o["index"] = raw(d["index"], min(rec[2] * 3, kb.set[s_].index_capacity) * 4).view(np.uint32)
+            for name, (dt, comps) in d.get("dtypes", {}).items():
+                o[name] = raw(d[name], n * comps * np.dtype(_DT[dt]).itemsize).view(_DT[dt]).reshape(n, comps)
+            out.append(o)
         return out
 
     def meshlet_counts(self, i: int) -> MeshletCounts:

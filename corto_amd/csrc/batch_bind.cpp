@@ -1,5 +1,5 @@
-// batch_bind.cpp — what a caller binds to a batch's blobs and what reads a decode's records back: crthip_batch_bind / _bind_all, the eight derived
-// outputs (computed normals, computed tangents, meshlets, meshlet bounds, adjacency, weld, levels of detail of meshes and of clouds: DerivedBindings, batch_internal.h), the quantised attributes' records and the
+// batch_bind.cpp — what a caller binds to a batch's blobs and what reads a decode's records back: crthip_batch_bind / _bind_all, the nine derived
+// outputs (computed normals, computed tangents, meshlets, meshlet bounds, adjacency, weld, levels of detail of meshes and of clouds, compaction: DerivedBindings, batch_internal.h), the quantised attributes' records and the
 // meshlet counts.  Every check of a binding is made here, in the order corto_hip.h lists its errors, so that a decode has nothing new to fail on.
 // No HIP call: a program without the runtime links these (tests/cpp/plan_dump.cpp).
 #include "batch_internal.h"
@@ -106,7 +106,7 @@ extern "C" int crthip_batch_bind_computed_tangents(crthip_batch *b, uint32_t i, 
 	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_computed_tangents: no such blob");
 	BlobPlan &P = b->blobs[i];
 	const std::string who = " (blob " + std::to_string(i) + ")";
-	if(!buffer) { P.derived.tangents = Binding{}; b->dirty = true; return CRTHIP_OK; }
+	if(!buffer) { P.derived.tangents_change(); P.derived.tangents = Binding{}; b->dirty = true; return CRTHIP_OK; }
 	if(P.L.h.nface == 0) return fail(CRTHIP_E_ARGUMENT, "computed tangents need faces: a point cloud has none" + who);
 	if(format != CRTHIP_FMT_FLOAT && format != CRTHIP_FMT_INT16) return fail(CRTHIP_E_FORMAT, "computed tangents are FLOAT or INT16" + who);
 	const uint32_t el = format == CRTHIP_FMT_INT16 ? 2u : 4u;
@@ -119,6 +119,7 @@ extern "C" int crthip_batch_bind_computed_tangents(crthip_batch *b, uint32_t i, 
 		return fail(CRTHIP_E_ARGUMENT, "computed tangents need a bound two-component generic \"uv\" (bind the blob first)" + who);
 	if(!tangent_normal_source(P))
 		return fail(CRTHIP_E_ARGUMENT, "computed tangents need a normal source: a stored \"normal\" bound as FLOAT or INT16, or crthip_batch_bind_computed_normals before this call" + who);
+	P.derived.tangents_change();                                          // (a compaction that gathers the tangents is bound behind this call)
 	Binding &out = P.derived.tangents;
 	out.buffer = buffer; out.format = format; out.out_components = 4;
 	out.stride = stride == 4*el ? 0u : stride;
@@ -182,12 +183,13 @@ extern "C" int crthip_batch_bind_weld(crthip_batch *b, uint32_t i, const crthip_
 	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_weld: no such blob");
 	BlobPlan &P = b->blobs[i];
 	const std::string who = " (blob " + std::to_string(i) + ")";
-	if(!w) { P.derived.weld = crthip_weld_binding{}; b->dirty = true; return CRTHIP_OK; }
+	if(!w) { P.derived.source_change(CRTHIP_COMPACT_WELD); P.derived.weld = crthip_weld_binding{}; b->dirty = true; return CRTHIP_OK; }
 	if(P.L.h.nface == 0) return fail(CRTHIP_E_ARGUMENT, "a weld needs faces: a point cloud has none" + who);
 	if(const char *why = weld_binding_error(w, P.L.h.nvert, P.L.h.nface)) return fail(CRTHIP_E_ARGUMENT, why + who);
 	// (what meshlet bounds ask of the position)
 	if(!generic_source_ok(P, attr_named(P, "position"), 3))
 		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "a weld needs a bound three-component \"position\" (bind the blob first)" + who);
+	P.derived.source_change(CRTHIP_COMPACT_WELD);                         // (a compaction of the welded index is bound behind this call)
 	P.derived.weld = *w;
 	b->dirty = true;
 	return CRTHIP_OK;
@@ -199,12 +201,13 @@ extern "C" int crthip_batch_bind_lod(crthip_batch *b, uint32_t i, const crthip_l
 	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_lod: no such blob");
 	BlobPlan &P = b->blobs[i];
 	const std::string who = " (blob " + std::to_string(i) + ")";
-	if(!l) { P.derived.lod = crthip_lod_binding{}; b->dirty = true; return CRTHIP_OK; }
+	if(!l) { P.derived.source_change(CRTHIP_COMPACT_LOD); P.derived.lod = crthip_lod_binding{}; b->dirty = true; return CRTHIP_OK; }
 	if(P.L.h.nface == 0) return fail(CRTHIP_E_ARGUMENT, "levels of detail need faces: a point cloud has none" + who);
 	if(const char *why = lod_binding_error(l, P.L.h.nvert, P.L.h.nface)) return fail(CRTHIP_E_ARGUMENT, why + who);
 	// (what the weld asks of the position)
 	if(!generic_source_ok(P, attr_named(P, "position"), 3))
 		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "levels of detail need a bound three-component \"position\" (bind the blob first)" + who);
+	P.derived.source_change(CRTHIP_COMPACT_LOD);                          // (a compaction of a level is bound behind this call)
 	P.derived.lod = *l;
 	b->dirty = true;
 	return CRTHIP_OK;
@@ -216,14 +219,65 @@ extern "C" int crthip_batch_bind_cloud_lod(crthip_batch *b, uint32_t i, const cr
 	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_cloud_lod: no such blob");
 	BlobPlan &P = b->blobs[i];
 	const std::string who = " (blob " + std::to_string(i) + ")";
-	if(!l) { P.derived.cloud_lod = crthip_cloud_lod_binding{}; b->dirty = true; return CRTHIP_OK; }
+	if(!l) { P.derived.source_change(CRTHIP_COMPACT_CLOUD_LOD); P.derived.cloud_lod = crthip_cloud_lod_binding{}; b->dirty = true; return CRTHIP_OK; }
 	if(P.L.h.nface > 0) return fail(CRTHIP_E_ARGUMENT, "a cloud's levels of detail: the blob has faces, it is not a point cloud" + who);
 	if(P.L.h.nvert == 0) return fail(CRTHIP_E_ARGUMENT, "a cloud's levels of detail: the cloud has no points" + who);
 	if(const char *why = cloud_lod_binding_error(l, P.L.h.nvert)) return fail(CRTHIP_E_ARGUMENT, why + who);
 	// (what the weld asks of the position)
 	if(!generic_source_ok(P, attr_named(P, "position"), 3))
 		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "a cloud's levels of detail need a bound three-component \"position\" (bind the blob first)" + who);
+	P.derived.source_change(CRTHIP_COMPACT_CLOUD_LOD);                    // (a compaction of a level is bound behind this call)
 	P.derived.cloud_lod = *l;
+	b->dirty = true;
+	return CRTHIP_OK;
+}
+
+// Compaction (corto_hip.h has the contract): what a binding on blob P is refused for, in the header's order behind "no such blob"; CRTHIP_OK: fine.
+// The planner asks again (compact_jobs), so that a decode has nothing new to fail on
+int compact_binding_error(const BlobPlan &P, const crthip_compact_binding *c, std::string &why) {
+	if(c->sets < 1 || c->sets > CRTHIP_COMPACT_MAX_SETS) { why = "compact: sets is not in 1..CRTHIP_COMPACT_MAX_SETS"; return CRTHIP_E_ARGUMENT; }
+	if(c->flags) { why = "compact: unknown flag bits"; return CRTHIP_E_ARGUMENT; }
+	if(c->reserved[0] || c->reserved[1]) { why = "compact: reserved is not 0"; return CRTHIP_E_ARGUMENT; }
+	const bool mesh = P.L.h.nface > 0;
+	const uint32_t nvert = P.L.h.nvert;
+	for(uint32_t s = 0; s < c->sets; s++) {
+		const crthip_compact_set &t = c->set[s];
+		const std::string set = "compact, set " + std::to_string(s) + ": ";
+		auto bad = [&](const char *m) { why = set + m; return CRTHIP_E_ARGUMENT; };
+		if(t.source > CRTHIP_COMPACT_CLOUD_LOD) return bad("an unknown source");
+		if(t.reserved[0] || t.reserved[1]) return bad("reserved is not 0");
+		const bool cloud = t.source == CRTHIP_COMPACT_CLOUD_LOD;
+		if(cloud && mesh) return bad("the cloud source on a mesh");
+		if(!cloud && !mesh) return bad("a mesh source on a point cloud");
+		if(t.source == CRTHIP_COMPACT_WELD && !(binds_weld(P) && P.derived.weld.index)) return bad("the blob has no weld binding with an index");
+		if(t.source == CRTHIP_COMPACT_LOD && !(binds_lod(P) && t.level < P.derived.lod.levels)) return bad("the blob's lod binding has no such level");
+		if(cloud && !(binds_cloud_lod(P) && t.level < P.derived.cloud_lod.levels)) return bad("the blob's cloud lod binding has no such level");
+		if(cloud && (t.newid || t.order || t.index)) return bad("a cloud source takes no newid, order or index");
+		if((uintptr_t)t.newid % 4 || (uintptr_t)t.order % 4 || (uintptr_t)t.index % 4) return bad("newid, order or index is not 4-byte aligned");
+		if((uintptr_t)t.counts % 16) return bad("counts is not 16-byte aligned");
+		if(t.newid && t.newid_capacity < nvert) return bad("newid_capacity is below nvert");
+		if(t.ngather > CRTHIP_COMPACT_MAX_GATHERS) return bad("ngather is above CRTHIP_COMPACT_MAX_GATHERS");
+		for(uint32_t q = 0; q < t.ngather; q++) {
+			const crthip_compact_gather &g = t.gather[q];
+			const std::string gather = set + "gather " + std::to_string(q) + ": ";
+			const CompactSource src = compact_source_of(P, g.source);
+			if(src.err) { why = gather + src.why; return src.err; }
+			if(!g.dst || (uintptr_t)g.dst % src.A) { why = gather + "dst is NULL or not aligned to the source's element"; return CRTHIP_E_ARGUMENT; }
+			if(g.dst_stride && (g.dst_stride < src.E || g.dst_stride % src.A)) { why = gather + "dst_stride is below the element size or no multiple of its alignment"; return CRTHIP_E_ARGUMENT; }
+		}
+	}
+	return CRTHIP_OK;
+}
+
+// Every check is made here, in the header's order.  The binding reads other bindings' outputs: a later call that changes one of them drops it
+// (DerivedBindings::source_change, normals_change, tangents_change), and it drops none
+extern "C" int crthip_batch_bind_compact(crthip_batch *b, uint32_t i, const crthip_compact_binding *c) {
+	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_compact: no such blob");
+	BlobPlan &P = b->blobs[i];
+	if(!c) { P.derived.compact = crthip_compact_binding{}; b->dirty = true; return CRTHIP_OK; }
+	std::string why;
+	if(const int err = compact_binding_error(P, c, why)) return fail(err, why + " (blob " + std::to_string(i) + ")");
+	P.derived.compact = *c;
 	b->dirty = true;
 	return CRTHIP_OK;
 }

@@ -32,6 +32,7 @@
 #include "weld.h"
 #include "lod.h"
 #include "cloud_lod.h"
+#include "compact.h"
 
 using namespace corto_hip;
 
@@ -104,10 +105,11 @@ struct BlobScratch {
 	uint64_t weld = ~0ull;                                  // weld (DerivedBindings::weld) of a blob beyond weld_in_blob: weld_scratch_layout's block
 	uint64_t lod[CRTHIP_LOD_MAX_LEVELS] = {~0ull, ~0ull, ~0ull, ~0ull};   // levels of detail (DerivedBindings::lod): a level's lod_scratch_layout block
 	uint64_t cloud_lod[CRTHIP_CLOUD_LOD_MAX_LEVELS] = {~0ull, ~0ull, ~0ull, ~0ull};   // a cloud's levels of detail (DerivedBindings::cloud_lod) beyond weld_in_blob: a level's cloud_lod_scratch_layout block
+	uint64_t compact[CRTHIP_COMPACT_MAX_SETS] = {~0ull, ~0ull, ~0ull, ~0ull};   // compaction (DerivedBindings::compact): a set's compact_scratch_layout block
 	uint64_t cn_facen = ~0ull;                              // computed normals (DerivedBindings::normals) by the fused kernel without its face normals in LDS: AttrScratch::facen's counterpart
 	std::vector<AttrScratch> attr;
 	size_t nattr = 0;                                       // attr[0..nattr) are this decode's (the vector only grows)
-	void reset() { clers = pred = front_a = front_b = order = delayed = faces = progress = cn_facen = tan_acc = mlt = mlt_counts = adj = weld = ~0ull; for(uint64_t &l : lod) l = ~0ull; for(uint64_t &l : cloud_lod) l = ~0ull; front_cap = 0; aux_groups = 0; nattr = 0; }
+	void reset() { clers = pred = front_a = front_b = order = delayed = faces = progress = cn_facen = tan_acc = mlt = mlt_counts = adj = weld = ~0ull; for(uint64_t &l : lod) l = ~0ull; for(uint64_t &l : cloud_lod) l = ~0ull; for(uint64_t &l : compact) l = ~0ull; front_cap = 0; aux_groups = 0; nattr = 0; }
 	void set_attrs(size_t n) { if(attr.size() < n) attr.resize(n); for(size_t k = nattr; k < n; k++) attr[k].reset();
 		if(n > nattr) nattr = n; }
 };
@@ -154,6 +156,11 @@ struct Plan {
 	// among them), the others by id for the scan (k_cloud_lod_offsets), 256 vertices a block (k_cloud_lod_insert, _lookup, _scatter) and, those with
 	// a chunks array, a block a chunk of the capacity (k_cloud_lod_chunks)
 	HostArr<CloudLodJob> cloud_lod; HostArr<uint32_t> cloud_lod_blob_ids, cloud_lod_big_ids, cloud_lod_vblock_job, cloud_lod_cblock_job; uint32_t cloud_lod_lds = 0;
+	// crthip_batch_bind_compact: a job a bound MESH set.  Sets within compact_in_blob by id (k_compact_blob), the others by id for the scan
+	// (k_compact_offsets), 256 vertices a block (k_compact_count, _place) and 256 corners a block (k_compact_mark, _index); and a job a GATHER of every
+	// set, clouds' too, 256 copy units a block (k_compact_gather)
+	HostArr<CompactJob> compact; HostArr<uint32_t> compact_blob_ids, compact_big_ids, compact_vblock_job, compact_cblock_job;
+	HostArr<CompactGatherJob> compact_gather; HostArr<uint32_t> compact_gblock_job;
 	bool meshlet_records = false;                           // a crthip_meshlet_counts a blob behind the quant records: a batch with a meshlet binding
 	uint32_t quant_records = 0;                             // records behind the status words: sum(nattr) of a batch with a quantised binding, else 0
 	// scratch regions (offsets)
@@ -184,11 +191,14 @@ struct Plan {
 	template <class F> void each_lod_array(F f) { f(lod); f(lod_blob_ids); f(lod_big_ids); f(lod_vblock_job); f(lod_fblock_job); }
 	// ... and of the clouds' levels of detail, behind them
 	template <class F> void each_cloud_lod_array(F f) { f(cloud_lod); f(cloud_lod_blob_ids); f(cloud_lod_big_ids); f(cloud_lod_vblock_job); f(cloud_lod_cblock_job); }
+	// ... and of the compaction, behind them
+	template <class F> void each_compact_array(F f) { f(compact); f(compact_blob_ids); f(compact_big_ids); f(compact_vblock_job); f(compact_cblock_job); f(compact_gather); f(compact_gblock_job); }
 	void reset() {                                          // keep every vector's capacity
 		each_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
 		each_optional_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
 		each_lod_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
 		each_cloud_lod_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
+		each_compact_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
 		clers_groups = 0; topo_need.clear(); quant_records = 0; meshlet_waves = 0; meshlet_records = false;
 		topo_lds = topo_big_lds = normal_fused_lds = normal_computed_lds = tangent_lds = adjacency_lds = weld_lds = lod_lds = cloud_lod_lds = 0;
 		zero_begin = zero_end = tables_off = tun_partial_off = unpack_partial_off = cloud_partial_off = 0;
@@ -277,9 +287,24 @@ struct DerivedBindings {
 	crthip_weld_binding weld{};            // crthip_batch_bind_weld: weld.remap != null - where the blob's weld map goes (reads the integer positions and the index)
 	crthip_lod_binding lod{};              // crthip_batch_bind_lod: lod.levels != 0 - where the blob's levels of detail go (reads the integer positions and the index)
 	crthip_cloud_lod_binding cloud_lod{};  // crthip_batch_bind_cloud_lod: cloud_lod.levels != 0 - where a cloud's levels of detail go (reads the integer positions)
+	crthip_compact_binding compact{};      // crthip_batch_bind_compact: compact.sets != 0 - where the blob's compact sets go (reads other bindings' outputs: the functions below)
 	void clear() { *this = DerivedBindings{}; }       // a bind (and a blob adopted by a fill): all of them read what it binds
-	void normals_change() { tangents = Binding{}; }   // a normals call: the tangents' normal source may change
+	// a normals call: the tangents' normal source may change; a compaction that gathers either goes with them
+	void normals_change() { tangents = Binding{}; if(compact_gathers(CRTHIP_COMPACT_COMPUTED_NORMALS) || compact_gathers(CRTHIP_COMPACT_COMPUTED_TANGENTS)) compact = crthip_compact_binding{}; }
+	void tangents_change() { if(compact_gathers(CRTHIP_COMPACT_COMPUTED_TANGENTS)) compact = crthip_compact_binding{}; }   // a tangents call
 	void meshlets_change() { bounds = nullptr; }      // a meshlets call: the bounds' arrays and capacity change
+	void source_change(uint32_t source) { if(compact_reads(source)) compact = crthip_compact_binding{}; }   // a weld, lod or cloud lod call that sets, replaces or removes: a compaction that names it goes
+	bool compact_reads(uint32_t source) const { for(uint32_t s = 0; s < compact.sets && s < CRTHIP_COMPACT_MAX_SETS; s++) if(compact.set[s].source == source) return true; return false; }
+	bool compact_gathers(uint32_t what) const {
+		for(uint32_t s = 0; s < compact.sets && s < CRTHIP_COMPACT_MAX_SETS; s++)
+			for(uint32_t q = 0; q < compact.set[s].ngather && q < CRTHIP_COMPACT_MAX_GATHERS; q++) if(compact.set[s].gather[q].source == what) return true;
+		return false;
+	}
+	// the compaction reads level k of the lod (cloud: the cloud lod) binding, so its record must exist somewhere: the set that does, or -1
+	int compact_set_of(uint32_t source, uint32_t level) const {
+		for(uint32_t s = 0; s < compact.sets && s < CRTHIP_COMPACT_MAX_SETS; s++) if(compact.set[s].source == source && compact.set[s].level == level) return (int)s;
+		return -1;
+	}
 };
 
 struct BlobPlan {
@@ -397,6 +422,10 @@ static inline bool binds_lod(const BlobPlan &P) { return P.derived.lod.levels &&
 // others the five kernels over scratch (cloud_lod.h; weld.h: weld_in_blob)
 static inline bool binds_cloud_lod(const BlobPlan &P) { return P.derived.cloud_lod.levels && P.L.h.nface == 0 && P.L.h.nvert > 0; }
 
+// compaction (crthip_batch_bind_compact): a job a mesh set - one within compact_in_blob takes k_compact_blob, the others the five kernels over
+// scratch - and a job a gather of every set (compact.h)
+static inline bool binds_compact(const BlobPlan &P) { return P.derived.compact.sets != 0; }
+
 // where the derived outputs and the estimated normals take their inputs.  An attribute by name: the last one of that name, or -1
 static inline int attr_named(const BlobPlan &P, const char *name) {
 	int k = -1;
@@ -413,6 +442,38 @@ static inline const Binding *tangent_normal_source(const BlobPlan &P) {
 	for(size_t k = 0; k < P.bind.size(); k++)
 		if(P.L.h.attrs[k].name == "normal" && P.L.h.attrs[k].codec == CRTHIP_CODEC_NORMAL && P.bind[k].buffer) return &P.bind[k];
 	return nullptr;
+}
+// what a gather of crthip_batch_bind_compact copies: the source's own buffer as bound, its element size E, E's alignment A and the byte distance
+// of two vertices; or the error, in the header's order (a number out of range, unbound or missing: ARGUMENT; outside the table: FORMAT)
+struct CompactSource { const void *buffer; uint32_t E, A, stride; int err; const char *why; };
+static inline CompactSource compact_source_of(const BlobPlan &P, uint32_t source) {
+	auto of = [](const Binding &bd, uint32_t E, uint32_t A) { return CompactSource{bd.buffer, E, A, bd.stride ? bd.stride : E, CRTHIP_OK, nullptr}; };
+	if(source == CRTHIP_COMPACT_COMPUTED_NORMALS) {
+		if(!computes_normals(P)) return CompactSource{nullptr, 0, 0, 0, CRTHIP_E_ARGUMENT, "the blob has no computed normals binding"};
+		const bool i16 = P.derived.normals.format == CRTHIP_FMT_INT16;
+		return of(P.derived.normals, i16 ? 6u : 12u, i16 ? 2u : 4u);
+	}
+	if(source == CRTHIP_COMPACT_COMPUTED_TANGENTS) {
+		if(!computes_tangents(P)) return CompactSource{nullptr, 0, 0, 0, CRTHIP_E_ARGUMENT, "the blob has no computed tangents binding"};
+		const bool i16 = P.derived.tangents.format == CRTHIP_FMT_INT16;
+		return of(P.derived.tangents, i16 ? 8u : 16u, i16 ? 2u : 4u);
+	}
+	if(source >= P.bind.size()) return CompactSource{nullptr, 0, 0, 0, CRTHIP_E_ARGUMENT, "the attribute number is out of range"};
+	const Binding &bd = P.bind[source];
+	const AttrHeader &a = P.L.h.attrs[source];
+	if(!bd.buffer) return CompactSource{nullptr, 0, 0, 0, CRTHIP_E_ARGUMENT, "the attribute is not bound"};
+	if(a.codec == CRTHIP_CODEC_NORMAL) { const bool i16 = bd.format == CRTHIP_FMT_INT16; return of(bd, i16 ? 6u : 12u, i16 ? 2u : 4u); }
+	if(a.codec == CRTHIP_CODEC_COLOR) return of(bd, bd.out_components, 1u);
+	if(bd.stream_values) return CompactSource{nullptr, 0, 0, 0, CRTHIP_E_FORMAT, "the attribute is bound with CRTHIP_BIND_STREAM_VALUES: a work array, not vertex records"};
+	if(bd.quantized) return of(bd, 2u*a.N, 2u);
+	if(bd.format != CRTHIP_FMT_FLOAT) return CompactSource{nullptr, 0, 0, 0, CRTHIP_E_FORMAT, "the attribute is bound in an integer format or DOUBLE: a work array, not vertex records"};
+	return of(bd, 4u*a.N, 4u);
+}
+int compact_binding_error(const BlobPlan &P, const crthip_compact_binding *c, std::string &why);   // (batch_bind.cpp: every check of the bind call)
+// a set's block of scratch: a newid of its own where a bigger set has an index and no newid, an order of its own where a mesh set has gathers and no order
+static inline CompactScratchLayout compact_layout_of(const BlobPlan &P, const crthip_compact_set &t) {
+	const bool cloud = t.source == CRTHIP_COMPACT_CLOUD_LOD;
+	return compact_scratch_layout(P.L.h.nvert, P.L.h.nface, cloud, !t.newid && t.index, !cloud && !t.order && t.ngather ? std::min(t.vertex_capacity, P.L.h.nvert) : 0u);
 }
 
 struct Launch {
@@ -516,6 +577,6 @@ struct Planner {
 	bool inverse_job(const BlobView &v, size_t k, void *values, uint32_t N, bool para, uint8_t is_u8, bool hand_i16);
 	void stored_normal_job(const BlobView &v, size_t k, bool hand_i16); void quant_job(const BlobView &v, size_t k); void dequant_job(const BlobView &v, size_t k);
 	bool estimated_normal_tail(const BlobView &v, NormalJob &n, HostArr<uint32_t> &fused_ids, uint32_t &fused_lds, uint64_t facen);
-	bool computed_normal_job(const BlobView &v); bool tangent_job(const BlobView &v); void meshlet_jobs(const BlobView &v); void weld_jobs(const BlobView &v); void adjacency_jobs(const BlobView &v); void lod_jobs(const BlobView &v); void cloud_lod_jobs(const BlobView &v);
+	bool computed_normal_job(const BlobView &v); bool tangent_job(const BlobView &v); void meshlet_jobs(const BlobView &v); void weld_jobs(const BlobView &v); void adjacency_jobs(const BlobView &v); void lod_jobs(const BlobView &v); void cloud_lod_jobs(const BlobView &v); void compact_jobs(const BlobView &v);
 };
 

@@ -288,6 +288,36 @@ struct CloudLodJob {
 };
 static_assert(sizeof(CloudLodJob) == 96, "decode job layout");
 
+// one MESH SET of a blob bound with crthip_batch_bind_compact (k_compact.hip, compact.h): an id list -> the set's newid, order, renumbered index
+// and record.  A set within compact_in_blob needs nothing else; the others keep their mask and their block counts in scratch
+struct CompactJob {
+	const void *src;               // the id list, u32 or, with src_u16, u16: the blob's index (the caller's, or scratch), the weld's index, a level's index
+	const uint32_t *src_rec;       // the record whose word 1 is the list's face count (a level's crthip_lod_counts: the caller's, or scratch); null: nface
+	uint32_t *newid;               // nvert words: the set's, or (bigger sets with an index) scratch; null: none wanted
+	uint32_t *order;               // the set's, or (a set with gathers) scratch: min(vcap, nvert) words at most are written; null: none wanted
+	uint32_t *index;               // the set's: min(3*F, icap) words are written; null: none wanted
+	void *counts;                  // crthip_compact_counts in DEVICE memory: the set's, or scratch
+	uint32_t *mask, *blocks;       // bigger sets: ceil(nvert/32) words zeroed by one FillJob; a word a block of 256 vertices - its count, then its base
+	uint32_t nface, nvert;         // nface: the BOUND the grids and the source array were sized from
+	uint32_t vcap, icap;           // vertex_capacity, index_capacity
+	uint32_t vblock0, cblock0;     // first block of this job in the two block -> job maps (compact_count and _place; compact_mark and _index)
+	uint8_t src_u16, clip_v, pad[6];   // clip_v: the set has an order or a gather
+};
+// one GATHER of a set (k_compact_gather): E bytes of vertex order[j] of a final vertex output -> record j of a compact array
+struct CompactGatherJob {
+	const uint8_t *src;            // the source's own buffer, as bound
+	uint8_t *dst;
+	const uint32_t *order;         // the set's order (the caller's, or scratch); a cloud set's: its level's points
+	const uint32_t *count_rec;     // the record whose word 1 is `used`: the set's; a cloud set's: its level's (the caller's, or scratch)
+	void *cloud_rec;               // a cloud set's first gather: the set's record, which this kernel stores; else null
+	uint32_t E, sstride, dstride;  // element bytes (0: a cloud set without gathers - the record alone) and the two strides as byte distances
+	uint32_t unit;                 // compact_unit's choice
+	uint32_t vcap, nvert;
+	uint32_t block0;               // first block of this job in the block -> job map
+	uint8_t clip_v, pad[3];
+};
+static_assert(sizeof(CompactJob) == 96 && sizeof(CompactGatherJob) == 72, "decode job layout");
+
 // the layout the kernels read, pinned (TopoJob's size is performance-critical: TOPO_OPT_PROGRESS above)
 static_assert(sizeof(TunStream) == 64 && sizeof(FillJob) == 16 && sizeof(TopoJob) == 136 && sizeof(UnpackJob) == 56 && sizeof(DeltaJob) == 96 &&
               sizeof(CloudJob) == 24 && sizeof(NormalJob) == 104 && sizeof(DequantJob) == 64 && sizeof(QuantOutJob) == 72 && sizeof(TangentJob) == 80 &&

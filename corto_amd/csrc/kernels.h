@@ -109,6 +109,18 @@ __global__ void k_cloud_lod_offsets(const CloudLodJob *jobs, const uint32_t *job
 __global__ void k_cloud_lod_scatter(const CloudLodJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 __global__ void k_cloud_lod_chunks(const CloudLodJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 
+// k_compact.hip (crthip_batch_bind_compact; compact.h has the method and both partitions): a job is one mesh set of one blob.  Sets of up to
+// 8 192 vertices and bound faces by one workgroup each from an id list (2 KiB of static LDS); bigger ones 256 corners a block from a block -> job
+// map (mark, index), 256 vertices a block from a second map (count, place) and one workgroup a set from an id list (offsets).  k_compact_gather:
+// a job is one gather of one set, mesh or cloud, 256 copy units a block from a map of its own
+__global__ void k_compact_blob(const CompactJob *jobs, const uint32_t *job_ids, uint32_t njobs);
+__global__ void k_compact_mark(const CompactJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_compact_count(const CompactJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_compact_offsets(const CompactJob *jobs, const uint32_t *job_ids, uint32_t njobs);
+__global__ void k_compact_place(const CompactJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_compact_index(const CompactJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_compact_gather(const CompactGatherJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+
 // k_mesh.hip
 __global__ void k_topology(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);
 __global__ void k_topology_lds(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);

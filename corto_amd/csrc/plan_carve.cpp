@@ -132,6 +132,10 @@ int Planner::carve() {
 		if(binds_cloud_lod(P) && !weld_in_blob(P.L.h.nvert))
 			for(uint32_t k = 0; k < P.derived.cloud_lod.levels && k < CRTHIP_CLOUD_LOD_MAX_LEVELS; k++) bs[i].cloud_lod[k] = cv.take(cloud_lod_scratch_layout(P.L.h.nvert).total, 16);
 	}
+	for(uint32_t i = 0; i < nblobs; i++) {                           // compaction: a set's records, its own newid and order, and beyond compact_blob its mask (zeroed by a FillJob) and block counts
+		const BlobPlan &P = b->blobs[i];
+		if(binds_compact(P)) for(uint32_t k = 0; k < P.derived.compact.sets && k < CRTHIP_COMPACT_MAX_SETS; k++) bs[i].compact[k] = cv.take(compact_layout_of(P, P.derived.compact.set[k]).total, 16);
+	}
 	if(est_v) {
 		pl.start_off = cv.take(est_v*4 + 16); pl.flag_off = cv.take(est_v*4 + 16); pl.slot_off = cv.take(est_v*4 + 16);
 		pl.adj_off = cv.take(est_f*12 + 16); pl.facen_off = cv.take(est_f*12 + 16);

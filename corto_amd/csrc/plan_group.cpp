@@ -97,6 +97,7 @@ void Planner::group() {
 	pl.each_optional_array([&](auto &arr) { if(!arr.v.empty()) arr.dev_off = cv.take(arr.v.size()*sizeof(arr.v[0]) + 16, 16); });
 	pl.each_lod_array([&](auto &arr) { if(!arr.v.empty()) arr.dev_off = cv.take(arr.v.size()*sizeof(arr.v[0]) + 16, 16); });
 	pl.each_cloud_lod_array([&](auto &arr) { if(!arr.v.empty()) arr.dev_off = cv.take(arr.v.size()*sizeof(arr.v[0]) + 16, 16); });
+	pl.each_compact_array([&](auto &arr) { if(!arr.v.empty()) arr.dev_off = cv.take(arr.v.size()*sizeof(arr.v[0]) + 16, 16); });
 	pl.jobs_bytes = cv.take(0) - pl.jobs_begin;
 	pl.total = cv.take(0);
 }
@@ -135,6 +136,8 @@ int Planner::upload() {
 	for(auto &w : pl.weld.v) { resolve(w.position); resolve(w.index); resolve(w.counts); resolve(w.table); }
 	for(auto &l : pl.lod.v) { resolve(l.position); resolve(l.index); resolve(l.counts); resolve(l.triples); resolve(l.vtable); resolve(l.ftable); resolve(l.blocks); }
 	for(auto &c : pl.cloud_lod.v) { resolve(c.position); resolve(c.counts); resolve(c.table); resolve(c.wacc); resolve(c.blocks); }
+	for(auto &c : pl.compact.v) { resolve(c.src); resolve(c.src_rec); resolve(c.newid); resolve(c.order); resolve(c.counts); resolve(c.mask); resolve(c.blocks); }
+	for(auto &g : pl.compact_gather.v) { resolve(g.order); resolve(g.count_rec); resolve(g.cloud_rec); }
 
 	// host image -> device (one copy)
 	stage = (uint8_t *)set.staging.p;
@@ -149,7 +152,7 @@ int Planner::upload() {
 		}
 	}
 	auto stage_array = [&](auto &arr) { if(!arr.v.empty()) memcpy(stage + (arr.dev_off - pl.jobs_begin), arr.v.data(), arr.v.size()*sizeof(arr.v[0])); };
-	pl.each_array(stage_array); pl.each_optional_array(stage_array); pl.each_lod_array(stage_array); pl.each_cloud_lod_array(stage_array);
+	pl.each_array(stage_array); pl.each_optional_array(stage_array); pl.each_lod_array(stage_array); pl.each_cloud_lod_array(stage_array); pl.each_compact_array(stage_array);
 
 	return CRTHIP_OK;
 }

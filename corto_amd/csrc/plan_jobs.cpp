@@ -132,6 +132,7 @@ int Planner::jobs() {
 		if(binds_adjacency(v.P) && !v.P.host_status) adjacency_jobs(v);
 		if(binds_lod(v.P) && !v.P.host_status) lod_jobs(v);
 		if(binds_cloud_lod(v.P) && !v.P.host_status) cloud_lod_jobs(v);
+		if(binds_compact(v.P) && !v.P.host_status) compact_jobs(v);
 	}
 	return CRTHIP_OK;
 }
@@ -516,6 +517,9 @@ void Planner::lod_jobs(const BlobView &v) {
 		l.remap = lv.remap; l.lod_index = lv.index; l.counts = lv.counts; l.nface = v.nface; l.nvert = v.nvert; l.shift = lv.shift;
 		l.triples = (uint32_t *)SP(S + lay.triples);
 		const uint32_t id = (uint32_t)pl.lod.v.size();
+		// (a level that a compaction reads needs its record: the set keeps one for a level without)
+		if(const int cs = v.P.derived.compact_set_of(CRTHIP_COMPACT_LOD, k); blob && !lv.counts && cs >= 0 && v.S.compact[cs] != ~0ull)
+			l.counts = SP(v.S.compact[cs] + compact_layout_of(v.P, v.P.derived.compact.set[cs]).src_record);
 		if(blob) {
 			pl.lod_blob_ids.v.push_back(id);
 			pl.lod_lds = std::max(pl.lod_lds, (uint32_t)(lod_table_slots(v.nvert, v.nface)*4));
@@ -552,6 +556,8 @@ void Planner::cloud_lod_jobs(const BlobView &v) {
 		c.remap = lv.remap; c.points = lv.points; c.weight = lv.weight; c.chunks = lv.chunks; c.counts = lv.counts;
 		c.nvert = v.nvert; c.shift = lv.shift; c.chunk_points = lb.chunk_points;
 		const uint32_t id = (uint32_t)pl.cloud_lod.v.size();
+		if(const int cs = v.P.derived.compact_set_of(CRTHIP_COMPACT_CLOUD_LOD, k); blob && !lv.counts && cs >= 0 && v.S.compact[cs] != ~0ull)
+			c.counts = SP(v.S.compact[cs] + compact_layout_of(v.P, v.P.derived.compact.set[cs]).src_record);   // (as lod_jobs)
 		if(blob) {
 			pl.cloud_lod_blob_ids.v.push_back(id);
 			pl.cloud_lod_lds = std::max(pl.cloud_lod_lds, (uint32_t)(weld_slots(v.nvert)*4));
@@ -569,6 +575,83 @@ void Planner::cloud_lod_jobs(const BlobView &v) {
 			}
 		}
 		pl.cloud_lod.v.push_back(c);
+	}
+}
+
+// compaction: crthip_batch_bind_compact.  A job a MESH set: its id list where its source leaves it - the index where the automaton does, the welded
+// index, a level's index with the level's record, which lod_jobs has just given a job -, the set's arrays, and in scratch what it lacks: a record,
+// an order for its gathers, beyond compact_blob a newid for its index, the mask - zeroed by ONE FillJob in stage E, so that a second decode starts
+// clean - and a word a block of vertices.  And a job a GATHER of every set: the source's own buffer as bound, the set's order (a cloud's: its level's
+// points) and the record `used` is read from (a cloud's: its level's `cells`).  (The bind call checked all of it)
+void Planner::compact_jobs(const BlobView &v) {
+	const crthip_compact_binding &cb = v.P.derived.compact;
+	std::string why;
+	if(const int err = compact_binding_error(v.P, &cb, why)) { v.P.host_status = err; return; }
+	for(uint32_t s = 0; s < cb.sets; s++) if(v.S.compact[s] == ~0ull) { v.P.host_status = CRTHIP_E_ARGUMENT; return; }
+	// the record of a named level that has none and whose job keeps none: in the scratch of the FIRST set that names the level (lod_jobs, cloud_lod_jobs)
+	auto level_record = [&](uint32_t source, uint32_t level) {
+		const int cs = v.P.derived.compact_set_of(source, level);
+		return (const uint32_t *)SP(v.S.compact[cs] + compact_layout_of(v.P, cb.set[cs]).src_record);
+	};
+	for(uint32_t s = 0; s < cb.sets; s++) {
+		const crthip_compact_set &t = cb.set[s];
+		const uint64_t S = v.S.compact[s];
+		const CompactScratchLayout lay = compact_layout_of(v.P, t);
+		const bool cloud = t.source == CRTHIP_COMPACT_CLOUD_LOD, clip_v = t.order || t.ngather;
+		const uint32_t *order = t.order, *count_rec = nullptr;
+		void *rec = t.counts ? (void *)t.counts : (void *)SP(S + lay.record);
+		if(cloud) {
+			const crthip_cloud_lod_level &lv = v.P.derived.cloud_lod.level[t.level];
+			order = lv.points;
+			// (the level's record: the caller's, cloud_lod_jobs' in scratch beyond weld_in_blob, or this set's)
+			count_rec = lv.counts ? (const uint32_t *)lv.counts : weld_in_blob(v.nvert) ? level_record(t.source, t.level)
+				: (const uint32_t *)SP(v.S.cloud_lod[t.level] + cloud_lod_scratch_layout(v.nvert).record);
+		} else {
+			CompactJob c{};
+			const Faces f = faces_of(v.i);
+			if(t.source == CRTHIP_COMPACT_INDEX) { c.src = f.p; c.src_u16 = f.u16; }
+			else if(t.source == CRTHIP_COMPACT_WELD) c.src = v.P.derived.weld.index;
+			else {
+				const crthip_lod_level &lv = v.P.derived.lod.level[t.level];
+				c.src = lv.index;
+				c.src_rec = lv.counts ? (const uint32_t *)lv.counts : lod_in_blob(v.nvert, v.nface) ? level_record(t.source, t.level)
+					: (const uint32_t *)SP(v.S.lod[t.level] + lod_scratch_layout(v.nvert, v.nface).record);
+			}
+			const bool blob = compact_in_blob(v.nvert, v.nface);
+			if(!order && t.ngather) order = (const uint32_t *)SP(S + lay.order);
+			c.newid = t.newid; c.order = (uint32_t *)order; c.index = t.index; c.counts = rec;
+			c.nface = v.nface; c.nvert = v.nvert; c.vcap = t.vertex_capacity; c.icap = t.index_capacity; c.clip_v = clip_v;
+			const uint32_t id = (uint32_t)pl.compact.v.size();
+			if(blob) pl.compact_blob_ids.v.push_back(id);
+			else {
+				if(!c.newid && t.index) c.newid = (uint32_t *)SP(S + lay.newid);
+				c.mask = (uint32_t *)SP(S + lay.mask); c.blocks = (uint32_t *)SP(S + lay.blocks);
+				zero_fill(S + lay.mask, lay.mask_bytes);
+				pl.compact_big_ids.v.push_back(id);
+				c.vblock0 = (uint32_t)pl.compact_vblock_job.v.size();
+				push_blocks(pl.compact_vblock_job, id, compact_vblocks(v.nvert));
+				c.cblock0 = (uint32_t)pl.compact_cblock_job.v.size();
+				push_blocks(pl.compact_cblock_job, id, compact_cblocks(v.nface));
+			}
+			pl.compact.v.push_back(c);
+			count_rec = (const uint32_t *)rec;
+		}
+		// (a cloud set's record is stored by its first gather's first workgroup: a set without gathers gets a job of no bytes for it)
+		for(uint32_t q = 0; q < t.ngather || (cloud && q == 0 && t.counts); q++) {
+			CompactGatherJob g{};
+			g.order = order; g.count_rec = count_rec; g.cloud_rec = cloud && q == 0 && t.counts ? rec : nullptr;
+			g.vcap = t.vertex_capacity; g.nvert = v.nvert; g.clip_v = clip_v;
+			if(q < t.ngather) {
+				const CompactSource src = compact_source_of(v.P, t.gather[q].source);
+				g.src = (const uint8_t *)src.buffer; g.dst = (uint8_t *)t.gather[q].dst;
+				g.E = src.E; g.sstride = src.stride; g.dstride = t.gather[q].dst_stride ? t.gather[q].dst_stride : src.E;
+				g.unit = compact_unit((uintptr_t)g.src, (uintptr_t)g.dst, g.E, g.sstride, g.dstride);
+			}
+			const uint32_t id = (uint32_t)pl.compact_gather.v.size();
+			g.block0 = (uint32_t)pl.compact_gblock_job.v.size();
+			push_blocks(pl.compact_gblock_job, id, compact_gather_blocks(v.nvert, g.vcap, g.E, g.unit));
+			pl.compact_gather.v.push_back(g);
+		}
 	}
 }
 

@@ -254,6 +254,13 @@ void Planner::derived() {
 	by_ids("cloud_lod_offsets", k_cloud_lod_offsets, LOD_THREADS, 0, pl.cloud_lod, pl.cloud_lod_big_ids);
 	by_ids("cloud_lod_scatter", k_cloud_lod_scatter, LOD_THREADS, 0, pl.cloud_lod, pl.cloud_lod_vblock_job);
 	by_ids("cloud_lod_chunks", k_cloud_lod_chunks, LOD_THREADS, 0, pl.cloud_lod, pl.cloud_lod_cblock_job);
+	// compaction: a job a mesh set; every id list it reads - the index, the welded index, a level's index with its record - is final here
+	by_ids("compact_blob", k_compact_blob, COMPACT_THREADS, 0, pl.compact, pl.compact_blob_ids);
+	by_ids("compact_mark", k_compact_mark, COMPACT_THREADS, 0, pl.compact, pl.compact_cblock_job);
+	by_ids("compact_count", k_compact_count, COMPACT_THREADS, 0, pl.compact, pl.compact_vblock_job);
+	by_ids("compact_offsets", k_compact_offsets, COMPACT_THREADS, 0, pl.compact, pl.compact_big_ids);
+	by_ids("compact_place", k_compact_place, COMPACT_THREADS, 0, pl.compact, pl.compact_vblock_job);
+	by_ids("compact_index", k_compact_index, COMPACT_THREADS, 0, pl.compact, pl.compact_cblock_job);
 }
 // the scratch path's finishers: k_dequant, and where it would sit the kernels of CRTHIP_BIND_QUANTIZED
 void Planner::finish() {
@@ -261,6 +268,8 @@ void Planner::finish() {
 	by_ids("quant_out_blob", k_quant_out_blob, 256, 0, pl.quant, pl.quant_blob_ids);
 	by_ids("quant_range", k_quant_range, 256, 0, pl.quant, pl.quant_block_job);
 	by_ids("quant_store", k_quant_store, 256, 0, pl.quant, pl.quant_block_job);
+	// compaction's gathers: behind every kernel that writes a final vertex byte (dequantisation, normals, tangents and the quantised stores above)
+	by_ids("compact_gather", k_compact_gather, COMPACT_THREADS, 0, pl.compact_gather, pl.compact_gblock_job);
 }
 
 int Planner::launch(uint32_t phases, const Carry *carry) {

@@ -62,7 +62,11 @@ extern "C" {
                                      crthip_lod_binding, crthip_batch_bind_lod, crthip_lod_model (three structs and two new calls,
                                      nothing else: the number stays 6); CRTHIP_CLOUD_LOD_MAX_LEVELS, crthip_cloud_lod_counts,
                                      crthip_cloud_chunk, crthip_cloud_lod_level, crthip_cloud_lod_binding, crthip_batch_bind_cloud_lod,
-                                     crthip_cloud_lod_model (four structs and two new calls, nothing else: the number stays 6) */
+                                     crthip_cloud_lod_model (four structs and two new calls, nothing else: the number stays 6);
+                                     CRTHIP_COMPACT_MAX_SETS, CRTHIP_COMPACT_MAX_GATHERS, CRTHIP_NO_VERTEX, CRTHIP_COMPACT_*,
+                                     crthip_compact_counts, crthip_compact_gather, crthip_compact_set, crthip_compact_binding,
+                                     crthip_batch_bind_compact, crthip_compact_model_gather, crthip_compact_model (five structs and two
+                                     new calls, nothing else: the number stays 6) */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -608,6 +612,86 @@ typedef struct crthip_cloud_lod_binding {
  * launch nothing new; crthip_batch_bind_lod and the other derived bindings keep refusing a point cloud.
  * Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host, the crt::Decoder facade or the veneers. */
 int crthip_batch_bind_cloud_lod(crthip_batch *b, uint32_t i, const crthip_cloud_lod_binding *l);
+
+/* COMPACTION: a level's own vertex buffers.  Every derived binding above ends in ids into the blob's unchanged, full-size vertex arrays; this
+ * one renumbers the vertices an id list uses to 0..used-1, in vertex order, and copies the blob's FINAL vertex outputs of those vertices into
+ * small contiguous arrays, on the GPU in the decode call (kernels compact_blob, and compact_mark, compact_count, compact_offsets,
+ * compact_place, compact_index, and compact_gather in crthip_kernel_times; csrc/compact.h has the source the kernels and the test hook share).
+ * It is meshopt_optimizeVertexFetchRemap's job in ascending order followed by meshopt_remapVertexBuffer's.  Integer and byte work only; every
+ * byte is defined exactly, for any execution order.
+ * A binding holds 1..CRTHIP_COMPACT_MAX_SETS sets; a set is one independent job and names a SOURCE, whose words are src[k]:
+ *   CRTHIP_COMPACT_INDEX      the blob's final index (bound as uint32 or uint16, or unbound), k < 3*F with F = nface
+ *   CRTHIP_COMPACT_WELD       the `index` of the blob's crthip_batch_bind_weld, F = nface
+ *   CRTHIP_COMPACT_LOD        the `index` of level `level` of the blob's crthip_batch_bind_lod, F = that level's `faces`, read on the device
+ *   CRTHIP_COMPACT_CLOUD_LOD  the `points` of level `level` of the blob's crthip_batch_bind_cloud_lod (a point cloud; see below)
+ * For the three mesh sources:
+ * vertex v < nvert is USED if some src[k] == v.  An id >= nvert is compared and never used as an address.
+ * newid[v] (optional, nvert words) = the number of used u < v if v is used, else CRTHIP_NO_VERTEX.
+ * order[j] (optional), j < used = the v with newid[v] == j: strictly ascending.
+ * index[k] (optional), k < 3*F = newid[src[k]] if src[k] < nvert, else CRTHIP_NO_VERTEX.
+ * counts (optional device record) = {vertices: nvert, used, faces: F, clipped}.  There is no host record, as with the weld.
+ * For CRTHIP_COMPACT_CLOUD_LOD: used is the level's `cells` and order IS the level's `points`; newid, order and index must be NULL; the record
+ * ({nvert, cells, 0, clipped}) and the gathers are all that is produced.
+ * GATHERS: up to CRTHIP_COMPACT_MAX_GATHERS a set.  A gather names one of the blob's vertex outputs - attribute k of crthip_batch_info's
+ * order, CRTHIP_COMPACT_COMPUTED_NORMALS or CRTHIP_COMPACT_COMPUTED_TANGENTS -, a DEVICE dst and a dst_stride S (0: packed, S = E).  The
+ * element size E and its alignment A follow from the source's own binding: generic FLOAT 4*N and 4; generic CRTHIP_BIND_QUANTIZED 2*N and 2;
+ * normal FLOAT 12 and 4; normal INT16 6 and 2; colour out_components and 1; tangents FLOAT 16 and 4; tangents INT16 8 and 2.  For
+ * j < min(used, vertex_capacity) the E bytes at dst + j*S equal the E bytes of vertex order[j] in the source's buffer (packed or strided) at
+ * the end of the decode.  With a stride only those E bytes are written, so several gathers of a set may fill one interleaved record.  dst
+ * overlapping a source is the caller's error and is not checked.
+ * CAPACITIES CLIP, they do not fail: vertex_capacity (records of order and of every gather's dst) and index_capacity (words of index) may be
+ * any value.  order[j] and a gather's record j are written for j < min(used, vertex_capacity) only, index[k] for k < min(3*F, index_capacity)
+ * only; nothing behind a capacity is ever touched.  clipped = 1 if used > vertex_capacity in a set with an order or a gather, or
+ * 3*F > index_capacity in a set with an index; else 0.  used and faces are always the true values; the decode's status does not change.
+ * Nothing beyond the bytes named is written, and no other output changes. */
+#define CRTHIP_COMPACT_MAX_SETS 4
+#define CRTHIP_COMPACT_MAX_GATHERS 8
+#define CRTHIP_NO_VERTEX 0xFFFFFFFFu
+enum { CRTHIP_COMPACT_INDEX = 0, CRTHIP_COMPACT_WELD = 1, CRTHIP_COMPACT_LOD = 2, CRTHIP_COMPACT_CLOUD_LOD = 3 };
+#define CRTHIP_COMPACT_COMPUTED_NORMALS 0xFFFFFFFEu   /* a gather's source: what crthip_batch_bind_computed_normals bound */
+#define CRTHIP_COMPACT_COMPUTED_TANGENTS 0xFFFFFFFDu  /* ... and crthip_batch_bind_computed_tangents */
+typedef struct crthip_compact_counts { uint32_t vertices, used, faces, clipped; } crthip_compact_counts;
+typedef struct crthip_compact_gather {
+	void *dst;                         /* DEVICE, aligned to A, room for vertex_capacity records of stride S */
+	uint32_t source;                   /* an attribute number, or CRTHIP_COMPACT_COMPUTED_NORMALS / _TANGENTS */
+	uint32_t dst_stride;               /* 0: packed; else at least E and a multiple of A */
+} crthip_compact_gather;
+typedef struct crthip_compact_set {
+	uint32_t *newid;                   /* optional DEVICE array, 4-byte aligned, room for newid_capacity words; or NULL */
+	uint32_t *order;                   /* optional DEVICE array, 4-byte aligned, room for vertex_capacity words; or NULL */
+	uint32_t *index;                   /* optional DEVICE array, 4-byte aligned, room for index_capacity words; or NULL */
+	crthip_compact_counts *counts;     /* optional DEVICE record: 16 bytes, 16-byte aligned; or NULL.  There is no host record */
+	uint32_t newid_capacity;           /* words of newid: at least nvert when newid is given */
+	uint32_t vertex_capacity;          /* records of order and of every gather's dst: any value (it clips) */
+	uint32_t index_capacity;           /* words of index: any value (it clips) */
+	uint32_t source;                   /* CRTHIP_COMPACT_INDEX, _WELD, _LOD or _CLOUD_LOD */
+	uint32_t level;                    /* the level of a _LOD or _CLOUD_LOD source; else 0 */
+	uint32_t ngather;                  /* 0..CRTHIP_COMPACT_MAX_GATHERS: gather[0..ngather) are read */
+	uint32_t reserved[2];              /* 0 */
+	crthip_compact_gather gather[CRTHIP_COMPACT_MAX_GATHERS];
+} crthip_compact_set;
+typedef struct crthip_compact_binding {
+	crthip_compact_set set[CRTHIP_COMPACT_MAX_SETS];
+	uint32_t sets;                     /* 1..CRTHIP_COMPACT_MAX_SETS: set[0..sets) are read */
+	uint32_t flags;                    /* 0 */
+	uint32_t reserved[2];              /* 0 */
+} crthip_compact_binding;
+/* Blob i's sets go to c's buffers in the decode.  Call it after crthip_batch_bind of blob i, after the weld, lod or cloud lod binding a set
+ * names and after the computed normals or tangents binding a gather names; c == NULL removes the binding.  The WHOLE binding is dropped by a
+ * later crthip_batch_bind of that blob, by crthip_batch_reset*, and by any later call that sets, replaces or removes a binding it names
+ * (crthip_batch_bind_weld, _lod, _cloud_lod, _computed_normals - which also drops the tangents -, _computed_tangents).  Every error is
+ * returned here, in this order, and nothing new can fail at decode time.
+ * CRTHIP_E_ARGUMENT: b NULL or i out of range; sets not in 1..CRTHIP_COMPACT_MAX_SETS, unknown flags, a reserved word of the binding not 0.
+ * Then per set, in set order, CRTHIP_E_ARGUMENT: an unknown source, or a reserved word of the set not 0; a mesh source on a point cloud or the
+ * cloud source on a mesh; the named weld binding missing or without `index`, the named lod or cloud lod level missing; for the cloud source
+ * any of newid, order, index not NULL; newid, order or index not 4-byte aligned, or counts not 16-byte aligned; newid given and
+ * newid_capacity < nvert; ngather > CRTHIP_COMPACT_MAX_GATHERS.  Then per gather of that set, in gather order: an attribute number out of
+ * range (CRTHIP_E_ARGUMENT); a source that is unbound or missing (CRTHIP_E_ARGUMENT); a generic source in an integer format or DOUBLE, or
+ * bound with CRTHIP_BIND_STREAM_VALUES - their buffers are upstream's in-place work arrays, not vertex records - (CRTHIP_E_FORMAT); dst NULL
+ * or not A-aligned, or dst_stride neither 0 nor at least E and a multiple of A (CRTHIP_E_ARGUMENT).
+ * crthip_last_error() names the blob, the set and the gather.  Blobs without the binding plan, upload, zero and launch nothing new.
+ * Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host, the crt::Decoder facade or the veneers. */
+int crthip_batch_bind_compact(crthip_batch *b, uint32_t i, const crthip_compact_binding *c);
 
 /* The record of attribute `attr` of blob i, bound with CRTHIP_BIND_QUANTIZED.  Valid after crthip_batch_sync of a decode: the kernels write
  * the records into the batch's pinned status block, beside the status words.  CRTHIP_E_ARGUMENT if that attribute was not bound
@@ -1316,6 +1400,22 @@ int crthip_lod_model(const int32_t *position, const void *index, uint32_t index_
  * of this one level at capacities of exactly nvert and ceil(nvert / K), in its order. */
 int crthip_cloud_lod_model(const int32_t *position, uint32_t nvert, uint32_t shift, uint32_t chunk_points, uint32_t *remap, uint32_t *points,
                            uint32_t *weight, crthip_cloud_chunk *chunks, crthip_cloud_lod_counts *counts, uint64_t *stats, int which, uint32_t seed);
+
+/* (test hook, no device needed)  ONE set of crthip_batch_bind_compact on the host: csrc/compact.h, the kernels' source, in their partition.
+ * src: the id list, 3*nface words (uint16 if src_u16), of which the first 3*faces are read - nface is the bound the grids are sized from,
+ * faces <= nface what the kernels read from the source's record (a LOD level's `faces`; nface itself for the other sources).  newid: nvert
+ * words or NULL; order: vertex_capacity words or NULL; index: index_capacity words or NULL; counts: the record, or NULL.  gathers: ngather
+ * records of host pointers - E bytes of vertex v at src + v*src_stride go to dst + j*dst_stride (a stride of 0: packed); the copy unit is
+ * chosen from them as the planner chooses it.  which 0: compact_blob, one workgroup with its mask where the kernel has LDS (nvert or nface
+ * beyond 8 192 is CRTHIP_E_LIMIT here; the decode sends such a set down the other path); which 1: compact_mark, compact_count,
+ * compact_offsets, compact_place, compact_index; both end with compact_gather.  which 2: a cloud set - src is the level's points (nface words
+ * of capacity, `faces` of them kept: used), newid, order and index NULL, compact_gather alone.  Workgroups and threads, and with them every
+ * atomic, are walked in an order shuffled by seed: the bytes do not depend on it.  CRTHIP_E_ARGUMENT: an unknown partition, a NULL src with
+ * nface > 0, faces > nface, ngather > CRTHIP_COMPACT_MAX_GATHERS, a gather with a NULL pointer, E == 0 or a stride below E. */
+typedef struct crthip_compact_model_gather { const void *src; void *dst; uint32_t E, src_stride, dst_stride, reserved; } crthip_compact_model_gather;
+int crthip_compact_model(const void *src, uint32_t src_u16, uint32_t nface, uint32_t faces, uint32_t nvert, uint32_t *newid, uint32_t *order,
+                         uint32_t *index, uint32_t vertex_capacity, uint32_t index_capacity, crthip_compact_counts *counts,
+                         const crthip_compact_model_gather *gathers, uint32_t ngather, int which, uint32_t seed);
 
 #ifdef __cplusplus
 }
