@@ -109,6 +109,25 @@ class WeldBinding(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+BVH_LEAF = 0xFFFFFFFF                                # CRTHIP_BVH_LEAF: a leaf's `right`
+NO_NODE = 0xFFFFFFFF                                 # CRTHIP_NO_NODE: the root's parent
+BVH_NODE_DTYPE = np.dtype([("min", np.int32, 3), ("left", np.uint32), ("max", np.int32, 3), ("right", np.uint32)])   # crthip_bvh_node, 32 bytes
+
+
+class BvhCounts(C.Structure):
+    """crthip_bvh_counts: a blob's nodes (2*nface - 1), its faces, the absent ones among them, and the tree's height in edges"""
+    _fields_ = [("nodes", C.c_uint32), ("faces", C.c_uint32), ("absent", C.c_uint32), ("height", C.c_uint32)]
+
+    def as_tuple(self):
+        return (self.nodes, self.faces, self.absent, self.height)
+
+
+class BvhBinding(C.Structure):
+    """crthip_bvh_binding: the device node array, the optional device parent and order arrays and counts record, the two capacities, the flags"""
+    _fields_ = [("nodes", C.c_void_p), ("parent", C.c_void_p), ("order", C.c_void_p), ("counts", C.c_void_p), ("node_capacity", C.c_uint32),
+                ("order_capacity", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 LOD_MAX_LEVELS = 4                                   # CRTHIP_LOD_MAX_LEVELS
 
 
@@ -417,6 +436,9 @@ def lib():
         L.crthip_batch_bind_lod.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(LodBinding)]
         L.crthip_batch_bind_cloud_lod.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(CloudLodBinding)]
         L.crthip_batch_bind_compact.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(CompactBinding)]
+        L.crthip_batch_bind_bvh.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BvhBinding)]
+        L.crthip_bvh_model.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BvhCounts),
+                                       C.c_int, C.c_uint32]
         L.crthip_compact_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                            C.c_uint32, C.POINTER(CompactCounts), C.POINTER(CompactModelGather), C.c_uint32, C.c_int, C.c_uint32]
         L.crthip_cloud_lod_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1185,6 +1207,30 @@ def weld_model(position: np.ndarray, index: np.ndarray, which: int = 0, seed: in
     return remap, windex, counts, (int(stats[0]), int(stats[1]))
 
 
+def bvh_model(position: np.ndarray, index: np.ndarray, which: int = 0, seed: int = 0, fill: int = 0xCD, with_parent: bool = True, with_order: bool = True):
+    """crthip_bvh_model: crthip_batch_bind_bvh on the host in the kernels' partition (which 0: bvh_blob; 1: bvh_boxes / _keys / the sort /
+    _tree / _refit; workgroups and threads, and so every atomic and every arrival, shuffled by seed).  position (nvert, 3) int32; index
+    (nface, 3) uint32 or uint16, an id >= nvert makes its face absent.  The arrays are made here at exactly 2*nface - 1 records, 2*nface - 1
+    words and nface words and filled with `fill` first.  Returns (nodes as BVH_NODE_DTYPE (2*nface - 1,), parent uint32 or None, order uint32
+    or None, BvhCounts)."""
+    pos = np.ascontiguousarray(position, dtype=np.int32).reshape(-1, 3)
+    idx = np.ascontiguousarray(index)
+    if idx.dtype != np.uint16:
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    idx = idx.reshape(-1, 3)
+    nf = len(idx)
+    raw = np.full(max(2 * nf - 1, 1) * 32 + 16, fill, np.uint8)
+    o = (-raw.ctypes.data) % 16                                     # (the hook asks for 16-byte aligned nodes)
+    nodes = raw[o:o + max(2 * nf - 1, 0) * 32].view(BVH_NODE_DTYPE)
+    parent = np.full(max(2 * nf - 1, 0), fill * 0x01010101, np.uint32) if with_parent else None
+    order = np.full(nf, fill * 0x01010101, np.uint32) if with_order else None
+    counts = BvhCounts()
+    _check(lib().crthip_bvh_model(_np_ptr(pos) if len(pos) else None, len(pos), _np_ptr(idx) if nf else None, int(idx.dtype == np.uint16), nf,
+                                  _np_ptr(nodes) if nf else None, _np_ptr(parent) if with_parent and nf else None,
+                                  _np_ptr(order) if with_order and nf else None, C.byref(counts), which, seed))
+    return nodes, parent, order, counts
+
+
 def lod_model(position: np.ndarray, index: np.ndarray, shift: int, which: int = 0, seed: int = 0, fill: int = 0xCD):
     """crthip_lod_model: one level of crthip_batch_bind_lod on the host in the kernels' partition (which 0: lod_blob; 1: lod_insert / _lookup /
     _faces / _keep / _offsets / _scatter; workgroups and threads, and so every atomic's order, shuffled by seed).  position (nvert, 3) int32;
@@ -1479,6 +1525,7 @@ class Batch:
         self._adjacency = {}                         # blob -> (AdjacencyBinding, (twin tensor, counts tensor or None) or None): applied again by rebind() too
         self._weld = {}                              # blob -> (WeldBinding, (remap tensor, index tensor or None, counts tensor or None) or None): applied again by rebind() too
         self._lod = {}                               # blob -> (LodBinding, a list of (remap tensor, index tensor, counts tensor or None) a level, or None): applied again by rebind() too
+        self._bvh = {}                               # blob -> (BvhBinding, (nodes tensor, parent tensor or None, order tensor or None, counts tensor or None) or None): applied again by rebind() too
         self._compact = {}                           # blob -> (CompactBinding, a list of dicts a set (newid, order, index, counts and the gathered arrays by name as tensors, "dtypes"), or None): applied again by rebind() too
         self._cloud_lod = {}                         # blob -> (CloudLodBinding, a list of (remap, points, weight or None, chunks or None, counts or None) tensors a level, or None): applied again by rebind() too
         self._interleaved = None
@@ -1526,7 +1573,7 @@ class Batch:
     def allocate_outputs(self, normal_format=FMT_FLOAT, color_components: Optional[int] = None, index16=False,
                          only: Optional[set] = None, fill: Optional[int] = None, computed_normals=False, quantized=(),
                          computed_tangents=False, tangent_format=FMT_FLOAT, meshlets=None, meshlet_bounds=False, adjacency=False, weld=False, lod=None,
-                         cloud_lod=None, compact=False):
+                         cloud_lod=None, compact=False, bvh=False):
         """Allocate every output of every blob inside ONE device buffer (torch.uint8) and bind them.
         Returns a list (per blob) of dicts name -> torch tensor view.
         computed_normals: every mesh blob WITHOUT a normal attribute gets a "normal" tensor of normal_format all the same, bound
@@ -1552,7 +1599,9 @@ class Batch:
         through crthip_batch_bind_cloud_lod; meshes are skipped; read them with cloud_lod(i) after sync().
         compact: every blob gets, through crthip_batch_bind_compact, one set a level bound by lod= or cloud_lod= (a mesh without levels: one
         set over its own index).  A mesh set has newid, order (nvert words each), index (3*nface words) and a device counts record; every
-        set gathers every vertex output bound above (eight at most) into packed arrays of nvert records; read them with compact(i) after sync()."""
+        set gathers every vertex output bound above (eight at most) into packed arrays of nvert records; read them with compact(i) after sync().
+        bvh: every mesh blob gets a node array of 2*nface - 1 records, a parent array of as many words, an order array of nface words and a
+        device counts record, placed behind all other arrays and bound through crthip_batch_bind_bvh; read them with bvh(i) after sync()."""
         if meshlet_bounds and meshlets is None:
             raise ValueError("allocate_outputs: meshlet_bounds needs meshlets=")
         import torch
@@ -1636,6 +1685,8 @@ class Batch:
                     sets.append((source, level) + arrays + (co, gl))
                 if sets:
                     kplan.append((i, sets))
+        bplan = [(i, info.nface, take((2 * info.nface - 1) * 32), take((2 * info.nface - 1) * 4), take(info.nface * 4), take(16))
+                 for i, info in enumerate(self.infos) if info.nface] if bvh else []
         total = max(off, 256)
         buf = torch.empty(total, dtype=torch.uint8, device=dev) if fill is None else torch.full((total,), fill, dtype=torch.uint8, device=dev)
         _torch_ready(dev)                            # (the fill runs on torch's stream; the decode on the context's own)
@@ -1646,6 +1697,11 @@ class Batch:
         index_ptrs = (C.c_void_p * max(len(self), 1))()
         index_fmt = np.full(max(len(self), 1), FMT_UINT32, dtype=np.uint32)
         outs = [dict() for _ in self.infos]
+        self._bvh = {}
+        for (i, nf, no, po, oo, co) in bplan:
+            nn = 2 * nf - 1
+            self._bvh[i] = (BvhBinding(base + no, base + po, base + oo, base + co, nn, nf, 0, 0),
+                            (buf[no:no + nn * 32], buf[po:po + nn * 4], buf[oo:oo + nf * 4], buf[co:co + 16]))
         self._compact = {}
         for (i, sets) in kplan:
             nv, nf = self.infos[i].nvert, self.infos[i].nface
@@ -1770,6 +1826,7 @@ class Batch:
         self._lod = {}
         self._cloud_lod = {}
         self._compact = {}
+        self._bvh = {}
         self._interleaved = metas
         self.outputs = [dict() for _ in self.infos]
         self.rebind()
@@ -1829,6 +1886,8 @@ class Batch:
             _check(lib().crthip_batch_bind_cloud_lod(self.handle, i, C.byref(cb)))
         for i, (kb, _) in self._compact.items():                # (... and, behind everything it names, its compaction)
             _check(lib().crthip_batch_bind_compact(self.handle, i, C.byref(kb)))
+        for i, (vb, _) in self._bvh.items():                    # (... and its BVH)
+            _check(lib().crthip_batch_bind_bvh(self.handle, i, C.byref(vb)))
 
     def bind(self, i: int, bindings: Sequence[AttrBinding], index_ptr: Optional[int] = None, index_format=FMT_UINT32):
         arr = (AttrBinding * max(len(bindings), 1))(*bindings)
@@ -1916,6 +1975,29 @@ class Batch:
         index = None if len(keep) < 2 or keep[1] is None else words(keep[1], self.infos[i].nface * 3)
         counts = None if len(keep) < 3 or keep[2] is None else tuple(int(x) for x in words(keep[2], 4))
         return remap, index, counts
+
+    def bind_bvh(self, i: int, binding: Optional[BvhBinding] = None, keep=None):
+        """crthip_batch_bind_bvh: blob i's BVH goes to the binding's device arrays (nodes at least 2*nface - 1 records of 32 bytes, the optional
+        parent as many words, the optional order at least nface words).  After bind() / rebind() of that blob, which drop it; None removes it.
+        keep: whatever owns the memory (device tensors), held with the binding - a tuple (nodes, parent or None, order or None, counts or
+        None) makes bvh(i) work."""
+        if binding is None:
+            self._bvh.pop(i, None)
+            _check(lib().crthip_batch_bind_bvh(self.handle, i, None))
+            return
+        _check(lib().crthip_batch_bind_bvh(self.handle, i, C.byref(binding)))
+        self._bvh[i] = (binding, keep)
+
+    def bvh(self, i: int):
+        """Blob i's BVH on the host: (nodes as BVH_NODE_DTYPE (2*nface - 1,), parent uint32 (2*nface - 1,) or None, order uint32 (nface,) or
+        None, the counts as a tuple (nodes, faces, absent, height) or None where the binding has no device record).  After sync(); for
+        bindings made by allocate_outputs(bvh=) or bind_bvh(keep=)."""
+        _, keep = self._bvh[i]
+        nf = self.infos[i].nface
+        raw = lambda t, n: t.cpu().numpy().view(np.uint8).reshape(-1)[:n].copy()   # noqa: E731
+        part = lambda k, n: None if len(keep) <= k or keep[k] is None else raw(keep[k], n * 4).view(np.uint32)   # noqa: E731
+        counts = part(3, 4)
+        return raw(keep[0], (2 * nf - 1) * 32).view(BVH_NODE_DTYPE), part(1, 2 * nf - 1), part(2, nf), None if counts is None else tuple(int(x) for x in counts)
 
     def bind_lod(self, i: int, binding: Optional[LodBinding] = None, keep=None):
         """crthip_batch_bind_lod: blob i's levels of detail go to the binding's device arrays (a level: remap at least nvert words, index at least

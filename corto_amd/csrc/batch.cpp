@@ -167,6 +167,7 @@ extern "C" int crthip_ctx_create(int device, crthip_ctx **out) {
 	   hipFuncSetAttribute((const void *)k_weld_blob, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WELD_BLOB_LDS_MAX) != hipSuccess ||
 	   hipFuncSetAttribute((const void *)k_lod_blob, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LOD_BLOB_LDS_MAX) != hipSuccess ||
 	   hipFuncSetAttribute((const void *)k_cloud_lod_blob, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WELD_BLOB_LDS_MAX) != hipSuccess ||
+	   hipFuncSetAttribute((const void *)k_bvh_blob, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bvh_blob_lds_bytes(BVH_BLOB_FACES)) != hipSuccess ||
 	   hipFuncSetAttribute((const void *)k_enc_topo_walk<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ENC_TOPO_LDS_MAX) != hipSuccess ||
 	   hipFuncSetAttribute((const void *)k_enc_tun_parse, hipFuncAttributeMaxDynamicSharedMemorySize,
 	   	(int)enc_parse_lds(ENC_TRIE_LDS_MAX)) != hipSuccess) {

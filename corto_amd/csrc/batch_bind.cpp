@@ -1,5 +1,5 @@
-// batch_bind.cpp — what a caller binds to a batch's blobs and what reads a decode's records back: crthip_batch_bind / _bind_all, the nine derived
-// outputs (computed normals, computed tangents, meshlets, meshlet bounds, adjacency, weld, levels of detail of meshes and of clouds, compaction: DerivedBindings, batch_internal.h), the quantised attributes' records and the
+// batch_bind.cpp — what a caller binds to a batch's blobs and what reads a decode's records back: crthip_batch_bind / _bind_all, the ten derived
+// outputs (computed normals, computed tangents, meshlets, meshlet bounds, adjacency, weld, levels of detail of meshes and of clouds, compaction, BVH: DerivedBindings, batch_internal.h), the quantised attributes' records and the
 // meshlet counts.  Every check of a binding is made here, in the order corto_hip.h lists its errors, so that a decode has nothing new to fail on.
 // No HIP call: a program without the runtime links these (tests/cpp/plan_dump.cpp).
 #include "batch_internal.h"
@@ -278,6 +278,23 @@ extern "C" int crthip_batch_bind_compact(crthip_batch *b, uint32_t i, const crth
 	std::string why;
 	if(const int err = compact_binding_error(P, c, why)) return fail(err, why + " (blob " + std::to_string(i) + ")");
 	P.derived.compact = *c;
+	b->dirty = true;
+	return CRTHIP_OK;
+}
+
+// The BVH (corto_hip.h has the contract).  Every check is made here, in the header's order; it reads no other binding's output and no other
+// binding reads its own, so no later call but a bind of the blob or a reset drops it
+extern "C" int crthip_batch_bind_bvh(crthip_batch *b, uint32_t i, const crthip_bvh_binding *v) {
+	if(!b || i >= b->blobs.size()) return fail(CRTHIP_E_ARGUMENT, "crthip_batch_bind_bvh: no such blob");
+	BlobPlan &P = b->blobs[i];
+	const std::string who = " (blob " + std::to_string(i) + ")";
+	if(!v) { P.derived.bvh = crthip_bvh_binding{}; b->dirty = true; return CRTHIP_OK; }
+	if(P.L.h.nface == 0) return fail(CRTHIP_E_ARGUMENT, "a BVH needs faces: a point cloud has none" + who);
+	if(const char *why = bvh_binding_error(v, P.L.h.nface)) return fail(CRTHIP_E_ARGUMENT, why + who);
+	// (what the weld asks of the position)
+	if(!generic_source_ok(P, attr_named(P, "position"), 3))
+		return fail(CRTHIP_E_NORMAL_NEEDS_POSITION, "a BVH needs a bound three-component \"position\" (bind the blob first)" + who);
+	P.derived.bvh = *v;
 	b->dirty = true;
 	return CRTHIP_OK;
 }

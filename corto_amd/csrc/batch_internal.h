@@ -33,6 +33,7 @@
 #include "lod.h"
 #include "cloud_lod.h"
 #include "compact.h"
+#include "bvh.h"
 
 using namespace corto_hip;
 
@@ -106,10 +107,11 @@ struct BlobScratch {
 	uint64_t lod[CRTHIP_LOD_MAX_LEVELS] = {~0ull, ~0ull, ~0ull, ~0ull};   // levels of detail (DerivedBindings::lod): a level's lod_scratch_layout block
 	uint64_t cloud_lod[CRTHIP_CLOUD_LOD_MAX_LEVELS] = {~0ull, ~0ull, ~0ull, ~0ull};   // a cloud's levels of detail (DerivedBindings::cloud_lod) beyond weld_in_blob: a level's cloud_lod_scratch_layout block
 	uint64_t compact[CRTHIP_COMPACT_MAX_SETS] = {~0ull, ~0ull, ~0ull, ~0ull};   // compaction (DerivedBindings::compact): a set's compact_scratch_layout block
+	uint64_t bvh = ~0ull;                                   // the BVH (DerivedBindings::bvh) of a blob beyond bvh_in_blob: bvh_scratch_layout's block
 	uint64_t cn_facen = ~0ull;                              // computed normals (DerivedBindings::normals) by the fused kernel without its face normals in LDS: AttrScratch::facen's counterpart
 	std::vector<AttrScratch> attr;
 	size_t nattr = 0;                                       // attr[0..nattr) are this decode's (the vector only grows)
-	void reset() { clers = pred = front_a = front_b = order = delayed = faces = progress = cn_facen = tan_acc = mlt = mlt_counts = adj = weld = ~0ull; for(uint64_t &l : lod) l = ~0ull; for(uint64_t &l : cloud_lod) l = ~0ull; for(uint64_t &l : compact) l = ~0ull; front_cap = 0; aux_groups = 0; nattr = 0; }
+	void reset() { clers = pred = front_a = front_b = order = delayed = faces = progress = cn_facen = tan_acc = mlt = mlt_counts = adj = weld = bvh = ~0ull; for(uint64_t &l : lod) l = ~0ull; for(uint64_t &l : cloud_lod) l = ~0ull; for(uint64_t &l : compact) l = ~0ull; front_cap = 0; aux_groups = 0; nattr = 0; }
 	void set_attrs(size_t n) { if(attr.size() < n) attr.resize(n); for(size_t k = nattr; k < n; k++) attr[k].reset();
 		if(n > nattr) nattr = n; }
 };
@@ -161,6 +163,9 @@ struct Plan {
 	// set, clouds' too, 256 copy units a block (k_compact_gather)
 	HostArr<CompactJob> compact; HostArr<uint32_t> compact_blob_ids, compact_big_ids, compact_vblock_job, compact_cblock_job;
 	HostArr<CompactGatherJob> compact_gather; HostArr<uint32_t> compact_gblock_job;
+	// crthip_batch_bind_bvh: blobs within bvh_in_blob by id (k_bvh_blob, bvh_lds the largest request among them), the others by id for the scan
+	// (k_bvh_sort_offsets), 256 faces a block (k_bvh_boxes, _keys, _tree, _refit) and a sort tile a block (k_bvh_sort_count, _scatter)
+	HostArr<BvhJob> bvh; HostArr<uint32_t> bvh_blob_ids, bvh_big_ids, bvh_fblock_job, bvh_tblock_job; uint32_t bvh_lds = 0;
 	bool meshlet_records = false;                           // a crthip_meshlet_counts a blob behind the quant records: a batch with a meshlet binding
 	uint32_t quant_records = 0;                             // records behind the status words: sum(nattr) of a batch with a quantised binding, else 0
 	// scratch regions (offsets)
@@ -193,14 +198,17 @@ struct Plan {
 	template <class F> void each_cloud_lod_array(F f) { f(cloud_lod); f(cloud_lod_blob_ids); f(cloud_lod_big_ids); f(cloud_lod_vblock_job); f(cloud_lod_cblock_job); }
 	// ... and of the compaction, behind them
 	template <class F> void each_compact_array(F f) { f(compact); f(compact_blob_ids); f(compact_big_ids); f(compact_vblock_job); f(compact_cblock_job); f(compact_gather); f(compact_gblock_job); }
+	// ... and of the BVH, behind them
+	template <class F> void each_bvh_array(F f) { f(bvh); f(bvh_blob_ids); f(bvh_big_ids); f(bvh_fblock_job); f(bvh_tblock_job); }
 	void reset() {                                          // keep every vector's capacity
 		each_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
 		each_optional_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
 		each_lod_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
 		each_cloud_lod_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
 		each_compact_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
+		each_bvh_array([](auto &a) { a.v.clear(); a.dev_off = 0; });
 		clers_groups = 0; topo_need.clear(); quant_records = 0; meshlet_waves = 0; meshlet_records = false;
-		topo_lds = topo_big_lds = normal_fused_lds = normal_computed_lds = tangent_lds = adjacency_lds = weld_lds = lod_lds = cloud_lod_lds = 0;
+		topo_lds = topo_big_lds = normal_fused_lds = normal_computed_lds = tangent_lds = adjacency_lds = weld_lds = lod_lds = cloud_lod_lds = bvh_lds = 0;
 		zero_begin = zero_end = tables_off = tun_partial_off = unpack_partial_off = cloud_partial_off = 0;
 		facen_off = cnt_off = cursor_off = bnd_off = start_off = flag_off = slot_off = adj_off = nscan_partial_off = 0;
 		jobs_begin = jobs_bytes = 0; est_nvert = est_nface = 0; delta16_lds = 0;
@@ -288,6 +296,7 @@ struct DerivedBindings {
 	crthip_lod_binding lod{};              // crthip_batch_bind_lod: lod.levels != 0 - where the blob's levels of detail go (reads the integer positions and the index)
 	crthip_cloud_lod_binding cloud_lod{};  // crthip_batch_bind_cloud_lod: cloud_lod.levels != 0 - where a cloud's levels of detail go (reads the integer positions)
 	crthip_compact_binding compact{};      // crthip_batch_bind_compact: compact.sets != 0 - where the blob's compact sets go (reads other bindings' outputs: the functions below)
+	crthip_bvh_binding bvh{};              // crthip_batch_bind_bvh: bvh.nodes != null - where the blob's BVH goes (reads the integer positions and the index)
 	void clear() { *this = DerivedBindings{}; }       // a bind (and a blob adopted by a fill): all of them read what it binds
 	// a normals call: the tangents' normal source may change; a compaction that gathers either goes with them
 	void normals_change() { tangents = Binding{}; if(compact_gathers(CRTHIP_COMPACT_COMPUTED_NORMALS) || compact_gathers(CRTHIP_COMPACT_COMPUTED_TANGENTS)) compact = crthip_compact_binding{}; }
@@ -425,6 +434,9 @@ static inline bool binds_cloud_lod(const BlobPlan &P) { return P.derived.cloud_l
 // compaction (crthip_batch_bind_compact): a job a mesh set - one within compact_in_blob takes k_compact_blob, the others the five kernels over
 // scratch - and a job a gather of every set (compact.h)
 static inline bool binds_compact(const BlobPlan &P) { return P.derived.compact.sets != 0; }
+
+// the BVH (crthip_batch_bind_bvh): a blob within bvh_in_blob takes k_bvh_blob, the others the kernels over scratch (bvh.h)
+static inline bool binds_bvh(const BlobPlan &P) { return P.derived.bvh.nodes && P.L.h.nface > 0; }
 
 // where the derived outputs and the estimated normals take their inputs.  An attribute by name: the last one of that name, or -1
 static inline int attr_named(const BlobPlan &P, const char *name) {
@@ -577,6 +589,6 @@ struct Planner {
 	bool inverse_job(const BlobView &v, size_t k, void *values, uint32_t N, bool para, uint8_t is_u8, bool hand_i16);
 	void stored_normal_job(const BlobView &v, size_t k, bool hand_i16); void quant_job(const BlobView &v, size_t k); void dequant_job(const BlobView &v, size_t k);
 	bool estimated_normal_tail(const BlobView &v, NormalJob &n, HostArr<uint32_t> &fused_ids, uint32_t &fused_lds, uint64_t facen);
-	bool computed_normal_job(const BlobView &v); bool tangent_job(const BlobView &v); void meshlet_jobs(const BlobView &v); void weld_jobs(const BlobView &v); void adjacency_jobs(const BlobView &v); void lod_jobs(const BlobView &v); void cloud_lod_jobs(const BlobView &v); void compact_jobs(const BlobView &v);
+	bool computed_normal_job(const BlobView &v); bool tangent_job(const BlobView &v); void meshlet_jobs(const BlobView &v); void weld_jobs(const BlobView &v); void adjacency_jobs(const BlobView &v); void lod_jobs(const BlobView &v); void cloud_lod_jobs(const BlobView &v); void compact_jobs(const BlobView &v); void bvh_jobs(const BlobView &v);
 };
 

@@ -318,6 +318,22 @@ struct CompactGatherJob {
 };
 static_assert(sizeof(CompactJob) == 96 && sizeof(CompactGatherJob) == 72, "decode job layout");
 
+// a blob bound with crthip_batch_bind_bvh (k_bvh.hip, bvh.h): the integer positions and the index -> the caller's nodes, its parent and order
+// arrays and the blob's record.  A blob within bvh_in_blob needs nothing else; the others keep bvh_scratch_layout's block in scratch
+struct BvhJob {
+	const int32_t *position;       // nvert*3 delta-decoded integers (the caller's buffer or scratch)
+	const void *index;             // nface*3 u32 or, with index_u16, u16 (the caller's buffer or scratch)
+	void *nodes;                   // the binding's crthip_bvh_node array: 2*nface - 1 records are written
+	uint32_t *parent;              // 2*nface - 1 words: the binding's, or (bigger blobs only) scratch; null: none wanted
+	uint32_t *order;               // the binding's nface words; null: none wanted
+	void *counts;                  // crthip_bvh_counts in DEVICE memory: the binding's; null: none wanted
+	uint8_t *scratch;              // bigger blobs: the block, whose first zero_bytes (the extent, the arrival counters) one FillJob zeroes
+	uint32_t nface, nvert;
+	uint32_t fblock0, tblock0;     // first block of this job in the two block -> job maps (256 faces a block; a sort tile a block)
+	uint8_t index_u16, pad[7];
+};
+static_assert(sizeof(BvhJob) == 80, "decode job layout");
+
 // the layout the kernels read, pinned (TopoJob's size is performance-critical: TOPO_OPT_PROGRESS above)
 static_assert(sizeof(TunStream) == 64 && sizeof(FillJob) == 16 && sizeof(TopoJob) == 136 && sizeof(UnpackJob) == 56 && sizeof(DeltaJob) == 96 &&
               sizeof(CloudJob) == 24 && sizeof(NormalJob) == 104 && sizeof(DequantJob) == 64 && sizeof(QuantOutJob) == 72 && sizeof(TangentJob) == 80 &&

@@ -121,6 +121,19 @@ __global__ void k_compact_place(const CompactJob *jobs, const uint32_t *block_jo
 __global__ void k_compact_index(const CompactJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 __global__ void k_compact_gather(const CompactGatherJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 
+// k_bvh.hip (crthip_batch_bind_bvh; bvh.h has the method and both partitions): blobs of up to 4 096 faces by one workgroup each from an id
+// list, with bvh_blob_lds_bytes(nface) bytes of dynamic LDS (the launch asks for the largest among them); bigger ones 256 faces a block from a
+// block -> job map (boxes, keys, tree, refit), a sort tile a block from a second map (sort_count, sort_scatter: four passes, `pass` says which)
+// and one workgroup a blob from an id list (sort_offsets)
+__global__ void k_bvh_blob(const BvhJob *jobs, const uint32_t *job_ids, uint32_t njobs);
+__global__ void k_bvh_boxes(const BvhJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_bvh_keys(const BvhJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_bvh_sort_count(const BvhJob *jobs, const uint32_t *block_job, uint32_t nblocks, uint32_t pass);
+__global__ void k_bvh_sort_offsets(const BvhJob *jobs, const uint32_t *job_ids, uint32_t njobs);
+__global__ void k_bvh_sort_scatter(const BvhJob *jobs, const uint32_t *block_job, uint32_t nblocks, uint32_t pass);
+__global__ void k_bvh_tree(const BvhJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+__global__ void k_bvh_refit(const BvhJob *jobs, const uint32_t *block_job, uint32_t nblocks);
+
 // k_mesh.hip
 __global__ void k_topology(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);
 __global__ void k_topology_lds(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);

@@ -136,6 +136,10 @@ int Planner::carve() {
 		const BlobPlan &P = b->blobs[i];
 		if(binds_compact(P)) for(uint32_t k = 0; k < P.derived.compact.sets && k < CRTHIP_COMPACT_MAX_SETS; k++) bs[i].compact[k] = cv.take(compact_layout_of(P, P.derived.compact.set[k]).total, 16);
 	}
+	for(uint32_t i = 0; i < nblobs; i++) {                           // a BVH beyond one workgroup: the extent and the arrival counters (zeroed by a FillJob), the pairs twice, the sort's table, a parent array
+		const BlobPlan &P = b->blobs[i];
+		if(binds_bvh(P) && !bvh_in_blob(P.L.h.nface)) bs[i].bvh = cv.take(bvh_scratch_layout(P.L.h.nface, !P.derived.bvh.parent).total, 16);
+	}
 	if(est_v) {
 		pl.start_off = cv.take(est_v*4 + 16); pl.flag_off = cv.take(est_v*4 + 16); pl.slot_off = cv.take(est_v*4 + 16);
 		pl.adj_off = cv.take(est_f*12 + 16); pl.facen_off = cv.take(est_f*12 + 16);

@@ -98,6 +98,7 @@ void Planner::group() {
 	pl.each_lod_array([&](auto &arr) { if(!arr.v.empty()) arr.dev_off = cv.take(arr.v.size()*sizeof(arr.v[0]) + 16, 16); });
 	pl.each_cloud_lod_array([&](auto &arr) { if(!arr.v.empty()) arr.dev_off = cv.take(arr.v.size()*sizeof(arr.v[0]) + 16, 16); });
 	pl.each_compact_array([&](auto &arr) { if(!arr.v.empty()) arr.dev_off = cv.take(arr.v.size()*sizeof(arr.v[0]) + 16, 16); });
+	pl.each_bvh_array([&](auto &arr) { if(!arr.v.empty()) arr.dev_off = cv.take(arr.v.size()*sizeof(arr.v[0]) + 16, 16); });
 	pl.jobs_bytes = cv.take(0) - pl.jobs_begin;
 	pl.total = cv.take(0);
 }
@@ -138,6 +139,7 @@ int Planner::upload() {
 	for(auto &c : pl.cloud_lod.v) { resolve(c.position); resolve(c.counts); resolve(c.table); resolve(c.wacc); resolve(c.blocks); }
 	for(auto &c : pl.compact.v) { resolve(c.src); resolve(c.src_rec); resolve(c.newid); resolve(c.order); resolve(c.counts); resolve(c.mask); resolve(c.blocks); }
 	for(auto &g : pl.compact_gather.v) { resolve(g.order); resolve(g.count_rec); resolve(g.cloud_rec); }
+	for(auto &v : pl.bvh.v) { resolve(v.position); resolve(v.index); resolve(v.parent); resolve(v.scratch); }
 
 	// host image -> device (one copy)
 	stage = (uint8_t *)set.staging.p;
@@ -152,7 +154,7 @@ int Planner::upload() {
 		}
 	}
 	auto stage_array = [&](auto &arr) { if(!arr.v.empty()) memcpy(stage + (arr.dev_off - pl.jobs_begin), arr.v.data(), arr.v.size()*sizeof(arr.v[0])); };
-	pl.each_array(stage_array); pl.each_optional_array(stage_array); pl.each_lod_array(stage_array); pl.each_cloud_lod_array(stage_array); pl.each_compact_array(stage_array);
+	pl.each_array(stage_array); pl.each_optional_array(stage_array); pl.each_lod_array(stage_array); pl.each_cloud_lod_array(stage_array); pl.each_compact_array(stage_array); pl.each_bvh_array(stage_array);
 
 	return CRTHIP_OK;
 }

@@ -133,6 +133,7 @@ int Planner::jobs() {
 		if(binds_lod(v.P) && !v.P.host_status) lod_jobs(v);
 		if(binds_cloud_lod(v.P) && !v.P.host_status) cloud_lod_jobs(v);
 		if(binds_compact(v.P) && !v.P.host_status) compact_jobs(v);
+		if(binds_bvh(v.P) && !v.P.host_status) bvh_jobs(v);
 	}
 	return CRTHIP_OK;
 }
@@ -147,8 +148,8 @@ Planner::BlobView Planner::view_of(uint32_t i, size_t rec0) {
 	const bool tangents = computes_tangents(P);
 	// ... and so do meshlet bounds, behind the meshlet kernels: the integer positions last until k_dequant
 	const bool bounds = bounds_meshlets(P);
-	// ... and so do the weld, in front of the adjacency kernels, and the levels of detail behind them
-	const bool weld = binds_weld(P) || binds_lod(P);
+	// ... and so do the weld, in front of the adjacency kernels, and the levels of detail and the BVH behind them
+	const bool weld = binds_weld(P) || binds_lod(P) || binds_bvh(P);
 	// who turns the integer positions into floats: estimated normals read them as integers after K-DELTA, so the fused normal
 	// kernel does it as their last reader (pos_by_normal), the separate normal kernels leave it to k_dequant behind them, and
 	// without such normals K-DELTA does it on the way out of LDS like for every other attribute
@@ -653,6 +654,37 @@ void Planner::compact_jobs(const BlobView &v) {
 			pl.compact_gather.v.push_back(g);
 		}
 	}
+}
+
+// the BVH: crthip_batch_bind_bvh.  The integer positions as the weld takes them, the index where the automaton leaves it, the caller's arrays; a
+// blob of up to 4 096 faces needs no more.  The others keep their extent and their arrival counters - zeroed by ONE FillJob in stage E, so that a
+// second decode starts clean -, their pairs and the sort's table in scratch, and a parent array there if the binding has none.  (The bind call
+// checked all of it)
+void Planner::bvh_jobs(const BlobView &v) {
+	const crthip_bvh_binding &vb = v.P.derived.bvh;
+	const bool blob = bvh_in_blob(v.nface);
+	if(!generic_source_ok(v.P, v.pos_k, 3)) { v.P.host_status = CRTHIP_E_NORMAL_NEEDS_POSITION; return; }
+	if(bvh_binding_error(&vb, v.nface) || (!blob && v.S.bvh == ~0ull)) { v.P.host_status = CRTHIP_E_ARGUMENT; return; }
+	BvhJob j{};
+	j.position = ints_of(v.i, v.pos_k);
+	const Faces f = faces_of(v.i); j.index = f.p; j.index_u16 = f.u16;
+	j.nodes = vb.nodes; j.parent = vb.parent; j.order = vb.order; j.counts = vb.counts; j.nface = v.nface; j.nvert = v.nvert;
+	const uint32_t id = (uint32_t)pl.bvh.v.size();
+	if(blob) {
+		pl.bvh_blob_ids.v.push_back(id);
+		pl.bvh_lds = std::max(pl.bvh_lds, bvh_blob_lds_bytes(v.nface));
+	} else {
+		const BvhScratchLayout lay = bvh_scratch_layout(v.nface, !vb.parent);
+		j.scratch = (uint8_t *)SP(v.S.bvh);
+		if(!vb.parent) j.parent = (uint32_t *)SP(v.S.bvh + lay.parent);
+		zero_fill(v.S.bvh, lay.zero_bytes);
+		pl.bvh_big_ids.v.push_back(id);
+		j.fblock0 = (uint32_t)pl.bvh_fblock_job.v.size();
+		push_blocks(pl.bvh_fblock_job, id, bvh_fblocks(v.nface));
+		j.tblock0 = (uint32_t)pl.bvh_tblock_job.v.size();
+		push_blocks(pl.bvh_tblock_job, id, bvh_tiles(v.nface));
+	}
+	pl.bvh.v.push_back(j);
 }
 
 // adjacency: crthip_batch_bind_adjacency.  The index where the automaton leaves it - or, under CRTHIP_WELD_ADJACENCY, the welded index of the blob's

@@ -261,6 +261,17 @@ void Planner::derived() {
 	by_ids("compact_offsets", k_compact_offsets, COMPACT_THREADS, 0, pl.compact, pl.compact_big_ids);
 	by_ids("compact_place", k_compact_place, COMPACT_THREADS, 0, pl.compact, pl.compact_vblock_job);
 	by_ids("compact_index", k_compact_index, COMPACT_THREADS, 0, pl.compact, pl.compact_cblock_job);
+	// the BVH: one more reader of the integer positions (k_dequant runs behind) and of the final index
+	by_ids("bvh_blob", k_bvh_blob, BVH_THREADS, pl.bvh_lds, pl.bvh, pl.bvh_blob_ids);
+	by_ids("bvh_boxes", k_bvh_boxes, BVH_THREADS, 0, pl.bvh, pl.bvh_fblock_job);
+	by_ids("bvh_keys", k_bvh_keys, BVH_THREADS, 0, pl.bvh, pl.bvh_fblock_job);
+	for(uint32_t pass = 0; pass < BVH_PASSES; pass++) {                      // a stable LSD radix sort, 8 bits a pass
+		by_ids("bvh_sort_count", k_bvh_sort_count, BVH_THREADS, 0, pl.bvh, pl.bvh_tblock_job, pass);
+		by_ids("bvh_sort_offsets", k_bvh_sort_offsets, BVH_THREADS, 0, pl.bvh, pl.bvh_big_ids);
+		by_ids("bvh_sort_scatter", k_bvh_sort_scatter, BVH_THREADS, 0, pl.bvh, pl.bvh_tblock_job, pass);
+	}
+	by_ids("bvh_tree", k_bvh_tree, BVH_THREADS, 0, pl.bvh, pl.bvh_fblock_job);
+	by_ids("bvh_refit", k_bvh_refit, BVH_THREADS, 0, pl.bvh, pl.bvh_fblock_job);
 }
 // the scratch path's finishers: k_dequant, and where it would sit the kernels of CRTHIP_BIND_QUANTIZED
 void Planner::finish() {

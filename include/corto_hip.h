@@ -66,6 +66,8 @@ extern "C" {
                                      CRTHIP_COMPACT_MAX_SETS, CRTHIP_COMPACT_MAX_GATHERS, CRTHIP_NO_VERTEX, CRTHIP_COMPACT_*,
                                      crthip_compact_counts, crthip_compact_gather, crthip_compact_set, crthip_compact_binding,
                                      crthip_batch_bind_compact, crthip_compact_model_gather, crthip_compact_model (five structs and two
+                                     new calls, nothing else: the number stays 6); CRTHIP_BVH_LEAF, CRTHIP_NO_NODE, crthip_bvh_node,
+                                     crthip_bvh_counts, crthip_bvh_binding, crthip_batch_bind_bvh, crthip_bvh_model (three structs and two
                                      new calls, nothing else: the number stays 6) */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
@@ -692,6 +694,59 @@ typedef struct crthip_compact_binding {
  * crthip_last_error() names the blob, the set and the gather.  Blobs without the binding plan, upload, zero and launch nothing new.
  * Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host, the crt::Decoder facade or the veneers. */
 int crthip_batch_bind_compact(crthip_batch *b, uint32_t i, const crthip_compact_binding *c);
+
+/* A binary triangle BVH of the blob's faces, built on the GPU in the decode call (kernels bvh_blob, and bvh_boxes, bvh_keys, bvh_sort_count,
+ * bvh_sort_offsets, bvh_sort_scatter, bvh_tree, bvh_refit in crthip_kernel_times; csrc/bvh.h has the source the kernels and the hook share).
+ * It is the structure for spatial queries - ray casts, picking, collision, box and frustum queries, a software ray tracer's bottom level -
+ * and it is built from the INTEGER positions, so every byte below is defined exactly.
+ * p[v] is the delta-decoded INTEGER position of vertex v, as the weld reads it; the index is the blob's final one; F = nface >= 1.  A face
+ * is ABSENT if a corner is >= nvert (compared, never an address: only blobs whose topology failed have one); a face with two equal corners
+ * is an ordinary face.
+ * Box: bmin[f][c], bmax[f][c] = the signed minimum and maximum of component c over the three corners; an absent face has the EMPTY box,
+ *   min = INT32_MAX and max = INT32_MIN in every component - the identity of the union, on which every overlap test fails.
+ * Key: m[f][c] = (int32)(((int64)bmin[f][c] + bmax[f][c]) >> 1) (arithmetic); L[c], H[c] = the minimum and maximum of m[f][c] over the PRESENT
+ *   faces; E = max over c of (uint32)H[c] - (uint32)L[c]; k = max(0, bitlength(E) - 10); cell[f][c] = ((uint32)m[f][c] - (uint32)L[c]) >> k
+ *   (below 2^10); key[f] takes bit i of cell[f][0] at bit 3i + 2, of cell[f][1] at 3i + 1, of cell[f][2] at 3i, i in 0..9 (a 30-bit Morton
+ *   code); an absent face has key 0x80000000.  If no face is present, L and H play no part.
+ * Order: order[j] = the face of rank j when the faces are sorted by (key, f) ascending.
+ * Tree (Karras 2012, stated without the algorithm): leaf j holds face order[j], its code is c_j = ((uint64)key[order[j]] << 32) | j.  For a
+ *   range [a, b], a < b, let P = clz64(c_a ^ c_b); the split is the LARGEST m in [a, b - 1] with clz64(c_a ^ c_m) > P (clz64(0) = 64); the left
+ *   child covers [a, m], the right [m + 1, b]; a range of one is a leaf; the root covers [0, F - 1].
+ * Node ids: the root is node 0; an internal node reached as the LEFT child of a node with split m has id m, as the RIGHT child id m + 1; leaf
+ *   j is node F - 1 + j; for F == 1 the only node is leaf 0 at id 0.  The internal ids fill 0..F - 2 exactly, and the longest root-to-leaf
+ *   path has at most 64 edges.
+ * nodes[n], n < 2F - 1: an internal node's left and right are its children's node ids and its box is the union of theirs (the empty box over
+ *   absent faces only); a leaf's left is the face id, its right CRTHIP_BVH_LEAF, its box the face's.  A box is in grid units: the world box is
+ *   (float)min * q to (float)max * q with the position's one step q, as with the meshlet bounds.
+ * parent[n] (optional, 2F - 1 words) = the parent's node id, CRTHIP_NO_NODE for node 0.  order (optional, F words): what
+ *   meshopt_spatialSortTriangles is called for.  counts (optional device record) = {nodes: 2F - 1, faces: F, absent, height}; height is the
+ *   number of edges on the longest root-to-leaf path (0 for F == 1): a traversal stack of height + 1 entries suffices.  There is no host
+ *   record, as with the weld.  Nothing beyond these is written, and no other output of the blob changes, whatever the position's format.
+ * Chosen, not tuned: one workgroup builds a blob of up to 4 096 faces; bigger blobs sort in tiles of 2 048 faces, 8 bits a pass.
+ * Left out: a BVH of the welded index or of a LOD level (flags is kept for that), refitting an existing tree, wide (4- or 8-way) nodes, SAH
+ *   splits or treelet rotations, float boxes, point clouds. */
+#define CRTHIP_BVH_LEAF 0xFFFFFFFFu
+#define CRTHIP_NO_NODE 0xFFFFFFFFu
+typedef struct crthip_bvh_node { int32_t min[3]; uint32_t left; int32_t max[3]; uint32_t right; } crthip_bvh_node;
+typedef struct crthip_bvh_counts { uint32_t nodes, faces, absent, height; } crthip_bvh_counts;
+typedef struct crthip_bvh_binding {
+	crthip_bvh_node *nodes;            /* DEVICE array, 16-byte aligned, room for `node_capacity` records; 2*nface - 1 are written */
+	uint32_t *parent;                  /* optional DEVICE array, 4-byte aligned, room for `node_capacity` words; or NULL */
+	uint32_t *order;                   /* optional DEVICE array, 4-byte aligned, room for `order_capacity` words; or NULL */
+	crthip_bvh_counts *counts;         /* optional DEVICE record: 16 bytes, 16-byte aligned; or NULL.  There is no host record */
+	uint32_t node_capacity;            /* at least 2*nface - 1 */
+	uint32_t order_capacity;           /* with order: at least nface */
+	uint32_t flags;                    /* 0 */
+	uint32_t reserved;                 /* 0 */
+} crthip_bvh_binding;
+/* Blob i's BVH goes to v's buffers in the decode.  Call it after crthip_batch_bind of blob i; v == NULL removes the binding; a later
+ * crthip_batch_bind of that blob drops it, and so does crthip_batch_reset*.  It is independent of every other derived binding.  Every error
+ * is returned here, in this order, and nothing new can fail at decode time.
+ * CRTHIP_E_ARGUMENT: b NULL or i out of range; a point cloud; nodes NULL or not 16-byte aligned; parent or order not 4-byte aligned, or
+ * counts not 16-byte aligned; node_capacity < 2*nface - 1; order given and order_capacity < nface; flags != 0 or reserved != 0.
+ * CRTHIP_E_NORMAL_NEEDS_POSITION: by the weld's rule.  crthip_last_error() names the blob.  Blobs without the binding plan, upload, zero
+ * and launch nothing new.  Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host, the crt::Decoder facade or the veneers. */
+int crthip_batch_bind_bvh(crthip_batch *b, uint32_t i, const crthip_bvh_binding *v);
 
 /* The record of attribute `attr` of blob i, bound with CRTHIP_BIND_QUANTIZED.  Valid after crthip_batch_sync of a decode: the kernels write
  * the records into the batch's pinned status block, beside the status words.  CRTHIP_E_ARGUMENT if that attribute was not bound
@@ -1416,6 +1471,17 @@ typedef struct crthip_compact_model_gather { const void *src; void *dst; uint32_
 int crthip_compact_model(const void *src, uint32_t src_u16, uint32_t nface, uint32_t faces, uint32_t nvert, uint32_t *newid, uint32_t *order,
                          uint32_t *index, uint32_t vertex_capacity, uint32_t index_capacity, crthip_compact_counts *counts,
                          const crthip_compact_model_gather *gathers, uint32_t ngather, int which, uint32_t seed);
+
+/* (test hook, no device needed)  crthip_batch_bind_bvh on the host: csrc/bvh.h, the kernels' source, in their partition.  position: nvert*3
+ * int32, the delta-decoded integers; index: 3*nface ids (uint16 if index_u16), an id >= nvert makes its face absent; nodes: host memory,
+ * 2*nface - 1 records, 16-byte aligned; parent: 2*nface - 1 words or NULL; order: nface words or NULL; counts: the record, or NULL.
+ * which 0: bvh_blob, one workgroup with its arrays where the kernel has LDS (a blob beyond its limit - more than 4 096 faces - is
+ * CRTHIP_E_LIMIT here; the decode sends such a blob down the other path); which 1: bvh_boxes, bvh_keys, four passes of bvh_sort_count,
+ * bvh_sort_offsets and bvh_sort_scatter, bvh_tree, bvh_refit.  Workgroups and threads, and with them every atomic and every arrival, are
+ * walked in an order shuffled by seed: the bytes do not depend on it.  CRTHIP_E_ARGUMENT: an unknown partition, nface == 0, a NULL position
+ * with nvert > 0, a NULL index, nodes NULL or not 16-byte aligned. */
+int crthip_bvh_model(const int32_t *position, uint32_t nvert, const void *index, uint32_t index_u16, uint32_t nface, crthip_bvh_node *nodes,
+                     uint32_t *parent, uint32_t *order, crthip_bvh_counts *counts, int which, uint32_t seed);
 
 #ifdef __cplusplus
 }
