@@ -128,6 +128,21 @@ class BvhBinding(C.Structure):
                 ("order_capacity", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+CAST_ANY, CAST_FRONT = 1, 2                          # CRTHIP_CAST_ANY, CRTHIP_CAST_FRONT
+NO_FACE = 0xFFFFFFFF                                 # CRTHIP_NO_FACE
+CAST_MISS, CAST_HIT, CAST_RANGE, CAST_TREE = 0, 1, 2, 3   # crthip_cast_hit.status
+SEGMENT_DTYPE = np.dtype([("p", np.int32, 3), ("user0", np.uint32), ("q", np.int32, 3), ("user1", np.uint32)])   # crthip_segment, 32 bytes
+CAST_HIT_DTYPE = np.dtype([("status", np.uint32), ("face", np.uint32), ("side", np.uint32), ("reserved", np.uint32), ("num", np.uint64), ("den", np.uint64)])   # crthip_cast_hit, 32 bytes
+
+
+class CastSet(C.Structure):
+    """crthip_bvh_cast_set: the device nodes, quantised position, index, optional transform record, segments and hits; the base, the position's
+    stride, the counts, the index format, the flags"""
+    _fields_ = [("nodes", C.c_void_p), ("position", C.c_void_p), ("index", C.c_void_p), ("transform", C.c_void_p), ("segments", C.c_void_p),
+                ("hits", C.c_void_p), ("base", C.c_int32 * 3), ("pos_stride", C.c_uint32), ("nvert", C.c_uint32), ("nface", C.c_uint32),
+                ("index_format", C.c_uint32), ("nseg", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 LOD_MAX_LEVELS = 4                                   # CRTHIP_LOD_MAX_LEVELS
 
 
@@ -439,6 +454,9 @@ def lib():
         L.crthip_batch_bind_bvh.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BvhBinding)]
         L.crthip_bvh_model.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BvhCounts),
                                        C.c_int, C.c_uint32]
+        L.crthip_bvh_cast.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(CastSet)]
+        L.crthip_bvh_cast_model.argtypes = [C.POINTER(CastSet), C.c_void_p]
+        L.crthip_bvh_cast_model_stats.argtypes = [C.POINTER(CastSet), C.c_void_p, C.c_void_p]
         L.crthip_compact_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                            C.c_uint32, C.POINTER(CompactCounts), C.POINTER(CompactModelGather), C.c_uint32, C.c_int, C.c_uint32]
         L.crthip_cloud_lod_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1231,6 +1249,65 @@ def bvh_model(position: np.ndarray, index: np.ndarray, which: int = 0, seed: int
     return nodes, parent, order, counts
 
 
+def make_segments(p, q) -> np.ndarray:
+    """(n, 3) integer start and end points in grid units -> n crthip_segment records (SEGMENT_DTYPE), the user words 0"""
+    p = np.asarray(p, dtype=np.int64).reshape(-1, 3)
+    q = np.asarray(q, dtype=np.int64).reshape(-1, 3)
+    s = np.zeros(len(p), SEGMENT_DTYPE)
+    s["p"], s["q"] = p, q
+    return s
+
+
+def world_segments(p, q, transform) -> np.ndarray:
+    """World-space segments -> crthip_segment records in the grid of `transform` (a QuantTransform, or its step q as a float): a grid
+    coordinate g stands for the world coordinate float32(g) * q, as in crthip_quant_transform's contract, so a world coordinate w goes to
+    the nearest integer to float64(w) / float64(q), halves to the even one (numpy.rint), clipped to int32.  Nothing else rounds.  Whether a
+    segment is in a set's range is the cast's to say (CRTHIP_CAST_RANGE)."""
+    step = float(transform.q if isinstance(transform, QuantTransform) else transform)
+    g = lambda w: np.clip(np.rint(np.asarray(w, dtype=np.float64) / step), -2 ** 31, 2 ** 31 - 1).astype(np.int64)   # noqa: E731
+    return make_segments(g(p), g(q))
+
+
+def bvh_cast_model(nodes: np.ndarray, position: np.ndarray, index: np.ndarray, segments: np.ndarray, base=(0, 0, 0), flags: int = 0, transform=None,
+                   nvert: Optional[int] = None, fill: int = 0xCD, with_stats: bool = False, raw_set=None):
+    """crthip_bvh_cast_model: crthip_bvh_cast of one set on the host, csrc/bvh_cast.h as the kernel runs it.  nodes: BVH_NODE_DTYPE
+    (2*nface - 1,); position: uint16 (nvert, 3) packed, or a uint8 buffer (nvert, stride) whose first six bytes a row are the halfwords;
+    index (nface, 3) uint32 or uint16; segments: SEGMENT_DTYPE; transform: a QuantTransform (its base and `written` are read where the
+    kernel reads the device record) or None: `base`.  The hit array is made here at exactly nseg records and filled with `fill` first.
+    raw_set: a function that may change the CastSet before the call (the argument tests).  Returns CAST_HIT_DTYPE (nseg,), with
+    with_stats also (nodes taken, faces tested)."""
+    pos = np.ascontiguousarray(position)
+    if pos.dtype == np.uint16:
+        pos = pos.reshape(-1, 3); stride = 6
+    else:
+        pos = pos.view(np.uint8).reshape(len(pos), -1); stride = pos.shape[1]
+    idx = np.ascontiguousarray(index)
+    if idx.dtype != np.uint16:
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    idx = idx.reshape(-1, 3)
+    seg = np.ascontiguousarray(segments, dtype=SEGMENT_DTYPE)
+    nseg = len(seg)
+
+    def aligned(a, nbytes):                           # a 16-byte aligned copy of a's bytes
+        raw = np.empty(nbytes + 16, np.uint8)
+        o = (-raw.ctypes.data) % 16
+        v = raw[o:o + nbytes]
+        v[:] = np.frombuffer(a.tobytes(), np.uint8) if nbytes else 0
+        return v
+    nd, sg = aligned(np.ascontiguousarray(nodes), len(nodes) * 32), aligned(seg, nseg * 32)
+    hits = aligned(np.full(nseg * 32, fill, np.uint8), nseg * 32)
+    tr = aligned(np.frombuffer(bytes(transform), np.uint8), 48) if transform is not None else None
+    cs = CastSet(nd.ctypes.data if len(nd) else None, pos.ctypes.data if pos.size else None, idx.ctypes.data if idx.size else None,
+                 tr.ctypes.data if tr is not None else None, sg.ctypes.data if nseg else None, None, (C.c_int32 * 3)(*[int(b) for b in base]), 0 if stride == 6 else stride,
+                 len(pos) if nvert is None else nvert, len(idx), FMT_UINT16 if idx.dtype == np.uint16 else FMT_UINT32, nseg, flags, 0)
+    if raw_set is not None:
+        raw_set(cs)
+    stats = np.zeros(2, np.uint64)
+    _check(lib().crthip_bvh_cast_model_stats(C.byref(cs), hits.ctypes.data if nseg else None, _np_ptr(stats)))
+    out = hits.view(CAST_HIT_DTYPE).copy()
+    return (out, (int(stats[0]), int(stats[1]))) if with_stats else out
+
+
 def lod_model(position: np.ndarray, index: np.ndarray, shift: int, which: int = 0, seed: int = 0, fill: int = 0xCD):
     """crthip_lod_model: one level of crthip_batch_bind_lod on the host in the kernels' partition (which 0: lod_blob; 1: lod_insert / _lookup /
     _faces / _keep / _offsets / _scatter; workgroups and threads, and so every atomic's order, shuffled by seed).  position (nvert, 3) int32;
@@ -1430,6 +1507,12 @@ class Context:
         are adjacent in host memory - the views of two such buffers are two copies; beyond 8 runs the blobs are gathered (corto_hip.h)"""
         _check(lib().crthip_ctx_set_packed_host_blobs(self.handle, int(on)))
 
+    def bvh_cast(self, sets: Sequence[CastSet]):
+        """crthip_bvh_cast: every set's segments against its blob's BVH in one launch, asynchronously, behind everything this context has
+        enqueued (a decode included); sync() waits for it.  The caller keeps every array of the sets alive until then."""
+        arr = (CastSet * max(len(sets), 1))(*sets)
+        _check(lib().crthip_bvh_cast(self.handle, len(sets), arr))
+
     def sync(self):
         _check(lib().crthip_ctx_sync(self.handle))
 
@@ -1511,6 +1594,7 @@ class Batch:
         self._load_infos(n)
 
     def _load_infos(self, n):
+        self._quant_dev = None                       # (a create or a reset: crthip_batch_reset* drops the device transform records)
         self.infos = []
         for i in range(n):
             info = BlobInfo()
@@ -2109,6 +2193,47 @@ class Batch:
         """crthip_batch_bind_quant_transforms: a device array of sum(nattr) 48-byte records (16-byte aligned) that the decode fills for the
         quantised attributes, in bind_all's order; None or 0 removes it.  The caller keeps the memory alive."""
         _check(lib().crthip_batch_bind_quant_transforms(self.handle, C.c_void_p(ptr) if ptr else None))
+        self._quant_dev = ptr or None
+
+    def cast_set(self, i: int, segments, hits, nseg: int, flags: int = 0) -> CastSet:
+        """The crthip_bvh_cast_set of blob i, bound by allocate_outputs(bvh=True, quantized=("position",)): its kept node, position and
+        index tensors, `segments` and `hits` (device pointers, 16-byte aligned, nseg records).  The transform is the device record where
+        bind_quant_transforms gave one - then nothing here waits for the decode -, else quant_transform(i, "position")'s base (after sync())."""
+        info = self.infos[i]
+        pos, dt = self.outputs[i]["position"]
+        if dt != "u16" or i not in self._bvh:
+            raise ValueError("cast: blob %d needs allocate_outputs(bvh=True, quantized=(\"position\",))" % i)
+        idx, idt = self.outputs[i]["index"]
+        k = [a["name"] for a in info.attrs()].index("position")
+        cs = CastSet()
+        cs.nodes, cs.position, cs.index = self._bvh[i][1][0].data_ptr(), pos.data_ptr(), idx.data_ptr()
+        cs.segments, cs.hits, cs.nseg, cs.flags = segments, hits, nseg, flags
+        cs.nvert, cs.nface, cs.index_format = info.nvert, info.nface, FMT_UINT16 if idt == "u16" else FMT_UINT32
+        dev = getattr(self, "_quant_dev", None)
+        if dev:
+            cs.transform = dev + 48 * (sum(x.nattr for x in self.infos[:i]) + k)
+        else:
+            t = self.quant_transform(i, k)
+            cs.base[0], cs.base[1], cs.base[2] = t.base[0], t.base[1], t.base[2]
+            if not t.written:
+                raise ValueError("cast: blob %d has no quantised position (a span beyond 65535)" % i)
+        return cs
+
+    def cast(self, i: int, segments: np.ndarray, flags: int = 0) -> np.ndarray:
+        """Casts `segments` (SEGMENT_DTYPE, grid units: make_segments / world_segments) against blob i's BVH: uploads them, crthip_bvh_cast,
+        syncs the context, returns the hits (CAST_HIT_DTYPE).  For blobs bound by allocate_outputs(bvh=True, quantized=("position",))."""
+        import torch
+        seg = np.ascontiguousarray(segments, dtype=SEGMENT_DTYPE)
+        n = len(seg)
+        if not n:
+            return np.zeros(0, CAST_HIT_DTYPE)
+        dev = torch.device("cuda", self.ctx.device)
+        dseg = torch.from_numpy(seg.view(np.uint8).reshape(-1).copy()).to(dev)
+        dhit = torch.empty(n * 32, dtype=torch.uint8, device=dev)
+        _torch_ready(dev)                            # (the upload runs on torch's stream; the cast on the context's own)
+        self.ctx.bvh_cast([self.cast_set(i, dseg.data_ptr(), dhit.data_ptr(), n, flags)])
+        self.ctx.sync()
+        return dhit.cpu().numpy().view(CAST_HIT_DTYPE).copy()
 
     def host_outputs(self, i: int) -> Dict[str, np.ndarray]:
         """Copy blob i's outputs to the host as numpy arrays with the reference's dtypes."""

@@ -241,6 +241,8 @@ struct crthip_ctx {
 	crthip_splice_stats enc_splice{};                 // crthip_ctx_encode_splice_stats: the last crthip_encode_batch_to_device
 	int encode_topology = CRTHIP_TOPOLOGY_HOST;       // crthip_ctx_set_encode_topology: where crthip_encode_batch runs the CLERS topology pass
 	crthip_batch *last_decoded = nullptr;// whose intermediates the scratch block holds (crthip_batch_debug_read)
+	// crthip_bvh_cast: the call's job-table blocks, pinned and on the device, made by the first cast and rotated (bvh_cast.cpp)
+	struct CastState *cast = nullptr;
 	// crthip_decode_host: everything a one-blob decode with host buffers needs, kept from call to call (no hipMalloc / create in the
 	// steady state) and guarded by a mutex so that callers may share a context between threads
 	std::mutex host_mutex;
@@ -372,6 +374,7 @@ struct StatusWords {
 
 int harvest(crthip_ctx *ctx);     // wait for the batch in flight on the context, keep its per-blob status, learn from its flags (batch.cpp)
 int ctx_stream2(crthip_ctx *ctx, hipStream_t *out);   // the context's second stream, made on first use (batch.cpp)
+void cast_state_release(crthip_ctx *ctx);               // a context's cast blocks go with it (bvh_cast.cpp)
 
 // ------------------------------------------------------------------------------------------------
 // planner: what turns the walked layouts + bindings into job arrays inside one scratch block

@@ -134,6 +134,11 @@ __global__ void k_bvh_sort_scatter(const BvhJob *jobs, const uint32_t *block_job
 __global__ void k_bvh_tree(const BvhJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 __global__ void k_bvh_refit(const BvhJob *jobs, const uint32_t *block_job, uint32_t nblocks);
 
+// k_bvh_cast.hip (crthip_bvh_cast; bvh_cast.h has the tests and the walk): a thread a segment, 64 segments a workgroup, through a block_start
+// table over the call's sets (njobs entries are read); 16 640 bytes of static LDS hold the 64 traversal stacks
+struct CastJob;
+__global__ void k_bvh_cast(const CastJob *jobs, const uint32_t *block_start, uint32_t njobs);
+
 // k_mesh.hip
 __global__ void k_topology(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);
 __global__ void k_topology_lds(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);

@@ -68,7 +68,10 @@ extern "C" {
                                      crthip_batch_bind_compact, crthip_compact_model_gather, crthip_compact_model (five structs and two
                                      new calls, nothing else: the number stays 6); CRTHIP_BVH_LEAF, CRTHIP_NO_NODE, crthip_bvh_node,
                                      crthip_bvh_counts, crthip_bvh_binding, crthip_batch_bind_bvh, crthip_bvh_model (three structs and two
-                                     new calls, nothing else: the number stays 6) */
+                                     new calls, nothing else: the number stays 6); CRTHIP_CAST_ANY, CRTHIP_CAST_FRONT, CRTHIP_NO_FACE,
+                                     CRTHIP_CAST_*, crthip_segment, crthip_cast_hit, crthip_bvh_cast_set, crthip_bvh_cast,
+                                     crthip_bvh_cast_model, crthip_bvh_cast_model_stats (three structs and three new calls, nothing else:
+                                     the number stays 6) */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -747,6 +750,62 @@ typedef struct crthip_bvh_binding {
  * CRTHIP_E_NORMAL_NEEDS_POSITION: by the weld's rule.  crthip_last_error() names the blob.  Blobs without the binding plan, upload, zero
  * and launch nothing new.  Not part of crthip_pool_* / crthip_output_layout, crthip_decode_host, the crt::Decoder facade or the veneers. */
 int crthip_batch_bind_bvh(crthip_batch *b, uint32_t i, const crthip_bvh_binding *v);
+
+/* SEGMENT CASTS against a blob's BVH: the nearest face a segment meets, or whether it meets any (kernel bvh_cast; csrc/bvh_cast.h has the
+ * source the kernel and the hook share).  A stand-alone call on plain device pointers - the nodes crthip_batch_bind_bvh wrote, the blob's
+ * position bound with CRTHIP_BIND_QUANTIZED (the one form in which the integers survive the decode), its index and the position's base -,
+ * no part of a batch's plan: a batch that never casts launches what it launched before.  Everything is an integer in grid units, so every
+ * byte below is defined exactly, for any traversal order; a segment through a shared edge or a vertex of a closed surface cannot slip through.
+ * Frame: p[v][c] = base[c] + position[v][c] (the uint16 of the buffer).  With `transform`, base is transform->base, read on the DEVICE, and
+ *   transform->written == 0 (a span beyond 65 535: there is no such buffer) gives every segment of the set CRTHIP_CAST_RANGE.
+ * Range: a segment P -> Q is in range iff -2^19 <= E[c] - base[c] < 2^19 for both endpoints E and every c (in 64 bits).  Otherwise its record
+ *   is {CRTHIP_CAST_RANGE, CRTHIP_NO_FACE, 0, 0, 0, 0} and nothing is tested.  In range every difference below is under 2^20 in magnitude.
+ * Face test, a, b, c the corners of face f: d = Q - P, A = a - P, B = b - P, C = c - P, n = (B - A) x (C - A) (|n[c]| < 2^33), D = d . n and
+ *   K = A . n (below 2^55 in magnitude), U = d . (B x C), V = d . (C x A), W = d . (A x B) (below 2^63 in magnitude; U + V + W = D).
+ *   The segment HITS f iff D != 0; and U, V, W are all >= 0 or all <= 0; and K is 0 or has D's sign, and |K| <= |D| (t = K/D is in [0, 1]);
+ *   and, under CRTHIP_CAST_FRONT, D < 0.  Edges, vertices and both endpoints are inclusive.  A face with a corner >= nvert is absent and
+ *   never hit (the corner is compared, never an address); a face with two equal or three collinear corners has n = 0 and is never hit; a
+ *   segment in a face's plane has D = 0 and misses it.
+ * Nearest: among the hit faces the one with the least (t, f), where t1 < t2 iff |K1|*|D2| < |K2|*|D1| as 128-bit products.  Its record is
+ *   {CRTHIP_CAST_HIT, f, side = (D < 0), 0, num = |K|, den = |D|} (not reduced); no hit: {CRTHIP_CAST_MISS, CRTHIP_NO_FACE, 0, 0, 0, 0}.
+ * CRTHIP_CAST_ANY: {CRTHIP_CAST_HIT, CRTHIP_NO_FACE, 0, 0, 0, 0} if some face is hit, else the miss record (which face is found first
+ *   changes with the schedule, so none is reported).
+ * Tree: only a way to skip faces.  With the nodes crthip_batch_bind_bvh wrote for this index and these positions no answer depends on them.
+ *   ANY bytes in `nodes` are survived: a child id >= 2*nface - 1, a leaf whose face id is >= nface, a traversal stack deeper than 65 entries
+ *   or more than 2*nface - 1 nodes taken from it give {CRTHIP_CAST_TREE, CRTHIP_NO_FACE, 0, 0, 0, 0}; no access leaves the arrays and no
+ *   loop is unbounded.
+ * Chosen, not tuned: one thread a segment, one wave of 64 a workgroup, the stack in LDS.
+ * Left out: float or world-space rays; infinite rays (clip to the range box); barycentric outputs; positions in any form but quantised
+ *   uint16; instancing and a top-level structure over blobs; box, frustum and closest-point queries; any-hit face ids; the pool, the facade
+ *   and the veneers. */
+#define CRTHIP_CAST_ANY    1u   /* any hit instead of the nearest */
+#define CRTHIP_CAST_FRONT  2u   /* only faces the segment meets against their normal (D < 0) */
+#define CRTHIP_NO_FACE 0xFFFFFFFFu
+enum { CRTHIP_CAST_MISS = 0, CRTHIP_CAST_HIT = 1, CRTHIP_CAST_RANGE = 2, CRTHIP_CAST_TREE = 3 };
+typedef struct crthip_segment  { int32_t p[3]; uint32_t user0; int32_t q[3]; uint32_t user1; } crthip_segment;   /* 32 bytes; the user words never reach a result */
+typedef struct crthip_cast_hit { uint32_t status, face, side, reserved; uint64_t num, den; } crthip_cast_hit;    /* 32 bytes */
+typedef struct crthip_bvh_cast_set {
+	const crthip_bvh_node *nodes;          /* DEVICE, 16-byte aligned, 2*nface - 1 records as crthip_batch_bind_bvh wrote them */
+	const void *position;                  /* DEVICE, uint16 x 3 a vertex (CRTHIP_BIND_QUANTIZED), 2-byte aligned */
+	const void *index;                     /* DEVICE, nface*3 entries of index_format, aligned to an entry */
+	const crthip_quant_transform *transform; /* DEVICE record of that position (crthip_batch_bind_quant_transforms), 16-byte aligned; or NULL: base[] */
+	const crthip_segment *segments;        /* DEVICE, 16-byte aligned, nseg records */
+	crthip_cast_hit *hits;                 /* DEVICE, 16-byte aligned, nseg records; nothing else is written */
+	int32_t base[3]; uint32_t pos_stride;  /* 0 or 6: packed; else even and >= 6 */
+	uint32_t nvert, nface, index_format, nseg;
+	uint32_t flags, reserved;
+} crthip_bvh_cast_set;
+/* Casts every set - many blobs, any number of segments each - in ONE launch, asynchronously, on the context's main stream: behind everything
+ * the context enqueued before (a crthip_batch_decode's last kernels run on that stream, so a decode followed by a cast with a `transform`
+ * needs no host wait in between); crthip_ctx_sync waits for it.  `sets` is read before the call returns.  nsets == 0 and sets with
+ * nseg == 0 write nothing.  Every error comes from this call, before anything is enqueued, in this order:
+ * CRTHIP_E_ARGUMENT: ctx NULL; sets NULL with nsets > 0; then per set, in set order: with nseg > 0, nodes, position, index, segments or hits
+ * NULL or misaligned, or transform misaligned; nface == 0 or beyond 2^31 - 1; index_format neither CRTHIP_FMT_UINT32 nor CRTHIP_FMT_UINT16;
+ * pos_stride neither 0 nor even and >= 6; flags beyond the two; reserved != 0; then, with nseg > 0, an array that is not device memory of
+ * the context's device with its whole extent inside one allocation (nodes (2*nface - 1)*32 bytes, position up to the last vertex's sixth
+ * byte, index, the 48 bytes of transform, segments and hits nseg*32 bytes each).  CRTHIP_E_LIMIT: more than 2^31 - 1 workgroups of 64
+ * segments in all.  crthip_last_error() names the set and the field. */
+int crthip_bvh_cast(crthip_ctx *ctx, uint32_t nsets, const crthip_bvh_cast_set *sets);
 
 /* The record of attribute `attr` of blob i, bound with CRTHIP_BIND_QUANTIZED.  Valid after crthip_batch_sync of a decode: the kernels write
  * the records into the batch's pinned status block, beside the status words.  CRTHIP_E_ARGUMENT if that attribute was not bound
@@ -1482,6 +1541,14 @@ int crthip_compact_model(const void *src, uint32_t src_u16, uint32_t nface, uint
  * with nvert > 0, a NULL index, nodes NULL or not 16-byte aligned. */
 int crthip_bvh_model(const int32_t *position, uint32_t nvert, const void *index, uint32_t index_u16, uint32_t nface, crthip_bvh_node *nodes,
                      uint32_t *parent, uint32_t *order, crthip_bvh_counts *counts, int which, uint32_t seed);
+
+/* (test hook, no device needed)  crthip_bvh_cast of ONE set on the host: csrc/bvh_cast.h, the kernel's source, one workgroup of 64 segments
+ * after another, each with a stack block of the kernel's size.  Every pointer of the set is HOST memory, `transform` included; hits: nseg
+ * records.  The set's own checks are crthip_bvh_cast's, in its order (set or hits NULL: CRTHIP_E_ARGUMENT); where the memory is cannot be
+ * checked.  Any bytes in `nodes` end as the contract says.  stats (or NULL): two words, the nodes taken from the stacks and the faces tested,
+ * summed over the segments. */
+int crthip_bvh_cast_model(const crthip_bvh_cast_set *set, crthip_cast_hit *hits);
+int crthip_bvh_cast_model_stats(const crthip_bvh_cast_set *set, crthip_cast_hit *hits, uint64_t *stats);
 
 #ifdef __cplusplus
 }
