@@ -143,6 +143,21 @@ class CastSet(C.Structure):
                 ("index_format", C.c_uint32), ("nseg", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+QUERY_COUNT, QUERY_BOXES, QUERY_INSIDE = 1, 2, 4     # CRTHIP_QUERY_COUNT, CRTHIP_QUERY_BOXES, CRTHIP_QUERY_INSIDE
+QUERY_OK, QUERY_CLIPPED, QUERY_RANGE, QUERY_TREE = 0, 1, 2, 3   # crthip_query_result.status
+BOX_DTYPE = np.dtype([("min", np.int32, 3), ("user0", np.uint32), ("max", np.int32, 3), ("user1", np.uint32)])   # crthip_box, 32 bytes
+QUERY_RESULT_DTYPE = np.dtype([("status", np.uint32), ("count", np.uint32), ("written", np.uint32), ("reserved", np.uint32)])   # crthip_query_result, 16 bytes
+
+
+class QuerySet(C.Structure):
+    """crthip_bvh_query_set: the device nodes, quantised position, index and optional transform record as in CastSet; the boxes, the results
+    and the face lists; the base, the position's stride, the counts, the index format, a box's list capacity, the flags"""
+    _fields_ = [("nodes", C.c_void_p), ("position", C.c_void_p), ("index", C.c_void_p), ("transform", C.c_void_p), ("boxes", C.c_void_p),
+                ("results", C.c_void_p), ("faces", C.c_void_p), ("base", C.c_int32 * 3), ("pos_stride", C.c_uint32), ("nvert", C.c_uint32),
+                ("nface", C.c_uint32), ("index_format", C.c_uint32), ("nbox", C.c_uint32), ("face_capacity", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
 LOD_MAX_LEVELS = 4                                   # CRTHIP_LOD_MAX_LEVELS
 
 
@@ -457,6 +472,9 @@ def lib():
         L.crthip_bvh_cast.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(CastSet)]
         L.crthip_bvh_cast_model.argtypes = [C.POINTER(CastSet), C.c_void_p]
         L.crthip_bvh_cast_model_stats.argtypes = [C.POINTER(CastSet), C.c_void_p, C.c_void_p]
+        L.crthip_bvh_query.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(QuerySet)]
+        L.crthip_bvh_query_model.argtypes = [C.POINTER(QuerySet), C.c_void_p, C.c_void_p]
+        L.crthip_bvh_query_model_stats.argtypes = [C.POINTER(QuerySet), C.c_void_p, C.c_void_p, C.c_void_p]
         L.crthip_compact_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                            C.c_uint32, C.POINTER(CompactCounts), C.POINTER(CompactModelGather), C.c_uint32, C.c_int, C.c_uint32]
         L.crthip_cloud_lod_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1308,6 +1326,73 @@ def bvh_cast_model(nodes: np.ndarray, position: np.ndarray, index: np.ndarray, s
     return (out, (int(stats[0]), int(stats[1]))) if with_stats else out
 
 
+def make_boxes(lo, hi) -> np.ndarray:
+    """(n, 3) integer least and greatest corners in grid units -> n crthip_box records (BOX_DTYPE), the user words 0"""
+    lo = np.asarray(lo, dtype=np.int64).reshape(-1, 3)
+    hi = np.asarray(hi, dtype=np.int64).reshape(-1, 3)
+    b = np.zeros(len(lo), BOX_DTYPE)
+    b["min"], b["max"] = lo, hi
+    return b
+
+
+def world_boxes(lo, hi, transform) -> np.ndarray:
+    """World-space boxes -> crthip_box records in the grid of `transform` (a QuantTransform, or its step q as a float), rounded OUTWARD: a
+    grid coordinate g stands for the world coordinate float32(g) * q, so `min` is the floor and `max` the ceiling of float64(w) / float64(q),
+    clipped to int32 - the grid box holds the world box, and a face the world box touches is not lost to rounding.  Whether a box is in a
+    set's range is the query's to say (CRTHIP_QUERY_RANGE)."""
+    step = float(transform.q if isinstance(transform, QuantTransform) else transform)
+    g = lambda w, r: np.clip(r(np.asarray(w, dtype=np.float64) / step), -2 ** 31, 2 ** 31 - 1).astype(np.int64)   # noqa: E731
+    return make_boxes(g(lo, np.floor), g(hi, np.ceil))
+
+
+def bvh_query_model(nodes: np.ndarray, position: np.ndarray, index: np.ndarray, boxes: np.ndarray, base=(0, 0, 0), flags: int = 0, capacity: int = 0,
+                    transform=None, nvert: Optional[int] = None, fill: int = 0xCD, with_stats: bool = False, raw_set=None, null_faces: bool = False):
+    """crthip_bvh_query_model: crthip_bvh_query of one set on the host, csrc/bvh_query.h as the kernel runs it.  nodes, position, index,
+    transform, base, nvert: as in bvh_cast_model; boxes: BOX_DTYPE; capacity: face_capacity.  The result array is made here at exactly nbox
+    records and the list array at exactly nbox*capacity words, both filled with `fill` first and each between two guard blocks of `fill`
+    that must come back unchanged; null_faces: faces is NULL (legal under QUERY_COUNT or with capacity 0).  raw_set: a function that may
+    change the QuerySet before the call (the argument tests).  Returns (results QUERY_RESULT_DTYPE (nbox,), faces uint32 (nbox, capacity) -
+    the words beyond a box's `written` still hold `fill`), with with_stats also (nodes taken, faces tested)."""
+    pos = np.ascontiguousarray(position)
+    if pos.dtype == np.uint16:
+        pos = pos.reshape(-1, 3); stride = 6
+    else:
+        pos = pos.view(np.uint8).reshape(len(pos), -1); stride = pos.shape[1]
+    idx = np.ascontiguousarray(index)
+    if idx.dtype != np.uint16:
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    idx = idx.reshape(-1, 3)
+    bx = np.ascontiguousarray(boxes, dtype=BOX_DTYPE)
+    nbox = len(bx)
+    GUARD = 64
+
+    def aligned(a, nbytes, guard=0):                  # a 16-byte aligned copy of a's bytes, `guard` bytes of fill on either side
+        raw = np.full(nbytes + 16 + 2 * guard, fill, np.uint8)
+        o = (-(raw.ctypes.data + guard)) % 16 + guard
+        v = raw[o:o + nbytes]
+        v[:] = np.frombuffer(a.tobytes(), np.uint8) if nbytes else 0
+        return v, raw, o
+    nd, sg = aligned(np.ascontiguousarray(nodes), len(nodes) * 32)[0], aligned(bx, nbox * 32)[0]
+    res, res_raw, res_o = aligned(np.full(nbox * 16, fill, np.uint8), nbox * 16, GUARD)
+    lst, lst_raw, lst_o = aligned(np.full(nbox * capacity * 4, fill, np.uint8), nbox * capacity * 4, GUARD)
+    tr = aligned(np.frombuffer(bytes(transform), np.uint8), 48)[0] if transform is not None else None
+    qs = QuerySet(nd.ctypes.data if len(nd) else None, pos.ctypes.data if pos.size else None, idx.ctypes.data if idx.size else None,
+                  tr.ctypes.data if tr is not None else None, sg.ctypes.data if nbox else None, None, None, (C.c_int32 * 3)(*[int(b) for b in base]),
+                  0 if stride == 6 else stride, len(pos) if nvert is None else nvert, len(idx), FMT_UINT16 if idx.dtype == np.uint16 else FMT_UINT32, nbox,
+                  capacity, flags, (C.c_uint32 * 2)(0, 0))
+    if raw_set is not None:
+        raw_set(qs)
+    stats = np.zeros(2, np.uint64)
+    fp = None if null_faces or not (nbox and capacity) else lst.ctypes.data
+    _check(lib().crthip_bvh_query_model_stats(C.byref(qs), res.ctypes.data if nbox else None, fp, _np_ptr(stats)))
+    for raw, o, n in ((res_raw, res_o, nbox * 16), (lst_raw, lst_o, nbox * capacity * 4)):
+        if not ((raw[:o] == fill).all() and (raw[o + n:] == fill).all()):
+            raise AssertionError("crthip_bvh_query_model wrote outside its arrays")
+    out = res.view(QUERY_RESULT_DTYPE).copy()
+    faces = lst.view(np.uint32).reshape(nbox, capacity).copy()
+    return (out, faces, (int(stats[0]), int(stats[1]))) if with_stats else (out, faces)
+
+
 def lod_model(position: np.ndarray, index: np.ndarray, shift: int, which: int = 0, seed: int = 0, fill: int = 0xCD):
     """crthip_lod_model: one level of crthip_batch_bind_lod on the host in the kernels' partition (which 0: lod_blob; 1: lod_insert / _lookup /
     _faces / _keep / _offsets / _scatter; workgroups and threads, and so every atomic's order, shuffled by seed).  position (nvert, 3) int32;
@@ -1512,6 +1597,12 @@ class Context:
         enqueued (a decode included); sync() waits for it.  The caller keeps every array of the sets alive until then."""
         arr = (CastSet * max(len(sets), 1))(*sets)
         _check(lib().crthip_bvh_cast(self.handle, len(sets), arr))
+
+    def bvh_query(self, sets: Sequence[QuerySet]):
+        """crthip_bvh_query: every set's boxes against its blob's BVH in one launch, asynchronously, behind everything this context has
+        enqueued (a decode included); sync() waits for it.  The caller keeps every array of the sets alive until then."""
+        arr = (QuerySet * max(len(sets), 1))(*sets)
+        _check(lib().crthip_bvh_query(self.handle, len(sets), arr))
 
     def sync(self):
         _check(lib().crthip_ctx_sync(self.handle))
@@ -2234,6 +2325,48 @@ class Batch:
         self.ctx.bvh_cast([self.cast_set(i, dseg.data_ptr(), dhit.data_ptr(), n, flags)])
         self.ctx.sync()
         return dhit.cpu().numpy().view(CAST_HIT_DTYPE).copy()
+
+    def query_set(self, i: int, boxes, results, faces, nbox: int, capacity: int = 0, flags: int = 0) -> QuerySet:
+        """The crthip_bvh_query_set of blob i, bound by allocate_outputs(bvh=True, quantized=("position",)): its kept node, position and
+        index tensors as in cast_set, `boxes` and `results` (device pointers, 16-byte aligned, nbox records) and `faces` (a device pointer,
+        nbox*capacity words, or None where the call allows it).  The transform is the device record where bind_quant_transforms gave one -
+        then nothing here waits for the decode -, else quant_transform(i, "position")'s base (after sync())."""
+        cs = self.cast_set(i, None, None, 0)
+        qs = QuerySet()
+        qs.nodes, qs.position, qs.index, qs.transform = cs.nodes, cs.position, cs.index, cs.transform
+        qs.base[0], qs.base[1], qs.base[2] = cs.base[0], cs.base[1], cs.base[2]
+        qs.nvert, qs.nface, qs.index_format = cs.nvert, cs.nface, cs.index_format
+        qs.boxes, qs.results, qs.faces, qs.nbox, qs.face_capacity, qs.flags = boxes, results, faces, nbox, capacity, flags
+        return qs
+
+    def query(self, i: int, boxes: np.ndarray, flags: int = 0, capacity: Optional[int] = None):
+        """Queries `boxes` (BOX_DTYPE, grid units: make_boxes / world_boxes) against blob i's BVH: uploads them, crthip_bvh_query, syncs the
+        context, returns (results QUERY_RESULT_DTYPE, a list of uint32 arrays: box k's first `written` matching faces in BVH rank order).
+        capacity None: a QUERY_COUNT pass first, then one pass at the largest count, so that nothing is clipped; under QUERY_COUNT every
+        list is empty.  For blobs bound by allocate_outputs(bvh=True, quantized=("position",))."""
+        import torch
+        bx = np.ascontiguousarray(boxes, dtype=BOX_DTYPE)
+        n = len(bx)
+        if not n:
+            return np.zeros(0, QUERY_RESULT_DTYPE), []
+        dev = torch.device("cuda", self.ctx.device)
+        dbox = torch.from_numpy(bx.view(np.uint8).reshape(-1).copy()).to(dev)
+        dres = torch.empty(n * 16, dtype=torch.uint8, device=dev)
+        _torch_ready(dev)                            # (the upload runs on torch's stream; the query on the context's own)
+
+        def run(cap, fl):
+            dlist = torch.empty(max(n * cap, 1), dtype=torch.int32, device=dev) if cap and not fl & QUERY_COUNT else None
+            _torch_ready(dev)
+            self.ctx.bvh_query([self.query_set(i, dbox.data_ptr(), dres.data_ptr(), dlist.data_ptr() if dlist is not None else None, n, cap, fl)])
+            self.ctx.sync()
+            res = dres.cpu().numpy().view(QUERY_RESULT_DTYPE).copy()
+            words = dlist.cpu().numpy().view(np.uint32)[:n * cap].reshape(n, cap) if dlist is not None else np.zeros((n, 0), np.uint32)
+            return res, [words[k, :int(res["written"][k])].copy() for k in range(n)]
+        if flags & QUERY_COUNT:
+            return run(0, flags)
+        if capacity is None:
+            capacity = int(run(0, flags | QUERY_COUNT)[0]["count"].max())
+        return run(int(capacity), flags)
 
     def host_outputs(self, i: int) -> Dict[str, np.ndarray]:
         """Copy blob i's outputs to the host as numpy arrays with the reference's dtypes."""

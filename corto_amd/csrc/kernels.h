@@ -139,6 +139,11 @@ __global__ void k_bvh_refit(const BvhJob *jobs, const uint32_t *block_job, uint3
 struct CastJob;
 __global__ void k_bvh_cast(const CastJob *jobs, const uint32_t *block_start, uint32_t njobs);
 
+// k_bvh_query.hip (crthip_bvh_query; bvh_query.h has the face rules and the walk): a thread a box, 64 boxes a workgroup, through a block_start
+// table over the call's sets (njobs entries are read); the cast's 16 640 bytes of static LDS hold the 64 traversal stacks
+struct QueryJob;
+__global__ void k_bvh_query(const QueryJob *jobs, const uint32_t *block_start, uint32_t njobs);
+
 // k_mesh.hip
 __global__ void k_topology(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);
 __global__ void k_topology_lds(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);

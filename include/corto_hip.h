@@ -71,7 +71,9 @@ extern "C" {
                                      new calls, nothing else: the number stays 6); CRTHIP_CAST_ANY, CRTHIP_CAST_FRONT, CRTHIP_NO_FACE,
                                      CRTHIP_CAST_*, crthip_segment, crthip_cast_hit, crthip_bvh_cast_set, crthip_bvh_cast,
                                      crthip_bvh_cast_model, crthip_bvh_cast_model_stats (three structs and three new calls, nothing else:
-                                     the number stays 6) */
+                                     the number stays 6); CRTHIP_QUERY_COUNT, CRTHIP_QUERY_BOXES, CRTHIP_QUERY_INSIDE, CRTHIP_QUERY_*,
+                                     crthip_box, crthip_query_result, crthip_bvh_query_set, crthip_bvh_query, crthip_bvh_query_model,
+                                     crthip_bvh_query_model_stats (three structs and three new calls, nothing else: the number stays 6) */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -806,6 +808,71 @@ typedef struct crthip_bvh_cast_set {
  * byte, index, the 48 bytes of transform, segments and hits nseg*32 bytes each).  CRTHIP_E_LIMIT: more than 2^31 - 1 workgroups of 64
  * segments in all.  crthip_last_error() names the set and the field. */
 int crthip_bvh_cast(crthip_ctx *ctx, uint32_t nsets, const crthip_bvh_cast_set *sets);
+
+/* BOX QUERIES against a blob's BVH: the faces that share a point with an axis-aligned box - rubber-band selection, a collision broad phase
+ * of many small boxes, brick occupancy, "which faces lie in this tile" (kernel bvh_query; csrc/bvh_query.h has the source the kernel and the
+ * hook share).  A stand-alone call like crthip_bvh_cast, on the same device pointers and in the same frame, no part of a batch's plan: a batch
+ * that never queries launches what it launched before.  Everything is an integer in grid units and stays in signed 64 bits, so every byte
+ * below is defined exactly.
+ * Frame: crthip_bvh_cast's.  With `transform`, base is transform->base, read on the DEVICE, and transform->written == 0 gives every box of
+ *   the set CRTHIP_QUERY_RANGE.
+ * Range: a box is in range iff -2^19 <= E[c] - base[c] < 2^19 for both corners E = min, max and every c (in 64 bits).  Otherwise its record is
+ *   {CRTHIP_QUERY_RANGE, 0, 0, 0} and nothing is tested.
+ * Empty: an in-range box with min[c] > max[c] on some axis holds no point.  Its record is {CRTHIP_QUERY_OK, 0, 0, 0} and nothing is walked.
+ * Match (default): face f matches iff it is present - every corner < nvert; the corner is compared, never an address - and its CLOSED triangle,
+ *   the convex hull of its three corners, shares a point with the CLOSED box.  A face with equal or collinear corners is the segment or the
+ *   point that it is.  Decided by separating axes on DOUBLED coordinates: c2 = min + max and h = max - min of the box, the corners
+ *   V = 2p - c2 (|V[c]| < 2^21), the edges e0 = V1 - V0, e1 = V2 - V1, e2 = V0 - V2 (|e[c]| < 2^18).  NO match iff on a box axis c
+ *   min V[c] > h[c] or max V[c] < -h[c]; or |n . V0| > sum h[c]|n[c]| for n = e0 x e1 (|n[c]| < 2^36, both sides below 2^59); or on one of
+ *   the nine axes a = u_k x e_i (u_k the unit vector of axis k) the interval of the three a . V lies wholly beyond +-sum h[c]|a[c]| (below
+ *   2^41).  Touching counts: a box that meets a face in one vertex, along an edge or in its plane only matches it.
+ * CRTHIP_QUERY_BOXES: a present face matches iff its corner box overlaps the closed box on all three axes (the first of the tests above
+ *   alone: a conservative broad phase).  CRTHIP_QUERY_INSIDE: a present face matches iff all three corners lie in the closed box.
+ * Result of an in-range, non-empty box: count is the number of matching faces, whatever the capacity; written = min(count, face_capacity),
+ *   or 0 under CRTHIP_QUERY_COUNT; the box's slice of `faces` holds the first `written` matching faces in ascending BVH RANK - the j of
+ *   crthip_batch_bind_bvh's order[j], that is (key, f) ascending: the order in which a left-first walk of the tree meets them, a property of
+ *   the tree and not of the schedule; status is CRTHIP_QUERY_CLIPPED if written < count without CRTHIP_QUERY_COUNT, else CRTHIP_QUERY_OK.
+ *   The record is {status, count, written, 0}.  The words of a slice beyond `written` are not touched; nothing outside the `results` and
+ *   `faces` extents is written.
+ * Tree: only a way to skip faces - a node is taken iff its box (minus base, in 64 bits) overlaps the closed query box, the one use of the
+ *   nodes.  With the nodes crthip_batch_bind_bvh wrote for this index and these positions no answer depends on them.  ANY bytes in `nodes` are
+ *   survived under crthip_bvh_cast's four bounds: a child id >= 2*nface - 1, a leaf whose face id is >= nface, a traversal stack deeper than
+ *   65 entries or more than 2*nface - 1 nodes taken give {CRTHIP_QUERY_TREE, 0, 0, 0}, and the box's slice is then unspecified within its
+ *   face_capacity words; no access leaves the arrays and no loop is unbounded.
+ * Chosen, not tuned: one thread a box, one wave of 64 a workgroup, the cast's depth-major stack in LDS, plain 4-byte stores into the thread's
+ *   own slice.
+ * Left out: frustum or plane-set queries (few large queries: they want a wave or a workgroup a query); closest point (leaves 128 bits);
+ *   one-query-many-lanes traversal; a shortcut for nodes wholly inside the box; lists in face-id order; a per-face bitmask output; a top
+ *   level over blobs; the pool, the facade and the veneers. */
+#define CRTHIP_QUERY_COUNT  1u  /* counts only: no list is written, faces may be NULL, face_capacity is ignored */
+#define CRTHIP_QUERY_BOXES  2u  /* the face's own box stands for the face (conservative broad phase) */
+#define CRTHIP_QUERY_INSIDE 4u  /* only faces whose three corners all lie in the closed box */
+enum { CRTHIP_QUERY_OK = 0, CRTHIP_QUERY_CLIPPED = 1, CRTHIP_QUERY_RANGE = 2, CRTHIP_QUERY_TREE = 3 };
+typedef struct crthip_box { int32_t min[3]; uint32_t user0; int32_t max[3]; uint32_t user1; } crthip_box;   /* 32 bytes: the bytes of a crthip_bvh_node are a valid box; the user words never reach a result */
+typedef struct crthip_query_result { uint32_t status, count, written, reserved; } crthip_query_result;     /* 16 bytes */
+typedef struct crthip_bvh_query_set {
+	const crthip_bvh_node *nodes; const void *position; const void *index; const crthip_quant_transform *transform;   /* as in crthip_bvh_cast_set */
+	const crthip_box *boxes;               /* DEVICE, 16-byte aligned, nbox records */
+	crthip_query_result *results;          /* DEVICE, 16-byte aligned, nbox records */
+	uint32_t *faces;                       /* DEVICE, 4-byte aligned, nbox*face_capacity words: box i owns words [i*face_capacity, (i+1)*face_capacity) */
+	int32_t base[3]; uint32_t pos_stride;  /* 0 or 6: packed; else even and >= 6 */
+	uint32_t nvert, nface, index_format, nbox;
+	uint32_t face_capacity, flags, reserved[2];
+} crthip_bvh_query_set;
+/* Queries every set - many blobs, any number of boxes each - in ONE launch, asynchronously, on the context's main stream, with
+ * crthip_bvh_cast's stream order (a decode followed by a query with a `transform` needs no host wait in between); crthip_ctx_sync waits for
+ * it.  `sets` is read before the call returns.  nsets == 0 and sets with nbox == 0 write nothing.  Every error comes from this call, before
+ * anything is enqueued, in this order:
+ * CRTHIP_E_ARGUMENT: ctx NULL; sets NULL with nsets > 0; then per set, in set order: with nbox > 0, nodes, position or index NULL or
+ * misaligned, transform misaligned, boxes or results NULL or misaligned, or - without CRTHIP_QUERY_COUNT and with face_capacity > 0 -
+ * faces NULL or not 4-byte aligned (face_capacity == 0 without CRTHIP_QUERY_COUNT is legal: every match is clipped; under
+ * CRTHIP_QUERY_COUNT or with face_capacity == 0 faces is not looked at); nface == 0 or beyond
+ * 2^31 - 1; index_format neither CRTHIP_FMT_UINT32 nor CRTHIP_FMT_UINT16; pos_stride neither 0 nor even and >= 6; flags beyond the three,
+ * or CRTHIP_QUERY_BOXES together with CRTHIP_QUERY_INSIDE; reserved != 0; then, with nbox > 0, an array that is not device memory of the
+ * context's device with its whole extent inside one allocation (nodes, position, index and transform as in crthip_bvh_cast, boxes nbox*32
+ * bytes, results nbox*16 bytes, and without CRTHIP_QUERY_COUNT and with face_capacity > 0, faces nbox*face_capacity*4 bytes).
+ * CRTHIP_E_LIMIT: more than 2^31 - 1 workgroups of 64 boxes in all.  crthip_last_error() names the set and the field. */
+int crthip_bvh_query(crthip_ctx *ctx, uint32_t nsets, const crthip_bvh_query_set *sets);
 
 /* The record of attribute `attr` of blob i, bound with CRTHIP_BIND_QUANTIZED.  Valid after crthip_batch_sync of a decode: the kernels write
  * the records into the batch's pinned status block, beside the status words.  CRTHIP_E_ARGUMENT if that attribute was not bound
@@ -1549,6 +1616,14 @@ int crthip_bvh_model(const int32_t *position, uint32_t nvert, const void *index,
  * summed over the segments. */
 int crthip_bvh_cast_model(const crthip_bvh_cast_set *set, crthip_cast_hit *hits);
 int crthip_bvh_cast_model_stats(const crthip_bvh_cast_set *set, crthip_cast_hit *hits, uint64_t *stats);
+
+/* (test hook, no device needed)  crthip_bvh_query of ONE set on the host: csrc/bvh_query.h, the kernel's source, one workgroup of 64 boxes
+ * after another, each with a stack block of the kernel's size.  Every pointer of the set is HOST memory, `transform` included; results: nbox
+ * records; faces: nbox*face_capacity words (or NULL where the call allows it).  The set's own checks are crthip_bvh_query's, in its order
+ * (set or results NULL: CRTHIP_E_ARGUMENT); where the memory is cannot be checked.  Any bytes in `nodes` end as the contract says.  stats (or
+ * NULL): two words, the nodes taken from the stacks and the faces tested, summed over the boxes. */
+int crthip_bvh_query_model(const crthip_bvh_query_set *set, crthip_query_result *results, uint32_t *faces);
+int crthip_bvh_query_model_stats(const crthip_bvh_query_set *set, crthip_query_result *results, uint32_t *faces, uint64_t *stats);
 
 #ifdef __cplusplus
 }
