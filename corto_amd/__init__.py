@@ -158,6 +158,20 @@ class QuerySet(C.Structure):
                 ("reserved", C.c_uint32 * 2)]
 
 
+CLOSEST_WITHIN, CLOSEST_ANY = 1, 2                   # CRTHIP_CLOSEST_WITHIN, CRTHIP_CLOSEST_ANY
+CLOSEST_MISS, CLOSEST_HIT, CLOSEST_RANGE, CLOSEST_TREE = 0, 1, 2, 3   # crthip_closest_hit.status
+CLOSEST_POINT_DTYPE = np.dtype([("p", np.int32, 3), ("radius", np.uint32)])   # crthip_point, 16 bytes
+CLOSEST_HIT_DTYPE = np.dtype([("status", np.uint32), ("face", np.uint32), ("feature", np.uint32), ("reserved", np.uint32), ("num_lo", np.uint64),
+                              ("num_hi", np.uint64), ("den_lo", np.uint64), ("den_hi", np.uint64)])   # crthip_closest_hit, 48 bytes
+
+
+class ClosestSet(C.Structure):
+    """crthip_bvh_closest_set: CastSet field for field, with the points and their hit records where the segments and theirs are"""
+    _fields_ = [("nodes", C.c_void_p), ("position", C.c_void_p), ("index", C.c_void_p), ("transform", C.c_void_p), ("points", C.c_void_p),
+                ("hits", C.c_void_p), ("base", C.c_int32 * 3), ("pos_stride", C.c_uint32), ("nvert", C.c_uint32), ("nface", C.c_uint32),
+                ("index_format", C.c_uint32), ("npoint", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 LOD_MAX_LEVELS = 4                                   # CRTHIP_LOD_MAX_LEVELS
 
 
@@ -475,6 +489,9 @@ def lib():
         L.crthip_bvh_query.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(QuerySet)]
         L.crthip_bvh_query_model.argtypes = [C.POINTER(QuerySet), C.c_void_p, C.c_void_p]
         L.crthip_bvh_query_model_stats.argtypes = [C.POINTER(QuerySet), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.crthip_bvh_closest.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(ClosestSet)]
+        L.crthip_bvh_closest_model.argtypes = [C.POINTER(ClosestSet), C.c_void_p]
+        L.crthip_bvh_closest_model_stats.argtypes = [C.POINTER(ClosestSet), C.c_void_p, C.c_void_p, C.c_uint32]
         L.crthip_compact_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                            C.c_uint32, C.POINTER(CompactCounts), C.POINTER(CompactModelGather), C.c_uint32, C.c_int, C.c_uint32]
         L.crthip_cloud_lod_model.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1393,6 +1410,86 @@ def bvh_query_model(nodes: np.ndarray, position: np.ndarray, index: np.ndarray, 
     return (out, faces, (int(stats[0]), int(stats[1]))) if with_stats else (out, faces)
 
 
+def make_points(p, radius=0) -> np.ndarray:
+    """(n, 3) integer points in grid units and a radius (one, or one a point) -> n crthip_point records (CLOSEST_POINT_DTYPE)"""
+    p = np.asarray(p, dtype=np.int64).reshape(-1, 3)
+    s = np.zeros(len(p), CLOSEST_POINT_DTYPE)
+    s["p"], s["radius"] = p, radius
+    return s
+
+
+def world_points(p, transform, radius=None) -> np.ndarray:
+    """World-space points -> crthip_point records in the grid of `transform` (a QuantTransform, or its step q as a float), rounded as
+    world_segments rounds an endpoint: the nearest integer to float64(w) / float64(q), halves to the even one, clipped to int32.  radius
+    (world units, one or one a point; None: 0) is rounded UP to the next grid unit and clipped to uint32, so that under CLOSEST_WITHIN a face
+    the world radius reaches is not lost to rounding.  Whether a point is in a set's range is the query's to say (CRTHIP_CLOSEST_RANGE)."""
+    step = float(transform.q if isinstance(transform, QuantTransform) else transform)
+    g = np.clip(np.rint(np.asarray(p, dtype=np.float64) / step), -2 ** 31, 2 ** 31 - 1).astype(np.int64)
+    r = 0 if radius is None else np.clip(np.ceil(np.asarray(radius, dtype=np.float64) / step), 0, 2 ** 32 - 1).astype(np.uint32)
+    return make_points(g, r)
+
+
+def closest_fractions(hits: np.ndarray):
+    """The records' num and den as Python integers: a list of (num, den) a record (both 0 where the status is not CLOSEST_HIT or under
+    CLOSEST_ANY)"""
+    return [(int(h["num_lo"]) | int(h["num_hi"]) << 64, int(h["den_lo"]) | int(h["den_hi"]) << 64) for h in hits]
+
+
+def closest_distance(hits: np.ndarray) -> np.ndarray:
+    """sqrt(num/den) of every record in grid units as float64, from Python integers (an integer square root of num * 2^104 // den, then one
+    correctly rounded division: the error is below a float64's last bit); NaN where a record holds no distance.  A convenience: the records
+    are the contract."""
+    import math
+    out = np.full(len(hits), np.nan)
+    for k, (num, den) in enumerate(closest_fractions(hits)):
+        if den:
+            out[k] = math.isqrt((num << 104) // den) / float(1 << 52)
+    return out
+
+
+def bvh_closest_model(nodes: np.ndarray, position: np.ndarray, index: np.ndarray, points: np.ndarray, base=(0, 0, 0), flags: int = 0, transform=None,
+                      nvert: Optional[int] = None, fill: int = 0xCD, with_stats: bool = False, raw_set=None, order: int = 0):
+    """crthip_bvh_closest_model: crthip_bvh_closest of one set on the host, csrc/bvh_closest.h as the kernel runs it.  nodes, position, index,
+    transform, base, nvert: as in bvh_cast_model; points: CLOSEST_POINT_DTYPE.  The hit array is made here at exactly npoint records, filled
+    with `fill` first, between two guard blocks of `fill` that must come back unchanged.  order 0: the nearer child first (the kernel's); 1:
+    the nodes' own order.  raw_set: a function that may change the ClosestSet before the call (the argument tests).  Returns
+    CLOSEST_HIT_DTYPE (npoint,), with with_stats also (nodes taken, faces tested)."""
+    pos = np.ascontiguousarray(position)
+    if pos.dtype == np.uint16:
+        pos = pos.reshape(-1, 3); stride = 6
+    else:
+        pos = pos.view(np.uint8).reshape(len(pos), -1); stride = pos.shape[1]
+    idx = np.ascontiguousarray(index)
+    if idx.dtype != np.uint16:
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    idx = idx.reshape(-1, 3)
+    pt = np.ascontiguousarray(points, dtype=CLOSEST_POINT_DTYPE)
+    npoint = len(pt)
+    GUARD = 64
+
+    def aligned(a, nbytes, guard=0):                  # a 16-byte aligned copy of a's bytes, `guard` bytes of fill on either side
+        raw = np.full(nbytes + 16 + 2 * guard, fill, np.uint8)
+        o = (-(raw.ctypes.data + guard)) % 16 + guard
+        v = raw[o:o + nbytes]
+        v[:] = np.frombuffer(a.tobytes(), np.uint8) if nbytes else 0
+        return v, raw, o
+    nd, sg = aligned(np.ascontiguousarray(nodes), len(nodes) * 32)[0], aligned(pt, npoint * 16)[0]
+    hits, raw, o = aligned(np.full(npoint * 48, fill, np.uint8), npoint * 48, GUARD)
+    tr = aligned(np.frombuffer(bytes(transform), np.uint8), 48)[0] if transform is not None else None
+    cs = ClosestSet(nd.ctypes.data if len(nd) else None, pos.ctypes.data if pos.size else None, idx.ctypes.data if idx.size else None,
+                    tr.ctypes.data if tr is not None else None, sg.ctypes.data if npoint else None, None, (C.c_int32 * 3)(*[int(b) for b in base]),
+                    0 if stride == 6 else stride, len(pos) if nvert is None else nvert, len(idx), FMT_UINT16 if idx.dtype == np.uint16 else FMT_UINT32,
+                    npoint, flags, 0)
+    if raw_set is not None:
+        raw_set(cs)
+    stats = np.zeros(2, np.uint64)
+    _check(lib().crthip_bvh_closest_model_stats(C.byref(cs), hits.ctypes.data if npoint else None, _np_ptr(stats), order))
+    if not ((raw[:o] == fill).all() and (raw[o + npoint * 48:] == fill).all()):
+        raise AssertionError("crthip_bvh_closest_model wrote outside its array")
+    out = hits.view(CLOSEST_HIT_DTYPE).copy()
+    return (out, (int(stats[0]), int(stats[1]))) if with_stats else out
+
+
 def lod_model(position: np.ndarray, index: np.ndarray, shift: int, which: int = 0, seed: int = 0, fill: int = 0xCD):
     """crthip_lod_model: one level of crthip_batch_bind_lod on the host in the kernels' partition (which 0: lod_blob; 1: lod_insert / _lookup /
     _faces / _keep / _offsets / _scatter; workgroups and threads, and so every atomic's order, shuffled by seed).  position (nvert, 3) int32;
@@ -1603,6 +1700,12 @@ class Context:
         enqueued (a decode included); sync() waits for it.  The caller keeps every array of the sets alive until then."""
         arr = (QuerySet * max(len(sets), 1))(*sets)
         _check(lib().crthip_bvh_query(self.handle, len(sets), arr))
+
+    def bvh_closest(self, sets: Sequence[ClosestSet]):
+        """crthip_bvh_closest: every set's points against its blob's BVH in one launch, asynchronously, behind everything this context has
+        enqueued (a decode included); sync() waits for it"""
+        arr = (ClosestSet * max(len(sets), 1))(*sets)
+        _check(lib().crthip_bvh_closest(self.handle, len(sets), arr))
 
     def sync(self):
         _check(lib().crthip_ctx_sync(self.handle))
@@ -2367,6 +2470,38 @@ class Batch:
         if capacity is None:
             capacity = int(run(0, flags | QUERY_COUNT)[0]["count"].max())
         return run(int(capacity), flags)
+
+    def closest_set(self, i: int, points, hits, npoint: int, flags: int = 0) -> ClosestSet:
+        """The crthip_bvh_closest_set of blob i, bound by allocate_outputs(bvh=True, quantized=("position",)): its kept node, position and
+        index tensors as in cast_set, `points` (a device pointer, 16-byte aligned, npoint records of 16 bytes) and `hits` (the same, npoint
+        records of 48 bytes).  The transform is the device record where bind_quant_transforms gave one - then nothing here waits for the
+        decode -, else quant_transform(i, "position")'s base (after sync())."""
+        cs = self.cast_set(i, None, None, 0)
+        qs = ClosestSet()
+        qs.nodes, qs.position, qs.index, qs.transform = cs.nodes, cs.position, cs.index, cs.transform
+        qs.base[0], qs.base[1], qs.base[2] = cs.base[0], cs.base[1], cs.base[2]
+        qs.nvert, qs.nface, qs.index_format = cs.nvert, cs.nface, cs.index_format
+        qs.points, qs.hits, qs.npoint, qs.flags = points, hits, npoint, flags
+        return qs
+
+    def closest(self, i: int, points: np.ndarray, flags: int = 0):
+        """The face of blob i nearest to each of `points` (CLOSEST_POINT_DTYPE, grid units: make_points / world_points): uploads them,
+        crthip_bvh_closest, syncs the context, returns (hits CLOSEST_HIT_DTYPE, distance float64: sqrt(num/den) in grid units computed on the
+        host from Python integers, NaN where a record holds none).  The records are the contract, the float a convenience.  For blobs bound
+        by allocate_outputs(bvh=True, quantized=("position",))."""
+        import torch
+        pt = np.ascontiguousarray(points, dtype=CLOSEST_POINT_DTYPE)
+        n = len(pt)
+        if not n:
+            return np.zeros(0, CLOSEST_HIT_DTYPE), np.zeros(0, np.float64)
+        dev = torch.device("cuda", self.ctx.device)
+        dpt = torch.from_numpy(pt.view(np.uint8).reshape(-1).copy()).to(dev)
+        dhit = torch.empty(n * 48, dtype=torch.uint8, device=dev)
+        _torch_ready(dev)                            # (the upload runs on torch's stream; the query on the context's own)
+        self.ctx.bvh_closest([self.closest_set(i, dpt.data_ptr(), dhit.data_ptr(), n, flags)])
+        self.ctx.sync()
+        hits = dhit.cpu().numpy().view(CLOSEST_HIT_DTYPE).copy()
+        return hits, closest_distance(hits)
 
     def host_outputs(self, i: int) -> Dict[str, np.ndarray]:
         """Copy blob i's outputs to the host as numpy arrays with the reference's dtypes."""

@@ -19,7 +19,7 @@ LIB = os.path.join(LIBDIR, "libcorto_hip.so")
 VENEER = os.path.join(LIBDIR, "libcortocodec_hip.so")
 EMVENEER = os.path.join(LIBDIR, "libcorto_em_hip.so")    # upstream's wasm/JS C ABI (include/corto/emcorto.h) over the facade
 CLI = os.path.join(LIBDIR, "corto_hip")                   # the `corto` command line tool on this repo's encoder + GPU decoder (tools/corto_hip_cli.cpp)   # legacy Unity C ABI (include/corto/corto_codec.h) over the facade
-SOURCES = ["k_tunstall.hip", "k_stream.hip", "k_mesh.hip", "k_delta.hip", "k_normal.hip", "k_encode.hip", "k_encode_batch.hip", "k_encode_topo.hip", "k_encode_check.hip", "k_encode_splice.hip", "k_walk.hip", "k_quant_out.hip", "k_tangent.hip", "k_meshlet.hip", "k_meshlet_bounds.hip", "k_adjacency.hip", "k_weld.hip", "k_lod.hip", "k_cloud_lod.hip", "k_compact.hip", "k_bvh.hip", "k_bvh_cast.hip", "k_bvh_query.hip", "batch.cpp", "batch_bind.cpp", "host_probe.cpp", "plan_carve.cpp", "plan_jobs.cpp", "plan_group.cpp", "plan_launch.cpp", "crt_format.cpp", "decoder_facade.cpp", "encoder.cpp", "encode_gpu.cpp", "encode_batch.cpp", "enc_topology_host.cpp", "enc_input_host.cpp", "enc_splice_host.cpp", "quant_out_host.cpp", "tangent_host.cpp", "meshlet_host.cpp", "meshlet_bounds_host.cpp", "adjacency_host.cpp", "weld_host.cpp", "lod_host.cpp", "cloud_lod_host.cpp", "compact_host.cpp", "bvh_host.cpp", "bvh_cast_host.cpp", "bvh_cast.cpp", "bvh_query_host.cpp", "bvh_query.cpp", "pool.cpp"]
+SOURCES = ["k_tunstall.hip", "k_stream.hip", "k_mesh.hip", "k_delta.hip", "k_normal.hip", "k_encode.hip", "k_encode_batch.hip", "k_encode_topo.hip", "k_encode_check.hip", "k_encode_splice.hip", "k_walk.hip", "k_quant_out.hip", "k_tangent.hip", "k_meshlet.hip", "k_meshlet_bounds.hip", "k_adjacency.hip", "k_weld.hip", "k_lod.hip", "k_cloud_lod.hip", "k_compact.hip", "k_bvh.hip", "k_bvh_cast.hip", "k_bvh_query.hip", "k_bvh_closest.hip", "batch.cpp", "batch_bind.cpp", "host_probe.cpp", "plan_carve.cpp", "plan_jobs.cpp", "plan_group.cpp", "plan_launch.cpp", "crt_format.cpp", "decoder_facade.cpp", "encoder.cpp", "encode_gpu.cpp", "encode_batch.cpp", "enc_topology_host.cpp", "enc_input_host.cpp", "enc_splice_host.cpp", "quant_out_host.cpp", "tangent_host.cpp", "meshlet_host.cpp", "meshlet_bounds_host.cpp", "adjacency_host.cpp", "weld_host.cpp", "lod_host.cpp", "cloud_lod_host.cpp", "compact_host.cpp", "bvh_host.cpp", "bvh_cast_host.cpp", "bvh_cast.cpp", "bvh_query_host.cpp", "bvh_query.cpp", "bvh_closest_host.cpp", "bvh_closest.cpp", "pool.cpp"]
 # every header of csrc/ is a dependency of every object (a stale object behind a changed header decodes with yesterday's kernel)
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [
     os.path.join("..", "..", "include", "corto_hip.h"), os.path.join("..", "..", "include", "corto", "decoder.h")]

@@ -188,6 +188,7 @@ extern "C" void crthip_ctx_destroy(crthip_ctx *c) {
 	c->walk_dev.release(); c->walk_pin.release();
 	cast_state_release(c);
 	query_state_release(c);
+	closest_state_release(c);
 	if(c->ev_walk0) (void)hipEventDestroy(c->ev_walk0);
 	if(c->ev_walk1) (void)hipEventDestroy(c->ev_walk1);
 	if(c->stream2) (void)hipStreamSynchronize(c->stream2);

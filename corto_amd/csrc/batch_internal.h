@@ -245,6 +245,8 @@ struct crthip_ctx {
 	struct CastState *cast = nullptr;
 	// crthip_bvh_query: the same for the box queries, blocks of their own (bvh_query.cpp)
 	struct QueryState *query = nullptr;
+	// crthip_bvh_closest: and for the closest-face queries (bvh_closest.cpp)
+	struct ClosestState *closest = nullptr;
 	// crthip_decode_host: everything a one-blob decode with host buffers needs, kept from call to call (no hipMalloc / create in the
 	// steady state) and guarded by a mutex so that callers may share a context between threads
 	std::mutex host_mutex;
@@ -378,6 +380,7 @@ int harvest(crthip_ctx *ctx);     // wait for the batch in flight on the context
 int ctx_stream2(crthip_ctx *ctx, hipStream_t *out);   // the context's second stream, made on first use (batch.cpp)
 void cast_state_release(crthip_ctx *ctx);               // a context's cast blocks go with it (bvh_cast.cpp)
 void query_state_release(crthip_ctx *ctx);              // ... and its query blocks (bvh_query.cpp)
+void closest_state_release(crthip_ctx *ctx);            // ... and its closest-face blocks (bvh_closest.cpp)
 
 // ------------------------------------------------------------------------------------------------
 // planner: what turns the walked layouts + bindings into job arrays inside one scratch block

@@ -144,6 +144,11 @@ __global__ void k_bvh_cast(const CastJob *jobs, const uint32_t *block_start, uin
 struct QueryJob;
 __global__ void k_bvh_query(const QueryJob *jobs, const uint32_t *block_start, uint32_t njobs);
 
+// k_bvh_closest.hip (crthip_bvh_closest; bvh_closest.h has the wide arithmetic, the face rule and the walk): a thread a point, 64 points a
+// workgroup, through a block_start table over the call's sets (njobs entries are read); the cast's 16 640 bytes of static LDS hold the stacks
+struct ClosestJob;
+__global__ void k_bvh_closest(const ClosestJob *jobs, const uint32_t *block_start, uint32_t njobs);
+
 // k_mesh.hip
 __global__ void k_topology(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);
 __global__ void k_topology_lds(const TopoJob *jobs, const uint32_t *job_ids, uint32_t njobs);

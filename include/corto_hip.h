@@ -73,7 +73,10 @@ extern "C" {
                                      crthip_bvh_cast_model, crthip_bvh_cast_model_stats (three structs and three new calls, nothing else:
                                      the number stays 6); CRTHIP_QUERY_COUNT, CRTHIP_QUERY_BOXES, CRTHIP_QUERY_INSIDE, CRTHIP_QUERY_*,
                                      crthip_box, crthip_query_result, crthip_bvh_query_set, crthip_bvh_query, crthip_bvh_query_model,
-                                     crthip_bvh_query_model_stats (three structs and three new calls, nothing else: the number stays 6) */
+                                     crthip_bvh_query_model_stats (three structs and three new calls, nothing else: the number stays 6);
+                                     CRTHIP_CLOSEST_WITHIN, CRTHIP_CLOSEST_ANY, CRTHIP_CLOSEST_*, crthip_point, crthip_closest_hit,
+                                     crthip_bvh_closest_set, crthip_bvh_closest, crthip_bvh_closest_model, crthip_bvh_closest_model_stats
+                                     (three structs and three new calls, nothing else: the number stays 6) */
 
 /* VertexAttribute::Format, include/corto/vertex_attribute.h:32 */
 enum { CRTHIP_FMT_UINT32 = 0, CRTHIP_FMT_INT32 = 1, CRTHIP_FMT_UINT16 = 2, CRTHIP_FMT_INT16 = 3,
@@ -778,7 +781,8 @@ int crthip_batch_bind_bvh(crthip_batch *b, uint32_t i, const crthip_bvh_binding 
  *   loop is unbounded.
  * Chosen, not tuned: one thread a segment, one wave of 64 a workgroup, the stack in LDS.
  * Left out: float or world-space rays; infinite rays (clip to the range box); barycentric outputs; positions in any form but quantised
- *   uint16; instancing and a top-level structure over blobs; box, frustum and closest-point queries; any-hit face ids; the pool, the facade
+ *   uint16; instancing and a top-level structure over blobs; frustum queries (boxes: crthip_bvh_query, the closest face: crthip_bvh_closest); any-hit
+ *   face ids; the pool, the facade
  *   and the veneers. */
 #define CRTHIP_CAST_ANY    1u   /* any hit instead of the nearest */
 #define CRTHIP_CAST_FRONT  2u   /* only faces the segment meets against their normal (D < 0) */
@@ -841,7 +845,7 @@ int crthip_bvh_cast(crthip_ctx *ctx, uint32_t nsets, const crthip_bvh_cast_set *
  *   face_capacity words; no access leaves the arrays and no loop is unbounded.
  * Chosen, not tuned: one thread a box, one wave of 64 a workgroup, the cast's depth-major stack in LDS, plain 4-byte stores into the thread's
  *   own slice.
- * Left out: frustum or plane-set queries (few large queries: they want a wave or a workgroup a query); closest point (leaves 128 bits);
+ * Left out: frustum or plane-set queries (few large queries: they want a wave or a workgroup a query); the closest face (crthip_bvh_closest);
  *   one-query-many-lanes traversal; a shortcut for nodes wholly inside the box; lists in face-id order; a per-face bitmask output; a top
  *   level over blobs; the pool, the facade and the veneers. */
 #define CRTHIP_QUERY_COUNT  1u  /* counts only: no list is written, faces may be NULL, face_capacity is ignored */
@@ -873,6 +877,69 @@ typedef struct crthip_bvh_query_set {
  * bytes, results nbox*16 bytes, and without CRTHIP_QUERY_COUNT and with face_capacity > 0, faces nbox*face_capacity*4 bytes).
  * CRTHIP_E_LIMIT: more than 2^31 - 1 workgroups of 64 boxes in all.  crthip_last_error() names the set and the field. */
 int crthip_bvh_query(crthip_ctx *ctx, uint32_t nsets, const crthip_bvh_query_set *sets);
+
+/* CLOSEST-FACE QUERIES against a blob's BVH: for a point, the face nearest to it, the squared distance as an exact fraction and the part of
+ * the face - corner, edge, interior - that holds the closest point: snapping, proximity and clearance tests, collision response, distance
+ * fields, mesh-to-mesh error (kernel bvh_closest; csrc/bvh_closest.h has the source the kernel and the hook share).  A stand-alone call like
+ * crthip_bvh_cast, on the same device pointers and in the same frame, no part of a batch's plan: a batch that never asks launches what it
+ * launched before.  Everything is an integer in grid units, so every byte below is defined exactly, for any traversal order.
+ * Frame: crthip_bvh_cast's.  With `transform`, base is transform->base, read on the DEVICE, and transform->written == 0 gives every point of
+ *   the set CRTHIP_CLOSEST_RANGE.
+ * Range: a point is in range iff -2^19 <= p[c] - base[c] < 2^19 for every c (in 64 bits).  Otherwise its record is
+ *   {CRTHIP_CLOSEST_RANGE, CRTHIP_NO_FACE, 0, 0, 0, 0, 0, 0} and nothing is tested.
+ * Distance to one face: a face with a corner >= nvert is absent (the corner is compared, never an address).  For a present face with corners
+ *   a, b, c let A_0 = a - P, A_1 = b - P, A_2 = c - P (|A[c]| < 2^20) and e_0 = A_1 - A_0, e_1 = A_2 - A_1, e_2 = A_0 - A_2.  The squared
+ *   distance is that of the closest point of the CLOSED triangle (unique: a triangle is convex); a face with equal or collinear corners is
+ *   the segment or the point that it is.  It is reported as num/den, NOT reduced, by the feature that holds the closest point, and `feature`
+ *   is the least code whose closed feature holds it:
+ *     0, 1, 2  the corners a, b, c    {|A_k|^2, 1}                           always a candidate
+ *     3, 4, 5  the edges ab, bc, ca   {|A_i x e_i|^2, |e_i|^2}               iff |e_i|^2 > 0 and 0 <= -A_i . e_i <= |e_i|^2
+ *     6        the interior           {(n . A_0)^2, |n|^2}, n = e_0 x e_1    iff |n|^2 > 0 and (A_i x e_i) . n >= 0 for all three i
+ *   The candidates are met in the order 0 to 6 and one is taken only if it is STRICTLY less than the best so far; that gives the least code.
+ *   Widths: n[c] below 2^33, |n|^2 below 2^68, n . A below 2^55, an interior num below 2^110, a side test (A_i x e_i) . n below 2^72 (a signed
+ *   128-bit sum), an edge's num below 2^76 and its den below 2^34; num1*den2 against num2*den1 is below 2^178 and is compared in 256 bits.
+ * Answer: the minimum over the present faces under the total order (num/den, f): at equal distance the least face id.  Its record is
+ *   {CRTHIP_CLOSEST_HIT, f, feature, 0, num, den}, num and den as two 64-bit halves each.  No present face:
+ *   {CRTHIP_CLOSEST_MISS, CRTHIP_NO_FACE, 0, 0, 0, 0, 0, 0}.
+ * CRTHIP_CLOSEST_WITHIN: only faces with num/den <= r^2 count - inclusive -, r = min(point.radius, 2^21); every present face lies closer than
+ *   2^21 to any in-range point, so a larger radius is no limit.  No face within the radius: the MISS record.  Without the flag `radius` is a
+ *   user word and never reaches a result.
+ * CRTHIP_CLOSEST_ANY (only together with CRTHIP_CLOSEST_WITHIN): {CRTHIP_CLOSEST_HIT, CRTHIP_NO_FACE, 0, 0, 0, 0, 0, 0} if some face is
+ *   within the radius, else the MISS record (which face is found first changes with the schedule, so none is reported).
+ * Tree: only a way to skip faces - a node is skipped iff the squared distance from P to its box (minus base, in 64 bits, each axis clamped at
+ *   2^21) times den exceeds num of the best so far, strictly.  With the nodes crthip_batch_bind_bvh wrote for this index and these positions
+ *   no answer depends on them, nor on the order in which children are visited.  ANY bytes in `nodes` are survived under crthip_bvh_cast's
+ *   four bounds: a child id >= 2*nface - 1, a leaf whose face id is >= nface, a traversal stack deeper than 65 entries or more than
+ *   2*nface - 1 nodes taken give {CRTHIP_CLOSEST_TREE, CRTHIP_NO_FACE, 0, 0, 0, 0, 0, 0}; no access leaves the arrays and no loop is unbounded.
+ * Chosen, not tuned: one thread a point, one wave of 64 a workgroup, the cast's depth-major stack in LDS, every comparison of two distances
+ *   through 256-bit products.  The nearer child is visited first (profiles/bvh_closest.md has the counts behind that).
+ * Left out: the closest point's coordinates or barycentrics as outputs; k nearest faces and all-within-radius lists; signed distance or
+ *   inside-outside; float points; a query over welded or LOD sources; a top level over blobs; several lanes a point; the pool, the facade
+ *   and the veneers. */
+#define CRTHIP_CLOSEST_WITHIN 1u  /* only faces within point.radius (inclusive) */
+#define CRTHIP_CLOSEST_ANY    2u  /* with CRTHIP_CLOSEST_WITHIN: whether some face is within the radius, not which */
+enum { CRTHIP_CLOSEST_MISS = 0, CRTHIP_CLOSEST_HIT = 1, CRTHIP_CLOSEST_RANGE = 2, CRTHIP_CLOSEST_TREE = 3 };
+typedef struct crthip_point { int32_t p[3]; uint32_t radius; } crthip_point;   /* 16 bytes; without CRTHIP_CLOSEST_WITHIN radius is a user word */
+typedef struct crthip_closest_hit { uint32_t status, face, feature, reserved; uint64_t num_lo, num_hi, den_lo, den_hi; } crthip_closest_hit;   /* 48 bytes, 16-byte units */
+typedef struct crthip_bvh_closest_set {
+	const crthip_bvh_node *nodes; const void *position; const void *index; const crthip_quant_transform *transform;   /* as in crthip_bvh_cast_set */
+	const crthip_point *points;            /* DEVICE, 16-byte aligned, npoint records */
+	crthip_closest_hit *hits;              /* DEVICE, 16-byte aligned, npoint records; nothing else is written */
+	int32_t base[3]; uint32_t pos_stride;  /* 0 or 6: packed; else even and >= 6 */
+	uint32_t nvert, nface, index_format, npoint;
+	uint32_t flags, reserved;
+} crthip_bvh_closest_set;
+/* Answers every set - many blobs, any number of points each - in ONE launch, asynchronously, on the context's main stream, with
+ * crthip_bvh_cast's stream order (a decode followed by this call with a `transform` needs no host wait in between); crthip_ctx_sync waits for
+ * it.  `sets` is read before the call returns.  nsets == 0 and sets with npoint == 0 write nothing.  Every error comes from this call, before
+ * anything is enqueued, in crthip_bvh_cast's order:
+ * CRTHIP_E_ARGUMENT: ctx NULL; sets NULL with nsets > 0; then per set, in set order: with npoint > 0, nodes, position, index, points or hits
+ * NULL or misaligned, or transform misaligned; nface == 0 or beyond 2^31 - 1; index_format neither CRTHIP_FMT_UINT32 nor CRTHIP_FMT_UINT16;
+ * pos_stride neither 0 nor even and >= 6; flags beyond the two, or CRTHIP_CLOSEST_ANY without CRTHIP_CLOSEST_WITHIN; reserved != 0; then,
+ * with npoint > 0, an array that is not device memory of the context's device with its whole extent inside one allocation (nodes, position,
+ * index and transform as in crthip_bvh_cast, points npoint*16 bytes, hits npoint*48 bytes).  CRTHIP_E_LIMIT: more than 2^31 - 1 workgroups of
+ * 64 points in all.  crthip_last_error() names the set and the field. */
+int crthip_bvh_closest(crthip_ctx *ctx, uint32_t nsets, const crthip_bvh_closest_set *sets);
 
 /* The record of attribute `attr` of blob i, bound with CRTHIP_BIND_QUANTIZED.  Valid after crthip_batch_sync of a decode: the kernels write
  * the records into the batch's pinned status block, beside the status words.  CRTHIP_E_ARGUMENT if that attribute was not bound
@@ -1624,6 +1691,15 @@ int crthip_bvh_cast_model_stats(const crthip_bvh_cast_set *set, crthip_cast_hit 
  * NULL): two words, the nodes taken from the stacks and the faces tested, summed over the boxes. */
 int crthip_bvh_query_model(const crthip_bvh_query_set *set, crthip_query_result *results, uint32_t *faces);
 int crthip_bvh_query_model_stats(const crthip_bvh_query_set *set, crthip_query_result *results, uint32_t *faces, uint64_t *stats);
+
+/* (test hook, no device needed)  crthip_bvh_closest of ONE set on the host: csrc/bvh_closest.h, the kernel's source, one workgroup of 64
+ * points after another, each with a stack block of the kernel's size.  Every pointer of the set is HOST memory, `transform` included; hits:
+ * npoint records.  The set's own checks are crthip_bvh_closest's, in its order (set or hits NULL: CRTHIP_E_ARGUMENT); where the memory is
+ * cannot be checked.  Any bytes in `nodes` end as the contract says.  stats (or NULL): two words, the nodes taken from the stacks and the
+ * faces tested, summed over the points.  order: 0 visits the nearer child first, as the kernel does; 1 the children in the nodes' own order
+ * (the same bytes, other counts); anything else: CRTHIP_E_ARGUMENT. */
+int crthip_bvh_closest_model(const crthip_bvh_closest_set *set, crthip_closest_hit *hits);
+int crthip_bvh_closest_model_stats(const crthip_bvh_closest_set *set, crthip_closest_hit *hits, uint64_t *stats, uint32_t order);
 
 #ifdef __cplusplus
 }
